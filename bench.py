@@ -166,6 +166,37 @@ def pmc_traffic(kernel_family, expected_launches):
     return None, f'{name_}: kernel not in the profile'
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20      # all files of --dump-outputs together (float32)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write every tensor of ``arrays`` (name -> tensor) as ``directory/<name>.npy`` in float32, for comparing
+    two builds output for output.  The files share DUMP_BUDGET_BYTES; a tensor larger than its share is written as a sample
+    of its elements (flattened, ascending indices drawn with a fixed seed: the same sample in every run), else whole."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, name + '.npy'), t.float().cpu().numpy())
+
+
+def training_outputs(step):
+    """What one training step leaves its caller: the parameters of G, D and G_ema after the update and the gradients of G and D
+    from their last phase (zeros where a parameter took none), each module's tensors flattened and concatenated in parameter order."""
+    def cat(tensors):
+        return torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    out = {}
+    for name, module in (('G', step.G), ('D', step.D)):
+        params = list(module.parameters())
+        out[name + '_params'] = cat(params)
+        out[name + '_grads'] = cat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
+    out['G_ema_params'] = cat(step.G_ema.parameters())
+    return out
+
+
 
 
 def host_threads():
@@ -286,6 +317,8 @@ def run_infer(args, device):
     dt = time.perf_counter() - t0
     meter.enabled = conv.enabled = False
     upfirdn2d.launch_hook = conv2d_gradfix.launch_hook = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {f'synthesis_out{i}': t for i, t in enumerate(out) if isinstance(t, torch.Tensor)})
     assert all(torch.isfinite(t).all() for t in out[:2])
     graph_line = None
     if args.graph:
@@ -432,7 +465,12 @@ def main():
                     'and report fp64 sums of the parameters and of the last averaged gradients, so that two transports can be compared (tests/test_ddp_gpu.py)')
     ap.add_argument('--by-shape', action='store_true', help='also print a per-shape convolution table to stderr')
     ap.add_argument('--by-shape-top', type=int, default=40, help='rows of that table')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write what the last one computed as DIR/<name>.npy '
+                    '(float32, at most 60 MiB in all; a fixed sample of a larger tensor): train = parameters of G, D, G_ema and gradients of G, D '
+                    '(rank 0); infer = the synthesis outputs')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -526,6 +564,8 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, training_outputs(step))
 
     replica = None
     if args.replica_check:

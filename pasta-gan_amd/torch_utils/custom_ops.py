@@ -99,7 +99,9 @@ def _compile_and_link(hipcc, sources, lib_path, stamp, digest, verbose, extra_fl
     # units, csrc/conv_launch.h: a forced build takes about a minute on eight cores)
     objs = [os.path.join(_OBJDIR, os.path.basename(src)[:-4] + '.o') for src in sources]
     queue = sorted(zip(sources, objs), key=lambda so: -_unit_weight(so[0]))
-    jobs = max(1, min(len(queue), int(os.environ.get('PASTA_BUILD_JOBS', 0)) or os.cpu_count() or 1))
+    # PASTA_BUILD_JOBS, else MAX_JOBS (the usual cap for extension builds), else the CPUs this process may run on
+    jobs = int(os.environ.get('PASTA_BUILD_JOBS') or os.environ.get('MAX_JOBS') or 0) or len(os.sched_getaffinity(0))
+    jobs = max(1, min(len(queue), jobs))
     running, failed = [], None
     while (queue and failed is None) or running:
         while queue and failed is None and len(running) < jobs:

@@ -14,6 +14,9 @@ from conftest import ROOT, PKG
 
 
 def _worker(rank, world, port, out, ddp_mode):
+    # A CPU rank. torch.optim's step asks torch.cuda.is_available(), which on ROCm starts the HIP runtime and opens the GPU:
+    # on a GPU box every rank would hold the card, and eight of them exceed the processes one card admits.
+    torch.cuda.is_available = lambda: False
     for p in (PKG, ROOT, os.path.join(ROOT, 'tests')):
         if p not in sys.path:
             sys.path.insert(0, p)
