@@ -441,6 +441,24 @@ int pasta_affine_sample(const float* x, const float* theta, float* y, int64_t n,
 int pasta_affine_sample_adjoint(const float* dy, const float* theta, float* dx, int64_t n, int C, int IH, int IW, int OH, int OW,
                                 void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * grid_sample under a general sampling grid.  Replaces: grid_sample_gradfix.grid_sample(input, grid)
+ * torch_utils/ops/grid_sample_gradfix.py:22-83 -- F.grid_sample(bilinear, zeros, align_corners=False) forward (:44-51)
+ * and aten::grid_sampler_2d_backward for both gradients (:61-67).
+ * x: [n, C, IH, IW] dense, dtype PASTA_F32 / PASTA_F16 / PASTA_BF16 / PASTA_F64 (`dtype`); grid: [n, OH, OW, 2] dense,
+ * (x, y) in [-1, 1], dtype `grid_dtype` = `dtype` (or PASTA_F32 for a 16-bit image); y, dy: [n, C, OH, OW] of `dtype`.
+ * fp32 coordinates, weights and sums (fp64 for PASTA_F64).  n <= 65535, OH * OW < 2^31, C <= 65535 * 16.  Added in ABI 21 without a bump (purely additive).
+ * pasta_grid_sample_backward: dx = S^T dy ([n, C, IH, IW], `dtype`; NULL = not wanted) and grad_grid ([n, OH, OW, 2],
+ * `grid_dtype`; NULL = not wanted; needs x) in one pass over dy.  dx is accumulated with float atomics, so it is not
+ * bitwise reproducible from run to run (ATen's is not either); grad_grid is (one thread per output point, no atomics).
+ * ws: fp32 workspace of pasta_grid_sample_backward_workspace() bytes (nonzero only for a 16-bit dx); the entry zeroes it.
+ * ------------------------------------------------------------------------- */
+int pasta_grid_sample(const void* x, const void* grid, void* y, int64_t n, int C, int IH, int IW, int OH, int OW, int dtype,
+                      int grid_dtype, void* stream);
+int64_t pasta_grid_sample_backward_workspace(int64_t n, int C, int IH, int IW, int dtype);
+int pasta_grid_sample_backward(const void* dy, const void* x, const void* grid, void* dx, void* dgrid, void* ws, int64_t n, int C,
+                               int IH, int IW, int OH, int OW, int dtype, int grid_dtype, void* stream);
+
 /* nan_to_num(t, nan, posinf, neginf) in place over n float tensors in one launch per 96 tensors
  * (training_loop_wo_flow_fullbody.py:513-515; misc.py:45).  ptrs / numels: HOST arrays of device pointers / element
  * counts (< 2^31 each); empty tensors are skipped. */

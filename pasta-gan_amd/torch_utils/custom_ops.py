@@ -210,10 +210,22 @@ ABI = {
     'pasta_ada_grid':     (ctypes.c_int, [_c_ptr, _c_i64, ctypes.c_int, ctypes.c_int, _c_ptr, _c_ptr]),
     'pasta_affine_sample': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64] + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_affine_sample_adjoint': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64] + [ctypes.c_int] * 5 + [_c_ptr]),
+    'pasta_grid_sample':  (ctypes.c_int, [_c_ptr] * 3 + [_c_i64] + [ctypes.c_int] * 7 + [_c_ptr]),
+    'pasta_grid_sample_backward_workspace': (_c_i64, [_c_i64] + [ctypes.c_int] * 4),
+    'pasta_grid_sample_backward': (ctypes.c_int, [_c_ptr] * 6 + [_c_i64] + [ctypes.c_int] * 7 + [_c_ptr]),
     'pasta_nan_to_num_multi': (ctypes.c_int, [ctypes.POINTER(_c_ptr), ctypes.POINTER(_c_i64), ctypes.c_int, _c_f32, _c_f32, _c_f32, _c_ptr]),
     'pasta_warp_perspective_u8': (ctypes.c_int, [_c_ptr] * 5 + [ctypes.c_int] * 7 + [_c_ptr]),
     'pasta_patch_composite_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 6 + [_c_ptr]),
 }
+
+# Entries added to ABI 21 after its first release (purely additive, so the version did not move): a library built before them
+# (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.
+LATE_ENTRIES = frozenset(['pasta_grid_sample', 'pasta_grid_sample_backward_workspace', 'pasta_grid_sample_backward'])
+
+def _missing_entry(lib_path, name):
+    def missing(*args, **kwargs):
+        raise RuntimeError('%s has no %s: it predates this tree, rebuild it from this tree' % (lib_path, name))
+    return missing
 
 def get_plugin(module_name='pasta_hip', sources=None, **build_kwargs):
     """Return the loaded library (a ``ctypes.CDLL`` with typed entry points).
@@ -234,6 +246,9 @@ def get_plugin(module_name='pasta_hip', sources=None, **build_kwargs):
             lib_path = ab
         lib = ctypes.CDLL(lib_path)
         for name, (restype, argtypes) in ABI.items():
+            if name in LATE_ENTRIES and not hasattr(lib, name):
+                setattr(lib, name, _missing_entry(lib_path, name))
+                continue
             fn = getattr(lib, name)       # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

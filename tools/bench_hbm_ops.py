@@ -85,6 +85,32 @@ def main():
         dyo = torch.randn_like(out)
         ms = timeit(lambda: gs._AffineSampleAdjoint.apply(dyo, th, (700, 700)))
         rows.append(('affine_sample adjoint (gather)', list(big.shape), (big.numel() + out.numel()) * 4, ms))
+        # grid_sample under a general grid (csrc/grid_sample.hip), each next to the same ATen call; bytes = image + grid + output (forward),
+        # dy + grid + dx (adjoint; its adds are atomics: DESIGN.md section 4 gives the atomic budget), dy + image + grid + grad_grid (grid gradient)
+        F = torch.nn.functional
+        for shape, out_hw in (([48, 3, 256, 256], (256, 256)), ([16, 64, 128, 128], (128, 128))):
+            xs = torch.randn(shape, device=dev)
+            thg = torch.tensor([[0.9, 0.2, 0.03], [-0.2, 0.9, -0.02]], device=dev).repeat(shape[0], 1, 1)
+            grd = F.affine_grid(thg, [shape[0], shape[1], *out_hw], align_corners=False) + 0.01 * torch.randn([shape[0], *out_hw, 2], device=dev)
+            ys = gs._forward(xs, grd)
+            dys = torch.randn_like(ys)
+            fwd_b, adj_b, gg_b = (xs.numel() + grd.numel() + ys.numel()) * 4, (dys.numel() + grd.numel() + xs.numel()) * 4, (dys.numel() + xs.numel() + 2 * grd.numel()) * 4
+            ms = timeit(lambda: gs._forward(xs, grd))
+            rows.append(('grid_sample fwd', shape, fwd_b, ms))
+            ms = timeit(lambda: F.grid_sample(xs, grd, mode='bilinear', padding_mode='zeros', align_corners=False))
+            rows.append(('  ATen grid_sampler_2d', shape, fwd_b, ms))
+            ms = timeit(lambda: gs._backward(dys, None, grd, xs.shape, True, False))
+            rows.append(('grid_sample dx (atomics)', shape, adj_b, ms))
+            ms = timeit(lambda: torch.ops.aten.grid_sampler_2d_backward(dys, xs, grd, 0, 0, False, [True, False]))
+            rows.append(('  ATen backward, dx', shape, adj_b, ms))
+            ms = timeit(lambda: gs._backward(dys, xs, grd, xs.shape, False, True))
+            rows.append(('grid_sample grad_grid', shape, gg_b, ms))
+            ms = timeit(lambda: torch.ops.aten.grid_sampler_2d_backward(dys, xs, grd, 0, 0, False, [False, True]))
+            rows.append(('  ATen backward, grad_grid', shape, gg_b, ms))
+            ms = timeit(lambda: gs._backward(dys, xs, grd, xs.shape, True, True))
+            rows.append(('grid_sample dx + grad_grid', shape, adj_b + xs.numel() * 4 + grd.numel() * 4, ms))
+            ms = timeit(lambda: torch.ops.aten.grid_sampler_2d_backward(dys, xs, grd, 0, 0, False, [True, True]))
+            rows.append(('  ATen backward, both', shape, adj_b + xs.numel() * 4 + grd.numel() * 4, ms))
         ms = timeit(lambda: x + g)
         rows.append(('torch add (reference point)', list(x.shape), 3 * x.numel() * 4, ms))
         ms = timeit(lambda: x.clone())
