@@ -255,11 +255,14 @@ int pasta_conv2d_pack_pair(const float* w, const pasta_conv_desc* da, void* ws_a
  * lattice computes the four output parity classes of a tile from one staged (8 + 1) x (32 + 1) window image -- nine taps, weights by LDS-DMA --
  * and the remainder row / column as edge tiles of the same grid; *launches = 1; the workspace also holds the input's last column, gathered by a
  * small kernel in front).  Kernel 7 also takes pasta_conv_desc.x_layout = PASTA_LAYOUT_PIECES16 (round 5).
- * Any out pointer may be NULL. */
+ * A conv_transpose2d launched as one launch per output parity class (*launches > 1: stride >= 3, or stride 2 on the fp32 kernel or onto a plane
+ * under 2 x 2) reports the kernel of each class's launch: every class takes the same one.
+ * pasta_conv2d_plan answers with the choice pasta_conv2d(_ex) / pasta_conv2d_modulated make for the same flags.  Any out pointer may be NULL. */
 #define PASTA_PLAN_ISCALE   1
 #define PASTA_PLAN_OSCALE   2
 #define PASTA_PLAN_EPILOGUE 4
 #define PASTA_PLAN_MODULATED 8   /* pasta_conv2d_modulated (per-group modulated weights) */
+#define PASTA_PLAN_NOISE    16   /* the epilogue adds noise (pasta_conv_epilogue.noise; with PASTA_PLAN_EPILOGUE): not kernels 9 - 12 */
 int pasta_conv2d_plan(const pasta_conv_desc* d, int launch_flags, int* tile, int* ksplit, int* math, int* launches, int* kernel);
 
 /* Same for pasta_conv2d_wgrad: *kernel = 0 conv_wgrad_kernel (fp32 MFMA, taps x 64 x 64 tiles), 1

@@ -304,7 +304,7 @@ struct ConvFwdParams {
     // packed-K mode of conv_fwd_bf16x6_kernel (few input channels): "channel" k of the K loop is (input channel, tap) and lives
     // koff[k] bytes behind the pixel's base address in a zero-padded copy of the input; null = off
     const unsigned* koff;
-    int xcd_order;                        // conv_fwd_rows2d_bf16x6_kernel, eight-wave tile: consecutive pixel tiles on ONE XCD (PASTA_XCD_ORDER=0: off)
+    int xcd_order;                        // conv_fwd_rows2d_bf16x6_kernel, eight-wave tile: consecutive pixel tiles on ONE XCD (0: off)
     int x_pieces;                         // conv3x3s2_f16x3_kernel: x is PASTA_LAYOUT_PIECES16 (pieces.hip), p.x_amax the producer's bound row
 };
 

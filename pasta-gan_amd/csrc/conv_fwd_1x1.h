@@ -204,15 +204,4 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(ConvFwdParams p) 
     amax_commit(y_am, y_slot);
 }
 
-// Does the pointwise kernel take this launch?  Three-product arithmetic on fp32 tensors, one group, no scales / noise riding along,
-// at least 16 input channels into more than 32 outputs, planes that divide into the pixel tiles.
-static bool conv1x1_ok(const ConvFwdParams& p, int kh, int kw, int stride, int pad_h, int pad_w) {
-    static const bool enabled = !(getenv("PASTA_CONV1X1") && getenv("PASTA_CONV1X1")[0] == '0');       // A/B switch
-    if (!enabled || p.bf16x6 != NP_F16X3 || p.io != IO_F32 || p.G != 1 || kh != 1 || kw != 1 || stride != 1 || pad_h || pad_w) return false;
-    if (p.iscale || p.oscale || p.noise || p.ksplit != 1 || p.koff || p.Ig < 16 || p.Og <= 32) return false;
-    if (p.OH != p.H || p.OW != p.W) return false;
-    const int bn = p.Og <= 64 ? 256 : 128;
-    return ((int64_t)p.H * p.W) % bn == 0;
-}
-
 }  // namespace pasta

@@ -557,17 +557,16 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
 // pixels; the B
 // image is double-buffered per stage, the A image per step.  Control flow around memory operations is static as in
 // the base kernel.
-// Schedules (PASTA_ROWS_PIPE selects; all bit-compatible in their results up to the order of the six products):
-//   1 (default)  below.   0: weights fetched and stored within one step.
-//   2  register diet, three workgroups per CU (157 VGPRs): +2-4 % on the 128^2 SPADE layers, -4 % at 64^2 and 32^2.
-//   3  weights straight to registers, one barrier per stage instead of per step, half the LDS traffic: +-0 %.
+// Schedules: PIPE 1 below, for every launch but the parity-pair mode, which runs on PIPE 2 (the register diet).  Also measured and
+// retired: the weights fetched and stored within one step; the register diet at three workgroups per CU
+// (+2-4 % on the 128^2 SPADE layers, -4 % at 64^2 and 32^2); the weights straight to registers with one barrier per stage (+-0 %).
 // Round-2 finding (profiles/r2_ablation_rows.txt): three workgroups per CU, a third of the barriers,
 // half of the LDS traffic -- none of it moves the kernel, while removing either operand's global loads in a timing-only
 // build gains 20-24 %.  The kernel behaves as power / clock limited at ~1.25-1.3 PFLOP/s of executed bf16 MFMA (the
 // guide's tuned 256^2 GEMM template reaches 1.32-1.47 on random operands): what remains is energy per product, not schedule.
-// PIPE = 1 (default): the weights of a step are fetched TWO steps ahead into one of two register sets and stored to LDS a
-// full step later, so the store never waits for an L2 round trip (+1.5 % on the 128 x 128 x 128 layers; PIPE = 0 fetches
-// and stores within one step).  Also measured and dropped: reading the next step's fragments during the current step's
+// PIPE = 1: the weights of a step are fetched TWO steps ahead into one of two register sets and stored to LDS a
+// full step later, so the store never waits for an L2 round trip (+1.5 % on the 128 x 128 x 128 layers against fetching
+// and storing within one step).  Also measured and dropped: reading the next step's fragments during the current step's
 // MFMAs (two fragment sets, 236-256 VGPRs) -- no change, the other workgroup of the CU already covers that latency.
 // PAIR (stride-2 conv_transpose2d, 3x3: every upsampling layer and the input gradient of every stride-2 convolution): the
 // lattice is the INPUT plane, a workgroup owns one vertical output parity a and BOTH horizontal parities of its pixels.
@@ -581,11 +580,9 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
 template <int BM, int BN, int OCC, int PIPE, int NP, int IO = IO_F32, bool ISC = false, bool PAIR = false>     // ISC: as in conv_fwd_bf16x6_kernel
 __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdParams p) {
     static_assert(IO == IO_F32 || NP == 1, "16-bit storage: the element is the operand, one product");
-    static_assert(!ISC || PIPE <= 1, "the input scale is staged by the default schedules only");
-    static_assert(!PAIR || (PIPE == 2 && !ISC), "the parity-pair mode runs on the register-diet schedule");
+    static_assert(PAIR ? PIPE == 2 && !ISC : PIPE == 1, "PIPE 1, or the parity-pair mode on the register-diet schedule");
     constexpr unsigned ES = io_size<IO>::value;
-    constexpr bool HX = Arith<NP>::f16x3;               // PASTA_MATH_F16X3 (conv_common.h): default schedules only
-    static_assert(!HX || PIPE <= 1 || (PIPE == 2 && PAIR), "the three-product fp16 arithmetic runs on the default schedules and in the parity-pair mode");
+    constexpr bool HX = Arith<NP>::f16x3;               // PASTA_MATH_F16X3 (conv_common.h)
     constexpr int NPA = Arith<NP>::npa, NPB = Arith<NP>::npb;
     constexpr int WMT = 2, WNT = 2, KC = 16;
     constexpr int WAVES_N = BN / 64;
@@ -596,8 +593,8 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
     constexpr int SLOTS = BN + 16;                      // up to 8 segments with two halo slots each
     constexpr int ABUF = APT * 256 * 8, BSEG = SLOTS * 8, BBUF = 2 * NPB * BSEG;     // 16-bit elements
     extern __shared__ __attribute__((aligned(16))) __bf16 rows_smem[];
-    __bf16* const As = rows_smem;                       // [2][ABUF]  (PIPE 3: the weights never enter LDS)
-    __bf16* const Bs = rows_smem + (PIPE == 3 ? 0 : 2 * ABUF);            // [2][BBUF]
+    __bf16* const As = rows_smem;                       // [2][ABUF]
+    __bf16* const Bs = rows_smem + 2 * ABUF;            // [2][BBUF]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -832,21 +829,10 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
     };
     // One tap = one step: 24 MFMAs in six groups; TAP (0, 1, 2: position in the kernel row), ABUF_ and BBUF_ are literals.
     auto step = [&](const int TAP, const int abuf, const int bbuf) {
-        if (PIPE == 1) {
-            // weights of step t + 2 into the register set of this step's parity (abuf = parity); stored by step t + 1
-            if (TAP == 1) next_a_stage();
-            if (TAP == 0) load_b();
-            load_a(TAP == 0 ? 2 : TAP == 1 ? 0 : 1, abuf);
-        } else {
-        if (TAP == 2) next_a_stage();
-        if (TAP == 0) {
-            // halo loads (wave 0) are issued inside load_b ahead of everything else of this step
-            load_b();
-            load_a(1);
-        } else {
-            load_a(TAP == 1 ? 2 : 0);
-        }
-        }
+        // weights of step t + 2 into the register set of this step's parity (abuf = parity); stored by step t + 1
+        if (TAP == 1) next_a_stage();
+        if (TAP == 0) load_b();
+        load_a(TAP == 0 ? 2 : TAP == 1 ? 0 : 1, abuf);
         Frag f;
         read_frag(f, abuf, bbuf, p.rows_rev ? 2 - TAP : TAP);
 #define PASTA_MM(PA, PB)                                                                                       \
@@ -876,21 +862,21 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
         }
         if (TAP == 1) store_q(bbuf ^ 1, m_slot, half0);
         if (TAP == 2 && wave == h_owner) store_q(bbuf ^ 1, h_slot, h_half);
-        store_a(abuf ^ 1, PIPE == 1 ? abuf ^ 1 : 0);        // PIPE 1: the set fetched by the previous step
+        store_a(abuf ^ 1, abuf ^ 1);                     // the set fetched by the previous step
         PASTA_MM(0, 0)
 #undef PASTA_MM
 #undef PASTA_SPLIT
         __syncthreads();
     };
 
-    // Register diet (PIPE == 2, launched at THREE workgroups per CU: <= 168 VGPRs):
+    // Register diet (PIPE == 2, the parity-pair mode):
     //  * fragments are read one operand at a time, in an order in which consecutive product groups share an operand:
     //    (a3,b1) (a2,b1) (a2,b2) (a1,b2) (a1,b3) (a1,b1): seven operand reads (fourteen ds_read_b128) instead of six pairs
     //    held at once -- 24 fragment registers live instead of 48.  The order of the six products within a chunk is free:
     //    the accumulator already holds the sum over all earlier chunks;
     //  * the split runs piece by piece with the residuals kept IN the staging registers, each piece stored as soon as it is
     //    complete: 4 packed registers live instead of 12;
-    //  * the weights are fetched and stored within one step (one register set: PIPE 0's schedule).
+    //  * the weights are fetched and stored within one step (one register set).
     auto split_piece = [&](float* b, const int* nvalid, uint32_t (&q)[BPT][4], bool first) {
 #pragma unroll
         for (int i = 0; i < BPT; i++)
@@ -981,74 +967,9 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
         __syncthreads();
     };
 
-    // Weights straight to registers (PIPE == 3).  The packed weight chunk is already in fragment order -- [piece][k-half]
-    // [row][8 bf16]: the 64 lanes of a fragment read 2 x 512 contiguous bytes -- so each wave fetches ITS OWN A fragments
-    // from global memory (L2 / L1 resident: every workgroup of an output-channel tile reads the same 885 KB per layer) one
-    // step ahead, into the register set the previous step has just finished with.  The A operand never touches LDS: no
-    // ds_write / ds_read for it, half the LDS footprint, and -- the point -- the workgroup barrier is needed only where
-    // the B image changes hands, once per STAGE (72 MFMAs) instead of once per step (24).
-    bf16x8 ar0[WMT][3], ar1[WMT][3];
-    auto load_a_frags = [&](int tap_i, bf16x8 (&dst)[WMT][3]) {
-        const __bf16* wt = (tap_i == 0 ? a_w0 : tap_i == 1 ? a_w1 : a_w2) + (int64_t)a_cc * a_chunk;
-#pragma unroll
-        for (int pc = 0; pc < NP; pc++)
-#pragma unroll
-            for (int a = 0; a < WMT; a++)
-                dst[a][pc] = *(const bf16x8*)(wt + ((int64_t)(pc * 2 + hl) * p.Og_pad + o_blk + (wm * WMT + a) * 32 + jl) * 8);
-    };
-#ifndef PASTA_ABLATE
-#define PASTA_ABLATE 0          // timing-only builds (results are garbage): 1 = no activation loads, 2 = no split / LDS stores of B, 4 = no weight loads, 8 = no MFMAs
-#endif
-    auto step_areg = [&](const int TAP, const int bbuf, bf16x8 (&cur)[WMT][3], bf16x8 (&nxt)[WMT][3]) {
-        if (TAP == 2) next_a_stage();
-        if (TAP == 0 && !(PASTA_ABLATE & 1)) load_b();
-        if (!(PASTA_ABLATE & 4)) load_a_frags(TAP == 0 ? 1 : TAP == 1 ? 2 : 0, nxt);
-        // The fetches above are for the NEXT step.  Left alone, the scheduler sinks each of them to just in front of its
-        // first use to save registers (s_waitcnt vmcnt(1) / vmcnt(0) between the MFMAs of the next step: an L2 round trip
-        // per fragment); the scheduling barrier keeps them here, a whole step ahead.
-        __builtin_amdgcn_sched_barrier(0);
-        const int off = p.rows_rev ? 2 - TAP : TAP;
-        const __bf16* B_ = Bs + bbuf * BBUF;
-        bf16x8 fb[WNT];
-        auto ldb = [&](int pc) {
-#pragma unroll
-            for (int b = 0; b < WNT; b++) fb[b] = *(const bf16x8*)&B_[((pc * 2 + hl) * SLOTS + fslot[b] + off) * 8];
-        };
-        auto mm = [&](int pa) {
-            if (PASTA_ABLATE & 8) {
-#pragma unroll
-                for (int b = 0; b < WNT; b++) asm volatile("" :: "v"(fb[b]));
-#pragma unroll
-                for (int a = 0; a < WMT; a++) asm volatile("" :: "v"(cur[a][pa]));
-                return;
-            }
-#pragma unroll
-            for (int a = 0; a < WMT; a++)
-#pragma unroll
-                for (int b = 0; b < WNT; b++) acc[a][b] = io_mfma<IO>(cur[a][pa], fb[b], acc[a][b]);
-        };
-        const bool mine = !(PASTA_ABLATE & 2) && (TAP == 1 || (TAP == 2 && wave == h_owner));
-        float* const sb = TAP == 1 ? mb : hb;
-        const int* const sv = TAP == 1 ? m_nvalid : h_nvalid;
-        const int sslot = TAP == 1 ? m_slot : h_slot, shalf = TAP == 1 ? half0 : h_half;
-        uint32_t q[BPT][4];
-        if constexpr (NP == 3) {
-            ldb(0); mm(2);                                          // a3 b1
-            if (mine) { split_piece(sb, sv, q, true); store_piece(bbuf ^ 1, sslot, shalf, 0, q); }
-            mm(1);                                                  // a2 b1
-            ldb(1); mm(1);                                          // a2 b2
-            if (mine) { split_piece(sb, sv, q, false); store_piece(bbuf ^ 1, sslot, shalf, 1, q); }
-            mm(0);                                                  // a1 b2
-            ldb(2); mm(0);                                          // a1 b3
-            if (mine) { split_piece(sb, sv, q, false); store_piece(bbuf ^ 1, sslot, shalf, 2, q); }
-            ldb(0); mm(0);                                          // a1 b1
-        }
-        if (TAP == 2) __syncthreads();                              // the B image of the next stage is complete, this one is free
-    };
-
     // prologue: stage 0 of this K slice entirely, and the weights of its first tap
     load_b();
-    if (PIPE != 3) load_a(0);
+    load_a(0);
 #pragma unroll
     for (int j = 0; j < 4; j++)
 #pragma unroll
@@ -1061,17 +982,10 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
             for (int i = 0; i < BPT; i++) split_pair(hb, h_nvalid, i, j, hsc);
         store_q(0, h_slot, h_half);
     }
-    if (PIPE != 3) store_a(0);
+    store_a(0);
     if (PIPE == 1) load_a(1, 1);                     // weights of step 1: stored by step 0
-    if (PIPE == 3) load_a_frags(0, ar0);             // fragments of step 0
     __syncthreads();
-    if constexpr (PIPE == 3) {
-        static_assert(NP == 3, "the weights-in-registers schedule exists for the six-product arithmetic");
-        for (int s = 0; s < nstages; s += 2) {
-            step_areg(0, 0, ar0, ar1); step_areg(1, 0, ar1, ar0); step_areg(2, 0, ar0, ar1);
-            step_areg(0, 1, ar1, ar0); step_areg(1, 1, ar0, ar1); step_areg(2, 1, ar1, ar0);
-        }
-    } else if constexpr (PIPE == 2) {
+    if constexpr (PIPE == 2) {
         static_assert(NP == 3 || HX, "the register-diet schedule exists for the six- and the three-product arithmetic");
         for (int s = 0; s < nstages; s += 2) {
             step_diet(0, 0, 0); step_diet(1, 1, 0); step_diet(2, 0, 0);
@@ -1201,58 +1115,28 @@ static bool rows_tile_ok(int P, int Q, int BN) {
     return Q % 32 == 0 && (seg & (seg - 1)) == 0 && BN % seg == 0 && Q % seg == 0 && ((int64_t)P * Q) % BN == 0;
 }
 
-// The row-reuse kernel of one arithmetic / storage type, if the lattice is made of whole row segments (conv_tu_fwd_rows_*.hip).
-template <int BM, int BN, int NP, int IO>
-static bool launch_fwd_rows_np(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
-    if (!(q.rows && q.ncls == 1 && rows_tile_ok(q.cls[0].P, q.cls[0].Q, BN))) return false;
-    // full tiles made of whole row segments inside one image
+// The row-reuse kernel of one arithmetic / storage type (conv_tu_fwd_rows_*.hip; the lattice is made of whole row segments: the planner checked).
+// ISC: the input scale in the staging (fp32 storage, fp32-equivalent products: the forward of a modulated convolution; other arithmetics keep
+// the separate scaling pass).
+template <int BM, int BN, int NP, int IO, bool ISC = false>
+static void launch_fwd_rows_np(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
     constexpr int APT = (2 * Arith<NP>::npa * BM + 255) / 256;
     constexpr size_t lds = (size_t)(2 * APT * 256 * 8 + 2 * 2 * Arith<NP>::npb * (BN + 16) * 8) * sizeof(__bf16);
-    static const int pipe = getenv("PASTA_ROWS_PIPE") ? getenv("PASTA_ROWS_PIPE")[0] - '0' : 1;        // read once (thread-safe initialisation), never written again
-    if constexpr (IO == IO_F32 && NP != NP_F16X3)
-        PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 0, NP, IO>), lds);
-    if constexpr (IO == IO_F32 && NP == 3)
-        PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 3, 2, NP, IO>), lds);
-    PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO>), lds);
-    if constexpr (IO == IO_F32 && NP == 3) {
-        if (pipe == 2) { hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 3, 2, NP, IO>), grid, dim3(256), lds, s, q); return true; }
-        if (pipe == 3) {
-            constexpr size_t lds3 = (size_t)(2 * 2 * NP * (BN + 16) * 8) * sizeof(__bf16);       // the B images only
-            PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 3, NP, IO>), lds3);
-            hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 3, NP, IO>), grid, dim3(256), lds3, s, q);
-            return true;
-        }
-    }
-    if constexpr (IO == IO_F32 && NP != NP_F16X3) {
-        if (pipe == 0) { hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 0, NP, IO>), grid, dim3(256), lds, s, q); return true; }
-    }
-    hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO>), grid, dim3(256), lds, s, q);
-    return true;
-}
-
-// ... and with the input scale in the staging (fp32 storage, fp32-equivalent products: the forward of a modulated convolution;
-// other arithmetics keep the separate scaling pass).
-template <int BM, int BN, int NP>
-static bool launch_fwd_rows_isc(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
-    if (!(q.rows && q.ncls == 1 && rows_tile_ok(q.cls[0].P, q.cls[0].Q, BN))) return false;
-    constexpr int APT = (2 * Arith<NP>::npa * BM + 255) / 256;
-    constexpr size_t lds = (size_t)(2 * APT * 256 * 8 + 2 * 2 * Arith<NP>::npb * (BN + 16) * 8) * sizeof(__bf16);
-    PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO_F32, true>), lds);
-    hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO_F32, true>), grid, dim3(256), lds, s, q);
-    return true;
+    PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO, ISC>), lds);
+    hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO, ISC>), grid, dim3(256), lds, s, q);
 }
 
 // q.bf16x6 = pieces per operand (3: six products, 2: three, 1: one, NP_F16X3); q.iscale implies fp32 storage and fp32-equivalent products (the caller checked)
 template <int BM, int BN>
-static bool launch_fwd_rows_any(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
-    if (q.iscale && q.bf16x6 == NP_F16X3) return launch_fwd_rows_isc<BM, BN, NP_F16X3>(q, grid, s);
-    if (q.iscale)                  return launch_fwd_rows_isc<BM, BN, 3>(q, grid, s);
-    if (q.io == IO_BF16)           return launch_fwd_rows_np<BM, BN, 1, IO_BF16>(q, grid, s);       // 16-bit storage: always one product
-    if (q.io == IO_F16)            return launch_fwd_rows_np<BM, BN, 1, IO_F16>(q, grid, s);
-    if (q.bf16x6 == 1)             return launch_fwd_rows_np<BM, BN, 1, IO_F32>(q, grid, s);
-    if (q.bf16x6 == 2)             return launch_fwd_rows_np<BM, BN, 2, IO_F32>(q, grid, s);
-    if (q.bf16x6 == NP_F16X3)      return launch_fwd_rows_np<BM, BN, NP_F16X3, IO_F32>(q, grid, s);
-    return launch_fwd_rows_np<BM, BN, 3, IO_F32>(q, grid, s);
+static void launch_fwd_rows_any(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
+    if (q.iscale && q.bf16x6 == NP_F16X3) launch_fwd_rows_np<BM, BN, NP_F16X3, IO_F32, true>(q, grid, s);
+    else if (q.iscale)             launch_fwd_rows_np<BM, BN, 3, IO_F32, true>(q, grid, s);
+    else if (q.io == IO_BF16)      launch_fwd_rows_np<BM, BN, 1, IO_BF16>(q, grid, s);       // 16-bit storage: always one product
+    else if (q.io == IO_F16)       launch_fwd_rows_np<BM, BN, 1, IO_F16>(q, grid, s);
+    else if (q.bf16x6 == 1)        launch_fwd_rows_np<BM, BN, 1, IO_F32>(q, grid, s);
+    else if (q.bf16x6 == 2)        launch_fwd_rows_np<BM, BN, 2, IO_F32>(q, grid, s);
+    else if (q.bf16x6 == NP_F16X3) launch_fwd_rows_np<BM, BN, NP_F16X3, IO_F32>(q, grid, s);
+    else                           launch_fwd_rows_np<BM, BN, 3, IO_F32>(q, grid, s);
 }
 
 // The base kernel (conv_tu_fwd_base_*.hip): any lattice, the packed-K mode, the input scale.

@@ -159,8 +159,7 @@ __global__ __launch_bounds__(256) void conv1x1_fewcout_kernel(FewChParams p) {
 // Which of the two takes a launch (0: neither): fp32 or 16-bit tensors (the stored element is converted on the way in and out: fp32 FMAs), 1x1, stride 1, no padding, one group, plain weights, no output scale / noise,
 // planes of a multiple of four pixels, more than 8192 pixels (the K-sliced small-plane path keeps the rest); an input scale on the few-output side only.
 static int conv1x1_fewch_kind(const pasta_conv_desc* d, bool has_iscale, bool has_oscale, bool has_noise, bool modulated) {
-    static const bool enabled = !(getenv("PASTA_CONV_FEWCH") && getenv("PASTA_CONV_FEWCH")[0] == '0');       // A/B switch
-    if (!enabled || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad_h || d->pad_w || d->groups != 1) return 0;
+    if (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad_h || d->pad_w || d->groups != 1) return 0;
     if (has_oscale || has_noise || modulated || d->x2 || d->x_layout || d->OH != d->H || d->OW != d->W) return 0;
     const int64_t hw = (int64_t)d->H * d->W;
     if (hw % 4 || (int64_t)d->N * hw <= 8192) return 0;

@@ -46,16 +46,10 @@ namespace pasta {
 // XP (round 5): x is PASTA_LAYOUT_PIECES16 (pieces.hip) -- the producer wrote the operand's fp16 pieces h | l' as 16-byte units of eight channels,
 // [N][C/8][H][piece][W] -- so a staging unit is TWO 16-byte loads (lanes along a row: 1 KB runs) straight into the B image: eight dword loads,
 // the scale and the split (some forty vector instructions per unit) are the producer's, done once per tensor instead of once per consuming tile.
-// GA (round 5): the WEIGHTS of a step go from L2 straight into their LDS buffer (global_load_lds_dwordx4: the packed tensor already has the
-// image's layout, one 16-byte unit per lane, a wave's units contiguous) one step ahead, instead of two steps ahead into one of two register
-// sets and from there to LDS: no ds_write_b128 pass in front of the barrier, 24 registers fewer.  The waits are counted by hand (the DMA is a
-// vector-memory operation the compiler does not see as a write to LDS): at the end of a step `s_waitcnt vmcnt(K)`, K = the activation loads
-// issued BEHIND the DMA in that step (a compiler barrier pins that order), so that those stay in flight across the barrier and the DMA has
-// landed; in the steps that split and store a unit the DMA is issued behind the split (hipcc waits vmcnt(0) at the first use of an ordinary
-// load while a DMA is in flight: nothing else is outstanding there).
+// GA: retired (the weights by LDS-DMA, -2.3 % on the training step's mix: profiles/r5_ab_rows2d_glds.txt).
 template <int BM, int BN, int R, int NP = 3, int IO = IO_F32, bool ISC = false, int NT = 256, bool XP = false, bool GA = false>
 __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_kernel(ConvFwdParams p) {
-    static_assert(!GA || (!ISC && IO == IO_F32), "weights by LDS-DMA: the counted waits are written for the plain fp32-storage launches");
+    static_assert(!GA, "GA stays a parameter only so that the instances keep their names (tools and bench.py match them)");
     static_assert(IO == IO_F32 || NP == 1, "16-bit storage: the element is the operand, one product");
     static_assert(!XP || (NP == NP_F16X3 && IO == IO_F32 && !ISC), "operand pieces: the three-product arithmetic's, plain launches");
     static_assert(!ISC || ((NP == 3 || NP == NP_F16X3) && IO == IO_F32), "the input scale rides in the fp32-equivalent staging");
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
     // TFLOP/s, step 155.3 -> 154.4 ms (same box, twice; profiles/r3_ab_xcd_order.txt).  The same order on the four-wave 64 x 256 tile:
     // -2.4 %; on the base kernel: nothing (r3_ab_xcd_order2.txt) -- not applied there.  Also measured: the output-channel tiles of a pixel
     // tile back to back on one XCD (layers with more than 128 output channels): 315 -> 303 TFLOP/s on 128 -> 256, nothing on 256 -> 256 and
-    // 512 -> 512 (r3_ab_xcd_otiles.txt).  PASTA_XCD_ORDER=0 switches it off.
+    // 512 -> 512 (r3_ab_xcd_otiles.txt).  p.xcd_order = 0 switches it off.
     unsigned bx = blockIdx.x;
     if (NT == 512 && p.xcd_order && (gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
     const int n_img = bx / tpi;
@@ -170,24 +164,11 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         if (set == 0) { areg0 = unit(0); if (APT > 1) areg1 = unit(1); if (APT > 2) areg2 = unit(2); }
         else          { breg0 = unit(0); if (APT > 1) breg1 = unit(1); if (APT > 2) breg2 = unit(2); }
     };
-    auto glds_a = [&](int tap, int cc, int buf) {              // GA: the weights of (tap, chunk cc) into A buffer `buf`
-        const int ccl = cc < NC ? cc : NC - 1;
-        const __bf16* wt = wtap[tap] + (int64_t)ccl * a_chunk;
-#pragma unroll
-        for (int j = 0; j < APT; j++) {
-            int e = tid + NT * j;
-            if (NT * (j + 1) > AUNITS) e = e < AUNITS ? e : AUNITS - 1;       // past the image: a valid address into the buffer's padding
-            const int seg = e / BM, within = e - seg * BM;
-            const __bf16* src = wt + ((int64_t)seg * p.Og_pad + o_blk + within) * 8;
-            __bf16* dst = As + buf * ABUF + (wave * 64 + NT * j) * 8;        // the wave's base: the hardware adds lane * 16 bytes
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-        }
-    };
     // The first trip to memory is issued HERE, in front of the rest of the set-up (operand scale, accumulators, fragment slots, tap offsets:
     // several hundred mostly scalar instructions that the compiler otherwise places in front of the first load -- 680 instructions on the
     // eight-wave tile, whose workgroup is alone on its CU: nothing hides them): the weights of the first tap and every unit of the first
     // chunk (ONE trip to memory in front of the K loop instead of UPT; the accumulators are not live yet: the register sets are free).
-    if constexpr (GA) glds_a(0, c_first, 0); else load_a(0, c_first, 0);
+    load_a(0, c_first, 0);
     float fb[UPT][8], fc[UPT][ISC ? 8 : 1];
     int fnv[UPT];
 #pragma unroll
@@ -306,24 +287,17 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
 #pragma unroll
         for (int k = 0; k < UPT; k++)
             if (S == (USTRIDE * (k + 1) < 8 ? USTRIDE * (k + 1) : 8)) ku = k;
-        int behind = 0;                                  // GA: vector-memory loads issued behind the DMA in this step
         auto fetches = [&]() {
             // fetches first: they are the oldest outstanding loads when the split of a later step waits for them
-            if constexpr (GA) {
-                if (S + 1 < 9) glds_a(S + 1, cc, gpar ^ 1); else glds_a(0, cc + 1, gpar ^ 1);
-                asm volatile("" ::: "memory");           // the activation loads below stay behind the DMA (they are counted)
-            } else {
-                if (S + 2 < 9) load_a(S + 2, cc, gpar); else load_a(S + 2 - 9, cc + 1, gpar);
-            }
+            if (S + 2 < 9) load_a(S + 2, cc, gpar); else load_a(S + 2 - 9, cc + 1, gpar);
 #pragma unroll
             for (int k = 0; k < UPT; k++)
                 if (S == USTRIDE * k) {
                     if ((k & 1) == 0) load_unit(k, cc + 1 < c_first + nchunks ? cc + 1 : cc, next_real, sb0, sc0, nv0);
                     else              load_unit(k, cc + 1 < c_first + nchunks ? cc + 1 : cc, next_real, sb1, sc1, nv1);
-                    behind += XP ? 2 : 8;
                 }
         };
-        if (!GA || ku == NOUNIT) fetches();
+        fetches();
         Frag f;
         read_frag(f, gpar, PAR, toff[S]);
 #define PASTA_MM(PA, PB)                                                                                       \
@@ -331,15 +305,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         _Pragma("unroll") for (int a = 0; a < WMT; a++) _Pragma("unroll") for (int b = 0; b < WNT; b++)          \
             acc[a][b] = mfma16<IO, NP>(f.a[a][PA], f.b[b][PB], acc[a][b]); }
 #define PASTA_SPLIT(J) if (ku != NOUNIT) { if ((ku & 1) == 0) split_pair(sb0, sc0, nv0, J); else split_pair(sb1, sc1, nv1, J); }
-        if constexpr (HX && GA) {           // the whole split behind the first group, then the DMA: it has two groups to land
-            PASTA_MM(2, 1)
-            PASTA_SPLIT(0)
-            PASTA_SPLIT(1)
-            PASTA_SPLIT(2)
-            PASTA_SPLIT(3)
-            if (ku != NOUNIT) { store_unit(ku, PAR ^ 1); fetches(); }
-            PASTA_MM(1, 0)
-        } else if constexpr (HX) {          // three product groups: h'' l', l h, h h -- smallest terms first
+        if constexpr (HX) {          // three product groups: h'' l', l h, h h -- smallest terms first
             PASTA_MM(2, 1)
             PASTA_SPLIT(0)
             PASTA_SPLIT(1)
@@ -357,25 +323,12 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         PASTA_SPLIT(3)
         PASTA_MM(0, 1)
         }
-        if constexpr (HX && GA) {
-        } else if constexpr (GA) {
-            if (ku != NOUNIT) { store_unit(ku, PAR ^ 1); fetches(); }                 // behind the split (see the note at the head of the kernel)
-        } else {
-            if (ku != NOUNIT) store_unit(ku, PAR ^ 1);
-            store_a(gpar ^ 1, gpar ^ 1);
-        }
+        if (ku != NOUNIT) store_unit(ku, PAR ^ 1);
+        store_a(gpar ^ 1, gpar ^ 1);
         PASTA_MM(0, 0)
 #undef PASTA_MM
 #undef PASTA_SPLIT
-        if constexpr (GA) {
-            if (behind == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (behind == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if (behind == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        } else __syncthreads();
+        __syncthreads();
     };
 
     // prologue, second half: split and store the first chunk (fetched above), the weights of its first two taps
@@ -385,11 +338,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         for (int j = 0; j < 4; j++) split_pair(fb[k], fc[k], fnv[k], j);
         store_unit(k, 0);
     }
-    if constexpr (!GA) {
-        store_a(0, 0);
-        load_a(1, c_first, 1);                       // stored by step 0
-    }
-    __syncthreads();                                 // (GA: its fence waits for the DMA of the first tap's weights)
+    store_a(0, 0);
+    load_a(1, c_first, 1);                           // stored by step 0
+    __syncthreads();
     for (int c = 0; c < nchunks; c += 2) {           // an odd count runs one all-zero chunk (its fetches re-read valid addresses)
         const int cc = c_first + c;
         step(0, 0, cc); step(1, 0, cc); step(2, 0, cc); step(3, 0, cc); step(4, 0, cc); step(5, 0, cc); step(6, 0, cc); step(7, 0, cc); step(8, 0, cc);
@@ -535,13 +486,13 @@ static bool rows2d_tile_ok(int P, int Q) {
     return P % R == 0 && Q % SEG == 0;
 }
 
-template <int BM, int BN, int R, int NP, int IO, bool ISC = false, int NT = 256, bool XP = false, bool GA = false>
+template <int BM, int BN, int R, int NP, int IO, bool ISC = false, int NT = 256, bool XP = false>
 static void launch_fwd_rows2d_np(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
     constexpr int SEG = BN / R, SLOTS = (R + 2) * (SEG + 2);
     constexpr int APT = (2 * Arith<NP>::npa * BM + NT - 1) / NT;
     constexpr size_t lds = (size_t)(2 * APT * NT * 8 + 2 * 2 * Arith<NP>::npb * SLOTS * 8) * sizeof(__bf16);
-    PASTA_SET_LDS((conv_fwd_rows2d_bf16x6_kernel<BM, BN, R, NP, IO, ISC, NT, XP, GA>), lds);
-    hipLaunchKernelGGL((conv_fwd_rows2d_bf16x6_kernel<BM, BN, R, NP, IO, ISC, NT, XP, GA>), grid, dim3(NT), lds, s, q);
+    PASTA_SET_LDS((conv_fwd_rows2d_bf16x6_kernel<BM, BN, R, NP, IO, ISC, NT, XP>), lds);
+    hipLaunchKernelGGL((conv_fwd_rows2d_bf16x6_kernel<BM, BN, R, NP, IO, ISC, NT, XP>), grid, dim3(NT), lds, s, q);
 }
 
 template <int BM, int BN, int R>
@@ -561,27 +512,16 @@ static void launch_fwd_rows2d(const ConvFwdParams& p, hipStream_t s) {
     else                     launch_fwd_rows2d_np<BM, BN, R, 3, IO_F32>(q, grid, s);
 }
 
-// Rows per 2-D tile for a P x Q lattice on the 128 x 128 tile: 4 (32-column segments), else 2 (64 columns), else 0 = the row
-// kernel.  PASTA_ROWS2D=0 keeps the row kernel, =2 prefers two-row tiles, =1 keeps the 64 x 256 tile on the row kernel (A/B measurements).
+// Rows per 2-D tile for a P x Q lattice on the 128 x 128 tile: 4 (32-column segments), else 2 (64 columns), else 0 = the row kernel.
 static int rows2d_rows(int P, int Q) {
-    static const int mode = getenv("PASTA_ROWS2D") ? atoi(getenv("PASTA_ROWS2D")) : 8;
-    if (mode == 0) return 0;
-    if (mode != 2 && rows2d_tile_ok<128, 4>(P, Q)) return 4;
+    if (rows2d_tile_ok<128, 4>(P, Q)) return 4;
     return rows2d_tile_ok<128, 2>(P, Q) ? 2 : 0;
 }
 
 // Eight waves on a 128 x 256 tile (8 rows x 32 columns; plain six-product fp32 launches): the weights of a step are fetched from L2
 // and stored to LDS once for 256 pixels instead of once for 128 -- +3.7 .. 6 % over the four-wave 128 x 128 tile on every live
 // shape (profiles/r2_rows2d.txt).  A 64 x 512 tile on eight waves (the 64-channel layers) spills and is 10 % slower: not kept.
-// PASTA_ROWS2D=4 keeps the four-wave tiles.
-static bool rows2d_wide(int P, int Q) {
-    static const int mode = getenv("PASTA_ROWS2D") ? atoi(getenv("PASTA_ROWS2D")) : 8;
-    return mode == 8 && rows2d_tile_ok<256, 8>(P, Q);
-}
-
-static bool rows2d_rows256(int P, int Q) {
-    static const int mode = getenv("PASTA_ROWS2D") ? atoi(getenv("PASTA_ROWS2D")) : 8;
-    return mode != 0 && mode != 1 && rows2d_tile_ok<256, 8>(P, Q);          // PASTA_ROWS2D=1: 2-D tiles for the 128 x 128 tile only
-}
+// The 64 x 256 tile takes the same planes as tiles of eight rows.
+static bool rows2d_r8(int P, int Q) { return rows2d_tile_ok<256, 8>(P, Q); }
 
 }  // namespace pasta

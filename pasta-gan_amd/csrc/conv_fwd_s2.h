@@ -259,19 +259,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_f16x3_kernel(ConvFwdParams p
     amax_commit(y_am, y_slot);
 }
 
-// Does the stride-2 kernel take this launch?  (conv2d, 3x3, stride 2, equal pads of 0 or 1, three-product arithmetic on fp32 tensors, one
-// group, nothing riding along; output planes whose width is a power of two >= 16 and that divide into 128-pixel tiles of whole rows.)
+// Output planes of the stride-2 kernel: a width that is a power of two >= 16, planes that divide into 128-pixel tiles of whole rows.
+// (The rest of its conditions: choose_fwd, conv_igemm.hip.)
 static bool conv3x3s2_shape_ok(int OH, int OW) {
     if (OW < 16 || (OW & (OW - 1))) return false;
     const int seg = OW < 128 ? OW : 128, R = 128 / seg;
     return OH % R == 0;
-}
-static bool conv3x3s2_ok(const ConvFwdParams& p, int kh, int kw, int stride, int pad_h, int pad_w, int transposed) {
-    static const bool enabled = !(getenv("PASTA_CONV_S2") && getenv("PASTA_CONV_S2")[0] == '0');         // A/B switch
-    if (!enabled || transposed || p.bf16x6 != NP_F16X3 || p.io != IO_F32 || p.G != 1 || kh != 3 || kw != 3 || stride != 2 || pad_h != pad_w || pad_h > 1) return false;
-    if (p.iscale || p.oscale || p.noise || p.ksplit != 1 || p.koff || p.x2 || p.Ig < 16 || p.Og <= 32) return false;
-    if (p.x_pieces && ((p.Ig & 7) || pad_h != 0)) return false;         // the producer's units hold eight channels; the blur absorbs the padding
-    return conv3x3s2_shape_ok(p.OH, p.OW);
 }
 
 }  // namespace pasta

@@ -3,7 +3,7 @@
 // (v_mfma_f32_32x32x2_f32).  This file holds the launch plans, the descriptor checks and the C entry points.  The kernels
 // live in the headers included below as templates, which this file never instantiates (it includes them for their host-side
 // shape predicates): every kernel family is compiled in a translation unit of its own, conv_tu_*.hip, and reached through
-// the functions of conv_launch.h -- thirteen units built in parallel (round 5; one unit of 161 kernels took 3 - 12 minutes):
+// the functions of conv_launch.h -- eighteen units built in parallel (one unit of 161 kernels took 3 - 12 minutes):
 //   conv_common.h              parameter blocks, tile enumeration, epilogue
 //   conv_fwd_f32.h             fp32-MFMA forward-type kernel, weight packing        -> conv_tu_pack_f32.hip
 //   conv_fwd_bf16x6.h          split forward-type kernels (base and row-reuse)      -> conv_tu_fwd_base_{128,64}.hip, conv_tu_fwd_rows_{128,64}.hip
@@ -45,36 +45,9 @@ namespace pasta {
 // Packed input-channel padding: a multiple of the KC of the kernel instance that will run.
 static int fwd_ipad(int Ig, FwdTile t) { return (Ig <= 4 && t == T64x256) ? 4 : Ig <= 8 ? 8 : 16; }
 
-// The plain six-product fp32 launch of a 3x3 stride-1 lattice on 2-D tiles, if the plane divides into them.
-static bool try_fwd_rows2d(bool tile128, const ConvFwdParams& p, hipStream_t s) {
-    if (!p.rows || p.ncls != 1 || p.cls[0].T != 9 || !p.bf16x6) return false;        // every arithmetic and storage type (an input scale implies fp32 storage, six products)
-    int ymin = p.tap_dy[0], ymax = p.tap_dy[0], xmin = p.tap_dx[0], xmax = p.tap_dx[0];
-    for (int t = 1; t < 9; t++) {
-        ymin = p.tap_dy[t] < ymin ? p.tap_dy[t] : ymin; ymax = p.tap_dy[t] > ymax ? p.tap_dy[t] : ymax;
-        xmin = p.tap_dx[t] < xmin ? p.tap_dx[t] : xmin; xmax = p.tap_dx[t] > xmax ? p.tap_dx[t] : xmax;
-    }
-    if (ymax - ymin != 2 || xmax - xmin != 2 || xmin != p.rows_d0) return false;
-    ConvFwdParams q = p;
-    q.rows_y0 = ymin;
-    if (tile128) {
-        // eight waves on 128 x 256 (conv_tu_rows2d_wide.hip): fp32 storage, fp32-equivalent products; an input scale under the three-product arithmetic only
-        if (rows2d_wide(p.cls[0].P, p.cls[0].Q) && (p.bf16x6 == 3 || p.bf16x6 == NP_F16X3) && p.io == IO_F32 && (!p.iscale || p.bf16x6 == NP_F16X3)) {
-            if (q.x_pieces) tu_rows2d_wide_pieces(q, s); else tu_rows2d_wide(q, s);
-            return true;
-        }
-        const int R = rows2d_rows(p.cls[0].P, p.cls[0].Q);
-        if (R == 4) { tu_rows2d_128_r4(q, s); return true; }
-        if (R == 2) { tu_rows2d_128_r2(q, s); return true; }
-    } else {
-        // 64 x 256 tile: 8 rows x 32 columns (B image 10 x 34 slots, 65 KB double-buffered + 16 KB of weights: two workgroups per CU, just)
-        if (rows2d_rows256(p.cls[0].P, p.cls[0].Q)) { tu_rows2d_64_r8(q, s); return true; }
-    }
-    return false;
-}
-
-
-// The split forward-type kernels on a 128 x 128 or 64 x 256 tile: the row-reuse kernel where the lattice is made of whole row segments, else the base kernel.
-static void launch_fwd_bf16x6(bool tile128, const ConvFwdParams& p, hipStream_t s) {
+// The split forward-type kernels on a 128 x 128 or 64 x 256 tile: the row-reuse kernel (rows: the lattice is made of whole row segments), else
+// the base kernel.
+static void launch_fwd_bf16x6(bool tile128, bool rows, const ConvFwdParams& p, hipStream_t s) {
     const int BM = tile128 ? 128 : 64, BN = tile128 ? 128 : 256;
     ConvFwdParams q = p;
     q.o_tiles = (p.Og + BM - 1) / BM;
@@ -85,16 +58,19 @@ static void launch_fwd_bf16x6(bool tile128, const ConvFwdParams& p, hipStream_t 
     }
     tiles *= p.ncls;
     const dim3 grid((unsigned)tiles, q.o_tiles * q.ksplit, p.G);
-    if (tile128) { if (!tu_fwd_rows_128(q, grid, s)) tu_fwd_base_128(q, grid, s); }
-    else         { if (!tu_fwd_rows_64(q, grid, s)) tu_fwd_base_64(q, grid, s); }
+    if (rows) { if (tile128) tu_fwd_rows_128(q, grid, s); else tu_fwd_rows_64(q, grid, s); }
+    else      { if (tile128) tu_fwd_base_128(q, grid, s); else tu_fwd_base_64(q, grid, s); }
 }
 
-static void dispatch_fwd(FwdTile t, const ConvFwdParams& p, hipStream_t s) {
-    if (p.bf16x6 && (t == T128x128 || t == T64x256)) {
-        if (!try_fwd_rows2d(t == T128x128, p, s)) launch_fwd_bf16x6(t == T128x128, p, s);
-        return;
-    }
-    tu_fwd_f32(t, p, s);
+// A 3x3 stride-1 lattice on 2-D tiles (plan kernels 4 - 7): the rows of the tile start at the lattice's first tap row.
+static void launch_fwd_rows2d(int kernel, const ConvFwdParams& p, hipStream_t s) {
+    ConvFwdParams q = p;
+    q.rows_y0 = p.tap_dy[0];
+    for (int t = 1; t < 9; t++) q.rows_y0 = p.tap_dy[t] < q.rows_y0 ? p.tap_dy[t] : q.rows_y0;
+    if (kernel == 7) { if (q.x_pieces) tu_rows2d_wide_pieces(q, s); else tu_rows2d_wide(q, s); }
+    else if (kernel == 4) tu_rows2d_128_r4(q, s);
+    else if (kernel == 5) tu_rows2d_128_r2(q, s);
+    else tu_rows2d_64_r8(q, s);
 }
 
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
@@ -135,8 +111,6 @@ static int64_t fwd_lattice_pixels(const pasta_conv_desc* d) {
     return (int64_t)d->N * ((d->OH + d->stride - 1) / d->stride) * ((d->OW + d->stride - 1) / d->stride);
 }
 
-// Which kernel a forward-type launch uses: the tile, the number of K slices, and whether the split-bf16 kernel may
-// run (it also needs iscale == nullptr, known only at launch).
 // bf16 pieces per operand of the split-bf16 kernels for a math mode
 // (PASTA_MATH_F16X3: the pseudo count NP_F16X3 -- fp16 pieces, three products; conv_common.h)
 static int math_pieces(int math) { return math == PASTA_MATH_BF16 ? 1 : math == PASTA_MATH_BF16X3 ? 2 : math == PASTA_MATH_BF16X6 ? 3 : NP_F16X3; }    // PASTA_MATH_DEFAULT = PASTA_MATH_F16X3
@@ -158,6 +132,7 @@ __global__ __launch_bounds__(256) void amax_times_kernel(const float* __restrict
     parts_out[threadIdx.x] = parts_in[threadIdx.x] * m;
 }
 
+// The tile, the number of K slices, and whether the split-bf16 kernels may take a forward-type launch of d (choose_fwd below decides).
 struct FwdPlan { FwdTile tile; int ksplit; int bf16x6; int packed; };     // packed: the few-input-channel mode (conv_fwd_bf16x6_kernel, KT)
 
 // Do the split-bf16 kernels of this launch take the input scale (modulation) in their staging code?
@@ -170,8 +145,7 @@ static FwdPlan plan_fwd(const pasta_conv_desc* d) {
     // fewer than 16 input channels into more than 32 output channels over a large plane with at least 64 (channel, tap) pairs -- the 7x7
     // RGB stems: 0.394 -> 0.234 ms.  Below (3x3: 27 pairs, 1x1: 3) the output store is what the launch costs and the fp32 kernel's
     // epilogue is the faster one: 0.113 -> 0.141 ms and 0.205 -> 0.366 ms when forced (profiles/r3_ab_packed_k.txt)
-    static const bool packed_on = !(getenv("PASTA_PACKED_K") && getenv("PASTA_PACKED_K")[0] == '0');
-    const bool few = packed_on && !d->transposed && d->groups == 1 && Ig < 16 && Og > 32 && npix > 8192 && d->io_dtype == PASTA_F32 &&
+    const bool few = !d->transposed && d->groups == 1 && Ig < 16 && Og > 32 && npix > 8192 && d->io_dtype == PASTA_F32 &&
                      d->math != PASTA_MATH_F32 && fp32_equivalent(math_pieces(d->math)) && Ig * d->kh * d->kw >= 64 && Ig * d->kh * d->kw <= 1024 &&
                      (int64_t)d->N * d->C_in * (d->H + 2 * d->pad_h) * (d->W + 2 * d->pad_w) < (1ll << 28);
     FwdPlan f;
@@ -218,12 +192,11 @@ struct WgradPlan {
 // 3x3 stride-1 pad-1 weight gradients over planes of 16-pixel rows under a split arithmetic (round 5): the split kernel's chunk is 32 consecutive
 // pixels of a row, so these ran on the fp32-MFMA kernel (75 - 99 TFLOP/s: 157 peak).  A 16-pixel row is taken as a 32-pixel chunk whose second half
 // is zero (the S loads of the missing pixels are masked; the L halo's validity bits already zero the columns past the row): half of the MFMAs
-// multiply zeros, and the launch still runs twice as fast.  8-pixel rows (a quarter filled) stay where they are.  PASTA_WGRAD_WIDE16=0: off.
+// multiply zeros, and the launch still runs twice as fast.  8-pixel rows (a quarter filled) stay where they are.
 static bool wgrad_wide16(const pasta_conv_desc* d) {
-    static const bool enabled = !(getenv("PASTA_WGRAD_WIDE16") && getenv("PASTA_WGRAD_WIDE16")[0] == '0');
     const int P = d->transposed ? d->H : d->OH, Q = d->transposed ? d->W : d->OW;
     const int LH = d->transposed ? d->OH : d->H, LW = d->transposed ? d->OW : d->W;
-    return enabled && (d->math != PASTA_MATH_F32 || d->io_dtype != PASTA_F32) && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 &&
+    return (d->math != PASTA_MATH_F32 || d->io_dtype != PASTA_F32) && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 &&
            Q == 16 && LH == P && LW == Q && !d->x_layout;
 }
 
@@ -299,6 +272,116 @@ static int check_desc(const pasta_conv_desc* d, const char* who) {
     return 0;
 }
 
+// Stride-2 3x3 conv_transpose2d whose output covers the doubled input plane (OH = 2H or 2H + 1): the parity-pair mode of the row-reuse
+// kernel (conv_fwd_bf16x6.h) under the fp32-equivalent arithmetics, no K slices.  pair_small: also planes under 128 x 128 with a remainder.
+static bool pair_launch_ok(const pasta_conv_desc* d, int pieces, int ksplit, FwdTile tile, bool pair_small) {
+    if (!d->transposed || d->stride != 2 || d->kh != 3 || d->kw != 3 || d->pad_h != d->pad_w || d->pad_h > 1) return false;
+    if ((pieces != 3 && pieces != NP_F16X3) || d->io_dtype != PASTA_F32 || ksplit != 1) return false;
+    if (d->OH < 2 * d->H || d->OH > 2 * d->H + 1 || d->OW < 2 * d->W || d->OW > 2 * d->W + 1) return false;
+    if (tile != T128x128 && tile != T64x256) return false;
+    // Measured (profiles/r2_conv_pairs.txt): onto 2H x 2W outputs (no remainder) the pair kernel is 1.4x the per-class launch at
+    // every size; with the remainder row / column it wins where the main launch outlasts the remainder's K loop (a few
+    // dozen workgroups, 0.1 - 0.3 ms of serial latency however little they compute): input planes of 128 x 128 and larger.
+    const bool remainder = d->OH > 2 * d->H || d->OW > 2 * d->W;
+    if (remainder && (int64_t)d->H * d->W < 128 * 128 && !pair_small) return false;
+    return rows_tile_ok(d->H, d->W, tile == T128x128 ? 128 : 256);
+}
+
+// ... or the one-pass kernel over the input lattice (conv_fwd_t2.h, round 5; plan kernel 13): pad 0, the three-product arithmetic, planes of
+// 8 x 32 or 16 x 16 tiles, no K slices, one input tensor.  Takes precedence over the pair mode.  (At 32 x 32 and 16 x 16 the regular tiles of a
+// batch of 16 fill the chip once or half, and what the edge tiles in front of them take is added to the launch: +7 % / +12 % there, +30 % / +50 %
+// on the discriminator's stacked batches of 48 against planes of 64 x 64 and larger only -- profiles/r5_ab_conv_t2.txt.)
+static bool t2_shape_ok(const pasta_conv_desc* d, int pieces, int ksplit) {
+    if (!d->transposed || d->stride != 2 || d->kh != 3 || d->kw != 3 || d->pad_h != 0 || d->pad_w != 0) return false;
+    if (pieces != NP_F16X3 || d->io_dtype != PASTA_F32 || ksplit != 1 || d->x2 || d->x_layout) return false;
+    if (d->OH < 2 * d->H || d->OH > 2 * d->H + 1 || d->OW < 2 * d->W || d->OW > 2 * d->W + 1) return false;
+    return d->C_in / d->groups >= 16 && ((d->H % 8 == 0 && d->W % 32 == 0) || (d->H % 16 == 0 && d->W % 16 == 0));
+}
+
+// How a conv_transpose2d launch covers its output parity classes.
+enum TransposedLaunch { TL_NONE, TL_ONEPASS, TL_PAIR, TL_MERGED, TL_PER_CLASS };
+
+// Everything the planner reports and the launch does for a forward-type launch of d with launch_flags (PASTA_PLAN_*).
+struct FwdChoice {
+    int kernel;             // plan kernel id (include/pasta_hip.h); TL_PER_CLASS: the kernel of every class's launch
+    FwdTile tile;
+    int ksplit;
+    int pieces;             // operand pieces of the split-bf16 kernels as launched (16-bit storage: 1); 0: fp32 MFMA or a few-channel kernel
+    int math;               // PASTA_MATH_* actually used
+    int launches;           // launches of the main kernel
+    TransposedLaunch tl;
+    bool packed;            // the packed-K mode (kernel 8)
+    bool pieces_ok;         // a kernel takes x as PASTA_LAYOUT_PIECES16
+};
+
+// The one place that chooses a forward-type kernel: pasta_conv2d_plan reports the choice, conv2d_run launches it.
+static FwdChoice choose_fwd(const pasta_conv_desc* d, int launch_flags) {
+    // Test-only routing overrides (tests/test_conv_rows2d_gpu.py, tests/test_conv_pairs_gpu.py), read once: they send more shapes to kernels
+    // that are live elsewhere.  PASTA_ROWS2D=0: no 2-D tiles, =4: no eight-wave tile; PASTA_T2_PAIR=2: the pair mode on every eligible plane.
+    static const int rows2d_mode = getenv("PASTA_ROWS2D") ? atoi(getenv("PASTA_ROWS2D")) : 8;
+    static const bool pair_small = getenv("PASTA_T2_PAIR") && getenv("PASTA_T2_PAIR")[0] == '2';
+    const bool iscale = launch_flags & PASTA_PLAN_ISCALE, oscale = launch_flags & PASTA_PLAN_OSCALE;
+    const bool modulated = launch_flags & PASTA_PLAN_MODULATED, noise = launch_flags & PASTA_PLAN_NOISE;
+    const FwdPlan f = plan_fwd(d);
+    const int np = math_pieces(d->math);
+    const bool f32 = d->io_dtype == PASTA_F32;
+    FwdChoice c;
+    c.tile = f.tile;
+    c.tl = TL_NONE;
+    c.packed = false;
+    c.pieces = 0;
+    c.pieces_ok = false;
+    if (const int few = conv1x1_fewch_kind(d, iscale, oscale, noise, modulated)) {
+        // a streaming fp32 kernel on the raw weights (conv_fwd_fewch.h): no packing, no operand scale
+        c.kernel = 10 + few; c.ksplit = 1; c.math = PASTA_MATH_F32; c.launches = 1;
+        return c;
+    }
+    c.ksplit = f.ksplit;
+    // An input scale rides in the staging of the split kernels under fp32-equivalent products on fp32 tensors only; the packed-K mode takes neither
+    // an input scale nor modulated weights.
+    const bool sb = f.bf16x6 && (!iscale || isc_in_staging(d)) && !(f.packed && (iscale || modulated));
+    c.packed = sb && f.packed;
+    c.pieces = !sb ? 0 : !f32 ? 1 : np;
+    c.math = !sb ? PASTA_MATH_F32 : !f32 ? PASTA_MATH_BF16 : d->math == PASTA_MATH_BF16X3 ? PASTA_MATH_BF16X3 : d->math == PASTA_MATH_BF16 ? PASTA_MATH_BF16 :
+             d->math == PASTA_MATH_BF16X6 ? PASTA_MATH_BF16X6 : PASTA_MATH_F16X3;
+    const bool f16x3 = sb && f32 && np == NP_F16X3;
+    // the pointwise kernel (conv_fwd_1x1.h): one group, no scale vectors or noise, >= 16 input and > 32 output channels, planes of whole pixel tiles
+    const int bn1 = (d->C_out / d->groups) <= 64 ? 256 : 128;
+    const bool c1x1 = f16x3 && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->stride == 1 && !d->pad_h && !d->pad_w && !iscale && !oscale && !noise &&
+                      c.ksplit == 1 && !c.packed && d->C_in >= 16 && d->C_out > 32 && d->OH == d->H && d->OW == d->W && ((int64_t)d->H * d->W) % bn1 == 0;
+    // the stride-2 kernel (conv_fwd_s2.h): conv2d, 3x3, equal pads of 0 or 1, one group, no scale vectors (s2_fits) or noise (s2)
+    const bool s2_fits = f16x3 && !d->transposed && d->groups == 1 && d->kh == 3 && d->kw == 3 && d->stride == 2 && d->pad_h == d->pad_w && d->pad_h <= 1 &&
+                         !iscale && !oscale && c.ksplit == 1 && !c.packed && d->C_in >= 16 && d->C_out > 32 && conv3x3s2_shape_ok(d->OH, d->OW);
+    const bool s2 = s2_fits && !noise;
+    const bool t2 = sb && t2_shape_ok(d, np, c.ksplit) && !(launch_flags & ~(PASTA_PLAN_ISCALE | PASTA_PLAN_MODULATED));
+    // the pair kernel carries no scale vectors and no epilogue; modulated weights are packed like any others (the edge kernel modulates its own)
+    const bool pair = !t2 && sb && !(launch_flags & ~PASTA_PLAN_MODULATED) && pair_launch_ok(d, np, c.ksplit, c.tile, pair_small);
+    // the lattice of a stride-1 launch is the output plane itself, its taps kh rows of kw adjacent offsets
+    const bool rows = sb && d->stride == 1 && d->kw == 3 && rows_tile_ok(d->OH, d->OW, c.tile == T128x128 ? 128 : 256);
+    const bool plain6 = sb && d->stride == 1 && d->kw == 3 && d->kh == 3 && rows2d_mode != 0;
+    const int rows2d = plain6 && c.tile == T128x128 ? rows2d_rows(d->OH, d->OW) : 0;
+    const bool rows2d_256 = plain6 && c.tile == T64x256 && rows2d_r8(d->OH, d->OW);
+    // eight waves on 128 x 256: fp32 storage, fp32-equivalent products; an input scale under the three-product arithmetic only
+    const bool wide = rows2d && rows2d_mode == 8 && (!iscale || np == NP_F16X3) && fp32_equivalent(np) && f32 && rows2d_r8(d->OH, d->OW);
+    c.kernel = !sb ? 0 : c1x1 ? 9 : s2 ? 10 : c.packed ? 8 : t2 ? 13 : pair ? 3 : wide ? 7 : rows2d ? (rows2d == 4 ? 4 : 5) : rows2d_256 ? 6 : rows ? 2 : 1;
+    if (d->transposed)
+        c.tl = t2 ? TL_ONEPASS : pair ? TL_PAIR : merged_classes(d, sb) ? TL_MERGED : TL_PER_CLASS;
+    c.launches = c.tl == TL_PAIR ? 1 + (d->OH > 2 * d->H || d->OW > 2 * d->W ? 1 : 0) : c.tl != TL_PER_CLASS ? 1 :
+                 (d->stride < d->OH ? d->stride : d->OH) * (d->stride < d->OW ? d->stride : d->OW);
+    // x as PASTA_LAYOUT_PIECES16: the stride-2 kernel with pad 0, or the eight-wave 2-D tile; plain launches, whole channel octets, one input tensor
+    // (the launch refuses noise with it)
+    c.pieces_ok = f16x3 && d->groups == 1 && !(launch_flags & (PASTA_PLAN_ISCALE | PASTA_PLAN_MODULATED)) && d->C_in >= 16 && (d->C_in & 7) == 0 && !d->x2 &&
+                  (wide || (s2_fits && d->pad_h == 0));
+    return c;
+}
+
+// One lattice of a forward-type launch on the kernel choose_fwd chose (0 - 2, 4 - 7; detect_tap_rows has described its taps).
+static void launch_lattice(const FwdChoice& c, const ConvFwdParams& p, hipStream_t s) {
+    if (c.kernel == 0) tu_fwd_f32(c.tile, p, s);
+    else if (c.kernel <= 2) launch_fwd_bf16x6(c.tile == T128x128, c.kernel == 2, p, s);
+    else launch_fwd_rows2d(c.kernel, p, s);
+}
+
 }  // namespace pasta
 
 //------------------------------------------------------------------------------------
@@ -311,8 +394,6 @@ static int64_t packed_input_floats(const pasta_conv_desc* d) {
     return (int64_t)d->N * d->C_in * (d->H + 2 * d->pad_h) * (d->W + 2 * d->pad_w);
 }
 }
-
-namespace pasta { static bool t2_launch_ok(const pasta_conv_desc* d, int pieces, int ksplit, int launch_flags); }
 
 extern "C" int64_t pasta_conv2d_workspace(const pasta_conv_desc* d) {
     using namespace pasta;
@@ -331,7 +412,7 @@ extern "C" int64_t pasta_conv2d_workspace(const pasta_conv_desc* d) {
         pack = pack > pk ? pack : pk;
         extra = kp + packed_input_floats(d);
     }
-    if (t2_launch_ok(d, math_pieces(d->math), ks, 0)) extra = (int64_t)d->N * d->C_in * d->H;      // conv_fwd_t2.h: the input's last column, gathered
+    if (t2_shape_ok(d, math_pieces(d->math), ks)) extra = (int64_t)d->N * d->C_in * d->H;      // conv_fwd_t2.h: the input's last column, gathered
     const int64_t rowinv = (int64_t)d->groups * round_up(Og, fwd_tile_bm(t));      // PASTA_MATH_F16X3: 1 / S_w per packed weight row
     return (WS_AMAX_FLOATS + rowinv + round_up((int)pack, 4) + partial + round_up((int)extra, 4)) * (int64_t)sizeof(float);
 }
@@ -343,76 +424,25 @@ extern "C" int pasta_conv2d_tile(const pasta_conv_desc* d) {
 }
 
 namespace pasta {
-// Does conv3x3s2_f16x3_kernel take this launch with x as the producer wrote it (PASTA_LAYOUT_PIECES16)?  The conditions of conv3x3s2_ok (conv_fwd_s2.h)
-// on the descriptor, plus whole channel octets and the blur's pad 0.
-static bool pieces_fwd_ok(const pasta_conv_desc* d, int launch_flags) {
-    const FwdPlan f = plan_fwd(d);
-    // (round 5) ... or the eight-wave 2-D tile kernel (plan kernel 7: 3x3 stride-1 convolution or input gradient, >= 128 output channels, planes of
-    // 8 rows x 32 columns), plain launches of the three-product arithmetic
-    if (d->stride == 1 && d->kh == 3 && d->kw == 3 && f.bf16x6 && !f.packed && f.tile == T128x128 && math_pieces(d->math) == NP_F16X3 && d->io_dtype == PASTA_F32 &&
-        d->groups == 1 && !(launch_flags & (PASTA_PLAN_ISCALE | PASTA_PLAN_MODULATED)) && d->C_in >= 16 && (d->C_in & 7) == 0 && !d->x2 &&
-        rows2d_rows(d->OH, d->OW) > 0 && rows2d_wide(d->OH, d->OW))
-        return true;
-    return !d->transposed && f.bf16x6 && !f.packed && math_pieces(d->math) == NP_F16X3 && d->io_dtype == PASTA_F32 && d->groups == 1 && d->kh == 3 && d->kw == 3 &&
-           d->stride == 2 && d->pad_h == 0 && d->pad_w == 0 && !(launch_flags & (PASTA_PLAN_ISCALE | PASTA_PLAN_OSCALE | PASTA_PLAN_MODULATED)) && f.ksplit == 1 &&
-           d->C_in >= 16 && (d->C_in & 7) == 0 && d->C_out > 32 && !d->x2 && conv3x3s2_shape_ok(d->OH, d->OW) &&
-           !(getenv("PASTA_CONV_S2") && getenv("PASTA_CONV_S2")[0] == '0');
-}
-static bool pair_launch_ok(const pasta_conv_desc* d, int pieces, int ksplit, FwdTile tile, bool plain);
-// The parity-pair kernel carries no scales and no epilogue: ONE predicate for the planner and the launch.
-static inline bool pair_plain(int launch_flags) { return launch_flags == 0; }
-static inline int launch_flags_of(const float* iscale, const float* oscale, const pasta_conv_epilogue* ep) {
-    return (iscale ? PASTA_PLAN_ISCALE : 0) | (oscale ? PASTA_PLAN_OSCALE : 0) | (ep ? PASTA_PLAN_EPILOGUE : 0);
+static inline int launch_flags_of(const float* iscale, const float* oscale, const pasta_conv_epilogue* ep, const float* wmod_s) {
+    return (iscale ? PASTA_PLAN_ISCALE : 0) | (oscale ? PASTA_PLAN_OSCALE : 0) | (ep ? PASTA_PLAN_EPILOGUE : 0) | (wmod_s ? PASTA_PLAN_MODULATED : 0) |
+           (ep && ep->noise ? PASTA_PLAN_NOISE : 0);
 }
 }
 
 extern "C" int pasta_conv2d_plan(const pasta_conv_desc* d, int launch_flags, int* tile, int* ksplit, int* math, int* launches, int* kernel) {
     using namespace pasta;
     if (int e = check_desc(d, "conv2d_plan")) return e;
-    const bool has_iscale = (launch_flags & PASTA_PLAN_ISCALE) != 0;
-    const FwdPlan f = plan_fwd(d);
-    const bool packed = f.packed && !has_iscale && !(launch_flags & PASTA_PLAN_MODULATED);
-    const bool sb = f.bf16x6 && (!has_iscale || isc_in_staging(d)) && (!f.packed || packed);
-    const int few_kind = conv1x1_fewch_kind(d, has_iscale, (launch_flags & PASTA_PLAN_OSCALE) != 0, false, (launch_flags & PASTA_PLAN_MODULATED) != 0);
-    if (d->io_dtype != PASTA_F32 && !sb && !few_kind)
+    const FwdChoice c = choose_fwd(d, launch_flags);
+    if (d->io_dtype != PASTA_F32 && !c.pieces && c.kernel < 11)      // (11, 12: the few-channel kernels take 16-bit tensors)
         return fail("conv2d: no 16-bit-storage kernel for this shape (fewer than 16 input channels per group, at most 32 "
                     "output channels, or an input scale -- pointwise layers over more than 8192 pixels excepted): convert the tensors to fp32 for this launch");
-    if (const int few = conv1x1_fewch_kind(d, has_iscale, (launch_flags & PASTA_PLAN_OSCALE) != 0, false, (launch_flags & PASTA_PLAN_MODULATED) != 0)) {
-        // a streaming fp32 kernel on the raw weights (conv_fwd_fewch.h): no packing, no operand scale
-        if (tile) *tile = (int)f.tile;
-        if (ksplit) *ksplit = 1;
-        if (math) *math = PASTA_MATH_F32;
-        if (launches) *launches = 1;
-        if (kernel) *kernel = 10 + few;
-        return 0;
-    }
-    if (tile) *tile = (int)f.tile;
-    if (ksplit) *ksplit = f.ksplit;
-    if (math) *math = !sb ? PASTA_MATH_F32 : d->io_dtype != PASTA_F32 ? PASTA_MATH_BF16 : d->math == PASTA_MATH_BF16X3 ? PASTA_MATH_BF16X3 : d->math == PASTA_MATH_BF16 ? PASTA_MATH_BF16 :
-                       d->math == PASTA_MATH_BF16X6 ? PASTA_MATH_BF16X6 : PASTA_MATH_F16X3;
-    const bool t2 = sb && t2_launch_ok(d, math_pieces(d->math), f.ksplit, launch_flags);
-    const bool pair = t2 || (sb && pair_launch_ok(d, math_pieces(d->math), f.ksplit, f.tile, pair_plain(launch_flags)));
-    if (launches) *launches = !d->transposed ? 1 : t2 ? 1 : pair ? 1 + (d->OH > 2 * d->H || d->OW > 2 * d->W ? 1 : 0) : merged_classes(d, sb) ? 1 :
-                              (d->stride < d->OH ? d->stride : d->OH) * (d->stride < d->OW ? d->stride : d->OW);
-    if (kernel) {
-        // the lattice of a stride-1 launch is the output plane itself, its taps kh rows of kw adjacent offsets
-        const bool rows = sb && d->stride == 1 && d->kw == 3 && rows_tile_ok(d->OH, d->OW, f.tile == T128x128 ? 128 : 256);
-        const bool plain6 = sb && d->stride == 1 && d->kw == 3 && d->kh == 3;
-        const bool rows2d = plain6 && f.tile == T128x128 && rows2d_rows(d->OH, d->OW) > 0;
-        const bool rows2d_256 = plain6 && f.tile == T64x256 && rows2d_rows256(d->OH, d->OW);
-        const bool wide = rows2d && (!has_iscale || math_pieces(d->math) == NP_F16X3) && fp32_equivalent(math_pieces(d->math)) && d->io_dtype == PASTA_F32 && rows2d_wide(d->OH, d->OW);
-        static const bool c1x1_on = !(getenv("PASTA_CONV1X1") && getenv("PASTA_CONV1X1")[0] == '0');
-        const int bn1 = (d->C_out / d->groups) <= 64 ? 256 : 128;
-        const bool c1x1 = c1x1_on && sb && math_pieces(d->math) == NP_F16X3 && d->io_dtype == PASTA_F32 && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->stride == 1 &&
-                          !d->pad_h && !d->pad_w && !(launch_flags & (PASTA_PLAN_ISCALE | PASTA_PLAN_OSCALE)) && f.ksplit == 1 && !packed && d->C_in >= 16 &&
-                          d->C_out > 32 && d->OH == d->H && d->OW == d->W && ((int64_t)d->H * d->W) % bn1 == 0;
-        static const bool s2_on = !(getenv("PASTA_CONV_S2") && getenv("PASTA_CONV_S2")[0] == '0');
-        const bool s2k = s2_on && sb && !d->transposed && math_pieces(d->math) == NP_F16X3 && d->io_dtype == PASTA_F32 && d->groups == 1 && d->kh == 3 && d->kw == 3 &&
-                         d->stride == 2 && d->pad_h == d->pad_w && d->pad_h <= 1 && !(launch_flags & (PASTA_PLAN_ISCALE | PASTA_PLAN_OSCALE)) && f.ksplit == 1 && !packed &&
-                         d->C_in >= 16 && d->C_out > 32 && conv3x3s2_shape_ok(d->OH, d->OW);
-        *kernel = !sb ? 0 : c1x1 ? 9 : s2k ? 10 : packed ? 8 : t2 ? 13 : pair ? 3 : wide ? 7 : rows2d ? (rows2d_rows(d->OH, d->OW) == 4 ? 4 : 5) : rows2d_256 ? 6 : rows ? 2 : 1;
-    }
-    if (d->x_layout == PASTA_LAYOUT_PIECES16 && !pieces_fwd_ok(d, launch_flags))
+    if (tile) *tile = (int)c.tile;
+    if (ksplit) *ksplit = c.ksplit;
+    if (math) *math = c.math;
+    if (launches) *launches = c.launches;
+    if (kernel) *kernel = c.kernel;
+    if (d->x_layout == PASTA_LAYOUT_PIECES16 && !c.pieces_ok)
         return fail("conv2d: x_layout = PASTA_LAYOUT_PIECES16 is served by the 3x3 stride-2 forward kernel (conv2d, pad 0, fp32 y, PASTA_MATH_F16X3, one group, "
                     "C_in a multiple of 8 and >= 16, C_out > 32, output width a power of two >= 16, more than 8192 output pixels, no scale vectors) and by the "
                     "eight-wave 3x3 stride-1 tile kernel (plan kernel 7, no input scale, C_in a multiple of 8) only");
@@ -425,36 +455,6 @@ extern "C" int pasta_conv2d(const void* x, const float* w, void* y, const float*
 }
 
 namespace pasta {
-// Stride-2 3x3 conv_transpose2d whose output covers the doubled input plane (OH = 2H or 2H + 1): the parity-pair mode of
-// the row-reuse kernel (conv_fwd_bf16x6.h) when the launch is the plain six-product fp32 convolution.
-static bool pair_launch_ok(const pasta_conv_desc* d, int pieces, int ksplit, FwdTile tile, bool plain) {
-    static const bool enabled = !(getenv("PASTA_T2_PAIR") && getenv("PASTA_T2_PAIR")[0] == '0');
-    if (!enabled || !d->transposed || d->stride != 2 || d->kh != 3 || d->kw != 3 || d->pad_h != d->pad_w || d->pad_h > 1) return false;
-    if ((pieces != 3 && pieces != NP_F16X3) || d->io_dtype != PASTA_F32 || !plain || ksplit != 1) return false;
-    if (d->OH < 2 * d->H || d->OH > 2 * d->H + 1 || d->OW < 2 * d->W || d->OW > 2 * d->W + 1) return false;
-    if (tile != T128x128 && tile != T64x256) return false;
-    // Measured (profiles/r2_conv_pairs.txt): onto 2H x 2W outputs (no remainder) the pair kernel is 1.4x the per-class launch at
-    // every size; with the remainder row / column it wins where the main launch outlasts the remainder's K loop (a few
-    // dozen workgroups, 0.1 - 0.3 ms of serial latency however little they compute): input planes of 128 x 128 and larger.
-    const bool remainder = d->OH > 2 * d->H || d->OW > 2 * d->W;
-    if (remainder && (int64_t)d->H * d->W < 128 * 128 && !(getenv("PASTA_T2_PAIR") && getenv("PASTA_T2_PAIR")[0] == '2')) return false;
-    return rows_tile_ok(d->H, d->W, tile == T128x128 ? 128 : 256);
-}
-
-// ... or the one-pass kernel over the input lattice (conv_fwd_t2.h, round 5; plan kernel 13): pad 0, the three-product arithmetic, planes of
-// 8 x 32 tiles, an input scale allowed (the modulated layers of the training step), nothing behind the sum.  Takes precedence over the pair mode.
-static bool t2_launch_ok(const pasta_conv_desc* d, int pieces, int ksplit, int launch_flags) {
-    static const bool enabled = !(getenv("PASTA_CONV_T2") && getenv("PASTA_CONV_T2")[0] == '0');
-    if (!enabled || !d->transposed || d->stride != 2 || d->kh != 3 || d->kw != 3 || d->pad_h != 0 || d->pad_w != 0) return false;
-    if (pieces != NP_F16X3 || d->io_dtype != PASTA_F32 || (launch_flags & ~(PASTA_PLAN_ISCALE | PASTA_PLAN_MODULATED)) || ksplit != 1 || d->x2 || d->x_layout) return false;
-    if (d->OH < 2 * d->H || d->OH > 2 * d->H + 1 || d->OW < 2 * d->W || d->OW > 2 * d->W + 1) return false;
-    // Every plane of 8 x 32 or 16 x 16 tiles.  (At 32 x 32 and 16 x 16 the regular tiles of a batch of 16 fill the chip once or half, and what the edge
-    // tiles in front of them take is added to the launch: +7 % / +12 % there, +30 % / +50 % on the discriminator's stacked batches of 48 --
-    // profiles/r5_ab_conv_t2.txt.)  PASTA_CONV_T2=1: planes of 64 x 64 and larger only.
-    static const bool large_only = getenv("PASTA_CONV_T2") && getenv("PASTA_CONV_T2")[0] == '1';
-    return d->C_in / d->groups >= 16 && ((d->H % 8 == 0 && d->W % 32 == 0) || (d->H % 16 == 0 && d->W % 16 == 0)) && ((int64_t)d->H * d->W >= 4096 || !large_only);
-}
-
 // The remainder of the parity-pair launch: output row 2H and / or column 2W of a stride-2 conv_transpose2d onto an odd plane --
 // 1 % of the outputs, each a dot product over ONE input row or column (one or two taps).  As lattices of the MFMA kernels these
 // were a few dozen workgroups whose K loops are as long as anyone's: 0.17 ms of latency behind a 0.2 ms main launch (measured,
@@ -593,17 +593,13 @@ static void launch_transposed_pairs(const pasta_conv_desc* d, const ConvFwdParam
             add_class(1, 0, H, 1, 1, 2 * W, 0, W);
         }
     }
-    static const int edge_mode = getenv("PASTA_T2_EDGE") ? getenv("PASTA_T2_EDGE")[0] - '0' : 1;      // A/B: 0 = the remainder as MFMA lattices, 2 = after the main launch
-    auto launch_edge = [&]() {
-        if (!q.ncls) return;
-        if (edge_mode == 0) { dispatch_fwd(tile, q, s); return; }
+    if (q.ncls) {
         int tiles = 0;
         for (int c = 0; c < q.ncls; c++) tiles += (q.N * q.cls[c].P * q.cls[c].Q + 63) >> 6;
         const dim3 grid((unsigned)tiles, (unsigned)((q.Og + 63) / 64), (unsigned)q.G);
         if (ew.mod_s) hipLaunchKernelGGL(conv_t2_edge_kernel<true>, grid, dim3(256), 0, s, q, ew);
         else hipLaunchKernelGGL(conv_t2_edge_kernel<false>, grid, dim3(256), 0, s, q, ew);
-    };
-    if (edge_mode != 2) launch_edge();
+    }
     ConvFwdParams p = base;
     // main lattice: (p, q) of the input plane -> outputs (2p + a, 2q + b), a, b in {0, 1}
     p.ncls = 2; p.rows = 1; p.rows_rev = 0;
@@ -627,7 +623,6 @@ static void launch_transposed_pairs(const pasta_conv_desc* d, const ConvFwdParam
         p.cls[k] = {H, W, a, 0, nt, 6 * k};
     }
     if (tile == T128x128) tu_fwd_pair_128(p, s); else tu_fwd_pair_64(p, s);
-    if (edge_mode == 2) launch_edge();
 }
 
 static int conv2d_run(const void* x, const float* w, void* y, const float* iscale, const float* oscale,
@@ -654,20 +649,17 @@ namespace pasta {
 // would perform it at the head of the launch: false where the launch packs differently or not at all (few-channel kernels, the packed-K
 // mode of the stems, 16-bit storage, the other arithmetics) -- the caller then leaves w_prepacked at 0.
 static bool pack_job_of(const pasta_conv_desc* d, void* workspace, PackJob& j) {
-    if (d->io_dtype != PASTA_F32 || math_pieces(d->math) != NP_F16X3 || d->x2) return false;
-    if (conv1x1_fewch_kind(d, false, false, false, false)) return false;
-    const FwdPlan plan = plan_fwd(d);
-    if (!plan.bf16x6 || plan.packed) return false;
+    const FwdChoice c = choose_fwd(d, 0);
+    if (c.pieces != NP_F16X3 || c.packed || d->io_dtype != PASTA_F32 || d->x2) return false;
     const int Ig = d->C_in / d->groups, Og = d->C_out / d->groups;
     float* const ws_rowinv = (float*)workspace + WS_AMAX_FLOATS;
     j.rowinv = ws_rowinv;
-    j.wp = ws_rowinv + (int64_t)d->groups * round_up(Og, fwd_tile_bm(plan.tile));
+    j.wp = ws_rowinv + (int64_t)d->groups * round_up(Og, fwd_tile_bm(c.tile));
     j.G = d->groups; j.Ig = Ig; j.Og = Og;
-    j.Ig_pad = round_up(Ig, fwd_ipad(Ig, plan.tile)); j.Og_pad = round_up(Og, fwd_tile_bm(plan.tile));
+    j.Ig_pad = round_up(Ig, fwd_ipad(Ig, c.tile)); j.Og_pad = round_up(Og, fwd_tile_bm(c.tile));
     j.kh = d->kh; j.kw = d->kw; j.transposed = d->transposed; j.flip = d->flip;
     j.wscale = d->wscale == 0.f ? 1.f : d->wscale;
-    static const int pack_xcd = getenv("PASTA_PACK_XCD") ? atoi(getenv("PASTA_PACK_XCD")) : 1;
-    j.pack_xcd_rows = (j.Og_pad & 63) == 0 ? pack_xcd : 0;
+    j.pack_xcd_rows = (j.Og_pad & 63) == 0 ? 1 : 0;
     return true;
 }
 }
@@ -681,10 +673,9 @@ extern "C" int pasta_conv2d_pack_pair(const float* w, const pasta_conv_desc* da,
     if (int e = check_desc(db, "conv2d_pack_pair")) return e;
     PASTA_CHECK(ws_a_bytes >= pasta_conv2d_workspace(da) && ws_b_bytes >= pasta_conv2d_workspace(db), "conv2d_pack_pair: workspace too small");
     PASTA_CHECK((((uintptr_t)ws_a | (uintptr_t)ws_b) & 15) == 0, "conv2d_pack_pair: workspaces must be 16-byte aligned");
-    static const bool enabled = !(getenv("PASTA_PACK_PAIR") && getenv("PASTA_PACK_PAIR")[0] == '0');
     PackJob a, b;
     // both or nothing: one orientation alone is the launch the convolution would have made itself
-    if (!enabled || da->groups != db->groups || !pack_job_of(da, ws_a, a) || !pack_job_of(db, ws_b, b)) return 0;
+    if (da->groups != db->groups || !pack_job_of(da, ws_a, a) || !pack_job_of(db, ws_b, b)) return 0;
     tu_pack_weights_f16x3_pair(w, a, b, (hipStream_t)stream);
     *packed_mask = 3;
     return launch_status("conv2d_pack_pair");
@@ -701,7 +692,8 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
     PASTA_CHECK(workspace && workspace_bytes >= need, "conv2d: workspace of %lld bytes needed, %lld given", (long long)need, (long long)workspace_bytes);
     PASTA_CHECK(((uintptr_t)workspace & 15) == 0, "conv2d: workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    if (const int few = conv1x1_fewch_kind(d, iscale != nullptr, oscale != nullptr, ep && ep->noise, wmod_s != nullptr)) {
+    const FwdChoice ch = choose_fwd(d, launch_flags_of(iscale, oscale, ep, wmod_s));
+    if (ch.kernel == 11 || ch.kernel == 12) {
         FewChParams q;
         q.x = x; q.w = w; q.y = y; q.iscale = iscale; q.io = d->io_dtype;
         q.bias = ep ? ep->bias : nullptr; q.res = ep ? ep->res : nullptr; q.y_amax = ep ? ep->y_amax : nullptr;
@@ -709,23 +701,20 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
         q.w_io = d->transposed ? 1 : 0;
         q.wscale = d->wscale == 0.f ? 1.f : d->wscale;
         q.act = ep ? ep->act : 0; q.alpha = ep ? ep->alpha : 0.f; q.gain = ep ? ep->gain : 1.f; q.clamp = ep ? ep->clamp : -1.f;
-        tu_conv1x1_fewch(few, q, s);
+        tu_conv1x1_fewch(ch.kernel - 10, q, s);
         return launch_status("conv2d");
     }
 
     float* const ws_amax = (float*)workspace;                         // [2][AMAX_PARTS]: partial |max| of x (second row: spare)
     float* const ws_rowinv = ws_amax + WS_AMAX_FLOATS;                // [G][Og_pad]: 1 / S_w per packed weight row (PASTA_MATH_F16X3)
-    {
-        const FwdPlan pl = plan_fwd(d);
-        workspace = ws_rowinv + (int64_t)d->groups * round_up(d->C_out / d->groups, fwd_tile_bm(pl.tile));      // packed weights and K-slice partial sums follow
-    }
+    workspace = ws_rowinv + (int64_t)d->groups * round_up(d->C_out / d->groups, fwd_tile_bm(ch.tile));      // packed weights and K-slice partial sums follow
     ConvFwdParams p;
     p.x = (const float*)x; p.y = (float*)y; p.wp = (const float*)workspace; p.iscale = iscale; p.oscale = oscale;
     p.x_amax = nullptr; p.w_rowinv = nullptr;
     p.x_pieces = d->x_layout == PASTA_LAYOUT_PIECES16;
     if (p.x_pieces) {
         PASTA_CHECK(d->x_amax, "conv2d: x_layout = PASTA_LAYOUT_PIECES16 needs x_amax, the row pasta_blur_pieces wrote (the operand's scale)");
-        PASTA_CHECK(pieces_fwd_ok(d, launch_flags_of(iscale, oscale, nullptr) | (wmod_s ? PASTA_PLAN_MODULATED : 0)) && !(ep && ep->noise),
+        PASTA_CHECK(ch.pieces_ok && !(ep && ep->noise),
                     "conv2d: no kernel takes x_layout = PASTA_LAYOUT_PIECES16 for this launch (pasta_conv2d_plan tells beforehand)");
     }
     p.x2 = (const float*)d->x2; p.x2_amax = nullptr; p.C1 = d->C1;
@@ -733,24 +722,19 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
     p.N = d->N; p.Cin = d->C_in; p.H = d->H; p.W = d->W;
     p.Cout = d->C_out; p.OH = d->OH; p.OW = d->OW;
     p.G = d->groups; p.Ig = d->C_in / d->groups; p.Og = d->C_out / d->groups;
-    const FwdPlan plan = plan_fwd(d);
-    const FwdTile tile = plan.tile;
+    const FwdTile tile = ch.tile;
     p.Ig_pad = round_up(p.Ig, fwd_ipad(p.Ig, tile)); p.Og_pad = round_up(p.Og, fwd_tile_bm(tile));
     p.KK = d->kh * d->kw;
     p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0; p.res = ep ? (const float*)ep->res : nullptr;
     p.alpha = ep ? ep->alpha : 0.f; p.gain = ep ? ep->gain : 1.f; p.clamp = ep ? ep->clamp : -1.f;
     p.noise = ep ? ep->noise : nullptr; p.noise_strength = ep ? ep->noise_strength : nullptr; p.noise_ps = ep ? ep->noise_per_sample : 0;
     p.y_amax = ep ? ep->y_amax : nullptr;
-    p.ksplit = plan.ksplit;
+    p.ksplit = ch.ksplit;
     p.o_tiles = 1;
     p.partial = (float*)workspace + round_up((int)(((int64_t)p.G * p.KK * p.Ig_pad * p.Og_pad * 3 + 1) / 2), 4);
-    // bf16 pieces per operand; 0 = fp32 kernel.  An input scale rides in the staging of the six-product fp32-storage kernels only.
-    p.bf16x6 = (plan.bf16x6 && (!iscale || isc_in_staging(d)) && !(plan.packed && (iscale || wmod_s))) ? math_pieces(d->math) : 0;
+    p.bf16x6 = ch.pieces;            // bf16 pieces per operand (16-bit storage: 1, the stored element is the operand); 0 = fp32 kernel
     p.io = d->io_dtype;
-    if (p.io != IO_F32) {
-        PASTA_CHECK(p.bf16x6, "conv2d: no 16-bit-storage kernel for this shape (pasta_conv2d_plan tells beforehand)");
-        p.bf16x6 = 1;           // the stored element is the operand
-    }
+    PASTA_CHECK(p.io == IO_F32 || p.bf16x6, "conv2d: no 16-bit-storage kernel for this shape (pasta_conv2d_plan tells beforehand)");
     p.rows = 0; p.rows_d0 = 0; p.rows_rev = 0;
 
     const float wscale = d->wscale == 0.f ? 1.f : d->wscale;
@@ -777,9 +761,8 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
         }
     }
     p.koff = nullptr;
-    static const int xcd_order = getenv("PASTA_XCD_ORDER") ? atoi(getenv("PASTA_XCD_ORDER")) : 1;
-    p.xcd_order = xcd_order;
-    const bool packed = plan.packed && p.bf16x6 && !iscale && !wmod_s;
+    p.xcd_order = 1;
+    const bool packed = ch.packed;
     int pk_kh = d->kh, pk_kw = d->kw, pk_tr = d->transposed, pk_flip = d->flip;
     if (packed) {
         // K = (input channel, tap) pairs: one pseudo-tap over C_in kh kw "channels" of a zero-padded input (workspace: ... | offsets | copy)
@@ -807,9 +790,8 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
         PASTA_CHECK(p.bf16x6 == NP_F16X3 && p.io == IO_F32 && !packed && !wmod_s && !p.x2, "conv2d: w_prepacked with a launch pasta_conv2d_pack_pair does not serve");
     } else {   // pack weights (times wscale)
         if (p.bf16x6 == NP_F16X3 && p.io == IO_F32) {       // two fp16 pieces, one scale per output row found on the way
-            static const int pack_xcd = getenv("PASTA_PACK_XCD") ? atoi(getenv("PASTA_PACK_XCD")) : 1;      // A/B switch: 0 = row = workgroup index
             tu_pack_weights_f16x3(w, workspace, ws_rowinv, p.G, p.Ig, p.Og, p.Ig_pad, p.Og_pad, pk_kh, pk_kw, pk_tr, pk_flip, wscale, wmod_s, wmod_d,
-                                  (p.Og_pad & 63) == 0 ? pack_xcd : 0, s);
+                                  (p.Og_pad & 63) == 0 ? 1 : 0, s);
         }
         else if (p.bf16x6)
             tu_pack_weights_bf16(w, workspace, p.G, p.Ig, p.Og, p.Ig_pad, p.Og_pad, pk_kh, pk_kw, pk_tr, pk_flip, wscale, p.io == IO_F16 ? 1 : 0, wmod_s, wmod_d, s);
@@ -817,7 +799,7 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
             tu_pack_weights_f32(w, (float*)workspace, p.G, p.Ig, p.Og, p.Ig_pad, p.Og_pad, d->kh, d->kw, d->transposed, d->flip, wscale, wmod_s, wmod_d, s);
     }
 
-    if (conv1x1_ok(p, d->kh, d->kw, d->stride, d->pad_h, d->pad_w)) {
+    if (ch.kernel == 9) {
         tu_conv1x1(p, s);           // conv2d and conv_transpose2d coincide for 1x1 / stride 1 (the packing kernel reads either weight layout)
         return launch_status("conv2d");
     }
@@ -827,7 +809,7 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
         p.P = d->OH; p.Q = d->OW; p.oy0 = 0; p.ox0 = 0; p.osy = 1; p.osx = 1; p.isy = d->stride; p.isx = d->stride;
         p.T = 1; p.tap_dy[0] = 0; p.tap_dx[0] = 0; p.tap_slab[0] = 0;      // the window's corner in the padded plane; the taps are in koff
         p.ncls = 1; p.cls[0] = {p.P, p.Q, 0, 0, 1, 0};
-        launch_fwd_bf16x6(tile == T128x128, p, s);
+        launch_fwd_bf16x6(tile == T128x128, false, p, s);
     } else if (!d->transposed) {
         p.P = d->OH; p.Q = d->OW; p.oy0 = 0; p.ox0 = 0; p.osy = 1; p.osx = 1; p.isy = d->stride; p.isx = d->stride;
         p.T = p.KK;
@@ -837,27 +819,27 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
                 p.tap_dy[t] = r - d->pad_h; p.tap_dx[t] = c - d->pad_w; p.tap_slab[t] = t;
             }
         p.ncls = 1; p.cls[0] = {p.P, p.Q, 0, 0, p.T, 0};
-        if (conv3x3s2_ok(p, d->kh, d->kw, d->stride, d->pad_h, d->pad_w, d->transposed)) {
+        if (ch.kernel == 10) {
             tu_conv3x3s2(p, s);
             return launch_status("conv2d");
         }
         detect_tap_rows(p, p.T);
-        dispatch_fwd(tile, p, s);
+        launch_lattice(ch, p, s);
     } else {
         // output row oy = iy*u - pad + r.  For parity class a (oy = a + u*pp): taps r with (a + pad - r) % u == 0,
         // input row = pp + (a + pad - r)/u.
         const int u = d->stride;
         p.osy = u; p.osx = u; p.isy = 1; p.isx = 1;
-        if (t2_launch_ok(d, p.bf16x6, p.ksplit, launch_flags_of(iscale, oscale, ep))) {
+        if (ch.tl == TL_ONEPASS) {
             p.x2 = p.partial;                             // (no K slices: the region behind the packed weights holds the gathered column)
             tu_conv_t2(p, s);                             // the whole lattice, remainder row and column included, in one launch
             return launch_status("conv2d");
         }
-        if (pair_launch_ok(d, p.bf16x6, p.ksplit, tile, pair_plain(launch_flags_of(iscale, oscale, ep)))) {
+        if (ch.tl == TL_PAIR) {
             launch_transposed_pairs(d, p, tile, s, EdgeWeights{w, wmod_s, wmod_d, wscale, d->flip});
             return launch_status("conv2d");
         }
-        const bool merged = merged_classes(d, p.bf16x6 != 0);
+        const bool merged = ch.tl == TL_MERGED;
         int ntap = 0;
         p.ncls = 0;
         for (int a = 0; a < u && a < d->OH; a++)
@@ -884,10 +866,10 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
                 } else {
                     p.ncls = 1; p.cls[0] = {p.P, p.Q, a, b, p.T, 0};
                     detect_tap_rows(p, p.T);
-                    dispatch_fwd(tile, p, s);
+                    launch_lattice(ch, p, s);
                 }
             }
-        if (merged) dispatch_fwd(tile, p, s);
+        if (merged) launch_lattice(ch, p, s);
     }
     if (p.ksplit > 1) {
         const int64_t numel = (int64_t)d->N * d->C_out * d->OH * d->OW;
@@ -933,22 +915,38 @@ static bool wgrad_1x1_bf16x6(const pasta_conv_desc* d, const WgradPlan& w) {
            ((int64_t)P * Q) % 32 == 0 && (Ig >= 16 || Og >= 16) && w.kp == 32 && w.WA == w.WB &&
            d->H == d->OH && d->W == d->OW && (int64_t)w.chunks_total == (int64_t)d->N * P * Q / 32;
 }
+
+// Everything the planner reports and the launch does for a weight gradient of d.
+struct WgradChoice {
+    int kernel;             // plan kernel id 0 - 6 (include/pasta_hip.h)
+    WgradSmallPlan small;   // kernels 1 and 5
+    int fewcin_ks;          // kernel 5: K slices
+    WgradPlan w;            // kernels 0, 2, 3, 4 and 6
+};
+
+// The one place that chooses a weight-gradient kernel.  ks_multiple: as plan_wgrad's (pasta_conv2d_wgrad_modulated: the batch size).
+static WgradChoice choose_wgrad(const pasta_conv_desc* d, int ks_multiple) {
+    WgradChoice c{};
+    c.small = plan_wgrad_small(d);
+    c.fewcin_ks = plan_wgrad1x1_fewcin(d, c.small);
+    if (c.small.use) {
+        c.kernel = c.fewcin_ks ? 5 : 1;
+        return c;
+    }
+    const int Ig = d->C_in / d->groups, Og = d->C_out / d->groups;
+    c.w = d->transposed ? plan_wgrad(d->N, d->H, d->W, d->groups, Ig, Og, d->kh, d->kw, d->stride, ks_multiple, wgrad_wide16(d))
+                        : plan_wgrad(d->N, d->OH, d->OW, d->groups, Og, Ig, d->kh, d->kw, d->stride, ks_multiple, wgrad_wide16(d));
+    c.kernel = wgrad_bf16x6(d, c.w) ? 2 : wgrad_s2_bf16x6(d, c.w) ? (wgrad_pieces_ok(d, c.w) ? 6 : 3) : wgrad_1x1_bf16x6(d, c.w) ? 4 : 0;
+    return c;
+}
+// The split kernels: 3x3 stride 1, 3x3 stride 2 (x as operand pieces included), pointwise.
+static bool wgrad_split(int kernel) { return kernel == 2 || kernel == 3 || kernel == 4 || kernel == 6; }
 }  // namespace pasta
 
 extern "C" int pasta_conv2d_wgrad_plan(const pasta_conv_desc* d, int* kernel) {
     using namespace pasta;
     if (int e = check_desc(d, "conv2d_wgrad_plan")) return e;
-    const int Ig = d->C_in / d->groups, Og = d->C_out / d->groups;
-    int k = 0;
-    if (plan_wgrad1x1_fewcin(d, plan_wgrad_small(d))) k = 5;
-    else if (plan_wgrad_small(d).use) k = 1;
-    else {
-        const WgradPlan w = d->transposed ? plan_wgrad(d->N, d->H, d->W, d->groups, Ig, Og, d->kh, d->kw, d->stride, 1, wgrad_wide16(d))
-                                          : plan_wgrad(d->N, d->OH, d->OW, d->groups, Og, Ig, d->kh, d->kw, d->stride, 1, wgrad_wide16(d));
-        if (wgrad_bf16x6(d, w)) k = 2;
-        else if (wgrad_s2_bf16x6(d, w)) k = wgrad_pieces_ok(d, w) ? 6 : 3;
-        else if (wgrad_1x1_bf16x6(d, w)) k = 4;
-    }
+    const int k = choose_wgrad(d, 1).kernel;
     if (kernel) *kernel = k;
     if (d->x_layout == PASTA_LAYOUT_PIECES16 && k != 6)
         return fail("conv2d_wgrad: x_layout = PASTA_LAYOUT_PIECES16 is served by the 3x3 stride-2 weight gradient only (conv2d, pad 0, fp32 dy, PASTA_MATH_F16X3, "
@@ -961,23 +959,18 @@ extern "C" int pasta_conv2d_wgrad_plan(const pasta_conv_desc* d, int* kernel) {
 extern "C" int64_t pasta_conv2d_wgrad_workspace(const pasta_conv_desc* d) {
     using namespace pasta;
     if (check_desc(d, "conv2d_wgrad_workspace")) return -1;
-    const int Ig = d->C_in / d->groups, Og = d->C_out / d->groups;
-    const WgradSmallPlan ws = plan_wgrad_small(d);
-    if (ws.use) return (WS_AMAX_FLOATS + ws.slab_floats) * (int64_t)sizeof(float);
-    const WgradPlan w = d->transposed ? plan_wgrad(d->N, d->H, d->W, d->groups, Ig, Og, d->kh, d->kw, d->stride, 1, wgrad_wide16(d))
-                                      : plan_wgrad(d->N, d->OH, d->OW, d->groups, Og, Ig, d->kh, d->kw, d->stride, 1, wgrad_wide16(d));
-    return (WS_AMAX_FLOATS + w.slab_floats) * (int64_t)sizeof(float);
+    const WgradChoice c = choose_wgrad(d, 1);
+    return (WS_AMAX_FLOATS + (c.small.use ? c.small.slab_floats : c.w.slab_floats)) * (int64_t)sizeof(float);
 }
 
 namespace pasta {
 // Can the weight gradient of a MODULATED convolution come from the plain kernels with sample-aligned K slices (pasta_conv2d_wgrad_modulated)?
 // The main split kernels only (3x3 stride 1 / stride 2, pointwise), fp32 storage, one group, up to 32 samples that the chunk count divides into.
 static bool wgrad_modulated_ok(const pasta_conv_desc* d, WgradPlan* out) {
-    if (d->groups != 1 || d->io_dtype != PASTA_F32 || d->N < 1 || d->N > 32 || plan_wgrad_small(d).use) return false;
-    const int Ig = d->C_in, Og = d->C_out;
-    const WgradPlan w = d->transposed ? plan_wgrad(d->N, d->H, d->W, 1, Ig, Og, d->kh, d->kw, d->stride, d->N, wgrad_wide16(d))
-                                      : plan_wgrad(d->N, d->OH, d->OW, 1, Og, Ig, d->kh, d->kw, d->stride, d->N, wgrad_wide16(d));
-    if (!(wgrad_bf16x6(d, w) || wgrad_s2_bf16x6(d, w) || (wgrad_1x1_bf16x6(d, w) && !(w.TR == 3 && w.TS == 3) && w.TS != 7 && w.TS != 4))) return false;
+    if (d->groups != 1 || d->io_dtype != PASTA_F32 || d->N < 1 || d->N > 32) return false;
+    const WgradChoice c = choose_wgrad(d, d->N);
+    if (!wgrad_split(c.kernel)) return false;
+    const WgradPlan& w = c.w;
     const int P = d->transposed ? d->H : d->OH;
     const int chh = w.kp >> w.cw_log2;
     if (P % chh != 0 || w.chunks_total % d->N != 0 || w.ksplit > w.chunks_total) return false;     // whole chunks per sample, at least one chunk per slice
@@ -1028,14 +1021,15 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
     float* const ws_amax = (float*)workspace;                         // [2][AMAX_PARTS]: x, dy
     workspace = (float*)workspace + WS_AMAX_FLOATS;                  // the partial slabs follow
 
-    const WgradSmallPlan ws = mod_s ? WgradSmallPlan{} : plan_wgrad_small(d);
+    const WgradChoice c = choose_wgrad(d, mod_s ? d->N : 1);      // (modulated: never the small-cin kernels -- the workspace check above)
+    const WgradSmallPlan& ws = c.small;
     if (d->x_layout == PASTA_LAYOUT_PIECES16) {
-        int k = 0;
-        if (int e = pasta_conv2d_wgrad_plan(d, &k)) return e;
+        if (int e = pasta_conv2d_wgrad_plan(d, nullptr)) return e;
         PASTA_CHECK(!mod_s && d->x_amax, "conv2d_wgrad: x_layout = PASTA_LAYOUT_PIECES16 needs x_amax (the row pasta_blur_pieces wrote) and plain weights");
     }
-    PASTA_CHECK(d->io_dtype == PASTA_F32 || !ws.use || plan_wgrad1x1_fewcin(d, ws), "conv2d_wgrad: no 16-bit-storage kernel for this shape (pasta_conv2d_wgrad_plan tells beforehand)");
-    if (const int fks = plan_wgrad1x1_fewcin(d, ws)) {
+    PASTA_CHECK(d->io_dtype == PASTA_F32 || c.kernel == 5 || wgrad_split(c.kernel), "conv2d_wgrad: no 16-bit-storage kernel for this shape (pasta_conv2d_wgrad_plan tells beforehand)");
+    if (c.kernel == 5) {
+        const int fks = c.fewcin_ks;
         // few input channels, 1x1: one bandwidth-bound pass over dy with plain FMAs (conv_wgrad_f32.h)
         const int64_t total = (int64_t)d->N * ((int64_t)d->H * d->W / 4);
         const int64_t per = (total + fks - 1) / fks;
@@ -1045,7 +1039,7 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
         tu_wgrad_smallcin_reduce((const float*)workspace, dw, fks, d->C_out, ws.bprime, a_pad, bpad, d->wscale == 0.f ? 1.f : d->wscale, s);
         return launch_status("conv2d_wgrad(few-channel 1x1)");
     }
-    if (ws.use) {
+    if (c.kernel == 1) {
         WgradSmallParams q;
         q.S = dy; q.L = x; q.slab = (float*)workspace;
         q.N = d->N; q.Ag = d->C_out; q.P = d->OH; q.Q = d->OW; q.Bg = Ig; q.LH = d->H; q.LW = d->W;
@@ -1070,13 +1064,12 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
         p.S = x;  p.SC = d->C_in;  p.P = d->H; p.Q = d->W; p.Ag = Ig;
         p.L = dy; p.LC = d->C_out; p.LH = d->OH; p.LW = d->OW; p.Bg = Og;
     }
-    const WgradPlan w = plan_wgrad(p.N, p.P, p.Q, p.G, p.Ag, p.Bg, p.kh, p.kw, p.st, mod_s ? d->N : 1, wgrad_wide16(d));
+    const WgradPlan& w = c.w;
     p.cw_log2 = w.cw_log2; p.rows_total = w.rows_total; p.qblocks = w.qblocks; p.chunks_total = w.chunks_total;
     p.ksplit = w.ksplit; p.a_tiles = w.a_tiles; p.b_tiles = w.b_tiles; p.tap_groups_r = w.tgr; p.tap_groups_s = w.tgs;
     // measured (profiles/r3_ab_wgrad_xcd.txt): 256 -> 128 at 128^2 298.6 -> 303.4 TFLOP/s, stride 2 at 256^2 143 -> 154, at 257^2 140.7 -> 143.4,
     // every other shape within 0.5 %
-    static const int wgrad_xcd = getenv("PASTA_WGRAD_XCD") ? atoi(getenv("PASTA_WGRAD_XCD")) : 1;
-    p.xcd_order = wgrad_xcd;
+    p.xcd_order = 1;
     p.l_pieces = d->x_layout == PASTA_LAYOUT_PIECES16;
     PASTA_CHECK((int64_t)w.chunks_total * (w.ksplit + 1) < (1ll << 32), "conv2d_wgrad: %d chunks x %d K slices overflow the kernels' 32-bit slice bounds", w.chunks_total, w.ksplit);
     PASTA_CHECK(w.lds_bytes <= 160 * 1024, "conv2d_wgrad: LDS footprint %zu too large", w.lds_bytes);
@@ -1086,19 +1079,16 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
     PASTA_CHECK(blocks <= INT32_MAX, "conv2d_wgrad: grid too large");
     const int np = p.io != IO_F32 ? 1 : math_pieces(d->math);          // bf16 pieces per operand of the split-bf16 kernels (NP_F16X3: fp16 pieces)
     p.s_amax = p.l_amax = nullptr;
-    if (np == NP_F16X3 && (wgrad_bf16x6(d, w) || wgrad_s2_bf16x6(d, w) || (wgrad_1x1_bf16x6(d, w) && !(w.TR == 3 && w.TS == 3) && w.TS != 7 && w.TS != 4))) {
+    if (np == NP_F16X3 && wgrad_split(c.kernel)) {
         const float* xa = d->x_amax; const float* ya = d->dy_amax;
         if (!xa) { if (int e = tensor_amax(x, (int64_t)d->N * d->C_in * d->H * d->W, PASTA_F32, ws_amax, s)) return e; xa = ws_amax; }      // (pieces layout: given, checked above)
         if (!ya) { if (int e = tensor_amax(dy, (int64_t)d->N * d->C_out * d->OH * d->OW, PASTA_F32, ws_amax + AMAX_PARTS, s)) return e; ya = ws_amax + AMAX_PARTS; }
         p.s_amax = d->transposed ? xa : ya;
         p.l_amax = d->transposed ? ya : xa;
     }
-    PASTA_CHECK(p.io == IO_F32 || wgrad_bf16x6(d, w) || wgrad_s2_bf16x6(d, w) || (wgrad_1x1_bf16x6(d, w) && !(w.TR == 3 && w.TS == 3) && w.TS != 7 && w.TS != 4),
-                "conv2d_wgrad: no 16-bit-storage kernel for this shape (pasta_conv2d_wgrad_plan tells beforehand)");
-    const bool split1x1 = wgrad_1x1_bf16x6(d, w) && !(w.TR == 3 && w.TS == 3) && w.TS != 7 && w.TS != 4;
-    if (wgrad_bf16x6(d, w)) tu_wgrad3x3(np, p, blocks, s);
-    else if (wgrad_s2_bf16x6(d, w)) tu_wgrad3x3s2(np, p, blocks, s);
-    else if (split1x1) tu_wgrad1x1(np, w.WA, p, blocks, s);
+    if (c.kernel == 2) tu_wgrad3x3(np, p, blocks, s);
+    else if (c.kernel == 3 || c.kernel == 6) tu_wgrad3x3s2(np, p, blocks, s);
+    else if (c.kernel == 4) tu_wgrad1x1(np, w.WA, p, blocks, s);
     else if (int e = tu_wgrad_f32(w.TR, w.TS, w.WA, w.pipe, w.kp, p, blocks, w.lds_bytes, s)) return e;
     if (mod_s) {
         // slices [n m, (n + 1) m) hold sample n's gradient with respect to the modulated weight: dw = sum_n s[n, i] (.), ds[n, i] = sum_{o, taps} w (.)

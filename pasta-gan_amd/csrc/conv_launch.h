@@ -22,15 +22,14 @@ void tu_fwd_f32(FwdTile t, const ConvFwdParams& p, hipStream_t s);
 // conv_tu_fwd_base_{128,64}.hip: conv_fwd_bf16x6_kernel (q: o_tiles set, grid computed by the caller)
 void tu_fwd_base_128(const ConvFwdParams& q, dim3 grid, hipStream_t s);
 void tu_fwd_base_64(const ConvFwdParams& q, dim3 grid, hipStream_t s);
-// conv_tu_fwd_rows_{128,64}.hip: conv_fwd_rows_bf16x6_kernel; false = the lattice is not made of whole row segments (the base kernel takes it)
-bool tu_fwd_rows_128(const ConvFwdParams& q, dim3 grid, hipStream_t s);
-bool tu_fwd_rows_64(const ConvFwdParams& q, dim3 grid, hipStream_t s);
+// conv_tu_fwd_rows_{128,64}.hip: conv_fwd_rows_bf16x6_kernel (the lattice is made of whole row segments: the planner checked)
+void tu_fwd_rows_128(const ConvFwdParams& q, dim3 grid, hipStream_t s);
+void tu_fwd_rows_64(const ConvFwdParams& q, dim3 grid, hipStream_t s);
 void tu_fwd_pair_128(const ConvFwdParams& p, hipStream_t s);      // parity-pair mode (p.bf16x6: 3 or NP_F16X3)
 void tu_fwd_pair_64(const ConvFwdParams& p, hipStream_t s);
 
 // conv_tu_rows2d_*.hip: conv_fwd_rows2d_bf16x6_kernel, one unit per tile shape (q.rows_y0 set by the caller)
 void tu_rows2d_wide(const ConvFwdParams& q, hipStream_t s);       // <128, 256, 8, ., IO_F32, ., 512>: the dominant kernel
-void tu_rows2d_wide_glds(const ConvFwdParams& w8, dim3 grid8, hipStream_t s);     // conv_tu_rows2d_wide_glds.hip: the same with the weights by LDS-DMA
 void tu_rows2d_wide_pieces(const ConvFwdParams& q, hipStream_t s);       // conv_tu_rows2d_wide_xp.hip: x as PASTA_LAYOUT_PIECES16
 void tu_rows2d_128_r4(const ConvFwdParams& q, hipStream_t s);
 void tu_rows2d_128_r2(const ConvFwdParams& q, hipStream_t s);

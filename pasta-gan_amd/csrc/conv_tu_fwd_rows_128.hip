@@ -3,7 +3,7 @@
 #include "conv_fwd_bf16x6.h"
 
 namespace pasta {
-bool tu_fwd_rows_128(const ConvFwdParams& q, dim3 grid, hipStream_t s) { return launch_fwd_rows_any<128, 128>(q, grid, s); }
+void tu_fwd_rows_128(const ConvFwdParams& q, dim3 grid, hipStream_t s) { launch_fwd_rows_any<128, 128>(q, grid, s); }
 void tu_fwd_pair_128(const ConvFwdParams& p, hipStream_t s) {
     if (p.bf16x6 == NP_F16X3) launch_fwd_pair<128, 128, NP_F16X3>(p, s); else launch_fwd_pair<128, 128>(p, s);
 }

@@ -592,8 +592,7 @@ __global__ __launch_bounds__(256) void wgrad1x1_fewcin_kernel(const void* __rest
 
 // Does the few-channel pointwise kernel take this weight gradient, and with how many K slices (<= the slab the small-cin plan reserved)?
 static int plan_wgrad1x1_fewcin(const pasta_conv_desc* d, const WgradSmallPlan& ws) {
-    static const bool enabled = !(getenv("PASTA_WGRAD_FEWCIN") && getenv("PASTA_WGRAD_FEWCIN")[0] == '0');         // A/B switch
-    if (!enabled || !ws.use || d->kh != 1 || d->kw != 1 || d->pad_h || d->pad_w || d->C_in > 8) return 0;      // (any storage type: round 5)
+    if (!ws.use || d->kh != 1 || d->kw != 1 || d->pad_h || d->pad_w || d->C_in > 8) return 0;      // (any storage type: round 5)
     const int64_t hw = (int64_t)d->H * d->W;
     if (hw % 4 || d->OH != d->H || d->OW != d->W) return 0;
     int64_t ks = (int64_t)d->N * (hw / 4) / (256 * 8);          // at least eight trips per thread

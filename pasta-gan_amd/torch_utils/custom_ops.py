@@ -43,7 +43,7 @@ def _sources():
 
 def _digest(sources, extra_flags=()):
     h = hashlib.md5()
-    # the compile flags are part of what the library IS: a -DPASTA_ABLATE=... build must never carry the default stamp
+    # the compile flags are part of what the library IS: a build with extra -D flags must never carry the default stamp
     h.update(repr([str(f) for f in extra_flags]).encode())
     extra = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith('.h')]
     extra.append(os.path.join(_INCLUDE, 'pasta_hip.h'))
@@ -95,7 +95,7 @@ def _unit_weight(src):
 
 def _compile_and_link(hipcc, sources, lib_path, stamp, digest, verbose, extra_flags):
     flags = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-contract=fast', '-I', _INCLUDE] + list(extra_flags)
-    # one hipcc per translation unit, at most one per core at a time, the large units first (the convolution family is thirteen
+    # one hipcc per translation unit, at most one per core at a time, the large units first (the convolution family is eighteen
     # units, csrc/conv_launch.h: a forced build takes about a minute on eight cores)
     objs = [os.path.join(_OBJDIR, os.path.basename(src)[:-4] + '.o') for src in sources]
     queue = sorted(zip(sources, objs), key=lambda so: -_unit_weight(so[0]))

@@ -66,15 +66,8 @@ def _out_hw(cfg, h, w, kh, kw):
 
 IO_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 3}      # pasta_conv_desc.io_dtype (PASTA_F32 / _F16 / _BF16)
 
-_SCOPE = _os.environ.get('PASTA_F16X3_SCOPE', 'all')       # diagnostic: 'fwd' / 'wgrad' = the three-product arithmetic for those launches only
-
-def _desc(cfg, x_shape, c_out, oh, ow, kh, kw, io=torch.float32, kind='fwd'):
+def _desc(cfg, x_shape, c_out, oh, ow, kh, kw, io=torch.float32):
     n, c_in, h, w = x_shape
-    if _SCOPE != 'all' and _SCOPE != kind and conv_math in ('default', 'f16x3'):
-        d = custom_ops.ConvDesc(N=n, C_in=c_in, H=h, W=w, C_out=c_out, OH=oh, OW=ow, kh=kh, kw=kw, stride=cfg.stride,
-                                pad_h=cfg.pad_h, pad_w=cfg.pad_w, groups=cfg.groups, transposed=int(cfg.transposed), flip=0,
-                                math=MATH_CODES['bf16x6'], wscale=float(cfg.wgain), io_dtype=IO_CODES[io])
-        return d
     return custom_ops.ConvDesc(N=n, C_in=c_in, H=h, W=w, C_out=c_out, OH=oh, OW=ow, kh=kh, kw=kw, stride=cfg.stride,
                                pad_h=cfg.pad_h, pad_w=cfg.pad_w, groups=cfg.groups, transposed=int(cfg.transposed), flip=0,
                                math=MATH_CODES[conv_math], wscale=float(cfg.wgain), io_dtype=IO_CODES[io])
@@ -333,7 +326,7 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
 # gradient, and its magnitude is bounded by its input's: it can write its output once as the fp16 pieces h | l' of the three-product
 # arithmetic (16-byte units of eight channels, [N][C / 8][H][piece][W]), and both consumers copy pieces instead of fetching fp32 with eight
 # channel-strided loads per unit and splitting it -- in every launch that touches the tensor.
-_PIECES = _os.environ.get('PASTA_PIECES', '1') != '0'       # A/B switch: 0 = fp32 blurred tensor, as before
+_PIECES = True       # False: the blurred tensor in fp32, as the reference (tests compare the two)
 _pieces_cache = {}
 
 def pieces_available(x, f, weight, pad4, groups=1):
@@ -341,7 +334,7 @@ def pieces_available(x, f, weight, pad4, groups=1):
     weight-gradient kernel 6 of the planners)?  fp32 tensors, the default arithmetic, a 4 x 4 filter, whole channel octets."""
     if not (_PIECES and x.device.type == 'cuda' and x.dtype == torch.float32 and weight.dtype == torch.float32 and conv_math in ('default', 'f16x3')
             and groups == 1 and f is not None and f.ndim == 2 and tuple(f.shape) == (4, 4) and x.ndim == 4 and x.shape[1] % 8 == 0
-            and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1] and x.numel() > 0 and _SCOPE == 'all'):
+            and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == x.shape[1] and x.numel() > 0):
         return False
     px0, px1, py0, py1 = pad4
     n, c, h, wd = (int(v) for v in x.shape)
@@ -409,13 +402,12 @@ def pieces_pack(x, x_amax=None):
 # conv_mlp batches per generator pass, networks.py Spade_ResBlockV2) is packed ONCE and every forward launch copies the pieces (plan kernel 7
 # with x_layout = PASTA_LAYOUT_PIECES16: +10 % on 256 -> 384 at 128 x 128, profiles/r5_s1_pieces_microbench.txt).  The pieces ride on the tensor
 # object, keyed by version and address like the maxima rows; the weight gradients keep reading the fp32 tensor.
-_SHARED_PIECES = _os.environ.get('PASTA_SHARED_PIECES', '1') != '0'       # A/B switch: 0 = every launch splits the fp32 tensor itself
 _shared_cache = {}
 
 def _shared_pieces_ok(x, weight, cfg, has_epilogue):
     """Does the eight-wave stride-1 tile kernel take conv2d(x, weight) with x as pieces?"""
-    if not (_SHARED_PIECES and _PIECES and x.device.type == 'cuda' and x.dtype == torch.float32 and weight.dtype == torch.float32
-            and conv_math in ('default', 'f16x3') and _SCOPE == 'all' and cfg.groups == 1 and cfg.stride == 1 and not cfg.transposed
+    if not (_PIECES and x.device.type == 'cuda' and x.dtype == torch.float32 and weight.dtype == torch.float32
+            and conv_math in ('default', 'f16x3') and cfg.groups == 1 and cfg.stride == 1 and not cfg.transposed
             and tuple(weight.shape[2:]) == (3, 3) and x.ndim == 4 and x.shape[1] % 8 == 0):
         return False
     n, c, h, wd = (int(v) for v in x.shape)
@@ -432,8 +424,8 @@ def _shared_pieces_ok(x, weight, cfg, has_epilogue):
 
 def share_pieces(x):
     """Pack ``x`` for the stride-1 3x3 layers that will read it (a no-op where none of them could use the pieces); returns ``x``."""
-    if (_SHARED_PIECES and _PIECES and x.device.type == 'cuda' and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] % 8 == 0 and x.shape[1] >= 16
-            and conv_math in ('default', 'f16x3') and _SCOPE == 'all' and not x.is_inference() and x.is_contiguous()
+    if (_PIECES and x.device.type == 'cuda' and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] % 8 == 0 and x.shape[1] >= 16
+            and conv_math in ('default', 'f16x3') and not x.is_inference() and x.is_contiguous()
             and not torch.cuda.is_current_stream_capturing() and _shared_lookup(x) is None):
         pieces, bound, shape = pieces_pack(x)
         try:
@@ -506,7 +498,7 @@ def _launch_wgrad_pieces(pieces_x, dy, cfg, w_shape, pieces, out_dtype=None):
     out_dtype = dy.dtype if out_dtype is None else out_dtype
     dy = _f32(dy).contiguous()
     dw = torch.empty(list(w_shape), dtype=torch.float32, device=dy.device)
-    desc = _desc(cfg, (n, c_in, h, wd), dy.shape[1], dy.shape[2], dy.shape[3], w_shape[2], w_shape[3], kind='wgrad')
+    desc = _desc(cfg, (n, c_in, h, wd), dy.shape[1], dy.shape[2], dy.shape[3], w_shape[2], w_shape[3])
     desc.x_layout, desc.x_amax = 1, bound.data_ptr()
     amax_dy = tensor_amax(dy)
     desc.dy_amax = amax_dy.data_ptr()
@@ -543,7 +535,7 @@ def _launch_wgrad(x, dy, cfg, w_shape, out_dtype=None, x_amax=None):
         io = x.dtype
     x = x.contiguous() if io is not torch.float32 else _f32(x).contiguous()
     dy = dy.contiguous() if io is not torch.float32 else _f32(dy).contiguous()
-    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, io, kind='wgrad')
+    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, io)
     lib = _native.lib()
     nbytes = lib.pasta_conv2d_wgrad_workspace(ctypes.byref(desc))
     if nbytes < 0:
@@ -581,12 +573,12 @@ def _grad_cfg(cfg, x_hw, y_hw, kh, kw):
 # Every forward convolution whose input needs a gradient is followed, in the backward pass, by the same weights packed the other way round
 # (transposed and mirrored): 120 of the 310 packing launches of a training step.  The forward packs BOTH orientations with one kernel and the
 # autograd node carries the second workspace to its backward.
-_PACK_PAIR = _os.environ.get('PASTA_PACK_PAIR', '1') != '0'       # A/B switch: 0 = every launch packs for itself
+_PACK_PAIR = True       # False: every launch packs for itself (tests compare the two)
 
 def _pack_pair(x, w, cfg):
     """-> (workspace of the forward launch, workspace of its input-gradient launch), both with the weights packed, or (None, None)."""
     if not (_PACK_PAIR and x.device.type == 'cuda' and x.dtype == torch.float32 and w.dtype == torch.float32 and conv_math in ('default', 'f16x3')
-            and _SCOPE == 'all' and x.ndim == 4 and w.ndim == 4 and x.numel() > 0 and not torch.cuda.is_current_stream_capturing()):
+            and x.ndim == 4 and w.ndim == 4 and x.numel() > 0 and not torch.cuda.is_current_stream_capturing()):
         return None, None
     kh, kw = int(w.shape[2]), int(w.shape[3])
     n, c_in, h, wd = (int(v) for v in x.shape)
@@ -952,7 +944,7 @@ def modulated_conv2d_forward(x, weight, styles, dcoefs=None, stride=1, padding=0
 # instead of scale_planes (a read and a write of the activation) + a scan of x * s for its operand scale + scale_planes of the input
 # gradient + plane_dot(dx, x) (two reads): seven passes over the activation per modulated layer.  
 
-_MODCONV = _os.environ.get('PASTA_MODCONV_TRAIN', '1') != '0'         # A/B switch: 0 = scale_planes + the plain convolution, as before
+_MODCONV = True         # False: scale_planes + the plain convolution, as the reference (tests compare the two)
 _modconv_cache = {}
 
 def modconv_available(x, weight, styles, stride=1, padding=0, transposed=False):
@@ -967,7 +959,7 @@ def modconv_available(x, weight, styles, stride=1, padding=0, transposed=False):
         cfg = _Cfg((False, 1, ph, pw, 0, 0, 1, 1.0))
         kh, kw = int(weight.shape[2]), int(weight.shape[3])
         oh, ow = _out_hw(cfg, x.shape[2], x.shape[3], kh, kw)
-        desc = _desc(cfg, x.shape, int(weight.shape[0]), oh, ow, kh, kw, kind='wgrad')
+        desc = _desc(cfg, x.shape, int(weight.shape[0]), oh, ow, kh, kw)
         hit = _native.lib().pasta_conv2d_wgrad_modulated_workspace(ctypes.byref(desc)) >= 0
         _modconv_cache[key] = hit
     return hit
@@ -978,7 +970,7 @@ def _launch_wgrad_modulated(x, dy, cfg, styles, w, x_amax=None):
     kh, kw = int(w.shape[2]), int(w.shape[3])
     x, dy = _f32(x).contiguous(), _f32(dy).contiguous()
     styles, w32 = _f32(styles).contiguous(), _f32(w).contiguous()
-    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, kind='wgrad')
+    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw)
     lib = _native.lib()
     nbytes = lib.pasta_conv2d_wgrad_modulated_workspace(ctypes.byref(desc))
     if nbytes < 0:

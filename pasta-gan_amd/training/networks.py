@@ -212,9 +212,6 @@ def spade_modulate(x, gamma, beta, eps=1e-5, relu_gain=None, clamp=None, shared=
 
 #----------------------------------------------------------------------------
 
-import os as _os
-_GARMENT_FUSED = _os.environ.get('PASTA_GARMENT_FUSED', '1') != '0'         # A/B switch: 0 = the reference's element-wise passes + torch.cat
-
 class _GarmentFeat(torch.autograd.Function):
     """``cat([fill(feat_u), fill(feat_l)], dim=1)`` with ``fill(x) = x * (1 - hole) + (sum_hw(x * valid) / count) * hole`` -- the tail of
     ``get_spade_feat`` for the upper and the lower garment (networks.py:5777-5800, 5836) -- by ``pasta_masked_mean_fill``: one workgroup
@@ -265,8 +262,6 @@ class _GarmentFeat(torch.autograd.Function):
                     grads.append(dx if ctx.needs_input_grad[4 * k] else None)
         return grads[0], None, None, None, grads[1], None, None, None
 
-_MBA_AMAX = _os.environ.get('PASTA_MBA_AMAX', '1') != '0'         # A/B switch: 0 = the consumer scans the output of mod_bias_act
-
 class _ModBiasAct(torch.autograd.Function):
     """Tail of a modulated-convolution layer in one pass: ``clamp(act(u * d[n,c] + noise * strength + b[c]) * gain)``
     (the demodulation + noise of modulated_conv2d, networks.py:77-82, and SynthesisLayer's bias_act, :313-314).
@@ -286,7 +281,7 @@ class _ModBiasAct(torch.autograd.Function):
         # producer maxima for the large planes (one commit per 4096-element workgroup, most of them skipped by the look at the slot): the layer's
         # output is the operand of the next modulated convolution, whose launch would scan it (round 4: 150.35 -> 150.0 ms same box; small
         # tensors keep the scan: profiles/r4_ab_mba_amax.txt)
-        row = _native.amax_slot(y) if (_MBA_AMAX and y.numel() >= 1 << 22) else None
+        row = _native.amax_slot(y) if y.numel() >= 1 << 22 else None
         with torch.cuda.device(u.device):
             st = _native.lib().pasta_mod_bias_act(_native.ptr(u), _native.ptr(d), _native.ptr(noise), _native.ptr(strength), _native.ptr(b),
                                                   _native.ptr(y), _native.dtype_code(u, 'mod_bias_act'), n, c, h * w, per_sample, act_idx, float(alpha), float(gain), float(clamp),
@@ -483,16 +478,13 @@ class FullyConnectedLayer(torch.nn.Module):
         # both gains ride in the GEMM's alpha / beta: no scaling kernels, forwards (addmm) or backwards (_ScaledLinear)
         w = self.weight.to(x.dtype)
         b = None if self.bias is None else self.bias.to(x.dtype)
-        if _FC_FUSED_GRADS and x.ndim == 2 and x.device.type == 'cuda' and x.dtype == torch.float32 and x.shape[0] > 0:
+        if x.ndim == 2 and x.device.type == 'cuda' and x.dtype == torch.float32 and x.shape[0] > 0:
             y = _ScaledLinear.apply(x, w, b, float(self.weight_gain), float(self.bias_gain))
         elif b is None:
             y = torch.mm(x, w.t()) * self.weight_gain
         else:
             y = torch.addmm(b[None], x, w.t(), beta=float(self.bias_gain), alpha=float(self.weight_gain))
         return y if self.activation == 'linear' else bias_act.bias_act(y, None, act=self.activation)
-
-# A/B switch: 0 = autograd's own backward of addmm (a GEMM and a scaling kernel per gradient, a sum and a scaling kernel for the bias)
-_FC_FUSED_GRADS = _os.environ.get('PASTA_FC_FUSED_GRADS', '1') != '0'
 
 class _ScaledLinear(torch.autograd.Function):
     """``y = alpha x w^T + beta b`` (FullyConnectedLayer: reference networks.py:117-128 with the gains folded into the GEMM) whose backward is three
@@ -626,8 +618,8 @@ class Conv2dLayer(_FilteredConv):
         return conv2d_resample.conv2d_resample_bias_act(x=x, b=(None if self.bias is None else self.bias.to(x.dtype)), act=self.activation,
                                                         gain=act_gain, clamp=act_clamp, passthrough=passthrough, **self._resample_args(x))
 
-# A/B switch: 0 = ``shortcut.add_(...)`` as the reference writes the residual blocks; 1 = the sum in the skip convolution's epilogue
-_SKIP_ADD_FUSED = _os.environ.get('PASTA_SKIP_ADD_FUSED', '1') != '0'
+# the residual sum in the skip convolution's epilogue (False: ``shortcut.add_(...)`` as the reference writes it; tests compare the two)
+_SKIP_ADD_FUSED = True
 
 @persistence.persistent_class
 class Spade_Conv2dLayer(_FilteredConv):
@@ -788,8 +780,9 @@ class ToRGBLayerV18(_StyledHeads):
 #----------------------------------------------------------------------------
 # Encoders.
 
-# A/B switch: 0 = every consumer of a multi-consumer tensor returns its own input gradient and autograd adds them (two reads and a write per addition)
-_GRAD_JOIN = _os.environ.get('PASTA_GRAD_JOIN', '1') != '0'
+# the gradients of a multi-consumer tensor joined in a launch's epilogue (False: every consumer returns its own and autograd adds them, two reads
+# and a write per addition; tests compare the two)
+_GRAD_JOIN = True
 
 def _layer_and_input(layer, x):
     """``(layer(x), x')`` for a tensor with further consumers: give them ``x'`` (= ``x``), and their gradient is added in the epilogue of
@@ -1002,8 +995,7 @@ class Spade_ResBlockV2(torch.nn.Module):
         x = self._norm_then_conv(self.spade1, self.conv1, x, denorm_feat, half, gb=gb[2])
         return shortcut.add_(x), feat_next
 
-_SPADE_BATCH = _os.environ.get('PASTA_SPADE_BATCH', '1') != '0'         # A/B switch: 0 = three conv_mlp and three gamma | beta convolutions per SPADE residual block
-_MERGE_FUSED = _os.environ.get('PASTA_MERGE_FUSED', '1') != '0'         # A/B switch: 0 = torch.cat + one 1x1 convolution, as the reference
+_SPADE_BATCH = True         # False: three conv_mlp and three gamma | beta convolutions per SPADE residual block (tests compare the two)
 
 def _merge_without_cat(layer, x, side):
     """``layer(torch.cat([x, side], 1))`` for a 1x1 ``Conv2dLayer`` (networks.py:5698-5700) without the concatenated tensor: the
@@ -1012,7 +1004,7 @@ def _merge_without_cat(layer, x, side):
     the two input gradients come back as two contiguous tensors instead of channel slices of one.  (Measured and dropped, round 4,
     profiles/r4_ab_merge_split.txt: the same through linearity with the existing kernels -- conv(side, w[:, C:]) as the residual of
     conv(x, w[:, :C]) -- was 0.4 ms per step SLOWER than the concatenation: two 64-row one-tap launches cost more than the copy.)"""
-    if (_MERGE_FUSED and layer.up == 1 and layer.down == 1 and layer.activation in conv2d_gradfix.FUSABLE_ACTS
+    if (layer.up == 1 and layer.down == 1 and layer.activation in conv2d_gradfix.FUSABLE_ACTS
             and conv2d_gradfix.cat1x1_available(x, side, layer.weight)):
         act_gain, act_clamp = _scaled_act(layer.activation, 1, layer.conv_clamp)
         return conv2d_gradfix.conv2d_cat1x1_bias_act(x, side, _master_weight(layer.weight, x), None if layer.bias is None else layer.bias.to(x.dtype),
@@ -1214,7 +1206,7 @@ class _PatchRoutedSynthesis(torch.nn.Module):
         upper, lower = self._regions(heads)
         pu = self._spade_feat_parts(upper.detach(), du_mask, du_in)
         pl = self._spade_feat_parts(lower.detach(), dl_mask, dl_in)
-        if _GARMENT_FUSED and pu[0].dtype == torch.float32 and pu[0].device.type == 'cuda' and pu[1].dtype == torch.float32 and pu[0].shape == pl[0].shape:
+        if pu[0].dtype == torch.float32 and pu[0].device.type == 'cuda' and pu[1].dtype == torch.float32 and pu[0].shape == pl[0].shape:
             # both garments' masked-mean fills written straight into the halves of the concatenated map: two launches instead of
             # twelve element-wise / reduction passes and a torch.cat (fp32 storage; 16-bit storage keeps the reference's roundings)
             feat = _GarmentFeat.apply(*pu, *pl)

@@ -16,7 +16,6 @@ shapes (training_loop...:289-297, 425-456) directly in HBM.
 import copy
 
 import numpy as np
-import os
 import torch
 
 import dnnlib
@@ -188,8 +187,8 @@ class TrainingStep:
 
         self.phases = []
         for name, module, opt_kwargs, reg_interval in [('G', G, cfg.G_opt_kwargs, cfg.G_reg_interval), ('D', D, cfg.D_opt_kwargs, cfg.D_reg_interval)]:
-            if (device.type == 'cuda' and opt_kwargs.get('class_name') == 'torch.optim.Adam' and 'fused' not in opt_kwargs and 'foreach' not in opt_kwargs
-                    and os.environ.get('PASTA_FUSED_ADAM', '1') != '0'):
+            if (device.type == 'cuda' and opt_kwargs.get('class_name') == 'torch.optim.Adam' and 'fused' not in opt_kwargs
+                    and 'foreach' not in opt_kwargs):
                 # the same update (torch.optim.Adam's formula) as ONE multi-tensor kernel per step instead of seven foreach passes
                 opt_kwargs = dnnlib.EasyDict(opt_kwargs, fused=True)
             if reg_interval is None:

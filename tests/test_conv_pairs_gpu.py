@@ -50,7 +50,7 @@ def test_transposed_stride2_pairs_match_fp64(n, cin, cout, h, w, pad, opad, math
     assert y.shape == ref.shape
     err = float((y.cpu().double() - ref).abs().max() / ref.abs().max())
     assert err < 2e-6, err
-    t2 = (math == 'default' and pad == 0 and ((h % 8 == 0 and w % 32 == 0) or (h % 16 == 0 and w % 16 == 0)) and cin >= 16 and os.environ.get('PASTA_CONV_T2') in (None, '2'))
+    t2 = (math == 'default' and pad == 0 and ((h % 8 == 0 and w % 32 == 0) or (h % 16 == 0 and w % 16 == 0)) and cin >= 16)
     if t2:                          # round 5: the one-pass kernel (conv_fwd_t2.h), remainder row / column inside the launch
         assert kernel == 13 and launches == 1
     elif opad == 1:                 # even output planes: always the pair kernel

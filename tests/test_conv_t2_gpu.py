@@ -107,19 +107,3 @@ def test_input_gradient_of_a_stride_two_convolution_is_this_kernel():
     (gxd,) = torch.autograd.grad(torch.nn.functional.conv2d(xd, w.double(), stride=2), [xd], dy.double())
     assert _rel(gx, gxd) < 2e-6 and _rel(gx[:, :, -1], gxd[:, :, -1]) < 2e-6 and _rel(gx[:, :, :, -1], gxd[:, :, :, -1]) < 2e-6
 
-
-def test_weights_by_lds_dma_change_no_bit_of_the_tile_kernel():
-    """PASTA_ROWS2D_GLDS=1 (opt-in: profiles/r5_ab_rows2d_glds.txt): the eight-wave 3x3 stride-1 tile kernel with its weights by LDS-DMA and
-    hand-counted waits -- the same products in the same order, so the same bits.  The switch is read once per process: two child processes."""
-    import os, subprocess, sys
-    code = ("import sys, hashlib; sys.path.insert(0, %r); import torch; from torch_utils.ops import conv2d_gradfix as cg\n"
-            "g = torch.Generator().manual_seed(5)\n"
-            "x = torch.randn([3, 96, 64, 64], generator=g).cuda(); w = (torch.randn([256, 96, 3, 3], generator=g) * 0.1).cuda()\n"
-            "y = cg._launch_conv(x, w, cg._Cfg((False, 1, 1, 1, 0, 0, 1)))\n"
-            "print('HASH', hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest())\n") % os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pasta-gan_amd')
-    out = []
-    for v in ('0', '1'):
-        r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, PASTA_ROWS2D_GLDS=v), capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([l for l in r.stdout.splitlines() if l.startswith('HASH')][0])
-    assert out[0] == out[1]

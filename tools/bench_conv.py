@@ -112,7 +112,7 @@ DOWN = [  # the down path of conv2d_resample (blur to 2 k + 1, then 3x3 stride 2
 
 
 def down_path(args):
-    """blur / forward convolution / weight gradient of a down layer, with the blurred tensor as fp32 (PASTA_PIECES=0's path) and as the
+    """blur / forward convolution / weight gradient of a down layer, with the blurred tensor as fp32 (the reference's path) and as the
     producer-written operand pieces (round 5): per-stage times from events, TFLOP/s of the convolutions, GB/s of the blur on the bytes it moves."""
     from torch_utils.ops import upfirdn2d
     dev = torch.device('cuda')
