@@ -285,13 +285,15 @@ def bias_act(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=None, 
         raise NotImplementedError("bias_act(impl='ref'): this package has no PyTorch-op fallback; "
                                   "the CPU restatement used for testing is oracle/ref_ops.py")
     assert clamp is None or clamp >= 0
-    spec = activation_funcs[act]
-    alpha = float(alpha if alpha is not None else spec.def_alpha)
-    gain = float(gain if gain is not None else spec.def_gain)
-    clamp = float(clamp if clamp is not None else -1)
     if b is not None:
         assert isinstance(b, torch.Tensor) and b.ndim == 1
         assert 0 <= dim < x.ndim and b.shape[0] == x.shape[dim]
-    return _BiasActHip.apply(x, b, (dim, act, alpha, gain, clamp))
+    return _BiasActHip.apply(x, b, (dim,) + act_cfg(act, alpha, gain, clamp))
+
+def act_cfg(act, alpha=None, gain=None, clamp=None):
+    """(act, alpha, gain, clamp) with the activation's default ``alpha`` / ``gain`` for None and -1 (no clamping) for ``clamp=None``."""
+    spec = activation_funcs[act]
+    return (act, float(alpha if alpha is not None else spec.def_alpha), float(gain if gain is not None else spec.def_gain),
+            float(clamp if clamp is not None else -1))
 
 #----------------------------------------------------------------------------

@@ -9,8 +9,10 @@ to ``dy``; the weight gradient is its own Function whose backward is again expre
 forward operators, so R1's double backward works.
 """
 
+import collections
 import contextlib
 import ctypes
+import operator
 
 import torch
 
@@ -72,23 +74,49 @@ def _desc(cfg, x_shape, c_out, oh, ow, kh, kw, io=torch.float32):
                                pad_h=cfg.pad_h, pad_w=cfg.pad_w, groups=cfg.groups, transposed=int(cfg.transposed), flip=0,
                                math=MATH_CODES[conv_math], wscale=float(cfg.wgain), io_dtype=IO_CODES[io])
 
-# 16-bit storage (fp16 / bf16 tensors in HBM, one matrix-core product per multiply-add, fp32 accumulation; include/pasta_hip.h,
-# pasta_conv_desc.io_dtype) exists for the shapes the matrix-core kernel family covers; the planners say which.  Everything
-# else -- the few-channel stems and heads -- is converted to fp32 for that launch and back.
-_native16_cache = {}
+# The planners (include/pasta_hip.h): pasta_conv2d_plan / pasta_conv2d_wgrad_plan name the kernel a descriptor gets, and whether one exists --
+# 16-bit storage (fp16 / bf16 tensors in HBM, one matrix-core product per multiply-add, fp32 accumulation; pasta_conv_desc.io_dtype) exists for
+# the shapes the matrix-core kernel family covers, everything else -- the few-channel stems and heads -- is converted to fp32 for that launch
+# and back.  ``_plan`` is the one place that asks them.
+PLAN_ISCALE, PLAN_OSCALE, PLAN_EPILOGUE, PLAN_MODULATED, PLAN_NOISE = 1, 2, 4, 8, 16      # PASTA_PLAN_*: what a forward launch passes besides x, w
+_Plan = collections.namedtuple('_Plan', 'ok kernel math workspace')
+_DESC_PTRS = ('x_amax', 'x2', 'x2_amax', 'dy_amax')
+_desc_values = operator.attrgetter(*(f for f, _ in custom_ops.ConvDesc._fields_ if f not in _DESC_PTRS))
+_desc_ptrs = operator.attrgetter(*_DESC_PTRS)
+
+def _desc_key(desc):
+    """Every field of ``desc`` as the planners see it: the pointers as null / non-null."""
+    a, b, c, d = _desc_ptrs(desc)
+    return _desc_values(desc) + (a is not None, b is not None, c is not None, d is not None)
+
+_plan_cache = {}
+
+def _plan(kind, desc, flags=0):
+    """The planner's answer for ``desc``, memoised: (accepted, kernel id, math actually used, workspace bytes).  ``kind`` 'conv' asks
+    pasta_conv2d_plan with the launch's PLAN_* ``flags``; 'wgrad' pasta_conv2d_wgrad_plan (no math); 'wgrad_modulated' the sample-aligned weight
+    gradient, which exists where its workspace query answers (no kernel, no math).  kernel and math are None where the planner refuses."""
+    key = (kind, flags, _desc_key(desc))
+    hit = _plan_cache.get(key)
+    if hit is None:
+        lib, d = _native.lib(), ctypes.byref(desc)
+        kernel, math = ctypes.c_int(), ctypes.c_int()
+        if kind == 'conv':
+            ok = lib.pasta_conv2d_plan(d, int(flags), None, None, ctypes.byref(math), None, ctypes.byref(kernel)) == 0
+            hit = _Plan(ok, kernel.value, math.value, lib.pasta_conv2d_workspace(d))
+        elif kind == 'wgrad':
+            ok = lib.pasta_conv2d_wgrad_plan(d, ctypes.byref(kernel)) == 0
+            hit = _Plan(ok, kernel.value, None, lib.pasta_conv2d_wgrad_workspace(d))
+        else:
+            nbytes = lib.pasta_conv2d_wgrad_modulated_workspace(d)
+            hit = _Plan(nbytes >= 0, None, None, nbytes)
+        if not hit.ok:
+            hit = hit._replace(kernel=None, math=None)
+        _plan_cache[key] = hit
+    return hit
 
 def _native16(kind, desc, has_iscale=False):
-    key = (kind, desc.N, desc.C_in, desc.H, desc.W, desc.C_out, desc.OH, desc.OW, desc.kh, desc.kw, desc.stride, desc.pad_h, desc.pad_w,
-           desc.groups, desc.transposed, desc.io_dtype, bool(has_iscale))
-    hit = _native16_cache.get(key)
-    if hit is None:
-        lib = _native.lib()
-        if kind == 'conv':
-            hit = lib.pasta_conv2d_plan(ctypes.byref(desc), int(bool(has_iscale)), None, None, None, None, None) == 0
-        else:
-            hit = lib.pasta_conv2d_wgrad_plan(ctypes.byref(desc), None) == 0
-        _native16_cache[key] = hit
-    return hit
+    """Does a 16-bit-storage kernel take ``desc`` (io_dtype fp16 / bf16)?"""
+    return _plan(kind, desc, PLAN_ISCALE if has_iscale else 0).ok
 
 # PASTA_MATH_F16X3 (include/pasta_hip.h): the power-of-two operand scales of the ACTIVATIONS come from the tensors' largest
 # magnitudes (the weights are scaled per output row by their packing kernel at every launch: nothing about a weight is cached).
@@ -108,7 +136,6 @@ def _native16(kind, desc, has_iscale=False):
 # kernel that wrote the tensor and are trusted for that version.  Inference tensors (``torch.inference_mode()``) track no
 # version: nothing is cached on them or read back from them.
 AMAX_PARTS = 256
-_f16x3_cache = {}
 _SCAN_TRACE = {} if _os.environ.get('PASTA_AMAX_TRACE') else None
 if _SCAN_TRACE is not None:
     import atexit as _atexit
@@ -171,26 +198,54 @@ def _runs_f16x3(kind, desc, flags=0):
     """Does this launch run the three-product fp16 arithmetic (then it wants the operands' partial maxima)?"""
     if desc.math not in (0, MATH_CODES['f16x3']) or desc.io_dtype != 0:
         return False
-    key = (kind, flags & 9, desc.N, desc.C_in, desc.H, desc.W, desc.C_out, desc.OH, desc.OW, desc.kh, desc.kw, desc.stride, desc.pad_h,
-           desc.pad_w, desc.groups, desc.transposed)
-    hit = _f16x3_cache.get(key)
-    if hit is None:
-        lib = _native.lib()
-        if kind == 'conv':
-            math = ctypes.c_int()
-            hit = lib.pasta_conv2d_plan(ctypes.byref(desc), int(flags), None, None, ctypes.byref(math), None, None) == 0 and math.value == MATH_CODES['f16x3']
-        else:
-            kernel = ctypes.c_int()
-            hit = lib.pasta_conv2d_wgrad_plan(ctypes.byref(desc), ctypes.byref(kernel)) == 0 and kernel.value in (2, 3, 4)
-        _f16x3_cache[key] = hit
-    return hit
+    p = _plan(kind, desc, flags)
+    return p.math == MATH_CODES['f16x3'] if kind == 'conv' else p.kernel in (2, 3, 4)
 
-# Optional measurement hook (bench.py): when set, called as hook(kind, desc, launch) around every native
+# Optional measurement hook (bench.py): when set, called as hook(kind, desc, launch, flags) around every native
 # convolution launch; ``launch()`` performs it. None = no overhead.
 launch_hook = None
 
 def _f32(t):
     return t if t.dtype == torch.float32 else t.float()
+
+def _workspace(nbytes, device):
+    """The workspace of a launch (``_plan(...).workspace``; negative for a descriptor the library refuses: the launch then says why)."""
+    return torch.empty([max(nbytes // 4, 4)], dtype=torch.float32, device=device)
+
+def _issue(kind, flags, entry, args, desc, work, device):
+    """``entry(*args, desc, workspace, bytes, stream)`` -- the tail every convolution entry point shares --, through ``launch_hook`` when set.
+    ``kind`` ('conv', 'conv_isc' = with an input scale, 'wgrad') and ``flags`` (PLAN_*) are what the hook is told."""
+    def launch():
+        with torch.cuda.device(device):
+            _native.check(entry(*args, ctypes.byref(desc), _native.ptr(work), work.numel() * 4, _native.stream()))
+    if launch_hook is None:
+        launch()
+    else:
+        launch_hook(kind, desc, launch, flags)
+
+def _epilogue(epilogue, noise, y):
+    """The ``pasta_conv_epilogue`` of a launch onto ``y`` -> (ConvEpilogue, the producer row of y's maxima or None, the tensors it points to)."""
+    bias, act_code, alpha, gain, clamp = epilogue[:5]
+    res = epilogue[5] if len(epilogue) > 5 else None
+    bias = _f32(bias).contiguous() if bias is not None else None
+    if res is not None:
+        res = res.to(y.dtype).contiguous()
+        if res.shape != y.shape:
+            raise RuntimeError(f'conv2d: residual {tuple(res.shape)} does not match the output {tuple(y.shape)}')
+    nz = nstr = None
+    if noise is not None:
+        nz, nstr = _f32(noise[0]).contiguous(), _f32(noise[1]).reshape(1).contiguous()
+        n, _, oh, ow = y.shape
+        if nz.numel() not in (oh * ow, n * oh * ow):
+            raise RuntimeError(f'conv2d: noise {tuple(nz.shape)} is neither one {oh}x{ow} plane nor one per sample')
+    ep = custom_ops.ConvEpilogue(bias=bias.data_ptr() if bias is not None else None, act=int(act_code), alpha=float(alpha),
+                                 gain=float(gain), clamp=float(clamp), res=res.data_ptr() if res is not None else None,
+                                 noise=nz.data_ptr() if nz is not None else None, noise_strength=nstr.data_ptr() if nz is not None else None,
+                                 noise_per_sample=int(nz is not None and nz.numel() != y.shape[2] * y.shape[3]))
+    y_row = _native.amax_slot(y)            # the layer's output usually feeds the next convolution
+    if y_row is not None:
+        ep.y_amax = y_row.data_ptr()
+    return ep, y_row, (bias, res, nz, nstr)
 
 def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, noise=None, x2=None, used=None, pieces=None, prepacked=None):
     """y = conv(x * iscale[n,c]) * oscale[n,c'] through ``pasta_conv2d_ex``; fp32 accumulation.  fp32 tensors run the
@@ -208,18 +263,22 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
     Python object without the attribute the maxima travel on: it would be scanned a second time).
     ``pieces`` = (bound row [256], logical shape (N, C, H, W)): ``x`` is not an NCHW tensor but the producer-written operand of the three-product
     arithmetic (``blur_pieces``: PASTA_LAYOUT_PIECES16, include/pasta_hip.h) -- the launch copies its sixteen-byte pieces instead of splitting.
-    ``prepacked`` = the workspace tensor of THIS launch with the weights already packed in it (``pack_pair``): no packing kernel."""
+    ``prepacked`` = (descriptor key, workspace) from ``_pack_pair``: the weights packed for the descriptor of that key; a launch of that very
+    descriptor runs on it without a packing kernel, any other packs for itself."""
     _native.require_gpu(x, 'conv2d')
     if pieces is not None:
         assert iscale is None and oscale is None and wmod is None and noise is None and x2 is None
-        return _launch_conv_pieces(x, w, cfg, epilogue, pieces)
-    if x.ndim != 4 or w.ndim != 4:
-        raise RuntimeError('conv2d: x and w must be rank 4')
-    out_dtype = x.dtype
+        bound, x_shape = pieces
+        out_dtype = torch.float32
+    else:
+        if x.ndim != 4 or w.ndim != 4:
+            raise RuntimeError('conv2d: x and w must be rank 4')
+        x_shape, out_dtype = tuple(x.shape), x.dtype
+    n, h, wd = x_shape[0], x_shape[2], x_shape[3]
     w = _f32(w).contiguous()
     kh, kw = w.shape[2], w.shape[3]
     shared = cfg.groups if wmod is not None else 1        # the weight tensor holds one group
-    c_in = x.shape[1] + (x2.shape[1] if x2 is not None else 0)
+    c_in = x_shape[1] + (x2.shape[1] if x2 is not None else 0)
     if cfg.transposed:
         if w.shape[0] * shared != c_in:
             raise RuntimeError(f'conv_transpose2d: weight {tuple(w.shape)} does not match input channels {c_in}')
@@ -228,69 +287,48 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
         if w.shape[1] * cfg.groups != c_in:
             raise RuntimeError(f'conv2d: weight {tuple(w.shape)} does not match input channels {c_in} (groups={cfg.groups})')
         c_out = w.shape[0] * shared
-    oh, ow = _out_hw(cfg, x.shape[2], x.shape[3], kh, kw)
+    oh, ow = _out_hw(cfg, h, wd, kh, kw)
     if oh < 1 or ow < 1:
         raise RuntimeError('conv2d: output must be at least 1x1')
     if x.numel() == 0 or c_out * oh * ow == 0:
-        return torch.zeros([x.shape[0], c_out, oh, ow], dtype=out_dtype, device=x.device)
+        return torch.zeros([n, c_out, oh, ow], dtype=out_dtype, device=x.device)
+    if noise is not None and epilogue is None:
+        raise RuntimeError('conv2d: the noise operand is part of the fused epilogue')
+    # the launch's PASTA_PLAN_* flags, as the library derives them from what it is passed (the kernel it runs depends on them)
+    flags = ((PLAN_ISCALE if iscale is not None else 0) | (PLAN_OSCALE if oscale is not None else 0) | (PLAN_EPILOGUE if epilogue is not None else 0)
+             | (PLAN_MODULATED if wmod is not None else 0) | (PLAN_NOISE if noise is not None else 0))
     io = torch.float32
-    if x.dtype in (torch.float16, torch.bfloat16) and _native16('conv', _desc(cfg, x.shape, c_out, oh, ow, kh, kw, x.dtype), iscale is not None):
+    if x.dtype in (torch.float16, torch.bfloat16) and _native16('conv', _desc(cfg, x_shape, c_out, oh, ow, kh, kw, x.dtype), iscale is not None):
         io = x.dtype
-    x = x.contiguous() if io is not torch.float32 else _f32(x).contiguous()
-    y = torch.empty([x.shape[0], c_out, oh, ow], dtype=io, device=x.device)
-    desc = _desc(cfg, (x.shape[0], c_in, x.shape[2], x.shape[3]), c_out, oh, ow, kh, kw, io)
+    if pieces is None:
+        x = x.contiguous() if io is not torch.float32 else _f32(x).contiguous()
+    y = torch.empty([n, c_out, oh, ow], dtype=io, device=x.device)
+    desc = _desc(cfg, (n, c_in, h, wd), c_out, oh, ow, kh, kw, io)
     if x2 is not None:
-        if io is not torch.float32 or x2.dtype != torch.float32 or x2.shape[0] != x.shape[0] or x2.shape[2:] != x.shape[2:]:
+        if io is not torch.float32 or x2.dtype != torch.float32 or x2.shape[0] != n or x2.shape[2:] != x.shape[2:]:
             raise RuntimeError('conv2d: the second input tensor must be fp32 and match the first in batch and plane size')
         x2 = x2.contiguous()
         desc.x2, desc.C1 = x2.data_ptr(), int(x.shape[1])
-    lib = _native.lib()
-    nbytes = lib.pasta_conv2d_workspace(ctypes.byref(desc))
-    if nbytes < 0:
-        _native.check(1)
-    if prepacked is not None and prepacked.numel() * 4 >= nbytes and iscale is None and oscale is None and wmod is None and x2 is None and io is torch.float32:
-        work = prepacked
+    if pieces is not None:
+        desc.x_layout, desc.x_amax = 1, bound.data_ptr()
+    f16x3 = pieces is not None or _runs_f16x3('conv', desc, flags)
+    if prepacked is not None and prepacked[0] == _desc_key(desc):
+        assert iscale is None and oscale is None and wmod is None
+        work = prepacked[1]
         desc.w_prepacked = 1
     else:
-        work = torch.empty([max(nbytes // 4, 4)], dtype=torch.float32, device=x.device)
+        work = _workspace(_plan('conv', desc, flags).workspace, x.device)
     if iscale is not None:
         iscale = _f32(iscale).contiguous()
-        assert iscale.shape == (x.shape[0], x.shape[1])
+        assert iscale.shape == (n, x_shape[1])
     if oscale is not None:
         oscale = _f32(oscale).contiguous()
-        assert oscale.shape == (x.shape[0], c_out)
+        assert oscale.shape == (n, c_out)
     ep = y_row = None
     if epilogue is not None:
-        bias, act_code, alpha, gain, clamp = epilogue[:5]
-        res = epilogue[5] if len(epilogue) > 5 else None
-        bias = _f32(bias).contiguous() if bias is not None else None
-        if res is not None:
-            res = res.to(io).contiguous()
-            if res.shape != y.shape:
-                raise RuntimeError(f'conv2d: residual {tuple(res.shape)} does not match the output {tuple(y.shape)}')
-        nz = nstr = None
-        if noise is not None:
-            nz, nstr = _f32(noise[0]).contiguous(), _f32(noise[1]).reshape(1).contiguous()
-            if nz.numel() not in (oh * ow, x.shape[0] * oh * ow):
-                raise RuntimeError(f'conv2d: noise {tuple(nz.shape)} is neither one {oh}x{ow} plane nor one per sample')
-        ep = custom_ops.ConvEpilogue(bias=bias.data_ptr() if bias is not None else None, act=int(act_code), alpha=float(alpha),
-                                     gain=float(gain), clamp=float(clamp), res=res.data_ptr() if res is not None else None,
-                                     noise=nz.data_ptr() if nz is not None else None, noise_strength=nstr.data_ptr() if nz is not None else None,
-                                     noise_per_sample=int(nz is not None and nz.numel() != oh * ow))
-        y_row = _native.amax_slot(y)            # the layer's output usually feeds the next convolution
-        if y_row is not None:
-            ep.y_amax = y_row.data_ptr()
-    elif noise is not None:
-        raise RuntimeError('conv2d: the noise operand is part of the fused epilogue')
-    if wmod is not None:
-        assert iscale is None and oscale is None
-        mod_s = _f32(wmod[0]).contiguous()
-        mod_d = _f32(wmod[1]).contiguous() if wmod[1] is not None else None
-        assert mod_s.numel() == x.shape[1] and (mod_d is None or mod_d.numel() == c_out)
-    x_amax = None
-    f16x3 = _runs_f16x3('conv', desc, (1 if iscale is not None else 0) | (8 if wmod is not None else 0))
-    x2_amax = None
-    if f16x3:
+        ep, y_row, ep_tensors = _epilogue(epilogue, noise, y)        # (ep_tensors: what ep points to, held until the launch is issued)
+    x_amax = x2_amax = None
+    if f16x3 and pieces is None:
         x_amax = tensor_amax(x)                 # the weights are scaled per output row by their packing kernel: nothing to pass
         desc.x_amax = x_amax.data_ptr()
         if x2 is not None:
@@ -298,23 +336,18 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
             desc.x2_amax = x2_amax.data_ptr()
         if used is not None:
             used['x_amax'], used['x2_amax'] = x_amax, x2_amax
-    def launch():
-        with torch.cuda.device(x.device):
-            if wmod is not None:
-                st = lib.pasta_conv2d_modulated(_native.ptr(x), _native.ptr(w), _native.ptr(mod_s), _native.ptr(mod_d), _native.ptr(y),
-                                                ctypes.byref(ep) if ep is not None else None, ctypes.byref(desc), _native.ptr(work),
-                                                work.numel() * 4, _native.stream())
-            else:
-                st = lib.pasta_conv2d_ex(_native.ptr(x), _native.ptr(w), _native.ptr(y), _native.ptr(iscale), _native.ptr(oscale),
-                                         ctypes.byref(ep) if ep is not None else None, ctypes.byref(desc), _native.ptr(work),
-                                         work.numel() * 4, _native.stream())
-        _native.check(st)
-    if launch_hook is None:
-        launch()
+    ep_ref = ctypes.byref(ep) if ep is not None else None
+    lib = _native.lib()
+    if wmod is not None:
+        assert iscale is None and oscale is None
+        mod_s = _f32(wmod[0]).contiguous()
+        mod_d = _f32(wmod[1]).contiguous() if wmod[1] is not None else None
+        assert mod_s.numel() == x.shape[1] and (mod_d is None or mod_d.numel() == c_out)
+        args = (_native.ptr(x), _native.ptr(w), _native.ptr(mod_s), _native.ptr(mod_d), _native.ptr(y), ep_ref)
+        _issue('conv', flags, lib.pasta_conv2d_modulated, args, desc, work, x.device)
     else:
-        # 'conv_isc': the launch passes an input scale (another kernel instance); flags = PASTA_PLAN_* of include/pasta_hip.h
-        flags = (1 if iscale is not None else 0) | (2 if oscale is not None else 0) | (4 if ep is not None else 0) | (8 if wmod is not None else 0)
-        launch_hook('conv' if iscale is None else 'conv_isc', desc, launch, flags)
+        args = (_native.ptr(x), _native.ptr(w), _native.ptr(y), _native.ptr(iscale), _native.ptr(oscale), ep_ref)
+        _issue('conv' if iscale is None else 'conv_isc', flags, lib.pasta_conv2d_ex, args, desc, work, x.device)
     if f16x3:
         _check_finite(y, 'conv2d')
     if y_row is not None and y.dtype == out_dtype:
@@ -327,7 +360,6 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
 # arithmetic (16-byte units of eight channels, [N][C / 8][H][piece][W]), and both consumers copy pieces instead of fetching fp32 with eight
 # channel-strided loads per unit and splitting it -- in every launch that touches the tensor.
 _PIECES = True       # False: the blurred tensor in fp32, as the reference (tests compare the two)
-_pieces_cache = {}
 
 def pieces_available(x, f, weight, pad4, groups=1):
     """Can ``conv2d(upfirdn2d(x, f, padding=pad4), weight, stride=2)`` run on the blurred tensor as producer-written pieces (forward kernel 10 and
@@ -339,20 +371,13 @@ def pieces_available(x, f, weight, pad4, groups=1):
     px0, px1, py0, py1 = pad4
     n, c, h, wd = (int(v) for v in x.shape)
     bh, bw = h + py0 + py1 - 3, wd + px0 + px1 - 3
-    key = (n, c, bh, bw, int(weight.shape[0]))
-    hit = _pieces_cache.get(key)
-    if hit is None:
-        hit = False
-        if bh >= 3 and bw >= 3:
-            cfg = _Cfg((False, 2, 0, 0, 0, 0, 1, 1.0))
-            oh, ow = _out_hw(cfg, bh, bw, 3, 3)
-            desc = _desc(cfg, (n, c, bh, bw), int(weight.shape[0]), oh, ow, 3, 3)
-            desc.x_layout = 1
-            lib, k = _native.lib(), ctypes.c_int()
-            hit = lib.pasta_conv2d_plan(ctypes.byref(desc), 4, None, None, None, None, ctypes.byref(k)) == 0 and k.value == 10
-            hit = hit and lib.pasta_conv2d_wgrad_plan(ctypes.byref(desc), ctypes.byref(k)) == 0 and k.value == 6
-        _pieces_cache[key] = hit
-    return hit
+    if bh < 3 or bw < 3:
+        return False
+    cfg = _Cfg((False, 2, 0, 0, 0, 0, 1, 1.0))
+    oh, ow = _out_hw(cfg, bh, bw, 3, 3)
+    desc = _desc(cfg, (n, c, bh, bw), int(weight.shape[0]), oh, ow, 3, 3)
+    desc.x_layout = 1
+    return _plan('conv', desc, PLAN_EPILOGUE).kernel == 10 and _plan('wgrad', desc).kernel == 6
 
 def blur_pieces(x, f, pad4, flip_filter=False, gain=1.0, x_amax=None):
     """``upfirdn2d(x, f, padding=pad4, flip_filter, gain)`` for a 4 x 4 filter, written as PASTA_LAYOUT_PIECES16.  Returns (pieces -- a uint8
@@ -402,7 +427,6 @@ def pieces_pack(x, x_amax=None):
 # conv_mlp batches per generator pass, networks.py Spade_ResBlockV2) is packed ONCE and every forward launch copies the pieces (plan kernel 7
 # with x_layout = PASTA_LAYOUT_PIECES16: +10 % on 256 -> 384 at 128 x 128, profiles/r5_s1_pieces_microbench.txt).  The pieces ride on the tensor
 # object, keyed by version and address like the maxima rows; the weight gradients keep reading the fp32 tensor.
-_shared_cache = {}
 
 def _shared_pieces_ok(x, weight, cfg, has_epilogue):
     """Does the eight-wave stride-1 tile kernel take conv2d(x, weight) with x as pieces?"""
@@ -411,16 +435,10 @@ def _shared_pieces_ok(x, weight, cfg, has_epilogue):
             and tuple(weight.shape[2:]) == (3, 3) and x.ndim == 4 and x.shape[1] % 8 == 0):
         return False
     n, c, h, wd = (int(v) for v in x.shape)
-    key = (n, c, h, wd, int(weight.shape[0]), cfg.pad_h, cfg.pad_w, bool(has_epilogue))
-    hit = _shared_cache.get(key)
-    if hit is None:
-        oh, ow = _out_hw(cfg, h, wd, 3, 3)
-        desc = _desc(cfg, (n, c, h, wd), int(weight.shape[0]), oh, ow, 3, 3)
-        desc.x_layout = 1
-        k = ctypes.c_int()
-        hit = _native.lib().pasta_conv2d_plan(ctypes.byref(desc), 4 if has_epilogue else 0, None, None, None, None, ctypes.byref(k)) == 0 and k.value == 7
-        _shared_cache[key] = hit
-    return hit
+    oh, ow = _out_hw(cfg, h, wd, 3, 3)
+    desc = _desc(cfg, (n, c, h, wd), int(weight.shape[0]), oh, ow, 3, 3)
+    desc.x_layout = 1
+    return _plan('conv', desc, PLAN_EPILOGUE if has_epilogue else 0).kernel == 7
 
 def share_pieces(x):
     """Pack ``x`` for the stride-1 3x3 layers that will read it (a no-op where none of them could use the pieces); returns ``x``."""
@@ -448,79 +466,10 @@ def pieces_unpack(pieces, bound, shape):
         _native.check(_native.lib().pasta_pieces_unpack(_native.ptr(pieces), _native.ptr(bound), _native.ptr(y), n, c, h, wd, _native.stream()))
     return y
 
-def _launch_conv_pieces(x, w, cfg, epilogue, pieces):
-    """The stride-2 forward convolution on a producer-written operand (``_launch_conv`` with ``pieces``)."""
-    bound, (n, c_in, h, wd) = pieces
-    w = _f32(w).contiguous()
-    kh, kw = w.shape[2], w.shape[3]
-    assert cfg.groups == 1 and w.shape[0 if cfg.transposed else 1] == c_in
-    c_out = w.shape[1 if cfg.transposed else 0]
-    oh, ow = _out_hw(cfg, h, wd, kh, kw)
-    y = torch.empty([n, c_out, oh, ow], dtype=torch.float32, device=x.device)
-    desc = _desc(cfg, (n, c_in, h, wd), c_out, oh, ow, kh, kw)
-    desc.x_layout, desc.x_amax = 1, bound.data_ptr()
-    lib = _native.lib()
-    nbytes = lib.pasta_conv2d_workspace(ctypes.byref(desc))
-    if nbytes < 0:
-        _native.check(1)
-    work = torch.empty([max(nbytes // 4, 4)], dtype=torch.float32, device=x.device)
-    ep = y_row = None
-    if epilogue is not None:
-        bias, act_code, alpha, gain, clamp = epilogue[:5]
-        res = epilogue[5] if len(epilogue) > 5 else None
-        bias = _f32(bias).contiguous() if bias is not None else None
-        if res is not None:
-            res = res.float().contiguous()
-            if res.shape != y.shape:
-                raise RuntimeError(f'conv2d: residual {tuple(res.shape)} does not match the output {tuple(y.shape)}')
-        ep = custom_ops.ConvEpilogue(bias=bias.data_ptr() if bias is not None else None, act=int(act_code), alpha=float(alpha), gain=float(gain),
-                                     clamp=float(clamp), res=res.data_ptr() if res is not None else None, noise=None, noise_strength=None, noise_per_sample=0)
-        y_row = _native.amax_slot(y)
-        if y_row is not None:
-            ep.y_amax = y_row.data_ptr()
-    def launch():
-        with torch.cuda.device(x.device):
-            st = lib.pasta_conv2d_ex(_native.ptr(x), _native.ptr(w), _native.ptr(y), None, None, ctypes.byref(ep) if ep is not None else None,
-                                     ctypes.byref(desc), _native.ptr(work), work.numel() * 4, _native.stream())
-        _native.check(st)
-    if launch_hook is None:
-        launch()
-    else:
-        launch_hook('conv', desc, launch, 4 if ep is not None else 0)
-    _check_finite(y, 'conv2d')
-    if y_row is not None:
-        _native.amax_attach(y, y_row)
-    return y
-
-def _launch_wgrad_pieces(pieces_x, dy, cfg, w_shape, pieces, out_dtype=None):
-    """dw of the stride-2 convolution whose input is a producer-written operand (pasta_conv2d_wgrad_plan kernel 6)."""
-    bound, (n, c_in, h, wd) = pieces
-    out_dtype = dy.dtype if out_dtype is None else out_dtype
-    dy = _f32(dy).contiguous()
-    dw = torch.empty(list(w_shape), dtype=torch.float32, device=dy.device)
-    desc = _desc(cfg, (n, c_in, h, wd), dy.shape[1], dy.shape[2], dy.shape[3], w_shape[2], w_shape[3])
-    desc.x_layout, desc.x_amax = 1, bound.data_ptr()
-    amax_dy = tensor_amax(dy)
-    desc.dy_amax = amax_dy.data_ptr()
-    lib = _native.lib()
-    nbytes = lib.pasta_conv2d_wgrad_workspace(ctypes.byref(desc))
-    if nbytes < 0:
-        _native.check(1)
-    work = torch.empty([max(nbytes // 4, 4)], dtype=torch.float32, device=dy.device)
-    def launch():
-        with torch.cuda.device(dy.device):
-            st = lib.pasta_conv2d_wgrad(_native.ptr(pieces_x), _native.ptr(dy), _native.ptr(dw), ctypes.byref(desc), _native.ptr(work), work.numel() * 4, _native.stream())
-        _native.check(st)
-    if launch_hook is None:
-        launch()
-    else:
-        launch_hook('wgrad', desc, launch, 0)
-    _check_finite(dw, 'conv2d_wgrad')
-    return dw.to(out_dtype)
-
-def _launch_wgrad(x, dy, cfg, w_shape, out_dtype=None, x_amax=None):
+def _launch_wgrad(x, dy, cfg, w_shape, out_dtype=None, x_amax=None, pieces=None):
     """dw of ``conv(x, w)`` given dy through ``pasta_conv2d_wgrad``; the gradient comes out fp32 (weights are fp32 masters)
-    and is returned as ``out_dtype`` (default: dy's)."""
+    and is returned as ``out_dtype`` (default: dy's).  ``pieces`` = (bound row, logical shape) as for ``_launch_conv``: x is a
+    producer-written operand (``blur_pieces``; pasta_conv2d_wgrad_plan kernel 6)."""
     _native.require_gpu(x, 'conv2d_wgrad')
     out_dtype = dy.dtype if out_dtype is None else out_dtype
     kh, kw = w_shape[2], w_shape[3]
@@ -530,34 +479,33 @@ def _launch_wgrad(x, dy, cfg, w_shape, out_dtype=None, x_amax=None):
     if x.numel() == 0 or dy.numel() == 0:
         return dw.zero_().to(out_dtype)
     io = torch.float32
-    if x.dtype == dy.dtype and x.dtype in (torch.float16, torch.bfloat16) and \
-            _native16('wgrad', _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, x.dtype)):
-        io = x.dtype
-    x = x.contiguous() if io is not torch.float32 else _f32(x).contiguous()
-    dy = dy.contiguous() if io is not torch.float32 else _f32(dy).contiguous()
-    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, io)
-    lib = _native.lib()
-    nbytes = lib.pasta_conv2d_wgrad_workspace(ctypes.byref(desc))
-    if nbytes < 0:
-        _native.check(1)
-    work = torch.empty([max(nbytes // 4, 4)], dtype=torch.float32, device=x.device)
-    f16x3 = _runs_f16x3('wgrad', desc)
-    if f16x3:
-        # x_amax: the maxima the forward launch took for this very tensor (autograd has checked that it was not written since)
-        amax_x, amax_dy = (x_amax if x_amax is not None and x.dtype == torch.float32 else tensor_amax(x)), tensor_amax(dy)
-        desc.x_amax, desc.dy_amax = amax_x.data_ptr(), amax_dy.data_ptr()
-    def launch():
-        with torch.cuda.device(x.device):
-            st = lib.pasta_conv2d_wgrad(_native.ptr(x), _native.ptr(dy), _native.ptr(dw), ctypes.byref(desc),
-                                        _native.ptr(work), work.numel() * 4, _native.stream())
-        _native.check(st)
-    if launch_hook is None:
-        launch()
+    if pieces is not None:
+        x_amax, x_shape = pieces
     else:
-        launch_hook('wgrad', desc, launch, 0)
+        x_shape = tuple(x.shape)
+        if x.dtype == dy.dtype and x.dtype in (torch.float16, torch.bfloat16) and \
+                _native16('wgrad', _desc(cfg, x_shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, x.dtype)):
+            io = x.dtype
+        x = x.contiguous() if io is not torch.float32 else _f32(x).contiguous()
+    dy = dy.contiguous() if io is not torch.float32 else _f32(dy).contiguous()
+    desc = _desc(cfg, x_shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw, io)
+    if pieces is not None:
+        desc.x_layout = 1
+    f16x3 = pieces is not None or _runs_f16x3('wgrad', desc)
+    _wgrad_issue('wgrad', desc, x, dy, x_amax, f16x3, _native.lib().pasta_conv2d_wgrad, (x, dy, dw), dw)
+    return dw.to(out_dtype)
+
+def _wgrad_issue(kind, desc, x, dy, x_amax, f16x3, entry, tensors, dw):
+    """What every weight-gradient launch does around its entry point: workspace, the operands' maxima under the three-product arithmetic
+    (``x_amax``: the maxima the forward launch took for this very tensor -- autograd has checked that it was not written since -- or the
+    pieces' bound row), the launch, the finite check."""
+    work = _workspace(_plan(kind, desc).workspace, dy.device)
+    if f16x3:
+        amax_x, amax_dy = (x_amax if x_amax is not None else tensor_amax(x)), tensor_amax(dy)
+        desc.x_amax, desc.dy_amax = amax_x.data_ptr(), amax_dy.data_ptr()
+    _issue('wgrad', 0, entry, tuple(_native.ptr(t) for t in tensors), desc, work, dy.device)
     if f16x3:
         _check_finite(dw, 'conv2d_wgrad')
-    return dw.to(out_dtype)
 
 #----------------------------------------------------------------------------
 
@@ -576,7 +524,8 @@ def _grad_cfg(cfg, x_hw, y_hw, kh, kw):
 _PACK_PAIR = True       # False: every launch packs for itself (tests compare the two)
 
 def _pack_pair(x, w, cfg):
-    """-> (workspace of the forward launch, workspace of its input-gradient launch), both with the weights packed, or (None, None)."""
+    """-> the forward launch's and its input-gradient launch's (descriptor key, workspace) with the weights packed in it, or (None, None).  The
+    input-gradient launch takes its workspace only if its own descriptor has that key (the arithmetic may have been switched in between)."""
     if not (_PACK_PAIR and x.device.type == 'cuda' and x.dtype == torch.float32 and w.dtype == torch.float32 and conv_math in ('default', 'f16x3')
             and x.ndim == 4 and w.ndim == 4 and x.numel() > 0 and not torch.cuda.is_current_stream_capturing()):
         return None, None
@@ -589,18 +538,65 @@ def _pack_pair(x, w, cfg):
     gcfg = _grad_cfg(cfg, (h, wd), (oh, ow), kh, kw)
     da = _desc(cfg, (n, c_in, h, wd), c_out, oh, ow, kh, kw)
     db = _desc(gcfg, (n, c_out, oh, ow), c_in, h, wd, kh, kw)
-    lib = _native.lib()
-    na, nb = lib.pasta_conv2d_workspace(ctypes.byref(da)), lib.pasta_conv2d_workspace(ctypes.byref(db))
+    na, nb = _plan('conv', da).workspace, _plan('conv', db).workspace
     if na < 0 or nb < 0:
         return None, None
-    wa = torch.empty([max(na // 4, 4)], dtype=torch.float32, device=x.device)
-    wb = torch.empty([max(nb // 4, 4)], dtype=torch.float32, device=x.device)
+    wa, wb = _workspace(na, x.device), _workspace(nb, x.device)
     mask = ctypes.c_int(0)
     wc = w.contiguous()
     with torch.cuda.device(x.device):
-        _native.check(lib.pasta_conv2d_pack_pair(_native.ptr(wc), ctypes.byref(da), _native.ptr(wa), wa.numel() * 4, ctypes.byref(db), _native.ptr(wb),
-                                                 wb.numel() * 4, _native.stream(), ctypes.byref(mask)))
-    return (wa, wb) if mask.value == 3 else (None, None)
+        _native.check(_native.lib().pasta_conv2d_pack_pair(_native.ptr(wc), ctypes.byref(da), _native.ptr(wa), wa.numel() * 4, ctypes.byref(db),
+                                                           _native.ptr(wb), wb.numel() * 4, _native.stream(), ctypes.byref(mask)))
+    return ((_desc_key(da), wa), (_desc_key(db), wb)) if mask.value == 3 else (None, None)
+
+def _act_epilogue(b, act_cfg, res=None):
+    """The ``epilogue`` operand of ``_launch_conv`` for the bias ``b``, ``act_cfg`` = (act, alpha, gain, clamp) and the residual ``res``."""
+    from . import bias_act as ba
+    act, alpha, gain, clamp = act_cfg
+    return (b, ba.activation_funcs[act].cuda_idx, alpha, gain, clamp, res)
+
+def _save_epilogue_output(ctx, y, act_cfg, inputs, extra=(), passthrough=None, tape=True):
+    """Saves ``inputs``, the epilogue's output y and ``extra`` for the backward and returns the forward's result.  y is needed there only as
+    the activation / clamp mask: a linear, unclamped layer (the residual skips, whose output the blocks then update in place) must not pin it.
+    ``tape``: y passes the test instrument bias_act.SlopeTape first.  ``passthrough`` (the input x): returns (y, x)."""
+    from . import bias_act as ba
+    act, _, _, clamp = act_cfg
+    if tape and ba.slope_tape is not None:
+        y = ba.slope_tape.visit(y, act)
+    ctx.save_for_backward(*inputs, y if act != 'linear' or clamp >= 0 else None, *extra)
+    if passthrough is None:
+        return y
+    ctx.set_materialize_grads(False)        # an unused output's gradient arrives as None, not as a tensor of zeros
+    return y, passthrough
+
+def _epilogue_grad(dy, y, bias, act_cfg, want_db):
+    """(dz, db): the gradient at the convolution's output given the epilogue's dy, and the bias gradient (None unless ``want_db`` and a bias) --
+    in one pass where the epilogue has a derivative of its own."""
+    from . import bias_act as ba
+    act, alpha, gain, clamp = act_cfg
+    want_db = want_db and bias is not None
+    dz, db = dy, None
+    if act != 'linear' or gain != 1 or clamp >= 0:
+        if want_db:
+            dz, db = ba.grad_with_bias_grad(dy.contiguous(), y, (1, act, alpha, gain, clamp))
+        else:
+            dz = ba._BiasActHipGrad.apply(dy.contiguous(), None, None, y, (1, act, alpha, gain, clamp))
+    if want_db and db is None:
+        db = ba._BiasSum.apply(dz, 1)
+    return dz, db
+
+def _hand_over(x, again, pieces=False):
+    """``again`` is the pass-through output autograd made of ``x``: the same data at the same version, so x's maxima -- and with ``pieces`` its
+    packed pieces (``share_pieces``) -- go along for the next reader."""
+    if again.is_inference():
+        return again
+    hit = getattr(x, '_pasta_amax', None)
+    if hit is not None:
+        again._pasta_amax = hit
+    hit = _shared_lookup(x) if pieces else None
+    if hit is not None:
+        again._pasta_pieces = (again._version, again.data_ptr()) + hit[2:]
+    return again
 
 class _ConvHip(torch.autograd.Function):
     @staticmethod
@@ -637,47 +633,28 @@ class _ConvBiasActHip(torch.autograd.Function):
     the input-gradient launch (one read of it) -- instead of autograd adding two full tensors afterwards (two reads and a write)."""
     @staticmethod
     def forward(ctx, x, w, b, cfg, act_cfg, res=None, passthrough=False, prepacked=None):
-        act, alpha, gain, clamp = act_cfg
-        from . import bias_act as ba
         used = {}
         ctx.dgrad_ws = None
         shared = _shared_lookup(x) if not x.is_inference() else None
         if shared is not None and _shared_pieces_ok(x, w, cfg, True):
             # x was packed for its several readers (share_pieces): this launch copies the pieces; its maxima are the pack's bound row
-            y = _launch_conv(shared[2], w, cfg, epilogue=(b, ba.activation_funcs[act].cuda_idx, alpha, gain, clamp, res), pieces=(shared[3], shared[4]))
+            y = _launch_conv(shared[2], w, cfg, epilogue=_act_epilogue(b, act_cfg, res), pieces=(shared[3], shared[4]))
             used['x_amax'] = shared[3]
         else:
             if prepacked is None and ctx.needs_input_grad[0]:
                 prepacked, ctx.dgrad_ws = _pack_pair(x, w, cfg)
-            y = _launch_conv(x, w, cfg, epilogue=(b, ba.activation_funcs[act].cuda_idx, alpha, gain, clamp, res), used=used, prepacked=prepacked)
-        if ba.slope_tape is not None:               # test instrument (bias_act.SlopeTape)
-            y = ba.slope_tape.visit(y, act)
-        # y is needed by the backward only as the activation / clamp mask; a linear, unclamped layer (the residual
-        # skips, whose output the blocks then update in place) must not pin it
-        keep_y = act != 'linear' or clamp >= 0
-        ctx.save_for_backward(x, w, b, y if keep_y else None)
+            y = _launch_conv(x, w, cfg, epilogue=_act_epilogue(b, act_cfg, res), used=used, prepacked=prepacked)
         ctx.cfg, ctx.act_cfg, ctx.x_amax = cfg, act_cfg, (used.get('x_amax') if x.dtype == torch.float32 else None)
-        if passthrough:
-            ctx.set_materialize_grads(False)        # an unused output's gradient arrives as None, not as a tensor of zeros
-            return y, x
-        return y
+        return _save_epilogue_output(ctx, y, act_cfg, (x, w, b), passthrough=x if passthrough else None)
 
     @staticmethod
     def backward(ctx, dy, dxp=None):
-        from . import bias_act as ba
         x, w, b, y = ctx.saved_tensors
         if dy is None:                              # only the pass-through output was differentiated
             return dxp, None, None, None, None, None, None, None
-        act, alpha, gain, clamp = ctx.act_cfg
         cfg = ctx.cfg
-        dz = dy
-        dx = dw = db = None
-        want_db = b is not None and ctx.needs_input_grad[2]
-        if act != 'linear' or gain != 1 or clamp >= 0:
-            if want_db:     # derivative of the epilogue and the bias gradient in one pass
-                dz, db = ba.grad_with_bias_grad(dy.contiguous(), y, (1, act, alpha, gain, clamp))
-            else:
-                dz = ba._BiasActHipGrad.apply(dy.contiguous(), None, None, y, (1, act, alpha, gain, clamp))
+        dx = dw = None
+        dz, db = _epilogue_grad(dy, y, b, ctx.act_cfg, ctx.needs_input_grad[2])
         if ctx.needs_input_grad[0]:
             gcfg = _grad_cfg(cfg, x.shape[2:], dz.shape[2:], w.shape[2], w.shape[3])
             if dxp is not None and dxp.dtype == dz.dtype:
@@ -689,8 +666,6 @@ class _ConvBiasActHip(torch.autograd.Function):
             assert dx.shape == x.shape
         if ctx.needs_input_grad[1] and not weight_gradients_disabled:
             dw = _ConvWgradHip.apply(dz, x, cfg, tuple(w.shape), w.dtype, ctx.x_amax)
-        if want_db and db is None:
-            db = ba._BiasSum.apply(dz, 1)
         dres = dz if ctx.needs_input_grad[5] else None     # the residual enters before the activation
         return dx, dw, db, None, None, dres, None, None
 
@@ -704,39 +679,22 @@ class _BlurConvS2Hip(torch.autograd.Function):
     what reads ``x``, and the other consumers' gradient is the addend of its backward launch."""
     @staticmethod
     def forward(ctx, x, f, w, b, ucfg, cfg, act_cfg, res=None, passthrough=False):
-        act, alpha, gain, clamp = act_cfg
-        from . import bias_act as ba
         px0, px1, py0, py1, flip, ugain = ucfg
         pieces, bound, shape = blur_pieces(x, f, (px0, px1, py0, py1), flip, ugain)
-        y = _launch_conv(pieces, w, cfg, epilogue=(b, ba.activation_funcs[act].cuda_idx, alpha, gain, clamp, res), pieces=(bound, shape))
-        if ba.slope_tape is not None:               # test instrument (bias_act.SlopeTape)
-            y = ba.slope_tape.visit(y, act)
-        keep_y = act != 'linear' or clamp >= 0
-        ctx.save_for_backward(x, f, w, b, y if keep_y else None, pieces, bound)
+        y = _launch_conv(pieces, w, cfg, epilogue=_act_epilogue(b, act_cfg, res), pieces=(bound, shape))
         ctx.ucfg, ctx.cfg, ctx.act_cfg, ctx.shape = ucfg, cfg, act_cfg, shape
-        if passthrough:
-            ctx.set_materialize_grads(False)
-            return y, x
-        return y
+        return _save_epilogue_output(ctx, y, act_cfg, (x, f, w, b), (pieces, bound), passthrough=x if passthrough else None)
 
     @staticmethod
     def backward(ctx, dy, dxp=None):
-        from . import bias_act as ba
         from . import upfirdn2d as up
         x, f, w, b, y, pieces, bound = ctx.saved_tensors
         if dy is None:
             return dxp, None, None, None, None, None, None, None, None
-        act, alpha, gain, clamp = ctx.act_cfg
         cfg, shape = ctx.cfg, ctx.shape
         px0, px1, py0, py1, flip, ugain = ctx.ucfg
-        dz = dy
-        dx = dw = db = None
-        want_db = b is not None and ctx.needs_input_grad[3]
-        if act != 'linear' or gain != 1 or clamp >= 0:
-            if want_db:
-                dz, db = ba.grad_with_bias_grad(dy.contiguous(), y, (1, act, alpha, gain, clamp))
-            else:
-                dz = ba._BiasActHipGrad.apply(dy.contiguous(), None, None, y, (1, act, alpha, gain, clamp))
+        dx = dw = None
+        dz, db = _epilogue_grad(dy, y, b, ctx.act_cfg, ctx.needs_input_grad[3])
         if ctx.needs_input_grad[0]:
             gcfg = _grad_cfg(cfg, shape[2:], dz.shape[2:], w.shape[2], w.shape[3])
             dxb = _ConvHip.apply(dz, w, gcfg)                   # gradient of the blurred tensor
@@ -752,9 +710,7 @@ class _BlurConvS2Hip(torch.autograd.Function):
                 xb = up._Upfirdn2dHip.apply(x, f, (1, 1, 1, 1, px0, px1, py0, py1, flip, ugain))
                 dw = _ConvWgradHip.apply(dz, xb, cfg, tuple(w.shape), w.dtype, None)
             else:
-                dw = _launch_wgrad_pieces(pieces, dz, cfg, tuple(w.shape), (bound, shape), w.dtype)
-        if want_db and db is None:
-            db = ba._BiasSum.apply(dz, 1)
+                dw = _launch_wgrad(pieces, dz, cfg, tuple(w.shape), w.dtype, pieces=(bound, shape))
         dres = dz if ctx.needs_input_grad[7] else None
         return dx, None, dw, db, None, None, None, dres, None
 
@@ -763,27 +719,19 @@ def blur_conv2d_s2_bias_act(x, f, weight, pad4, flip_filter=False, bias=None, ac
     """``bias_act(conv2d(upfirdn2d(x, f, padding=pad4, flip_filter=flip_filter), weight, stride=2) [+ residual], bias, ...)`` with the blurred
     tensor as producer-written operand pieces (``pieces_available`` says whether the kernels exist for these shapes)."""
     from . import bias_act as ba
-    spec = ba.activation_funcs[act]
-    alpha = float(alpha if alpha is not None else spec.def_alpha)
-    gain = float(gain if gain is not None else spec.def_gain)
-    clampf = float(clamp if clamp is not None else -1)
+    act_cfg = ba.act_cfg(act, alpha, gain, clamp)
     assert act in FUSABLE_ACTS
     cfg = _Cfg((False, 2, 0, 0, 0, 0, 1, float(wgain)))
     ucfg = (int(pad4[0]), int(pad4[1]), int(pad4[2]), int(pad4[3]), bool(flip_filter), 1.0)
     if passthrough and torch.is_grad_enabled() and x.requires_grad:
-        y, again = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, (act, alpha, gain, clampf), residual, True)
-        hit = getattr(x, '_pasta_amax', None)
-        if hit is not None and not again.is_inference():
-            again._pasta_amax = hit
-        return y, again
-    y = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, (act, alpha, gain, clampf), residual)
+        y, again = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, act_cfg, residual, True)
+        return y, _hand_over(x, again)
+    y = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, act_cfg, residual)
     return (y, x) if passthrough else y
 
 _LINEAR_EPILOGUE = ('linear', 0.0, 1.0, -1.0)      # (act, alpha, gain, clamp) of an epilogue that only adds the residual
 
 FUSABLE_ACTS = ('linear', 'relu', 'lrelu')
-
-_cat1x1_cache = {}
 
 def cat1x1_available(x, x2, weight):
     """Will ``conv2d_cat1x1_bias_act`` run as ONE launch over the two tensors (the pointwise kernel, pasta_conv2d_plan kernel 9)?"""
@@ -791,15 +739,9 @@ def cat1x1_available(x, x2, weight):
             and x2.shape[2:] == x.shape[2:] and tuple(weight.shape[2:]) == (1, 1) and weight.shape[1] == x.shape[1] + x2.shape[1]
             and conv_math in ('default', 'f16x3') and x.numel() > 0):
         return False
-    key = (int(x.shape[0]), int(x.shape[1]), int(x2.shape[1]), int(x.shape[2]), int(x.shape[3]), int(weight.shape[0]))
-    hit = _cat1x1_cache.get(key)
-    if hit is None:
-        n, c1, c2, h, w_, o = key
-        desc = _desc(_Cfg((False, 1, 0, 0, 0, 0, 1, 1.0)), (n, c1 + c2, h, w_), o, h, w_, 1, 1)
-        kernel = ctypes.c_int()
-        hit = _native.lib().pasta_conv2d_plan(ctypes.byref(desc), 4, None, None, None, None, ctypes.byref(kernel)) == 0 and kernel.value == 9
-        _cat1x1_cache[key] = hit
-    return hit
+    n, h, w_ = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    desc = _desc(_Cfg((False, 1, 0, 0, 0, 0, 1, 1.0)), (n, int(x.shape[1]) + int(x2.shape[1]), h, w_), int(weight.shape[0]), h, w_, 1, 1)
+    return _plan('conv', desc, PLAN_EPILOGUE).kernel == 9
 
 class _CatConv1x1BiasActHip(torch.autograd.Function):
     """``bias_act(conv2d(cat([x, x2], 1), w), b)`` for a 1x1 weight in one launch over the two tensors; the backward is assembled from the
@@ -808,30 +750,18 @@ class _CatConv1x1BiasActHip(torch.autograd.Function):
     results are concatenated (a few hundred KB)."""
     @staticmethod
     def forward(ctx, x, x2, w, b, wgain, act_cfg):
-        act, alpha, gain, clamp = act_cfg
-        from . import bias_act as ba
         cfg = _Cfg((False, 1, 0, 0, 0, 0, 1, float(wgain)))
         used = {}
-        y = _launch_conv(x, w, cfg, epilogue=(b, ba.activation_funcs[act].cuda_idx, alpha, gain, clamp, None), x2=x2, used=used)
-        keep_y = act != 'linear' or clamp >= 0
-        ctx.save_for_backward(x, x2, w, b, y if keep_y else None)
+        y = _launch_conv(x, w, cfg, epilogue=_act_epilogue(b, act_cfg), x2=x2, used=used)
         ctx.cfg, ctx.act_cfg, ctx.amax = cfg, act_cfg, (used.get('x_amax'), used.get('x2_amax'))
-        return y
+        return _save_epilogue_output(ctx, y, act_cfg, (x, x2, w, b), tape=False)
 
     @staticmethod
     def backward(ctx, dy):
-        from . import bias_act as ba
         x, x2, w, b, y = ctx.saved_tensors
-        act, alpha, gain, clamp = ctx.act_cfg
         cfg = ctx.cfg
-        dz = dy
-        dx = dx2 = dw = db = None
-        want_db = b is not None and ctx.needs_input_grad[3]
-        if act != 'linear' or gain != 1 or clamp >= 0:
-            if want_db:
-                dz, db = ba.grad_with_bias_grad(dy.contiguous(), y, (1, act, alpha, gain, clamp))
-            else:
-                dz = ba._BiasActHipGrad.apply(dy.contiguous(), None, None, y, (1, act, alpha, gain, clamp))
+        dx = dx2 = dw = None
+        dz, db = _epilogue_grad(dy, y, b, ctx.act_cfg, ctx.needs_input_grad[3])
         c1 = x.shape[1]
         gcfg = _grad_cfg(cfg, x.shape[2:], dz.shape[2:], 1, 1)
         if ctx.needs_input_grad[0]:
@@ -841,21 +771,16 @@ class _CatConv1x1BiasActHip(torch.autograd.Function):
         if ctx.needs_input_grad[2] and not weight_gradients_disabled:
             dw = torch.cat([_ConvWgradHip.apply(dz, x, cfg, (w.shape[0], c1, 1, 1), w.dtype, ctx.amax[0]),
                             _ConvWgradHip.apply(dz, x2, cfg, (w.shape[0], w.shape[1] - c1, 1, 1), w.dtype, ctx.amax[1])], dim=1)
-        if want_db and db is None:
-            db = ba._BiasSum.apply(dz, 1)
         return dx, dx2, dw, db, None, None
 
 def conv2d_cat1x1_bias_act(x, x2, weight, bias=None, act='linear', alpha=None, gain=None, clamp=None, wgain=1.0):
     """``bias_act(conv2d(torch.cat([x, x2], 1), weight), bias, ...)`` for a 1x1 ``weight`` without the concatenated tensor
     (``cat1x1_available`` says whether the one-launch form exists for these shapes; otherwise the concatenation is formed)."""
     from . import bias_act as ba
-    spec = ba.activation_funcs[act]
-    alpha = float(alpha if alpha is not None else spec.def_alpha)
-    gain = float(gain if gain is not None else spec.def_gain)
-    clampf = float(clamp if clamp is not None else -1)
+    act_cfg = ba.act_cfg(act, alpha, gain, clamp)
     if act in FUSABLE_ACTS and cat1x1_available(x, x2, weight):
-        return _CatConv1x1BiasActHip.apply(x, x2, weight, bias, float(wgain), (act, alpha, gain, clampf))
-    return conv2d_bias_act(torch.cat([x, x2], dim=1), weight, bias, act=act, alpha=alpha, gain=gain, clamp=clamp, wgain=wgain)
+        return _CatConv1x1BiasActHip.apply(x, x2, weight, bias, float(wgain), act_cfg)
+    return conv2d_bias_act(torch.cat([x, x2], dim=1), weight, bias, act=act, alpha=act_cfg[1], gain=act_cfg[2], clamp=clamp, wgain=wgain)
 
 def conv2d_bias_act(input, weight, bias=None, stride=1, padding=0, groups=1, act='linear', alpha=None, gain=None, clamp=None, wgain=1.0,
                     residual=None, passthrough=False):
@@ -863,30 +788,21 @@ def conv2d_bias_act(input, weight, bias=None, stride=1, padding=0, groups=1, act
     act in FUSABLE_ACTS); other cases run the ops separately.  ``passthrough=True`` returns ``(y, input')`` where ``input'`` is the
     input again, for its other consumers: see ``_ConvBiasActHip``."""
     from . import bias_act as ba
-    spec = ba.activation_funcs[act]
-    alpha = float(alpha if alpha is not None else spec.def_alpha)
-    gain = float(gain if gain is not None else spec.def_gain)
-    clampf = float(clamp if clamp is not None else -1)
+    act_cfg = ba.act_cfg(act, alpha, gain, clamp)
     if act in FUSABLE_ACTS and input.dtype in IO_CODES and input.device.type == 'cuda' and input.numel() > 0:
         sh, sw = _pair(stride)
         ph, pw = _pair(padding)
         assert sh == sw
         cfg = _Cfg((False, sh, ph, pw, 0, 0, int(groups), float(wgain)))
         if passthrough and torch.is_grad_enabled() and input.requires_grad:
-            y, again = _ConvBiasActHip.apply(input, weight, bias, cfg, (act, alpha, gain, clampf), residual, True)
-            hit = getattr(input, '_pasta_amax', None)      # the view autograd made of the input is the same data at the same version: its maxima go along
-            if hit is not None and not again.is_inference():
-                again._pasta_amax = hit
-            hit = _shared_lookup(input)                     # ... and its packed pieces (share_pieces), for the next reader
-            if hit is not None and not again.is_inference():
-                again._pasta_pieces = (again._version, again.data_ptr()) + hit[2:]
-            return y, again
-        y = _ConvBiasActHip.apply(input, weight, bias, cfg, (act, alpha, gain, clampf), residual)
+            y, again = _ConvBiasActHip.apply(input, weight, bias, cfg, act_cfg, residual, True)
+            return y, _hand_over(input, again, pieces=True)
+        y = _ConvBiasActHip.apply(input, weight, bias, cfg, act_cfg, residual)
         return (y, input) if passthrough else y
     y = conv2d(input, weight, stride=stride, padding=padding, groups=groups, wgain=wgain)
     if residual is not None:
         y = y + residual
-    y = ba.bias_act(y, bias, act=act, alpha=alpha, gain=gain, clamp=clamp)
+    y = ba.bias_act(y, bias, act=act, alpha=act_cfg[1], gain=act_cfg[2], clamp=clamp)
     return (y, input) if passthrough else y
 
 def modulated_conv2d_forward(x, weight, styles, dcoefs=None, stride=1, padding=0, transposed=False, per_sample=False, tail=None):
@@ -912,14 +828,11 @@ def modulated_conv2d_forward(x, weight, styles, dcoefs=None, stride=1, padding=0
     assert sh == sw
     epilogue = noise = None
     if tail is not None:
-        spec = ba.activation_funcs[tail['act']]
         assert tail['act'] in FUSABLE_ACTS
         bias = tail.get('bias')
         if bias is not None and per_sample:
             bias = bias.repeat(n)                       # the grouped launch has N * O output channels
-        epilogue = (bias, spec.cuda_idx, float(tail['alpha'] if tail.get('alpha') is not None else spec.def_alpha),
-                    float(tail['gain'] if tail.get('gain') is not None else spec.def_gain),
-                    float(tail['clamp'] if tail.get('clamp') is not None else -1))
+        epilogue = _act_epilogue(bias, ba.act_cfg(tail['act'], tail.get('alpha'), tail.get('gain'), tail.get('clamp')))
         if tail.get('noise') is not None:
             noise = (tail['noise'], tail['strength'])
     if per_sample:
@@ -945,7 +858,6 @@ def modulated_conv2d_forward(x, weight, styles, dcoefs=None, stride=1, padding=0
 # gradient + plane_dot(dx, x) (two reads): seven passes over the activation per modulated layer.  
 
 _MODCONV = True         # False: scale_planes + the plain convolution, as the reference (tests compare the two)
-_modconv_cache = {}
 
 def modconv_available(x, weight, styles, stride=1, padding=0, transposed=False):
     """Does ``modulated_conv2d_shared`` run natively for these operands (else the caller scales the planes itself)?"""
@@ -953,41 +865,20 @@ def modconv_available(x, weight, styles, stride=1, padding=0, transposed=False):
             and conv_math in ('default', 'f16x3') and not transposed and stride == 1):
         return False
     ph, pw = _pair(padding)
-    key = (tuple(x.shape), tuple(weight.shape), ph, pw)
-    hit = _modconv_cache.get(key)
-    if hit is None:
-        cfg = _Cfg((False, 1, ph, pw, 0, 0, 1, 1.0))
-        kh, kw = int(weight.shape[2]), int(weight.shape[3])
-        oh, ow = _out_hw(cfg, x.shape[2], x.shape[3], kh, kw)
-        desc = _desc(cfg, x.shape, int(weight.shape[0]), oh, ow, kh, kw)
-        hit = _native.lib().pasta_conv2d_wgrad_modulated_workspace(ctypes.byref(desc)) >= 0
-        _modconv_cache[key] = hit
-    return hit
+    cfg = _Cfg((False, 1, ph, pw, 0, 0, 1, 1.0))
+    kh, kw = int(weight.shape[2]), int(weight.shape[3])
+    oh, ow = _out_hw(cfg, x.shape[2], x.shape[3], kh, kw)
+    return _plan('wgrad_modulated', _desc(cfg, x.shape, int(weight.shape[0]), oh, ow, kh, kw)).ok
 
 def _launch_wgrad_modulated(x, dy, cfg, styles, w, x_amax=None):
-    """(dw, dstyles) of ``conv(x * styles, w)`` given dy: pasta_conv2d_wgrad_modulated."""
+    """(dw, dstyles) of ``conv(x * styles, w)`` given dy: pasta_conv2d_wgrad_modulated (``modconv_available`` says where it exists)."""
     _native.require_gpu(x, 'conv2d_wgrad_modulated')
-    kh, kw = int(w.shape[2]), int(w.shape[3])
     x, dy = _f32(x).contiguous(), _f32(dy).contiguous()
     styles, w32 = _f32(styles).contiguous(), _f32(w).contiguous()
-    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], kh, kw)
-    lib = _native.lib()
-    nbytes = lib.pasta_conv2d_wgrad_modulated_workspace(ctypes.byref(desc))
-    if nbytes < 0:
-        raise RuntimeError('conv2d_wgrad_modulated: no sample-aligned weight-gradient kernel for this shape (modconv_available tells beforehand)')
-    work = torch.empty([max(nbytes // 4, 4)], dtype=torch.float32, device=x.device)
+    desc = _desc(cfg, x.shape, dy.shape[1], dy.shape[2], dy.shape[3], int(w.shape[2]), int(w.shape[3]))
     dw = torch.empty(list(w.shape), dtype=torch.float32, device=x.device)
     ds = torch.empty([x.shape[0], x.shape[1]], dtype=torch.float32, device=x.device)
-    amax_x, amax_dy = (x_amax if x_amax is not None else tensor_amax(x)), tensor_amax(dy)
-    desc.x_amax, desc.dy_amax = amax_x.data_ptr(), amax_dy.data_ptr()
-    def launch():
-        with torch.cuda.device(x.device):
-            _native.check(lib.pasta_conv2d_wgrad_modulated(_native.ptr(x), _native.ptr(dy), _native.ptr(styles), _native.ptr(w32), _native.ptr(dw), _native.ptr(ds),
-                                                           ctypes.byref(desc), _native.ptr(work), work.numel() * 4, _native.stream()))
-    if launch_hook is None:
-        launch()
-    else:
-        launch_hook('wgrad', desc, launch, 0)
+    _wgrad_issue('wgrad_modulated', desc, x, dy, x_amax, True, _native.lib().pasta_conv2d_wgrad_modulated, (x, dy, styles, w32, dw, ds), dw)
     return dw, ds
 
 class _ModConvHip(torch.autograd.Function):

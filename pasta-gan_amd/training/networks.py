@@ -320,10 +320,9 @@ def mod_bias_act(u, dcoefs, noise, strength, bias, act='lrelu', alpha=None, gain
     unit noise ([H,W] or [N,1,H,W]) and ``strength`` the 0-dim strength parameter (both None = no noise).
     First-order differentiable (the generator takes no double backward)."""
     _native.require_gpu(u, 'mod_bias_act')
-    spec = bias_act.activation_funcs[act]
     assert act in ('linear', 'lrelu') and u.dtype in _HIP_DTYPES
-    cfg = (spec.cuda_idx, float(alpha if alpha is not None else spec.def_alpha), float(gain if gain is not None else spec.def_gain),
-           float(clamp if clamp is not None else -1))
+    _, alpha, gain, clamp = bias_act.act_cfg(act, alpha, gain, clamp)
+    cfg = (bias_act.activation_funcs[act].cuda_idx, alpha, gain, clamp)
     return _ModBiasAct.apply(u, dcoefs, noise, strength, bias, cfg)
 
 #----------------------------------------------------------------------------

@@ -86,3 +86,41 @@ def test_layer_with_epilogue_and_second_derivative():
 
     for u, v in zip(run(False), run(True)):
         assert torch.equal(u, v)
+
+
+@pytest.mark.parametrize('fused', [False, True])
+def test_arithmetic_switched_between_forward_and_backward(fused):
+    """The workspace packed for the input gradient belongs to the descriptor it was packed for: a backward under another arithmetic than its
+    forward packs for itself and gives, bit for bit, what it gives without pair packing."""
+    from torch_utils.ops import conv2d_gradfix as cg
+    g = torch.Generator().manual_seed(5)
+    x0 = torch.randn([9, 32, 32, 32], generator=g).cuda()
+    w0 = (torch.randn([64, 32, 3, 3], generator=g) * 0.1).cuda()
+    b0 = torch.randn([64], generator=g).cuda()
+    dy = torch.randn([9, 64, 32, 32], generator=g).cuda()
+    calls = []
+    real = cg._pack_pair
+
+    def counted(x, w, cfg):
+        r = real(x, w, cfg)
+        calls.append(r[0] is not None)
+        return r
+
+    def run(pair):
+        old = cg._PACK_PAIR, cg._pack_pair, cg.conv_math
+        cg._PACK_PAIR, cg._pack_pair = pair, counted
+        try:
+            x, w = x0.clone().requires_grad_(True), w0.clone().requires_grad_(True)
+            cg.conv_math = 'f16x3'
+            y = cg.conv2d_bias_act(x, w, b0, padding=1, act='lrelu') if fused else cg.conv2d(x, w, padding=1)
+            cg.conv_math = 'bf16x6'
+            gx, gw = torch.autograd.grad(y, [x, w], dy)
+        finally:
+            cg._PACK_PAIR, cg._pack_pair, cg.conv_math = old
+        return y.detach(), gx, gw
+
+    a = run(False)
+    b = run(True)
+    assert calls == [False, True]          # the paired run did pack both orientations in its forward
+    for u, v in zip(a, b):
+        assert torch.equal(u, v)

@@ -138,7 +138,7 @@ def test_results_do_not_depend_on_which_power_of_two_scaled_the_operand():
         pieces, bound, shape = cg.blur_pieces(x, f, (2, 2, 2, 2), x_amax=parts * mul)
         assert torch.equal(bound, parts * mul * (bound.max() / (parts.max() * mul)))       # the same row, scaled
         ys.append(cg._launch_conv(pieces, w, cfg, pieces=(bound, shape)))
-        dws.append(cg._launch_wgrad_pieces(pieces, dy, cfg, tuple(w.shape), (bound, shape)))
+        dws.append(cg._launch_wgrad(pieces, dy, cfg, tuple(w.shape), pieces=(bound, shape)))
     for y, dw in zip(ys[1:], dws[1:]):
         assert torch.equal(y, ys[0]) and torch.equal(dw, dws[0])
     # and the values are right (fp64)
@@ -167,7 +167,7 @@ def test_weight_gradient_from_pieces_per_tap_and_ragged_channels():
     assert cg.pieces_available(x, f, w, (2, 2, 2, 2))
     cfg = cg._Cfg((False, 2, 0, 0, 0, 0, 1, 0.5))              # a weight gain rides in the reduction
     pieces, bound, shape = cg.blur_pieces(x, f, (2, 2, 2, 2))
-    dw = cg._launch_wgrad_pieces(pieces, dy, cfg, tuple(w.shape), (bound, shape))
+    dw = cg._launch_wgrad(pieces, dy, cfg, tuple(w.shape), pieces=(bound, shape))
     xb = torch.nn.functional.conv2d(torch.nn.functional.pad(x.double().cpu(), [2, 2, 2, 2]).reshape(n * ci, 1, h + 4, h + 4),
                                     f.double().cpu().flip([0, 1])[None, None]).reshape(n, ci, h + 1, h + 1)
     w64 = w.double().cpu().requires_grad_(True)

@@ -134,7 +134,7 @@ def down_path(args):
         stages = [('blur fp32', lambda: upfirdn2d.upfirdn2d(x, f, padding=[2, 2, 2, 2]), None), ('blur pieces', lambda: cg.blur_pieces(x, f, (2, 2, 2, 2), x_amax=parts), None),
                   ('fwd fp32', lambda: cg._launch_conv(xb, w, cfg), flops), ('fwd pieces', lambda: cg._launch_conv(pieces, w, cfg, pieces=(bound, shape)), flops),
                   ('wgrad fp32', lambda: cg._launch_wgrad(xb, dy, cfg, tuple(w.shape)), flops),
-                  ('wgrad pieces', lambda: cg._launch_wgrad_pieces(pieces, dy, cfg, tuple(w.shape), (bound, shape)), flops)]
+                  ('wgrad pieces', lambda: cg._launch_wgrad(pieces, dy, cfg, tuple(w.shape), pieces=(bound, shape)), flops)]
         for tag, fn, fl in stages:
             ms = timeit(fn, args.reps)
             print(f'{name:28s} {tag:14s} {ms:8.3f} {(fl / ms / 1e9) if fl else (nbytes / ms / 1e6):14.1f}', flush=True)

@@ -1,7 +1,9 @@
 """Is the training step energy-bound?  The dominant convolution alone in a loop, then interleaved with a memory-bound copy of growing size:
 if the socket's power cap averages over more than a kernel, the convolution behind a low-power kernel runs faster than in the pure loop."""
+import os
 import sys
-sys.path.insert(0, '/root/repo/pasta-gan_amd')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'pasta-gan_amd'))
 import torch
 from torch_utils.ops import conv2d_gradfix as cg, _native
 dev = torch.device('cuda')
