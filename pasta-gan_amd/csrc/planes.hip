@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const T* __restrict__ x,
 }
 
 //------------------------------------------------------------------------------------
-// out[plane] = sum_hw p*q (q may be null).  One workgroup per plane, fixed summation order.
+// out[plane] = sum_hw p*q (q may be null).  One workgroup per plane, fixed summation order; 16-byte accesses when HW % 4 == 0
+// and both operands are 16-byte aligned (a contiguous view at an element offset takes the scalar loop).
 
 template <class T>
 __global__ __launch_bounds__(256) void plane_dot_kernel(const T* __restrict__ p, const T* __restrict__ q,
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void plane_dot_kernel(const T* __restrict__ p,
         const T* pp = p + plane * HW;
         const T* qp = q ? q + plane * HW : nullptr;
         float acc = 0.f;
-        if ((HW & 3) == 0) {
+        if ((HW & 3) == 0 && ((((uintptr_t)p | (uintptr_t)q) & 15) == 0)) {
             for (int64_t i = threadIdx.x; i < HW / 4; i += 256) {
                 float4 a = ld4<T>(pp + 4 * i);
                 if (qp) { float4 b = ld4<T>(qp + 4 * i); acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(1024) void masked_mean_fill_kernel(const float* __r
 //   y = clamp(act(u * d[n,c] + noise[n|.,hw] * strength + b[c]) * gain),   act = linear (1) or leaky relu (3)
 // and its backward: with dz = dy * act'(y) * gain (zero where |y| >= clamp)
 //   du = dz * d[n,c],   partial[n,c][chunk] = (sum dz*u, sum dz*noise, sum dz)  -> dd[n,c], dstrength, db[c] on the host.
-// One workgroup per (plane, chunk of 4096 elements); 16-byte accesses when HW % 4 == 0.
+// One workgroup per (plane, chunk of 4096 elements); 16-byte accesses when HW % 4 == 0 and every operand is 16-byte aligned.
 constexpr int MBA_CHUNK = 4096;
 
 __device__ __forceinline__ float mba_fwd(float u, float d, float nz, float b, int act, float alpha, float gain, float clamp) {
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(256) void mod_bias_act_kernel(const T* __restrict__
     const float* np_ = noise ? noise + (noise_per_sample ? (int64_t)n * HW : 0) : nullptr;
     T* yp = y + plane * HW;
     const int64_t i0 = (int64_t)blockIdx.y * MBA_CHUNK, i1 = i0 + MBA_CHUNK < HW ? i0 + MBA_CHUNK : HW;
-    if ((HW & 3) == 0) {
+    if ((HW & 3) == 0 && ((((uintptr_t)u | (uintptr_t)y | (uintptr_t)noise) & 15) == 0)) {
         // the chunk's four fetches per operand first, then the arithmetic and the stores: 64 - 128 bytes in flight per thread
         constexpr int U = MBA_CHUNK / 1024;
         float4 uv[U], nv[U];
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(256) void mod_bias_act_bwd_kernel(const T* __restri
     T* dup = du + plane * HW;
     const int64_t i0 = (int64_t)blockIdx.y * MBA_CHUNK, i1 = i0 + MBA_CHUNK < HW ? i0 + MBA_CHUNK : HW;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    if ((HW & 3) == 0) {
+    if ((HW & 3) == 0 && ((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)u | (uintptr_t)du | (uintptr_t)noise) & 15) == 0)) {
         constexpr int U = MBA_CHUNK / 1024;             // fetches first, as in the forward kernel
         float4 gvs[U], yvs[U], uvs[U], nvs[U];
 #pragma unroll
@@ -529,7 +530,6 @@ extern "C" int pasta_plane_dot(const void* p, const void* q, float* out, int dty
     using namespace pasta;
     PASTA_CHECK(p && out, "plane_dot: null pointer");
     PASTA_CHECK(planes >= 1 && HW >= 1, "plane_dot: empty tensor");
-    PASTA_CHECK((((uintptr_t)p | (uintptr_t)q) & 15) == 0 || (HW & 3) != 0, "plane_dot: operands must be 16-byte aligned");
     int grid = (int)(planes < 65535 ? planes : 65535);
 #define PASTA_L(T) hipLaunchKernelGGL(plane_dot_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)p, (const T*)q, out, planes, HW)
     PASTA_BY_DTYPE(dtype, "plane_dot", PASTA_L)
@@ -676,7 +676,6 @@ extern "C" int pasta_mod_bias_act(const void* u, const float* d, const float* no
     PASTA_CHECK(N >= 1 && C >= 1 && HW >= 1, "mod_bias_act: empty tensor");
     PASTA_CHECK(act == 1 || act == 3, "mod_bias_act: activation code %d (linear = 1 and lrelu = 3 are supported)", act);
     PASTA_CHECK(!noise || strength, "mod_bias_act: noise without strength");
-    PASTA_CHECK(((HW & 3) != 0) || ((((uintptr_t)u | (uintptr_t)y | (uintptr_t)noise) & 15) == 0), "mod_bias_act: pointers must be 16-byte aligned");
     const int64_t chunks = (HW + MBA_CHUNK - 1) / MBA_CHUNK;
     PASTA_CHECK(chunks <= 65535 && (int64_t)N * C <= INT32_MAX, "mod_bias_act: tensor too large");
 #define PASTA_L(T) hipLaunchKernelGGL(mod_bias_act_kernel<T>, dim3((unsigned)(N * C), (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, (const T*)u, d, noise, \
@@ -698,8 +697,6 @@ extern "C" int pasta_mod_bias_act_bwd(const void* dy, const void* y, const void*
     PASTA_CHECK(dy && y && u && du && partial, "mod_bias_act_bwd: null pointer");
     PASTA_CHECK(N >= 1 && C >= 1 && HW >= 1, "mod_bias_act_bwd: empty tensor");
     PASTA_CHECK(act == 1 || act == 3, "mod_bias_act_bwd: activation code %d (linear = 1 and lrelu = 3 are supported)", act);
-    PASTA_CHECK(((HW & 3) != 0) || ((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)u | (uintptr_t)du | (uintptr_t)noise) & 15) == 0),
-                "mod_bias_act_bwd: pointers must be 16-byte aligned");
     const int64_t chunks = (HW + MBA_CHUNK - 1) / MBA_CHUNK;
     PASTA_CHECK(chunks <= 65535 && (int64_t)N * C <= INT32_MAX, "mod_bias_act_bwd: tensor too large");
 #define PASTA_L(T) hipLaunchKernelGGL(mod_bias_act_bwd_kernel<T>, dim3((unsigned)(N * C), (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, \

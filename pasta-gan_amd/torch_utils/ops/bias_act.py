@@ -122,9 +122,12 @@ def _bias_grad(dx, dim):
     _native.check(st)
     return db
 
-def _grad_db_workspace(dy, dim, act_idx):
-    """Bytes of scratch for the fused (dx, db) launch, 0 when the case is not covered by it."""
+def _grad_db_workspace(dy, dim, act_idx, y=None):
+    """Bytes of scratch for the fused (dx, db) launch, 0 when the case is not covered by it.  The kernel moves 16-byte packs, so a
+    contiguous view at an element offset (autograd hands such a ``grad_output`` on unchanged) takes the two-launch path."""
     if dy.device.type != 'cuda' or dy.dtype not in (torch.float32, torch.float16, torch.bfloat16) or not dy.is_contiguous() or dy.numel() == 0:
+        return 0
+    if (dy.data_ptr() | (y.data_ptr() if y is not None else 0)) & 15:
         return 0
     return _native.lib().pasta_bias_act_grad_db_workspace(_native.dtype_code(dy, 'bias_act'), dy.numel(), dy.shape[dim], dy.stride(dim), act_idx)
 
@@ -149,7 +152,7 @@ def grad_with_bias_grad(dy, y, cfg):
     dim, act, alpha, gain, clamp = cfg
     spec = activation_funcs[act]
     if not spec.has_2nd_grad and 'x' not in spec.ref:
-        nbytes = _grad_db_workspace(dy, dim, spec.cuda_idx)
+        nbytes = _grad_db_workspace(dy, dim, spec.cuda_idx, y)
         if nbytes > 0:
             return _BiasActHipGradDb.apply(dy, y, cfg)
     dx = _BiasActHipGrad.apply(dy, None, None, y, cfg)
@@ -236,7 +239,7 @@ class _BiasActHipGradDb(torch.autograd.Function):
     def forward(ctx, dy, y, cfg):
         dim, act, alpha, gain, clamp = cfg
         spec = activation_funcs[act]
-        nbytes = _grad_db_workspace(dy, dim, spec.cuda_idx)
+        nbytes = _grad_db_workspace(dy, dim, spec.cuda_idx, y)
         dx, db = _launch_grad_db(dy, y, dim, spec.cuda_idx, alpha, gain, clamp, nbytes)
         ctx.save_for_backward(y)
         ctx.cfg = cfg

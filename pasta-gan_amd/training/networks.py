@@ -277,6 +277,8 @@ class _ModBiasAct(torch.autograd.Function):
             per_sample = int(noise.numel() == n * h * w and n > 1)
             assert noise.numel() in (h * w, n * h * w)
             noise = noise.contiguous()
+        strength = strength.contiguous() if strength is not None else None
+        b = b.contiguous() if b is not None else None
         y = torch.empty_like(u)
         # producer maxima for the large planes (one commit per 4096-element workgroup, most of them skipped by the look at the slot): the layer's
         # output is the operand of the next modulated convolution, whose launch would scan it (round 4: 150.35 -> 150.0 ms same box; small
@@ -321,6 +323,22 @@ def mod_bias_act(u, dcoefs, noise, strength, bias, act='lrelu', alpha=None, gain
     First-order differentiable (the generator takes no double backward)."""
     _native.require_gpu(u, 'mod_bias_act')
     assert act in ('linear', 'lrelu') and u.dtype in _HIP_DTYPES
+    n, c, h, w = u.shape
+    # the kernel reads dcoefs, noise, strength and bias as fp32 on u's device, whatever the storage type of u (differentiable conversions)
+    def f32(t, name, sizes):
+        if t is None:
+            return None
+        if not t.is_floating_point() or t.numel() not in sizes:
+            raise RuntimeError(f'mod_bias_act: {name} must be a floating-point tensor of {" or ".join(map(str, sizes))} elements, '
+                               f'got {t.dtype} {tuple(t.shape)}')
+        return t.to(device=u.device, dtype=torch.float32)
+    dcoefs, bias, noise, strength = (f32(dcoefs, 'dcoefs', (n * c,)), f32(bias, 'bias', (c,)), f32(noise, 'noise', (h * w, n * h * w)),
+                                     f32(strength, 'strength', (1,)))
+    if noise is not None and strength is None:
+        raise RuntimeError('mod_bias_act: noise without strength')
+    # the shapes the backward's gradients have: dd [N, C], db [C], dstrength []
+    dcoefs, bias = (dcoefs.reshape(n, c) if dcoefs is not None else None), (bias.reshape(c) if bias is not None else None)
+    strength = strength.reshape([]) if strength is not None else None
     _, alpha, gain, clamp = bias_act.act_cfg(act, alpha, gain, clamp)
     cfg = (bias_act.activation_funcs[act].cuda_idx, alpha, gain, clamp)
     return _ModBiasAct.apply(u, dcoefs, noise, strength, bias, cfg)

@@ -8,6 +8,7 @@ import torch
 
 from conftest import load_golden, rel_err
 from oracle import ref_ops as R
+import storage_ref as S
 
 pytestmark = pytest.mark.gpu
 
@@ -66,29 +67,46 @@ LIVE_UPFIRDN = [   # shapes of SURVEY.md 2.2 / 8(a1), scaled down in N and C onl
 ]
 
 
+def _upfirdn_storage_check(x, f, dy, y, dx, dtype, kw):
+    """y and dx of a 16-bit upfirdn2d against fp64 from the same rounded inputs: the filter taps summed in fp32 and stored once
+    (tests/storage_ref.py); the scale of an element is the same filter applied to |x| with |f|."""
+    x64, f64, dy64 = x.double().requires_grad_(True), f.double(), dy.double()
+    yr = R.upfirdn2d(x64, f64, **kw)
+    dxr, = torch.autograd.grad(yr, x64, dy64)
+    xa = x.double().abs().requires_grad_(True)
+    ys = R.upfirdn2d(xa, f64.abs(), **kw)
+    dxs, = torch.autograd.grad(ys, xa, dy64.abs())
+    k = f.numel() + 2
+    S.assert_stored(y, yr.detach(), dtype, ys.detach(), k=k, what='y')
+    S.assert_stored(dx, dxr, dtype, dxs, k=k, what='dx')
+
+
 @pytest.mark.parametrize('idx', range(len(LIVE_UPFIRDN)))
-@pytest.mark.parametrize('dtype', [torch.float32, torch.float16])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.bfloat16])
 def test_upfirdn2d_live_shapes(idx, dtype):
     from torch_utils.ops import upfirdn2d
     c = LIVE_UPFIRDN[idx]
     gen = torch.Generator().manual_seed(idx)
     xc = torch.randn(c['shape'], generator=gen)
-    if dtype == torch.float16:
-        xc = xc.half().float()
+    if dtype != torch.float32:
+        xc = xc.to(dtype).float()
     f = R.setup_filter([1, 3, 3, 1])
     xr = xc.clone().requires_grad_(True)
     yr = R.upfirdn2d(xr, f, **c['kw'])
     dyc = torch.randn(yr.shape, generator=gen)
-    if dtype == torch.float16:
-        dyc = dyc.half().float()
+    if dtype != torch.float32:
+        dyc = dyc.to(dtype).float()
     dxr, = torch.autograd.grad(yr, xr, dyc)
     x = xc.to('cuda', dtype).requires_grad_(True)
     y = upfirdn2d.upfirdn2d(x, f.cuda(), **c['kw'])
     assert y.dtype == dtype and y.shape == yr.shape
     dx, = torch.autograd.grad(y, x, dyc.to('cuda', dtype))
-    tol = TOL if dtype == torch.float32 else TOL_FP16
-    assert rel_err(y.float(), yr) < tol
-    assert rel_err(dx.float(), dxr) < tol
+    if dtype != torch.bfloat16:
+        tol = TOL if dtype == torch.float32 else TOL_FP16
+        assert rel_err(y.float(), yr) < tol
+        assert rel_err(dx.float(), dxr) < tol
+    if dtype != torch.float32:
+        _upfirdn_storage_check(xc, f, dyc, y, dx, dtype, c['kw'])
 
 
 NONSQUARE_UPFIRDN = [   # planes whose one dimension is k*tile + 1 and whose other ends inside a tile (ADVICE r2, high)
@@ -137,6 +155,22 @@ def test_upfirdn2d_nonsquare_planes_stay_inside_their_plane(idx):
     assert rel_err(out, yr) < TOL
     assert float(parts.max()) == float(out.abs().max()) and float(parts.min()) >= 0      # producer-side |max| of the output
     assert bool(torch.isnan(buf[:n]).all()) and bool(torch.isnan(buf[2 * n:]).all()), 'stores outside the output tensor'
+
+
+@pytest.mark.parametrize('idx', range(len(NONSQUARE_UPFIRDN)))
+@pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
+def test_upfirdn2d_nonsquare_planes_16bit(idx, dtype):
+    from torch_utils.ops import upfirdn2d
+    c = NONSQUARE_UPFIRDN[idx]
+    gen = torch.Generator().manual_seed(200 + idx)
+    xc = torch.randn(c['shape'], generator=gen).to(dtype).float()
+    f = R.setup_filter([1, 3, 3, 1])
+    x = xc.to('cuda', dtype).requires_grad_(True)
+    y = upfirdn2d.upfirdn2d(x, f.cuda(), **c['kw'])
+    dyc = torch.randn(y.shape, generator=gen).to(dtype).float()
+    dx, = torch.autograd.grad(y, x, dyc.to('cuda', dtype))
+    assert y.dtype == dtype and dx.dtype == dtype
+    _upfirdn_storage_check(xc, f, dyc, y, dx, dtype, c['kw'])
 
 
 def test_upfirdn2d_channels_last_and_fp64():
@@ -206,7 +240,7 @@ def test_bias_act_golden(idx):
     assert rel_err(g_x, g[n + '.g_x']) < 2e-5 or float(np.abs(g[n + '.g_x']).max()) == 0.0, n
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.float64])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.float64, torch.bfloat16])
 @pytest.mark.parametrize('shape', [[4, 64, 64, 64], [3, 7, 33, 31], [16, 512]])
 def test_bias_act_large(shape, dtype):
     from torch_utils.ops import bias_act
@@ -215,8 +249,8 @@ def test_bias_act_large(shape, dtype):
     bc = torch.randn([shape[1]], generator=gen).to(dtype)
     xr = xc.double().requires_grad_(True)
     br = bc.double().requires_grad_(True)
-    # fp16 storage rounds y onto the clamp value itself, which moves the gradient mask; clamp only in fp32/fp64.
-    clamp = None if dtype == torch.float16 else 1.5
+    # 16-bit storage rounds y onto the clamp value itself, which moves the gradient mask; clamp only in fp32/fp64.
+    clamp = None if dtype in (torch.float16, torch.bfloat16) else 1.5
     yr = R.bias_act(xr, br, act='lrelu', gain=np.sqrt(2), clamp=clamp)
     dyc = torch.randn(shape, generator=gen).to(dtype)
     dxr, dbr = torch.autograd.grad(yr, [xr, br], dyc.double())
@@ -224,9 +258,35 @@ def test_bias_act_large(shape, dtype):
     b = bc.cuda().requires_grad_(True)
     y = bias_act.bias_act(x, b, act='lrelu', gain=np.sqrt(2), clamp=clamp)
     dx, db = torch.autograd.grad(y, [x, b], dyc.cuda())
-    tol = {torch.float32: TOL, torch.float16: TOL_FP16, torch.float64: 1e-6}[dtype]
     assert y.dtype == dtype
-    assert rel_err(y, yr) < tol and rel_err(dx, dxr) < tol and rel_err(db, dbr) < max(tol, 1e-4)
+    if dtype != torch.bfloat16:
+        tol = {torch.float32: TOL, torch.float16: TOL_FP16, torch.float64: 1e-6}[dtype]
+        assert rel_err(y, yr) < tol and rel_err(dx, dxr) < tol and rel_err(db, dbr) < max(tol, 1e-4)
+    if dtype in (torch.float16, torch.bfloat16):
+        _bias_act_storage_check(xc, bc, dyc, y, dx, db, dtype, 1, np.sqrt(2))
+
+
+def _bias_act_storage_check(xc, bc, dyc, y, dx, db, dtype, dim, gain, act='lrelu', clamp=None):
+    """16-bit bias_act against fp64 from the same rounded inputs (tests/storage_ref.py): y and dx are one fp32 evaluation and
+    one store; the slope and clamp mask of dx come from the stored y (bias_act.cu semantics); db is the fp32 sum of the STORED
+    dx (what the kernels sum), stored once."""
+    view = [-1 if i == dim else 1 for i in range(xc.ndim)]
+    pre = xc.double() + bc.double().reshape(view)
+    gain, alpha = float(np.float32(gain)), float(np.float32(0.2)) if act == 'lrelu' else 1.0      # as the kernel receives them
+    clamp = float(np.float32(clamp)) if clamp is not None else None
+    yr = torch.where(pre > 0, pre, pre * alpha) * gain
+    if clamp is not None:
+        yr = yr.clamp(-clamp, clamp)
+    S.assert_stored(y, yr, dtype, (xc.double().abs() + bc.double().abs().reshape(view)) * gain, k=4, what='y')
+    ys = y.detach().cpu().double()
+    dxr = dyc.double() * gain * torch.where(ys > 0, 1.0, alpha)
+    if clamp is not None:
+        dxr = torch.where((ys > -clamp) & (ys < clamp), dxr, torch.zeros_like(dxr))
+    S.assert_stored(dx, dxr, dtype, dxr.abs(), k=3, what='dx')
+    dxs = dx.detach().cpu().double()
+    other = [i for i in range(xc.ndim) if i != dim]
+    n = xc.numel() // xc.shape[dim]
+    S.assert_stored(db, dxs.sum(dim=other), dtype, dxs.abs().sum(dim=other), k=S.reduction_depth(n, 256, 8), bitwise=None, what='db')
 
 
 @pytest.mark.parametrize('act,gain,clamp', [('lrelu', np.sqrt(2), 1.0), ('relu', 1.0, None), ('linear', 0.5, None), ('linear', 1.0, 0.8)])
@@ -249,6 +309,27 @@ def test_bias_act_fused_grad_and_bias_grad(act, gain, clamp):
     out = run(bias_act.bias_act, xc.cuda(), bc.cuda(), dyc.cuda(), wc.cuda(), vc.cuda())
     for name, a, r in zip(['y', 'dx', 'db', 'g_dy'], out, ref):
         assert rel_err(a, r) < (1e-4 if name == 'db' else TOL), name
+
+
+@pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize('act,gain,clamp', [('lrelu', np.sqrt(2), 1.0), ('linear', 0.5, None)])
+def test_bias_act_fused_grad_and_bias_grad_16bit(dtype, act, gain, clamp):
+    """The one-pass (dx, db) kernel on 16-bit storage (8-element packs) with a ragged last chunk: a plane of 8 (1024 * 2 + 100)
+    elements is chunks of 1024, 1024 and 100 packs.  The last element of every plane is planted in dy."""
+    from torch_utils.ops import bias_act
+    shape = [2, 5, 48, 358]
+    assert 48 * 358 == 8 * (1024 * 2 + 100)
+    assert bias_act._grad_db_workspace(torch.empty(shape, device='cuda', dtype=dtype), 1, bias_act.activation_funcs[act].cuda_idx) == 2 * 5 * 3 * 4
+    gen = torch.Generator().manual_seed(6)
+    xc = torch.randn(shape, generator=gen).to(dtype).float()
+    bc = torch.randn([5], generator=gen).to(dtype).float()
+    dyc = torch.randn(shape, generator=gen)
+    dyc[:, :, -1, -1] = 40.0 * torch.arange(1, 6)
+    dyc = dyc.to(dtype).float()
+    x, b = xc.to('cuda', dtype).requires_grad_(True), bc.to('cuda', dtype).requires_grad_(True)
+    y = bias_act.bias_act(x, b, act=act, gain=gain, clamp=clamp)
+    dx, db = torch.autograd.grad(y, [x, b], dyc.to('cuda', dtype))
+    _bias_act_storage_check(xc, bc, dyc, y, dx, db, dtype, 1, gain, act, clamp)
 
 
 def test_bias_act_errors():
