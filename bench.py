@@ -1,6 +1,6 @@
 """Benchmark: PASTA-GAN 256x192 (tensor 256x256) training images/sec on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1: one process per GPU.  Started through ``torch.distributed.run`` (RANK / LOCAL_RANK / WORLD_SIZE in the environment)
 each process is one rank; started plainly, this process only spawns the N ranks itself -- before any GPU call, like the
@@ -9,9 +9,10 @@ reference's launcher (train_wo_flow_fullbody.py:393-400, 567) -- waits for them 
 A step = one iteration of the reference hot loop (training_loop_wo_flow_fullbody.py:484-529) on a
 synthetic, HBM-resident batch of 16 images per GPU: Gmain + Dmain every iteration, Dreg every 16th,
 Greg (a no-op besides the style encoder, pl_weight 0) every 4th, Adam steps and the EMA update.
-Prints ONE JSON line (rank 0) with the whole-job throughput, the roofline of the dominant kernel
-(measured with HIP events on the launch stream, inside the timed region) and a CPU baseline
-(the oracle restatement on the host cores, config 1 of BASELINE.json).
+Prints ONE JSON line (rank 0) with the whole-job throughput and the roofline of the dominant kernel
+(measured with HIP events on the launch stream, inside the timed region).  A plain run does nothing else;
+``--full`` appends what takes runs of its own: the side measurements of other precisions and sizes
+(``also_measured``) and a CPU baseline (the oracle restatement on the host cores, config 1 of BASELINE.json).
 """
 
 import argparse
@@ -456,9 +457,11 @@ def main():
     ap.add_argument('--d-fp16-res', type=int, default=0, help="discriminator blocks of the N highest resolutions store and multiply in fp16 "
                     "(networks.py:1107-1120).  The reference's train script sets 4 (train_wo_flow_fullbody.py:195-196); the headline keeps 0 = "
                     "everything fp32-equivalent, which is what the parity oracle (the reference's force_fp32 CPU path) computes")
-    ap.add_argument('--no-variants', action='store_true', help='skip the two reduced-precision side measurements (fp16 discriminator blocks as in '
-                    'the reference train script; bf16 activation storage = BASELINE config 5) that a default single-GPU run appends as `also_measured`')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='after the headline, also take the measurements that need runs of their own: `also_measured` '
+                    '(a single-GPU headline run: the same step at other arithmetic, precisions and sizes) and `cpu_baseline`')
+    ap.add_argument('--no-variants', action='store_true', help='--full: skip the side measurements (six-product arithmetic; fp16 discriminator blocks as in '
+                    'the reference train script; bf16 activation storage = BASELINE config 5) that a single-GPU run appends as `also_measured`')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--graph', action='store_true', help='--mode infer: also capture the forward as a hipGraph and time its replay (reported as hipgraph_replay)')
     ap.add_argument('--no-meter', action='store_true', help='do not bracket convolution launches with events')
     ap.add_argument('--replica-check', action='store_true', help='N > 1: after the timed steps compare the replicas (bitwise parameter checksums over all ranks) '
@@ -642,7 +645,7 @@ def main():
             for shape, calls, ms, tf in meter.by_shape()[:args.by_shape_top]:
                 print(f'{str(shape):70s} calls/step={calls / args.steps:6.1f} ms/step={ms / args.steps:8.2f} TF/s={tf:7.1f}', file=sys.stderr)
         headline_cfg = args.mode == 'train' and act is None and args.d_fp16_res == 0 and args.train_res == 256 and args.conv_math in (None, 'default')
-        if world == 1 and headline_cfg and not args.no_variants and args.aug == 'noaug' and args.vgg_weight <= 0:
+        if args.full and world == 1 and headline_cfg and not args.no_variants and args.aug == 'noaug' and args.vgg_weight <= 0:
             # Side measurements, AFTER the headline's timed region and never part of `value`: the same step at the precision the
             # reference's own train script uses for D, and in 16-bit activation storage (BASELINE config 5 at this resolution).
             del step
@@ -677,7 +680,7 @@ def main():
                 conv2d_gradfix.conv_math = math_before
                 del vstep, vdata
                 torch.cuda.empty_cache()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -20,6 +20,29 @@ def _run(extra_env, *args, timeout=900):
                           stderr=subprocess.PIPE, text=True, timeout=timeout)
 
 
+def _line(res):
+    assert res.returncode == 0, res.stderr[-4000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, res.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(1200)
+def test_plain_run_is_the_headline_alone_and_full_adds_the_side_measurements():
+    """A plain single-GPU run measures what its line's headline needs; ``--full`` appends the side measurements of other
+    precisions and sizes and the CPU baseline to the same line."""
+    plain = _line(_run({}, '--gpus', '1', '--steps', '1', '--warmup', '1'))
+    assert plain['n_gpus'] == 1 and plain['value'] > 0 and plain['ms_per_step'] > 0 and plain['dtype'] == 'f32'
+    assert plain['roofline']['frac'] > 0
+    assert 'also_measured' not in plain and 'cpu_baseline' not in plain
+    full = _line(_run({}, '--gpus', '1', '--steps', '1', '--warmup', '1', '--full'))
+    assert full['metric'] == plain['metric'] and full['value'] > 0
+    assert set(full['also_measured']) == {'conv_math_bf16x6', 'd_fp16_res_3', 'storage_bf16', 'storage_bf16_512'}
+    assert all(v['value'] > 0 for v in full['also_measured'].values())
+    assert full['cpu_baseline']['value'] > 0 and full['cpu_baseline']['unit'] == 'images/sec'
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='checks the failure path of a box without a GPU')
 def test_launcher_reports_a_failed_rank():
     res = _run({}, '--gpus', '2', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', timeout=300)

@@ -29,7 +29,7 @@ if stats:
     shutil.copy(stats[-1], os.path.join(P, f'{tag}_infer512_kernel_stats.csv'))
 path = os.path.join(P, f'{tag}_bench.jsonl')
 lines = [l for l in open(path).read().rstrip('\n').split('\n') if f'at {commit}' not in l]
-runs = {'bench_final': 'default run (with also_measured and cpu_baseline), same box as the kernel stats / PMC passes',
+runs = {'bench_final': '--full run (with also_measured and cpu_baseline), same box as the kernel stats / PMC passes',
         'bench_bf16_final': '--storage bf16', 'bench_bf16_512_final': '--storage bf16 --train-res 512 --batch-gpu 8 (config 5, one GPU)',
         'infer512_final': '--mode infer --res 512 (config 4)', 'infer256_final': '--mode infer --res 256'}
 for f, what in runs.items():
