@@ -489,6 +489,55 @@ int pasta_warp_perspective_u8(const uint8_t* src, const int32_t* src_index, cons
 int pasta_patch_composite_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
                              uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Per-sample preparation of the try-on data set (row f4; UvitonDatasetFull._load_raw_image / __getitem__,
+ * training/dataset.py:515-568, 619-736, 929-993, and the loop's conversions, training_loop_wo_flow_fullbody.py:425-456),
+ * which the reference runs on the host with OpenCV, pycocotools and skimage.  Each entry does a batch in one launch.
+ * The unpadded canvas is H x W (256 x 192), padded by lp = (H - W) / 2 columns on the left into an H x H square.
+ * Exact by construction: padding, label masks, gt_parsing, joint discs, the palm rule, the box dilation of a given fill,
+ * the erase rule and the float conversions.  Restated (parity with the libraries UNPINNED):
+ *   cv2.line(thickness=2)   -> every pixel centre within distance 1 of the segment (the capsule of half-width 1);
+ *   pycocotools rleFrPoly   -> its algorithm: corners (int)(5 x + .5), boundary points along each edge, a run toggles at
+ *                              ceil(clamp((v + .5) / 5 - .5, 0, h)) where the boundary steps from u = 5X + 2 to 5X + 3;
+ *   cv2.resize(INTER_LINEAR, uint8) -> OpenCV's scalar fixed point: (float)((d + .5) * scale - .5), 11-bit coefficients
+ *                              rint((1 - f) * 2048), rint(f * 2048); columns outside pinned, rows clamped;
+ *                              (b0 * row0 + b1 * row1 + 2^21) >> 22.
+ * ------------------------------------------------------------------------- */
+/* The pose stick figure (draw_pose_from_cords, dataset.py:704-736) into out [N, H, H, 3] (zero padding): per pixel of the
+ * canvas, the 19 limbs in order (limbs [N][19][5] int32 = x0, y0, x1, y1, drawn: int()-truncated key points, coordinates within
+ * +-4096), then the 18 joints (joints [N][18][3] = x, y, drawn) as the discs (r - y)^2 + (c - x)^2 < 4; the last hit wins,
+ * colour = kptcolors[index].  H <= 4096, W <= H. */
+int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, void* stream);
+
+/* The palm mask (get_palm, :682-702) into out [N, 256, 256] (0 / 1): parsing [N, 256, W] uint8 (unpadded labels);
+ * quads [N][4][4][2] doubles = the corners of get_rectangle_mask (in its order, padded coordinates within +-1e5) for the left
+ * upper arm, left forearm, right upper arm, right forearm; present [N][4]: 0 = the segment is missing (an all-ones mask).
+ * Each fill is dilated with a 25 x 25 (upper arm, offsets -12..12) or 16 x 16 box (forearm, offsets -8..7);
+ * palm = hand & !upper & !forearm per side (hand = label 14 left, 15 right), the sides OR-ed.  H must be 256. */
+int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H, int W,
+                       void* stream);
+
+/* :537-556 from image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H]: retain = shoes(18, 19) + palm +
+ * head(1, 2, 4, 13) and gt_parsing = upper(5, 6, 7) + 2 lower(9, 12) + 3 hands(14, 15) + 4 legs(16, 17) + 5 neck(10), [N, H, H];
+ * upper_img / lower_img = mask * padded image (pad 255) and upper_mask / lower_mask = 255 * mask, [N, H, H, 3] (the inputs
+ * of patch_pipeline.normalize_batch). */
+int pasta_tryon_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain, uint8_t* gt_parsing,
+                         uint8_t* upper_img, uint8_t* lower_img, uint8_t* upper_mask, uint8_t* lower_mask, int N, int H, int W,
+                         void* stream);
+
+/* After the warps: the erase mask erase = (arm_masks[2] + arm_masks[3] + resize(erase_masks, H x H)) > 0 in uint8 arithmetic
+ * (the reference's += on uint8 wraps), then the nine fp32 NCHW tensors of SyntheticFullBodyBatch.KEYS, in that order, through
+ * outputs (a HOST array of 9 device pointers): real_img [N,3,H,H], style_input [N,c_upper+c_lower,ph,pw], retain [N,3,H,H],
+ * pose [N,6,H,H], denorm_upper_input / denorm_lower_input [N,3,H,H], denorm_upper_mask / denorm_lower_mask [N,1,H,H],
+ * gt_parsing [N,1,H,H].  x / 127.5 - 1 is evaluated as torch does on the GPU: x * (1 / 127.5f) - 1.
+ * image [N,H,W,3]; stick, denorm_upper, denorm_lower [N,H,H,3]; retain_mask, gt_parsing [N,H,H]; norm_img [N,ph,pw,c_upper];
+ * norm_img_lower [N,ph,pw,c_lower]; arm_masks [N,4,H,H]; erase_masks [N,mh_max,mw_max] with each sample's (h, w) in
+ * erase_hw [N][2] int32 (1 <= h <= mh_max, 1 <= w <= mw_max). */
+int pasta_tryon_assemble(const uint8_t* image, const uint8_t* stick, const uint8_t* retain_mask, const uint8_t* gt_parsing,
+                         const uint8_t* norm_img, const uint8_t* norm_img_lower, const uint8_t* denorm_upper, const uint8_t* denorm_lower,
+                         const uint8_t* arm_masks, const uint8_t* erase_masks, const int32_t* erase_hw, float* const* outputs, int N,
+                         int H, int W, int ph, int pw, int c_upper, int c_lower, int mh_max, int mw_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

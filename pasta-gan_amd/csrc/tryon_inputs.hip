@@ -1,0 +1,326 @@
+// Per-sample preparation of the try-on data set on the GPU (row f4, the part of UvitonDatasetFull._load_raw_image /
+// __getitem__ and of the training loop's float conversions that is not the body-part warps of csrc/patches.hip):
+//   pasta_pose_stickman_u8  the pose stick figure (draw_pose_from_cords, dataset.py:704-736), padded;
+//   pasta_palm_mask_u8      the palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702);
+//   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556);
+//   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456).
+// Every entry does a whole batch in one launch.  The reference does this on the host with OpenCV, pycocotools and skimage.
+// What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
+// DESIGN.md section 9): cv2.line(thickness=2), pycocotools' rleFrPoly and cv2.resize(INTER_LINEAR) on uint8.
+#include "common.h"
+
+namespace pasta {
+
+// The library is compiled with -ffp-contract=fast, which fuses a * b + c into one fma whatever a pragma says.  The polygon,
+// resize and float-conversion arithmetic below must round every product on its own (as the C, numpy and torch expressions it
+// restates do): tr_rounded() makes the product a value the compiler cannot fuse into the next addition.
+__device__ __forceinline__ float tr_rounded(float x) { __asm__ volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ double tr_rounded(double x) { __asm__ volatile("" : "+v"(x)); return x; }
+
+__constant__ uint8_t kpt_colors[19][3] = {          // dataset.py kptcolors
+    {255, 0, 0}, {255, 85, 0}, {255, 170, 0}, {255, 255, 0}, {170, 255, 0}, {85, 255, 0}, {0, 255, 0}, {0, 255, 85},
+    {0, 255, 170}, {0, 255, 255}, {0, 170, 255}, {0, 85, 255}, {0, 0, 255}, {85, 0, 255}, {170, 0, 255}, {255, 0, 255},
+    {255, 0, 170}, {255, 0, 85}, {255, 0, 0}};
+
+constexpr int TRYON_LIMBS = 19, TRYON_JOINTS = 18;
+
+// The pixel (px, py) lies within distance 1 (the half-thickness) of the segment a -> b: the capsule of a thickness-2 line.
+__device__ __forceinline__ bool capsule_hit(int px, int py, int x0, int y0, int x1, int y1) {
+    const int64_t dx = x1 - x0, dy = y1 - y0, ux = px - x0, uy = py - y0;
+    const int64_t len2 = dx * dx + dy * dy, t = ux * dx + uy * dy;
+    if (len2 == 0 || t <= 0) return ux * ux + uy * uy <= 1;
+    if (t >= len2) { const int64_t vx = px - x1, vy = py - y1; return vx * vx + vy * vy <= 1; }
+    const int64_t cr = ux * dy - uy * dx;
+    return cr * cr <= len2;
+}
+
+// out[n, y, x, :] for the padded H x H square: limbs in order, then the 3 x 3 joint discs, the last hit wins.
+__global__ __launch_bounds__(256) void pose_stickman_kernel(const int32_t* __restrict__ limbs, const int32_t* __restrict__ joints,
+                                                            uint8_t* __restrict__ out, int H, int W, int lp) {
+    const int n = blockIdx.y;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= H * H) return;
+    const int y = pix / H, c = pix - y * H - lp;         // c: column of the unpadded canvas
+    int color = -1;
+    if (c >= 0 && c < W) {
+        const int32_t* lb = limbs + (int64_t)n * TRYON_LIMBS * 5;
+        for (int i = 0; i < TRYON_LIMBS; i++, lb += 5)
+            if (lb[4] && capsule_hit(c, y, lb[0], lb[1], lb[2], lb[3])) color = i;
+        const int32_t* jt = joints + (int64_t)n * TRYON_JOINTS * 3;
+        for (int j = 0; j < TRYON_JOINTS; j++, jt += 3) {
+            const int ddx = c - jt[0], ddy = y - jt[1];
+            if (jt[2] && ddx >= -1 && ddx <= 1 && ddy >= -1 && ddy <= 1) color = j;     // (r - y)^2 + (c - x)^2 < 4
+        }
+    }
+    uint8_t* o = out + ((int64_t)n * H * H + pix) * 3;
+    o[0] = color < 0 ? 0 : kpt_colors[color][0];
+    o[1] = color < 0 ? 0 : kpt_colors[color][1];
+    o[2] = color < 0 ? 0 : kpt_colors[color][2];
+}
+
+// ---- palm mask ----
+
+constexpr int PALM_S = 256;         // get_hand_mask works on a 256 x 256 square
+constexpr int PALM_BAND = 16;       // output rows per block
+constexpr int PALM_SEGS = 4;        // left upper arm, left forearm, right upper arm, right forearm
+
+// rleFrPoly's boundary points: u = t + xs, v = (int)(ys + s * t + .5) (dx >= dy), or v = t + ys, u = (int)(xs + s * t + .5)
+__device__ __forceinline__ int rle_round(double a, double s, int t) { return (int)(a + tr_rounded(s * (double)t) + .5); }
+
+// The y boundary of edge (xs, ys) -> (xe, ye) (5x upsampled integers) at pixel column X: the smaller v of the two consecutive
+// boundary points whose u are 5X + 2 and 5X + 3, turned into the row where the run toggles; -1 when the edge does not cross.
+__device__ int rle_edge_crossing(int xs, int ys, int xe, int ye, int X, int h) {
+    const int dx = abs(xe - xs), dy = abs(ys - ye);
+    const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
+    if (flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
+    const int u0 = 5 * X + 2;
+    int vmin;
+    if (dx >= dy) {
+        if (dx == 0) return -1;
+        const double s = (double)(ye - ys) / dx;
+        if (u0 < xs || u0 + 1 > xs + dx) return -1;
+        const int t = u0 - xs;
+        const int v1 = rle_round(ys, s, t), v2 = rle_round(ys, s, t + 1);
+        vmin = v1 < v2 ? v1 : v2;
+    } else {
+        const double s = (double)(xe - xs) / dy;
+        const int ua = rle_round(xs, s, 0), ub = rle_round(xs, s, dy);
+        const bool up = ub >= ua;
+        if (up ? !(ua <= u0 && ub >= u0 + 1) : !(ua >= u0 + 1 && ub <= u0)) return -1;
+        int lo = 1, hi = dy;                   // the first t past the step: u(t) >= u0 + 1 (rising) or u(t) <= u0 (falling)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int u = rle_round(xs, s, mid);
+            if (up ? u >= u0 + 1 : u <= u0) hi = mid; else lo = mid + 1;
+        }
+        vmin = ys + lo - 1;
+    }
+    double yd = ((double)vmin + .5) / 5 - .5;
+    if (yd < 0) yd = 0; else if (yd > h) yd = h;
+    return (int)ceil(yd);
+}
+
+// Fill of the quadrilateral `q` (4 corners, x then y, doubles) at column X: up to two runs [r[0], r[1]) and [r[2], r[3]).
+__device__ void rle_column_runs(const double* __restrict__ q, int X, int h, int16_t* r) {
+    int x[5], y[5];
+    for (int j = 0; j < 4; j++) { x[j] = (int)(tr_rounded(5.0 * q[2 * j]) + .5); y[j] = (int)(tr_rounded(5.0 * q[2 * j + 1]) + .5); }
+    x[4] = x[0]; y[4] = y[0];
+    int c[4], k = 0;
+    for (int j = 0; j < 4; j++) {
+        const int v = rle_edge_crossing(x[j], y[j], x[j + 1], y[j + 1], X, h);
+        if (v >= 0) {                          // insertion into the sorted list
+            int i = k++;
+            while (i > 0 && c[i - 1] > v) { c[i] = c[i - 1]; i--; }
+            c[i] = v;
+        }
+    }
+    for (int i = k; i < 4; i++) c[i] = h;     // an odd count toggles to the end of the column
+    for (int i = 0; i < 4; i++) r[i] = (int16_t)c[i];
+}
+
+__device__ __forceinline__ bool dilated_hit(const int16_t (*runs)[4], int X, int y, int lo, int hi, int S) {
+    const int x0 = X - lo < 0 ? 0 : X - lo, x1 = X + hi > S - 1 ? S - 1 : X + hi;
+    const int y0 = y - lo, y1 = y + hi;
+    for (int xx = x0; xx <= x1; xx++) {
+        const int16_t* r = runs[xx];
+        if ((r[0] < r[1] && r[0] <= y1 && r[1] - 1 >= y0) || (r[2] < r[3] && r[2] <= y1 && r[3] - 1 >= y0)) return true;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(256) void palm_mask_kernel(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
+                                                        const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int H, int W, int lp) {
+    __shared__ int16_t runs[PALM_SEGS][PALM_S][4];
+    const int n = blockIdx.y;
+    const int X = threadIdx.x;
+    const uint8_t* pres = present + n * PALM_SEGS;
+    for (int sgm = 0; sgm < PALM_SEGS; sgm++)
+        if (pres[sgm]) rle_column_runs(quads + ((int64_t)n * PALM_SEGS + sgm) * 8, X, PALM_S, runs[sgm][X]);
+    __syncthreads();
+    const uint8_t* lab = parsing + (int64_t)n * H * W;
+    for (int yy = 0; yy < PALM_BAND; yy++) {
+        const int y = blockIdx.x * PALM_BAND + yy;
+        const int c = X - lp;
+        const int label = (c >= 0 && c < W) ? lab[(int64_t)y * W + c] : 0;
+        int palm = 0;
+        if (label == 14 || label == 15) {     // hand: left = 14 (segments 0, 1), right = 15 (segments 2, 3)
+            const int s0 = label == 14 ? 0 : 2;
+            // a missing segment is an all-ones mask; boxes 25 x 25 (offsets -12..12) and 16 x 16 (anchor 8: -8..7)
+            const bool up = !pres[s0] || dilated_hit(runs[s0], X, y, 12, 12, PALM_S);
+            const bool bottom = !pres[s0 + 1] || dilated_hit(runs[s0 + 1], X, y, 8, 7, PALM_S);
+            palm = !up && !bottom;
+        }
+        out[((int64_t)n * H + y) * H + X] = (uint8_t)palm;
+    }
+}
+
+// ---- label masks ----
+
+__global__ __launch_bounds__(256) void tryon_masks_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ parsing,
+                                                          const uint8_t* __restrict__ palm, uint8_t* __restrict__ retain,
+                                                          uint8_t* __restrict__ gt, uint8_t* __restrict__ upper_img,
+                                                          uint8_t* __restrict__ lower_img, uint8_t* __restrict__ upper_mask,
+                                                          uint8_t* __restrict__ lower_mask, int H, int W, int lp) {
+    const int n = blockIdx.y;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= H * H) return;
+    const int y = pix / H, c = pix - y * H - lp;
+    const bool inside = c >= 0 && c < W;
+    const int64_t src = (int64_t)n * H * W + (int64_t)y * W + c;
+    const int L = inside ? parsing[src] : 0;
+    const int64_t o = (int64_t)n * H * H + pix;
+    const int shoes = L == 18 || L == 19, head = L == 1 || L == 2 || L == 4 || L == 13;
+    const int up = L == 5 || L == 6 || L == 7, low = L == 9 || L == 12;
+    const int hands = L == 14 || L == 15, legs = L == 16 || L == 17, neck = L == 10;
+    retain[o] = (uint8_t)(shoes + palm[o] + head);
+    gt[o] = (uint8_t)(up + low * 2 + hands * 3 + legs * 4 + neck * 5);
+    for (int ch = 0; ch < 3; ch++) {
+        const int v = inside ? image[src * 3 + ch] : 255;
+        upper_img[o * 3 + ch] = (uint8_t)(up * v);
+        lower_img[o * 3 + ch] = (uint8_t)(low * v);
+        upper_mask[o * 3 + ch] = (uint8_t)(up * 255);
+        lower_mask[o * 3 + ch] = (uint8_t)(low * 255);
+    }
+}
+
+// ---- erase mask and float conversions ----
+
+// cv2.resize(INTER_LINEAR) on uint8, one axis: source index and the two 11-bit coefficients of destination index d.
+__device__ __forceinline__ void resize_taps(int d, double scale, int size, bool clamp_coord, int& s0, int& s1, int& a0, int& a1) {
+    float f = (float)(tr_rounded(((double)d + 0.5) * scale) - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (clamp_coord) {                         // columns: coordinates outside the source are pinned with weight (1, 0)
+        if (s < 0) { f = 0.f; s = 0; }
+        if (s >= size - 1) { f = 0.f; s = size - 1; }
+    }
+    a0 = (int)rintf((1.f - f) * 2048.f);
+    a1 = (int)rintf(f * 2048.f);
+    s0 = s < 0 ? 0 : s > size - 1 ? size - 1 : s;          // rows: the row index is clamped, the weights are kept
+    s1 = s + 1 < 0 ? 0 : s + 1 > size - 1 ? size - 1 : s + 1;
+}
+
+__device__ __forceinline__ float to_unit(int v) {           // torch's x / 127.5 - 1 on the GPU: x * (1 / 127.5f) - 1
+    const float inv = 1.0f / 127.5f;
+    return tr_rounded((float)v * inv) - 1.0f;
+}
+
+struct TryonOut {
+    float *real_img, *style_input, *retain, *pose, *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask, *denorm_lower_mask,
+          *gt_parsing;
+};
+
+__global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ stick,
+                                                             const uint8_t* __restrict__ retain_mask, const uint8_t* __restrict__ gt,
+                                                             const uint8_t* __restrict__ norm_img, const uint8_t* __restrict__ norm_lower,
+                                                             const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l,
+                                                             const uint8_t* __restrict__ arm_masks, const uint8_t* __restrict__ erase_src,
+                                                             const int32_t* __restrict__ erase_hw, TryonOut o, int H, int W, int lp,
+                                                             int ph, int pw, int CU, int CL, int mh_max, int mw_max) {
+    const int n = blockIdx.y;
+    const int HH = H * H;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= HH) {                           // style_input = cat(norm_img, norm_img_lower) / 127.5 - 1 at (ph, pw)
+        const int q = pix - HH;
+        if (q >= ph * pw) return;
+        const int CS = CU + CL;
+        for (int ch = 0; ch < CS; ch++) {
+            const int v = ch < CU ? norm_img[((int64_t)n * ph * pw + q) * CU + ch] : norm_lower[((int64_t)n * ph * pw + q) * CL + ch - CU];
+            o.style_input[((int64_t)n * CS + ch) * ph * pw + q] = to_unit(v);
+        }
+        return;
+    }
+    const int y = pix / H, x = pix - y * H, c = x - lp;
+    const bool inside = c >= 0 && c < W;
+    const int64_t p = (int64_t)n * HH + pix;
+
+    // erase = (hand_mask[2] + hand_mask[3] + resize(acgpn)) in uint8 (wrapping) > 0
+    const int mh = erase_hw[2 * n], mw = erase_hw[2 * n + 1];
+    int sx0, sx1, ax0, ax1, sy0, sy1, by0, by1;
+    resize_taps(x, (double)mw / H, mw, true, sx0, sx1, ax0, ax1);
+    resize_taps(y, (double)mh / H, mh, false, sy0, sy1, by0, by1);
+    const uint8_t* m = erase_src + (int64_t)n * mh_max * mw_max;
+    const int r0 = m[(int64_t)sy0 * mw_max + sx0] * ax0 + m[(int64_t)sy0 * mw_max + sx1] * ax1;
+    const int r1 = m[(int64_t)sy1 * mw_max + sx0] * ax0 + m[(int64_t)sy1 * mw_max + sx1] * ax1;
+    int rs = (int)(((int64_t)r0 * by0 + (int64_t)r1 * by1 + (1 << 21)) >> 22);
+    rs = rs < 0 ? 0 : rs > 255 ? 255 : rs;
+    const int sum8 = (arm_masks[((int64_t)n * 4 + 2) * HH + pix] + arm_masks[((int64_t)n * 4 + 3) * HH + pix] + rs) & 255;
+    const int keep = sum8 > 0 ? 0 : 1;
+
+    const int rm = retain_mask[p];
+    int su = 0, sl = 0;
+    for (int ch = 0; ch < 3; ch++) {
+        const int64_t oc = ((int64_t)n * 3 + ch) * HH + pix;
+        const float real = to_unit(inside ? image[((int64_t)n * H * W + (int64_t)y * W + c) * 3 + ch] : 255);
+        o.real_img[oc] = real;
+        const float ret = tr_rounded((float)rm * real) - (float)(uint8_t)(1 - rm);
+        o.retain[oc] = ret;
+        o.pose[((int64_t)n * 6 + ch) * HH + pix] = to_unit(stick[p * 3 + ch]);
+        o.pose[((int64_t)n * 6 + 3 + ch) * HH + pix] = ret;
+        const int u = den_u[p * 3 + ch] * keep, l = den_l[p * 3 + ch] * keep;
+        su += u; sl += l;
+        o.denorm_upper_input[oc] = to_unit(u);
+        o.denorm_lower_input[oc] = to_unit(l);
+    }
+    o.denorm_upper_mask[p] = su > 0 ? 1.f : 0.f;
+    o.denorm_lower_mask[p] = sl > 0 ? 1.f : 0.f;
+    o.gt_parsing[p] = (float)gt[p];
+}
+
+}  // namespace pasta
+
+extern "C" int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(limbs && joints && out, "pose_stickman_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "pose_stickman_u8: bad shape");
+    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(pose_stickman_kernel, grid, dim3(256), 0, (hipStream_t)stream, limbs, joints, out, H, W, (H - W) / 2);
+    return launch_status("pose_stickman_u8");
+}
+
+extern "C" int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H,
+                                  int W, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(parsing && quads && present && out, "palm_mask_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H == PALM_S && W >= 1 && W <= H, "palm_mask_u8: bad shape (the padded square is 256 x 256)");
+    dim3 grid((unsigned)(PALM_S / PALM_BAND), (unsigned)N);
+    hipLaunchKernelGGL(palm_mask_kernel, grid, dim3(PALM_S), 0, (hipStream_t)stream, parsing, quads, present, out, H, W, (H - W) / 2);
+    return launch_status("palm_mask_u8");
+}
+
+extern "C" int pasta_tryon_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain, uint8_t* gt_parsing,
+                                    uint8_t* upper_img, uint8_t* lower_img, uint8_t* upper_mask, uint8_t* lower_mask, int N, int H, int W,
+                                    void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && parsing && palm && retain && gt_parsing && upper_img && lower_img && upper_mask && lower_mask,
+                "tryon_masks_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "tryon_masks_u8: bad shape");
+    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, retain, gt_parsing, upper_img,
+                       lower_img, upper_mask, lower_mask, H, W, (H - W) / 2);
+    return launch_status("tryon_masks_u8");
+}
+
+extern "C" int pasta_tryon_assemble(const uint8_t* image, const uint8_t* stick, const uint8_t* retain_mask, const uint8_t* gt_parsing,
+                                    const uint8_t* norm_img, const uint8_t* norm_img_lower, const uint8_t* denorm_upper,
+                                    const uint8_t* denorm_lower, const uint8_t* arm_masks, const uint8_t* erase_masks,
+                                    const int32_t* erase_hw, float* const* outputs, int N, int H, int W, int ph, int pw, int c_upper,
+                                    int c_lower, int mh_max, int mw_max, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && stick && retain_mask && gt_parsing && norm_img && norm_img_lower && denorm_upper && denorm_lower && arm_masks &&
+                erase_masks && erase_hw && outputs, "tryon_assemble: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && ph >= 1 && pw >= 1 && c_upper >= 1 && c_lower >= 1 &&
+                mh_max >= 1 && mw_max >= 1, "tryon_assemble: bad shape");
+    TryonOut o;
+    float** f[9] = {&o.real_img, &o.style_input, &o.retain, &o.pose, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask,
+                    &o.denorm_lower_mask, &o.gt_parsing};
+    for (int i = 0; i < 9; i++) {
+        PASTA_CHECK(outputs[i], "tryon_assemble: output %d is null", i);
+        *f[i] = outputs[i];
+    }
+    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, stick, retain_mask, gt_parsing, norm_img,
+                       norm_img_lower, denorm_upper, denorm_lower, arm_masks, erase_masks, erase_hw, o, H, W, (H - W) / 2, ph, pw, c_upper,
+                       c_lower, mh_max, mw_max);
+    return launch_status("tryon_assemble");
+}

@@ -1,0 +1,175 @@
+"""The try-on training data set of the reference (training/dataset.py: ``Dataset`` :54-185, ``UvitonDatasetFull`` :426-995),
+reading the same directory layout with PIL and ``json`` only.
+
+Difference from the reference, by design: ``UvitonDatasetFull.__getitem__`` returns the RAW sample -- the decoded files -- and
+not the prepared 13-tuple.  The preparation (stick figure, palm / retain masks, garment images and masks, body-part warps, erase
+mask, float conversions) runs for a whole batch on the GPU in ``training.tryon_batch.FullBodyBatchBuilder``; ``collate`` turns
+a list of raw samples into the batch the builder takes.  Only directory data sets are supported, as in the reference."""
+
+import json
+import os
+
+import numpy as np
+import PIL.Image
+import torch
+
+SUB_DATASETS = ('Zalando_256_192', 'Zalora_256_192', 'Deepfashion_256_192', 'MPV_256_192')     # dataset.py:435
+PAIR_LIST = 'train_pairs_front_list_0508.txt'
+
+#----------------------------------------------------------------------------
+
+class Dataset(torch.utils.data.Dataset):
+    """The reference's base class (dataset.py:54-185) without its unused label machinery."""
+
+    def __init__(self, name, raw_shape, max_size=None, use_labels=False, xflip=False, random_seed=0):
+        if xflip:
+            raise ValueError('xflip=True is not supported: no caller of the reference sets it, and its flip of the prepared tuple is undefined')
+        self._name = name
+        self._raw_shape = list(raw_shape)
+        self._use_labels = use_labels
+        self._raw_idx = np.arange(self._raw_shape[0], dtype=np.int64)
+        if (max_size is not None) and (self._raw_idx.size > max_size):
+            np.random.RandomState(random_seed).shuffle(self._raw_idx)
+            self._raw_idx = np.sort(self._raw_idx[:max_size])
+        self._xflip = np.zeros(self._raw_idx.size, dtype=np.uint8)
+
+    def close(self):
+        pass
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self._raw_idx.size
+
+    @property
+    def name(self):
+        return self._name
+
+    @property
+    def image_shape(self):
+        return list(self._raw_shape[1:])
+
+    @property
+    def num_channels(self):
+        assert len(self.image_shape) == 3  # CHW
+        return self.image_shape[0]
+
+    @property
+    def resolution(self):
+        assert len(self.image_shape) == 3  # CHW
+        assert self.image_shape[1] == self.image_shape[2]
+        return self.image_shape[1]
+
+    @property
+    def vis_index(self):
+        return self._vis_index
+
+#----------------------------------------------------------------------------
+
+def read_channel0(path):
+    """Channel 0 of ``cv2.imread(path)`` (BGR): the blue component, which for a palette image is that of the palette colour,
+    not the index; for a grayscale file the value itself."""
+    with PIL.Image.open(path) as img:
+        if img.mode == 'L':
+            return np.array(img)
+        return np.ascontiguousarray(np.array(img.convert('RGB'))[..., 2])
+
+
+def read_keypoints(path):
+    """``people[0].pose_keypoints_2d`` as float64 [18, 3], zeros when ``people`` is empty (dataset.py:738-746)."""
+    with open(path, 'r') as f:
+        data = json.load(f)
+    if len(data['people']) == 0:
+        return np.zeros((18, 3))
+    return np.array(data['people'][0]['pose_keypoints_2d'], dtype=np.float64).reshape(-1, 3)
+
+
+class UvitonDatasetFull(Dataset):
+    """dataset.py:426-995 -- file lists, ``_vis_index`` and the ACGPN erase masks of a directory tree; ``__getitem__``
+    returns the raw sample (see the module docstring): a dict with
+    ``image`` uint8 [H, W, 3], ``parsing`` uint8 [H, W] (channel 0 as cv2.imread reads it), ``keypoints`` float64 [18, 3],
+    ``erase_mask`` uint8 [h, w] (channel 0 of the ACGPN mask file ``raw_idx % count``, whatever its size) and ``raw_idx``.
+    Key points stay float64 because the reference truncates and offsets them in float64."""
+
+    def __init__(self, path, resolution=None, **super_kwargs):
+        self._path = path
+        if not os.path.isdir(self._path):
+            raise IOError('Path must point to a directory')
+        self._type = 'dir'
+        self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
+        for dataset in SUB_DATASETS:
+            with open(os.path.join(self._path, dataset, PAIR_LIST), 'r') as f:
+                for person in f.readlines():
+                    if not person.strip():
+                        continue
+                    person = person.strip().split()[0]
+                    self._image_fnames.append(os.path.join(dataset, 'image', person))
+                    self._kpt_fnames.append(os.path.join(dataset, 'keypoints', person.replace('.jpg', '_keypoints.json')))
+                    label = person.replace('.jpg', '.png') if dataset == 'MPV_256_192' else person.replace('.jpg', '_label.png')
+                    self._parsing_fnames.append(os.path.join(dataset, 'parsing', label))
+
+        vis_index = []
+        for image_name in sorted(os.listdir(os.path.join(self._path, 'train_img_vis'))):         # :461-472
+            if os.path.exists(os.path.join(self._path, 'Zalando_256_192', 'image', image_name)):
+                vis_index.append(self._image_fnames.index(os.path.join('Zalando_256_192', 'image', image_name)))
+            elif os.path.exists(os.path.join(self._path, 'Deepfashion_256_192', 'image', 'train', image_name)):
+                vis_index.append(self._image_fnames.index(os.path.join('Deepfashion_256_192', 'image', 'train', image_name)))
+        self._vis_index = vis_index
+
+        acgpn_dir = os.path.join(self._path, 'train_random_mask_acgpn')
+        self._random_mask_acgpn_fnames = [os.path.join(acgpn_dir, name) for name in os.listdir(acgpn_dir)]     # os.listdir order (:476)
+        self._mask_acgpn_numbers = len(self._random_mask_acgpn_fnames)
+
+        PIL.Image.init()
+        if len(self._image_fnames) == 0:
+            raise IOError('No image files found in the specified path')
+        h, w, c = self._load_image(0).shape
+        raw_shape = [len(self._image_fnames), c, h, h]         # the padded square, as the reference's image_shape
+        if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
+            raise IOError('Image files do not match the specified resolution')
+        super().__init__(name=os.path.splitext(os.path.basename(self._path))[0], raw_shape=raw_shape, **super_kwargs)
+
+    def _load_image(self, raw_idx):
+        image = np.array(PIL.Image.open(os.path.join(self._path, self._image_fnames[raw_idx])))
+        if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < image.shape[1]:
+            raise IOError('%s: expected an RGB image at least as tall as wide, got %s' % (self._image_fnames[raw_idx], image.shape))
+        return image
+
+    def load_raw(self, raw_idx):
+        image = self._load_image(raw_idx)
+        parsing = read_channel0(os.path.join(self._path, self._parsing_fnames[raw_idx]))
+        if parsing.shape != image.shape[:2]:
+            raise IOError('%s: label map %s does not match the image %s' % (self._parsing_fnames[raw_idx], parsing.shape, image.shape[:2]))
+        keypoints = read_keypoints(os.path.join(self._path, self._kpt_fnames[raw_idx]))
+        erase = read_channel0(self._random_mask_acgpn_fnames[raw_idx % self._mask_acgpn_numbers])
+        return dict(image=image, parsing=parsing, keypoints=keypoints, erase_mask=erase, raw_idx=int(raw_idx))
+
+    def __getitem__(self, idx):
+        return self.load_raw(self._raw_idx[idx])
+
+#----------------------------------------------------------------------------
+
+def collate(samples):
+    """A list of raw samples -> one batch: ``image`` uint8 [N, H, W, 3], ``parsing`` uint8 [N, H, W], ``keypoints`` float64
+    [N, 18, 3], ``erase_masks`` uint8 [N, h_max, w_max] (each mask in the top-left corner) with ``erase_hw`` int32 [N, 2]
+    (its own size), ``raw_idx`` int64 [N].  Use as the DataLoader's ``collate_fn``."""
+    n = len(samples)
+    h_max = max(s['erase_mask'].shape[0] for s in samples)
+    w_max = max(s['erase_mask'].shape[1] for s in samples)
+    erase = np.zeros([n, h_max, w_max], np.uint8)
+    erase_hw = np.zeros([n, 2], np.int32)
+    for i, s in enumerate(samples):
+        h, w = s['erase_mask'].shape
+        erase[i, :h, :w] = s['erase_mask']
+        erase_hw[i] = h, w
+    return dict(image=torch.from_numpy(np.stack([s['image'] for s in samples])),
+                parsing=torch.from_numpy(np.stack([s['parsing'] for s in samples])),
+                keypoints=torch.from_numpy(np.stack([s['keypoints'] for s in samples])),
+                erase_masks=torch.from_numpy(erase), erase_hw=torch.from_numpy(erase_hw),
+                raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
+
+#----------------------------------------------------------------------------

@@ -8,9 +8,10 @@ One process per GPU; gradients are all-reduced by RCCL (``backend='nccl'`` on RO
 with backward: by default through one ``FlatGradReducer`` per optimised module (``ddp_mode='flat'``,
 training/grad_reducer.py), or through the reference's five DistributedDataParallel wrappers (``ddp_mode='torch'``).
 
-Dataset loading, snapshots, image grids, ADA and metrics of the reference loop are host
-orchestration outside this path; ``SyntheticFullBodyBatch`` supplies tensors of the dataset's
-shapes (training_loop...:289-297, 425-456) directly in HBM.
+Snapshots, image grids and metrics of the reference loop are host orchestration outside this path.
+``SyntheticFullBodyBatch`` supplies tensors of the dataset's shapes (training_loop...:289-297, 425-456)
+directly in HBM; with ``training_set_kwargs``, ``training_loop`` reads the reference's data set
+(training/dataset.py) and prepares each batch on the GPU (training/tryon_batch.py).
 """
 
 import copy
@@ -270,13 +271,28 @@ class TrainingStep:
 
 #----------------------------------------------------------------------------
 
-def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None):
-    """Run ``total_iters`` iterations on synthetic data (the reference's loop runs until ``total_kimg``)."""
+def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
+                  training_set_kwargs=None, data_loader_kwargs=None):
+    """Run ``total_iters`` iterations (the reference's loop runs until ``total_kimg``).  Without ``training_set_kwargs`` the data is
+    synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
+    path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
+    ``training.tryon_batch.FullBodyBatchBuilder``."""
     device = device if device is not None else torch.device('cuda', rank)
     step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
-    data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
+    if training_set_kwargs is None:
+        data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
+        batches = iter(lambda: data, None)
+    else:
+        from training import dataset as dataset_module
+        from training.tryon_batch import FullBodyBatchBuilder
+        training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
+        sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed)
+        loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
+                                             collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
+        builder = FullBodyBatchBuilder(device)
+        batches = (builder.build(raw) for raw in loader)
     for it in range(total_iters):
-        step.run(data)
+        step.run(next(batches))
         if progress_fn is not None:
             progress_fn(it + 1, total_iters)
     return step
