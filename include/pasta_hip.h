@@ -538,6 +538,57 @@ int pasta_tryon_assemble(const uint8_t* image, const uint8_t* stick, const uint8
                          const uint8_t* arm_masks, const uint8_t* erase_masks, const int32_t* erase_hw, float* const* outputs, int N,
                          int H, int W, int ph, int pw, int c_upper, int c_lower, int mh_max, int mw_max, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Per-batch preparation of the try-on TEST pairs (row f4; UvitonDatasetV19_test._load_raw_image / normalize / __getitem__,
+ * training/dataset.py:1085-1525, and test.py:104-150).  Same canvas, restated primitives and exactness as the entries
+ * above.  Where the test set differs from the training preparation:
+ *   1. two people: parts 0-5 are warped from the clothes DONOR's upper garment, stick figure and mask with the donor's key
+ *      points, parts 6-9 from the PERSON's lower garment, stick figure and mask with the person's (:1470-1478);
+ *   2. the warp-back uses the person's M_inv for all ten parts; an upper part is composited wherever the person's part
+ *      exists, its patch being zeros where the donor's does not (:1481-1492);
+ *   3. the warped-back mask of parts 0-5 is eroded (cv2.erode, 5 x 5, default border) before the == 255 test (:1460, :1484);
+ *   4. the forearm box of the palm rule is 15 x 15 (:1252; training: 16 x 16), the upper arm 25 x 25 in both;
+ *   5. the lower garment is labels 6, 9, 12 of the person (:1113), the upper garment labels 5, 6, 7 of the donor (:1133);
+ *   6. key points are shifted by the padding in float64 before get_crop's float32 conversion (:1100, :1129; host side);
+ * and, on the host too, get_crop's knee-without-ankle fall-back, which the training set's get_crop has commented out (:1355).
+ * ------------------------------------------------------------------------- */
+/* pasta_palm_mask_u8 with the dilation boxes as arguments: a k x k box covers offsets -(k / 2) .. k - 1 - k / 2 (cv2's
+ * default anchor); k_upper for the upper arm, k_lower for the forearm, 1 <= k <= 256.  (25, 16) is pasta_palm_mask_u8,
+ * (25, 15) the test set's rule. */
+int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H, int W,
+                           int k_upper, int k_lower, void* stream);
+
+/* :1105-1141 from the person's image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H] and the donor's image and
+ * parsing: retain_img = padded image * (palm + head(1, 2, 4, 13) + shoes(18, 19)); lower_img / lower_mask = the person's
+ * labels 6, 9, 12 (image, 255); upper_img / upper_mask = the donor's labels 5, 6, 7.  Outputs [N, H, H, 3], padding 255 in the
+ * images before the masks are applied. */
+int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
+                              const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* lower_img, uint8_t* lower_mask,
+                              uint8_t* upper_img, uint8_t* upper_mask, int N, int H, int W, void* stream);
+
+/* pasta_patch_composite_u8 with the warped-back mask eroded by a (2 radius + 1)^2 box before the == 255 test: a pixel takes
+ * part k where channel 0 of the warped-back mask is 255 at every in-image pixel within +-radius (pixels outside the image do
+ * not erode, cv2's default border).  part_mask (optional) receives the eroded 0 / 1 mask of every part.  0 <= radius <= 8;
+ * radius 0 is pasta_patch_composite_u8 bit for bit. */
+int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
+                                    uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
+                                    void* stream);
+
+/* __getitem__ (:1502-1525) and test.py:104-117: the seven fp32 NCHW tensors G takes, through outputs (a HOST array of 7
+ * device pointers) in this order: retain [N,3,H,H] (test.py's image), pose [N,6,H,H] = stick || retain,
+ * style_input [N,6P,ph,pw] = the P garment patches (channel 3k + c of part k) || the P stick-figure patches,
+ * denorm_upper_input / denorm_lower_input [N,3,H,H], denorm_upper_mask / denorm_lower_mask [N,1,H,H] = channel sum > 0 (no
+ * wrap).  x / 127.5 - 1 as torch evaluates it on the GPU: x * (1 / 127.5f) - 1.  retain_img, stick, denorm_upper,
+ * denorm_lower [N,H,H,3]; patches, stick_patches [N,P,ph,pw,3] uint8. */
+int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* stick_patches,
+                              const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int P,
+                              int ph, int pw, void* stream);
+
+/* test.py:133-137: images [N, 3, H, Wt] fp32 -> out [N, H, W, 3] uint8 of columns c0 .. c0 + W - 1: (x + 1.0f) * 127.5f with
+ * each operation rounded on its own, clipped to [0, 255], truncated.  A NaN becomes 0 (numpy leaves that conversion
+ * undefined). */
+int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,119 @@
+// Device helpers of the try-on preparation shared by csrc/tryon_inputs.hip (the training set) and csrc/tryon_pairs.hip (the
+// test pairs): separately rounded arithmetic, the restated rleFrPoly fill of a quadrilateral, the palm rule with its box
+// dilations, and torch's x / 127.5 - 1.
+#pragma once
+#include "common.h"
+
+namespace pasta {
+
+// The library is compiled with -ffp-contract=fast, which fuses a * b + c into one fma whatever a pragma says.  The polygon,
+// resize and float-conversion arithmetic below must round every product on its own (as the C, numpy and torch expressions it
+// restates do): tr_rounded() makes the product a value the compiler cannot fuse into the next addition.
+__device__ __forceinline__ float tr_rounded(float x) { __asm__ volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ double tr_rounded(double x) { __asm__ volatile("" : "+v"(x)); return x; }
+
+// ---- palm mask ----
+
+constexpr int PALM_S = 256;         // get_hand_mask works on a 256 x 256 square
+constexpr int PALM_BAND = 16;       // output rows per block
+constexpr int PALM_SEGS = 4;        // left upper arm, left forearm, right upper arm, right forearm
+
+// rleFrPoly's boundary points: u = t + xs, v = (int)(ys + s * t + .5) (dx >= dy), or v = t + ys, u = (int)(xs + s * t + .5)
+__device__ __forceinline__ int rle_round(double a, double s, int t) { return (int)(a + tr_rounded(s * (double)t) + .5); }
+
+// The y boundary of edge (xs, ys) -> (xe, ye) (5x upsampled integers) at pixel column X: the smaller v of the two consecutive
+// boundary points whose u are 5X + 2 and 5X + 3, turned into the row where the run toggles; -1 when the edge does not cross.
+__device__ inline int rle_edge_crossing(int xs, int ys, int xe, int ye, int X, int h) {
+    const int dx = abs(xe - xs), dy = abs(ys - ye);
+    const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
+    if (flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
+    const int u0 = 5 * X + 2;
+    int vmin;
+    if (dx >= dy) {
+        if (dx == 0) return -1;
+        const double s = (double)(ye - ys) / dx;
+        if (u0 < xs || u0 + 1 > xs + dx) return -1;
+        const int t = u0 - xs;
+        const int v1 = rle_round(ys, s, t), v2 = rle_round(ys, s, t + 1);
+        vmin = v1 < v2 ? v1 : v2;
+    } else {
+        const double s = (double)(xe - xs) / dy;
+        const int ua = rle_round(xs, s, 0), ub = rle_round(xs, s, dy);
+        const bool up = ub >= ua;
+        if (up ? !(ua <= u0 && ub >= u0 + 1) : !(ua >= u0 + 1 && ub <= u0)) return -1;
+        int lo = 1, hi = dy;                   // the first t past the step: u(t) >= u0 + 1 (rising) or u(t) <= u0 (falling)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int u = rle_round(xs, s, mid);
+            if (up ? u >= u0 + 1 : u <= u0) hi = mid; else lo = mid + 1;
+        }
+        vmin = ys + lo - 1;
+    }
+    double yd = ((double)vmin + .5) / 5 - .5;
+    if (yd < 0) yd = 0; else if (yd > h) yd = h;
+    return (int)ceil(yd);
+}
+
+// Fill of the quadrilateral `q` (4 corners, x then y, doubles) at column X: up to two runs [r[0], r[1]) and [r[2], r[3]).
+__device__ inline void rle_column_runs(const double* __restrict__ q, int X, int h, int16_t* r) {
+    int x[5], y[5];
+    for (int j = 0; j < 4; j++) { x[j] = (int)(tr_rounded(5.0 * q[2 * j]) + .5); y[j] = (int)(tr_rounded(5.0 * q[2 * j + 1]) + .5); }
+    x[4] = x[0]; y[4] = y[0];
+    int c[4], k = 0;
+    for (int j = 0; j < 4; j++) {
+        const int v = rle_edge_crossing(x[j], y[j], x[j + 1], y[j + 1], X, h);
+        if (v >= 0) {                          // insertion into the sorted list
+            int i = k++;
+            while (i > 0 && c[i - 1] > v) { c[i] = c[i - 1]; i--; }
+            c[i] = v;
+        }
+    }
+    for (int i = k; i < 4; i++) c[i] = h;     // an odd count toggles to the end of the column
+    for (int i = 0; i < 4; i++) r[i] = (int16_t)c[i];
+}
+
+__device__ __forceinline__ bool dilated_hit(const int16_t (*runs)[4], int X, int y, int lo, int hi, int S) {
+    const int x0 = X - lo < 0 ? 0 : X - lo, x1 = X + hi > S - 1 ? S - 1 : X + hi;
+    const int y0 = y - lo, y1 = y + hi;
+    for (int xx = x0; xx <= x1; xx++) {
+        const int16_t* r = runs[xx];
+        if ((r[0] < r[1] && r[0] <= y1 && r[1] - 1 >= y0) || (r[2] < r[3] && r[2] <= y1 && r[3] - 1 >= y0)) return true;
+    }
+    return false;
+}
+
+// The palm rule for one band of PALM_BAND rows of one sample (blockIdx.x = band, blockIdx.y = sample, 256 threads = columns):
+// each fill is dilated with the box of offsets -u_lo..u_hi (upper arm) or -b_lo..b_hi (forearm); runs: the block's
+// [PALM_SEGS][PALM_S][4] LDS array.
+__device__ __forceinline__ void palm_mask_band(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
+                                               const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int H, int W, int lp,
+                                               int u_lo, int u_hi, int b_lo, int b_hi, int16_t (*runs)[PALM_S][4]) {
+    const int n = blockIdx.y;
+    const int X = threadIdx.x;
+    const uint8_t* pres = present + n * PALM_SEGS;
+    for (int sgm = 0; sgm < PALM_SEGS; sgm++)
+        if (pres[sgm]) rle_column_runs(quads + ((int64_t)n * PALM_SEGS + sgm) * 8, X, PALM_S, runs[sgm][X]);
+    __syncthreads();
+    const uint8_t* lab = parsing + (int64_t)n * H * W;
+    for (int yy = 0; yy < PALM_BAND; yy++) {
+        const int y = blockIdx.x * PALM_BAND + yy;
+        const int c = X - lp;
+        const int label = (c >= 0 && c < W) ? lab[(int64_t)y * W + c] : 0;
+        int palm = 0;
+        if (label == 14 || label == 15) {     // hand: left = 14 (segments 0, 1), right = 15 (segments 2, 3)
+            const int s0 = label == 14 ? 0 : 2;
+            // a missing segment is an all-ones mask
+            const bool up = !pres[s0] || dilated_hit(runs[s0], X, y, u_lo, u_hi, PALM_S);
+            const bool bottom = !pres[s0 + 1] || dilated_hit(runs[s0 + 1], X, y, b_lo, b_hi, PALM_S);
+            palm = !up && !bottom;
+        }
+        out[((int64_t)n * H + y) * H + X] = (uint8_t)palm;
+    }
+}
+
+__device__ __forceinline__ float to_unit(int v) {           // torch's x / 127.5 - 1 on the GPU: x * (1 / 127.5f) - 1
+    const float inv = 1.0f / 127.5f;
+    return tr_rounded((float)v * inv) - 1.0f;
+}
+
+}  // namespace pasta

@@ -1,0 +1,259 @@
+// Per-batch preparation of the try-on TEST pairs on the GPU (row f4, UvitonDatasetV19_test._load_raw_image / normalize /
+// __getitem__, training/dataset.py:1085-1525, and test.py:104-150), which the reference runs per sample on the host in four
+// loader processes with OpenCV, pycocotools and skimage:
+//   pasta_palm_mask_box_u8           the palm mask with both box sizes as arguments (25 / 15 here, :1240-1253);
+//   pasta_tryon_pair_masks_u8        retain image, the person's lower garment and the donor's upper garment (:1105-1141);
+//   pasta_patch_composite_eroded_u8  the warp-back composite with cv2.erode(5 x 5) of the mask before the == 255 test
+//                                    (:1480-1492);
+//   pasta_tryon_pair_assemble        __getitem__ (:1502-1525) and test.py's conversions (:104-117) into the seven fp32 tensors;
+//   pasta_images_to_u8               test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137).
+// The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures tryon_inputs.hip's stick-figure
+// entry.  Where the test set differs from the training preparation (the six rules of include/pasta_hip.h): two people (the
+// donor's upper garment with the donor's key points, the person's lower garment with the person's), the person's M_inv for
+// every part, an eroded mask for parts 0-5, a 15 x 15 forearm box, lower garment = labels 6, 9, 12, and key points shifted by
+// the padding in float64 on the host.  Every entry does a whole batch in one launch.
+#include "common.h"
+#include "tryon_common.h"
+
+#pragma clang fp contract(off)      // the warp-back coordinates must round as csrc/patches.hip's do
+#include "patch_warp.h"
+
+namespace pasta {
+
+// ---- palm mask with the box sizes as arguments ----
+
+__global__ __launch_bounds__(256) void palm_mask_box_kernel(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
+                                                            const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int H, int W,
+                                                            int lp, int k_upper, int k_lower) {
+    __shared__ int16_t runs[PALM_SEGS][PALM_S][4];
+    // a k x k box with cv2's default anchor k / 2: offsets -(k / 2) .. k - 1 - k / 2
+    palm_mask_band(parsing, quads, present, out, H, W, lp, k_upper / 2, k_upper - 1 - k_upper / 2, k_lower / 2, k_lower - 1 - k_lower / 2, runs);
+}
+
+// ---- label masks of a pair ----
+
+__global__ __launch_bounds__(256) void tryon_pair_masks_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ parsing,
+                                                               const uint8_t* __restrict__ palm, const uint8_t* __restrict__ d_image,
+                                                               const uint8_t* __restrict__ d_parsing, uint8_t* __restrict__ retain_img,
+                                                               uint8_t* __restrict__ lower_img, uint8_t* __restrict__ lower_mask,
+                                                               uint8_t* __restrict__ upper_img, uint8_t* __restrict__ upper_mask, int H, int W,
+                                                               int lp) {
+    const int n = blockIdx.y;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= H * H) return;
+    const int y = pix / H, c = pix - y * H - lp;
+    const bool inside = c >= 0 && c < W;
+    const int64_t src = (int64_t)n * H * W + (int64_t)y * W + c;
+    const int L = inside ? parsing[src] : 0, D = inside ? d_parsing[src] : 0;
+    const int64_t o = (int64_t)n * H * H + pix;
+    const int keep = (L == 18 || L == 19) + palm[o] + (L == 1 || L == 2 || L == 4 || L == 13);      // shoes + palm + head
+    const int low = L == 6 || L == 9 || L == 12;                                                    // rule 5: label 6 too
+    const int up = D == 5 || D == 6 || D == 7;                                                      // the donor's
+    for (int ch = 0; ch < 3; ch++) {
+        const int v = inside ? image[src * 3 + ch] : 255, dv = inside ? d_image[src * 3 + ch] : 255;
+        retain_img[o * 3 + ch] = (uint8_t)(keep * v);
+        lower_img[o * 3 + ch] = (uint8_t)(low * v);
+        lower_mask[o * 3 + ch] = (uint8_t)(low * 255);
+        upper_img[o * 3 + ch] = (uint8_t)(up * dv);
+        upper_mask[o * 3 + ch] = (uint8_t)(up * 255);
+    }
+}
+
+// ---- eroded composite ----
+
+constexpr int ER_T = 16;            // output tile side: one thread per pixel of a 16 x 16 tile
+constexpr int ER_MAX_R = 8;         // largest erosion radius (a 17 x 17 box)
+constexpr int ER_S = ER_T + 2 * ER_MAX_R;
+
+// patch_composite_u8_kernel with cv2.erode(mask, ones(2r+1, 2r+1)) of the warped-back mask before the == 255 test.  Since
+// 255 is the largest uint8, the eroded channel 0 is 255 exactly where every in-image pixel within +-r has channel 0 == 255
+// (cv2's default erode border: pixels outside the image do not erode).  Per part: the == 255 flags of the tile and an r-pixel
+// halo go to LDS, are AND-ed along rows and then along columns; the running RGB stays in registers.
+__global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8_t* __restrict__ patches, const uint8_t* __restrict__ masks,
+                                                                     const double* __restrict__ minv, const uint8_t* __restrict__ valid,
+                                                                     uint8_t* __restrict__ out, uint8_t* __restrict__ part_mask, int P, int ph,
+                                                                     int pw, int H, int W, int r, int tiles_x) {
+    __shared__ uint8_t flags[ER_S * ER_S];
+    __shared__ uint8_t rows[ER_S * ER_T];
+    const int n = blockIdx.y;
+    const int tx0 = (blockIdx.x % tiles_x) * ER_T, ty0 = (blockIdx.x / tiles_x) * ER_T;
+    const int S = ER_T + 2 * r;
+    const int ty = threadIdx.x / ER_T, tx = threadIdx.x % ER_T;
+    const int y = ty0 + ty, x = tx0 + tx;
+    const bool mine = y < H && x < W;
+    int red = 0, green = 0, blue = 0;
+    for (int k = 0; k < P; k++) {
+        const int64_t item = (int64_t)n * P + k;
+        if (!valid[item]) {                                     // uniform across the block: no barrier is skipped by a part
+            if (part_mask && mine) part_mask[item * H * W + (int64_t)y * W + x] = 0;
+            continue;
+        }
+        const double* m = minv + item * 9;
+        const uint8_t* mk = masks + item * ph * pw * 3;
+        for (int i = threadIdx.x; i < S * S; i += 256) {
+            const int gy = ty0 - r + i / S, gx = tx0 - r + i % S;
+            uint8_t f = 1;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                int X, Y;
+                pw_source(m, gx, gy, X, Y);
+                f = pw_sample(mk, pw, 3, 0, pw_taps(X, Y, pw, ph, 0)) == 255;
+            }
+            flags[i] = f;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < S * ER_T; i += 256) {
+            const int ry = i / ER_T, rx = i % ER_T;
+            uint8_t f = 1;
+            for (int d = 0; d <= 2 * r; d++) f &= flags[ry * S + rx + d];
+            rows[i] = f;
+        }
+        __syncthreads();
+        if (mine) {
+            uint8_t hit = 1;
+            for (int d = 0; d <= 2 * r; d++) hit &= rows[(ty + d) * ER_T + tx];
+            if (hit) {
+                int X, Y;
+                pw_source(m, x, y, X, Y);
+                const PwTaps t = pw_taps(X, Y, pw, ph, 0);
+                const uint8_t* pt = patches + item * ph * pw * 3;
+                red = pw_sample(pt, pw, 3, 0, t); green = pw_sample(pt, pw, 3, 1, t); blue = pw_sample(pt, pw, 3, 2, t);
+            }
+            if (part_mask) part_mask[item * H * W + (int64_t)y * W + x] = hit;
+        }
+        // the next part writes `flags` only after this barrier pair, and `rows` only after its own first barrier
+    }
+    if (mine) {
+        uint8_t* o = out + ((int64_t)n * H * W + (int64_t)y * W + x) * 3;
+        o[0] = (uint8_t)red; o[1] = (uint8_t)green; o[2] = (uint8_t)blue;
+    }
+}
+
+// ---- the seven tensors G takes ----
+
+struct PairOut {
+    float *retain, *pose, *style_input, *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask, *denorm_lower_mask;
+};
+
+__global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t* __restrict__ retain_img, const uint8_t* __restrict__ stick,
+                                                                  const uint8_t* __restrict__ patches, const uint8_t* __restrict__ stick_patches,
+                                                                  const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l,
+                                                                  PairOut o, int H, int P, int ph, int pw) {
+    const int n = blockIdx.y;
+    const int HH = H * H;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= HH) {                // style_input = cat(norm_img, norm_pose): channel 3k + c of part k, patches then stick patches
+        const int q = pix - HH;
+        if (q >= ph * pw) return;
+        const int CP = 3 * P;
+        for (int ch = 0; ch < 2 * CP; ch++) {
+            const int cc = ch < CP ? ch : ch - CP, k = cc / 3, c = cc - 3 * k;
+            const uint8_t* src = ch < CP ? patches : stick_patches;
+            o.style_input[((int64_t)n * 2 * CP + ch) * ph * pw + q] = to_unit(src[(((int64_t)n * P + k) * ph * pw + q) * 3 + c]);
+        }
+        return;
+    }
+    const int64_t p = (int64_t)n * HH + pix;
+    int su = 0, sl = 0;
+    for (int ch = 0; ch < 3; ch++) {
+        const int64_t oc = ((int64_t)n * 3 + ch) * HH + pix;
+        const float ret = to_unit(retain_img[p * 3 + ch]);
+        o.retain[oc] = ret;
+        o.pose[((int64_t)n * 6 + ch) * HH + pix] = to_unit(stick[p * 3 + ch]);
+        o.pose[((int64_t)n * 6 + 3 + ch) * HH + pix] = ret;
+        const int u = den_u[p * 3 + ch], l = den_l[p * 3 + ch];
+        su += u; sl += l;                                       // numpy sums uint8 in a wider type: no wrap
+        o.denorm_upper_input[oc] = to_unit(u);
+        o.denorm_lower_input[oc] = to_unit(l);
+    }
+    o.denorm_upper_mask[p] = su > 0 ? 1.f : 0.f;
+    o.denorm_lower_mask[p] = sl > 0 ? 1.f : 0.f;
+}
+
+// ---- generated images to uint8 ----
+
+// test.py:133-137 on fp32: (x + 1.0) * 127.5 with each operation rounded on its own, clip to [0, 255], truncation.  A NaN
+// becomes 0 (numpy leaves its uint8 conversion undefined).
+__global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int H, int Wt, int c0,
+                                                           int W) {
+    const int n = blockIdx.y;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= H * W) return;
+    const int y = pix / W, x = pix - y * W;
+    uint8_t* o = dst + ((int64_t)n * H * W + pix) * 3;
+    for (int ch = 0; ch < 3; ch++) {
+        const float v = tr_rounded(src[(((int64_t)n * 3 + ch) * H + y) * Wt + c0 + x] + 1.0f) * 127.5f;
+        o[ch] = v != v ? 0 : (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
+    }
+}
+
+}  // namespace pasta
+
+extern "C" int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H,
+                                      int W, int k_upper, int k_lower, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(parsing && quads && present && out, "palm_mask_box_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H == PALM_S && W >= 1 && W <= H, "palm_mask_box_u8: bad shape (the padded square is 256 x 256)");
+    PASTA_CHECK(k_upper >= 1 && k_upper <= PALM_S && k_lower >= 1 && k_lower <= PALM_S, "palm_mask_box_u8: box sizes %d, %d (1..256)",
+                k_upper, k_lower);
+    dim3 grid((unsigned)(PALM_S / PALM_BAND), (unsigned)N);
+    hipLaunchKernelGGL(palm_mask_box_kernel, grid, dim3(PALM_S), 0, (hipStream_t)stream, parsing, quads, present, out, H, W, (H - W) / 2,
+                       k_upper, k_lower);
+    return launch_status("palm_mask_box_u8");
+}
+
+extern "C" int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
+                                         const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* lower_img, uint8_t* lower_mask,
+                                         uint8_t* upper_img, uint8_t* upper_mask, int N, int H, int W, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && parsing && palm && donor_image && donor_parsing && retain_img && lower_img && lower_mask && upper_img && upper_mask,
+                "tryon_pair_masks_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "tryon_pair_masks_u8: bad shape");
+    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, donor_image, donor_parsing,
+                       retain_img, lower_img, lower_mask, upper_img, upper_mask, H, W, (H - W) / 2);
+    return launch_status("tryon_pair_masks_u8");
+}
+
+extern "C" int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
+                                               uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
+                                               void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(patches && masks && minv && valid && out, "patch_composite_eroded_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && P >= 1 && ph >= 1 && pw >= 1 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
+                "patch_composite_eroded_u8: bad shape");
+    PASTA_CHECK(radius >= 0 && radius <= ER_MAX_R, "patch_composite_eroded_u8: radius %d (0..%d)", radius, ER_MAX_R);
+    const int tiles_x = (W + ER_T - 1) / ER_T, tiles_y = (H + ER_T - 1) / ER_T;
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
+    hipLaunchKernelGGL(patch_composite_eroded_kernel, grid, dim3(256), 0, (hipStream_t)stream, patches, masks, minv, valid, out, part_mask, P,
+                       ph, pw, H, W, radius, tiles_x);
+    return launch_status("patch_composite_eroded_u8");
+}
+
+extern "C" int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* stick_patches,
+                                         const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int P,
+                                         int ph, int pw, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(retain_img && stick && patches && stick_patches && denorm_upper && denorm_lower && outputs, "tryon_pair_assemble: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && P >= 1 && P <= 64 && ph >= 1 && pw >= 1 && ph * pw <= H * H,
+                "tryon_pair_assemble: bad shape");
+    PairOut o;
+    float** f[7] = {&o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask, &o.denorm_lower_mask};
+    for (int i = 0; i < 7; i++) {
+        PASTA_CHECK(outputs[i], "tryon_pair_assemble: output %d is null", i);
+        *f[i] = outputs[i];
+    }
+    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, retain_img, stick, patches, stick_patches,
+                       denorm_upper, denorm_lower, o, H, P, ph, pw);
+    return launch_status("tryon_pair_assemble");
+}
+
+extern "C" int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(images && out, "images_to_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && Wt >= 1 && Wt <= 4096 && W >= 1 && c0 >= 0 && c0 + W <= Wt,
+                "images_to_u8: bad shape or crop (columns %d + %d of %d)", c0, W, Wt);
+    dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(images_to_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, images, out, H, Wt, c0, W);
+    return launch_status("images_to_u8");
+}

@@ -4,7 +4,9 @@ reading the same directory layout with PIL and ``json`` only.
 Difference from the reference, by design: ``UvitonDatasetFull.__getitem__`` returns the RAW sample -- the decoded files -- and
 not the prepared 13-tuple.  The preparation (stick figure, palm / retain masks, garment images and masks, body-part warps, erase
 mask, float conversions) runs for a whole batch on the GPU in ``training.tryon_batch.FullBodyBatchBuilder``; ``collate`` turns
-a list of raw samples into the batch the builder takes.  Only directory data sets are supported, as in the reference."""
+a list of raw samples into the batch the builder takes.  Only directory data sets are supported, as in the reference.
+The test pairs (``UvitonDatasetV19_test``, dataset.py:997-1525) follow the same design: raw pairs out, ``collate_pairs``, and
+``training.tryon_pairs.TryOnPairBatchBuilder`` on the GPU."""
 
 import json
 import os
@@ -15,6 +17,8 @@ import torch
 
 SUB_DATASETS = ('Zalando_256_192', 'Zalora_256_192', 'Deepfashion_256_192', 'MPV_256_192')     # dataset.py:435
 PAIR_LIST = 'train_pairs_front_list_0508.txt'
+TEST_SUB_DATASETS = ('UPT_subset1_256_192', 'UPT_subset2_256_192')                              # dataset.py:1009
+TEST_PAIR_LIST = 'test_pairs_front_list_shuffle_0508.txt'
 
 #----------------------------------------------------------------------------
 
@@ -171,5 +175,78 @@ def collate(samples):
                 keypoints=torch.from_numpy(np.stack([s['keypoints'] for s in samples])),
                 erase_masks=torch.from_numpy(erase), erase_hw=torch.from_numpy(erase_hw),
                 raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
+
+#----------------------------------------------------------------------------
+
+class UvitonDatasetV19_test(Dataset):
+    """dataset.py:997-1153 -- the unpaired test pairs of ``UPT_subset1_256_192`` and ``UPT_subset2_256_192``: each line
+    ``person clothes`` of ``test_pairs_front_list_shuffle_0508.txt``, in file order.  ``__getitem__`` returns the raw pair (see
+    the module docstring): a dict with the person's ``image`` uint8 [H, W, 3], ``parsing`` uint8 [H, W] (channel 0 as
+    cv2.imread reads it) and ``keypoints`` float64 [18, 3] (unshifted), the same three of the clothes donor as
+    ``clothes_image`` / ``clothes_parsing`` / ``clothes_keypoints``, and ``person_name`` / ``clothes_name`` (the reference's
+    relative paths, ``<sub-dataset>/image/<file>``)."""
+
+    def __init__(self, path, resolution=None, **super_kwargs):
+        self._path = path
+        if not os.path.isdir(self._path):
+            raise IOError('Path must point to a directory')
+        self._type = 'dir'
+        self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
+        self._clothes_image_fnames, self._clothes_kpt_fnames, self._clothes_parsing_fnames = [], [], []
+        for dataset in TEST_SUB_DATASETS:
+            with open(os.path.join(self._path, dataset, TEST_PAIR_LIST), 'r') as f:
+                for line in f.readlines():
+                    if not line.strip():
+                        continue
+                    person, clothes = line.strip().split()
+                    for name, images, kpts, labels in ((person, self._image_fnames, self._kpt_fnames, self._parsing_fnames),
+                                                       (clothes, self._clothes_image_fnames, self._clothes_kpt_fnames, self._clothes_parsing_fnames)):
+                        images.append(os.path.join(dataset, 'image', name))
+                        kpts.append(os.path.join(dataset, 'keypoints', name.replace('.jpg', '_keypoints.json')))
+                        label = name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')     # :1030-1033
+                        labels.append(os.path.join(dataset, 'parsing', label))
+        self._vis_index = list(range(64))
+
+        PIL.Image.init()
+        if len(self._image_fnames) == 0:
+            raise IOError('No image files found in the specified path')
+        h, w, c = self._load_person(self._image_fnames[0], self._parsing_fnames[0], self._kpt_fnames[0])[0].shape
+        raw_shape = [len(self._image_fnames), c, h, h]         # the padded square, as the reference's image_shape
+        if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
+            raise IOError('Image files do not match the specified resolution')
+        super().__init__(name=os.path.splitext(os.path.basename(self._path))[0], raw_shape=raw_shape, **super_kwargs)
+
+    def _load_person(self, image_fname, parsing_fname, kpt_fname):
+        image = np.array(PIL.Image.open(os.path.join(self._path, image_fname)))
+        if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < image.shape[1]:
+            raise IOError('%s: expected an RGB image at least as tall as wide, got %s' % (image_fname, image.shape))
+        parsing = read_channel0(os.path.join(self._path, parsing_fname))
+        if parsing.shape != image.shape[:2]:
+            raise IOError('%s: label map %s does not match the image %s' % (parsing_fname, parsing.shape, image.shape[:2]))
+        return image, parsing, read_keypoints(os.path.join(self._path, kpt_fname))
+
+    def load_raw(self, raw_idx):
+        image, parsing, keypoints = self._load_person(self._image_fnames[raw_idx], self._parsing_fnames[raw_idx], self._kpt_fnames[raw_idx])
+        c_image, c_parsing, c_keypoints = self._load_person(self._clothes_image_fnames[raw_idx], self._clothes_parsing_fnames[raw_idx],
+                                                            self._clothes_kpt_fnames[raw_idx])
+        if c_image.shape != image.shape:
+            raise IOError('%s: the clothes image %s does not match the person %s' % (self._clothes_image_fnames[raw_idx], c_image.shape, image.shape))
+        return dict(image=image, parsing=parsing, keypoints=keypoints, clothes_image=c_image, clothes_parsing=c_parsing,
+                    clothes_keypoints=c_keypoints, person_name=self._image_fnames[raw_idx], clothes_name=self._clothes_image_fnames[raw_idx],
+                    raw_idx=int(raw_idx))
+
+    def __getitem__(self, idx):
+        return self.load_raw(self._raw_idx[idx])
+
+
+def collate_pairs(samples):
+    """A list of raw pairs -> one batch: ``image`` / ``clothes_image`` uint8 [N, H, W, 3], ``parsing`` / ``clothes_parsing``
+    uint8 [N, H, W], ``keypoints`` / ``clothes_keypoints`` float64 [N, 18, 3], ``person_name`` / ``clothes_name`` lists of str,
+    ``raw_idx`` int64 [N].  Use as the DataLoader's ``collate_fn``."""
+    stack = lambda key: torch.from_numpy(np.stack([s[key] for s in samples]))
+    out = {k: stack(k) for k in ('image', 'parsing', 'keypoints', 'clothes_image', 'clothes_parsing', 'clothes_keypoints')}
+    out.update(person_name=[s['person_name'] for s in samples], clothes_name=[s['clothes_name'] for s in samples],
+               raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
+    return out
 
 #----------------------------------------------------------------------------

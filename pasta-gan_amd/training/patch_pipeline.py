@@ -37,13 +37,17 @@ def _box_around(p, q, half_width_ratio):
     return np.float32([p + normal, p - normal, q - normal, q + normal])
 
 
-def part_quadrilateral(joints, part, image_height, aspect=0.5, x_pad=32):
+def part_quadrilateral(joints, part, image_height, aspect=0.5, x_pad=32, shin_fallback=False):
     """Source quadrilateral [4, 2] float32 of one body part, or None when its key points are missing (dataset.py:751-829).
-    ``joints`` [18, 3] = (x, y, confidence) in the unpadded 192-wide image; ``x_pad`` shifts into the padded square."""
+    ``joints`` [18, 3] = (x, y, confidence) in the unpadded 192-wide image; ``x_pad`` shifts into the padded square.
+    ``shin_fallback``: a shin without its ankle goes straight down from the knee, as the test set's get_crop does (:1355-1362;
+    the training set's has it commented out)."""
     names = list(part)
     if not _seen(joints, names):
         if names[0] in ('lhip', 'rhip') and names[1] in ('lknee', 'rknee') and names[0][0] == names[1][0]:
             names = names[:1]                                   # thigh without its knee: straight down from the hip
+        elif shin_fallback and names[0] in ('lknee', 'rknee') and names[1] in ('lankle', 'rankle') and names[0][0] == names[1][0]:
+            names = names[:1]                                   # shin without its ankle: straight down from the knee
         elif names == ['lshoulder', 'rshoulder', 'cnose']:
             names = ['lshoulder', 'rshoulder', 'rshoulder']     # head without the nose: a square above the shoulders
         if not _seen(joints, names):
@@ -97,9 +101,10 @@ def adjugate_inverse(m):
     return c * (1.0 / det) if det != 0 else np.zeros([3, 3])
 
 
-def part_matrices(joints, width, height, box_factor=2):
+def part_matrices(joints, width, height, box_factor=2, x_pad=32, shin_fallback=False):
     """For a batch of key points [N, 18, 3]: (M [N,10,3,3], M_inv [N,10,3,3], valid [N,10]) float64 / bool -- image -> patch and
-    patch -> image maps of the ten parts (dataset.py:831-836); zeros where a part is missing."""
+    patch -> image maps of the ten parts (dataset.py:831-836); zeros where a part is missing.  ``x_pad`` and ``shin_fallback``
+    go to part_quadrilateral (the test set passes key points already shifted in float64, x_pad = 0, and its fall-back)."""
     joints = np.asarray(joints, np.float64)
     n = joints.shape[0]
     pw, ph = width // 2 ** box_factor, height // 2 ** box_factor
@@ -107,7 +112,7 @@ def part_matrices(joints, width, height, box_factor=2):
     fwd, back, valid = np.zeros([n, 10, 3, 3]), np.zeros([n, 10, 3, 3]), np.zeros([n, 10], bool)
     for i in range(n):
         for k, part in enumerate(BODY_PARTS):
-            quad = part_quadrilateral(joints[i], part, height)
+            quad = part_quadrilateral(joints[i], part, height, x_pad=x_pad, shin_fallback=shin_fallback)
             if quad is not None:
                 fwd[i, k], back[i, k], valid[i, k] = perspective_matrix(quad, corners), perspective_matrix(corners, quad), True
     return fwd, back, valid
@@ -177,3 +182,49 @@ def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_fa
     m_invs = torch.from_numpy(np.where(valid[..., None, None], back, 0.0).astype(np.float32))
     hand_masks = part_masks[:, list(ARM_PARTS)].unsqueeze(-1)
     return hwc(p_img), hwc(p_img_l), den_u, den_l, m_invs, hand_masks, hwc(p_mask), hwc(p_mask_l)
+
+
+UPPER_PARTS = 6             # the test set: parts 0..5 from the clothes donor, 6..9 from the person (dataset.py:1470-1478)
+ERODE_RADIUS = 2            # cv2.erode(..., np.ones((5, 5))) of the warped-back masks of parts 0..5 (:1460, :1484-1485)
+
+
+def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower_img, lower_stick, lower_mask, lower_joints, box_factor=2):
+    """The test set's ``normalize`` (dataset.py:1430-1500) for a batch on the GPU.  ``upper_*``: the clothes donor's upper garment,
+    stick figure and 3-channel mask; ``lower_*``: the person's lower garment, stick figure and mask; uint8 [N, H, W, 3] CUDA
+    tensors.  ``*_joints`` [N, 18, 3] float64 (host), already shifted by the padding (x_pad = 0 below).
+    Parts 0..5 are cut from the donor's tensors with the donor's matrices and parts 6..9 from the person's with the person's:
+    three forward-warp launches (image, stick figure, mask), each over the two people stacked.  All ten parts are warped back
+    with the PERSON's M_inv: parts 0..5 into denorm_upper through the eroded composite, parts 6..9 into denorm_lower through the
+    plain one.  Returns (patches, stick_patches, mask_patches [N,10,h,w,3], denorm_upper, denorm_lower [N,H,W,3],
+    M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid [N,10] bool)."""
+    upper_img, upper_stick, upper_mask = _u8(upper_img), _u8(upper_stick), _u8(upper_mask)
+    lower_img, lower_stick, lower_mask = _u8(lower_img), _u8(lower_stick), _u8(lower_mask)
+    n, height, width, _ = upper_img.shape
+    ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
+    fwd_u, _, valid_u = part_matrices(upper_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
+    fwd_l, back_l, valid_l = part_matrices(lower_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
+    dev = upper_img.device
+    donor = np.arange(10) < UPPER_PARTS
+    mats = np.where(donor[None, :, None, None], fwd_u, fwd_l).reshape(-1, 3, 3)
+    valid = np.where(donor[None, :], valid_u, valid_l).reshape(-1)
+    # item (i, k) reads person i of the donors (0..N-1) for k < 6 and of the persons (N..2N-1) otherwise
+    src_index = (np.arange(n, dtype=np.int32)[:, None] + np.where(donor, 0, n).astype(np.int32)[None, :]).reshape(-1)
+    warp = lambda a, b: warp_perspective(torch.cat([a, b]), mats, (ph, pw), 'replicate', src_index, valid).reshape(n, 10, ph, pw, 3)
+    patches, stick_patches, mask_patches = warp(upper_img, lower_img), warp(upper_stick, lower_stick), warp(upper_mask, lower_mask)
+
+    def composite(parts, entry, *radius):
+        p = len(parts)
+        inv = np.ascontiguousarray(np.stack([adjugate_inverse(back_l[i, k]) for i in range(n) for k in parts]).reshape(n * p, 9))
+        inv_t = torch.from_numpy(inv).to(dev)
+        val_t = torch.as_tensor(np.ascontiguousarray(valid_l[:, parts]).astype(np.uint8), device=dev)
+        out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
+        src, msk = patches[:, parts].contiguous(), mask_patches[:, parts].contiguous()     # held until the launch is queued
+        with torch.cuda.device(dev):
+            _native.check(entry(_native.ptr(src), _native.ptr(msk), _native.ptr(inv_t),
+                                _native.ptr(val_t), _native.ptr(out), None, n, p, ph, pw, height, width, *radius, _native.stream()))
+        return out
+    lib = _native.lib()
+    den_u = composite(list(range(UPPER_PARTS)), lib.pasta_patch_composite_eroded_u8, ERODE_RADIUS)
+    den_l = composite(list(range(UPPER_PARTS, 10)), lib.pasta_patch_composite_u8)
+    m_invs = torch.from_numpy(np.where(valid_l[..., None, None], back_l, 0.0).astype(np.float32))
+    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l
