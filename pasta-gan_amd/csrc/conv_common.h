@@ -255,6 +255,95 @@ __device__ __forceinline__ float conv_scale_noise(float v, const float* osb, int
     return osb ? fmaf(v, osb[o], nz) : v + nz;
 }
 
+//------------------------------------------------------------------------------------
+// The epilogue of the forward-type kernels, registers -> NCHW: rows of a 32 x 32 accumulator sub-tile are output channels, lanes are pixels.
+// Every kernel keeps where its pixels lie (and its `for b` / `for a` loops); what happens to a sub-tile on the way out is here, once.
+// Two kernels keep a block of their own, measured: conv_fwd_kernel (conv_fwd_f32.h; through these functions three of its instances ran 15 - 32 %
+// faster and <64,256,2,2,4,1> 2.3 % slower, twice) and conv3x3s2_f16x3_kernel (conv_fwd_s2.h) -- profiles/epilogue_single_source_ab.txt.
+
+// Back to the operands' units (PASTA_MATH_F16X3): row o of every accumulator set handed in times `scale` (1 / S_x of the tile) times wri[o]
+// (1 / S_w of the weight row, p.w_rowinv, written by the packing kernel; wri points at the tile's first row).  The 16 x WMT row scales of this
+// lane are fetched in one go in front of the multiplies (a load in front of every store cost 9 % of the kernel); the pair mode of the row
+// kernel hands in both of its sets, which share them.
+template <int WMT, int WNT, class... Acc>
+__device__ __forceinline__ void conv_unscale_rows(const float* wri, float scale, int wm, int lane, Acc&... accs) {
+    float ws[WMT][16];
+#pragma unroll
+    for (int a = 0; a < WMT; a++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) ws[a][r] = wri[(wm * WMT + a) * 32 + acc_row(r, lane)];
+#pragma unroll
+    for (int a = 0; a < WMT; a++)
+#pragma unroll
+        for (int b = 0; b < WNT; b++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) ((accs[a][b][r] = (accs[a][b][r] * scale) * ws[a][r]), ...);
+}
+
+// What one lane's pixel (column b of the wave's sub-tiles) brings to the epilogue.  Element (row o of the group, this pixel) of y, res and
+// partial lies at off + o * ostride; oscale and bias are indexed by o.  An operand that is absent is a null pointer.
+struct EpiColumn {
+    void* y; const void* res;           // elements of the kernel's storage type
+    float* partial;                     // K slices: this slice's fp32 partial sums; the sub-tile is written there and nothing else happens
+    int64_t off, ostride;
+    const float* oscale;                // this pixel's sample
+    const float* bias;
+    float nz; bool has_noise;           // noise * strength of this pixel (0 without noise)
+};
+
+// One 32 x 32 sub-tile (rows o0 + acc_row(r, lane) of a group of Og) from registers to memory: output scale with noise (as mod_bias_act_kernel
+// rounds them: fma(acc, d, noise * strength)) or noise alone, residual, (K slices: the partial sums, and out), bias, then the sixteen stores.
+// What the stores need from memory is fetched in front of them, sixteen loads in a row and then their use (a load in front of every store
+// serialises on the memory counter: the input-gradient launches that carry another consumer's gradient as residual ran 4 % SLOWER than launch
+// + torch addition that way, profiles/r4_ab_grad_join.txt), and ONE operand kind at a time through the same sixteen registers: output scale,
+// residual and bias in arrays of their own spill next to the sixty-four accumulators and the store addresses on the three-workgroup tiles.
+// full / case_c: what conv_epilogue_dispatch hands its callable.  y_am: the lane's running |max| of y for amax_commit.  RES_ROWTEST (EPI_RES_ROWTEST at the call): the residual keeps its row test in whole tiles too -- the
+// base kernel's 16-bit instances take 3 - 19 more VGPRs than they had with sixteen unconditional loads in flight (the note at the end of
+// profiles/epilogue_single_source_resources.txt).
+constexpr bool EPI_RES_ROWTEST = true;
+template <int IO, bool RES_ROWTEST = false, class Full, int MODE>
+__device__ __forceinline__ void conv_store_subtile(f32x16& acc, const EpiColumn& c, int o0, int Og, int lane, const EpiAct& ea, uint32_t& y_am,
+                                                   Full full, EpiCase<MODE> case_c) {
+    const bool FULL = full;
+    constexpr unsigned ES = io_size<IO>::value;
+    float tv[16];
+    if (c.oscale) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) { const int o = o0 + acc_row(r, lane); tv[r] = c.oscale[(FULL || o < Og) ? o : Og - 1]; }
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = fmaf(acc[r], tv[r], c.nz);
+    } else if (c.has_noise) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] += c.nz;
+    }
+    if (c.res) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = o0 + acc_row(r, lane);
+            tv[r] = ((FULL && !RES_ROWTEST) || o < Og) ? io_ld1<IO>((const char*)c.res + (c.off + (int64_t)o * c.ostride) * ES) : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] += tv[r];
+    }
+    if (c.partial) {                    // scale, residual, bias, activation ride in the reduction
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = o0 + acc_row(r, lane);
+            if (FULL || o < Og) c.partial[c.off + (int64_t)o * c.ostride] = acc[r];
+        }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) { const int o = o0 + acc_row(r, lane); tv[r] = c.bias ? c.bias[(FULL || o < Og) ? o : Og - 1] : 0.f; }
+    // instantiated per (activation, clamp, whole tile of rows): no wave-uniform branch per element (conv_epilogue_dispatch)
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = o0 + acc_row(r, lane);
+        const float v = conv_epilogue_c(acc[r], tv[r], ea, case_c);
+        if (FULL || o < Og) { io_st<IO>(c.y, c.off + (int64_t)o * c.ostride, v); amax_take(y_am, v); }
+    }
+}
+
 // Parameters of the forward-type kernels (conv2d, conv_transpose2d and both input gradients).
 // One packing job of pack_weights_f16x3_(pair_)kernel: where the packed rows and their scales go, and how the weight tensor is read
 struct PackJob {
@@ -307,6 +396,44 @@ struct ConvFwdParams {
     int xcd_order;                        // conv_fwd_rows2d_bf16x6_kernel, eight-wave tile: consecutive pixel tiles on ONE XCD (0: off)
     int x_pieces;                         // conv3x3s2_f16x3_kernel: x is PASTA_LAYOUT_PIECES16 (pieces.hip), p.x_amax the producer's bound row
 };
+
+// The column of the pixel at plane offset plane_off of sample n, for group g and K slice ks of a launch: every operand the launch carries
+// (output scale, noise, residual, bias and activation exist only without K slices: they ride in the reduction otherwise).
+// nstr: p.noise_strength[0], read once per kernel.
+__device__ __forceinline__ EpiColumn conv_epi_column(const ConvFwdParams& p, const EpiAct& ea, int g, int ks, int n, int plane_off, float nstr) {
+    const int OHW = p.OH * p.OW;
+    const bool fused = p.ksplit == 1;
+    EpiColumn c;
+    c.y = p.y;
+    c.res = fused ? p.res : nullptr;
+    c.partial = fused ? nullptr : p.partial + (int64_t)ks * p.N * p.Cout * OHW;
+    c.off = ((int64_t)n * p.Cout + (int64_t)g * p.Og) * OHW + plane_off;
+    c.ostride = OHW;
+    c.oscale = (p.oscale && fused) ? p.oscale + (int64_t)n * p.Cout + (int64_t)g * p.Og : nullptr;
+    c.bias = (ea.on && p.bias) ? p.bias + g * p.Og : nullptr;
+    c.has_noise = p.noise && fused;
+    c.nz = c.has_noise ? p.noise[(p.noise_ps ? (int64_t)n * OHW : 0) + plane_off] * nstr : 0.f;
+    return c;
+}
+
+// The arithmetic of a launch of the split forward-type kernels as their template arguments: f(NP, IO, ISC) with std::integral_constants.
+// q.bf16x6 = pieces per operand (3: six products, 2: three, 1: one, NP_F16X3); 16-bit storage is always one product; q.iscale (the input
+// scale rides in the staging) implies fp32 storage and fp32-equivalent products (the caller checked).
+template <class F>
+static void conv_arith_dispatch(const ConvFwdParams& q, F&& f) {
+    using std::integral_constant;
+    typedef integral_constant<int, NP_F16X3> HX;
+    typedef integral_constant<int, IO_F32> F32;
+    const bool hx = q.bf16x6 == NP_F16X3;
+    if (q.iscale && hx)       f(HX{}, F32{}, std::true_type{});
+    else if (q.iscale)        f(integral_constant<int, 3>{}, F32{}, std::true_type{});
+    else if (q.io == IO_BF16) f(integral_constant<int, 1>{}, integral_constant<int, IO_BF16>{}, std::false_type{});
+    else if (q.io == IO_F16)  f(integral_constant<int, 1>{}, integral_constant<int, IO_F16>{}, std::false_type{});
+    else if (q.bf16x6 == 1)   f(integral_constant<int, 1>{}, F32{}, std::false_type{});
+    else if (q.bf16x6 == 2)   f(integral_constant<int, 2>{}, F32{}, std::false_type{});
+    else if (hx)              f(HX{}, F32{}, std::false_type{});
+    else                      f(integral_constant<int, 3>{}, F32{}, std::false_type{});
+}
 
 // Tile choice.  O_pad multiple returned so that the caller can pack weights accordingly.
 enum FwdTile { T128x128 = 0, T64x256 = 1, T32x256 = 2, T64x64 = 3 };

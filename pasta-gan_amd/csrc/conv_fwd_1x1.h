@@ -150,55 +150,21 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(ConvFwdParams p) 
         __syncthreads();
     }
 
-    // back to the operands' units, then the epilogue of the forward-type kernels (residual, bias, activation, gain, clamp)
-    {
-        const float* const wri = p.w_rowinv + o_blk;
-        float ws[WMT][16];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) ws[a][r] = wri[(wm * WMT + a) * 32 + acc_row(r, lane)];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int b = 0; b < WNT; b++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] = (acc[a][b][r] * isx) * ws[a][r];
-    }
+    // back to the operands' units, then the epilogue of the forward-type kernels (residual, bias, activation, gain, clamp: conv_common.h)
+    conv_unscale_rows<WMT, WNT>(p.w_rowinv + o_blk, isx, wm, lane, acc);
     const int64_t ybase = (int64_t)n_img * p.Cout * HW + (pix_blk - (int64_t)n_img * HW);
-    // bias per output row and the residual of a 32 x 32 sub-tile are fetched in front of the stores (a load in front of every store serialises on
-    // the memory counter: conv_fwd_rows2d_bf16x6.h)
     // the stores: instantiated per (activation, clamp, whole tile of rows) and chosen once per workgroup (conv_common.h)
     const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, true);
     conv_epilogue_dispatch<true>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
-        const bool FULL = full_c;
 #pragma unroll
         for (int b = 0; b < WNT; b++) {
             const int64_t yoff = ybase + (wn * WNT + b) * 32 + jl;
+            EpiColumn col = {};               // no output scale, noise or K slices in this kernel
+            col.y = p.y; col.res = p.res; col.off = yoff; col.ostride = HW;
+            col.bias = ea.on ? p.bias : nullptr;
 #pragma unroll
-            for (int a = 0; a < WMT; a++) {
-                float tv[16];                           // residual, then bias, through the same registers: sixteen loads in a row, then their use
-                if (p.res) {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                        tv[r] = (FULL || o < p.Og) ? p.res[yoff + (int64_t)o * HW] : 0.f;
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; r++) acc[a][b][r] += tv[r];
-                }
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                    tv[r] = (ea.on && p.bias) ? p.bias[(FULL || o < p.Og) ? o : p.Og - 1] : 0.f;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                    const float v = conv_epilogue_c(acc[a][b][r], tv[r], ea, case_c);
-                    if (FULL || o < p.Og) { p.y[yoff + (int64_t)o * HW] = v; amax_take(y_am, v); }
-                }
-            }
+            for (int a = 0; a < WMT; a++)
+                conv_store_subtile<IO_F32>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
         }
     });
     amax_commit(y_am, y_slot);

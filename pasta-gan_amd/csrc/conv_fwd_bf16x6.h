@@ -457,31 +457,12 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
         step(1, st1, st0);
     }
 
-    const int OHW = p.OH * p.OW;
     if constexpr (HX) {
-        // back to the operands' units: 1 / S_x for the tile, 1 / S_w per weight row (p.w_rowinv, written by the packing kernel).  The 32 row
-        // scales of this lane are fetched in one go in front of the stores (a load in front of every store cost 9 % of the kernel).
-        const float* const wri = p.w_rowinv + (int64_t)g * p.Og_pad + o_blk;
-        float ws[WMT][16];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) ws[a][r] = wri[(wm * WMT + a) * 32 + acc_row(r, lane)];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int b = 0; b < WNT; b++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    acc[a][b][r] = (acc[a][b][r] * out_scale) * ws[a][r];
-                    
-                }
+        conv_unscale_rows<WMT, WNT>(p.w_rowinv + (int64_t)g * p.Og_pad + o_blk, out_scale, wm, lane, acc);
     }
-    const bool has_noise = p.noise && p.ksplit == 1;
-    const float nstr = has_noise ? p.noise_strength[0] : 0.f;
+    const float nstr = (p.noise && p.ksplit == 1) ? p.noise_strength[0] : 0.f;
     const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, p.ksplit == 1);
     conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32)>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
-    const bool FULL = full_c;
 #pragma unroll
     for (int b = 0; b < WNT; b++) {
         const int64_t pix = pix_blk + (wn * WNT + b) * 32 + jl;
@@ -490,54 +471,10 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
         const int rem = (int)(pix - (int64_t)n * P * Q);
         const int pp = rem / Q, qq = rem - pp * Q;
         const int plane_off = (oy0 + pp * p.osy) * p.OW + ox0 + qq * p.osx;
-        const int64_t yoff = ((int64_t)n * p.Cout + (int64_t)g * p.Og) * OHW + plane_off;
-        const float nz = has_noise ? p.noise[(p.noise_ps ? (int64_t)n * OHW : 0) + plane_off] * nstr : 0.f;
-        float* pb = p.ksplit > 1 ? p.partial + (int64_t)ks * p.N * p.Cout * OHW + yoff : nullptr;      // K slices: fp32 partial sums
-        const bool has_res = p.res && p.ksplit == 1;
-        const float* osb = (p.oscale && p.ksplit == 1) ? p.oscale + (int64_t)n * p.Cout + (int64_t)g * p.Og : nullptr;
+        const EpiColumn col = conv_epi_column(p, ea, g, ks, n, plane_off, nstr);
 #pragma unroll
-        for (int a = 0; a < WMT; a++) {
-            // what the sixteen stores of a 32 x 32 sub-tile need from memory -- output scale, residual, bias -- is fetched in front of them
-            // (a load in front of every store serialises on the memory counter: conv_fwd_rows2d_bf16x6.h)
-            // (one operand kind at a time through the same sixteen registers: three arrays side by side spill on the three-workgroup tiles)
-            float tv[16];
-            const bool has_bias = p.act && p.ksplit == 1 && p.bias;
-            if (osb) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) { const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane); tv[r] = osb[o < p.Og ? o : p.Og - 1]; }
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] = fmaf(acc[a][b][r], tv[r], nz);
-            } else if (has_noise) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] += nz;
-            }
-            if (has_res) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                    tv[r] = o < p.Og ? io_ld1<IO>((const char*)p.res + (yoff + (int64_t)o * OHW) * ES) : 0.f;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] += tv[r];
-            }
-            if (pb) {                                   // K slices: fp32 partial sums, nothing else (scale, residual, bias, activation ride in the reduction)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                    if (o < p.Og) pb[(int64_t)o * OHW] = acc[a][b][r];
-                }
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; r++) { const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane); tv[r] = has_bias ? p.bias[g * p.Og + (o < p.Og ? o : p.Og - 1)] : 0.f; }
-            // the stores: instantiated per (activation, clamp, whole tile of rows), no wave-uniform branch per element (conv_common.h)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                const float v = conv_epilogue_c(acc[a][b][r], tv[r], ea, case_c);
-                if (FULL || o < p.Og) { io_st<IO>(p.y, yoff + (int64_t)o * OHW, v); amax_take(y_am, v); }
-            }
-        }
+        for (int a = 0; a < WMT; a++)
+            conv_store_subtile<IO, EPI_RES_ROWTEST>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
     }
     });
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
@@ -1001,23 +938,8 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
 
     const int OHW = p.OH * p.OW;
     if constexpr (HX) {
-        // back to the operands' units: 1 / S_x for the tile, 1 / S_w per weight row (p.w_rowinv, written by the packing kernel).  The 32 row
-        // scales of this lane are fetched in one go in front of the stores (a load in front of every store cost 9 % of the kernel).
         const float* const wri = p.w_rowinv + (int64_t)g * p.Og_pad + o_blk;
-        float ws[WMT][16];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) ws[a][r] = wri[(wm * WMT + a) * 32 + acc_row(r, lane)];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int b = 0; b < WNT; b++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    acc[a][b][r] = (acc[a][b][r] * out_scale) * ws[a][r];
-                    if constexpr (PAIR) acc2[a][b][r] = (acc2[a][b][r] * out_scale) * ws[a][r];
-                }
+        if constexpr (PAIR) conv_unscale_rows<WMT, WNT>(wri, out_scale, wm, lane, acc, acc2); else conv_unscale_rows<WMT, WNT>(wri, out_scale, wm, lane, acc);
     }
     if constexpr (PAIR) {
         // (p, q) of the input lattice -> output row 2p + a, columns 2q and 2q + 1: one 8-byte store per lane
@@ -1044,11 +966,9 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
         }
         return;
     }
-    const bool has_noise = p.noise && p.ksplit == 1;
-    const float nstr = has_noise ? p.noise_strength[0] : 0.f;
+    const float nstr = (p.noise && p.ksplit == 1) ? p.noise_strength[0] : 0.f;
     const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, p.ksplit == 1);
     conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32)>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
-    const bool FULL = full_c;
 #pragma unroll
     for (int b = 0; b < WNT; b++) {
         const int64_t pix = pix_blk + (wn * WNT + b) * 32 + jl;
@@ -1056,54 +976,10 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
         const int rem = (int)(pix - (int64_t)n * P * Q);
         const int pp = rem / Q, qq = rem - pp * Q;
         const int plane_off = (oy0 + pp * p.osy) * p.OW + ox0 + qq * p.osx;
-        const int64_t yoff = ((int64_t)n * p.Cout + (int64_t)g * p.Og) * OHW + plane_off;
-        const float nz = has_noise ? p.noise[(p.noise_ps ? (int64_t)n * OHW : 0) + plane_off] * nstr : 0.f;
-        float* pb = p.ksplit > 1 ? p.partial + (int64_t)ks * p.N * p.Cout * OHW + yoff : nullptr;      // K slices: fp32 partial sums
-        const bool has_res = p.res && p.ksplit == 1;
-        const float* osb = (p.oscale && p.ksplit == 1) ? p.oscale + (int64_t)n * p.Cout + (int64_t)g * p.Og : nullptr;
+        const EpiColumn col = conv_epi_column(p, ea, g, ks, n, plane_off, nstr);
 #pragma unroll
-        for (int a = 0; a < WMT; a++) {
-            // what the sixteen stores of a 32 x 32 sub-tile need from memory -- output scale, residual, bias -- is fetched in front of them
-            // (a load in front of every store serialises on the memory counter: conv_fwd_rows2d_bf16x6.h)
-            // (one operand kind at a time through the same sixteen registers: three arrays side by side spill on the three-workgroup tiles)
-            float tv[16];
-            const bool has_bias = p.act && p.ksplit == 1 && p.bias;
-            if (osb) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) { const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane); tv[r] = osb[o < p.Og ? o : p.Og - 1]; }
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] = fmaf(acc[a][b][r], tv[r], nz);
-            } else if (has_noise) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] += nz;
-            }
-            if (has_res) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                    tv[r] = o < p.Og ? io_ld1<IO>((const char*)p.res + (yoff + (int64_t)o * OHW) * ES) : 0.f;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] += tv[r];
-            }
-            if (pb) {                                   // K slices: fp32 partial sums, nothing else (scale, residual, bias, activation ride in the reduction)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                    if (o < p.Og) pb[(int64_t)o * OHW] = acc[a][b][r];
-                }
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; r++) { const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane); tv[r] = has_bias ? p.bias[g * p.Og + (o < p.Og ? o : p.Og - 1)] : 0.f; }
-            // the stores: instantiated per (activation, clamp, whole tile of rows), no wave-uniform branch per element (conv_common.h)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r, lane);
-                const float v = conv_epilogue_c(acc[a][b][r], tv[r], ea, case_c);
-                if (FULL || o < p.Og) { io_st<IO>(p.y, yoff + (int64_t)o * OHW, v); amax_take(y_am, v); }
-            }
-        }
+        for (int a = 0; a < WMT; a++)
+            conv_store_subtile<IO>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
     }
     });
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
@@ -1126,17 +1002,9 @@ static void launch_fwd_rows_np(const ConvFwdParams& q, dim3 grid, hipStream_t s)
     hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 1, NP, IO, ISC>), grid, dim3(256), lds, s, q);
 }
 
-// q.bf16x6 = pieces per operand (3: six products, 2: three, 1: one, NP_F16X3); q.iscale implies fp32 storage and fp32-equivalent products (the caller checked)
 template <int BM, int BN>
 static void launch_fwd_rows_any(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
-    if (q.iscale && q.bf16x6 == NP_F16X3) launch_fwd_rows_np<BM, BN, NP_F16X3, IO_F32, true>(q, grid, s);
-    else if (q.iscale)             launch_fwd_rows_np<BM, BN, 3, IO_F32, true>(q, grid, s);
-    else if (q.io == IO_BF16)      launch_fwd_rows_np<BM, BN, 1, IO_BF16>(q, grid, s);       // 16-bit storage: always one product
-    else if (q.io == IO_F16)       launch_fwd_rows_np<BM, BN, 1, IO_F16>(q, grid, s);
-    else if (q.bf16x6 == 1)        launch_fwd_rows_np<BM, BN, 1, IO_F32>(q, grid, s);
-    else if (q.bf16x6 == 2)        launch_fwd_rows_np<BM, BN, 2, IO_F32>(q, grid, s);
-    else if (q.bf16x6 == NP_F16X3) launch_fwd_rows_np<BM, BN, NP_F16X3, IO_F32>(q, grid, s);
-    else                           launch_fwd_rows_np<BM, BN, 3, IO_F32>(q, grid, s);
+    conv_arith_dispatch(q, [&](auto np, auto io, auto isc) { launch_fwd_rows_np<BM, BN, decltype(np)::value, decltype(io)::value, decltype(isc)::value>(q, grid, s); });
 }
 
 // The base kernel (conv_tu_fwd_base_*.hip): any lattice, the packed-K mode, the input scale.
@@ -1150,14 +1018,11 @@ static void launch_fwd_base_np(const ConvFwdParams& q, dim3 grid, hipStream_t s)
 
 template <int BM, int BN>
 static void launch_fwd_base_any(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
-    if (q.iscale && q.bf16x6 == NP_F16X3) hipLaunchKernelGGL((conv_fwd_bf16x6_kernel<BM, BN, 2, NP_F16X3, IO_F32, true>), grid, dim3(256), 0, s, q);
-    else if (q.iscale)             hipLaunchKernelGGL((conv_fwd_bf16x6_kernel<BM, BN, 2, 3, IO_F32, true>), grid, dim3(256), 0, s, q);
-    else if (q.io == IO_BF16)      launch_fwd_base_np<BM, BN, 1, IO_BF16>(q, grid, s);
-    else if (q.io == IO_F16)       launch_fwd_base_np<BM, BN, 1, IO_F16>(q, grid, s);
-    else if (q.bf16x6 == 1)        launch_fwd_base_np<BM, BN, 1, IO_F32>(q, grid, s);
-    else if (q.bf16x6 == 2)        launch_fwd_base_np<BM, BN, 2, IO_F32>(q, grid, s);
-    else if (q.bf16x6 == NP_F16X3) launch_fwd_base_np<BM, BN, NP_F16X3, IO_F32>(q, grid, s);
-    else                           launch_fwd_base_np<BM, BN, 3, IO_F32>(q, grid, s);
+    conv_arith_dispatch(q, [&](auto np, auto io, auto isc) {
+        constexpr int NP = decltype(np)::value, IO = decltype(io)::value;
+        if constexpr (decltype(isc)::value) hipLaunchKernelGGL((conv_fwd_bf16x6_kernel<BM, BN, 2, NP, IO, true>), grid, dim3(256), 0, s, q);
+        else launch_fwd_base_np<BM, BN, NP, IO>(q, grid, s);
+    });
 }
 
 // Parity-pair launch of the row-reuse kernel (see its PAIR note): p.cls[0..1] are the two vertical parities over the input

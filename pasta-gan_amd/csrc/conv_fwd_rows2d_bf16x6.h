@@ -349,29 +349,10 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
 
     const int OHW = p.OH * p.OW;
     if constexpr (HX) {
-        // back to the operands' units: 1 / S_x for the tile, 1 / S_w per weight row (p.w_rowinv, written by the packing kernel).  The 32 row
-        // scales of this lane are fetched in one go in front of the stores (a load in front of every store cost 9 % of the kernel).
-        const float* const wri = p.w_rowinv + (int64_t)g * p.Og_pad + o_blk;
-        float ws[WMT][16];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) ws[a][r] = wri[(wm * WMT + a) * 32 + acc_row(r, lane)];
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-#pragma unroll
-            for (int b = 0; b < WNT; b++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    acc[a][b][r] = (acc[a][b][r] * out_scale) * ws[a][r];
-                }
+        conv_unscale_rows<WMT, WNT>(p.w_rowinv + (int64_t)g * p.Og_pad + o_blk, out_scale, wm, lane, acc);
     }
     const bool has_noise = p.noise && p.ksplit == 1;
     const float nstr = has_noise ? p.noise_strength[0] : 0.f;
-    // What an output ROW brings to the epilogue -- bias, output scale -- depends on (a, r16) only: fetched once, in front of the stores, like
-    // the row scales above; the residual of a 32 x 32 sub-tile is fetched as sixteen loads in a row and then stored over.  (One load in
-    // front of every store serialises on the memory counter: the input-gradient launches that carry another consumer's gradient as residual
-    // ran 4 % SLOWER than launch + torch addition that way, profiles/r4_ab_grad_join.txt.)
     const bool fused = p.ksplit == 1;
     const bool has_res = p.res && fused;
     const float* osb = (p.oscale && fused) ? p.oscale + (int64_t)n_img * p.Cout + (int64_t)g * p.Og : nullptr;
@@ -434,46 +415,15 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
     // (here fused holds: an output scale, a bias or a residual exist only without K slices)
     const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, true);
     conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32)>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
-        const bool FULL = full_c;
 #pragma unroll
         for (int b = 0; b < WNT; b++) {
             const int t = (wn * WNT + b) * 32 + jl;
             const int r = t / SEG, c = t - r * SEG;
             const int plane_off = (p0 + r) * p.OW + q0 + c;             // stride-1 lattice: the output plane itself
-            const int64_t yoff = ((int64_t)n_img * p.Cout + (int64_t)g * p.Og) * OHW + plane_off;
-            const float nz = has_noise ? p.noise[(p.noise_ps ? (int64_t)n_img * OHW : 0) + plane_off] * nstr : 0.f;
+            const EpiColumn col = conv_epi_column(p, ea, g, ks, n_img, plane_off, nstr);       // (no K slices here: col.partial is null, its branch never taken)
 #pragma unroll
-            for (int a = 0; a < WMT; a++) {
-                // one operand kind at a time through the same sixteen registers (output scale, residual, bias side by side in arrays of
-                // their own spill next to the sixty-four accumulators and the store addresses): sixteen loads in a row, then their use
-                float tv[16];
-                if (osb) {
-#pragma unroll
-                    for (int r16 = 0; r16 < 16; r16++) { const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r16, lane); tv[r16] = osb[(FULL || o < p.Og) ? o : p.Og - 1]; }
-#pragma unroll
-                    for (int r16 = 0; r16 < 16; r16++) acc[a][b][r16] = fmaf(acc[a][b][r16], tv[r16], nz);
-                } else if (has_noise) {
-#pragma unroll
-                    for (int r16 = 0; r16 < 16; r16++) acc[a][b][r16] += nz;
-                }
-                if (has_res) {
-#pragma unroll
-                    for (int r16 = 0; r16 < 16; r16++) {
-                        const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r16, lane);
-                        tv[r16] = (FULL || o < p.Og) ? io_ld1<IO>((const char*)p.res + (yoff + (int64_t)o * OHW) * ES) : 0.f;
-                    }
-#pragma unroll
-                    for (int r16 = 0; r16 < 16; r16++) acc[a][b][r16] += tv[r16];
-                }
-#pragma unroll
-                for (int r16 = 0; r16 < 16; r16++) { const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r16, lane); tv[r16] = bsb ? bsb[(FULL || o < p.Og) ? o : p.Og - 1] : 0.f; }
-#pragma unroll
-                for (int r16 = 0; r16 < 16; r16++) {
-                    const int o = o_blk + (wm * WMT + a) * 32 + acc_row(r16, lane);
-                    const float v = conv_epilogue_c(acc[a][b][r16], tv[r16], ea, case_c);
-                    if (FULL || o < p.Og) { io_st<IO>(p.y, yoff + (int64_t)o * OHW, v); amax_take(y_am, v); }
-                }
-            }
+            for (int a = 0; a < WMT; a++)
+                conv_store_subtile<IO>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
         }
     });
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
@@ -502,14 +452,7 @@ static void launch_fwd_rows2d(const ConvFwdParams& p, hipStream_t s) {
     constexpr int SEG = BN / R;
     const int64_t tiles = (int64_t)p.N * (p.cls[0].P / R) * (p.cls[0].Q / SEG);
     dim3 grid((unsigned)tiles, q.o_tiles * q.ksplit, p.G);
-    if (p.iscale && p.bf16x6 == NP_F16X3) launch_fwd_rows2d_np<BM, BN, R, NP_F16X3, IO_F32, true>(q, grid, s);
-    else if (p.iscale)       launch_fwd_rows2d_np<BM, BN, R, 3, IO_F32, true>(q, grid, s);   // fp32 storage, six products (the caller checked)
-    else if (p.io == IO_BF16) launch_fwd_rows2d_np<BM, BN, R, 1, IO_BF16>(q, grid, s);     // 16-bit storage: one product
-    else if (p.io == IO_F16) launch_fwd_rows2d_np<BM, BN, R, 1, IO_F16>(q, grid, s);
-    else if (p.bf16x6 == 1)  launch_fwd_rows2d_np<BM, BN, R, 1, IO_F32>(q, grid, s);
-    else if (p.bf16x6 == 2)  launch_fwd_rows2d_np<BM, BN, R, 2, IO_F32>(q, grid, s);
-    else if (p.bf16x6 == NP_F16X3) launch_fwd_rows2d_np<BM, BN, R, NP_F16X3, IO_F32>(q, grid, s);
-    else                     launch_fwd_rows2d_np<BM, BN, R, 3, IO_F32>(q, grid, s);
+    conv_arith_dispatch(q, [&](auto np, auto io, auto isc) { launch_fwd_rows2d_np<BM, BN, R, decltype(np)::value, decltype(io)::value, decltype(isc)::value>(q, grid, s); });
 }
 
 // Rows per 2-D tile for a P x Q lattice on the 128 x 128 tile: 4 (32-column segments), else 2 (64 columns), else 0 = the row kernel.

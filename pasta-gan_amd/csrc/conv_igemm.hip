@@ -4,7 +4,8 @@
 // live in the headers included below as templates, which this file never instantiates (it includes them for their host-side
 // shape predicates): every kernel family is compiled in a translation unit of its own, conv_tu_*.hip, and reached through
 // the functions of conv_launch.h -- eighteen units built in parallel (one unit of 161 kernels took 3 - 12 minutes):
-//   conv_common.h              parameter blocks, tile enumeration, epilogue
+//   conv_common.h              parameter blocks, tile enumeration, the shared epilogue of the split forward-type kernels (conv_unscale_rows,
+//                              conv_store_subtile) and the (input scale, storage, pieces) -> <NP, IO, ISC> dispatch of their launches
 //   conv_fwd_f32.h             fp32-MFMA forward-type kernel, weight packing        -> conv_tu_pack_f32.hip
 //   conv_fwd_bf16x6.h          split forward-type kernels (base and row-reuse)      -> conv_tu_fwd_base_{128,64}.hip, conv_tu_fwd_rows_{128,64}.hip
 //   conv_fwd_rows2d_bf16x6.h   2-D pixel tiles                                      -> conv_tu_rows2d_{wide,128_r4,128_r2,64_r8}.hip
@@ -104,6 +105,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
     amax_commit(am, aslot);
 }
+
+// the factor applied to the weights on the way in; a descriptor that leaves it zero means one
+static float desc_wscale(const pasta_conv_desc* d) { return d->wscale == 0.f ? 1.f : d->wscale; }
 
 // K slices for launches that would leave most CUs idle (the 4..17 pixel layers: K = 9*512 against <= 4624 pixels).
 static int64_t fwd_lattice_pixels(const pasta_conv_desc* d) {
@@ -658,7 +662,7 @@ static bool pack_job_of(const pasta_conv_desc* d, void* workspace, PackJob& j) {
     j.G = d->groups; j.Ig = Ig; j.Og = Og;
     j.Ig_pad = round_up(Ig, fwd_ipad(Ig, c.tile)); j.Og_pad = round_up(Og, fwd_tile_bm(c.tile));
     j.kh = d->kh; j.kw = d->kw; j.transposed = d->transposed; j.flip = d->flip;
-    j.wscale = d->wscale == 0.f ? 1.f : d->wscale;
+    j.wscale = desc_wscale(d);
     j.pack_xcd_rows = (j.Og_pad & 63) == 0 ? 1 : 0;
     return true;
 }
@@ -699,7 +703,7 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
         q.bias = ep ? ep->bias : nullptr; q.res = ep ? ep->res : nullptr; q.y_amax = ep ? ep->y_amax : nullptr;
         q.N = d->N; q.Cin = d->C_in; q.Cout = d->C_out; q.HW = d->H * d->W;
         q.w_io = d->transposed ? 1 : 0;
-        q.wscale = d->wscale == 0.f ? 1.f : d->wscale;
+        q.wscale = desc_wscale(d);
         q.act = ep ? ep->act : 0; q.alpha = ep ? ep->alpha : 0.f; q.gain = ep ? ep->gain : 1.f; q.clamp = ep ? ep->clamp : -1.f;
         tu_conv1x1_fewch(ch.kernel - 10, q, s);
         return launch_status("conv2d");
@@ -737,7 +741,7 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
     PASTA_CHECK(p.io == IO_F32 || p.bf16x6, "conv2d: no 16-bit-storage kernel for this shape (pasta_conv2d_plan tells beforehand)");
     p.rows = 0; p.rows_d0 = 0; p.rows_rev = 0;
 
-    const float wscale = d->wscale == 0.f ? 1.f : d->wscale;
+    const float wscale = desc_wscale(d);
     if (p.bf16x6 == NP_F16X3 && p.io == IO_F32) {
         // operand scale of x: partial |max| (the caller's, or one pass here), times max |iscale| when the styles ride in the staging.
         // The weights carry one scale per output row, found by their packing kernel (no |max| of w is passed or cached).
@@ -1036,7 +1040,7 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
         const int a_pad = ws.a_tiles * 64, bpad = ws.nb * 32;
         const dim3 grid((unsigned)fks, (unsigned)((d->C_out + 7) / 8));
         tu_wgrad1x1_fewcin(d->C_in, d->io_dtype, grid, dy, x, (float*)workspace, d->N, d->C_out, d->H * d->W, per, a_pad, bpad, s);
-        tu_wgrad_smallcin_reduce((const float*)workspace, dw, fks, d->C_out, ws.bprime, a_pad, bpad, d->wscale == 0.f ? 1.f : d->wscale, s);
+        tu_wgrad_smallcin_reduce((const float*)workspace, dw, fks, d->C_out, ws.bprime, a_pad, bpad, desc_wscale(d), s);
         return launch_status("conv2d_wgrad(few-channel 1x1)");
     }
     if (c.kernel == 1) {
@@ -1048,7 +1052,7 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
         q.chunks_total = ws.chunks_total; q.ksplit = ws.ksplit; q.a_tiles = ws.a_tiles;
         PASTA_CHECK(ws.lds_bytes <= 64 * 1024, "conv2d_wgrad: small-cin LDS footprint %zu too large", ws.lds_bytes);
         tu_wgrad_smallcin(q, ws.a_tiles * ws.ksplit, ws.lds_bytes, s);
-        tu_wgrad_smallcin_reduce((const float*)workspace, dw, ws.ksplit, d->C_out, ws.bprime, ws.a_tiles * 64, ws.nb * 32, d->wscale == 0.f ? 1.f : d->wscale, s);
+        tu_wgrad_smallcin_reduce((const float*)workspace, dw, ws.ksplit, d->C_out, ws.bprime, ws.a_tiles * 64, ws.nb * 32, desc_wscale(d), s);
         return launch_status("conv2d_wgrad(small-cin)");
     }
 
@@ -1094,7 +1098,7 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
         // slices [n m, (n + 1) m) hold sample n's gradient with respect to the modulated weight: dw = sum_n s[n, i] (.), ds[n, i] = sum_{o, taps} w (.)
         const int Ap = w.a_tiles * 64 * w.WA, Bp = w.b_tiles * 64 * w.WB;
         float* const dsp = (float*)workspace + w.slab_floats;
-        const float wsc = d->wscale == 0.f ? 1.f : d->wscale;
+        const float wsc = desc_wscale(d);
         const int wg_rows = wgrad_mod_rows(Ap, Bp, p.kh * p.kw);
         const dim3 grid((unsigned)(Bp / 64), (unsigned)(Ap / wg_rows), (unsigned)(p.kh * p.kw));
         tu_wgrad_reduce_modulated(d->transposed != 0, grid, (const float*)workspace, mod_s, mod_w, dw, dsp, w.ksplit, d->N, p.Ag, p.Bg, Ap, Bp, p.kh, p.kw, d->flip, wsc, wg_rows, s);
@@ -1104,6 +1108,6 @@ int pasta::wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_con
         return launch_status("conv2d_wgrad_modulated");
     }
     tu_wgrad_reduce((const float*)workspace, dw, w.ksplit, p.G, p.Ag, p.Bg, w.a_tiles * 64 * w.WA, w.b_tiles * 64 * w.WB, p.kh, p.kw, d->flip,
-                    d->wscale == 0.f ? 1.f : d->wscale, s);
+                    desc_wscale(d), s);
     return launch_status("conv2d_wgrad");
 }

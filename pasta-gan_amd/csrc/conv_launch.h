@@ -3,7 +3,9 @@
 // The planner and the C ABI live in conv_igemm.hip; every kernel family is compiled in a translation unit of its own (conv_tu_*.hip:
 // explicit instances behind plain host functions, built in parallel by torch_utils/custom_ops.py) and reached through the functions
 // declared here.  The kernel headers hold templates and host predicates only, so including them instantiates nothing; the few
-// non-template kernels are fenced by PASTA_TU_PACK / PASTA_TU_WGRAD_F32 and defined by exactly one unit.
+// non-template kernels are fenced by PASTA_TU_PACK / PASTA_TU_WGRAD_F32 and defined by exactly one unit.  What the forward-type kernels share
+// -- the epilogue of a 32 x 32 sub-tile (conv_store_subtile) and the choice of <NP, IO, ISC> for a launch (conv_arith_dispatch) -- is in
+// conv_common.h.
 #pragma once
 #include "conv_common.h"
 
