@@ -513,7 +513,8 @@ int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t*
  * quads [N][4][4][2] doubles = the corners of get_rectangle_mask (in its order, padded coordinates within +-1e5) for the left
  * upper arm, left forearm, right upper arm, right forearm; present [N][4]: 0 = the segment is missing (an all-ones mask).
  * Each fill is dilated with a 25 x 25 (upper arm, offsets -12..12) or 16 x 16 box (forearm, offsets -8..7);
- * palm = hand & !upper & !forearm per side (hand = label 14 left, 15 right), the sides OR-ed.  H must be 256. */
+ * palm = hand & !upper & !forearm per side (hand = label 14 left, 15 right), the sides OR-ed.  H must be 256
+ * (pasta_palm_mask_square_u8 takes the side and the boxes as arguments). */
 int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H, int W,
                        void* stream);
 
@@ -588,6 +589,59 @@ int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, c
  * each operation rounded on its own, clipped to [0, 255], truncated.  A NaN becomes 0 (numpy leaves that conversion
  * undefined). */
 int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Per-batch preparation of the 512 x 320 try-on pairs with a change region (row f4; UvitonDatasetFull_512_test,
+ * training/dataset.py:1528-2214, and test_512.py:115-131).  The unpadded canvas is 512 x 320, padded by 96 columns into a
+ * 512 x 512 square.  Same restated primitives and exactness as the entries above.  Where this set differs from the 256 test
+ * pairs:
+ *   1. the stick figure has lines of thickness 5 and discs of radius 5 (:1851, :1861); only the person's is used;
+ *   2. the palm rule works on the 512 square with a 35 x 35 upper-arm and a 20 x 20 forearm box (:1785-1796);
+ *   3. the lower garment is labels 9, 12 (:1639, :1669; not 6), the upper garment labels 5, 6, 7;
+ *   4. the change region picks whose garment is worn (:1679-1690): full body = both from the donor, upper body = the donor's
+ *      upper and the person's own lower garment, lower body = the person's own upper and the donor's lower garment; a garment
+ *      is warped forward with the matrices of the person it was taken from, and back with the person's M_inv;
+ *   5. all ten parts of the upper garment go into norm_img and denorm_upper, parts 0, 6, 7, 8, 9 of the lower garment into
+ *      norm_img_lower and denorm_lower; every warped-back mask is eroded 5 x 5, the legs' included (:2016, :2031);
+ *   6. there are no stick-figure patches: style_input is norm_img || norm_img_lower, 45 channels;
+ *   7. on the host, get_crop has no knee-without-ankle fall-back (:1893-1900) and its thigh fall-back ends at row 511.
+ * ------------------------------------------------------------------------- */
+/* pasta_pose_stickman_u8 with the line thickness t and the disc radius r as arguments.  Line: every pixel centre within
+ * distance t / 2 of the segment (the capsule of half-width t / 2), in integers 4 cross^2 <= t^2 len2 along the segment and
+ * 4 d^2 <= t^2 at its ends; for t = 2 that is pasta_pose_stickman_u8's rule, for t = 5 this project's restatement of cv2's
+ * thick line (a polygon of half-width t / 2 with round caps in 16.16 fixed point; parity UNPINNED).  Disc:
+ * (r - y)^2 + (c - x)^2 < radius^2, clipped to the canvas -- skimage's ((r - y) / R)^2 + ((c - x) / R)^2 < 1 on every integer
+ * offset for R = 2 and R = 5.  1 <= thickness, radius <= 64; (2, 2) is pasta_pose_stickman_u8 bit for bit. */
+int pasta_pose_stickman_thick_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness,
+                                 int radius, void* stream);
+
+/* pasta_palm_mask_box_u8 on an S x S square (get_hand_mask :1779-1799 has h = w = 512): parsing [N, S, W], out [N, S, S];
+ * S a multiple of 16, 16 <= S <= 512; 1 <= k <= S.  S = 256 is pasta_palm_mask_box_u8 bit for bit; the 512 x 320 set calls
+ * it with S = 512 and boxes (35, 20), offsets -17..17 and -10..9. */
+int pasta_palm_mask_square_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S, int W,
+                              int k_upper, int k_lower, void* stream);
+
+/* :1631-1690 from the person's image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H] and the donor's image and
+ * parsing: retain_img = the person's padded image * (shoes(18, 19) + palm + head(1, 2, 4, 13)); upper_img / upper_mask =
+ * labels 5, 6, 7 (image, 255) and lower_img / lower_mask = labels 9, 12 of the person the region names: region 0 (full body)
+ * both from the donor, 1 (upper body) upper from the donor and lower from the person, 2 (lower body) upper from the person
+ * and lower from the donor.  Outputs [N, H, H, 3], padding 255 in the images before the masks are applied, 0 in the labels. */
+int pasta_tryon_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
+                                const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask,
+                                uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W, int region, void* stream);
+
+/* __getitem__ (:2196-2214) and test_512.py:115-131: nine fp32 NCHW tensors through outputs (a HOST array of 9 device
+ * pointers) in this order: image, clothes [N,3,H,H] (the padded person and donor, padding 255), retain [N,3,H,H] =
+ * image * mask - (1 - mask) with the 0 / 1 retain mask, which equals x / 127.5 - 1 of retain_img bit for bit (the label groups
+ * are disjoint), pose [N,6,H,H] = stick || retain, style_input [N,3(P+P_lower),ph,pw] = the P upper-garment patches (channel
+ * 3k + c of part k) || the P_lower lower-garment patches, denorm_upper_input / denorm_lower_input [N,3,H,H],
+ * denorm_upper_mask / denorm_lower_mask [N,1,H,H] = channel sum > 0 (no wrap).  x / 127.5 - 1 as torch evaluates it on the
+ * GPU: x * (1 / 127.5f) - 1.  image, donor_image [N,H,W,3]; retain_img, stick, denorm_upper, denorm_lower [N,H,H,3];
+ * patches [N,P,ph,pw,3], patches_lower [N,P_lower,ph,pw,3] uint8. */
+int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image, const uint8_t* retain_img, const uint8_t* stick,
+                                const uint8_t* patches, const uint8_t* patches_lower, const uint8_t* denorm_upper,
+                                const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw,
+                                void* stream);
 
 #ifdef __cplusplus
 }

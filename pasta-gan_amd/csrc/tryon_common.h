@@ -14,7 +14,8 @@ __device__ __forceinline__ double tr_rounded(double x) { __asm__ volatile("" : "
 
 // ---- palm mask ----
 
-constexpr int PALM_S = 256;         // get_hand_mask works on a 256 x 256 square
+constexpr int PALM_S = 256;         // get_hand_mask of the 256 x 192 sets works on a 256 x 256 square
+constexpr int PALM_S_MAX = 512;     // the largest square (one thread per column; the 512 x 320 set's 512 x 512)
 constexpr int PALM_BAND = 16;       // output rows per block
 constexpr int PALM_SEGS = 4;        // left upper arm, left forearm, right upper arm, right forearm
 
@@ -82,19 +83,19 @@ __device__ __forceinline__ bool dilated_hit(const int16_t (*runs)[4], int X, int
     return false;
 }
 
-// The palm rule for one band of PALM_BAND rows of one sample (blockIdx.x = band, blockIdx.y = sample, 256 threads = columns):
-// each fill is dilated with the box of offsets -u_lo..u_hi (upper arm) or -b_lo..b_hi (forearm); runs: the block's
-// [PALM_SEGS][PALM_S][4] LDS array.
+// The palm rule for one band of PALM_BAND rows of one sample on an S x S square (blockIdx.x = band, blockIdx.y = sample, S
+// threads = columns): each fill is dilated with the box of offsets -u_lo..u_hi (upper arm) or -b_lo..b_hi (forearm); runs: the
+// block's [PALM_SEGS][S][4] LDS array.
 __device__ __forceinline__ void palm_mask_band(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
-                                               const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int H, int W, int lp,
-                                               int u_lo, int u_hi, int b_lo, int b_hi, int16_t (*runs)[PALM_S][4]) {
+                                               const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int S, int W, int lp,
+                                               int u_lo, int u_hi, int b_lo, int b_hi, int16_t (*runs)[4]) {
     const int n = blockIdx.y;
     const int X = threadIdx.x;
     const uint8_t* pres = present + n * PALM_SEGS;
     for (int sgm = 0; sgm < PALM_SEGS; sgm++)
-        if (pres[sgm]) rle_column_runs(quads + ((int64_t)n * PALM_SEGS + sgm) * 8, X, PALM_S, runs[sgm][X]);
+        if (pres[sgm]) rle_column_runs(quads + ((int64_t)n * PALM_SEGS + sgm) * 8, X, S, runs[sgm * S + X]);
     __syncthreads();
-    const uint8_t* lab = parsing + (int64_t)n * H * W;
+    const uint8_t* lab = parsing + (int64_t)n * S * W;
     for (int yy = 0; yy < PALM_BAND; yy++) {
         const int y = blockIdx.x * PALM_BAND + yy;
         const int c = X - lp;
@@ -103,11 +104,11 @@ __device__ __forceinline__ void palm_mask_band(const uint8_t* __restrict__ parsi
         if (label == 14 || label == 15) {     // hand: left = 14 (segments 0, 1), right = 15 (segments 2, 3)
             const int s0 = label == 14 ? 0 : 2;
             // a missing segment is an all-ones mask
-            const bool up = !pres[s0] || dilated_hit(runs[s0], X, y, u_lo, u_hi, PALM_S);
-            const bool bottom = !pres[s0 + 1] || dilated_hit(runs[s0 + 1], X, y, b_lo, b_hi, PALM_S);
+            const bool up = !pres[s0] || dilated_hit(runs + s0 * S, X, y, u_lo, u_hi, S);
+            const bool bottom = !pres[s0 + 1] || dilated_hit(runs + (s0 + 1) * S, X, y, b_lo, b_hi, S);
             palm = !up && !bottom;
         }
-        out[((int64_t)n * H + y) * H + X] = (uint8_t)palm;
+        out[((int64_t)n * S + y) * S + X] = (uint8_t)palm;
     }
 }
 

@@ -1,7 +1,9 @@
 // Per-sample preparation of the try-on data set on the GPU (row f4, the part of UvitonDatasetFull._load_raw_image /
 // __getitem__ and of the training loop's float conversions that is not the body-part warps of csrc/patches.hip):
-//   pasta_pose_stickman_u8  the pose stick figure (draw_pose_from_cords, dataset.py:704-736), padded;
-//   pasta_palm_mask_u8      the palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702);
+//   pasta_pose_stickman_u8  the pose stick figure (draw_pose_from_cords, dataset.py:704-736), padded; the line thickness and the
+//                           disc radius are arguments of pasta_pose_stickman_thick_u8 (2 and 2 here, 5 and 5 at 512 x 320);
+//   pasta_palm_mask_u8      the palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702): boxes 25 and 16 of
+//                           csrc/tryon_pairs.hip's kernel;
 //   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556);
 //   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456).
 // Every entry does a whole batch in one launch.  The reference does this on the host with OpenCV, pycocotools and skimage.
@@ -19,19 +21,22 @@ __constant__ uint8_t kpt_colors[19][3] = {          // dataset.py kptcolors
 
 constexpr int TRYON_LIMBS = 19, TRYON_JOINTS = 18;
 
-// The pixel (px, py) lies within distance 1 (the half-thickness) of the segment a -> b: the capsule of a thickness-2 line.
-__device__ __forceinline__ bool capsule_hit(int px, int py, int x0, int y0, int x1, int y1) {
+// The pixel (px, py) lies within distance t / 2 (the half-thickness) of the segment a -> b: the capsule of a thickness-t line,
+// in integers with t2 = t * t: 4 d^2 <= t^2 at the caps and 4 cross^2 <= t^2 len2 along the segment.  t = 2 is the thickness-2
+// rule d^2 <= 1, cross^2 <= len2.  Coordinates are within +-4096 (+ the canvas), so 4 cross^2 < 2^58.
+__device__ __forceinline__ bool capsule_hit(int px, int py, int x0, int y0, int x1, int y1, int64_t t2) {
     const int64_t dx = x1 - x0, dy = y1 - y0, ux = px - x0, uy = py - y0;
     const int64_t len2 = dx * dx + dy * dy, t = ux * dx + uy * dy;
-    if (len2 == 0 || t <= 0) return ux * ux + uy * uy <= 1;
-    if (t >= len2) { const int64_t vx = px - x1, vy = py - y1; return vx * vx + vy * vy <= 1; }
+    if (len2 == 0 || t <= 0) return 4 * (ux * ux + uy * uy) <= t2;
+    if (t >= len2) { const int64_t vx = px - x1, vy = py - y1; return 4 * (vx * vx + vy * vy) <= t2; }
     const int64_t cr = ux * dy - uy * dx;
-    return cr * cr <= len2;
+    return 4 * cr * cr <= t2 * len2;
 }
 
-// out[n, y, x, :] for the padded H x H square: limbs in order, then the 3 x 3 joint discs, the last hit wins.
+// out[n, y, x, :] for the padded H x H square: limbs of thickness t (t2 = t * t) in order, then the joint discs of radius r
+// (r2 = r * r), the last hit wins.
 __global__ __launch_bounds__(256) void pose_stickman_kernel(const int32_t* __restrict__ limbs, const int32_t* __restrict__ joints,
-                                                            uint8_t* __restrict__ out, int H, int W, int lp) {
+                                                            uint8_t* __restrict__ out, int H, int W, int lp, int t2, int r2) {
     const int n = blockIdx.y;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= H * H) return;
@@ -40,24 +45,17 @@ __global__ __launch_bounds__(256) void pose_stickman_kernel(const int32_t* __res
     if (c >= 0 && c < W) {
         const int32_t* lb = limbs + (int64_t)n * TRYON_LIMBS * 5;
         for (int i = 0; i < TRYON_LIMBS; i++, lb += 5)
-            if (lb[4] && capsule_hit(c, y, lb[0], lb[1], lb[2], lb[3])) color = i;
+            if (lb[4] && capsule_hit(c, y, lb[0], lb[1], lb[2], lb[3], t2)) color = i;
         const int32_t* jt = joints + (int64_t)n * TRYON_JOINTS * 3;
         for (int j = 0; j < TRYON_JOINTS; j++, jt += 3) {
-            const int ddx = c - jt[0], ddy = y - jt[1];
-            if (jt[2] && ddx >= -1 && ddx <= 1 && ddy >= -1 && ddy <= 1) color = j;     // (r - y)^2 + (c - x)^2 < 4
+            const int64_t ddx = c - jt[0], ddy = y - jt[1];
+            if (jt[2] && ddx * ddx + ddy * ddy < r2) color = j;          // (r - y)^2 + (c - x)^2 < radius^2 (radius 2: the 3 x 3 square)
         }
     }
     uint8_t* o = out + ((int64_t)n * H * H + pix) * 3;
     o[0] = color < 0 ? 0 : kpt_colors[color][0];
     o[1] = color < 0 ? 0 : kpt_colors[color][1];
     o[2] = color < 0 ? 0 : kpt_colors[color][2];
-}
-
-// boxes 25 x 25 (offsets -12..12) and 16 x 16 (anchor 8: -8..7)
-__global__ __launch_bounds__(256) void palm_mask_kernel(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
-                                                        const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int H, int W, int lp) {
-    __shared__ int16_t runs[PALM_SEGS][PALM_S][4];
-    palm_mask_band(parsing, quads, present, out, H, W, lp, 12, 12, 8, 7, runs);
 }
 
 // ---- label masks ----
@@ -170,23 +168,26 @@ __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __re
 
 }  // namespace pasta
 
-extern "C" int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, void* stream) {
+extern "C" int pasta_pose_stickman_thick_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness,
+                                            int radius, void* stream) {
     using namespace pasta;
-    PASTA_CHECK(limbs && joints && out, "pose_stickman_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "pose_stickman_u8: bad shape");
+    PASTA_CHECK(limbs && joints && out, "pose_stickman_thick_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "pose_stickman_thick_u8: bad shape");
+    PASTA_CHECK(thickness >= 1 && thickness <= 64 && radius >= 1 && radius <= 64, "pose_stickman_thick_u8: thickness %d, radius %d (1..64)",
+                thickness, radius);
     dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(pose_stickman_kernel, grid, dim3(256), 0, (hipStream_t)stream, limbs, joints, out, H, W, (H - W) / 2);
-    return launch_status("pose_stickman_u8");
+    hipLaunchKernelGGL(pose_stickman_kernel, grid, dim3(256), 0, (hipStream_t)stream, limbs, joints, out, H, W, (H - W) / 2,
+                       thickness * thickness, radius * radius);
+    return launch_status("pose_stickman_thick_u8");
+}
+
+extern "C" int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, void* stream) {
+    return pasta_pose_stickman_thick_u8(limbs, joints, out, N, H, W, 2, 2, stream);
 }
 
 extern "C" int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H,
                                   int W, void* stream) {
-    using namespace pasta;
-    PASTA_CHECK(parsing && quads && present && out, "palm_mask_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H == PALM_S && W >= 1 && W <= H, "palm_mask_u8: bad shape (the padded square is 256 x 256)");
-    dim3 grid((unsigned)(PALM_S / PALM_BAND), (unsigned)N);
-    hipLaunchKernelGGL(palm_mask_kernel, grid, dim3(PALM_S), 0, (hipStream_t)stream, parsing, quads, present, out, H, W, (H - W) / 2);
-    return launch_status("palm_mask_u8");
+    return pasta_palm_mask_box_u8(parsing, quads, present, out, N, H, W, 25, 16, stream);      // offsets -12..12 and -8..7
 }
 
 extern "C" int pasta_tryon_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain, uint8_t* gt_parsing,

@@ -1,7 +1,8 @@
 // Per-batch preparation of the try-on TEST pairs on the GPU (row f4, UvitonDatasetV19_test._load_raw_image / normalize /
 // __getitem__, training/dataset.py:1085-1525, and test.py:104-150), which the reference runs per sample on the host in four
 // loader processes with OpenCV, pycocotools and skimage:
-//   pasta_palm_mask_box_u8           the palm mask with both box sizes as arguments (25 / 15 here, :1240-1253);
+//   pasta_palm_mask_box_u8           the palm mask with both box sizes as arguments (25 / 15 here, :1240-1253), and
+//                                    pasta_palm_mask_square_u8 with the side of the square as well (512 for the 512 x 320 set);
 //   pasta_tryon_pair_masks_u8        retain image, the person's lower garment and the donor's upper garment (:1105-1141);
 //   pasta_patch_composite_eroded_u8  the warp-back composite with cv2.erode(5 x 5) of the mask before the == 255 test
 //                                    (:1480-1492);
@@ -22,12 +23,12 @@ namespace pasta {
 
 // ---- palm mask with the box sizes as arguments ----
 
-__global__ __launch_bounds__(256) void palm_mask_box_kernel(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
-                                                            const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int H, int W,
-                                                            int lp, int k_upper, int k_lower) {
-    __shared__ int16_t runs[PALM_SEGS][PALM_S][4];
+__global__ __launch_bounds__(PALM_S_MAX) void palm_mask_box_kernel(const uint8_t* __restrict__ parsing, const double* __restrict__ quads,
+                                                                   const uint8_t* __restrict__ present, uint8_t* __restrict__ out, int S,
+                                                                   int W, int lp, int k_upper, int k_lower) {
+    extern __shared__ int16_t runs[][4];        // [PALM_SEGS][S][4]: 8 KB at 256, 16 KB at 512
     // a k x k box with cv2's default anchor k / 2: offsets -(k / 2) .. k - 1 - k / 2
-    palm_mask_band(parsing, quads, present, out, H, W, lp, k_upper / 2, k_upper - 1 - k_upper / 2, k_lower / 2, k_lower - 1 - k_lower / 2, runs);
+    palm_mask_band(parsing, quads, present, out, S, W, lp, k_upper / 2, k_upper - 1 - k_upper / 2, k_lower / 2, k_lower - 1 - k_lower / 2, runs);
 }
 
 // ---- label masks of a pair ----
@@ -188,17 +189,25 @@ __global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restri
 
 }  // namespace pasta
 
+extern "C" int pasta_palm_mask_square_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S,
+                                         int W, int k_upper, int k_lower, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(parsing && quads && present && out, "palm_mask_square_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && S >= PALM_BAND && S <= PALM_S_MAX && S % PALM_BAND == 0 && W >= 1 && W <= S,
+                "palm_mask_square_u8: bad shape (the padded square: a multiple of %d up to %d)", PALM_BAND, PALM_S_MAX);
+    PASTA_CHECK(k_upper >= 1 && k_upper <= S && k_lower >= 1 && k_lower <= S, "palm_mask_square_u8: box sizes %d, %d (1..%d)", k_upper,
+                k_lower, S);
+    dim3 grid((unsigned)(S / PALM_BAND), (unsigned)N);
+    hipLaunchKernelGGL(palm_mask_box_kernel, grid, dim3(S), (size_t)PALM_SEGS * S * 4 * sizeof(int16_t), (hipStream_t)stream, parsing, quads,
+                       present, out, S, W, (S - W) / 2, k_upper, k_lower);
+    return launch_status("palm_mask_square_u8");
+}
+
 extern "C" int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H,
                                       int W, int k_upper, int k_lower, void* stream) {
     using namespace pasta;
-    PASTA_CHECK(parsing && quads && present && out, "palm_mask_box_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H == PALM_S && W >= 1 && W <= H, "palm_mask_box_u8: bad shape (the padded square is 256 x 256)");
-    PASTA_CHECK(k_upper >= 1 && k_upper <= PALM_S && k_lower >= 1 && k_lower <= PALM_S, "palm_mask_box_u8: box sizes %d, %d (1..256)",
-                k_upper, k_lower);
-    dim3 grid((unsigned)(PALM_S / PALM_BAND), (unsigned)N);
-    hipLaunchKernelGGL(palm_mask_box_kernel, grid, dim3(PALM_S), 0, (hipStream_t)stream, parsing, quads, present, out, H, W, (H - W) / 2,
-                       k_upper, k_lower);
-    return launch_status("palm_mask_box_u8");
+    PASTA_CHECK(H == PALM_S, "palm_mask_box_u8: bad shape (the padded square is 256 x 256)");
+    return pasta_palm_mask_square_u8(parsing, quads, present, out, N, H, W, k_upper, k_lower, stream);
 }
 
 extern "C" int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,

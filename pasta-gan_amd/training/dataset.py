@@ -6,7 +6,8 @@ not the prepared 13-tuple.  The preparation (stick figure, palm / retain masks, 
 mask, float conversions) runs for a whole batch on the GPU in ``training.tryon_batch.FullBodyBatchBuilder``; ``collate`` turns
 a list of raw samples into the batch the builder takes.  Only directory data sets are supported, as in the reference.
 The test pairs (``UvitonDatasetV19_test``, dataset.py:997-1525) follow the same design: raw pairs out, ``collate_pairs``, and
-``training.tryon_pairs.TryOnPairBatchBuilder`` on the GPU."""
+``training.tryon_pairs.TryOnPairBatchBuilder`` on the GPU; so do the 512 x 320 pairs with a change region
+(``UvitonDatasetFull_512_test``, dataset.py:1528-2214) with ``training.tryon_regions.TryOnRegionBatchBuilder``."""
 
 import json
 import os
@@ -19,6 +20,8 @@ SUB_DATASETS = ('Zalando_256_192', 'Zalora_256_192', 'Deepfashion_256_192', 'MPV
 PAIR_LIST = 'train_pairs_front_list_0508.txt'
 TEST_SUB_DATASETS = ('UPT_subset1_256_192', 'UPT_subset2_256_192')                              # dataset.py:1009
 TEST_PAIR_LIST = 'test_pairs_front_list_shuffle_0508.txt'
+SUB_DATASETS_512 = ('Zalando_512_320', 'Zalora_512_320', 'Deepfashion_512_320', 'MPV_512_320')     # dataset.py:1542
+CHANGE_REGIONS = ('fullbody', 'upperbody', 'lowerbody')                                         # dataset.py:1679-1692
 
 #----------------------------------------------------------------------------
 
@@ -186,6 +189,12 @@ class UvitonDatasetV19_test(Dataset):
     ``clothes_image`` / ``clothes_parsing`` / ``clothes_keypoints``, and ``person_name`` / ``clothes_name`` (the reference's
     relative paths, ``<sub-dataset>/image/<file>``)."""
 
+    _sub_datasets = TEST_SUB_DATASETS
+
+    @staticmethod
+    def _label_name(dataset, name):
+        return name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')     # :1030-1033
+
     def __init__(self, path, resolution=None, **super_kwargs):
         self._path = path
         if not os.path.isdir(self._path):
@@ -193,7 +202,7 @@ class UvitonDatasetV19_test(Dataset):
         self._type = 'dir'
         self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
         self._clothes_image_fnames, self._clothes_kpt_fnames, self._clothes_parsing_fnames = [], [], []
-        for dataset in TEST_SUB_DATASETS:
+        for dataset in self._sub_datasets:
             with open(os.path.join(self._path, dataset, TEST_PAIR_LIST), 'r') as f:
                 for line in f.readlines():
                     if not line.strip():
@@ -203,8 +212,7 @@ class UvitonDatasetV19_test(Dataset):
                                                        (clothes, self._clothes_image_fnames, self._clothes_kpt_fnames, self._clothes_parsing_fnames)):
                         images.append(os.path.join(dataset, 'image', name))
                         kpts.append(os.path.join(dataset, 'keypoints', name.replace('.jpg', '_keypoints.json')))
-                        label = name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')     # :1030-1033
-                        labels.append(os.path.join(dataset, 'parsing', label))
+                        labels.append(os.path.join(dataset, 'parsing', self._label_name(dataset, name)))
         self._vis_index = list(range(64))
 
         PIL.Image.init()
@@ -237,6 +245,36 @@ class UvitonDatasetV19_test(Dataset):
 
     def __getitem__(self, idx):
         return self.load_raw(self._raw_idx[idx])
+
+
+class UvitonDatasetFull_512_test(UvitonDatasetV19_test):
+    """dataset.py:1528-2214 -- the unpaired test pairs at 512 x 320 of ``Zalando_512_320``, ``Zalora_512_320``,
+    ``Deepfashion_512_320`` and ``MPV_512_320``, in this order: each line ``person clothes`` of their
+    ``test_pairs_front_list_shuffle_0508.txt``, in file order.  Label maps are ``parsing/<stem>_label.png`` in all four (the
+    256 set's ``.png`` exception for MPV does not apply, :1562-1563).  ``change_region`` is 'fullbody', 'upperbody' or
+    'lowerbody': which garments the person takes from the donor.
+
+    Differences from the reference, by design: ``__getitem__`` returns the raw pair, with the keys of
+    ``UvitonDatasetV19_test`` (so ``collate_pairs`` serves both), and not the prepared 12-tuple: stick figure, palm and label
+    masks, the region's warps and composites and the float conversions run for a whole batch on the GPU in
+    ``training.tryon_regions.TryOnRegionBatchBuilder``, which takes ``change_region`` itself.  Key points stay float64 and
+    unshifted.  An unknown ``change_region`` raises ValueError here, at construction; the reference raises it at the first
+    item (:1692)."""
+    _sub_datasets = SUB_DATASETS_512
+
+    @staticmethod
+    def _label_name(dataset, name):
+        return name.replace('.jpg', '_label.png')
+
+    def __init__(self, path, change_region, resolution=None, **super_kwargs):
+        if change_region not in CHANGE_REGIONS:
+            raise ValueError('change region %s is invalid.' % change_region)
+        self._change_region = change_region
+        super().__init__(path, resolution=resolution, **super_kwargs)
+
+    @property
+    def change_region(self):
+        return self._change_region
 
 
 def collate_pairs(samples):

@@ -1305,11 +1305,15 @@ class _TryOnGenerator(torch.nn.Module):
 
 @persistence.persistent_class
 class GeneratorFull(_TryOnGenerator):
-    """The training generator (networks.py:5843-5881): 14 garment patches x 3 channels."""
+    """The training generator (networks.py:5843-5881): 14 garment patches x 3 channels.  ``patch_channels`` (own extension,
+    an init kwarg so that it survives pickling) overrides the width of the patch stack: 45 for the 512 x 320 model of
+    test_512.py (ten upper-garment and five lower-garment patches), whose class the reference does not ship."""
     synthesis_class, patch_channels = SynthesisNetworkFull, 10 * 3 + 4 * 3
 
-    def __init__(self, z_dim, c_dim, w_dim, img_resolution, img_channels, mapping_kwargs={}, synthesis_kwargs={}):
+    def __init__(self, z_dim, c_dim, w_dim, img_resolution, img_channels, mapping_kwargs={}, synthesis_kwargs={}, patch_channels=None):
         super().__init__()
+        if patch_channels is not None:
+            self.patch_channels = int(patch_channels)
         self._build(z_dim, c_dim, w_dim, img_resolution, img_channels, mapping_kwargs, synthesis_kwargs)
 
 @persistence.persistent_class

@@ -228,3 +228,54 @@ def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower
     den_l = composite(list(range(UPPER_PARTS, 10)), lib.pasta_patch_composite_u8)
     m_invs = torch.from_numpy(np.where(valid_l[..., None, None], back_l, 0.0).astype(np.float32))
     return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l
+
+
+LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
+
+
+def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joints, upper_from_donor, lower_from_donor, box_factor=2):
+    """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch
+    on the GPU.  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image, 3-channel
+    mask) followed by the N lower garments.  ``donor_joints`` / ``person_joints`` [N, 18, 3] float64 (host), already shifted by
+    the padding (x_pad = 0); get_crop here has no shin fall-back (:1893-1900).  ``upper_from_donor`` / ``lower_from_donor``:
+    whose garment each is (full body: both the donor's; upper body: True, False; lower body: False, True).
+    All ten parts of the upper garment and parts 0, 6, 7, 8, 9 of the lower one are warped forward with the matrices of the
+    person the garment was taken from (one launch for the images, one for the masks) and back with the PERSON's M_inv through
+    the eroded composite, every part 5 x 5.  A part whose forward matrix is missing is zeros; a part whose M_inv is missing
+    is skipped.  Returns (patches [N,10,h,w,3], patches_lower [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper,
+    denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), donor_valid, person_valid [N,10] bool)."""
+    garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
+    n2, height, width, _ = garment_img.shape
+    n = n2 // 2
+    assert n2 == 2 * n and garment_mask.shape == garment_img.shape
+    ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
+    fwd_d, _, valid_d = part_matrices(donor_joints, width, height, box_factor, x_pad=0)
+    fwd_p, back, valid_p = part_matrices(person_joints, width, height, box_factor, x_pad=0)
+    fwd_u, valid_u = (fwd_d, valid_d) if upper_from_donor else (fwd_p, valid_p)
+    fwd_l, valid_l = (fwd_d, valid_d) if lower_from_donor else (fwd_p, valid_p)
+    dev = garment_img.device
+    low = list(LOWER_PARTS_512)
+    pu, pl = 10, len(low)
+    # items: (i, k) of the upper garments, then (i, k) of the lower garments, which read source N + i
+    mats = np.concatenate([fwd_u.reshape(-1, 3, 3), fwd_l[:, low].reshape(-1, 3, 3)])
+    valid = np.concatenate([valid_u.reshape(-1), valid_l[:, low].reshape(-1)])
+    src_index = np.concatenate([np.repeat(np.arange(n, dtype=np.int32), pu), np.repeat(np.arange(n, 2 * n, dtype=np.int32), pl)])
+    warp = lambda src: warp_perspective(src, mats, (ph, pw), 'replicate', src_index, valid)
+    split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
+    (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
+
+    def composite(src, msk, parts):
+        p = len(parts)
+        inv = np.ascontiguousarray(np.stack([adjugate_inverse(back[i, k]) for i in range(n) for k in parts]).reshape(n * p, 9))
+        inv_t = torch.from_numpy(inv).to(dev)
+        val_t = torch.as_tensor(np.ascontiguousarray(valid_p[:, parts]).astype(np.uint8), device=dev)
+        out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().pasta_patch_composite_eroded_u8(_native.ptr(src), _native.ptr(msk), _native.ptr(inv_t), _native.ptr(val_t),
+                                                                        _native.ptr(out), None, n, p, ph, pw, height, width, ERODE_RADIUS,
+                                                                        _native.stream()))
+        return out
+    den_u = composite(patches, mask_patches, list(range(pu)))
+    den_l = composite(patches_l, mask_patches_l, low)
+    m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
+    return patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p
