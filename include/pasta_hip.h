@@ -643,6 +643,43 @@ int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image
                                 const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw,
                                 void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The training run's snapshot image (setup_snapshot_image_grid, denorm_clothes, combine_parts and save_image_grid,
+ * training/training_loop_wo_flow_fullbody.py:36-209): a gnum x gnum mix-and-match grid, cell = row * gnum + col, row the
+ * person (pose, retain, M_inv) and col the clothes donor; gap = gnum / 3: rows < gap swap the trousers, rows < 2 gap the
+ * whole outfit, the others the top.  The reference warps and erodes on the host, about ten thousand OpenCV calls, and keeps
+ * fp32 tensors of all cells on the device; here the resident state is uint8 and the fp32 tensors exist per minibatch.  Same
+ * restated warp as the entries above (parity with OpenCV UNPINNED).
+ * ------------------------------------------------------------------------- */
+/* denorm_clothes (:59-107) for all cells of one garment in one launch: pasta_patch_composite_eroded_u8 whose part k of cell i
+ * reads patch and mask index[i][k] of a pool [T, ph, pw, 3] (int32; an index outside 0 .. T - 1 skips the part, as valid = 0
+ * does), warped with minv [cells][P][9] (doubles, dst -> src) into out [cells, H, W, 3]; parts composite in index order.
+ * With index[i][k] = i * P + k it is pasta_patch_composite_eroded_u8 bit for bit.  cells <= 65535, 0 <= radius <= 8. */
+int pasta_grid_composite_eroded_u8(const uint8_t* pool, const uint8_t* mask_pool, const int32_t* index, const double* minv,
+                                   const uint8_t* valid, uint8_t* out, int cells, int P, int T, int ph, int pw, int H, int W,
+                                   int radius, void* stream);
+
+/* The fp32 NCHW tensors G_ema takes (:121-175, :580-583) for cells lo .. lo + n - 1, through outputs (a HOST array of 7 device
+ * pointers) in this order: denorm_upper_input / denorm_lower_input [n,3,H,H] = x * (1 / 127.5f) - 1 of the cell's images,
+ * denorm_upper_mask / denorm_lower_mask [n,1,H,H] = channel sum > 0 (no uint8 wrap, :104-105), style_input
+ * [n,c_upper+c_lower,ph,pw] by combine_parts' rule (:36-56: upper channels of person row when row < gap, else of col; lower
+ * channels of col when row < 2 gap, else of row), pose [n,6,H,H] = stick || retain and retain [n,3,H,H] =
+ * retain_mask * image - (1 - retain_mask) of person row (:160-175).  denorm_upper, denorm_lower [gnum^2,H,H,3]; image (padded),
+ * stick [gnum,H,H,3]; retain_mask [gnum,H,H]; norm_img [gnum,ph,pw,c_upper]; norm_img_lower [gnum,ph,pw,c_lower]; all uint8.
+ * H and pw multiples of 4 (four pixels per thread), gnum <= 255. */
+int pasta_grid_assemble(const uint8_t* denorm_upper, const uint8_t* denorm_lower, const uint8_t* image, const uint8_t* stick,
+                        const uint8_t* retain_mask, const uint8_t* norm_img, const uint8_t* norm_img_lower, float* const* outputs,
+                        int lo, int n, int gnum, int H, int ph, int pw, int c_upper, int c_lower, void* stream);
+
+/* save_image_grid (:182-203): images [n, C, H, W] fp32 (C = 1 or 3) become tiles first .. first + n - 1 of a uint8 canvas
+ * [canvas_h, canvas_w, C]; tile t sits at tile row t / gw + oy and tile column t % gw + ox (the grid proper: gw = gnum,
+ * ox = oy = 1; the side column: gw = 1, ox = 0, oy = 1; the top row: ox = 1, oy = 0, its corner tile a tile of zeros at
+ * ox = oy = 0).  Per element rint((x - lo) * scale) in fp32 as numpy evaluates :184-186 with scale = 255 / (hi - lo): one
+ * subtraction and one multiplication, each rounded on its own, round half to even, clipped to [0, 255].  A NaN becomes 0
+ * (numpy leaves that conversion undefined).  W a multiple of 4; the tiles must lie inside the canvas. */
+int pasta_image_grid_tile_u8(const float* images, uint8_t* canvas, int n, int C, int H, int W, int first, int gw, int ox, int oy,
+                             int canvas_h, int canvas_w, float lo, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

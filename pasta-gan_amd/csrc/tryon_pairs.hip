@@ -17,7 +17,7 @@
 #include "tryon_common.h"
 
 #pragma clang fp contract(off)      // the warp-back coordinates must round as csrc/patches.hip's do
-#include "patch_warp.h"
+#include "patch_erode.h"
 
 namespace pasta {
 
@@ -62,14 +62,7 @@ __global__ __launch_bounds__(256) void tryon_pair_masks_kernel(const uint8_t* __
 
 // ---- eroded composite ----
 
-constexpr int ER_T = 16;            // output tile side: one thread per pixel of a 16 x 16 tile
-constexpr int ER_MAX_R = 8;         // largest erosion radius (a 17 x 17 box)
-constexpr int ER_S = ER_T + 2 * ER_MAX_R;
-
-// patch_composite_u8_kernel with cv2.erode(mask, ones(2r+1, 2r+1)) of the warped-back mask before the == 255 test.  Since
-// 255 is the largest uint8, the eroded channel 0 is 255 exactly where every in-image pixel within +-r has channel 0 == 255
-// (cv2's default erode border: pixels outside the image do not erode).  Per part: the == 255 flags of the tile and an r-pixel
-// halo go to LDS, are AND-ed along rows and then along columns; the running RGB stays in registers.
+// The tile work is csrc/patch_erode.h's (shared with the snapshot grid's indexed composite); here part k of sample n is item n * P + k.
 __global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8_t* __restrict__ patches, const uint8_t* __restrict__ masks,
                                                                      const double* __restrict__ minv, const uint8_t* __restrict__ valid,
                                                                      uint8_t* __restrict__ out, uint8_t* __restrict__ part_mask, int P, int ph,
@@ -77,56 +70,12 @@ __global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8
     __shared__ uint8_t flags[ER_S * ER_S];
     __shared__ uint8_t rows[ER_S * ER_T];
     const int n = blockIdx.y;
-    const int tx0 = (blockIdx.x % tiles_x) * ER_T, ty0 = (blockIdx.x / tiles_x) * ER_T;
-    const int S = ER_T + 2 * r;
-    const int ty = threadIdx.x / ER_T, tx = threadIdx.x % ER_T;
-    const int y = ty0 + ty, x = tx0 + tx;
-    const bool mine = y < H && x < W;
-    int red = 0, green = 0, blue = 0;
-    for (int k = 0; k < P; k++) {
+    const auto part_of = [=](int k) {
         const int64_t item = (int64_t)n * P + k;
-        if (!valid[item]) {                                     // uniform across the block: no barrier is skipped by a part
-            if (part_mask && mine) part_mask[item * H * W + (int64_t)y * W + x] = 0;
-            continue;
-        }
-        const double* m = minv + item * 9;
-        const uint8_t* mk = masks + item * ph * pw * 3;
-        for (int i = threadIdx.x; i < S * S; i += 256) {
-            const int gy = ty0 - r + i / S, gx = tx0 - r + i % S;
-            uint8_t f = 1;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                int X, Y;
-                pw_source(m, gx, gy, X, Y);
-                f = pw_sample(mk, pw, 3, 0, pw_taps(X, Y, pw, ph, 0)) == 255;
-            }
-            flags[i] = f;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < S * ER_T; i += 256) {
-            const int ry = i / ER_T, rx = i % ER_T;
-            uint8_t f = 1;
-            for (int d = 0; d <= 2 * r; d++) f &= flags[ry * S + rx + d];
-            rows[i] = f;
-        }
-        __syncthreads();
-        if (mine) {
-            uint8_t hit = 1;
-            for (int d = 0; d <= 2 * r; d++) hit &= rows[(ty + d) * ER_T + tx];
-            if (hit) {
-                int X, Y;
-                pw_source(m, x, y, X, Y);
-                const PwTaps t = pw_taps(X, Y, pw, ph, 0);
-                const uint8_t* pt = patches + item * ph * pw * 3;
-                red = pw_sample(pt, pw, 3, 0, t); green = pw_sample(pt, pw, 3, 1, t); blue = pw_sample(pt, pw, 3, 2, t);
-            }
-            if (part_mask) part_mask[item * H * W + (int64_t)y * W + x] = hit;
-        }
-        // the next part writes `flags` only after this barrier pair, and `rows` only after its own first barrier
-    }
-    if (mine) {
-        uint8_t* o = out + ((int64_t)n * H * W + (int64_t)y * W + x) * 3;
-        o[0] = (uint8_t)red; o[1] = (uint8_t)green; o[2] = (uint8_t)blue;
-    }
+        return ErPart{patches + item * ph * pw * 3, valid[item] ? masks + item * ph * pw * 3 : nullptr, minv + item * 9};
+    };
+    composite_eroded_tile(part_of, out + (int64_t)n * H * W * 3, part_mask ? part_mask + (int64_t)n * P * H * W : nullptr, P, ph, pw, H, W, r,
+                          blockIdx.x, tiles_x, flags, rows);
 }
 
 // ---- the seven tensors G takes ----

@@ -1,0 +1,300 @@
+"""Train PASTA-GAN's full-body model from the command line: the reference's train_wo_flow_fullbody.py (options :33-75 and
+:424-470, their mapping onto the training loop's arguments :76-385, the run directory and process start :472-567).
+
+    python train_wo_flow_fullbody.py --outdir=runs --data=<training tree> --gpus=8 --cfg=fashion --batch=64 \\
+        --l1_weight=40 --vgg_weight=0 --mask_weight=20 --aug=noaug
+
+The G / D / optimiser / loss options are ``training_loop_wo_flow_fullbody.fashion_config``'s and the augmentation options
+``augment_options``'s; a base config contributes the figures of the reference's ``cfg_specs`` table below.  Options this
+package cannot honour are refused with the reason, not ignored."""
+
+import json
+import os
+import re
+import tempfile
+
+import click
+import torch
+
+import dnnlib
+from training import training_loop_wo_flow_fullbody as training_loop
+
+#----------------------------------------------------------------------------
+
+class UserError(Exception):
+    pass
+
+# train_wo_flow_fullbody.py:166-174.  'auto' is filled in from the resolution and the GPU count (:178-187).
+CFG_SPECS = {
+    'auto':      dict(ref_gpus=-1, kimg=25000, mb=-1, mbstd=-1, fmaps=-1,  lrate=-1,    gamma=-1, ema=-1, ramp=0.05, map=2),
+    'stylegan2': dict(ref_gpus=8,  kimg=25000, mb=32, mbstd=4,  fmaps=0.5, lrate=0.002, gamma=10, ema=10, ramp=None, map=2),
+    'fashion':   dict(ref_gpus=8,  kimg=8000,  mb=32, mbstd=4,  fmaps=0.5, lrate=0.002, gamma=10, ema=10, ramp=None, map=1),
+}
+UNSUPPORTED_CFGS = ('paper256', 'paper512', 'paper1024', 'cifar')
+
+def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
+                               gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
+                               fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
+                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False):
+    """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
+    args = dnnlib.EasyDict()
+
+    # General options: gpus, snap, metrics, seed (:82-109)
+    gpus = 1 if gpus is None else gpus
+    if not (gpus >= 1 and gpus & (gpus - 1) == 0):
+        raise UserError('--gpus must be a power of two')
+    args.num_gpus = gpus
+    snap = 50 if snap is None else snap
+    if snap < 1:
+        raise UserError('--snap must be at least 1')
+    args.image_snapshot_ticks = args.network_snapshot_ticks = snap
+    if metrics:
+        raise UserError('--metrics must be none: metrics are not evaluated (the reference loop has its metric call commented out, and '
+                        'this package has no metrics/ with the Inception and VGG weights it needs)')
+    args.random_seed = 0 if seed is None else seed
+
+    # Dataset: data, cond, subset, mirror (:115-155)
+    assert isinstance(data, str)
+    args.training_set_kwargs = dnnlib.EasyDict(class_name='training.dataset.UvitonDatasetFull', path=data, use_labels=False, max_size=None,
+                                               xflip=False)
+    args.data_loader_kwargs = dnnlib.EasyDict(pin_memory=True, num_workers=0)
+    try:
+        training_set = dnnlib.util.construct_class_by_name(**args.training_set_kwargs)
+        args.training_set_kwargs.resolution = training_set.resolution
+        args.training_set_kwargs.max_size = len(training_set)
+        desc = training_set.name
+        del training_set
+    except IOError as err:
+        raise UserError(f'--data: {err}')
+    if cond:
+        raise UserError('--cond=true is not supported: the try-on data set has no labels (the generator is conditioned on the garment patches)')
+    if subset is not None:
+        if not 1 <= subset <= args.training_set_kwargs.max_size:
+            raise UserError(f'--subset must be between 1 and {args.training_set_kwargs.max_size}')
+        desc += f'-subset{subset}'
+        if subset < args.training_set_kwargs.max_size:
+            args.training_set_kwargs.max_size = subset
+            args.training_set_kwargs.random_seed = args.random_seed
+    if mirror:
+        raise UserError('--mirror=true is not supported: a mirrored person would need mirrored key points and left / right labels, '
+                        'which the data set does not provide')
+
+    # Base config: cfg, gamma, kimg, batch (:161-246)
+    cfg = 'auto' if cfg is None else cfg
+    desc += f'-{cfg}'
+    if cfg in UNSUPPORTED_CFGS:
+        raise UserError(f'--cfg={cfg} is not supported: only auto, stylegan2 and fashion are; the others are the image-synthesis '
+                        'presets of the code the reference was derived from')
+    spec = dnnlib.EasyDict(CFG_SPECS[cfg])
+    res = args.training_set_kwargs.resolution
+    if cfg == 'auto':
+        desc += f'{gpus:d}'
+        spec.ref_gpus = gpus
+        spec.mb = max(min(gpus * min(4096 // res, 32), 64), gpus)
+        spec.mbstd = min(spec.mb // gpus, 4)
+        spec.fmaps = 1 if res >= 512 else 0.5
+        spec.lrate = 0.002 if res >= 1024 else 0.0025
+        spec.gamma = 0.0002 * (res ** 2) / spec.mb
+        spec.ema = spec.mb * 10 / 32
+    # mixed precision as the reference enables it (:195-196): the three highest resolutions of G and of D in fp16
+    config = training_loop.fashion_config(channel_base=int(spec.fmaps * 32768), d_fp16_res=3, mbstd_group_size=spec.mbstd, img_resolution=res)
+    config.G_kwargs.mapping_kwargs.num_layers = spec.map
+    config.G_kwargs.synthesis_kwargs.use_noise = bool(use_noise_const_branch)
+    config.G_opt_kwargs.lr = config.D_opt_kwargs.lr = spec.lrate
+    config.loss_kwargs.update(r1_gamma=spec.gamma, l1_weight=l1_weight or 0, vgg_weight=vgg_weight or 0, pl_weight=pl_weight or 0,
+                              contextual_weight=contextual_weight or 0, mask_weight=mask_weight or 0)
+    config.ema_kimg, config.ema_rampup = spec.ema, spec.ramp
+    args.total_kimg = spec.kimg
+    args.batch_size = spec.mb
+    args.batch_gpu = spec.mb // spec.ref_gpus
+    if gamma is not None:
+        if not gamma >= 0:
+            raise UserError('--gamma must be non-negative')
+        desc += f'-gamma{gamma:g}'
+        config.loss_kwargs.r1_gamma = gamma
+    if kimg is not None:
+        if not kimg >= 1:
+            raise UserError('--kimg must be at least 1')
+        desc += f'-kimg{kimg:d}'
+        args.total_kimg = kimg
+    if batch is not None:
+        if not (batch >= 1 and batch % gpus == 0):
+            raise UserError('--batch must be at least 1 and divisible by --gpus')
+        desc += f'-batch{batch}'
+        args.batch_size = batch
+        args.batch_gpu = batch // gpus
+
+    # Discriminator augmentation: aug, p, target, augpipe (:252-313)
+    if aug is None:
+        aug = 'ada'
+    else:
+        desc += f'-{aug}'
+    if aug not in ('ada', 'noaug', 'fixed'):
+        raise UserError(f'--aug={aug} not supported')
+    if aug == 'fixed' and p is None:
+        raise UserError(f'--aug={aug} requires specifying --p')
+    if p is not None:
+        if aug != 'fixed':
+            raise UserError('--p can only be specified with --aug=fixed')
+        if not 0 <= p <= 1:
+            raise UserError('--p must be between 0 and 1')
+        desc += f'-p{p:g}'
+    if target is not None:
+        if aug != 'ada':
+            raise UserError('--target can only be specified with --aug=ada')
+        if not 0 <= target <= 1:
+            raise UserError('--target must be between 0 and 1')
+        desc += f'-target{target:g}'
+    if augpipe is None:
+        augpipe = 'bgc'
+    else:
+        if aug == 'noaug':
+            raise UserError('--augpipe cannot be specified with --aug=noaug')
+        desc += f'-{augpipe}'
+    config.update(training_loop.augment_options(aug=aug, augpipe=augpipe, p=p, target=target))
+
+    # Transfer learning: resume, freezed (:327-348)
+    if resume is None or resume == 'noresume':
+        desc += '-noresume' if resume is not None else ''
+    else:
+        if not os.path.isfile(resume):
+            raise UserError(f'--resume={resume}: not a file (the reference\'s named source networks and URLs are downloads, which are '
+                            'not supported; give the path of a network pickle)')
+        desc += '-resumecustom'
+        args.resume_pkl = resume
+        config.ada_kimg = 100       # make ADA react faster at the beginning
+        config.ema_rampup = None
+    if freezed is not None:
+        if not freezed >= 0:
+            raise UserError('--freezed must be non-negative')
+        desc += f'-freezed{freezed:d}'
+        config.D_kwargs.block_kwargs.freeze_layers = freezed
+
+    # Performance options: fp32, nhwc, allow_tf32, workers (:354-383); --nobench is accepted and means nothing here (no cuDNN)
+    if fp32:
+        config.G_kwargs.synthesis_kwargs.num_fp16_res = config.D_kwargs.num_fp16_res = 0
+        config.G_kwargs.synthesis_kwargs.conv_clamp = config.D_kwargs.conv_clamp = None
+    if nhwc:
+        raise UserError('--nhwc=true is not supported: the HIP convolution kernels take NCHW tensors')
+    if allow_tf32:
+        config.allow_tf32 = True
+    if workers is not None:
+        if not workers >= 1:
+            raise UserError('--workers must be at least 1')
+        args.data_loader_kwargs.num_workers = workers
+        args.data_loader_kwargs.prefetch_factor = 2
+
+    args.cfg = config
+    return desc, args
+
+#----------------------------------------------------------------------------
+
+def subprocess_fn(rank, args, temp_dir):
+    from torch_utils import training_stats
+    dnnlib.util.Logger(file_name=os.path.join(args.run_dir, 'log.txt'), file_mode='a', should_flush=True)
+    if args.num_gpus > 1:
+        init_file = os.path.abspath(os.path.join(temp_dir, '.torch_distributed_init'))
+        torch.distributed.init_process_group(backend='nccl', init_method=f'file://{init_file}', rank=rank, world_size=args.num_gpus)
+    sync_device = torch.device('cuda', rank) if args.num_gpus > 1 else None
+    training_stats.init_multiprocessing(rank=rank, sync_device=sync_device)
+    training_loop.training_loop(rank=rank, **args)
+
+#----------------------------------------------------------------------------
+
+class CommaSeparatedList(click.ParamType):
+    name = 'list'
+
+    def convert(self, value, param, ctx):
+        if value is None or value.lower() == 'none' or value == '':
+            return []
+        return value.split(',')
+
+@click.command()
+@click.pass_context
+# General options.
+@click.option('--outdir', help='Where to save the results', required=True, metavar='DIR')
+@click.option('--gpus', help='Number of GPUs to use [default: 1]', type=int, metavar='INT')
+@click.option('--snap', help='Snapshot interval [default: 50 ticks]', type=int, metavar='INT')
+@click.option('--metrics', help='"none" [default: none]; metrics are not evaluated', type=CommaSeparatedList())
+@click.option('--seed', help='Random seed [default: 0]', type=int, metavar='INT')
+@click.option('-n', '--dry-run', help='Print training options and exit', is_flag=True)
+# Dataset.
+@click.option('--data', help='Training data (directory)', metavar='PATH', required=True)
+@click.option('--cond', help='Not supported [default: false]', type=bool, metavar='BOOL')
+@click.option('--subset', help='Train with only N images [default: all]', type=int, metavar='INT')
+@click.option('--mirror', help='Not supported [default: false]', type=bool, metavar='BOOL')
+# Base config.
+@click.option('--cfg', help='Base config [default: auto]', type=click.Choice(list(CFG_SPECS) + list(UNSUPPORTED_CFGS)))
+@click.option('--gamma', help='Override R1 gamma', type=float)
+@click.option('--kimg', help='Override training duration', type=int, metavar='INT')
+@click.option('--batch', help='Override batch size', type=int, metavar='INT')
+# Discriminator augmentation.
+@click.option('--aug', help='Augmentation mode [default: ada]', type=click.Choice(['noaug', 'ada', 'fixed']))
+@click.option('--p', help='Augmentation probability for --aug=fixed', type=float)
+@click.option('--target', help='ADA target value for --aug=ada', type=float)
+@click.option('--augpipe', help='Augmentation pipeline [default: bgc]', type=click.Choice(sorted(training_loop.AUGPIPE_SPECS)))
+# Transfer learning.
+@click.option('--resume', help='Resume from a network pickle [default: noresume]', metavar='PKL')
+@click.option('--freezed', help='Freeze-D [default: 0 layers]', type=int, metavar='INT')
+# Performance options.
+@click.option('--fp32', help='Disable mixed-precision training', type=bool, metavar='BOOL')
+@click.option('--nhwc', help='Not supported', type=bool, metavar='BOOL')
+@click.option('--nobench', help='Accepted for compatibility; no effect', type=bool, metavar='BOOL')
+@click.option('--allow-tf32', help='Use the three-product split-bf16 convolution arithmetic', type=bool, metavar='BOOL')
+@click.option('--workers', help='Override number of DataLoader workers', type=int, metavar='INT')
+# Loss weights.
+@click.option('--pl_weight', type=float)
+@click.option('--l1_weight', help='G L1 loss weight', type=float)
+@click.option('--vgg_weight', help='vgg loss weight', type=float)
+@click.option('--contextual_weight', help='contextual loss weight', type=float)
+@click.option('--mask_weight', type=float)
+@click.option('--use_noise_const_branch', help='Enable const_branch noise input?', type=bool, metavar='BOOL')
+def main(ctx, outdir, dry_run, **config_kwargs):
+    """Train PASTA-GAN's full-body try-on model on the reference's training tree."""
+    try:
+        run_desc, args = setup_training_loop_kwargs(**config_kwargs)
+    except UserError as err:
+        ctx.fail(str(err))
+
+    # Pick output directory (:525-532).
+    prev_run_dirs = []
+    if os.path.isdir(outdir):
+        prev_run_dirs = [x for x in os.listdir(outdir) if os.path.isdir(os.path.join(outdir, x))]
+    prev_run_ids = [re.match(r'^\d+', x) for x in prev_run_dirs]
+    prev_run_ids = [int(x.group()) for x in prev_run_ids if x is not None]
+    cur_run_id = max(prev_run_ids, default=-1) + 1
+    args.run_dir = os.path.join(outdir, f'{cur_run_id:05d}-{run_desc}')
+    assert not os.path.exists(args.run_dir)
+
+    print()
+    print('Training options:')
+    print(json.dumps(args, indent=2))
+    print()
+    print(f'Output directory:   {args.run_dir}')
+    print(f'Training data:      {args.training_set_kwargs.path}')
+    print(f'Training duration:  {args.total_kimg} kimg')
+    print(f'Number of GPUs:     {args.num_gpus}')
+    print(f'Number of images:   {args.training_set_kwargs.max_size}')
+    print(f'Image resolution:   {args.training_set_kwargs.resolution}')
+    print()
+    if dry_run:
+        print('Dry run; exiting.')
+        return
+
+    print('Creating output directory...')
+    os.makedirs(args.run_dir)
+    with open(os.path.join(args.run_dir, 'training_options.json'), 'wt') as f:
+        json.dump(args, f, indent=2)
+
+    # One process for one GPU; fresh children (spawn) joined through a file for more.
+    print('Launching processes...')
+    with tempfile.TemporaryDirectory() as temp_dir:
+        if args.num_gpus == 1:
+            subprocess_fn(rank=0, args=args, temp_dir=temp_dir)
+        else:
+            torch.multiprocessing.spawn(fn=subprocess_fn, args=(args, temp_dir), nprocs=args.num_gpus)
+
+#----------------------------------------------------------------------------
+
+if __name__ == '__main__':
+    main()  # pylint: disable=no-value-for-parameter

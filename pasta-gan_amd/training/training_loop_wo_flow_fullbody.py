@@ -8,19 +8,27 @@ One process per GPU; gradients are all-reduced by RCCL (``backend='nccl'`` on RO
 with backward: by default through one ``FlatGradReducer`` per optimised module (``ddp_mode='flat'``,
 training/grad_reducer.py), or through the reference's five DistributedDataParallel wrappers (``ddp_mode='torch'``).
 
-Snapshots, image grids and metrics of the reference loop are host orchestration outside this path.
+With a ``run_dir``, ``training_loop`` is the reference's whole loop (:247-654): ticks counted in kimg, the status line,
+stats.jsonl, the sample-image grid (training/snapshot_grid.py), network snapshots, resuming and aborting; the statistics
+accumulate on the device (torch_utils/training_stats.py) and none of it touches ``TrainingStep.run``'s arithmetic.  Metrics are
+not evaluated (the reference's call is commented out, :604-614).
 ``SyntheticFullBodyBatch`` supplies tensors of the dataset's shapes (training_loop...:289-297, 425-456)
 directly in HBM; with ``training_set_kwargs``, ``training_loop`` reads the reference's data set
 (training/dataset.py) and prepares each batch on the GPU (training/tryon_batch.py).
 """
 
 import copy
+import json
+import os
+import pickle
+import time
 
 import numpy as np
 import torch
 
 import dnnlib
 from torch_utils import misc
+from torch_utils import training_stats
 from training.grad_reducer import FlatGradReducer, broadcast_module_states
 
 #----------------------------------------------------------------------------
@@ -116,7 +124,8 @@ class TrainingStep:
     """Owns G, D, G_ema, the DDP wrappers, the loss and the four optimiser phases; ``run()`` executes one
     iteration of the reference's hot loop on a device-resident batch."""
 
-    def __init__(self, device, cfg=None, num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, ddp_bucket_mb=None, ddp_mode='flat'):
+    def __init__(self, device, cfg=None, num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, ddp_bucket_mb=None, ddp_mode='flat',
+                 resume_data=None):
         cfg = cfg if cfg is not None else fashion_config(mbstd_group_size=min(batch_gpu, 4))
         assert ddp_mode in ('flat', 'torch')
         self.device, self.num_gpus, self.rank = device, num_gpus, rank
@@ -135,6 +144,9 @@ class TrainingStep:
         self.D = dnnlib.util.construct_class_by_name(**cfg.D_kwargs).train().requires_grad_(False).to(device)
         self.G_ema = copy.deepcopy(self.G).eval()
         self.ema_kimg, self.ema_rampup = cfg.ema_kimg, cfg.ema_rampup
+        if resume_data is not None and rank == 0:      # :280-285, before the replicas take rank 0's state below
+            for name, module in [('G', self.G), ('D', self.D), ('G_ema', self.G_ema)]:
+                misc.copy_params_and_buffers(resume_data[name], module, require_all=False)
 
         # Replicas: rank 0's state everywhere, then a gradient exchange per optimised module.
         #   'flat'  - one FlatGradReducer for G and one for D (64 MiB buckets: G = 3 all-reduces, D = 2), gated by this
@@ -203,6 +215,8 @@ class TrainingStep:
                 opt = dnnlib.util.construct_class_by_name(module.parameters(), **opt_kwargs)
                 self.phases += [dnnlib.EasyDict(name=name + 'main', module=module, opt=opt, interval=1)]
                 self.phases += [dnnlib.EasyDict(name=name + 'reg', module=module, opt=opt, interval=reg_interval)]
+        for phase in self.phases:           # set by whoever wants phase timings (:344-349); recorded in run() when present
+            phase.start_event = phase.end_event = None
         self.batch_idx = 0
         self.cur_nimg = 0
         self._buf_versions = {}         # G buffer index -> version counter at its last copy into G_ema
@@ -218,6 +232,8 @@ class TrainingStep:
             if self.batch_idx % phase.interval != 0:
                 continue
             reducer = self.reducers.get(phase.name[0])
+            if phase.start_event is not None:
+                phase.start_event.record(torch.cuda.current_stream(self.device))
             phase.module.requires_grad_(True)
             if reducer is not None:
                 reducer.begin()
@@ -237,6 +253,8 @@ class TrainingStep:
             if grads:       # nan_to_num(grad, nan=0, posinf=1e5, neginf=-1e5) (:513-515), one launch per 96 gradients
                 misc.nan_to_num_(grads, nan=0, posinf=1e5, neginf=-1e5)
             phase.opt.step()
+            if phase.end_event is not None:
+                phase.end_event.record(torch.cuda.current_stream(self.device))
 
         ema_nimg = self.ema_kimg * 1000
         if self.ema_rampup is not None:
@@ -271,30 +289,212 @@ class TrainingStep:
 
 #----------------------------------------------------------------------------
 
+def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs):
+    """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263)."""
+    from training import dataset as dataset_module
+    from training.tryon_batch import FullBodyBatchBuilder
+    training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
+    sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed)
+    loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
+                                         collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
+    builder = FullBodyBatchBuilder(device)
+    return training_set, builder, (builder.build(raw) for raw in loader)
+
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
-                  training_set_kwargs=None, data_loader_kwargs=None):
-    """Run ``total_iters`` iterations (the reference's loop runs until ``total_kimg``).  Without ``training_set_kwargs`` the data is
+                  training_set_kwargs=None, data_loader_kwargs=None, run_dir=None, total_kimg=25000, kimg_per_tick=4,
+                  image_snapshot_ticks=50, network_snapshot_ticks=50, resume_pkl=None, abort_fn=None, snapshot_gnum=23):
+    """Without ``run_dir``: run ``total_iters`` iterations and write nothing.  Without ``training_set_kwargs`` the data is
     synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
     path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
-    ``training.tryon_batch.FullBodyBatchBuilder``."""
+    ``training.tryon_batch.FullBodyBatchBuilder``.
+    With ``run_dir`` (and a data set): the reference's loop until ``total_kimg`` (``training_run`` below); ``total_iters`` is unused."""
     device = device if device is not None else torch.device('cuda', rank)
+    if run_dir is not None:
+        return training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs,
+                            data_loader_kwargs, total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn,
+                            snapshot_gnum)
     step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
     if training_set_kwargs is None:
         data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
         batches = iter(lambda: data, None)
     else:
-        from training import dataset as dataset_module
-        from training.tryon_batch import FullBodyBatchBuilder
-        training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
-        sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed)
-        loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
-                                             collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
-        builder = FullBodyBatchBuilder(device)
-        batches = (builder.build(raw) for raw in loader)
+        _, _, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs)
     for it in range(total_iters):
         step.run(next(batches))
         if progress_fn is not None:
             progress_fn(it + 1, total_iters)
+    return step
+
+#----------------------------------------------------------------------------
+
+def sample_images(G_ema, grid, grid_z, batch_gpu):
+    """G_ema's try-on images over the grid (:580-583), one ``batch_gpu`` minibatch at a time: a generator of fp32 [n, 3, H, H]."""
+    with torch.no_grad():
+        for i, z in enumerate(grid_z):
+            lo = i * batch_gpu
+            yield G_ema(z=z, **grid.inputs(lo, lo + int(z.shape[0])), noise_mode='const')[1]
+
+def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs, data_loader_kwargs,
+                 total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn, snapshot_gnum):
+    """The reference's training_loop (:247-654) around ``TrainingStep.run``.  Returns the step; on rank 0 it carries the
+    ``snapshot_grid`` and the ``grid_z`` the sample images were drawn with."""
+    import psutil
+    start_time = time.time()
+    if training_set_kwargs is None:
+        raise ValueError('a training run needs training_set_kwargs: the sample grid is made of the data set\'s train_img_vis people')
+    cfg = dnnlib.EasyDict(cfg if cfg is not None else fashion_config(mbstd_group_size=min(batch_gpu, 4)))
+    cfg.loss_kwargs = dnnlib.EasyDict(cfg.loss_kwargs, report_fn=training_stats.report)
+
+    if rank == 0:
+        print('Loading training set...')
+    training_set, builder, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs)
+    if rank == 0:
+        print()
+        print('Num images: ', len(training_set))
+        print('Image shape:', training_set.image_shape)
+        print()
+
+    resume_data = None
+    if resume_pkl is not None and rank == 0:
+        import legacy
+        print(f'Resuming from "{resume_pkl}"')
+        with open(resume_pkl, 'rb') as f:
+            resume_data = legacy.load_network_pkl(f)
+    if rank == 0:
+        print('Constructing networks...')
+    step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed,
+                        resume_data=resume_data)
+    del resume_data
+    G, D, G_ema, augment_pipe = step.G, step.D, step.G_ema, step.augment_pipe
+    if rank == 0:
+        for phase in step.phases:
+            phase.start_event = torch.cuda.Event(enable_timing=True)
+            phase.end_event = torch.cuda.Event(enable_timing=True)
+
+    grid = None
+    if rank == 0:
+        from training.snapshot_grid import SnapshotGrid
+        print('Exporting sample images...')
+        grid = SnapshotGrid.setup(training_set, builder, device, gnum=snapshot_gnum)
+        grid.save_init(run_dir)
+        step.snapshot_grid = grid
+        step.grid_z = torch.randn([grid.cells, G.z_dim], device=device).split(batch_gpu)       # drawn once (:376)
+
+    if rank == 0:
+        print('Initializing logs...')
+    stats_collector = training_stats.Collector(regex='.*')
+    stats_jsonl = None
+    stats_tfevents = None
+    if rank == 0:
+        stats_jsonl = open(os.path.join(run_dir, 'stats.jsonl'), 'w')
+        try:
+            import torch.utils.tensorboard as tensorboard
+            stats_tfevents = tensorboard.SummaryWriter(run_dir)
+        except ImportError as err:
+            print('Skipping tfevents export:', err)
+
+    if rank == 0:
+        print(f'Training for {total_kimg} kimg...')
+        print()
+    total_nimg = total_kimg * 1000
+    cur_tick = 0
+    tick_start_nimg = step.cur_nimg
+    tick_start_time = time.time()
+    maintenance_time = tick_start_time - start_time
+    if progress_fn is not None:
+        progress_fn(0, total_kimg)
+    while True:
+        if step.cur_nimg < total_nimg:          # total_kimg = 0: no iteration at all, one tick of maintenance (a resumed state written back)
+            step.run(next(batches))
+        cur_nimg = step.cur_nimg
+
+        # Perform maintenance tasks once per tick.
+        done = (cur_nimg >= total_nimg)
+        if (not done) and (cur_tick != 0) and (cur_nimg < tick_start_nimg + kimg_per_tick * 1000):
+            continue
+
+        # Print status line, accumulating the same information in stats_collector.
+        tick_end_time = time.time()
+        report0 = training_stats.report0
+        fields = []
+        fields += [f"tick {report0('Progress/tick', cur_tick):<5d}"]
+        fields += [f"kimg {report0('Progress/kimg', cur_nimg / 1e3):<8.1f}"]
+        fields += [f"time {dnnlib.util.format_time(report0('Timing/total_sec', tick_end_time - start_time)):<12s}"]
+        fields += [f"sec/tick {report0('Timing/sec_per_tick', tick_end_time - tick_start_time):<7.1f}"]
+        fields += [f"sec/kimg {report0('Timing/sec_per_kimg', (tick_end_time - tick_start_time) / max(cur_nimg - tick_start_nimg, 1) * 1e3):<7.2f}"]
+        fields += [f"maintenance {report0('Timing/maintenance_sec', maintenance_time):<6.1f}"]
+        fields += [f"cpumem {report0('Resources/cpu_mem_gb', psutil.Process(os.getpid()).memory_info().rss / 2**30):<6.2f}"]
+        fields += [f"gpumem {report0('Resources/peak_gpu_mem_gb', torch.cuda.max_memory_allocated(device) / 2**30):<6.2f}"]
+        torch.cuda.reset_peak_memory_stats(device)
+        fields += [f"augment {report0('Progress/augment', float(augment_pipe.p.cpu()) if augment_pipe is not None else 0):.3f}"]
+        report0('Timing/total_hours', (tick_end_time - start_time) / (60 * 60))
+        report0('Timing/total_days', (tick_end_time - start_time) / (24 * 60 * 60))
+        if rank == 0:
+            print(' '.join(fields))
+
+        # Check for abort.
+        if (not done) and (abort_fn is not None) and abort_fn():
+            done = True
+            if rank == 0:
+                print()
+                print('Aborting...')
+
+        # Save image snapshot.
+        if (rank == 0) and (image_snapshot_ticks is not None) and (done or cur_tick % image_snapshot_ticks == 0):
+            grid.save(sample_images(G_ema, grid, step.grid_z, batch_gpu), os.path.join(run_dir, f'fakes{cur_nimg//1000:06d}_finetune.png'))
+
+        # Save network snapshot.
+        if (network_snapshot_ticks is not None) and (done or cur_tick % network_snapshot_ticks == 0):
+            snapshot_data = dict(training_set_kwargs=dict(training_set_kwargs))
+            for name, module in [('G', G), ('D', D), ('G_ema', G_ema), ('augment_pipe', augment_pipe)]:
+                if module is not None:
+                    if num_gpus > 1:
+                        misc.check_ddp_consistency(module, ignore_regex=r'.*\.w_avg')
+                    module = copy.deepcopy(module).eval().requires_grad_(False).cpu()
+                snapshot_data[name] = module
+                del module      # conserve memory
+            if rank == 0:
+                with open(os.path.join(run_dir, f'network-snapshot-{cur_nimg//1000:06d}.pkl'), 'wb') as f:
+                    pickle.dump(snapshot_data, f)
+            del snapshot_data
+
+        # Collect statistics.
+        for phase in step.phases:
+            value = []
+            if (phase.start_event is not None) and (phase.end_event is not None) and step.batch_idx > 0:
+                phase.end_event.synchronize()
+                value = phase.start_event.elapsed_time(phase.end_event)
+            report0('Timing/' + phase.name, value)
+        stats_collector.update()
+        stats_dict = stats_collector.as_dict()
+
+        # Update logs.
+        timestamp = time.time()
+        if stats_jsonl is not None:
+            stats_jsonl.write(json.dumps(dict(stats_dict, timestamp=timestamp)) + '\n')
+            stats_jsonl.flush()
+        if stats_tfevents is not None:
+            global_step = int(cur_nimg / 1e3)
+            walltime = timestamp - start_time
+            for name, value in stats_dict.items():
+                stats_tfevents.add_scalar(name, value.mean, global_step=global_step, walltime=walltime)
+            stats_tfevents.flush()
+        if progress_fn is not None:
+            progress_fn(cur_nimg // 1000, total_kimg)
+
+        # Update state.
+        cur_tick += 1
+        tick_start_nimg = cur_nimg
+        tick_start_time = time.time()
+        maintenance_time = tick_start_time - tick_end_time
+        if done:
+            break
+
+    if stats_jsonl is not None:
+        stats_jsonl.close()
+    if rank == 0:
+        print()
+        print('Exiting...')
     return step
 
 #----------------------------------------------------------------------------

@@ -122,7 +122,8 @@ class FullBodyBatchBuilder:
             _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, H, W, s))
             _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, s))
             _native.check(lib.pasta_tryon_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), *[P(g) for g in garments], n, H, W, s))
-        norm_img, norm_lower, den_u, den_l, m_invs, hand_masks, _, _ = patch_pipeline.normalize_batch(*garments, keypoints, self.box_factor)
+        norm_img, norm_lower, den_u, den_l, m_invs, hand_masks, norm_mask, norm_mask_lower = patch_pipeline.normalize_batch(
+            *garments, keypoints, self.box_factor)
         norm_img, norm_lower, den_u, den_l = (t.contiguous() for t in (norm_img, norm_lower, den_u, den_l))
         arm = hand_masks.reshape(n, 4, H, H).contiguous()
         ph, pw, cu, cl = norm_img.shape[1], norm_img.shape[2], norm_img.shape[3], norm_lower.shape[3]
@@ -139,5 +140,6 @@ class FullBodyBatchBuilder:
         if keep_stages:
             stages = dict(stick=stick, palm=palm, retain_mask=retain_mask, gt_parsing=gt, upper_img=garments[0], lower_img=garments[1],
                           upper_mask=garments[2], lower_mask=garments[3], norm_img=norm_img, norm_img_lower=norm_lower,
-                          denorm_upper=den_u, denorm_lower=den_l, arm_masks=arm, M_invs=m_invs)
+                          denorm_upper=den_u, denorm_lower=den_l, arm_masks=arm, M_invs=m_invs, norm_clothes_mask=norm_mask.contiguous(),
+                          norm_clothes_mask_lower=norm_mask_lower.contiguous())
         return FullBodyBatch(t, stages)
