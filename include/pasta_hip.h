@@ -680,6 +680,29 @@ int pasta_grid_assemble(const uint8_t* denorm_upper, const uint8_t* denorm_lower
 int pasta_image_grid_tile_u8(const float* images, uint8_t* canvas, int n, int C, int H, int W, int first, int gw, int ox, int oy,
                              int canvas_h, int canvas_w, float lo, float scale, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Statistics of the paired-reconstruction metric (metrics/reconstruction.py; csrc/recon_metrics.hip): G_ema's image of a
+ * person against that person's photograph, and its parsing against the label map.  Only the content columns
+ * c0 .. c0 + W - 1 of the padded square are scored.
+ * ------------------------------------------------------------------------- */
+/* images [N, 3, H, Wt] fp32, each value first turned into the byte pasta_images_to_u8 writes; photos [N, H, W, 3] uint8.
+ * sums [N, 3] int64 = sum |d|, sum d^2 over the H W 3 bytes (exact) and the SSIM window count 3 (H - 10) (W - 10);
+ * ssim [N] fp64 = the sum over those windows of SSIM (Wang et al. 2004) per RGB channel: 11 x 11 Gaussian window of sigma 1.5
+ * normalised to 1, valid positions, weighted population moments, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2,
+ * (2 mx my + C1) (2 sxy + C2) / ((mx^2 + my^2 + C1) (sxx + syy + C2)), evaluated in fp32 on bytes centred at 127.5.  One fp64
+ * partial per workgroup, reduced in a fixed order: two launches on the same input give the same bits.  workspace: device
+ * memory of pasta_recon_image_stats_workspace(N, H, W) bytes (0 for a shape that is refused).  H >= 11 and W >= 11. */
+int64_t pasta_recon_image_stats_workspace(int N, int H, int W);
+int pasta_recon_image_stats(const float* images, const uint8_t* photos, int64_t* sums, double* ssim, void* workspace,
+                            int64_t workspace_bytes, int N, int H, int Wt, int c0, int W, void* stream);
+
+/* logits [N, C, H, Wt] and labels [N, 1, H, Wt] fp32, C <= 32: matrix [C, C] int64 (row = label, column = prediction) is
+ * ADDED to, the caller zeroes it once.  Prediction: the arg-max over the channels, the lowest index on ties; a NaN never wins,
+ * all NaN predicts class 0.  The label is truncated as .long() does; one outside 0 .. C - 1 (or a NaN) skips the pixel, as
+ * ignore_index does in the loss. */
+int pasta_parsing_confusion(const float* logits, const float* labels, int64_t* matrix, int N, int C, int H, int Wt, int c0, int W,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

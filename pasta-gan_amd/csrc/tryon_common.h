@@ -1,6 +1,6 @@
 // Device helpers of the try-on preparation shared by csrc/tryon_inputs.hip (the training set) and csrc/tryon_pairs.hip (the
 // test pairs): separately rounded arithmetic, the restated rleFrPoly fill of a quadrilateral, the palm rule with its box
-// dilations, and torch's x / 127.5 - 1.
+// dilations, torch's x / 127.5 - 1 and test.py's conversion of a generated value to a byte (also csrc/recon_metrics.hip).
 #pragma once
 #include "common.h"
 
@@ -115,6 +115,13 @@ __device__ __forceinline__ void palm_mask_band(const uint8_t* __restrict__ parsi
 __device__ __forceinline__ float to_unit(int v) {           // torch's x / 127.5 - 1 on the GPU: x * (1 / 127.5f) - 1
     const float inv = 1.0f / 127.5f;
     return tr_rounded((float)v * inv) - 1.0f;
+}
+
+// test.py:133-137 on fp32: (x + 1.0) * 127.5 with each operation rounded on its own, clip to [0, 255], truncation.  A NaN
+// becomes 0 (numpy leaves its uint8 conversion undefined).
+__device__ __forceinline__ uint8_t unit_to_u8(float x) {
+    const float v = tr_rounded(x + 1.0f) * 127.5f;
+    return v != v ? 0 : (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
 }
 
 }  // namespace pasta

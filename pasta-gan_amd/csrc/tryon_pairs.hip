@@ -121,8 +121,7 @@ __global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t*
 
 // ---- generated images to uint8 ----
 
-// test.py:133-137 on fp32: (x + 1.0) * 127.5 with each operation rounded on its own, clip to [0, 255], truncation.  A NaN
-// becomes 0 (numpy leaves its uint8 conversion undefined).
+// test.py:133-137 on fp32, per value csrc/tryon_common.h's unit_to_u8.
 __global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int H, int Wt, int c0,
                                                            int W) {
     const int n = blockIdx.y;
@@ -130,10 +129,7 @@ __global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restri
     if (pix >= H * W) return;
     const int y = pix / W, x = pix - y * W;
     uint8_t* o = dst + ((int64_t)n * H * W + pix) * 3;
-    for (int ch = 0; ch < 3; ch++) {
-        const float v = tr_rounded(src[(((int64_t)n * 3 + ch) * H + y) * Wt + c0 + x] + 1.0f) * 127.5f;
-        o[ch] = v != v ? 0 : (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
-    }
+    for (int ch = 0; ch < 3; ch++) o[ch] = unit_to_u8(src[(((int64_t)n * 3 + ch) * H + y) * Wt + c0 + x]);
 }
 
 }  // namespace pasta

@@ -31,8 +31,9 @@ CFG_SPECS = {
     'fashion':   dict(ref_gpus=8,  kimg=8000,  mb=32, mbstd=4,  fmaps=0.5, lrate=0.002, gamma=10, ema=10, ramp=None, map=1),
 }
 UNSUPPORTED_CFGS = ('paper256', 'paper512', 'paper1024', 'cifar')
+SUPPORTED_METRICS = ('recon_full', 'recon2k')       # metrics/metric_main.py; the reference's detector metrics are refused
 
-def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
+def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False):
@@ -48,9 +49,13 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, seed=None, da
     if snap < 1:
         raise UserError('--snap must be at least 1')
     args.image_snapshot_ticks = args.network_snapshot_ticks = snap
-    if metrics:
+    metrics = list(metrics) if metrics else []
+    refused = [m for m in metrics if m not in SUPPORTED_METRICS]
+    if refused:
         raise UserError('--metrics must be none: metrics are not evaluated (the reference loop has its metric call commented out, and '
-                        'this package has no metrics/ with the Inception and VGG weights it needs)')
+                        'this package has no metrics/ with the Inception and VGG weights it needs); refused: ' + ', '.join(refused) +
+                        ' (evaluated without those weights: ' + ', '.join(SUPPORTED_METRICS) + ')')
+    args.metrics = metrics
     args.random_seed = 0 if seed is None else seed
 
     # Dataset: data, cond, subset, mirror (:115-155)
@@ -66,6 +71,20 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, seed=None, da
         del training_set
     except IOError as err:
         raise UserError(f'--data: {err}')
+    # --metrics_data: a held-out tree of the same layout for the metrics (own option; default: the training tree)
+    args.metric_set_kwargs = None
+    if metrics_data is not None:
+        if not metrics:
+            raise UserError('--metrics_data needs --metrics')
+        args.metric_set_kwargs = dnnlib.EasyDict(class_name='training.dataset.UvitonDatasetFull', path=metrics_data, use_labels=False,
+                                                 max_size=None, xflip=False)
+        try:
+            metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
+            if metric_set.resolution != args.training_set_kwargs.resolution:
+                raise UserError(f'--metrics_data: resolution {metric_set.resolution}, the training data has {args.training_set_kwargs.resolution}')
+            del metric_set
+        except IOError as err:
+            raise UserError(f'--metrics_data: {err}')
     if cond:
         raise UserError('--cond=true is not supported: the try-on data set has no labels (the generator is conditioned on the garment patches)')
     if subset is not None:
@@ -215,7 +234,8 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--outdir', help='Where to save the results', required=True, metavar='DIR')
 @click.option('--gpus', help='Number of GPUs to use [default: 1]', type=int, metavar='INT')
 @click.option('--snap', help='Snapshot interval [default: 50 ticks]', type=int, metavar='INT')
-@click.option('--metrics', help='"none" [default: none]; metrics are not evaluated', type=CommaSeparatedList())
+@click.option('--metrics', help='Comma-separated list of recon_full, recon2k, or "none" [default: none]', type=CommaSeparatedList())
+@click.option('--metrics_data', help='Tree the metrics are evaluated on [default: the training data]', metavar='PATH')
 @click.option('--seed', help='Random seed [default: 0]', type=int, metavar='INT')
 @click.option('-n', '--dry-run', help='Print training options and exit', is_flag=True)
 # Dataset.

@@ -10,8 +10,8 @@ training/grad_reducer.py), or through the reference's five DistributedDataParall
 
 With a ``run_dir``, ``training_loop`` is the reference's whole loop (:247-654): ticks counted in kimg, the status line,
 stats.jsonl, the sample-image grid (training/snapshot_grid.py), network snapshots, resuming and aborting; the statistics
-accumulate on the device (torch_utils/training_stats.py) and none of it touches ``TrainingStep.run``'s arithmetic.  Metrics are
-not evaluated (the reference's call is commented out, :604-614).
+accumulate on the device (torch_utils/training_stats.py) and none of it touches ``TrainingStep.run``'s arithmetic.  With
+``metrics``, every network snapshot is scored on all ranks (metrics/; the reference has this call commented out, :604-614).
 ``SyntheticFullBodyBatch`` supplies tensors of the dataset's shapes (training_loop...:289-297, 425-456)
 directly in HBM; with ``training_set_kwargs``, ``training_loop`` reads the reference's data set
 (training/dataset.py) and prepares each batch on the GPU (training/tryon_batch.py).
@@ -302,17 +302,20 @@ def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_
 
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
                   training_set_kwargs=None, data_loader_kwargs=None, run_dir=None, total_kimg=25000, kimg_per_tick=4,
-                  image_snapshot_ticks=50, network_snapshot_ticks=50, resume_pkl=None, abort_fn=None, snapshot_gnum=23):
+                  image_snapshot_ticks=50, network_snapshot_ticks=50, resume_pkl=None, abort_fn=None, snapshot_gnum=23, metrics=None,
+                  metric_set_kwargs=None):
     """Without ``run_dir``: run ``total_iters`` iterations and write nothing.  Without ``training_set_kwargs`` the data is
     synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
     path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
     ``training.tryon_batch.FullBodyBatchBuilder``.
-    With ``run_dir`` (and a data set): the reference's loop until ``total_kimg`` (``training_run`` below); ``total_iters`` is unused."""
+    With ``run_dir`` (and a data set): the reference's loop until ``total_kimg`` (``training_run`` below); ``total_iters`` is unused.
+    ``metrics`` (names of metrics/metric_main.py) are evaluated on G_ema after every network snapshot, on ``metric_set_kwargs``
+    (default: the training set's)."""
     device = device if device is not None else torch.device('cuda', rank)
     if run_dir is not None:
         return training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs,
                             data_loader_kwargs, total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn,
-                            snapshot_gnum)
+                            snapshot_gnum, metrics, metric_set_kwargs)
     step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
     if training_set_kwargs is None:
         data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
@@ -335,7 +338,8 @@ def sample_images(G_ema, grid, grid_z, batch_gpu):
             yield G_ema(z=z, **grid.inputs(lo, lo + int(z.shape[0])), noise_mode='const')[1]
 
 def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs, data_loader_kwargs,
-                 total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn, snapshot_gnum):
+                 total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn, snapshot_gnum, metrics=None,
+                 metric_set_kwargs=None):
     """The reference's training_loop (:247-654) around ``TrainingStep.run``.  Returns the step; on rank 0 it carries the
     ``snapshot_grid`` and the ``grid_z`` the sample images were drawn with."""
     import psutil
@@ -383,6 +387,7 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
     if rank == 0:
         print('Initializing logs...')
     stats_collector = training_stats.Collector(regex='.*')
+    stats_metrics = dict()
     stats_jsonl = None
     stats_tfevents = None
     if rank == 0:
@@ -444,6 +449,7 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
             grid.save(sample_images(G_ema, grid, step.grid_z, batch_gpu), os.path.join(run_dir, f'fakes{cur_nimg//1000:06d}_finetune.png'))
 
         # Save network snapshot.
+        snapshot_pkl = None
         if (network_snapshot_ticks is not None) and (done or cur_tick % network_snapshot_ticks == 0):
             snapshot_data = dict(training_set_kwargs=dict(training_set_kwargs))
             for name, module in [('G', G), ('D', D), ('G_ema', G_ema), ('augment_pipe', augment_pipe)]:
@@ -453,10 +459,23 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
                     module = copy.deepcopy(module).eval().requires_grad_(False).cpu()
                 snapshot_data[name] = module
                 del module      # conserve memory
+            snapshot_pkl = os.path.join(run_dir, f'network-snapshot-{cur_nimg//1000:06d}.pkl')
             if rank == 0:
-                with open(os.path.join(run_dir, f'network-snapshot-{cur_nimg//1000:06d}.pkl'), 'wb') as f:
+                with open(snapshot_pkl, 'wb') as f:
                     pickle.dump(snapshot_data, f)
             del snapshot_data
+
+        # Evaluate metrics (:604-614): every rank computes, rank 0 reports.
+        if (snapshot_pkl is not None) and metrics:
+            from metrics import metric_main
+            if rank == 0:
+                print('Evaluating metrics...')
+            for metric in metrics:
+                result_dict = metric_main.calc_metric(metric=metric, G=G_ema, num_gpus=num_gpus, rank=rank, device=device,
+                                                      dataset_kwargs=metric_set_kwargs if metric_set_kwargs is not None else training_set_kwargs)
+                if rank == 0:
+                    metric_main.report_metric(result_dict, run_dir=run_dir, snapshot_pkl=snapshot_pkl)
+                stats_metrics.update(result_dict.results)
 
         # Collect statistics.
         for phase in step.phases:
@@ -478,6 +497,8 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
             walltime = timestamp - start_time
             for name, value in stats_dict.items():
                 stats_tfevents.add_scalar(name, value.mean, global_step=global_step, walltime=walltime)
+            for name, value in stats_metrics.items():
+                stats_tfevents.add_scalar(f'Metrics/{name}', value, global_step=global_step, walltime=walltime)
             stats_tfevents.flush()
         if progress_fn is not None:
             progress_fn(cur_nimg // 1000, total_kimg)

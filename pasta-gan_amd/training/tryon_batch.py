@@ -76,14 +76,16 @@ def palm_quads(keypoints, left_padding):
 
 class FullBodyBatch:
     """The interface TrainingStep.run consumes (as SyntheticFullBodyBatch): ``tensors`` (the nine KEYS), ``batch``, ``split``.
-    ``stages`` holds the uint8 intermediates when the builder was asked to keep them."""
+    ``stages`` holds the uint8 intermediates when the builder was asked to keep them; ``image`` is the photographs' uint8 batch
+    [N, H, W, 3] as the builder uploaded it (the reconstruction metric scores against it)."""
     KEYS = ['real_img', 'style_input', 'retain', 'pose', 'denorm_upper_input', 'denorm_lower_input',
             'denorm_upper_mask', 'denorm_lower_mask', 'gt_parsing']
 
-    def __init__(self, tensors, stages=None):
+    def __init__(self, tensors, stages=None, image=None):
         self.tensors = tensors
         self.batch = int(tensors['real_img'].shape[0])
         self.stages = stages
+        self.image = image
 
     def split(self, batch_gpu):
         parts = {k: v.split(batch_gpu) for k, v in self.tensors.items()}
@@ -142,4 +144,4 @@ class FullBodyBatchBuilder:
                           upper_mask=garments[2], lower_mask=garments[3], norm_img=norm_img, norm_img_lower=norm_lower,
                           denorm_upper=den_u, denorm_lower=den_l, arm_masks=arm, M_invs=m_invs, norm_clothes_mask=norm_mask.contiguous(),
                           norm_clothes_mask_lower=norm_mask_lower.contiguous())
-        return FullBodyBatch(t, stages)
+        return FullBodyBatch(t, stages, image)
