@@ -696,6 +696,23 @@ int64_t pasta_recon_image_stats_workspace(int N, int H, int W);
 int pasta_recon_image_stats(const float* images, const uint8_t* photos, int64_t* sums, double* ssim, void* workspace,
                             int64_t workspace_bytes, int N, int H, int Wt, int c0, int W, void* stream);
 
+/* pasta_recon_image_stats restricted to a region (metrics/tryon_fidelity.py scores what an unpaired try-on must keep: the body
+ * parts that come in through `retain` against the photograph, the warped garment patches against themselves).  images
+ * [N, 3, H, Wt] fp32 as above, content columns c0 .. c0 + W - 1; ref [N, H, Wr, 3] uint8, content columns from r0 (a photograph:
+ * Wr = W, r0 = 0; a padded stage: Wr = H, r0 = c0); mask [N, H, Wm] uint8, content columns from m0, nonzero = the pixel is in the
+ * region.  sums [N, 4] int64 = sum |d| and sum d^2 over the three bytes of every region pixel (exact), the SSIM windows -- one
+ * per RGB channel and valid 11 x 11 position whose 121 pixels are ALL in the region -- and the bytes, 3 x region pixels;
+ * ssim [N] fp64 = the sum of SSIM over those windows, the same Gaussian, constants, centring and fp32 evaluation.  Same tiles,
+ * same device code and same summation order as pasta_recon_image_stats: with a mask of ones and ref a photograph, sums[:, :3]
+ * and ssim are that entry's bit for bit.  An empty region gives four zeros and 0.0; nothing is divided by a count on the
+ * device.  One partial per workgroup and a fixed-order second launch: two calls on the same input give the same bits.
+ * workspace: pasta_region_image_stats_workspace(N, H, W) bytes (0 for a shape that is refused).  H >= 11, W >= 11, and every
+ * column range inside its tensor: anything else is refused before a launch. */
+int64_t pasta_region_image_stats_workspace(int N, int H, int W);
+int pasta_region_image_stats(const float* images, const uint8_t* ref, const uint8_t* mask, int64_t* sums, double* ssim,
+                             void* workspace, int64_t workspace_bytes, int N, int H, int Wt, int c0, int Wr, int r0, int Wm, int m0,
+                             int W, void* stream);
+
 /* logits [N, C, H, Wt] and labels [N, 1, H, Wt] fp32, C <= 32: matrix [C, C] int64 (row = label, column = prediction) is
  * ADDED to, the caller zeroes it once.  Prediction: the arg-max over the channels, the lowest index on ties; a NaN never wins,
  * all NaN predicts class 0.  The label is truncated as .long() does; one outside 0 .. C - 1 (or a NaN) skips the pixel, as

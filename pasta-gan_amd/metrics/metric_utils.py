@@ -1,5 +1,5 @@
 """What every metric is handed (``MetricOptions``, as the reference's metrics/metric_utils.py:25-41 without its detector cache),
-a progress printer, and the two statistics kernels of csrc/recon_metrics.hip."""
+a progress printer, and the statistics kernels of csrc/recon_metrics.hip."""
 
 import copy
 import time
@@ -62,6 +62,29 @@ def recon_image_stats(images, photos, c0):
     with torch.cuda.device(images.device):
         _native.check(lib.pasta_recon_image_stats(_native.ptr(images), _native.ptr(photos), _native.ptr(sums), _native.ptr(ssim),
                                                   _native.ptr(work), nbytes, n, h, wt, int(c0), w, _native.stream()))
+    return sums, ssim
+
+def region_image_stats(images, ref, mask, c0, r0, m0, W):
+    """images fp32 [N, 3, H, Wt] against ref uint8 [N, H, Wr, 3] inside the region mask uint8 [N, H, Wm] != 0, over W columns that
+    start at c0, r0 and m0 of the three tensors (pasta_region_image_stats): (sums int64 [N, 4] = sum |d|, sum d^2, SSIM windows
+    wholly inside the region, bytes; ssim fp64 [N] = the sum of SSIM over those windows)."""
+    _native.require_gpu(images, 'region_image_stats')
+    assert images.dtype == torch.float32 and images.ndim == 4 and images.shape[1] == 3
+    assert ref.dtype == torch.uint8 and ref.ndim == 4 and ref.shape[3] == 3 and ref.device == images.device
+    assert mask.dtype == torch.uint8 and mask.ndim == 3 and mask.device == images.device
+    images, ref, mask = images.contiguous(), ref.contiguous(), mask.contiguous()
+    n, _, h, wt = images.shape
+    assert tuple(ref.shape[:2]) == (n, h) and tuple(mask.shape[:2]) == (n, h)
+    w = int(W)
+    lib = _native.lib()
+    nbytes = int(lib.pasta_region_image_stats_workspace(n, h, w))
+    work = torch.empty([max(nbytes, 8)], dtype=torch.uint8, device=images.device)
+    sums = torch.empty([n, 4], dtype=torch.int64, device=images.device)
+    ssim = torch.empty([n], dtype=torch.float64, device=images.device)
+    with torch.cuda.device(images.device):
+        _native.check(lib.pasta_region_image_stats(_native.ptr(images), _native.ptr(ref), _native.ptr(mask), _native.ptr(sums),
+                                                   _native.ptr(ssim), _native.ptr(work), nbytes, n, h, wt, int(c0), int(ref.shape[2]), int(r0),
+                                                   int(mask.shape[2]), int(m0), w, _native.stream()))
     return sums, ssim
 
 def parsing_confusion(logits, labels, c0, width, out=None):

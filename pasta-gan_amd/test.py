@@ -15,8 +15,12 @@ Differences from the reference, on purpose:
   --network must name a local file: URLs are refused (nothing is downloaded).
   --workers sets the loader's processes (the reference: 4).
   --seeds, --class and --projected-w are accepted and unused, as in the reference.
+  --scores FILE scores every image by region against what the generator was told to reproduce (metrics/tryon_fidelity.py: kept
+  body parts against the photograph, garment patches against themselves; L1, PSNR, SSIM) and writes one JSON object.  These are
+  this project's own figures; the reference has none for test.py.
 """
 
+import json
 import os
 import re
 from typing import List, Optional
@@ -52,8 +56,11 @@ def _local_snapshot(path):
 @click.option('--dataroot', help='Root of the test data set', type=str, required=True)
 @click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=16, show_default=True)
 @click.option('--workers', help='Loader processes (file decoding only)', type=click.IntRange(min=0), default=4, show_default=True)
+@click.option('--scores', 'scores_file', help='Score the written images by region (kept body parts, upper and lower garment patches: L1, PSNR, '
+              'SSIM) and write the results to FILE as JSON. With this option z of pair i is np.random.RandomState(i).randn(z_dim), so that '
+              'the figures describe the images whatever the batch size [default: no scores]', type=str, metavar='FILE')
 def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi: float, class_idx: Optional[int], noise_mode: str,
-                    projected_w: Optional[str], outdir: str, dataroot: str, batchsize: int, workers: int):
+                    projected_w: Optional[str], outdir: str, dataroot: str, batchsize: int, workers: int, scores_file: Optional[str]):
     """Generate unpaired try-on images from the test pairs with a trained snapshot.
 
     \b
@@ -81,12 +88,19 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
                                          collate_fn=custom_dataset.collate_pairs)
     print(len(dataset))
     builder = TryOnPairBatchBuilder(device)
+    if scores_file is not None:
+        from metrics import tryon_fidelity
+        partials = tryon_fidelity.new_partials(len(dataset), device)
+        pixels = tryon_fidelity.PIXELS                              # content pixels of a pair; every batch brings its own
     written = 0
     for raw in loader:
-        batch = builder.build(raw)
+        batch = builder.build(raw, keep_stages=scores_file is not None)
         t, n = batch.tensors, batch.batch
         height, width = raw['image'].shape[1], raw['image'].shape[2]
         gen_z = torch.empty([n, 0], device=device)
+        if scores_file is not None:
+            pair_index = raw['raw_idx'].tolist()                    # the pairs' positions in the pair lists
+            gen_z = tryon_fidelity.pair_z(pair_index, G.z_dim, device)
         with torch.no_grad():
             gen_c, cat_feat_list = G.style_encoding(t['style_input'], t['retain'])
             pose_feat = G.const_encoding(t['pose'])
@@ -95,6 +109,9 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
             _, gen_imgs, _, _ = G.synthesis(ws, pose_feat, cat_feats, t['denorm_upper_input'], t['denorm_lower_input'], t['denorm_upper_mask'],
                                             t['denorm_lower_mask'], noise_mode=noise_mode)
         images = images_to_u8(gen_imgs, (height - width) // 2, width).cpu().numpy()
+        if scores_file is not None:
+            tryon_fidelity.score_batch(gen_imgs, batch, pair_index, partials)
+            pixels = height * width
         for img, person, clothes in zip(images, batch.person_name, batch.clothes_name):
             save_dir = os.path.join(outdir, person.split('/')[0])
             os.makedirs(save_dir, exist_ok=True)
@@ -102,6 +119,13 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
             PIL.Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(save_dir, name))
             written += 1
     print('finish: %d images under %s' % (written, outdir))
+    if scores_file is not None:
+        results = tryon_fidelity.finish(partials, 'tryon', pixels=pixels)
+        line = json.dumps(dict(results=results, pairs=written, network=network_pkl, dataroot=dataroot, noise_mode=noise_mode))
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
+        with open(scores_file, 'w') as f:
+            f.write(line + '\n')
 
 
 if __name__ == '__main__':

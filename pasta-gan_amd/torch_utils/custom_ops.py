@@ -235,6 +235,8 @@ ABI = {
     'pasta_recon_image_stats_workspace': (_c_i64, [ctypes.c_int] * 3),
     'pasta_recon_image_stats': (ctypes.c_int, [_c_ptr] * 5 + [_c_i64] + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_parsing_confusion': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 6 + [_c_ptr]),
+    'pasta_region_image_stats_workspace': (_c_i64, [ctypes.c_int] * 3),
+    'pasta_region_image_stats': (ctypes.c_int, [_c_ptr] * 6 + [_c_i64] + [ctypes.c_int] * 9 + [_c_ptr]),
 }
 
 # Entries added to ABI 21 after its first release (purely additive, so the version did not move): a library built before them
@@ -245,7 +247,8 @@ LATE_ENTRIES = frozenset(['pasta_grid_sample', 'pasta_grid_sample_backward_works
                           'pasta_tryon_pair_assemble', 'pasta_images_to_u8', 'pasta_pose_stickman_thick_u8',
                           'pasta_palm_mask_square_u8', 'pasta_tryon_region_masks_u8', 'pasta_tryon_region_assemble',
                           'pasta_grid_composite_eroded_u8', 'pasta_grid_assemble', 'pasta_image_grid_tile_u8',
-                          'pasta_recon_image_stats_workspace', 'pasta_recon_image_stats', 'pasta_parsing_confusion'])
+                          'pasta_recon_image_stats_workspace', 'pasta_recon_image_stats', 'pasta_parsing_confusion',
+                          'pasta_region_image_stats_workspace', 'pasta_region_image_stats'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

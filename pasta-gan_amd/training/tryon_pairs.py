@@ -27,7 +27,8 @@ PALM_BOXES = (25, 15)       # get_hand_mask of the test set: upper arm 25 x 25, 
 
 class TryOnPairBatch:
     """``tensors``: the seven inputs of test.py's generator calls (KEYS); ``person_name`` / ``clothes_name``: the data set's
-    relative paths; ``stages``: the uint8 intermediates when the builder was asked to keep them."""
+    relative paths; ``stages``: the uint8 intermediates (and the person's unpadded ``image`` and ``parsing``, which
+    metrics.tryon_fidelity scores against) when the builder was asked to keep them."""
     KEYS = ['retain', 'pose', 'style_input', 'denorm_upper_input', 'denorm_lower_input', 'denorm_upper_mask', 'denorm_lower_mask']
 
     def __init__(self, tensors, person_name, clothes_name, stages=None):
@@ -85,7 +86,7 @@ class TryOnPairBatchBuilder:
                                                         parts, ph, pw, _native.stream()))
         stages = None
         if keep_stages:
-            stages = dict(stick=stick, clothes_stick=d_stick, palm=palm, retain_img=retain_img, lower_img=lower_img, lower_mask=lower_mask,
+            stages = dict(image=image, parsing=parsing, stick=stick, clothes_stick=d_stick, palm=palm, retain_img=retain_img, lower_img=lower_img, lower_mask=lower_mask,
                           upper_img=upper_img, upper_mask=upper_mask, patches=patches, stick_patches=stick_patches, mask_patches=mask_patches,
                           denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, upper_valid=valid_u, lower_valid=valid_l)
         return TryOnPairBatch(t, raw['person_name'], raw['clothes_name'], stages)

@@ -1,4 +1,4 @@
-"""Timings of the reconstruction metric's two kernels on one GPU ("Scoring snapshots"):
+"""Timings of the reconstruction metric's kernels and of the try-on region statistics on one GPU (sections 8c and 8d):
 
     python tools/bench_recon_metrics.py --prepare DIR [--people 256]     # a tree of --people persons and DIR/snapshot.pkl
     python tools/bench_recon_metrics.py [--batch 16] [--iters 200]       # the kernels, a stock-torch yardstick, G_ema's forward
@@ -33,14 +33,19 @@ def prepare(root, people):
     print('wrote', os.path.join(root, 'snapshot.pkl'), 'and a tree of', people, 'people')
 
 
-def torch_image_stats(images, photos, c0, window):
-    """pasta_recon_image_stats from stock torch ops: (sums [N, 2], ssim sums [N])."""
+def torch_image_stats(images, photos, c0, window, mask=None):
+    """pasta_recon_image_stats from stock torch ops: (sums [N, 2], ssim sums [N]); with ``mask`` (uint8 [N, H, W])
+    pasta_region_image_stats: the differences of the region's pixels, SSIM over the windows wholly inside it (a min-pool)."""
     import torch
     n, h, w, _ = photos.shape
     v = (images[..., c0:c0 + w] + 1.0) * 127.5
     x = torch.where(v != v, torch.zeros_like(v), v.clamp(0, 255)).floor()
     y = photos.permute(0, 3, 1, 2).to(torch.float32)
     d = x - y
+    if mask is not None:
+        m = (mask != 0).to(torch.float32).unsqueeze(1)
+        d = d * m
+        inside = -torch.nn.functional.max_pool2d(-m, 11, stride=1)
     sums = torch.stack([d.abs().sum(dim=(1, 2, 3), dtype=torch.float64), (d * d).sum(dim=(1, 2, 3), dtype=torch.float64)], dim=1)
     a, b = x - 127.5, y - 127.5
     maps = torch.stack([a, b, a * a, b * b, a * b], dim=1).reshape(n * 15, 1, h, w)
@@ -49,6 +54,8 @@ def torch_image_stats(images, photos, c0, window):
     sxx, syy, sxy = e[:, 2] - e[:, 0] * e[:, 0], e[:, 3] - e[:, 1] * e[:, 1], e[:, 4] - e[:, 0] * e[:, 1]
     c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
     ssim = (2 * mx * my + c1) * (2 * sxy + c2) / ((mx * mx + my * my + c1) * (sxx + syy + c2))
+    if mask is not None:
+        ssim = ssim * inside
     return sums, ssim.sum(dim=(1, 2, 3), dtype=torch.float64)
 
 
@@ -100,6 +107,14 @@ def main():
     assert torch.equal(hip_sums[:, :2].double(), ref_sums), 'the yardstick computes other sums'
     print('largest |mean SSIM (HIP) - mean SSIM (torch, fp32)|: %.3e' % float(((hip_ssim - ref_ssim) / hip_sums[:, 2]).abs().max()))
 
+    # the region kernel on a blocky mask (8 x 8 blocks, three in four inside), against the same torch ops with a mask
+    mask = (torch.rand([n, H // 8, W // 8], generator=gen) < 0.75).to(torch.uint8).repeat_interleave(8, 1).repeat_interleave(8, 2).contiguous().to(device)
+    reg_sums, reg_ssim = metric_utils.region_image_stats(images, photos, mask, c0, 0, 0, W)
+    ref_sums, ref_ssim_m = torch_image_stats(images, photos, c0, window, mask)
+    assert torch.equal(reg_sums[:, :2].double(), ref_sums) and int(reg_sums[:, 2].min()) > 0, 'the masked yardstick computes other sums'
+    print('the same under a mask (%.0f %% of the windows count): %.3e' % (100.0 * float(reg_sums[:, 2].sum()) / float(hip_sums[:, 2].sum()),
+          float(((reg_ssim - ref_ssim_m) / reg_sums[:, 2]).abs().max())))
+
     # the same call on inputs that cannot stay in the 256 MiB Infinity Cache: 24 copies (360 MB) taken in turn
     copies = [(images.clone(), photos.clone()) for _ in range(24)]
     turn = [0]
@@ -113,6 +128,9 @@ def main():
              images.numel() * 4 + photos.numel()),
             ('  the same, inputs rotating through 360 MB', rotating, images.numel() * 4 + photos.numel()),
             ('the same statistics from stock torch ops', lambda: torch_image_stats(images, photos, c0, window), None),
+            ('pasta_region_image_stats (+ its reduce launch)', lambda: metric_utils.region_image_stats(images, photos, mask, c0, 0, 0, W),
+             images.numel() * 4 + photos.numel() + mask.numel()),
+            ('the region statistics from stock torch ops', lambda: torch_image_stats(images, photos, c0, window, mask), None),
             ('pasta_parsing_confusion', lambda: metric_utils.parsing_confusion(logits, labels, c0, W, out=conf), (logits.numel() + labels.numel()) * 4)]
     for name, fn, nbytes in rows:
         med, lo, hi = timed(fn, opt.iters)
