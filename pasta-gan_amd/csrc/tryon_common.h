@@ -1,6 +1,7 @@
-// Device helpers of the try-on preparation shared by csrc/tryon_inputs.hip (the training set) and csrc/tryon_pairs.hip (the
-// test pairs): separately rounded arithmetic, the restated rleFrPoly fill of a quadrilateral, the palm rule with its box
-// dilations, torch's x / 127.5 - 1 and test.py's conversion of a generated value to a byte (also csrc/recon_metrics.hip).
+// Device helpers of the try-on preparation shared by csrc/tryon_inputs.hip (the training set) and csrc/tryon_pairs.hip (both sets
+// of test pairs): separately rounded arithmetic, the restated rleFrPoly fill of a quadrilateral, the palm rule with its box
+// dilations, torch's x / 127.5 - 1 and test.py's conversion of a generated value to a byte (also csrc/recon_metrics.hip), the
+// pixel of a padded square, the per-pixel body of the three assemble kernels and the copy of an entry's output-pointer array.
 #pragma once
 #include "common.h"
 
@@ -122,6 +123,55 @@ __device__ __forceinline__ float to_unit(int v) {           // torch's x / 127.5
 __device__ __forceinline__ uint8_t unit_to_u8(float x) {
     const float v = tr_rounded(x + 1.0f) * 127.5f;
     return v != v ? 0 : (uint8_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
+}
+
+// ---- the padded square and the tensors G takes ----
+
+// Pixel `pix` of sample n's padded H x H square, whose W-wide image has lp columns of padding to its left: row y and column c
+// of the unpadded image, whether the pixel lies inside it, and the index of its pixel (n, y, c) there.
+struct SquarePixel { int y, c; bool inside; int64_t src; };
+__device__ __forceinline__ SquarePixel square_pixel(int n, int pix, int H, int W, int lp) {
+    const int y = pix / H, c = pix - y * H - lp;
+    return {y, c, c >= 0 && c < W, (int64_t)n * H * W + (int64_t)y * W + c};
+}
+
+// Every fp32 tensor an assemble entry may write; an entry sets those of its KEYS and leaves the others null.
+struct TryonOut {
+    float *image, *clothes, *gt_parsing, *style_input, *retain, *pose, *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask,
+          *denorm_lower_mask;
+};
+
+// outputs[i] -> *fields[i] for the `count` tensors of an entry; the index of the first null output, -1 when there is none.
+inline int take_outputs(float* const* outputs, float** const* fields, int count) {
+    for (int i = 0; i < count; i++) {
+        if (!outputs[i]) return i;
+        *fields[i] = outputs[i];
+    }
+    return -1;
+}
+
+// Pixel `pix` of sample n of what every data set gives G: `ret` (the caller's retain value per channel) into retain and
+// pose[3..5], the stick figure into pose[0..2], the two denormalised inputs (times keep, 0 or 1) and their masks.  stick, den_u
+// and den_l point at the pixel's three bytes.  numpy sums uint8 in a wider type, so the masks' channel sums do not wrap.
+__device__ __forceinline__ void tryon_pixel(const TryonOut& o, int n, int pix, int HH, const float* ret, const uint8_t* __restrict__ stick,
+                                            const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l, int keep) {
+    const int64_t p = (int64_t)n * HH + pix;
+    int s[3], u[3], l[3], su = 0, sl = 0;
+    for (int ch = 0; ch < 3; ch++) {           // every load before the first store
+        s[ch] = stick[ch];
+        u[ch] = den_u[ch] * keep; l[ch] = den_l[ch] * keep;
+        su += u[ch]; sl += l[ch];
+    }
+    for (int ch = 0; ch < 3; ch++) {
+        const int64_t oc = ((int64_t)n * 3 + ch) * HH + pix;
+        o.retain[oc] = ret[ch];
+        o.pose[((int64_t)n * 6 + ch) * HH + pix] = to_unit(s[ch]);
+        o.pose[((int64_t)n * 6 + 3 + ch) * HH + pix] = ret[ch];
+        o.denorm_upper_input[oc] = to_unit(u[ch]);
+        o.denorm_lower_input[oc] = to_unit(l[ch]);
+    }
+    o.denorm_upper_mask[p] = su > 0 ? 1.f : 0.f;
+    o.denorm_lower_mask[p] = sl > 0 ? 1.f : 0.f;
 }
 
 }  // namespace pasta

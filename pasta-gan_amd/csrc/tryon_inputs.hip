@@ -5,7 +5,8 @@
 //   pasta_palm_mask_u8      the palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702): boxes 25 and 16 of
 //                           csrc/tryon_pairs.hip's kernel;
 //   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556);
-//   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456).
+//   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456); its
+//                           per-pixel body is csrc/tryon_common.h's tryon_pixel, shared with the test pairs' kernel.
 // Every entry does a whole batch in one launch.  The reference does this on the host with OpenCV, pycocotools and skimage.
 // What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
 // DESIGN.md section 9): cv2.line(thickness=2), pycocotools' rleFrPoly and cv2.resize(INTER_LINEAR) on uint8.
@@ -40,9 +41,10 @@ __global__ __launch_bounds__(256) void pose_stickman_kernel(const int32_t* __res
     const int n = blockIdx.y;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= H * H) return;
-    const int y = pix / H, c = pix - y * H - lp;         // c: column of the unpadded canvas
+    const SquarePixel s = square_pixel(n, pix, H, W, lp);
+    const int y = s.y, c = s.c;                          // c: column of the unpadded canvas
     int color = -1;
-    if (c >= 0 && c < W) {
+    if (s.inside) {
         const int32_t* lb = limbs + (int64_t)n * TRYON_LIMBS * 5;
         for (int i = 0; i < TRYON_LIMBS; i++, lb += 5)
             if (lb[4] && capsule_hit(c, y, lb[0], lb[1], lb[2], lb[3], t2)) color = i;
@@ -68,10 +70,8 @@ __global__ __launch_bounds__(256) void tryon_masks_kernel(const uint8_t* __restr
     const int n = blockIdx.y;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= H * H) return;
-    const int y = pix / H, c = pix - y * H - lp;
-    const bool inside = c >= 0 && c < W;
-    const int64_t src = (int64_t)n * H * W + (int64_t)y * W + c;
-    const int L = inside ? parsing[src] : 0;
+    const SquarePixel s = square_pixel(n, pix, H, W, lp);
+    const int L = s.inside ? parsing[s.src] : 0;
     const int64_t o = (int64_t)n * H * H + pix;
     const int shoes = L == 18 || L == 19, head = L == 1 || L == 2 || L == 4 || L == 13;
     const int up = L == 5 || L == 6 || L == 7, low = L == 9 || L == 12;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void tryon_masks_kernel(const uint8_t* __restr
     retain[o] = (uint8_t)(shoes + palm[o] + head);
     gt[o] = (uint8_t)(up + low * 2 + hands * 3 + legs * 4 + neck * 5);
     for (int ch = 0; ch < 3; ch++) {
-        const int v = inside ? image[src * 3 + ch] : 255;
+        const int v = s.inside ? image[s.src * 3 + ch] : 255;
         upper_img[o * 3 + ch] = (uint8_t)(up * v);
         lower_img[o * 3 + ch] = (uint8_t)(low * v);
         upper_mask[o * 3 + ch] = (uint8_t)(up * 255);
@@ -104,11 +104,6 @@ __device__ __forceinline__ void resize_taps(int d, double scale, int size, bool 
     s1 = s + 1 < 0 ? 0 : s + 1 > size - 1 ? size - 1 : s + 1;
 }
 
-struct TryonOut {
-    float *real_img, *style_input, *retain, *pose, *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask, *denorm_lower_mask,
-          *gt_parsing;
-};
-
 __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ stick,
                                                              const uint8_t* __restrict__ retain_mask, const uint8_t* __restrict__ gt,
                                                              const uint8_t* __restrict__ norm_img, const uint8_t* __restrict__ norm_lower,
@@ -129,8 +124,8 @@ __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __re
         }
         return;
     }
-    const int y = pix / H, x = pix - y * H, c = x - lp;
-    const bool inside = c >= 0 && c < W;
+    const SquarePixel s = square_pixel(n, pix, H, W, lp);
+    const int y = s.y, x = s.c + lp;
     const int64_t p = (int64_t)n * HH + pix;
 
     // erase = (hand_mask[2] + hand_mask[3] + resize(acgpn)) in uint8 (wrapping) > 0
@@ -147,23 +142,15 @@ __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __re
     const int keep = sum8 > 0 ? 0 : 1;
 
     const int rm = retain_mask[p];
-    int su = 0, sl = 0;
-    for (int ch = 0; ch < 3; ch++) {
-        const int64_t oc = ((int64_t)n * 3 + ch) * HH + pix;
-        const float real = to_unit(inside ? image[((int64_t)n * H * W + (int64_t)y * W + c) * 3 + ch] : 255);
-        o.real_img[oc] = real;
-        const float ret = tr_rounded((float)rm * real) - (float)(uint8_t)(1 - rm);
-        o.retain[oc] = ret;
-        o.pose[((int64_t)n * 6 + ch) * HH + pix] = to_unit(stick[p * 3 + ch]);
-        o.pose[((int64_t)n * 6 + 3 + ch) * HH + pix] = ret;
-        const int u = den_u[p * 3 + ch] * keep, l = den_l[p * 3 + ch] * keep;
-        su += u; sl += l;
-        o.denorm_upper_input[oc] = to_unit(u);
-        o.denorm_lower_input[oc] = to_unit(l);
+    const float label = (float)gt[p];
+    float real[3], ret[3];
+    for (int ch = 0; ch < 3; ch++) {           // real_img is the photograph; retain = real_img * mask - (1 - mask) from the 0 / 1 mask
+        real[ch] = to_unit(s.inside ? image[s.src * 3 + ch] : 255);
+        ret[ch] = tr_rounded((float)rm * real[ch]) - (float)(uint8_t)(1 - rm);
     }
-    o.denorm_upper_mask[p] = su > 0 ? 1.f : 0.f;
-    o.denorm_lower_mask[p] = sl > 0 ? 1.f : 0.f;
-    o.gt_parsing[p] = (float)gt[p];
+    tryon_pixel(o, n, pix, HH, ret, stick + p * 3, den_u + p * 3, den_l + p * 3, keep);
+    for (int ch = 0; ch < 3; ch++) o.image[((int64_t)n * 3 + ch) * HH + pix] = real[ch];
+    o.gt_parsing[p] = label;
 }
 
 }  // namespace pasta
@@ -213,13 +200,11 @@ extern "C" int pasta_tryon_assemble(const uint8_t* image, const uint8_t* stick, 
                 erase_masks && erase_hw && outputs, "tryon_assemble: null pointer");
     PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && ph >= 1 && pw >= 1 && c_upper >= 1 && c_lower >= 1 &&
                 mh_max >= 1 && mw_max >= 1, "tryon_assemble: bad shape");
-    TryonOut o;
-    float** f[9] = {&o.real_img, &o.style_input, &o.retain, &o.pose, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask,
-                    &o.denorm_lower_mask, &o.gt_parsing};
-    for (int i = 0; i < 9; i++) {
-        PASTA_CHECK(outputs[i], "tryon_assemble: output %d is null", i);
-        *f[i] = outputs[i];
-    }
+    TryonOut o{};
+    float** f[9] = {&o.image, &o.style_input, &o.retain, &o.pose, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask,
+                    &o.denorm_lower_mask, &o.gt_parsing};          // FullBodyBatch.KEYS; real_img is o.image
+    const int missing = take_outputs(outputs, f, 9);
+    PASTA_CHECK(missing < 0, "tryon_assemble: output %d is null", missing);
     dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
     hipLaunchKernelGGL(tryon_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, stick, retain_mask, gt_parsing, norm_img,
                        norm_img_lower, denorm_upper, denorm_lower, arm_masks, erase_masks, erase_hw, o, H, W, (H - W) / 2, ph, pw, c_upper,

@@ -1,6 +1,6 @@
-// Per-batch preparation of the try-on TEST pairs on the GPU (row f4, UvitonDatasetV19_test._load_raw_image / normalize /
-// __getitem__, training/dataset.py:1085-1525, and test.py:104-150), which the reference runs per sample on the host in four
-// loader processes with OpenCV, pycocotools and skimage:
+// Per-batch preparation of both sets of try-on TEST pairs on the GPU (row f4), which the reference runs per sample on the host
+// in four loader processes with OpenCV, pycocotools and skimage.  The 256 x 192 pairs (UvitonDatasetV19_test._load_raw_image /
+// normalize / __getitem__, training/dataset.py:1085-1525, and test.py:104-150):
 //   pasta_palm_mask_box_u8           the palm mask with both box sizes as arguments (25 / 15 here, :1240-1253), and
 //                                    pasta_palm_mask_square_u8 with the side of the square as well (512 for the 512 x 320 set);
 //   pasta_tryon_pair_masks_u8        retain image, the person's lower garment and the donor's upper garment (:1105-1141);
@@ -8,8 +8,17 @@
 //                                    (:1480-1492);
 //   pasta_tryon_pair_assemble        __getitem__ (:1502-1525) and test.py's conversions (:104-117) into the seven fp32 tensors;
 //   pasta_images_to_u8               test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137).
+// The 512 x 320 pairs with a change region (UvitonDatasetFull_512_test._load_raw_image / normalize_full / normalize_upper /
+// normalize_lower / __getitem__, :1528-2214, and test_512.py:115-131):
+//   pasta_tryon_region_masks_u8      retain image and the upper and lower garment, each taken from the donor or the person as
+//                                    the region says (:1631-1690);
+//   pasta_tryon_region_assemble      __getitem__ (:2196-2214) and test_512.py's conversions (:115-131) into the nine fp32 tensors.
+// Both masks entries launch tryon_pair_masks_kernel and both assemble entries tryon_pair_assemble_kernel: the 256 pairs are
+// the 512 rules with "upper from the donor, lower from the person" fixed, label 6 added to the lower garment, stick patches as
+// the second patch list and no image / clothes tensors.  The flags are kernel arguments, uniform per launch.
 // The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures tryon_inputs.hip's stick-figure
-// entry.  Where the test set differs from the training preparation (the six rules of include/pasta_hip.h): two people (the
+// entries (thickness 2, radius 2 at 256; 5 and 5 at 512, whose palm boxes are 35 and 20 and whose composites are both eroded).
+// Where the 256 test set differs from the training preparation (the six rules of include/pasta_hip.h): two people (the
 // donor's upper garment with the donor's key points, the person's lower garment with the person's), the person's M_inv for
 // every part, an eroded mask for parts 0-5, a 15 x 15 forearm box, lower garment = labels 6, 9, 12, and key points shifted by
 // the padding in float64 on the host.  Every entry does a whole batch in one launch.
@@ -33,30 +42,30 @@ __global__ __launch_bounds__(PALM_S_MAX) void palm_mask_box_kernel(const uint8_t
 
 // ---- label masks of a pair ----
 
+// The upper and the lower garment each come from the donor or from the person; label 6 belongs to the lower garment at 256 x 192 only.
 __global__ __launch_bounds__(256) void tryon_pair_masks_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ parsing,
                                                                const uint8_t* __restrict__ palm, const uint8_t* __restrict__ d_image,
                                                                const uint8_t* __restrict__ d_parsing, uint8_t* __restrict__ retain_img,
-                                                               uint8_t* __restrict__ lower_img, uint8_t* __restrict__ lower_mask,
-                                                               uint8_t* __restrict__ upper_img, uint8_t* __restrict__ upper_mask, int H, int W,
-                                                               int lp) {
+                                                               uint8_t* __restrict__ upper_img, uint8_t* __restrict__ upper_mask,
+                                                               uint8_t* __restrict__ lower_img, uint8_t* __restrict__ lower_mask, int H, int W,
+                                                               int lp, int upper_from_donor, int lower_from_donor, int six_is_lower) {
     const int n = blockIdx.y;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= H * H) return;
-    const int y = pix / H, c = pix - y * H - lp;
-    const bool inside = c >= 0 && c < W;
-    const int64_t src = (int64_t)n * H * W + (int64_t)y * W + c;
-    const int L = inside ? parsing[src] : 0, D = inside ? d_parsing[src] : 0;
+    const SquarePixel s = square_pixel(n, pix, H, W, lp);
+    const int L = s.inside ? parsing[s.src] : 0, D = s.inside ? d_parsing[s.src] : 0;
     const int64_t o = (int64_t)n * H * H + pix;
-    const int keep = (L == 18 || L == 19) + palm[o] + (L == 1 || L == 2 || L == 4 || L == 13);      // shoes + palm + head
-    const int low = L == 6 || L == 9 || L == 12;                                                    // rule 5: label 6 too
-    const int up = D == 5 || D == 6 || D == 7;                                                      // the donor's
+    const int keep = (L == 18 || L == 19) + palm[o] + (L == 1 || L == 2 || L == 4 || L == 13);      // shoes + palm + head, the person's
+    const int U = upper_from_donor ? D : L, Lo = lower_from_donor ? D : L;
+    const int up = U == 5 || U == 6 || U == 7;
+    const int low = Lo == 9 || Lo == 12 || (six_is_lower && Lo == 6);
     for (int ch = 0; ch < 3; ch++) {
-        const int v = inside ? image[src * 3 + ch] : 255, dv = inside ? d_image[src * 3 + ch] : 255;
+        const int v = s.inside ? image[s.src * 3 + ch] : 255, dv = s.inside ? d_image[s.src * 3 + ch] : 255;
         retain_img[o * 3 + ch] = (uint8_t)(keep * v);
-        lower_img[o * 3 + ch] = (uint8_t)(low * v);
-        lower_mask[o * 3 + ch] = (uint8_t)(low * 255);
-        upper_img[o * 3 + ch] = (uint8_t)(up * dv);
+        upper_img[o * 3 + ch] = (uint8_t)(up * (upper_from_donor ? dv : v));
         upper_mask[o * 3 + ch] = (uint8_t)(up * 255);
+        lower_img[o * 3 + ch] = (uint8_t)(low * (lower_from_donor ? dv : v));
+        lower_mask[o * 3 + ch] = (uint8_t)(low * 255);
     }
 }
 
@@ -78,45 +87,48 @@ __global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8
                           blockIdx.x, tiles_x, flags, rows);
 }
 
-// ---- the seven tensors G takes ----
+// ---- the seven tensors G takes, or the nine of test_512.py ----
 
-struct PairOut {
-    float *retain, *pose, *style_input, *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask, *denorm_lower_mask;
-};
-
-__global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t* __restrict__ retain_img, const uint8_t* __restrict__ stick,
-                                                                  const uint8_t* __restrict__ patches, const uint8_t* __restrict__ stick_patches,
+// Two lists of patches, PA and PB parts, make style_input: (patches, stick patches) at 256 x 192, (patches, patches_lower) at
+// 512 x 320.  o.image and o.clothes are written from image and d_image (W wide, lp columns of padding) unless they are null.
+// retain: test_512.py forms image * mask - (1 - mask) from the 0 / 1 retain mask (shoes, palm and head are disjoint label groups,
+// the palm a subset of labels 14 / 15, so the mask never exceeds 1).  Where the mask is 1 that is to_unit(v) * 1 - 0 = to_unit(v);
+// where it is 0 it is (+-0) - 1 = -1 = to_unit(0).  Both are to_unit(mask * v) = to_unit(retain_img) bit for bit, test.py's form.
+__global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ d_image,
+                                                                  const uint8_t* __restrict__ retain_img, const uint8_t* __restrict__ stick,
+                                                                  const uint8_t* __restrict__ patches_a, const uint8_t* __restrict__ patches_b,
                                                                   const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l,
-                                                                  PairOut o, int H, int P, int ph, int pw) {
+                                                                  TryonOut o, int H, int W, int lp, int PA, int PB, int ph, int pw) {
     const int n = blockIdx.y;
     const int HH = H * H;
     const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= HH) {                // style_input = cat(norm_img, norm_pose): channel 3k + c of part k, patches then stick patches
+    if (pix >= HH) {                // style_input = cat of the two lists: channel 3k + c of part k of its list
         const int q = pix - HH;
         if (q >= ph * pw) return;
-        const int CP = 3 * P;
-        for (int ch = 0; ch < 2 * CP; ch++) {
-            const int cc = ch < CP ? ch : ch - CP, k = cc / 3, c = cc - 3 * k;
-            const uint8_t* src = ch < CP ? patches : stick_patches;
-            o.style_input[((int64_t)n * 2 * CP + ch) * ph * pw + q] = to_unit(src[(((int64_t)n * P + k) * ph * pw + q) * 3 + c]);
+        const int CS = 3 * (PA + PB);
+        for (int ch = 0; ch < CS; ch++) {
+            const int k = ch / 3, c = ch - 3 * k;
+            const uint8_t* src = k < PA ? patches_a + (((int64_t)n * PA + k) * ph * pw + q) * 3 : patches_b + (((int64_t)n * PB + k - PA) * ph * pw + q) * 3;
+            o.style_input[((int64_t)n * CS + ch) * ph * pw + q] = to_unit(src[c]);
         }
         return;
     }
     const int64_t p = (int64_t)n * HH + pix;
-    int su = 0, sl = 0;
-    for (int ch = 0; ch < 3; ch++) {
-        const int64_t oc = ((int64_t)n * 3 + ch) * HH + pix;
-        const float ret = to_unit(retain_img[p * 3 + ch]);
-        o.retain[oc] = ret;
-        o.pose[((int64_t)n * 6 + ch) * HH + pix] = to_unit(stick[p * 3 + ch]);
-        o.pose[((int64_t)n * 6 + 3 + ch) * HH + pix] = ret;
-        const int u = den_u[p * 3 + ch], l = den_l[p * 3 + ch];
-        su += u; sl += l;                                       // numpy sums uint8 in a wider type: no wrap
-        o.denorm_upper_input[oc] = to_unit(u);
-        o.denorm_lower_input[oc] = to_unit(l);
+    float ret[3], person[3] = {}, donor[3] = {};
+    for (int ch = 0; ch < 3; ch++) ret[ch] = to_unit(retain_img[p * 3 + ch]);
+    if (o.image) {                  // read before anything is stored
+        const SquarePixel s = square_pixel(n, pix, H, W, lp);
+        for (int ch = 0; ch < 3; ch++) {
+            person[ch] = to_unit(s.inside ? image[s.src * 3 + ch] : 255);
+            donor[ch] = to_unit(s.inside ? d_image[s.src * 3 + ch] : 255);
+        }
     }
-    o.denorm_upper_mask[p] = su > 0 ? 1.f : 0.f;
-    o.denorm_lower_mask[p] = sl > 0 ? 1.f : 0.f;
+    tryon_pixel(o, n, pix, HH, ret, stick + p * 3, den_u + p * 3, den_l + p * 3, 1);
+    if (o.image)
+        for (int ch = 0; ch < 3; ch++) {
+            o.image[((int64_t)n * 3 + ch) * HH + pix] = person[ch];
+            o.clothes[((int64_t)n * 3 + ch) * HH + pix] = donor[ch];
+        }
 }
 
 // ---- generated images to uint8 ----
@@ -155,17 +167,35 @@ extern "C" int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quad
     return pasta_palm_mask_square_u8(parsing, quads, present, out, N, H, W, k_upper, k_lower, stream);
 }
 
+// Both label-masks entries, `what` naming the caller in the error texts: the 512 x 320 entry passes its region and no label 6, the
+// 256 x 192 one the constant region 1 (upper garment from the donor, lower from the person) with label 6 in the lower garment.
+static int launch_pair_masks(const char* what, const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
+                             const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                             uint8_t* lower_mask, int N, int H, int W, int region, int six_is_lower, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && parsing && palm && donor_image && donor_parsing && retain_img && upper_img && upper_mask && lower_img && lower_mask,
+                "%s: null pointer", what);
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "%s: bad shape", what);
+    PASTA_CHECK(region >= 0 && region <= 2, "%s: region %d (0 full body, 1 upper body, 2 lower body)", what, region);
+    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, donor_image, donor_parsing,
+                       retain_img, upper_img, upper_mask, lower_img, lower_mask, H, W, (H - W) / 2, region != 2, region != 1,
+                       six_is_lower);
+    return launch_status(what);
+}
+
 extern "C" int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
                                          const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* lower_img, uint8_t* lower_mask,
                                          uint8_t* upper_img, uint8_t* upper_mask, int N, int H, int W, void* stream) {
-    using namespace pasta;
-    PASTA_CHECK(image && parsing && palm && donor_image && donor_parsing && retain_img && lower_img && lower_mask && upper_img && upper_mask,
-                "tryon_pair_masks_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "tryon_pair_masks_u8: bad shape");
-    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, donor_image, donor_parsing,
-                       retain_img, lower_img, lower_mask, upper_img, upper_mask, H, W, (H - W) / 2);
-    return launch_status("tryon_pair_masks_u8");
+    return launch_pair_masks("tryon_pair_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
+                             lower_img, lower_mask, N, H, W, 1, 1, stream);
+}
+
+extern "C" int pasta_tryon_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
+                                           const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask,
+                                           uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W, int region, void* stream) {
+    return launch_pair_masks("tryon_region_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
+                             lower_img, lower_mask, N, H, W, region, 0, stream);
 }
 
 extern "C" int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
@@ -190,16 +220,34 @@ extern "C" int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_
     PASTA_CHECK(retain_img && stick && patches && stick_patches && denorm_upper && denorm_lower && outputs, "tryon_pair_assemble: null pointer");
     PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && P >= 1 && P <= 64 && ph >= 1 && pw >= 1 && ph * pw <= H * H,
                 "tryon_pair_assemble: bad shape");
-    PairOut o;
+    TryonOut o{};                   // image and clothes stay null: not written, and no photograph is read
     float** f[7] = {&o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask, &o.denorm_lower_mask};
-    for (int i = 0; i < 7; i++) {
-        PASTA_CHECK(outputs[i], "tryon_pair_assemble: output %d is null", i);
-        *f[i] = outputs[i];
-    }
+    const int missing = take_outputs(outputs, f, 7);
+    PASTA_CHECK(missing < 0, "tryon_pair_assemble: output %d is null", missing);
     dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, retain_img, stick, patches, stick_patches,
-                       denorm_upper, denorm_lower, o, H, P, ph, pw);
+    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr, (const uint8_t*)nullptr,
+                       retain_img, stick, patches, stick_patches, denorm_upper, denorm_lower, o, H, H, 0, P, P, ph, pw);
     return launch_status("tryon_pair_assemble");
+}
+
+extern "C" int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image, const uint8_t* retain_img, const uint8_t* stick,
+                                           const uint8_t* patches, const uint8_t* patches_lower, const uint8_t* denorm_upper,
+                                           const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph,
+                                           int pw, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && donor_image && retain_img && stick && patches && patches_lower && denorm_upper && denorm_lower && outputs,
+                "tryon_region_assemble: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && P >= 1 && P <= 64 && P_lower >= 1 && P_lower <= 64 &&
+                ph >= 1 && pw >= 1 && ph * pw <= H * H, "tryon_region_assemble: bad shape");
+    TryonOut o{};
+    float** f[9] = {&o.image, &o.clothes, &o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input,
+                    &o.denorm_upper_mask, &o.denorm_lower_mask};
+    const int missing = take_outputs(outputs, f, 9);
+    PASTA_CHECK(missing < 0, "tryon_region_assemble: output %d is null", missing);
+    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, donor_image, retain_img, stick, patches,
+                       patches_lower, denorm_upper, denorm_lower, o, H, W, (H - W) / 2, P, P_lower, ph, pw);
+    return launch_status("tryon_region_assemble");
 }
 
 extern "C" int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream) {

@@ -22,40 +22,16 @@ Differences from the reference, on purpose:
 
 import json
 import os
-import re
 from typing import List, Optional
 
 import click
 
-
-def num_range(s: str) -> List[int]:
-    """Either a comma-separated list 'a,b,c' or a range 'a-c'."""
-    first, dash, last = s.partition('-')
-    if dash and first.isdigit() and last.isdigit():
-        return list(range(int(first), int(last) + 1))
-    return [int(x) for x in s.split(',')]
-
-
-def _local_snapshot(path):
-    if re.match(r'^[A-Za-z][A-Za-z0-9+.-]*://', path):
-        raise click.BadParameter('%r is a URL: give the path of a local snapshot file' % path, param_hint='--network')
-    if not os.path.isfile(path):
-        raise click.BadParameter('%r is not a file' % path, param_hint='--network')
-    return path
+import tryon_cli
 
 
 @click.command()
-@click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True)
-@click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)')
-@click.option('--trunc', 'truncation_psi', type=float, help='Truncation psi, forwarded to G.mapping', default=1, show_default=True)
-@click.option('--class', 'class_idx', type=int, help='Class label (unused, as in the reference)')
-@click.option('--noise-mode', help='Noise mode, forwarded to G.synthesis', type=click.Choice(['const', 'random', 'none']), default='const',
-              show_default=True)
-@click.option('--projected-w', help='Projection result file (unused, as in the reference)', type=str, metavar='FILE')
-@click.option('--outdir', help='Where to save the output images', type=str, required=True, metavar='DIR')
-@click.option('--dataroot', help='Root of the test data set', type=str, required=True)
-@click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=16, show_default=True)
-@click.option('--workers', help='Loader processes (file decoding only)', type=click.IntRange(min=0), default=4, show_default=True)
+@tryon_cli.shared_options('Root of the test data set', 16)
+@tryon_cli.workers_option
 @click.option('--scores', 'scores_file', help='Score the written images by region (kept body parts, upper and lower garment patches: L1, PSNR, '
               'SSIM) and write the results to FILE as JSON. With this option z of pair i is np.random.RandomState(i).randn(z_dim), so that '
               'the figures describe the images whatever the batch size [default: no scores]', type=str, metavar='FILE')
@@ -67,26 +43,20 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
     python test.py --network snapshot.pkl --outdir out --dataroot PASTA_UPT_256 --batchsize 16
     """
     del seeds, class_idx, projected_w
-    _local_snapshot(network_pkl)
+    tryon_cli._local_snapshot(network_pkl)
 
     import numpy as np
     import PIL.Image
     import torch
 
-    import legacy
     from training import dataset as custom_dataset
     from training.tryon_pairs import TryOnPairBatchBuilder, images_to_u8
 
     device = torch.device('cuda')
-    print('Loading networks from "%s"...' % network_pkl)
-    with open(network_pkl, 'rb') as f:
-        G = legacy.load_network_pkl(f)['G_ema'].to(device).eval().requires_grad_(False)  # type: ignore
-
+    G = tryon_cli.load_generator(network_pkl, device)
     os.makedirs(outdir, exist_ok=True)
     dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
-    loader = torch.utils.data.DataLoader(dataset, batch_size=batchsize, shuffle=False, num_workers=workers, pin_memory=True,
-                                         collate_fn=custom_dataset.collate_pairs)
-    print(len(dataset))
+    loader = tryon_cli.pair_loader(dataset, batchsize, workers)
     builder = TryOnPairBatchBuilder(device)
     if scores_file is not None:
         from metrics import tryon_fidelity
@@ -101,13 +71,7 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
         if scores_file is not None:
             pair_index = raw['raw_idx'].tolist()                    # the pairs' positions in the pair lists
             gen_z = tryon_fidelity.pair_z(pair_index, G.z_dim, device)
-        with torch.no_grad():
-            gen_c, cat_feat_list = G.style_encoding(t['style_input'], t['retain'])
-            pose_feat = G.const_encoding(t['pose'])
-            ws = G.mapping(gen_z, gen_c, truncation_psi=truncation_psi)
-            cat_feats = {str(feat.shape[2]): feat for feat in cat_feat_list}
-            _, gen_imgs, _, _ = G.synthesis(ws, pose_feat, cat_feats, t['denorm_upper_input'], t['denorm_lower_input'], t['denorm_upper_mask'],
-                                            t['denorm_lower_mask'], noise_mode=noise_mode)
+        gen_imgs = tryon_cli.generate(G, t, gen_z, truncation_psi, noise_mode)
         images = images_to_u8(gen_imgs, (height - width) // 2, width).cpu().numpy()
         if scores_file is not None:
             tryon_fidelity.score_batch(gen_imgs, batch, pair_index, partials)

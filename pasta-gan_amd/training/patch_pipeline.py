@@ -142,6 +142,32 @@ def warp_perspective(src, matrices, out_hw, border='constant', src_index=None, v
     return dst
 
 
+def inverse_maps(back, parts):
+    """[n * p, 9] float64: the inverse cv2.warpPerspective applies to ``back[i, k]`` for every sample i and every k of ``parts``,
+    sample-major."""
+    return np.ascontiguousarray(np.stack([adjugate_inverse(back[i, k]) for i in range(len(back)) for k in parts]).reshape(-1, 9))
+
+
+def composite(patches, masks, back, valid, parts, height, width, radius=None, want_part_masks=False):
+    """patch -> image (BORDER_CONSTANT) + mask test + compositing of ``patches`` / ``masks`` [N, p, h, w, 3] in order, one launch:
+    index j is part ``parts[j]`` of ``back`` [N, 10, 3, 3] / ``valid`` [N, 10], the maps of the people the result is drawn on.
+    ``radius`` None: pasta_patch_composite_u8, the mask tested as warped; a value: pasta_patch_composite_eroded_u8, the mask eroded
+    (2 * radius + 1) square first.  Returns (image uint8 [N, height, width, 3], part masks uint8 [N, p, height, width] or None)."""
+    n, p, ph, pw = patches.shape[:4]
+    dev = patches.device
+    inv_t = torch.from_numpy(inverse_maps(back, parts)).to(dev)
+    val_t = torch.as_tensor(np.ascontiguousarray(valid[:, parts]).astype(np.uint8), device=dev)
+    out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
+    pm = torch.empty([n, p, height, width], dtype=torch.uint8, device=dev) if want_part_masks else None
+    patches, masks = patches.contiguous(), masks.contiguous()             # held until the launch is queued
+    lib = _native.lib()
+    entry, extra = (lib.pasta_patch_composite_u8, ()) if radius is None else (lib.pasta_patch_composite_eroded_u8, (radius,))
+    with torch.cuda.device(dev):
+        _native.check(entry(_native.ptr(patches), _native.ptr(masks), _native.ptr(inv_t), _native.ptr(val_t), _native.ptr(out), _native.ptr(pm),
+                            n, p, ph, pw, height, width, *extra, _native.stream()))
+    return out, pm
+
+
 def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_factor=2):
     """``normalize`` (dataset.py:838-927) for a batch on the GPU.  Images and 3-channel masks: uint8 [N, H, W, 3] CUDA tensors;
     ``joints`` [N, 18, 3] (host).  Returns the reference's tuple, batched:
@@ -151,7 +177,6 @@ def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_fa
     n, height, width, _ = upper_img.shape
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
     fwd, back, valid = part_matrices(joints, width, height, box_factor)
-    dev = upper_img.device
     sample = np.repeat(np.arange(n, dtype=np.int32), 10)
     flat_valid = valid.reshape(-1)
     # image -> patch (BORDER_REPLICATE): all ten parts of every sample in one launch per source tensor
@@ -163,21 +188,9 @@ def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_fa
     p_img_l = warp(lower_img, legs).reshape(n, 10 - LOWER_FROM, ph, pw, 3)
     p_mask_l = warp(lower_mask, legs).reshape(n, 10 - LOWER_FROM, ph, pw, 3)
 
-    # patch -> image (BORDER_CONSTANT) + mask test + compositing, all parts in order, one launch per garment
-    def composite(patches, masks, part_ids, want_part_masks):
-        p = len(part_ids)
-        inv = np.ascontiguousarray(np.stack([adjugate_inverse(back[i, k]) for i in range(n) for k in part_ids]).reshape(n * p, 9))
-        inv_t = torch.from_numpy(inv).to(dev)
-        val_t = torch.as_tensor(np.ascontiguousarray(valid[:, part_ids]).astype(np.uint8), device=dev)
-        out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
-        pm = torch.empty([n, p, height, width], dtype=torch.uint8, device=dev) if want_part_masks else None
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().pasta_patch_composite_u8(_native.ptr(patches.contiguous()), _native.ptr(masks.contiguous()), _native.ptr(inv_t),
-                                                                 _native.ptr(val_t), _native.ptr(out), _native.ptr(pm), n, p, ph, pw, height, width,
-                                                                 _native.stream()))
-        return out, pm
-    den_u, part_masks = composite(p_img, p_mask, list(range(10)), True)
-    den_l, _ = composite(p_img_l, p_mask_l, list(range(LOWER_FROM, 10)), False)
+    # patch -> image + mask test + compositing, all parts in order, one launch per garment
+    den_u, part_masks = composite(p_img, p_mask, back, valid, list(range(10)), height, width, want_part_masks=True)
+    den_l, _ = composite(p_img_l, p_mask_l, back, valid, list(range(LOWER_FROM, 10)), height, width)
     hwc = lambda t: t.permute(0, 2, 3, 1, 4).reshape(n, ph, pw, -1)            # parts concatenated along the channel axis (:918-921)
     m_invs = torch.from_numpy(np.where(valid[..., None, None], back, 0.0).astype(np.float32))
     hand_masks = part_masks[:, list(ARM_PARTS)].unsqueeze(-1)
@@ -203,7 +216,6 @@ def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
     fwd_u, _, valid_u = part_matrices(upper_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
     fwd_l, back_l, valid_l = part_matrices(lower_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
-    dev = upper_img.device
     donor = np.arange(10) < UPPER_PARTS
     mats = np.where(donor[None, :, None, None], fwd_u, fwd_l).reshape(-1, 3, 3)
     valid = np.where(donor[None, :], valid_u, valid_l).reshape(-1)
@@ -212,20 +224,9 @@ def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower
     warp = lambda a, b: warp_perspective(torch.cat([a, b]), mats, (ph, pw), 'replicate', src_index, valid).reshape(n, 10, ph, pw, 3)
     patches, stick_patches, mask_patches = warp(upper_img, lower_img), warp(upper_stick, lower_stick), warp(upper_mask, lower_mask)
 
-    def composite(parts, entry, *radius):
-        p = len(parts)
-        inv = np.ascontiguousarray(np.stack([adjugate_inverse(back_l[i, k]) for i in range(n) for k in parts]).reshape(n * p, 9))
-        inv_t = torch.from_numpy(inv).to(dev)
-        val_t = torch.as_tensor(np.ascontiguousarray(valid_l[:, parts]).astype(np.uint8), device=dev)
-        out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
-        src, msk = patches[:, parts].contiguous(), mask_patches[:, parts].contiguous()     # held until the launch is queued
-        with torch.cuda.device(dev):
-            _native.check(entry(_native.ptr(src), _native.ptr(msk), _native.ptr(inv_t),
-                                _native.ptr(val_t), _native.ptr(out), None, n, p, ph, pw, height, width, *radius, _native.stream()))
-        return out
-    lib = _native.lib()
-    den_u = composite(list(range(UPPER_PARTS)), lib.pasta_patch_composite_eroded_u8, ERODE_RADIUS)
-    den_l = composite(list(range(UPPER_PARTS, 10)), lib.pasta_patch_composite_u8)
+    upper, lower = list(range(UPPER_PARTS)), list(range(UPPER_PARTS, 10))
+    den_u, _ = composite(patches[:, upper], mask_patches[:, upper], back_l, valid_l, upper, height, width, ERODE_RADIUS)
+    den_l, _ = composite(patches[:, lower], mask_patches[:, lower], back_l, valid_l, lower, height, width)
     m_invs = torch.from_numpy(np.where(valid_l[..., None, None], back_l, 0.0).astype(np.float32))
     return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l
 
@@ -253,7 +254,6 @@ def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joint
     fwd_p, back, valid_p = part_matrices(person_joints, width, height, box_factor, x_pad=0)
     fwd_u, valid_u = (fwd_d, valid_d) if upper_from_donor else (fwd_p, valid_p)
     fwd_l, valid_l = (fwd_d, valid_d) if lower_from_donor else (fwd_p, valid_p)
-    dev = garment_img.device
     low = list(LOWER_PARTS_512)
     pu, pl = 10, len(low)
     # items: (i, k) of the upper garments, then (i, k) of the lower garments, which read source N + i
@@ -264,18 +264,7 @@ def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joint
     split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
     (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
 
-    def composite(src, msk, parts):
-        p = len(parts)
-        inv = np.ascontiguousarray(np.stack([adjugate_inverse(back[i, k]) for i in range(n) for k in parts]).reshape(n * p, 9))
-        inv_t = torch.from_numpy(inv).to(dev)
-        val_t = torch.as_tensor(np.ascontiguousarray(valid_p[:, parts]).astype(np.uint8), device=dev)
-        out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().pasta_patch_composite_eroded_u8(_native.ptr(src), _native.ptr(msk), _native.ptr(inv_t), _native.ptr(val_t),
-                                                                        _native.ptr(out), None, n, p, ph, pw, height, width, ERODE_RADIUS,
-                                                                        _native.stream()))
-        return out
-    den_u = composite(patches, mask_patches, list(range(pu)))
-    den_l = composite(patches_l, mask_patches_l, low)
+    den_u, _ = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS)
+    den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
     m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
     return patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p

@@ -71,7 +71,7 @@ class SnapshotGrid:
         # M_inv.sum() == 0 (:87), its stand-in for "get_crop found no quadrilateral"; part_matrices' valid flag says that
         # directly (a present matrix whose entries happen to sum to zero is used here and skipped there).
         _, back, valid = patch_pipeline.part_matrices(np.asarray(raw['keypoints'], np.float64), H, H, box_factor)
-        inv = np.stack([[patch_pipeline.adjugate_inverse(back[i, k]) for k in range(pu)] for i in range(g)]).reshape(g, pu, 9)
+        inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(g, pu, 9)
         upper_src, lower_src = cell_sources(gnum)
         lower_parts = np.arange(pu - pl, pu)                       # parts 6..9 are also cut from the lower garment (:76)
         parts_u, parts_l = np.arange(pu, dtype=np.int32), np.arange(pl, dtype=np.int32)

@@ -8,7 +8,11 @@ do per sample on the host, as a few launches per batch:
     patch_pipeline.normalize_batch   the ten body-part warps    (csrc/patches.hip)
     pasta_tryon_assemble     erase mask and every float conversion, into the nine tensors of SyntheticFullBodyBatch.KEYS
 
-The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps."""
+The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
+
+The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
+``upload_person`` (upload and checks), ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32
+tensors of a KEYS list with their pointer array) and ``shift_keypoints``."""
 
 import ctypes
 import math
@@ -74,6 +78,49 @@ def palm_quads(keypoints, left_padding):
     return np.ascontiguousarray(np.clip(np.nan_to_num(quads), -QUAD_LIMIT, QUAD_LIMIT)), present
 
 
+def upload_person(raw, device, who, prefix=''):
+    """One person set of a collated batch (``prefix`` 'clothes_': the donors) -> (image uint8 [N, H, W, 3], parsing uint8 [N, H, W]
+    on ``device``, key points float64 [N, 18, 3] on the host), checked."""
+    up = lambda t: torch.as_tensor(t).to(device, non_blocking=True).contiguous()
+    image, parsing = up(raw[prefix + 'image']), up(raw[prefix + 'parsing'])
+    keypoints = np.asarray(raw[prefix + 'keypoints'], np.float64)
+    _native.require_gpu(image, who)
+    assert image.dtype == torch.uint8 and parsing.dtype == torch.uint8
+    n, H, W, _ = image.shape
+    assert H >= W and tuple(parsing.shape) == (n, H, W) and keypoints.shape == (n, 18, 3)
+    return image, parsing, keypoints
+
+
+def upload_pair(raw, device, who):
+    """(image, parsing, key points) of the persons, then of the clothes donors, of a batch of ``training.dataset.collate_pairs``."""
+    person, donor = upload_person(raw, device, who), upload_person(raw, device, who, 'clothes_')
+    assert donor[0].shape == person[0].shape
+    return person + donor
+
+
+def device_tables(stick_keypoints, palm_keypoints, left_padding, device):
+    """(limbs, joints, quads, present) on ``device``: stick_tables of the first (UNSHIFTED) key points, palm_quads of the second."""
+    arrays = stick_tables(stick_keypoints) + palm_quads(palm_keypoints, left_padding)
+    return tuple(torch.from_numpy(a).to(device, non_blocking=True) for a in arrays)
+
+
+def allocator(dtype, device):
+    return lambda *shape: torch.empty(shape, dtype=dtype, device=device)
+
+
+def output_tensors(keys, n, H, style_shape, device):
+    """The fp32 tensors an assemble entry fills, in the order of ``keys``, and the array of their pointers: style_input
+    [n, *style_shape]; on the padded square pose has 6 planes, the masks and gt_parsing 1, every other tensor 3."""
+    f32, planes = allocator(torch.float32, device), dict(pose=6, denorm_upper_mask=1, denorm_lower_mask=1, gt_parsing=1)
+    t = {k: f32(n, *style_shape) if k == 'style_input' else f32(n, planes.get(k, 3), H, H) for k in keys}
+    return t, (ctypes.c_void_p * len(keys))(*[t[k].data_ptr() for k in keys])
+
+
+def shift_keypoints(keypoints, left_padding):
+    """float64, as the test sets' keypoints[:, 0] += left_padding before get_crop's float32 conversion."""
+    return np.concatenate([keypoints[..., :1] + left_padding, keypoints[..., 1:]], axis=-1)
+
+
 class FullBodyBatch:
     """The interface TrainingStep.run consumes (as SyntheticFullBodyBatch): ``tensors`` (the nine KEYS), ``batch``, ``split``.
     ``stages`` holds the uint8 intermediates when the builder was asked to keep them; ``image`` is the photographs' uint8 batch
@@ -101,21 +148,15 @@ class FullBodyBatchBuilder:
 
     def build(self, raw, keep_stages=False):
         dev = self.device
-        up = lambda t: torch.as_tensor(t).to(dev, non_blocking=True).contiguous()
-        image, parsing = up(raw['image']), up(raw['parsing'])
-        erase, erase_hw = up(raw['erase_masks']), up(torch.as_tensor(raw['erase_hw'], dtype=torch.int32))
-        keypoints = np.asarray(raw['keypoints'], np.float64)
-        _native.require_gpu(image, 'FullBodyBatchBuilder')
-        assert image.dtype == torch.uint8 and parsing.dtype == torch.uint8 and erase.dtype == torch.uint8
+        image, parsing, keypoints = upload_person(raw, dev, 'FullBodyBatchBuilder')
+        erase = torch.as_tensor(raw['erase_masks']).to(dev, non_blocking=True).contiguous()
+        erase_hw = torch.as_tensor(raw['erase_hw'], dtype=torch.int32).to(dev, non_blocking=True).contiguous()
         n, H, W, _ = image.shape
-        assert H >= W and tuple(parsing.shape) == (n, H, W) and keypoints.shape == (n, 18, 3) and erase.ndim == 3
         hw = np.asarray(raw['erase_hw'])
-        assert hw.shape == (n, 2) and (hw >= 1).all() and (hw[:, 0] <= erase.shape[1]).all() and (hw[:, 1] <= erase.shape[2]).all()
-        lp = (H - W) // 2
-        limbs, joints = stick_tables(keypoints)
-        quads, present = palm_quads(keypoints, lp)
-        limbs, joints, quads, present = (torch.from_numpy(a).to(dev, non_blocking=True) for a in (limbs, joints, quads, present))
-        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)
+        assert erase.dtype == torch.uint8 and erase.ndim == 3 and hw.shape == (n, 2) and (hw >= 1).all()
+        assert (hw[:, 0] <= erase.shape[1]).all() and (hw[:, 1] <= erase.shape[2]).all()
+        limbs, joints, quads, present = device_tables(keypoints, keypoints, (H - W) // 2, dev)
+        u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)
         garments = [u8(n, H, H, 3) for _ in range(4)]          # upper image, lower image, upper mask, lower mask
         lib, P = _native.lib(), _native.ptr
@@ -129,11 +170,7 @@ class FullBodyBatchBuilder:
         norm_img, norm_lower, den_u, den_l = (t.contiguous() for t in (norm_img, norm_lower, den_u, den_l))
         arm = hand_masks.reshape(n, 4, H, H).contiguous()
         ph, pw, cu, cl = norm_img.shape[1], norm_img.shape[2], norm_img.shape[3], norm_lower.shape[3]
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        t = dict(real_img=f32(n, 3, H, H), style_input=f32(n, cu + cl, ph, pw), retain=f32(n, 3, H, H), pose=f32(n, 6, H, H),
-                 denorm_upper_input=f32(n, 3, H, H), denorm_lower_input=f32(n, 3, H, H), denorm_upper_mask=f32(n, 1, H, H),
-                 denorm_lower_mask=f32(n, 1, H, H), gt_parsing=f32(n, 1, H, H))
-        outs = (ctypes.c_void_p * 9)(*[t[k].data_ptr() for k in FullBodyBatch.KEYS])
+        t, outs = output_tensors(FullBodyBatch.KEYS, n, H, (cu + cl, ph, pw), dev)
         with torch.cuda.device(dev):
             _native.check(lib.pasta_tryon_assemble(P(image), P(stick), P(retain_mask), P(gt), P(norm_img), P(norm_lower), P(den_u), P(den_l),
                                                    P(arm), P(erase), P(erase_hw), outs, n, H, W, ph, pw, cu, cl,

@@ -13,14 +13,12 @@ The host keeps the file decoding (training/dataset.py), the key-point geometry a
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads)."""
 
-import ctypes
-
 import numpy as np
 import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
-from training.tryon_batch import palm_quads, stick_tables
+from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_pair
 
 PALM_BOXES = (25, 15)       # get_hand_mask of the test set: upper arm 25 x 25, forearm 15 x 15 (dataset.py:1240-1253)
 
@@ -28,7 +26,8 @@ PALM_BOXES = (25, 15)       # get_hand_mask of the test set: upper arm 25 x 25, 
 class TryOnPairBatch:
     """``tensors``: the seven inputs of test.py's generator calls (KEYS); ``person_name`` / ``clothes_name``: the data set's
     relative paths; ``stages``: the uint8 intermediates (and the person's unpadded ``image`` and ``parsing``, which
-    metrics.tryon_fidelity scores against) when the builder was asked to keep them."""
+    metrics.tryon_fidelity scores against) when the builder was asked to keep them.  training.tryon_regions.TryOnRegionBatch is
+    this class with the nine KEYS of test_512.py."""
     KEYS = ['retain', 'pose', 'style_input', 'denorm_upper_input', 'denorm_lower_input', 'denorm_upper_mask', 'denorm_lower_mask']
 
     def __init__(self, tensors, person_name, clothes_name, stages=None):
@@ -48,21 +47,11 @@ class TryOnPairBatchBuilder:
 
     def build(self, raw, keep_stages=False):
         dev = self.device
-        up = lambda t: torch.as_tensor(t).to(dev, non_blocking=True).contiguous()
-        image, parsing = up(raw['image']), up(raw['parsing'])
-        d_image, d_parsing = up(raw['clothes_image']), up(raw['clothes_parsing'])
-        kp = np.asarray(raw['keypoints'], np.float64)
-        d_kp = np.asarray(raw['clothes_keypoints'], np.float64)
-        _native.require_gpu(image, 'TryOnPairBatchBuilder')
-        assert all(t.dtype == torch.uint8 for t in (image, parsing, d_image, d_parsing))
+        image, parsing, kp, d_image, d_parsing, d_kp = upload_pair(raw, dev, 'TryOnPairBatchBuilder')
         n, H, W, _ = image.shape
-        assert H >= W and tuple(d_image.shape) == (n, H, W, 3) and tuple(parsing.shape) == tuple(d_parsing.shape) == (n, H, W)
-        assert kp.shape == d_kp.shape == (n, 18, 3)
         lp = (H - W) // 2
-        limbs, joints = stick_tables(np.concatenate([d_kp, kp]))          # stick figures from the UNSHIFTED key points
-        quads, present = palm_quads(kp, lp)
-        limbs, joints, quads, present = (torch.from_numpy(a).to(dev, non_blocking=True) for a in (limbs, joints, quads, present))
-        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)
+        limbs, joints, quads, present = device_tables(np.concatenate([d_kp, kp]), kp, lp, dev)
+        u8 = allocator(torch.uint8, dev)
         sticks, palm = u8(2 * n, H, H, 3), u8(n, H, H)                     # sticks: the donors, then the persons
         retain_img, lower_img, lower_mask, upper_img, upper_mask = (u8(n, H, H, 3) for _ in range(5))
         lib, P = _native.lib(), _native.ptr
@@ -73,14 +62,10 @@ class TryOnPairBatchBuilder:
             _native.check(lib.pasta_tryon_pair_masks_u8(P(image), P(parsing), P(palm), P(d_image), P(d_parsing), P(retain_img), P(lower_img),
                                                         P(lower_mask), P(upper_img), P(upper_mask), n, H, W, s))
         d_stick, stick = sticks[:n], sticks[n:]
-        shift = lambda k: np.concatenate([k[..., :1] + lp, k[..., 1:]], axis=-1)     # float64, as keypoints[:, 0] += left_padding
         patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l = patch_pipeline.normalize_pair_batch(
-            upper_img, d_stick, upper_mask, shift(d_kp), lower_img, stick, lower_mask, shift(kp), self.box_factor)
+            upper_img, d_stick, upper_mask, shift_keypoints(d_kp, lp), lower_img, stick, lower_mask, shift_keypoints(kp, lp), self.box_factor)
         parts, ph, pw = patches.shape[1], patches.shape[2], patches.shape[3]
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        t = dict(retain=f32(n, 3, H, H), pose=f32(n, 6, H, H), style_input=f32(n, 6 * parts, ph, pw), denorm_upper_input=f32(n, 3, H, H),
-                 denorm_lower_input=f32(n, 3, H, H), denorm_upper_mask=f32(n, 1, H, H), denorm_lower_mask=f32(n, 1, H, H))
-        outs = (ctypes.c_void_p * 7)(*[t[k].data_ptr() for k in TryOnPairBatch.KEYS])
+        t, outs = output_tensors(TryOnPairBatch.KEYS, n, H, (6 * parts, ph, pw), dev)
         with torch.cuda.device(dev):
             _native.check(lib.pasta_tryon_pair_assemble(P(retain_img), P(stick), P(patches), P(stick_patches), P(den_u), P(den_l), outs, n, H,
                                                         parts, ph, pw, _native.stream()))

@@ -5,7 +5,7 @@ in four loader processes, as a few launches per batch:
 
     pasta_pose_stickman_thick_u8      the person's stick figure, thickness 5 and radius 5   (csrc/tryon_inputs.hip)
     pasta_palm_mask_square_u8         the person's palm mask on the 512 square, boxes 35 and 20 (csrc/tryon_pairs.hip)
-    pasta_tryon_region_masks_u8       retain image, upper and lower garment of the person the region names (csrc/tryon_regions.hip)
+    pasta_tryon_region_masks_u8       retain image, upper and lower garment of the person the region names (csrc/tryon_pairs.hip)
     patch_pipeline.normalize_region_batch   two forward warps + two eroded composites (csrc/patches.hip, csrc/tryon_pairs.hip)
     pasta_tryon_region_assemble       the nine fp32 tensors of test_512.py
 
@@ -13,14 +13,12 @@ The host keeps the file decoding (training/dataset.py), the key-point geometry a
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621)."""
 
-import ctypes
-
-import numpy as np
 import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
-from training.tryon_batch import palm_quads, stick_tables
+from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_pair
+from training.tryon_pairs import TryOnPairBatch
 
 PALM_BOXES = (35, 20)       # get_hand_mask of the 512 set: upper arm 35 x 35, forearm 20 x 20 (dataset.py:1790, :1795)
 STICK_THICKNESS = 5         # cv2.line(..., 5) (dataset.py:1851)
@@ -29,19 +27,12 @@ STICK_RADIUS = 5            # circle(..., radius=5) (dataset.py:1832, :1861)
 REGIONS = dict(fullbody=(0, True, True), upperbody=(1, True, False), lowerbody=(2, False, True))
 
 
-class TryOnRegionBatch:
+class TryOnRegionBatch(TryOnPairBatch):
     """``tensors``: the nine tensors test_512.py forms (KEYS; the generator takes all but ``image`` and ``clothes``, which
     test_512.py writes next to the result); ``person_name`` / ``clothes_name``: the data set's relative paths; ``stages``: the
     uint8 intermediates when the builder was asked to keep them."""
     KEYS = ['image', 'clothes', 'retain', 'pose', 'style_input', 'denorm_upper_input', 'denorm_lower_input', 'denorm_upper_mask',
             'denorm_lower_mask']
-
-    def __init__(self, tensors, person_name, clothes_name, stages=None):
-        self.tensors = tensors
-        self.batch = int(tensors['retain'].shape[0])
-        self.person_name = list(person_name)
-        self.clothes_name = list(clothes_name)
-        self.stages = stages
 
 
 class TryOnRegionBatchBuilder:
@@ -57,22 +48,12 @@ class TryOnRegionBatchBuilder:
 
     def build(self, raw, keep_stages=False):
         dev = self.device
-        up = lambda t: torch.as_tensor(t).to(dev, non_blocking=True).contiguous()
-        image, parsing = up(raw['image']), up(raw['parsing'])
-        d_image, d_parsing = up(raw['clothes_image']), up(raw['clothes_parsing'])
-        kp = np.asarray(raw['keypoints'], np.float64)
-        d_kp = np.asarray(raw['clothes_keypoints'], np.float64)
-        _native.require_gpu(image, 'TryOnRegionBatchBuilder')
-        assert all(t.dtype == torch.uint8 for t in (image, parsing, d_image, d_parsing))
+        image, parsing, kp, d_image, d_parsing, d_kp = upload_pair(raw, dev, 'TryOnRegionBatchBuilder')
         n, H, W, _ = image.shape
-        assert H >= W and tuple(d_image.shape) == (n, H, W, 3) and tuple(parsing.shape) == tuple(d_parsing.shape) == (n, H, W)
-        assert kp.shape == d_kp.shape == (n, 18, 3)
         lp = (H - W) // 2
         code, upper_donor, lower_donor = REGIONS[self.change_region]
-        limbs, joints = stick_tables(kp)                                   # the stick figure from the UNSHIFTED key points
-        quads, present = palm_quads(kp, lp)
-        limbs, joints, quads, present = (torch.from_numpy(a).to(dev, non_blocking=True) for a in (limbs, joints, quads, present))
-        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)
+        limbs, joints, quads, present = device_tables(kp, kp, lp, dev)
+        u8 = allocator(torch.uint8, dev)
         stick, palm, retain_img = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H, 3)
         garment_img, garment_mask = u8(2 * n, H, H, 3), u8(2 * n, H, H, 3)  # the upper garments, then the lower garments
         upper_img, lower_img, upper_mask, lower_mask = garment_img[:n], garment_img[n:], garment_mask[:n], garment_mask[n:]
@@ -83,15 +64,10 @@ class TryOnRegionBatchBuilder:
             _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
             _native.check(lib.pasta_tryon_region_masks_u8(P(image), P(parsing), P(palm), P(d_image), P(d_parsing), P(retain_img), P(upper_img),
                                                           P(upper_mask), P(lower_img), P(lower_mask), n, H, W, code, s))
-        shift = lambda k: np.concatenate([k[..., :1] + lp, k[..., 1:]], axis=-1)     # float64, as keypoints[:, 0] += left_padding
         patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p = patch_pipeline.normalize_region_batch(
-            garment_img, garment_mask, shift(d_kp), shift(kp), upper_donor, lower_donor, self.box_factor)
+            garment_img, garment_mask, shift_keypoints(d_kp, lp), shift_keypoints(kp, lp), upper_donor, lower_donor, self.box_factor)
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        t = dict(image=f32(n, 3, H, H), clothes=f32(n, 3, H, H), retain=f32(n, 3, H, H), pose=f32(n, 6, H, H),
-                 style_input=f32(n, 3 * (pu + pl), ph, pw), denorm_upper_input=f32(n, 3, H, H), denorm_lower_input=f32(n, 3, H, H),
-                 denorm_upper_mask=f32(n, 1, H, H), denorm_lower_mask=f32(n, 1, H, H))
-        outs = (ctypes.c_void_p * 9)(*[t[k].data_ptr() for k in TryOnRegionBatch.KEYS])
+        t, outs = output_tensors(TryOnRegionBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
         with torch.cuda.device(dev):
             _native.check(lib.pasta_tryon_region_assemble(P(image), P(d_image), P(retain_img), P(stick), P(patches), P(patches_l), P(den_u),
                                                           P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))

@@ -1,4 +1,4 @@
-"""Row f4 for the 512 x 320 try-on pairs with a change region on the GPU (csrc/tryon_regions.hip, the generalised stick-figure
+"""Row f4 for the 512 x 320 try-on pairs with a change region on the GPU (the region entries of csrc/tryon_pairs.hip, the generalised stick-figure
 and palm entries, training/tryon_regions.py, pasta-gan_amd/test_512.py) against the numpy restatement of the reference
 (tests/tryon_512_ref.py) -- EXACT: every uint8 stage bit for bit, the nine fp32 tensors equal to test_512.py's own expressions
 evaluated by torch on the GPU, and the written images against an in-process run."""
@@ -139,32 +139,35 @@ def test_palm_512_and_region_masks_equal_the_restatement():
 
 def test_region_assemble_equals_test_512_expressions():
     """On random uint8 stages (a 0 / 1 retain mask times the image, patches, composites with all-zero pixels and with pixels
-    whose channels sum past 255): the nine tensors equal test_512.py's torch expressions bit for bit."""
+    whose channels sum past 255): the nine tensors equal test_512.py's torch expressions bit for bit.  At 512 x 320, and at
+    20 x 12 with 3 and 2 parts of 5 x 5, where the 400 pixels and the style_input tail meet inside one block of 256."""
     import ctypes
     from training.tryon_regions import TryOnRegionBatch
     rng = np.random.default_rng(3)
-    n, ph, pw = 2, 128, 128
-    u8 = lambda *shape: rng.integers(0, 256, shape, dtype=np.uint8)
-    image, clothes, stick = u8(n, H, W, 3), u8(n, H, W, 3), u8(n, H, H, 3)
-    pad = lambda a: np.pad(a, ((0, 0), (0, 0), (LP, LP), (0, 0)), constant_values=255)
-    retain_mask = (rng.uniform(size=[n, H, H, 1]) < 0.5).astype(np.uint8)
-    patches, patches_l = u8(n, 10, ph, pw, 3), u8(n, 5, ph, pw, 3)
-    den_u, den_l = (u8(n, H, H, 3) * (rng.uniform(size=[n, H, H, 1]) < 0.6).astype(np.uint8) for _ in range(2))
-    den_u[0, :8, :8] = (128, 64, 64)                              # sums to 256: a wrapping uint8 sum would call it empty
-    stages = [dict(image=pad(image)[i], clothes=pad(clothes)[i], stick=stick[i], retain_mask=retain_mask[i],
-                   patches=patches[i].transpose(1, 2, 0, 3).reshape(ph, pw, 30), patches_lower=patches_l[i].transpose(1, 2, 0, 3).reshape(ph, pw, 15),
-                   denorm_upper=den_u[i], denorm_lower=den_l[i]) for i in range(n)]
-    want = FR.generator_inputs([FR.getitem(s) for s in stages], 'cuda')
-    N = _lib()
-    t = {k: torch.empty_like(want[k]) for k in TryOnRegionBatch.KEYS}
-    outs = (ctypes.c_void_p * 9)(*[t[k].data_ptr() for k in TryOnRegionBatch.KEYS])
-    ins = [_cu(a) for a in (image, clothes, retain_mask * pad(image), stick, patches, patches_l, den_u, den_l)]
-    N.check(N.lib().pasta_tryon_region_assemble(*[N.ptr(a) for a in ins], outs, n, H, W, 10, 5, ph, pw, N.stream()))
-    for k in TryOnRegionBatch.KEYS:
-        assert torch.equal(t[k], want[k]), k
-    assert tuple(t['style_input'].shape) == (n, 45, ph, pw) and tuple(t['pose'].shape) == (n, 6, H, H)
-    assert t['denorm_upper_mask'][0, 0, :8, :8].all() and 0 < float(t['denorm_upper_mask'].mean()) < 1
-    assert float(t['retain'].min()) == -1.0 and float(t['image'][..., :LP].min()) > 0.99          # zeros outside the mask, white padding
+    for h, w, pu, pl, ph, pw in ((H, W, 10, 5, 128, 128), (20, 12, 3, 2, 5, 5)):
+        n, lp = 2, (h - w) // 2
+        u8 = lambda *shape: rng.integers(0, 256, shape, dtype=np.uint8)
+        image, clothes, stick = u8(n, h, w, 3), u8(n, h, w, 3), u8(n, h, h, 3)
+        pad = lambda a: np.pad(a, ((0, 0), (0, 0), (lp, lp), (0, 0)), constant_values=255)
+        retain_mask = (rng.uniform(size=[n, h, h, 1]) < 0.5).astype(np.uint8)
+        patches, patches_l = u8(n, pu, ph, pw, 3), u8(n, pl, ph, pw, 3)
+        den_u, den_l = (u8(n, h, h, 3) * (rng.uniform(size=[n, h, h, 1]) < 0.6).astype(np.uint8) for _ in range(2))
+        den_u[0, :8, :8] = (128, 64, 64)                          # sums to 256: a wrapping uint8 sum would call it empty
+        stages = [dict(image=pad(image)[i], clothes=pad(clothes)[i], stick=stick[i], retain_mask=retain_mask[i],
+                       patches=patches[i].transpose(1, 2, 0, 3).reshape(ph, pw, 3 * pu),
+                       patches_lower=patches_l[i].transpose(1, 2, 0, 3).reshape(ph, pw, 3 * pl), denorm_upper=den_u[i], denorm_lower=den_l[i])
+                  for i in range(n)]
+        want = FR.generator_inputs([FR.getitem(s) for s in stages], 'cuda')
+        N = _lib()
+        t = {k: torch.empty_like(want[k]) for k in TryOnRegionBatch.KEYS}
+        outs = (ctypes.c_void_p * 9)(*[t[k].data_ptr() for k in TryOnRegionBatch.KEYS])
+        ins = [_cu(a) for a in (image, clothes, retain_mask * pad(image), stick, patches, patches_l, den_u, den_l)]
+        N.check(N.lib().pasta_tryon_region_assemble(*[N.ptr(a) for a in ins], outs, n, h, w, pu, pl, ph, pw, N.stream()))
+        for k in TryOnRegionBatch.KEYS:
+            assert torch.equal(t[k], want[k]), (h, k)
+        assert tuple(t['style_input'].shape) == (n, 3 * (pu + pl), ph, pw) and tuple(t['pose'].shape) == (n, 6, h, h)
+        assert t['denorm_upper_mask'][0, 0, :8, :8].all() and 0 < float(t['denorm_upper_mask'].mean()) < 1
+        assert float(t['retain'].min()) == -1.0 and float(t['image'][..., :lp].min()) > 0.99      # zeros outside the mask, white padding
 
 
 @pytest.fixture(scope='module')

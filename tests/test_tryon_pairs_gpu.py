@@ -167,6 +167,38 @@ def test_images_to_u8_equals_test_py_conversion():
     assert got.min() == 0 and got.max() == 255
 
 
+def test_pair_assemble_equals_test_py_expressions():
+    """The entry on its own, on random uint8 stages (composites with all-zero pixels and one pixel whose channels sum to 256):
+    the seven tensors equal test.py's torch expressions bit for bit.  N = 2, H = 20, P = 3 parts of 5 x 5: the 400 pixels do not
+    fill whole blocks of 256, so the image part and the style_input tail meet inside one block."""
+    import ctypes
+    from training.tryon_pairs import TryOnPairBatch
+    rng = np.random.default_rng(4)
+    n, h, parts, ph, pw = 2, 20, 3, 5, 5
+    u8 = lambda *shape: rng.integers(0, 256, shape, dtype=np.uint8)
+    retain_img = u8(n, h, h, 3) * (rng.uniform(size=[n, h, h, 1]) < 0.5).astype(np.uint8)
+    stick, patches, stick_patches = u8(n, h, h, 3), u8(n, parts, ph, pw, 3), u8(n, parts, ph, pw, 3)
+    den_u, den_l = (u8(n, h, h, 3) * (rng.uniform(size=[n, h, h, 1]) < 0.6).astype(np.uint8) for _ in range(2))
+    den_u[1, 7, 13] = (128, 64, 64)                               # sums to 256: a wrapping uint8 sum would call it empty
+    hwc = lambda a: a.transpose(1, 2, 0, 3).reshape(ph, pw, 3 * parts)
+    stages = [dict(retain_img=retain_img[i], stick=stick[i], patches=hwc(patches[i]), stick_patches=hwc(stick_patches[i]),
+                   denorm_upper=den_u[i], denorm_lower=den_l[i]) for i in range(n)]
+    want = PR.generator_inputs([PR.getitem(s) for s in stages], 'cuda')
+    N = _lib()
+    # contiguous NaN-filled outputs (the restated tensors keep the strides of getitem's transposed views)
+    t = {k: torch.full(want[k].shape, float('nan'), device='cuda') for k in TryOnPairBatch.KEYS}
+    outs = (ctypes.c_void_p * 7)(*[t[k].data_ptr() for k in TryOnPairBatch.KEYS])
+    ins = [_cu(a) for a in (retain_img, stick, patches, stick_patches, den_u, den_l)]
+    N.check(N.lib().pasta_tryon_pair_assemble(*[N.ptr(a) for a in ins], outs, n, h, parts, ph, pw, N.stream()))
+    for k in TryOnPairBatch.KEYS:
+        assert not torch.isnan(t[k]).any(), k                     # every element was written
+        assert t[k].shape == want[k].shape and torch.equal(t[k], want[k]), k
+    assert tuple(t['style_input'].shape) == (n, 6 * parts, ph, pw) and tuple(t['pose'].shape) == (n, 6, h, h)
+    assert t['denorm_upper_mask'][1, 0, 7, 13] == 1
+    for k in ('denorm_upper_mask', 'denorm_lower_mask'):
+        assert 0 < float(t[k].mean()) < 1, k                      # neither all 0 nor all 1
+
+
 @pytest.fixture(scope='module')
 def tree(tmp_path_factory):
     return make_pair_tree(tmp_path_factory.mktemp('pairs_gpu'))

@@ -2,7 +2,7 @@
 ``UvitonDatasetFull_512_test``: ``_load_raw_image`` :1605-1695, ``get_hand_mask`` / ``get_palm`` :1779-1827,
 ``draw_pose_from_cords`` :1831-1864, ``get_crop`` :1879-1965, ``normalize_full`` / ``normalize_upper`` / ``normalize_lower``
 :1967-2193, ``__getitem__`` :2196-2214) and of test_512.py's tensor expressions (:115-131) and panels (:144-188), one pair at a
-time.  The kernels of csrc/tryon_regions.hip and training/tryon_regions.py are held to it bit for bit
+time.  The region entries of csrc/tryon_pairs.hip and training/tryon_regions.py are held to it bit for bit
 (tests/test_tryon_512_gpu.py).
 
 Built from the primitives of tests/tryon_ref.py (rleFrPoly fill, box dilation, palm rule), tests/tryon_pairs_ref.py (erode)

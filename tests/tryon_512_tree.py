@@ -4,14 +4,12 @@ and json.  The pairs carry the oddities the loader and the preparation must surv
 torso, head and upper arms are missing while the person's exist), a person without an ankle (the shin is invalid here, where
 the 256 test set would fall back to the knee), a person without a knee (the thigh falls back to row 511), an empty ``people``
 on either side, a wrist beyond the canvas, a zero-length forearm, and hands (labels 14, 15) around the wrists and elbows."""
-import json
-import os
-
 import numpy as np
+
+from tryon_pairs_tree import PAIR_LIST, make_tree, write_person
 
 H, W = 512, 320
 SUBSETS = ('Zalando_512_320', 'Zalora_512_320', 'Deepfashion_512_320', 'MPV_512_320')
-PAIR_LIST = 'test_pairs_front_list_shuffle_0508.txt'
 # (sub-dataset, person, clothes): the order the data set must read them in
 PAIRS = [('Zalando_512_320', 'p0.jpg', 'c0.jpg'), ('Zalando_512_320', 'p1.jpg', 'c1.jpg'), ('Zalora_512_320', 'p2.jpg', 'c2.jpg'),
          ('Deepfashion_512_320', 'p3.jpg', 'c3.jpg'), ('MPV_512_320', 'p4.jpg', 'c4.jpg')]
@@ -57,31 +55,6 @@ def label_map(rng, kp):
     return lab
 
 
-def _write_one(root, ds, name, kp, rng):
-    import PIL.Image
-    stem = name[:-len('.jpg')]
-    img = rng.integers(0, 256, [H // 8, W // 8, 3]).repeat(8, 0).repeat(8, 1).astype(np.uint8)
-    PIL.Image.fromarray(img).save(os.path.join(root, ds, 'image', name), quality=95)
-    people = [] if kp is None else [{'pose_keypoints_2d': [float(v) for v in kp.reshape(-1)]}]
-    with open(os.path.join(root, ds, 'keypoints', stem + '_keypoints.json'), 'w') as f:
-        json.dump({'version': 1.3, 'people': people}, f)
-    lab = label_map(rng, kp if kp is not None else standing_person(rng))
-    PIL.Image.fromarray(lab, mode='L').save(os.path.join(root, ds, 'parsing', stem + '_label.png'))
-
-
 def make_512_tree(root, seed=0):
-    rng = np.random.default_rng(seed)
-    root = str(root)
-    for ds in SUBSETS:
-        for sub in ('image', 'keypoints', 'parsing'):
-            os.makedirs(os.path.join(root, ds, sub), exist_ok=True)
-    lists = {ds: [] for ds in SUBSETS}
-    for i, (ds, person, clothes) in enumerate(PAIRS):
-        kp_p, kp_c = pair_keypoints(i, rng)
-        _write_one(root, ds, person, kp_p, rng)
-        _write_one(root, ds, clothes, kp_c, rng)
-        lists[ds].append('%s %s\n' % (person, clothes))
-    for ds in SUBSETS:
-        with open(os.path.join(root, ds, PAIR_LIST), 'w') as f:
-            f.writelines(lists[ds])
-    return root
+    files = dict(shape=(H, W), block=8, label_map=label_map, any_person=standing_person)
+    return make_tree(root, seed, SUBSETS, PAIRS, pair_keypoints, files)

@@ -38,38 +38,44 @@ def pair_keypoints(i, rng):
     return person, donor
 
 
-def _write_one(root, ds, name, kp, rng, lower_six):
+def write_person(root, ds, name, kp, rng, shape, block, label_map, any_person, lower_six=False):
+    """A person's three files (shared with tryon_512_tree): a blocky random image of ``shape``, the key points (None: an empty
+    ``people``) and the label map, drawn around ``any_person(rng)`` where there are no key points."""
+    import PIL.Image
     stem = name[:-len('.jpg')]
-    img = rng.integers(0, 256, [H // 4, W // 4, 3]).repeat(4, 0).repeat(4, 1).astype(np.uint8)
-    PIL_save(img, os.path.join(root, ds, 'image', name), quality=95)
+    h, w = shape
+    img = rng.integers(0, 256, [h // block, w // block, 3]).repeat(block, 0).repeat(block, 1).astype(np.uint8)
+    PIL.Image.fromarray(img).save(os.path.join(root, ds, 'image', name), quality=95)
     people = [] if kp is None else [{'pose_keypoints_2d': [float(v) for v in kp.reshape(-1)]}]
     with open(os.path.join(root, ds, 'keypoints', stem + '_keypoints.json'), 'w') as f:
         json.dump({'version': 1.3, 'people': people}, f)
-    lab = label_map(rng, kp if kp is not None else person_keypoints(0, rng))
+    lab = label_map(rng, kp if kp is not None else any_person(rng))
     if lower_six:
         lab[180:215, 60:130] = 6                       # label 6 over the legs: lower garment of the person
         lab[105:140, 75:115] = 6                       # and over the torso
-    PIL_save(lab, os.path.join(root, ds, 'parsing', stem + '_label.png'), mode='L')
+    PIL.Image.fromarray(lab, mode='L').save(os.path.join(root, ds, 'parsing', stem + '_label.png'))
 
 
-def PIL_save(a, path, mode=None, **kw):
-    import PIL.Image
-    PIL.Image.fromarray(a, mode=mode).save(path, **kw)
-
-
-def make_pair_tree(root, seed=0):
+def make_tree(root, seed, subsets, pairs, pair_keypoints, files, person_lower_six=False):
+    """The sub-datasets' directories, every pair's person and donor through ``write_person(..., **files)`` (the person with
+    ``lower_six`` where ``person_lower_six``) and the pair lists (shared with tryon_512_tree)."""
     rng = np.random.default_rng(seed)
     root = str(root)
-    for ds in SUBSETS:
+    for ds in subsets:
         for sub in ('image', 'keypoints', 'parsing'):
             os.makedirs(os.path.join(root, ds, sub), exist_ok=True)
-    lists = {ds: [] for ds in SUBSETS}
-    for i, (ds, person, clothes) in enumerate(PAIRS):
+    lists = {ds: [] for ds in subsets}
+    for i, (ds, person, clothes) in enumerate(pairs):
         kp_p, kp_c = pair_keypoints(i, rng)
-        _write_one(root, ds, person, kp_p, rng, lower_six=True)
-        _write_one(root, ds, clothes, kp_c, rng, lower_six=False)
+        write_person(root, ds, person, kp_p, rng, lower_six=person_lower_six, **files)
+        write_person(root, ds, clothes, kp_c, rng, **files)
         lists[ds].append('%s %s\n' % (person, clothes))
-    for ds in SUBSETS:
+    for ds in subsets:
         with open(os.path.join(root, ds, PAIR_LIST), 'w') as f:
             f.writelines(lists[ds])
     return root
+
+
+def make_pair_tree(root, seed=0):
+    files = dict(shape=(H, W), block=4, label_map=label_map, any_person=lambda rng: person_keypoints(0, rng))
+    return make_tree(root, seed, SUBSETS, PAIRS, pair_keypoints, files, person_lower_six=True)
