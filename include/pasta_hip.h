@@ -272,7 +272,10 @@ int pasta_conv2d_plan(const pasta_conv_desc* d, int launch_flags, int* tile, int
  * conv_wgrad1x1_bf16x6_kernel (split-bf16; 1x1, stride 1, planes of a multiple of 32 pixels, >= 16 channels), 5
  * wgrad1x1_fewcin_kernel (round 4: 1x1, <= 8 input channels, planes of a multiple of 4 pixels: one bandwidth-bound fp32 pass over dy), 6
  * conv_wgrad3x3s2_pieces_kernel (round 5: kernel 3's shapes with pad 0 and x given as PASTA_LAYOUT_PIECES16: the x halo is copied into a
- * [pixel][channel] LDS image and the stride-2 tap operands are gathered by ds_read_b64_tr_b16, no split and no permutes). */
+ * [pixel][channel] LDS image and the stride-2 tap operands are gathered by ds_read_b64_tr_b16, no split and no permutes).
+ * The K slices of kernels 2 - 4 can be read off pasta_conv2d_wgrad_workspace, and tests/conv16_cases.py does: the workspace is 2 x 256 floats
+ * (the operands' partial maxima) followed by one slab per slice of groups x kh x kw x A x B floats, A and B the two per-group channel counts
+ * rounded up to the channel tile -- 64, or 128 for kernel 4 with more than 64 channels on both sides.  This layout is part of the contract. */
 int pasta_conv2d_wgrad_plan(const pasta_conv_desc* d, int* kernel);
 
 /* y = conv(x, w).  w is the PyTorch-layout weight ([C_out, C_in/g, kh, kw], or
