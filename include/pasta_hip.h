@@ -647,6 +647,48 @@ int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image
                                 void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Per-batch preparation of the 512 x 320 try-on TRAINING samples (training/tryon_regions.py, FullBodyRegionBatchBuilder).
+ * The reference ships no 512 training set: the rules are this project's own, and one rule governs them -- the generator is
+ * trained on exactly the inputs test_512.py will later feed it.  A sample is the entries' above full-body preparation of the
+ * pair (person, person), with the 256 training set's three extras on top:
+ *   1. stick figure of thickness 5 and radius 5 from the unshifted key points, palm boxes 35 and 20 on the 512 square
+ *      (pasta_pose_stickman_thick_u8, pasta_palm_mask_square_u8);
+ *   2. the upper garment is labels 5, 6, 7 and the lower garment labels 9, 12, both the person's own;
+ *   3. key points are shifted by the padding in float64 (host side), get_crop has no knee-without-ankle fall-back;
+ *   4. all ten parts of the upper garment, parts 0, 6, 7, 8, 9 of the lower one; every warped-back mask is eroded 5 x 5
+ *      (pasta_patch_composite_eroded_u8); style_input has 45 channels;
+ *   5. real_img is the padded photograph (padding 255) and gt_parsing the 256 training set's label rule;
+ *   6. erase = (arm[2] + arm[3] + resize(erase mask, 512 x 512)) > 0 in uint8 wrapping arithmetic, arm[k] the ERODED 0 / 1
+ *      mask of arm part ARM_PARTS[k] = 2, 3, 4, 5 from the upper composite (the fixed pick the reference's random.seed(1)
+ *      makes at 256), resize the restated cv2.resize of pasta_tryon_assemble;
+ *   7. the two denormalised inputs are zeroed where erase is 1 before x / 127.5 - 1, their masks are the channel sum > 0 of
+ *      the erased image.
+ * ------------------------------------------------------------------------- */
+/* From the person's image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H], in one pass: retain_mask = shoes(18,
+ * 19) + palm + head(1, 2, 4, 13) (0 / 1) and gt_parsing = upper(5, 6, 7) + 2 lower(9, 12) + 3 hands(14, 15) + 4 legs(16, 17) +
+ * 5 neck(10), [N, H, H]; upper_img / upper_mask = labels 5, 6, 7 (image, 255) and lower_img / lower_mask = labels 9, 12,
+ * [N, H, H, 3], padding 255 in the images before the masks are applied.  The four garment pointers are the halves of the
+ * stacked [2N, H, H, 3] image and mask tensors patch_pipeline.normalize_region_batch takes (upper garments, then lower).
+ * These are pasta_tryon_masks_u8's rules: the two training sets name the same labels, and the entry is its launch. */
+int pasta_tryon_train_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain_mask,
+                                      uint8_t* gt_parsing, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                                      uint8_t* lower_mask, int N, int H, int W, void* stream);
+
+/* Rules 5-7 and the float conversions: the nine fp32 NCHW tensors of FullBodyBatch.KEYS, in that order, through outputs (a
+ * HOST array of 9 device pointers), shaped as pasta_tryon_assemble's with style_input [N,3(P+P_lower),ph,pw] = the P
+ * upper-garment patches (channel 3k + c of part k) || the P_lower lower-garment patches, as pasta_tryon_region_assemble
+ * forms it.  image [N,H,W,3]; stick, denorm_upper, denorm_lower [N,H,H,3]; retain_mask, gt_parsing [N,H,H];
+ * patches [N,P,ph,pw,3], patches_lower [N,P_lower,ph,pw,3]; part_masks [N,P,H,H]: the eroded 0 / 1 part masks of the upper
+ * composite, of which planes arm_a and arm_b (4 and 5: arm[2] and arm[3]) enter the erase mask; erase_masks
+ * [N,mh_max,mw_max] with each sample's (h, w) in erase_hw [N][2] int32.  Every pixel is the body pasta_tryon_assemble runs.
+ * pw a multiple of 4 (four patch pixels per thread). */
+int pasta_tryon_train_region_assemble(const uint8_t* image, const uint8_t* stick, const uint8_t* retain_mask, const uint8_t* gt_parsing,
+                                      const uint8_t* patches, const uint8_t* patches_lower, const uint8_t* denorm_upper,
+                                      const uint8_t* denorm_lower, const uint8_t* part_masks, int arm_a, int arm_b,
+                                      const uint8_t* erase_masks, const int32_t* erase_hw, float* const* outputs, int N, int H, int W,
+                                      int P, int P_lower, int ph, int pw, int mh_max, int mw_max, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The training run's snapshot image (setup_snapshot_image_grid, denorm_clothes, combine_parts and save_image_grid,
  * training/training_loop_wo_flow_fullbody.py:36-209): a gnum x gnum mix-and-match grid, cell = row * gnum + col, row the
  * person (pose, retain, M_inv) and col the clothes donor; gap = gnum / 3: rows < gap swap the trousers, rows < 2 gap the

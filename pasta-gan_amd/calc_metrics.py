@@ -5,7 +5,7 @@ registers: the paired-reconstruction metrics ``recon_full`` and ``recon2k``).
     python calc_metrics.py --network snapshot.pkl --metrics recon2k --data held_out_tree --gpus 8
 
 Without --data the snapshot's own ``training_set_kwargs`` name the tree; --data names another one of the same layout (a held-out
-tree).  When the snapshot lies in a training run's directory (one with training_options.json), the result is also appended to
+tree; a tree of ``*_512_320`` folders is read as the 512 x 320 training set).  When the snapshot lies in a training run's directory (one with training_options.json), the result is also appended to
 that directory's ``metric-<name>.jsonl``.  --network must name a local file: URLs are refused (nothing is downloaded).  One
 process per GPU; for more than one GPU fresh processes are spawned, each loading the snapshot itself."""
 
@@ -86,7 +86,8 @@ def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, wor
     if data is not None:
         if not os.path.isdir(data):
             ctx.fail('--data: %r is not a directory' % data)
-        args.dataset_kwargs = dnnlib.EasyDict(class_name='training.dataset.UvitonDatasetFull', path=data)
+        from training.dataset import training_set_class
+        args.dataset_kwargs = dnnlib.EasyDict(class_name=training_set_class(data), path=data)
     else:
         import legacy
         with open(network_pkl, 'rb') as f:

@@ -7,6 +7,7 @@
 //   pasta_image_grid_tile_u8         save_image_grid's conversion and tiling (:182-203) into the uint8 canvas.
 // Cell = row * gnum + col: row is the person (pose, retain, M_inv), col the clothes donor.
 #include "common.h"
+#include "tryon_common.h"      // Px4, load_px4, store4
 
 #pragma clang fp contract(off)      // the warp-back coordinates must round as csrc/patches.hip's do
 #include "patch_erode.h"
@@ -40,18 +41,6 @@ __device__ __forceinline__ float mul_rounded(int a, float b) { return (float)((d
 
 // torch's x / 127.5 - 1 on the GPU: x * (1 / 127.5f) - 1, as csrc/tryon_common.h's to_unit
 __device__ __forceinline__ float grid_to_unit(int v) { return mul_rounded(v, 1.0f / 127.5f) - 1.0f; }
-
-struct Px4 { uint8_t v[12]; };      // four RGB pixels of a uint8 HWC image
-
-__device__ __forceinline__ Px4 load_px4(const uint8_t* __restrict__ p) {     // p is 4-byte aligned: pixel index a multiple of 4
-    union { uint3 w; Px4 px; } u;
-    u.w = *reinterpret_cast<const uint3*>(p);
-    return u.px;
-}
-
-__device__ __forceinline__ void store4(float* __restrict__ p, float a, float b, float c, float d) {
-    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-}
 
 struct GridOut {
     float *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask, *denorm_lower_mask, *style_input, *pose, *retain;

@@ -1,7 +1,9 @@
 // Device helpers of the try-on preparation shared by csrc/tryon_inputs.hip (the training set) and csrc/tryon_pairs.hip (both sets
 // of test pairs): separately rounded arithmetic, the restated rleFrPoly fill of a quadrilateral, the palm rule with its box
 // dilations, torch's x / 127.5 - 1 and test.py's conversion of a generated value to a byte (also csrc/recon_metrics.hip), the
-// pixel of a padded square, the per-pixel body of the three assemble kernels and the copy of an entry's output-pointer array.
+// pixel of a padded square, the per-pixel body of the assemble kernels, the erase rule with its restated cv2.resize and the
+// per-pixel body of the two training sets' assemble kernels, four-pixel loads and stores (also csrc/train_grid.hip) and the copy
+// of an entry's output-pointer array.
 #pragma once
 #include "common.h"
 
@@ -172,6 +174,76 @@ __device__ __forceinline__ void tryon_pixel(const TryonOut& o, int n, int pix, i
     }
     o.denorm_upper_mask[p] = su > 0 ? 1.f : 0.f;
     o.denorm_lower_mask[p] = sl > 0 ? 1.f : 0.f;
+}
+
+// ---- the training sets: erase mask and the photograph ----
+
+// cv2.resize(INTER_LINEAR) on uint8, one axis: source index and the two 11-bit coefficients of destination index d.
+__device__ __forceinline__ void resize_taps(int d, double scale, int size, bool clamp_coord, int& s0, int& s1, int& a0, int& a1) {
+    float f = (float)(tr_rounded(((double)d + 0.5) * scale) - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (clamp_coord) {                         // columns: coordinates outside the source are pinned with weight (1, 0)
+        if (s < 0) { f = 0.f; s = 0; }
+        if (s >= size - 1) { f = 0.f; s = size - 1; }
+    }
+    a0 = (int)rintf((1.f - f) * 2048.f);
+    a1 = (int)rintf(f * 2048.f);
+    s0 = s < 0 ? 0 : s > size - 1 ? size - 1 : s;          // rows: the row index is clamped, the weights are kept
+    s1 = s + 1 < 0 ? 0 : s + 1 > size - 1 ? size - 1 : s + 1;
+}
+
+// Pixel `pix` of sample n of what both training sets give the loop beyond tryon_pixel: the erase mask
+// erase = (arm_a + arm_b + resize(erase mask, H x H)) in uint8 (wrapping) > 0, which zeroes the two denormalised inputs, the
+// photograph (real_img = o.image), retain = real_img * mask - (1 - mask) from the 0 / 1 retain mask, and gt_parsing.
+// arm_a, arm_b: the sample's two [H, H] arm-part masks; erase_src [N, mh_max, mw_max] with the sample's own size in erase_hw.
+__device__ __forceinline__ void train_pixel(const TryonOut& o, int n, int pix, int H, int W, int lp, const uint8_t* __restrict__ image,
+                                            const uint8_t* __restrict__ stick, const uint8_t* __restrict__ retain_mask,
+                                            const uint8_t* __restrict__ gt, const uint8_t* __restrict__ den_u,
+                                            const uint8_t* __restrict__ den_l, const uint8_t* __restrict__ arm_a,
+                                            const uint8_t* __restrict__ arm_b, const uint8_t* __restrict__ erase_src,
+                                            const int32_t* __restrict__ erase_hw, int mh_max, int mw_max) {
+    const int HH = H * H;
+    const SquarePixel s = square_pixel(n, pix, H, W, lp);
+    const int y = s.y, x = s.c + lp;
+    const int64_t p = (int64_t)n * HH + pix;
+
+    const int mh = erase_hw[2 * n], mw = erase_hw[2 * n + 1];
+    int sx0, sx1, ax0, ax1, sy0, sy1, by0, by1;
+    resize_taps(x, (double)mw / H, mw, true, sx0, sx1, ax0, ax1);
+    resize_taps(y, (double)mh / H, mh, false, sy0, sy1, by0, by1);
+    const uint8_t* m = erase_src + (int64_t)n * mh_max * mw_max;
+    const int r0 = m[(int64_t)sy0 * mw_max + sx0] * ax0 + m[(int64_t)sy0 * mw_max + sx1] * ax1;
+    const int r1 = m[(int64_t)sy1 * mw_max + sx0] * ax0 + m[(int64_t)sy1 * mw_max + sx1] * ax1;
+    int rs = (int)(((int64_t)r0 * by0 + (int64_t)r1 * by1 + (1 << 21)) >> 22);
+    rs = rs < 0 ? 0 : rs > 255 ? 255 : rs;
+    const int sum8 = (arm_a[pix] + arm_b[pix] + rs) & 255;
+    const int keep = sum8 > 0 ? 0 : 1;
+
+    const int rm = retain_mask[p];
+    const float label = (float)gt[p];
+    float real[3], ret[3];
+    for (int ch = 0; ch < 3; ch++) {           // real_img is the photograph; retain = real_img * mask - (1 - mask) from the 0 / 1 mask
+        real[ch] = to_unit(s.inside ? image[s.src * 3 + ch] : 255);
+        ret[ch] = tr_rounded((float)rm * real[ch]) - (float)(uint8_t)(1 - rm);
+    }
+    tryon_pixel(o, n, pix, HH, ret, stick + p * 3, den_u + p * 3, den_l + p * 3, keep);
+    for (int ch = 0; ch < 3; ch++) o.image[((int64_t)n * 3 + ch) * HH + pix] = real[ch];
+    o.gt_parsing[p] = label;
+}
+
+// ---- four pixels per thread ----
+
+struct Px4 { uint8_t v[12]; };      // four RGB pixels of a uint8 HWC image
+
+__device__ __forceinline__ Px4 load_px4(const uint8_t* __restrict__ p) {     // p is 4-byte aligned: pixel index a multiple of 4
+    union { uint3 w; Px4 px; } u;
+    u.w = *reinterpret_cast<const uint3*>(p);
+    return u.px;
+}
+
+__device__ __forceinline__ void store4(float* __restrict__ p, float a, float b, float c, float d) {
+    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
 }
 
 }  // namespace pasta

@@ -6,7 +6,8 @@
 //                           csrc/tryon_pairs.hip's kernel;
 //   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556);
 //   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456); its
-//                           per-pixel body is csrc/tryon_common.h's tryon_pixel, shared with the test pairs' kernel.
+//                           per-pixel body is csrc/tryon_common.h's train_pixel (the erase rule with the restated resize, then
+//                           tryon_pixel), shared with the 512 x 320 training kernel of csrc/tryon_pairs.hip.
 // Every entry does a whole batch in one launch.  The reference does this on the host with OpenCV, pycocotools and skimage.
 // What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
 // DESIGN.md section 9): cv2.line(thickness=2), pycocotools' rleFrPoly and cv2.resize(INTER_LINEAR) on uint8.
@@ -89,21 +90,6 @@ __global__ __launch_bounds__(256) void tryon_masks_kernel(const uint8_t* __restr
 
 // ---- erase mask and float conversions ----
 
-// cv2.resize(INTER_LINEAR) on uint8, one axis: source index and the two 11-bit coefficients of destination index d.
-__device__ __forceinline__ void resize_taps(int d, double scale, int size, bool clamp_coord, int& s0, int& s1, int& a0, int& a1) {
-    float f = (float)(tr_rounded(((double)d + 0.5) * scale) - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (clamp_coord) {                         // columns: coordinates outside the source are pinned with weight (1, 0)
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= size - 1) { f = 0.f; s = size - 1; }
-    }
-    a0 = (int)rintf((1.f - f) * 2048.f);
-    a1 = (int)rintf(f * 2048.f);
-    s0 = s < 0 ? 0 : s > size - 1 ? size - 1 : s;          // rows: the row index is clamped, the weights are kept
-    s1 = s + 1 < 0 ? 0 : s + 1 > size - 1 ? size - 1 : s + 1;
-}
-
 __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ stick,
                                                              const uint8_t* __restrict__ retain_mask, const uint8_t* __restrict__ gt,
                                                              const uint8_t* __restrict__ norm_img, const uint8_t* __restrict__ norm_lower,
@@ -124,33 +110,9 @@ __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __re
         }
         return;
     }
-    const SquarePixel s = square_pixel(n, pix, H, W, lp);
-    const int y = s.y, x = s.c + lp;
-    const int64_t p = (int64_t)n * HH + pix;
-
-    // erase = (hand_mask[2] + hand_mask[3] + resize(acgpn)) in uint8 (wrapping) > 0
-    const int mh = erase_hw[2 * n], mw = erase_hw[2 * n + 1];
-    int sx0, sx1, ax0, ax1, sy0, sy1, by0, by1;
-    resize_taps(x, (double)mw / H, mw, true, sx0, sx1, ax0, ax1);
-    resize_taps(y, (double)mh / H, mh, false, sy0, sy1, by0, by1);
-    const uint8_t* m = erase_src + (int64_t)n * mh_max * mw_max;
-    const int r0 = m[(int64_t)sy0 * mw_max + sx0] * ax0 + m[(int64_t)sy0 * mw_max + sx1] * ax1;
-    const int r1 = m[(int64_t)sy1 * mw_max + sx0] * ax0 + m[(int64_t)sy1 * mw_max + sx1] * ax1;
-    int rs = (int)(((int64_t)r0 * by0 + (int64_t)r1 * by1 + (1 << 21)) >> 22);
-    rs = rs < 0 ? 0 : rs > 255 ? 255 : rs;
-    const int sum8 = (arm_masks[((int64_t)n * 4 + 2) * HH + pix] + arm_masks[((int64_t)n * 4 + 3) * HH + pix] + rs) & 255;
-    const int keep = sum8 > 0 ? 0 : 1;
-
-    const int rm = retain_mask[p];
-    const float label = (float)gt[p];
-    float real[3], ret[3];
-    for (int ch = 0; ch < 3; ch++) {           // real_img is the photograph; retain = real_img * mask - (1 - mask) from the 0 / 1 mask
-        real[ch] = to_unit(s.inside ? image[s.src * 3 + ch] : 255);
-        ret[ch] = tr_rounded((float)rm * real[ch]) - (float)(uint8_t)(1 - rm);
-    }
-    tryon_pixel(o, n, pix, HH, ret, stick + p * 3, den_u + p * 3, den_l + p * 3, keep);
-    for (int ch = 0; ch < 3; ch++) o.image[((int64_t)n * 3 + ch) * HH + pix] = real[ch];
-    o.gt_parsing[p] = label;
+    // the erase rule on arm_masks[2] and arm_masks[3], the photograph, gt_parsing and csrc/tryon_common.h's tryon_pixel
+    train_pixel(o, n, pix, H, W, lp, image, stick, retain_mask, gt, den_u, den_l, arm_masks + ((int64_t)n * 4 + 2) * HH,
+                arm_masks + ((int64_t)n * 4 + 3) * HH, erase_src, erase_hw, mh_max, mw_max);
 }
 
 }  // namespace pasta

@@ -13,6 +13,12 @@
 //   pasta_tryon_region_masks_u8      retain image and the upper and lower garment, each taken from the donor or the person as
 //                                    the region says (:1631-1690);
 //   pasta_tryon_region_assemble      __getitem__ (:2196-2214) and test_512.py's conversions (:115-131) into the nine fp32 tensors.
+// The 512 x 320 TRAINING samples (this project's own: the reference ships no 512 training set) are that set's full-body
+// preparation of the pair (person, person) with the 256 training set's photograph, gt_parsing and erase mask on top:
+//   pasta_tryon_train_region_masks_u8  retain mask, gt_parsing and both garments of the person, in the stacked [2N] layout
+//                                      normalize_region_batch takes (csrc/tryon_inputs.hip's label-masks launch: the two
+//                                      training sets name the same labels);
+//   pasta_tryon_train_region_assemble  the erase mask from two eroded arm-part masks and the nine fp32 tensors of the loop.
 // Both masks entries launch tryon_pair_masks_kernel and both assemble entries tryon_pair_assemble_kernel: the 256 pairs are
 // the 512 rules with "upper from the donor, lower from the person" fixed, label 6 added to the lower garment, stick patches as
 // the second patch list and no image / clothes tensors.  The flags are kernel arguments, uniform per launch.
@@ -129,6 +135,37 @@ __global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t*
             o.image[((int64_t)n * 3 + ch) * HH + pix] = person[ch];
             o.clothes[((int64_t)n * 3 + ch) * HH + pix] = donor[ch];
         }
+}
+
+// ---- the nine tensors of the training loop at 512 x 320 ----
+
+// style_input as tryon_pair_assemble_kernel forms it from the two per-part lists, four patch pixels per thread (12-byte loads,
+// 16-byte stores); every pixel of the square is csrc/tryon_common.h's train_pixel, the 256 training kernel's own body, with the
+// eroded masks of parts arm_a and arm_b of the upper composite (part_masks [N, PA, H, H]) as the two arm masks.
+__global__ __launch_bounds__(256) void tryon_train_region_assemble_kernel(
+    const uint8_t* __restrict__ image, const uint8_t* __restrict__ stick, const uint8_t* __restrict__ retain_mask,
+    const uint8_t* __restrict__ gt, const uint8_t* __restrict__ patches_a, const uint8_t* __restrict__ patches_b,
+    const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l, const uint8_t* __restrict__ part_masks, int arm_a, int arm_b,
+    const uint8_t* __restrict__ erase_src, const int32_t* __restrict__ erase_hw, TryonOut o, int H, int W, int lp, int PA, int PB, int ph,
+    int pw, int mh_max, int mw_max) {
+    const int n = blockIdx.y;
+    const int HH = H * H;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= HH) {
+        const int q = (pix - HH) * 4;          // ph * pw is a multiple of 4: the four pixels lie in the patch
+        if (q >= ph * pw) return;
+        const int CS = 3 * (PA + PB);
+        for (int k = 0; k < PA + PB; k++) {
+            const uint8_t* src = k < PA ? patches_a + (((int64_t)n * PA + k) * ph * pw + q) * 3 : patches_b + (((int64_t)n * PB + k - PA) * ph * pw + q) * 3;
+            const Px4 px = load_px4(src);
+            for (int c = 0; c < 3; c++)
+                store4(o.style_input + ((int64_t)n * CS + 3 * k + c) * ph * pw + q, to_unit(px.v[c]), to_unit(px.v[3 + c]), to_unit(px.v[6 + c]),
+                       to_unit(px.v[9 + c]));
+        }
+        return;
+    }
+    train_pixel(o, n, pix, H, W, lp, image, stick, retain_mask, gt, den_u, den_l, part_masks + ((int64_t)n * PA + arm_a) * HH,
+                part_masks + ((int64_t)n * PA + arm_b) * HH, erase_src, erase_hw, mh_max, mw_max);
 }
 
 // ---- generated images to uint8 ----
@@ -248,6 +285,41 @@ extern "C" int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* 
     hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, donor_image, retain_img, stick, patches,
                        patches_lower, denorm_upper, denorm_lower, o, H, W, (H - W) / 2, P, P_lower, ph, pw);
     return launch_status("tryon_region_assemble");
+}
+
+extern "C" int pasta_tryon_train_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain_mask,
+                                                 uint8_t* gt_parsing, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                                                 uint8_t* lower_mask, int N, int H, int W, void* stream) {
+    PASTA_CHECK(image && parsing && palm && retain_mask && gt_parsing && upper_img && upper_mask && lower_img && lower_mask,
+                "tryon_train_region_masks_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "tryon_train_region_masks_u8: bad shape");
+    // the 256 training set's rules for all six outputs (labels 5, 6, 7 and 9, 12; no label 6 in the lower garment): its launch
+    return pasta_tryon_masks_u8(image, parsing, palm, retain_mask, gt_parsing, upper_img, lower_img, upper_mask, lower_mask, N, H, W, stream);
+}
+
+extern "C" int pasta_tryon_train_region_assemble(const uint8_t* image, const uint8_t* stick, const uint8_t* retain_mask,
+                                                 const uint8_t* gt_parsing, const uint8_t* patches, const uint8_t* patches_lower,
+                                                 const uint8_t* denorm_upper, const uint8_t* denorm_lower, const uint8_t* part_masks,
+                                                 int arm_a, int arm_b, const uint8_t* erase_masks, const int32_t* erase_hw,
+                                                 float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw, int mh_max,
+                                                 int mw_max, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && stick && retain_mask && gt_parsing && patches && patches_lower && denorm_upper && denorm_lower && part_masks &&
+                erase_masks && erase_hw && outputs, "tryon_train_region_assemble: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && P >= 1 && P <= 64 && P_lower >= 1 && P_lower <= 64 &&
+                ph >= 1 && pw >= 4 && pw % 4 == 0 && ph * pw <= H * H && mh_max >= 1 && mw_max >= 1,
+                "tryon_train_region_assemble: bad shape (pw a multiple of 4)");
+    PASTA_CHECK(arm_a >= 0 && arm_a < P && arm_b >= 0 && arm_b < P, "tryon_train_region_assemble: arm parts %d, %d of %d", arm_a, arm_b, P);
+    TryonOut o{};
+    float** f[9] = {&o.image, &o.style_input, &o.retain, &o.pose, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask,
+                    &o.denorm_lower_mask, &o.gt_parsing};          // FullBodyBatch.KEYS; real_img is o.image
+    const int missing = take_outputs(outputs, f, 9);
+    PASTA_CHECK(missing < 0, "tryon_train_region_assemble: output %d is null", missing);
+    dim3 grid((unsigned)((H * H + ph * pw / 4 + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_train_region_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, stick, retain_mask, gt_parsing,
+                       patches, patches_lower, denorm_upper, denorm_lower, part_masks, arm_a, arm_b, erase_masks, erase_hw, o, H, W,
+                       (H - W) / 2, P, P_lower, ph, pw, mh_max, mw_max);
+    return launch_status("tryon_train_region_assemble");
 }
 
 extern "C" int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream) {

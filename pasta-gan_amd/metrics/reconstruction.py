@@ -2,7 +2,7 @@
 and parsing terms train -- and its fine-tuned image and predicted parsing are scored against the person's photograph and label
 map: L1, PSNR and SSIM over the bytes test.py would write, mIoU and pixel accuracy over the parsing classes.
 
-Per batch: ``FullBodyBatchBuilder`` (training/tryon_batch.py), G in eval mode with ``noise_mode='const'`` and z drawn per item from
+Per batch: the data set's training builder (training/tryon_batch.py ``builder_for``), G in eval mode with ``noise_mode='const'`` and z drawn per item from
 ``np.random.RandomState(raw_idx)``, then the two statistics kernels of csrc/recon_metrics.hip.  Nothing but the statistics is
 kept: five 8-byte words per item and the confusion matrix.
 
@@ -90,13 +90,13 @@ def compute_partials(opts):
     """This rank's items -- (i * num_gpus + rank) % num_items as the reference's metrics take theirs, without the repeats of the
     wrap-around, so that each item is scored once -- scored into device partials, combined over the ranks by one all_reduce."""
     from training import dataset as dataset_module
-    from training.tryon_batch import FullBodyBatchBuilder
+    from training.tryon_batch import builder_for
     dataset = dnnlib.util.construct_class_by_name(**opts.dataset_kwargs)
     num_items = len(dataset)
     rounds = (num_items - 1) // opts.num_gpus + 1
     subset = [i * opts.num_gpus + opts.rank for i in range(rounds) if i * opts.num_gpus + opts.rank < num_items]
     G = copy.deepcopy(opts.G).eval().requires_grad_(False).to(opts.device)
-    builder = FullBodyBatchBuilder(opts.device)
+    builder = builder_for(dataset, opts.device)
     loader = torch.utils.data.DataLoader(dataset, sampler=subset, batch_size=opts.batch_size, collate_fn=dataset_module.collate,
                                          **opts.data_loader_kwargs)
     partials = new_partials(num_items, NUM_CLASSES, opts.device)      # a rank without items still takes part in the exchange

@@ -18,6 +18,7 @@ import torch
 
 import dnnlib
 from training import training_loop_wo_flow_fullbody as training_loop
+from training.dataset import training_set_class
 
 #----------------------------------------------------------------------------
 
@@ -60,8 +61,8 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
 
     # Dataset: data, cond, subset, mirror (:115-155)
     assert isinstance(data, str)
-    args.training_set_kwargs = dnnlib.EasyDict(class_name='training.dataset.UvitonDatasetFull', path=data, use_labels=False, max_size=None,
-                                               xflip=False)
+    # a tree of *_512_320 folders (and no Zalando_256_192) is the 512 x 320 training set, whose batches carry 45 patch channels
+    args.training_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(data), path=data, use_labels=False, max_size=None, xflip=False)
     args.data_loader_kwargs = dnnlib.EasyDict(pin_memory=True, num_workers=0)
     try:
         training_set = dnnlib.util.construct_class_by_name(**args.training_set_kwargs)
@@ -76,7 +77,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     if metrics_data is not None:
         if not metrics:
             raise UserError('--metrics_data needs --metrics')
-        args.metric_set_kwargs = dnnlib.EasyDict(class_name='training.dataset.UvitonDatasetFull', path=metrics_data, use_labels=False,
+        args.metric_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(metrics_data), path=metrics_data, use_labels=False,
                                                  max_size=None, xflip=False)
         try:
             metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
@@ -118,6 +119,8 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     # mixed precision as the reference enables it (:195-196): the three highest resolutions of G and of D in fp16
     config = training_loop.fashion_config(channel_base=int(spec.fmaps * 32768), d_fp16_res=3, mbstd_group_size=spec.mbstd, img_resolution=res)
     config.G_kwargs.mapping_kwargs.num_layers = spec.map
+    if args.training_set_kwargs.class_name.endswith('UvitonDatasetFull_512'):
+        config.G_kwargs.patch_channels = 45     # ten parts of the upper garment and five of the lower one (training/tryon_regions.py)
     config.G_kwargs.synthesis_kwargs.use_noise = bool(use_noise_const_branch)
     config.G_opt_kwargs.lr = config.D_opt_kwargs.lr = spec.lrate
     config.loss_kwargs.update(r1_gamma=spec.gamma, l1_weight=l1_weight or 0, vgg_weight=vgg_weight or 0, pl_weight=pl_weight or 0,
@@ -292,6 +295,7 @@ def main(ctx, outdir, dry_run, **config_kwargs):
     print()
     print(f'Output directory:   {args.run_dir}')
     print(f'Training data:      {args.training_set_kwargs.path}')
+    print(f'Data set class:     {args.training_set_kwargs.class_name.rsplit(".", 1)[-1]}')
     print(f'Training duration:  {args.total_kimg} kimg')
     print(f'Number of GPUs:     {args.num_gpus}')
     print(f'Number of images:   {args.training_set_kwargs.max_size}')

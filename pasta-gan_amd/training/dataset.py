@@ -7,7 +7,9 @@ mask, float conversions) runs for a whole batch on the GPU in ``training.tryon_b
 a list of raw samples into the batch the builder takes.  Only directory data sets are supported, as in the reference.
 The test pairs (``UvitonDatasetV19_test``, dataset.py:997-1525) follow the same design: raw pairs out, ``collate_pairs``, and
 ``training.tryon_pairs.TryOnPairBatchBuilder`` on the GPU; so do the 512 x 320 pairs with a change region
-(``UvitonDatasetFull_512_test``, dataset.py:1528-2214) with ``training.tryon_regions.TryOnRegionBatchBuilder``."""
+(``UvitonDatasetFull_512_test``, dataset.py:1528-2214) with ``training.tryon_regions.TryOnRegionBatchBuilder``.
+``UvitonDatasetFull_512`` is this project's own: the training layout at 512 x 320, which the reference does not ship, prepared
+by ``training.tryon_regions.FullBodyRegionBatchBuilder``."""
 
 import json
 import os
@@ -102,13 +104,20 @@ class UvitonDatasetFull(Dataset):
     ``erase_mask`` uint8 [h, w] (channel 0 of the ACGPN mask file ``raw_idx % count``, whatever its size) and ``raw_idx``.
     Key points stay float64 because the reference truncates and offsets them in float64."""
 
+    _sub_datasets = SUB_DATASETS
+    _vis_sources = (('Zalando_256_192', 'image'), ('Deepfashion_256_192', os.path.join('image', 'train')))     # :461-472, in this order
+
+    @staticmethod
+    def _label_name(dataset, name):
+        return name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')
+
     def __init__(self, path, resolution=None, **super_kwargs):
         self._path = path
         if not os.path.isdir(self._path):
             raise IOError('Path must point to a directory')
         self._type = 'dir'
         self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
-        for dataset in SUB_DATASETS:
+        for dataset in self._sub_datasets:
             with open(os.path.join(self._path, dataset, PAIR_LIST), 'r') as f:
                 for person in f.readlines():
                     if not person.strip():
@@ -116,15 +125,14 @@ class UvitonDatasetFull(Dataset):
                     person = person.strip().split()[0]
                     self._image_fnames.append(os.path.join(dataset, 'image', person))
                     self._kpt_fnames.append(os.path.join(dataset, 'keypoints', person.replace('.jpg', '_keypoints.json')))
-                    label = person.replace('.jpg', '.png') if dataset == 'MPV_256_192' else person.replace('.jpg', '_label.png')
-                    self._parsing_fnames.append(os.path.join(dataset, 'parsing', label))
+                    self._parsing_fnames.append(os.path.join(dataset, 'parsing', self._label_name(dataset, person)))
 
         vis_index = []
         for image_name in sorted(os.listdir(os.path.join(self._path, 'train_img_vis'))):         # :461-472
-            if os.path.exists(os.path.join(self._path, 'Zalando_256_192', 'image', image_name)):
-                vis_index.append(self._image_fnames.index(os.path.join('Zalando_256_192', 'image', image_name)))
-            elif os.path.exists(os.path.join(self._path, 'Deepfashion_256_192', 'image', 'train', image_name)):
-                vis_index.append(self._image_fnames.index(os.path.join('Deepfashion_256_192', 'image', 'train', image_name)))
+            for dataset, folder in self._vis_sources:
+                if os.path.exists(os.path.join(self._path, dataset, folder, image_name)):
+                    vis_index.append(self._image_fnames.index(os.path.join(dataset, folder, image_name)))
+                    break
         self._vis_index = vis_index
 
         acgpn_dir = os.path.join(self._path, 'train_random_mask_acgpn')
@@ -157,6 +165,28 @@ class UvitonDatasetFull(Dataset):
 
     def __getitem__(self, idx):
         return self.load_raw(self._raw_idx[idx])
+
+
+class UvitonDatasetFull_512(UvitonDatasetFull):
+    """The training layout at 512 x 320 (this project's own; the reference ships only the 512 x 320 test set):
+    ``Zalando_512_320``, ``Zalora_512_320``, ``Deepfashion_512_320`` and ``MPV_512_320``, in this order, each with ``image/``,
+    ``keypoints/``, ``parsing/`` and the training list of ``UvitonDatasetFull``; label maps are ``parsing/<stem>_label.png`` in
+    all four, as in ``UvitonDatasetFull_512_test``; ``train_img_vis/`` names people of ``Zalando_512_320/image`` or
+    ``Deepfashion_512_320/image/train``.  Raw samples as ``UvitonDatasetFull``'s, so ``collate`` serves both."""
+
+    _sub_datasets = SUB_DATASETS_512
+    _vis_sources = (('Zalando_512_320', 'image'), ('Deepfashion_512_320', os.path.join('image', 'train')))
+
+    @staticmethod
+    def _label_name(dataset, name):
+        return name.replace('.jpg', '_label.png')
+
+
+def training_set_class(path):
+    """The class name of the training data set a tree holds: the 512 x 320 one when ``Zalando_512_320`` is present and
+    ``Zalando_256_192`` is not, else the 256 x 192 one (also for a tree with neither, whose error names the 256 layout)."""
+    is_512 = os.path.isdir(os.path.join(path, SUB_DATASETS_512[0])) and not os.path.isdir(os.path.join(path, SUB_DATASETS[0]))
+    return 'training.dataset.UvitonDatasetFull_512' if is_512 else 'training.dataset.UvitonDatasetFull'
 
 #----------------------------------------------------------------------------
 

@@ -234,7 +234,8 @@ def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
 
 
-def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joints, upper_from_donor, lower_from_donor, box_factor=2):
+def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joints, upper_from_donor, lower_from_donor, box_factor=2,
+                           want_part_masks=False):
     """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch
     on the GPU.  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image, 3-channel
     mask) followed by the N lower garments.  ``donor_joints`` / ``person_joints`` [N, 18, 3] float64 (host), already shifted by
@@ -244,14 +245,16 @@ def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joint
     person the garment was taken from (one launch for the images, one for the masks) and back with the PERSON's M_inv through
     the eroded composite, every part 5 x 5.  A part whose forward matrix is missing is zeros; a part whose M_inv is missing
     is skipped.  Returns (patches [N,10,h,w,3], patches_lower [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper,
-    denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), donor_valid, person_valid [N,10] bool)."""
+    denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), donor_valid, person_valid [N,10] bool).
+    ``donor_joints is person_joints`` (the training samples: everyone wears their own garments) solves the matrices once.
+    ``want_part_masks``: a tenth value, the eroded 0 / 1 masks [N,10,H,W] of the upper composite's parts."""
     garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
     assert n2 == 2 * n and garment_mask.shape == garment_img.shape
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    fwd_d, _, valid_d = part_matrices(donor_joints, width, height, box_factor, x_pad=0)
     fwd_p, back, valid_p = part_matrices(person_joints, width, height, box_factor, x_pad=0)
+    fwd_d, valid_d = (fwd_p, valid_p) if donor_joints is person_joints else part_matrices(donor_joints, width, height, box_factor, x_pad=0)[::2]
     fwd_u, valid_u = (fwd_d, valid_d) if upper_from_donor else (fwd_p, valid_p)
     fwd_l, valid_l = (fwd_d, valid_d) if lower_from_donor else (fwd_p, valid_p)
     low = list(LOWER_PARTS_512)
@@ -264,7 +267,8 @@ def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joint
     split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
     (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
 
-    den_u, _ = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS)
+    den_u, part_masks = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS, want_part_masks)
     den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
     m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
-    return patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p
+    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p)
+    return out + (part_masks,) if want_part_masks else out

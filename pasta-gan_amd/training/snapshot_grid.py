@@ -4,7 +4,7 @@ row r is a person, column c a clothes donor; with gap = gnum // 3 the first thir
 the whole outfit, the last the top.  The reference warps and erodes every cell on the host (about ten thousand OpenCV calls at
 gnum = 23) and keeps fp32 tensors of all cells on the device; here
 
-    setup    FullBodyBatchBuilder.build(keep_stages=True) of the gnum people, then pasta_grid_composite_eroded_u8 twice
+    setup    the training builder's build(keep_stages=True) of the gnum people, then pasta_grid_composite_eroded_u8 twice
              (upper, lower) for all cells                                                  (csrc/train_grid.hip)
     inputs   pasta_grid_assemble: the fp32 tensors G_ema takes, for one minibatch of cells
     save     pasta_image_grid_tile_u8 per minibatch into one uint8 canvas, one copy to the host, PIL writes the PNG
@@ -22,6 +22,7 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import collate
+from training.tryon_batch import shift_keypoints
 
 ERODE_RADIUS = 2            # cv2.erode(..., np.ones((5, 5))) of every warped-back mask, upper and lower (:63, :91, :98)
 INPUT_KEYS = ['denorm_upper_input', 'denorm_lower_input', 'denorm_upper_mask', 'denorm_lower_mask', 'style_input', 'pose', 'retain']
@@ -45,9 +46,9 @@ class SnapshotGrid:
         if len(vis) < gnum:
             raise IOError('the snapshot grid needs %d people listed in train_img_vis, the data set has %d' % (gnum, len(vis)))
         raw = collate([training_set[i] for i in vis[:gnum]])       # grid_indices = training_set.vis_index (:113-116)
-        return cls(raw, builder.build(raw, keep_stages=True).stages, torch.device(device), gnum, builder.box_factor)
+        return cls(raw, builder.build(raw, keep_stages=True).stages, torch.device(device), gnum, builder)
 
-    def __init__(self, raw, stages, device, gnum, box_factor=2):
+    def __init__(self, raw, stages, device, gnum, builder):
         self.device, self.gnum, self.cells = device, gnum, gnum * gnum
         image = torch.as_tensor(raw['image']).to(device)
         g, H, W, _ = image.shape
@@ -70,10 +71,16 @@ class SnapshotGrid:
         # float64 matrices normalize_batch inverts, not the float32 copy it returns.  The reference skips a part on
         # M_inv.sum() == 0 (:87), its stand-in for "get_crop found no quadrilateral"; part_matrices' valid flag says that
         # directly (a present matrix whose entries happen to sum to zero is used here and skipped there).
-        _, back, valid = patch_pipeline.part_matrices(np.asarray(raw['keypoints'], np.float64), H, H, box_factor)
+        # The builder says how it formed them: 256 x 192 adds the padding inside get_crop, 512 x 320 shifts the key points first.
+        keypoints = np.asarray(raw['keypoints'], np.float64)
+        if builder.shifted:
+            keypoints = shift_keypoints(keypoints, lp)
+        _, back, valid = patch_pipeline.part_matrices(keypoints, H, H, builder.box_factor, x_pad=builder.x_pad,
+                                                      shin_fallback=builder.shin_fallback)
         inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(g, pu, 9)
         upper_src, lower_src = cell_sources(gnum)
-        lower_parts = np.arange(pu - pl, pu)                       # parts 6..9 are also cut from the lower garment (:76)
+        lower_parts = np.asarray(builder.lower_parts)              # the parts also cut from the lower garment (:76: 6..9 at 256 x 192)
+        assert len(lower_parts) == pl
         parts_u, parts_l = np.arange(pu, dtype=np.int32), np.arange(pl, dtype=np.int32)
         index_u = (upper_src.reshape(-1, 1) * pu + parts_u).astype(np.int32)
         index_l = (g * pu + lower_src.reshape(-1, 1) * pl + parts_l).astype(np.int32)

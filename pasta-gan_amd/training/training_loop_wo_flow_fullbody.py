@@ -292,12 +292,12 @@ class TrainingStep:
 def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs):
     """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263)."""
     from training import dataset as dataset_module
-    from training.tryon_batch import FullBodyBatchBuilder
+    from training.tryon_batch import builder_for
     training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
     sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed)
     loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
                                          collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
-    builder = FullBodyBatchBuilder(device)
+    builder = builder_for(training_set, device)
     return training_set, builder, (builder.build(raw) for raw in loader)
 
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
@@ -307,7 +307,7 @@ def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0
     """Without ``run_dir``: run ``total_iters`` iterations and write nothing.  Without ``training_set_kwargs`` the data is
     synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
     path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
-    ``training.tryon_batch.FullBodyBatchBuilder``.
+    ``training.tryon_batch.builder_for``'s builder (``UvitonDatasetFull_512``: the 512 x 320 one).
     With ``run_dir`` (and a data set): the reference's loop until ``total_kimg`` (``training_run`` below); ``total_iters`` is unused.
     ``metrics`` (names of metrics/metric_main.py) are evaluated on G_ema after every network snapshot, on ``metric_set_kwargs``
     (default: the training set's)."""

@@ -11,8 +11,9 @@ do per sample on the host, as a few launches per batch:
 The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
-``upload_person`` (upload and checks), ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32
-tensors of a KEYS list with their pointer array) and ``shift_keypoints``."""
+``upload_person`` (upload and checks), ``upload_erase`` (the training sets' erase masks), ``device_tables`` (stick and palm
+tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their pointer array) and ``shift_keypoints``.
+``builder_for`` picks the training builder of a data set: this one, or training/tryon_regions.py's at 512 x 320."""
 
 import ctypes
 import math
@@ -91,6 +92,17 @@ def upload_person(raw, device, who, prefix=''):
     return image, parsing, keypoints
 
 
+def upload_erase(raw, device, n):
+    """The erase masks of a batch of ``training.dataset.collate`` -> (masks uint8 [N, h_max, w_max], their sizes int32 [N, 2]) on
+    ``device``, checked: every size lies within the stacked tensor."""
+    erase = torch.as_tensor(raw['erase_masks']).to(device, non_blocking=True).contiguous()
+    erase_hw = torch.as_tensor(raw['erase_hw'], dtype=torch.int32).to(device, non_blocking=True).contiguous()
+    hw = np.asarray(raw['erase_hw'])
+    assert erase.dtype == torch.uint8 and erase.ndim == 3 and erase.shape[0] == n and hw.shape == (n, 2) and (hw >= 1).all()
+    assert (hw[:, 0] <= erase.shape[1]).all() and (hw[:, 1] <= erase.shape[2]).all()
+    return erase, erase_hw
+
+
 def upload_pair(raw, device, who):
     """(image, parsing, key points) of the persons, then of the clothes donors, of a batch of ``training.dataset.collate_pairs``."""
     person, donor = upload_person(raw, device, who), upload_person(raw, device, who, 'clothes_')
@@ -142,6 +154,11 @@ class FullBodyBatch:
 class FullBodyBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate`` -> FullBodyBatch on ``device``."""
 
+    # how the warp-back matrices of this builder's stages are formed (training/snapshot_grid.py forms them again per cell):
+    # the parts also cut from the lower garment, part_matrices' x_pad and shin_fallback, and whether the key points are shifted
+    # by the padding in float64 first
+    lower_parts, x_pad, shin_fallback, shifted = (6, 7, 8, 9), 32, False, False
+
     def __init__(self, device, box_factor=2):
         self.device = torch.device(device)
         self.box_factor = box_factor
@@ -149,12 +166,8 @@ class FullBodyBatchBuilder:
     def build(self, raw, keep_stages=False):
         dev = self.device
         image, parsing, keypoints = upload_person(raw, dev, 'FullBodyBatchBuilder')
-        erase = torch.as_tensor(raw['erase_masks']).to(dev, non_blocking=True).contiguous()
-        erase_hw = torch.as_tensor(raw['erase_hw'], dtype=torch.int32).to(dev, non_blocking=True).contiguous()
         n, H, W, _ = image.shape
-        hw = np.asarray(raw['erase_hw'])
-        assert erase.dtype == torch.uint8 and erase.ndim == 3 and hw.shape == (n, 2) and (hw >= 1).all()
-        assert (hw[:, 0] <= erase.shape[1]).all() and (hw[:, 1] <= erase.shape[2]).all()
+        erase, erase_hw = upload_erase(raw, dev, n)
         limbs, joints, quads, present = device_tables(keypoints, keypoints, (H - W) // 2, dev)
         u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)
@@ -182,3 +195,14 @@ class FullBodyBatchBuilder:
                           denorm_upper=den_u, denorm_lower=den_l, arm_masks=arm, M_invs=m_invs, norm_clothes_mask=norm_mask.contiguous(),
                           norm_clothes_mask_lower=norm_mask_lower.contiguous())
         return FullBodyBatch(t, stages, image)
+
+
+def builder_for(training_set, device):
+    """The builder that prepares the batches of ``training_set``: by the data set's class."""
+    from training import dataset
+    if isinstance(training_set, dataset.UvitonDatasetFull_512):
+        from training.tryon_regions import FullBodyRegionBatchBuilder
+        return FullBodyRegionBatchBuilder(device)
+    if isinstance(training_set, dataset.UvitonDatasetFull):
+        return FullBodyBatchBuilder(device)
+    raise TypeError('no training batch builder for %s' % type(training_set).__name__)

@@ -11,13 +11,24 @@ in four loader processes, as a few launches per batch:
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
-formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621)."""
+formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621).
+
+``FullBodyRegionBatchBuilder`` prepares TRAINING batches at 512 x 320 (``training.dataset.UvitonDatasetFull_512``).  The
+reference has no 512 training set, so the rule is this project's own: the generator is trained on exactly the inputs
+test_512.py will later feed it.  A sample is the full-body preparation above of the pair (person, person), plus the 256
+training set's photograph as target, ``gt_parsing`` and erase mask (include/pasta_hip.h lists the rules):
+
+    pasta_pose_stickman_thick_u8, pasta_palm_mask_square_u8     as above
+    pasta_tryon_train_region_masks_u8     retain mask, gt_parsing and the person's own two garments in one pass
+    patch_pipeline.normalize_region_batch the matrices solved once, the eroded part masks of the upper composite kept
+    pasta_tryon_train_region_assemble     the erase mask and the nine fp32 tensors of FullBodyBatch.KEYS"""
 
 import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
-from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_pair
+from training.tryon_batch import (FullBodyBatch, allocator, device_tables, output_tensors, shift_keypoints, upload_erase, upload_pair,
+                                  upload_person)
 from training.tryon_pairs import TryOnPairBatch
 
 PALM_BOXES = (35, 20)       # get_hand_mask of the 512 set: upper arm 35 x 35, forearm 20 x 20 (dataset.py:1790, :1795)
@@ -78,3 +89,52 @@ class TryOnRegionBatchBuilder:
                           mask_patches_lower=mask_patches_l, denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, clothes_valid=valid_d,
                           person_valid=valid_p)
         return TryOnRegionBatch(t, raw['person_name'], raw['clothes_name'], stages)
+
+
+class FullBodyRegionBatchBuilder:
+    """``build(raw_batch)``: a batch of ``training.dataset.collate`` at 512 x 320 -> FullBodyBatch on ``device``, which
+    TrainingStep.run consumes as the 256 builder's.  ``stages`` (``keep_stages``) carry the 256 builder's names, so that
+    training/snapshot_grid.py has one code path."""
+
+    # see FullBodyBatchBuilder: parts 0, 6..9 are also cut from the lower garment; key points shifted in float64, x_pad = 0
+    lower_parts, x_pad, shin_fallback, shifted = patch_pipeline.LOWER_PARTS_512, 0, False, True
+
+    def __init__(self, device, box_factor=2):
+        self.device = torch.device(device)
+        self.box_factor = box_factor
+
+    def build(self, raw, keep_stages=False):
+        dev = self.device
+        image, parsing, kp = upload_person(raw, dev, 'FullBodyRegionBatchBuilder')
+        n, H, W, _ = image.shape
+        lp = (H - W) // 2
+        erase, erase_hw = upload_erase(raw, dev, n)
+        limbs, joints, quads, present = device_tables(kp, kp, lp, dev)
+        u8 = allocator(torch.uint8, dev)
+        stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)
+        garment_img, garment_mask = u8(2 * n, H, H, 3), u8(2 * n, H, H, 3)  # the upper garments, then the lower garments
+        lib, P = _native.lib(), _native.ptr
+        with torch.cuda.device(dev):
+            s = _native.stream()
+            _native.check(lib.pasta_pose_stickman_thick_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
+            _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
+            _native.check(lib.pasta_tryon_train_region_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), P(garment_img[:n]),
+                                                                P(garment_mask[:n]), P(garment_img[n:]), P(garment_mask[n:]), n, H, W, s))
+        shifted = shift_keypoints(kp, lp)
+        patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, part_masks = patch_pipeline.normalize_region_batch(
+            garment_img, garment_mask, shifted, shifted, True, True, self.box_factor, want_part_masks=True)
+        pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
+        arm_a, arm_b = patch_pipeline.ARM_PARTS[2], patch_pipeline.ARM_PARTS[3]
+        t, outs = output_tensors(FullBodyBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.pasta_tryon_train_region_assemble(P(image), P(stick), P(retain_mask), P(gt), P(patches), P(patches_l), P(den_u),
+                                                                P(den_l), P(part_masks), arm_a, arm_b, P(erase), P(erase_hw), outs, n, H, W,
+                                                                pu, pl, ph, pw, int(erase.shape[1]), int(erase.shape[2]), _native.stream()))
+        stages = None
+        if keep_stages:
+            hwc = lambda x: x.permute(0, 2, 3, 1, 4).reshape(n, ph, pw, -1).contiguous()       # parts along the channel axis, as at 256
+            stages = dict(stick=stick, palm=palm, retain_mask=retain_mask, gt_parsing=gt, upper_img=garment_img[:n], lower_img=garment_img[n:],
+                          upper_mask=garment_mask[:n], lower_mask=garment_mask[n:], norm_img=hwc(patches), norm_img_lower=hwc(patches_l),
+                          denorm_upper=den_u, denorm_lower=den_l, arm_masks=part_masks[:, list(patch_pipeline.ARM_PARTS)].contiguous(),
+                          M_invs=m_invs, norm_clothes_mask=hwc(mask_patches), norm_clothes_mask_lower=hwc(mask_patches_l))
+        return FullBodyBatch(t, stages, image)
