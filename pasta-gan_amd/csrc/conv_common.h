@@ -457,8 +457,150 @@ struct WgradParams {
     int chunks_total;       // ceil(rows_total / CHH) * qblocks
     int ksplit;             // K slices
     int a_tiles, b_tiles, tap_groups_r, tap_groups_s;
-    int xcd_order;          // split weight-gradient kernels: workgroup order (0: K slice fastest; 1: see wgrad_decode)
+    int xcd_order;          // split weight-gradient kernels: workgroup order (0: K slice fastest; 1: see wgrad_workgroup)
     int l_pieces;           // conv_wgrad3x3s2_pieces_kernel: L is PASTA_LAYOUT_PIECES16 (pieces.hip), l_amax the producer's bound row
 };
+
+//------------------------------------------------------------------------------------
+// What the weight-gradient kernels share (conv_wgrad_f32.h, conv_wgrad_bf16x6.h).  Every kernel keeps its own staging -- which pixels a thread
+// fetches, in which order, with which validity -- and its own product loop; where its workgroup is, which chunks its K slice holds, how eight
+// fp32 values become pieces in LDS and where the chunk walk stands is here, once, and leaves every kernel's device assembly as it was
+// (profiles/wgrad_single_source_resources.txt).  The store of a sub-tile into the slab and the slab sum of the reductions stay in their kernels:
+// as shared functions they changed the assembly, and timed against their own blocks they missed the allowance (the notes at those blocks;
+// profiles/wgrad_single_source_ab.txt).
+
+// Workgroup -> (K slice, b tile, a tile, group) of the split kernels.  The workgroups that read the same pixels are the tiles (a, b) of one
+// K slice.  Order 0 (the original): K slice fastest -- those workgroups are ksplit apart in the grid (on one XCD when ksplit is a multiple
+// of 8, but dispatched far from each other).  Order 1: the slice index modulo 8 fastest, then the tile, then the rest of the slice
+// index: the tiles of a slice are 8 apart -- the same XCD (workgroups go round-robin to the eight XCDs), dispatched together.
+__device__ __forceinline__ void wgrad_workgroup(const WgradParams& p, int& ks, int& bt, int& at, int& g) {
+    int bid = blockIdx.x;
+    if (p.xcd_order && (p.ksplit & 7) == 0) {
+        const int lo = bid & 7; bid >>= 3;
+        const int tiles = p.a_tiles * p.b_tiles;
+        const int tile = bid % tiles; bid /= tiles;
+        const int hi = bid % (p.ksplit >> 3); bid /= (p.ksplit >> 3);
+        ks = hi * 8 + lo; bt = tile % p.b_tiles; at = tile / p.b_tiles; g = bid;
+        return;
+    }
+    ks = bid % p.ksplit; bid /= p.ksplit;
+    bt = bid % p.b_tiles; bid /= p.b_tiles;
+    at = bid % p.a_tiles; bid /= p.a_tiles;
+    g = bid;
+}
+
+// Chunks [c_begin, c_end) of K slice ks: the slices differ by at most one chunk.  The products are 32-bit and unsigned: the host refuses a launch
+// whose chunks_total * (ksplit + 1) does not fit (conv_igemm.hip, the PASTA_CHECK in front of the launch; the small-cin plan stays far below it).
+__device__ __forceinline__ void wgrad_slice(int chunks_total, int ksplit, int ks, int& c_begin, int& c_end) {
+    c_begin = (int)(((unsigned)chunks_total * (unsigned)ks) / (unsigned)ksplit); c_end = (int)(((unsigned)chunks_total * (unsigned)(ks + 1)) / (unsigned)ksplit);
+}
+
+// PASTA_MATH_F16X3: the operand scales from the tensors' partial maxima, and what the slab is multiplied by on the way out; ones otherwise.
+template <int NP>
+__device__ __forceinline__ void wgrad_scales(const WgradParams& p, float& s_scale, float& l_scale, float& out_scale) {
+    s_scale = 1.f; l_scale = 1.f; out_scale = 1.f;
+    if constexpr (Arith<NP>::f16x3) {
+        float is_, il_;
+        scale_from_amax(amax_of_parts(p.s_amax), s_scale, is_);
+        scale_from_amax(amax_of_parts(p.l_amax), l_scale, il_);
+        out_scale = is_ * il_;
+    }
+}
+
+// two float4 halves, each possibly invalid -> 0, as eight values
+__device__ __forceinline__ void masked8(float4 h0, float4 h1, bool ok0, bool ok1, float (&vals)[8]) {
+    vals[0] = ok0 ? h0.x : 0.f; vals[1] = ok0 ? h0.y : 0.f; vals[2] = ok0 ? h0.z : 0.f; vals[3] = ok0 ? h0.w : 0.f;
+    vals[4] = ok1 ? h1.x : 0.f; vals[5] = ok1 ? h1.y : 0.f; vals[6] = ok1 ? h1.z : 0.f; vals[7] = ok1 ? h1.w : 0.f;
+}
+
+// eight fp32 values -> Arith<NP>::npw packed pieces of eight 16-bit elements (split-bf16: v = q1 + q2 + q3, each the bf16 of what is left;
+// PASTA_MATH_F16X3: (h, l) of v * scale; 16-bit storage: the element itself), piece i stored at dst + i * piece_stride
+template <int NP, int IO>
+__device__ __forceinline__ void wgrad_split_store8(const float (&vals)[8], __bf16* dst, int piece_stride, float scale) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    constexpr int NPW = Arith<NP>::npw;
+    uint32_t q1[4], q2[4], q3[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if constexpr (Arith<NP>::f16x3) {
+            f16_split2_direct(vals[2 * j] * scale, vals[2 * j + 1] * scale, q1[j], q2[j]);
+            continue;
+        }
+        f32x2 v = {vals[2 * j], vals[2 * j + 1]};
+        uint32_t w = io_pack2<IO>(vals[2 * j], vals[2 * j + 1]);
+        q1[j] = w;
+        if constexpr (NP >= 2) {
+            v[0] -= __builtin_bit_cast(float, w << 16);
+            v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
+            w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+            q2[j] = w;
+        }
+        if constexpr (NP >= 3) {
+            v[0] -= __builtin_bit_cast(float, w << 16);
+            v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
+            q3[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+        }
+    }
+    *(uint4*)(dst) = make_uint4(q1[0], q1[1], q1[2], q1[3]);
+    if constexpr (NPW >= 2) *(uint4*)(dst + piece_stride) = make_uint4(q2[0], q2[1], q2[2], q2[3]);
+    if constexpr (NPW >= 3) *(uint4*)(dst + 2 * piece_stride) = make_uint4(q3[0], q3[1], q3[2], q3[3]);
+}
+
+// Where the chunk walk of the ring kernels stands: the chunks go down a column block (pp fastest), then through the column blocks of an image,
+// then through the images.  A position is decoded ONCE per K slice (two divisions by run-time values) and then advanced, for the current
+// chunk and for the prefetched one (a decode per chunk and per prefetch was ~200 scalar instructions per chunk in front of the wave's matrix
+// instructions).
+struct WgradChunkPos { int n, qb, pp; };        // sample, column block, row
+// (out-parameters by reference: returned by value, or as member functions, the same arithmetic changes the kernels' register allocation)
+__device__ __forceinline__ void wgrad_chunk_at(const WgradParams& p, int ch, WgradChunkPos& c) {
+    const int per_img = p.P * p.qblocks;
+    c.n = ch / per_img;
+    const int rem = ch - c.n * per_img;
+    c.qb = rem / p.P; c.pp = rem - c.qb * p.P;
+}
+__device__ __forceinline__ void wgrad_chunk_next(const WgradParams& p, const WgradChunkPos& c, WgradChunkPos& next) {
+    next.pp = c.pp + 1; next.qb = c.qb; next.n = c.n;
+    if (next.pp == p.P) { next.pp = 0; next.qb = c.qb + 1; if (next.qb == p.qblocks) { next.qb = 0; next.n = c.n + 1; } }
+}
+
+// The three halo rows of a chunk live in a ring in LDS: image row y (>= -1) in slot y mod 3; `row` (0..2) slots after slot0
+__device__ __forceinline__ int ring_slot(int y) { return (y + 3) % 3; }
+__device__ __forceinline__ int ring_wrap(int slot0, int row) { return slot0 + row >= 3 ? slot0 + row - 3 : slot0 + row; }
+
+// one accumulator sub-tile to zero (the loops over a kernel's sub-tiles stay in the kernel: zeroed by one call for a whole array, the stride-1
+// kernel's assembly differs in 1950 of 13964 lines, main loop included)
+__device__ __forceinline__ void wgrad_zero(f32x16& acc) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.f;
+}
+
+// The arithmetic of a launch of the split weight-gradient kernels as their template arguments: f(NP, IO) with std::integral_constants.
+// np = pieces per operand (3: six products, 2: three, 1: one, NP_F16X3); 16-bit storage is always one product.
+template <class F>
+static void wgrad_arith_dispatch(int np, int io, F&& f) {
+    using std::integral_constant;
+    typedef integral_constant<int, IO_F32> F32;
+    if (io == IO_BF16)       f(integral_constant<int, 1>{}, integral_constant<int, IO_BF16>{});
+    else if (io == IO_F16)   f(integral_constant<int, 1>{}, integral_constant<int, IO_F16>{});
+    else if (np == 1)        f(integral_constant<int, 1>{}, F32{});
+    else if (np == 2)        f(integral_constant<int, 2>{}, F32{});
+    else if (np == NP_F16X3) f(integral_constant<int, NP_F16X3>{}, F32{});
+    else                     f(integral_constant<int, 3>{}, F32{});
+}
+
+// Chunk geometry of a weight gradient over rows of Q pixels: a chunk is kp lattice pixels, (kp >> cw_log2) rows of (1 << cw_log2) columns, the
+// width a power of two that shrinks to cover Q (keep_width: it stays kp).
+struct WgradChunks { int cw_log2, qblocks, chunks_total; };
+static WgradChunks wgrad_chunks(int kp, int rows_total, int Q, bool keep_width = false) {
+    WgradChunks c;
+    int cw = kp, lg = kp == 32 ? 5 : 4;
+    while (cw > 1 && cw / 2 >= Q && !keep_width) { cw /= 2; lg--; }
+    const int chh = kp / cw;
+    c.cw_log2 = lg;
+    c.qblocks = (Q + cw - 1) / cw;
+    c.chunks_total = ((rows_total + chh - 1) / chh) * c.qblocks;
+    return c;
+}
 
 }  // namespace pasta

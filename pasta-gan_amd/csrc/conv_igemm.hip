@@ -221,19 +221,17 @@ static WgradPlan plan_wgrad(int N, int P, int Q, int G, int Ag, int Bg, int kh, 
     // chunk = KP lattice pixels (CHH rows x CW columns, CW a power of two covering Q when Q is small); halve the
     // chunk when the L halo of a 32-pixel chunk is too wide for the register-prefetch pipeline (stride 2)
     int kp = 32;
+    w.rows_total = N * P;
     for (;;) {
-        int cw = kp, lg = kp == 32 ? 5 : 4;
-        while (cw > 1 && cw / 2 >= Q && !wide16) { cw /= 2; lg--; }
-        const int chh = kp / cw;
+        const WgradChunks c = wgrad_chunks(kp, w.rows_total, Q, wide16);
+        const int cw = 1 << c.cw_log2, chh = kp >> c.cw_log2;
         const int lwid = (cw - 1) * st + w.TS;
-        w.cw_log2 = lg; w.kp = kp; w.npos = chh * w.TR * lwid;
+        w.cw_log2 = c.cw_log2; w.qblocks = c.qblocks; w.chunks_total = c.chunks_total;
+        w.kp = kp; w.npos = chh * w.TR * lwid;
         if (w.npos <= 128 || kp == 16) break;
         kp = 16;
     }
     const int cw = 1 << w.cw_log2, chh = w.kp >> w.cw_log2;
-    w.rows_total = N * P;
-    w.qblocks = (Q + cw - 1) / cw;
-    w.chunks_total = ((w.rows_total + chh - 1) / chh) * w.qblocks;
     const int64_t base_blocks = (int64_t)G * w.a_tiles * w.b_tiles * w.tgr * w.tgs;
     int64_t ks = (512 + base_blocks / 2) / base_blocks;  // one full wave of workgroups at 2 per CU (register-limited)
     if (ks > w.chunks_total / 8) ks = w.chunks_total / 8; // at least eight chunks per slice

@@ -5,7 +5,7 @@
 // declared here.  The kernel headers hold templates and host predicates only, so including them instantiates nothing; the few
 // non-template kernels are fenced by PASTA_TU_PACK / PASTA_TU_WGRAD_F32 and defined by exactly one unit.  What the forward-type kernels share
 // -- the epilogue of a 32 x 32 sub-tile (conv_store_subtile) and the choice of <NP, IO, ISC> for a launch (conv_arith_dispatch) -- is in
-// conv_common.h.
+// conv_common.h, and so is what the weight-gradient kernels share (wgrad_slice, wgrad_split_store8, WgradChunkPos, wgrad_arith_dispatch, ...).
 #pragma once
 #include "conv_common.h"
 

@@ -4,19 +4,12 @@
 
 namespace pasta {
 
-// LAUNCH_(NP, IO) for the runtime piece count and storage type
-#define PASTA_NP(LAUNCH_)                                                                                                  \
-    do { if (p.io == IO_BF16) { LAUNCH_(1, IO_BF16); } else if (p.io == IO_F16) { LAUNCH_(1, IO_F16); }                    \
-         else if (np == 1) { LAUNCH_(1, IO_F32); } else if (np == 2) { LAUNCH_(2, IO_F32); } else if (np == NP_F16X3) { LAUNCH_(NP_F16X3, IO_F32); } else { LAUNCH_(3, IO_F32); } } while (0)
-
 void tu_wgrad1x1(int np, int WA, const WgradParams& p, int64_t blocks, hipStream_t s) {
-    const int npw = np == NP_F16X3 ? 2 : np;
-    const size_t lds = (size_t)(npw * 64 * 40) * 2 * 2 * WA;        // S and L images of 64 WA (= 64 WB) channels
-#define PASTA_L(NP_, IO_)                                                                                                     \
-    if (WA == 2) hipLaunchKernelGGL((conv_wgrad1x1_bf16x6_kernel<2, 2, NP_, IO_>), dim3((unsigned)blocks), dim3(256), lds, s, p); \
-    else         hipLaunchKernelGGL((conv_wgrad1x1_bf16x6_kernel<1, 1, NP_, IO_>), dim3((unsigned)blocks), dim3(256), lds, s, p)
-    PASTA_NP(PASTA_L);
-#undef PASTA_L
+    wgrad_arith_dispatch(np, p.io, [&](auto np_c, auto io_c) {
+        constexpr int NP = decltype(np_c)::value, IO = decltype(io_c)::value, NPW = Arith<NP>::npw;
+        const size_t lds = WA == 2 ? Wgrad1x1Tile<2, 2>::lds_bytes(NPW) : Wgrad1x1Tile<1, 1>::lds_bytes(NPW);
+        if (WA == 2) hipLaunchKernelGGL((conv_wgrad1x1_bf16x6_kernel<2, 2, NP, IO>), dim3((unsigned)blocks), dim3(256), lds, s, p);
+        else         hipLaunchKernelGGL((conv_wgrad1x1_bf16x6_kernel<1, 1, NP, IO>), dim3((unsigned)blocks), dim3(256), lds, s, p);
+    });
 }
-#undef PASTA_NP
 }  // namespace pasta

@@ -1,29 +1,8 @@
-// Split-bf16 weight-gradient kernels for 3x3 convolutions: stride 1 (conv_wgrad3x3_bf16x6_kernel) and stride 2 (conv_wgrad3x3s2_bf16x6_kernel).  Instantiated by conv_tu_wgrad_{3x3,3x3s2,1x1}.hip (conv_launch.h).
+// Split-bf16 weight-gradient kernels: 3x3 stride 1 (conv_wgrad3x3_bf16x6_kernel), 3x3 stride 2 (conv_wgrad3x3s2_bf16x6_kernel, conv_wgrad3x3s2_pieces_kernel), 1x1 (conv_wgrad1x1_bf16x6_kernel); what they share is in conv_common.h.  Instantiated by conv_tu_wgrad_{3x3,3x3s2,1x1}.hip (conv_launch.h).
 #pragma once
 #include "conv_common.h"
 
 namespace pasta {
-
-// Workgroup -> (K slice, b tile, a tile, group).  The workgroups that read the same pixels are the tiles (a, b) of one K slice.
-// Order 0 (the original): K slice fastest -- those workgroups are ksplit apart in the grid (on one XCD when ksplit is a multiple
-// of 8, but dispatched far from each other).  Order 1: the slice index modulo 8 fastest, then the tile, then the rest of the slice
-// index: the tiles of a slice are 8 apart -- the same XCD (workgroups go round-robin to the eight XCDs), dispatched together.
-__device__ __forceinline__ void wgrad_decode(const WgradParams& p, int& ks, int& bt, int& at, int& g) {
-    int bid = blockIdx.x;
-    if (p.xcd_order && (p.ksplit & 7) == 0) {
-        const int lo = bid & 7; bid >>= 3;
-        const int tiles = p.a_tiles * p.b_tiles;
-        const int tile = bid % tiles; bid /= tiles;
-        const int hi = bid % (p.ksplit >> 3); bid /= (p.ksplit >> 3);
-        ks = hi * 8 + lo; bt = tile % p.b_tiles; at = tile / p.b_tiles; g = bid;
-        return;
-    }
-    ks = bid % p.ksplit; bid /= p.ksplit;
-    bt = bid % p.b_tiles; bid /= p.b_tiles;
-    at = bid % p.a_tiles; bid /= p.a_tiles;
-    g = bid;
-}
-
 
 //------------------------------------------------------------------------------------
 // Weight gradient of 3x3 / stride-1 / pad-1 convolutions on the bf16 matrix cores with split-bf16 products
@@ -35,15 +14,21 @@ __device__ __forceinline__ void wgrad_decode(const WgradParams& p, int& ks, int&
 //              of two aligned 16-byte blocks with v_alignbit (ts = 0, 2) or by register renaming (ts = 1).
 // One wave owns a 32 x 32 (a, b) tile for all 9 taps (144 accumulator registers): 54 MFMAs per K step.
 
+// The kernel's LDS image, S [npw][64][SP] then L [npw][64][3][LP]: the kernel carves it, the launch sizes it (npw = Arith<NP>::npw pieces per operand)
+struct Wgrad3x3Tile {
+    static constexpr int SP = 40, LP = 40;              // row pitches in bf16 elements (80 B)
+    static constexpr int S_PIECE = 64 * SP;             // one piece of the S tile
+    static constexpr int L_PIECE = 64 * 3 * LP;         // one piece of the L halo tile
+    static constexpr size_t lds_bytes(int npw) { return (size_t)npw * (S_PIECE + L_PIECE) * sizeof(__bf16); }
+};
+
 template <int NP, int IO = IO_F32>       // bf16 pieces per operand: 3 (six products), 2 (three), 1 (one); IO: storage type of S and L (conv_common.h)
 __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParams p) {
     static_assert(IO == IO_F32 || NP == 1, "16-bit storage: one product");
     constexpr bool HX = Arith<NP>::f16x3;           // PASTA_MATH_F16X3: both operands as (h, l), three products (conv_common.h)
     constexpr int NPW = Arith<NP>::npw;             // pieces per operand in LDS
     constexpr int ES = io_size<IO>::value;
-    constexpr int SP = 40, LP = 40;                 // row pitches in bf16 elements (80 B)
-    constexpr int S_PIECE = 64 * SP;                // one piece of the S tile
-    constexpr int L_PIECE = 64 * 3 * LP;            // one piece of the L halo tile
+    constexpr int SP = Wgrad3x3Tile::SP, LP = Wgrad3x3Tile::LP, S_PIECE = Wgrad3x3Tile::S_PIECE, L_PIECE = Wgrad3x3Tile::L_PIECE;
     extern __shared__ __attribute__((aligned(16))) __bf16 smem16[];
     __bf16* Ss = smem16;                            // [3][64][SP]
     __bf16* Ls = smem16 + NPW * S_PIECE;            // [NPW][64][3][LP]
@@ -51,16 +36,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;
     const int hl = lane >> 5, jl = lane & 31;
-    float s_scale = 1.f, l_scale = 1.f, out_scale = 1.f;       // PASTA_MATH_F16X3: operand scales from the tensors' partial maxima
-    if constexpr (HX) {
-        float is_, il_;
-        scale_from_amax(amax_of_parts(p.s_amax), s_scale, is_);
-        scale_from_amax(amax_of_parts(p.l_amax), l_scale, il_);
-        out_scale = is_ * il_;
-    }
+    float s_scale, l_scale, out_scale;
+    wgrad_scales<NP>(p, s_scale, l_scale, out_scale);
 
     int ks, bt, at, g;
-    wgrad_decode(p, ks, bt, at, g);
+    wgrad_workgroup(p, ks, bt, at, g);
     const int a_blk = at * 64, b_blk = bt * 64;
     const int PQ = p.P * p.Q;
     const char* const Sg = (const char*)p.S + ((int64_t)g * p.Ag + a_blk) * PQ * ES;
@@ -80,12 +60,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
 
     float4 sreg[2], lreg[2][2];
     unsigned vmask = 0;                              // validity of the 6 sixteen-byte halves held in registers
-    auto decode = [&](int ch, int& n, int& qb, int& pp) {
-        const int per_img = p.P * p.qblocks;
-        n = ch / per_img;
-        const int rem = ch - n * per_img;
-        qb = rem / p.P; pp = rem - qb * p.P;
-    };
     // one L row (image row ly of sample n, columns q0 - 4 .. q0 + 36) into r[0..1]; returns the validity bits of its four halves
     // (no control flow around the loads: every load is issued, from the tensor's first element where its four-pack lies outside the plane or the
     // channel does not exist, and the validity bits zero it at the split -- the branches this was written with, one per four-pack, made the
@@ -110,8 +84,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
         return m;
     };
     // prefetch of chunk ch: its S pixels and the ONE L row the ring does not hold yet (pp + 1)
-    auto fetch = [&](int n, int qb, int pp) {
-        const int q0 = qb * 32;
+    auto fetch = [&](const WgradChunkPos& c) {
+        const int n = c.n, pp = c.pp, q0 = c.qb * 32;
         vmask = 0;
         const bool s_in = s_ch_ok && q0 + 8 * s_grp + 8 <= p.Q;         // (rows of 16 pixels: the second half of the chunk does not exist -- conv_igemm.hip, wgrad_wide16)
         const char* sp = s_in ? Sg + ((int64_t)n * p.SC * PQ + (int64_t)s_a * PQ + pp * p.Q + q0 + 8 * s_grp) * ES : Sg;
@@ -119,76 +93,40 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
         vmask |= s_in ? 3u : 0u;
         vmask |= fetch_row(n, q0, pp + 1, lreg) << 2;
     };
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    // split 8 floats (two float4 halves, each possibly invalid -> 0) into three packed bf16x8 pieces and store them
+    // two float4 halves, each possibly invalid -> 0, split into pieces and stored
     auto split_store = [&](float4 h0, float4 h1, bool ok0, bool ok1, __bf16* dst, int piece_stride, float scale) {
-        const float vals[8] = {ok0 ? h0.x : 0.f, ok0 ? h0.y : 0.f, ok0 ? h0.z : 0.f, ok0 ? h0.w : 0.f,
-                               ok1 ? h1.x : 0.f, ok1 ? h1.y : 0.f, ok1 ? h1.z : 0.f, ok1 ? h1.w : 0.f};
-        uint32_t q1[4], q2[4], q3[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if constexpr (HX) {
-                f16_split2_direct(vals[2 * j] * scale, vals[2 * j + 1] * scale, q1[j], q2[j]);
-                continue;
-            }
-            f32x2 v = {vals[2 * j], vals[2 * j + 1]};
-            uint32_t w = io_pack2<IO>(vals[2 * j], vals[2 * j + 1]);
-            q1[j] = w;
-            if constexpr (NP >= 2) {
-                v[0] -= __builtin_bit_cast(float, w << 16);
-                v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
-                w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-                q2[j] = w;
-            }
-            if constexpr (NP >= 3) {
-                v[0] -= __builtin_bit_cast(float, w << 16);
-                v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
-                q3[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-            }
-        }
-        *(uint4*)(dst) = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-        if constexpr (NPW >= 2) *(uint4*)(dst + piece_stride) = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-        if constexpr (NPW >= 3) *(uint4*)(dst + 2 * piece_stride) = make_uint4(q3[0], q3[1], q3[2], q3[3]);
+        float vals[8];
+        masked8(h0, h1, ok0, ok1, vals);
+        wgrad_split_store8<NP, IO>(vals, dst, piece_stride, scale);
     };
     // one L row from registers into ring slot `slot`
     auto stash_row = [&](const float4 (&r)[2][2], unsigned m, int slot) {
         split_store(r[0][0], r[0][1], m & 1u, m & 2u, Ls + (l_b0 * 3 + slot) * LP + 8 * l_g0, L_PIECE, l_scale);
         if (tid < 64) split_store(r[1][0], r[1][1], m & 4u, m & 8u, Ls + (l_b1 * 3 + slot) * LP + 8 * l_g1, L_PIECE, l_scale);
     };
-    auto slot_of = [](int y) { return (y + 3) % 3; };       // y >= -1
 
     f32x16 acc[9];
 #pragma unroll
-    for (int t = 0; t < 9; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+    for (int t = 0; t < 9; t++) wgrad_zero(acc[t]);
 
-    const int c_begin = (int)(((unsigned)p.chunks_total * (unsigned)ks) / (unsigned)p.ksplit);
-    const int c_end = (int)(((unsigned)p.chunks_total * (unsigned)(ks + 1)) / (unsigned)p.ksplit);
-    // position of the current chunk and of the next one: decoded ONCE (two divisions by run-time values), then advanced -- the chunks walk down a
-    // column block, then the column blocks of an image, then the images (a decode per chunk and per prefetch was ~200 scalar instructions per
-    // chunk in front of this wave's matrix instructions)
-    int n_c = 0, qb_c = 0, pp_c = 0, n_n = 0, qb_n = 0, pp_n = 0;
-    auto advance = [&](int n, int qb, int pp, int& n2, int& qb2, int& pp2) {
-        pp2 = pp + 1; qb2 = qb; n2 = n;
-        if (pp2 == p.P) { pp2 = 0; qb2 = qb + 1; if (qb2 == p.qblocks) { qb2 = 0; n2 = n + 1; } }
-    };
-    if (c_begin < c_end) { decode(c_begin, n_c, qb_c, pp_c); fetch(n_c, qb_c, pp_c); advance(n_c, qb_c, pp_c, n_n, qb_n, pp_n); }
+    int c_begin, c_end;
+    wgrad_slice(p.chunks_total, p.ksplit, ks, c_begin, c_end);
+    WgradChunkPos cur = {0, 0, 0}, nxt = {0, 0, 0};         // the current chunk and the prefetched one
+    if (c_begin < c_end) { wgrad_chunk_at(p, c_begin, cur); fetch(cur); wgrad_chunk_next(p, cur, nxt); }
     for (int ch = c_begin; ch < c_end; ch++) {
         __syncthreads();                  // the previous chunk's fragment reads are done
-        if (pp_c == 0 || ch == c_begin) { // a column block or this K slice begins: rows pp-1 and pp are not in the ring yet
+        if (cur.pp == 0 || ch == c_begin) { // a column block or this K slice begins: rows pp-1 and pp are not in the ring yet
             float4 t[2][2];
-            unsigned m = fetch_row(n_c, qb_c * 32, pp_c - 1, t);
-            stash_row(t, m, slot_of(pp_c - 1));
-            m = fetch_row(n_c, qb_c * 32, pp_c, t);
-            stash_row(t, m, slot_of(pp_c));
+            unsigned m = fetch_row(cur.n, cur.qb * 32, cur.pp - 1, t);
+            stash_row(t, m, ring_slot(cur.pp - 1));
+            m = fetch_row(cur.n, cur.qb * 32, cur.pp, t);
+            stash_row(t, m, ring_slot(cur.pp));
         }
         split_store(sreg[0], sreg[1], vmask & 1u, vmask & 2u, Ss + s_a * SP + 8 * s_grp, S_PIECE, s_scale);
-        stash_row(lreg, vmask >> 2, slot_of(pp_c + 1));
+        stash_row(lreg, vmask >> 2, ring_slot(cur.pp + 1));
         __syncthreads();
-        if (ch + 1 < c_end) fetch(n_n, qb_n, pp_n);
-        const int slot0 = slot_of(pp_c - 1);          // ring slot of halo row 0; rows 1, 2 follow cyclically
+        if (ch + 1 < c_end) fetch(nxt);
+        const int slot0 = ring_slot(cur.pp - 1);          // ring slot of halo row 0; rows 1, 2 follow cyclically
 #pragma unroll
         for (int s = 0; s < 2; s++) {
             bf16x8 af[3];
@@ -198,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
             for (int pb = NPW - 1; pb >= 0; pb--) {  // B pieces from the smallest to the largest
 #pragma unroll
                 for (int row = 0; row < 3; row++) {
-                    const int slot = slot0 + row >= 3 ? slot0 + row - 3 : slot0 + row;
+                    const int slot = ring_wrap(slot0, row);
                     const __bf16* lb = &Ls[pb * L_PIECE + ((wb * 32 + jl) * 3 + slot) * LP + 16 * s + 8 * hl];
                     // Only dwords 1..6 are used and the compiler narrows the two reads to ds_read2_b64 + ds_read2_b32, whose
                     // 32-bank rule makes the 60-dword lane stride conflict 2-way (SQ_LDS_BANK_CONFLICT = half of this kernel's
@@ -228,13 +166,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
                 }
             }
         }
-        n_c = n_n; qb_c = qb_n; pp_c = pp_n;
-        advance(n_c, qb_c, pp_c, n_n, qb_n, pp_n);
+        cur = nxt; wgrad_chunk_next(p, cur, nxt);
     }
 
     // partial slab: [ksplit][G][9][Ag_pad][Bg_pad], b contiguous (same layout as conv_wgrad_kernel)
     const int Ag_pad = p.a_tiles * 64, Bg_pad = p.b_tiles * 64;
     float* out = p.slab + ((int64_t)ks * p.G + g) * 9 * Ag_pad * Bg_pad;
+    // own block, not a shared sub-tile store: timed old/new/old/new (profiles/wgrad_single_source_ab.txt), <4, 0>: 242.67 / 242.97 us old, 243.30 / 242.92 us new, allowance 243.27
 #pragma unroll
     for (int t = 0; t < 9; t++) {
         float* ot = out + (int64_t)t * Ag_pad * Bg_pad;
@@ -255,15 +193,20 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16x6_kernel(WgradParam
 // (the bf16 pairs of a dword are halo columns 2i, 2i + 1: a window of even or of odd columns is the low or the high
 // halves of eight consecutive dwords).  L rows are not 16-byte aligned in general (257-pixel planes), so the halo is
 // fetched with dword loads.
+struct Wgrad3x3s2Tile {      // S [npw][64][SP] then L [npw][64][3][LP], as Wgrad3x3Tile
+    static constexpr int SP = 16, LP = 40;              // row pitches in bf16 elements
+    static constexpr int S_PIECE = 64 * SP;
+    static constexpr int L_PIECE = 64 * 3 * LP;
+    static constexpr size_t lds_bytes(int npw) { return (size_t)npw * (S_PIECE + L_PIECE) * sizeof(__bf16); }
+};
+
 template <int PW, int NP, int IO = IO_F32>
 __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradParams p) {
     static_assert(IO == IO_F32 || NP == 1, "16-bit storage: one product");
     constexpr bool HX = Arith<NP>::f16x3;           // PASTA_MATH_F16X3: both operands as (h, l), three products (conv_common.h)
     constexpr int NPW = Arith<NP>::npw;             // pieces per operand in LDS
     constexpr int ES = io_size<IO>::value;
-    constexpr int SP = 16, LP = 40;                 // row pitches in bf16 elements
-    constexpr int S_PIECE = 64 * SP;
-    constexpr int L_PIECE = 64 * 3 * LP;
+    constexpr int SP = Wgrad3x3s2Tile::SP, LP = Wgrad3x3s2Tile::LP, S_PIECE = Wgrad3x3s2Tile::S_PIECE, L_PIECE = Wgrad3x3s2Tile::L_PIECE;
     extern __shared__ __attribute__((aligned(16))) __bf16 smem16[];
     __bf16* Ss = smem16;                            // [3][64][SP]
     __bf16* Ls = smem16 + NPW * S_PIECE;            // [NPW][64][3][LP]
@@ -271,16 +214,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradPar
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;
     const int hl = lane >> 5, jl = lane & 31;
-    float s_scale = 1.f, l_scale = 1.f, out_scale = 1.f;       // PASTA_MATH_F16X3: operand scales from the tensors' partial maxima
-    if constexpr (HX) {
-        float is_, il_;
-        scale_from_amax(amax_of_parts(p.s_amax), s_scale, is_);
-        scale_from_amax(amax_of_parts(p.l_amax), l_scale, il_);
-        out_scale = is_ * il_;
-    }
+    float s_scale, l_scale, out_scale;
+    wgrad_scales<NP>(p, s_scale, l_scale, out_scale);
 
     int ks, bt, at, g;
-    wgrad_decode(p, ks, bt, at, g);
+    wgrad_workgroup(p, ks, bt, at, g);
     const int a_blk = at * 64, b_blk = bt * 64;
     const int PQ = p.P * p.Q, LHW = p.LH * p.LW;
     const char* const Sg = (const char*)p.S + ((int64_t)g * p.Ag + a_blk) * PQ * ES;
@@ -311,12 +249,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradPar
     float lreg[3][8];
     unsigned lmask = 0;                              // validity bit of each of the 24 halo elements held in registers
     bool s_ok = false;
-    auto decode = [&](int ch, int& n, int& qb, int& pp) {
-        const int per_img = p.P * p.qblocks;
-        n = ch / per_img;
-        const int rem = ch - n * per_img;
-        qb = rem / p.P; pp = rem - qb * p.P;
-    };
     // eight consecutive elements of L row ly of channel b (sample n) from column lx on; returns their validity bits
     auto fetch_unit = [&](int n, int ly, int lx, int b, bool ch_ok, float (&r)[8]) -> unsigned {
         const bool rok = ch_ok && (unsigned)ly < (unsigned)p.LH;
@@ -337,8 +269,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradPar
         // four-packs -- two address selects per ELEMENT here: 123 -> 98 TFLOP/s on 64 -> 128 at 257 x 257, profiles/r5_ab_wgrad_branchfree.txt)
         return m;
     };
-    auto fetch = [&](int n, int qb, int pp) {
-        const int q0 = qb * 16;
+    auto fetch = [&](const WgradChunkPos& c) {
+        const int n = c.n, pp = c.pp, q0 = c.qb * 16;
         s_ok = s_on;
         if (tid < 128) {                              // (wave-uniform: the S units belong to the first two waves)
             const char* sp = s_on ? Sg + ((int64_t)n * p.SC * PQ + (int64_t)s_a * PQ + pp * p.Q + q0 + 8 * s_grp) * ES : Sg;
@@ -349,87 +281,48 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradPar
         for (int j = 0; j < 3; j++)
             lmask |= fetch_unit(n, 2 * pp + l_k[j] - p.pad_h, 2 * q0 - 4 + 8 * l_grp[j], l_b[j], l_ch_ok[j], lreg[j]) << (8 * j);
     };
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    auto split_store = [&](const float* vals, __bf16* dst, int piece_stride, float scale) {
-        uint32_t q1[4], q2[4], q3[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if constexpr (HX) {
-                f16_split2_direct(vals[2 * j] * scale, vals[2 * j + 1] * scale, q1[j], q2[j]);
-                continue;
-            }
-            f32x2 v = {vals[2 * j], vals[2 * j + 1]};
-            uint32_t w = io_pack2<IO>(vals[2 * j], vals[2 * j + 1]);
-            q1[j] = w;
-            if constexpr (NP >= 2) {
-                v[0] -= __builtin_bit_cast(float, w << 16);
-                v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
-                w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-                q2[j] = w;
-            }
-            if constexpr (NP >= 3) {
-                v[0] -= __builtin_bit_cast(float, w << 16);
-                v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
-                q3[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-            }
-        }
-        *(uint4*)(dst) = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-        if constexpr (NPW >= 2) *(uint4*)(dst + piece_stride) = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-        if constexpr (NPW >= 3) *(uint4*)(dst + 2 * piece_stride) = make_uint4(q3[0], q3[1], q3[2], q3[3]);
-    };
     auto stash = [&]() {
         if (tid < 128) {
-            const float sv[8] = {s_ok ? sreg[0].x : 0.f, s_ok ? sreg[0].y : 0.f, s_ok ? sreg[0].z : 0.f, s_ok ? sreg[0].w : 0.f,
-                                 s_ok ? sreg[1].x : 0.f, s_ok ? sreg[1].y : 0.f, s_ok ? sreg[1].z : 0.f, s_ok ? sreg[1].w : 0.f};
-            split_store(sv, Ss + s_a * SP + 8 * s_grp, S_PIECE, s_scale);
+            float sv[8];
+            masked8(sreg[0], sreg[1], s_ok, s_ok, sv);
+            wgrad_split_store8<NP, IO>(sv, Ss + s_a * SP + 8 * s_grp, S_PIECE, s_scale);
         }
     };
-    auto slot_of = [](int y) { return (y + 3) % 3; };       // y >= -1
     // one staged L unit (eight elements, validity bits m) into ring slot `slot`
     auto stash_unit = [&](const float (&r)[8], unsigned m, int b, int grp, int slot) {
         float lv[8];
 #pragma unroll
         for (int e = 0; e < 8; e++) lv[e] = ((m >> e) & 1u) ? r[e] : 0.f;
-        split_store(lv, Ls + (b * 3 + slot) * LP + 8 * grp, L_PIECE, l_scale);
+        wgrad_split_store8<NP, IO>(lv, Ls + (b * 3 + slot) * LP + 8 * grp, L_PIECE, l_scale);
     };
 
     f32x16 acc[9];
 #pragma unroll
-    for (int t = 0; t < 9; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+    for (int t = 0; t < 9; t++) wgrad_zero(acc[t]);
 
-    const int c_begin = (int)(((unsigned)p.chunks_total * (unsigned)ks) / (unsigned)p.ksplit);
-    const int c_end = (int)(((unsigned)p.chunks_total * (unsigned)(ks + 1)) / (unsigned)p.ksplit);
-    // position of the current chunk and of the next one: decoded ONCE (two divisions by run-time values), then advanced -- the chunks walk down a
-    // column block, then the column blocks of an image, then the images (a decode per chunk and per prefetch was ~200 scalar instructions per
-    // chunk in front of this wave's matrix instructions)
-    int n_c = 0, qb_c = 0, pp_c = 0, n_n = 0, qb_n = 0, pp_n = 0;
-    auto advance = [&](int n, int qb, int pp, int& n2, int& qb2, int& pp2) {
-        pp2 = pp + 1; qb2 = qb; n2 = n;
-        if (pp2 == p.P) { pp2 = 0; qb2 = qb + 1; if (qb2 == p.qblocks) { qb2 = 0; n2 = n + 1; } }
-    };
-    if (c_begin < c_end) { decode(c_begin, n_c, qb_c, pp_c); fetch(n_c, qb_c, pp_c); advance(n_c, qb_c, pp_c, n_n, qb_n, pp_n); }
+    int c_begin, c_end;
+    wgrad_slice(p.chunks_total, p.ksplit, ks, c_begin, c_end);
+    WgradChunkPos cur = {0, 0, 0}, nxt = {0, 0, 0};         // the current chunk and the prefetched one
+    if (c_begin < c_end) { wgrad_chunk_at(p, c_begin, cur); fetch(cur); wgrad_chunk_next(p, cur, nxt); }
     for (int ch = c_begin; ch < c_end; ch++) {
-        const int y0 = 2 * pp_c - p.pad_h;
+        const int y0 = 2 * cur.pp - p.pad_h;
         __syncthreads();                  // the previous chunk's fragment reads are done
-        if (pp_c == 0 || ch == c_begin) { // a column block or this K slice begins: the first halo row is not in the ring yet
+        if (cur.pp == 0 || ch == c_begin) { // a column block or this K slice begins: the first halo row is not in the ring yet
             float t[8];
-            unsigned m = fetch_unit(n_c, y0, 2 * qb_c * 16 - 4 + 8 * p_g0, p_b0, b_blk + p_b0 < p.Bg, t);
-            stash_unit(t, m, p_b0, p_g0, slot_of(y0));
+            unsigned m = fetch_unit(cur.n, y0, 2 * cur.qb * 16 - 4 + 8 * p_g0, p_b0, b_blk + p_b0 < p.Bg, t);
+            stash_unit(t, m, p_b0, p_g0, ring_slot(y0));
             if (tid < 64) {
-                m = fetch_unit(n_c, y0, 2 * qb_c * 16 - 4 + 8 * p_g1, p_b1, b_blk + p_b1 < p.Bg, t);
-                stash_unit(t, m, p_b1, p_g1, slot_of(y0));
+                m = fetch_unit(cur.n, y0, 2 * cur.qb * 16 - 4 + 8 * p_g1, p_b1, b_blk + p_b1 < p.Bg, t);
+                stash_unit(t, m, p_b1, p_g1, ring_slot(y0));
             }
         }
         stash();
 #pragma unroll
         for (int j = 0; j < 3; j++)
-            if (tid + 256 * j < 640) stash_unit(lreg[j], (lmask >> (8 * j)) & 0xffu, l_b[j], l_grp[j], slot_of(y0 + l_k[j]));
+            if (tid + 256 * j < 640) stash_unit(lreg[j], (lmask >> (8 * j)) & 0xffu, l_b[j], l_grp[j], ring_slot(y0 + l_k[j]));
         __syncthreads();
-        if (ch + 1 < c_end) fetch(n_n, qb_n, pp_n);
-        const int slot0 = slot_of(y0);
+        if (ch + 1 < c_end) fetch(nxt);
+        const int slot0 = ring_slot(y0);
         bf16x8 af[3];
 #pragma unroll
         for (int pc = 0; pc < NPW; pc++) af[pc] = *(const bf16x8*)&Ss[pc * S_PIECE + (wa * 32 + jl) * SP + 8 * hl];
@@ -437,14 +330,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradPar
         for (int pb = NPW - 1; pb >= 0; pb--) {      // B pieces from the smallest to the largest
 #pragma unroll
             for (int row = 0; row < 3; row++) {
-                const int slot = slot0 + row >= 3 ? slot0 + row - 3 : slot0 + row;
+                const int slot = ring_wrap(slot0, row);
                 const __bf16* lb = &Ls[pb * L_PIECE + ((wb * 32 + jl) * 3 + slot) * LP + 16 * hl];
                 uint4 b0 = *(const uint4*)lb, b1 = *(const uint4*)(lb + 8), b2 = *(const uint4*)(lb + 16);
                 PASTA_KEEP_WHOLE(b0); PASTA_KEEP_WHOLE(b1); PASTA_KEEP_WHOLE(b2);      // whole ds_read_b128 (conflict-free) instead of narrowed read2 pairs: +2 % here
                 const uint32_t d[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
 #pragma unroll
                 for (int ts = 0; ts < 3; ts++) {
-                    constexpr int dummy = 0; (void)dummy;
                     const int c0 = 4 - PW + ts, d0 = c0 >> 1;
                     const uint32_t sel = (c0 & 1) ? 0x07060302u : 0x05040100u;
                     const uint4 w = make_uint4(__builtin_amdgcn_perm(d[d0 + 1], d[d0], sel), __builtin_amdgcn_perm(d[d0 + 3], d[d0 + 2], sel),
@@ -457,12 +349,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_bf16x6_kernel(WgradPar
                 }
             }
         }
-        n_c = n_n; qb_c = qb_n; pp_c = pp_n;
-        advance(n_c, qb_c, pp_c, n_n, qb_n, pp_n);
+        cur = nxt; wgrad_chunk_next(p, cur, nxt);
     }
 
     const int Ag_pad = p.a_tiles * 64, Bg_pad = p.b_tiles * 64;
     float* out = p.slab + ((int64_t)ks * p.G + g) * 9 * Ag_pad * Bg_pad;
+    // own block, not a shared sub-tile store: timed old/new/old/new (profiles/wgrad_single_source_ab.txt), <0, 4, 0>: 295.86 / 296.61 us old, 296.99 / 297.72 us new, allowance 297.36
 #pragma unroll
     for (int t = 0; t < 9; t++) {
         float* ot = out + (int64_t)t * Ag_pad * Bg_pad;
@@ -502,25 +394,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;
     const int hl = lane >> 5, jl = lane & 31;
-    float s_scale, l_scale, is_, il_;
-    scale_from_amax(amax_of_parts(p.s_amax), s_scale, is_);
-    scale_from_amax(amax_of_parts(p.l_amax), l_scale, il_);           // the producer's bound row: the S the pieces were written with
-    const float out_scale = is_ * il_;
+    float s_scale, l_scale, out_scale;
+    wgrad_scales<NP_F16X3>(p, s_scale, l_scale, out_scale);          // l_amax: the producer's bound row, the S the pieces were written with
 
     int ks, bt, at, g;
-    wgrad_decode(p, ks, bt, at, g);                  // g = 0: one group
+    wgrad_workgroup(p, ks, bt, at, g);               // g = 0: one group
     const int a_blk = at * 64, b_blk = bt * 64;
     const int PQ = p.P * p.Q;
     const float* const Sg = p.S + (int64_t)a_blk * PQ;
     const int LC8 = p.LC >> 3;
     const char* const Lg = (const char*)p.L + (int64_t)(b_blk >> 3) * p.LH * p.LW * 32;
 
-    auto decode = [&](int ch, int& n, int& qb, int& pp) {
-        const int per_img = p.P * p.qblocks;
-        n = ch / per_img;
-        const int rem = ch - n * per_img;
-        qb = rem / p.P; pp = rem - qb * p.P;
-    };
     // staging roles: S unit = (channel a, eight pixels), threads 0..127; L units = (column, octet) of one halo row: 34 x 8 = 272 per row,
     // unit v = tid + 256 j < 544 belongs to new row 1 + v / 272 (the ring holds row 0); octet fastest: eight lanes fill one column's 128 bytes
     const int s_a = tid >> 1, s_grp = tid & 1;
@@ -552,8 +436,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
         *(u32x4*)d = ok ? r[0] : z;
         *(u32x4*)(d + L_PIECE) = ok ? r[1] : z;
     };
-    auto fetch = [&](int n, int qb, int pp) {
-        const int q0 = qb * 16;
+    auto fetch = [&](const WgradChunkPos& c) {
+        const int n = c.n, pp = c.pp, q0 = c.qb * 16;
         if (tid < 128) {                              // (wave-uniform; a channel beyond the tensor re-reads its first element and is zeroed at the split)
             const float* sp = s_on ? Sg + (int64_t)n * p.SC * PQ + (int64_t)s_a * PQ + pp * p.Q + q0 + 8 * s_grp : Sg;
             sreg[0] = *(const float4*)sp; sreg[1] = *(const float4*)(sp + 4);
@@ -562,12 +446,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
         for (int j = 0; j < 3; j++)
             lok[j] = fetch_unit(n, 2 * pp + l_k[j], 2 * q0 + l_col[j], l_oct[j], l_on[j], lreg[j]);
     };
-    auto slot_of = [](int y) { return y % 3; };          // y >= 0 (pad 0)
+    auto slot_of = [](int y) { return y % 3; };          // y >= 0 (pad 0); ring_slot's (y + 3) % 3 changes 91 of this kernel's 2185 assembly lines, product loop included
     typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
     auto stash_s = [&]() {
         if (tid >= 128) return;
-        const float sv[8] = {s_on ? sreg[0].x : 0.f, s_on ? sreg[0].y : 0.f, s_on ? sreg[0].z : 0.f, s_on ? sreg[0].w : 0.f,
-                             s_on ? sreg[1].x : 0.f, s_on ? sreg[1].y : 0.f, s_on ? sreg[1].z : 0.f, s_on ? sreg[1].w : 0.f};
+        float sv[8];
+        masked8(sreg[0], sreg[1], s_on, s_on, sv);
         uint32_t qh[4], ql[4], qs[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -584,9 +468,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
 
     f32x16 acc[9];
 #pragma unroll
-    for (int t = 0; t < 9; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+    for (int t = 0; t < 9; t++) wgrad_zero(acc[t]);
 
     // transposed reads: lane 4 q + c of a 16-lane group supplies the address of block row q (K), columns 4 c .. 4 c + 3 (channels); the group's
     // lane i receives column i, row q in element q.  Group (lane >> 4): channels 16 (grp & 1) .. + 15 of this wave's 32, K block 8 (grp >> 1) (= 8 hl)
@@ -595,26 +477,19 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
     typedef __fp16 v4h __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) v4h* lds_v4h;
 
-    const int c_begin = (int)(((unsigned)p.chunks_total * (unsigned)ks) / (unsigned)p.ksplit);
-    const int c_end = (int)(((unsigned)p.chunks_total * (unsigned)(ks + 1)) / (unsigned)p.ksplit);
-    // position of the current chunk and of the next one: decoded ONCE (two divisions by run-time values), then advanced -- the chunks walk down a
-    // column block, then the column blocks of an image, then the images (a decode per chunk and per prefetch was ~200 scalar instructions per
-    // chunk in front of this wave's matrix instructions)
-    int n_c = 0, qb_c = 0, pp_c = 0, n_n = 0, qb_n = 0, pp_n = 0;
-    auto advance = [&](int n, int qb, int pp, int& n2, int& qb2, int& pp2) {
-        pp2 = pp + 1; qb2 = qb; n2 = n;
-        if (pp2 == p.P) { pp2 = 0; qb2 = qb + 1; if (qb2 == p.qblocks) { qb2 = 0; n2 = n + 1; } }
-    };
-    if (c_begin < c_end) { decode(c_begin, n_c, qb_c, pp_c); fetch(n_c, qb_c, pp_c); advance(n_c, qb_c, pp_c, n_n, qb_n, pp_n); }
+    int c_begin, c_end;
+    wgrad_slice(p.chunks_total, p.ksplit, ks, c_begin, c_end);
+    WgradChunkPos cur = {0, 0, 0}, nxt = {0, 0, 0};         // the current chunk and the prefetched one
+    if (c_begin < c_end) { wgrad_chunk_at(p, c_begin, cur); fetch(cur); wgrad_chunk_next(p, cur, nxt); }
     for (int ch = c_begin; ch < c_end; ch++) {
-        const int y0 = 2 * pp_c;
+        const int y0 = 2 * cur.pp;
         __syncthreads();                  // the previous chunk's fragment reads are done
-        if (pp_c == 0 || ch == c_begin) { // a column block or this K slice begins: the first halo row is not in the ring yet (272 units: tid, and 256 + tid for 16 threads)
+        if (cur.pp == 0 || ch == c_begin) { // a column block or this K slice begins: the first halo row is not in the ring yet (272 units: tid, and 256 + tid for 16 threads)
             u32x4 t[2];
-            bool ok = fetch_unit(n_c, y0, 2 * qb_c * 16 + (tid >> 3), tid & 7, b_blk + 8 * (tid & 7) < p.Bg, t);
+            bool ok = fetch_unit(cur.n, y0, 2 * cur.qb * 16 + (tid >> 3), tid & 7, b_blk + 8 * (tid & 7) < p.Bg, t);
             stash_unit(t, ok, slot_of(y0), tid >> 3, tid & 7);
             if (tid < 16) {
-                ok = fetch_unit(n_c, y0, 2 * qb_c * 16 + 32 + (tid >> 3), tid & 7, b_blk + 8 * (tid & 7) < p.Bg, t);
+                ok = fetch_unit(cur.n, y0, 2 * cur.qb * 16 + 32 + (tid >> 3), tid & 7, b_blk + 8 * (tid & 7) < p.Bg, t);
                 stash_unit(t, ok, slot_of(y0), 32 + (tid >> 3), tid & 7);
             }
         }
@@ -623,14 +498,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
         for (int j = 0; j < 3; j++)
             if (tid + 256 * j < 544) stash_unit(lreg[j], lok[j], slot_of(y0 + l_k[j]), l_col[j], l_oct[j]);
         __syncthreads();
-        if (ch + 1 < c_end) fetch(n_n, qb_n, pp_n);
+        if (ch + 1 < c_end) fetch(nxt);
         const int slot0 = slot_of(y0);
         bf16x8 af[3];
 #pragma unroll
         for (int pc = 0; pc < 3; pc++) af[pc] = *(const bf16x8*)&Ss[pc * S_PIECE + (wa * 32 + jl) * SP + 8 * hl];
 #pragma unroll
         for (int row = 0; row < 3; row++) {
-            const int slot = slot0 + row >= 3 ? slot0 + row - 3 : slot0 + row;
+            const int slot = ring_wrap(slot0, row);
             const _Float16* const lrow = lbase + slot * L_ROW;
 #pragma unroll
             for (int ts = 0; ts < 3; ts++) {
@@ -648,12 +523,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
                 acc[tap] = mfma16<IO_F32, NP_F16X3>(af[0], bh, acc[tap]);       // (S h)(L h)
             }
         }
-        n_c = n_n; qb_c = qb_n; pp_c = pp_n;
-        advance(n_c, qb_c, pp_c, n_n, qb_n, pp_n);
+        cur = nxt; wgrad_chunk_next(p, cur, nxt);
     }
 
     const int Ag_pad = p.a_tiles * 64, Bg_pad = p.b_tiles * 64;
     float* out = p.slab + (int64_t)ks * 9 * Ag_pad * Bg_pad;
+    // own block, not a shared sub-tile store: timed old/new/old/new (profiles/wgrad_single_source_ab.txt), 284.21 / 284.25 us old, 283.07 / 285.57 us new, allowance 284.28
 #pragma unroll
     for (int t = 0; t < 9; t++) {
         float* ot = out + (int64_t)t * Ag_pad * Bg_pad;
@@ -671,15 +546,21 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3s2_pieces_kernel(WgradPar
 // split-bf16 arithmetic; workgroup tile (64 WA) x (64 WB) channels, every wave WA x WB tiles of 32 x 32; K chunk = 32
 // consecutive pixels of one image (P*Q % 32 == 0).  Both operands are split and stored as [piece][channel][32 px]
 // (row pitch 40 bf16).  The shape is bandwidth-bound: 2 x 64 x (WA + WB) x 32 floats per 32 x (64 WA)(64 WB) MACs.
+template <int WA, int WB> struct Wgrad1x1Tile {      // S [npw][TA][SP] then L [npw][TB][SP]
+    static constexpr int SP = 40;
+    static constexpr int TA = 64 * WA, TB = 64 * WB;
+    static constexpr int A_PIECE = TA * SP, B_PIECE = TB * SP;
+    static constexpr size_t lds_bytes(int npw) { return (size_t)npw * (A_PIECE + B_PIECE) * sizeof(__bf16); }
+};
+
 template <int WA, int WB, int NP, int IO = IO_F32>
 __global__ __launch_bounds__(256, 2) void conv_wgrad1x1_bf16x6_kernel(WgradParams p) {
     static_assert(IO == IO_F32 || NP == 1, "16-bit storage: one product");
     constexpr bool HX = Arith<NP>::f16x3;           // PASTA_MATH_F16X3: both operands as (h, l), three products (conv_common.h)
     constexpr int NPW = Arith<NP>::npw;             // pieces per operand in LDS
     constexpr int ES = io_size<IO>::value;
-    constexpr int SP = 40;
-    constexpr int TA = 64 * WA, TB = 64 * WB;
-    constexpr int A_PIECE = TA * SP, B_PIECE = TB * SP;
+    typedef Wgrad1x1Tile<WA, WB> Tile;
+    constexpr int SP = Tile::SP, TA = Tile::TA, TB = Tile::TB, A_PIECE = Tile::A_PIECE, B_PIECE = Tile::B_PIECE;
     constexpr int UA = TA * 4 / 256, UB = TB * 4 / 256;             // (channel, 8-pixel group) units per thread
     extern __shared__ __attribute__((aligned(16))) __bf16 smem16[];
     __bf16* Ss = smem16;                            // [3][TA][SP]
@@ -688,16 +569,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad1x1_bf16x6_kernel(WgradParam
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;
     const int hl = lane >> 5, jl = lane & 31;
-    float s_scale = 1.f, l_scale = 1.f, out_scale = 1.f;       // PASTA_MATH_F16X3: operand scales from the tensors' partial maxima
-    if constexpr (HX) {
-        float is_, il_;
-        scale_from_amax(amax_of_parts(p.s_amax), s_scale, is_);
-        scale_from_amax(amax_of_parts(p.l_amax), l_scale, il_);
-        out_scale = is_ * il_;
-    }
+    float s_scale, l_scale, out_scale;
+    wgrad_scales<NP>(p, s_scale, l_scale, out_scale);
 
     int ks, bt, at, g;
-    wgrad_decode(p, ks, bt, at, g);
+    wgrad_workgroup(p, ks, bt, at, g);
     const int a_blk = at * TA, b_blk = bt * TB;
     const int PQ = p.P * p.Q;
     const char* const Sg = (const char*)p.S + ((int64_t)g * p.Ag + a_blk) * PQ * ES;
@@ -724,36 +600,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad1x1_bf16x6_kernel(WgradParam
             }
         }
     };
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     auto split_store = [&](float4 h0, float4 h1, bool ok, __bf16* dst, int piece_stride, float scale) {
-        const float vals[8] = {ok ? h0.x : 0.f, ok ? h0.y : 0.f, ok ? h0.z : 0.f, ok ? h0.w : 0.f,
-                               ok ? h1.x : 0.f, ok ? h1.y : 0.f, ok ? h1.z : 0.f, ok ? h1.w : 0.f};
-        uint32_t q1[4], q2[4], q3[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if constexpr (HX) {
-                f16_split2_direct(vals[2 * j] * scale, vals[2 * j + 1] * scale, q1[j], q2[j]);
-                continue;
-            }
-            f32x2 v = {vals[2 * j], vals[2 * j + 1]};
-            uint32_t w = io_pack2<IO>(vals[2 * j], vals[2 * j + 1]);
-            q1[j] = w;
-            if constexpr (NP >= 2) {
-                v[0] -= __builtin_bit_cast(float, w << 16);
-                v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
-                w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-                q2[j] = w;
-            }
-            if constexpr (NP >= 3) {
-                v[0] -= __builtin_bit_cast(float, w << 16);
-                v[1] -= __builtin_bit_cast(float, w & 0xffff0000u);
-                q3[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-            }
-        }
-        *(uint4*)(dst) = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-        if constexpr (NPW >= 2) *(uint4*)(dst + piece_stride) = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-        if constexpr (NPW >= 3) *(uint4*)(dst + 2 * piece_stride) = make_uint4(q3[0], q3[1], q3[2], q3[3]);
+        float vals[8];
+        masked8(h0, h1, ok, ok, vals);
+        wgrad_split_store8<NP, IO>(vals, dst, piece_stride, scale);
     };
     auto stash = [&]() {
 #pragma unroll
@@ -772,12 +622,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad1x1_bf16x6_kernel(WgradParam
 #pragma unroll
     for (int a = 0; a < WA; a++)
 #pragma unroll
-        for (int b = 0; b < WB; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+        for (int b = 0; b < WB; b++) wgrad_zero(acc[a][b]);
 
-    const int c_begin = (int)(((unsigned)p.chunks_total * (unsigned)ks) / (unsigned)p.ksplit);
-    const int c_end = (int)(((unsigned)p.chunks_total * (unsigned)(ks + 1)) / (unsigned)p.ksplit);
+    int c_begin, c_end;
+    wgrad_slice(p.chunks_total, p.ksplit, ks, c_begin, c_end);
     if (c_begin < c_end) fetch(c_begin);
     for (int ch = c_begin; ch < c_end; ch++) {
         __syncthreads();                  // the previous chunk's fragment reads are done
@@ -814,6 +662,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad1x1_bf16x6_kernel(WgradParam
     for (int a = 0; a < WA; a++)
 #pragma unroll
         for (int b = 0; b < WB; b++)
+            // own block, not a shared sub-tile store (profiles/wgrad_single_source_ab.txt): <2, 2, 4, 0> 58.26 / 58.26 us old, 58.30 / 58.42 us new, allowance 58.26
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int ai = a_blk + (wa * WA + a) * 32 + acc_row(r, lane), bi = b_blk + (wb * WB + b) * 32 + jl;

@@ -67,12 +67,10 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 1) void conv_wgrad_kernel(WgradPara
 #pragma unroll
         for (int i = 0; i < WA; i++)
 #pragma unroll
-            for (int j = 0; j < WB; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[t][i][j][r] = 0.f;
+            for (int j = 0; j < WB; j++) wgrad_zero(acc[t][i][j]);
 
-    const int c_begin = (int)(((unsigned)p.chunks_total * (unsigned)ks) / (unsigned)p.ksplit);
-    const int c_end = (int)(((unsigned)p.chunks_total * (unsigned)(ks + 1)) / (unsigned)p.ksplit);
+    int c_begin, c_end;
+    wgrad_slice(p.chunks_total, p.ksplit, ks, c_begin, c_end);
     const int kl = lane >> 5, jl = lane & 31;
     const float* const Sg = p.S + ((int64_t)g * p.Ag + a_blk) * PQ;
     const float* const Lg = p.L + ((int64_t)g * p.Bg + b_blk) * LHW;
@@ -194,6 +192,7 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 1) void conv_wgrad_kernel(WgradPara
             for (int i = 0; i < WA; i++)
 #pragma unroll
                 for (int j = 0; j < WB; j++)
+                    // own block, not wgrad_store_subtile: with it the instances without prefetch take 66 VGPRs for 54 - 62 and <1,4,1,1,0,.> falls from 4 to 3 waves per SIMD, <1,7,1,1,0,.> from 3 to 2
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
                         const int a = a_blk + (wa * WA + i) * 32 + acc_row(r, lane), b = b_blk + (wb * WB + j) * 32 + jl;
@@ -217,7 +216,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
         const int t = (int)(r % KK);
         const int g = (int)(r / KK);
         const float* src = slab + (((int64_t)g * KK + t) * Ag_pad + a) * Bg_pad + b;
-        // sixteen slabs in flight per thread; four partial sums combined in a fixed order (bitwise reproducible)
+        // sixteen slabs in flight per thread; four partial sums combined in a fixed order (bitwise reproducible).  Own block in both reductions: as a
+        // shared function, wgrad_smallcin_reduce_kernel 28.63 / 28.59 us old, 28.66 / 28.74 us new, allowance 28.68 (profiles/wgrad_single_source_ab.txt)
         float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
         int k = 0;
         for (; k + 16 <= ksplit; k += 16) {
@@ -388,14 +388,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_smallcin_kernel(WgradSmallPara
     }
     f32x16 acc[MAXT];
 #pragma unroll
-    for (int t = 0; t < MAXT; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+    for (int t = 0; t < MAXT; t++) wgrad_zero(acc[t]);
 
     const int s_k = tid & 31, s_a0 = tid >> 5;
     const int s_dr = s_k >> p.cw_log2, s_dq = s_k & (CW - 1);
-    const int c_begin = (int)(((unsigned)p.chunks_total * (unsigned)ks) / (unsigned)p.ksplit);
-    const int c_end = (int)(((unsigned)p.chunks_total * (unsigned)(ks + 1)) / (unsigned)p.ksplit);
+    int c_begin, c_end;
+    wgrad_slice(p.chunks_total, p.ksplit, ks, c_begin, c_end);
 
     // Register prefetch: chunk ch+1 is fetched while chunk ch is multiplied out of LDS.  Every thread owns the same 8 S
     // elements (channel s_a0 + 8j, pixel s_k) and up to 4 halo slots of every chunk; the slot -> (channel, kernel row,
@@ -470,7 +468,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_smallcin_kernel(WgradSmallPara
     for (int t = 0; t < MAXT; t++) {
         if (wb + 2 * t >= p.nb) continue;
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
+        for (int r = 0; r < 16; r++) {      // (the same store as conv_wgrad_kernel's, other pitch: no second user was left for a shared function -- profiles/wgrad_single_source_ab.txt)
             const int a = a_blk + wa * 32 + acc_row(r, lane), b = (wb + 2 * t) * 32 + jl;
             out[(int64_t)a * bpad + b] = acc[t][r];
         }
@@ -510,12 +508,10 @@ static WgradSmallPlan plan_wgrad_small(const pasta_conv_desc* d) {
     if (d->transposed || d->groups != 1 || d->stride != 1 || d->flip || Ig > 8 || Ig * d->kh * d->kw > 160) return w;
     w.use = true;
     w.bprime = Ig * d->kh * d->kw; w.nb = (w.bprime + 31) / 32;
-    int cw = 32, lg = 5;
-    while (cw > 1 && cw / 2 >= d->OW) { cw /= 2; lg--; }
-    const int chh = 32 / cw;
-    w.cw_log2 = lg; w.rows_total = d->N * d->OH;
-    w.qblocks = (d->OW + cw - 1) / cw;
-    w.chunks_total = ((w.rows_total + chh - 1) / chh) * w.qblocks;
+    w.rows_total = d->N * d->OH;
+    const WgradChunks c = wgrad_chunks(32, w.rows_total, d->OW);
+    w.cw_log2 = c.cw_log2; w.qblocks = c.qblocks; w.chunks_total = c.chunks_total;
+    const int cw = 1 << c.cw_log2, chh = 32 >> c.cw_log2;
     w.a_tiles = (d->C_out + 63) / 64;
     int64_t ks = (1024 + w.a_tiles - 1) / w.a_tiles;        // four workgroups per CU: one chunk in flight each
     if (ks > w.chunks_total / 8) ks = w.chunks_total / 8;
