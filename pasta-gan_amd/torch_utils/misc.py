@@ -118,18 +118,23 @@ class InfiniteSampler(torch.utils.data.Sampler):
     stream (identical on every rank: same seed, same draws) belongs to rank ``t % num_replicas``, so the ranks read disjoint
     items; after each position the item just passed is swapped with one at most ``window_size * len(dataset)`` places behind
     it, which keeps the order drifting without ever reshuffling the whole set.  Same constructor, same index stream for a
-    given seed as the reference's class (misc.py:115-146; pinned by tests/golden/sampler.npz)."""
+    given seed as the reference's class (misc.py:115-146; pinned by tests/golden/sampler.npz).  ``skip`` (own keyword, for a
+    continued run): that many positions of the global stream are already consumed; their draws are replayed without yielding
+    and the stream goes on at position ``skip``."""
 
-    def __init__(self, dataset, rank=0, num_replicas=1, shuffle=True, seed=0, window_size=0.5):
+    def __init__(self, dataset, rank=0, num_replicas=1, shuffle=True, seed=0, window_size=0.5, skip=0):
         if len(dataset) <= 0:
             raise AssertionError('InfiniteSampler: empty dataset')
         if not (num_replicas > 0 and 0 <= rank < num_replicas):
             raise AssertionError(f'InfiniteSampler: rank {rank} is not in [0, {num_replicas})')
         if not 0 <= window_size <= 1:
             raise AssertionError('InfiniteSampler: window_size must lie in [0, 1]')
+        if not skip >= 0:
+            raise AssertionError('InfiniteSampler: skip must not be negative')
         super().__init__()
         self.dataset, self.rank, self.num_replicas = dataset, rank, num_replicas
         self.shuffle, self.seed, self.window_size = shuffle, seed, window_size
+        self.skip = int(skip)
 
     def __iter__(self):
         n = len(self.dataset)
@@ -139,7 +144,18 @@ class InfiniteSampler(torch.utils.data.Sampler):
             draw = np.random.RandomState(self.seed)
             draw.shuffle(perm)
             reach = int(np.rint(n * self.window_size))
-        for t in itertools.count():
+        if self.skip > 0 and reach >= 2:
+            # the swaps of positions 0 .. skip - 1 on a Python list, their draws taken a block at a time: RandomState.randint
+            # gives a block of k the values of k single calls (tests/test_train_state_cpu.py holds the two streams together)
+            order, t = perm.tolist(), 0
+            while t < self.skip:
+                for d in draw.randint(reach, size=min(self.skip - t, 1 << 16)).tolist():
+                    here = t % n
+                    back = (here - d) % n
+                    order[here], order[back] = order[back], order[here]
+                    t += 1
+            perm = np.array(order, dtype=perm.dtype)
+        for t in itertools.count(self.skip):
             here = t % n
             if t % self.num_replicas == self.rank:
                 yield perm[here]

@@ -6,11 +6,19 @@
 
 The G / D / optimiser / loss options are ``training_loop_wo_flow_fullbody.fashion_config``'s and the augmentation options
 ``augment_options``'s; a base config contributes the figures of the reference's ``cfg_specs`` table below.  Options this
-package cannot honour are refused with the reason, not ignored."""
+package cannot honour are refused with the reason, not ignored.
+
+A run writes ``training-state-<kimg>.pt`` next to every network snapshot (``--save-state``) and stops at the next tick on SIGTERM
+or SIGUSR1 with snapshot and state written; ``--continue=<run directory or state file>`` goes on from there, bit for bit, with
+the options the state file recorded:
+
+    python train_wo_flow_fullbody.py --outdir=runs --data=<training tree> --continue=runs/00000-...
+"""
 
 import json
 import os
 import re
+import signal
 import tempfile
 
 import click
@@ -37,7 +45,7 @@ SUPPORTED_METRICS = ('recon_full', 'recon2k')       # metrics/metric_main.py; th
 def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
-                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False):
+                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -58,6 +66,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                         ' (evaluated without those weights: ' + ', '.join(SUPPORTED_METRICS) + ')')
     args.metrics = metrics
     args.random_seed = 0 if seed is None else seed
+    args.save_state = True if save_state is None else bool(save_state)
 
     # Dataset: data, cond, subset, mirror (:115-155)
     assert isinstance(data, str)
@@ -211,15 +220,128 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
 
 #----------------------------------------------------------------------------
 
+# what --continue may be combined with (besides --outdir and --data): these replace the recorded values, everything else is the run's
+CONTINUE_MAY_CHANGE = ('kimg', 'snap', 'metrics', 'metrics_data', 'workers', 'save_state')
+
+def find_state_file(path):
+    """``--continue``'s PATH -> the state file: the path itself, or the one with the highest kimg of a run directory."""
+    from training import train_state
+    if os.path.isdir(path):
+        found = train_state.state_files(path)
+        if not found:
+            raise UserError(f'--continue={path}: the directory holds no training-state-*.pt (was the run started with --save-state=false?)')
+        return found[-1][1]
+    if not os.path.isfile(path):
+        raise UserError(f'--continue={path}: neither a run directory nor a training-state-*.pt file')
+    return path
+
+def setup_continue_kwargs(continue_path, data=None, **given):
+    """``--continue``: (run description, keyword arguments of ``training_loop``) from the options the state file recorded."""
+    from training import train_state
+    state_file = os.path.abspath(find_state_file(continue_path))
+    try:
+        state = train_state.load_state(state_file, mmap=True)      # the options and the counters; no tensor is read
+    except (ValueError, RuntimeError, OSError) as err:
+        raise UserError(f'--continue: {err}')
+    if not state.get('options'):
+        raise UserError(f'--continue={continue_path}: the state file records no options (it was not written by this command)')
+    args = json.loads(state['options'], object_hook=dnnlib.EasyDict)
+    kimg_done = int(state['cur_nimg']) // 1000
+    del state
+
+    given = {name: value for name, value in given.items() if value is not None}
+    for name, value in given.items():
+        recorded = {'gpus': args.num_gpus, 'batch': args.batch_size}.get(name)
+        if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
+            continue
+        option = '--' + ('allow-tf32' if name == 'allow_tf32' else name)
+        raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
+                        (f' ({recorded})' if recorded is not None else ''))
+
+    # the data: the tree may have moved; it must still be the recorded set
+    assert isinstance(data, str)
+    recorded = args.training_set_kwargs
+    class_name = training_set_class(data)
+    try:
+        training_set = dnnlib.util.construct_class_by_name(**dict(recorded, class_name=class_name, path=data, max_size=None))
+        people, resolution = len(training_set), training_set.resolution
+        del training_set
+    except IOError as err:
+        raise UserError(f'--data: {err}')
+    if class_name != recorded.class_name:
+        raise UserError(f'--data: a tree of {class_name.rsplit(".", 1)[-1]}, the run was recorded on {recorded.class_name.rsplit(".", 1)[-1]}')
+    if resolution != recorded.resolution:
+        raise UserError(f'--data: resolution {resolution}, the run was recorded at {recorded.resolution}')
+    subset = 'random_seed' in recorded          # --subset: max_size is the subset's size, the tree's own size was not recorded
+    if (people < recorded.max_size) if subset else (people != recorded.max_size):
+        raise UserError(f'--data: {people} people, the run was recorded on {"a subset of " if subset else ""}{recorded.max_size}')
+    recorded.path = data
+
+    if 'kimg' in given:
+        if not given['kimg'] >= 1:
+            raise UserError('--kimg must be at least 1')
+        args.total_kimg = given['kimg']
+    if 'snap' in given:
+        if given['snap'] < 1:
+            raise UserError('--snap must be at least 1')
+        args.image_snapshot_ticks = args.network_snapshot_ticks = given['snap']
+    if 'metrics' in given:
+        refused = [m for m in given['metrics'] if m not in SUPPORTED_METRICS]
+        if refused:
+            raise UserError('--metrics: not evaluated: ' + ', '.join(refused) + ' (evaluated: ' + ', '.join(SUPPORTED_METRICS) + ')')
+        args.metrics = list(given['metrics'])
+        if not args.metrics:
+            args.metric_set_kwargs = None
+    if 'metrics_data' in given:
+        if not args.metrics:
+            raise UserError('--metrics_data needs --metrics')
+        metrics_data = given['metrics_data']
+        args.metric_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(metrics_data), path=metrics_data, use_labels=False,
+                                                 max_size=None, xflip=False)
+        try:
+            metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
+            if metric_set.resolution != recorded.resolution:
+                raise UserError(f'--metrics_data: resolution {metric_set.resolution}, the training data has {recorded.resolution}')
+            del metric_set
+        except IOError as err:
+            raise UserError(f'--metrics_data: {err}')
+    if 'workers' in given:
+        if not given['workers'] >= 1:
+            raise UserError('--workers must be at least 1')
+        args.data_loader_kwargs.num_workers = given['workers']
+        args.data_loader_kwargs.prefetch_factor = 2
+    if 'save_state' in given:
+        args.save_state = bool(given['save_state'])
+
+    # <recorded description>-continue<kimg>; a run continued twice keeps one suffix
+    desc = re.sub(r'^\d+-', '', os.path.basename(os.path.normpath(args.pop('run_dir', '') or 'run')))
+    desc = re.sub(r'-continue\d{6}$', '', desc) + f'-continue{kimg_done:06d}'
+    args.pop('resume_pkl', None)        # the networks come from the state file; cfg stays as that run had it
+    args.resume_state = state_file
+    return desc, args
+
+#----------------------------------------------------------------------------
+
+def install_abort_signals(signals=(signal.SIGTERM, signal.SIGUSR1)):
+    """Handlers that set a flag; returns the flag's reader, which is the loop's ``abort_fn``: the run ends at the next tick
+    boundary with image, snapshot and state written.  A second signal changes nothing."""
+    flag = []
+    def handler(signum, frame):
+        flag.append(signum)
+    for signum in signals:
+        signal.signal(signum, handler)
+    return lambda: bool(flag)
+
 def subprocess_fn(rank, args, temp_dir):
     from torch_utils import training_stats
+    abort_fn = install_abort_signals()
     dnnlib.util.Logger(file_name=os.path.join(args.run_dir, 'log.txt'), file_mode='a', should_flush=True)
     if args.num_gpus > 1:
         init_file = os.path.abspath(os.path.join(temp_dir, '.torch_distributed_init'))
         torch.distributed.init_process_group(backend='nccl', init_method=f'file://{init_file}', rank=rank, world_size=args.num_gpus)
     sync_device = torch.device('cuda', rank) if args.num_gpus > 1 else None
     training_stats.init_multiprocessing(rank=rank, sync_device=sync_device)
-    training_loop.training_loop(rank=rank, **args)
+    training_loop.training_loop(rank=rank, abort_fn=abort_fn, **args)
 
 #----------------------------------------------------------------------------
 
@@ -241,6 +363,9 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--metrics_data', help='Tree the metrics are evaluated on [default: the training data]', metavar='PATH')
 @click.option('--seed', help='Random seed [default: 0]', type=int, metavar='INT')
 @click.option('-n', '--dry-run', help='Print training options and exit', is_flag=True)
+@click.option('--save-state', help='Write a training-state file with every network snapshot [default: true]', type=bool, metavar='BOOL')
+@click.option('--continue', 'continue_path', help='Continue the run of this directory or training-state-*.pt file, with its recorded options',
+              metavar='PATH')
 # Dataset.
 @click.option('--data', help='Training data (directory)', metavar='PATH', required=True)
 @click.option('--cond', help='Not supported [default: false]', type=bool, metavar='BOOL')
@@ -272,10 +397,13 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--contextual_weight', help='contextual loss weight', type=float)
 @click.option('--mask_weight', type=float)
 @click.option('--use_noise_const_branch', help='Enable const_branch noise input?', type=bool, metavar='BOOL')
-def main(ctx, outdir, dry_run, **config_kwargs):
+def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
     """Train PASTA-GAN's full-body try-on model on the reference's training tree."""
     try:
-        run_desc, args = setup_training_loop_kwargs(**config_kwargs)
+        if continue_path is not None:
+            run_desc, args = setup_continue_kwargs(continue_path, **config_kwargs)
+        else:
+            run_desc, args = setup_training_loop_kwargs(**config_kwargs)
     except UserError as err:
         ctx.fail(str(err))
 
@@ -316,7 +444,18 @@ def main(ctx, outdir, dry_run, **config_kwargs):
         if args.num_gpus == 1:
             subprocess_fn(rank=0, args=args, temp_dir=temp_dir)
         else:
-            torch.multiprocessing.spawn(fn=subprocess_fn, args=(args, temp_dir), nprocs=args.num_gpus)
+            # the children's handlers end the run; this process hands both signals on to them and waits
+            context = torch.multiprocessing.spawn(fn=subprocess_fn, args=(args, temp_dir), nprocs=args.num_gpus, join=False)
+            def forward(signum, frame):
+                for pid in context.pids():
+                    try:
+                        os.kill(pid, signum)
+                    except ProcessLookupError:
+                        pass
+            for signum in (signal.SIGTERM, signal.SIGUSR1):
+                signal.signal(signum, forward)
+            while not context.join():
+                pass
 
 #----------------------------------------------------------------------------
 

@@ -101,6 +101,24 @@ class _ColorAffine(torch.autograd.Function):
 
 #----------------------------------------------------------------------------
 
+def _reflect_pad(x, pad):
+    """``torch.nn.functional.pad(x, pad, mode='reflect')`` of the last two axes, ``pad`` = [left, right, top, bottom], built from
+    slices, flips and one ``cat`` per axis: the same values, and a gradient (of any order) that is again slices, flips and
+    additions in a fixed order.  ATen's reflection_pad2d_backward scatters with float atomics on the GPU, which made the R1 pass
+    behind the pipeline -- and with it a whole training run -- differ from run to run in its last bits."""
+    def axis(x, dim, lo, hi):
+        if lo < 0 or hi < 0:        # a negative margin crops, as in torch's pad
+            x = x.narrow(dim, max(-lo, 0), x.shape[dim] - max(-lo, 0) - max(-hi, 0))
+            lo, hi = max(lo, 0), max(hi, 0)
+        n = x.shape[dim]
+        if not (lo < n and hi < n):
+            raise ValueError(f'reflect padding ({lo}, {hi}) must be smaller than the axis ({n})')
+        parts = ([x.narrow(dim, 1, lo).flip(dim)] if lo else []) + [x] + ([x.narrow(dim, n - 1 - hi, hi).flip(dim)] if hi else [])
+        return torch.cat(parts, dim) if len(parts) > 1 else x
+    left, right, top, bottom = (int(v) for v in pad)
+    return axis(axis(x, x.ndim - 1, left, right), x.ndim - 2, top, bottom)
+
+
 @persistence.persistent_class
 class AugmentPipe(torch.nn.Module):
     """augment.py:121-431.  All augmentations are off by default; a multiplier of 1 enables one."""
@@ -175,7 +193,7 @@ class AugmentPipe(torch.nn.Module):
         if geometry:        # pad (reflect) -> 2x up -> resample under G_inv -> 2x down and crop (augment.py:268-301)
             mx0, my0, mx1, my1 = margins.tolist()
             hz_pad = self.Hz_geom.shape[0] // 4
-            images = torch.nn.functional.pad(input=images, pad=[mx0, mx1, my0, my1], mode='reflect')
+            images = _reflect_pad(images, [mx0, mx1, my0, my1])
             images = upfirdn2d.upsample2d(x=images, f=self.Hz_geom, up=2)
             out_h, out_w = (height + hz_pad * 2) * 2, (width + hz_pad * 2) * 2
             # pixel_out -> pixel_in in normalised coordinates of the sampling grid: A @ G_inv @ B with
@@ -222,7 +240,7 @@ class AugmentPipe(torch.nn.Module):
             taps = (g @ self.Hz_fbank).unsqueeze(1).repeat([1, num_channels, 1]).reshape([batch_size * num_channels, 1, -1])
             pad = self.Hz_fbank.shape[1] // 2
             images = images.reshape([1, batch_size * num_channels, height, width])
-            images = torch.nn.functional.pad(input=images, pad=[pad, pad, pad, pad], mode='reflect')
+            images = _reflect_pad(images, [pad, pad, pad, pad])
             images = conv2d_gradfix.conv2d(input=images, weight=taps.unsqueeze(2), groups=batch_size * num_channels)
             images = conv2d_gradfix.conv2d(input=images, weight=taps.unsqueeze(3), groups=batch_size * num_channels)
             images = images.reshape([batch_size, num_channels, height, width])

@@ -9,7 +9,8 @@ with backward: by default through one ``FlatGradReducer`` per optimised module (
 training/grad_reducer.py), or through the reference's five DistributedDataParallel wrappers (``ddp_mode='torch'``).
 
 With a ``run_dir``, ``training_loop`` is the reference's whole loop (:247-654): ticks counted in kimg, the status line,
-stats.jsonl, the sample-image grid (training/snapshot_grid.py), network snapshots, resuming and aborting; the statistics
+stats.jsonl, the sample-image grid (training/snapshot_grid.py), network snapshots, resuming and aborting, and -- beyond the
+reference -- a training-state file per network snapshot from which a run continues bit for bit (training/train_state.py); the statistics
 accumulate on the device (torch_utils/training_stats.py) and none of it touches ``TrainingStep.run``'s arithmetic.  With
 ``metrics``, every network snapshot is scored on all ranks (metrics/; the reference has this call commented out, :604-614).
 ``SyntheticFullBodyBatch`` supplies tensors of the dataset's shapes (training_loop...:289-297, 425-456)
@@ -217,6 +218,7 @@ class TrainingStep:
                 self.phases += [dnnlib.EasyDict(name=name + 'reg', module=module, opt=opt, interval=reg_interval)]
         for phase in self.phases:           # set by whoever wants phase timings (:344-349); recorded in run() when present
             phase.start_event = phase.end_event = None
+            phase.timed = False             # the events have been recorded (a continued run has not yet run every phase at its first tick)
         self.batch_idx = 0
         self.cur_nimg = 0
         self._buf_versions = {}         # G buffer index -> version counter at its last copy into G_ema
@@ -255,6 +257,7 @@ class TrainingStep:
             phase.opt.step()
             if phase.end_event is not None:
                 phase.end_event.record(torch.cuda.current_stream(self.device))
+                phase.timed = True
 
         ema_nimg = self.ema_kimg * 1000
         if self.ema_rampup is not None:
@@ -289,12 +292,14 @@ class TrainingStep:
 
 #----------------------------------------------------------------------------
 
-def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs):
-    """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263)."""
+def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs, cur_nimg=0):
+    """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263).  ``cur_nimg``: the images
+    a continued run has consumed; one iteration takes ``batch_size`` positions of the sampler's global stream whatever the
+    number of ranks, so the stream goes on at that position."""
     from training import dataset as dataset_module
     from training.tryon_batch import builder_for
     training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
-    sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed)
+    sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed, skip=cur_nimg)
     loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
                                          collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
     builder = builder_for(training_set, device)
@@ -303,19 +308,26 @@ def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
                   training_set_kwargs=None, data_loader_kwargs=None, run_dir=None, total_kimg=25000, kimg_per_tick=4,
                   image_snapshot_ticks=50, network_snapshot_ticks=50, resume_pkl=None, abort_fn=None, snapshot_gnum=23, metrics=None,
-                  metric_set_kwargs=None):
+                  metric_set_kwargs=None, save_state=False, resume_state=None):
     """Without ``run_dir``: run ``total_iters`` iterations and write nothing.  Without ``training_set_kwargs`` the data is
     synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
     path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
     ``training.tryon_batch.builder_for``'s builder (``UvitonDatasetFull_512``: the 512 x 320 one).
     With ``run_dir`` (and a data set): the reference's loop until ``total_kimg`` (``training_run`` below); ``total_iters`` is unused.
     ``metrics`` (names of metrics/metric_main.py) are evaluated on G_ema after every network snapshot, on ``metric_set_kwargs``
-    (default: the training set's)."""
+    (default: the training set's).
+    ``save_state``: every tick that writes a network snapshot also writes ``training-state-<kimg>.pt`` (training/train_state.py),
+    the newest one kept.  ``resume_state``: the path of such a file; the run goes on from it exactly where the other stopped.
+    The state file records the text of ``run_dir``'s training_options.json, when the command line has written one, for ``--continue``."""
     device = device if device is not None else torch.device('cuda', rank)
+    if resume_state is not None and run_dir is None:
+        raise ValueError('resume_state needs a run_dir: only a training run is continued')
+    if resume_state is not None and resume_pkl is not None:
+        raise ValueError(f'resume_state={resume_state!r} and resume_pkl={resume_pkl!r}: a continued run takes its networks from the state file')
     if run_dir is not None:
         return training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs,
                             data_loader_kwargs, total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn,
-                            snapshot_gnum, metrics, metric_set_kwargs)
+                            snapshot_gnum, metrics, metric_set_kwargs, save_state, resume_state)
     step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
     if training_set_kwargs is None:
         data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
@@ -339,11 +351,21 @@ def sample_images(G_ema, grid, grid_z, batch_gpu):
 
 def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs, data_loader_kwargs,
                  total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn, snapshot_gnum, metrics=None,
-                 metric_set_kwargs=None):
+                 metric_set_kwargs=None, save_state=False, resume_state=None):
     """The reference's training_loop (:247-654) around ``TrainingStep.run``.  Returns the step; on rank 0 it carries the
     ``snapshot_grid`` and the ``grid_z`` the sample images were drawn with."""
     import psutil
-    start_time = time.time()
+    from training import train_state
+    start_time = launch_time = time.time()
+    state = None
+    if resume_state is not None:        # every rank reads the file: its own generators and w_avg are in it
+        state = train_state.load_state(resume_state)
+        train_state.check_run(state, num_gpus=num_gpus, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
+        start_time -= float(state['elapsed_sec'])       # Timing/total_* go on from the wall clock of the run so far
+    options_json = ''
+    if save_state and rank == 0 and os.path.isfile(os.path.join(run_dir, 'training_options.json')):
+        with open(os.path.join(run_dir, 'training_options.json'), 'rt') as f:
+            options_json = f.read()
     if training_set_kwargs is None:
         raise ValueError('a training run needs training_set_kwargs: the sample grid is made of the data set\'s train_img_vis people')
     cfg = dnnlib.EasyDict(cfg if cfg is not None else fashion_config(mbstd_group_size=min(batch_gpu, 4)))
@@ -351,7 +373,8 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
 
     if rank == 0:
         print('Loading training set...')
-    training_set, builder, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs)
+    training_set, builder, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs,
+                                                   cur_nimg=int(state['cur_nimg']) if state is not None else 0)
     if rank == 0:
         print()
         print('Num images: ', len(training_set))
@@ -382,7 +405,16 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
         grid = SnapshotGrid.setup(training_set, builder, device, gnum=snapshot_gnum)
         grid.save_init(run_dir)
         step.snapshot_grid = grid
-        step.grid_z = torch.randn([grid.cells, G.z_dim], device=device).split(batch_gpu)       # drawn once (:376)
+        if state is None:
+            step.grid_z = torch.randn([grid.cells, G.z_dim], device=device).split(batch_gpu)       # drawn once (:376)
+        else:
+            if tuple(state['grid_z'].shape) != (grid.cells, G.z_dim):
+                raise ValueError(f'grid_z: {tuple(state["grid_z"].shape)} in the state file, this run\'s grid needs {(grid.cells, G.z_dim)}')
+            step.grid_z = state['grid_z'].to(device).split(batch_gpu)
+    if state is not None:
+        if rank == 0:
+            print(f'Continuing from "{resume_state}"')
+        train_state.restore(step, state)
 
     if rank == 0:
         print('Initializing logs...')
@@ -402,21 +434,28 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
         print(f'Training for {total_kimg} kimg...')
         print()
     total_nimg = total_kimg * 1000
-    cur_tick = 0
+    cur_tick = int(state['cur_tick']) if state is not None else 0
     tick_start_nimg = step.cur_nimg
     tick_start_time = time.time()
-    maintenance_time = tick_start_time - start_time
+    maintenance_time = tick_start_time - launch_time
     if progress_fn is not None:
         progress_fn(0, total_kimg)
     while True:
         if step.cur_nimg < total_nimg:          # total_kimg = 0: no iteration at all, one tick of maintenance (a resumed state written back)
-            step.run(next(batches))
+            batch = next(batches)
+            if state is not None:               # the generators last of all: the first fetch starts the loader, which draws its base seed
+                train_state.restore_rng(step, state)
+                state = None
+            step.run(batch)
+        elif state is not None:                 # nothing left to train: the state written below carries the generators on
+            train_state.restore_rng(step, state)
+            state = None
         cur_nimg = step.cur_nimg
 
         # Perform maintenance tasks once per tick.
         done = (cur_nimg >= total_nimg)
-        if (not done) and (cur_tick != 0) and (cur_nimg < tick_start_nimg + kimg_per_tick * 1000):
-            continue
+        if (not done) and (cur_tick != 0 or resume_state is not None) and (cur_nimg < tick_start_nimg + kimg_per_tick * 1000):
+            continue        # (a continued run has no tick 0: its first maintenance round is the next regular tick)
 
         # Print status line, accumulating the same information in stats_collector.
         tick_end_time = time.time()
@@ -438,7 +477,12 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
             print(' '.join(fields))
 
         # Check for abort.
-        if (not done) and (abort_fn is not None) and abort_fn():
+        abort = (not done) and (abort_fn is not None) and bool(abort_fn())
+        if num_gpus > 1 and abort_fn is not None:       # one answer for all ranks: a rank that stopped alone would leave the others waiting
+            flag = torch.tensor([int(abort)], dtype=torch.int32, device=device)
+            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MAX)
+            abort = (not done) and bool(flag.item())
+        if abort:
             done = True
             if rank == 0:
                 print()
@@ -480,7 +524,7 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
         # Collect statistics.
         for phase in step.phases:
             value = []
-            if (phase.start_event is not None) and (phase.end_event is not None) and step.batch_idx > 0:
+            if (phase.start_event is not None) and (phase.end_event is not None) and step.batch_idx > 0 and phase.timed:
                 phase.end_event.synchronize()
                 value = phase.start_event.elapsed_time(phase.end_event)
             report0('Timing/' + phase.name, value)
@@ -506,6 +550,21 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
         # Update state.
         cur_tick += 1
         tick_start_nimg = cur_nimg
+
+        # Save the training state: the last act of the tick's maintenance, so that the next thing that happens is step.run.
+        if save_state and snapshot_pkl is not None:
+            extras = dict(cur_tick=cur_tick, elapsed_sec=time.time() - start_time, random_seed=int(random_seed), options=options_json)
+            if rank == 0:
+                extras['grid_z'] = torch.cat(step.grid_z)
+            state_pt = os.path.join(run_dir, f'training-state-{cur_nimg//1000:06d}.pt')
+            if train_state.save_state(state_pt, step, extras) is not None:
+                for _, older in train_state.state_files(run_dir):
+                    if os.path.abspath(older) != os.path.abspath(state_pt):
+                        os.remove(older)
+            if num_gpus > 1:        # nobody goes on (or returns, to read the file) before rank 0 has written it
+                written = torch.zeros([1], device=device)
+                torch.distributed.all_reduce(written)
+                written.item()
         tick_start_time = time.time()
         maintenance_time = tick_start_time - tick_end_time
         if done:
