@@ -6,7 +6,9 @@ registers: the paired-reconstruction metrics ``recon_full`` and ``recon2k``).
 
 Without --data the snapshot's own ``training_set_kwargs`` name the tree; --data names another one of the same layout (a held-out
 tree; a tree of ``*_512_320`` folders is read as the 512 x 320 training set).  When the snapshot lies in a training run's directory (one with training_options.json), the result is also appended to
-that directory's ``metric-<name>.jsonl``.  --network must name a local file: URLs are refused (nothing is downloaded).  One
+that directory's ``metric-<name>.jsonl``.  --network must name a local file: URLs are refused (nothing is downloaded).
+--storage f32 | bf16 | f16 scores the generator in that activation storage, whatever it was pickled with; the result line then
+carries a ``storage`` field.  One
 process per GPU; for more than one GPU fresh processes are spawned, each loading the snapshot itself."""
 
 import json
@@ -15,6 +17,8 @@ import re
 import tempfile
 
 import click
+
+import tryon_cli
 
 #----------------------------------------------------------------------------
 
@@ -32,6 +36,9 @@ def subprocess_fn(rank, args, temp_dir):
         print(f'Loading network from "{args.network_pkl}"...')
     with open(args.network_pkl, 'rb') as f:
         G = legacy.load_network_pkl(f)['G_ema'].eval().requires_grad_(False).to(device)
+    if args.storage is not None and args.storage != 'snapshot':
+        from training.networks import set_activation_storage
+        set_activation_storage(G, tryon_cli.STORAGE_DTYPES[args.storage])
     for metric in args.metrics:
         if verbose:
             print(f'Calculating {metric}...')
@@ -39,6 +46,8 @@ def subprocess_fn(rank, args, temp_dir):
         result_dict = metric_main.calc_metric(metric=metric, G=G, dataset_kwargs=args.dataset_kwargs, num_gpus=args.num_gpus, rank=rank,
                                               device=device, progress=progress, batch_size=args.batch_size,
                                               data_loader_kwargs=dict(num_workers=args.workers, pin_memory=True))
+        if args.storage is not None:
+            result_dict.storage = args.storage
         if rank == 0:
             metric_main.report_metric(result_dict, run_dir=args.run_dir, snapshot_pkl=args.network_pkl)
         if verbose:
@@ -69,11 +78,13 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--batch', 'batch_size', help='Items per batch and GPU (the results do not depend on it)', type=click.IntRange(min=1), default=16,
               show_default=True)
 @click.option('--workers', help='Loader processes (file decoding only)', type=click.IntRange(min=0), default=0, show_default=True)
-def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, workers):
+@tryon_cli.storage_option
+def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, workers, storage):
     """Calculate quality metrics of a network snapshot on a tree of the training set's layout."""
     import dnnlib
     from metrics import metric_main
-    args = dnnlib.EasyDict(metrics=metrics, num_gpus=gpus, network_pkl=network_pkl, verbose=verbose, batch_size=batch_size, workers=workers)
+    args = dnnlib.EasyDict(metrics=metrics, num_gpus=gpus, network_pkl=network_pkl, verbose=verbose, batch_size=batch_size, workers=workers,
+                           storage=storage)
     unknown = [m for m in args.metrics if not metric_main.is_valid_metric(m)]
     if unknown:
         ctx.fail('\n'.join(['--metrics: unknown metric ' + ', '.join(unknown), 'valid metrics: ' + ', '.join(metric_main.list_valid_metrics())]))

@@ -96,6 +96,10 @@ def compute_partials(opts):
     rounds = (num_items - 1) // opts.num_gpus + 1
     subset = [i * opts.num_gpus + opts.rank for i in range(rounds) if i * opts.num_gpus + opts.rank < num_items]
     G = copy.deepcopy(opts.G).eval().requires_grad_(False).to(opts.device)
+    # a copy is rebuilt from the recorded constructor arguments: a storage switched at run time (calc_metrics.py --storage) is handed on
+    from training.networks import activation_storage, set_activation_storage
+    if activation_storage(G) != activation_storage(opts.G):
+        set_activation_storage(G, activation_storage(opts.G))
     builder = builder_for(dataset, opts.device)
     loader = torch.utils.data.DataLoader(dataset, sampler=subset, batch_size=opts.batch_size, collate_fn=dataset_module.collate,
                                          **opts.data_loader_kwargs)

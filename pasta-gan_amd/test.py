@@ -15,6 +15,7 @@ Differences from the reference, on purpose:
   --network must name a local file: URLs are refused (nothing is downloaded).
   --workers sets the loader's processes (the reference: 4).
   --seeds, --class and --projected-w are accepted and unused, as in the reference.
+  --storage f32 | bf16 | f16 runs the generator in that activation storage, whatever it was pickled with.
   --scores FILE scores every image by region against what the generator was told to reproduce (metrics/tryon_fidelity.py: kept
   body parts against the photograph, garment patches against themselves; L1, PSNR, SSIM) and writes one JSON object.  These are
   this project's own figures; the reference has none for test.py.
@@ -36,7 +37,8 @@ import tryon_cli
               'SSIM) and write the results to FILE as JSON. With this option z of pair i is np.random.RandomState(i).randn(z_dim), so that '
               'the figures describe the images whatever the batch size [default: no scores]', type=str, metavar='FILE')
 def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi: float, class_idx: Optional[int], noise_mode: str,
-                    projected_w: Optional[str], outdir: str, dataroot: str, batchsize: int, workers: int, scores_file: Optional[str]):
+                    projected_w: Optional[str], outdir: str, dataroot: str, batchsize: int, workers: int, scores_file: Optional[str],
+                    storage: Optional[str] = None):
     """Generate unpaired try-on images from the test pairs with a trained snapshot.
 
     \b
@@ -53,7 +55,7 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
     from training.tryon_pairs import TryOnPairBatchBuilder, images_to_u8
 
     device = torch.device('cuda')
-    G = tryon_cli.load_generator(network_pkl, device)
+    G = tryon_cli.load_generator(network_pkl, device, storage)
     os.makedirs(outdir, exist_ok=True)
     dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
     loader = tryon_cli.pair_loader(dataset, batchsize, workers)
@@ -85,7 +87,10 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
     print('finish: %d images under %s' % (written, outdir))
     if scores_file is not None:
         results = tryon_fidelity.finish(partials, 'tryon', pixels=pixels)
-        line = json.dumps(dict(results=results, pairs=written, network=network_pkl, dataroot=dataroot, noise_mode=noise_mode))
+        report = dict(results=results, pairs=written, network=network_pkl, dataroot=dataroot, noise_mode=noise_mode)
+        if storage is not None:
+            report['storage'] = storage
+        line = json.dumps(report)
         print(line)
         os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
         with open(scores_file, 'w') as f:

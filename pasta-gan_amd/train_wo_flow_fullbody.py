@@ -13,6 +13,9 @@ or SIGUSR1 with snapshot and state written; ``--continue=<run directory or state
 the options the state file recorded:
 
     python train_wo_flow_fullbody.py --outdir=runs --data=<training tree> --continue=runs/00000-...
+
+``--storage=bf16`` (or ``f16``) keeps the activations of G and of every block of D in that type; parameters, demodulation,
+statistics, the images and the loss stay fp32.
 """
 
 import json
@@ -40,12 +43,13 @@ CFG_SPECS = {
     'fashion':   dict(ref_gpus=8,  kimg=8000,  mb=32, mbstd=4,  fmaps=0.5, lrate=0.002, gamma=10, ema=10, ramp=None, map=1),
 }
 UNSUPPORTED_CFGS = ('paper256', 'paper512', 'paper1024', 'cifar')
+STORAGE_DTYPES = {None: None, 'f32': None, 'bf16': 'bfloat16', 'f16': 'float16'}      # --storage -> fashion_config's act_dtype
 SUPPORTED_METRICS = ('recon_full', 'recon2k')       # metrics/metric_main.py; the reference's detector metrics are refused
 
 def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
-                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None):
+                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -126,7 +130,11 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         spec.gamma = 0.0002 * (res ** 2) / spec.mb
         spec.ema = spec.mb * 10 / 32
     # mixed precision as the reference enables it (:195-196): the three highest resolutions of G and of D in fp16
-    config = training_loop.fashion_config(channel_base=int(spec.fmaps * 32768), d_fp16_res=3, mbstd_group_size=spec.mbstd, img_resolution=res)
+    # --storage: 16-bit activation storage in G and in every block of D, as fashion_config(act_dtype=) states it
+    if storage not in STORAGE_DTYPES:
+        raise UserError(f'--storage={storage} not supported')
+    config = training_loop.fashion_config(channel_base=int(spec.fmaps * 32768), d_fp16_res=3, mbstd_group_size=spec.mbstd, img_resolution=res,
+                                          act_dtype=STORAGE_DTYPES[storage])
     config.G_kwargs.mapping_kwargs.num_layers = spec.map
     if args.training_set_kwargs.class_name.endswith('UvitonDatasetFull_512'):
         config.G_kwargs.patch_channels = 45     # ten parts of the upper garment and five of the lower one (training/tryon_regions.py)
@@ -202,6 +210,11 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         config.D_kwargs.block_kwargs.freeze_layers = freezed
 
     # Performance options: fp32, nhwc, allow_tf32, workers (:354-383); --nobench is accepted and means nothing here (no cuDNN)
+    if STORAGE_DTYPES[storage] is not None:
+        if fp32:
+            raise UserError(f'--fp32=true and --storage={storage} contradict: --fp32 asks for fp32 activations in every block, '
+                            '--storage for 16-bit ones')
+        desc += f'-{storage}'
     if fp32:
         config.G_kwargs.synthesis_kwargs.num_fp16_res = config.D_kwargs.num_fp16_res = 0
         config.G_kwargs.synthesis_kwargs.conv_clamp = config.D_kwargs.conv_clamp = None
@@ -390,6 +403,8 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--nobench', help='Accepted for compatibility; no effect', type=bool, metavar='BOOL')
 @click.option('--allow-tf32', help='Use the three-product split-bf16 convolution arithmetic', type=bool, metavar='BOOL')
 @click.option('--workers', help='Override number of DataLoader workers', type=int, metavar='INT')
+@click.option('--storage', help='Activation storage of G and D: f32, or 16-bit (bf16, f16) with fp32 parameters and statistics [default: f32]',
+              type=click.Choice(['f32', 'bf16', 'f16']))
 # Loss weights.
 @click.option('--pl_weight', type=float)
 @click.option('--l1_weight', help='G L1 loss weight', type=float)

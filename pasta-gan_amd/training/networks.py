@@ -1040,12 +1040,14 @@ class _PoseStyleBlock(torch.nn.Module):
     extra_outputs = 0           # outputs of torgb_class besides the image
 
     def _build(self, in_channels, out_channels, w_dim, resolution, img_channels, is_last, architecture, resample_filter,
-               conv_clamp, use_fp16, fp16_channels_last, torgb_kwargs, layer_kwargs):
+               conv_clamp, use_fp16, fp16_channels_last, torgb_kwargs, layer_kwargs, half_dtype='float16'):
         assert architecture in ['orig', 'skip', 'resnet']
         self.in_channels, self.w_dim, self.resolution, self.img_channels = in_channels, w_dim, resolution, img_channels
         self.is_last, self.architecture, self.use_fp16 = is_last, architecture, use_fp16
         self.channels_last = bool(use_fp16 and fp16_channels_last)
-        self.half_dtype = torch.float16         # storage type of a use_fp16 block (the synthesis network may set bfloat16)
+        # storage type of a use_fp16 block (own extension: the synthesis network passes bfloat16 for BASELINE config 5).  A constructor
+        # argument, so that it is recorded with the block: persistence rebuilds every sub-module through its own constructor
+        self.half_dtype = _as_dtype(half_dtype) or torch.float16
         _attach_filter(self, resample_filter)
         styled = dict(w_dim=w_dim, resolution=resolution, conv_clamp=conv_clamp, channels_last=self.channels_last, **layer_kwargs)
         first = (in_channels == 0)
@@ -1107,10 +1109,10 @@ class SynthesisBlockFull(_PoseStyleBlock):
     torgb_class, extra_outputs = ToRGBLayerFull, 1
 
     def __init__(self, in_channels, out_channels, w_dim, resolution, img_channels, is_last, is_style=False, architecture='skip',
-                 resample_filter=[1,3,3,1], conv_clamp=None, use_fp16=False, fp16_channels_last=False, **layer_kwargs):
+                 resample_filter=[1,3,3,1], conv_clamp=None, use_fp16=False, fp16_channels_last=False, half_dtype='float16', **layer_kwargs):
         super().__init__()
         self._build(in_channels, out_channels, w_dim, resolution, img_channels, is_last, architecture, resample_filter, conv_clamp,
-                    use_fp16, fp16_channels_last, dict(is_style=is_style), layer_kwargs)
+                    use_fp16, fp16_channels_last, dict(is_style=is_style), layer_kwargs, half_dtype)
 
 @persistence.persistent_class
 class SynthesisBlockV18(_PoseStyleBlock):
@@ -1118,10 +1120,10 @@ class SynthesisBlockV18(_PoseStyleBlock):
     torgb_class, extra_outputs = ToRGBLayerV18, 2
 
     def __init__(self, in_channels, out_channels, w_dim, resolution, img_channels, is_last, architecture='skip',
-                 resample_filter=[1,3,3,1], conv_clamp=None, use_fp16=False, fp16_channels_last=False, **layer_kwargs):
+                 resample_filter=[1,3,3,1], conv_clamp=None, use_fp16=False, fp16_channels_last=False, half_dtype='float16', **layer_kwargs):
         super().__init__()
         self._build(in_channels, out_channels, w_dim, resolution, img_channels, is_last, architecture, resample_filter, conv_clamp,
-                    use_fp16, fp16_channels_last, dict(), layer_kwargs)
+                    use_fp16, fp16_channels_last, dict(), layer_kwargs, half_dtype)
 
 class _PatchRoutedSynthesis(torch.nn.Module):
     """Style pyramid b4 .. b<R>; three SPADE residual blocks at R/2 whose modulation maps come from the warped garment
@@ -1149,11 +1151,10 @@ class _PatchRoutedSynthesis(torch.nn.Module):
         self.spade_resolution = below
 
         def block(res, style):          # every block of the generator computes in fp32 (networks.py:5747-5748) unless act_dtype is set
-            b = self.block_class(width[res // 2] if res > 4 else 0, width[res], w_dim=w_dim, resolution=res, img_channels=img_channels,
-                                 is_last=(res == top), use_fp16=(self.act_dtype is not None), **self.block_kwargs_extra(style), **block_kwargs)
-            if self.act_dtype is not None:
-                b.half_dtype = self.act_dtype
-            return b
+            storage = dict() if self.act_dtype is None else dict(half_dtype=self.act_dtype)
+            return self.block_class(width[res // 2] if res > 4 else 0, width[res], w_dim=w_dim, resolution=res, img_channels=img_channels,
+                                    is_last=(res == top), use_fp16=(self.act_dtype is not None), **storage, **self.block_kwargs_extra(style),
+                                    **block_kwargs)
         self.num_ws = 0
         for res in self.block_resolutions:
             b = block(res, True)
@@ -1332,14 +1333,17 @@ class GeneratorV18(_TryOnGenerator):
 class DiscriminatorBlock(torch.nn.Module):
     """[fromrgb ->] 3x3 -> 3x3 /2, with a 1x1 /2 residual branch in the 'resnet' architecture (networks.py:916-996)."""
     def __init__(self, in_channels, tmp_channels, out_channels, resolution, img_channels, first_layer_idx, architecture='resnet',
-                 activation='lrelu', resample_filter=[1,3,3,1], conv_clamp=None, use_fp16=False, fp16_channels_last=False, freeze_layers=0):
+                 activation='lrelu', resample_filter=[1,3,3,1], conv_clamp=None, use_fp16=False, fp16_channels_last=False, freeze_layers=0,
+                 half_dtype='float16'):
         assert in_channels in [0, tmp_channels]
         assert architecture in ['orig', 'skip', 'resnet']
         super().__init__()
         self.in_channels, self.resolution, self.img_channels = in_channels, resolution, img_channels
         self.first_layer_idx, self.architecture, self.use_fp16 = first_layer_idx, architecture, use_fp16
         self.channels_last = bool(use_fp16 and fp16_channels_last)
-        self.half_dtype = torch.float16         # storage type of a use_fp16 block (Discriminator(half_dtype=...) may set bfloat16)
+        # storage type of a use_fp16 block (own extension: Discriminator(half_dtype='bfloat16') for BASELINE config 5); a constructor
+        # argument, so that it is recorded with the block (see _PoseStyleBlock._build)
+        self.half_dtype = _as_dtype(half_dtype) or torch.float16
         _attach_filter(self, resample_filter)
         # Freeze-D: layers are numbered through the whole discriminator; those below ``freeze_layers`` hold buffers
         plan = []
@@ -1444,10 +1448,11 @@ class Discriminator(torch.nn.Module):
             cmap_dim = width[4]
         shared = dict(img_channels=img_channels, architecture=architecture, conv_clamp=conv_clamp)
         layer_idx = 0
+        half = _as_dtype(half_dtype) or torch.float16                     # own extension: 'bfloat16' for BASELINE config 5
+        storage = dict() if half == torch.float16 else dict(half_dtype=half)
         for res in self.block_resolutions:
             blk = DiscriminatorBlock(width[res] if res < img_resolution else 0, width[res], width[res // 2], resolution=res,
-                                     first_layer_idx=layer_idx, use_fp16=(res >= first_fp16), **block_kwargs, **shared)
-            blk.half_dtype = _as_dtype(half_dtype) or torch.float16       # own extension: 'bfloat16' for BASELINE config 5
+                                     first_layer_idx=layer_idx, use_fp16=(res >= first_fp16), **storage, **block_kwargs, **shared)
             setattr(self, f'b{res}', blk)
             layer_idx += blk.num_layers
         if c_dim > 0:
@@ -1459,5 +1464,52 @@ class Discriminator(torch.nn.Module):
         for res in self.block_resolutions:
             x, img = getattr(self, f'b{res}')(x, img, **block_kwargs)
         return self.b4(x, img, self.mapping(None, c) if self.c_dim > 0 else None)
+
+#----------------------------------------------------------------------------
+# Activation storage of a network that exists already.
+
+def activation_storage(module):
+    """The 16-bit activation storage a try-on generator runs in at this moment (a torch dtype); None for fp32 and for any other module."""
+    return module.synthesis.act_dtype if isinstance(module, _TryOnGenerator) else None
+
+def set_activation_storage(module, dtype):
+    """Switch a generator (``GeneratorFull``, ``GeneratorV18``) or a ``Discriminator`` to the activation storage ``dtype``:
+    None or 'float32', 'bfloat16', 'float16', or the torch dtype.  Returns ``module``.
+
+    A generator gets what construction with ``synthesis_kwargs.act_dtype=dtype`` sets (``synthesis.act_dtype``; ``use_fp16`` and
+    ``half_dtype`` of every block b<res> and of texture_b<top>), a discriminator what ``half_dtype=dtype,
+    num_fp16_res=log2(res) - 2`` sets (every block b<R> .. b8).  None / 'float32': every block of a generator computes in fp32,
+    as without ``act_dtype``; a discriminator becomes the one of ``num_fp16_res=0``.  After the call the module computes bit
+    for bit what a module constructed with those arguments and the same state dict computes.
+
+    Parameters stay fp32 and no entry of the state dict changes.  This is a switch of the running module only: the recorded
+    ``init_kwargs`` are not touched, so a pickle OR A ``copy.deepcopy`` of the module (both rebuild it from those arguments) comes
+    back in the storage it was constructed with; whoever copies a switched module hands ``activation_storage(module)`` on to the copy
+    (metrics/reconstruction.py does).
+
+    A module built with ``fp16_channels_last=True`` is refused: there ``use_fp16`` also decided the memory format of the
+    blocks' weights at construction, which a switch afterwards cannot reproduce."""
+    if isinstance(dtype, torch.dtype):
+        assert dtype in (torch.float16, torch.bfloat16, torch.float32)
+        dtype = None if dtype == torch.float32 else dtype
+    dtype = _as_dtype(dtype)
+    if isinstance(module, _TryOnGenerator):
+        syn = module.synthesis
+        blocks = [getattr(syn, f'b{res}') for res in syn.block_resolutions] + [getattr(syn, f'texture_b{syn.img_resolution}')]
+    elif isinstance(module, Discriminator):
+        syn = None
+        blocks = [getattr(module, f'b{res}') for res in module.block_resolutions]
+    else:
+        raise TypeError(f'set_activation_storage: {type(module).__name__} is neither a try-on generator nor a Discriminator')
+    for b in blocks:
+        if b.channels_last or getattr(b, 'init_kwargs', {}).get('fp16_channels_last', False):
+            raise ValueError('set_activation_storage: the module was built with fp16_channels_last=True, whose weights took their '
+                             'memory format from use_fp16 at construction')
+    for b in blocks:
+        b.use_fp16 = dtype is not None
+        b.half_dtype = dtype or torch.float16
+    if syn is not None:
+        syn.act_dtype = dtype
+    return module
 
 #----------------------------------------------------------------------------
