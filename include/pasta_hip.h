@@ -227,34 +227,33 @@ int pasta_conv2d_tile(const pasta_conv_desc* d);
 int pasta_conv2d_pack_pair(const float* w, const pasta_conv_desc* da, void* ws_a, int64_t ws_a_bytes, const pasta_conv_desc* db, void* ws_b, int64_t ws_b_bytes,
                            void* stream, int* packed_mask);
 
+/* The forward-type kernels (conv2d, conv_transpose2d and both input gradients), as pasta_conv2d_plan names them.  The split kernels (1 - 8) run
+ * every split arithmetic and 16-bit storage; 9, 10 and 13 PASTA_MATH_F16X3 on fp32 tensors only. */
+enum {
+    PASTA_FWD_F32       = 0,   /* conv_fwd_kernel: fp32 MFMA, every shape */
+    PASTA_FWD_BASE      = 1,   /* conv_fwd_bf16x6_kernel: split arithmetic, any lattice */
+    PASTA_FWD_ROWS      = 2,   /* conv_fwd_rows_bf16x6_kernel: row reuse, 3-wide stride-1 kernels on rows of a multiple of 32 pixels */
+    PASTA_FWD_PAIR      = 3,   /* ... its parity-pair mode: 3x3 stride-2 conv_transpose2d onto 2H(+1) x 2W(+1), last row / column by conv_t2_edge_kernel */
+    PASTA_FWD_ROWS2D_R4 = 4,   /* conv_fwd_rows2d_bf16x6_kernel<128,128,4>: 3x3 stride 1, pixel tiles of 4 rows x 32 columns */
+    PASTA_FWD_ROWS2D_R2 = 5,   /* ... <128,128,2>: 2 rows x 64 columns */
+    PASTA_FWD_ROWS2D_R8 = 6,   /* ... <64,256,8>: 8 rows x 32 columns on the 64-channel tile */
+    PASTA_FWD_ROWS2D_WIDE = 7, /* ... eight waves on a 128 x 256 tile, fp32-equivalent products on fp32 tensors; takes PASTA_LAYOUT_PIECES16 */
+    PASTA_FWD_PACKED_K  = 8,   /* conv_fwd_bf16x6_kernel, K over (channel, tap) pairs: < 16 input channels, >= 64 pairs (the 7x7 RGB stems) */
+    PASTA_FWD_1X1       = 9,   /* conv1x1_f16x3_kernel: pointwise, >= 16 input and > 32 output channels, optionally two input tensors (x2) */
+    PASTA_FWD_3X3S2     = 10,  /* conv3x3s2_f16x3_kernel: 3x3 stride-2 conv2d, pads 0 / 1, power-of-two output widths; takes PASTA_LAYOUT_PIECES16 */
+    PASTA_FWD_FEWCIN    = 11,  /* conv1x1_fewcin_kernel: pointwise, <= 16 input channels, fp32 FMAs on the raw weights (*math = PASTA_MATH_F32) */
+    PASTA_FWD_FEWCOUT   = 12,  /* conv1x1_fewcout_kernel: pointwise, <= 16 output channels, likewise */
+    PASTA_FWD_T2        = 13   /* conv_t2_f16x3_kernel: 3x3 stride-2 conv_transpose2d, pad 0, onto 2H(+1) x 2W(+1) in one pass over the input lattice */
+};
+
 /* The full launch plan of pasta_conv2d(_ex) for d, for reporting (bench.py attributes time and FLOPs to kernel
  * families with it): *tile as pasta_conv2d_tile, *ksplit = number of K slices (> 1: partial sums in the workspace,
- * reduced by a second kernel), *math = PASTA_MATH_F32 or PASTA_MATH_BF16X6 actually used (launch_flags = OR of PASTA_PLAN_*:
- * what the launch will pass besides x, w, y -- an iscale vector, which the split-bf16 kernels take in their staging for fp32
- * storage and six products only; an oscale vector; a fused epilogue.  0 / 1 keep their round-2 meaning), *launches = launches of the main kernel (conv_transpose2d: one per output parity class unless the classes share a
- * grid), *kernel = 0 conv_fwd_kernel (fp32 MFMA), 1 conv_fwd_bf16x6_kernel, 2 conv_fwd_rows_bf16x6_kernel (split-bf16 with
- * row reuse: 3-wide stride-1 kernels on planes whose rows are a multiple of 32 pixels), 3 the same kernel's parity-pair
- * mode (3x3 stride-2 conv_transpose2d onto 2H(+1) x 2W(+1) outputs: one launch over the input lattice + one small
- * launch of kernel 1 for the last row / column), 4 / 5 / 6 conv_fwd_rows2d_bf16x6_kernel<128,128,4>, <128,128,2>, <64,256,8>: R output rows per
- * pixel tile (3x3 stride-1 lattices on the 128 x 128 tile whose planes divide into R x 128/R tiles: the R + 2 input rows of a
- * tile are staged once per 16-channel chunk), 7 the same kernel on eight waves and a 128 x 256 tile (<128,256,8,3,0,false,512>: plain
- * six-product fp32 launches on planes of a multiple of 8 rows; round 3: the launch of kernel 3's last row / column is
- * conv_t2_edge_kernel, and kernels 1 - 7 also run PASTA_MATH_F16X3), 8 conv_fwd_bf16x6_kernel in its packed-K mode (round 3: fewer than
- * 16 input channels, more than 32 output channels, at least 64 (channel, tap) pairs, planes above 8192 pixels -- the 7x7 RGB stems:
- * K runs over the pairs; the workspace then also holds the offset table and a zero-padded copy of the input, and two small
- * kernels fill them), 9 conv1x1_f16x3_kernel (round 4: 1x1 stride-1 convolutions and their input gradients under PASTA_MATH_F16X3, fp32 tensors,
- * >= 16 input and > 32 output channels, planes of a multiple of 128 / 256 pixels: 16-byte loads along the pixels, 32 channels per barrier pair,
- * optionally over two input tensors -- pasta_conv_desc.x2), 10 conv3x3s2_f16x3_kernel (round 4: 3x3 stride-2 conv2d with pads 0 / 1 under PASTA_MATH_F16X3,
- * fp32 tensors, >= 16 input and > 32 output channels, output widths 16 .. 128 .. that are powers of two: a round stages the input ROW segments of a kernel
- * row once, de-interleaved by pixel parity, for its three taps; round 5: with pasta_conv_desc.x_layout = PASTA_LAYOUT_PIECES16 its staging is a copy of
- * the producer's sixteen-byte pieces, no split), 11 / 12 conv1x1_fewcin_kernel / conv1x1_fewcout_kernel (round 5: 1x1 stride-1 launches with <= 16 input
- * or <= 16 output channels over more than 8192 pixels, fp32 tensors, one group, planes of a multiple of four pixels -- the RGB / pose stems, the ToRGB and
- * parsing heads and their input gradients: streaming kernels of plain fp32 FMAs on the raw weights, no packing launch, *math = PASTA_MATH_F32),
- * 13 conv_t2_f16x3_kernel (round 5: 3x3 stride-2 conv_transpose2d with pad 0 onto 2H(+1) x 2W(+1) outputs under PASTA_MATH_F16X3, fp32 tensors, >= 16
- * input channels, input planes of 8 x 32 or of 16 x 16 tiles, optionally an input scale, nothing behind the sum: ONE launch over the input
- * lattice computes the four output parity classes of a tile from one staged (8 + 1) x (32 + 1) window image -- nine taps, weights by LDS-DMA --
- * and the remainder row / column as edge tiles of the same grid; *launches = 1; the workspace also holds the input's last column, gathered by a
- * small kernel in front).  Kernel 7 also takes pasta_conv_desc.x_layout = PASTA_LAYOUT_PIECES16 (round 5).
+ * reduced by a second kernel), *math = the PASTA_MATH_* actually used (launch_flags = OR of PASTA_PLAN_*:
+ * what the launch will pass besides x, w, y -- an iscale vector, which the split kernels take in their staging for fp32
+ * storage and fp32-equivalent products only; an oscale vector; a fused epilogue), *launches = launches of the main kernel (conv_transpose2d:
+ * one per output parity class unless the classes share a grid), *kernel = PASTA_FWD_*.
+ * With PASTA_FWD_PACKED_K the workspace also holds the offset table and a zero-padded copy of the input, and two small kernels fill them; with
+ * PASTA_FWD_T2 the input's last column, gathered by a small kernel in front.
  * A conv_transpose2d launched as one launch per output parity class (*launches > 1: stride >= 3, or stride 2 on the fp32 kernel or onto a plane
  * under 2 x 2) reports the kernel of each class's launch: every class takes the same one.
  * pasta_conv2d_plan answers with the choice pasta_conv2d(_ex) / pasta_conv2d_modulated make for the same flags.  Any out pointer may be NULL. */
@@ -265,14 +264,18 @@ int pasta_conv2d_pack_pair(const float* w, const pasta_conv_desc* da, void* ws_a
 #define PASTA_PLAN_NOISE    16   /* the epilogue adds noise (pasta_conv_epilogue.noise; with PASTA_PLAN_EPILOGUE): not kernels 9 - 12 */
 int pasta_conv2d_plan(const pasta_conv_desc* d, int launch_flags, int* tile, int* ksplit, int* math, int* launches, int* kernel);
 
-/* Same for pasta_conv2d_wgrad: *kernel = 0 conv_wgrad_kernel (fp32 MFMA, taps x 64 x 64 tiles), 1
- * conv_wgrad_smallcin_kernel (<= 8 input channels: (channel, tap) pairs as GEMM columns), 2
- * conv_wgrad3x3_bf16x6_kernel (split-bf16; 3x3, stride 1, pad 1, row length a multiple of 32 -- round 5: or exactly 16, as half-filled chunks), 3
- * conv_wgrad3x3s2_bf16x6_kernel (split-bf16; 3x3, stride 2, pad 0 or 1, row length a multiple of 16), 4
- * conv_wgrad1x1_bf16x6_kernel (split-bf16; 1x1, stride 1, planes of a multiple of 32 pixels, >= 16 channels), 5
- * wgrad1x1_fewcin_kernel (round 4: 1x1, <= 8 input channels, planes of a multiple of 4 pixels: one bandwidth-bound fp32 pass over dy), 6
- * conv_wgrad3x3s2_pieces_kernel (round 5: kernel 3's shapes with pad 0 and x given as PASTA_LAYOUT_PIECES16: the x halo is copied into a
- * [pixel][channel] LDS image and the stride-2 tap operands are gathered by ds_read_b64_tr_b16, no split and no permutes).
+/* The weight-gradient kernels, as pasta_conv2d_wgrad_plan names them. */
+enum {
+    PASTA_WGRAD_F32      = 0,  /* conv_wgrad_kernel: fp32 MFMA, taps x 64 x 64 tiles, every shape */
+    PASTA_WGRAD_SMALLCIN = 1,  /* conv_wgrad_smallcin_kernel: <= 8 input channels, (channel, tap) pairs as GEMM columns */
+    PASTA_WGRAD_3X3      = 2,  /* conv_wgrad3x3_bf16x6_kernel: split; 3x3, stride 1, pad 1, rows of a multiple of 32 pixels, or of exactly 16 */
+    PASTA_WGRAD_3X3S2    = 3,  /* conv_wgrad3x3s2_bf16x6_kernel: split; 3x3, stride 2, pad 0 or 1, rows of a multiple of 16 pixels */
+    PASTA_WGRAD_1X1      = 4,  /* conv_wgrad1x1_bf16x6_kernel: split; 1x1, stride 1, planes of a multiple of 32 pixels, >= 16 channels */
+    PASTA_WGRAD_FEWCIN   = 5,  /* wgrad1x1_fewcin_kernel: 1x1, <= 8 input channels, planes of a multiple of 4 pixels, one fp32 pass over dy */
+    PASTA_WGRAD_3X3S2_PIECES = 6   /* conv_wgrad3x3s2_pieces_kernel: PASTA_WGRAD_3X3S2's shapes with pad 0 and x as PASTA_LAYOUT_PIECES16 */
+};
+
+/* Same for pasta_conv2d_wgrad: *kernel = PASTA_WGRAD_*.
  * The K slices of kernels 2 - 4 can be read off pasta_conv2d_wgrad_workspace, and tests/conv16_cases.py does: the workspace is 2 x 256 floats
  * (the operands' partial maxima) followed by one slab per slice of groups x kh x kw x A x B floats, A and B the two per-group channel counts
  * rounded up to the channel tile -- 64, or 128 for kernel 4 with more than 64 channels on both sides.  This layout is part of the contract. */

@@ -8,17 +8,9 @@
 #include <atomic>
 
 #include "../../include/pasta_hip.h"
+#include "host_common.h"      // pasta::fail, PASTA_CHECK, ceil_div64, floordiv, posmod
 
 namespace pasta {
-
-// Thread-local error text returned by pasta_last_error().
-char* error_buffer();
-int   fail(const char* fmt, ...);
-
-#define PASTA_CHECK(cond, ...)                         \
-    do {                                               \
-        if (!(cond)) return ::pasta::fail(__VA_ARGS__); \
-    } while (0)
 
 #define PASTA_HIP_CHECK(expr)                                                      \
     do {                                                                           \
@@ -133,19 +125,6 @@ __device__ __forceinline__ void amax_commit_block(uint32_t m, const AmaxSlot& a,
         for (int i = 1; i < NT / 64; i++) m = red[i] > m ? red[i] : m;
         if (m > a.seen && m > __hip_atomic_load(a.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.slot, m);
     }
-}
-
-static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// floor(a / b) for b > 0 and any sign of a.
-__host__ __device__ __forceinline__ int floordiv(int a, int b) {
-    int q = a / b;
-    return (a % b != 0 && a < 0) ? q - 1 : q;
-}
-// a mod b in [0, b) for b > 0.
-__host__ __device__ __forceinline__ int posmod(int a, int b) {
-    int r = a % b;
-    return r < 0 ? r + b : r;
 }
 
 }  // namespace pasta

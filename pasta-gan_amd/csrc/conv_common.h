@@ -1,7 +1,9 @@
-// Shared declarations of the convolution family (conv_igemm.hip and the kernel headers it includes).
+// Shared declarations of the convolution family: what the kernel headers and the launches of conv_igemm.hip have in common.  The constants the
+// kernels share with the planner (MAX_TAPS, NP_F16X3, AMAX_PARTS, FwdTile, wgrad_chunks, ...) are in conv_plan.h, plain C++.
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -14,8 +16,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));      // sixteen 
 #define PASTA_KEEP_SCALAR(x) asm("" : "+v"(x))
 // every component of a 16-byte vector counts as used: a partly used LDS read stays one ds_read_b128
 #define PASTA_KEEP_WHOLE(q) asm("" : "+v"((q).x), "+v"((q).y), "+v"((q).z), "+v"((q).w))
-
-constexpr int MAX_TAPS = 49;   // up to 7x7
 
 __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
@@ -188,8 +188,7 @@ template <int IO> __device__ __forceinline__ f32x16 io_mfma(bf16x8_t a, bf16x8_t
 // Scales: the tensor's |max| arrives as 256 partial maxima (pasta_tensor_amax: one pass at HBM rate, non-finite elements
 // skipped so that an inf / NaN stays local); every wave reduces them itself (one 16-byte load per lane) -- no finalising
 // launch, no atomics, no host round trip.
-constexpr int NP_F16X3 = 4;             // pseudo piece count of the template parameter NP: fp16 pieces, three products
-constexpr int AMAX_PARTS = 256;         // partial maxima per tensor
+// (NP_F16X3, the pseudo piece count of the template parameter NP, and AMAX_PARTS, the partial maxima per tensor: conv_plan.h)
 
 template <int NP> struct Arith {
     static constexpr bool f16x3 = NP == NP_F16X3;
@@ -435,11 +434,6 @@ static void conv_arith_dispatch(const ConvFwdParams& q, F&& f) {
     else                      f(integral_constant<int, 3>{}, F32{}, std::false_type{});
 }
 
-// Tile choice.  O_pad multiple returned so that the caller can pack weights accordingly.
-enum FwdTile { T128x128 = 0, T64x256 = 1, T32x256 = 2, T64x64 = 3 };
-
-static int fwd_tile_bm(FwdTile t) { return t == T128x128 ? 128 : t == T32x256 ? 32 : 64; }
-
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // Parameters of the weight-gradient kernels: dW[tap][a][b] = sum_pix S[a][pix] * L[b][pix * st + tap offset].
@@ -459,6 +453,29 @@ struct WgradParams {
     int a_tiles, b_tiles, tap_groups_r, tap_groups_s;
     int xcd_order;          // split weight-gradient kernels: workgroup order (0: K slice fastest; 1: see wgrad_workgroup)
     int l_pieces;           // conv_wgrad3x3s2_pieces_kernel: L is PASTA_LAYOUT_PIECES16 (pieces.hip), l_amax the producer's bound row
+};
+
+// Parameters of the few-channel pointwise kernels (conv_fwd_fewch.h).
+struct FewChParams {
+    const void* x; const float* w; void* y;      // x, y, res: elements of the storage type IO (fp32, or 16-bit storage: BASELINE config 5)
+    const float* iscale;            // [N][Cin] or null (fewcout only)
+    const float* bias; const void* res;
+    float* y_amax;
+    int io;                         // IO_F32 / IO_F16 / IO_BF16
+    int N, Cin, Cout, HW;
+    int w_io;                       // the weight tensor is [Cin][Cout] (conv_transpose2d), else [Cout][Cin]
+    float wscale;
+    int act; float alpha, gain, clamp;
+};
+
+// Parameters of the small-cin weight-gradient kernel (conv_wgrad_f32.h, conv_wgrad_smallcin_kernel).
+struct WgradSmallParams {
+    const float* S; const float* L; float* slab;
+    int N, Ag, P, Q;        // S = dy: [N, Ag, P, Q]
+    int Bg, LH, LW;         // L = x : [N, Bg, LH, LW]
+    int kh, kw, pad_h, pad_w;
+    int bprime, nb;         // Bg*kh*kw and its number of 32-column tiles (<= 5)
+    int cw_log2, rows_total, qblocks, chunks_total, ksplit, a_tiles;
 };
 
 //------------------------------------------------------------------------------------
@@ -587,20 +604,6 @@ static void wgrad_arith_dispatch(int np, int io, F&& f) {
     else if (np == 2)        f(integral_constant<int, 2>{}, F32{});
     else if (np == NP_F16X3) f(integral_constant<int, NP_F16X3>{}, F32{});
     else                     f(integral_constant<int, 3>{}, F32{});
-}
-
-// Chunk geometry of a weight gradient over rows of Q pixels: a chunk is kp lattice pixels, (kp >> cw_log2) rows of (1 << cw_log2) columns, the
-// width a power of two that shrinks to cover Q (keep_width: it stays kp).
-struct WgradChunks { int cw_log2, qblocks, chunks_total; };
-static WgradChunks wgrad_chunks(int kp, int rows_total, int Q, bool keep_width = false) {
-    WgradChunks c;
-    int cw = kp, lg = kp == 32 ? 5 : 4;
-    while (cw > 1 && cw / 2 >= Q && !keep_width) { cw /= 2; lg--; }
-    const int chh = kp / cw;
-    c.cw_log2 = lg;
-    c.qblocks = (Q + cw - 1) / cw;
-    c.chunks_total = ((rows_total + chh - 1) / chh) * c.qblocks;
-    return c;
 }
 
 }  // namespace pasta

@@ -985,12 +985,6 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
 }
 
-// Pixel tiles of the row-reuse kernel: full tiles of BN pixels made of whole row segments inside one image.
-static bool rows_tile_ok(int P, int Q, int BN) {
-    const int seg = Q < BN ? Q : BN;
-    return Q % 32 == 0 && (seg & (seg - 1)) == 0 && BN % seg == 0 && Q % seg == 0 && ((int64_t)P * Q) % BN == 0;
-}
-
 // The row-reuse kernel of one arithmetic / storage type (conv_tu_fwd_rows_*.hip; the lattice is made of whole row segments: the planner checked).
 // ISC: the input scale in the staging (fp32 storage, fp32-equivalent products: the forward of a modulated convolution; other arithmetics keep
 // the separate scaling pass).
@@ -1037,20 +1031,6 @@ static void launch_fwd_pair(const ConvFwdParams& p, hipStream_t s) {
     constexpr size_t lds = (size_t)(2 * APT * 256 * 8 + 2 * 2 * Arith<NP>::npb * (BN + 16) * 8) * sizeof(__bf16);
     PASTA_SET_LDS((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 2, NP, IO_F32, false, true>), lds);
     hipLaunchKernelGGL((conv_fwd_rows_bf16x6_kernel<BM, BN, 2, 2, NP, IO_F32, false, true>), grid, dim3(256), lds, s, q);
-}
-
-// Do the T taps at table positions [0, T) form rows of three horizontally adjacent offsets (ascending or descending)?
-static bool detect_tap_rows(ConvFwdParams& p, int T) {
-    p.rows = 0;
-    if (T % 3 != 0 || p.isx != 1 || p.isy != 1 || p.osx != 1 || p.osy != 1) return false;
-    const int step = p.tap_dx[1] - p.tap_dx[0];
-    if (step != 1 && step != -1) return false;
-    const int d0 = step == 1 ? p.tap_dx[0] : p.tap_dx[2];
-    for (int j = 0; j < T; j += 3)
-        for (int i = 0; i < 3; i++)
-            if (p.tap_dy[j + i] != p.tap_dy[j] || p.tap_dx[j + i] != p.tap_dx[0] + i * step) return false;
-    p.rows = 1; p.rows_d0 = d0; p.rows_rev = step == -1 ? 1 : 0;
-    return true;
 }
 
 

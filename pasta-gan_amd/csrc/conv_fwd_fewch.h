@@ -20,18 +20,6 @@
 
 namespace pasta {
 
-struct FewChParams {
-    const void* x; const float* w; void* y;      // x, y, res: elements of the storage type IO (fp32, or 16-bit storage: BASELINE config 5)
-    const float* iscale;            // [N][Cin] or null (fewcout only)
-    const float* bias; const void* res;
-    float* y_amax;
-    int io;                         // IO_F32 / IO_F16 / IO_BF16
-    int N, Cin, Cout, HW;
-    int w_io;                       // the weight tensor is [Cin][Cout] (conv_transpose2d), else [Cout][Cin]
-    float wscale;
-    int act; float alpha, gain, clamp;
-};
-
 // four consecutive elements at element index `idx` of `base` (a multiple of four: naturally aligned), as fp32 / from fp32
 template <int IO> __device__ __forceinline__ float4 fewch_ld4(const void* base, int64_t idx) { return io_ld4<IO>((const char*)base + idx * io_size<IO>::value); }
 template <int IO> __device__ __forceinline__ void fewch_st4(void* base, int64_t idx, float4 v) {
@@ -156,16 +144,6 @@ __global__ __launch_bounds__(256) void conv1x1_fewcout_kernel(FewChParams p) {
     amax_commit(am, aslot);
 }
 
-// Which of the two takes a launch (0: neither): fp32 or 16-bit tensors (the stored element is converted on the way in and out: fp32 FMAs), 1x1, stride 1, no padding, one group, plain weights, no output scale / noise,
-// planes of a multiple of four pixels, more than 8192 pixels (the K-sliced small-plane path keeps the rest); an input scale on the few-output side only.
-static int conv1x1_fewch_kind(const pasta_conv_desc* d, bool has_iscale, bool has_oscale, bool has_noise, bool modulated) {
-    if (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad_h || d->pad_w || d->groups != 1) return 0;
-    if (has_oscale || has_noise || modulated || d->x2 || d->x_layout || d->OH != d->H || d->OW != d->W) return 0;
-    const int64_t hw = (int64_t)d->H * d->W;
-    if (hw % 4 || (int64_t)d->N * hw <= 8192) return 0;
-    if (d->C_in <= 16 && !has_iscale && d->C_out >= 16 && d->C_out <= 512) return 1;
-    if (d->C_out <= 16 && d->C_in >= 16 && (int64_t)d->C_in * ((d->C_out + 3) & ~3) * 4 <= 64 * 1024) return 2;      // the launch's weights fit the default LDS window
-    return 0;
-}
+// (Which of the two takes a launch: conv1x1_fewch_kind, conv_plan.h.)
 
 }  // namespace pasta

@@ -429,13 +429,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
 }
 
-// Is the 2-D tile applicable: 3x3 stride-1 lattice (9 taps in 3 rows of 3, any order), planes divisible into R x (BN / R) tiles.
-template <int BN, int R>
-static bool rows2d_tile_ok(int P, int Q) {
-    constexpr int SEG = BN / R;
-    return P % R == 0 && Q % SEG == 0;
-}
-
+// (Which planes the 2-D tiles take: rows2d_tile_ok, rows2d_rows, rows2d_r8 of conv_plan.h.)
 template <int BM, int BN, int R, int NP, int IO, bool ISC = false, int NT = 256, bool XP = false>
 static void launch_fwd_rows2d_np(const ConvFwdParams& q, dim3 grid, hipStream_t s) {
     constexpr int SEG = BN / R, SLOTS = (R + 2) * (SEG + 2);
@@ -454,17 +448,5 @@ static void launch_fwd_rows2d(const ConvFwdParams& p, hipStream_t s) {
     dim3 grid((unsigned)tiles, q.o_tiles * q.ksplit, p.G);
     conv_arith_dispatch(q, [&](auto np, auto io, auto isc) { launch_fwd_rows2d_np<BM, BN, R, decltype(np)::value, decltype(io)::value, decltype(isc)::value>(q, grid, s); });
 }
-
-// Rows per 2-D tile for a P x Q lattice on the 128 x 128 tile: 4 (32-column segments), else 2 (64 columns), else 0 = the row kernel.
-static int rows2d_rows(int P, int Q) {
-    if (rows2d_tile_ok<128, 4>(P, Q)) return 4;
-    return rows2d_tile_ok<128, 2>(P, Q) ? 2 : 0;
-}
-
-// Eight waves on a 128 x 256 tile (8 rows x 32 columns; plain six-product fp32 launches): the weights of a step are fetched from L2
-// and stored to LDS once for 256 pixels instead of once for 128 -- +3.7 .. 6 % over the four-wave 128 x 128 tile on every live
-// shape (profiles/r2_rows2d.txt).  A 64 x 512 tile on eight waves (the 64-channel layers) spills and is 10 % slower: not kept.
-// The 64 x 256 tile takes the same planes as tiles of eight rows.
-static bool rows2d_r8(int P, int Q) { return rows2d_tile_ok<256, 8>(P, Q); }
 
 }  // namespace pasta

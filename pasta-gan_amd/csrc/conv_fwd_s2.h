@@ -259,12 +259,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_f16x3_kernel(ConvFwdParams p
     amax_commit(y_am, y_slot);
 }
 
-// Output planes of the stride-2 kernel: a width that is a power of two >= 16, planes that divide into 128-pixel tiles of whole rows.
-// (The rest of its conditions: choose_fwd, conv_igemm.hip.)
-static bool conv3x3s2_shape_ok(int OH, int OW) {
-    if (OW < 16 || (OW & (OW - 1))) return false;
-    const int seg = OW < 128 ? OW : 128, R = 128 / seg;
-    return OH % R == 0;
-}
+// (Which output planes the stride-2 kernel takes: conv3x3s2_shape_ok and choose_fwd, conv_plan.h.)
 
 }  // namespace pasta

@@ -1,9 +1,10 @@
 // Launch entry points of the convolution family's translation units.
 //
-// The planner and the C ABI live in conv_igemm.hip; every kernel family is compiled in a translation unit of its own (conv_tu_*.hip:
-// explicit instances behind plain host functions, built in parallel by torch_utils/custom_ops.py) and reached through the functions
-// declared here.  The kernel headers hold templates and host predicates only, so including them instantiates nothing; the few
-// non-template kernels are fenced by PASTA_TU_PACK / PASTA_TU_WGRAD_F32 and defined by exactly one unit.  What the forward-type kernels share
+// The planner is conv_plan.h (plain C++, no device code), the C ABI and the launches live in conv_igemm.hip; every kernel family is compiled in
+// a translation unit of its own (conv_tu_*.hip: explicit instances behind plain host functions, built in parallel by
+// torch_utils/custom_ops.py) and reached through the functions declared here -- conv_igemm.hip includes no kernel header.  The kernel headers
+// hold templates only, so including them instantiates nothing; the few non-template kernels are fenced by PASTA_TU_PACK / PASTA_TU_WGRAD_F32
+// and defined by exactly one unit.  What the forward-type kernels share
 // -- the epilogue of a 32 x 32 sub-tile (conv_store_subtile) and the choice of <NP, IO, ISC> for a launch (conv_arith_dispatch) -- is in
 // conv_common.h, and so is what the weight-gradient kernels share (wgrad_slice, wgrad_split_store8, WgradChunkPos, wgrad_arith_dispatch, ...).
 #pragma once
@@ -45,8 +46,15 @@ void tu_conv3x3s2(const ConvFwdParams& p, hipStream_t s);
 void tu_conv_t2(const ConvFwdParams& p, hipStream_t s);
 
 // conv_tu_fwd_fewch.hip: pointwise convolutions with <= 16 channels on one side (kind 1: few input channels, 2: few output channels)
-struct FewChParams;
 void tu_conv1x1_fewch(int kind, const FewChParams& p, hipStream_t s);
+
+// conv_tu_aux.hip: the small kernels around a launch
+void tu_splitk_reduce(const ConvFwdParams& p, hipStream_t s);     // y = epilogue(sum of the p.ksplit slices at p.partial), every operand from p
+void tu_amax_times(const float* parts_in, const float* v, int n, float* parts_out, hipStream_t s);      // parts_out[i] = parts_in[i] * max |v[0 .. n)|
+struct EdgeWeights { const float* w; const float* mod_s; const float* mod_d; float wscale; int flip; };
+void tu_conv_t2_edge(const ConvFwdParams& q, const EdgeWeights& ew, hipStream_t s);      // the remainder classes of the pair launch (q.cls), raw weights
+void tu_packed_koff(unsigned* koff, int K, int kh, int kw, int flip, int HWp, int Wp, hipStream_t s);  // the packed-K mode's offset table
+void tu_pad_planes(const float* x, float* xp, int64_t planes, int H, int W, int ph, int pw, hipStream_t s);      // ... and its zero-padded input copy
 
 // conv_tu_wgrad_f32.hip: fp32-MFMA weight gradients, few-channel kernels, slab reductions
 int  tu_wgrad_f32(int TR, int TS, int WA, int pipe, int kp, const WgradParams& p, int64_t blocks, size_t lds_bytes, hipStream_t s);
@@ -55,7 +63,6 @@ void tu_wgrad_reduce(const float* slab, float* dw, int ksplit, int G, int Ag, in
 void tu_wgrad_reduce_modulated(bool mod_a, dim3 grid, const float* slab, const float* sty, const float* w, float* dw, float* dsp, int ksplit, int N,
                                int Ag, int Bg, int Ap, int Bp, int kh, int kw, int flip, float wscale, int wg_rows, hipStream_t s);
 void tu_sum_blocks(const float* blocks, float* out, int nblocks, int n, hipStream_t s);
-struct WgradSmallParams;
 void tu_wgrad_smallcin(const WgradSmallParams& q, int blocks, size_t lds_bytes, hipStream_t s);
 void tu_wgrad_smallcin_reduce(const float* slab, float* dw, int ksplit, int Ag, int bprime, int a_pad, int bpad, float wscale, hipStream_t s);
 void tu_wgrad1x1_fewcin(int CI, int io, dim3 grid, const void* dy, const void* x, float* slab, int N, int Co, int HW, int64_t quads_per_slice, int a_pad,

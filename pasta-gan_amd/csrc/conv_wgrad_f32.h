@@ -245,8 +245,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 // sum_hw dx x (two reads) exist.  Workgroup = (64 b, 16 or 4 a, one tap); wave = four rows a or one, lanes along b (the slab's contiguous index).
 // MOD_A: the modulated (input) channel is the a index (conv_transpose2d: weight [I, O, kh, kw]).  Partial ds per workgroup row:
 // dsp[(a block * KK + t)][n][b] (MOD_A: dsp[(b tile * KK + t)][n][a]), summed in a fixed order by sum_blocks_kernel.  N <= 32.
-// rows a per workgroup: 16, or 4 where 16 would leave the grid below 512 workgroups (the 64- and 128-channel layers: 75 MB of slabs each)
-static int wgrad_mod_rows(int Ap, int Bp, int KK) { return (int64_t)(Bp / 64) * (Ap / 16) * KK >= 512 ? 16 : 4; }
+// rows a per workgroup (wg_rows): 16 or 4, wgrad_mod_rows of conv_plan.h
 template <bool MOD_A>
 __global__ __launch_bounds__(256) void wgrad_reduce_modulated_kernel(const float* __restrict__ slab, const float* __restrict__ sty, const float* __restrict__ w,
                                                                      float* __restrict__ dw, float* __restrict__ dsp, int ksplit, int N,
@@ -346,15 +345,6 @@ __global__ __launch_bounds__(256) void sum_blocks_kernel(const float* __restrict
 // the (channel, tap) pairs become the GEMM's column index b' = (i*kh + r)*kw + s, so a 7x7x3 kernel fills
 // 147 of 160 MFMA columns instead of 3 of 64.  conv2d, stride 1, groups 1 only.
 //   dW[o][b'] = sum_{n,p,q} dy[n,o,p,q] * x[n, i, p + r - pad_h, q + s - pad_w]
-
-struct WgradSmallParams {
-    const float* S; const float* L; float* slab;
-    int N, Ag, P, Q;        // S = dy: [N, Ag, P, Q]
-    int Bg, LH, LW;         // L = x : [N, Bg, LH, LW]
-    int kh, kw, pad_h, pad_w;
-    int bprime, nb;         // Bg*kh*kw and its number of 32-column tiles (<= 5)
-    int cw_log2, rows_total, qblocks, chunks_total, ksplit, a_tiles;
-};
 
 #ifdef PASTA_TU_WGRAD_F32  // defined by conv_tu_wgrad_f32.hip only (conv_launch.h)
 __global__ __launch_bounds__(256) void conv_wgrad_smallcin_kernel(WgradSmallParams p) {
@@ -500,28 +490,7 @@ __global__ __launch_bounds__(256) void wgrad_smallcin_reduce_kernel(const float*
 }
 #endif  // PASTA_TU_WGRAD_F32
 
-struct WgradSmallPlan { bool use; int nb, bprime, cw_log2, qblocks, chunks_total, ksplit, a_tiles, rows_total; int64_t slab_floats; size_t lds_bytes; };
-
-static WgradSmallPlan plan_wgrad_small(const pasta_conv_desc* d) {
-    WgradSmallPlan w; w.use = false;
-    const int Ig = d->C_in / d->groups;
-    if (d->transposed || d->groups != 1 || d->stride != 1 || d->flip || Ig > 8 || Ig * d->kh * d->kw > 160) return w;
-    w.use = true;
-    w.bprime = Ig * d->kh * d->kw; w.nb = (w.bprime + 31) / 32;
-    w.rows_total = d->N * d->OH;
-    const WgradChunks c = wgrad_chunks(32, w.rows_total, d->OW);
-    w.cw_log2 = c.cw_log2; w.qblocks = c.qblocks; w.chunks_total = c.chunks_total;
-    const int cw = 1 << c.cw_log2, chh = 32 >> c.cw_log2;
-    w.a_tiles = (d->C_out + 63) / 64;
-    int64_t ks = (1024 + w.a_tiles - 1) / w.a_tiles;        // four workgroups per CU: one chunk in flight each
-    if (ks > w.chunks_total / 8) ks = w.chunks_total / 8;
-    if (ks < 1) ks = 1;
-    w.ksplit = (int)ks;
-    w.slab_floats = (int64_t)w.ksplit * w.a_tiles * 64 * w.nb * 32;
-    w.lds_bytes = (size_t)(64 * 33 + Ig * chh * d->kh * (cw + d->kw - 1) + 4) * sizeof(float);
-    if (Ig * chh * d->kh * (cw + d->kw - 1) > 1024) w.use = false;      // four halo slots per thread in the kernel
-    return w;
-}
+// (The plan of this kernel: plan_wgrad_small, conv_plan.h.)
 
 //------------------------------------------------------------------------------------
 // Pointwise weight gradient with very few input channels (round 4: the discriminator's fromrgb, 3 -> 64 over 48 stacked images, the pose /
@@ -586,14 +555,6 @@ __global__ __launch_bounds__(256) void wgrad1x1_fewcin_kernel(const void* __rest
     }
 }
 
-// Does the few-channel pointwise kernel take this weight gradient, and with how many K slices (<= the slab the small-cin plan reserved)?
-static int plan_wgrad1x1_fewcin(const pasta_conv_desc* d, const WgradSmallPlan& ws) {
-    if (!ws.use || d->kh != 1 || d->kw != 1 || d->pad_h || d->pad_w || d->C_in > 8) return 0;      // (any storage type: round 5)
-    const int64_t hw = (int64_t)d->H * d->W;
-    if (hw % 4 || d->OH != d->H || d->OW != d->W) return 0;
-    int64_t ks = (int64_t)d->N * (hw / 4) / (256 * 8);          // at least eight trips per thread
-    ks = ks < 1 ? 1 : ks > 256 ? 256 : ks;
-    return (int)(ks < ws.ksplit ? ks : ws.ksplit);
-}
+// (Whether this kernel takes a weight gradient, and with how many K slices: plan_wgrad1x1_fewcin, conv_plan.h.)
 
 }  // namespace pasta

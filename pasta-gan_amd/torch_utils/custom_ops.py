@@ -33,6 +33,11 @@ LIB_NAME = 'libpasta_hip.so'
 EXPECTED_ABI = 21                   # PASTA_ABI_VERSION of include/pasta_hip.h = pasta_abi_version() of csrc/common.hip
 ARCH = 'gfx950'
 
+# The kernels as the planners name them: PASTA_FWD_* (pasta_conv2d_plan) and PASTA_WGRAD_* (pasta_conv2d_wgrad_plan) of include/pasta_hip.h
+(FWD_F32, FWD_BASE, FWD_ROWS, FWD_PAIR, FWD_ROWS2D_R4, FWD_ROWS2D_R2, FWD_ROWS2D_R8, FWD_ROWS2D_WIDE, FWD_PACKED_K, FWD_1X1, FWD_3X3S2,
+ FWD_FEWCIN, FWD_FEWCOUT, FWD_T2) = range(14)
+WGRAD_F32, WGRAD_SMALLCIN, WGRAD_3X3, WGRAD_3X3S2, WGRAD_1X1, WGRAD_FEWCIN, WGRAD_3X3S2_PIECES = range(7)
+
 _lock = threading.Lock()
 _cached_plugins = dict()
 
@@ -95,7 +100,7 @@ def _unit_weight(src):
 
 def _compile_and_link(hipcc, sources, lib_path, stamp, digest, verbose, extra_flags):
     flags = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-contract=fast', '-I', _INCLUDE] + list(extra_flags)
-    # one hipcc per translation unit, at most one per core at a time, the large units first (the convolution family is eighteen
+    # one hipcc per translation unit, at most one per core at a time, the large units first (the convolution family is nineteen
     # units, csrc/conv_launch.h: a forced build takes about a minute on eight cores)
     objs = [os.path.join(_OBJDIR, os.path.basename(src)[:-4] + '.o') for src in sources]
     queue = sorted(zip(sources, objs), key=lambda so: -_unit_weight(so[0]))

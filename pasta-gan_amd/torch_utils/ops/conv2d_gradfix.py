@@ -199,7 +199,7 @@ def _runs_f16x3(kind, desc, flags=0):
     if desc.math not in (0, MATH_CODES['f16x3']) or desc.io_dtype != 0:
         return False
     p = _plan(kind, desc, flags)
-    return p.math == MATH_CODES['f16x3'] if kind == 'conv' else p.kernel in (2, 3, 4)
+    return p.math == MATH_CODES['f16x3'] if kind == 'conv' else p.kernel in (custom_ops.WGRAD_3X3, custom_ops.WGRAD_3X3S2, custom_ops.WGRAD_1X1)
 
 # Optional measurement hook (bench.py): when set, called as hook(kind, desc, launch, flags) around every native
 # convolution launch; ``launch()`` performs it. None = no overhead.
@@ -377,7 +377,7 @@ def pieces_available(x, f, weight, pad4, groups=1):
     oh, ow = _out_hw(cfg, bh, bw, 3, 3)
     desc = _desc(cfg, (n, c, bh, bw), int(weight.shape[0]), oh, ow, 3, 3)
     desc.x_layout = 1
-    return _plan('conv', desc, PLAN_EPILOGUE).kernel == 10 and _plan('wgrad', desc).kernel == 6
+    return _plan('conv', desc, PLAN_EPILOGUE).kernel == custom_ops.FWD_3X3S2 and _plan('wgrad', desc).kernel == custom_ops.WGRAD_3X3S2_PIECES
 
 def blur_pieces(x, f, pad4, flip_filter=False, gain=1.0, x_amax=None):
     """``upfirdn2d(x, f, padding=pad4, flip_filter, gain)`` for a 4 x 4 filter, written as PASTA_LAYOUT_PIECES16.  Returns (pieces -- a uint8
@@ -438,7 +438,7 @@ def _shared_pieces_ok(x, weight, cfg, has_epilogue):
     oh, ow = _out_hw(cfg, h, wd, 3, 3)
     desc = _desc(cfg, (n, c, h, wd), int(weight.shape[0]), oh, ow, 3, 3)
     desc.x_layout = 1
-    return _plan('conv', desc, PLAN_EPILOGUE if has_epilogue else 0).kernel == 7
+    return _plan('conv', desc, PLAN_EPILOGUE if has_epilogue else 0).kernel == custom_ops.FWD_ROWS2D_WIDE
 
 def share_pieces(x):
     """Pack ``x`` for the stride-1 3x3 layers that will read it (a no-op where none of them could use the pieces); returns ``x``."""
@@ -741,7 +741,7 @@ def cat1x1_available(x, x2, weight):
         return False
     n, h, w_ = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
     desc = _desc(_Cfg((False, 1, 0, 0, 0, 0, 1, 1.0)), (n, int(x.shape[1]) + int(x2.shape[1]), h, w_), int(weight.shape[0]), h, w_, 1, 1)
-    return _plan('conv', desc, PLAN_EPILOGUE).kernel == 9
+    return _plan('conv', desc, PLAN_EPILOGUE).kernel == custom_ops.FWD_1X1
 
 class _CatConv1x1BiasActHip(torch.autograd.Function):
     """``bias_act(conv2d(cat([x, x2], 1), w), b)`` for a 1x1 weight in one launch over the two tensors; the backward is assembled from the
