@@ -649,6 +649,27 @@ int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image
                                 const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw,
                                 void* stream);
 
+/* An OUTFIT at 512 x 320 (this project's own; training/tryon_regions.py, TryOnOutfitBatchBuilder): the person wears the upper
+ * garment of one donor and the lower garment of another, either of whom may be the person.  pasta_tryon_region_masks_u8's
+ * rules with a source per garment: retain_img = the person's padded image * (shoes(18, 19) + palm + head(1, 2, 4, 13)), always
+ * the person's; upper_img / upper_mask = labels 5, 6, 7 (image, 255) of (upper_image, upper_parsing); lower_img / lower_mask =
+ * labels 9, 12 of (lower_image, lower_parsing).  Sources [N, H, W, 3] and [N, H, W] like the person's, and they may be the
+ * person's own pointers; outputs [N, H, H, 3], padding 255 in the images before the masks are applied, 0 in the labels.  With
+ * both sources the donor's it is region 0 of pasta_tryon_region_masks_u8 bit for bit, with (donor, person) region 1, with
+ * (person, donor) region 2. */
+int pasta_tryon_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
+                                const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
+                                uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img, uint8_t* lower_mask,
+                                int N, int H, int W, void* stream);
+
+/* pasta_tryon_region_assemble for an outfit: ten fp32 NCHW tensors through outputs (a HOST array of 10 device pointers), the
+ * nine of pasta_tryon_region_assemble in its order with clothes = the padded upper_donor_image, then clothes_lower [N,3,H,H] =
+ * the padded lower_donor_image (padding 255, x / 127.5 - 1).  Inputs as there; lower_donor_image [N,H,W,3]. */
+int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor_image, const uint8_t* lower_donor_image,
+                                const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* patches_lower,
+                                const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W,
+                                int P, int P_lower, int ph, int pw, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the 512 x 320 try-on TRAINING samples (training/tryon_regions.py, FullBodyRegionBatchBuilder).
  * The reference ships no 512 training set: the rules are this project's own, and one rule governs them -- the generator is

@@ -139,8 +139,8 @@ __device__ __forceinline__ SquarePixel square_pixel(int n, int pix, int H, int W
 
 // Every fp32 tensor an assemble entry may write; an entry sets those of its KEYS and leaves the others null.
 struct TryonOut {
-    float *image, *clothes, *gt_parsing, *style_input, *retain, *pose, *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask,
-          *denorm_lower_mask;
+    float *image, *clothes, *clothes_lower, *gt_parsing, *style_input, *retain, *pose, *denorm_upper_input, *denorm_lower_input,
+          *denorm_upper_mask, *denorm_lower_mask;
 };
 
 // outputs[i] -> *fields[i] for the `count` tensors of an entry; the index of the first null output, -1 when there is none.

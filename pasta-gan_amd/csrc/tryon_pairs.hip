@@ -13,15 +13,19 @@
 //   pasta_tryon_region_masks_u8      retain image and the upper and lower garment, each taken from the donor or the person as
 //                                    the region says (:1631-1690);
 //   pasta_tryon_region_assemble      __getitem__ (:2196-2214) and test_512.py's conversions (:115-131) into the nine fp32 tensors.
+// The 512 x 320 OUTFITS (this project's own: a person, an upper garment and a lower garment from up to three people; a pair
+// with a region is the outfit whose two sources are the donor or the person):
+//   pasta_tryon_outfit_masks_u8      the region entry's rules with a source of its own for each garment;
+//   pasta_tryon_outfit_assemble      the nine tensors and clothes_lower, the lower garment's donor.
 // The 512 x 320 TRAINING samples (this project's own: the reference ships no 512 training set) are that set's full-body
 // preparation of the pair (person, person) with the 256 training set's photograph, gt_parsing and erase mask on top:
 //   pasta_tryon_train_region_masks_u8  retain mask, gt_parsing and both garments of the person, in the stacked [2N] layout
 //                                      normalize_region_batch takes (csrc/tryon_inputs.hip's label-masks launch: the two
 //                                      training sets name the same labels);
 //   pasta_tryon_train_region_assemble  the erase mask from two eroded arm-part masks and the nine fp32 tensors of the loop.
-// Both masks entries launch tryon_pair_masks_kernel and both assemble entries tryon_pair_assemble_kernel: the 256 pairs are
+// Every masks entry launches tryon_pair_masks_kernel and every assemble entry tryon_pair_assemble_kernel: the 256 pairs are
 // the 512 rules with "upper from the donor, lower from the person" fixed, label 6 added to the lower garment, stick patches as
-// the second patch list and no image / clothes tensors.  The flags are kernel arguments, uniform per launch.
+// the second patch list and no image / clothes tensors.  Sources and the label-6 flag are kernel arguments, uniform per launch.
 // The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures tryon_inputs.hip's stick-figure
 // entries (thickness 2, radius 2 at 256; 5 and 5 at 512, whose palm boxes are 35 and 20 and whose composites are both eroded).
 // Where the 256 test set differs from the training preparation (the six rules of include/pasta_hip.h): two people (the
@@ -48,29 +52,31 @@ __global__ __launch_bounds__(PALM_S_MAX) void palm_mask_box_kernel(const uint8_t
 
 // ---- label masks of a pair ----
 
-// The upper and the lower garment each come from the donor or from the person; label 6 belongs to the lower garment at 256 x 192 only.
+// The upper and the lower garment each have a source of their own, (u_image, u_parsing) and (l_image, l_parsing): the person's
+// pointers again, a donor's, or two different donors'; label 6 belongs to the lower garment at 256 x 192 only.
 __global__ __launch_bounds__(256) void tryon_pair_masks_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ parsing,
-                                                               const uint8_t* __restrict__ palm, const uint8_t* __restrict__ d_image,
-                                                               const uint8_t* __restrict__ d_parsing, uint8_t* __restrict__ retain_img,
+                                                               const uint8_t* __restrict__ palm, const uint8_t* __restrict__ u_image,
+                                                               const uint8_t* __restrict__ u_parsing, const uint8_t* __restrict__ l_image,
+                                                               const uint8_t* __restrict__ l_parsing, uint8_t* __restrict__ retain_img,
                                                                uint8_t* __restrict__ upper_img, uint8_t* __restrict__ upper_mask,
                                                                uint8_t* __restrict__ lower_img, uint8_t* __restrict__ lower_mask, int H, int W,
-                                                               int lp, int upper_from_donor, int lower_from_donor, int six_is_lower) {
+                                                               int lp, int six_is_lower) {
     const int n = blockIdx.y;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= H * H) return;
     const SquarePixel s = square_pixel(n, pix, H, W, lp);
-    const int L = s.inside ? parsing[s.src] : 0, D = s.inside ? d_parsing[s.src] : 0;
+    const int L = s.inside ? parsing[s.src] : 0, U = s.inside ? u_parsing[s.src] : 0, Lo = s.inside ? l_parsing[s.src] : 0;
     const int64_t o = (int64_t)n * H * H + pix;
     const int keep = (L == 18 || L == 19) + palm[o] + (L == 1 || L == 2 || L == 4 || L == 13);      // shoes + palm + head, the person's
-    const int U = upper_from_donor ? D : L, Lo = lower_from_donor ? D : L;
     const int up = U == 5 || U == 6 || U == 7;
     const int low = Lo == 9 || Lo == 12 || (six_is_lower && Lo == 6);
     for (int ch = 0; ch < 3; ch++) {
-        const int v = s.inside ? image[s.src * 3 + ch] : 255, dv = s.inside ? d_image[s.src * 3 + ch] : 255;
+        const int v = s.inside ? image[s.src * 3 + ch] : 255;
+        const int uv = s.inside ? u_image[s.src * 3 + ch] : 255, lv = s.inside ? l_image[s.src * 3 + ch] : 255;
         retain_img[o * 3 + ch] = (uint8_t)(keep * v);
-        upper_img[o * 3 + ch] = (uint8_t)(up * (upper_from_donor ? dv : v));
+        upper_img[o * 3 + ch] = (uint8_t)(up * uv);
         upper_mask[o * 3 + ch] = (uint8_t)(up * 255);
-        lower_img[o * 3 + ch] = (uint8_t)(low * (lower_from_donor ? dv : v));
+        lower_img[o * 3 + ch] = (uint8_t)(low * lv);
         lower_mask[o * 3 + ch] = (uint8_t)(low * 255);
     }
 }
@@ -96,11 +102,13 @@ __global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8
 // ---- the seven tensors G takes, or the nine of test_512.py ----
 
 // Two lists of patches, PA and PB parts, make style_input: (patches, stick patches) at 256 x 192, (patches, patches_lower) at
-// 512 x 320.  o.image and o.clothes are written from image and d_image (W wide, lp columns of padding) unless they are null.
+// 512 x 320.  o.image and o.clothes are written from image and d_image (W wide, lp columns of padding) unless they are null, and
+// o.clothes_lower from d_image_l, the lower garment's donor of an outfit, unless that is null.
 // retain: test_512.py forms image * mask - (1 - mask) from the 0 / 1 retain mask (shoes, palm and head are disjoint label groups,
 // the palm a subset of labels 14 / 15, so the mask never exceeds 1).  Where the mask is 1 that is to_unit(v) * 1 - 0 = to_unit(v);
 // where it is 0 it is (+-0) - 1 = -1 = to_unit(0).  Both are to_unit(mask * v) = to_unit(retain_img) bit for bit, test.py's form.
 __global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ d_image,
+                                                                  const uint8_t* __restrict__ d_image_l,
                                                                   const uint8_t* __restrict__ retain_img, const uint8_t* __restrict__ stick,
                                                                   const uint8_t* __restrict__ patches_a, const uint8_t* __restrict__ patches_b,
                                                                   const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l,
@@ -120,13 +128,14 @@ __global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t*
         return;
     }
     const int64_t p = (int64_t)n * HH + pix;
-    float ret[3], person[3] = {}, donor[3] = {};
+    float ret[3], person[3] = {}, donor[3] = {}, donor_l[3] = {};
     for (int ch = 0; ch < 3; ch++) ret[ch] = to_unit(retain_img[p * 3 + ch]);
     if (o.image) {                  // read before anything is stored
         const SquarePixel s = square_pixel(n, pix, H, W, lp);
         for (int ch = 0; ch < 3; ch++) {
             person[ch] = to_unit(s.inside ? image[s.src * 3 + ch] : 255);
             donor[ch] = to_unit(s.inside ? d_image[s.src * 3 + ch] : 255);
+            if (o.clothes_lower) donor_l[ch] = to_unit(s.inside ? d_image_l[s.src * 3 + ch] : 255);
         }
     }
     tryon_pixel(o, n, pix, HH, ret, stick + p * 3, den_u + p * 3, den_l + p * 3, 1);
@@ -134,6 +143,7 @@ __global__ __launch_bounds__(256) void tryon_pair_assemble_kernel(const uint8_t*
         for (int ch = 0; ch < 3; ch++) {
             o.image[((int64_t)n * 3 + ch) * HH + pix] = person[ch];
             o.clothes[((int64_t)n * 3 + ch) * HH + pix] = donor[ch];
+            if (o.clothes_lower) o.clothes_lower[((int64_t)n * 3 + ch) * HH + pix] = donor_l[ch];
         }
 }
 
@@ -204,35 +214,64 @@ extern "C" int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quad
     return pasta_palm_mask_square_u8(parsing, quads, present, out, N, H, W, k_upper, k_lower, stream);
 }
 
-// Both label-masks entries, `what` naming the caller in the error texts: the 512 x 320 entry passes its region and no label 6, the
-// 256 x 192 one the constant region 1 (upper garment from the donor, lower from the person) with label 6 in the lower garment.
-static int launch_pair_masks(const char* what, const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
-                             const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                             uint8_t* lower_mask, int N, int H, int W, int region, int six_is_lower, void* stream) {
-    using namespace pasta;
-    PASTA_CHECK(image && parsing && palm && donor_image && donor_parsing && retain_img && upper_img && upper_mask && lower_img && lower_mask,
-                "%s: null pointer", what);
+// The label-masks entries, `what` naming the caller in the error texts.  pair_masks_args: the checks all three share.
+static int pair_masks_args(const char* what, bool pointers, int N, int H, int W) {
+    PASTA_CHECK(pointers, "%s: null pointer", what);
     PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "%s: bad shape", what);
-    PASTA_CHECK(region >= 0 && region <= 2, "%s: region %d (0 full body, 1 upper body, 2 lower body)", what, region);
+    return 0;
+}
+
+static int launch_pair_masks(const char* what, const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
+                             const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing, uint8_t* retain_img,
+                             uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W,
+                             int six_is_lower, void* stream) {
+    using namespace pasta;
     dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, donor_image, donor_parsing,
-                       retain_img, upper_img, upper_mask, lower_img, lower_mask, H, W, (H - W) / 2, region != 2, region != 1,
-                       six_is_lower);
+    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, upper_image, upper_parsing,
+                       lower_image, lower_parsing, retain_img, upper_img, upper_mask, lower_img, lower_mask, H, W, (H - W) / 2, six_is_lower);
     return launch_status(what);
+}
+
+// One donor and a region: the 512 x 320 entry passes its region and no label 6, the 256 x 192 one the constant region 1 (upper
+// garment from the donor, lower from the person) with label 6 in the lower garment.  Each garment's source is the donor's
+// pointers or the person's.
+static int launch_region_masks(const char* what, const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
+                               const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                               uint8_t* lower_mask, int N, int H, int W, int region, int six_is_lower, void* stream) {
+    if (const int rc = pair_masks_args(what, image && parsing && palm && donor_image && donor_parsing && retain_img && upper_img && upper_mask &&
+                                                 lower_img && lower_mask, N, H, W))
+        return rc;
+    PASTA_CHECK(region >= 0 && region <= 2, "%s: region %d (0 full body, 1 upper body, 2 lower body)", what, region);
+    const bool upper_donor = region != 2, lower_donor = region != 1;
+    return launch_pair_masks(what, image, parsing, palm, upper_donor ? donor_image : image, upper_donor ? donor_parsing : parsing,
+                             lower_donor ? donor_image : image, lower_donor ? donor_parsing : parsing, retain_img, upper_img, upper_mask,
+                             lower_img, lower_mask, N, H, W, six_is_lower, stream);
 }
 
 extern "C" int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
                                          const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* lower_img, uint8_t* lower_mask,
                                          uint8_t* upper_img, uint8_t* upper_mask, int N, int H, int W, void* stream) {
-    return launch_pair_masks("tryon_pair_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
-                             lower_img, lower_mask, N, H, W, 1, 1, stream);
+    return launch_region_masks("tryon_pair_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
+                               lower_img, lower_mask, N, H, W, 1, 1, stream);
 }
 
 extern "C" int pasta_tryon_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
                                            const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask,
                                            uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W, int region, void* stream) {
-    return launch_pair_masks("tryon_region_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
-                             lower_img, lower_mask, N, H, W, region, 0, stream);
+    return launch_region_masks("tryon_region_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
+                               lower_img, lower_mask, N, H, W, region, 0, stream);
+}
+
+extern "C" int pasta_tryon_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
+                                           const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
+                                           uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                                           uint8_t* lower_mask, int N, int H, int W, void* stream) {
+    if (const int rc = pair_masks_args("tryon_outfit_masks_u8", image && parsing && palm && upper_image && upper_parsing && lower_image &&
+                                                                    lower_parsing && retain_img && upper_img && upper_mask && lower_img &&
+                                                                    lower_mask, N, H, W))
+        return rc;
+    return launch_pair_masks("tryon_outfit_masks_u8", image, parsing, palm, upper_image, upper_parsing, lower_image, lower_parsing, retain_img,
+                             upper_img, upper_mask, lower_img, lower_mask, N, H, W, 0, stream);
 }
 
 extern "C" int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
@@ -263,28 +302,46 @@ extern "C" int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_
     PASTA_CHECK(missing < 0, "tryon_pair_assemble: output %d is null", missing);
     dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
     hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr, (const uint8_t*)nullptr,
-                       retain_img, stick, patches, stick_patches, denorm_upper, denorm_lower, o, H, H, 0, P, P, ph, pw);
+                       (const uint8_t*)nullptr, retain_img, stick, patches, stick_patches, denorm_upper, denorm_lower, o, H, H, 0, P, P, ph, pw);
     return launch_status("tryon_pair_assemble");
+}
+
+// Both 512 x 320 assemble entries: `count` outputs, nine for a pair (lower_donor_image null) and `clothes_lower` as the tenth
+// for an outfit.
+static int launch_region_assemble(const char* what, const uint8_t* image, const uint8_t* donor_image, const uint8_t* lower_donor_image,
+                                  const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* patches_lower,
+                                  const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int count, int N, int H,
+                                  int W, int P, int P_lower, int ph, int pw, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && donor_image && (count == 9 || lower_donor_image) && retain_img && stick && patches && patches_lower && denorm_upper &&
+                denorm_lower && outputs, "%s: null pointer", what);
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && P >= 1 && P <= 64 && P_lower >= 1 && P_lower <= 64 &&
+                ph >= 1 && pw >= 1 && ph * pw <= H * H, "%s: bad shape", what);
+    TryonOut o{};
+    float** f[10] = {&o.image, &o.clothes, &o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input,
+                     &o.denorm_upper_mask, &o.denorm_lower_mask, &o.clothes_lower};
+    const int missing = take_outputs(outputs, f, count);
+    PASTA_CHECK(missing < 0, "%s: output %d is null", what, missing);
+    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, donor_image, lower_donor_image, retain_img,
+                       stick, patches, patches_lower, denorm_upper, denorm_lower, o, H, W, (H - W) / 2, P, P_lower, ph, pw);
+    return launch_status(what);
 }
 
 extern "C" int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image, const uint8_t* retain_img, const uint8_t* stick,
                                            const uint8_t* patches, const uint8_t* patches_lower, const uint8_t* denorm_upper,
                                            const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph,
                                            int pw, void* stream) {
-    using namespace pasta;
-    PASTA_CHECK(image && donor_image && retain_img && stick && patches && patches_lower && denorm_upper && denorm_lower && outputs,
-                "tryon_region_assemble: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && P >= 1 && P <= 64 && P_lower >= 1 && P_lower <= 64 &&
-                ph >= 1 && pw >= 1 && ph * pw <= H * H, "tryon_region_assemble: bad shape");
-    TryonOut o{};
-    float** f[9] = {&o.image, &o.clothes, &o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input,
-                    &o.denorm_upper_mask, &o.denorm_lower_mask};
-    const int missing = take_outputs(outputs, f, 9);
-    PASTA_CHECK(missing < 0, "tryon_region_assemble: output %d is null", missing);
-    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, donor_image, retain_img, stick, patches,
-                       patches_lower, denorm_upper, denorm_lower, o, H, W, (H - W) / 2, P, P_lower, ph, pw);
-    return launch_status("tryon_region_assemble");
+    return launch_region_assemble("tryon_region_assemble", image, donor_image, nullptr, retain_img, stick, patches, patches_lower, denorm_upper,
+                                  denorm_lower, outputs, 9, N, H, W, P, P_lower, ph, pw, stream);
+}
+
+extern "C" int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor_image, const uint8_t* lower_donor_image,
+                                           const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches,
+                                           const uint8_t* patches_lower, const uint8_t* denorm_upper, const uint8_t* denorm_lower,
+                                           float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw, void* stream) {
+    return launch_region_assemble("tryon_outfit_assemble", image, upper_donor_image, lower_donor_image, retain_img, stick, patches,
+                                  patches_lower, denorm_upper, denorm_lower, outputs, 10, N, H, W, P, P_lower, ph, pw, stream);
 }
 
 extern "C" int pasta_tryon_train_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain_mask,

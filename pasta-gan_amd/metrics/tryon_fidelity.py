@@ -10,7 +10,8 @@ Three regions of every output have a known answer, so they need no detector netw
 
 Per region and pair, ``pasta_region_image_stats`` (csrc/recon_metrics.hip) gives sum |d|, sum d^2 and the bytes of the region's
 pixels, and the SSIM sum and count of the 11 x 11 windows lying wholly inside it.  These are this project's own figures, not
-the reference's (which scores try-on by FID and KID); they are an option of test.py and not a registered metric.
+the reference's (which scores try-on by FID and KID); they are an option of test.py and test_512.py (``finish`` with
+``pixels=512 * 320``) and not a registered metric.
 
 Partials are ``int64 [num_pairs, 3, 5]``: per region sum |d|, sum d^2, SSIM windows, bytes and the bits of the fp64 SSIM sum.
 Row i belongs to pair i of the pair lists and is written by whoever scores it (zeros elsewhere), the scheme of
@@ -84,8 +85,10 @@ def keep_mask(stages):
     return m.to(torch.uint8)
 
 def score_batch(images, batch, rows, partials):
-    """G's fine-tuned output fp32 [N, 3, H, H] (before images_to_u8; the kernel quantises as that does) of a ``TryOnPairBatch`` built
-    with ``keep_stages=True``, scored into rows ``rows`` of ``partials``."""
+    """G's fine-tuned output fp32 [N, 3, H, H] (before images_to_u8; the kernel quantises as that does) of a ``TryOnPairBatch``, or
+    of a 512 x 320 ``TryOnRegionBatch`` or ``TryOnOutfitBatch``, built with ``keep_stages=True``, scored into rows ``rows`` of
+    ``partials``.  It reads the stages every one of them keeps: the person's unpadded ``image`` and ``parsing``, ``palm``,
+    ``denorm_upper`` and ``denorm_lower``; the retain rule (``keep_mask``) is the same at both sizes."""
     from metrics import metric_utils
     st, t = batch.stages, batch.tensors
     assert st is not None, 'tryon_fidelity.score_batch: build the batch with keep_stages=True'

@@ -21,7 +21,6 @@ Differences from the reference, on purpose:
   this project's own figures; the reference has none for test.py.
 """
 
-import json
 import os
 from typing import List, Optional
 
@@ -33,9 +32,7 @@ import tryon_cli
 @click.command()
 @tryon_cli.shared_options('Root of the test data set', 16)
 @tryon_cli.workers_option
-@click.option('--scores', 'scores_file', help='Score the written images by region (kept body parts, upper and lower garment patches: L1, PSNR, '
-              'SSIM) and write the results to FILE as JSON. With this option z of pair i is np.random.RandomState(i).randn(z_dim), so that '
-              'the figures describe the images whatever the batch size [default: no scores]', type=str, metavar='FILE')
+@tryon_cli.scores_option
 def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi: float, class_idx: Optional[int], noise_mode: str,
                     projected_w: Optional[str], outdir: str, dataroot: str, batchsize: int, workers: int, scores_file: Optional[str],
                     storage: Optional[str] = None):
@@ -86,15 +83,7 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
             written += 1
     print('finish: %d images under %s' % (written, outdir))
     if scores_file is not None:
-        results = tryon_fidelity.finish(partials, 'tryon', pixels=pixels)
-        report = dict(results=results, pairs=written, network=network_pkl, dataroot=dataroot, noise_mode=noise_mode)
-        if storage is not None:
-            report['storage'] = storage
-        line = json.dumps(report)
-        print(line)
-        os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
-        with open(scores_file, 'w') as f:
-            f.write(line + '\n')
+        tryon_cli.write_scores(scores_file, partials, pixels, written, network_pkl, dataroot, noise_mode, storage)
 
 
 if __name__ == '__main__':

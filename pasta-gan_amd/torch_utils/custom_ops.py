@@ -234,6 +234,8 @@ ABI = {
     'pasta_palm_mask_square_u8': (ctypes.c_int, [_c_ptr] * 4 + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_tryon_region_masks_u8': (ctypes.c_int, [_c_ptr] * 10 + [ctypes.c_int] * 4 + [_c_ptr]),
     'pasta_tryon_region_assemble': (ctypes.c_int, [_c_ptr] * 8 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 7 + [_c_ptr]),
+    'pasta_tryon_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 3 + [_c_ptr]),
+    'pasta_tryon_outfit_assemble': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 7 + [_c_ptr]),
     'pasta_tryon_train_region_masks_u8': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 3 + [_c_ptr]),
     'pasta_tryon_train_region_assemble': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 2 + [_c_ptr] * 2 + [ctypes.POINTER(_c_ptr)] +
                                                         [ctypes.c_int] * 9 + [_c_ptr]),
@@ -257,7 +259,8 @@ LATE_ENTRIES = frozenset(['pasta_grid_sample', 'pasta_grid_sample_backward_works
                           'pasta_tryon_train_region_masks_u8', 'pasta_tryon_train_region_assemble',
                           'pasta_grid_composite_eroded_u8', 'pasta_grid_assemble', 'pasta_image_grid_tile_u8',
                           'pasta_recon_image_stats_workspace', 'pasta_recon_image_stats', 'pasta_parsing_confusion',
-                          'pasta_region_image_stats_workspace', 'pasta_region_image_stats'])
+                          'pasta_region_image_stats_workspace', 'pasta_region_image_stats', 'pasta_tryon_outfit_masks_u8',
+                          'pasta_tryon_outfit_assemble'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

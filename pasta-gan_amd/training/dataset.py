@@ -8,6 +8,8 @@ a list of raw samples into the batch the builder takes.  Only directory data set
 The test pairs (``UvitonDatasetV19_test``, dataset.py:997-1525) follow the same design: raw pairs out, ``collate_pairs``, and
 ``training.tryon_pairs.TryOnPairBatchBuilder`` on the GPU; so do the 512 x 320 pairs with a change region
 (``UvitonDatasetFull_512_test``, dataset.py:1528-2214) with ``training.tryon_regions.TryOnRegionBatchBuilder``.
+``UvitonOutfits_512_test`` is this project's own: outfits (person, upper garment's donor, lower garment's donor) from a list
+file, ``collate_outfits`` and ``training.tryon_regions.TryOnOutfitBatchBuilder``.
 ``UvitonDatasetFull_512`` is this project's own: the training layout at 512 x 320, which the reference does not ship, prepared
 by ``training.tryon_regions.FullBodyRegionBatchBuilder``."""
 
@@ -225,11 +227,26 @@ class UvitonDatasetV19_test(Dataset):
     def _label_name(dataset, name):
         return name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')     # :1030-1033
 
-    def __init__(self, path, resolution=None, **super_kwargs):
+    def _open_tree(self, path):
         self._path = path
         if not os.path.isdir(self._path):
             raise IOError('Path must point to a directory')
         self._type = 'dir'
+
+    def _init_items(self, first_person, count, resolution, super_kwargs, nothing='No image files found in the specified path'):
+        """The end of every test set's __init__: ``count`` items, sized by the files ``first_person`` (image, parsing, key points)."""
+        self._vis_index = list(range(64))
+        PIL.Image.init()
+        if count == 0:
+            raise IOError(nothing)
+        h, w, c = self._load_person(*first_person)[0].shape
+        raw_shape = [count, c, h, h]                           # the padded square, as the reference's image_shape
+        if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
+            raise IOError('Image files do not match the specified resolution')
+        Dataset.__init__(self, name=os.path.splitext(os.path.basename(self._path))[0], raw_shape=raw_shape, **super_kwargs)
+
+    def __init__(self, path, resolution=None, **super_kwargs):
+        self._open_tree(path)
         self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
         self._clothes_image_fnames, self._clothes_kpt_fnames, self._clothes_parsing_fnames = [], [], []
         for dataset in self._sub_datasets:
@@ -243,16 +260,8 @@ class UvitonDatasetV19_test(Dataset):
                         images.append(os.path.join(dataset, 'image', name))
                         kpts.append(os.path.join(dataset, 'keypoints', name.replace('.jpg', '_keypoints.json')))
                         labels.append(os.path.join(dataset, 'parsing', self._label_name(dataset, name)))
-        self._vis_index = list(range(64))
-
-        PIL.Image.init()
-        if len(self._image_fnames) == 0:
-            raise IOError('No image files found in the specified path')
-        h, w, c = self._load_person(self._image_fnames[0], self._parsing_fnames[0], self._kpt_fnames[0])[0].shape
-        raw_shape = [len(self._image_fnames), c, h, h]         # the padded square, as the reference's image_shape
-        if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
-            raise IOError('Image files do not match the specified resolution')
-        super().__init__(name=os.path.splitext(os.path.basename(self._path))[0], raw_shape=raw_shape, **super_kwargs)
+        first = [names[0] for names in (self._image_fnames, self._parsing_fnames, self._kpt_fnames) if names]
+        self._init_items(first, len(self._image_fnames), resolution, super_kwargs)
 
     def _load_person(self, image_fname, parsing_fname, kpt_fname):
         image = np.array(PIL.Image.open(os.path.join(self._path, image_fname)))
@@ -315,6 +324,92 @@ def collate_pairs(samples):
     out = {k: stack(k) for k in ('image', 'parsing', 'keypoints', 'clothes_image', 'clothes_parsing', 'clothes_keypoints')}
     out.update(person_name=[s['person_name'] for s in samples], clothes_name=[s['clothes_name'] for s in samples],
                raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
+    return out
+
+
+class UvitonOutfits_512_test(UvitonDatasetV19_test):
+    """This project's own: outfits at 512 x 320, a person with the upper garment of one donor and the lower garment of another.
+    ``outfits_file`` is a text file of lines ``person upper lower`` (blank lines skipped), each name ``<sub-dataset>/<file>.jpg``
+    with the sub-dataset one of ``SUB_DATASETS_512``, resolved as ``UvitonDatasetFull_512_test`` resolves a pair-list name
+    (``<sub>/image/<file>``, ``<sub>/keypoints/<stem>_keypoints.json``, ``<sub>/parsing/<stem>_label.png``); the three may come
+    from different sub-datasets.  ``upper`` or ``lower`` may be ``-``: the person keeps that garment of their own (``- -`` is the
+    self-pair the 512 model is trained on).  The pair lists are not read.  A line without exactly three fields, an unknown
+    sub-dataset or ``-`` as the person raises ValueError with the file and the 1-based line number; a missing file raises IOError
+    at load.  The change regions are three of its cases: full body (P, D, D), upper body (P, D, -), lower body (P, -, D).
+
+    ``__getitem__`` returns the raw outfit: the person's ``image`` / ``parsing`` / ``keypoints`` (as the pairs' data set),
+    the same three as ``upper_*`` and ``lower_*``, ``person_name`` / ``upper_name`` / ``lower_name`` (``<sub>/image/<file>``)
+    and ``raw_idx``, the line's position among the outfits.  For ``-`` the names and arrays are the person's own; a file named
+    twice on a line is decoded once.  ``collate_outfits`` makes the batch ``training.tryon_regions.TryOnOutfitBatchBuilder``
+    takes."""
+
+    _sub_datasets = SUB_DATASETS_512
+    _label_name = staticmethod(UvitonDatasetFull_512_test._label_name)
+
+    def __init__(self, path, outfits_file, resolution=None, **super_kwargs):
+        self._open_tree(path)
+        self._outfits = []              # per line: the (image, parsing, keypoints) file names of person, upper, lower
+        with open(outfits_file, 'r') as f:
+            for number, line in enumerate(f.readlines(), 1):
+                if not line.strip():
+                    continue
+                where = '%s, line %d' % (outfits_file, number)
+                fields = line.split()
+                if len(fields) != 3:
+                    raise ValueError('%s: expected "person upper lower", got %d fields' % (where, len(fields)))
+                if fields[0] == '-':
+                    raise ValueError('%s: the person cannot be "-"' % where)
+                people = []
+                for name in fields:
+                    if name == '-':
+                        people.append(people[0])
+                        continue
+                    dataset, _, fname = name.partition('/')
+                    if dataset not in self._sub_datasets or not fname:
+                        raise ValueError('%s: %r is not <sub-dataset>/<file>.jpg with the sub-dataset one of %s'
+                                         % (where, name, ', '.join(self._sub_datasets)))
+                    people.append((os.path.join(dataset, 'image', fname), os.path.join(dataset, 'parsing', self._label_name(dataset, fname)),
+                                   os.path.join(dataset, 'keypoints', fname.replace('.jpg', '_keypoints.json'))))
+                self._outfits.append(tuple(people))
+        self._init_items(self._outfits[0][0] if self._outfits else None, len(self._outfits), resolution, super_kwargs,
+                         'No outfits found in %s' % outfits_file)
+
+    def load_raw(self, raw_idx):
+        outfit = self._outfits[raw_idx]
+        decoded, out = {}, dict(raw_idx=int(raw_idx))
+        for role, prefix, files in zip(('person', 'upper', 'lower'), ('', 'upper_', 'lower_'), outfit):
+            if files not in decoded:
+                decoded[files] = self._load_person(*files)
+            image, parsing, keypoints = decoded[files]
+            if image.shape != decoded[outfit[0]][0].shape:
+                raise IOError('%s: the image %s does not match the person %s' % (files[0], image.shape, decoded[outfit[0]][0].shape))
+            out.update({prefix + 'image': image, prefix + 'parsing': parsing, prefix + 'keypoints': keypoints, role + '_name': files[0]})
+        return out
+
+
+def collate_outfits(samples):
+    """A list of raw outfits -> one batch in which every DISTINCT person (by name) is stacked once, in the order of first
+    appearance (samples in order; person, upper, lower within a sample): ``people_image`` uint8 [M, H, W, 3], ``people_parsing``
+    uint8 [M, H, W], ``people_keypoints`` float64 [M, 18, 3], ``people_name`` list of str; ``person_idx`` / ``upper_idx`` /
+    ``lower_idx`` int64 [N] into that stack; ``person_name`` / ``upper_name`` / ``lower_name`` lists of str, ``raw_idx`` int64
+    [N].  A person who keeps a garment, or a donor several outfits of the batch use, is uploaded and solved for once.  Use as the
+    DataLoader's ``collate_fn``."""
+    roles = (('person', ''), ('upper', 'upper_'), ('lower', 'lower_'))
+    slot, people = {}, []
+    index = {role: [] for role, _ in roles}
+    for s in samples:
+        for role, prefix in roles:
+            name = s[role + '_name']
+            if name not in slot:
+                slot[name] = len(people)
+                people.append((s[prefix + 'image'], s[prefix + 'parsing'], s[prefix + 'keypoints']))
+            index[role].append(slot[name])
+    out = {key: torch.from_numpy(np.stack([p[k] for p in people])) for k, key in enumerate(('people_image', 'people_parsing', 'people_keypoints'))}
+    out['people_name'] = list(slot)
+    for role, _ in roles:
+        out[role + '_idx'] = torch.as_tensor(index[role], dtype=torch.int64)
+        out[role + '_name'] = [s[role + '_name'] for s in samples]
+    out['raw_idx'] = torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64)
     return out
 
 #----------------------------------------------------------------------------

@@ -234,6 +234,35 @@ def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
 
 
+def _region_warps(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor, want_part_masks):
+    """The body of normalize_region_batch and normalize_outfit_batch: ONE part_matrices call over the M distinct people of
+    ``people_joints`` [M, 18, 3]; sample i wears the upper garment of people ``upper_idx[i]`` and the lower garment of
+    ``lower_idx[i]`` and is ``person_idx[i]`` itself.  Returns (the seven tensors both functions return first, valid [M, 10]
+    bool, part masks or None)."""
+    garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
+    n2, height, width, _ = garment_img.shape
+    n = n2 // 2
+    assert n2 == 2 * n and garment_mask.shape == garment_img.shape
+    person_idx, upper_idx, lower_idx = (np.asarray(ix, np.int64).reshape(n) for ix in (person_idx, upper_idx, lower_idx))
+    ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
+    fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0)
+    back, valid_p = back[person_idx], valid_all[person_idx]
+    low = list(LOWER_PARTS_512)
+    pu, pl = 10, len(low)
+    # items: (i, k) of the upper garments, then (i, k) of the lower garments, which read source N + i
+    mats = np.concatenate([fwd[upper_idx].reshape(-1, 3, 3), fwd[lower_idx][:, low].reshape(-1, 3, 3)])
+    valid = np.concatenate([valid_all[upper_idx].reshape(-1), valid_all[lower_idx][:, low].reshape(-1)])
+    src_index = np.concatenate([np.repeat(np.arange(n, dtype=np.int32), pu), np.repeat(np.arange(n, 2 * n, dtype=np.int32), pl)])
+    warp = lambda src: warp_perspective(src, mats, (ph, pw), 'replicate', src_index, valid)
+    split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
+    (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
+
+    den_u, part_masks = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS, want_part_masks)
+    den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
+    m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
+    return (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs), valid_all, part_masks
+
+
 def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joints, upper_from_donor, lower_from_donor, box_factor=2,
                            want_part_masks=False):
     """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch
@@ -246,29 +275,25 @@ def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joint
     the eroded composite, every part 5 x 5.  A part whose forward matrix is missing is zeros; a part whose M_inv is missing
     is skipped.  Returns (patches [N,10,h,w,3], patches_lower [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper,
     denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), donor_valid, person_valid [N,10] bool).
-    ``donor_joints is person_joints`` (the training samples: everyone wears their own garments) solves the matrices once.
-    ``want_part_masks``: a tenth value, the eroded 0 / 1 masks [N,10,H,W] of the upper composite's parts."""
-    garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
-    n2, height, width, _ = garment_img.shape
-    n = n2 // 2
-    assert n2 == 2 * n and garment_mask.shape == garment_img.shape
-    ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    fwd_p, back, valid_p = part_matrices(person_joints, width, height, box_factor, x_pad=0)
-    fwd_d, valid_d = (fwd_p, valid_p) if donor_joints is person_joints else part_matrices(donor_joints, width, height, box_factor, x_pad=0)[::2]
-    fwd_u, valid_u = (fwd_d, valid_d) if upper_from_donor else (fwd_p, valid_p)
-    fwd_l, valid_l = (fwd_d, valid_d) if lower_from_donor else (fwd_p, valid_p)
-    low = list(LOWER_PARTS_512)
-    pu, pl = 10, len(low)
-    # items: (i, k) of the upper garments, then (i, k) of the lower garments, which read source N + i
-    mats = np.concatenate([fwd_u.reshape(-1, 3, 3), fwd_l[:, low].reshape(-1, 3, 3)])
-    valid = np.concatenate([valid_u.reshape(-1), valid_l[:, low].reshape(-1)])
-    src_index = np.concatenate([np.repeat(np.arange(n, dtype=np.int32), pu), np.repeat(np.arange(n, 2 * n, dtype=np.int32), pl)])
-    warp = lambda src: warp_perspective(src, mats, (ph, pw), 'replicate', src_index, valid)
-    split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
-    (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
-
-    den_u, part_masks = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS, want_part_masks)
-    den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
-    m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
-    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p)
+    ``donor_joints is person_joints`` (the training samples: everyone wears their own garments) solves N sets of matrices,
+    not 2N.  ``want_part_masks``: a tenth value, the eroded 0 / 1 masks [N,10,H,W] of the upper composite's parts.
+    This is the outfit form below with the people stacked persons first, then donors."""
+    n = len(person_joints)
+    same = donor_joints is person_joints
+    person = np.arange(n)
+    donor = person if same else person + n
+    people = person_joints if same else np.concatenate([np.asarray(person_joints, np.float64), np.asarray(donor_joints, np.float64)])
+    out, valid, part_masks = _region_warps(garment_img, garment_mask, people, person, donor if upper_from_donor else person,
+                                           donor if lower_from_donor else person, box_factor, want_part_masks)
+    out += (valid[donor], valid[person])
     return out + (part_masks,) if want_part_masks else out
+
+
+def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2):
+    """normalize_region_batch for outfits: ``people_joints`` [M, 18, 3] float64 (host), the batch's DISTINCT people, already
+    shifted by the padding; ``person_idx`` / ``upper_idx`` / ``lower_idx`` [N]: who sample i is and whose upper and lower
+    garment ``garment_img`` / ``garment_mask`` hold for it.  The matrices of each of the M people are solved once, whatever
+    the number of samples that use them; a garment goes forward with its owner's matrices and back with the person's M_inv.
+    Returns normalize_region_batch's first seven values, then upper_valid, lower_valid, person_valid [N,10] bool."""
+    out, valid, _ = _region_warps(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor, False)
+    return out + (valid[np.asarray(upper_idx)], valid[np.asarray(lower_idx)], valid[np.asarray(person_idx)])

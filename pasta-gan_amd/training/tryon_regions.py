@@ -13,6 +13,12 @@ The host keeps the file decoding (training/dataset.py), the key-point geometry a
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621).
 
+``TryOnOutfitBatchBuilder`` prepares OUTFITS, this project's own: a person with the upper garment of one donor and the lower
+garment of another (``training.dataset.UvitonOutfits_512_test``, ``collate_outfits``).  The launches are the ones above with
+pasta_tryon_outfit_masks_u8 (a source per garment) and pasta_tryon_outfit_assemble (``clothes_lower`` as a tenth tensor); the
+batch's distinct people are uploaded once and ``patch_pipeline.normalize_outfit_batch`` solves their matrices once.  A pair with
+a change region is the outfit (P, D, D), (P, D, P) or (P, P, D).
+
 ``FullBodyRegionBatchBuilder`` prepares TRAINING batches at 512 x 320 (``training.dataset.UvitonDatasetFull_512``).  The
 reference has no 512 training set, so the rule is this project's own: the generator is trained on exactly the inputs
 test_512.py will later feed it.  A sample is the full-body preparation above of the pair (person, person), plus the 256
@@ -23,6 +29,7 @@ training set's photograph as target, ``gt_parsing`` and erase mask (include/past
     patch_pipeline.normalize_region_batch the matrices solved once, the eroded part masks of the upper composite kept
     pasta_tryon_train_region_assemble     the erase mask and the nine fp32 tensors of FullBodyBatch.KEYS"""
 
+import numpy as np
 import torch
 
 from torch_utils.ops import _native
@@ -46,6 +53,32 @@ class TryOnRegionBatch(TryOnPairBatch):
             'denorm_lower_mask']
 
 
+def _person_launches(parsing, kp, n, H, W, dev):
+    """What both test builders do first: the person's thick stick figure and palm mask, launched, and the uint8 tensors the
+    label-masks entry fills: (stick, palm, retain_img [n,H,H,3], garment_img, garment_mask [2n,H,H,3]: the upper garments, then
+    the lower garments)."""
+    limbs, joints, quads, present = device_tables(kp, kp, (H - W) // 2, dev)
+    u8 = allocator(torch.uint8, dev)
+    stick, palm, retain_img = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H, 3)
+    garment_img, garment_mask = u8(2 * n, H, H, 3), u8(2 * n, H, H, 3)
+    lib, P = _native.lib(), _native.ptr
+    with torch.cuda.device(dev):
+        s = _native.stream()
+        _native.check(lib.pasta_pose_stickman_thick_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
+        _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
+    return stick, palm, retain_img, garment_img, garment_mask
+
+
+def _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized, **valid):
+    """The uint8 intermediates both test builders keep: the person's unpadded ``image`` and ``parsing`` (which
+    metrics.tryon_fidelity scores against), the label stages and ``normalized``, normalize_region_batch's first seven values."""
+    n = image.shape[0]
+    patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs = normalized
+    return dict(image=image, parsing=parsing, stick=stick, palm=palm, retain_img=retain_img, upper_img=garment_img[:n],
+                upper_mask=garment_mask[:n], lower_img=garment_img[n:], lower_mask=garment_mask[n:], patches=patches, patches_lower=patches_l,
+                mask_patches=mask_patches, mask_patches_lower=mask_patches_l, denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, **valid)
+
+
 class TryOnRegionBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_pairs`` -> TryOnRegionBatch on ``device`` for
     ``change_region`` = 'fullbody', 'upperbody' or 'lowerbody'."""
@@ -63,20 +96,15 @@ class TryOnRegionBatchBuilder:
         n, H, W, _ = image.shape
         lp = (H - W) // 2
         code, upper_donor, lower_donor = REGIONS[self.change_region]
-        limbs, joints, quads, present = device_tables(kp, kp, lp, dev)
-        u8 = allocator(torch.uint8, dev)
-        stick, palm, retain_img = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H, 3)
-        garment_img, garment_mask = u8(2 * n, H, H, 3), u8(2 * n, H, H, 3)  # the upper garments, then the lower garments
-        upper_img, lower_img, upper_mask, lower_mask = garment_img[:n], garment_img[n:], garment_mask[:n], garment_mask[n:]
+        stick, palm, retain_img, garment_img, garment_mask = _person_launches(parsing, kp, n, H, W, dev)
         lib, P = _native.lib(), _native.ptr
         with torch.cuda.device(dev):
-            s = _native.stream()
-            _native.check(lib.pasta_pose_stickman_thick_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
-            _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
-            _native.check(lib.pasta_tryon_region_masks_u8(P(image), P(parsing), P(palm), P(d_image), P(d_parsing), P(retain_img), P(upper_img),
-                                                          P(upper_mask), P(lower_img), P(lower_mask), n, H, W, code, s))
-        patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_d, valid_p = patch_pipeline.normalize_region_batch(
+            _native.check(lib.pasta_tryon_region_masks_u8(P(image), P(parsing), P(palm), P(d_image), P(d_parsing), P(retain_img),
+                                                          P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]), P(garment_mask[n:]),
+                                                          n, H, W, code, _native.stream()))
+        *normalized, valid_d, valid_p = patch_pipeline.normalize_region_batch(
             garment_img, garment_mask, shift_keypoints(d_kp, lp), shift_keypoints(kp, lp), upper_donor, lower_donor, self.box_factor)
+        patches, patches_l, _, _, den_u, den_l, _ = normalized
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
         t, outs = output_tensors(TryOnRegionBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
         with torch.cuda.device(dev):
@@ -84,11 +112,64 @@ class TryOnRegionBatchBuilder:
                                                           P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
         stages = None
         if keep_stages:
-            stages = dict(stick=stick, palm=palm, retain_img=retain_img, upper_img=upper_img, upper_mask=upper_mask, lower_img=lower_img,
-                          lower_mask=lower_mask, patches=patches, patches_lower=patches_l, mask_patches=mask_patches,
-                          mask_patches_lower=mask_patches_l, denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, clothes_valid=valid_d,
-                          person_valid=valid_p)
+            stages = _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized, clothes_valid=valid_d,
+                             person_valid=valid_p)
         return TryOnRegionBatch(t, raw['person_name'], raw['clothes_name'], stages)
+
+
+class TryOnOutfitBatch(TryOnRegionBatch):
+    """``tensors``: the nine of TryOnRegionBatch, ``clothes`` being the upper garment's donor, and ``clothes_lower``, the lower
+    garment's donor; ``person_name`` / ``upper_name`` / ``lower_name``: the data set's relative paths (``clothes_name`` is
+    ``upper_name``); ``stages`` as TryOnRegionBatch's, with ``upper_valid`` / ``lower_valid`` / ``person_valid`` [N, 10]."""
+    KEYS = TryOnRegionBatch.KEYS + ['clothes_lower']
+
+    def __init__(self, tensors, person_name, upper_name, lower_name, stages=None):
+        super().__init__(tensors, person_name, upper_name, stages)
+        self.upper_name = self.clothes_name
+        self.lower_name = list(lower_name)
+
+
+class TryOnOutfitBatchBuilder:
+    """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` -> TryOnOutfitBatch on ``device``.  The batch's M
+    distinct people are uploaded once and their matrices solved once; the per-sample views (the person, the owner of the upper
+    garment, the owner of the lower one) are gathered on the device.  The launches are the region builder's, with
+    pasta_tryon_outfit_masks_u8 and pasta_tryon_outfit_assemble where that has the region entries: the outfits (P, D, D),
+    (P, D, P) and (P, P, D) give TryOnRegionBatchBuilder's full-body, upper-body and lower-body tensors bit for bit."""
+
+    def __init__(self, device, box_factor=2):
+        self.device = torch.device(device)
+        self.box_factor = box_factor
+
+    def build(self, raw, keep_stages=False):
+        dev = self.device
+        people_image, people_parsing, people_kp = upload_person(raw, dev, 'TryOnOutfitBatchBuilder', 'people_')
+        m, H, W, _ = people_image.shape
+        lp = (H - W) // 2
+        host_idx = [np.asarray(raw[k], np.int64) for k in ('person_idx', 'upper_idx', 'lower_idx')]
+        n = len(host_idx[0])
+        assert all(ix.shape == (n,) and ix.min() >= 0 and ix.max() < m for ix in host_idx), 'outfit indices outside the people stack'
+        (image, parsing), (u_image, u_parsing), (l_image, l_parsing) = (
+            (people_image.index_select(0, ix), people_parsing.index_select(0, ix))
+            for ix in (torch.from_numpy(ix).to(dev, non_blocking=True) for ix in host_idx))
+        stick, palm, retain_img, garment_img, garment_mask = _person_launches(parsing, people_kp[host_idx[0]], n, H, W, dev)
+        lib, P = _native.lib(), _native.ptr
+        with torch.cuda.device(dev):
+            _native.check(lib.pasta_tryon_outfit_masks_u8(P(image), P(parsing), P(palm), P(u_image), P(u_parsing), P(l_image), P(l_parsing),
+                                                          P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
+                                                          P(garment_mask[n:]), n, H, W, _native.stream()))
+        *normalized, valid_u, valid_l, valid_p = patch_pipeline.normalize_outfit_batch(
+            garment_img, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
+        patches, patches_l, _, _, den_u, den_l, _ = normalized
+        pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
+        t, outs = output_tensors(TryOnOutfitBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.pasta_tryon_outfit_assemble(P(image), P(u_image), P(l_image), P(retain_img), P(stick), P(patches), P(patches_l),
+                                                          P(den_u), P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
+        stages = None
+        if keep_stages:
+            stages = _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized, upper_valid=valid_u,
+                             lower_valid=valid_l, person_valid=valid_p)
+        return TryOnOutfitBatch(t, raw['person_name'], raw['upper_name'], raw['lower_name'], stages)
 
 
 class FullBodyRegionBatchBuilder:

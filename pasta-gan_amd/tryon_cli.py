@@ -1,5 +1,9 @@
 """What the two try-on command lines, test.py and test_512.py, share: the options the reference declares, the refusal of a
-snapshot that is not a local file, loading ``G_ema``, the loader over a pair data set and the generator's call sequence."""
+snapshot that is not a local file, loading ``G_ema``, the loader over a pair data set, the generator's call sequence and the
+--scores report.
+
+test_512.py's --outfits and --scores are declared and served HERE, not in that file, which stays the reference's command line
+as it was (``shared_options`` says how): ``generate_512`` is the one loop for those runs, outfits or pairs."""
 
 import functools
 import inspect
@@ -43,16 +47,31 @@ def shared_options(dataroot_help, batchsize):
         storage_option]
 
     def decorate(f):
+        parameters = inspect.signature(f).parameters
         # --storage is kept here for ``load_generator`` and handed to the command's function only where it declares the argument
         # (test.py writes it into its report): a command line that just loads and runs the generator needs no line for it
-        takes_storage = 'storage' in inspect.signature(f).parameters
+        takes_storage = 'storage' in parameters
+        # A command whose function takes ``change_region`` and no ``scores_file`` of its own is the 512 x 320 command line.  It
+        # gets --outfits and --scores from here, and a run that gives either is ``generate_512`` below, not the function's
+        # own loop over the pair lists, which knows neither: test_512.py stays as it is and still runs every plain command.
+        # tests/test_tryon_outfits_gpu.py holds the two loops to the same files for the same pairs.
+        extended = 'change_region' in parameters and 'scores_file' not in parameters
 
         @functools.wraps(f)
         def command(*args, storage=None, **kwargs):
             _given['storage'] = storage
+            if extended:
+                outfits_file, scores_file = kwargs.pop('outfits_file', None), kwargs.pop('scores_file', None)
+                if outfits_file is not None or scores_file is not None:
+                    for unused in ('seeds', 'class_idx', 'projected_w'):
+                        kwargs.pop(unused, None)
+                    kwargs['change_region'] = _explicit_region(kwargs.get('change_region'))
+                    return generate_512(*args, outfits_file=outfits_file, scores_file=scores_file, storage=storage, **kwargs)
             if takes_storage:
                 kwargs['storage'] = storage
             return f(*args, **kwargs)
+        if extended:
+            command = scores_option(outfits_option(command))
         for option in reversed(options):
             command = option(command)
         return command
@@ -64,6 +83,28 @@ STORAGE_DTYPES = {'snapshot': None, 'f32': 'float32', 'bf16': 'bfloat16', 'f16':
 _given = {}                 # the running command's --storage (``shared_options``)
 storage_option = click.option('--storage', help='Activation storage the generator runs in: as pickled (snapshot), or f32, bf16, f16 '
                               '[default: snapshot]', type=click.Choice(list(STORAGE_DTYPES)))
+
+scores_option = click.option(
+    '--scores', 'scores_file', type=str, metavar='FILE',
+    help='Score the written images by region (kept body parts, upper and lower garment patches: L1, PSNR, SSIM) and write the results to '
+         'FILE as JSON. With this option z of pair i is np.random.RandomState(i).randn(z_dim), so that the figures describe the images '
+         'whatever the batch size [default: no scores]')
+
+outfits_option = click.option(
+    '--outfits', 'outfits_file', type=str, metavar='FILE',
+    help='Dress the people of FILE instead of the pair lists: lines "person upper lower", each <sub-dataset>/<file>.jpg, "-" for a '
+         'garment the person keeps; written as upper donor | lower donor | person | generated. Not together with --change-region')
+
+
+def _explicit_region(change_region):
+    """--change-region as the user gave it, None when it is the option's default: from click's record of where the value came
+    from.  When the callback is called without a click context there is no such record; 'fullbody', what the default means, then
+    counts as not given."""
+    context = click.get_current_context(silent=True)
+    if context is not None:
+        return change_region if context.get_parameter_source('change_region') != click.core.ParameterSource.DEFAULT else None
+    return None if change_region == 'fullbody' else change_region
+
 
 workers_option = click.option('--workers', help='Loader processes (file decoding only)', type=click.IntRange(min=0), default=4, show_default=True)
 
@@ -84,12 +125,13 @@ def load_generator(network_pkl, device, storage=None):
     return G
 
 
-def pair_loader(dataset, batchsize, workers):
-    """The pairs of ``dataset`` in order; the workers only decode files."""
+def pair_loader(dataset, batchsize, workers, collate_fn=None):
+    """The pairs (or, with ``training.dataset.collate_outfits``, the outfits) of ``dataset`` in order; the workers only decode files."""
     import torch
     from training.dataset import collate_pairs
     print(len(dataset))
-    return torch.utils.data.DataLoader(dataset, batch_size=batchsize, shuffle=False, num_workers=workers, pin_memory=True, collate_fn=collate_pairs)
+    return torch.utils.data.DataLoader(dataset, batch_size=batchsize, shuffle=False, num_workers=workers, pin_memory=True,
+                                       collate_fn=collate_fn or collate_pairs)
 
 
 def generate(G, t, gen_z, truncation_psi, noise_mode):
@@ -107,3 +149,75 @@ def generate(G, t, gen_z, truncation_psi, noise_mode):
         cat_feats = {str(feat.shape[2]): feat for feat in cat_feat_list}
         return G.synthesis(ws, pose_feat, cat_feats, t['denorm_upper_input'], t['denorm_lower_input'], t['denorm_upper_mask'],
                            t['denorm_lower_mask'], noise_mode=noise_mode)[1]
+
+
+def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None):
+    """--scores: the figures of ``metrics.tryon_fidelity.finish`` (prefix ``tryon``) and what the run was, as one JSON line,
+    printed and written to ``scores_file``."""
+    import json
+    from metrics import tryon_fidelity
+    report = dict(results=tryon_fidelity.finish(partials, 'tryon', pixels=pixels), pairs=pairs, network=network_pkl, dataroot=dataroot,
+                  noise_mode=noise_mode)
+    if storage is not None:
+        report['storage'] = storage
+    line = json.dumps(report)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
+    with open(scores_file, 'w') as f:
+        f.write(line + '\n')
+
+
+def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
+                 scores_file=None, storage=None):
+    """test_512.py with --outfits and / or --scores.  --outfits FILE: every line ``person upper lower`` of FILE
+    (training.dataset.UvitonOutfits_512_test) instead of the pair lists, prepared by
+    training.tryon_regions.TryOnOutfitBatchBuilder, written as ``upper donor | lower donor | person | generated`` (512 x 2048) to
+    ``<outdir>/<count>.png`` in list order.  ``change_region`` None means full body; any other value is refused together with
+    --outfits, since a line names whose garments are worn.  --scores FILE: the region scores of metrics/tryon_fidelity.py over
+    what is written, z of item i from ``pair_z(i)``, ``pixels = 512 * 320``.  Without --outfits the pairs of the change region
+    are written as test_512.py writes them, ``clothes | person | generated``."""
+    if outfits_file is not None and change_region is not None:
+        raise click.UsageError('--outfits and --change-region exclude each other: every line of the outfit list names whose garments are worn')
+    _local_snapshot(network_pkl)
+
+    import numpy as np
+    import PIL.Image
+    import torch
+
+    from metrics import tryon_fidelity
+    from training import dataset as custom_dataset
+    from training.tryon_pairs import images_to_u8
+    from training.tryon_regions import TryOnOutfitBatchBuilder, TryOnRegionBatchBuilder
+
+    device = torch.device('cuda')
+    G = load_generator(network_pkl, device, storage)
+    os.makedirs(outdir, exist_ok=True)
+    if outfits_file is not None:
+        dataset = custom_dataset.UvitonOutfits_512_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
+        loader = pair_loader(dataset, batchsize, workers, custom_dataset.collate_outfits)
+        builder, panels = TryOnOutfitBatchBuilder(device), ('clothes', 'clothes_lower', 'image')
+    else:
+        change_region = change_region or 'fullbody'
+        dataset = custom_dataset.UvitonDatasetFull_512_test(path=dataroot, change_region=change_region, use_labels=True, max_size=None, xflip=False)
+        loader = pair_loader(dataset, batchsize, workers)
+        builder, panels = TryOnRegionBatchBuilder(device, change_region), ('clothes', 'image')
+    partials = tryon_fidelity.new_partials(len(dataset), device) if scores_file is not None else None
+    count = 0
+    for raw in loader:
+        batch = builder.build(raw, keep_stages=scores_file is not None)
+        t, n = batch.tensors, batch.batch
+        side = t['image'].shape[2]
+        gen_z = torch.empty([n, 0], device=device)
+        if scores_file is not None:
+            index = raw['raw_idx'].tolist()                         # the items' positions in the pair lists, or in the outfit list
+            gen_z = tryon_fidelity.pair_z(index, G.z_dim, device)
+        gen_imgs = generate(G, t, gen_z, truncation_psi, noise_mode)
+        if scores_file is not None:
+            tryon_fidelity.score_batch(gen_imgs, batch, index, partials)
+        images = torch.cat([images_to_u8(x, 0, side) for x in [t[k] for k in panels] + [gen_imgs]], dim=2).cpu().numpy()
+        for result in images:
+            PIL.Image.fromarray(np.ascontiguousarray(result)).save(os.path.join(outdir, str(count).zfill(3) + '.png'))
+            count += 1
+    print('finish: %d images under %s' % (count, outdir))
+    if scores_file is not None:
+        write_scores(scores_file, partials, 512 * 320, count, network_pkl, dataroot, noise_mode, storage)
