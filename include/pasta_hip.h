@@ -581,6 +581,16 @@ int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks
                                     uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
                                     void* stream);
 
+/* pasta_patch_composite_eroded_u8 with a radius per sample: sample n is eroded by radius[n] (uint8 [N] on the device, each
+ * 0 .. 8), all samples in the one launch; the radius is uniform across a workgroup, which works on one sample.  A sample with
+ * radius 0 is pasta_patch_composite_u8 bit for bit and takes no barrier; a sample with radius r is
+ * pasta_patch_composite_eroded_u8 at r bit for bit, part_mask included.  The values live on the device, so the entry cannot
+ * refuse one: the caller checks them on the host (patch_pipeline.composite raises), and the kernel reads a value above 8 as
+ * 8, the halo its LDS tiles hold. */
+int pasta_patch_composite_radii_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
+                                   uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W,
+                                   const uint8_t* radius, void* stream);
+
 /* __getitem__ (:1502-1525) and test.py:104-117: the seven fp32 NCHW tensors G takes, through outputs (a HOST array of 7
  * device pointers) in this order: retain [N,3,H,H] (test.py's image), pose [N,6,H,H] = stick || retain,
  * style_input [N,6P,ph,pw] = the P garment patches (channel 3k + c of part k) || the P stick-figure patches,
@@ -595,6 +605,29 @@ int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, c
  * each operation rounded on its own, clipped to [0, 255], truncated.  A NaN becomes 0 (numpy leaves that conversion
  * undefined). */
 int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream);
+
+/* An OUTFIT at 256 x 192 (this project's own; training/tryon_pairs.py, TryOnPairOutfitBatchBuilder): (P, U, L), the person P in
+ * the upper garment of U and the lower garment of L, either of whom may be P.  The pair rules above with a source per garment:
+ *   1. retain_img, the palm mask (boxes 25 and 15), the stick figure in `pose` and every M_inv are P's;
+ *   2. the upper garment is labels 5, 6, 7 of U; parts 0-5 of the garment, of U's stick figure and of the mask are warped
+ *      forward with U's matrices;
+ *   3. the lower garment is labels 6, 9, 12 of L; parts 6-9 of the garment, of L's stick figure and of the mask are warped
+ *      forward with L's matrices;
+ *   4. key points shifted by the padding in float64, x_pad = 0, the knee-without-ankle fall-back, for all three people;
+ *   5. all ten parts go back with P's M_inv; a missing forward matrix gives zeros, a part whose M_inv is missing is skipped;
+ *   6. parts 0-5 go into denorm_upper through the eroded composite (5 x 5) whoever U is, as the reference erodes them;
+ *   7. parts 6-9 go into denorm_lower through the plain composite when L is P (the reference's case, bit for bit) and through
+ *      the eroded composite (5 x 5) when L is somebody else: a mask warped onto another body has a fringe, the reference's
+ *      reason for rule 6.  The choice is per sample (pasta_patch_composite_radii_u8 with radius 0 or 2).
+ * The change regions are three outfits: upper body (P, D, P), which is the pair rules above; lower body (P, P, D); full body
+ * (P, D, D).
+ * pasta_tryon_pair_masks_u8's rules with a source per garment, arguments and output order as pasta_tryon_outfit_masks_u8:
+ * upper_img / upper_mask = labels 5, 6, 7 of (upper_image, upper_parsing), lower_img / lower_mask = labels 6, 9, 12 of
+ * (lower_image, lower_parsing).  With (donor, person) as the two sources it is pasta_tryon_pair_masks_u8 byte for byte. */
+int pasta_tryon_pair_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
+                                     const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
+                                     uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                                     uint8_t* lower_mask, int N, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the 512 x 320 try-on pairs with a change region (row f4; UvitonDatasetFull_512_test,

@@ -15,7 +15,9 @@ struct ErPart { const uint8_t* patch; const uint8_t* mask; const double* m; };  
 // patch_composite_u8_kernel with cv2.erode(mask, ones(2r+1, 2r+1)) of the warped-back mask before the == 255 test.  Since
 // 255 is the largest uint8, the eroded channel 0 is 255 exactly where every in-image pixel within +-r has channel 0 == 255
 // (cv2's default erode border: pixels outside the image do not erode).  Per part: the == 255 flags of the tile and an r-pixel
-// halo go to LDS, are AND-ed along rows and then along columns; the running RGB stays in registers.
+// halo go to LDS, are AND-ed along rows and then along columns; the running RGB stays in registers.  r is a run-time value that
+// is the same in every thread of the block (a launch's scalar, or the radius of the block's sample); with r == 0 a part is
+// patch_composite_u8_kernel's own test and touches neither LDS nor a barrier.
 // part_of(k) names part k of this block's image (the same answer in every thread of the block); out: the image [H, W, 3];
 // part_mask: its [P, H, W] masks or nullptr; flags [ER_S * ER_S] and rows [ER_S * ER_T]: the block's LDS.  256 threads.
 template <class PartOf>
@@ -33,32 +35,38 @@ __device__ __forceinline__ void composite_eroded_tile(PartOf part_of, uint8_t* _
             if (part_mask && mine) part_mask[((int64_t)k * H + y) * W + x] = 0;
             continue;
         }
-        for (int i = threadIdx.x; i < S * S; i += 256) {
-            const int gy = ty0 - r + i / S, gx = tx0 - r + i % S;
-            uint8_t f = 1;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                int X, Y;
-                pw_source(part.m, gx, gy, X, Y);
-                f = pw_sample(part.mask, pw, 3, 0, pw_taps(X, Y, pw, ph, 0)) == 255;
+        if (r > 0) {                                            // uniform across the block, as r is
+            for (int i = threadIdx.x; i < S * S; i += 256) {
+                const int gy = ty0 - r + i / S, gx = tx0 - r + i % S;
+                uint8_t f = 1;
+                if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                    int X, Y;
+                    pw_source(part.m, gx, gy, X, Y);
+                    f = pw_sample(part.mask, pw, 3, 0, pw_taps(X, Y, pw, ph, 0)) == 255;
+                }
+                flags[i] = f;
             }
-            flags[i] = f;
+            __syncthreads();
+            for (int i = threadIdx.x; i < S * ER_T; i += 256) {
+                const int ry = i / ER_T, rx = i % ER_T;
+                uint8_t f = 1;
+                for (int d = 0; d <= 2 * r; d++) f &= flags[ry * S + rx + d];
+                rows[i] = f;
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < S * ER_T; i += 256) {
-            const int ry = i / ER_T, rx = i % ER_T;
-            uint8_t f = 1;
-            for (int d = 0; d <= 2 * r; d++) f &= flags[ry * S + rx + d];
-            rows[i] = f;
-        }
-        __syncthreads();
         if (mine) {
             uint8_t hit = 1;
-            for (int d = 0; d <= 2 * r; d++) hit &= rows[(ty + d) * ER_T + tx];
-            if (hit) {
+            if (r > 0)
+                for (int d = 0; d <= 2 * r; d++) hit &= rows[(ty + d) * ER_T + tx];
+            if (hit) {                                          // r == 0: the pixel's own mask value decides, no LDS and no barrier
                 int X, Y;
                 pw_source(part.m, x, y, X, Y);
                 const PwTaps t = pw_taps(X, Y, pw, ph, 0);
-                red = pw_sample(part.patch, pw, 3, 0, t); green = pw_sample(part.patch, pw, 3, 1, t); blue = pw_sample(part.patch, pw, 3, 2, t);
+                if (r == 0) hit = pw_sample(part.mask, pw, 3, 0, t) == 255;
+                if (hit) {
+                    red = pw_sample(part.patch, pw, 3, 0, t); green = pw_sample(part.patch, pw, 3, 1, t); blue = pw_sample(part.patch, pw, 3, 2, t);
+                }
             }
             if (part_mask) part_mask[((int64_t)k * H + y) * W + x] = hit;
         }

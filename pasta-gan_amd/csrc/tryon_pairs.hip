@@ -6,6 +6,9 @@
 //   pasta_tryon_pair_masks_u8        retain image, the person's lower garment and the donor's upper garment (:1105-1141);
 //   pasta_patch_composite_eroded_u8  the warp-back composite with cv2.erode(5 x 5) of the mask before the == 255 test
 //                                    (:1480-1492);
+//   pasta_patch_composite_radii_u8   that composite with a radius per sample in one launch: 0, the plain composite, for a
+//                                    person's own lower garment and 2 for another's (the 256 OUTFITS, this project's own);
+//   pasta_tryon_pair_outfit_masks_u8 pasta_tryon_pair_masks_u8's rules with a source of its own for each garment (the same);
 //   pasta_tryon_pair_assemble        __getitem__ (:1502-1525) and test.py's conversions (:104-117) into the seven fp32 tensors;
 //   pasta_images_to_u8               test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137).
 // The 512 x 320 pairs with a change region (UvitonDatasetFull_512_test._load_raw_image / normalize_full / normalize_upper /
@@ -84,13 +87,18 @@ __global__ __launch_bounds__(256) void tryon_pair_masks_kernel(const uint8_t* __
 // ---- eroded composite ----
 
 // The tile work is csrc/patch_erode.h's (shared with the snapshot grid's indexed composite); here part k of sample n is item n * P + k.
+// The one kernel of both entries: sample n is eroded by radius[n], or by r where radius is null.  A block works on one sample, so
+// its radius is uniform across the block; a value above ER_MAX_R (the entry's callers check theirs on the host) is taken as
+// ER_MAX_R, what the LDS tiles hold.
 __global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8_t* __restrict__ patches, const uint8_t* __restrict__ masks,
                                                                      const double* __restrict__ minv, const uint8_t* __restrict__ valid,
                                                                      uint8_t* __restrict__ out, uint8_t* __restrict__ part_mask, int P, int ph,
-                                                                     int pw, int H, int W, int r, int tiles_x) {
+                                                                     int pw, int H, int W, const uint8_t* __restrict__ radius, int r,
+                                                                     int tiles_x) {
     __shared__ uint8_t flags[ER_S * ER_S];
     __shared__ uint8_t rows[ER_S * ER_T];
     const int n = blockIdx.y;
+    if (radius) r = radius[n] < ER_MAX_R ? radius[n] : ER_MAX_R;
     const auto part_of = [=](int k) {
         const int64_t item = (int64_t)n * P + k;
         return ErPart{patches + item * ph * pw * 3, valid[item] ? masks + item * ph * pw * 3 : nullptr, minv + item * 9};
@@ -214,7 +222,7 @@ extern "C" int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quad
     return pasta_palm_mask_square_u8(parsing, quads, present, out, N, H, W, k_upper, k_lower, stream);
 }
 
-// The label-masks entries, `what` naming the caller in the error texts.  pair_masks_args: the checks all three share.
+// The label-masks entries, `what` naming the caller in the error texts.  pair_masks_args: the checks all four share.
 static int pair_masks_args(const char* what, bool pointers, int N, int H, int W) {
     PASTA_CHECK(pointers, "%s: null pointer", what);
     PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "%s: bad shape", what);
@@ -274,19 +282,46 @@ extern "C" int pasta_tryon_outfit_masks_u8(const uint8_t* image, const uint8_t* 
                              upper_img, upper_mask, lower_img, lower_mask, N, H, W, 0, stream);
 }
 
-extern "C" int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
-                                               uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
-                                               void* stream) {
+extern "C" int pasta_tryon_pair_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
+                                                const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
+                                                uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
+                                                uint8_t* lower_mask, int N, int H, int W, void* stream) {
+    if (const int rc = pair_masks_args("tryon_pair_outfit_masks_u8", image && parsing && palm && upper_image && upper_parsing && lower_image &&
+                                                                         lower_parsing && retain_img && upper_img && upper_mask && lower_img &&
+                                                                         lower_mask, N, H, W))
+        return rc;
+    return launch_pair_masks("tryon_pair_outfit_masks_u8", image, parsing, palm, upper_image, upper_parsing, lower_image, lower_parsing,
+                             retain_img, upper_img, upper_mask, lower_img, lower_mask, N, H, W, 1, stream);
+}
+
+// Both eroded composites: `radius` [N] on the device, or null and the scalar r for every sample.
+static int launch_composite_eroded(const char* what, const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
+                                   uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, const uint8_t* radius, int r,
+                                   void* stream) {
     using namespace pasta;
-    PASTA_CHECK(patches && masks && minv && valid && out, "patch_composite_eroded_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && P >= 1 && ph >= 1 && pw >= 1 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
-                "patch_composite_eroded_u8: bad shape");
-    PASTA_CHECK(radius >= 0 && radius <= ER_MAX_R, "patch_composite_eroded_u8: radius %d (0..%d)", radius, ER_MAX_R);
+    PASTA_CHECK(patches && masks && minv && valid && out, "%s: null pointer", what);
+    PASTA_CHECK(N >= 1 && N <= 65535 && P >= 1 && ph >= 1 && pw >= 1 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "%s: bad shape", what);
+    PASTA_CHECK(r >= 0 && r <= ER_MAX_R, "%s: radius %d (0..%d)", what, r, ER_MAX_R);
     const int tiles_x = (W + ER_T - 1) / ER_T, tiles_y = (H + ER_T - 1) / ER_T;
     dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
     hipLaunchKernelGGL(patch_composite_eroded_kernel, grid, dim3(256), 0, (hipStream_t)stream, patches, masks, minv, valid, out, part_mask, P,
-                       ph, pw, H, W, radius, tiles_x);
-    return launch_status("patch_composite_eroded_u8");
+                       ph, pw, H, W, radius, r, tiles_x);
+    return launch_status(what);
+}
+
+extern "C" int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
+                                               uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
+                                               void* stream) {
+    return launch_composite_eroded("patch_composite_eroded_u8", patches, masks, minv, valid, out, part_mask, N, P, ph, pw, H, W, nullptr, radius,
+                                   stream);
+}
+
+extern "C" int pasta_patch_composite_radii_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
+                                              uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W,
+                                              const uint8_t* radius, void* stream) {
+    PASTA_CHECK(radius, "patch_composite_radii_u8: null pointer");
+    return launch_composite_eroded("patch_composite_radii_u8", patches, masks, minv, valid, out, part_mask, N, P, ph, pw, H, W, radius, 0,
+                                   stream);
 }
 
 extern "C" int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* stick_patches,

@@ -19,6 +19,13 @@ Differences from the reference, on purpose:
   --scores FILE scores every image by region against what the generator was told to reproduce (metrics/tryon_fidelity.py: kept
   body parts against the photograph, garment patches against themselves; L1, PSNR, SSIM) and writes one JSON object.  These are
   this project's own figures; the reference has none for test.py.
+  --change-region upperbody | lowerbody | fullbody takes the donor's upper garment (what a run without the option does, and the
+  same bytes), the donor's lower garment over the person's own top, or both.  The reference's 256 test set knows the first only.
+  --outfits FILE dresses every line ``person upper lower`` of FILE instead of the pair lists: the upper garment of one donor,
+  the lower garment of another, ``-`` for a garment the person keeps (training.dataset.UvitonOutfits_256_test), written to
+  ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower stem>.png``.  Both options are this project's own
+  (include/pasta_hip.h lists the rules), exclude each other and are served by ``tryon_cli.generate_256``; a run with neither is
+  the loop below.
 """
 
 import os
@@ -31,17 +38,22 @@ import tryon_cli
 
 @click.command()
 @tryon_cli.shared_options('Root of the test data set', 16)
+@tryon_cli.region_option
+@tryon_cli.pair_outfits_option
 @tryon_cli.workers_option
 @tryon_cli.scores_option
 def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi: float, class_idx: Optional[int], noise_mode: str,
                     projected_w: Optional[str], outdir: str, dataroot: str, batchsize: int, workers: int, scores_file: Optional[str],
-                    storage: Optional[str] = None):
+                    storage: Optional[str] = None, change_region: Optional[str] = None, outfits_file: Optional[str] = None):
     """Generate unpaired try-on images from the test pairs with a trained snapshot.
 
     \b
     python test.py --network snapshot.pkl --outdir out --dataroot PASTA_UPT_256 --batchsize 16
     """
     del seeds, class_idx, projected_w
+    if outfits_file is not None or change_region is not None:
+        return tryon_cli.generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file,
+                                      change_region, scores_file, storage)
     tryon_cli._local_snapshot(network_pkl)
 
     import numpy as np

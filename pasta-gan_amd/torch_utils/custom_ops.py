@@ -228,6 +228,8 @@ ABI = {
     'pasta_palm_mask_box_u8': (ctypes.c_int, [_c_ptr] * 4 + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_tryon_pair_masks_u8': (ctypes.c_int, [_c_ptr] * 10 + [ctypes.c_int] * 3 + [_c_ptr]),
     'pasta_patch_composite_eroded_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 7 + [_c_ptr]),
+    'pasta_patch_composite_radii_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 6 + [_c_ptr] * 2),
+    'pasta_tryon_pair_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 3 + [_c_ptr]),
     'pasta_tryon_pair_assemble': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_images_to_u8': (ctypes.c_int, [_c_ptr] * 2 + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_pose_stickman_thick_u8': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 5 + [_c_ptr]),
@@ -260,7 +262,7 @@ LATE_ENTRIES = frozenset(['pasta_grid_sample', 'pasta_grid_sample_backward_works
                           'pasta_grid_composite_eroded_u8', 'pasta_grid_assemble', 'pasta_image_grid_tile_u8',
                           'pasta_recon_image_stats_workspace', 'pasta_recon_image_stats', 'pasta_parsing_confusion',
                           'pasta_region_image_stats_workspace', 'pasta_region_image_stats', 'pasta_tryon_outfit_masks_u8',
-                          'pasta_tryon_outfit_assemble'])
+                          'pasta_tryon_outfit_assemble', 'pasta_patch_composite_radii_u8', 'pasta_tryon_pair_outfit_masks_u8'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

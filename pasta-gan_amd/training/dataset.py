@@ -387,6 +387,18 @@ class UvitonOutfits_512_test(UvitonDatasetV19_test):
         return out
 
 
+class UvitonOutfits_256_test(UvitonOutfits_512_test):
+    """This project's own: outfits for the 256 x 192 model, ``UvitonOutfits_512_test`` on the 256 test tree.  The sub-dataset of
+    a name is one of ``TEST_SUB_DATASETS`` and label maps follow ``UvitonDatasetV19_test``'s rule (``parsing/<stem>_label.png``;
+    ``parsing/<stem>.png`` for ``MPV_256_192``).  The line format, the ``-`` rule, the errors and the raw outfit are the 512
+    class's, so ``collate_outfits`` serves both; ``training.tryon_pairs.TryOnPairOutfitBatchBuilder`` takes its batches.  The
+    change regions are three of its cases: upper body (P, D, -), what test.py does with a pair, lower body (P, -, D) and full
+    body (P, D, D)."""
+
+    _sub_datasets = TEST_SUB_DATASETS
+    _label_name = staticmethod(UvitonDatasetV19_test._label_name)
+
+
 def collate_outfits(samples):
     """A list of raw outfits -> one batch in which every DISTINCT person (by name) is stacked once, in the order of first
     appearance (samples in order; person, upper, lower within a sample): ``people_image`` uint8 [M, H, W, 3], ``people_parsing``
@@ -410,6 +422,27 @@ def collate_outfits(samples):
         out[role + '_idx'] = torch.as_tensor(index[role], dtype=torch.int64)
         out[role + '_name'] = [s[role + '_name'] for s in samples]
     out['raw_idx'] = torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64)
+    return out
+
+
+def pair_as_outfit(sample, change_region):
+    """A raw pair (``UvitonDatasetV19_test``) -> the raw outfit of a change region: upper body (P, D, P), the pair as test.py
+    dresses it, lower body (P, P, D), full body (P, D, D).  ``clothes_name`` stays."""
+    if change_region not in CHANGE_REGIONS:
+        raise ValueError('change region %s is invalid.' % change_region)
+    out = {k: sample[k] for k in ('image', 'parsing', 'keypoints', 'person_name', 'clothes_name', 'raw_idx')}
+    for role, prefix, donor in (('upper', 'upper_', change_region != 'lowerbody'), ('lower', 'lower_', change_region != 'upperbody')):
+        src, name = ('clothes_', 'clothes_name') if donor else ('', 'person_name')
+        out.update({prefix + k: sample[src + k] for k in ('image', 'parsing', 'keypoints')})
+        out[role + '_name'] = sample[name]
+    return out
+
+
+def collate_region_outfits(change_region, samples):
+    """``collate_outfits`` of raw PAIRS taken as the outfits of ``change_region`` (``pair_as_outfit``), with the pairs'
+    ``clothes_name``.  ``functools.partial(collate_region_outfits, region)`` is the DataLoader's ``collate_fn``."""
+    out = collate_outfits([pair_as_outfit(s, change_region) for s in samples])
+    out['clothes_name'] = [s['clothes_name'] for s in samples]
     return out
 
 #----------------------------------------------------------------------------

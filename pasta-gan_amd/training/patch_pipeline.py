@@ -148,20 +148,37 @@ def inverse_maps(back, parts):
     return np.ascontiguousarray(np.stack([adjugate_inverse(back[i, k]) for i in range(len(back)) for k in parts]).reshape(-1, 9))
 
 
+MAX_ERODE_RADIUS = 8        # ER_MAX_R of csrc/patch_erode.h: the halo its LDS tiles hold
+
+
 def composite(patches, masks, back, valid, parts, height, width, radius=None, want_part_masks=False):
     """patch -> image (BORDER_CONSTANT) + mask test + compositing of ``patches`` / ``masks`` [N, p, h, w, 3] in order, one launch:
     index j is part ``parts[j]`` of ``back`` [N, 10, 3, 3] / ``valid`` [N, 10], the maps of the people the result is drawn on.
     ``radius`` None: pasta_patch_composite_u8, the mask tested as warped; a value: pasta_patch_composite_eroded_u8, the mask eroded
-    (2 * radius + 1) square first.  Returns (image uint8 [N, height, width, 3], part masks uint8 [N, p, height, width] or None)."""
+    (2 * radius + 1) square first; a sequence [N]: pasta_patch_composite_radii_u8, sample i eroded by ``radius[i]`` (0: as warped),
+    still one launch.  A radius outside 0 .. 8 raises ValueError.  Returns (image uint8 [N, height, width, 3], part masks uint8
+    [N, p, height, width] or None)."""
     n, p, ph, pw = patches.shape[:4]
     dev = patches.device
+    lib = _native.lib()
+    if radius is None:
+        entry, extra = lib.pasta_patch_composite_u8, ()
+    elif np.ndim(radius) == 0:
+        entry, extra = lib.pasta_patch_composite_eroded_u8, (radius,)
+    else:
+        radii = np.asarray(radius).reshape(-1)
+        if radii.shape != (n,):
+            raise ValueError('composite: %d radii for %d samples' % (len(radii), n))
+        bad = np.flatnonzero((radii < 0) | (radii > MAX_ERODE_RADIUS))
+        if len(bad):
+            raise ValueError('composite: radius %d of sample %d (0..%d)' % (radii[bad[0]], bad[0], MAX_ERODE_RADIUS))
+        radius_t = torch.from_numpy(radii.astype(np.uint8)).to(dev)       # held until the launch is queued
+        entry, extra = lib.pasta_patch_composite_radii_u8, (_native.ptr(radius_t),)
     inv_t = torch.from_numpy(inverse_maps(back, parts)).to(dev)
     val_t = torch.as_tensor(np.ascontiguousarray(valid[:, parts]).astype(np.uint8), device=dev)
     out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
     pm = torch.empty([n, p, height, width], dtype=torch.uint8, device=dev) if want_part_masks else None
     patches, masks = patches.contiguous(), masks.contiguous()             # held until the launch is queued
-    lib = _native.lib()
-    entry, extra = (lib.pasta_patch_composite_u8, ()) if radius is None else (lib.pasta_patch_composite_eroded_u8, (radius,))
     with torch.cuda.device(dev):
         _native.check(entry(_native.ptr(patches), _native.ptr(masks), _native.ptr(inv_t), _native.ptr(val_t), _native.ptr(out), _native.ptr(pm),
                             n, p, ph, pw, height, width, *extra, _native.stream()))
@@ -201,34 +218,59 @@ UPPER_PARTS = 6             # the test set: parts 0..5 from the clothes donor, 6
 ERODE_RADIUS = 2            # cv2.erode(..., np.ones((5, 5))) of the warped-back masks of parts 0..5 (:1460, :1484-1485)
 
 
+def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2):
+    """The test set's ``normalize`` (dataset.py:1430-1500) for a batch of OUTFITS on the GPU (include/pasta_hip.h lists the
+    rules).  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image, 3-channel mask)
+    followed by the N lower garments.  ``people_stick`` [M, H, W, 3]: the stick figures of the batch's M DISTINCT people;
+    ``people_joints`` [M, 18, 3] float64 (host), already shifted by the padding (x_pad = 0 below).  ``person_idx`` /
+    ``upper_idx`` / ``lower_idx`` [N]: who sample i is and whose upper and lower garment it wears.
+    ONE part_matrices call solves the M people.  Parts 0..5 are cut from the upper garment, its owner's stick figure and its mask
+    with the owner's matrices, parts 6..9 from the lower garment's likewise: three forward-warp launches (image, stick figure,
+    mask).  All ten parts are warped back with the PERSON's M_inv: parts 0..5 into denorm_upper through the eroded composite,
+    parts 6..9 into denorm_lower in one launch whose radius is per sample, 0 (the plain composite) where the person wears their
+    own lower garment and ERODE_RADIUS where it is somebody else's.  Returns (patches, stick_patches, mask_patches
+    [N,10,h,w,3], denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid,
+    person_valid [N,10] bool)."""
+    garment_img, people_stick, garment_mask = _u8(garment_img), _u8(people_stick), _u8(garment_mask)
+    n2, height, width, _ = garment_img.shape
+    n = n2 // 2
+    assert n2 == 2 * n and garment_mask.shape == garment_img.shape and people_stick.shape[1:] == garment_img.shape[1:]
+    person_idx, upper_idx, lower_idx = (np.asarray(ix, np.int64).reshape(n) for ix in (person_idx, upper_idx, lower_idx))
+    ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
+    fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
+    back, valid_p = back[person_idx], valid_all[person_idx]
+    from_upper = np.arange(10) < UPPER_PARTS
+    owner = np.where(from_upper[None, :], upper_idx[:, None], lower_idx[:, None])      # [N, 10]: whose matrices and stick figure part k takes
+    part = np.arange(10)[None, :]
+    mats, valid = fwd[owner, part].reshape(-1, 3, 3), valid_all[owner, part].reshape(-1)
+    # item (i, k) reads garment i of the upper ones (0..N-1) for k < 6 and of the lower ones (N..2N-1) otherwise
+    garment = (np.arange(n, dtype=np.int32)[:, None] + np.where(from_upper, 0, n).astype(np.int32)[None, :]).reshape(-1)
+    warp = lambda src, index: warp_perspective(src, mats, (ph, pw), 'replicate', index, valid).reshape(n, 10, ph, pw, 3)
+    patches, mask_patches = warp(garment_img, garment), warp(garment_mask, garment)
+    stick_patches = warp(people_stick, owner.astype(np.int32).reshape(-1))
+
+    upper, lower = list(range(UPPER_PARTS)), list(range(UPPER_PARTS, 10))
+    den_u, _ = composite(patches[:, upper], mask_patches[:, upper], back, valid_p, upper, height, width, ERODE_RADIUS)
+    radius = np.where(lower_idx != person_idx, ERODE_RADIUS, 0)
+    den_l, _ = composite(patches[:, lower], mask_patches[:, lower], back, valid_p, lower, height, width, radius)
+    m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
+    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_p
+
+
 def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower_img, lower_stick, lower_mask, lower_joints, box_factor=2):
     """The test set's ``normalize`` (dataset.py:1430-1500) for a batch on the GPU.  ``upper_*``: the clothes donor's upper garment,
     stick figure and 3-channel mask; ``lower_*``: the person's lower garment, stick figure and mask; uint8 [N, H, W, 3] CUDA
-    tensors.  ``*_joints`` [N, 18, 3] float64 (host), already shifted by the padding (x_pad = 0 below).
-    Parts 0..5 are cut from the donor's tensors with the donor's matrices and parts 6..9 from the person's with the person's:
-    three forward-warp launches (image, stick figure, mask), each over the two people stacked.  All ten parts are warped back
-    with the PERSON's M_inv: parts 0..5 into denorm_upper through the eroded composite, parts 6..9 into denorm_lower through the
-    plain one.  Returns (patches, stick_patches, mask_patches [N,10,h,w,3], denorm_upper, denorm_lower [N,H,W,3],
-    M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid [N,10] bool)."""
-    upper_img, upper_stick, upper_mask = _u8(upper_img), _u8(upper_stick), _u8(upper_mask)
-    lower_img, lower_stick, lower_mask = _u8(lower_img), _u8(lower_stick), _u8(lower_mask)
-    n, height, width, _ = upper_img.shape
-    ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    fwd_u, _, valid_u = part_matrices(upper_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
-    fwd_l, back_l, valid_l = part_matrices(lower_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
-    donor = np.arange(10) < UPPER_PARTS
-    mats = np.where(donor[None, :, None, None], fwd_u, fwd_l).reshape(-1, 3, 3)
-    valid = np.where(donor[None, :], valid_u, valid_l).reshape(-1)
-    # item (i, k) reads person i of the donors (0..N-1) for k < 6 and of the persons (N..2N-1) otherwise
-    src_index = (np.arange(n, dtype=np.int32)[:, None] + np.where(donor, 0, n).astype(np.int32)[None, :]).reshape(-1)
-    warp = lambda a, b: warp_perspective(torch.cat([a, b]), mats, (ph, pw), 'replicate', src_index, valid).reshape(n, 10, ph, pw, 3)
-    patches, stick_patches, mask_patches = warp(upper_img, lower_img), warp(upper_stick, lower_stick), warp(upper_mask, lower_mask)
-
-    upper, lower = list(range(UPPER_PARTS)), list(range(UPPER_PARTS, 10))
-    den_u, _ = composite(patches[:, upper], mask_patches[:, upper], back_l, valid_l, upper, height, width, ERODE_RADIUS)
-    den_l, _ = composite(patches[:, lower], mask_patches[:, lower], back_l, valid_l, lower, height, width)
-    m_invs = torch.from_numpy(np.where(valid_l[..., None, None], back_l, 0.0).astype(np.float32))
-    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l
+    tensors.  ``*_joints`` [N, 18, 3] float64 (host), already shifted by the padding.
+    Parts 0..5 are cut from the donor's tensors with the donor's matrices and parts 6..9 from the person's with the person's;
+    all ten parts are warped back with the PERSON's M_inv: parts 0..5 into denorm_upper through the eroded composite, parts 6..9
+    into denorm_lower through the plain one.  This is the outfit form above with the people stacked donors first, then persons,
+    and every person in their own lower garment.  Returns (patches, stick_patches, mask_patches [N,10,h,w,3], denorm_upper,
+    denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid [N,10] bool)."""
+    n = upper_img.shape[0]
+    donor, person = np.arange(n), np.arange(n) + n
+    people = np.concatenate([np.asarray(upper_joints, np.float64), np.asarray(lower_joints, np.float64)])
+    return normalize_pair_outfit_batch(torch.cat([upper_img, lower_img]), torch.cat([upper_stick, lower_stick]),
+                                       torch.cat([upper_mask, lower_mask]), people, person, donor, person, box_factor)[:8]
 
 
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)

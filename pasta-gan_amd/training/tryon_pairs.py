@@ -11,14 +11,21 @@ the host in four loader processes, as a few launches per batch:
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
-formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads)."""
+formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads).
+
+``TryOnPairOutfitBatchBuilder`` prepares OUTFITS for the same model, this project's own: a person with the upper garment of one
+donor and the lower garment of another (``training.dataset.UvitonOutfits_256_test``, ``collate_outfits``; include/pasta_hip.h
+lists the rules).  The launches are the ones above with pasta_tryon_pair_outfit_masks_u8 (a source per garment) and
+``patch_pipeline.normalize_pair_outfit_batch``, whose lower composite erodes a sample's masks 5 x 5 exactly where the lower
+garment is somebody else's (pasta_patch_composite_radii_u8); the batch's distinct people are uploaded once, drawn once and their
+matrices solved once.  A test pair is the outfit (P, D, -); lower-body and full-body try-on are (P, -, D) and (P, D, D)."""
 
 import numpy as np
 import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
-from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_pair
+from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_pair, upload_person
 
 PALM_BOXES = (25, 15)       # get_hand_mask of the test set: upper arm 25 x 25, forearm 15 x 15 (dataset.py:1240-1253)
 
@@ -75,6 +82,68 @@ class TryOnPairBatchBuilder:
                           upper_img=upper_img, upper_mask=upper_mask, patches=patches, stick_patches=stick_patches, mask_patches=mask_patches,
                           denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, upper_valid=valid_u, lower_valid=valid_l)
         return TryOnPairBatch(t, raw['person_name'], raw['clothes_name'], stages)
+
+
+class TryOnPairOutfitBatch(TryOnPairBatch):
+    """``tensors``: the seven of TryOnPairBatch; ``person_name`` / ``upper_name`` / ``lower_name``: the data set's relative paths
+    (``clothes_name`` is ``upper_name``); ``stages`` as TryOnPairBatch's (``clothes_stick`` the upper garment's owner's), with
+    ``lower_stick`` and ``upper_valid`` / ``lower_valid`` / ``person_valid`` [N, 10]."""
+
+    def __init__(self, tensors, person_name, upper_name, lower_name, stages=None):
+        super().__init__(tensors, person_name, upper_name, stages)
+        self.upper_name = self.clothes_name
+        self.lower_name = list(lower_name)
+
+
+class TryOnPairOutfitBatchBuilder:
+    """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` at 256 x 192 -> TryOnPairOutfitBatch on ``device``.
+    The batch's M distinct people are uploaded once, their stick figures drawn once and their matrices solved once; the
+    per-sample views (the person, the owner of the upper garment, the owner of the lower one) are gathered on the device.  The
+    outfit (P, D, -) gives TryOnPairBatchBuilder's tensors and stages for the pair (P, D) bit for bit."""
+
+    def __init__(self, device, box_factor=2):
+        self.device = torch.device(device)
+        self.box_factor = box_factor
+
+    def build(self, raw, keep_stages=False):
+        dev = self.device
+        people_image, people_parsing, people_kp = upload_person(raw, dev, 'TryOnPairOutfitBatchBuilder', 'people_')
+        m, H, W, _ = people_image.shape
+        lp = (H - W) // 2
+        host_idx = [np.asarray(raw[k], np.int64) for k in ('person_idx', 'upper_idx', 'lower_idx')]
+        n = len(host_idx[0])
+        assert all(ix.shape == (n,) and ix.min() >= 0 and ix.max() < m for ix in host_idx), 'outfit indices outside the people stack'
+        person_ix, upper_ix, lower_ix = (torch.from_numpy(ix).to(dev, non_blocking=True) for ix in host_idx)
+        (image, parsing), (u_image, u_parsing), (l_image, l_parsing) = (
+            (people_image.index_select(0, ix), people_parsing.index_select(0, ix)) for ix in (person_ix, upper_ix, lower_ix))
+        limbs, joints, quads, present = device_tables(people_kp, people_kp[host_idx[0]], lp, dev)      # M stick figures, N palms
+        u8 = allocator(torch.uint8, dev)
+        sticks, palm, retain_img = u8(m, H, H, 3), u8(n, H, H), u8(n, H, H, 3)
+        garment_img, garment_mask = u8(2 * n, H, H, 3), u8(2 * n, H, H, 3)   # the upper garments, then the lower garments
+        lib, P = _native.lib(), _native.ptr
+        with torch.cuda.device(dev):
+            s = _native.stream()
+            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(sticks), m, H, W, s))
+            _native.check(lib.pasta_palm_mask_box_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
+            _native.check(lib.pasta_tryon_pair_outfit_masks_u8(P(image), P(parsing), P(palm), P(u_image), P(u_parsing), P(l_image), P(l_parsing),
+                                                               P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
+                                                               P(garment_mask[n:]), n, H, W, s))
+        patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l, valid_p = patch_pipeline.normalize_pair_outfit_batch(
+            garment_img, sticks, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
+        stick = sticks.index_select(0, person_ix)
+        parts, ph, pw = patches.shape[1], patches.shape[2], patches.shape[3]
+        t, outs = output_tensors(TryOnPairOutfitBatch.KEYS, n, H, (6 * parts, ph, pw), dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.pasta_tryon_pair_assemble(P(retain_img), P(stick), P(patches), P(stick_patches), P(den_u), P(den_l), outs, n, H,
+                                                        parts, ph, pw, _native.stream()))
+        stages = None
+        if keep_stages:
+            stages = dict(image=image, parsing=parsing, stick=stick, clothes_stick=sticks.index_select(0, upper_ix),
+                          lower_stick=sticks.index_select(0, lower_ix), palm=palm, retain_img=retain_img, lower_img=garment_img[n:],
+                          lower_mask=garment_mask[n:], upper_img=garment_img[:n], upper_mask=garment_mask[:n], patches=patches,
+                          stick_patches=stick_patches, mask_patches=mask_patches, denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs,
+                          upper_valid=valid_u, lower_valid=valid_l, person_valid=valid_p)
+        return TryOnPairOutfitBatch(t, raw['person_name'], raw['upper_name'], raw['lower_name'], stages)
 
 
 def images_to_u8(images, c0, width):

@@ -2,6 +2,8 @@
 snapshot that is not a local file, loading ``G_ema``, the loader over a pair data set, the generator's call sequence and the
 --scores report.
 
+test.py's --outfits and --change-region are served by ``generate_256`` below; a run with neither is test.py's own loop.
+
 test_512.py's --outfits and --scores are declared and served HERE, not in that file, which stays the reference's command line
 as it was (``shared_options`` says how): ``generate_512`` is the one loop for those runs, outfits or pairs."""
 
@@ -90,10 +92,20 @@ scores_option = click.option(
          'FILE as JSON. With this option z of pair i is np.random.RandomState(i).randn(z_dim), so that the figures describe the images '
          'whatever the batch size [default: no scores]')
 
-outfits_option = click.option(
-    '--outfits', 'outfits_file', type=str, metavar='FILE',
-    help='Dress the people of FILE instead of the pair lists: lines "person upper lower", each <sub-dataset>/<file>.jpg, "-" for a '
-         'garment the person keeps; written as upper donor | lower donor | person | generated. Not together with --change-region')
+def _outfits_option(written):
+    return click.option(
+        '--outfits', 'outfits_file', type=str, metavar='FILE',
+        help='Dress the people of FILE instead of the pair lists: lines "person upper lower", each <sub-dataset>/<file>.jpg, "-" for a '
+             'garment the person keeps; written %s. Not together with --change-region' % written)
+
+
+outfits_option = _outfits_option('as upper donor | lower donor | person | generated')
+pair_outfits_option = _outfits_option('to <person\'s sub-dataset>/<person>__<upper>__<lower>.png, a kept garment under the person\'s name')
+region_option = click.option(
+    '--change-region', type=click.Choice(['upperbody', 'lowerbody', 'fullbody']),
+    help='Which garments the person takes from the donor of the pair lists: the upper garment (what a run without this option does), '
+         'the lower garment, or both [default: upperbody]')
+BOTH_MODES = '--outfits and --change-region exclude each other: every line of the outfit list names whose garments are worn'
 
 
 def _explicit_region(change_region):
@@ -151,15 +163,17 @@ def generate(G, t, gen_z, truncation_psi, noise_mode):
                            t['denorm_lower_mask'], noise_mode=noise_mode)[1]
 
 
-def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None):
+def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None):
     """--scores: the figures of ``metrics.tryon_fidelity.finish`` (prefix ``tryon``) and what the run was, as one JSON line,
-    printed and written to ``scores_file``."""
+    printed and written to ``scores_file``.  ``mode``: what was dressed, when it was not the plain pair lists."""
     import json
     from metrics import tryon_fidelity
     report = dict(results=tryon_fidelity.finish(partials, 'tryon', pixels=pixels), pairs=pairs, network=network_pkl, dataroot=dataroot,
                   noise_mode=noise_mode)
     if storage is not None:
         report['storage'] = storage
+    if mode is not None:
+        report['mode'] = mode
     line = json.dumps(report)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
@@ -177,7 +191,7 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     what is written, z of item i from ``pair_z(i)``, ``pixels = 512 * 320``.  Without --outfits the pairs of the change region
     are written as test_512.py writes them, ``clothes | person | generated``."""
     if outfits_file is not None and change_region is not None:
-        raise click.UsageError('--outfits and --change-region exclude each other: every line of the outfit list names whose garments are worn')
+        raise click.UsageError(BOTH_MODES)
     _local_snapshot(network_pkl)
 
     import numpy as np
@@ -221,3 +235,65 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     print('finish: %d images under %s' % (count, outdir))
     if scores_file is not None:
         write_scores(scores_file, partials, 512 * 320, count, network_pkl, dataroot, noise_mode, storage)
+
+
+def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
+                 scores_file=None, storage=None):
+    """test.py with --outfits or --change-region: the 256 x 192 model on outfits, prepared by
+    training.tryon_pairs.TryOnPairOutfitBatchBuilder.  --outfits FILE: every line ``person upper lower`` of FILE
+    (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
+    stem>.png``, a kept garment under the person's stem.  --change-region: the pairs of the pair lists as the outfits (P, D, -),
+    (P, -, D) or (P, D, D), written under test.py's name ``<person stem>__<clothes stem>.png``; 'upperbody' writes the bytes of a
+    run without the option.  The two exclude each other, and that is refused before anything is read.  Only the generated image
+    is written, as test.py writes it.  --scores FILE: the region scores over what is written, z of item i from ``pair_z(i)``;
+    the report's ``mode`` is ``outfits`` or ``change-region <region>``."""
+    if outfits_file is not None and change_region is not None:
+        raise click.UsageError(BOTH_MODES)
+    _local_snapshot(network_pkl)
+
+    import numpy as np
+    import PIL.Image
+    import torch
+
+    from metrics import tryon_fidelity
+    from training import dataset as custom_dataset
+    from training.tryon_pairs import TryOnPairOutfitBatchBuilder, images_to_u8
+
+    device = torch.device('cuda')
+    G = load_generator(network_pkl, device, storage)
+    os.makedirs(outdir, exist_ok=True)
+    if outfits_file is not None:
+        dataset = custom_dataset.UvitonOutfits_256_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
+        loader, mode = pair_loader(dataset, batchsize, workers, custom_dataset.collate_outfits), 'outfits'
+    else:
+        dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
+        loader = pair_loader(dataset, batchsize, workers, functools.partial(custom_dataset.collate_region_outfits, change_region))
+        mode = 'change-region ' + change_region
+    builder = TryOnPairOutfitBatchBuilder(device)
+    partials = tryon_fidelity.new_partials(len(dataset), device) if scores_file is not None else None
+    pixels = tryon_fidelity.PIXELS
+    stem = lambda name: os.path.basename(name)[:-4]
+    written = 0
+    for raw in loader:
+        batch = builder.build(raw, keep_stages=scores_file is not None)
+        t, n = batch.tensors, batch.batch
+        height, width = raw['people_image'].shape[1], raw['people_image'].shape[2]
+        gen_z = torch.empty([n, 0], device=device)
+        if scores_file is not None:
+            index = raw['raw_idx'].tolist()                         # the items' positions in the pair lists, or in the outfit list
+            gen_z = tryon_fidelity.pair_z(index, G.z_dim, device)
+        gen_imgs = generate(G, t, gen_z, truncation_psi, noise_mode)
+        images = images_to_u8(gen_imgs, (height - width) // 2, width).cpu().numpy()
+        if scores_file is not None:
+            tryon_fidelity.score_batch(gen_imgs, batch, index, partials)
+            pixels = height * width
+        worn = zip(batch.upper_name, batch.lower_name) if outfits_file is not None else zip(raw['clothes_name'])
+        for img, person, garments in zip(images, batch.person_name, worn):
+            save_dir = os.path.join(outdir, person.split('/')[0])
+            os.makedirs(save_dir, exist_ok=True)
+            name = '__'.join([stem(person)] + [stem(g) for g in garments]) + '.png'
+            PIL.Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(save_dir, name))
+            written += 1
+    print('finish: %d images under %s' % (written, outdir))
+    if scores_file is not None:
+        write_scores(scores_file, partials, pixels, written, network_pkl, dataroot, noise_mode, storage, mode)

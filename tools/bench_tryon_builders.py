@@ -1,13 +1,17 @@
-"""Timings of the 512 x 320 test builders on one GPU, the figures of DESIGN.md section 9 (outfits):
+"""Timings of the test builders on one GPU, the figures of DESIGN.md section 9 (outfits), at 512 x 320:
 
     python tools/bench_tryon_builders.py [--batch 16] [--warmup 5] [--repeats 30]
 
   1. TryOnOutfitBatchBuilder.build for --batch fully mixed outfits (three distinct people each: M = 3 * batch);
   2. the same for --batch (p, c, -) outfits (M = 2 * batch);
-  3. TryOnRegionBatchBuilder('fullbody').build for --batch pairs (M = 2 * batch as well).
+  3. TryOnRegionBatchBuilder('fullbody').build for --batch pairs (M = 2 * batch as well);
+and at 256 x 192, with the people of tests/tryon_pairs_tree.py:
+  4. TryOnPairOutfitBatchBuilder.build for --batch fully mixed outfits (M = 3 * batch);
+  5. the same for --batch (p, c, -) outfits (M = 2 * batch);
+  6. TryOnPairBatchBuilder.build for --batch pairs (M = 2 * batch), which 5 equals bit for bit.
 Each line is the median wall time around build() and torch.cuda.synchronize() after the warm-ups, and the median host time
-spent inside patch_pipeline.part_matrices (the 8 x 8 solves) with its share.  The people are those of tests/tryon_512_tree.py
-that have key points, repeated under distinct names: only the count of distinct people matters to the timing."""
+spent inside patch_pipeline.part_matrices (the 8 x 8 solves) with its share.  The people are those of the tiny trees that have
+key points, repeated under distinct names: only the count of distinct people matters to the timing."""
 import argparse
 import json
 import os
@@ -44,14 +48,20 @@ def main():
 
     import torch
     from training import patch_pipeline
-    from training.dataset import UvitonDatasetFull_512_test, collate_pairs
+    from training.dataset import UvitonDatasetFull_512_test, UvitonDatasetV19_test, collate_pairs
+    from training.tryon_pairs import TryOnPairBatchBuilder, TryOnPairOutfitBatchBuilder
     from training.tryon_regions import TryOnOutfitBatchBuilder, TryOnRegionBatchBuilder
     from tryon_512_tree import make_512_tree
+    from tryon_pairs_tree import make_pair_tree
 
     with tempfile.TemporaryDirectory() as root:
         pairs = UvitonDatasetFull_512_test(path=make_512_tree(root), change_region='fullbody')
         pairs = [pairs[i] for i in (0, 1, 2)]                    # both people of these pairs have key points
-    people = [(p[k + 'image'], p[k + 'parsing'], p[k + 'keypoints']) for p in pairs for k in ('', 'clothes_')]
+    with tempfile.TemporaryDirectory() as root:
+        pairs_256 = UvitonDatasetV19_test(path=make_pair_tree(root))
+        pairs_256 = [pairs_256[i] for i in (0, 1, 4)]            # both people of these pairs have key points
+    stack = lambda chosen: [(p[k + 'image'], p[k + 'parsing'], p[k + 'keypoints']) for p in chosen for k in ('', 'clothes_')]
+    people, people_256 = stack(pairs), stack(pairs_256)
     n = args.batch
     mixed = np.arange(3 * n, dtype=np.int64).reshape(n, 3)
     own_lower = np.stack([np.arange(0, 2 * n, 2), np.arange(1, 2 * n, 2), np.arange(0, 2 * n, 2)], axis=1).astype(np.int64)
@@ -87,6 +97,10 @@ def main():
     measure('outfits, fully mixed (M = %d)' % (3 * n), outfits.build, outfit_batch(people, mixed))
     measure('outfits (p, c, -) (M = %d)' % (2 * n), outfits.build, outfit_batch(people, own_lower))
     measure('region builder, fullbody (M = %d)' % (2 * n), regions.build, collate_pairs([pairs[i % len(pairs)] for i in range(n)]))
+    outfits, plain = TryOnPairOutfitBatchBuilder('cuda'), TryOnPairBatchBuilder('cuda')
+    measure('256: outfits, fully mixed (M = %d)' % (3 * n), outfits.build, outfit_batch(people_256, mixed))
+    measure('256: outfits (p, c, -) (M = %d)' % (2 * n), outfits.build, outfit_batch(people_256, own_lower))
+    measure('256: pair builder (M = %d)' % (2 * n), plain.build, collate_pairs([pairs_256[i % len(pairs_256)] for i in range(n)]))
 
 
 if __name__ == '__main__':
