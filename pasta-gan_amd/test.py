@@ -4,8 +4,9 @@ For every line ``person clothes`` of the pair lists of ``UPT_subset1_256_192`` a
 the person is dressed in the donor's upper garment and the image is written to
 ``<outdir>/<sub-dataset>/<person stem>__<clothes stem>.png`` (RGB, 256 x 192: columns 32..223 of the generator's square).
 
-Loader workers only decode files (training.dataset.collate_pairs).  Everything on the GPU runs in this process: the batch
-preparation (training.tryon_pairs.TryOnPairBatchBuilder), the call sequence of the reference's test.py:119-128
+Loader workers only decode files and stack every distinct person of a batch once (training.dataset.collate_region_outfits: a
+pair is the outfit (person, donor, -)).  Everything on the GPU runs in this process, in ``tryon_cli.generate_256``: the batch
+preparation (training.tryon_pairs.TryOnPairOutfitBatchBuilder), the call sequence of the reference's test.py:119-128
 (style_encoding, const_encoding, mapping, synthesis) and the conversion to uint8 (pasta_images_to_u8).
 
 Differences from the reference, on purpose:
@@ -24,11 +25,9 @@ Differences from the reference, on purpose:
   --outfits FILE dresses every line ``person upper lower`` of FILE instead of the pair lists: the upper garment of one donor,
   the lower garment of another, ``-`` for a garment the person keeps (training.dataset.UvitonOutfits_256_test), written to
   ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower stem>.png``.  Both options are this project's own
-  (include/pasta_hip.h lists the rules), exclude each other and are served by ``tryon_cli.generate_256``; a run with neither is
-  the loop below.
+  (include/pasta_hip.h lists the rules) and exclude each other.
 """
 
-import os
 from typing import List, Optional
 
 import click
@@ -51,51 +50,8 @@ def generate_images(network_pkl: str, seeds: Optional[List[int]], truncation_psi
     python test.py --network snapshot.pkl --outdir out --dataroot PASTA_UPT_256 --batchsize 16
     """
     del seeds, class_idx, projected_w
-    if outfits_file is not None or change_region is not None:
-        return tryon_cli.generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file,
-                                      change_region, scores_file, storage)
-    tryon_cli._local_snapshot(network_pkl)
-
-    import numpy as np
-    import PIL.Image
-    import torch
-
-    from training import dataset as custom_dataset
-    from training.tryon_pairs import TryOnPairBatchBuilder, images_to_u8
-
-    device = torch.device('cuda')
-    G = tryon_cli.load_generator(network_pkl, device, storage)
-    os.makedirs(outdir, exist_ok=True)
-    dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
-    loader = tryon_cli.pair_loader(dataset, batchsize, workers)
-    builder = TryOnPairBatchBuilder(device)
-    if scores_file is not None:
-        from metrics import tryon_fidelity
-        partials = tryon_fidelity.new_partials(len(dataset), device)
-        pixels = tryon_fidelity.PIXELS                              # content pixels of a pair; every batch brings its own
-    written = 0
-    for raw in loader:
-        batch = builder.build(raw, keep_stages=scores_file is not None)
-        t, n = batch.tensors, batch.batch
-        height, width = raw['image'].shape[1], raw['image'].shape[2]
-        gen_z = torch.empty([n, 0], device=device)
-        if scores_file is not None:
-            pair_index = raw['raw_idx'].tolist()                    # the pairs' positions in the pair lists
-            gen_z = tryon_fidelity.pair_z(pair_index, G.z_dim, device)
-        gen_imgs = tryon_cli.generate(G, t, gen_z, truncation_psi, noise_mode)
-        images = images_to_u8(gen_imgs, (height - width) // 2, width).cpu().numpy()
-        if scores_file is not None:
-            tryon_fidelity.score_batch(gen_imgs, batch, pair_index, partials)
-            pixels = height * width
-        for img, person, clothes in zip(images, batch.person_name, batch.clothes_name):
-            save_dir = os.path.join(outdir, person.split('/')[0])
-            os.makedirs(save_dir, exist_ok=True)
-            name = os.path.basename(person)[:-4] + '__' + os.path.basename(clothes)[:-4] + '.png'
-            PIL.Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(save_dir, name))
-            written += 1
-    print('finish: %d images under %s' % (written, outdir))
-    if scores_file is not None:
-        tryon_cli.write_scores(scores_file, partials, pixels, written, network_pkl, dataroot, noise_mode, storage)
+    tryon_cli.generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file, change_region,
+                           scores_file, storage)
 
 
 if __name__ == '__main__':

@@ -445,4 +445,24 @@ def collate_region_outfits(change_region, samples):
     out['clothes_name'] = [s['clothes_name'] for s in samples]
     return out
 
+
+def pairs_batch_as_outfits(raw, change_region):
+    """A COLLATED batch of pairs (``collate_pairs``) -> the batch ``collate_outfits`` makes of the same pairs taken as the outfits
+    of ``change_region``, without looking for people named twice: the stack is the N persons followed by the N clothes donors
+    (M = 2N, ``people_name`` may repeat), ``person_idx`` 0..N-1, ``upper_idx`` / ``lower_idx`` the donors' N..2N-1 where the region
+    takes that garment from the donor.  ``clothes_name`` stays.  The tensors are concatenated where they are: a batch whose
+    images a builder has uploaded is stacked on the device.  The pair builders are the outfit builders behind this function; the
+    command lines go through ``collate_region_outfits`` in the loader's workers instead, which does deduplicate."""
+    if change_region not in CHANGE_REGIONS:
+        raise ValueError('change region %s is invalid.' % change_region)
+    out = {'people_' + k: torch.cat([torch.as_tensor(raw[k]), torch.as_tensor(raw['clothes_' + k])]) for k in ('image', 'parsing', 'keypoints')}
+    person = torch.arange(len(raw['person_name']), dtype=torch.int64)
+    index = dict(person=person, clothes=person + len(person))
+    names = dict(person=list(raw['person_name']), clothes=list(raw['clothes_name']))
+    out.update(people_name=names['person'] + names['clothes'], person_idx=person, person_name=names['person'], clothes_name=names['clothes'],
+               raw_idx=raw['raw_idx'])
+    for role, donor in (('upper', change_region != 'lowerbody'), ('lower', change_region != 'upperbody')):
+        out[role + '_idx'], out[role + '_name'] = index['clothes' if donor else 'person'], names['clothes' if donor else 'person']
+    return out
+
 #----------------------------------------------------------------------------

@@ -257,30 +257,23 @@ def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_
     return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_p
 
 
-def normalize_pair_batch(upper_img, upper_stick, upper_mask, upper_joints, lower_img, lower_stick, lower_mask, lower_joints, box_factor=2):
-    """The test set's ``normalize`` (dataset.py:1430-1500) for a batch on the GPU.  ``upper_*``: the clothes donor's upper garment,
-    stick figure and 3-channel mask; ``lower_*``: the person's lower garment, stick figure and mask; uint8 [N, H, W, 3] CUDA
-    tensors.  ``*_joints`` [N, 18, 3] float64 (host), already shifted by the padding.
-    Parts 0..5 are cut from the donor's tensors with the donor's matrices and parts 6..9 from the person's with the person's;
-    all ten parts are warped back with the PERSON's M_inv: parts 0..5 into denorm_upper through the eroded composite, parts 6..9
-    into denorm_lower through the plain one.  This is the outfit form above with the people stacked donors first, then persons,
-    and every person in their own lower garment.  Returns (patches, stick_patches, mask_patches [N,10,h,w,3], denorm_upper,
-    denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid [N,10] bool)."""
-    n = upper_img.shape[0]
-    donor, person = np.arange(n), np.arange(n) + n
-    people = np.concatenate([np.asarray(upper_joints, np.float64), np.asarray(lower_joints, np.float64)])
-    return normalize_pair_outfit_batch(torch.cat([upper_img, lower_img]), torch.cat([upper_stick, lower_stick]),
-                                       torch.cat([upper_mask, lower_mask]), people, person, donor, person, box_factor)[:8]
-
-
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
 
 
-def _region_warps(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor, want_part_masks):
-    """The body of normalize_region_batch and normalize_outfit_batch: ONE part_matrices call over the M distinct people of
-    ``people_joints`` [M, 18, 3]; sample i wears the upper garment of people ``upper_idx[i]`` and the lower garment of
-    ``lower_idx[i]`` and is ``person_idx[i]`` itself.  Returns (the seven tensors both functions return first, valid [M, 10]
-    bool, part masks or None)."""
+def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2, want_part_masks=False):
+    """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch of
+    OUTFITS on the GPU.  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image,
+    3-channel mask) followed by the N lower garments.  ``people_joints`` [M, 18, 3] float64 (host): the batch's DISTINCT people,
+    already shifted by the padding (x_pad = 0); get_crop here has no shin fall-back (:1893-1900).  ``person_idx`` / ``upper_idx``
+    / ``lower_idx`` [N]: who sample i is and whose upper and lower garment it wears (a pair with a change region: full body
+    (P, D, D), upper body (P, D, P), lower body (P, P, D); a training sample: all three the person).
+    ONE part_matrices call solves the M people, whatever the number of samples that use them.  All ten parts of the upper
+    garment and parts 0, 6, 7, 8, 9 of the lower one are warped forward with their owner's matrices (one launch for the images,
+    one for the masks) and back with the PERSON's M_inv through the eroded composite, every part 5 x 5.  A part whose forward
+    matrix is missing is zeros; a part whose M_inv is missing is skipped.  Returns (patches [N,10,h,w,3], patches_lower
+    [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the
+    person's), upper_valid, lower_valid, person_valid [N,10] bool).  ``want_part_masks``: an eleventh value, the eroded 0 / 1
+    masks [N,10,H,W] of the upper composite's parts."""
     garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
@@ -302,40 +295,5 @@ def _region_warps(garment_img, garment_mask, people_joints, person_idx, upper_id
     den_u, part_masks = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS, want_part_masks)
     den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
     m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
-    return (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs), valid_all, part_masks
-
-
-def normalize_region_batch(garment_img, garment_mask, donor_joints, person_joints, upper_from_donor, lower_from_donor, box_factor=2,
-                           want_part_masks=False):
-    """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch
-    on the GPU.  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image, 3-channel
-    mask) followed by the N lower garments.  ``donor_joints`` / ``person_joints`` [N, 18, 3] float64 (host), already shifted by
-    the padding (x_pad = 0); get_crop here has no shin fall-back (:1893-1900).  ``upper_from_donor`` / ``lower_from_donor``:
-    whose garment each is (full body: both the donor's; upper body: True, False; lower body: False, True).
-    All ten parts of the upper garment and parts 0, 6, 7, 8, 9 of the lower one are warped forward with the matrices of the
-    person the garment was taken from (one launch for the images, one for the masks) and back with the PERSON's M_inv through
-    the eroded composite, every part 5 x 5.  A part whose forward matrix is missing is zeros; a part whose M_inv is missing
-    is skipped.  Returns (patches [N,10,h,w,3], patches_lower [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper,
-    denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), donor_valid, person_valid [N,10] bool).
-    ``donor_joints is person_joints`` (the training samples: everyone wears their own garments) solves N sets of matrices,
-    not 2N.  ``want_part_masks``: a tenth value, the eroded 0 / 1 masks [N,10,H,W] of the upper composite's parts.
-    This is the outfit form below with the people stacked persons first, then donors."""
-    n = len(person_joints)
-    same = donor_joints is person_joints
-    person = np.arange(n)
-    donor = person if same else person + n
-    people = person_joints if same else np.concatenate([np.asarray(person_joints, np.float64), np.asarray(donor_joints, np.float64)])
-    out, valid, part_masks = _region_warps(garment_img, garment_mask, people, person, donor if upper_from_donor else person,
-                                           donor if lower_from_donor else person, box_factor, want_part_masks)
-    out += (valid[donor], valid[person])
+    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_p)
     return out + (part_masks,) if want_part_masks else out
-
-
-def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2):
-    """normalize_region_batch for outfits: ``people_joints`` [M, 18, 3] float64 (host), the batch's DISTINCT people, already
-    shifted by the padding; ``person_idx`` / ``upper_idx`` / ``lower_idx`` [N]: who sample i is and whose upper and lower
-    garment ``garment_img`` / ``garment_mask`` hold for it.  The matrices of each of the M people are solved once, whatever
-    the number of samples that use them; a garment goes forward with its owner's matrices and back with the person's M_inv.
-    Returns normalize_region_batch's first seven values, then upper_valid, lower_valid, person_valid [N,10] bool."""
-    out, valid, _ = _region_warps(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor, False)
-    return out + (valid[np.asarray(upper_idx)], valid[np.asarray(lower_idx)], valid[np.asarray(person_idx)])

@@ -11,8 +11,9 @@ do per sample on the host, as a few launches per batch:
 The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
-``upload_person`` (upload and checks), ``upload_erase`` (the training sets' erase masks), ``device_tables`` (stick and palm
-tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their pointer array) and ``shift_keypoints``.
+``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
+masks), ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their
+pointer array) and ``shift_keypoints``.
 ``builder_for`` picks the training builder of a data set: this one, or training/tryon_regions.py's at 512 x 320."""
 
 import ctypes
@@ -103,11 +104,10 @@ def upload_erase(raw, device, n):
     return erase, erase_hw
 
 
-def upload_pair(raw, device, who):
-    """(image, parsing, key points) of the persons, then of the clothes donors, of a batch of ``training.dataset.collate_pairs``."""
-    person, donor = upload_person(raw, device, who), upload_person(raw, device, who, 'clothes_')
-    assert donor[0].shape == person[0].shape
-    return person + donor
+def upload_images(raw, device):
+    """``raw`` with its photographs and label maps (every ``*image`` / ``*parsing`` tensor) on ``device``; key points, names and
+    indices stay on the host.  The pair builders stack a batch of ``training.dataset.collate_pairs`` after this, on the device."""
+    return {k: torch.as_tensor(v).to(device, non_blocking=True) if k.endswith(('image', 'parsing')) else v for k, v in raw.items()}
 
 
 def device_tables(stick_keypoints, palm_keypoints, left_padding, device):

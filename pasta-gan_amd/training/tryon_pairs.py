@@ -2,30 +2,31 @@
 ``normalize`` / ``__getitem__`` (training/dataset.py:1085-1525) and test.py's conversions (test.py:104-117) do per sample on
 the host in four loader processes, as a few launches per batch:
 
-    pasta_pose_stickman_u8            both people's stick figures, one launch  (csrc/tryon_inputs.hip)
+    pasta_pose_stickman_u8            the stick figures of the batch's people, one launch  (csrc/tryon_inputs.hip)
     pasta_palm_mask_box_u8            the person's palm mask, boxes 25 and 15 (csrc/tryon_pairs.hip)
-    pasta_tryon_pair_masks_u8         retain image, the person's lower garment, the donor's upper garment
-    patch_pipeline.normalize_pair_batch   three forward warps + the eroded and the plain composite (csrc/patches.hip,
-                                          csrc/tryon_pairs.hip)
+    pasta_tryon_pair_outfit_masks_u8  retain image, the lower garment and the upper garment, a source per garment
+    patch_pipeline.normalize_pair_outfit_batch   three forward warps + the eroded composite and the one with a radius per
+                                                 sample (csrc/patches.hip, csrc/tryon_pairs.hip)
     pasta_tryon_pair_assemble         the seven fp32 tensors G takes
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads).
 
-``TryOnPairOutfitBatchBuilder`` prepares OUTFITS for the same model, this project's own: a person with the upper garment of one
-donor and the lower garment of another (``training.dataset.UvitonOutfits_256_test``, ``collate_outfits``; include/pasta_hip.h
-lists the rules).  The launches are the ones above with pasta_tryon_pair_outfit_masks_u8 (a source per garment) and
-``patch_pipeline.normalize_pair_outfit_batch``, whose lower composite erodes a sample's masks 5 x 5 exactly where the lower
-garment is somebody else's (pasta_patch_composite_radii_u8); the batch's distinct people are uploaded once, drawn once and their
-matrices solved once.  A test pair is the outfit (P, D, -); lower-body and full-body try-on are (P, -, D) and (P, D, D)."""
+The implementation is the OUTFIT form, this project's own: a person with the upper garment of one donor and the lower garment of
+another (``training.dataset.UvitonOutfits_256_test``, ``collate_outfits``; include/pasta_hip.h lists the rules).  The lower
+composite erodes a sample's masks 5 x 5 exactly where the lower garment is somebody else's (pasta_patch_composite_radii_u8); the
+batch's distinct people are uploaded once, drawn once and their matrices solved once.  ``TryOnPairOutfitBatchBuilder`` is that
+body; the reference's pair (P, D) is the outfit (P, D, -), and ``TryOnPairBatchBuilder`` is the same body behind
+``training.dataset.pairs_batch_as_outfits``.  Lower-body and full-body try-on are (P, -, D) and (P, D, D)."""
 
 import numpy as np
 import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
-from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_pair, upload_person
+from training.dataset import pairs_batch_as_outfits
+from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_images, upload_person
 
 PALM_BOXES = (25, 15)       # get_hand_mask of the test set: upper arm 25 x 25, forearm 15 x 15 (dataset.py:1240-1253)
 
@@ -45,45 +46,6 @@ class TryOnPairBatch:
         self.stages = stages
 
 
-class TryOnPairBatchBuilder:
-    """``build(raw_batch)``: a batch of ``training.dataset.collate_pairs`` -> TryOnPairBatch on ``device``."""
-
-    def __init__(self, device, box_factor=2):
-        self.device = torch.device(device)
-        self.box_factor = box_factor
-
-    def build(self, raw, keep_stages=False):
-        dev = self.device
-        image, parsing, kp, d_image, d_parsing, d_kp = upload_pair(raw, dev, 'TryOnPairBatchBuilder')
-        n, H, W, _ = image.shape
-        lp = (H - W) // 2
-        limbs, joints, quads, present = device_tables(np.concatenate([d_kp, kp]), kp, lp, dev)
-        u8 = allocator(torch.uint8, dev)
-        sticks, palm = u8(2 * n, H, H, 3), u8(n, H, H)                     # sticks: the donors, then the persons
-        retain_img, lower_img, lower_mask, upper_img, upper_mask = (u8(n, H, H, 3) for _ in range(5))
-        lib, P = _native.lib(), _native.ptr
-        with torch.cuda.device(dev):
-            s = _native.stream()
-            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(sticks), 2 * n, H, W, s))
-            _native.check(lib.pasta_palm_mask_box_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
-            _native.check(lib.pasta_tryon_pair_masks_u8(P(image), P(parsing), P(palm), P(d_image), P(d_parsing), P(retain_img), P(lower_img),
-                                                        P(lower_mask), P(upper_img), P(upper_mask), n, H, W, s))
-        d_stick, stick = sticks[:n], sticks[n:]
-        patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l = patch_pipeline.normalize_pair_batch(
-            upper_img, d_stick, upper_mask, shift_keypoints(d_kp, lp), lower_img, stick, lower_mask, shift_keypoints(kp, lp), self.box_factor)
-        parts, ph, pw = patches.shape[1], patches.shape[2], patches.shape[3]
-        t, outs = output_tensors(TryOnPairBatch.KEYS, n, H, (6 * parts, ph, pw), dev)
-        with torch.cuda.device(dev):
-            _native.check(lib.pasta_tryon_pair_assemble(P(retain_img), P(stick), P(patches), P(stick_patches), P(den_u), P(den_l), outs, n, H,
-                                                        parts, ph, pw, _native.stream()))
-        stages = None
-        if keep_stages:
-            stages = dict(image=image, parsing=parsing, stick=stick, clothes_stick=d_stick, palm=palm, retain_img=retain_img, lower_img=lower_img, lower_mask=lower_mask,
-                          upper_img=upper_img, upper_mask=upper_mask, patches=patches, stick_patches=stick_patches, mask_patches=mask_patches,
-                          denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, upper_valid=valid_u, lower_valid=valid_l)
-        return TryOnPairBatch(t, raw['person_name'], raw['clothes_name'], stages)
-
-
 class TryOnPairOutfitBatch(TryOnPairBatch):
     """``tensors``: the seven of TryOnPairBatch; ``person_name`` / ``upper_name`` / ``lower_name``: the data set's relative paths
     (``clothes_name`` is ``upper_name``); ``stages`` as TryOnPairBatch's (``clothes_stick`` the upper garment's owner's), with
@@ -98,8 +60,7 @@ class TryOnPairOutfitBatch(TryOnPairBatch):
 class TryOnPairOutfitBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` at 256 x 192 -> TryOnPairOutfitBatch on ``device``.
     The batch's M distinct people are uploaded once, their stick figures drawn once and their matrices solved once; the
-    per-sample views (the person, the owner of the upper garment, the owner of the lower one) are gathered on the device.  The
-    outfit (P, D, -) gives TryOnPairBatchBuilder's tensors and stages for the pair (P, D) bit for bit."""
+    per-sample views (the person, the owner of the upper garment, the owner of the lower one) are gathered on the device."""
 
     def __init__(self, device, box_factor=2):
         self.device = torch.device(device)
@@ -107,7 +68,7 @@ class TryOnPairOutfitBatchBuilder:
 
     def build(self, raw, keep_stages=False):
         dev = self.device
-        people_image, people_parsing, people_kp = upload_person(raw, dev, 'TryOnPairOutfitBatchBuilder', 'people_')
+        people_image, people_parsing, people_kp = upload_person(raw, dev, type(self).__name__, 'people_')
         m, H, W, _ = people_image.shape
         lp = (H - W) // 2
         host_idx = [np.asarray(raw[k], np.int64) for k in ('person_idx', 'upper_idx', 'lower_idx')]
@@ -144,6 +105,18 @@ class TryOnPairOutfitBatchBuilder:
                           stick_patches=stick_patches, mask_patches=mask_patches, denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs,
                           upper_valid=valid_u, lower_valid=valid_l, person_valid=valid_p)
         return TryOnPairOutfitBatch(t, raw['person_name'], raw['upper_name'], raw['lower_name'], stages)
+
+
+class TryOnPairBatchBuilder(TryOnPairOutfitBatchBuilder):
+    """``build(raw_batch)``: a batch of ``training.dataset.collate_pairs`` -> TryOnPairBatch on ``device``: the pairs as the
+    upper-body outfits (P, D, -), stacked on the device after the upload.  Its stages are the reference's eighteen: the person is
+    the owner of the lower garment, so ``lower_stick`` is ``stick`` and ``person_valid`` is ``lower_valid``."""
+
+    def build(self, raw, keep_stages=False):
+        batch = super().build(pairs_batch_as_outfits(upload_images(raw, self.device), 'upperbody'), keep_stages)
+        if keep_stages:
+            del batch.stages['lower_stick'], batch.stages['person_valid']
+        return TryOnPairBatch(batch.tensors, raw['person_name'], raw['clothes_name'], batch.stages)
 
 
 def images_to_u8(images, c0, width):

@@ -5,19 +5,20 @@ in four loader processes, as a few launches per batch:
 
     pasta_pose_stickman_thick_u8      the person's stick figure, thickness 5 and radius 5   (csrc/tryon_inputs.hip)
     pasta_palm_mask_square_u8         the person's palm mask on the 512 square, boxes 35 and 20 (csrc/tryon_pairs.hip)
-    pasta_tryon_region_masks_u8       retain image, upper and lower garment of the person the region names (csrc/tryon_pairs.hip)
-    patch_pipeline.normalize_region_batch   two forward warps + two eroded composites (csrc/patches.hip, csrc/tryon_pairs.hip)
+    pasta_tryon_outfit_masks_u8       retain image, upper and lower garment, a source per garment (csrc/tryon_pairs.hip)
+    patch_pipeline.normalize_outfit_batch   two forward warps + two eroded composites (csrc/patches.hip, csrc/tryon_pairs.hip)
     pasta_tryon_region_assemble       the nine fp32 tensors of test_512.py
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621).
 
-``TryOnOutfitBatchBuilder`` prepares OUTFITS, this project's own: a person with the upper garment of one donor and the lower
-garment of another (``training.dataset.UvitonOutfits_512_test``, ``collate_outfits``).  The launches are the ones above with
-pasta_tryon_outfit_masks_u8 (a source per garment) and pasta_tryon_outfit_assemble (``clothes_lower`` as a tenth tensor); the
-batch's distinct people are uploaded once and ``patch_pipeline.normalize_outfit_batch`` solves their matrices once.  A pair with
-a change region is the outfit (P, D, D), (P, D, P) or (P, P, D).
+The implementation is the OUTFIT form, this project's own: a person with the upper garment of one donor and the lower garment of
+another (``training.dataset.UvitonOutfits_512_test``, ``collate_outfits``).  The batch's distinct people are uploaded once and
+``patch_pipeline.normalize_outfit_batch`` solves their matrices once.  ``TryOnOutfitBatchBuilder`` is that body, with
+pasta_tryon_outfit_assemble (``clothes_lower`` as a tenth tensor).  A pair with a change region is the outfit (P, D, D), (P, D, P)
+or (P, P, D), and ``TryOnRegionBatchBuilder`` is the same body behind ``training.dataset.pairs_batch_as_outfits``, told whose
+photograph ``clothes`` is.
 
 ``FullBodyRegionBatchBuilder`` prepares TRAINING batches at 512 x 320 (``training.dataset.UvitonDatasetFull_512``).  The
 reference has no 512 training set, so the rule is this project's own: the generator is trained on exactly the inputs
@@ -26,7 +27,7 @@ training set's photograph as target, ``gt_parsing`` and erase mask (include/past
 
     pasta_pose_stickman_thick_u8, pasta_palm_mask_square_u8     as above
     pasta_tryon_train_region_masks_u8     retain mask, gt_parsing and the person's own two garments in one pass
-    patch_pipeline.normalize_region_batch the matrices solved once, the eroded part masks of the upper composite kept
+    patch_pipeline.normalize_outfit_batch everyone their own donor: N solves; the eroded part masks of the upper composite kept
     pasta_tryon_train_region_assemble     the erase mask and the nine fp32 tensors of FullBodyBatch.KEYS"""
 
 import numpy as np
@@ -34,14 +35,16 @@ import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
-from training.tryon_batch import (FullBodyBatch, allocator, device_tables, output_tensors, shift_keypoints, upload_erase, upload_pair,
+from training.dataset import pairs_batch_as_outfits
+from training.tryon_batch import (FullBodyBatch, allocator, device_tables, output_tensors, shift_keypoints, upload_erase, upload_images,
                                   upload_person)
 from training.tryon_pairs import TryOnPairBatch
 
 PALM_BOXES = (35, 20)       # get_hand_mask of the 512 set: upper arm 35 x 35, forearm 20 x 20 (dataset.py:1790, :1795)
 STICK_THICKNESS = 5         # cv2.line(..., 5) (dataset.py:1851)
 STICK_RADIUS = 5            # circle(..., radius=5) (dataset.py:1832, :1861)
-# change region -> (code of pasta_tryon_region_masks_u8, upper garment from the donor, lower garment from the donor) (:1679-1690)
+# change region -> (code of pasta_tryon_region_masks_u8, upper garment from the donor, lower garment from the donor) (:1679-1690);
+# the builders take the garments' owners from the outfit's indices, the entry is held to the same rule by its tests
 REGIONS = dict(fullbody=(0, True, True), upperbody=(1, True, False), lowerbody=(2, False, True))
 
 
@@ -54,7 +57,7 @@ class TryOnRegionBatch(TryOnPairBatch):
 
 
 def _person_launches(parsing, kp, n, H, W, dev):
-    """What both test builders do first: the person's thick stick figure and palm mask, launched, and the uint8 tensors the
+    """What the test builders' body does first: the person's thick stick figure and palm mask, launched, and the uint8 tensors the
     label-masks entry fills: (stick, palm, retain_img [n,H,H,3], garment_img, garment_mask [2n,H,H,3]: the upper garments, then
     the lower garments)."""
     limbs, joints, quads, present = device_tables(kp, kp, (H - W) // 2, dev)
@@ -70,51 +73,13 @@ def _person_launches(parsing, kp, n, H, W, dev):
 
 
 def _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized, **valid):
-    """The uint8 intermediates both test builders keep: the person's unpadded ``image`` and ``parsing`` (which
-    metrics.tryon_fidelity scores against), the label stages and ``normalized``, normalize_region_batch's first seven values."""
+    """The uint8 intermediates the test builders keep: the person's unpadded ``image`` and ``parsing`` (which
+    metrics.tryon_fidelity scores against), the label stages and ``normalized``, normalize_outfit_batch's first seven values."""
     n = image.shape[0]
     patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs = normalized
     return dict(image=image, parsing=parsing, stick=stick, palm=palm, retain_img=retain_img, upper_img=garment_img[:n],
                 upper_mask=garment_mask[:n], lower_img=garment_img[n:], lower_mask=garment_mask[n:], patches=patches, patches_lower=patches_l,
                 mask_patches=mask_patches, mask_patches_lower=mask_patches_l, denorm_upper=den_u, denorm_lower=den_l, M_invs=m_invs, **valid)
-
-
-class TryOnRegionBatchBuilder:
-    """``build(raw_batch)``: a batch of ``training.dataset.collate_pairs`` -> TryOnRegionBatch on ``device`` for
-    ``change_region`` = 'fullbody', 'upperbody' or 'lowerbody'."""
-
-    def __init__(self, device, change_region, box_factor=2):
-        if change_region not in REGIONS:
-            raise ValueError('change region %s is invalid.' % change_region)
-        self.device = torch.device(device)
-        self.change_region = change_region
-        self.box_factor = box_factor
-
-    def build(self, raw, keep_stages=False):
-        dev = self.device
-        image, parsing, kp, d_image, d_parsing, d_kp = upload_pair(raw, dev, 'TryOnRegionBatchBuilder')
-        n, H, W, _ = image.shape
-        lp = (H - W) // 2
-        code, upper_donor, lower_donor = REGIONS[self.change_region]
-        stick, palm, retain_img, garment_img, garment_mask = _person_launches(parsing, kp, n, H, W, dev)
-        lib, P = _native.lib(), _native.ptr
-        with torch.cuda.device(dev):
-            _native.check(lib.pasta_tryon_region_masks_u8(P(image), P(parsing), P(palm), P(d_image), P(d_parsing), P(retain_img),
-                                                          P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]), P(garment_mask[n:]),
-                                                          n, H, W, code, _native.stream()))
-        *normalized, valid_d, valid_p = patch_pipeline.normalize_region_batch(
-            garment_img, garment_mask, shift_keypoints(d_kp, lp), shift_keypoints(kp, lp), upper_donor, lower_donor, self.box_factor)
-        patches, patches_l, _, _, den_u, den_l, _ = normalized
-        pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
-        t, outs = output_tensors(TryOnRegionBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
-        with torch.cuda.device(dev):
-            _native.check(lib.pasta_tryon_region_assemble(P(image), P(d_image), P(retain_img), P(stick), P(patches), P(patches_l), P(den_u),
-                                                          P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
-        stages = None
-        if keep_stages:
-            stages = _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized, clothes_valid=valid_d,
-                             person_valid=valid_p)
-        return TryOnRegionBatch(t, raw['person_name'], raw['clothes_name'], stages)
 
 
 class TryOnOutfitBatch(TryOnRegionBatch):
@@ -132,17 +97,23 @@ class TryOnOutfitBatch(TryOnRegionBatch):
 class TryOnOutfitBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` -> TryOnOutfitBatch on ``device``.  The batch's M
     distinct people are uploaded once and their matrices solved once; the per-sample views (the person, the owner of the upper
-    garment, the owner of the lower one) are gathered on the device.  The launches are the region builder's, with
-    pasta_tryon_outfit_masks_u8 and pasta_tryon_outfit_assemble where that has the region entries: the outfits (P, D, D),
-    (P, D, P) and (P, P, D) give TryOnRegionBatchBuilder's full-body, upper-body and lower-body tensors bit for bit."""
+    garment, the owner of the lower one) are gathered on the device."""
 
     def __init__(self, device, box_factor=2):
         self.device = torch.device(device)
         self.box_factor = box_factor
 
     def build(self, raw, keep_stages=False):
+        t, stages = self._prepare(raw, ('upper', 'lower'), dict(upper='upper_valid', lower='lower_valid', person='person_valid'), keep_stages)
+        return TryOnOutfitBatch(t, raw['person_name'], raw['upper_name'], raw['lower_name'], stages)
+
+    def _prepare(self, raw, panels, valid_stages, keep_stages):
+        """The one body of the test builders: (fp32 tensors, stages or None) of a batch of ``collate_outfits``.  ``panels``: whose
+        photographs follow ``image``, by role: two give ``clothes`` and ``clothes_lower`` (pasta_tryon_outfit_assemble), one gives
+        ``clothes`` alone (pasta_tryon_region_assemble: the same launcher with nine outputs).  ``valid_stages``: the name under
+        which the stages keep the [N, 10] valid flags of a role's matrices."""
         dev = self.device
-        people_image, people_parsing, people_kp = upload_person(raw, dev, 'TryOnOutfitBatchBuilder', 'people_')
+        people_image, people_parsing, people_kp = upload_person(raw, dev, type(self).__name__, 'people_')
         m, H, W, _ = people_image.shape
         lp = (H - W) // 2
         host_idx = [np.asarray(raw[k], np.int64) for k in ('person_idx', 'upper_idx', 'lower_idx')]
@@ -161,15 +132,38 @@ class TryOnOutfitBatchBuilder:
             garment_img, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
         patches, patches_l, _, _, den_u, den_l, _ = normalized
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
-        t, outs = output_tensors(TryOnOutfitBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
+        photograph = dict(upper=u_image, lower=l_image)
+        assemble, keys = ((lib.pasta_tryon_outfit_assemble, TryOnOutfitBatch.KEYS) if len(panels) == 2 else
+                          (lib.pasta_tryon_region_assemble, TryOnRegionBatch.KEYS))
+        t, outs = output_tensors(keys, n, H, (3 * (pu + pl), ph, pw), dev)
         with torch.cuda.device(dev):
-            _native.check(lib.pasta_tryon_outfit_assemble(P(image), P(u_image), P(l_image), P(retain_img), P(stick), P(patches), P(patches_l),
-                                                          P(den_u), P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
+            _native.check(assemble(P(image), *[P(photograph[role]) for role in panels], P(retain_img), P(stick), P(patches), P(patches_l),
+                                   P(den_u), P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
         stages = None
         if keep_stages:
-            stages = _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized, upper_valid=valid_u,
-                             lower_valid=valid_l, person_valid=valid_p)
-        return TryOnOutfitBatch(t, raw['person_name'], raw['upper_name'], raw['lower_name'], stages)
+            valid = dict(upper=valid_u, lower=valid_l, person=valid_p)
+            stages = _stages(image, parsing, stick, palm, retain_img, garment_img, garment_mask, normalized,
+                             **{name: valid[role] for role, name in valid_stages.items()})
+        return t, stages
+
+
+class TryOnRegionBatchBuilder(TryOnOutfitBatchBuilder):
+    """``build(raw_batch)``: a batch of ``training.dataset.collate_pairs`` -> TryOnRegionBatch on ``device`` for
+    ``change_region`` = 'fullbody', 'upperbody' or 'lowerbody': the pairs as the outfits (P, D, D), (P, D, -) or (P, -, D),
+    stacked on the device after the upload.  ``clothes`` is always the DONOR's photograph, which at 'lowerbody' is not the upper
+    garment's owner, and there is no ``clothes_lower``."""
+
+    def __init__(self, device, change_region, box_factor=2):
+        if change_region not in REGIONS:
+            raise ValueError('change region %s is invalid.' % change_region)
+        super().__init__(device, box_factor)
+        self.change_region = change_region
+
+    def build(self, raw, keep_stages=False):
+        donor = 'lower' if self.change_region == 'lowerbody' else 'upper'
+        t, stages = self._prepare(pairs_batch_as_outfits(upload_images(raw, self.device), self.change_region), (donor,),
+                                  {donor: 'clothes_valid', 'person': 'person_valid'}, keep_stages)
+        return TryOnRegionBatch(t, raw['person_name'], raw['clothes_name'], stages)
 
 
 class FullBodyRegionBatchBuilder:
@@ -201,9 +195,9 @@ class FullBodyRegionBatchBuilder:
             _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
             _native.check(lib.pasta_tryon_train_region_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), P(garment_img[:n]),
                                                                 P(garment_mask[:n]), P(garment_img[n:]), P(garment_mask[n:]), n, H, W, s))
-        shifted = shift_keypoints(kp, lp)
-        patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, part_masks = patch_pipeline.normalize_region_batch(
-            garment_img, garment_mask, shifted, shifted, True, True, self.box_factor, want_part_masks=True)
+        own = np.arange(n)                  # everyone wears their own garments: the N people are solved once
+        patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, _, part_masks = patch_pipeline.normalize_outfit_batch(
+            garment_img, garment_mask, shift_keypoints(kp, lp), own, own, own, self.box_factor, want_part_masks=True)
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
         arm_a, arm_b = patch_pipeline.ARM_PARTS[2], patch_pipeline.ARM_PARTS[3]
         t, outs = output_tensors(FullBodyBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)

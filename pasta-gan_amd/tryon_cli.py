@@ -1,14 +1,13 @@
-"""What the two try-on command lines, test.py and test_512.py, share: the options the reference declares, the refusal of a
-snapshot that is not a local file, loading ``G_ema``, the loader over a pair data set, the generator's call sequence and the
---scores report.
+"""What the two try-on command lines, test.py and test_512.py, share: the options the reference declares and this project's own
+(each command line lists its options itself, in the order --help prints them), the refusal of a snapshot that is not a local
+file, loading ``G_ema``, the loader over a test data set, the generator's call sequence, the --scores report, and the ONE loop
+that dresses a data set (``dress``): build, z, generate, score, convert, write.
 
-test.py's --outfits and --change-region are served by ``generate_256`` below; a run with neither is test.py's own loop.
-
-test_512.py's --outfits and --scores are declared and served HERE, not in that file, which stays the reference's command line
-as it was (``shared_options`` says how): ``generate_512`` is the one loop for those runs, outfits or pairs."""
+Every run dresses OUTFITS.  ``generate_256`` (test.py) and ``generate_512`` (test_512.py) choose the data set, the collate
+function, the builder and how an item is written; pair lists become the outfits of the change region in the loader's workers
+(``training.dataset.collate_region_outfits``), where a person named twice in a batch is stacked, uploaded and solved once."""
 
 import functools
-import inspect
 import os
 import re
 from typing import List
@@ -33,8 +32,8 @@ def _local_snapshot(path):
 
 
 def shared_options(dataroot_help, batchsize):
-    """The decorator of the options both command lines take up to --batchsize, in the order --help prints them; each command
-    line puts its own options and --workers (``workers_option``) below it."""
+    """The decorator of the options both command lines take up to --storage, in the order --help prints them; each command line
+    puts its own options and --workers (``workers_option``) below it."""
     options = [
         click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True),
         click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)'),
@@ -49,40 +48,14 @@ def shared_options(dataroot_help, batchsize):
         storage_option]
 
     def decorate(f):
-        parameters = inspect.signature(f).parameters
-        # --storage is kept here for ``load_generator`` and handed to the command's function only where it declares the argument
-        # (test.py writes it into its report): a command line that just loads and runs the generator needs no line for it
-        takes_storage = 'storage' in parameters
-        # A command whose function takes ``change_region`` and no ``scores_file`` of its own is the 512 x 320 command line.  It
-        # gets --outfits and --scores from here, and a run that gives either is ``generate_512`` below, not the function's
-        # own loop over the pair lists, which knows neither: test_512.py stays as it is and still runs every plain command.
-        # tests/test_tryon_outfits_gpu.py holds the two loops to the same files for the same pairs.
-        extended = 'change_region' in parameters and 'scores_file' not in parameters
-
-        @functools.wraps(f)
-        def command(*args, storage=None, **kwargs):
-            _given['storage'] = storage
-            if extended:
-                outfits_file, scores_file = kwargs.pop('outfits_file', None), kwargs.pop('scores_file', None)
-                if outfits_file is not None or scores_file is not None:
-                    for unused in ('seeds', 'class_idx', 'projected_w'):
-                        kwargs.pop(unused, None)
-                    kwargs['change_region'] = _explicit_region(kwargs.get('change_region'))
-                    return generate_512(*args, outfits_file=outfits_file, scores_file=scores_file, storage=storage, **kwargs)
-            if takes_storage:
-                kwargs['storage'] = storage
-            return f(*args, **kwargs)
-        if extended:
-            command = scores_option(outfits_option(command))
         for option in reversed(options):
-            command = option(command)
-        return command
+            f = option(f)
+        return f
     return decorate
 
 
 # --storage: run the loaded generator in this activation storage instead of the one it was pickled with
 STORAGE_DTYPES = {'snapshot': None, 'f32': 'float32', 'bf16': 'bfloat16', 'f16': 'float16'}
-_given = {}                 # the running command's --storage (``shared_options``)
 storage_option = click.option('--storage', help='Activation storage the generator runs in: as pickled (snapshot), or f32, bf16, f16 '
                               '[default: snapshot]', type=click.Choice(list(STORAGE_DTYPES)))
 
@@ -123,11 +96,9 @@ workers_option = click.option('--workers', help='Loader processes (file decoding
 
 def load_generator(network_pkl, device, storage=None):
     """``G_ema`` of a snapshot file on ``device``, in eval mode and without gradients.  ``storage``: a key of ``STORAGE_DTYPES``,
-    by default the --storage of the running command; None or 'snapshot' runs the network as pickled, another value switches its
-    activation storage (``training.networks.set_activation_storage``)."""
+    the command's --storage; None or 'snapshot' runs the network as pickled, another value switches its activation storage
+    (``training.networks.set_activation_storage``)."""
     import legacy
-    if storage is None:
-        storage = _given.get('storage')
     print('Loading networks from "%s"...' % network_pkl)
     with open(network_pkl, 'rb') as f:
         G = legacy.load_network_pkl(f)['G_ema'].to(device).eval().requires_grad_(False)  # type: ignore
@@ -137,13 +108,13 @@ def load_generator(network_pkl, device, storage=None):
     return G
 
 
-def pair_loader(dataset, batchsize, workers, collate_fn=None):
-    """The pairs (or, with ``training.dataset.collate_outfits``, the outfits) of ``dataset`` in order; the workers only decode files."""
+def pair_loader(dataset, batchsize, workers, collate_fn):
+    """The items of ``dataset`` in order, collated by ``collate_fn`` (``training.dataset.collate_outfits``, or
+    ``collate_region_outfits`` for a pair list); the workers only decode files and stack."""
     import torch
-    from training.dataset import collate_pairs
     print(len(dataset))
     return torch.utils.data.DataLoader(dataset, batch_size=batchsize, shuffle=False, num_workers=workers, pin_memory=True,
-                                       collate_fn=collate_fn or collate_pairs)
+                                       collate_fn=collate_fn)
 
 
 def generate(G, t, gen_z, truncation_psi, noise_mode):
@@ -181,17 +152,11 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
         f.write(line + '\n')
 
 
-def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
-                 scores_file=None, storage=None):
-    """test_512.py with --outfits and / or --scores.  --outfits FILE: every line ``person upper lower`` of FILE
-    (training.dataset.UvitonOutfits_512_test) instead of the pair lists, prepared by
-    training.tryon_regions.TryOnOutfitBatchBuilder, written as ``upper donor | lower donor | person | generated`` (512 x 2048) to
-    ``<outdir>/<count>.png`` in list order.  ``change_region`` None means full body; any other value is refused together with
-    --outfits, since a line names whose garments are worn.  --scores FILE: the region scores of metrics/tryon_fidelity.py over
-    what is written, z of item i from ``pair_z(i)``, ``pixels = 512 * 320``.  Without --outfits the pairs of the change region
-    are written as test_512.py writes them, ``clothes | person | generated``."""
-    if outfits_file is not None and change_region is not None:
-        raise click.UsageError(BOTH_MODES)
+def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None):
+    """The loop of both command lines.  ``choose(device)`` -> (data set, collate function, builder, ``pictures``), called once the
+    snapshot is loaded; ``pictures(batch, raw, gen_imgs, count)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names under
+    ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
+    item i is ``pair_z(i)`` and the region scores of metrics/tryon_fidelity.py over what is written go to FILE (``write_scores``)."""
     _local_snapshot(network_pkl)
 
     import numpy as np
@@ -199,101 +164,99 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     import torch
 
     from metrics import tryon_fidelity
-    from training import dataset as custom_dataset
-    from training.tryon_pairs import images_to_u8
-    from training.tryon_regions import TryOnOutfitBatchBuilder, TryOnRegionBatchBuilder
 
     device = torch.device('cuda')
     G = load_generator(network_pkl, device, storage)
     os.makedirs(outdir, exist_ok=True)
-    if outfits_file is not None:
-        dataset = custom_dataset.UvitonOutfits_512_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
-        loader = pair_loader(dataset, batchsize, workers, custom_dataset.collate_outfits)
-        builder, panels = TryOnOutfitBatchBuilder(device), ('clothes', 'clothes_lower', 'image')
-    else:
-        change_region = change_region or 'fullbody'
-        dataset = custom_dataset.UvitonDatasetFull_512_test(path=dataroot, change_region=change_region, use_labels=True, max_size=None, xflip=False)
-        loader = pair_loader(dataset, batchsize, workers)
-        builder, panels = TryOnRegionBatchBuilder(device, change_region), ('clothes', 'image')
-    partials = tryon_fidelity.new_partials(len(dataset), device) if scores_file is not None else None
+    dataset, collate_fn, builder, pictures = choose(device)
+    loader = pair_loader(dataset, batchsize, workers, collate_fn)
+    scoring = scores_file is not None
+    partials = tryon_fidelity.new_partials(len(dataset), device) if scoring else None
+    pixels = tryon_fidelity.PIXELS                                  # content pixels of an item; every batch brings its own
     count = 0
     for raw in loader:
-        batch = builder.build(raw, keep_stages=scores_file is not None)
-        t, n = batch.tensors, batch.batch
-        side = t['image'].shape[2]
-        gen_z = torch.empty([n, 0], device=device)
-        if scores_file is not None:
+        batch = builder.build(raw, keep_stages=scoring)
+        gen_z = torch.empty([batch.batch, 0], device=device)
+        if scoring:
             index = raw['raw_idx'].tolist()                         # the items' positions in the pair lists, or in the outfit list
             gen_z = tryon_fidelity.pair_z(index, G.z_dim, device)
-        gen_imgs = generate(G, t, gen_z, truncation_psi, noise_mode)
-        if scores_file is not None:
+        gen_imgs = generate(G, batch.tensors, gen_z, truncation_psi, noise_mode)
+        if scoring:
             tryon_fidelity.score_batch(gen_imgs, batch, index, partials)
-        images = torch.cat([images_to_u8(x, 0, side) for x in [t[k] for k in panels] + [gen_imgs]], dim=2).cpu().numpy()
-        for result in images:
-            PIL.Image.fromarray(np.ascontiguousarray(result)).save(os.path.join(outdir, str(count).zfill(3) + '.png'))
+            pixels = raw['people_image'].shape[1] * raw['people_image'].shape[2]
+        images, names = pictures(batch, raw, gen_imgs, count)
+        for img, name in zip(images.cpu().numpy(), names):
+            os.makedirs(os.path.dirname(os.path.join(outdir, name)), exist_ok=True)
+            PIL.Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(outdir, name))
             count += 1
     print('finish: %d images under %s' % (count, outdir))
-    if scores_file is not None:
-        write_scores(scores_file, partials, 512 * 320, count, network_pkl, dataroot, noise_mode, storage)
+    if scoring:
+        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode)
+
+
+def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
+                 scores_file=None, storage=None):
+    """test_512.py: the 512 x 320 model on outfits, prepared by training.tryon_regions.TryOnOutfitBatchBuilder and written to
+    ``<outdir>/<count>.png`` in list order.  --outfits FILE: every line ``person upper lower`` of FILE
+    (training.dataset.UvitonOutfits_512_test), written as ``upper donor | lower donor | person | generated`` (512 x 2048).
+    Without it: the pairs of the pair lists as the outfits of ``change_region`` (None means full body), written as the reference
+    writes them, ``clothes | person | generated`` with the DONOR as ``clothes``, who for 'lowerbody' owns the lower garment.
+    A ``change_region`` other than None is refused together with --outfits, since a line names whose garments are worn, and that
+    is refused before anything is read."""
+    if outfits_file is not None and change_region is not None:
+        raise click.UsageError(BOTH_MODES)
+
+    def choose(device):
+        import torch
+        from training import dataset as custom_dataset
+        from training.tryon_pairs import images_to_u8
+        from training.tryon_regions import TryOnOutfitBatchBuilder
+        if outfits_file is not None:
+            dataset = custom_dataset.UvitonOutfits_512_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
+            collate_fn, panels = custom_dataset.collate_outfits, ('clothes', 'clothes_lower', 'image')
+        else:
+            region = change_region or 'fullbody'
+            dataset = custom_dataset.UvitonDatasetFull_512_test(path=dataroot, change_region=region, use_labels=True, max_size=None, xflip=False)
+            collate_fn = functools.partial(custom_dataset.collate_region_outfits, region)
+            panels = ('clothes_lower' if region == 'lowerbody' else 'clothes', 'image')
+
+        def pictures(batch, raw, gen_imgs, count):
+            t = batch.tensors
+            side = t['image'].shape[2]
+            images = torch.cat([images_to_u8(x, 0, side) for x in [t[k] for k in panels] + [gen_imgs]], dim=2)
+            return images, [str(count + i).zfill(3) + '.png' for i in range(batch.batch)]
+        return dataset, collate_fn, TryOnOutfitBatchBuilder(device), pictures
+    dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage)
 
 
 def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
                  scores_file=None, storage=None):
-    """test.py with --outfits or --change-region: the 256 x 192 model on outfits, prepared by
-    training.tryon_pairs.TryOnPairOutfitBatchBuilder.  --outfits FILE: every line ``person upper lower`` of FILE
+    """test.py: the 256 x 192 model on outfits, prepared by training.tryon_pairs.TryOnPairOutfitBatchBuilder; only the generated
+    image is written, columns 32..223 of the generator's square.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
-    stem>.png``, a kept garment under the person's stem.  --change-region: the pairs of the pair lists as the outfits (P, D, -),
-    (P, -, D) or (P, D, D), written under test.py's name ``<person stem>__<clothes stem>.png``; 'upperbody' writes the bytes of a
-    run without the option.  The two exclude each other, and that is refused before anything is read.  Only the generated image
-    is written, as test.py writes it.  --scores FILE: the region scores over what is written, z of item i from ``pair_z(i)``;
-    the report's ``mode`` is ``outfits`` or ``change-region <region>``."""
+    stem>.png``, a kept garment under the person's stem.  Without it: the pairs of the pair lists as the outfits (P, D, -),
+    (P, -, D) or (P, D, D) of ``change_region`` (None: upper body, the reference's run), written to ``<person stem>__<clothes
+    stem>.png``.  The two exclude each other, and that is refused before anything is read.  The --scores report's ``mode`` is
+    ``outfits`` or ``change-region <region>``; a run with neither option has none."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
-    _local_snapshot(network_pkl)
 
-    import numpy as np
-    import PIL.Image
-    import torch
+    def choose(device):
+        from training import dataset as custom_dataset
+        from training.tryon_pairs import TryOnPairOutfitBatchBuilder, images_to_u8
+        if outfits_file is not None:
+            dataset = custom_dataset.UvitonOutfits_256_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
+            collate_fn, worn = custom_dataset.collate_outfits, ('upper_name', 'lower_name')
+        else:
+            dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
+            collate_fn, worn = functools.partial(custom_dataset.collate_region_outfits, change_region or 'upperbody'), ('clothes_name',)
+        stem = lambda name: os.path.basename(name)[:-4]
 
-    from metrics import tryon_fidelity
-    from training import dataset as custom_dataset
-    from training.tryon_pairs import TryOnPairOutfitBatchBuilder, images_to_u8
-
-    device = torch.device('cuda')
-    G = load_generator(network_pkl, device, storage)
-    os.makedirs(outdir, exist_ok=True)
-    if outfits_file is not None:
-        dataset = custom_dataset.UvitonOutfits_256_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
-        loader, mode = pair_loader(dataset, batchsize, workers, custom_dataset.collate_outfits), 'outfits'
-    else:
-        dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
-        loader = pair_loader(dataset, batchsize, workers, functools.partial(custom_dataset.collate_region_outfits, change_region))
-        mode = 'change-region ' + change_region
-    builder = TryOnPairOutfitBatchBuilder(device)
-    partials = tryon_fidelity.new_partials(len(dataset), device) if scores_file is not None else None
-    pixels = tryon_fidelity.PIXELS
-    stem = lambda name: os.path.basename(name)[:-4]
-    written = 0
-    for raw in loader:
-        batch = builder.build(raw, keep_stages=scores_file is not None)
-        t, n = batch.tensors, batch.batch
-        height, width = raw['people_image'].shape[1], raw['people_image'].shape[2]
-        gen_z = torch.empty([n, 0], device=device)
-        if scores_file is not None:
-            index = raw['raw_idx'].tolist()                         # the items' positions in the pair lists, or in the outfit list
-            gen_z = tryon_fidelity.pair_z(index, G.z_dim, device)
-        gen_imgs = generate(G, t, gen_z, truncation_psi, noise_mode)
-        images = images_to_u8(gen_imgs, (height - width) // 2, width).cpu().numpy()
-        if scores_file is not None:
-            tryon_fidelity.score_batch(gen_imgs, batch, index, partials)
-            pixels = height * width
-        worn = zip(batch.upper_name, batch.lower_name) if outfits_file is not None else zip(raw['clothes_name'])
-        for img, person, garments in zip(images, batch.person_name, worn):
-            save_dir = os.path.join(outdir, person.split('/')[0])
-            os.makedirs(save_dir, exist_ok=True)
-            name = '__'.join([stem(person)] + [stem(g) for g in garments]) + '.png'
-            PIL.Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(save_dir, name))
-            written += 1
-    print('finish: %d images under %s' % (written, outdir))
-    if scores_file is not None:
-        write_scores(scores_file, partials, pixels, written, network_pkl, dataroot, noise_mode, storage, mode)
+        def pictures(batch, raw, gen_imgs, count):
+            height, width = raw['people_image'].shape[1], raw['people_image'].shape[2]
+            names = [os.path.join(who[0].split('/')[0], '__'.join(stem(name) for name in who) + '.png')
+                     for who in zip(raw['person_name'], *[raw[k] for k in worn])]
+            return images_to_u8(gen_imgs, (height - width) // 2, width), names
+        return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device), pictures
+    mode = 'outfits' if outfits_file is not None else change_region and 'change-region ' + change_region
+    dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode)

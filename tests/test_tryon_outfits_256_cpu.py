@@ -1,6 +1,7 @@
 """Outfits for the 256 x 192 model on the host: the list format of ``training.dataset.UvitonOutfits_256_test`` on the tiny test
 tree (tests/tryon_pairs_tree.py), its refusals, the raw outfit, ``collate_outfits``' deduplicated people stack on a 256 batch,
-a pair taken as the outfit of a change region, the two native entries' declarations and test.py's two options.  No GPU."""
+a pair, and a collated batch of pairs, taken as the outfits of a change region, the two native entries' declarations and test.py's
+two options.  No GPU."""
 import os
 import re
 import subprocess
@@ -159,6 +160,42 @@ def test_a_pair_is_the_outfit_of_its_change_region(tree):
     b = functools.partial(collate_region_outfits, 'lowerbody')([pairs[0], pairs[1]])
     assert b['clothes_name'] == [pairs[i]['clothes_name'] for i in (0, 1)] and b['upper_name'] == b['person_name']
     assert b['lower_name'] == b['clothes_name'] and len(b['people_name']) == 4 and b['upper_idx'].tolist() == b['person_idx'].tolist()
+
+
+def test_a_collated_pair_batch_is_the_outfit_batch_of_its_region(tree):
+    """``pairs_batch_as_outfits``, what the pair builders put in front of the outfit builders: the persons, then the donors,
+    nobody looked up twice.  Pair 1 comes twice, so its two people are in the stack twice, where ``collate_region_outfits``
+    of the same samples stacks them once; through the indices both name the same arrays."""
+    from training.dataset import (UvitonDatasetV19_test, collate_outfits, collate_pairs, collate_region_outfits, pair_as_outfit,
+                                  pairs_batch_as_outfits)
+    pairs = UvitonDatasetV19_test(path=tree)
+    samples = [pairs[1], pairs[0], pairs[1]]
+    n = len(samples)
+    raw = collate_pairs(samples)
+    person, donor = list(range(n)), list(range(n, 2 * n))
+    whose = dict(upperbody=(donor, person), lowerbody=(person, donor), fullbody=(donor, donor))
+    for region, (upper, lower) in whose.items():
+        b = pairs_batch_as_outfits(raw, region)
+        dedup = collate_region_outfits(region, samples)
+        assert sorted(b) == sorted(dedup) == sorted(list(collate_outfits([pair_as_outfit(s, region) for s in samples])) + ['clothes_name'])
+        assert b['people_name'] == raw['person_name'] + raw['clothes_name'] and len(dedup['people_name']) == 4 < len(b['people_name']) == 2 * n
+        assert b['person_idx'].tolist() == person and b['upper_idx'].tolist() == upper and b['lower_idx'].tolist() == lower
+        assert b['person_name'] == raw['person_name'] and b['clothes_name'] == raw['clothes_name'] and b['raw_idx'].tolist() == [1, 0, 1]
+        assert b['upper_name'] == dedup['upper_name'] and b['lower_name'] == dedup['lower_name']
+        for k, dtype, shape in (('people_image', torch.uint8, (2 * n, 256, 192, 3)), ('people_parsing', torch.uint8, (2 * n, 256, 192)),
+                                ('people_keypoints', torch.float64, (2 * n, 18, 3))):
+            assert b[k].dtype == dtype and tuple(b[k].shape) == shape and b[k].dtype == dedup[k].dtype, k
+            assert torch.equal(b[k], torch.cat([raw[k[len('people_'):]], raw['clothes_' + k[len('people_'):]]])), k
+        for role in ('person', 'upper', 'lower'):
+            ix, ix_dedup = b[role + '_idx'], dedup[role + '_idx']
+            # what the builders assert of a batch of collate_outfits
+            assert ix.dtype == torch.int64 and tuple(ix.shape) == (n,) and int(ix.min()) >= 0 and int(ix.max()) < len(b['people_image'])
+            assert [b['people_name'][j] for j in ix.tolist()] == b[role + '_name'] == [dedup['people_name'][j] for j in ix_dedup.tolist()]
+            for k in ('people_image', 'people_parsing', 'people_keypoints'):
+                assert torch.equal(b[k][ix], dedup[k][ix_dedup]), (region, role, k)
+        assert torch.equal(b['people_image'][0], b['people_image'][2]) and not torch.equal(b['people_image'][0], b['people_image'][1])
+    with pytest.raises(ValueError, match='change region'):
+        pairs_batch_as_outfits(raw, 'legs')
 
 
 def test_the_entries_are_declared_typed_and_exported():

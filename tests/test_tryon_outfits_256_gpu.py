@@ -247,6 +247,36 @@ def test_the_upper_body_outfit_equals_the_pair_builder(tree):
     assert TryOnPairOutfitBatchBuilder('cuda').build(raw).stages is None
 
 
+def test_the_pair_view_equals_the_outfit_builder_on_deduplicated_people(tree):
+    """A batch of three with pair 1 twice: TryOnPairBatchBuilder stacks its six people as they come (M = 2N), the outfit builder
+    takes the same samples through ``collate_region_outfits`` with every person once (M = 4).  One launch holds a person used
+    twice and people used once."""
+    from training.dataset import UvitonDatasetV19_test, collate_pairs, collate_region_outfits
+    from training.tryon_pairs import TryOnPairBatch, TryOnPairBatchBuilder, TryOnPairOutfitBatchBuilder
+    pairs = UvitonDatasetV19_test(path=tree)
+    samples = [pairs[1], pairs[0], pairs[1]]
+    dedup = collate_region_outfits('upperbody', samples)
+    assert len(dedup['people_name']) == 4 < 2 * len(samples)
+    want = TryOnPairOutfitBatchBuilder('cuda').build(dedup, keep_stages=True)
+    got = TryOnPairBatchBuilder('cuda').build(collate_pairs(samples), keep_stages=True)
+    assert type(got) is TryOnPairBatch and got.batch == 3 and got.person_name == want.person_name and got.clothes_name == dedup['clothes_name']
+    assert list(got.tensors) == TryOnPairBatch.KEYS
+    for k in TryOnPairBatch.KEYS:
+        assert got.tensors[k].shape == want.tensors[k].shape and torch.equal(got.tensors[k], want.tensors[k]), k
+        assert torch.equal(got.tensors[k][0], got.tensors[k][2]), k                                      # the pair named twice
+    assert not torch.equal(got.tensors['retain'][0], got.tensors['retain'][1])
+    assert len(got.stages) == 18 and sorted(set(want.stages) - set(got.stages)) == ['lower_stick', 'person_valid']
+    u8 = [k for k, x in got.stages.items() if torch.is_tensor(x) and x.dtype == torch.uint8]
+    assert len(u8) == 15 and set(U8_STAGES) - {'lower_stick'} <= set(u8) and set(PATCH_STAGES) <= set(u8)
+    for k, x in got.stages.items():
+        if torch.is_tensor(x):
+            assert want.stages[k].dtype == x.dtype and torch.equal(want.stages[k], x), k
+        else:
+            assert k.endswith('_valid') and np.array_equal(want.stages[k], x), k
+    assert got.stages['denorm_upper'].any() and got.stages['denorm_lower'].any() and got.stages['palm'].any()
+    assert TryOnPairBatchBuilder('cuda').build(collate_pairs(samples)).stages is None
+
+
 def _listed(name):
     """'p3' -> 'UPT_subset2_256_192/p3.jpg', '-' -> '-'."""
     if name == '-':

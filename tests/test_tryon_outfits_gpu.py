@@ -1,7 +1,7 @@
 """Outfits at 512 x 320 on the GPU (pasta_tryon_outfit_masks_u8 / pasta_tryon_outfit_assemble of csrc/tryon_pairs.hip,
 training.tryon_regions.TryOnOutfitBatchBuilder, ``test_512.py --outfits`` and ``--scores``) -- EXACT: the entries against a numpy
 statement of their rule and against the region entries they generalise, the builder against the region builder on the three
-degenerate outfits of every pair, a truly mixed list against values composed from tests/tryon_512_ref.py, and the command line
+degenerate outfits of every pair and on a batch that names a pair twice, a truly mixed list against values composed from tests/tryon_512_ref.py, and the command line
 against an in-process run and the region scores' numpy restatement (tests/tryon_fidelity_ref.py)."""
 import ctypes
 import json
@@ -177,6 +177,42 @@ def test_degenerate_outfits_equal_the_region_builder(tree, tmp_path):
         donor_valid = got.stages['lower_valid' if region == 'lowerbody' else 'upper_valid']
         assert np.array_equal(donor_valid, want.stages['clothes_valid'])
         assert got.stages['denorm_upper'].any() and got.stages['denorm_lower'].any() and not torch.equal(got.tensors['image'], donor)
+
+
+def test_the_pair_view_equals_the_outfit_builder_on_deduplicated_people(tree):
+    """A batch of three with pair 0 twice: TryOnRegionBatchBuilder stacks its six people as they come (M = 2N), the outfit builder
+    takes the same samples through ``collate_region_outfits`` with every person once (M = 4).  One launch holds a person used
+    twice and people used once.  The pair view has the nine tensors and no tenth, and its ``clothes`` is the donor's photograph
+    in every region."""
+    from training.dataset import UvitonDatasetFull_512_test, collate_pairs, collate_region_outfits
+    from training.tryon_regions import TryOnOutfitBatchBuilder, TryOnRegionBatch, TryOnRegionBatchBuilder
+    donors = {}
+    for region in ('fullbody', 'upperbody', 'lowerbody'):
+        pairs = UvitonDatasetFull_512_test(path=tree, change_region=region)
+        samples = [pairs[0], pairs[1], pairs[0]]
+        dedup = collate_region_outfits(region, samples)
+        assert len(dedup['people_name']) == 4 < 2 * len(samples)
+        want = TryOnOutfitBatchBuilder('cuda').build(dedup, keep_stages=True)
+        builder = TryOnRegionBatchBuilder('cuda', region)
+        plain, got = builder.build(collate_pairs(samples)), builder.build(collate_pairs(samples), keep_stages=True)
+        assert list(plain.tensors) == list(got.tensors) == TryOnRegionBatch.KEYS and len(TryOnRegionBatch.KEYS) == 9       # no tenth tensor
+        assert plain.stages is None and got.batch == 3 and got.person_name == want.person_name and got.clothes_name == dedup['clothes_name']
+        for k in TryOnRegionBatch.KEYS:
+            x = want.tensors['clothes_lower'] if (k == 'clothes' and region == 'lowerbody') else want.tensors[k]        # the donor's
+            assert got.tensors[k].shape == x.shape and torch.equal(got.tensors[k], x), (region, k)
+            assert torch.equal(plain.tensors[k], x), (region, k)
+            assert torch.equal(got.tensors[k][0], got.tensors[k][2]), (region, k)                                           # the pair named twice
+        shared = [k for k in got.stages if k in want.stages and torch.is_tensor(got.stages[k]) and got.stages[k].dtype == torch.uint8]
+        assert len(shared) == 15 and {'image', 'parsing', 'palm', 'patches_lower', 'denorm_lower'} <= set(shared)
+        for k in shared:
+            assert torch.equal(got.stages[k], want.stages[k]), (region, k)
+        assert torch.equal(got.stages['M_invs'], want.stages['M_invs']) and np.array_equal(got.stages['person_valid'], want.stages['person_valid'])
+        assert np.array_equal(got.stages['clothes_valid'], want.stages['lower_valid' if region == 'lowerbody' else 'upper_valid'])
+        assert sorted(set(got.stages) - set(want.stages)) == ['clothes_valid']
+        assert got.stages['denorm_upper'].any() and got.stages['denorm_lower'].any() and got.stages['palm'].any()
+        donors[region] = got.tensors['clothes']
+        assert not torch.equal(got.tensors['clothes'], got.tensors['image'])
+    assert torch.equal(donors['lowerbody'], donors['fullbody']) and torch.equal(donors['upperbody'], donors['fullbody'])
 
 
 _EXPECTED = {}
@@ -395,7 +431,7 @@ def test_cli_writes_and_scores_the_outfits(tree, tmp_path, tmp_path_factory):
     assert sorted(pairs) == sorted(report) and sorted(pairs['results']) == sorted(got) and pairs['pairs'] == len(PAIRS)
     assert sorted(os.listdir(short)) == ['%03d.png' % i for i in range(len(PAIRS))] + ['scores.json']
     assert pairs['results']['tryon_keep_pairs'] == len(PAIRS) and np.isfinite(pairs['results']['tryon_upper_l1'])
-    # test_512.py's own loop, which runs when neither option is given, writes the same files for the same pairs (z_dim = 0: the
+    # the command's function called without --scores, as a plain run, writes the same files for the same pairs (z_dim = 0: the
     # per-pair z is the plain run's z)
     import importlib.util
     spec = importlib.util.spec_from_file_location('pasta_test_512_cli', CLI)
