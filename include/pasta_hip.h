@@ -30,7 +30,7 @@ enum { PASTA_F32 = 0, PASTA_F16 = 1, PASTA_F64 = 2, PASTA_BF16 = 3 };
 
 /* Library identification / error reporting. */
 const char* pasta_last_error(void);
-int         pasta_abi_version(void);           /* bumps when a signature changes   */
+int         pasta_abi_version(void);           /* 22; bumps when a signature changes */
 const char* pasta_build_info(void);            /* "gfx950 <date> <hip version>"    */
 
 /* ------------------------------------------------------------------------- *
@@ -500,9 +500,12 @@ int pasta_patch_composite_u8(const uint8_t* patches, const uint8_t* masks, const
  * training/dataset.py:515-568, 619-736, 929-993, and the loop's conversions, training_loop_wo_flow_fullbody.py:425-456),
  * which the reference runs on the host with OpenCV, pycocotools and skimage.  Each entry does a batch in one launch.
  * The unpadded canvas is H x W (256 x 192), padded by lp = (H - W) / 2 columns on the left into an H x H square.
+ * This set passes thickness 2 and radius 2 to the stick figure and boxes (25, 16) to the palm mask.
  * Exact by construction: padding, label masks, gt_parsing, joint discs, the palm rule, the box dilation of a given fill,
  * the erase rule and the float conversions.  Restated (parity with the libraries UNPINNED):
- *   cv2.line(thickness=2)   -> every pixel centre within distance 1 of the segment (the capsule of half-width 1);
+ *   cv2.line(thickness=t)   -> every pixel centre within distance t / 2 of the segment (the capsule of half-width t / 2), in
+ *                              integers 4 cross^2 <= t^2 len2 along the segment and 4 d^2 <= t^2 at its ends; for t = 5 cv2
+ *                              draws a polygon of half-width t / 2 with round caps in 16.16 fixed point;
  *   pycocotools rleFrPoly   -> its algorithm: corners (int)(5 x + .5), boundary points along each edge, a run toggles at
  *                              ceil(clamp((v + .5) / 5 - .5, 0, h)) where the boundary steps from u = 5X + 2 to 5X + 3;
  *   cv2.resize(INTER_LINEAR, uint8) -> OpenCV's scalar fixed point: (float)((d + .5) * scale - .5), 11-bit coefficients
@@ -511,23 +514,28 @@ int pasta_patch_composite_u8(const uint8_t* patches, const uint8_t* masks, const
  * ------------------------------------------------------------------------- */
 /* The pose stick figure (draw_pose_from_cords, dataset.py:704-736) into out [N, H, H, 3] (zero padding): per pixel of the
  * canvas, the 19 limbs in order (limbs [N][19][5] int32 = x0, y0, x1, y1, drawn: int()-truncated key points, coordinates within
- * +-4096), then the 18 joints (joints [N][18][3] = x, y, drawn) as the discs (r - y)^2 + (c - x)^2 < 4; the last hit wins,
- * colour = kptcolors[index].  H <= 4096, W <= H. */
-int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, void* stream);
+ * +-4096) as lines of `thickness`, then the 18 joints (joints [N][18][3] = x, y, drawn) as the discs
+ * (r - y)^2 + (c - x)^2 < radius^2, clipped to the canvas -- skimage's ((r - y) / R)^2 + ((c - x) / R)^2 < 1 on every integer
+ * offset for R = 2 and R = 5; the last hit wins, colour = kptcolors[index].  H <= 4096, W <= H, 1 <= thickness, radius <= 64. */
+int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness, int radius,
+                           void* stream);
 
-/* The palm mask (get_palm, :682-702) into out [N, 256, 256] (0 / 1): parsing [N, 256, W] uint8 (unpadded labels);
- * quads [N][4][4][2] doubles = the corners of get_rectangle_mask (in its order, padded coordinates within +-1e5) for the left
- * upper arm, left forearm, right upper arm, right forearm; present [N][4]: 0 = the segment is missing (an all-ones mask).
- * Each fill is dilated with a 25 x 25 (upper arm, offsets -12..12) or 16 x 16 box (forearm, offsets -8..7);
- * palm = hand & !upper & !forearm per side (hand = label 14 left, 15 right), the sides OR-ed.  H must be 256
- * (pasta_palm_mask_square_u8 takes the side and the boxes as arguments). */
-int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H, int W,
-                       void* stream);
+/* The palm mask (get_palm, :682-702; get_hand_mask works on the padded S x S square) into out [N, S, S] (0 / 1): parsing
+ * [N, S, W] uint8 (unpadded labels); quads [N][4][4][2] doubles = the corners of get_rectangle_mask (in its order, padded
+ * coordinates within +-1e5) for the left upper arm, left forearm, right upper arm, right forearm; present [N][4]: 0 = the
+ * segment is missing (an all-ones mask).  Each fill is dilated with a k_upper (upper arm) or k_lower (forearm) box; a k x k box
+ * covers offsets -(k / 2) .. k - 1 - k / 2 (cv2's default anchor): -12..12 for 25, -8..7 for 16, -17..17 for 35, -10..9 for 20.
+ * palm = hand & !upper & !forearm per side (hand = label 14 left, 15 right), the sides OR-ed.  S a multiple of 16,
+ * 16 <= S <= 512; W <= S; 1 <= k <= S. */
+int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S, int W,
+                       int k_upper, int k_lower, void* stream);
 
 /* :537-556 from image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H]: retain = shoes(18, 19) + palm +
  * head(1, 2, 4, 13) and gt_parsing = upper(5, 6, 7) + 2 lower(9, 12) + 3 hands(14, 15) + 4 legs(16, 17) + 5 neck(10), [N, H, H];
  * upper_img / lower_img = mask * padded image (pad 255) and upper_mask / lower_mask = 255 * mask, [N, H, H, 3] (the inputs
- * of patch_pipeline.normalize_batch). */
+ * of patch_pipeline.normalize_batch).  Mind the order: both images, then both masks.  The 512 x 320 training set names the
+ * same labels and calls this entry too, its four garment pointers being the halves of the stacked [2N, H, H, 3] image and
+ * mask tensors patch_pipeline.normalize_outfit_batch takes (upper garments, then lower). */
 int pasta_tryon_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain, uint8_t* gt_parsing,
                          uint8_t* upper_img, uint8_t* lower_img, uint8_t* upper_mask, uint8_t* lower_mask, int N, int H, int W,
                          void* stream);
@@ -558,48 +566,51 @@ int pasta_tryon_assemble(const uint8_t* image, const uint8_t* stick, const uint8
  *   5. the lower garment is labels 6, 9, 12 of the person (:1113), the upper garment labels 5, 6, 7 of the donor (:1133);
  *   6. key points are shifted by the padding in float64 before get_crop's float32 conversion (:1100, :1129; host side);
  * and, on the host too, get_crop's knee-without-ankle fall-back, which the training set's get_crop has commented out (:1355).
+ * This set passes thickness 2 and radius 2 to pasta_pose_stickman_u8, boxes (25, 15) to pasta_palm_mask_u8 and
+ * six_is_lower = 1 to the label masks below.
  * ------------------------------------------------------------------------- */
-/* pasta_palm_mask_u8 with the dilation boxes as arguments: a k x k box covers offsets -(k / 2) .. k - 1 - k / 2 (cv2's
- * default anchor); k_upper for the upper arm, k_lower for the forearm, 1 <= k <= 256.  (25, 16) is pasta_palm_mask_u8,
- * (25, 15) the test set's rule. */
-int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H, int W,
-                           int k_upper, int k_lower, void* stream);
+/* The label masks of a person in two garments (:1105-1141, :1631-1690) from the person's image [N, H, W, 3], parsing [N, H, W]
+ * (unpadded) and palm [N, H, H] and a source per garment, (upper_image, upper_parsing) and (lower_image, lower_parsing), shaped
+ * like the person's; they may be the person's own pointers.  retain_img = the person's padded image * (shoes(18, 19) + palm +
+ * head(1, 2, 4, 13)), always the person's; upper_img / upper_mask = labels 5, 6, 7 (image, 255) of the upper source;
+ * lower_img / lower_mask = labels 9, 12 of the lower source, and label 6 as well where six_is_lower is 1 (0 or 1; anything else
+ * is refused).  Outputs [N, H, H, 3], padding 255 in the images before the masks are applied, 0 in the labels.  The reference's
+ * 256 pair is the sources (donor, person). */
+int pasta_tryon_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
+                                const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
+                                uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img, uint8_t* lower_mask,
+                                int N, int H, int W, int six_is_lower, void* stream);
 
-/* :1105-1141 from the person's image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H] and the donor's image and
- * parsing: retain_img = padded image * (palm + head(1, 2, 4, 13) + shoes(18, 19)); lower_img / lower_mask = the person's
- * labels 6, 9, 12 (image, 255); upper_img / upper_mask = the donor's labels 5, 6, 7.  Outputs [N, H, H, 3], padding 255 in the
- * images before the masks are applied. */
-int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
-                              const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* lower_img, uint8_t* lower_mask,
-                              uint8_t* upper_img, uint8_t* upper_mask, int N, int H, int W, void* stream);
-
-/* pasta_patch_composite_u8 with the warped-back mask eroded by a (2 radius + 1)^2 box before the == 255 test: a pixel takes
- * part k where channel 0 of the warped-back mask is 255 at every in-image pixel within +-radius (pixels outside the image do
- * not erode, cv2's default border).  part_mask (optional) receives the eroded 0 / 1 mask of every part.  0 <= radius <= 8;
- * radius 0 is pasta_patch_composite_u8 bit for bit. */
+/* pasta_patch_composite_u8 with the warped-back mask eroded by a (2 r + 1)^2 box before the == 255 test: a pixel takes part k
+ * where channel 0 of the warped-back mask is 255 at every in-image pixel within +-r (pixels outside the image do not erode,
+ * cv2's default border).  part_mask (optional) receives the eroded 0 / 1 mask of every part.  r = 0 gives
+ * pasta_patch_composite_u8's bits and takes no barrier.  radii (optional, uint8 [N] on the device):
+ *   null      every sample is eroded by r = radius, 0 <= radius <= 8;
+ *   non-null  sample n is eroded by r = radii[n], all samples in the one launch (a workgroup works on one sample, so r is
+ *             uniform across it), and radius is not read.  The values live on the device, so the entry cannot refuse one: the
+ *             caller checks them on the host (patch_pipeline.composite raises), and the kernel reads a value above 8 as 8, the
+ *             halo its LDS tiles hold. */
 int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
                                     uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
-                                    void* stream);
+                                    const uint8_t* radii, void* stream);
 
-/* pasta_patch_composite_eroded_u8 with a radius per sample: sample n is eroded by radius[n] (uint8 [N] on the device, each
- * 0 .. 8), all samples in the one launch; the radius is uniform across a workgroup, which works on one sample.  A sample with
- * radius 0 is pasta_patch_composite_u8 bit for bit and takes no barrier; a sample with radius r is
- * pasta_patch_composite_eroded_u8 at r bit for bit, part_mask included.  The values live on the device, so the entry cannot
- * refuse one: the caller checks them on the host (patch_pipeline.composite raises), and the kernel reads a value above 8 as
- * 8, the halo its LDS tiles hold. */
-int pasta_patch_composite_radii_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
-                                   uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W,
-                                   const uint8_t* radius, void* stream);
-
-/* __getitem__ (:1502-1525) and test.py:104-117: the seven fp32 NCHW tensors G takes, through outputs (a HOST array of 7
- * device pointers) in this order: retain [N,3,H,H] (test.py's image), pose [N,6,H,H] = stick || retain,
- * style_input [N,6P,ph,pw] = the P garment patches (channel 3k + c of part k) || the P stick-figure patches,
+/* __getitem__ and the scripts' conversions (:1502-1525 and test.py:104-117; :2196-2214 and test_512.py:115-131): fp32 NCHW
+ * tensors through outputs (a HOST array of 10 device pointers) in this order: image, clothes [N,3,H,H] (the padded person and
+ * upper_donor_image, padding 255), retain [N,3,H,H] = x / 127.5 - 1 of retain_img (test.py's form; test_512.py's
+ * image * mask - (1 - mask) with the 0 / 1 retain mask equals it bit for bit, the label groups being disjoint), pose [N,6,H,H] =
+ * stick || retain, style_input [N,3(P+P_lower),ph,pw] = the P patches (channel 3k + c of part k) || the P_lower patches_lower,
  * denorm_upper_input / denorm_lower_input [N,3,H,H], denorm_upper_mask / denorm_lower_mask [N,1,H,H] = channel sum > 0 (no
- * wrap).  x / 127.5 - 1 as torch evaluates it on the GPU: x * (1 / 127.5f) - 1.  retain_img, stick, denorm_upper,
- * denorm_lower [N,H,H,3]; patches, stick_patches [N,P,ph,pw,3] uint8. */
-int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* stick_patches,
-                              const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int P,
-                              int ph, int pw, void* stream);
+ * wrap), clothes_lower [N,3,H,H] = the padded lower_donor_image.  x / 127.5 - 1 as torch evaluates it on the GPU:
+ * x * (1 / 127.5f) - 1.  image, upper_donor_image, lower_donor_image [N,H,W,3]; retain_img, stick, denorm_upper, denorm_lower
+ * [N,H,H,3]; patches [N,P,ph,pw,3], patches_lower [N,P_lower,ph,pw,3] uint8.
+ * Outputs 0, 1 and 9 may be null: a null output is not written and its photograph is not read (it may be null too); a non-null
+ * one needs its photograph.  Outputs 0 and 1 are null together or not at all, and output 9 needs them.  Outputs 2..8 are
+ * required.  The seven tensors G takes at 256 x 192 are outputs 2..8 with the stick-figure patches as patches_lower; test_512.py
+ * takes outputs 0..8, an outfit all ten. */
+int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor_image, const uint8_t* lower_donor_image,
+                                const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* patches_lower,
+                                const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W,
+                                int P, int P_lower, int ph, int pw, void* stream);
 
 /* test.py:133-137: images [N, 3, H, Wt] fp32 -> out [N, H, W, 3] uint8 of columns c0 .. c0 + W - 1: (x + 1.0f) * 127.5f with
  * each operation rounded on its own, clipped to [0, 255], truncated.  A NaN becomes 0 (numpy leaves that conversion
@@ -618,16 +629,9 @@ int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, 
  *   6. parts 0-5 go into denorm_upper through the eroded composite (5 x 5) whoever U is, as the reference erodes them;
  *   7. parts 6-9 go into denorm_lower through the plain composite when L is P (the reference's case, bit for bit) and through
  *      the eroded composite (5 x 5) when L is somebody else: a mask warped onto another body has a fringe, the reference's
- *      reason for rule 6.  The choice is per sample (pasta_patch_composite_radii_u8 with radius 0 or 2).
+ *      reason for rule 6.  The choice is per sample (pasta_patch_composite_eroded_u8 with radii of 0 or 2).
  * The change regions are three outfits: upper body (P, D, P), which is the pair rules above; lower body (P, P, D); full body
- * (P, D, D).
- * pasta_tryon_pair_masks_u8's rules with a source per garment, arguments and output order as pasta_tryon_outfit_masks_u8:
- * upper_img / upper_mask = labels 5, 6, 7 of (upper_image, upper_parsing), lower_img / lower_mask = labels 6, 9, 12 of
- * (lower_image, lower_parsing).  With (donor, person) as the two sources it is pasta_tryon_pair_masks_u8 byte for byte. */
-int pasta_tryon_pair_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
-                                     const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
-                                     uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                                     uint8_t* lower_mask, int N, int H, int W, void* stream);
+ * (P, D, D). */
 
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the 512 x 320 try-on pairs with a change region (row f4; UvitonDatasetFull_512_test,
@@ -644,64 +648,14 @@ int pasta_tryon_pair_outfit_masks_u8(const uint8_t* image, const uint8_t* parsin
  *      norm_img_lower and denorm_lower; every warped-back mask is eroded 5 x 5, the legs' included (:2016, :2031);
  *   6. there are no stick-figure patches: style_input is norm_img || norm_img_lower, 45 channels;
  *   7. on the host, get_crop has no knee-without-ankle fall-back (:1893-1900) and its thigh fall-back ends at row 511.
+ * This set passes thickness 5 and radius 5 to pasta_pose_stickman_u8, S = 512 and boxes (35, 20) to pasta_palm_mask_u8,
+ * six_is_lower = 0 to pasta_tryon_outfit_masks_u8 and radius 2 to pasta_patch_composite_eroded_u8 for both garments.  The
+ * sources of pasta_tryon_outfit_masks_u8 by change region: full body (donor, donor), upper body (donor, person), lower body
+ * (person, donor); pasta_tryon_outfit_assemble takes the donor's photograph as upper_donor_image and fills outputs 0..8.
+ * An OUTFIT at 512 x 320 (this project's own; training/tryon_regions.py, TryOnOutfitBatchBuilder): the person wears the upper
+ * garment of one donor and the lower garment of another, either of whom may be the person; the two sources are the two
+ * donors', and all ten outputs are filled.
  * ------------------------------------------------------------------------- */
-/* pasta_pose_stickman_u8 with the line thickness t and the disc radius r as arguments.  Line: every pixel centre within
- * distance t / 2 of the segment (the capsule of half-width t / 2), in integers 4 cross^2 <= t^2 len2 along the segment and
- * 4 d^2 <= t^2 at its ends; for t = 2 that is pasta_pose_stickman_u8's rule, for t = 5 this project's restatement of cv2's
- * thick line (a polygon of half-width t / 2 with round caps in 16.16 fixed point; parity UNPINNED).  Disc:
- * (r - y)^2 + (c - x)^2 < radius^2, clipped to the canvas -- skimage's ((r - y) / R)^2 + ((c - x) / R)^2 < 1 on every integer
- * offset for R = 2 and R = 5.  1 <= thickness, radius <= 64; (2, 2) is pasta_pose_stickman_u8 bit for bit. */
-int pasta_pose_stickman_thick_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness,
-                                 int radius, void* stream);
-
-/* pasta_palm_mask_box_u8 on an S x S square (get_hand_mask :1779-1799 has h = w = 512): parsing [N, S, W], out [N, S, S];
- * S a multiple of 16, 16 <= S <= 512; 1 <= k <= S.  S = 256 is pasta_palm_mask_box_u8 bit for bit; the 512 x 320 set calls
- * it with S = 512 and boxes (35, 20), offsets -17..17 and -10..9. */
-int pasta_palm_mask_square_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S, int W,
-                              int k_upper, int k_lower, void* stream);
-
-/* :1631-1690 from the person's image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H] and the donor's image and
- * parsing: retain_img = the person's padded image * (shoes(18, 19) + palm + head(1, 2, 4, 13)); upper_img / upper_mask =
- * labels 5, 6, 7 (image, 255) and lower_img / lower_mask = labels 9, 12 of the person the region names: region 0 (full body)
- * both from the donor, 1 (upper body) upper from the donor and lower from the person, 2 (lower body) upper from the person
- * and lower from the donor.  Outputs [N, H, H, 3], padding 255 in the images before the masks are applied, 0 in the labels. */
-int pasta_tryon_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
-                                const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask,
-                                uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W, int region, void* stream);
-
-/* __getitem__ (:2196-2214) and test_512.py:115-131: nine fp32 NCHW tensors through outputs (a HOST array of 9 device
- * pointers) in this order: image, clothes [N,3,H,H] (the padded person and donor, padding 255), retain [N,3,H,H] =
- * image * mask - (1 - mask) with the 0 / 1 retain mask, which equals x / 127.5 - 1 of retain_img bit for bit (the label groups
- * are disjoint), pose [N,6,H,H] = stick || retain, style_input [N,3(P+P_lower),ph,pw] = the P upper-garment patches (channel
- * 3k + c of part k) || the P_lower lower-garment patches, denorm_upper_input / denorm_lower_input [N,3,H,H],
- * denorm_upper_mask / denorm_lower_mask [N,1,H,H] = channel sum > 0 (no wrap).  x / 127.5 - 1 as torch evaluates it on the
- * GPU: x * (1 / 127.5f) - 1.  image, donor_image [N,H,W,3]; retain_img, stick, denorm_upper, denorm_lower [N,H,H,3];
- * patches [N,P,ph,pw,3], patches_lower [N,P_lower,ph,pw,3] uint8. */
-int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image, const uint8_t* retain_img, const uint8_t* stick,
-                                const uint8_t* patches, const uint8_t* patches_lower, const uint8_t* denorm_upper,
-                                const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw,
-                                void* stream);
-
-/* An OUTFIT at 512 x 320 (this project's own; training/tryon_regions.py, TryOnOutfitBatchBuilder): the person wears the upper
- * garment of one donor and the lower garment of another, either of whom may be the person.  pasta_tryon_region_masks_u8's
- * rules with a source per garment: retain_img = the person's padded image * (shoes(18, 19) + palm + head(1, 2, 4, 13)), always
- * the person's; upper_img / upper_mask = labels 5, 6, 7 (image, 255) of (upper_image, upper_parsing); lower_img / lower_mask =
- * labels 9, 12 of (lower_image, lower_parsing).  Sources [N, H, W, 3] and [N, H, W] like the person's, and they may be the
- * person's own pointers; outputs [N, H, H, 3], padding 255 in the images before the masks are applied, 0 in the labels.  With
- * both sources the donor's it is region 0 of pasta_tryon_region_masks_u8 bit for bit, with (donor, person) region 1, with
- * (person, donor) region 2. */
-int pasta_tryon_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
-                                const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
-                                uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img, uint8_t* lower_mask,
-                                int N, int H, int W, void* stream);
-
-/* pasta_tryon_region_assemble for an outfit: ten fp32 NCHW tensors through outputs (a HOST array of 10 device pointers), the
- * nine of pasta_tryon_region_assemble in its order with clothes = the padded upper_donor_image, then clothes_lower [N,3,H,H] =
- * the padded lower_donor_image (padding 255, x / 127.5 - 1).  Inputs as there; lower_donor_image [N,H,W,3]. */
-int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor_image, const uint8_t* lower_donor_image,
-                                const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* patches_lower,
-                                const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W,
-                                int P, int P_lower, int ph, int pw, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the 512 x 320 try-on TRAINING samples (training/tryon_regions.py, FullBodyRegionBatchBuilder).
@@ -709,7 +663,7 @@ int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor
  * trained on exactly the inputs test_512.py will later feed it.  A sample is the entries' above full-body preparation of the
  * pair (person, person), with the 256 training set's three extras on top:
  *   1. stick figure of thickness 5 and radius 5 from the unshifted key points, palm boxes 35 and 20 on the 512 square
- *      (pasta_pose_stickman_thick_u8, pasta_palm_mask_square_u8);
+ *      (pasta_pose_stickman_u8, pasta_palm_mask_u8);
  *   2. the upper garment is labels 5, 6, 7 and the lower garment labels 9, 12, both the person's own;
  *   3. key points are shifted by the padding in float64 (host side), get_crop has no knee-without-ankle fall-back;
  *   4. all ten parts of the upper garment, parts 0, 6, 7, 8, 9 of the lower one; every warped-back mask is eroded 5 x 5
@@ -720,20 +674,12 @@ int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor
  *      makes at 256), resize the restated cv2.resize of pasta_tryon_assemble;
  *   7. the two denormalised inputs are zeroed where erase is 1 before x / 127.5 - 1, their masks are the channel sum > 0 of
  *      the erased image.
+ * Retain mask, gt_parsing and both garments (rules 2 and 5) are pasta_tryon_masks_u8's: the two training sets name the same
+ * labels.
  * ------------------------------------------------------------------------- */
-/* From the person's image [N, H, W, 3], parsing [N, H, W] (unpadded) and palm [N, H, H], in one pass: retain_mask = shoes(18,
- * 19) + palm + head(1, 2, 4, 13) (0 / 1) and gt_parsing = upper(5, 6, 7) + 2 lower(9, 12) + 3 hands(14, 15) + 4 legs(16, 17) +
- * 5 neck(10), [N, H, H]; upper_img / upper_mask = labels 5, 6, 7 (image, 255) and lower_img / lower_mask = labels 9, 12,
- * [N, H, H, 3], padding 255 in the images before the masks are applied.  The four garment pointers are the halves of the
- * stacked [2N, H, H, 3] image and mask tensors patch_pipeline.normalize_region_batch takes (upper garments, then lower).
- * These are pasta_tryon_masks_u8's rules: the two training sets name the same labels, and the entry is its launch. */
-int pasta_tryon_train_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain_mask,
-                                      uint8_t* gt_parsing, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                                      uint8_t* lower_mask, int N, int H, int W, void* stream);
-
 /* Rules 5-7 and the float conversions: the nine fp32 NCHW tensors of FullBodyBatch.KEYS, in that order, through outputs (a
  * HOST array of 9 device pointers), shaped as pasta_tryon_assemble's with style_input [N,3(P+P_lower),ph,pw] = the P
- * upper-garment patches (channel 3k + c of part k) || the P_lower lower-garment patches, as pasta_tryon_region_assemble
+ * upper-garment patches (channel 3k + c of part k) || the P_lower lower-garment patches, as pasta_tryon_outfit_assemble
  * forms it.  image [N,H,W,3]; stick, denorm_upper, denorm_lower [N,H,H,3]; retain_mask, gt_parsing [N,H,H];
  * patches [N,P,ph,pw,3], patches_lower [N,P_lower,ph,pw,3]; part_masks [N,P,H,H]: the eroded 0 / 1 part masks of the upper
  * composite, of which planes arm_a and arm_b (4 and 5: arm[2] and arm[3]) enter the erase mask; erase_masks

@@ -17,7 +17,6 @@ __device__ __forceinline__ double tr_rounded(double x) { __asm__ volatile("" : "
 
 // ---- palm mask ----
 
-constexpr int PALM_S = 256;         // get_hand_mask of the 256 x 192 sets works on a 256 x 256 square
 constexpr int PALM_S_MAX = 512;     // the largest square (one thread per column; the 512 x 320 set's 512 x 512)
 constexpr int PALM_BAND = 16;       // output rows per block
 constexpr int PALM_SEGS = 4;        // left upper arm, left forearm, right upper arm, right forearm

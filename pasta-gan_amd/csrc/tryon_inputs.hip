@@ -1,16 +1,15 @@
-// Per-sample preparation of the try-on data set on the GPU (row f4, the part of UvitonDatasetFull._load_raw_image /
+// Per-sample preparation of the try-on data sets on the GPU (row f4, the part of UvitonDatasetFull._load_raw_image /
 // __getitem__ and of the training loop's float conversions that is not the body-part warps of csrc/patches.hip):
-//   pasta_pose_stickman_u8  the pose stick figure (draw_pose_from_cords, dataset.py:704-736), padded; the line thickness and the
-//                           disc radius are arguments of pasta_pose_stickman_thick_u8 (2 and 2 here, 5 and 5 at 512 x 320);
-//   pasta_palm_mask_u8      the palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702): boxes 25 and 16 of
-//                           csrc/tryon_pairs.hip's kernel;
-//   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556);
+//   pasta_pose_stickman_u8  the pose stick figure (draw_pose_from_cords, dataset.py:704-736), padded, with the line thickness and
+//                           the disc radius as arguments: every data set's (2 and 2 at 256 x 192, 5 and 5 at 512 x 320);
+//   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556) of both training sets;
 //   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456); its
 //                           per-pixel body is csrc/tryon_common.h's train_pixel (the erase rule with the restated resize, then
 //                           tryon_pixel), shared with the 512 x 320 training kernel of csrc/tryon_pairs.hip.
-// Every entry does a whole batch in one launch.  The reference does this on the host with OpenCV, pycocotools and skimage.
-// What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
-// DESIGN.md section 9): cv2.line(thickness=2), pycocotools' rleFrPoly and cv2.resize(INTER_LINEAR) on uint8.
+// The palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702) is csrc/tryon_pairs.hip's pasta_palm_mask_u8.
+// Every entry is its checks and one launch for a whole batch.  The reference does this on the host with OpenCV, pycocotools and
+// skimage.  What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
+// DESIGN.md section 9): cv2.line(thickness), pycocotools' rleFrPoly and cv2.resize(INTER_LINEAR) on uint8.
 #include "common.h"
 #include "tryon_common.h"
 
@@ -117,26 +116,17 @@ __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __re
 
 }  // namespace pasta
 
-extern "C" int pasta_pose_stickman_thick_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness,
-                                            int radius, void* stream) {
+extern "C" int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness, int radius,
+                                      void* stream) {
     using namespace pasta;
-    PASTA_CHECK(limbs && joints && out, "pose_stickman_thick_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "pose_stickman_thick_u8: bad shape");
-    PASTA_CHECK(thickness >= 1 && thickness <= 64 && radius >= 1 && radius <= 64, "pose_stickman_thick_u8: thickness %d, radius %d (1..64)",
+    PASTA_CHECK(limbs && joints && out, "pose_stickman_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "pose_stickman_u8: bad shape");
+    PASTA_CHECK(thickness >= 1 && thickness <= 64 && radius >= 1 && radius <= 64, "pose_stickman_u8: thickness %d, radius %d (1..64)",
                 thickness, radius);
     dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
     hipLaunchKernelGGL(pose_stickman_kernel, grid, dim3(256), 0, (hipStream_t)stream, limbs, joints, out, H, W, (H - W) / 2,
                        thickness * thickness, radius * radius);
-    return launch_status("pose_stickman_thick_u8");
-}
-
-extern "C" int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, void* stream) {
-    return pasta_pose_stickman_thick_u8(limbs, joints, out, N, H, W, 2, 2, stream);
-}
-
-extern "C" int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H,
-                                  int W, void* stream) {
-    return pasta_palm_mask_box_u8(parsing, quads, present, out, N, H, W, 25, 16, stream);      // offsets -12..12 and -8..7
+    return launch_status("pose_stickman_u8");
 }
 
 extern "C" int pasta_tryon_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain, uint8_t* gt_parsing,

@@ -1,40 +1,27 @@
 // Per-batch preparation of both sets of try-on TEST pairs on the GPU (row f4), which the reference runs per sample on the host
-// in four loader processes with OpenCV, pycocotools and skimage.  The 256 x 192 pairs (UvitonDatasetV19_test._load_raw_image /
-// normalize / __getitem__, training/dataset.py:1085-1525, and test.py:104-150):
-//   pasta_palm_mask_box_u8           the palm mask with both box sizes as arguments (25 / 15 here, :1240-1253), and
-//                                    pasta_palm_mask_square_u8 with the side of the square as well (512 for the 512 x 320 set);
-//   pasta_tryon_pair_masks_u8        retain image, the person's lower garment and the donor's upper garment (:1105-1141);
-//   pasta_patch_composite_eroded_u8  the warp-back composite with cv2.erode(5 x 5) of the mask before the == 255 test
-//                                    (:1480-1492);
-//   pasta_patch_composite_radii_u8   that composite with a radius per sample in one launch: 0, the plain composite, for a
-//                                    person's own lower garment and 2 for another's (the 256 OUTFITS, this project's own);
-//   pasta_tryon_pair_outfit_masks_u8 pasta_tryon_pair_masks_u8's rules with a source of its own for each garment (the same);
-//   pasta_tryon_pair_assemble        __getitem__ (:1502-1525) and test.py's conversions (:104-117) into the seven fp32 tensors;
-//   pasta_images_to_u8               test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137).
-// The 512 x 320 pairs with a change region (UvitonDatasetFull_512_test._load_raw_image / normalize_full / normalize_upper /
-// normalize_lower / __getitem__, :1528-2214, and test_512.py:115-131):
-//   pasta_tryon_region_masks_u8      retain image and the upper and lower garment, each taken from the donor or the person as
-//                                    the region says (:1631-1690);
-//   pasta_tryon_region_assemble      __getitem__ (:2196-2214) and test_512.py's conversions (:115-131) into the nine fp32 tensors.
-// The 512 x 320 OUTFITS (this project's own: a person, an upper garment and a lower garment from up to three people; a pair
-// with a region is the outfit whose two sources are the donor or the person):
-//   pasta_tryon_outfit_masks_u8      the region entry's rules with a source of its own for each garment;
-//   pasta_tryon_outfit_assemble      the nine tensors and clothes_lower, the lower garment's donor.
-// The 512 x 320 TRAINING samples (this project's own: the reference ships no 512 training set) are that set's full-body
-// preparation of the pair (person, person) with the 256 training set's photograph, gt_parsing and erase mask on top:
-//   pasta_tryon_train_region_masks_u8  retain mask, gt_parsing and both garments of the person, in the stacked [2N] layout
-//                                      normalize_region_batch takes (csrc/tryon_inputs.hip's label-masks launch: the two
-//                                      training sets name the same labels);
-//   pasta_tryon_train_region_assemble  the erase mask from two eroded arm-part masks and the nine fp32 tensors of the loop.
-// Every masks entry launches tryon_pair_masks_kernel and every assemble entry tryon_pair_assemble_kernel: the 256 pairs are
-// the 512 rules with "upper from the donor, lower from the person" fixed, label 6 added to the lower garment, stick patches as
-// the second patch list and no image / clothes tensors.  Sources and the label-6 flag are kernel arguments, uniform per launch.
-// The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures tryon_inputs.hip's stick-figure
-// entries (thickness 2, radius 2 at 256; 5 and 5 at 512, whose palm boxes are 35 and 20 and whose composites are both eroded).
-// Where the 256 test set differs from the training preparation (the six rules of include/pasta_hip.h): two people (the
-// donor's upper garment with the donor's key points, the person's lower garment with the person's), the person's M_inv for
-// every part, an eroded mask for parts 0-5, a 15 x 15 forearm box, lower garment = labels 6, 9, 12, and key points shifted by
-// the padding in float64 on the host.  Every entry does a whole batch in one launch.
+// in four loader processes with OpenCV, pycocotools and skimage: the 256 x 192 pairs (UvitonDatasetV19_test._load_raw_image /
+// normalize / __getitem__, training/dataset.py:1085-1525, and test.py:104-150) and the 512 x 320 pairs with a change region
+// (UvitonDatasetFull_512_test._load_raw_image / normalize_full / normalize_upper / normalize_lower / __getitem__, :1528-2214,
+// and test_512.py:115-131).  The same entries prepare the OUTFITS of both sizes (this
+// project's own: a person, an upper garment and a lower garment from up to three people; a pair with a region is the outfit
+// whose two sources are the donor or the person) and the 512 x 320 TRAINING samples (this project's own as well).  One entry
+// per kernel, each its checks and one launch for a whole batch:
+//   pasta_palm_mask_u8                 the palm mask on an S x S square with both box sizes as arguments (:1240-1253,
+//                                      :1779-1799): every data set's, the two training sets included;
+//   pasta_tryon_outfit_masks_u8        retain image, upper and lower garment with a source of its own for each garment
+//                                      (:1105-1141, :1631-1690); six_is_lower: label 6 belongs to the lower garment (256 x 192);
+//   pasta_patch_composite_eroded_u8    the warp-back composite with cv2.erode of the mask before the == 255 test (:1480-1492),
+//                                      by one radius or by a radius per sample (0, the plain composite, for a person's own
+//                                      lower garment and 2 for another's in the 256 outfits);
+//   pasta_tryon_outfit_assemble        __getitem__ and the scripts' conversions (:1502-1525 and test.py:104-117; :2196-2214 and
+//                                      test_512.py:115-131) into the seven fp32 tensors G takes, with image and clothes nine,
+//                                      with clothes_lower (the lower garment's donor) ten;
+//   pasta_tryon_train_region_assemble  the erase mask from two eroded arm-part masks and the nine fp32 tensors of the loop at
+//                                      512 x 320 (the label masks of that set are csrc/tryon_inputs.hip's pasta_tryon_masks_u8);
+//   pasta_images_to_u8                 test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137).
+// The 256 pairs are the 512 rules with label 6 added to the lower garment, stick patches as the second patch list and no image /
+// clothes tensors.  The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures
+// csrc/tryon_inputs.hip's entry.  include/pasta_hip.h lists where the data sets differ and the constants each one passes.
 #include "common.h"
 #include "tryon_common.h"
 
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(256) void tryon_pair_masks_kernel(const uint8_t* __
 // ---- eroded composite ----
 
 // The tile work is csrc/patch_erode.h's (shared with the snapshot grid's indexed composite); here part k of sample n is item n * P + k.
-// The one kernel of both entries: sample n is eroded by radius[n], or by r where radius is null.  A block works on one sample, so
+// Sample n is eroded by radius[n], or by r where radius is null.  A block works on one sample, so
 // its radius is uniform across the block; a value above ER_MAX_R (the entry's callers check theirs on the host) is taken as
 // ER_MAX_R, what the LDS tiles hold.
 __global__ __launch_bounds__(256) void patch_composite_eroded_kernel(const uint8_t* __restrict__ patches, const uint8_t* __restrict__ masks,
@@ -201,192 +188,72 @@ __global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restri
 
 }  // namespace pasta
 
-extern "C" int pasta_palm_mask_square_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S,
-                                         int W, int k_upper, int k_lower, void* stream) {
+extern "C" int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S, int W,
+                                  int k_upper, int k_lower, void* stream) {
     using namespace pasta;
-    PASTA_CHECK(parsing && quads && present && out, "palm_mask_square_u8: null pointer");
+    PASTA_CHECK(parsing && quads && present && out, "palm_mask_u8: null pointer");
     PASTA_CHECK(N >= 1 && N <= 65535 && S >= PALM_BAND && S <= PALM_S_MAX && S % PALM_BAND == 0 && W >= 1 && W <= S,
-                "palm_mask_square_u8: bad shape (the padded square: a multiple of %d up to %d)", PALM_BAND, PALM_S_MAX);
-    PASTA_CHECK(k_upper >= 1 && k_upper <= S && k_lower >= 1 && k_lower <= S, "palm_mask_square_u8: box sizes %d, %d (1..%d)", k_upper,
-                k_lower, S);
+                "palm_mask_u8: bad shape (the padded square: a multiple of %d up to %d)", PALM_BAND, PALM_S_MAX);
+    PASTA_CHECK(k_upper >= 1 && k_upper <= S && k_lower >= 1 && k_lower <= S, "palm_mask_u8: box sizes %d, %d (1..%d)", k_upper, k_lower, S);
     dim3 grid((unsigned)(S / PALM_BAND), (unsigned)N);
     hipLaunchKernelGGL(palm_mask_box_kernel, grid, dim3(S), (size_t)PALM_SEGS * S * 4 * sizeof(int16_t), (hipStream_t)stream, parsing, quads,
                        present, out, S, W, (S - W) / 2, k_upper, k_lower);
-    return launch_status("palm_mask_square_u8");
-}
-
-extern "C" int pasta_palm_mask_box_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int H,
-                                      int W, int k_upper, int k_lower, void* stream) {
-    using namespace pasta;
-    PASTA_CHECK(H == PALM_S, "palm_mask_box_u8: bad shape (the padded square is 256 x 256)");
-    return pasta_palm_mask_square_u8(parsing, quads, present, out, N, H, W, k_upper, k_lower, stream);
-}
-
-// The label-masks entries, `what` naming the caller in the error texts.  pair_masks_args: the checks all four share.
-static int pair_masks_args(const char* what, bool pointers, int N, int H, int W) {
-    PASTA_CHECK(pointers, "%s: null pointer", what);
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "%s: bad shape", what);
-    return 0;
-}
-
-static int launch_pair_masks(const char* what, const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
-                             const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing, uint8_t* retain_img,
-                             uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W,
-                             int six_is_lower, void* stream) {
-    using namespace pasta;
-    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, upper_image, upper_parsing,
-                       lower_image, lower_parsing, retain_img, upper_img, upper_mask, lower_img, lower_mask, H, W, (H - W) / 2, six_is_lower);
-    return launch_status(what);
-}
-
-// One donor and a region: the 512 x 320 entry passes its region and no label 6, the 256 x 192 one the constant region 1 (upper
-// garment from the donor, lower from the person) with label 6 in the lower garment.  Each garment's source is the donor's
-// pointers or the person's.
-static int launch_region_masks(const char* what, const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
-                               const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                               uint8_t* lower_mask, int N, int H, int W, int region, int six_is_lower, void* stream) {
-    if (const int rc = pair_masks_args(what, image && parsing && palm && donor_image && donor_parsing && retain_img && upper_img && upper_mask &&
-                                                 lower_img && lower_mask, N, H, W))
-        return rc;
-    PASTA_CHECK(region >= 0 && region <= 2, "%s: region %d (0 full body, 1 upper body, 2 lower body)", what, region);
-    const bool upper_donor = region != 2, lower_donor = region != 1;
-    return launch_pair_masks(what, image, parsing, palm, upper_donor ? donor_image : image, upper_donor ? donor_parsing : parsing,
-                             lower_donor ? donor_image : image, lower_donor ? donor_parsing : parsing, retain_img, upper_img, upper_mask,
-                             lower_img, lower_mask, N, H, W, six_is_lower, stream);
-}
-
-extern "C" int pasta_tryon_pair_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
-                                         const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* lower_img, uint8_t* lower_mask,
-                                         uint8_t* upper_img, uint8_t* upper_mask, int N, int H, int W, void* stream) {
-    return launch_region_masks("tryon_pair_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
-                               lower_img, lower_mask, N, H, W, 1, 1, stream);
-}
-
-extern "C" int pasta_tryon_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* donor_image,
-                                           const uint8_t* donor_parsing, uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask,
-                                           uint8_t* lower_img, uint8_t* lower_mask, int N, int H, int W, int region, void* stream) {
-    return launch_region_masks("tryon_region_masks_u8", image, parsing, palm, donor_image, donor_parsing, retain_img, upper_img, upper_mask,
-                               lower_img, lower_mask, N, H, W, region, 0, stream);
+    return launch_status("palm_mask_u8");
 }
 
 extern "C" int pasta_tryon_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
                                            const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
                                            uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                                           uint8_t* lower_mask, int N, int H, int W, void* stream) {
-    if (const int rc = pair_masks_args("tryon_outfit_masks_u8", image && parsing && palm && upper_image && upper_parsing && lower_image &&
-                                                                    lower_parsing && retain_img && upper_img && upper_mask && lower_img &&
-                                                                    lower_mask, N, H, W))
-        return rc;
-    return launch_pair_masks("tryon_outfit_masks_u8", image, parsing, palm, upper_image, upper_parsing, lower_image, lower_parsing, retain_img,
-                             upper_img, upper_mask, lower_img, lower_mask, N, H, W, 0, stream);
-}
-
-extern "C" int pasta_tryon_pair_outfit_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, const uint8_t* upper_image,
-                                                const uint8_t* upper_parsing, const uint8_t* lower_image, const uint8_t* lower_parsing,
-                                                uint8_t* retain_img, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                                                uint8_t* lower_mask, int N, int H, int W, void* stream) {
-    if (const int rc = pair_masks_args("tryon_pair_outfit_masks_u8", image && parsing && palm && upper_image && upper_parsing && lower_image &&
-                                                                         lower_parsing && retain_img && upper_img && upper_mask && lower_img &&
-                                                                         lower_mask, N, H, W))
-        return rc;
-    return launch_pair_masks("tryon_pair_outfit_masks_u8", image, parsing, palm, upper_image, upper_parsing, lower_image, lower_parsing,
-                             retain_img, upper_img, upper_mask, lower_img, lower_mask, N, H, W, 1, stream);
-}
-
-// Both eroded composites: `radius` [N] on the device, or null and the scalar r for every sample.
-static int launch_composite_eroded(const char* what, const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
-                                   uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, const uint8_t* radius, int r,
-                                   void* stream) {
+                                           uint8_t* lower_mask, int N, int H, int W, int six_is_lower, void* stream) {
     using namespace pasta;
-    PASTA_CHECK(patches && masks && minv && valid && out, "%s: null pointer", what);
-    PASTA_CHECK(N >= 1 && N <= 65535 && P >= 1 && ph >= 1 && pw >= 1 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096, "%s: bad shape", what);
-    PASTA_CHECK(r >= 0 && r <= ER_MAX_R, "%s: radius %d (0..%d)", what, r, ER_MAX_R);
-    const int tiles_x = (W + ER_T - 1) / ER_T, tiles_y = (H + ER_T - 1) / ER_T;
-    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
-    hipLaunchKernelGGL(patch_composite_eroded_kernel, grid, dim3(256), 0, (hipStream_t)stream, patches, masks, minv, valid, out, part_mask, P,
-                       ph, pw, H, W, radius, r, tiles_x);
-    return launch_status(what);
+    PASTA_CHECK(image && parsing && palm && upper_image && upper_parsing && lower_image && lower_parsing && retain_img && upper_img &&
+                upper_mask && lower_img && lower_mask, "tryon_outfit_masks_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "tryon_outfit_masks_u8: bad shape");
+    PASTA_CHECK(six_is_lower == 0 || six_is_lower == 1, "tryon_outfit_masks_u8: six_is_lower %d (0 or 1)", six_is_lower);
+    dim3 grid((unsigned)((H * H + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_masks_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, palm, upper_image, upper_parsing,
+                       lower_image, lower_parsing, retain_img, upper_img, upper_mask, lower_img, lower_mask, H, W, (H - W) / 2, six_is_lower);
+    return launch_status("tryon_outfit_masks_u8");
 }
 
 extern "C" int pasta_patch_composite_eroded_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
                                                uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, int radius,
-                                               void* stream) {
-    return launch_composite_eroded("patch_composite_eroded_u8", patches, masks, minv, valid, out, part_mask, N, P, ph, pw, H, W, nullptr, radius,
-                                   stream);
-}
-
-extern "C" int pasta_patch_composite_radii_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
-                                              uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W,
-                                              const uint8_t* radius, void* stream) {
-    PASTA_CHECK(radius, "patch_composite_radii_u8: null pointer");
-    return launch_composite_eroded("patch_composite_radii_u8", patches, masks, minv, valid, out, part_mask, N, P, ph, pw, H, W, radius, 0,
-                                   stream);
-}
-
-extern "C" int pasta_tryon_pair_assemble(const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* stick_patches,
-                                         const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int N, int H, int P,
-                                         int ph, int pw, void* stream) {
+                                               const uint8_t* radii, void* stream) {
     using namespace pasta;
-    PASTA_CHECK(retain_img && stick && patches && stick_patches && denorm_upper && denorm_lower && outputs, "tryon_pair_assemble: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && P >= 1 && P <= 64 && ph >= 1 && pw >= 1 && ph * pw <= H * H,
-                "tryon_pair_assemble: bad shape");
-    TryonOut o{};                   // image and clothes stay null: not written, and no photograph is read
-    float** f[7] = {&o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask, &o.denorm_lower_mask};
-    const int missing = take_outputs(outputs, f, 7);
-    PASTA_CHECK(missing < 0, "tryon_pair_assemble: output %d is null", missing);
-    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)nullptr, (const uint8_t*)nullptr,
-                       (const uint8_t*)nullptr, retain_img, stick, patches, stick_patches, denorm_upper, denorm_lower, o, H, H, 0, P, P, ph, pw);
-    return launch_status("tryon_pair_assemble");
-}
-
-// Both 512 x 320 assemble entries: `count` outputs, nine for a pair (lower_donor_image null) and `clothes_lower` as the tenth
-// for an outfit.
-static int launch_region_assemble(const char* what, const uint8_t* image, const uint8_t* donor_image, const uint8_t* lower_donor_image,
-                                  const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches, const uint8_t* patches_lower,
-                                  const uint8_t* denorm_upper, const uint8_t* denorm_lower, float* const* outputs, int count, int N, int H,
-                                  int W, int P, int P_lower, int ph, int pw, void* stream) {
-    using namespace pasta;
-    PASTA_CHECK(image && donor_image && (count == 9 || lower_donor_image) && retain_img && stick && patches && patches_lower && denorm_upper &&
-                denorm_lower && outputs, "%s: null pointer", what);
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && P >= 1 && P <= 64 && P_lower >= 1 && P_lower <= 64 &&
-                ph >= 1 && pw >= 1 && ph * pw <= H * H, "%s: bad shape", what);
-    TryonOut o{};
-    float** f[10] = {&o.image, &o.clothes, &o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input,
-                     &o.denorm_upper_mask, &o.denorm_lower_mask, &o.clothes_lower};
-    const int missing = take_outputs(outputs, f, count);
-    PASTA_CHECK(missing < 0, "%s: output %d is null", what, missing);
-    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, donor_image, lower_donor_image, retain_img,
-                       stick, patches, patches_lower, denorm_upper, denorm_lower, o, H, W, (H - W) / 2, P, P_lower, ph, pw);
-    return launch_status(what);
-}
-
-extern "C" int pasta_tryon_region_assemble(const uint8_t* image, const uint8_t* donor_image, const uint8_t* retain_img, const uint8_t* stick,
-                                           const uint8_t* patches, const uint8_t* patches_lower, const uint8_t* denorm_upper,
-                                           const uint8_t* denorm_lower, float* const* outputs, int N, int H, int W, int P, int P_lower, int ph,
-                                           int pw, void* stream) {
-    return launch_region_assemble("tryon_region_assemble", image, donor_image, nullptr, retain_img, stick, patches, patches_lower, denorm_upper,
-                                  denorm_lower, outputs, 9, N, H, W, P, P_lower, ph, pw, stream);
+    PASTA_CHECK(patches && masks && minv && valid && out, "patch_composite_eroded_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && P >= 1 && ph >= 1 && pw >= 1 && H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
+                "patch_composite_eroded_u8: bad shape");
+    PASTA_CHECK(radii || (radius >= 0 && radius <= ER_MAX_R), "patch_composite_eroded_u8: radius %d (0..%d)", radius, ER_MAX_R);
+    const int tiles_x = (W + ER_T - 1) / ER_T, tiles_y = (H + ER_T - 1) / ER_T;
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
+    hipLaunchKernelGGL(patch_composite_eroded_kernel, grid, dim3(256), 0, (hipStream_t)stream, patches, masks, minv, valid, out, part_mask, P,
+                       ph, pw, H, W, radii, radius, tiles_x);
+    return launch_status("patch_composite_eroded_u8");
 }
 
 extern "C" int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor_image, const uint8_t* lower_donor_image,
                                            const uint8_t* retain_img, const uint8_t* stick, const uint8_t* patches,
                                            const uint8_t* patches_lower, const uint8_t* denorm_upper, const uint8_t* denorm_lower,
                                            float* const* outputs, int N, int H, int W, int P, int P_lower, int ph, int pw, void* stream) {
-    return launch_region_assemble("tryon_outfit_assemble", image, upper_donor_image, lower_donor_image, retain_img, stick, patches,
-                                  patches_lower, denorm_upper, denorm_lower, outputs, 10, N, H, W, P, P_lower, ph, pw, stream);
-}
-
-extern "C" int pasta_tryon_train_region_masks_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* palm, uint8_t* retain_mask,
-                                                 uint8_t* gt_parsing, uint8_t* upper_img, uint8_t* upper_mask, uint8_t* lower_img,
-                                                 uint8_t* lower_mask, int N, int H, int W, void* stream) {
-    PASTA_CHECK(image && parsing && palm && retain_mask && gt_parsing && upper_img && upper_mask && lower_img && lower_mask,
-                "tryon_train_region_masks_u8: null pointer");
-    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H, "tryon_train_region_masks_u8: bad shape");
-    // the 256 training set's rules for all six outputs (labels 5, 6, 7 and 9, 12; no label 6 in the lower garment): its launch
-    return pasta_tryon_masks_u8(image, parsing, palm, retain_mask, gt_parsing, upper_img, lower_img, upper_mask, lower_mask, N, H, W, stream);
+    using namespace pasta;
+    PASTA_CHECK(retain_img && stick && patches && patches_lower && denorm_upper && denorm_lower && outputs, "tryon_outfit_assemble: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && W >= 1 && W <= H && P >= 1 && P <= 64 && P_lower >= 1 && P_lower <= 64 &&
+                ph >= 1 && pw >= 1 && ph * pw <= H * H, "tryon_outfit_assemble: bad shape");
+    TryonOut o{};
+    float** f[7] = {&o.retain, &o.pose, &o.style_input, &o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask, &o.denorm_lower_mask};
+    const int missing = take_outputs(outputs + 2, f, 7);
+    PASTA_CHECK(missing < 0, "tryon_outfit_assemble: output %d is null", missing + 2);
+    // image, clothes and clothes_lower may be null: a null tensor is not written and its photograph is not read.  The kernel
+    // writes the photographs' tensors under `if (o.image)`, so clothes comes with image and clothes_lower only with both.
+    o.image = outputs[0], o.clothes = outputs[1], o.clothes_lower = outputs[9];
+    PASTA_CHECK(!o.image == !o.clothes && (o.image || !o.clothes_lower),
+                "tryon_outfit_assemble: outputs 0 and 1 (image, clothes) are null together or not at all, and output 9 needs them");
+    PASTA_CHECK((!o.image || (image && upper_donor_image)) && (!o.clothes_lower || lower_donor_image),
+                "tryon_outfit_assemble: null photograph of a requested output");
+    dim3 grid((unsigned)((H * H + ph * pw + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL(tryon_pair_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, image, upper_donor_image, lower_donor_image, retain_img,
+                       stick, patches, patches_lower, denorm_upper, denorm_lower, o, H, W, (H - W) / 2, P, P_lower, ph, pw);
+    return launch_status("tryon_outfit_assemble");
 }
 
 extern "C" int pasta_tryon_train_region_assemble(const uint8_t* image, const uint8_t* stick, const uint8_t* retain_mask,

@@ -2,7 +2,7 @@
 
 Three regions of every output have a known answer, so they need no detector network:
 
-    keep     head, palms and shoes -- the pixels ``retain`` carries (``pasta_tryon_pair_masks_u8``'s mask: palm != 0 or the
+    keep     head, palms and shoes -- the pixels ``retain`` carries (``pasta_tryon_outfit_masks_u8``'s mask: palm != 0 or the
              person's label in KEEP_LABELS) -- against the person's photograph;
     upper    where the donor's upper-garment patches were warped onto the person (``denorm_upper_mask``) against those
              warped patches (stage ``denorm_upper``);
@@ -75,7 +75,7 @@ def finish(partials, prefix, pixels=PIXELS):
 #----------------------------------------------------------------------------
 
 def keep_mask(stages):
-    """uint8 [N, H, W]: the content columns of the mask ``pasta_tryon_pair_masks_u8`` multiplies ``retain_img`` with."""
+    """uint8 [N, H, W]: the content columns of the mask ``pasta_tryon_outfit_masks_u8`` multiplies ``retain_img`` with."""
     parsing, palm = stages['parsing'], stages['palm']
     H, W = int(parsing.shape[1]), int(parsing.shape[2])
     c0 = (H - W) // 2

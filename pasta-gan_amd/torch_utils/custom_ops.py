@@ -30,7 +30,7 @@ _LIBDIR = os.path.join(_ROOT, 'lib')
 _OBJDIR = os.path.join(_ROOT, 'build')
 _INCLUDE = os.path.join(os.path.dirname(_ROOT), 'include')
 LIB_NAME = 'libpasta_hip.so'
-EXPECTED_ABI = 21                   # PASTA_ABI_VERSION of include/pasta_hip.h = pasta_abi_version() of csrc/common.hip
+EXPECTED_ABI = 22                   # pasta_abi_version() of include/pasta_hip.h and csrc/common.hip
 ARCH = 'gfx950'
 
 # The kernels as the planners name them: PASTA_FWD_* (pasta_conv2d_plan) and PASTA_WGRAD_* (pasta_conv2d_wgrad_plan) of include/pasta_hip.h
@@ -221,24 +221,14 @@ ABI = {
     'pasta_nan_to_num_multi': (ctypes.c_int, [ctypes.POINTER(_c_ptr), ctypes.POINTER(_c_i64), ctypes.c_int, _c_f32, _c_f32, _c_f32, _c_ptr]),
     'pasta_warp_perspective_u8': (ctypes.c_int, [_c_ptr] * 5 + [ctypes.c_int] * 7 + [_c_ptr]),
     'pasta_patch_composite_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 6 + [_c_ptr]),
-    'pasta_pose_stickman_u8': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 3 + [_c_ptr]),
-    'pasta_palm_mask_u8': (ctypes.c_int, [_c_ptr] * 4 + [ctypes.c_int] * 3 + [_c_ptr]),
+    'pasta_pose_stickman_u8': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 5 + [_c_ptr]),
+    'pasta_palm_mask_u8': (ctypes.c_int, [_c_ptr] * 4 + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_tryon_masks_u8': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 3 + [_c_ptr]),
     'pasta_tryon_assemble': (ctypes.c_int, [_c_ptr] * 11 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 9 + [_c_ptr]),
-    'pasta_palm_mask_box_u8': (ctypes.c_int, [_c_ptr] * 4 + [ctypes.c_int] * 5 + [_c_ptr]),
-    'pasta_tryon_pair_masks_u8': (ctypes.c_int, [_c_ptr] * 10 + [ctypes.c_int] * 3 + [_c_ptr]),
-    'pasta_patch_composite_eroded_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 7 + [_c_ptr]),
-    'pasta_patch_composite_radii_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 6 + [_c_ptr] * 2),
-    'pasta_tryon_pair_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 3 + [_c_ptr]),
-    'pasta_tryon_pair_assemble': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 5 + [_c_ptr]),
-    'pasta_images_to_u8': (ctypes.c_int, [_c_ptr] * 2 + [ctypes.c_int] * 5 + [_c_ptr]),
-    'pasta_pose_stickman_thick_u8': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 5 + [_c_ptr]),
-    'pasta_palm_mask_square_u8': (ctypes.c_int, [_c_ptr] * 4 + [ctypes.c_int] * 5 + [_c_ptr]),
-    'pasta_tryon_region_masks_u8': (ctypes.c_int, [_c_ptr] * 10 + [ctypes.c_int] * 4 + [_c_ptr]),
-    'pasta_tryon_region_assemble': (ctypes.c_int, [_c_ptr] * 8 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 7 + [_c_ptr]),
-    'pasta_tryon_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 3 + [_c_ptr]),
+    'pasta_tryon_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 4 + [_c_ptr]),
+    'pasta_patch_composite_eroded_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 7 + [_c_ptr] * 2),
     'pasta_tryon_outfit_assemble': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 7 + [_c_ptr]),
-    'pasta_tryon_train_region_masks_u8': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 3 + [_c_ptr]),
+    'pasta_images_to_u8': (ctypes.c_int, [_c_ptr] * 2 + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_tryon_train_region_assemble': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 2 + [_c_ptr] * 2 + [ctypes.POINTER(_c_ptr)] +
                                                         [ctypes.c_int] * 9 + [_c_ptr]),
     'pasta_grid_composite_eroded_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 8 + [_c_ptr]),
@@ -251,18 +241,10 @@ ABI = {
     'pasta_region_image_stats': (ctypes.c_int, [_c_ptr] * 6 + [_c_i64] + [ctypes.c_int] * 9 + [_c_ptr]),
 }
 
-# Entries added to ABI 21 after its first release (purely additive, so the version did not move): a library built before them
-# (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.
-LATE_ENTRIES = frozenset(['pasta_grid_sample', 'pasta_grid_sample_backward_workspace', 'pasta_grid_sample_backward',
-                          'pasta_pose_stickman_u8', 'pasta_palm_mask_u8', 'pasta_tryon_masks_u8', 'pasta_tryon_assemble',
-                          'pasta_palm_mask_box_u8', 'pasta_tryon_pair_masks_u8', 'pasta_patch_composite_eroded_u8',
-                          'pasta_tryon_pair_assemble', 'pasta_images_to_u8', 'pasta_pose_stickman_thick_u8',
-                          'pasta_palm_mask_square_u8', 'pasta_tryon_region_masks_u8', 'pasta_tryon_region_assemble',
-                          'pasta_tryon_train_region_masks_u8', 'pasta_tryon_train_region_assemble',
-                          'pasta_grid_composite_eroded_u8', 'pasta_grid_assemble', 'pasta_image_grid_tile_u8',
-                          'pasta_recon_image_stats_workspace', 'pasta_recon_image_stats', 'pasta_parsing_confusion',
-                          'pasta_region_image_stats_workspace', 'pasta_region_image_stats', 'pasta_tryon_outfit_masks_u8',
-                          'pasta_tryon_outfit_assemble', 'pasta_patch_composite_radii_u8', 'pasta_tryon_pair_outfit_masks_u8'])
+# Entries added to the current ABI after its first release (purely additive, so the version did not move): a library built before
+# them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  None at 22: a
+# library that reports 22 has every symbol of ABI.
+LATE_ENTRIES = frozenset()
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

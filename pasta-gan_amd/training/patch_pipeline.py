@@ -155,7 +155,7 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
     """patch -> image (BORDER_CONSTANT) + mask test + compositing of ``patches`` / ``masks`` [N, p, h, w, 3] in order, one launch:
     index j is part ``parts[j]`` of ``back`` [N, 10, 3, 3] / ``valid`` [N, 10], the maps of the people the result is drawn on.
     ``radius`` None: pasta_patch_composite_u8, the mask tested as warped; a value: pasta_patch_composite_eroded_u8, the mask eroded
-    (2 * radius + 1) square first; a sequence [N]: pasta_patch_composite_radii_u8, sample i eroded by ``radius[i]`` (0: as warped),
+    (2 * radius + 1) square first; a sequence [N]: the same entry with its ``radii``, sample i eroded by ``radius[i]`` (0: as warped),
     still one launch.  A radius outside 0 .. 8 raises ValueError.  Returns (image uint8 [N, height, width, 3], part masks uint8
     [N, p, height, width] or None)."""
     n, p, ph, pw = patches.shape[:4]
@@ -164,7 +164,7 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
     if radius is None:
         entry, extra = lib.pasta_patch_composite_u8, ()
     elif np.ndim(radius) == 0:
-        entry, extra = lib.pasta_patch_composite_eroded_u8, (radius,)
+        entry, extra = lib.pasta_patch_composite_eroded_u8, (radius, None)
     else:
         radii = np.asarray(radius).reshape(-1)
         if radii.shape != (n,):
@@ -173,7 +173,7 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
         if len(bad):
             raise ValueError('composite: radius %d of sample %d (0..%d)' % (radii[bad[0]], bad[0], MAX_ERODE_RADIUS))
         radius_t = torch.from_numpy(radii.astype(np.uint8)).to(dev)       # held until the launch is queued
-        entry, extra = lib.pasta_patch_composite_radii_u8, (_native.ptr(radius_t),)
+        entry, extra = lib.pasta_patch_composite_eroded_u8, (0, _native.ptr(radius_t))
     inv_t = torch.from_numpy(inverse_maps(back, parts)).to(dev)
     val_t = torch.as_tensor(np.ascontiguousarray(valid[:, parts]).astype(np.uint8), device=dev)
     out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)

@@ -2,9 +2,9 @@
 ``__getitem__`` (training/dataset.py:515-568, 619-736, 929-993) and its training loop (training_loop_wo_flow_fullbody.py:425-456)
 do per sample on the host, as a few launches per batch:
 
-    pasta_pose_stickman_u8   stick figure                       (csrc/tryon_inputs.hip)
-    pasta_palm_mask_u8       palm part of the retain mask
-    pasta_tryon_masks_u8     retain mask, gt_parsing, garment images and masks
+    pasta_pose_stickman_u8   stick figure, thickness 2 and radius 2   (csrc/tryon_inputs.hip)
+    pasta_palm_mask_u8       palm part of the retain mask, boxes 25 and 16   (csrc/tryon_pairs.hip)
+    pasta_tryon_masks_u8     retain mask, gt_parsing, garment images and masks   (csrc/tryon_inputs.hip)
     patch_pipeline.normalize_batch   the ten body-part warps    (csrc/patches.hip)
     pasta_tryon_assemble     erase mask and every float conversion, into the nine tensors of SyntheticFullBodyBatch.KEYS
 
@@ -31,6 +31,9 @@ LIMBSEQ = ((2, 3), (2, 6), (3, 4), (4, 5), (6, 7), (7, 8), (2, 9), (9, 10), (10,
 ARMS = ((5, 6, 7), (2, 3, 4))       # left, right: shoulder, elbow, wrist (get_palm :683-684)
 COORD_LIMIT = 4096                  # stick-figure coordinates are clamped to +-COORD_LIMIT (integer arithmetic in the kernel)
 QUAD_LIMIT = 1e5                    # palm quadrilateral corners are clamped to +-QUAD_LIMIT
+STICK_THICKNESS = 2                 # cv2.line(..., 2) of both 256 x 192 sets (dataset.py:724, :1307)
+STICK_RADIUS = 2                    # circle(..., radius=2) (:734, :1318)
+PALM_BOXES = (25, 16)               # get_hand_mask of the training set: upper arm 25 x 25, forearm 16 x 16 (:663, :668)
 
 
 def stick_tables(keypoints):
@@ -120,12 +123,20 @@ def allocator(dtype, device):
     return lambda *shape: torch.empty(shape, dtype=dtype, device=device)
 
 
-def output_tensors(keys, n, H, style_shape, device):
+# the ten outputs of pasta_tryon_outfit_assemble in its order; the test batches' KEYS are this list or a part of it
+OUTFIT_OUTPUTS = ['image', 'clothes', 'retain', 'pose', 'style_input', 'denorm_upper_input', 'denorm_lower_input', 'denorm_upper_mask',
+                  'denorm_lower_mask', 'clothes_lower']
+
+
+def output_tensors(keys, n, H, style_shape, device, slots=None):
     """The fp32 tensors an assemble entry fills, in the order of ``keys``, and the array of their pointers: style_input
-    [n, *style_shape]; on the padded square pose has 6 planes, the masks and gt_parsing 1, every other tensor 3."""
+    [n, *style_shape]; on the padded square pose has 6 planes, the masks and gt_parsing 1, every other tensor 3.  ``slots``: the
+    entry's own output order where ``keys`` is a part of it (OUTFIT_OUTPUTS); a slot the batch has no key for is a null pointer."""
     f32, planes = allocator(torch.float32, device), dict(pose=6, denorm_upper_mask=1, denorm_lower_mask=1, gt_parsing=1)
     t = {k: f32(n, *style_shape) if k == 'style_input' else f32(n, planes.get(k, 3), H, H) for k in keys}
-    return t, (ctypes.c_void_p * len(keys))(*[t[k].data_ptr() for k in keys])
+    slots = keys if slots is None else slots
+    assert set(keys) <= set(slots)
+    return t, (ctypes.c_void_p * len(slots))(*[t[k].data_ptr() if k in t else None for k in slots])
 
 
 def shift_keypoints(keypoints, left_padding):
@@ -175,8 +186,8 @@ class FullBodyBatchBuilder:
         lib, P = _native.lib(), _native.ptr
         with torch.cuda.device(dev):
             s = _native.stream()
-            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, H, W, s))
-            _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, s))
+            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
+            _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
             _native.check(lib.pasta_tryon_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), *[P(g) for g in garments], n, H, W, s))
         norm_img, norm_lower, den_u, den_l, m_invs, hand_masks, norm_mask, norm_mask_lower = patch_pipeline.normalize_batch(
             *garments, keypoints, self.box_factor)

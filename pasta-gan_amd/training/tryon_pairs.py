@@ -2,12 +2,13 @@
 ``normalize`` / ``__getitem__`` (training/dataset.py:1085-1525) and test.py's conversions (test.py:104-117) do per sample on
 the host in four loader processes, as a few launches per batch:
 
-    pasta_pose_stickman_u8            the stick figures of the batch's people, one launch  (csrc/tryon_inputs.hip)
-    pasta_palm_mask_box_u8            the person's palm mask, boxes 25 and 15 (csrc/tryon_pairs.hip)
-    pasta_tryon_pair_outfit_masks_u8  retain image, the lower garment and the upper garment, a source per garment
+    pasta_pose_stickman_u8            the stick figures of the batch's people, thickness 2 and radius 2, one launch
+                                      (csrc/tryon_inputs.hip)
+    pasta_palm_mask_u8                the person's palm mask, boxes 25 and 15 (csrc/tryon_pairs.hip)
+    pasta_tryon_outfit_masks_u8       retain image, the lower garment (labels 6, 9, 12) and the upper garment, a source per garment
     patch_pipeline.normalize_pair_outfit_batch   three forward warps + the eroded composite and the one with a radius per
                                                  sample (csrc/patches.hip, csrc/tryon_pairs.hip)
-    pasta_tryon_pair_assemble         the seven fp32 tensors G takes
+    pasta_tryon_outfit_assemble       the seven fp32 tensors G takes (its outputs 2..8)
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
@@ -15,7 +16,7 @@ formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the s
 
 The implementation is the OUTFIT form, this project's own: a person with the upper garment of one donor and the lower garment of
 another (``training.dataset.UvitonOutfits_256_test``, ``collate_outfits``; include/pasta_hip.h lists the rules).  The lower
-composite erodes a sample's masks 5 x 5 exactly where the lower garment is somebody else's (pasta_patch_composite_radii_u8); the
+composite erodes a sample's masks 5 x 5 exactly where the lower garment is somebody else's (pasta_patch_composite_eroded_u8's radii); the
 batch's distinct people are uploaded once, drawn once and their matrices solved once.  ``TryOnPairOutfitBatchBuilder`` is that
 body; the reference's pair (P, D) is the outfit (P, D, -), and ``TryOnPairBatchBuilder`` is the same body behind
 ``training.dataset.pairs_batch_as_outfits``.  Lower-body and full-body try-on are (P, -, D) and (P, D, D)."""
@@ -26,9 +27,11 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import pairs_batch_as_outfits
-from training.tryon_batch import allocator, device_tables, output_tensors, shift_keypoints, upload_images, upload_person
+from training.tryon_batch import (OUTFIT_OUTPUTS, STICK_RADIUS, STICK_THICKNESS, allocator, device_tables, output_tensors, shift_keypoints,
+                                  upload_images, upload_person)
 
 PALM_BOXES = (25, 15)       # get_hand_mask of the test set: upper arm 25 x 25, forearm 15 x 15 (dataset.py:1240-1253)
+SIX_IS_LOWER = 1            # the lower garment is labels 6, 9, 12 (dataset.py:1113)
 
 
 class TryOnPairBatch:
@@ -84,19 +87,19 @@ class TryOnPairOutfitBatchBuilder:
         lib, P = _native.lib(), _native.ptr
         with torch.cuda.device(dev):
             s = _native.stream()
-            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(sticks), m, H, W, s))
-            _native.check(lib.pasta_palm_mask_box_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
-            _native.check(lib.pasta_tryon_pair_outfit_masks_u8(P(image), P(parsing), P(palm), P(u_image), P(u_parsing), P(l_image), P(l_parsing),
-                                                               P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
-                                                               P(garment_mask[n:]), n, H, W, s))
+            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(sticks), m, H, W, STICK_THICKNESS, STICK_RADIUS, s))
+            _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
+            _native.check(lib.pasta_tryon_outfit_masks_u8(P(image), P(parsing), P(palm), P(u_image), P(u_parsing), P(l_image), P(l_parsing),
+                                                          P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
+                                                          P(garment_mask[n:]), n, H, W, SIX_IS_LOWER, s))
         patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l, valid_p = patch_pipeline.normalize_pair_outfit_batch(
             garment_img, sticks, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
         stick = sticks.index_select(0, person_ix)
         parts, ph, pw = patches.shape[1], patches.shape[2], patches.shape[3]
-        t, outs = output_tensors(TryOnPairOutfitBatch.KEYS, n, H, (6 * parts, ph, pw), dev)
-        with torch.cuda.device(dev):
-            _native.check(lib.pasta_tryon_pair_assemble(P(retain_img), P(stick), P(patches), P(stick_patches), P(den_u), P(den_l), outs, n, H,
-                                                        parts, ph, pw, _native.stream()))
+        t, outs = output_tensors(TryOnPairOutfitBatch.KEYS, n, H, (6 * parts, ph, pw), dev, OUTFIT_OUTPUTS)
+        with torch.cuda.device(dev):             # no image / clothes tensors, so no photographs; the stick patches are the second list
+            _native.check(lib.pasta_tryon_outfit_assemble(None, None, None, P(retain_img), P(stick), P(patches), P(stick_patches), P(den_u),
+                                                          P(den_l), outs, n, H, W, parts, parts, ph, pw, _native.stream()))
         stages = None
         if keep_stages:
             stages = dict(image=image, parsing=parsing, stick=stick, clothes_stick=sticks.index_select(0, upper_ix),

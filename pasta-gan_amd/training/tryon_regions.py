@@ -3,11 +3,11 @@
 ``__getitem__`` (training/dataset.py:1605-2214) and test_512.py's conversions (test_512.py:115-131) do per sample on the host
 in four loader processes, as a few launches per batch:
 
-    pasta_pose_stickman_thick_u8      the person's stick figure, thickness 5 and radius 5   (csrc/tryon_inputs.hip)
-    pasta_palm_mask_square_u8         the person's palm mask on the 512 square, boxes 35 and 20 (csrc/tryon_pairs.hip)
-    pasta_tryon_outfit_masks_u8       retain image, upper and lower garment, a source per garment (csrc/tryon_pairs.hip)
+    pasta_pose_stickman_u8            the person's stick figure, thickness 5 and radius 5   (csrc/tryon_inputs.hip)
+    pasta_palm_mask_u8                the person's palm mask on the 512 square, boxes 35 and 20 (csrc/tryon_pairs.hip)
+    pasta_tryon_outfit_masks_u8       retain image, upper and lower garment (labels 9, 12), a source per garment
     patch_pipeline.normalize_outfit_batch   two forward warps + two eroded composites (csrc/patches.hip, csrc/tryon_pairs.hip)
-    pasta_tryon_region_assemble       the nine fp32 tensors of test_512.py
+    pasta_tryon_outfit_assemble       the nine fp32 tensors of test_512.py (its outputs 0..8)
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
@@ -16,7 +16,7 @@ formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from th
 The implementation is the OUTFIT form, this project's own: a person with the upper garment of one donor and the lower garment of
 another (``training.dataset.UvitonOutfits_512_test``, ``collate_outfits``).  The batch's distinct people are uploaded once and
 ``patch_pipeline.normalize_outfit_batch`` solves their matrices once.  ``TryOnOutfitBatchBuilder`` is that body, with
-pasta_tryon_outfit_assemble (``clothes_lower`` as a tenth tensor).  A pair with a change region is the outfit (P, D, D), (P, D, P)
+``clothes_lower`` as a tenth tensor.  A pair with a change region is the outfit (P, D, D), (P, D, P)
 or (P, P, D), and ``TryOnRegionBatchBuilder`` is the same body behind ``training.dataset.pairs_batch_as_outfits``, told whose
 photograph ``clothes`` is.
 
@@ -25,8 +25,8 @@ reference has no 512 training set, so the rule is this project's own: the genera
 test_512.py will later feed it.  A sample is the full-body preparation above of the pair (person, person), plus the 256
 training set's photograph as target, ``gt_parsing`` and erase mask (include/pasta_hip.h lists the rules):
 
-    pasta_pose_stickman_thick_u8, pasta_palm_mask_square_u8     as above
-    pasta_tryon_train_region_masks_u8     retain mask, gt_parsing and the person's own two garments in one pass
+    pasta_pose_stickman_u8, pasta_palm_mask_u8     as above
+    pasta_tryon_masks_u8                  retain mask, gt_parsing and the person's own two garments in one pass, the 256 set's entry
     patch_pipeline.normalize_outfit_batch everyone their own donor: N solves; the eroded part masks of the upper composite kept
     pasta_tryon_train_region_assemble     the erase mask and the nine fp32 tensors of FullBodyBatch.KEYS"""
 
@@ -36,15 +36,16 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import pairs_batch_as_outfits
-from training.tryon_batch import (FullBodyBatch, allocator, device_tables, output_tensors, shift_keypoints, upload_erase, upload_images,
-                                  upload_person)
+from training.tryon_batch import (OUTFIT_OUTPUTS, FullBodyBatch, allocator, device_tables, output_tensors, shift_keypoints, upload_erase,
+                                  upload_images, upload_person)
 from training.tryon_pairs import TryOnPairBatch
 
 PALM_BOXES = (35, 20)       # get_hand_mask of the 512 set: upper arm 35 x 35, forearm 20 x 20 (dataset.py:1790, :1795)
 STICK_THICKNESS = 5         # cv2.line(..., 5) (dataset.py:1851)
 STICK_RADIUS = 5            # circle(..., radius=5) (dataset.py:1832, :1861)
-# change region -> (code of pasta_tryon_region_masks_u8, upper garment from the donor, lower garment from the donor) (:1679-1690);
-# the builders take the garments' owners from the outfit's indices, the entry is held to the same rule by its tests
+SIX_IS_LOWER = 0            # the lower garment is labels 9, 12 (dataset.py:1639, :1669)
+# change region -> (its index in training.dataset.CHANGE_REGIONS, upper garment from the donor, lower garment from the donor)
+# (:1679-1690); the builders take the garments' owners from the outfit's indices
 REGIONS = dict(fullbody=(0, True, True), upperbody=(1, True, False), lowerbody=(2, False, True))
 
 
@@ -67,8 +68,8 @@ def _person_launches(parsing, kp, n, H, W, dev):
     lib, P = _native.lib(), _native.ptr
     with torch.cuda.device(dev):
         s = _native.stream()
-        _native.check(lib.pasta_pose_stickman_thick_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
-        _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
+        _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
+        _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
     return stick, palm, retain_img, garment_img, garment_mask
 
 
@@ -109,9 +110,9 @@ class TryOnOutfitBatchBuilder:
 
     def _prepare(self, raw, panels, valid_stages, keep_stages):
         """The one body of the test builders: (fp32 tensors, stages or None) of a batch of ``collate_outfits``.  ``panels``: whose
-        photographs follow ``image``, by role: two give ``clothes`` and ``clothes_lower`` (pasta_tryon_outfit_assemble), one gives
-        ``clothes`` alone (pasta_tryon_region_assemble: the same launcher with nine outputs).  ``valid_stages``: the name under
-        which the stages keep the [N, 10] valid flags of a role's matrices."""
+        photographs follow ``image``, by role: two give ``clothes`` and ``clothes_lower``, one gives ``clothes`` alone (no tenth
+        output and no third photograph).  ``valid_stages``: the name under which the stages keep the [N, 10] valid flags of a
+        role's matrices."""
         dev = self.device
         people_image, people_parsing, people_kp = upload_person(raw, dev, type(self).__name__, 'people_')
         m, H, W, _ = people_image.shape
@@ -127,18 +128,18 @@ class TryOnOutfitBatchBuilder:
         with torch.cuda.device(dev):
             _native.check(lib.pasta_tryon_outfit_masks_u8(P(image), P(parsing), P(palm), P(u_image), P(u_parsing), P(l_image), P(l_parsing),
                                                           P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
-                                                          P(garment_mask[n:]), n, H, W, _native.stream()))
+                                                          P(garment_mask[n:]), n, H, W, SIX_IS_LOWER, _native.stream()))
         *normalized, valid_u, valid_l, valid_p = patch_pipeline.normalize_outfit_batch(
             garment_img, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
         patches, patches_l, _, _, den_u, den_l, _ = normalized
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
         photograph = dict(upper=u_image, lower=l_image)
-        assemble, keys = ((lib.pasta_tryon_outfit_assemble, TryOnOutfitBatch.KEYS) if len(panels) == 2 else
-                          (lib.pasta_tryon_region_assemble, TryOnRegionBatch.KEYS))
-        t, outs = output_tensors(keys, n, H, (3 * (pu + pl), ph, pw), dev)
+        clothes, clothes_lower = photograph[panels[0]], photograph[panels[1]] if len(panels) == 2 else None
+        keys = TryOnOutfitBatch.KEYS if len(panels) == 2 else TryOnRegionBatch.KEYS
+        t, outs = output_tensors(keys, n, H, (3 * (pu + pl), ph, pw), dev, OUTFIT_OUTPUTS)
         with torch.cuda.device(dev):
-            _native.check(assemble(P(image), *[P(photograph[role]) for role in panels], P(retain_img), P(stick), P(patches), P(patches_l),
-                                   P(den_u), P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
+            _native.check(lib.pasta_tryon_outfit_assemble(P(image), P(clothes), P(clothes_lower), P(retain_img), P(stick), P(patches),
+                                                          P(patches_l), P(den_u), P(den_l), outs, n, H, W, pu, pl, ph, pw, _native.stream()))
         stages = None
         if keep_stages:
             valid = dict(upper=valid_u, lower=valid_l, person=valid_p)
@@ -191,10 +192,11 @@ class FullBodyRegionBatchBuilder:
         lib, P = _native.lib(), _native.ptr
         with torch.cuda.device(dev):
             s = _native.stream()
-            _native.check(lib.pasta_pose_stickman_thick_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
-            _native.check(lib.pasta_palm_mask_square_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
-            _native.check(lib.pasta_tryon_train_region_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), P(garment_img[:n]),
-                                                                P(garment_mask[:n]), P(garment_img[n:]), P(garment_mask[n:]), n, H, W, s))
+            _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
+            _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
+            # pasta_tryon_masks_u8's order: both images, then both masks
+            _native.check(lib.pasta_tryon_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), P(garment_img[:n]), P(garment_img[n:]),
+                                                   P(garment_mask[:n]), P(garment_mask[n:]), n, H, W, s))
         own = np.arange(n)                  # everyone wears their own garments: the N people are solved once
         patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, _, part_masks = patch_pipeline.normalize_outfit_batch(
             garment_img, garment_mask, shift_keypoints(kp, lp), own, own, own, self.box_factor, want_part_masks=True)

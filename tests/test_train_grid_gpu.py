@@ -99,7 +99,7 @@ def test_identity_index_equals_the_eroded_composite():
     lib, p, s = _native.lib(), _native.ptr, _native.stream()
     for radius in (0, 2):
         want, got = (torch.full([n, H, W, 3], 7, dtype=torch.uint8, device='cuda') for _ in range(2))
-        _native.check(lib.pasta_patch_composite_eroded_u8(p(patches), p(masks), p(minv_t), p(valid_t), p(want), None, n, P, ph, pw, H, W, radius, s))
+        _native.check(lib.pasta_patch_composite_eroded_u8(p(patches), p(masks), p(minv_t), p(valid_t), p(want), None, n, P, ph, pw, H, W, radius, None, s))
         _native.check(lib.pasta_grid_composite_eroded_u8(p(patches), p(masks), p(index), p(minv_t), p(valid_t), p(got), n, P, n * P, ph, pw, H, W,
                                                          radius, s))
         assert torch.equal(got, want), radius

@@ -76,31 +76,42 @@ def test_thick_stick_figure_equals_the_restatement():
     rng = np.random.default_rng(0)
     kp = _keypoints(rng, 4)
     lib = _lib().lib()
-    got = _stick(lib.pasta_pose_stickman_thick_u8, kp, H, W, 5, 5)
+    got = _stick(lib.pasta_pose_stickman_u8, kp, H, W, 5, 5)
     for i in range(len(kp)):
         ref = np.pad(FR.draw_pose_from_cords(kp[i], (H, W)), ((0, 0), (LP, LP), (0, 0)))
         assert np.array_equal(got[i], ref), (i, int((got[i] != ref).any(axis=2).sum()))
     assert got.any() and not got[:, :, :LP].any() and not got[:, :, LP + W:].any()
-    thin = _stick(lib.pasta_pose_stickman_thick_u8, kp, H, W, 2, 2)
+    thin = _stick(lib.pasta_pose_stickman_u8, kp, H, W, 2, 2)
     assert (got.any(axis=3).sum() > 2 * thin.any(axis=3).sum())  # thickness 5 covers far more than thickness 2
 
 
 def test_generalised_entries_with_the_old_constants_equal_the_old_entries():
+    """The 256 x 192 sets' constants through the one stick-figure and the one palm entry, each against its restatement: the
+    thickness-2 figure of tests/tryon_ref.py, and the palm rule on the 256 square with the training set's boxes, the test set's
+    and a pair of small ones."""
+    import tryon_ref as R
     rng = np.random.default_rng(1)
     kp = _keypoints(rng, 4, 256, 192)
     kp[1, 7, :2] = (300.5, -20.25)
     lib = _lib().lib()
-    old = _stick(lib.pasta_pose_stickman_u8, kp, 256, 192)
-    assert np.array_equal(_stick(lib.pasta_pose_stickman_thick_u8, kp, 256, 192, 2, 2), old) and old.any()
+    thin = _stick(lib.pasta_pose_stickman_u8, kp, 256, 192, 2, 2)
+    for i in range(len(kp)):
+        assert np.array_equal(thin[i], np.pad(R.draw_pose_from_cords(kp[i], (256, 192)), ((0, 0), (32, 32), (0, 0)))), i
+    assert thin.any()
     parsing = _labels(rng, kp, 256, 192)
+    padded = np.pad(parsing, ((0, 0), (0, 0), (32, 32)))
+    shifted = kp.copy()
+    shifted[..., 0] += 32
+    seen = []
     for boxes in ((25, 15), (25, 16), (7, 4)):
-        box = _palm(lib.pasta_palm_mask_box_u8, parsing, kp, 256, 192, *boxes)
-        assert np.array_equal(_palm(lib.pasta_palm_mask_square_u8, parsing, kp, 256, 192, *boxes), box) and box.any()
-    assert np.array_equal(_palm(lib.pasta_palm_mask_square_u8, parsing, kp, 256, 192, 25, 16), _palm(lib.pasta_palm_mask_u8, parsing, kp, 256, 192))
-    with pytest.raises(RuntimeError, match='256 x 256'):         # the 256 entries still refuse any other square
-        _palm(lib.pasta_palm_mask_box_u8, _labels(rng, kp[:1]), kp[:1], H, W, 25, 15)
+        got = _palm(lib.pasta_palm_mask_u8, parsing, kp, 256, 192, *boxes)
+        for i in range(len(kp)):
+            assert np.array_equal(got[i], FR.palm_mask(shifted[i], padded[i], boxes)), (boxes, i)
+        assert got.any()
+        seen.append(got)
+    assert (seen[0] != seen[1]).any() and (seen[1] != seen[2]).any()          # the boxes matter
     with pytest.raises(RuntimeError, match='bad shape'):
-        _palm(lib.pasta_palm_mask_square_u8, np.zeros([1, 520, 320], np.uint8), kp[:1], 520, 320, 35, 20)
+        _palm(lib.pasta_palm_mask_u8, np.zeros([1, 520, 320], np.uint8), kp[:1], 520, 320, 35, 20)
 
 
 def test_palm_512_and_region_masks_equal_the_restatement():
@@ -112,15 +123,18 @@ def test_palm_512_and_region_masks_equal_the_restatement():
     image, d_image = (rng.integers(0, 256, [n, H, W, 3], dtype=np.uint8) for _ in range(2))
     N = _lib()
     lib = N.lib()
-    palm = _palm(lib.pasta_palm_mask_square_u8, parsing, kp, H, W, 35, 20)
-    other = _palm(lib.pasta_palm_mask_square_u8, parsing, kp, H, W, 25, 15)
+    palm = _palm(lib.pasta_palm_mask_u8, parsing, kp, H, W, 35, 20)
+    other = _palm(lib.pasta_palm_mask_u8, parsing, kp, H, W, 25, 15)
     raws = [dict(image=image[i], parsing=parsing[i], keypoints=kp[i], clothes_image=d_image[i], clothes_parsing=d_parsing[i],
                  clothes_keypoints=d_kp[i]) for i in range(n)]
-    ins = [_cu(a) for a in (image, parsing, palm, d_image, d_parsing)]     # held: a freed input's memory would be reused by the next one
+    person = [_cu(a) for a in (image, parsing, palm)]     # held: a freed input's memory would be reused by the next one
+    own, donor = person[:2], [_cu(a) for a in (d_image, d_parsing)]
     seen = {}
-    for code, region in enumerate(FR.REGIONS):
+    for region in FR.REGIONS:
+        upper_donor, lower_donor = FR.region_sources(region)
+        ins = person + (donor if upper_donor else own) + (donor if lower_donor else own)
         outs = [torch.empty([n, H, H, 3], dtype=torch.uint8, device='cuda') for _ in range(5)]
-        N.check(lib.pasta_tryon_region_masks_u8(*[N.ptr(t) for t in ins + outs], n, H, W, code, N.stream()))
+        N.check(lib.pasta_tryon_outfit_masks_u8(*[N.ptr(t) for t in ins + outs], n, H, W, 0, N.stream()))
         outs = [t.cpu().numpy() for t in outs]
         for i in range(n):
             ref = FR.label_stages(raws[i], region)
@@ -132,9 +146,9 @@ def test_palm_512_and_region_masks_equal_the_restatement():
     assert palm.any() and (palm != other).any()
     assert not np.array_equal(seen['fullbody'][3], seen['upperbody'][3]) and np.array_equal(seen['fullbody'][1], seen['upperbody'][1])
     assert not np.array_equal(seen['fullbody'][1], seen['lowerbody'][1]) and np.array_equal(seen['fullbody'][3], seen['lowerbody'][3])
-    with pytest.raises(RuntimeError, match='region 3'):
+    with pytest.raises(RuntimeError, match='six_is_lower 3'):
         outs = [torch.empty([n, H, H, 3], dtype=torch.uint8, device='cuda') for _ in range(5)]
-        N.check(lib.pasta_tryon_region_masks_u8(*[N.ptr(t) for t in ins + outs], n, H, W, 3, N.stream()))
+        N.check(lib.pasta_tryon_outfit_masks_u8(*[N.ptr(t) for t in ins + outs], n, H, W, 3, N.stream()))
 
 
 def test_region_assemble_equals_test_512_expressions():
@@ -160,9 +174,9 @@ def test_region_assemble_equals_test_512_expressions():
         want = FR.generator_inputs([FR.getitem(s) for s in stages], 'cuda')
         N = _lib()
         t = {k: torch.empty_like(want[k]) for k in TryOnRegionBatch.KEYS}
-        outs = (ctypes.c_void_p * 9)(*[t[k].data_ptr() for k in TryOnRegionBatch.KEYS])
-        ins = [_cu(a) for a in (image, clothes, retain_mask * pad(image), stick, patches, patches_l, den_u, den_l)]
-        N.check(N.lib().pasta_tryon_region_assemble(*[N.ptr(a) for a in ins], outs, n, h, w, pu, pl, ph, pw, N.stream()))
+        outs = (ctypes.c_void_p * 10)(*[t[k].data_ptr() for k in TryOnRegionBatch.KEYS], None)       # no clothes_lower, no third photograph
+        ins = [_cu(a) for a in (image, clothes)] + [None] + [_cu(a) for a in (retain_mask * pad(image), stick, patches, patches_l, den_u, den_l)]
+        N.check(N.lib().pasta_tryon_outfit_assemble(*[N.ptr(a) for a in ins], outs, n, h, w, pu, pl, ph, pw, N.stream()))
         for k in TryOnRegionBatch.KEYS:
             assert torch.equal(t[k], want[k]), (h, k)
         assert tuple(t['style_input'].shape) == (n, 3 * (pu + pl), ph, pw) and tuple(t['pose'].shape) == (n, 6, h, h)

@@ -170,9 +170,9 @@ def test_interface_carries_the_two_entries():
     text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'pasta_hip.h')).read(), flags=re.S)
     declared = set(re.findall(r'\b(pasta_[a-z0-9_]+)\s*\(', text))
     lib = ctypes.CDLL(custom_ops.build())
-    for name in ('pasta_tryon_train_region_masks_u8', 'pasta_tryon_train_region_assemble'):
-        assert name in declared and name in custom_ops.ABI and name in custom_ops.LATE_ENTRIES and hasattr(lib, name), name
-    assert custom_ops.EXPECTED_ABI == 21
+    for name in ('pasta_tryon_masks_u8', 'pasta_tryon_train_region_assemble'):          # the label masks are the 256 training set's entry
+        assert name in declared and name in custom_ops.ABI and hasattr(lib, name), name
+    assert custom_ops.EXPECTED_ABI == 22
     # bad arguments are refused on the host, before any launch
     typed = custom_ops.get_plugin()
     outs = (ctypes.c_void_p * 9)(*[1] * 9)
@@ -180,5 +180,5 @@ def test_interface_carries_the_two_entries():
     assert b'pw a multiple of 4' in typed.pasta_last_error()
     assert typed.pasta_tryon_train_region_assemble(*[1] * 9, 4, 10, 1, 1, outs, 1, 512, 320, 10, 5, 128, 128, 8, 8, None) != 0
     assert b'arm parts 4, 10 of 10' in typed.pasta_last_error()
-    assert typed.pasta_tryon_train_region_masks_u8(*[1] * 8, None, 1, 512, 320, None) != 0
-    assert b'tryon_train_region_masks_u8: null pointer' in typed.pasta_last_error()
+    assert typed.pasta_tryon_masks_u8(*[1] * 8, None, 1, 512, 320, None) != 0
+    assert b'tryon_masks_u8: null pointer' in typed.pasta_last_error()

@@ -83,8 +83,9 @@ def test_masks_entry_equals_the_restatement(cases):
     ins = [_cu(np.stack(a)) for a in ([s['image'] for s in samples], [s['parsing'] for s in samples], [st['palm'] for st in stages])]
     u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device='cuda')
     retain, gt, img, mask = u8(n, H, H), u8(n, H, H), u8(2 * n, H, H, 3), u8(2 * n, H, H, 3)
-    N.check(N.lib().pasta_tryon_train_region_masks_u8(*[N.ptr(a) for a in ins], N.ptr(retain), N.ptr(gt), N.ptr(img[:n]), N.ptr(mask[:n]),
-                                                      N.ptr(img[n:]), N.ptr(mask[n:]), n, H, W, N.stream()))
+    # the 256 training set's entry in its own order (both images, then both masks), on the halves of the stacked tensors
+    N.check(N.lib().pasta_tryon_masks_u8(*[N.ptr(a) for a in ins], N.ptr(retain), N.ptr(gt), N.ptr(img[:n]), N.ptr(img[n:]),
+                                         N.ptr(mask[:n]), N.ptr(mask[n:]), n, H, W, N.stream()))
     got = dict(retain_mask=retain, gt_parsing=gt, upper_img=img[:n], upper_mask=mask[:n], lower_img=img[n:], lower_mask=mask[n:])
     for k, v in got.items():
         v = v.cpu().numpy()

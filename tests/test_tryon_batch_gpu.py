@@ -52,8 +52,8 @@ def _launch_front(image, parsing, kp):
     stick, palm, retain, gt = u8(n, 256, 256, 3), u8(n, 256, 256), u8(n, 256, 256), u8(n, 256, 256)
     g = [u8(n, 256, 256, 3) for _ in range(4)]
     lib, P, s = _native.lib(), _native.ptr, _native.stream()
-    _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, 256, 192, s))
-    _native.check(lib.pasta_palm_mask_u8(P(lab), P(quads), P(present), P(palm), n, 256, 192, s))
+    _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, 256, 192, 2, 2, s))
+    _native.check(lib.pasta_palm_mask_u8(P(lab), P(quads), P(present), P(palm), n, 256, 192, 25, 16, s))
     _native.check(lib.pasta_tryon_masks_u8(P(img), P(lab), P(palm), P(retain), P(gt), *[P(t) for t in g], n, 256, 192, s))
     out = [t.cpu().numpy() for t in (stick, palm, retain, gt, *g)]
     return out
@@ -98,7 +98,7 @@ def test_palm_dilation_equals_a_brute_force_max_filter(box):
         out = torch.empty([1, 256, 256], dtype=torch.uint8, device='cuda')
         lab_t, quads_t, present_t = cu(lab), cu(quads), cu(present)       # held: the kernel runs after the pointers are taken
         _native.check(_native.lib().pasta_palm_mask_u8(_native.ptr(lab_t), _native.ptr(quads_t), _native.ptr(present_t),
-                                                      _native.ptr(out), 1, 256, 192, _native.stream()))
+                                                      _native.ptr(out), 1, 256, 192, 25, 16, _native.stream()))
         fill = R.rle_fr_poly([float(v) for v in corners.reshape(-1)], 256, 256)
         want = 1 - R.dilate(fill, box)
         want[:, :32] = 0

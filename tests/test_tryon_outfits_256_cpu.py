@@ -202,11 +202,11 @@ def test_the_entries_are_declared_typed_and_exported():
     from torch_utils import custom_ops
     header = open(os.path.join(ROOT, 'include', 'pasta_hip.h')).read()
     lib = custom_ops.get_plugin()
-    for name, args in (('pasta_tryon_pair_outfit_masks_u8', 16), ('pasta_patch_composite_radii_u8', 14)):
+    # the label masks with six_is_lower, the eroded composite with radius and radii
+    for name, args in (('pasta_tryon_outfit_masks_u8', 17), ('pasta_patch_composite_eroded_u8', 15)):
         assert re.search(r'\bint %s\(' % name, header) and hasattr(lib, name), name
-        assert name in custom_ops.LATE_ENTRIES and len(custom_ops.ABI[name][1]) == args
-    assert len(custom_ops.ABI['pasta_patch_composite_radii_u8'][1]) == len(custom_ops.ABI['pasta_patch_composite_eroded_u8'][1])
-    assert lib.pasta_abi_version() == custom_ops.EXPECTED_ABI == 21             # additive entries: the version does not move
+        assert name in custom_ops.ABI and len(custom_ops.ABI[name][1]) == args
+    assert lib.pasta_abi_version() == custom_ops.EXPECTED_ABI == 22
 
 
 def test_cli_lists_the_options_and_refuses_outfits_with_a_region(tmp_path):

@@ -1,7 +1,7 @@
-"""Outfits for the 256 x 192 model on the GPU (pasta_patch_composite_radii_u8 and pasta_tryon_pair_outfit_masks_u8 of
-csrc/tryon_pairs.hip, training.tryon_pairs.TryOnPairOutfitBatchBuilder, ``test.py --outfits`` / ``--change-region`` / ``--scores``)
--- EXACT: the per-sample-radius composite against the plain and the scalar entries and against a brute-force erode, the masks
-entry against the pair entry and a numpy statement of its rule, the builder on (p, c, -) against the pair builder on every pair
+"""Outfits for the 256 x 192 model on the GPU (pasta_patch_composite_eroded_u8 with its radii and pasta_tryon_outfit_masks_u8 with
+label 6 in the lower garment, csrc/tryon_pairs.hip, training.tryon_pairs.TryOnPairOutfitBatchBuilder, ``test.py --outfits`` / ``--change-region`` / ``--scores``)
+-- EXACT: the per-sample-radius composite against the plain entry and the scalar radius and against a brute-force erode, the masks
+entry against a numpy statement of its rule, the builder on (p, c, -) against the pair builder on every pair
 of the tree, a truly mixed list against values composed from tests/tryon_pairs_ref.py (tests/tryon_outfits_256_ref.py), and the
 command line against an in-process run and the region scores' numpy restatement (tests/tryon_fidelity_ref.py)."""
 import importlib.util
@@ -121,10 +121,10 @@ def test_radii_composite_equals_the_plain_and_the_scalar_entries(height, width):
             run(bad)
     with pytest.raises(ValueError, match='2 radii for 3 samples'):
         run([0, 2])
-    with pytest.raises(RuntimeError, match='patch_composite_radii_u8: null pointer'):
+    with pytest.raises(RuntimeError, match='patch_composite_eroded_u8: null pointer'):
         N = _native()
-        keep = [_cu(patches), _cu(masks), _cu(PP.inverse_maps(back, order)), _cu(valid.astype(np.uint8)), torch.empty_like(got)]
-        N.check(N.lib().pasta_patch_composite_radii_u8(*[N.ptr(t) for t in keep], None, n, parts, ph, pw, height, width, None, N.stream()))
+        keep = [_cu(patches), _cu(masks), _cu(PP.inverse_maps(back, order)), _cu(valid.astype(np.uint8)), None]         # no output image
+        N.check(N.lib().pasta_patch_composite_eroded_u8(*[N.ptr(t) for t in keep], None, n, parts, ph, pw, height, width, 2, None, N.stream()))
 
 
 def test_radius_8_is_the_largest_and_equals_the_scalar_entry():
@@ -138,6 +138,15 @@ def test_radius_8_is_the_largest_and_equals_the_scalar_entry():
     for i, want in enumerate((eight, plain, eight)):
         assert torch.equal(got[0][i], want[0][i]) and torch.equal(got[1][i], want[1][i]), i
     assert got[1][0].any() and not torch.equal(eight[1][0], plain[1][0])
+    # the entry itself with radii AND a scalar radius of 5: the scalar is not read
+    N = _native()
+    keep = [_cu(patches), _cu(masks), _cu(PP.inverse_maps(back, [0, 1, 2, 3])), _cu(valid.astype(np.uint8)), torch.empty_like(got[0]),
+            torch.empty_like(got[1]), _cu(np.array([8, 0, 8], np.uint8))]
+    N.check(N.lib().pasta_patch_composite_eroded_u8(*[N.ptr(t) for t in keep[:6]], 3, 4, 16, 12, 64, 48, 5, N.ptr(keep[6]), N.stream()))
+    five = run(5)
+    for i, want in enumerate((eight, plain, eight)):
+        assert torch.equal(keep[4][i], want[0][i]) and torch.equal(keep[5][i], want[1][i]), i
+    assert not torch.equal(five[0][0], eight[0][0]) and not torch.equal(five[0][1], plain[0][1])          # radius 5 would have shown
 
 
 # ---- 2. the label masks with a source per garment ----
@@ -145,10 +154,10 @@ def test_radius_8_is_the_largest_and_equals_the_scalar_entry():
 OUTPUTS = ('retain_img', 'upper_img', 'upper_mask', 'lower_img', 'lower_mask')
 
 
-def _masks(entry, ins, n, h, w):
+def _masks(entry, ins, n, h, w, six_is_lower):
     N = _native()
     outs = [torch.empty([n, h, h, 3], dtype=torch.uint8, device='cuda') for _ in OUTPUTS]
-    N.check(entry(*[N.ptr(t) for t in list(ins) + outs], n, h, w, N.stream()))
+    N.check(entry(*[N.ptr(t) for t in list(ins) + outs], n, h, w, six_is_lower, N.stream()))
     return [t.cpu().numpy() for t in outs]
 
 
@@ -188,27 +197,22 @@ def test_pair_outfit_masks_equal_the_pair_entry_and_their_rule():
     stacks = (person, a, b)
     results = {}
     for upper, lower in ((1, 0), (0, 1), (1, 2), (2, 2), (0, 0)):         # the pair, swapped, two third parties, one donor, nobody
-        got = _masks(lib.pasta_tryon_pair_outfit_masks_u8, person + (palm_t,) + stacks[upper] + stacks[lower], n, h, w)
+        got = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + stacks[upper] + stacks[lower], n, h, w, 1)
         for name, g, x in zip(OUTPUTS, got, rule(upper, lower)):
             assert g.dtype == x.dtype and np.array_equal(g, x), (upper, lower, name)
             assert g.any() and not g.all(), name
         results[upper, lower] = got
-    # (donor, person) is the pair entry byte for byte; its outputs come in another order
-    N = _native()
-    outs = [torch.empty([n, h, h, 3], dtype=torch.uint8, device='cuda') for _ in range(5)]
-    N.check(lib.pasta_tryon_pair_masks_u8(*[N.ptr(t) for t in person + (palm_t,) + a + tuple(outs)], n, h, w, N.stream()))
-    pair = dict(zip(('retain_img', 'lower_img', 'lower_mask', 'upper_img', 'upper_mask'), (t.cpu().numpy() for t in outs)))
-    for name, g in zip(OUTPUTS, results[1, 0]):
-        assert np.array_equal(g, pair[name]), name
-    # label 6 is in BOTH garments here, which the 512 entry's lower garment leaves out
-    six = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + person, n, h, w)
+    # (donor, person) is the reference's pair, compared with its rule above
+    pair = dict(zip(OUTPUTS, results[1, 0]))
+    # label 6 is in BOTH garments here, which six_is_lower = 0 (the 512 x 320 sets) leaves out of the lower garment
+    six = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + person, n, h, w, 0)
     assert np.array_equal(six[2], pair['upper_mask']) and not np.array_equal(six[4], pair['lower_mask'])
     assert ((pair['lower_mask'][..., 0] != 0) == np.isin(np.pad(parsings[0], ((0, 0), (0, 0), (lp, lp))), (6, 9, 12))).all()
     assert not np.array_equal(results[1, 2][3], results[1, 0][3]) and not np.array_equal(results[0, 1][1], results[1, 0][1])
-    with pytest.raises(RuntimeError, match='tryon_pair_outfit_masks_u8: null pointer'):
-        _masks(lib.pasta_tryon_pair_outfit_masks_u8, person + (palm_t,) + a + (b[0], None), n, h, w)
-    with pytest.raises(RuntimeError, match='tryon_pair_outfit_masks_u8: bad shape'):
-        _masks(lib.pasta_tryon_pair_outfit_masks_u8, person + (palm_t,) + a + b, n, w, h)
+    with pytest.raises(RuntimeError, match='tryon_outfit_masks_u8: null pointer'):
+        _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + (b[0], None), n, h, w, 1)
+    with pytest.raises(RuntimeError, match='tryon_outfit_masks_u8: bad shape'):
+        _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + b, n, w, h, 1)
 
 
 # ---- 3. and 4. the builder on the tree ----

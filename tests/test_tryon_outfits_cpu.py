@@ -130,10 +130,34 @@ def test_the_entries_are_declared_typed_and_exported():
     from torch_utils import custom_ops
     header = open(os.path.join(ROOT, 'include', 'pasta_hip.h')).read()
     lib = custom_ops.get_plugin()
-    for name, args in (('pasta_tryon_outfit_masks_u8', 16), ('pasta_tryon_outfit_assemble', 18)):
+    for name, args in (('pasta_tryon_outfit_masks_u8', 17), ('pasta_tryon_outfit_assemble', 18)):
         assert re.search(r'\bint %s\(' % name, header) and hasattr(lib, name), name
-        assert name in custom_ops.LATE_ENTRIES and len(custom_ops.ABI[name][1]) == args
-    assert lib.pasta_abi_version() == custom_ops.EXPECTED_ABI == 21             # additive entries: the version does not move
+        assert name in custom_ops.ABI and len(custom_ops.ABI[name][1]) == args
+    assert lib.pasta_abi_version() == custom_ops.EXPECTED_ABI == 22
+
+
+def test_the_merged_entries_refuse_bad_arguments_before_any_launch():
+    """The host guards of the ABI-22 try-on entries: pointers are the never-dereferenced value 1, and every call is refused with
+    the entry's own text before anything is launched."""
+    import ctypes
+    from torch_utils import custom_ops
+    lib = custom_ops.get_plugin()
+
+    def refused(status, text):
+        assert status != 0 and text in lib.pasta_last_error(), lib.pasta_last_error()
+
+    def assemble(slots, photographs):
+        outs = (ctypes.c_void_p * 10)(*slots)
+        return lib.pasta_tryon_outfit_assemble(*photographs, *[1] * 6, outs, 2, 20, 12, 3, 3, 5, 5, None)
+    refused(assemble([None] + [1] * 9, [1, 1, 1]), b'tryon_outfit_assemble: outputs 0 and 1')          # slot 0 null, slot 1 set
+    refused(assemble([1] * 10, [1, 1, None]), b'tryon_outfit_assemble: null photograph')               # slot 9 without lower_donor_image
+    refused(assemble([1] * 10, [None, 1, 1]), b'tryon_outfit_assemble: null photograph')               # slot 0 without image
+    refused(assemble([1] * 4 + [None] + [1] * 5, [1, 1, 1]), b'tryon_outfit_assemble: output 4 is null')
+    refused(assemble([None, None] + [1] * 8, [None, None, 1]), b'output 9 needs them')                 # clothes_lower without image / clothes
+    refused(lib.pasta_patch_composite_eroded_u8(*[1] * 6, 3, 4, 5, 5, 64, 48, 9, None, None), b'patch_composite_eroded_u8: radius 9 (0..8)')
+    refused(lib.pasta_tryon_outfit_masks_u8(*[1] * 12, 2, 20, 12, 2, None), b'tryon_outfit_masks_u8: six_is_lower 2')
+    refused(lib.pasta_pose_stickman_u8(*[1] * 3, 2, 20, 12, 0, 2, None), b'pose_stickman_u8: thickness 0, radius 2')
+    refused(lib.pasta_palm_mask_u8(*[1] * 4, 1, 520, 320, 35, 20, None), b'palm_mask_u8: bad shape')
 
 
 def test_cli_lists_the_options_and_refuses_outfits_with_a_region(tmp_path):

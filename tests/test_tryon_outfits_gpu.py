@@ -1,6 +1,6 @@
 """Outfits at 512 x 320 on the GPU (pasta_tryon_outfit_masks_u8 / pasta_tryon_outfit_assemble of csrc/tryon_pairs.hip,
 training.tryon_regions.TryOnOutfitBatchBuilder, ``test_512.py --outfits`` and ``--scores``) -- EXACT: the entries against a numpy
-statement of their rule and against the region entries they generalise, the builder against the region builder on the three
+statement of their rule and test_512.py's expressions, the builder against the region builder on the three
 degenerate outfits of every pair and on a batch that names a pair twice, a truly mixed list against values composed from tests/tryon_512_ref.py, and the command line
 against an in-process run and the region scores' numpy restatement (tests/tryon_fidelity_ref.py)."""
 import ctypes
@@ -72,14 +72,19 @@ def test_outfit_masks_equal_their_rule_and_the_region_entry():
     lib = _native().lib()
     person, a, b = (_cu(image), _cu(parsing)), (_cu(a_image), _cu(a_parsing)), (_cu(b_image), _cu(b_parsing))
     palm_t = _cu(palm)
-    got = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + b, n, h, w)
+    got = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + b, n, h, w, 0)
 
-    # the rule: labels and images padded with 0 and 255; retain from the person, upper from A, lower from B
-    label, upper, lower = pad(parsing, 0), np.isin(pad(a_parsing, 0), (5, 6, 7)), np.isin(pad(b_parsing, 0), (9, 12))
+    # the rule: labels and images padded with 0 and 255; retain from the person, upper and lower from a source each
+    label = pad(parsing, 0)
     keep = np.isin(label, (18, 19)).astype(np.uint8) + palm + np.isin(label, (1, 2, 4, 13)).astype(np.uint8)
     mask3 = lambda m: np.repeat(m[..., None], 3, axis=3).astype(np.uint8) * 255
-    want = [keep[..., None] * pad(image, 255), upper[..., None] * pad(a_image, 255), mask3(upper), lower[..., None] * pad(b_image, 255),
-            mask3(lower)]
+
+    def rule(up, low):
+        upper, lower = np.isin(pad(up[1], 0), (5, 6, 7)), np.isin(pad(low[1], 0), (9, 12))
+        return [keep[..., None] * pad(image, 255), upper[..., None] * pad(up[0], 255), mask3(upper), lower[..., None] * pad(low[0], 255),
+                mask3(lower)]
+    host = dict(person=(image, parsing), a=(a_image, a_parsing), b=(b_image, b_parsing))
+    want = rule(host['a'], host['b'])
     assert keep.max() == 1
     for name, g, x in zip(OUTPUTS, got, want):
         assert g.dtype == x.dtype and np.array_equal(g, x), name
@@ -87,51 +92,57 @@ def test_outfit_masks_equal_their_rule_and_the_region_entry():
     assert not got[0][:, :, :lp].any() and not got[0][:, :, lp + w:].any()                # label 0 and no palm there: nothing is kept
     assert not got[2][:, :, :lp].any() and not got[4][:, :, lp + w:].any()                # label 0 there: no garment
 
-    # one donor: the three regions are three choices of the two sources
-    for code, (up, low) in enumerate(((a, a), (a, person), (person, a))):
-        outfit = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + up + low, n, h, w)
-        region = _masks(lib.pasta_tryon_region_masks_u8, person + (palm_t,) + a, n, h, w, code)
-        for name, g, x in zip(OUTPUTS, outfit, region):
-            assert np.array_equal(g, x), (code, name)
+    # one donor: the three regions (full, upper, lower body) are three choices of the two sources, the person's own pointers among them
+    device = dict(person=person, a=a)
+    for up, low in (('a', 'a'), ('a', 'person'), ('person', 'a')):
+        outfit = _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + device[up] + device[low], n, h, w, 0)
+        for name, g, x in zip(OUTPUTS, outfit, rule(host[up], host[low])):
+            assert np.array_equal(g, x), (up, low, name)
     assert not np.array_equal(got[3], outfit[3])                     # B's lower garment is not A's
     with pytest.raises(RuntimeError, match='tryon_outfit_masks_u8: null pointer'):
-        _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + (b[0], None), n, h, w)
+        _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + (b[0], None), n, h, w, 0)
     with pytest.raises(RuntimeError, match='tryon_outfit_masks_u8: bad shape'):
-        _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + b, n, w, h)
+        _masks(lib.pasta_tryon_outfit_masks_u8, person + (palm_t,) + a + b, n, w, h, 0)
 
 
 def test_outfit_assemble_equals_two_region_assembles():
+    """All ten outputs against test_512.py's expressions (tests/tryon_512_ref.generator_inputs): the nine of the pair (person,
+    upper donor), and clothes_lower = the restatement's ``clothes`` of the pair (person, lower donor)."""
     from training.tryon_regions import TryOnOutfitBatch, TryOnRegionBatch
     assert TryOnOutfitBatch.KEYS == TryOnRegionBatch.KEYS + ['clothes_lower']
     rng = np.random.default_rng(1)
     n, h, w, pu, pl, ph, pw = 3, 48, 30, 3, 2, 6, 5
-    u8 = lambda *shape: _cu(rng.integers(0, 256, shape, dtype=np.uint8))
-    image, a_image, b_image = (u8(n, h, w, 3) for _ in range(3))
-    rest = [u8(n, h, h, 3), u8(n, h, h, 3), u8(n, pu, ph, pw, 3), u8(n, pl, ph, pw, 3), u8(n, h, h, 3), u8(n, h, h, 3)]
+    lp = (h - w) // 2
+    u8 = lambda *shape: rng.integers(0, 256, shape, dtype=np.uint8)
+    pad = lambda a: np.pad(a, ((0, 0), (0, 0), (lp, lp), (0, 0)), constant_values=255)
+    image, a_image, b_image, stick = u8(n, h, w, 3), u8(n, h, w, 3), u8(n, h, w, 3), u8(n, h, h, 3)
+    retain_mask = (rng.uniform(size=[n, h, h, 1]) < 0.5).astype(np.uint8)
+    patches, patches_l, den_u, den_l = u8(n, pu, ph, pw, 3), u8(n, pl, ph, pw, 3), u8(n, h, h, 3), u8(n, h, h, 3)
+
+    def restated(clothes):
+        stages = [dict(image=pad(image)[i], clothes=pad(clothes)[i], stick=stick[i], retain_mask=retain_mask[i],
+                       patches=patches[i].transpose(1, 2, 0, 3).reshape(ph, pw, 3 * pu),
+                       patches_lower=patches_l[i].transpose(1, 2, 0, 3).reshape(ph, pw, 3 * pl), denorm_upper=den_u[i], denorm_lower=den_l[i])
+                  for i in range(n)]
+        return FR.generator_inputs([FR.getitem(s) for s in stages], 'cuda')
+    want = dict(restated(a_image), clothes_lower=restated(b_image)['clothes'])
+    assert list(want) == TryOnOutfitBatch.KEYS
     N = _native()
     lib = N.lib()
-    shape = lambda k: dict(style_input=(n, 3 * (pu + pl), ph, pw), pose=(n, 6, h, h), denorm_upper_mask=(n, 1, h, h),
-                           denorm_lower_mask=(n, 1, h, h)).get(k, (n, 3, h, h))
-
-    def run(entry, keys, photos):
-        t = {k: torch.full(shape(k), float('nan'), device='cuda') for k in keys}
-        outs = (ctypes.c_void_p * len(keys))(*[t[k].data_ptr() for k in keys])
-        N.check(entry(*[N.ptr(x) for x in photos + rest], outs, n, h, w, pu, pl, ph, pw, N.stream()))
-        return t
-
-    outfit = run(lib.pasta_tryon_outfit_assemble, TryOnOutfitBatch.KEYS, [image, a_image, b_image])
-    upper = run(lib.pasta_tryon_region_assemble, TryOnRegionBatch.KEYS, [image, a_image])
-    lower = run(lib.pasta_tryon_region_assemble, TryOnRegionBatch.KEYS, [image, b_image])
-    for k in TryOnRegionBatch.KEYS:
-        assert torch.equal(outfit[k], upper[k]) and not torch.isnan(outfit[k]).any(), k
-    assert torch.equal(outfit['clothes_lower'], lower['clothes']) and not torch.equal(outfit['clothes_lower'], outfit['clothes'])
-    assert float(outfit['clothes_lower'][..., :(h - w) // 2].min()) == 1.0                   # white padding
-    with pytest.raises(RuntimeError, match='tryon_outfit_assemble: null pointer'):
-        run(lib.pasta_tryon_outfit_assemble, TryOnOutfitBatch.KEYS, [image, a_image, None])
-    with pytest.raises(RuntimeError, match='tryon_outfit_assemble: output 9 is null'):
-        t = {k: torch.empty(shape(k), device='cuda') for k in TryOnRegionBatch.KEYS}
-        outs = (ctypes.c_void_p * 10)(*[t[k].data_ptr() for k in TryOnRegionBatch.KEYS], None)
-        N.check(lib.pasta_tryon_outfit_assemble(*[N.ptr(x) for x in [image, a_image, b_image] + rest], outs, n, h, w, pu, pl, ph, pw, N.stream()))
+    photos = [_cu(x) for x in (image, a_image, b_image)]
+    rest = [_cu(x) for x in (retain_mask * pad(image), stick, patches, patches_l, den_u, den_l)]
+    outfit = {k: torch.full_like(want[k], float('nan')) for k in TryOnOutfitBatch.KEYS}
+    outs = (ctypes.c_void_p * 10)(*[outfit[k].data_ptr() for k in TryOnOutfitBatch.KEYS])
+    N.check(lib.pasta_tryon_outfit_assemble(*[N.ptr(x) for x in photos + rest], outs, n, h, w, pu, pl, ph, pw, N.stream()))
+    for k in TryOnOutfitBatch.KEYS:
+        assert torch.equal(outfit[k], want[k]) and not torch.isnan(outfit[k]).any(), k
+    assert not torch.equal(outfit['clothes_lower'], outfit['clothes'])
+    assert float(outfit['clothes_lower'][..., :lp].min()) == 1.0                             # white padding
+    with pytest.raises(RuntimeError, match='tryon_outfit_assemble: null photograph'):
+        N.check(lib.pasta_tryon_outfit_assemble(*[N.ptr(x) for x in photos[:2] + [None] + rest], outs, n, h, w, pu, pl, ph, pw, N.stream()))
+    with pytest.raises(RuntimeError, match='tryon_outfit_assemble: output 8 is null'):
+        outs = (ctypes.c_void_p * 10)(*[outfit[k].data_ptr() for k in TryOnOutfitBatch.KEYS[:8]], None, outfit['clothes_lower'].data_ptr())
+        N.check(lib.pasta_tryon_outfit_assemble(*[N.ptr(x) for x in photos + rest], outs, n, h, w, pu, pl, ph, pw, N.stream()))
 
 
 # ---- 2. and 3. the builder on the tree ----

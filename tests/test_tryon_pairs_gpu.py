@@ -67,24 +67,25 @@ def test_palm_box_and_pair_masks_equal_the_restatement():
     parsing[:, 200:230, 40:150] = 6
     image, d_image = (rng.integers(0, 256, [n, 256, 192, 3], dtype=np.uint8) for _ in range(2))
     lib = _lib().lib()
-    palm15 = _palm(lib.pasta_palm_mask_box_u8, parsing, kp, 25, 15)
-    assert np.array_equal(_palm(lib.pasta_palm_mask_box_u8, parsing, kp, 25, 16), _palm(lib.pasta_palm_mask_u8, parsing, kp))
+    palm15, palm16 = _palm(lib.pasta_palm_mask_u8, parsing, kp, 25, 15), _palm(lib.pasta_palm_mask_u8, parsing, kp, 25, 16)
     N = _lib()
     u8 = lambda: torch.empty([n, 256, 256, 3], dtype=torch.uint8, device='cuda')
-    outs = [u8() for _ in range(5)]                               # retain, lower img, lower mask, upper img, upper mask
+    outs = [u8() for _ in range(5)]                               # retain, upper img, upper mask, lower img, lower mask
+    # the pair: the upper garment's source is the donor, the lower garment's the person, label 6 in the lower garment
     ins = [_cu(a) for a in (image, parsing, palm15, d_image, d_parsing)]  # held: a freed input's memory would be reused by the next one
-    N.check(lib.pasta_tryon_pair_masks_u8(*[N.ptr(t) for t in ins + outs], n, 256, 192, N.stream()))
+    N.check(lib.pasta_tryon_outfit_masks_u8(*[N.ptr(t) for t in ins + ins[:2] + outs], n, 256, 192, 1, N.stream()))
     outs = [t.cpu().numpy() for t in outs]
     differs = 0
     for i in range(n):
         raw = dict(image=image[i], parsing=parsing[i], keypoints=kp[i], clothes_image=d_image[i], clothes_parsing=d_parsing[i], clothes_keypoints=d_kp[i])
         ref = PR.load_pair(raw)
         _, _, pad_parsing, shifted = PR.person_stages(image[i], parsing[i], kp[i])
-        differs += int((PR.palm_mask(shifted, pad_parsing[..., 0], 16) != ref['palm']).sum())
-        assert np.array_equal(palm15[i], ref['palm']), (i, 'palm')
-        for k, name in enumerate(('retain_img', 'lower_img', 'lower_mask', 'upper_img', 'upper_mask')):
+        ref16 = PR.palm_mask(shifted, pad_parsing[..., 0], 16)
+        differs += int((ref16 != ref['palm']).sum())
+        assert np.array_equal(palm15[i], ref['palm']) and np.array_equal(palm16[i], ref16), (i, 'palm')
+        for k, name in enumerate(('retain_img', 'upper_img', 'upper_mask', 'lower_img', 'lower_mask')):
             assert np.array_equal(outs[k][i], ref[name]), (i, name)
-    assert palm15.any() and differs > 0 and (outs[1] > 0).any()
+    assert palm15.any() and differs > 0 and (outs[3] > 0).any()
 
 
 def _composite_case(rng, n, parts):
@@ -120,7 +121,7 @@ def test_eroded_composite_equals_the_restatement(radius):
     out = torch.empty([n, 256, 256, 3], dtype=torch.uint8, device='cuda')
     pm = torch.empty([n, parts, 256, 256], dtype=torch.uint8, device='cuda')
     N.check(lib.pasta_patch_composite_eroded_u8(N.ptr(patches_t), N.ptr(masks_t), N.ptr(inv), N.ptr(val), N.ptr(out), N.ptr(pm), n, parts,
-                                                64, 64, 256, 256, radius, N.stream()))
+                                                64, 64, 256, 256, radius, None, N.stream()))
     out, pm = out.cpu().numpy(), pm.cpu().numpy()
     hits = 0
     for i in range(n):
@@ -168,9 +169,11 @@ def test_images_to_u8_equals_test_py_conversion():
 
 
 def test_pair_assemble_equals_test_py_expressions():
-    """The entry on its own, on random uint8 stages (composites with all-zero pixels and one pixel whose channels sum to 256):
-    the seven tensors equal test.py's torch expressions bit for bit.  N = 2, H = 20, P = 3 parts of 5 x 5: the 400 pixels do not
-    fill whole blocks of 256, so the image part and the style_input tail meet inside one block."""
+    """The seven-tensor form of pasta_tryon_outfit_assemble (outputs 0, 1 and 9 null, no photographs) on its own, on random
+    uint8 stages (composites with all-zero pixels and one pixel whose channels sum to 256): the seven tensors equal test.py's
+    torch expressions bit for bit.  N = 2, H = 20, P = 3 parts of 5 x 5: the 400 pixels do not fill whole blocks of 256, so the
+    image part and the style_input tail meet inside one block.  The width is not read without photographs: W = 12, what the
+    builder passes for such a square's canvas, and W = 20 give the same bits."""
     import ctypes
     from training.tryon_pairs import TryOnPairBatch
     rng = np.random.default_rng(4)
@@ -186,13 +189,16 @@ def test_pair_assemble_equals_test_py_expressions():
     want = PR.generator_inputs([PR.getitem(s) for s in stages], 'cuda')
     N = _lib()
     # contiguous NaN-filled outputs (the restated tensors keep the strides of getitem's transposed views)
-    t = {k: torch.full(want[k].shape, float('nan'), device='cuda') for k in TryOnPairBatch.KEYS}
-    outs = (ctypes.c_void_p * 7)(*[t[k].data_ptr() for k in TryOnPairBatch.KEYS])
-    ins = [_cu(a) for a in (retain_img, stick, patches, stick_patches, den_u, den_l)]
-    N.check(N.lib().pasta_tryon_pair_assemble(*[N.ptr(a) for a in ins], outs, n, h, parts, ph, pw, N.stream()))
-    for k in TryOnPairBatch.KEYS:
-        assert not torch.isnan(t[k]).any(), k                     # every element was written
-        assert t[k].shape == want[k].shape and torch.equal(t[k], want[k]), k
+    from training.tryon_batch import OUTFIT_OUTPUTS
+    assert OUTFIT_OUTPUTS[2:9] == TryOnPairBatch.KEYS
+    ins = [None] * 3 + [_cu(a) for a in (retain_img, stick, patches, stick_patches, den_u, den_l)]
+    for w in (12, 20):
+        t = {k: torch.full(want[k].shape, float('nan'), device='cuda') for k in TryOnPairBatch.KEYS}
+        outs = (ctypes.c_void_p * 10)(None, None, *[t[k].data_ptr() for k in TryOnPairBatch.KEYS], None)
+        N.check(N.lib().pasta_tryon_outfit_assemble(*[N.ptr(a) for a in ins], outs, n, h, w, parts, parts, ph, pw, N.stream()))
+        for k in TryOnPairBatch.KEYS:
+            assert not torch.isnan(t[k]).any(), (w, k)            # every element was written
+            assert t[k].shape == want[k].shape and torch.equal(t[k], want[k]), (w, k)
     assert tuple(t['style_input'].shape) == (n, 6 * parts, ph, pw) and tuple(t['pose'].shape) == (n, 6, h, h)
     assert t['denorm_upper_mask'][1, 0, 7, 13] == 1
     for k in ('denorm_upper_mask', 'denorm_lower_mask'):
