@@ -768,6 +768,54 @@ int pasta_region_image_stats(const float* images, const uint8_t* ref, const uint
 int pasta_parsing_confusion(const float* logits, const float* labels, int64_t* matrix, int N, int C, int H, int Wt, int c0, int W,
                             void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * PNG files of a batch of RGB8 images, encoded on the GPU (torch_utils/ops/png_encode.py; csrc/png_encode.hip).
+ * The stream is this project's own choice of a valid PNG:
+ *   1. every row is filter type 4 (Paeth, bpp 3) with left, up and upper-left taken from the ORIGINAL pixels, zero outside the
+ *      image; an image's filtered stream is H rows of 1 + 3 W bytes;
+ *   2. PASTA_PNG_ROWS consecutive rows are a SEGMENT: one dynamic-Huffman deflate block (BFINAL 0) followed by an empty stored
+ *      block (three header bits, BFINAL 1 only on the image's last segment, zeros to the byte boundary, 00 00 FF FF), so every
+ *      segment starts and ends on a byte boundary;
+ *   3. a segment's bytes are taken in tiles of 32 from its start; a full tile of zeros whose preceding byte in the image's
+ *      filtered stream exists and is zero is ONE match (symbol 272 with extra bits 01 = length 32, distance symbol 0 =
+ *      distance 1); every other byte is a literal; symbol 256 closes the block;
+ *   4. the literal/length code (286 symbols, at most 15 bits) and the code-length code (19 symbols, at most 7 bits) are
+ *      pasta_png_code_lengths of the segment's counts; HDIST = 0, the one distance code has length 1 with a match and 0 without;
+ *      the header sends the 287 lengths plainly, without the run symbols 16 / 17 / 18;
+ *   5. a segment's size follows from its counts and lengths, so every segment is written at its final place.
+ * The caller frames the file: signature, IHDR, ONE IDAT of 78 01 | segments | Adler-32 (big-endian), IEND.
+ * ------------------------------------------------------------------------- */
+#define PASTA_PNG_ROWS        16    /* rows of a segment */
+#define PASTA_PNG_SYMS        286   /* literal/length symbols */
+#define PASTA_PNG_META_WORDS  288   /* per segment from the filter pass: 286 token counts, then the two Adler parts */
+#define PASTA_PNG_TABLE_WORDS 354   /* per segment into the encode pass: 286 symbols, header bits, 0, 66 words of header */
+
+/* images [N, H, W, C] uint8 -> filtered [N, H, 1 + 3 W] uint8 and meta [N, S, PASTA_PNG_META_WORDS] uint32, S = ceil(H /
+ * PASTA_PNG_ROWS): words 0 .. 285 the segment's token counts (literals, 272 = matches, 256 = 1), word 286 = sum d_i mod 65521
+ * and word 287 = sum (n - i) d_i mod 65521 over the segment's n bytes d_0 .. d_{n-1}; the Adler-32 of the stream follows from
+ * A = 1, B = 0 and, per segment in order, B = (B + n A + s2) mod 65521, A = (A + s1) mod 65521.  One workgroup per (image,
+ * segment).  Refused: C != 3, N outside 1 .. 65535, H or W outside 1 .. 8192, a filtered stream of 2^31 bytes or more. */
+int pasta_png_filter(const uint8_t* images, uint8_t* filtered, uint32_t* meta, int N, int H, int W, int C, void* stream);
+
+/* HOST ONLY, launches nothing: Huffman code lengths of counts[0 .. n - 1], none above `limit` bits (1 .. 15), 0 exactly where
+ * the count is 0.  With two or more used symbols the code is COMPLETE, its Kraft sum exactly 1: inflate refuses an incomplete
+ * literal/length or code-length set as it refuses an over-subscribed one.  A lone used symbol gets length 1.  Equal to the
+ * unlimited Huffman code whenever that fits the limit.  n <= 288; refused when every count is 0 or 2^limit < used symbols. */
+int pasta_png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* lengths);
+
+/* HOST ONLY, launches nothing: meta [segments, PASTA_PNG_META_WORDS] as pasta_png_filter wrote it (HOST memory) -> tables
+ * [segments, PASTA_PNG_TABLE_WORDS] uint32 and seg_bytes [segments], the exact size of every segment.  A table: words 0 .. 285
+ * = bit-reversed code | bits << 24 of every symbol (272: the whole match, code | 01 | distance code 0, bits + 3), word 286 the
+ * number of header bits, words 288 .. the block header's bits from BFINAL on, least significant bit first. */
+int pasta_png_segment_tables(const uint32_t* meta, int64_t segments, uint32_t* tables, int64_t* seg_bytes);
+
+/* filtered and tables as above (device), offsets [N, S] int64 (device): the byte every segment starts at in out.  out: out_bytes
+ * bytes, ZEROED by the caller, 4-byte aligned, out_bytes a multiple of 4 and at least the last segment's end; nothing is
+ * written past it.  One workgroup per (image, segment), one tile of 32 bytes per thread; bits are OR-ed or stored as whole
+ * words, so the result does not depend on the order of execution. */
+int pasta_png_encode(const uint8_t* filtered, const uint32_t* tables, const int64_t* offsets, uint8_t* out, int64_t out_bytes,
+                     int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,12 +239,16 @@ ABI = {
     'pasta_parsing_confusion': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 6 + [_c_ptr]),
     'pasta_region_image_stats_workspace': (_c_i64, [ctypes.c_int] * 3),
     'pasta_region_image_stats': (ctypes.c_int, [_c_ptr] * 6 + [_c_i64] + [ctypes.c_int] * 9 + [_c_ptr]),
+    'pasta_png_filter': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 4 + [_c_ptr]),
+    'pasta_png_code_lengths': (ctypes.c_int, [_c_ptr, ctypes.c_int, ctypes.c_int, _c_ptr]),
+    'pasta_png_segment_tables': (ctypes.c_int, [_c_ptr, _c_i64, _c_ptr, _c_ptr]),
+    'pasta_png_encode': (ctypes.c_int, [_c_ptr] * 4 + [_c_i64] + [ctypes.c_int] * 3 + [_c_ptr]),
 }
 
 # Entries added to the current ABI after its first release (purely additive, so the version did not move): a library built before
-# them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  None at 22: a
-# library that reports 22 has every symbol of ABI.
-LATE_ENTRIES = frozenset()
+# them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  At 22: the PNG
+# encoder's four entries (csrc/png_encode.hip).
+LATE_ENTRIES = frozenset(['pasta_png_filter', 'pasta_png_code_lengths', 'pasta_png_segment_tables', 'pasta_png_encode'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

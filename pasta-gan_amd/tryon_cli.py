@@ -32,8 +32,8 @@ def _local_snapshot(path):
 
 
 def shared_options(dataroot_help, batchsize):
-    """The decorator of the options both command lines take up to --storage, in the order --help prints them; each command line
-    puts its own options and --workers (``workers_option``) below it."""
+    """The decorator of the options both command lines take up to --storage and --png-encoder, in the order --help prints them;
+    each command line puts its own options and --workers (``workers_option``) below it."""
     options = [
         click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True),
         click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)'),
@@ -45,7 +45,7 @@ def shared_options(dataroot_help, batchsize):
         click.option('--outdir', help='Where to save the output images', type=str, required=True, metavar='DIR'),
         click.option('--dataroot', help=dataroot_help, type=str, required=True),
         click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=batchsize, show_default=True),
-        storage_option]
+        storage_option, png_encoder_option]
 
     def decorate(f):
         for option in reversed(options):
@@ -58,6 +58,32 @@ def shared_options(dataroot_help, batchsize):
 STORAGE_DTYPES = {'snapshot': None, 'f32': 'float32', 'bf16': 'bfloat16', 'f16': 'float16'}
 storage_option = click.option('--storage', help='Activation storage the generator runs in: as pickled (snapshot), or f32, bf16, f16 '
                               '[default: snapshot]', type=click.Choice(list(STORAGE_DTYPES)))
+
+# --png-encoder: who turns the uint8 batch into PNG files: PIL in this process, one image at a time, or the GPU.  The
+# option comes with ``shared_options`` and hands the commands' callbacks no argument: its value is recorded in the click context,
+# where ``generate_256`` and ``generate_512`` find it (``_chosen_encoder``), as ``_explicit_region`` finds where a region came from.
+_ENCODER_KEY = 'pasta.png_encoder'
+
+
+def _record_encoder(context, param, value):
+    context.meta[_ENCODER_KEY] = value
+    return value
+
+
+png_encoder_option = click.option('--png-encoder', help='Who encodes the PNG files: PIL on the host, one image at a time, or the GPU, a batch '
+                                  'at a time (torch_utils/ops/png_encode.py; the same pixels in larger files)',
+                                  type=click.Choice(['pil', 'gpu']), default='pil', show_default=True, expose_value=False,
+                                  callback=_record_encoder)
+
+
+def _chosen_encoder(png_encoder):
+    """The ``png_encoder`` keyword of ``generate_256`` / ``generate_512``; left at 'pil' under a running command line, it is what
+    that command line's --png-encoder said.  A call without a click context has only the keyword."""
+    context = click.get_current_context(silent=True)
+    if png_encoder == 'pil' and context is not None:
+        return context.meta.get(_ENCODER_KEY, png_encoder)
+    return png_encoder
+
 
 scores_option = click.option(
     '--scores', 'scores_file', type=str, metavar='FILE',
@@ -152,18 +178,24 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
         f.write(line + '\n')
 
 
-def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None):
+def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None,
+          png_encoder='pil'):
     """The loop of both command lines.  ``choose(device)`` -> (data set, collate function, builder, ``pictures``), called once the
     snapshot is loaded; ``pictures(batch, raw, gen_imgs, count)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names under
     ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
-    item i is ``pair_z(i)`` and the region scores of metrics/tryon_fidelity.py over what is written go to FILE (``write_scores``)."""
+    item i is ``pair_z(i)`` and the region scores of metrics/tryon_fidelity.py over what is written go to FILE (``write_scores``).
+    ``png_encoder``: 'pil' copies the batch to the host and saves image by image; 'gpu' encodes the batch where it is
+    (torch_utils.ops.png_encode.save) and copies back the compressed bytes.  Names, layout and scores are settled before either."""
     _local_snapshot(network_pkl)
+    if png_encoder not in ('pil', 'gpu'):
+        raise click.BadParameter('%r is not one of pil, gpu' % (png_encoder,), param_hint='--png-encoder')
 
     import numpy as np
     import PIL.Image
     import torch
 
     from metrics import tryon_fidelity
+    from torch_utils.ops import png_encode
 
     device = torch.device('cuda')
     G = load_generator(network_pkl, device, storage)
@@ -185,6 +217,10 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
             tryon_fidelity.score_batch(gen_imgs, batch, index, partials)
             pixels = raw['people_image'].shape[1] * raw['people_image'].shape[2]
         images, names = pictures(batch, raw, gen_imgs, count)
+        if png_encoder == 'gpu':
+            png_encode.save(images, [os.path.join(outdir, name) for name in names])
+            count += len(names)
+            continue
         for img, name in zip(images.cpu().numpy(), names):
             os.makedirs(os.path.dirname(os.path.join(outdir, name)), exist_ok=True)
             PIL.Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(outdir, name))
@@ -195,14 +231,14 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
 
 
 def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
-                 scores_file=None, storage=None):
+                 scores_file=None, storage=None, png_encoder='pil'):
     """test_512.py: the 512 x 320 model on outfits, prepared by training.tryon_regions.TryOnOutfitBatchBuilder and written to
     ``<outdir>/<count>.png`` in list order.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_512_test), written as ``upper donor | lower donor | person | generated`` (512 x 2048).
     Without it: the pairs of the pair lists as the outfits of ``change_region`` (None means full body), written as the reference
     writes them, ``clothes | person | generated`` with the DONOR as ``clothes``, who for 'lowerbody' owns the lower garment.
     A ``change_region`` other than None is refused together with --outfits, since a line names whose garments are worn, and that
-    is refused before anything is read."""
+    is refused before anything is read.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
 
@@ -226,18 +262,19 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             images = torch.cat([images_to_u8(x, 0, side) for x in [t[k] for k in panels] + [gen_imgs]], dim=2)
             return images, [str(count + i).zfill(3) + '.png' for i in range(batch.batch)]
         return dataset, collate_fn, TryOnOutfitBatchBuilder(device), pictures
-    dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage)
+    dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage,
+          png_encoder=_chosen_encoder(png_encoder))
 
 
 def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
-                 scores_file=None, storage=None):
+                 scores_file=None, storage=None, png_encoder='pil'):
     """test.py: the 256 x 192 model on outfits, prepared by training.tryon_pairs.TryOnPairOutfitBatchBuilder; only the generated
     image is written, columns 32..223 of the generator's square.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
     stem>.png``, a kept garment under the person's stem.  Without it: the pairs of the pair lists as the outfits (P, D, -),
     (P, -, D) or (P, D, D) of ``change_region`` (None: upper body, the reference's run), written to ``<person stem>__<clothes
     stem>.png``.  The two exclude each other, and that is refused before anything is read.  The --scores report's ``mode`` is
-    ``outfits`` or ``change-region <region>``; a run with neither option has none."""
+    ``outfits`` or ``change-region <region>``; a run with neither option has none.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
 
@@ -259,4 +296,5 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             return images_to_u8(gen_imgs, (height - width) // 2, width), names
         return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device), pictures
     mode = 'outfits' if outfits_file is not None else change_region and 'change-region ' + change_region
-    dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode)
+    dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode,
+          _chosen_encoder(png_encoder))
