@@ -617,6 +617,24 @@ int pasta_tryon_outfit_assemble(const uint8_t* image, const uint8_t* upper_donor
  * undefined). */
 int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, int c0, int W, void* stream);
 
+/* The photograph's kept parts pasted into the generated bytes (this project's own rule; --kept-parts photo of test.py and
+ * test_512.py, training/tryon_pairs.py's images_keep_to_u8), in the launch that makes the bytes, so that they are never
+ * written uncomposited.  Per image: g = the bytes pasta_images_to_u8 writes for columns c0 .. c0 + W - 1 of images
+ * [N, 3, H, Wt] fp32 (a NaN is 0 here too); p = photo [N, H, W, 3] uint8, the person's photograph; k = (keep [N, H, W] uint8
+ * != 0), the kept flag; r = radius, 0..8, the feather; K = (2r + 1)^2.  For pixel (y, x):
+ *   s = how many of the K positions (y + dy, x + dx), |dy|, |dx| <= r, lie outside the image or have k = 1.  A position
+ *       outside the image counts as kept, as the border of csrc/patch_erode.h's erosion does not erode: hair that touches the
+ *       top edge is not faded;
+ *   a = k(y, x) ? s : 0.  Nothing of the photograph is taken from outside the kept region, so the old garment at the neck
+ *       cannot leak in;
+ *   out_c = (g_c * (K - a) + p_c * a + K / 2) / K per channel, in integers with a floor division.
+ * So a = K, every pixel whose whole window is kept, gives the photograph's byte; a = 0, every pixel outside the region, gives
+ * the generated byte; r = 0 is the hard paste k ? p : g; in between the weight rises linearly with the kept share of the
+ * window, and every byte lies between g_c and p_c.  Refused before any launch: a null pointer, the shape and crop conditions
+ * of pasta_images_to_u8, a radius outside 0..8. */
+int pasta_images_keep_to_u8(const float* images, const uint8_t* photo, const uint8_t* keep, uint8_t* out, int N, int H, int Wt, int c0,
+                            int W, int radius, void* stream);
+
 /* An OUTFIT at 256 x 192 (this project's own; training/tryon_pairs.py, TryOnPairOutfitBatchBuilder): (P, U, L), the person P in
  * the upper garment of U and the lower garment of L, either of whom may be P.  The pair rules above with a source per garment:
  *   1. retain_img, the palm mask (boxes 25 and 15), the stick figure in `pose` and every M_inv are P's;

@@ -18,7 +18,9 @@
 //                                      with clothes_lower (the lower garment's donor) ten;
 //   pasta_tryon_train_region_assemble  the erase mask from two eroded arm-part masks and the nine fp32 tensors of the loop at
 //                                      512 x 320 (the label masks of that set are csrc/tryon_inputs.hip's pasta_tryon_masks_u8);
-//   pasta_images_to_u8                 test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137).
+//   pasta_images_to_u8                 test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137);
+//   pasta_images_keep_to_u8            the same with the photograph's kept parts pasted in under a feathered weight (this
+//                                      project's own, --kept-parts photo), in the one launch.
 // The 256 pairs are the 512 rules with label 6 added to the lower garment, stick patches as the second patch list and no image /
 // clothes tensors.  The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures
 // csrc/tryon_inputs.hip's entry.  include/pasta_hip.h lists where the data sets differ and the constants each one passes.
@@ -186,6 +188,114 @@ __global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restri
     for (int ch = 0; ch < 3; ch++) o[ch] = unit_to_u8(src[(((int64_t)n * 3 + ch) * H + y) * Wt + c0 + x]);
 }
 
+// ---- generated images to uint8 with the photograph's kept parts pasted in ----
+
+// include/pasta_hip.h's rule of pasta_images_keep_to_u8 (this project's own).  A block of 256 threads makes a tile of 16 rows by
+// 16 * PX columns, PX adjacent pixels of a row per thread: PX = 4 where the entry found every row of every tensor aligned for it
+// (16-byte loads of the three fp32 planes, one 12-byte load of the photograph and one 12-byte store), PX = 1 for any other
+// width.  The kept flags of the tile and an r-pixel halo (1 outside the image) go to LDS as bytes, are summed along rows (at
+// most 17, a byte) and then along columns into a register (at most 289).  r is the launch's scalar; with r == 0 the pixel's own
+// flag decides and the kernel touches neither LDS nor a barrier (csrc/patch_erode.h's convention).
+constexpr int KC_TY = 16;           // tile rows
+constexpr int KC_MAX_R = 8;         // largest feather radius (a 17 x 17 window)
+
+template <int PX>
+__global__ __launch_bounds__(256) void images_keep_to_u8_kernel(const float* __restrict__ src, const uint8_t* __restrict__ photo,
+                                                                const uint8_t* __restrict__ keep, uint8_t* __restrict__ dst, int H, int Wt,
+                                                                int c0, int W, int r, int tiles_x) {
+    constexpr int TX = 16 * PX;
+    __shared__ uint8_t flags[(KC_TY + 2 * KC_MAX_R) * (TX + 2 * KC_MAX_R)];
+    __shared__ __attribute__((aligned(4))) uint8_t rows[(KC_TY + 2 * KC_MAX_R) * TX];
+    const int n = blockIdx.y;
+    const int tx0 = (blockIdx.x % tiles_x) * TX, ty0 = (blockIdx.x / tiles_x) * KC_TY;
+    const int ty = threadIdx.x / 16, tg = (threadIdx.x % 16) * PX;
+    const int y = ty0 + ty, x = tx0 + tg;
+    const bool mine = y < H && x < W;           // PX == 4: W is a multiple of 4, so a thread's four pixels are inside together
+    const uint8_t* kp = keep + (int64_t)n * H * W;
+    const int64_t pix = ((int64_t)n * H + y) * W + x;
+
+    float g[3][PX];                             // every global load of the pixels before the LDS phases
+    uint8_t p[3 * PX];
+    if (mine) {
+        for (int ch = 0; ch < 3; ch++) {
+            const float* s = src + (((int64_t)n * 3 + ch) * H + y) * Wt + c0 + x;
+            if constexpr (PX == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(s);
+                g[ch][0] = v.x; g[ch][1] = v.y; g[ch][2] = v.z; g[ch][3] = v.w;
+            } else {
+                g[ch][0] = s[0];
+            }
+        }
+        if constexpr (PX == 4) {
+            const Px4 px = load_px4(photo + pix * 3);
+            for (int i = 0; i < 12; i++) p[i] = px.v[i];
+        } else {
+            for (int i = 0; i < 3; i++) p[i] = photo[pix * 3 + i];
+        }
+    }
+
+    int a[PX];                                  // the photograph's weight out of K
+    if (r > 0) {                                // uniform across the launch
+        const int SX = TX + 2 * r, SY = KC_TY + 2 * r;
+        for (int i = threadIdx.x; i < SY * SX; i += 256) {
+            const int gy = ty0 - r + i / SX, gx = tx0 - r + i % SX;
+            flags[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? kp[(int64_t)gy * W + gx] != 0 : 1;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < SY * 16; i += 256) {     // PX adjacent row sums per item, a sliding window
+            const int ry = i / 16, cx = (i % 16) * PX;
+            const uint8_t* f = flags + ry * SX + cx;
+            int s = 0;
+            for (int d = 0; d <= 2 * r; d++) s += f[d];
+            for (int j = 0; j < PX; j++) {
+                rows[ry * TX + cx + j] = (uint8_t)s;
+                if (j + 1 < PX) s += f[j + 2 * r + 1] - f[j];
+            }
+        }
+        __syncthreads();
+        for (int j = 0; j < PX; j++) a[j] = 0;
+        for (int d = 0; d <= 2 * r; d++) {
+            const uint8_t* rp = rows + (ty + d) * TX + tg;
+            if constexpr (PX == 4) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
+                for (int j = 0; j < 4; j++) a[j] += (w >> (8 * j)) & 255;
+            } else {
+                a[0] += rp[0];
+            }
+        }
+        for (int j = 0; j < PX; j++)
+            if (!flags[(ty + r) * SX + tg + r + j]) a[j] = 0;
+    } else if (mine) {
+        if constexpr (PX == 4) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(kp + (int64_t)y * W + x);
+            for (int j = 0; j < 4; j++) a[j] = ((w >> (8 * j)) & 255) != 0;
+        } else {
+            a[0] = kp[(int64_t)y * W + x] != 0;
+        }
+    }
+    if (!mine) return;                          // after the last barrier
+
+    // (g (K - a) + p a + K / 2) / K by a multiplication: m = ceil(2^32 / K) gives the floor quotient of every numerator up to
+    // 2^32 / K, and the largest here is 255 * 289 + 144.  K is odd and at least 9 in this branch; r == 0 divides nothing.
+    const uint32_t K = (uint32_t)((2 * r + 1) * (2 * r + 1));
+    const uint32_t m = 0xFFFFFFFFu / K + 1;
+    uint8_t o[3 * PX];
+    for (int j = 0; j < PX; j++)
+        for (int ch = 0; ch < 3; ch++) {
+            const uint32_t gb = unit_to_u8(g[ch][j]), pb = p[3 * j + ch], w = (uint32_t)a[j];
+            o[3 * j + ch] = r > 0 ? (uint8_t)__umulhi(gb * (K - w) + pb * w + K / 2, m) : (uint8_t)(w ? pb : gb);
+        }
+    if constexpr (PX == 4) {
+        uint3 words;
+        words.x = o[0] | o[1] << 8 | o[2] << 16 | (uint32_t)o[3] << 24;
+        words.y = o[4] | o[5] << 8 | o[6] << 16 | (uint32_t)o[7] << 24;
+        words.z = o[8] | o[9] << 8 | o[10] << 16 | (uint32_t)o[11] << 24;
+        *reinterpret_cast<uint3*>(dst + pix * 3) = words;
+    } else {
+        for (int i = 0; i < 3; i++) dst[pix * 3 + i] = o[i];
+    }
+}
+
 }  // namespace pasta
 
 extern "C" int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S, int W,
@@ -289,4 +399,26 @@ extern "C" int pasta_images_to_u8(const float* images, uint8_t* out, int N, int 
     dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)N);
     hipLaunchKernelGGL(images_to_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, images, out, H, Wt, c0, W);
     return launch_status("images_to_u8");
+}
+
+extern "C" int pasta_images_keep_to_u8(const float* images, const uint8_t* photo, const uint8_t* keep, uint8_t* out, int N, int H, int Wt,
+                                       int c0, int W, int radius, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(images && photo && keep && out, "images_keep_to_u8: null pointer");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && Wt >= 1 && Wt <= 4096 && W >= 1 && c0 >= 0 && c0 + W <= Wt,
+                "images_keep_to_u8: bad shape or crop (columns %d + %d of %d)", c0, W, Wt);
+    PASTA_CHECK(radius >= 0 && radius <= KC_MAX_R, "images_keep_to_u8: radius %d (0..%d)", radius, KC_MAX_R);
+    // four pixels per thread where every row of every tensor starts on the boundary its wide access needs
+    const bool wide = W % 4 == 0 && Wt % 4 == 0 && c0 % 4 == 0 && (uintptr_t)images % 16 == 0 && (uintptr_t)photo % 4 == 0 &&
+                      (uintptr_t)keep % 4 == 0 && (uintptr_t)out % 4 == 0;
+    const int tile_w = wide ? 64 : 16;
+    const int tiles_x = (W + tile_w - 1) / tile_w, tiles_y = (H + KC_TY - 1) / KC_TY;
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N);
+    if (wide)
+        hipLaunchKernelGGL(images_keep_to_u8_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, images, photo, keep, out, H, Wt, c0, W, radius,
+                           tiles_x);
+    else
+        hipLaunchKernelGGL(images_keep_to_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, images, photo, keep, out, H, Wt, c0, W, radius,
+                           tiles_x);
+    return launch_status("images_keep_to_u8");
 }

@@ -10,6 +10,9 @@ the host in four loader processes, as a few launches per batch:
                                                  sample (csrc/patches.hip, csrc/tryon_pairs.hip)
     pasta_tryon_outfit_assemble       the seven fp32 tensors G takes (its outputs 2..8)
 
+and, after the generator, ``images_to_u8`` (pasta_images_to_u8: the bytes test.py writes) or, with --kept-parts photo,
+``images_keep_to_u8`` (pasta_images_keep_to_u8: those bytes with the photograph's kept parts pasted in, one launch).
+
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads).
@@ -132,4 +135,39 @@ def images_to_u8(images, c0, width):
     out = torch.empty([n, h, width, 3], dtype=torch.uint8, device=images.device)
     with torch.cuda.device(images.device):
         _native.check(_native.lib().pasta_images_to_u8(_native.ptr(images), _native.ptr(out), n, h, wt, c0, width, _native.stream()))
+    return out
+
+
+KEEP_MAX_RADIUS = 8         # the largest feather of images_keep_to_u8: a 17 x 17 window (csrc/tryon_pairs.hip's KC_MAX_R)
+
+
+def images_keep_to_u8(images, c0, width, photo, keep, radius):
+    """``images_to_u8`` with the photograph's kept parts pasted in, in the same launch (include/pasta_hip.h,
+    pasta_images_keep_to_u8; this project's own rule): fp32 [N, 3, H, Wt], ``photo`` uint8 [N, H, width, 3], ``keep`` uint8
+    [N, H, width] (non-zero: kept, metrics.tryon_fidelity.keep_mask) -> uint8 [N, H, width, 3].  Where the whole
+    (2 radius + 1)^2 window round a kept pixel is kept (or outside the image) the byte is the photograph's, outside the kept
+    region it is ``images_to_u8``'s, in between a weighted mean of the two; radius 0 is a hard paste.  Refuses with ValueError."""
+    for name, t in (('images', images), ('photo', photo), ('keep', keep)):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+            raise ValueError('images_keep_to_u8: %s is not a tensor on the GPU (there is no CPU path)' % name)
+    if images.dtype != torch.float32 or photo.dtype != torch.uint8 or keep.dtype != torch.uint8:
+        raise ValueError('images_keep_to_u8: images fp32, photo and keep uint8, not %s, %s, %s' % (images.dtype, photo.dtype, keep.dtype))
+    if images.ndim != 4 or images.shape[1] != 3:
+        raise ValueError('images_keep_to_u8: images [N, 3, H, Wt], not %s' % (list(images.shape),))
+    n, _, h, wt = images.shape
+    c0, width = int(c0), int(width)
+    if width < 1 or c0 < 0 or c0 + width > wt:
+        raise ValueError('images_keep_to_u8: columns %d + %d of %d' % (c0, width, wt))
+    if tuple(photo.shape) != (n, h, width, 3) or tuple(keep.shape) != (n, h, width):
+        raise ValueError('images_keep_to_u8: photo %s and keep %s for images %s and width %d'
+                         % (list(photo.shape), list(keep.shape), list(images.shape), width))
+    if photo.device != images.device or keep.device != images.device:
+        raise ValueError('images_keep_to_u8: tensors on different devices')
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= KEEP_MAX_RADIUS:
+        raise ValueError('images_keep_to_u8: radius %r (an integer 0..%d)' % (radius, KEEP_MAX_RADIUS))
+    images, photo, keep = images.contiguous(), photo.contiguous(), keep.contiguous()
+    out = torch.empty([n, h, width, 3], dtype=torch.uint8, device=images.device)
+    with torch.cuda.device(images.device):
+        _native.check(_native.lib().pasta_images_keep_to_u8(_native.ptr(images), _native.ptr(photo), _native.ptr(keep), _native.ptr(out), n, h,
+                                                            wt, c0, width, radius, _native.stream()))
     return out

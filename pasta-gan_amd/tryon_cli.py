@@ -32,8 +32,8 @@ def _local_snapshot(path):
 
 
 def shared_options(dataroot_help, batchsize):
-    """The decorator of the options both command lines take up to --storage and --png-encoder, in the order --help prints them;
-    each command line puts its own options and --workers (``workers_option``) below it."""
+    """The decorator of the options both command lines take up to --storage, --png-encoder and the two --kept options, in the
+    order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
     options = [
         click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True),
         click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)'),
@@ -45,7 +45,7 @@ def shared_options(dataroot_help, batchsize):
         click.option('--outdir', help='Where to save the output images', type=str, required=True, metavar='DIR'),
         click.option('--dataroot', help=dataroot_help, type=str, required=True),
         click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=batchsize, show_default=True),
-        storage_option, png_encoder_option]
+        storage_option, png_encoder_option, kept_parts_option, kept_feather_option]
 
     def decorate(f):
         for option in reversed(options):
@@ -83,6 +83,53 @@ def _chosen_encoder(png_encoder):
     if png_encoder == 'pil' and context is not None:
         return context.meta.get(_ENCODER_KEY, png_encoder)
     return png_encoder
+
+
+# --kept-parts photo: the photograph's head, palms and shoes (metrics.tryon_fidelity.keep_mask, the region `retain` carries) are
+# pasted into the generated picture where its bytes are made (training.tryon_pairs.images_keep_to_u8), feathered over
+# --kept-feather pixels.  Both options come with ``shared_options`` and, like --png-encoder, hand the commands' callbacks no
+# argument (test.py and test_512.py are untouched): their values are recorded in the click context, where ``_kept_radius`` finds
+# them when the keywords ``kept_parts`` / ``kept_feather`` of ``generate_256`` / ``generate_512`` are left at their defaults.
+_KEPT_PARTS_KEY, _KEPT_FEATHER_KEY = 'pasta.kept_parts', 'pasta.kept_feather'
+KEPT_PARTS = ('generated', 'photo')
+KEPT_FEATHER_DEFAULT = 2            # the 5 x 5 window of the project's erosions
+KEPT_FEATHER_MAX = 8
+
+
+def _record(key):
+    def record(context, param, value):
+        context.meta[key] = value
+        return value
+    return record
+
+
+kept_parts_option = click.option('--kept-parts', help='Where the written head, palms and shoes come from: the generator, or the person\'s '
+                                 'photograph, pasted in on the GPU', type=click.Choice(list(KEPT_PARTS)), default='generated', show_default=True,
+                                 expose_value=False, callback=_record(_KEPT_PARTS_KEY))
+kept_feather_option = click.option('--kept-feather', help='With --kept-parts photo: the paste fades over R pixels inside the kept region, '
+                                   '0 for a hard edge [default: %d]' % KEPT_FEATHER_DEFAULT, type=click.IntRange(0, KEPT_FEATHER_MAX),
+                                   metavar='R', expose_value=False, callback=_record(_KEPT_FEATHER_KEY))
+
+
+def _kept_radius(kept_parts, kept_feather):
+    """The feather radius of a run with --kept-parts photo, None for a run that writes the generator's own pixels.  A feather
+    without the paste is a usage error; the two generate functions raise it before anything is read.  Keywords left at their
+    defaults ('generated', None) under a running command line are what that command line's options said; a call without a click
+    context has only the keywords."""
+    context = click.get_current_context(silent=True)
+    if context is not None and kept_parts == 'generated' and kept_feather is None:
+        kept_parts = context.meta.get(_KEPT_PARTS_KEY, kept_parts)
+        kept_feather = context.meta.get(_KEPT_FEATHER_KEY, kept_feather)
+    if kept_parts not in KEPT_PARTS:
+        raise click.BadParameter('%r is not one of %s' % (kept_parts, ', '.join(KEPT_PARTS)), param_hint='--kept-parts')
+    if kept_feather is not None and (isinstance(kept_feather, bool) or not isinstance(kept_feather, int)
+                                     or not 0 <= kept_feather <= KEPT_FEATHER_MAX):
+        raise click.BadParameter('%r is not an integer 0..%d' % (kept_feather, KEPT_FEATHER_MAX), param_hint='--kept-feather')
+    if kept_parts != 'photo':
+        if kept_feather is not None:
+            raise click.UsageError('--kept-feather needs --kept-parts photo: without it nothing is pasted')
+        return None
+    return KEPT_FEATHER_DEFAULT if kept_feather is None else kept_feather
 
 
 scores_option = click.option(
@@ -160,9 +207,10 @@ def generate(G, t, gen_z, truncation_psi, noise_mode):
                            t['denorm_lower_mask'], noise_mode=noise_mode)[1]
 
 
-def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None):
+def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None, kept_radius=None):
     """--scores: the figures of ``metrics.tryon_fidelity.finish`` (prefix ``tryon``) and what the run was, as one JSON line,
-    printed and written to ``scores_file``.  ``mode``: what was dressed, when it was not the plain pair lists."""
+    printed and written to ``scores_file``.  ``mode``: what was dressed, when it was not the plain pair lists; ``kept_radius``:
+    the feather of a run with --kept-parts photo, whose report says so."""
     import json
     from metrics import tryon_fidelity
     report = dict(results=tryon_fidelity.finish(partials, 'tryon', pixels=pixels), pairs=pairs, network=network_pkl, dataroot=dataroot,
@@ -171,6 +219,8 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
         report['storage'] = storage
     if mode is not None:
         report['mode'] = mode
+    if kept_radius is not None:
+        report['kept_parts'], report['kept_feather'] = 'photo', kept_radius
     line = json.dumps(report)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
@@ -179,11 +229,15 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
 
 
 def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None,
-          png_encoder='pil'):
+          kept_radius=None, png_encoder='pil'):
     """The loop of both command lines.  ``choose(device)`` -> (data set, collate function, builder, ``pictures``), called once the
-    snapshot is loaded; ``pictures(batch, raw, gen_imgs, count)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names under
-    ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
+    snapshot is loaded; ``pictures(batch, raw, gen_imgs, count, content)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names
+    under ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
     item i is ``pair_z(i)`` and the region scores of metrics/tryon_fidelity.py over what is written go to FILE (``write_scores``).
+    ``kept_radius`` (``_kept_radius``; None: the generator's own pixels, and ``content`` is None): the batches keep their stages,
+    and ``content``, uint8 [N, H, W, 3], is the generated picture's content columns with the photograph's kept parts
+    (``tryon_fidelity.keep_mask``) pasted in by ``images_keep_to_u8``; the scores are then those of these bytes, handed to
+    ``score_batch`` as the centres (b + 0.5) / 127.5 - 1 of the bytes' intervals, which ``unit_to_u8`` returns to b.
     ``png_encoder``: 'pil' copies the batch to the host and saves image by image; 'gpu' encodes the batch where it is
     (torch_utils.ops.png_encode.save) and copies back the compressed bytes.  Names, layout and scores are settled before either."""
     _local_snapshot(network_pkl)
@@ -196,6 +250,7 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
 
     from metrics import tryon_fidelity
     from torch_utils.ops import png_encode
+    from training.tryon_pairs import images_keep_to_u8
 
     device = torch.device('cuda')
     G = load_generator(network_pkl, device, storage)
@@ -207,16 +262,24 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
     pixels = tryon_fidelity.PIXELS                                  # content pixels of an item; every batch brings its own
     count = 0
     for raw in loader:
-        batch = builder.build(raw, keep_stages=scoring)
+        batch = builder.build(raw, keep_stages=scoring or kept_radius is not None)
         gen_z = torch.empty([batch.batch, 0], device=device)
         if scoring:
             index = raw['raw_idx'].tolist()                         # the items' positions in the pair lists, or in the outfit list
             gen_z = tryon_fidelity.pair_z(index, G.z_dim, device)
         gen_imgs = generate(G, batch.tensors, gen_z, truncation_psi, noise_mode)
+        content, scored = None, gen_imgs
+        if kept_radius is not None:
+            photo = batch.stages['image']
+            c0, width = (photo.shape[1] - photo.shape[2]) // 2, photo.shape[2]
+            content = images_keep_to_u8(gen_imgs, c0, width, photo, tryon_fidelity.keep_mask(batch.stages), kept_radius)
+            if scoring:
+                scored = gen_imgs.to(torch.float32).clone()
+                scored[:, :, :, c0:c0 + width] = ((content.to(torch.float32) + 0.5) / 127.5 - 1).permute(0, 3, 1, 2)
         if scoring:
-            tryon_fidelity.score_batch(gen_imgs, batch, index, partials)
+            tryon_fidelity.score_batch(scored, batch, index, partials)
             pixels = raw['people_image'].shape[1] * raw['people_image'].shape[2]
-        images, names = pictures(batch, raw, gen_imgs, count)
+        images, names = pictures(batch, raw, gen_imgs, count, content)
         if png_encoder == 'gpu':
             png_encode.save(images, [os.path.join(outdir, name) for name in names])
             count += len(names)
@@ -227,20 +290,23 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
             count += 1
     print('finish: %d images under %s' % (count, outdir))
     if scoring:
-        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode)
+        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius)
 
 
 def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
-                 scores_file=None, storage=None, png_encoder='pil'):
+                 scores_file=None, storage=None, kept_parts='generated', kept_feather=None, png_encoder='pil'):
     """test_512.py: the 512 x 320 model on outfits, prepared by training.tryon_regions.TryOnOutfitBatchBuilder and written to
     ``<outdir>/<count>.png`` in list order.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_512_test), written as ``upper donor | lower donor | person | generated`` (512 x 2048).
     Without it: the pairs of the pair lists as the outfits of ``change_region`` (None means full body), written as the reference
     writes them, ``clothes | person | generated`` with the DONOR as ``clothes``, who for 'lowerbody' owns the lower garment.
     A ``change_region`` other than None is refused together with --outfits, since a line names whose garments are worn, and that
-    is refused before anything is read.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
+    is refused before anything is read.  ``kept_parts`` 'photo' with ``kept_feather`` (None: 2): the ``generated`` panel's content
+    columns carry the photograph's kept parts (``dress``), the other panels and the panel's padding are untouched; a feather
+    without it is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
+    kept_radius = _kept_radius(kept_parts, kept_feather)
 
     def choose(device):
         import torch
@@ -256,27 +322,33 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             collate_fn = functools.partial(custom_dataset.collate_region_outfits, region)
             panels = ('clothes_lower' if region == 'lowerbody' else 'clothes', 'image')
 
-        def pictures(batch, raw, gen_imgs, count):
+        def pictures(batch, raw, gen_imgs, count, content):
             t = batch.tensors
             side = t['image'].shape[2]
             images = torch.cat([images_to_u8(x, 0, side) for x in [t[k] for k in panels] + [gen_imgs]], dim=2)
+            if content is not None:             # the last panel's content columns; its padding stays the generator's
+                c0 = len(panels) * side + (side - content.shape[2]) // 2
+                images[:, :, c0:c0 + content.shape[2]] = content
             return images, [str(count + i).zfill(3) + '.png' for i in range(batch.batch)]
         return dataset, collate_fn, TryOnOutfitBatchBuilder(device), pictures
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage,
-          png_encoder=_chosen_encoder(png_encoder))
+          kept_radius=kept_radius, png_encoder=_chosen_encoder(png_encoder))
 
 
 def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
-                 scores_file=None, storage=None, png_encoder='pil'):
+                 scores_file=None, storage=None, kept_parts='generated', kept_feather=None, png_encoder='pil'):
     """test.py: the 256 x 192 model on outfits, prepared by training.tryon_pairs.TryOnPairOutfitBatchBuilder; only the generated
     image is written, columns 32..223 of the generator's square.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
     stem>.png``, a kept garment under the person's stem.  Without it: the pairs of the pair lists as the outfits (P, D, -),
     (P, -, D) or (P, D, D) of ``change_region`` (None: upper body, the reference's run), written to ``<person stem>__<clothes
     stem>.png``.  The two exclude each other, and that is refused before anything is read.  The --scores report's ``mode`` is
-    ``outfits`` or ``change-region <region>``; a run with neither option has none.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
+    ``outfits`` or ``change-region <region>``; a run with neither option has none.  ``kept_parts`` 'photo' with ``kept_feather``
+    (None: 2): the written image carries the photograph's kept parts (``dress``); a feather without it is refused like the two
+    modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
+    kept_radius = _kept_radius(kept_parts, kept_feather)
 
     def choose(device):
         from training import dataset as custom_dataset
@@ -289,12 +361,12 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             collate_fn, worn = functools.partial(custom_dataset.collate_region_outfits, change_region or 'upperbody'), ('clothes_name',)
         stem = lambda name: os.path.basename(name)[:-4]
 
-        def pictures(batch, raw, gen_imgs, count):
+        def pictures(batch, raw, gen_imgs, count, content):
             height, width = raw['people_image'].shape[1], raw['people_image'].shape[2]
             names = [os.path.join(who[0].split('/')[0], '__'.join(stem(name) for name in who) + '.png')
                      for who in zip(raw['person_name'], *[raw[k] for k in worn])]
-            return images_to_u8(gen_imgs, (height - width) // 2, width), names
+            return (images_to_u8(gen_imgs, (height - width) // 2, width) if content is None else content), names
         return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device), pictures
     mode = 'outfits' if outfits_file is not None else change_region and 'change-region ' + change_region
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode,
-          _chosen_encoder(png_encoder))
+          kept_radius=kept_radius, png_encoder=_chosen_encoder(png_encoder))
