@@ -30,7 +30,7 @@ enum { PASTA_F32 = 0, PASTA_F16 = 1, PASTA_F64 = 2, PASTA_BF16 = 3 };
 
 /* Library identification / error reporting. */
 const char* pasta_last_error(void);
-int         pasta_abi_version(void);           /* 22; bumps when a signature changes */
+int         pasta_abi_version(void);           /* 22; bumps when a signature changes (entries added since: marked "additive at ABI 22") */
 const char* pasta_build_info(void);            /* "gfx950 <date> <hip version>"    */
 
 /* ------------------------------------------------------------------------- *
@@ -320,6 +320,50 @@ int pasta_conv2d_ex(const void* x, const float* w, void* y,
                     const float* iscale, const float* oscale, const pasta_conv_epilogue* ep,
                     const pasta_conv_desc* d, void* workspace, int64_t workspace_bytes,
                     void* stream);
+
+/* The input-activation mask (additive at ABI 22).  A launch that writes the gradient dx of a layer's INPUT x holds x; where x is the activated
+ * output of the layer in front, y = clamp(act(u) * gain) with act linear / relu / lrelu, the derivative of that activation is a function of y
+ * alone (bias_act.cu:38-146: gain or gain * alpha by the sign of y, zero where |y| >= clamp), so the launch can hand back dz = dx * act'(y) --
+ * the gradient at the OUTPUT of the convolution in front -- from its own saved tensor, and that layer's stand-alone pass
+ * (pasta_bias_act with grad = 1: two reads and a write of the activation) does not run.  The rule is the one pasta_bias_act applies
+ * (csrc/common.h, act_grad1): the result is bit-identical to launch + pass. */
+typedef struct pasta_act_mask {
+    const void* m;                /* the activated tensor, laid out like the launch's output (same shape, strides and element type) */
+    int32_t act;                  /* 1 linear, 2 relu, 3 lrelu */
+    float alpha, gain, clamp;     /* of the activation that produced m; clamp < 0 = none */
+} pasta_act_mask;
+
+/* pasta_conv2d_ex whose store computes  y = (conv [+ ep->res]) * act'(mask->m)  (mask NULL = pasta_conv2d_ex).  The residual is added BEFORE the
+ * mask (another consumer's gradient of the same tensor), ep->y_amax sees the masked value.  ep, when given, is linear without bias, gain, clamp or
+ * noise; no scale vectors.  Served where pasta_conv2d_mask_available answers 1 for the launch's flags -- the default arithmetic on fp32 tensors
+ * without K slices on the 2-D tiles of the 3x3 stride-1 launches (plan kernels 4 - 7) --, an error elsewhere: the caller then runs the pass. */
+int pasta_conv2d_masked(const void* x, const float* w, void* y,
+                        const float* iscale, const float* oscale, const pasta_conv_epilogue* ep, const pasta_act_mask* mask,
+                        const pasta_conv_desc* d, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int pasta_conv2d_mask_available(const pasta_conv_desc* d, int launch_flags);       /* 1 / 0; -1: the descriptor is refused */
+
+/* pasta_upfirdn2d whose store computes  y = (gain * fir(x) [+ y_add]) * act'(mask->m)  (mask NULL = pasta_upfirdn2d): the filter's transpose that
+ * ends the backward of a low-pass in front of a stride-2 convolution, with the low-pass's saved input as the mask.  Served by the tile and the
+ * small-plane kernels on dense fp32 NCHW tensors; pasta_upfirdn2d_mask_available answers 1 where one of them takes the launch
+ * (dense NCHW assumed), and the masked launch is an error elsewhere. */
+int pasta_upfirdn2d_masked(const void* x, const float* f, void* y, int dtype,
+                           const int32_t in_size[4], const int64_t in_stride[4],
+                           const int32_t f_size[2],
+                           const int32_t out_size[4], const int64_t out_stride[4],
+                           int upx, int upy, int downx, int downy,
+                           int padx0, int padx1, int pady0, int pady1,
+                           int flip, float gain, void* stream, float* y_amax,
+                           const void* y_add, const pasta_act_mask* mask);
+int pasta_upfirdn2d_mask_available(int dtype, const int32_t in_size[4], const int32_t f_size[2],
+                                   int upx, int upy, int downx, int downy,
+                                   int padx0, int padx1, int pady0, int pady1);
+
+/* The bias gradient of a layer that deferred its activation gradient to the reader of its output (additive at ABI 22): db[c] = sum of dx over the
+ * planes of channel c, where dx already is the gradient at the convolution's output.  One read and no store; the shapes, the workspace
+ * (pasta_bias_act_grad_db_workspace with act = 1) and the order of the partial sums are those of pasta_bias_act_grad_db, so db has the bits
+ * that pass would have produced. */
+int pasta_bias_sum_db(const void* dx, void* db, float* work, int dtype, int64_t n, int size_b, int64_t step_b, void* stream);
 
 /* Modulated convolution in its per-sample-weight form (networks.py:84-94, the `fused_modconv` branch test.py runs):
  * d describes the grouped convolution the reference launches (groups = N samples, C_in = N*I, C_out = N*O, x viewed as

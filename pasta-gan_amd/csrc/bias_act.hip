@@ -27,17 +27,17 @@ __device__ __forceinline__ S bias_act_point(S x, S b, S xref, S yref, S dy, S al
     const S selu_scale = (S)1.0507009873554804934193349852946;
     const S selu_alpha = (S)1.6732632423543772848170429916717;
     S y = 0;
+    // the piecewise-linear activations' first derivative: the rule the convolution and FIR stores share (common.h)
+    if (G == 1 && A <= 3) return act_grad1<S>(x, yref, A, alpha, gain, gain * dy, clamp);
     if (G == 0) x += b; else xref += b;
     const S yy = (gain != 0) ? yref / gain : (S)0;
 
     if (A == 1) {            // linear
-        if (G <= 1) y = x;
+        if (G == 0) y = x;
     } else if (A == 2) {     // relu
         if (G == 0) y = x > 0 ? x : (S)0;
-        if (G == 1) y = yy > 0 ? x : (S)0;
     } else if (A == 3) {     // leaky relu
         if (G == 0) y = x > 0 ? x : x * alpha;
-        if (G == 1) y = yy > 0 ? x : x * alpha;
     } else if (A == 4) {     // tanh
         if (G == 0) { S c = exp(x), d = one / c; y = x < -exp_range ? -one : x > exp_range ? one : (c - d) / (c + d); }
         if (G == 1) y = x * (one - yy * yy);
@@ -280,7 +280,10 @@ constexpr int DB_CHUNK_PACKS = 1024;
 
 constexpr int DB_SPAN = 8;          // chunks of one plane per workgroup: one reduction and one |max| commit per 128 KB of dx
 
-template <class T, int A, int V>
+// SUM_ONLY (pasta_bias_sum_db): p.x already IS dx -- the reader of the activation applied its gradient in the launch that wrote dx
+// (pasta_act_mask) -- and only the bias gradient is formed: one read, no store, and the partial sums of the very same elements in the very same
+// order, so that db has the bits the folded pass gives.
+template <class T, int A, int V, bool SUM_ONLY = false>
 __global__ __launch_bounds__(256) void bias_act_grad_db_kernel(BiasActParams p, float* work, int outer, int chunks, int spans) {
     typedef typename acc_of<T>::type S;
     constexpr int U = DB_CHUNK_PACKS / 256;
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(256) void bias_act_grad_db_kernel(BiasActParams p, 
         for (int u = 0; u < U; u++) {
             const int j = jb + 256 * u < plane_packs ? jb + 256 * u : plane_packs - 1;
             it.vdy[u] = dys[j];
-            if (yr) it.vyr[u] = yr[j];
+            if (!SUM_ONLY && yr) it.vyr[u] = yr[j];
         }
     };
     auto process = [&](int chunk, const Item& it) {
@@ -310,6 +313,11 @@ __global__ __launch_bounds__(256) void bias_act_grad_db_kernel(BiasActParams p, 
 #pragma unroll
         for (int u = 0; u < U; u++) {
             if (jb + 256 * u >= plane_packs) continue;
+            if constexpr (SUM_ONLY) {
+#pragma unroll
+                for (int k = 0; k < V; k++) acc += (float)ld<T>(&it.vdy[u].v[k]);
+                continue;
+            }
             Pack<T, V> out;
 #pragma unroll
             for (int k = 0; k < V; k++) {
@@ -360,6 +368,7 @@ static int launch_grad_db(const BiasActParams& p, float* work, void* db, int act
     const int spans = (chunks + DB_SPAN - 1) / DB_SPAN;          // partial sums [c][n][span]: the first outer * size_b * spans floats of `work`
     dim3 grid((unsigned)(outer * p.size_b), (unsigned)spans);
     switch (act) {
+        case 0: hipLaunchKernelGGL((bias_act_grad_db_kernel<T, 1, V, true>), grid, dim3(256), 0, s, p, work, outer, chunks, spans); break;      // the sum alone
         case 1: hipLaunchKernelGGL((bias_act_grad_db_kernel<T, 1, V>), grid, dim3(256), 0, s, p, work, outer, chunks, spans); break;
         case 2: hipLaunchKernelGGL((bias_act_grad_db_kernel<T, 2, V>), grid, dim3(256), 0, s, p, work, outer, chunks, spans); break;
         default: hipLaunchKernelGGL((bias_act_grad_db_kernel<T, 3, V>), grid, dim3(256), 0, s, p, work, outer, chunks, spans); break;
@@ -393,6 +402,24 @@ extern "C" int pasta_bias_act_grad_db(const void* dy, const void* yref, void* dx
     if (dtype == PASTA_F32) return launch_grad_db<float, 4>(p, work, db, act, outer, chunks, s);
     if (dtype == PASTA_BF16) return launch_grad_db<__bf16, 8>(p, work, db, act, outer, chunks, s);
     return launch_grad_db<__half, 8>(p, work, db, act, outer, chunks, s);
+}
+
+extern "C" int pasta_bias_sum_db(const void* dx, void* db, float* work, int dtype, int64_t n, int size_b, int64_t step_b, void* stream) {
+    using namespace pasta;
+    const int chunks = grad_db_chunks(dtype, n, size_b, step_b, 1);
+    PASTA_CHECK(chunks > 0, "bias_sum_db: unsupported case (dtype %d, n %lld, size_b %d, step_b %lld): pasta_bias_act_grad_db_workspace tells beforehand",
+                dtype, (long long)n, size_b, (long long)step_b);
+    PASTA_CHECK(dx && db && work, "bias_sum_db: null pointer");
+    PASTA_CHECK(((uintptr_t)dx & 15) == 0, "bias_sum_db: dx must be 16-byte aligned");
+    BiasActParams p;
+    p.x = dx; p.b = nullptr; p.xref = nullptr; p.yref = nullptr; p.dy = nullptr; p.y = nullptr;
+    p.n = n; p.size_b = size_b; p.step_b = step_b;
+    p.alpha = 0.f; p.gain = 1.f; p.clamp = -1.f; p.y_amax = nullptr;
+    const int outer = (int)(n / ((int64_t)size_b * step_b));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PASTA_F32) return launch_grad_db<float, 4>(p, work, db, 0, outer, chunks, s);
+    if (dtype == PASTA_BF16) return launch_grad_db<__bf16, 8>(p, work, db, 0, outer, chunks, s);
+    return launch_grad_db<__half, 8>(p, work, db, 0, outer, chunks, s);
 }
 
 extern "C" int pasta_bias_act(const void* x, const void* b, const void* xref, const void* yref, const void* dy, void* y,

@@ -77,6 +77,20 @@ template <>        __device__ __forceinline__ void st4<__half>(__half* p, float4
     *(h4*)p = __builtin_convertvector(f, h4);
 }
 
+// Gradient order 1 of the piecewise-linear activations (act 1 linear, 2 relu, 3 lrelu) through y = clamp(act(u) * gain), expressed in the
+// activated output yref (torch_utils/ops/bias_act.cu:38-146): v * act'(.) * mul, zero where the clamp was active.  The ONE statement of the rule:
+// bias_act.hip applies it in its passes (mul = gain * dy), the convolution and FIR stores as their "input-activation mask" (mul = gain).
+// The branch of the activation is the sign of yref / gain, read off the two signs (no division per element; for a subnormal yref under a
+// gain above 2 the quotient could round to zero where the sign cannot).
+template <class S>
+__device__ __forceinline__ S act_grad1(S v, S yref, int act, S alpha, S gain, S mul, S clamp) {
+    const bool up = act == 1 || (gain > 0 ? yref > 0 : (gain < 0 && yref < 0));
+    S y = up ? v : (act == 2 ? (S)0 : v * alpha);
+    y *= mul;
+    if (clamp >= 0) y = (yref > -clamp && yref < clamp) ? y : (S)0;
+    return y;
+}
+
 // V elements moved as one 16-byte (or narrower) access.
 template <class T, int V> struct alignas(sizeof(T) * V) Pack { T v[V]; };
 

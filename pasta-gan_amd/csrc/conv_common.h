@@ -33,7 +33,12 @@ __device__ __forceinline__ float conv_epilogue(float v, float b, int act, float 
 // scalar branches per element (the compiler does not unswitch them) they cost the dominant kernel 5 % -- profiles/r4_ab_epilogues.txt.
 // "No activation" is expressed by the caller as b = 0, slope = 1, relu = false, gain = 1, clamp_on = false (EpiAct below): the value then
 // passes unchanged (NaN and infinities included).  relu selects an exact 0 for v <= 0 and for NaN, as conv_epilogue does.
-struct EpiAct { float slope, gain, clamp; bool relu, clamp_on, on; };
+struct EpiAct {
+    float slope, gain, clamp; bool relu, clamp_on, on;
+    // the input-activation mask of an input-gradient launch (pasta_act_mask, conv_epi_input_mask below): the store multiplies by the
+    // derivative of the activation that PRODUCED this launch's output position, read from that activation's output
+    bool mask; int m_act; float m_alpha, m_gain, m_clamp;
+};
 __device__ __forceinline__ EpiAct conv_epi_act(int act, float alpha, float gain, float clamp, bool fused) {
     EpiAct e;
     e.on = act != 0 && fused;
@@ -42,6 +47,7 @@ __device__ __forceinline__ EpiAct conv_epi_act(int act, float alpha, float gain,
     e.gain = e.on ? gain : 1.f;
     e.clamp_on = e.on && clamp >= 0.f;
     e.clamp = clamp;
+    e.mask = false; e.m_act = 1; e.m_alpha = 0.f; e.m_gain = 1.f; e.m_clamp = -1.f;
     return e;
 }
 __device__ __forceinline__ float conv_epilogue_u(float v, float b, const EpiAct& e) {
@@ -59,7 +65,8 @@ __device__ __forceinline__ float conv_epilogue_u(float v, float b, const EpiAct&
 // the folded form (compile time: an instance is sixty-four unrolled stores, and those arithmetics are side lines).  Round 4 folded every
 // kernel because the family was one translation unit that took 12 minutes with the instances; since round 5 the family is thirteen units
 // compiled in parallel (conv_launch.h).  f(full, EpiCase<MODE>{}): full is std::bool_constant for SPEC kernels, bool otherwise.
-template <int MODE> struct EpiCase {};          // 0: folded, branch-free (conv_epilogue_u); 1: no activation; 2: activation; 3: activation and clamp
+template <int MODE> struct EpiCase {};          // 0: folded, branch-free (conv_epilogue_u); 1: no activation; 2: activation; 3: activation and clamp;
+                                                // 4: the input-activation mask (no bias / activation of the launch's own: conv_store_subtile)
 template <int MODE>
 __device__ __forceinline__ float conv_epilogue_c(float v, float b, const EpiAct& e, EpiCase<MODE>) {
     if constexpr (MODE == 0) return conv_epilogue_u(v, b, e);
@@ -76,8 +83,16 @@ __device__ __forceinline__ float conv_epilogue_c(float v, float b, const EpiAct&
 #ifndef PASTA_EPI_CASES
 #define PASTA_EPI_CASES 1       // build switch for same-box A/B (tools/ab_lib.sh): 0 = round 4's final form, an instance per whole-tile answer with the folded activation
 #endif
-template <bool SPEC, class F>
+// MASK: the kernel also carries the instance of the input-activation mask (the default arithmetic on fp32 tensors of the 2-D tiles: what
+// mask_launch_ok of conv_plan.h admits); every other kernel compiles what it always did.
+template <bool SPEC, bool MASK = false, class F>
 __device__ __forceinline__ void conv_epilogue_dispatch(bool full, const EpiAct& e, F&& f) {
+    if constexpr (SPEC && MASK) {
+        if (e.mask) {
+            if (full) f(std::true_type{}, EpiCase<4>{}); else f(std::false_type{}, EpiCase<4>{});
+            return;
+        }
+    }
     if constexpr (SPEC && !PASTA_EPI_CASES) {
         if (full) f(std::true_type{}, EpiCase<0>{}); else f(std::false_type{}, EpiCase<0>{});
     } else if constexpr (SPEC) {
@@ -283,6 +298,7 @@ __device__ __forceinline__ void conv_unscale_rows(const float* wri, float scale,
 // partial lies at off + o * ostride; oscale and bias are indexed by o.  An operand that is absent is a null pointer.
 struct EpiColumn {
     void* y; const void* res;           // elements of the kernel's storage type
+    const void* mask;                   // the input-activation mask's tensor (EpiCase<4>), laid out like y
     float* partial;                     // K slices: this slice's fp32 partial sums; the sub-tile is written there and nothing else happens
     int64_t off, ostride;
     const float* oscale;                // this pixel's sample
@@ -323,6 +339,22 @@ __device__ __forceinline__ void conv_store_subtile(f32x16& acc, const EpiColumn&
         }
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[r] += tv[r];
+    }
+    if constexpr (MODE == 4) {
+        // the input-activation mask: (acc [+ res]) times the derivative of the activation whose output lies at c.mask, the residual's access
+        // pattern once more through the same sixteen registers (a masked launch has no K slices, no bias and no activation of its own)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = o0 + acc_row(r, lane);
+            tv[r] = ((FULL && !RES_ROWTEST) || o < Og) ? io_ld1<IO>((const char*)c.mask + (c.off + (int64_t)o * c.ostride) * ES) : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = o0 + acc_row(r, lane);
+            const float v = act_grad1<float>(acc[r], tv[r], ea.m_act, ea.m_alpha, ea.m_gain, ea.m_gain, ea.m_clamp);
+            if (FULL || o < Og) { io_st<IO>(c.y, c.off + (int64_t)o * c.ostride, v); amax_take(y_am, v); }
+        }
+        return;
     }
     if (c.partial) {                    // scale, residual, bias, activation ride in the reduction
 #pragma unroll
@@ -394,7 +426,15 @@ struct ConvFwdParams {
     const unsigned* koff;
     int xcd_order;                        // conv_fwd_rows2d_bf16x6_kernel, eight-wave tile: consecutive pixel tiles on ONE XCD (0: off)
     int x_pieces;                         // conv3x3s2_f16x3_kernel: x is PASTA_LAYOUT_PIECES16 (pieces.hip), p.x_amax the producer's bound row
+    // the input-activation mask (pasta_act_mask; the 2-D tiles, no K slices): [N, Cout, OH, OW] like y, null = off
+    const float* mask; int m_act; float m_alpha, m_gain, m_clamp;
 };
+
+// ea for a launch that may carry the input-activation mask (the kernels whose conv_epilogue_dispatch has MASK set call this)
+__device__ __forceinline__ void conv_epi_input_mask(EpiAct& e, const ConvFwdParams& p) {
+    e.mask = p.mask && p.ksplit == 1;
+    e.m_act = p.m_act; e.m_alpha = p.m_alpha; e.m_gain = p.m_gain; e.m_clamp = p.m_clamp;
+}
 
 // The column of the pixel at plane offset plane_off of sample n, for group g and K slice ks of a launch: every operand the launch carries
 // (output scale, noise, residual, bias and activation exist only without K slices: they ride in the reduction otherwise).
@@ -405,6 +445,7 @@ __device__ __forceinline__ EpiColumn conv_epi_column(const ConvFwdParams& p, con
     EpiColumn c;
     c.y = p.y;
     c.res = fused ? p.res : nullptr;
+    c.mask = ea.mask ? p.mask : nullptr;
     c.partial = fused ? nullptr : p.partial + (int64_t)ks * p.N * p.Cout * OHW;
     c.off = ((int64_t)n * p.Cout + (int64_t)g * p.Og) * OHW + plane_off;
     c.ostride = OHW;

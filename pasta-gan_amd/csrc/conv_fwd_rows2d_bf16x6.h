@@ -357,7 +357,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
     const bool has_res = p.res && fused;
     const float* osb = (p.oscale && fused) ? p.oscale + (int64_t)n_img * p.Cout + (int64_t)g * p.Og : nullptr;
     const float* bsb = (p.act && fused && p.bias) ? p.bias + g * p.Og : nullptr;
-    if (!osb && !bsb && !has_res) {
+    constexpr bool MASK = NP == NP_F16X3 && IO == IO_F32 && !ISC && !XP;       // the instances that carry the input-activation mask
+    const bool has_mask = MASK && p.mask && fused;
+    if (!osb && !bsb && !has_res && !has_mask) {
         // nothing to fetch: the plain launches (every input gradient without a residual, every convolution without an epilogue) keep the
         // store loop they always had -- the general path below, taken by them too, cost the dominant kernel 3.0 % (286.3 -> 294.8 us on
         // the micro-benchmark's shapes, same box, profiles/r4_ab_epilogues.txt)
@@ -413,8 +415,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         return;
     }
     // (here fused holds: an output scale, a bias or a residual exist only without K slices)
-    const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, true);
-    conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32)>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
+    EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, true);
+    if constexpr (MASK) conv_epi_input_mask(ea, p);
+    conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32), MASK>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
 #pragma unroll
         for (int b = 0; b < WNT; b++) {
             const int t = (wn * WNT + b) * 32 + jl;

@@ -114,7 +114,7 @@ static void launch_transposed_pairs(const pasta_conv_desc* d, const ConvFwdParam
 
 static int conv2d_run(const void* x, const float* w, void* y, const float* iscale, const float* oscale,
                       const pasta_conv_epilogue* ep, const pasta_conv_desc* d, void* workspace, int64_t workspace_bytes,
-                      void* stream, const float* wmod_s, const float* wmod_d);
+                      void* stream, const float* wmod_s, const float* wmod_d, const pasta_act_mask* mask = nullptr);
 static int wgrad_run(const void* xv, const void* dyv, float* dw, const pasta_conv_desc* d, void* workspace, int64_t workspace_bytes, void* stream,
                      const float* mod_s, const float* mod_w, float* ds);
 
@@ -181,7 +181,20 @@ extern "C" int pasta_conv2d(const void* x, const float* w, void* y, const float*
 extern "C" int pasta_conv2d_ex(const void* x, const float* w, void* y, const float* iscale, const float* oscale,
                                const pasta_conv_epilogue* ep, const pasta_conv_desc* d, void* workspace, int64_t workspace_bytes,
                                void* stream) {
-    return pasta::conv2d_run(x, w, y, iscale, oscale, ep, d, workspace, workspace_bytes, stream, nullptr, nullptr);
+    return pasta_conv2d_masked(x, w, y, iscale, oscale, ep, nullptr, d, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pasta_conv2d_masked(const void* x, const float* w, void* y, const float* iscale, const float* oscale,
+                                   const pasta_conv_epilogue* ep, const pasta_act_mask* mask, const pasta_conv_desc* d, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    return pasta::conv2d_run(x, w, y, iscale, oscale, ep, d, workspace, workspace_bytes, stream, nullptr, nullptr, mask);
+}
+
+extern "C" int pasta_conv2d_mask_available(const pasta_conv_desc* d, int launch_flags) {
+    using namespace pasta;
+    if (check_desc(d, "conv2d_mask_available")) return -1;
+    if (launch_flags & ~PASTA_PLAN_EPILOGUE) return 0;
+    return mask_launch_ok(d, choose_fwd(d, launch_flags)) ? 1 : 0;
 }
 
 extern "C" int pasta_conv2d_modulated(const void* x, const float* w, const float* styles, const float* dcoefs, void* y,
@@ -211,7 +224,7 @@ extern "C" int pasta_conv2d_pack_pair(const float* w, const pasta_conv_desc* da,
 
 int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscale, const float* oscale,
                       const pasta_conv_epilogue* ep, const pasta_conv_desc* d, void* workspace, int64_t workspace_bytes,
-                      void* stream, const float* wmod_s, const float* wmod_d) {
+                      void* stream, const float* wmod_s, const float* wmod_d, const pasta_act_mask* mask) {
     // ---- check
     if (int e = check_desc(d, "conv2d")) return e;
     PASTA_CHECK(!ep || (ep->act >= 1 && ep->act <= 3), "conv2d: fused epilogue supports act 1..3 (linear, relu, lrelu), got %d", ep ? ep->act : 0);
@@ -219,6 +232,13 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
     PASTA_CHECK(x && w && y, "conv2d: null pointer");
     // ---- choose, and lay out the workspace
     const FwdChoice ch = choose_fwd(d, launch_flags_of(iscale, oscale, ep, wmod_s));
+    if (mask) {
+        PASTA_CHECK(mask->m && mask->act >= 1 && mask->act <= 3, "conv2d: the input-activation mask needs its tensor and act 1..3 (linear, relu, lrelu)");
+        PASTA_CHECK(!iscale && !oscale && !wmod_s && (!ep || (ep->act == 1 && !ep->bias && !ep->noise && ep->gain == 1.f && ep->clamp < 0.f)),
+                    "conv2d: a launch with the input-activation mask carries no scale vector, bias, noise or activation of its own");
+        PASTA_CHECK(mask_launch_ok(d, ch), "conv2d: no kernel applies the input-activation mask for this launch (pasta_conv2d_mask_available tells "
+                                           "beforehand): run pasta_bias_act with grad = 1 on the result instead");
+    }
     FwdWorkspace lay;
     if (int e = fwd_workspace(d, ch.plan, lay)) return e;
     const int64_t need = lay.total_floats * (int64_t)sizeof(float);
@@ -261,6 +281,7 @@ int pasta::conv2d_run(const void* x, const float* w, void* y, const float* iscal
     p.alpha = ep ? ep->alpha : 0.f; p.gain = ep ? ep->gain : 1.f; p.clamp = ep ? ep->clamp : -1.f;
     p.noise = ep ? ep->noise : nullptr; p.noise_strength = ep ? ep->noise_strength : nullptr; p.noise_ps = ep ? ep->noise_per_sample : 0;
     p.y_amax = ep ? ep->y_amax : nullptr;
+    if (mask) { p.mask = (const float*)mask->m; p.m_act = mask->act; p.m_alpha = mask->alpha; p.m_gain = mask->gain; p.m_clamp = mask->clamp; }
     p.ksplit = ch.ksplit;
     p.o_tiles = 1;
     p.partial = ws + lay.partial;

@@ -325,6 +325,15 @@ static inline FwdChoice choose_fwd(const pasta_conv_desc* d, int launch_flags) {
     return c;
 }
 
+// Does the store of this launch take the input-activation mask (pasta_act_mask)?  The default arithmetic on fp32 tensors, no K slices, on a 2-D
+// tile (3x3, stride 1: the mask is indexed like the output); the launch itself checks that it carries no scale vector, bias, noise or activation
+// of its own.  Not the base kernel: with the masked store its three-workgroup instances go to scratch (12 -> 1152 bytes per lane for
+// <128,128,3,NP_F16X3>) and EVERY launch of theirs ran at half speed (profiles/act_grad_in_writer_ab.txt); those launches keep the pass.
+static inline bool mask_launch_ok(const pasta_conv_desc* d, const FwdChoice& c) {
+    return c.pieces == NP_F16X3 && d->io_dtype == PASTA_F32 && c.ksplit == 1 && !d->x2 && !d->x_layout && is_rows2d(c.kernel) &&
+           (c.tl == TL_NONE || c.tl == TL_MERGED || c.tl == TL_PER_CLASS);
+}
+
 // Where everything lies in the workspace of a forward-type launch, in floats from its (16-byte aligned) base:
 //   [amax 2 x 256 | rowinv G x Og_pad | packed weights | K-slice partial sums | packed-K offset table | extra]
 // extra: the zero-padded copy of the input (packed-K mode; absent where the convolution has no padding: the input itself serves), or the input's

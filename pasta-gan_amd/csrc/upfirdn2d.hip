@@ -49,7 +49,13 @@ struct UpfirdnParams {
     float* y_amax;                // optional: PASTA_AMAX_PARTS zeroed floats that receive the largest finite |y| (common.h)
     const void* y_add;            // optional: a tensor laid out like y, added to the result on its way out (ABI 18: another consumer's gradient
                                   // when this launch is the backward of a tensor with several consumers)
+    const void* mask;             // optional: the input-activation mask (pasta_act_mask), a tensor laid out like y -- the store multiplies by the
+    int m_act;                    // derivative of the activation that produced it (common.h, act_grad1), after the gain and the addend.
+    float m_alpha, m_gain, m_clamp;     // Tile and small-plane kernels; the generic kernel refuses the mode
 };
+
+// the value a tile / small-plane kernel stores for v where the mask's element is m
+__device__ __forceinline__ float up_masked(const UpfirdnParams& p, float v, float m) { return act_grad1<float>(v, m, p.m_act, p.m_alpha, p.m_gain, p.m_gain, p.m_clamp); }
 
 //------------------------------------------------------------------------------------
 // Generic kernel.
@@ -217,6 +223,7 @@ __global__ __launch_bounds__(BX* BY) void upfirdn2d_tile_kernel(UpfirdnParams p,
             }
         const int ox = tile_x * TOW + tx * MX, oy = tile_y * TOH + ty * MY;
         const T* ap = p.y_add ? (const T*)p.y_add + (int64_t)plane * OHW : nullptr;
+        const T* mp = p.mask ? (const T*)p.mask + (int64_t)plane * OHW : nullptr;
         if (ap) {                                       // the addend of this thread's outputs, fetched in one go in front of the stores
 #pragma unroll
             for (int b = 0; b < MY; b++)
@@ -226,6 +233,26 @@ __global__ __launch_bounds__(BX* BY) void upfirdn2d_tile_kernel(UpfirdnParams p,
                         if constexpr (PL == 2) { acc[b][a][0] += ld<T>(ap + (int64_t)(oy + b) * p.outW + ox + a); acc[b][a][1] += ld<T>(ap + OHW + (int64_t)(oy + b) * p.outW + ox + a); }
                         else acc[b][a] += ld<T>(ap + (int64_t)(oy + b) * p.outW + ox + a);
                     }
+        }
+        if (mp) {                                       // ... and the mask's elements likewise, applied in registers
+            V mk[MY][MX];
+#pragma unroll
+            for (int b = 0; b < MY; b++)
+#pragma unroll
+                for (int a = 0; a < MX; a++) {
+                    mk[b][a] = V(0.f);
+                    if (oy + b < p.outH && ox + a < p.outW) {
+                        if constexpr (PL == 2) { mk[b][a][0] = ld<T>(mp + (int64_t)(oy + b) * p.outW + ox + a); mk[b][a][1] = ld<T>(mp + OHW + (int64_t)(oy + b) * p.outW + ox + a); }
+                        else mk[b][a] = ld<T>(mp + (int64_t)(oy + b) * p.outW + ox + a);
+                    }
+                }
+#pragma unroll
+            for (int b = 0; b < MY; b++)
+#pragma unroll
+                for (int a = 0; a < MX; a++) {
+                    if constexpr (PL == 2) { acc[b][a][0] = up_masked(p, acc[b][a][0], mk[b][a][0]); acc[b][a][1] = up_masked(p, acc[b][a][1], mk[b][a][1]); }
+                    else acc[b][a] = up_masked(p, acc[b][a], mk[b][a]);
+                }
         }
 #pragma unroll
         for (int b = 0; b < MY; b++) {
@@ -258,6 +285,7 @@ __global__ __launch_bounds__(BX* BY) void upfirdn2d_tile_kernel(UpfirdnParams p,
                 for (int k = 0; k < PL; k++) {
                     float w = up_lane(v, k);
                     if (ap) w += ld<T>(ap + k * OHW + (int64_t)(tile_y * TOH + yy) * p.outW + tile_x * TOW + xx);
+                    if (mp) w = up_masked(p, w, ld<T>(mp + k * OHW + (int64_t)(tile_y * TOH + yy) * p.outW + tile_x * TOW + xx));
                     st<T>(yp + k * OHW + (int64_t)(tile_y * TOH + yy) * p.outW + tile_x * TOW + xx, w);
                     if (p.y_amax) amax_take(am, w);
                 }
@@ -330,6 +358,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_small_kernel(UpfirdnParams p, i
                 }
                 v *= p.gain;
                 if (p.y_add) v += ld<T>((const T*)p.y_add + (int64_t)p0 * out_sz + e);
+                if (p.mask) v = up_masked(p, v, ld<T>((const T*)p.mask + (int64_t)p0 * out_sz + e));
                 st<T>(yp + e, v);
                 if (p.y_amax) amax_take(am, v);
             } else {
@@ -351,6 +380,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_small_kernel(UpfirdnParams p, i
                 }
                 v *= p.gain;
                 if (p.y_add) v += ld<T>((const T*)p.y_add + (int64_t)p0 * out_sz + e);
+                if (p.mask) v = up_masked(p, v, ld<T>((const T*)p.mask + (int64_t)p0 * out_sz + e));
                 st<T>(yp + e, v);
                 if (p.y_amax) amax_take(am, v);
             }
@@ -362,8 +392,9 @@ __global__ __launch_bounds__(256) void upfirdn2d_small_kernel(UpfirdnParams p, i
 // ceil(2^32 / d): umulhi(e, magic) == e / d for e * d < 2^32
 static unsigned recip_magic(int d) { return d <= 1 ? 0xffffffffu : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
+// dry: answer only, launch nothing
 template <class T>
-static bool try_small(const UpfirdnParams& p, hipStream_t s) {
+static bool try_small(const UpfirdnParams& p, hipStream_t s, bool dry = false) {
     const int in_sz = p.inH * p.inW;
     const int64_t out_sz = (int64_t)p.outH * p.outW;
     const int64_t planes = (int64_t)p.N * p.C;
@@ -372,6 +403,7 @@ static bool try_small(const UpfirdnParams& p, hipStream_t s) {
     // enough workgroups to fill the chip before planes are stacked deeper
     while (PL > 1 && planes / PL < 512) PL >>= 1;
     if ((int64_t)PL * out_sz * out_sz >= (1ll << 32) || out_sz == 1 || p.outW == 1) return false;      // reciprocal range (d = 1 has no 32-bit reciprocal)
+    if (dry) return true;
     const int64_t groups = (planes + PL - 1) / PL;
     const dim3 grid((unsigned)(groups < 4096 ? groups : 4096));
     const unsigned msz = recip_magic((int)out_sz), mw = recip_magic(p.outW);
@@ -440,11 +472,12 @@ static void launch_phase(const UpfirdnParams& p, hipStream_t s) {
 // (and the mirrored gradients), separable 12-tap x2 up / /2 down in x or y (ADA).
 // Returns true when a tile kernel was launched.
 template <class T>
-static bool try_tile(const UpfirdnParams& p, hipStream_t s) {
+static bool try_tile(const UpfirdnParams& p, hipStream_t s, bool dry = false) {
     // Planes narrower than half a wavefront (the 4..16 pixel layers): several planes per workgroup (try_small)
     if (p.outW < 24) return false;
 #define PASTA_UPF(UX, UY, DX, DY, FW_, FH_, MX, MY)                                                           \
     if (p.upx == UX && p.upy == UY && p.downx == DX && p.downy == DY && p.fw == FW_ && p.fh == FH_) {        \
+        if (dry) return true;                                                                                 \
         if (p.outW <= 40 * MX) launch_phase<T, UX, UY, DX, DY, FW_, FH_, MX, MY, 32, 8>(p, s);               \
         else                   launch_phase<T, UX, UY, DX, DY, FW_, FH_, MX, MY, 64, 4>(p, s);               \
         return true;                                                                                          \
@@ -464,6 +497,8 @@ static bool try_tile(const UpfirdnParams& p, hipStream_t s) {
 template <class T>
 static int run(const UpfirdnParams& p, bool dense_nchw, hipStream_t s) {
     if (!(dense_nchw && (try_tile<T>(p, s) || try_small<T>(p, s)))) {
+        if (p.mask) return fail("upfirdn2d: the input-activation mask is applied by the tile and small-plane kernels only (dense NCHW tensors; "
+                                "pasta_upfirdn2d_mask_available tells beforehand): run pasta_bias_act with grad = 1 on the result instead");
         const int64_t total = (int64_t)p.N * p.C * p.outH * p.outW;
         int64_t blocks = ceil_div64(total, 256);
         if (blocks > 256 * 32) blocks = 256 * 32;
@@ -481,7 +516,35 @@ extern "C" int pasta_upfirdn2d(const void* x, const float* f, void* y, int dtype
                                int upx, int upy, int downx, int downy,
                                int padx0, int padx1, int pady0, int pady1,
                                int flip, float gain, void* stream, float* y_amax, const void* y_add) {
+    return pasta_upfirdn2d_masked(x, f, y, dtype, in_size, in_stride, f_size, out_size, out_stride, upx, upy, downx, downy, padx0, padx1, pady0, pady1,
+                                  flip, gain, stream, y_amax, y_add, nullptr);
+}
+
+extern "C" int pasta_upfirdn2d_mask_available(int dtype, const int32_t in_size[4], const int32_t f_size[2], int upx, int upy, int downx, int downy,
+                                              int padx0, int padx1, int pady0, int pady1) {
     using namespace pasta;
+    if (upx < 1 || upy < 1 || downx < 1 || downy < 1 || f_size[0] < 1 || f_size[1] < 1) return 0;
+    UpfirdnParams p{};
+    p.N = in_size[0]; p.C = in_size[1]; p.inH = in_size[2]; p.inW = in_size[3];
+    p.fh = f_size[0]; p.fw = f_size[1];
+    p.upx = upx; p.upy = upy; p.downx = downx; p.downy = downy; p.padx0 = padx0; p.pady0 = pady0;
+    if (p.N < 1 || p.C < 1 || p.inH < 1 || p.inW < 1 || p.inW * upx + padx0 + padx1 - p.fw < 0 || p.inH * upy + pady0 + pady1 - p.fh < 0) return 0;
+    p.outW = (p.inW * upx + padx0 + padx1 - p.fw + downx) / downx;
+    p.outH = (p.inH * upy + pady0 + pady1 - p.fh + downy) / downy;
+    // fp32 only: in 16-bit storage the filter's result is rounded to the storage type in front of the pass, and the fused store would round once
+    return dtype == PASTA_F32 && (try_tile<float>(p, nullptr, true) || try_small<float>(p, nullptr, true)) ? 1 : 0;
+}
+
+extern "C" int pasta_upfirdn2d_masked(const void* x, const float* f, void* y, int dtype,
+                                      const int32_t in_size[4], const int64_t in_stride[4],
+                                      const int32_t f_size[2],
+                                      const int32_t out_size[4], const int64_t out_stride[4],
+                                      int upx, int upy, int downx, int downy,
+                                      int padx0, int padx1, int pady0, int pady1,
+                                      int flip, float gain, void* stream, float* y_amax, const void* y_add, const pasta_act_mask* mask) {
+    using namespace pasta;
+    PASTA_CHECK(!mask || (mask->m && mask->act >= 1 && mask->act <= 3), "upfirdn2d: the input-activation mask needs its tensor and act 1..3 (linear, relu, lrelu)");
+    PASTA_CHECK(!mask || dtype == PASTA_F32, "upfirdn2d: the input-activation mask is applied to fp32 tensors (16-bit storage rounds between filter and pass)");
     PASTA_CHECK(x && f && y, "upfirdn2d: null pointer");
     PASTA_CHECK(upx >= 1 && upy >= 1, "upfirdn2d: upsampling factor must be at least 1");
     PASTA_CHECK(downx >= 1 && downy >= 1, "upfirdn2d: downsampling factor must be at least 1");
@@ -505,6 +568,8 @@ extern "C" int pasta_upfirdn2d(const void* x, const float* f, void* y, int dtype
     p.osn = out_stride[0]; p.osc = out_stride[1]; p.osy = out_stride[2]; p.osx = out_stride[3];
     p.upx = upx; p.upy = upy; p.downx = downx; p.downy = downy;
     p.padx0 = padx0; p.pady0 = pady0; p.flip = flip ? 1 : 0; p.gain = gain; p.y_amax = y_amax; p.y_add = y_add;
+    p.mask = mask ? mask->m : nullptr; p.m_act = mask ? mask->act : 1; p.m_alpha = mask ? mask->alpha : 0.f; p.m_gain = mask ? mask->gain : 1.f;
+    p.m_clamp = mask ? mask->clamp : -1.f;
 
     const bool dense_nchw =
         p.isx == 1 && p.isy == p.inW && p.isc == (int64_t)p.inH * p.inW && (p.N == 1 || p.isn == p.isc * p.C) &&
@@ -515,7 +580,7 @@ extern "C" int pasta_upfirdn2d(const void* x, const float* f, void* y, int dtype
         case PASTA_F32: return run<float>(p, dense_nchw, s);
         case PASTA_F16: return run<__half>(p, dense_nchw, s);
         case PASTA_BF16: return run<__bf16>(p, dense_nchw, s);
-        case PASTA_F64: return run<double>(p, false, s);       // generic kernel only (fp64 accumulation)
+        case PASTA_F64: return run<double>(p, false, s);       // generic kernel only (fp64 accumulation; refuses the mask)
         default: return fail("upfirdn2d: unsupported dtype code %d", dtype);
     }
 }

@@ -158,6 +158,10 @@ class ConvEpilogue(ctypes.Structure):
     _fields_ = [('bias', _c_ptr), ('act', _c_i32), ('alpha', _c_f32), ('gain', _c_f32), ('clamp', _c_f32), ('res', _c_ptr),
                 ('noise', _c_ptr), ('noise_strength', _c_ptr), ('noise_per_sample', _c_i32), ('y_amax', _c_ptr)]
 
+class ActMask(ctypes.Structure):
+    """Mirror of ``pasta_act_mask`` (include/pasta_hip.h)."""
+    _fields_ = [('m', _c_ptr), ('act', _c_i32), ('alpha', _c_f32), ('gain', _c_f32), ('clamp', _c_f32)]
+
 class AdaConfig(ctypes.Structure):
     """Mirror of ``pasta_ada_config`` (include/pasta_hip.h)."""
     _fields_ = [(name, _c_f32) for name in (
@@ -180,6 +184,7 @@ ABI = {
     'pasta_bias_act_grad_db_workspace': (_c_i64, [ctypes.c_int, _c_i64, ctypes.c_int, _c_i64, ctypes.c_int]),
     'pasta_bias_act_grad_db': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.c_int, _c_i64, ctypes.c_int, _c_i64, ctypes.c_int,
                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_ptr, _c_ptr]),
+    'pasta_bias_sum_db':   (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, ctypes.c_int, _c_i64, ctypes.c_int, _c_i64, _c_ptr]),
     'pasta_pieces_bytes':  (_c_i64, [ctypes.c_int] * 4),
     'pasta_blur_pieces':   (ctypes.c_int, [_c_ptr] * 5 + [ctypes.c_int] * 9 + [_c_f32, _c_ptr]),
     'pasta_pieces_unpack': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 4 + [_c_ptr]),
@@ -192,6 +197,13 @@ ABI = {
     'pasta_conv2d_wgrad_plan': (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]),
     'pasta_conv2d':       (ctypes.c_int, [_c_ptr] * 5 + [ctypes.POINTER(ConvDesc), _c_ptr, _c_i64, _c_ptr]),
     'pasta_conv2d_ex':    (ctypes.c_int, [_c_ptr] * 5 + [ctypes.POINTER(ConvEpilogue), ctypes.POINTER(ConvDesc), _c_ptr, _c_i64, _c_ptr]),
+    'pasta_conv2d_masked': (ctypes.c_int, [_c_ptr] * 5 + [ctypes.POINTER(ConvEpilogue), ctypes.POINTER(ActMask), ctypes.POINTER(ConvDesc), _c_ptr, _c_i64, _c_ptr]),
+    'pasta_conv2d_mask_available': (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.c_int]),
+    'pasta_upfirdn2d_masked': (ctypes.c_int, [_c_ptr, _c_ptr, _c_ptr, ctypes.c_int,
+                                              ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i32),
+                                              ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64)] + [ctypes.c_int] * 9 + [_c_f32, _c_ptr, _c_ptr, _c_ptr,
+                                                                                                                      ctypes.POINTER(ActMask)]),
+    'pasta_upfirdn2d_mask_available': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32)] + [ctypes.c_int] * 8),
     'pasta_conv2d_wgrad': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.POINTER(ConvDesc), _c_ptr, _c_i64, _c_ptr]),
     'pasta_conv2d_wgrad_modulated': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.POINTER(ConvDesc), _c_ptr, _c_i64, _c_ptr]),
     'pasta_conv2d_wgrad_modulated_workspace': (_c_i64, [ctypes.POINTER(ConvDesc)]),
@@ -248,14 +260,21 @@ ABI = {
 
 # Entries added to the current ABI after its first release (purely additive, so the version did not move): a library built before
 # them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  At 22: the PNG
-# encoder's four entries (csrc/png_encode.hip) and pasta_images_keep_to_u8 (csrc/tryon_pairs.hip).
+# encoder's four entries (csrc/png_encode.hip), pasta_images_keep_to_u8 (csrc/tryon_pairs.hip) and the five entries of the input-activation mask
+# (pasta_act_mask: csrc/conv_igemm.hip, csrc/upfirdn2d.hip; pasta_bias_sum_db: csrc/bias_act.hip).
 LATE_ENTRIES = frozenset(['pasta_png_filter', 'pasta_png_code_lengths', 'pasta_png_segment_tables', 'pasta_png_encode',
-                          'pasta_images_keep_to_u8'])
+                          'pasta_images_keep_to_u8', 'pasta_conv2d_masked', 'pasta_conv2d_mask_available', 'pasta_upfirdn2d_masked',
+                          'pasta_upfirdn2d_mask_available', 'pasta_bias_sum_db'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):
         raise RuntimeError('%s has no %s: it predates this tree, rebuild it from this tree' % (lib_path, name))
+    missing.pasta_missing = True
     return missing
+
+def has_entry(lib, name):
+    """Does the loaded library export the late entry ``name`` (an older PASTA_LIB_AB build may not)?"""
+    return not getattr(getattr(lib, name), 'pasta_missing', False)
 
 def get_plugin(module_name='pasta_hip', sources=None, **build_kwargs):
     """Return the loaded library (a ``ctypes.CDLL`` with typed entry points).

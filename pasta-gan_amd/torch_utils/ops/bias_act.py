@@ -260,11 +260,22 @@ class _BiasActHipGradDb(torch.autograd.Function):
         return _BiasActHipGrad.apply(g.contiguous(), None, None, y, ctx.cfg), None, None
 
 class _BiasSum(torch.autograd.Function):
-    """db = sum of dx over all dimensions except ``dim`` (differentiable: the transpose is a broadcast)."""
+    """db = sum of dx over all dimensions except ``dim`` (differentiable: the transpose is a broadcast).  ``as_folded=True``: where the pass with
+    the bias sum folded in (``grad_with_bias_grad``) would have taken ``dx``, the sum has that pass's partial sums (``pasta_bias_sum_db``: one read,
+    the same bits) -- the bias gradient of a layer whose activation gradient its reader applied (conv2d_gradfix ``_ACT_GRAD_IN_WRITER``)."""
     @staticmethod
-    def forward(ctx, dx, dim):
+    def forward(ctx, dx, dim, as_folded=False):
         ctx.dim = dim
         ctx.shape = dx.shape
+        if as_folded:
+            nbytes = _grad_db_workspace(dx, dim, 1)
+            if nbytes > 0:
+                db = torch.empty([dx.shape[dim]], dtype=dx.dtype, device=dx.device)
+                work = torch.empty([nbytes // 4], dtype=torch.float32, device=dx.device)
+                with torch.cuda.device(dx.device):
+                    _native.check(_native.lib().pasta_bias_sum_db(_native.ptr(dx), _native.ptr(db), _native.ptr(work), _native.dtype_code(dx, 'bias_act'),
+                                                                  dx.numel(), dx.shape[dim], dx.stride(dim), _native.stream()))
+                return db
         if dx.device.type == 'cuda' and _bias_grad_supported(dx, dim):
             return _bias_grad(dx, dim)
         return dx.sum([i for i in range(dx.ndim) if i != dim])
@@ -272,7 +283,7 @@ class _BiasSum(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         view = [-1 if i == ctx.dim else 1 for i in range(len(ctx.shape))]
-        return g.reshape(view).expand(ctx.shape), None
+        return g.reshape(view).expand(ctx.shape), None, None
 
 #----------------------------------------------------------------------------
 

@@ -247,7 +247,7 @@ def _epilogue(epilogue, noise, y):
         ep.y_amax = y_row.data_ptr()
     return ep, y_row, (bias, res, nz, nstr)
 
-def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, noise=None, x2=None, used=None, pieces=None, prepacked=None):
+def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, noise=None, x2=None, used=None, pieces=None, prepacked=None, mask=None):
     """y = conv(x * iscale[n,c]) * oscale[n,c'] through ``pasta_conv2d_ex``; fp32 accumulation.  fp32 tensors run the
     split-bf16 (fp32-equivalent) or fp32 matrix-core kernels; fp16 / bf16 tensors stay 16-bit in HBM where a kernel exists
     (``_native16``) and are converted for the launch otherwise.
@@ -264,7 +264,9 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
     ``pieces`` = (bound row [256], logical shape (N, C, H, W)): ``x`` is not an NCHW tensor but the producer-written operand of the three-product
     arithmetic (``blur_pieces``: PASTA_LAYOUT_PIECES16, include/pasta_hip.h) -- the launch copies its sixteen-byte pieces instead of splitting.
     ``prepacked`` = (descriptor key, workspace) from ``_pack_pair``: the weights packed for the descriptor of that key; a launch of that very
-    descriptor runs on it without a packing kernel, any other packs for itself."""
+    descriptor runs on it without a packing kernel, any other packs for itself.
+    ``mask`` = (m, (act, alpha, gain, clamp)): the input-activation mask of an input-gradient launch (``pasta_conv2d_masked``; ``_mask_launch_ok``
+    says where a kernel applies it) -- the store multiplies by the derivative of the activation that produced ``m`` (shape of the output)."""
     _native.require_gpu(x, 'conv2d')
     if pieces is not None:
         assert iscale is None and oscale is None and wmod is None and noise is None and x2 is None
@@ -338,7 +340,17 @@ def _launch_conv(x, w, cfg, iscale=None, oscale=None, epilogue=None, wmod=None, 
             used['x_amax'], used['x2_amax'] = x_amax, x2_amax
     ep_ref = ctypes.byref(ep) if ep is not None else None
     lib = _native.lib()
-    if wmod is not None:
+    if mask is not None:
+        from . import bias_act as ba
+        assert iscale is None and oscale is None and wmod is None and noise is None and io is torch.float32
+        m, (m_act, m_alpha, m_gain, m_clamp) = mask
+        if m.dtype != torch.float32 or tuple(m.shape) != tuple(y.shape):
+            raise RuntimeError(f'conv2d: the input-activation mask {tuple(m.shape)} {m.dtype} does not match the fp32 output {tuple(y.shape)}')
+        m = m.contiguous()
+        am = custom_ops.ActMask(m=m.data_ptr(), act=int(ba.activation_funcs[m_act].cuda_idx), alpha=float(m_alpha), gain=float(m_gain), clamp=float(m_clamp))
+        args = (_native.ptr(x), _native.ptr(w), _native.ptr(y), None, None, ep_ref, ctypes.byref(am))
+        _issue('conv', flags, lib.pasta_conv2d_masked, args, desc, work, x.device)
+    elif wmod is not None:
         assert iscale is None and oscale is None
         mod_s = _f32(wmod[0]).contiguous()
         mod_d = _f32(wmod[1]).contiguous() if wmod[1] is not None else None
@@ -555,15 +567,16 @@ def _act_epilogue(b, act_cfg, res=None):
     act, alpha, gain, clamp = act_cfg
     return (b, ba.activation_funcs[act].cuda_idx, alpha, gain, clamp, res)
 
-def _save_epilogue_output(ctx, y, act_cfg, inputs, extra=(), passthrough=None, tape=True):
+def _save_epilogue_output(ctx, y, act_cfg, inputs, extra=(), passthrough=None, tape=True, keep_y=True):
     """Saves ``inputs``, the epilogue's output y and ``extra`` for the backward and returns the forward's result.  y is needed there only as
     the activation / clamp mask: a linear, unclamped layer (the residual skips, whose output the blocks then update in place) must not pin it.
-    ``tape``: y passes the test instrument bias_act.SlopeTape first.  ``passthrough`` (the input x): returns (y, x)."""
+    ``tape``: y passes the test instrument bias_act.SlopeTape first.  ``passthrough`` (the input x): returns (y, x).  ``keep_y=False``: the
+    layer defers its activation gradient to the reader of y, which holds y itself."""
     from . import bias_act as ba
     act, _, _, clamp = act_cfg
     if tape and ba.slope_tape is not None:
         y = ba.slope_tape.visit(y, act)
-    ctx.save_for_backward(*inputs, y if act != 'linear' or clamp >= 0 else None, *extra)
+    ctx.save_for_backward(*inputs, y if keep_y and (act != 'linear' or clamp >= 0) else None, *extra)
     if passthrough is None:
         return y
     ctx.set_materialize_grads(False)        # an unused output's gradient arrives as None, not as a tensor of zeros
@@ -585,6 +598,13 @@ def _epilogue_grad(dy, y, bias, act_cfg, want_db):
         db = ba._BiasSum.apply(dz, 1)
     return dz, db
 
+def _output_grad(dy, y, bias, act_cfg, want_db, deferred):
+    """``_epilogue_grad``, or -- ``deferred``: the reader of y has applied this layer's activation gradient, ``dy`` IS dz -- the bias sum alone."""
+    if not deferred:
+        return _epilogue_grad(dy, y, bias, act_cfg, want_db)
+    from . import bias_act as ba
+    return dy, (ba._BiasSum.apply(dy.contiguous(), 1, True) if want_db and bias is not None else None)
+
 def _hand_over(x, again, pieces=False):
     """``again`` is the pass-through output autograd made of ``x``: the same data at the same version, so x's maxima -- and with ``pieces`` its
     packed pieces (``share_pieces``) -- go along for the next reader."""
@@ -598,11 +618,70 @@ def _hand_over(x, again, pieces=False):
         again._pasta_pieces = (again._version, again.data_ptr()) + hit[2:]
     return again
 
+# ---- an input's activation gradient in the launch that writes its gradient (include/pasta_hip.h, pasta_act_mask) --------------------------------
+# A layer whose input x is the activated output y of the layer in front holds, in its backward, everything the activation gradient of THAT layer
+# needs: dz = dx * act'(y) depends on y alone (relu / lrelu, gain, clamp).  So the launch that writes dx applies it in its store, from its own
+# saved tensor, and the layer in front skips its stand-alone pass (two reads and a write of the activation per pair).  The protocol:
+#   consumer  ``input_act=(act, alpha, gain, clamp)``: "my x is the activated output of a layer that will not apply its own activation gradient" --
+#             the backward returns dz of that layer instead of dx: in the store of the input-gradient launch where a kernel does it and no graph
+#             of the backward is recorded, by the differentiable stand-alone pass otherwise (R1's double backward, K-sliced launches, 16-bit
+#             storage, the other arithmetics), so that what the producer receives is ALWAYS dz;
+#   producer  ``defer_act_grad=True``: its backward takes the incoming gradient as dz and only sums the bias gradient from it.
+# Both flags are set together, by the module that owns both layers, for a tensor with no other reader (or whose other reader's gradient joins
+# through ``passthrough``, in front of the mask).  Results are bit-identical to the passes: same fp32 value, same rule (csrc/common.h act_grad1).
+_ACT_GRAD_IN_WRITER = True      # False: nobody defers, every layer runs its own pass (tests and the A/B compare the two)
+
+def act_grad_pair_ok(x, act):
+    """May a module set ``defer_act_grad`` on the layer that writes ``act(.)`` from the fp32 GPU tensor ``x`` and ``input_act`` on its reader?"""
+    return (_ACT_GRAD_IN_WRITER and act in ('relu', 'lrelu') and x.device.type == 'cuda' and x.dtype == torch.float32 and x.numel() > 0
+            and custom_ops.has_entry(_native.lib(), 'pasta_conv2d_masked'))         # (a library that predates the mask: nobody defers)
+
+def input_act_pass(dx, x, input_act):
+    """dz = dx * act'(x) by the stand-alone pass (differentiable to any order): the consumer's fallback."""
+    from . import bias_act as ba
+    return ba._BiasActHipGrad.apply(dx.contiguous(), None, None, x, (1,) + tuple(input_act))
+
+def mask_store_allowed(dy, x):
+    """What every store-side mask asks of the backward it runs in: the protocol on, no graph being recorded, fp32 GPU tensors, a library that has it."""
+    return (_ACT_GRAD_IN_WRITER and not torch.is_grad_enabled() and dy.device.type == 'cuda' and dy.dtype == torch.float32 and x.dtype == torch.float32
+            and dy.numel() > 0 and custom_ops.has_entry(_native.lib(), 'pasta_conv2d_masked'))
+
+def _mask_launch_ok(dz, w, gcfg):
+    """Does a kernel apply the input-activation mask in the store of ``conv(dz, w)`` under ``gcfg`` (pasta_conv2d_mask_available)?"""
+    n, c_in, h, wd = (int(v) for v in dz.shape)
+    kh, kw = int(w.shape[2]), int(w.shape[3])
+    c_out = int(w.shape[1]) * gcfg.groups if gcfg.transposed else int(w.shape[0])
+    oh, ow = _out_hw(gcfg, h, wd, kh, kw)
+    if oh < 1 or ow < 1:
+        return False
+    desc = _desc(gcfg, (n, c_in, h, wd), c_out, oh, ow, kh, kw)
+    key = ('mask', PLAN_EPILOGUE, _desc_key(desc))
+    hit = _plan_cache.get(key)
+    if hit is None:
+        hit = _plan_cache[key] = _native.lib().pasta_conv2d_mask_available(ctypes.byref(desc), PLAN_EPILOGUE) == 1
+    return hit
+
+def _input_grad(dz, w, gcfg, dxp, x, input_act, ws):
+    """The gradient at a convolution's input ``x`` given ``dz`` at its output, plus ``dxp`` (another consumer's gradient of ``x``, joined in the
+    launch's epilogue where the types agree); with ``input_act`` the result is the gradient at the OUTPUT of the convolution in front of ``x``:
+    mask in the store, or launch and pass.  ``ws``: the prepacked workspace of the launch (``_pack_pair``)."""
+    join = dxp is not None and dxp.dtype == dz.dtype
+    if input_act is not None and (dxp is None or join) and mask_store_allowed(dz, x) and w.dtype == torch.float32 and _mask_launch_ok(dz, w, gcfg):
+        return _launch_conv(dz, w, gcfg, epilogue=_act_epilogue(None, _LINEAR_EPILOGUE, dxp), mask=(x, input_act), prepacked=ws)
+    if join:
+        dx = _ConvBiasActHip.apply(dz, w, None, gcfg, _LINEAR_EPILOGUE, dxp, False, ws)
+    else:
+        dx = _ConvHip.apply(dz, w, gcfg, ws)
+        if dxp is not None:
+            dx = dx + dxp
+    return dx if input_act is None else input_act_pass(dx, x, input_act)
+
 class _ConvHip(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, cfg, prepacked=None):
+    def forward(ctx, x, w, cfg, prepacked=None, input_act=None):
         used = {}
         ctx.dgrad_ws = None
+        ctx.input_act = input_act
         if prepacked is None and ctx.needs_input_grad[0]:
             prepacked, ctx.dgrad_ws = _pack_pair(x, w, cfg)
         y = _launch_conv(x, w, cfg, used=used, prepacked=prepacked)
@@ -617,11 +696,11 @@ class _ConvHip(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             gcfg = _grad_cfg(cfg, x.shape[2:], dy.shape[2:], w.shape[2], w.shape[3])
-            dx = _ConvHip.apply(dy, w, gcfg, ctx.dgrad_ws)
+            dx = _input_grad(dy, w, gcfg, None, x, ctx.input_act, ctx.dgrad_ws)
             assert dx.shape == x.shape
         if ctx.needs_input_grad[1] and not weight_gradients_disabled:
             dw = _ConvWgradHip.apply(dy, x, cfg, tuple(w.shape), w.dtype, ctx.x_amax)
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 class _ConvBiasActHip(torch.autograd.Function):
     """y = bias_act(conv(x, w), b) with the bias / activation / gain / clamp applied in the convolution's epilogue.
@@ -630,11 +709,13 @@ class _ConvBiasActHip(torch.autograd.Function):
 
     ``passthrough=True`` returns ``(y, x)``: the second output is the input again, to be handed to the OTHER consumers of ``x`` (a
     residual block's skip branch).  Their gradient then arrives here as ``dxp`` and joins this layer's input gradient in the epilogue of
-    the input-gradient launch (one read of it) -- instead of autograd adding two full tensors afterwards (two reads and a write)."""
+    the input-gradient launch (one read of it) -- instead of autograd adding two full tensors afterwards (two reads and a write).
+    ``input_act`` / ``defer_act_grad``: the protocol above ``_ACT_GRAD_IN_WRITER`` (this layer as consumer / as producer)."""
     @staticmethod
-    def forward(ctx, x, w, b, cfg, act_cfg, res=None, passthrough=False, prepacked=None):
+    def forward(ctx, x, w, b, cfg, act_cfg, res=None, passthrough=False, prepacked=None, input_act=None, defer_act_grad=False):
         used = {}
         ctx.dgrad_ws = None
+        ctx.input_act, ctx.defer_act_grad = input_act, bool(defer_act_grad)
         shared = _shared_lookup(x) if not x.is_inference() else None
         if shared is not None and _shared_pieces_ok(x, w, cfg, True):
             # x was packed for its several readers (share_pieces): this launch copies the pieces; its maxima are the pack's bound row
@@ -645,29 +726,26 @@ class _ConvBiasActHip(torch.autograd.Function):
                 prepacked, ctx.dgrad_ws = _pack_pair(x, w, cfg)
             y = _launch_conv(x, w, cfg, epilogue=_act_epilogue(b, act_cfg, res), used=used, prepacked=prepacked)
         ctx.cfg, ctx.act_cfg, ctx.x_amax = cfg, act_cfg, (used.get('x_amax') if x.dtype == torch.float32 else None)
-        return _save_epilogue_output(ctx, y, act_cfg, (x, w, b), passthrough=x if passthrough else None)
+        return _save_epilogue_output(ctx, y, act_cfg, (x, w, b), passthrough=x if passthrough else None, keep_y=not defer_act_grad)
 
     @staticmethod
     def backward(ctx, dy, dxp=None):
         x, w, b, y = ctx.saved_tensors
         if dy is None:                              # only the pass-through output was differentiated
-            return dxp, None, None, None, None, None, None, None
+            if dxp is not None and ctx.input_act is not None:
+                dxp = input_act_pass(dxp, x, ctx.input_act)
+            return (dxp,) + (None,) * 9
         cfg = ctx.cfg
         dx = dw = None
-        dz, db = _epilogue_grad(dy, y, b, ctx.act_cfg, ctx.needs_input_grad[2])
+        dz, db = _output_grad(dy, y, b, ctx.act_cfg, ctx.needs_input_grad[2], ctx.defer_act_grad)
         if ctx.needs_input_grad[0]:
             gcfg = _grad_cfg(cfg, x.shape[2:], dz.shape[2:], w.shape[2], w.shape[3])
-            if dxp is not None and dxp.dtype == dz.dtype:
-                dx = _ConvBiasActHip.apply(dz, w, None, gcfg, _LINEAR_EPILOGUE, dxp, False, ctx.dgrad_ws)
-            else:
-                dx = _ConvHip.apply(dz, w, gcfg, ctx.dgrad_ws)
-                if dxp is not None:
-                    dx = dx + dxp
+            dx = _input_grad(dz, w, gcfg, dxp, x, ctx.input_act, ctx.dgrad_ws)
             assert dx.shape == x.shape
         if ctx.needs_input_grad[1] and not weight_gradients_disabled:
             dw = _ConvWgradHip.apply(dz, x, cfg, tuple(w.shape), w.dtype, ctx.x_amax)
         dres = dz if ctx.needs_input_grad[5] else None     # the residual enters before the activation
-        return dx, dw, db, None, None, dres, None, None
+        return dx, dw, db, None, None, dres, None, None, None, None
 
 class _BlurConvS2Hip(torch.autograd.Function):
     """``bias_act(conv2d(upfirdn2d(x, f, padding), w, stride=2) [+ res], b)`` -- the down path of conv2d_resample (reference :119-122 followed by the
@@ -678,8 +756,9 @@ class _BlurConvS2Hip(torch.autograd.Function):
     fp32 blurred tensor recomputed from ``x`` by the differentiable operators instead.  ``passthrough`` as in ``_ConvBiasActHip``: the filter is
     what reads ``x``, and the other consumers' gradient is the addend of its backward launch."""
     @staticmethod
-    def forward(ctx, x, f, w, b, ucfg, cfg, act_cfg, res=None, passthrough=False):
+    def forward(ctx, x, f, w, b, ucfg, cfg, act_cfg, res=None, passthrough=False, input_act=None):
         px0, px1, py0, py1, flip, ugain = ucfg
+        ctx.input_act = input_act        # (consumer side of the protocol above ``_ACT_GRAD_IN_WRITER``: the mask rides in the filter's transpose)
         pieces, bound, shape = blur_pieces(x, f, (px0, px1, py0, py1), flip, ugain)
         y = _launch_conv(pieces, w, cfg, epilogue=_act_epilogue(b, act_cfg, res), pieces=(bound, shape))
         ctx.ucfg, ctx.cfg, ctx.act_cfg, ctx.shape = ucfg, cfg, act_cfg, shape
@@ -690,7 +769,9 @@ class _BlurConvS2Hip(torch.autograd.Function):
         from . import upfirdn2d as up
         x, f, w, b, y, pieces, bound = ctx.saved_tensors
         if dy is None:
-            return dxp, None, None, None, None, None, None, None, None
+            if dxp is not None and ctx.input_act is not None:
+                dxp = input_act_pass(dxp, x, ctx.input_act)
+            return (dxp,) + (None,) * 9
         cfg, shape = ctx.cfg, ctx.shape
         px0, px1, py0, py1, flip, ugain = ctx.ucfg
         dx = dw = None
@@ -701,10 +782,10 @@ class _BlurConvS2Hip(torch.autograd.Function):
             assert tuple(dxb.shape) == tuple(shape)
             ih, iw = x.shape[2], x.shape[3]
             ucfg_t = (1, 1, 1, 1, 3 - px0, iw - shape[3] + px0, 3 - py0, ih - shape[2] + py0, not flip, ugain)      # upfirdn2d._Upfirdn2dHip.backward, up = down = 1, 4 taps
-            dx = up._Upfirdn2dHip.apply(dxb, f, ucfg_t, dxp) if dxp is not None else up._Upfirdn2dHip.apply(dxb, f, ucfg_t)
+            dx = up.input_grad(dxb, f, ucfg_t, dxp, x, ctx.input_act)
             assert dx.shape == x.shape
         elif dxp is not None:
-            dx = dxp
+            dx = dxp if ctx.input_act is None else input_act_pass(dxp, x, ctx.input_act)
         if ctx.needs_input_grad[2] and not weight_gradients_disabled:
             if torch.is_grad_enabled():             # a graph of this backward pass is being recorded: keep everything differentiable
                 xb = up._Upfirdn2dHip.apply(x, f, (1, 1, 1, 1, px0, px1, py0, py1, flip, ugain))
@@ -712,10 +793,10 @@ class _BlurConvS2Hip(torch.autograd.Function):
             else:
                 dw = _launch_wgrad(pieces, dz, cfg, tuple(w.shape), w.dtype, pieces=(bound, shape))
         dres = dz if ctx.needs_input_grad[7] else None
-        return dx, None, dw, db, None, None, None, dres, None
+        return dx, None, dw, db, None, None, None, dres, None, None
 
 def blur_conv2d_s2_bias_act(x, f, weight, pad4, flip_filter=False, bias=None, act='linear', alpha=None, gain=None, clamp=None, wgain=1.0,
-                            residual=None, passthrough=False):
+                            residual=None, passthrough=False, input_act=None):
     """``bias_act(conv2d(upfirdn2d(x, f, padding=pad4, flip_filter=flip_filter), weight, stride=2) [+ residual], bias, ...)`` with the blurred
     tensor as producer-written operand pieces (``pieces_available`` says whether the kernels exist for these shapes)."""
     from . import bias_act as ba
@@ -724,9 +805,9 @@ def blur_conv2d_s2_bias_act(x, f, weight, pad4, flip_filter=False, bias=None, ac
     cfg = _Cfg((False, 2, 0, 0, 0, 0, 1, float(wgain)))
     ucfg = (int(pad4[0]), int(pad4[1]), int(pad4[2]), int(pad4[3]), bool(flip_filter), 1.0)
     if passthrough and torch.is_grad_enabled() and x.requires_grad:
-        y, again = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, act_cfg, residual, True)
+        y, again = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, act_cfg, residual, True, input_act)
         return y, _hand_over(x, again)
-    y = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, act_cfg, residual)
+    y = _BlurConvS2Hip.apply(x, f, weight, bias, ucfg, cfg, act_cfg, residual, False, input_act)
     return (y, x) if passthrough else y
 
 _LINEAR_EPILOGUE = ('linear', 0.0, 1.0, -1.0)      # (act, alpha, gain, clamp) of an epilogue that only adds the residual
@@ -783,10 +864,11 @@ def conv2d_cat1x1_bias_act(x, x2, weight, bias=None, act='linear', alpha=None, g
     return conv2d_bias_act(torch.cat([x, x2], dim=1), weight, bias, act=act, alpha=act_cfg[1], gain=act_cfg[2], clamp=clamp, wgain=wgain)
 
 def conv2d_bias_act(input, weight, bias=None, stride=1, padding=0, groups=1, act='linear', alpha=None, gain=None, clamp=None, wgain=1.0,
-                    residual=None, passthrough=False):
+                    residual=None, passthrough=False, input_act=None, defer_act_grad=False):
     """``bias_act(conv2d(input, weight) [+ residual], bias, act, alpha, gain, clamp)`` in one launch (fp32 GPU tensors,
     act in FUSABLE_ACTS); other cases run the ops separately.  ``passthrough=True`` returns ``(y, input')`` where ``input'`` is the
-    input again, for its other consumers: see ``_ConvBiasActHip``."""
+    input again, for its other consumers: see ``_ConvBiasActHip``.  ``input_act`` / ``defer_act_grad``: the protocol above
+    ``_ACT_GRAD_IN_WRITER`` (fused launches only: ``act_grad_pair_ok`` is what a module asks before it sets them)."""
     from . import bias_act as ba
     act_cfg = ba.act_cfg(act, alpha, gain, clamp)
     if act in FUSABLE_ACTS and input.dtype in IO_CODES and input.device.type == 'cuda' and input.numel() > 0:
@@ -795,10 +877,11 @@ def conv2d_bias_act(input, weight, bias=None, stride=1, padding=0, groups=1, act
         assert sh == sw
         cfg = _Cfg((False, sh, ph, pw, 0, 0, int(groups), float(wgain)))
         if passthrough and torch.is_grad_enabled() and input.requires_grad:
-            y, again = _ConvBiasActHip.apply(input, weight, bias, cfg, act_cfg, residual, True)
+            y, again = _ConvBiasActHip.apply(input, weight, bias, cfg, act_cfg, residual, True, None, input_act, defer_act_grad)
             return y, _hand_over(input, again, pieces=True)
-        y = _ConvBiasActHip.apply(input, weight, bias, cfg, act_cfg, residual)
+        y = _ConvBiasActHip.apply(input, weight, bias, cfg, act_cfg, residual, False, None, input_act, defer_act_grad)
         return (y, input) if passthrough else y
+    assert input_act is None and not defer_act_grad, 'input_act / defer_act_grad belong to the fused launches (act_grad_pair_ok)'
     y = conv2d(input, weight, stride=stride, padding=padding, groups=groups, wgain=wgain)
     if residual is not None:
         y = y + residual
@@ -980,16 +1063,17 @@ def _check_common(input, weight, dilation):
 def _add_bias(y, bias):
     return y if bias is None else y + bias.to(y.dtype).reshape(1, -1, 1, 1)
 
-def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, wgain=1.0):
+def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, wgain=1.0, input_act=None):
     """Same contract as ``torch.nn.functional.conv2d`` (reference :35-38); equal strides in x and y.
-    ``wgain`` (extension): convolve with ``weight * wgain`` without materialising the product."""
+    ``wgain`` (extension): convolve with ``weight * wgain`` without materialising the product.  ``input_act`` (extension): this layer as
+    consumer in the protocol above ``_ACT_GRAD_IN_WRITER``."""
     _check_common(input, weight, dilation)
     sh, sw = _pair(stride)
     if sh != sw:
         raise NotImplementedError('conv2d_gradfix: anisotropic stride is not implemented')
     ph, pw = _pair(padding)
     cfg = _Cfg((False, sh, ph, pw, 0, 0, int(groups), float(wgain)))
-    return _add_bias(_ConvHip.apply(input, weight, cfg), bias)
+    return _add_bias(_ConvHip.apply(input, weight, cfg, None, input_act), bias)
 
 def conv_transpose2d(input, weight, bias=None, stride=1, padding=0, output_padding=0, groups=1, dilation=1, wgain=1.0):
     """Same contract as ``torch.nn.functional.conv_transpose2d`` (reference :40-43)."""

@@ -19,7 +19,7 @@ from .upfirdn2d import _get_filter_size
 def _get_weight_shape(w):
     return [int(sz) for sz in w.shape]
 
-def _conv2d_wrapper(x, w, stride=1, padding=0, groups=1, transpose=False, flip_weight=True, wgain=1.0, modulation=None):
+def _conv2d_wrapper(x, w, stride=1, padding=0, groups=1, transpose=False, flip_weight=True, wgain=1.0, modulation=None, input_act=None):
     """Dispatch to ``conv2d`` / ``conv_transpose2d``. Both are correlations, so a true convolution
     (``flip_weight=False``) mirrors the taps first."""
     if not flip_weight:
@@ -30,12 +30,13 @@ def _conv2d_wrapper(x, w, stride=1, padding=0, groups=1, transpose=False, flip_w
                                                        per_sample=modulation[2])
     if transpose:
         return conv2d_gradfix.conv_transpose2d(x, w, stride=stride, padding=padding, groups=groups, wgain=wgain)
-    return conv2d_gradfix.conv2d(x, w, stride=stride, padding=padding, groups=groups, wgain=wgain)
+    return conv2d_gradfix.conv2d(x, w, stride=stride, padding=padding, groups=groups, wgain=wgain, input_act=input_act)
 
 #----------------------------------------------------------------------------
 
 def conv2d_resample_bias_act(x, w, b=None, f=None, up=1, down=1, padding=0, groups=1, flip_weight=True, flip_filter=False,
-                             act='linear', alpha=None, gain=None, clamp=None, wgain=1.0, residual=None, passthrough=False):
+                             act='linear', alpha=None, gain=None, clamp=None, wgain=1.0, residual=None, passthrough=False,
+                             input_act=None, defer_act_grad=False):
     """``bias_act(conv2d_resample(x, w, ...), b, act, alpha, gain, clamp)`` -- the body of ``Conv2dLayer.forward``
     (reference training/networks.py:170-179). When the dense convolution is the last step of the resampling
     decomposition (no upsampling), bias / activation / gain / clamp ride in its epilogue; otherwise the two ops run
@@ -44,9 +45,14 @@ def conv2d_resample_bias_act(x, w, b=None, f=None, up=1, down=1, padding=0, grou
     the bias -- also in the epilogue when the convolution is fused.  ``passthrough=True`` (extension) returns ``(y, x')``: ``x'`` is ``x``
     again, to be given to the other consumers of ``x`` so that their gradient joins this layer's input gradient in that launch's epilogue
     (``conv2d_gradfix._ConvBiasActHip``).  In a downsampling layer the FILTER is what reads ``x``: it hands ``x`` on and takes the gradient
-    as the addend of its backward launch (``upfirdn2d._Upfirdn2dHip``); an upsampling layer returns ``x`` itself (nothing joined)."""
+    as the addend of its backward launch (``upfirdn2d._Upfirdn2dHip``); an upsampling layer returns ``x`` itself (nothing joined).
+    ``input_act`` / ``defer_act_grad`` (extension): the layer as consumer / producer of the protocol above
+    ``conv2d_gradfix._ACT_GRAD_IN_WRITER`` -- whatever reads ``x`` first (the convolution, or the filter of a downsampling layer) is the
+    consumer; a producer is a layer without resampling.  Fused launches only: ``conv2d_gradfix.act_grad_pair_ok``."""
     from . import bias_act
     fusable = up == 1 and x.dtype in conv2d_gradfix.IO_CODES and x.device.type == 'cuda' and act in conv2d_gradfix.FUSABLE_ACTS
+    assert (input_act is None and not defer_act_grad) or (fusable and x.numel() > 0 and (not defer_act_grad or down == 1)), \
+        'input_act / defer_act_grad belong to the fused launches (conv2d_gradfix.act_grad_pair_ok)'
     if passthrough and (up != 1 or (down != 1 and not fusable)):
         return conv2d_resample_bias_act(x, w, b=b, f=f, up=up, down=down, padding=padding, groups=groups, flip_weight=flip_weight, flip_filter=flip_filter,
                                         act=act, alpha=alpha, gain=gain, clamp=clamp, wgain=wgain, residual=residual), x
@@ -63,7 +69,7 @@ def conv2d_resample_bias_act(x, w, b=None, f=None, up=1, down=1, padding=0, grou
         wc = w if flip_weight else w.flip([2, 3])
         # (downsampling layers with ``passthrough``: the FILTER is what reads x, so it hands x on and takes the other consumers' gradient)
         if kw == 1 and kh == 1 and down > 1:          # decimate, then the fused 1x1 convolution
-            x = upfirdn2d.upfirdn2d(x=x, f=f, down=down, padding=[px0, px1, py0, py1], flip_filter=flip_filter, passthrough=passthrough)
+            x = upfirdn2d.upfirdn2d(x=x, f=f, down=down, padding=[px0, px1, py0, py1], flip_filter=flip_filter, passthrough=passthrough, input_act=input_act)
             if passthrough:
                 x, again = x
             y = conv2d_gradfix.conv2d_bias_act(x, wc, b, groups=groups, act=act, alpha=alpha, gain=gain, clamp=clamp, wgain=wgain, residual=residual)
@@ -72,16 +78,17 @@ def conv2d_resample_bias_act(x, w, b=None, f=None, up=1, down=1, padding=0, grou
             # round 5: the low-pass writes the operand pieces of the default arithmetic instead of an fp32 tensor; the strided convolution and
             # its weight gradient copy them (conv2d_gradfix._BlurConvS2Hip)
             return conv2d_gradfix.blur_conv2d_s2_bias_act(x, f, wc, (px0, px1, py0, py1), flip_filter=flip_filter, bias=b, act=act, alpha=alpha, gain=gain,
-                                                          clamp=clamp, wgain=wgain, residual=residual, passthrough=passthrough)
+                                                          clamp=clamp, wgain=wgain, residual=residual, passthrough=passthrough, input_act=input_act)
         if down > 1:                                  # low-pass, then the fused strided convolution
-            x = upfirdn2d.upfirdn2d(x=x, f=f, padding=[px0, px1, py0, py1], flip_filter=flip_filter, passthrough=passthrough)
+            x = upfirdn2d.upfirdn2d(x=x, f=f, padding=[px0, px1, py0, py1], flip_filter=flip_filter, passthrough=passthrough, input_act=input_act)
             if passthrough:
                 x, again = x
             y = conv2d_gradfix.conv2d_bias_act(x, wc, b, stride=down, groups=groups, act=act, alpha=alpha, gain=gain, clamp=clamp, wgain=wgain, residual=residual)
             return (y, again) if passthrough else y
         if px0 == px1 and py0 == py1 and px0 >= 0 and py0 >= 0:
             return conv2d_gradfix.conv2d_bias_act(x, wc, b, padding=[py0, px0], groups=groups, act=act, alpha=alpha, gain=gain, clamp=clamp, wgain=wgain,
-                                                  residual=residual, passthrough=passthrough)
+                                                  residual=residual, passthrough=passthrough, input_act=input_act, defer_act_grad=defer_act_grad)
+        assert input_act is None and not defer_act_grad, 'input_act / defer_act_grad: asymmetric padding has no fused launch'
     if passthrough:
         return conv2d_resample_bias_act(x, w, b=b, f=f, up=up, down=down, padding=padding, groups=groups, flip_weight=flip_weight, flip_filter=flip_filter,
                                         act=act, alpha=alpha, gain=gain, clamp=clamp, wgain=wgain, residual=residual), x
@@ -93,7 +100,7 @@ def conv2d_resample_bias_act(x, w, b=None, f=None, up=1, down=1, padding=0, grou
 
 #----------------------------------------------------------------------------
 
-def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight=True, flip_filter=False, wgain=1.0, modulation=None):
+def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight=True, flip_filter=False, wgain=1.0, modulation=None, input_act=None):
     """Convolve ``x`` [N,C,H,W] with ``w`` [O,C//groups,kh,kw], upsampling by ``up`` before and/or
     downsampling by ``down`` after, low-pass filtered with ``f`` (from ``upfirdn2d.setup_filter``).
 
@@ -101,7 +108,9 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
     ``flip_weight=True`` is correlation (``torch.nn.functional.conv2d``), ``False`` convolution.
     ``modulation`` (extension, forward only, groups == 1) = (styles [N,I], dcoefs [N,O] or None, per_sample): the dense
     convolution of the decomposition is ``conv2d_gradfix.modulated_conv2d_forward`` -- styles in the kernel's staging
-    (shared weight; dcoefs are then left to the caller) or styles and dcoefs in the weight packing (per-sample weights)."""
+    (shared weight; dcoefs are then left to the caller) or styles and dcoefs in the weight packing (per-sample weights).
+    ``input_act`` (extension; the plain convolution without resampling only): the layer as consumer of the protocol above
+    ``conv2d_gradfix._ACT_GRAD_IN_WRITER``."""
     assert isinstance(x, torch.Tensor) and x.ndim == 4
     assert isinstance(w, torch.Tensor) and w.ndim == 4 and (w.dtype == x.dtype or w.dtype == torch.float32)    # fp32 master weights may meet 16-bit activations
     assert f is None or (isinstance(f, torch.Tensor) and f.ndim in [1, 2] and f.dtype == torch.float32)
@@ -125,6 +134,7 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
         py1 += (fh - down) // 2
     pad = [px0, px1, py0, py1]
     pointwise = (kw == 1 and kh == 1)
+    assert input_act is None or (up == 1 and down == 1 and modulation is None), 'input_act: the plain convolution only'
 
     # 1x1 kernel, downsampling: decimate first, then mix channels on the small image.
     if pointwise and down > 1 and up == 1:
@@ -163,7 +173,8 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
 
     # No resampling and symmetric non-negative padding: a plain convolution.
     if up == 1 and down == 1 and px0 == px1 and py0 == py1 and px0 >= 0 and py0 >= 0:
-        return _conv2d_wrapper(x=x, w=w, padding=[py0, px0], groups=groups, flip_weight=flip_weight, wgain=wgain, modulation=modulation)
+        return _conv2d_wrapper(x=x, w=w, padding=[py0, px0], groups=groups, flip_weight=flip_weight, wgain=wgain, modulation=modulation, input_act=input_act)
+    assert input_act is None, 'input_act: the plain convolution only'
 
     # Anything else: pad/upsample, convolve, downsample as three separate steps.
     x = upfirdn2d.upfirdn2d(x=x, f=(f if up > 1 else None), up=up, padding=pad, gain=up ** 2, flip_filter=flip_filter)

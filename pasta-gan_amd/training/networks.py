@@ -615,13 +615,20 @@ class _FilteredConv(torch.nn.Module):
 class Conv2dLayer(_FilteredConv):
     """conv2d_resample -> bias_act, bias / activation / gain / clamp in the convolution's epilogue where the dense
     convolution is the last step (networks.py:132-179)."""
-    def forward(self, x, gain=1, passthrough=False, add=None):
+    def output_act(self, gain=1):
+        """(act, alpha, gain, clamp) of what ``forward(x, gain)`` applies: what the reader of the output passes as ``input_act``."""
+        return bias_act.act_cfg(self.activation, None, *_scaled_act(self.activation, gain, self.conv_clamp))
+
+    def forward(self, x, gain=1, passthrough=False, add=None, input_act=None, defer_act_grad=False):
         """``passthrough=True`` (own extension) returns ``(y, x')``: hand ``x'`` instead of ``x`` to the other consumers of ``x`` (a residual
         block's skip branch) and their gradient is added in the epilogue of this layer's input-gradient launch (conv2d_gradfix._ConvBiasActHip).
         ``add`` (own extension; shape of the output): returns ``layer(x, gain) + add`` -- for a linear, bias-free, unclamped layer on fp32 GPU
         tensors (the skip branch of the residual blocks) the sum is formed in the convolution's epilogue, the gain folded into the weight
-        gain; otherwise by ``add_`` as the reference writes it (networks.py:557, :994)."""
+        gain; otherwise by ``add_`` as the reference writes it (networks.py:557, :994).
+        ``input_act`` / ``defer_act_grad`` (own extension): the layer as consumer / producer of a pair whose activation gradient is applied
+        by the consumer's backward launch (conv2d_gradfix, ``_ACT_GRAD_IN_WRITER``); set together by the module that owns both layers."""
         if add is not None:
+            assert input_act is None and not defer_act_grad
             if _SKIP_ADD_FUSED and self.activation == 'linear' and self.bias is None and self.conv_clamp is None and x.dtype == torch.float32 \
                     and x.device.type == 'cuda' and self.up == 1 and not passthrough:
                 args = self._resample_args(x)
@@ -633,7 +640,8 @@ class Conv2dLayer(_FilteredConv):
             return y.add_(add)
         act_gain, act_clamp = _scaled_act(self.activation, gain, self.conv_clamp)
         return conv2d_resample.conv2d_resample_bias_act(x=x, b=(None if self.bias is None else self.bias.to(x.dtype)), act=self.activation,
-                                                        gain=act_gain, clamp=act_clamp, passthrough=passthrough, **self._resample_args(x))
+                                                        gain=act_gain, clamp=act_clamp, passthrough=passthrough, input_act=input_act,
+                                                        defer_act_grad=defer_act_grad, **self._resample_args(x))
 
 # the residual sum in the skip convolution's epilogue (False: ``shortcut.add_(...)`` as the reference writes it; tests compare the two)
 _SKIP_ADD_FUSED = True
@@ -801,12 +809,12 @@ class ToRGBLayerV18(_StyledHeads):
 # and a write per addition; tests compare the two)
 _GRAD_JOIN = True
 
-def _layer_and_input(layer, x):
+def _layer_and_input(layer, x, **kw):
     """``(layer(x), x')`` for a tensor with further consumers: give them ``x'`` (= ``x``), and their gradient is added in the epilogue of
     the layer's input-gradient launch instead of by a pass of its own (``Conv2dLayer.forward(passthrough=True)``)."""
     # fp32 storage only: in 16-bit storage the reference rounds each consumer's gradient to the storage type BEFORE the addition, and the
     # config-5 fixtures (tests/test_config5_gpu.py) hold the path to that sequence of roundings
-    return layer(x, passthrough=True) if (_GRAD_JOIN and x.dtype == torch.float32) else (layer(x), x)
+    return layer(x, passthrough=True, **kw) if (_GRAD_JOIN and x.dtype == torch.float32) else (layer(x, **kw), x)
 
 @persistence.persistent_class
 class ResBlock(torch.nn.Module):
@@ -913,13 +921,16 @@ class Spade_Norm_Block(torch.nn.Module):
             return spade_modulate(x, gb[0], None, eps=self.param_free_norm.eps, relu_gain=relu_gain, clamp=clamp, shared=(gb[1], gb[2]),
                                   passthrough=passthrough)
         mlp = self.conv_mlp         # no activation in front, nn.ReLU behind (:4373-4374): the ReLU rides in the epilogue
-        actv = conv2d_resample.conv2d_resample_bias_act(x=denorm_feats, b=None, act='relu', gain=1, **mlp._resample_args(denorm_feats))
+        # the hidden map has ONE reader where gamma | beta come from one convolution: that launch's backward applies the ReLU's gradient
+        pair = self._twin_convs(denorm_feats) and mlp.up == mlp.down == 1 and conv2d_gradfix.act_grad_pair_ok(denorm_feats, 'relu')
+        actv = conv2d_resample.conv2d_resample_bias_act(x=denorm_feats, b=None, act='relu', gain=1, defer_act_grad=pair, **mlp._resample_args(denorm_feats))
         if self._twin_convs(actv):
             # conv_gamma and conv_beta read the same tensor (:4375-4376): ONE convolution over the concatenated weights
             # writes gamma | beta as channel halves, which the normalisation kernel reads (and, backwards, writes) in place
             g = self.conv_gamma
             gamma = conv2d_resample.conv2d_resample(x=actv, w=torch.cat([g.weight, self.conv_beta.weight], dim=0), f=g.resample_filter,
-                                                    padding=g.padding, flip_weight=True, wgain=g.weight_gain)
+                                                    padding=g.padding, flip_weight=True, wgain=g.weight_gain,
+                                                    input_act=bias_act.act_cfg('relu', None, 1, None) if pair else None)
             beta = None
         else:
             gamma, beta = self.conv_gamma(actv, no_act=True), self.conv_beta(actv, no_act=True)
@@ -977,13 +988,17 @@ class Spade_ResBlockV2(torch.nn.Module):
         conv2d_gradfix.share_pieces(feat)                # the blocks of a generator pass read ONE feature map: packed once, copied by every conv_mlp launch
         # (the feature map again as second result: the next SPADE block reads IT, and its gradient joins this convolution's input gradient
         # in that launch's epilogue -- the three blocks' gradients into the map without the two 268 MB additions autograd would make)
+        # (the hidden maps have ONE reader, the grouped convolution: its backward launch applies the ReLU's gradient -- conv2d_gradfix,
+        # ``_ACT_GRAD_IN_WRITER``)
+        pair = conv2d_gradfix.act_grad_pair_ok(feat, 'relu')
         actv = conv2d_resample.conv2d_resample_bias_act(x=feat, w=torch.cat([n.conv_mlp.weight for n in norms], dim=0), b=None, act='relu', gain=1,
                                                         f=mlp.resample_filter, padding=mlp.padding, flip_weight=True, wgain=mlp.weight_gain,
-                                                        passthrough=_GRAD_JOIN)
+                                                        passthrough=_GRAD_JOIN, defer_act_grad=pair)
         if _GRAD_JOIN:
             actv, feat = actv
         w_gb = torch.cat([w for n in norms for w in (n.conv_gamma.weight, n.conv_beta.weight)], dim=0)
-        gb_all = conv2d_gradfix.conv2d(actv, w_gb, padding=g.padding, groups=3, wgain=g.weight_gain)
+        gb_all = conv2d_gradfix.conv2d(actv, w_gb, padding=g.padding, groups=3, wgain=g.weight_gain,
+                                       input_act=bias_act.act_cfg('relu', None, 1, None) if pair else None)
         holder = _SharedGrad(gb_all, 3)
         return [(v, holder, i) for i, v in enumerate(_SplitGroups.apply(gb_all, holder))], feat
 
@@ -1364,16 +1379,25 @@ class DiscriminatorBlock(torch.nn.Module):
         if x is not None:
             misc.assert_shape(x, [None, self.in_channels, self.resolution, self.resolution])
             x = x.to(dtype=dtype, memory_format=memory_format)
+        rgb_act = None
         if hasattr(self, 'fromrgb'):
             misc.assert_shape(img, [None, self.img_channels, self.resolution, self.resolution])
             img = img.to(dtype=dtype, memory_format=memory_format)
-            y = self.fromrgb(img)
+            # fromrgb -> conv0: the other reader of fromrgb's output, the skip branch, hands its gradient to conv0's backward launch
+            # (``_layer_and_input``), which adds it in front of the mask
+            rgb_act = self.fromrgb.output_act() if (x is None and self.architecture == 'resnet' and _GRAD_JOIN and self.conv0.up == self.conv0.down == 1
+                                                    and self.conv0.activation in conv2d_gradfix.FUSABLE_ACTS
+                                                    and conv2d_gradfix.act_grad_pair_ok(img, self.fromrgb.activation)) else None
+            y = self.fromrgb(img, defer_act_grad=rgb_act is not None)
             x = y if x is None else x + y
             img = upfirdn2d.downsample2d(img, self.resample_filter) if self.architecture == 'skip' else None
         if self.architecture == 'resnet':
             half = np.sqrt(0.5)
-            h, x = _layer_and_input(self.conv0, x)      # x again: the skip branch's gradient joins conv0's input gradient in that launch
-            x = self.skip(x, gain=half, add=self.conv1(h, gain=half))     # skip(x) + conv1(.): the sum in the skip convolution's epilogue
+            # conv0 -> conv1: conv1's low-pass is the one reader of conv0's output, the filter's transpose applies conv0's activation gradient
+            pair = (conv2d_gradfix.act_grad_pair_ok(x, self.conv0.activation) and self.conv0.up == self.conv0.down == 1 and self.conv1.up == 1
+                    and self.conv1.activation in conv2d_gradfix.FUSABLE_ACTS)
+            h, x = _layer_and_input(self.conv0, x, input_act=rgb_act, defer_act_grad=pair)      # x again: the skip branch's gradient joins conv0's input gradient in that launch
+            x = self.skip(x, gain=half, add=self.conv1(h, gain=half, input_act=self.conv0.output_act() if pair else None))     # skip(x) + conv1(.): the sum in the skip convolution's epilogue
         else:
             x = self.conv1(self.conv0(x))
         assert x.dtype == dtype
