@@ -679,6 +679,30 @@ int pasta_images_to_u8(const float* images, uint8_t* out, int N, int H, int Wt, 
 int pasta_images_keep_to_u8(const float* images, const uint8_t* photo, const uint8_t* keep, uint8_t* out, int N, int H, int Wt, int c0,
                             int W, int radius, void* stream);
 
+/* Where the photograph may be pasted (this project's own rule; --kept-parts / --background / --kept-garments photo of test.py and
+ * test_512.py, training/tryon_pairs.py's photo_paste_mask): the 0 / 1 region that goes to pasta_images_keep_to_u8 as `keep`.  A
+ * pixel of the photograph is pasted only where the photograph's label map AND the generator's own statement of what it drew
+ * there agree.  Per item n: L = parsing [N, H, W] uint8, the person's labels; palm [N, H, Ht] uint8 or null, the palm mask on
+ * the padded rows; c0 = (Ht - W) / 2; rule [N, 256] uint8: rule[n][l] is a 4-bit set of the statements under which label l of
+ * item n's photograph may be pasted (256 rows, so that any byte a label file holds indexes it without a check).
+ *   The generator's statement s(y, x) in {0 other, 1 upper garment, 2 lower garment, 3 skin}, read at column c0 + x of its heads:
+ *     head_planes = 6  heads_a fp32 [N, 6, Ht, Ht], the parsing logits (GeneratorFull), heads_b null: c = argmax over the six
+ *                      planes exactly as torch.argmax(dim=1) -- the first NaN if there is one, else the first of the largest --
+ *                      and s = 0, 1, 2, 3, 3, 3 for c = 0..5 (gt_parsing's classes: 3 hands, 4 legs, 5 neck);
+ *     head_planes = 1  heads_a = u, heads_b = l, fp32 [N, 1, Ht, Ht] each, the sigmoid heads (GeneratorV18): s = 1 if u > 0.5,
+ *                      else 2 if l > 0.5, else 0, in IEEE comparisons, so a NaN is "other";
+ *     head_planes = 0  both null: s = 0 everywhere.
+ *   out [N, H, W] uint8: m(y, x) = (palm(y, c0 + x) != 0) || ((rule[n][L(y, x)] >> s(y, x)) & 1); a null palm has no palm term.
+ * The host fills the table (training.tryon_pairs.paste_rules): kept parts 0b1111 at labels 1, 2, 4, 13, 18, 19 (with the palm
+ * pointer); the background 0b0001 at label 0 (pasted only where the generator claims neither garment nor skin); the person's
+ * own upper garment 0b0010 at the upper labels of an item whose outfit keeps it, the own lower garment 0b0100 at the lower
+ * labels likewise -- the label sets of pasta_tryon_outfit_masks_u8 for that size; at 256 x 192 label 6 is in both and the bits
+ * OR.  One launch, every pixel independent.  Refused before any launch: a null parsing, rule or out; head_planes outside
+ * {0, 1, 6}; a heads pointer that disagrees with head_planes; N outside 1..65535, H or Ht outside 1..4096, H > Ht, W < 1,
+ * W > Ht. */
+int pasta_photo_paste_mask_u8(const uint8_t* parsing, const uint8_t* palm, const uint8_t* rule, const float* heads_a, const float* heads_b,
+                              int head_planes, uint8_t* out, int N, int H, int W, int Ht, void* stream);
+
 /* An OUTFIT at 256 x 192 (this project's own; training/tryon_pairs.py, TryOnPairOutfitBatchBuilder): (P, U, L), the person P in
  * the upper garment of U and the lower garment of L, either of whom may be P.  The pair rules above with a source per garment:
  *   1. retain_img, the palm mask (boxes 25 and 15), the stick figure in `pose` and every M_inv are P's;

@@ -20,7 +20,10 @@
 //                                      512 x 320 (the label masks of that set are csrc/tryon_inputs.hip's pasta_tryon_masks_u8);
 //   pasta_images_to_u8                 test.py's (x + 1) * 127.5, crop, clip and uint8 truncation (:133-137);
 //   pasta_images_keep_to_u8            the same with the photograph's kept parts pasted in under a feathered weight (this
-//                                      project's own, --kept-parts photo), in the one launch.
+//                                      project's own, --kept-parts photo), in the one launch;
+//   pasta_photo_paste_mask_u8          the region that entry pastes, widened to the background and the person's own garments
+//                                      (this project's own, --background / --kept-garments photo): the photograph's label map,
+//                                      the palm mask and the generator's own region heads, agreed per pixel, in one pass.
 // The 256 pairs are the 512 rules with label 6 added to the lower garment, stick patches as the second patch list and no image /
 // clothes tensors.  The forward warps are csrc/patches.hip's pasta_warp_perspective_u8 and the stick figures
 // csrc/tryon_inputs.hip's entry.  include/pasta_hip.h lists where the data sets differ and the constants each one passes.
@@ -296,6 +299,76 @@ __global__ __launch_bounds__(256) void images_keep_to_u8_kernel(const float* __r
     }
 }
 
+// ---- where the photograph may be pasted: the label map and the generator's statement agree ----
+
+// include/pasta_hip.h's rule of pasta_photo_paste_mask_u8 (this project's own).  Every pixel is independent: its label indexes the
+// item's 256-byte rule row (in LDS, one byte per thread of the block), whose bit s says whether the generator's statement s allows
+// the paste; a palm pixel is pasted whatever the heads say.  PLANES is the kind of heads: 6 logit planes in heads_a (argmax as
+// torch.argmax: the first NaN, else the first largest), 1 sigmoid plane in each of heads_a and heads_b, or 0, no statement.
+// PX = 4 where the entry found every row aligned for it (a dword of labels, a dword of palm flags, 16-byte loads of the planes,
+// one dword store), PX = 1 otherwise.  Every global load stands before the barrier.
+template <int PX, int PLANES>
+__global__ __launch_bounds__(256) void photo_paste_mask_kernel(const uint8_t* __restrict__ parsing, const uint8_t* __restrict__ palm,
+                                                               const uint8_t* __restrict__ rule, const float* __restrict__ heads_a,
+                                                               const float* __restrict__ heads_b, uint8_t* __restrict__ out, int H, int W,
+                                                               int Ht, int c0) {
+    constexpr int NV = PLANES == 6 ? 6 : PLANES == 1 ? 2 : 0;
+    __shared__ uint8_t row[256];
+    const int n = blockIdx.y;
+    row[threadIdx.x] = rule[(int64_t)n * 256 + threadIdx.x];
+    const int first = (blockIdx.x * 256 + threadIdx.x) * PX;    // PX == 4: W is a multiple of 4, so the four pixels share a row
+    const bool mine = first < H * W;
+    const int y = first / W, x = first - y * W;
+    const int64_t pix = (int64_t)n * H * W + first;
+
+    uint8_t label[PX], hand[PX];
+    float v[NV > 0 ? NV : 1][PX];
+    if (mine) {
+        if constexpr (PX == 4) {
+            const uint32_t lw = *reinterpret_cast<const uint32_t*>(parsing + pix);
+            const uint32_t pw = palm ? *reinterpret_cast<const uint32_t*>(palm + ((int64_t)n * H + y) * Ht + c0 + x) : 0u;
+            for (int j = 0; j < 4; j++) label[j] = (uint8_t)(lw >> (8 * j)), hand[j] = (uint8_t)(pw >> (8 * j));
+        } else {
+            label[0] = parsing[pix];
+            hand[0] = palm ? palm[((int64_t)n * H + y) * Ht + c0 + x] : (uint8_t)0;
+        }
+        for (int k = 0; k < NV; k++) {
+            const float* plane = PLANES == 6 ? heads_a + ((int64_t)n * 6 + k) * Ht * Ht : (k == 0 ? heads_a : heads_b) + (int64_t)n * Ht * Ht;
+            const float* s = plane + (int64_t)y * Ht + c0 + x;
+            if constexpr (PX == 4) {
+                const float4 q = *reinterpret_cast<const float4*>(s);
+                v[k][0] = q.x; v[k][1] = q.y; v[k][2] = q.z; v[k][3] = q.w;
+            } else {
+                v[k][0] = s[0];
+            }
+        }
+    }
+    __syncthreads();
+    if (!mine) return;
+
+    uint32_t word = 0;
+    for (int j = 0; j < PX; j++) {
+        int s = 0;                              // the generator's statement: 0 other, 1 upper, 2 lower, 3 skin
+        if constexpr (PLANES == 6) {
+            float best = v[0][j];
+            int c = 0;
+            for (int k = 1; k < 6; k++) {       // a later plane wins only when it is larger, or the first NaN
+                const float t = v[k][j];
+                if (!(best != best) && (t != t || t > best)) best = t, c = k;
+            }
+            s = c < 3 ? c : 3;                  // gt_parsing's classes: 3 hands, 4 legs, 5 neck are skin
+        } else if constexpr (PLANES == 1) {
+            s = v[0][j] > 0.5f ? 1 : v[1][j] > 0.5f ? 2 : 0;        // IEEE comparisons: a NaN claims nothing
+        }
+        const uint32_t m = (hand[j] != 0) | ((row[label[j]] >> s) & 1u);
+        word |= m << (8 * j);
+    }
+    if constexpr (PX == 4)
+        *reinterpret_cast<uint32_t*>(out + pix) = word;
+    else
+        out[pix] = (uint8_t)word;
+}
+
 }  // namespace pasta
 
 extern "C" int pasta_palm_mask_u8(const uint8_t* parsing, const double* quads, const uint8_t* present, uint8_t* out, int N, int S, int W,
@@ -421,4 +494,39 @@ extern "C" int pasta_images_keep_to_u8(const float* images, const uint8_t* photo
         hipLaunchKernelGGL(images_keep_to_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, images, photo, keep, out, H, Wt, c0, W, radius,
                            tiles_x);
     return launch_status("images_keep_to_u8");
+}
+
+template <int PLANES>
+static void launch_photo_paste_mask(bool wide, dim3 grid, hipStream_t stream, const uint8_t* parsing, const uint8_t* palm, const uint8_t* rule,
+                                    const float* heads_a, const float* heads_b, uint8_t* out, int H, int W, int Ht, int c0) {
+    using namespace pasta;
+    if (wide)
+        hipLaunchKernelGGL((photo_paste_mask_kernel<4, PLANES>), grid, dim3(256), 0, stream, parsing, palm, rule, heads_a, heads_b, out, H, W, Ht, c0);
+    else
+        hipLaunchKernelGGL((photo_paste_mask_kernel<1, PLANES>), grid, dim3(256), 0, stream, parsing, palm, rule, heads_a, heads_b, out, H, W, Ht, c0);
+}
+
+extern "C" int pasta_photo_paste_mask_u8(const uint8_t* parsing, const uint8_t* palm, const uint8_t* rule, const float* heads_a,
+                                         const float* heads_b, int head_planes, uint8_t* out, int N, int H, int W, int Ht, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(parsing && rule && out, "photo_paste_mask_u8: null pointer");
+    PASTA_CHECK(head_planes == 0 || head_planes == 1 || head_planes == 6, "photo_paste_mask_u8: head_planes %d (0, 1 or 6)", head_planes);
+    PASTA_CHECK(!heads_a == (head_planes == 0) && !heads_b == (head_planes != 1),
+                "photo_paste_mask_u8: %d head planes want %s", head_planes,
+                head_planes == 0 ? "no heads" : head_planes == 1 ? "heads_a and heads_b" : "heads_a alone");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 4096 && Ht >= 1 && Ht <= 4096 && H <= Ht && W >= 1 && W <= Ht,
+                "photo_paste_mask_u8: bad shape (%d x %d in a square of %d)", H, W, Ht);
+    const int c0 = (Ht - W) / 2;
+    // four pixels per thread where every row of every tensor starts on the boundary its wide access needs
+    const bool wide = W % 4 == 0 && Ht % 4 == 0 && c0 % 4 == 0 && (uintptr_t)parsing % 4 == 0 && (uintptr_t)palm % 4 == 0 &&
+                      (uintptr_t)heads_a % 16 == 0 && (uintptr_t)heads_b % 16 == 0 && (uintptr_t)out % 4 == 0;
+    const int per_block = wide ? 1024 : 256;
+    dim3 grid((unsigned)((H * W + per_block - 1) / per_block), (unsigned)N);
+    if (head_planes == 6)
+        launch_photo_paste_mask<6>(wide, grid, (hipStream_t)stream, parsing, palm, rule, heads_a, heads_b, out, H, W, Ht, c0);
+    else if (head_planes == 1)
+        launch_photo_paste_mask<1>(wide, grid, (hipStream_t)stream, parsing, palm, rule, heads_a, heads_b, out, H, W, Ht, c0);
+    else
+        launch_photo_paste_mask<0>(wide, grid, (hipStream_t)stream, parsing, palm, rule, heads_a, heads_b, out, H, W, Ht, c0);
+    return launch_status("photo_paste_mask_u8");
 }

@@ -11,7 +11,9 @@ the host in four loader processes, as a few launches per batch:
     pasta_tryon_outfit_assemble       the seven fp32 tensors G takes (its outputs 2..8)
 
 and, after the generator, ``images_to_u8`` (pasta_images_to_u8: the bytes test.py writes) or, with --kept-parts photo,
-``images_keep_to_u8`` (pasta_images_keep_to_u8: those bytes with the photograph's kept parts pasted in, one launch).
+``images_keep_to_u8`` (pasta_images_keep_to_u8: those bytes with the photograph's kept parts pasted in, one launch) over the
+region of ``photo_paste_mask`` (pasta_photo_paste_mask_u8: the kept parts, and with --background / --kept-garments photo the
+background and the person's own garments where the generator's region heads agree; ``paste_rules`` fills its table).
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
@@ -170,4 +172,98 @@ def images_keep_to_u8(images, c0, width, photo, keep, radius):
     with torch.cuda.device(images.device):
         _native.check(_native.lib().pasta_images_keep_to_u8(_native.ptr(images), _native.ptr(photo), _native.ptr(keep), _native.ptr(out), n, h,
                                                             wt, c0, width, radius, _native.stream()))
+    return out
+
+
+# ---- where the photograph may be pasted: kept parts, background, the person's own garments ----
+
+# The label sets of pasta_tryon_outfit_masks_u8 (csrc/tryon_pairs.hip's tryon_pair_masks_kernel): the upper garment, the lower
+# garment, and label 6, which belongs to the lower garment as well where a size's SIX_IS_LOWER says so.  paste_rules takes them
+# from here, the one statement on the host.
+UPPER_LABELS = (5, 6, 7)
+LOWER_LABELS = (9, 12)
+SHARED_LABEL = 6
+# the bits of a rule row, by the generator's statement (include/pasta_hip.h, pasta_photo_paste_mask_u8)
+STATE_OTHER, STATE_UPPER, STATE_LOWER, STATE_SKIN = 0, 1, 2, 3
+PASTE_SIZES = (256, 512)    # the heights of the two try-on models: 256 x 192 and 512 x 320
+
+
+def garment_labels(size):
+    """(upper labels, lower labels) of the masks entry as the builder of ``size`` (256 or 512, the height) calls it."""
+    if size == 256:
+        six_is_lower = SIX_IS_LOWER
+    elif size == 512:
+        from training.tryon_regions import SIX_IS_LOWER as six_is_lower
+    else:
+        raise ValueError('paste_rules: size %r (one of %s)' % (size, ', '.join(map(str, PASTE_SIZES))))
+    return UPPER_LABELS, LOWER_LABELS + ((SHARED_LABEL,) if six_is_lower else ())
+
+
+def paste_rules(kept_parts, background, kept_garments, person_idx, upper_idx, lower_idx, size):
+    """The rule table of ``photo_paste_mask``: uint8 [N, 256] on the host, row n for item n of a batch of ``collate_outfits``
+    (``person_idx`` / ``upper_idx`` / ``lower_idx``: whose photograph, upper and lower garment).  Entry [n, L] is the set of the
+    generator's statements (bit 0 other, 1 upper, 2 lower, 3 skin) under which label L of the photograph may be pasted:
+    ``kept_parts``: every statement at metrics.tryon_fidelity.KEEP_LABELS; ``background``: 'other' at label 0;
+    ``kept_garments``: 'upper' at the upper labels of an item that wears its own upper garment, 'lower' at the lower labels of
+    one that wears its own lower garment (``garment_labels(size)``; a label in both sets gets both bits)."""
+    from metrics.tryon_fidelity import KEEP_LABELS
+    upper_labels, lower_labels = garment_labels(size)
+    person, upper, lower = (np.asarray(ix, np.int64).reshape(-1) for ix in (person_idx, upper_idx, lower_idx))
+    if not person.shape == upper.shape == lower.shape:
+        raise ValueError('paste_rules: %d people, %d upper and %d lower garments' % (len(person), len(upper), len(lower)))
+    rule = np.zeros([len(person), 256], np.uint8)
+    if kept_parts:
+        rule[:, list(KEEP_LABELS)] |= 0b1111
+    if background:
+        rule[:, 0] |= 1 << STATE_OTHER
+    if kept_garments:
+        for labels, owner, state in ((upper_labels, upper, STATE_UPPER), (lower_labels, lower, STATE_LOWER)):
+            own = np.flatnonzero(owner == person)
+            rule[np.ix_(own, list(labels))] |= 1 << state
+    return torch.from_numpy(rule)
+
+
+def photo_paste_mask(parsing, palm, rule, heads, c0):
+    """Where the photograph is pasted (include/pasta_hip.h, pasta_photo_paste_mask_u8; this project's own rule), one launch:
+    ``parsing`` uint8 [N, H, W], the person's labels; ``palm`` uint8 [N, H, Ht] or None; ``rule`` uint8 [N, 256]
+    (``paste_rules``); ``heads``: what the synthesis network returned after its images -- () for no statement, one tensor
+    [N, 6, Ht, Ht] (the parsing logits of GeneratorFull) or two [N, 1, Ht, Ht] (the sigmoid heads of GeneratorV18), cast to fp32
+    here (16-bit storage); ``c0`` = (Ht - W) // 2, the content's first column in the heads and the palm mask.
+    -> uint8 [N, H, W], 0 / 1.  Refuses with ValueError."""
+    heads = tuple(heads) if isinstance(heads, (tuple, list)) else (heads,)
+    named = [('parsing', parsing), ('rule', rule)] + ([('palm', palm)] if palm is not None else []) + [('heads[%d]' % i, h) for i, h in enumerate(heads)]
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+            raise ValueError('photo_paste_mask: %s is not a tensor on the GPU (there is no CPU path)' % name)
+    if parsing.dtype != torch.uint8 or rule.dtype != torch.uint8 or (palm is not None and palm.dtype != torch.uint8):
+        raise ValueError('photo_paste_mask: parsing, palm and rule uint8, not %s, %s, %s'
+                         % (parsing.dtype, None if palm is None else palm.dtype, rule.dtype))
+    if any(not h.dtype.is_floating_point for h in heads):
+        raise ValueError('photo_paste_mask: floating-point heads, not %s' % ', '.join(str(h.dtype) for h in heads))
+    if parsing.ndim != 3:
+        raise ValueError('photo_paste_mask: parsing [N, H, W], not %s' % (list(parsing.shape),))
+    n, h, w = (int(v) for v in parsing.shape)
+    c0 = int(c0)
+    if len(heads) not in (0, 1, 2) or any(x.ndim != 4 or int(x.shape[1]) != (6, 1)[len(heads) - 1] for x in heads):
+        raise ValueError('photo_paste_mask: heads are none, one tensor of 6 planes or two of 1 plane, not %s' % ([list(x.shape) for x in heads],))
+    ht = int(palm.shape[2]) if palm is not None and palm.ndim == 3 else int(heads[0].shape[3]) if heads else w + 2 * c0
+    if c0 < 0 or ht < w or c0 != (ht - w) // 2:
+        raise ValueError('photo_paste_mask: c0 %d for a width of %d in %d columns (their centred position)' % (c0, w, ht))
+    if tuple(rule.shape) != (n, 256):
+        raise ValueError('photo_paste_mask: rule %s for %d items (one row of 256 per item)' % (list(rule.shape), n))
+    if palm is not None and tuple(palm.shape) != (n, h, ht):
+        raise ValueError('photo_paste_mask: palm %s for parsing %s (the rows padded to %d)' % (list(palm.shape), list(parsing.shape), ht))
+    if h > ht or any(tuple(x.shape) != (n, x.shape[1], ht, ht) for x in heads):
+        raise ValueError('photo_paste_mask: heads %s for parsing %s in a square of %d' % ([list(x.shape) for x in heads], list(parsing.shape), ht))
+    if any(t.device != parsing.device for _, t in named):
+        raise ValueError('photo_paste_mask: tensors on different devices')
+    parsing, rule = parsing.contiguous(), rule.contiguous()
+    palm = None if palm is None else palm.contiguous()
+    heads = [x.to(torch.float32).contiguous() for x in heads]
+    a, b = (heads + [None, None])[:2]
+    out = torch.empty([n, h, w], dtype=torch.uint8, device=parsing.device)
+    with torch.cuda.device(parsing.device):
+        _native.check(_native.lib().pasta_photo_paste_mask_u8(_native.ptr(parsing), _native.ptr(palm), _native.ptr(rule), _native.ptr(a),
+                                                              _native.ptr(b), (0, 6, 1)[len(heads)], _native.ptr(out), n, h, w, ht,
+                                                              _native.stream()))
     return out

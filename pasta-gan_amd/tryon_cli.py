@@ -32,8 +32,8 @@ def _local_snapshot(path):
 
 
 def shared_options(dataroot_help, batchsize):
-    """The decorator of the options both command lines take up to --storage, --png-encoder and the two --kept options, in the
-    order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
+    """The decorator of the options both command lines take up to --storage, --png-encoder, the two --kept options, --background
+    and --kept-garments, in the order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
     options = [
         click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True),
         click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)'),
@@ -45,7 +45,7 @@ def shared_options(dataroot_help, batchsize):
         click.option('--outdir', help='Where to save the output images', type=str, required=True, metavar='DIR'),
         click.option('--dataroot', help=dataroot_help, type=str, required=True),
         click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=batchsize, show_default=True),
-        storage_option, png_encoder_option, kept_parts_option, kept_feather_option]
+        storage_option, png_encoder_option, kept_parts_option, kept_feather_option, background_option, kept_garments_option]
 
     def decorate(f):
         for option in reversed(options):
@@ -88,7 +88,7 @@ def _chosen_encoder(png_encoder):
 # --kept-parts photo: the photograph's head, palms and shoes (metrics.tryon_fidelity.keep_mask, the region `retain` carries) are
 # pasted into the generated picture where its bytes are made (training.tryon_pairs.images_keep_to_u8), feathered over
 # --kept-feather pixels.  Both options come with ``shared_options`` and, like --png-encoder, hand the commands' callbacks no
-# argument (test.py and test_512.py are untouched): their values are recorded in the click context, where ``_kept_radius`` finds
+# argument (test.py and test_512.py are untouched): their values are recorded in the click context, where ``_paste_plan`` finds
 # them when the keywords ``kept_parts`` / ``kept_feather`` of ``generate_256`` / ``generate_512`` are left at their defaults.
 _KEPT_PARTS_KEY, _KEPT_FEATHER_KEY = 'pasta.kept_parts', 'pasta.kept_feather'
 KEPT_PARTS = ('generated', 'photo')
@@ -106,30 +106,55 @@ def _record(key):
 kept_parts_option = click.option('--kept-parts', help='Where the written head, palms and shoes come from: the generator, or the person\'s '
                                  'photograph, pasted in on the GPU', type=click.Choice(list(KEPT_PARTS)), default='generated', show_default=True,
                                  expose_value=False, callback=_record(_KEPT_PARTS_KEY))
-kept_feather_option = click.option('--kept-feather', help='With --kept-parts photo: the paste fades over R pixels inside the kept region, '
-                                   '0 for a hard edge [default: %d]' % KEPT_FEATHER_DEFAULT, type=click.IntRange(0, KEPT_FEATHER_MAX),
-                                   metavar='R', expose_value=False, callback=_record(_KEPT_FEATHER_KEY))
+kept_feather_option = click.option('--kept-feather', help='With --kept-parts, --background or --kept-garments photo: the paste fades over R '
+                                   'pixels inside the pasted region, 0 for a hard edge [default: %d]' % KEPT_FEATHER_DEFAULT,
+                                   type=click.IntRange(0, KEPT_FEATHER_MAX), metavar='R', expose_value=False, callback=_record(_KEPT_FEATHER_KEY))
+
+# --background photo and --kept-garments photo widen the pasted region: the photograph's background, and the garment(s)
+# of the person's own that an item's outfit keeps, each only where the generator's own region heads agree with the photograph's
+# label map (training.tryon_pairs.photo_paste_mask).  Recorded in the click context as the --kept options are; the keywords are
+# ``background`` / ``kept_garments`` of ``generate_256`` / ``generate_512``.
+_BACKGROUND_KEY, _KEPT_GARMENTS_KEY = 'pasta.background', 'pasta.kept_garments'
+PASTE_OPTIONS = ('kept_parts', 'background', 'kept_garments')      # by keyword; the options are --kept-parts, --background, --kept-garments
+background_option = click.option('--background', help='Where the written background comes from: the generator, or the person\'s photograph '
+                                 'where the generator claims neither garment nor skin, pasted in on the GPU', type=click.Choice(list(KEPT_PARTS)),
+                                 default='generated', show_default=True, expose_value=False, callback=_record(_BACKGROUND_KEY))
+kept_garments_option = click.option('--kept-garments', help='Where a garment the outfit does not change comes from: the generator, or the '
+                                    'person\'s photograph where the generator puts that garment, pasted in on the GPU',
+                                    type=click.Choice(list(KEPT_PARTS)), default='generated', show_default=True, expose_value=False,
+                                    callback=_record(_KEPT_GARMENTS_KEY))
 
 
-def _kept_radius(kept_parts, kept_feather):
-    """The feather radius of a run with --kept-parts photo, None for a run that writes the generator's own pixels.  A feather
-    without the paste is a usage error; the two generate functions raise it before anything is read.  Keywords left at their
-    defaults ('generated', None) under a running command line are what that command line's options said; a call without a click
-    context has only the keywords."""
+def _paste_plan(kept_parts, kept_feather, background='generated', kept_garments='generated'):
+    """(feather radius, the PASTE_OPTIONS that are 'photo') of a run; (None, ()) for a run that writes the generator's own
+    pixels.  A feather without any paste is a usage error; the two generate functions raise it before anything is read.  Keywords
+    all left at their defaults ('generated', None) under a running command line are what that command line's options said; a call
+    without a click context has only the keywords."""
     context = click.get_current_context(silent=True)
-    if context is not None and kept_parts == 'generated' and kept_feather is None:
+    if context is not None and kept_parts == background == kept_garments == 'generated' and kept_feather is None:
         kept_parts = context.meta.get(_KEPT_PARTS_KEY, kept_parts)
         kept_feather = context.meta.get(_KEPT_FEATHER_KEY, kept_feather)
-    if kept_parts not in KEPT_PARTS:
-        raise click.BadParameter('%r is not one of %s' % (kept_parts, ', '.join(KEPT_PARTS)), param_hint='--kept-parts')
+        background = context.meta.get(_BACKGROUND_KEY, background)
+        kept_garments = context.meta.get(_KEPT_GARMENTS_KEY, kept_garments)
+    chosen = dict(kept_parts=kept_parts, background=background, kept_garments=kept_garments)
+    for name, value in chosen.items():
+        if value not in KEPT_PARTS:
+            raise click.BadParameter('%r is not one of %s' % (value, ', '.join(KEPT_PARTS)), param_hint='--' + name.replace('_', '-'))
     if kept_feather is not None and (isinstance(kept_feather, bool) or not isinstance(kept_feather, int)
                                      or not 0 <= kept_feather <= KEPT_FEATHER_MAX):
         raise click.BadParameter('%r is not an integer 0..%d' % (kept_feather, KEPT_FEATHER_MAX), param_hint='--kept-feather')
-    if kept_parts != 'photo':
+    pasted = tuple(name for name in PASTE_OPTIONS if chosen[name] == 'photo')
+    if not pasted:
         if kept_feather is not None:
-            raise click.UsageError('--kept-feather needs --kept-parts photo: without it nothing is pasted')
-        return None
-    return KEPT_FEATHER_DEFAULT if kept_feather is None else kept_feather
+            raise click.UsageError('--kept-feather needs --kept-parts photo, --background photo or --kept-garments photo: '
+                                   'without one of them nothing is pasted')
+        return None, ()
+    return (KEPT_FEATHER_DEFAULT if kept_feather is None else kept_feather), pasted
+
+
+def _kept_radius(kept_parts, kept_feather, background='generated', kept_garments='generated'):
+    """The feather radius of a run that pastes from the photograph, None for one that does not (``_paste_plan``)."""
+    return _paste_plan(kept_parts, kept_feather, background, kept_garments)[0]
 
 
 scores_option = click.option(
@@ -190,9 +215,10 @@ def pair_loader(dataset, batchsize, workers, collate_fn):
                                        collate_fn=collate_fn)
 
 
-def generate(G, t, gen_z, truncation_psi, noise_mode):
-    """The reference's call sequence (test.py:119-128, test_512.py:134-142) on a batch's tensors ``t``: the generated images.
-    ``synthesis`` returns them second, of four values (GeneratorV18) or of three (the 512 x 320 GeneratorFull)."""
+def generate_outputs(G, t, gen_z, truncation_psi, noise_mode):
+    """The reference's call sequence (test.py:119-128, test_512.py:134-142) on a batch's tensors ``t``: everything ``synthesis``
+    returns.  The generated images are second, of four values (GeneratorV18: then the two sigmoid garment heads) or of three
+    (the 512 x 320 GeneratorFull: then the six parsing logits)."""
     import torch
     with torch.no_grad():
         style_input, retain, pose = t['style_input'], t['retain'], t['pose']
@@ -204,13 +230,19 @@ def generate(G, t, gen_z, truncation_psi, noise_mode):
         ws = G.mapping(gen_z, gen_c, truncation_psi=truncation_psi)
         cat_feats = {str(feat.shape[2]): feat for feat in cat_feat_list}
         return G.synthesis(ws, pose_feat, cat_feats, t['denorm_upper_input'], t['denorm_lower_input'], t['denorm_upper_mask'],
-                           t['denorm_lower_mask'], noise_mode=noise_mode)[1]
+                           t['denorm_lower_mask'], noise_mode=noise_mode)
 
 
-def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None, kept_radius=None):
+def generate(G, t, gen_z, truncation_psi, noise_mode):
+    """The generated images of ``generate_outputs``: same launches, same value."""
+    return generate_outputs(G, t, gen_z, truncation_psi, noise_mode)[1]
+
+
+def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None, kept_radius=None,
+                 pasted=('kept_parts',)):
     """--scores: the figures of ``metrics.tryon_fidelity.finish`` (prefix ``tryon``) and what the run was, as one JSON line,
     printed and written to ``scores_file``.  ``mode``: what was dressed, when it was not the plain pair lists; ``kept_radius``:
-    the feather of a run with --kept-parts photo, whose report says so."""
+    the feather of a run that pastes from the photograph, whose report says so and names each of ``pasted`` (PASTE_OPTIONS)."""
     import json
     from metrics import tryon_fidelity
     report = dict(results=tryon_fidelity.finish(partials, 'tryon', pixels=pixels), pairs=pairs, network=network_pkl, dataroot=dataroot,
@@ -220,7 +252,8 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
     if mode is not None:
         report['mode'] = mode
     if kept_radius is not None:
-        report['kept_parts'], report['kept_feather'] = 'photo', kept_radius
+        report.update([(name, 'photo') for name in pasted if name == 'kept_parts'], kept_feather=kept_radius)
+        report.update((name, 'photo') for name in pasted if name != 'kept_parts')
     line = json.dumps(report)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
@@ -229,14 +262,17 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
 
 
 def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None,
-          kept_radius=None, png_encoder='pil'):
+          kept_radius=None, pasted=('kept_parts',), png_encoder='pil'):
     """The loop of both command lines.  ``choose(device)`` -> (data set, collate function, builder, ``pictures``), called once the
     snapshot is loaded; ``pictures(batch, raw, gen_imgs, count, content)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names
     under ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
     item i is ``pair_z(i)`` and the region scores of metrics/tryon_fidelity.py over what is written go to FILE (``write_scores``).
-    ``kept_radius`` (``_kept_radius``; None: the generator's own pixels, and ``content`` is None): the batches keep their stages,
-    and ``content``, uint8 [N, H, W, 3], is the generated picture's content columns with the photograph's kept parts
-    (``tryon_fidelity.keep_mask``) pasted in by ``images_keep_to_u8``; the scores are then those of these bytes, handed to
+    ``kept_radius`` (``_paste_plan``; None: the generator's own pixels, and ``content`` is None): the batches keep their stages,
+    and ``content``, uint8 [N, H, W, 3], is the generated picture's content columns with the photograph pasted in by
+    ``images_keep_to_u8`` over the region of ``pasted`` (PASTE_OPTIONS: the kept parts, the background, the person's own
+    garments), which ``photo_paste_mask`` forms once per batch from the builder's stages, ``paste_rules`` and, for the last two,
+    the generator's own region heads; with the kept parts alone it is ``tryon_fidelity.keep_mask``.  The scores are
+    then those of these bytes, handed to
     ``score_batch`` as the centres (b + 0.5) / 127.5 - 1 of the bytes' intervals, which ``unit_to_u8`` returns to b.
     ``png_encoder``: 'pil' copies the batch to the host and saves image by image; 'gpu' encodes the batch where it is
     (torch_utils.ops.png_encode.save) and copies back the compressed bytes.  Names, layout and scores are settled before either."""
@@ -250,7 +286,7 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
 
     from metrics import tryon_fidelity
     from torch_utils.ops import png_encode
-    from training.tryon_pairs import images_keep_to_u8
+    from training.tryon_pairs import images_keep_to_u8, paste_rules, photo_paste_mask
 
     device = torch.device('cuda')
     G = load_generator(network_pkl, device, storage)
@@ -267,12 +303,16 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
         if scoring:
             index = raw['raw_idx'].tolist()                         # the items' positions in the pair lists, or in the outfit list
             gen_z = tryon_fidelity.pair_z(index, G.z_dim, device)
-        gen_imgs = generate(G, batch.tensors, gen_z, truncation_psi, noise_mode)
+        _, gen_imgs, *heads = generate_outputs(G, batch.tensors, gen_z, truncation_psi, noise_mode)
         content, scored = None, gen_imgs
         if kept_radius is not None:
             photo = batch.stages['image']
             c0, width = (photo.shape[1] - photo.shape[2]) // 2, photo.shape[2]
-            content = images_keep_to_u8(gen_imgs, c0, width, photo, tryon_fidelity.keep_mask(batch.stages), kept_radius)
+            rule = paste_rules('kept_parts' in pasted, 'background' in pasted, 'kept_garments' in pasted, raw['person_idx'], raw['upper_idx'],
+                               raw['lower_idx'], int(photo.shape[1])).to(device)
+            region = photo_paste_mask(batch.stages['parsing'], batch.stages['palm'] if 'kept_parts' in pasted else None, rule,
+                                      heads if pasted != ('kept_parts',) else (), c0)       # the kept parts need no statement
+            content = images_keep_to_u8(gen_imgs, c0, width, photo, region, kept_radius)
             if scoring:
                 scored = gen_imgs.to(torch.float32).clone()
                 scored[:, :, :, c0:c0 + width] = ((content.to(torch.float32) + 0.5) / 127.5 - 1).permute(0, 3, 1, 2)
@@ -290,11 +330,12 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
             count += 1
     print('finish: %d images under %s' % (count, outdir))
     if scoring:
-        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius)
+        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius, pasted)
 
 
 def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
-                 scores_file=None, storage=None, kept_parts='generated', kept_feather=None, png_encoder='pil'):
+                 scores_file=None, storage=None, kept_parts='generated', kept_feather=None, background='generated',
+                 kept_garments='generated', png_encoder='pil'):
     """test_512.py: the 512 x 320 model on outfits, prepared by training.tryon_regions.TryOnOutfitBatchBuilder and written to
     ``<outdir>/<count>.png`` in list order.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_512_test), written as ``upper donor | lower donor | person | generated`` (512 x 2048).
@@ -302,11 +343,12 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     writes them, ``clothes | person | generated`` with the DONOR as ``clothes``, who for 'lowerbody' owns the lower garment.
     A ``change_region`` other than None is refused together with --outfits, since a line names whose garments are worn, and that
     is refused before anything is read.  ``kept_parts`` 'photo' with ``kept_feather`` (None: 2): the ``generated`` panel's content
-    columns carry the photograph's kept parts (``dress``), the other panels and the panel's padding are untouched; a feather
-    without it is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
+    columns carry the photograph's kept parts (``dress``), the other panels and the panel's padding are untouched; ``background``
+    / ``kept_garments`` 'photo' widen the pasted region to the photograph's background and to the garment(s) of the person's own
+    that an item keeps; a feather with none of the three is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
-    kept_radius = _kept_radius(kept_parts, kept_feather)
+    kept_radius, pasted = _paste_plan(kept_parts, kept_feather, background, kept_garments)
 
     def choose(device):
         import torch
@@ -332,11 +374,12 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             return images, [str(count + i).zfill(3) + '.png' for i in range(batch.batch)]
         return dataset, collate_fn, TryOnOutfitBatchBuilder(device), pictures
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage,
-          kept_radius=kept_radius, png_encoder=_chosen_encoder(png_encoder))
+          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder))
 
 
 def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
-                 scores_file=None, storage=None, kept_parts='generated', kept_feather=None, png_encoder='pil'):
+                 scores_file=None, storage=None, kept_parts='generated', kept_feather=None, background='generated',
+                 kept_garments='generated', png_encoder='pil'):
     """test.py: the 256 x 192 model on outfits, prepared by training.tryon_pairs.TryOnPairOutfitBatchBuilder; only the generated
     image is written, columns 32..223 of the generator's square.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
@@ -344,11 +387,12 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     (P, -, D) or (P, D, D) of ``change_region`` (None: upper body, the reference's run), written to ``<person stem>__<clothes
     stem>.png``.  The two exclude each other, and that is refused before anything is read.  The --scores report's ``mode`` is
     ``outfits`` or ``change-region <region>``; a run with neither option has none.  ``kept_parts`` 'photo' with ``kept_feather``
-    (None: 2): the written image carries the photograph's kept parts (``dress``); a feather without it is refused like the two
-    modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
+    (None: 2): the written image carries the photograph's kept parts (``dress``); ``background`` / ``kept_garments`` 'photo' widen
+    the pasted region to the photograph's background and to the garment(s) of the person's own that an item keeps; a
+    feather with none of the three is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
-    kept_radius = _kept_radius(kept_parts, kept_feather)
+    kept_radius, pasted = _paste_plan(kept_parts, kept_feather, background, kept_garments)
 
     def choose(device):
         from training import dataset as custom_dataset
@@ -369,4 +413,4 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
         return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device), pictures
     mode = 'outfits' if outfits_file is not None else change_region and 'change-region ' + change_region
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode,
-          kept_radius=kept_radius, png_encoder=_chosen_encoder(png_encoder))
+          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder))
