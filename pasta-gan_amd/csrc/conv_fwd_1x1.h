@@ -1,7 +1,7 @@
 // Pointwise (1x1, stride 1) convolutions of the three-product fp16 arithmetic, optionally over the channel concatenation of TWO
 // tensors that is never formed.  Instantiated by conv_tu_fwd_small.hip (conv_launch.h).
 #pragma once
-#include "conv_fwd_bf16x6.h"
+#include "conv_fwd_mma.h"
 
 namespace pasta {
 
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(ConvFwdParams p) 
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 float v0 = xv[2 * k][px], v1 = xv[2 * k + 1][px];
-                if (xvalid < 8) { v0 = 2 * k < xvalid ? v0 : 0.f; v1 = 2 * k + 1 < xvalid ? v1 : 0.f; }
+                fwd_mask2(v0, v1, k, xvalid);
                 f16_split2(v0 * sx, v1 * sx, h[k], l[k]);
             }
             __bf16* const d = &Bs[(wave * BN + lane * PX + px) * 8];
@@ -130,22 +130,16 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(ConvFwdParams p) 
         load_a(rn);
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) {
-            bf16x8 fa[WMT][3], fb[WNT][2];
+            FwdFrag<WMT, WNT> f;            // read piece by piece (this kernel hides the LDS latency by occupancy, not by the read order)
 #pragma unroll
             for (int pc = 0; pc < 3; pc++)
 #pragma unroll
-                for (int a = 0; a < WMT; a++) fa[a][pc] = *(const bf16x8*)&As[((pc * NOCT + ks * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8];
+                for (int a = 0; a < WMT; a++) f.a[a][pc] = *(const bf16x8*)&As[((pc * NOCT + ks * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8];
 #pragma unroll
             for (int pc = 0; pc < 2; pc++)
 #pragma unroll
-                for (int b = 0; b < WNT; b++) fb[b][pc] = *(const bf16x8*)&Bs[((pc * NOCT + ks * 2 + hl) * BN + (wn * WNT + b) * 32 + jl) * 8];
-#define PASTA_MM1(PA, PB)                                                                                          \
-            _Pragma("unroll") for (int a = 0; a < WMT; a++) _Pragma("unroll") for (int b = 0; b < WNT; b++)          \
-                acc[a][b] = mfma16<IO_F32, NP>(fa[a][PA], fb[b][PB], acc[a][b]);
-            PASTA_MM1(2, 1)     // h'' l', l h, h h: smallest terms first
-            PASTA_MM1(1, 0)
-            PASTA_MM1(0, 0)
-#undef PASTA_MM1
+                for (int b = 0; b < WNT; b++) f.b[b][pc] = *(const bf16x8*)&Bs[((pc * NOCT + ks * 2 + hl) * BN + (wn * WNT + b) * 32 + jl) * 8];
+            fwd_products<NP, IO_F32>(f, acc, FwdNoSlot{}, FwdNoStores{});       // the staging of this kernel runs between the rounds
         }
         __syncthreads();
     }

@@ -1,6 +1,6 @@
-// Split-bf16 forward-type kernels (v_mfma_f32_32x32x16_bf16, fp32-equivalent products): weight packing, conv_fwd_bf16x6_kernel, conv_fwd_rows_bf16x6_kernel and their launchers.  Instantiated by conv_tu_pack_f32.hip (packing), conv_tu_fwd_base_*.hip, conv_tu_fwd_rows_*.hip.
+// Split-bf16 forward-type kernels (v_mfma_f32_32x32x16_bf16, fp32-equivalent products): conv_fwd_bf16x6_kernel, conv_fwd_rows_bf16x6_kernel and their launchers.  Instantiated by conv_tu_fwd_base_*.hip, conv_tu_fwd_rows_*.hip.  (The weight packing: conv_pack.h.)
 #pragma once
-#include "conv_common.h"
+#include "conv_fwd_mma.h"
 
 namespace pasta {
 
@@ -15,178 +15,34 @@ namespace pasta {
 // Tile 128 x 128, K chunks of 16 channels of one tap; weights are split once by the packing kernel, activations by
 // the staging code (after the optional modulation scale).  Layouts in LDS (per piece and per k-half of 8):
 // [piece][half][row or pixel][8 bf16] so that a fragment is one conflict-free 16-byte read.
+// The operand split, the fragment read order and the product schedule of a chunk: conv_fwd_mma.h.
 
-
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-    a = (__bf16)v;
-    float r = v - (float)a;
-    b = (__bf16)r;
-    r -= (float)b;
-    c = (__bf16)r;
-}
-
-#ifdef PASTA_TU_PACK       // the packing kernels are defined by conv_tu_pack_f32.hip only (conv_launch.h)
-// [g][tap][chunk of 16 channels][piece 3][half 2][O_pad][8]
-__global__ __launch_bounds__(256) void pack_weights_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ wp, int G, int Ig,
-                                                                int Og, int Ig_pad, int Og_pad, int kh, int kw, int transposed,
-                                                                int flip, float wscale, int f16, const float* __restrict__ mod_s,
-                                                                const float* __restrict__ mod_d) {
-    // f16: 0 = three bf16 pieces, 1 = fp16 storage (leading piece = the fp16 operand).  PASTA_MATH_F16X3: pack_weights_f16x3_kernel
-    const int64_t total = (int64_t)G * kh * kw * Ig_pad * Og_pad;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-        const int j = (int)(idx & 7);
-        int64_t r = idx >> 3;
-        const int o = (int)(r % Og_pad); r /= Og_pad;
-        const int half = (int)(r & 1); r >>= 1;
-        const int cc = (int)(r % (Ig_pad / 16)); r /= (Ig_pad / 16);
-        const int t = (int)(r % (kh * kw));
-        const int g = (int)(r / (kh * kw));
-        const int i = cc * 16 + half * 8 + j;
-        float v = 0.f;
-        if (i < Ig && o < Og) {
-            int ty = t / kw, tx = t - ty * kw;
-            if (flip) { ty = kh - 1 - ty; tx = kw - 1 - tx; }
-            // mod_s: ONE weight of a single group, shared by all groups, modulated per group (= sample) on the way:
-            // w[o,i] * s[g,i] (* d[g,o]) rounded in this order, as networks.py:65-68, 84-86 forms its per-sample weights
-            const int gs = mod_s ? 0 : g;
-            const int64_t src = transposed ? (((int64_t)(gs * Ig + i) * Og + o) * kh + ty) * kw + tx
-                                           : (((int64_t)(gs * Og + o) * Ig + i) * kh + ty) * kw + tx;
-            v = w[src] * wscale;
-            if (mod_s) { v *= mod_s[(int64_t)g * Ig + i]; if (mod_d) v *= mod_d[(int64_t)g * Og + o]; }
+// The store loop of the base and the row-reuse kernel: this lane's pixel of every column block b of the wave -> (n, p, q) of the lattice ->
+// plane offset -> conv_epi_column -> conv_store_subtile per sub-tile, instantiated per epilogue case (conv_epilogue_dispatch).
+// The tile: output rows from o_blk, BM of them, lattice pixels from pix_blk; the wave (wm, wn) owns WMT x WNT sub-tiles of it.  GUARD: the grid
+// covers pixels beyond npix (the base kernel; the row kernel's tiles are full).  RES_ROWTEST: conv_store_subtile.
+template <int IO, bool SPEC, bool GUARD, bool RES_ROWTEST, int BM, int WMT, int WNT>
+__device__ __forceinline__ void fwd_store_lattice(const ConvFwdParams& p, f32x16 (&acc)[WMT][WNT], const ConvFwdParams::Lattice& lat, int64_t pix_blk, int64_t npix,
+                                                  int g, int ks, int o_blk, int wm, int wn, int lane, uint32_t& y_am) {
+    const int P = lat.P, Q = lat.Q, jl = lane & 31;
+    const float nstr = (p.noise && p.ksplit == 1) ? p.noise_strength[0] : 0.f;
+    const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, p.ksplit == 1);
+    conv_epilogue_dispatch<SPEC>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
+#pragma unroll
+        for (int b = 0; b < WNT; b++) {
+            const int64_t pix = pix_blk + (wn * WNT + b) * 32 + jl;
+            if (GUARD && pix >= npix) continue;
+            const int n = (int)(pix / (P * Q));
+            const int rem = (int)(pix - (int64_t)n * P * Q);
+            const int pp = rem / Q, qq = rem - pp * Q;
+            const int plane_off = (lat.oy0 + pp * p.osy) * p.OW + lat.ox0 + qq * p.osx;
+            const EpiColumn col = conv_epi_column(p, ea, g, ks, n, plane_off, nstr);
+#pragma unroll
+            for (int a = 0; a < WMT; a++)
+                conv_store_subtile<IO, RES_ROWTEST>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
         }
-        __bf16 p1, p2, p3;
-        split3(v, p1, p2, p3);
-        if (f16 == 1) p1 = __builtin_bit_cast(__bf16, (_Float16)v);      // fp16 storage: the leading piece is the fp16 operand (the others are unused)
-        const int64_t chunk = (((int64_t)g * kh * kw + t) * (Ig_pad / 16) + cc) * 6 * Og_pad * 8;
-        const int64_t within = ((int64_t)half * Og_pad + o) * 8 + j;
-        wp[chunk + within] = p1;
-        wp[chunk + 2 * Og_pad * 8 + within] = p2;
-        wp[chunk + 4 * Og_pad * 8 + within] = p3;
-    }
+    });
 }
-
-// PASTA_MATH_F16X3 (conv_common.h): the same layout with the fp16 pieces h = fp16(v S), l = fp16(v S - h), h'' = h 2^-11 and the power-of-two scale S taken
-// PER OUTPUT ROW from the row's own largest magnitude, found here: one workgroup owns one row o of one group over the whole K
-// range (C_in kh kw values: at most a few thousand), first pass = fetch the row (every load of a thread in flight at once), form
-// v = w wscale (s[g,i] d[g,o]), keep it in LDS and reduce |v| over the workgroup (non-finite values skipped, as the tensor scan
-// does); second pass = split and store sixteen-byte units out of LDS, plus rowinv[g][o] = 1 / S for the convolution's epilogue.
-// Hundreds of short workgroups: 5 - 8 us per layer like the element-parallel kernel it replaces (a first version with eight rows
-// per workgroup and serial loads took 50 - 100 us: 341 launches per training step).  Nothing about w is cached between launches: a
-// weight written behind autograd's back (`p.data.mul_()`, an optimiser that works on `.data`) cannot meet a stale scale, and
-// per-sample modulated weights (pasta_conv2d_modulated) get their own scale per (sample, output channel).
-constexpr int PACK_ROW_LDS = 8192;          // floats of a row kept in LDS; longer rows are re-read from global memory (L2)
-__device__ __forceinline__ void pack_row_f16x3(const float* __restrict__ w, __bf16* __restrict__ wp, float* __restrict__ rowinv,
-                                               int Ig, int Og, int Ig_pad, int Og_pad, int kh, int kw, int transposed, int flip,
-                                               float wscale, const float* __restrict__ mod_s, const float* __restrict__ mod_d, int pack_xcd_rows, const unsigned bx) {
-    // one packed row.  Eight consecutive rows share every 128-byte line of the packed layout ([...][O_pad][8 x 2 bytes]) and workgroups go round-robin
-    // to the eight XCDs: XCD x takes the rows [x O_pad / 8, (x + 1) O_pad / 8), so that the sixteen-byte stores of a line meet in ONE L2 and leave it
-    // as a whole line (O_pad is a multiple of 64)
-    const int g = blockIdx.y, o = pack_xcd_rows ? (int)(bx & 7u) * (Og_pad >> 3) + (int)(bx >> 3) : (int)bx;
-    const int taps = kh * kw, NC = Ig_pad / 16, K = Ig * taps;
-    const int tid = threadIdx.x;
-    const int gs = mod_s ? 0 : g;
-    __shared__ float row[PACK_ROW_LDS];                     // v[i * taps + t], t = the tap index of the WEIGHT tensor (before the flip)
-    __shared__ float wmax[4];
-    const bool real = o < Og;
-    const float md = (real && mod_d) ? mod_d[(int64_t)g * Og + o] : 1.f;
-    // element k = i * taps + t of the row, as it lies in the weight tensor: the taps of one input channel are contiguous in both layouts
-    auto tap_run = [&](int i) -> const float* {
-        return w + (transposed ? ((int64_t)(gs * Ig + i) * Og + o) * taps : ((int64_t)(gs * Og + o) * Ig + i) * taps);
-    };
-    auto fetch = [&](int k) -> float {                       // rows longer than PACK_ROW_LDS: the second pass re-reads the tail
-        const int i = k / taps, t = k - i * taps;
-        float v = tap_run(i)[t] * wscale;
-        if (mod_s) { v *= mod_s[(int64_t)g * Ig + i]; v *= md; }
-        return v;
-    };
-    float m = 0.f;
-    if (real) {
-        if (taps <= 9) {
-            // a thread owns input channels tid, tid + 256, ...: up to nine contiguous loads in flight, no division
-            for (int i = tid; i < Ig; i += 256) {
-                const float* const src = tap_run(i);
-                const float ms = mod_s ? mod_s[(int64_t)g * Ig + i] : 1.f;
-                float v[9];
-#pragma unroll
-                for (int t = 0; t < 9; t++) v[t] = t < taps ? src[t] : 0.f;
-#pragma unroll
-                for (int t = 0; t < 9; t++) {
-                    if (t < taps) {
-                        float x = v[t] * wscale;
-                        if (mod_s) { x *= ms; x *= md; }
-                        const int k = i * taps + t;
-                        if (k < PACK_ROW_LDS) row[k] = x;
-                        const float a = fabsf(x);
-                        m = (a < __builtin_inff() && a > m) ? a : m;
-                    }
-                }
-            }
-        } else {
-            for (int k0 = tid; k0 < K; k0 += 256 * 8) {          // eight loads in flight per thread and trip
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) { const int k = k0 + 256 * j; v[j] = k < K ? fetch(k) : 0.f; }
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int k = k0 + 256 * j;
-                    if (k < K && k < PACK_ROW_LDS) row[k] = v[j];
-                    const float a = fabsf(v[j]);
-                    m = (a < __builtin_inff() && a > m) ? a : m;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    if ((tid & 63) == 0) wmax[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    float S, inv;
-    scale_from_amax(m, S, inv);
-    if (tid == 0) rowinv[(int64_t)g * Og_pad + o] = inv;
-    // second pass: unit u = (t_packed NC + cc) 2 + half -> sixteen bytes of h and of l: channels cc 16 + half 8 + 0..7 of packed tap t_packed
-    const int units = taps * NC * 2;
-    for (int u = tid; u < units; u += 256) {
-        const int half = u & 1, k2 = u >> 1;
-        const int cc = k2 % NC, tp = k2 / NC;
-        int ty = tp / kw, tx = tp - ty * kw;
-        if (flip) { ty = kh - 1 - ty; tx = kw - 1 - tx; }
-        const int t = ty * kw + tx;
-        uint32_t hq[4], lq[4], sq[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = cc * 16 + half * 8 + 2 * j;
-            float v0 = 0.f, v1 = 0.f;
-            if (real) {
-                const int k = i * taps + t;
-                if (i < Ig) v0 = k < PACK_ROW_LDS ? row[k] : fetch(k);
-                if (i + 1 < Ig) v1 = k + taps < PACK_ROW_LDS ? row[k + taps] : fetch(k + taps);
-            }
-            f16_split2_direct(v0 * S, v1 * S, hq[j], lq[j]);
-            sq[j] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2_t, hq[j]) * f16x2_t{(_Float16)0.00048828125f, (_Float16)0.00048828125f});
-        }
-        __bf16* const d = wp + (((int64_t)g * taps + tp) * NC + cc) * 6 * Og_pad * 8 + ((int64_t)half * Og_pad + o) * 8;
-        *(uint4*)d = make_uint4(hq[0], hq[1], hq[2], hq[3]);
-        *(uint4*)(d + 2 * Og_pad * 8) = make_uint4(lq[0], lq[1], lq[2], lq[3]);
-        *(uint4*)(d + 4 * Og_pad * 8) = make_uint4(sq[0], sq[1], sq[2], sq[3]);
-    }
-}
-__global__ __launch_bounds__(256) void pack_weights_f16x3_kernel(const float* __restrict__ w, __bf16* __restrict__ wp, float* __restrict__ rowinv,
-                                                                 int Ig, int Og, int Ig_pad, int Og_pad, int kh, int kw, int transposed, int flip,
-                                                                 float wscale, const float* __restrict__ mod_s, const float* __restrict__ mod_d, int pack_xcd_rows) {
-    pack_row_f16x3(w, wp, rowinv, Ig, Og, Ig_pad, Og_pad, kh, kw, transposed, flip, wscale, mod_s, mod_d, pack_xcd_rows, blockIdx.x);
-}
-// Round 5: ONE weight tensor packed for TWO launches at once -- the forward convolution and its input gradient (the same weights transposed
-// and mirrored) -- so that the backward pass finds its operand packed (pasta_conv2d_pack_pair; 120 of the 310 packing launches of a step).
-// The first a.rows workgroups of the grid's x axis pack for a, the others for b.
-__global__ __launch_bounds__(256) void pack_weights_f16x3_pair_kernel(const float* __restrict__ w, PackJob a, PackJob b) {
-    const bool first = blockIdx.x < (unsigned)a.Og_pad;
-    const PackJob& j = first ? a : b;
-    pack_row_f16x3(w, (__bf16*)j.wp, j.rowinv, j.Ig, j.Og, j.Ig_pad, j.Og_pad, j.kh, j.kw, j.transposed, j.flip, j.wscale, nullptr, nullptr, j.pack_xcd_rows,
-                   first ? blockIdx.x : blockIdx.x - (unsigned)a.Og_pad);
-}
-#endif  // PASTA_TU_PACK
 
 // NP = bf16 pieces kept per operand: 3 = six products (fp32-equivalent, the default), 2 = three products (hi*hi, hi*mid,
 // mid*hi: ~2^-16 relative, PASTA_MATH_BF16X3), 1 = one product (plain bf16 operands, PASTA_MATH_BF16).  The packed
@@ -332,40 +188,11 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
         }
     };
     uint32_t q1[BPT][4], q2[BPT][4], q3[BPT][4];          // 8 bf16 per piece, packed two per dword
-    // Two elements at a time: v_cvt_pk_bf16_f32 yields the packed pair, the residuals come from its halves.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     auto split_pair = [&](const Stage& st, int i, int j) {
         float v0 = st.b[8 * i + 2 * j], v1 = st.b[8 * i + 2 * j + 1];
         if constexpr (ISC) { v0 *= st.sc[8 * i + 2 * j]; v1 *= st.sc[8 * i + 2 * j + 1]; }
-        if (st.nvalid[i] < 8) {                  // border pixel or channel tail
-            v0 = 2 * j < st.nvalid[i] ? v0 : 0.f;
-            v1 = 2 * j + 1 < st.nvalid[i] ? v1 : 0.f;
-        }
-        if constexpr (HX) {
-            f16_split2(v0 * x_scale, v1 * x_scale, q1[i][j], q2[i][j]);
-            return;
-        }
-        f32x2 v = {v0, v1};
-        uint32_t w = io_pack2<IO>(v0, v1);
-        q1[i][j] = w;
-        if constexpr (NP >= 2) {
-            // the two residual subtractions stay scalar: packed f32 VALU next to MFMAs costs more than it saves
-            // (MI355X_MICROARCH.md, cycle table), and the empty asm keeps the SLP vectoriser from pairing them
-            v0 -= __builtin_bit_cast(float, w << 16);
-            v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-            PASTA_KEEP_SCALAR(v0);
-            v = f32x2{v0, v1};
-            w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-            q2[i][j] = w;
-        }
-        if constexpr (NP >= 3) {
-            v0 -= __builtin_bit_cast(float, w << 16);
-            v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-            PASTA_KEEP_SCALAR(v0);
-            v = f32x2{v0, v1};
-            q3[i][j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-        }
+        fwd_mask2(v0, v1, j, st.nvalid[i]);
+        fwd_split2<NP, IO>(v0, v1, x_scale, q1[i][j], q2[i][j], q3[i][j]);
     };
     auto store_b = [&](int buf) {
 #pragma unroll
@@ -393,52 +220,20 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
     const int hl = lane >> 5, jl = lane & 31;
     uint32_t y_am = 0;
     const AmaxSlot y_slot = amax_begin(p.y_amax);      // the slot's present value arrives behind the K loop
-    // Fragments of one chunk: [tile][piece], read in the order the MFMA groups consume them.
-    struct Frag { bf16x8 a[WMT][3], b[WNT][3]; };
-    auto read_frag = [&](Frag& f, int buf) {
-#define PASTA_LDA(PC) if constexpr ((PC) < NPA) { _Pragma("unroll") for (int a = 0; a < WMT; a++) f.a[a][PC] = *(const bf16x8*)&As[buf][(((PC) * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8]; }
-#define PASTA_LDB(PC) if constexpr ((PC) < NPB) { _Pragma("unroll") for (int b = 0; b < WNT; b++) f.b[b][PC] = *(const bf16x8*)&Bs[buf][(((PC) * 2 + hl) * BN + (wn * WNT + b) * 32 + jl) * 8]; }
-        // in the order the product groups consume them, so that the first group starts when ITS operands have landed (the LDS
-        // returns reads in order: counted lgkmcnt waits): three-product arithmetic (h'' l'), (l h), (h h)
-        if constexpr (HX) { PASTA_LDA(2) PASTA_LDB(1) PASTA_LDA(1) PASTA_LDB(0) PASTA_LDA(0) }
-        else { PASTA_LDA(2) PASTA_LDB(0) PASTA_LDA(0) PASTA_LDB(2) PASTA_LDA(1) PASTA_LDB(1) }
-#undef PASTA_LDA
-#undef PASTA_LDB
-    };
     // One K chunk: 24 MFMAs in six groups of four; the staging work for the next chunk is slotted between the groups.
     auto step = [&](int buf, Stage& cur_next, Stage& fetch_into) {
         load_a();                   // weights of the next chunk first: they are waited for with the activation fetch still in flight
         load_chunk(fetch_into);
-        Frag f;
-        read_frag(f, buf);
-#define PASTA_MM(PA, PB)                                                                                       \
-        if constexpr (mm_on<NP>(PA, PB)) {                                                                       \
-        _Pragma("unroll") for (int a = 0; a < WMT; a++) _Pragma("unroll") for (int b = 0; b < WNT; b++)          \
-            acc[a][b] = mfma16<IO, NP>(f.a[a][PA], f.b[b][PB], acc[a][b]); }
-#define PASTA_SPLIT(J) _Pragma("unroll") for (int i = 0; i < BPT; i++) split_pair(cur_next, i, J);
-        // smallest terms first: a3b1, a1b3, a2b2, a2b1, a1b2, a1b1
-        if constexpr (HX) {
-            PASTA_MM(2, 1)
-            PASTA_SPLIT(0)
-            PASTA_SPLIT(1)
-            PASTA_MM(1, 0)
-            PASTA_SPLIT(2)
-            PASTA_SPLIT(3)
-        } else {
-        PASTA_MM(2, 0)
-        PASTA_SPLIT(0)
-        PASTA_MM(0, 2)
-        PASTA_SPLIT(1)
-        PASTA_MM(1, 1)
-        PASTA_SPLIT(2)
-        PASTA_MM(1, 0)
-        PASTA_SPLIT(3)
-        PASTA_MM(0, 1)
-        }
-        store_b(buf ^ 1); store_a(buf ^ 1);
-        PASTA_MM(0, 0)
-#undef PASTA_MM
-#undef PASTA_SPLIT
+        FwdFrag<WMT, WNT> f;
+        fwd_read_frag<NP>(f,
+            [&](int pc, int a) { return (const bf16x8*)&As[buf][((pc * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8]; },
+            [&](int pc, int b) { return (const bf16x8*)&Bs[buf][((pc * 2 + hl) * BN + (wn * WNT + b) * 32 + jl) * 8]; });
+        fwd_products<NP, IO>(f, acc,
+            [&](auto j) {
+#pragma unroll
+                for (int i = 0; i < BPT; i++) split_pair(cur_next, i, j);
+            },
+            [&]() { store_b(buf ^ 1); store_a(buf ^ 1); });
         __syncthreads();
     };
 
@@ -460,23 +255,7 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_bf16x6_kernel(ConvFwdParams
     if constexpr (HX) {
         conv_unscale_rows<WMT, WNT>(p.w_rowinv + (int64_t)g * p.Og_pad + o_blk, out_scale, wm, lane, acc);
     }
-    const float nstr = (p.noise && p.ksplit == 1) ? p.noise_strength[0] : 0.f;
-    const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, p.ksplit == 1);
-    conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32)>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
-#pragma unroll
-    for (int b = 0; b < WNT; b++) {
-        const int64_t pix = pix_blk + (wn * WNT + b) * 32 + jl;
-        if (pix >= npix) continue;
-        const int n = (int)(pix / (P * Q));
-        const int rem = (int)(pix - (int64_t)n * P * Q);
-        const int pp = rem / Q, qq = rem - pp * Q;
-        const int plane_off = (oy0 + pp * p.osy) * p.OW + ox0 + qq * p.osx;
-        const EpiColumn col = conv_epi_column(p, ea, g, ks, n, plane_off, nstr);
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-            conv_store_subtile<IO, EPI_RES_ROWTEST>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
-    }
-    });
+    fwd_store_lattice<IO, (NP == NP_F16X3 || IO != IO_F32), true, EPI_RES_ROWTEST, BM>(p, acc, p.cls[cls], pix_blk, npix, g, ks, o_blk, wm, wn, lane, y_am);
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
 }
 
@@ -689,39 +468,11 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
     };
 
     uint32_t q1[BPT][4], q2[BPT][4], q3[BPT][4];
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     auto split_pair = [&](const float* b, const int* nvalid, int i, int j, const float* sc = nullptr) {
         float v0 = b[8 * i + 2 * j], v1 = b[8 * i + 2 * j + 1];
         if constexpr (ISC) { v0 *= sc[8 * i + 2 * j]; v1 *= sc[8 * i + 2 * j + 1]; }
-        if (nvalid[i] < 8) {
-            v0 = 2 * j < nvalid[i] ? v0 : 0.f;
-            v1 = 2 * j + 1 < nvalid[i] ? v1 : 0.f;
-        }
-        if constexpr (HX) {
-            f16_split2(v0 * x_scale, v1 * x_scale, q1[i][j], q2[i][j]);
-            return;
-        }
-        f32x2 v = {v0, v1};
-        uint32_t w = io_pack2<IO>(v0, v1);
-        q1[i][j] = w;
-        if constexpr (NP >= 2) {
-            // the two residual subtractions stay scalar: packed f32 VALU next to MFMAs costs more than it saves
-            // (MI355X_MICROARCH.md, cycle table), and the empty asm keeps the SLP vectoriser from pairing them
-            v0 -= __builtin_bit_cast(float, w << 16);
-            v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-            PASTA_KEEP_SCALAR(v0);
-            v = f32x2{v0, v1};
-            w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-            q2[i][j] = w;
-        }
-        if constexpr (NP >= 3) {
-            v0 -= __builtin_bit_cast(float, w << 16);
-            v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-            PASTA_KEEP_SCALAR(v0);
-            v = f32x2{v0, v1};
-            q3[i][j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-        }
+        fwd_mask2(v0, v1, j, nvalid[i]);
+        fwd_split2<NP, IO>(v0, v1, x_scale, q1[i][j], q2[i][j], q3[i][j]);
     };
     auto store_q = [&](int buf, int slot, int hbase) {
 #pragma unroll
@@ -751,68 +502,47 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
         const int t = (wn * WNT + b) * 32 + jl;
         fslot[b] = t + 2 * (t >> seg_log2);
     }
-    struct Frag { bf16x8 a[WMT][3], b[WNT][3]; };
-    auto read_frag = [&](Frag& f, int abuf, int bbuf, int off) {
-        const __bf16* A_ = As + abuf * ABUF;
-        const __bf16* B_ = Bs + bbuf * BBUF;
-#define PASTA_LDA(PC) if constexpr ((PC) < NPA) { _Pragma("unroll") for (int a = 0; a < WMT; a++) f.a[a][PC] = *(const bf16x8*)&A_[(((PC) * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8]; }
-#define PASTA_LDB(PC) if constexpr ((PC) < NPB) { _Pragma("unroll") for (int b = 0; b < WNT; b++) f.b[b][PC] = *(const bf16x8*)&B_[(((PC) * 2 + hl) * SLOTS + fslot[b] + off) * 8]; }
-        // in the order the product groups consume them, so that the first group starts when ITS operands have landed (the LDS
-        // returns reads in order: counted lgkmcnt waits): three-product arithmetic (h'' l'), (l h), (h h)
-        if constexpr (HX) { PASTA_LDA(2) PASTA_LDB(1) PASTA_LDA(1) PASTA_LDB(0) PASTA_LDA(0) }
-        else { PASTA_LDA(2) PASTA_LDB(0) PASTA_LDA(0) PASTA_LDB(2) PASTA_LDA(1) PASTA_LDB(1) }
-#undef PASTA_LDA
-#undef PASTA_LDB
-    };
     // One tap = one step: 24 MFMAs in six groups; TAP (0, 1, 2: position in the kernel row), ABUF_ and BBUF_ are literals.
     auto step = [&](const int TAP, const int abuf, const int bbuf) {
         // weights of step t + 2 into the register set of this step's parity (abuf = parity); stored by step t + 1
         if (TAP == 1) next_a_stage();
         if (TAP == 0) load_b();
         load_a(TAP == 0 ? 2 : TAP == 1 ? 0 : 1, abuf);
-        Frag f;
-        read_frag(f, abuf, bbuf, p.rows_rev ? 2 - TAP : TAP);
-#define PASTA_MM(PA, PB)                                                                                       \
-        if constexpr (mm_on<NP>(PA, PB)) {                                                                       \
-        _Pragma("unroll") for (int a = 0; a < WMT; a++) _Pragma("unroll") for (int b = 0; b < WNT; b++)          \
-            acc[a][b] = mfma16<IO, NP>(f.a[a][PA], f.b[b][PB], acc[a][b]); }
-#define PASTA_SPLIT(J)                                                                                         \
-        if (TAP == 1) { _Pragma("unroll") for (int i = 0; i < BPT; i++) split_pair(mb, m_nvalid, i, J, msc); }   \
-        if (TAP == 2 && wave == h_owner) { _Pragma("unroll") for (int i = 0; i < BPT; i++) split_pair(hb, h_nvalid, i, J, hsc); }
-        if constexpr (HX) {
-            PASTA_MM(2, 1)
-            PASTA_SPLIT(0)
-            PASTA_SPLIT(1)
-            PASTA_MM(1, 0)
-            PASTA_SPLIT(2)
-            PASTA_SPLIT(3)
-        } else {
-        PASTA_MM(2, 0)
-        PASTA_SPLIT(0)
-        PASTA_MM(0, 2)
-        PASTA_SPLIT(1)
-        PASTA_MM(1, 1)
-        PASTA_SPLIT(2)
-        PASTA_MM(1, 0)
-        PASTA_SPLIT(3)
-        PASTA_MM(0, 1)
-        }
-        if (TAP == 1) store_q(bbuf ^ 1, m_slot, half0);
-        if (TAP == 2 && wave == h_owner) store_q(bbuf ^ 1, h_slot, h_half);
-        store_a(abuf ^ 1, abuf ^ 1);                     // the set fetched by the previous step
-        PASTA_MM(0, 0)
-#undef PASTA_MM
-#undef PASTA_SPLIT
+        const __bf16* A_ = As + abuf * ABUF;
+        const __bf16* B_ = Bs + bbuf * BBUF;
+        const int off = p.rows_rev ? 2 - TAP : TAP;
+        FwdFrag<WMT, WNT> f;
+        fwd_read_frag<NP>(f,
+            [&](int pc, int a) { return (const bf16x8*)&A_[((pc * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8]; },
+            [&](int pc, int b) { return (const bf16x8*)&B_[((pc * 2 + hl) * SLOTS + fslot[b] + off) * 8]; });
+        fwd_products<NP, IO>(f, acc,
+            [&](auto j) {
+                if (TAP == 1) {
+#pragma unroll
+                    for (int i = 0; i < BPT; i++) split_pair(mb, m_nvalid, i, j, msc);
+                }
+                if (TAP == 2 && wave == h_owner) {
+#pragma unroll
+                    for (int i = 0; i < BPT; i++) split_pair(hb, h_nvalid, i, j, hsc);
+                }
+            },
+            [&]() {
+                if (TAP == 1) store_q(bbuf ^ 1, m_slot, half0);
+                if (TAP == 2 && wave == h_owner) store_q(bbuf ^ 1, h_slot, h_half);
+                store_a(abuf ^ 1, abuf ^ 1);             // the set fetched by the previous step
+            });
         __syncthreads();
     };
 
-    // Register diet (PIPE == 2, the parity-pair mode):
+    // Register diet (PIPE == 2, the parity-pair mode) -- the ONE schedule that deviates from fwd_read_frag / fwd_products (conv_fwd_mma.h), on
+    // purpose: it trades their order for registers, which is what leaves room for the pair mode's second accumulator set.
     //  * fragments are read one operand at a time, in an order in which consecutive product groups share an operand:
     //    (a3,b1) (a2,b1) (a2,b2) (a1,b2) (a1,b3) (a1,b1): seven operand reads (fourteen ds_read_b128) instead of six pairs
     //    held at once -- 24 fragment registers live instead of 48.  The order of the six products within a chunk is free:
-    //    the accumulator already holds the sum over all earlier chunks;
+    //    the accumulator already holds the sum over all earlier chunks -- but it is NOT the order of fwd_products: a change made there
+    //    does not reach the pair mode, and its sums need not match another tile's in the last bits;
     //  * the split runs piece by piece with the residuals kept IN the staging registers, each piece stored as soon as it is
-    //    complete: 4 packed registers live instead of 12;
+    //    complete: 4 packed registers live instead of 12 (the residual step itself is the shared one, fwd_residual2);
     //  * the weights are fetched and stored within one step (one register set).
     auto split_piece = [&](float* b, const int* nvalid, uint32_t (&q)[BPT][4], bool first) {
 #pragma unroll
@@ -820,15 +550,10 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 float v0 = b[8 * i + 2 * j], v1 = b[8 * i + 2 * j + 1];
-                if (first && nvalid[i] < 8) {
-                    v0 = 2 * j < nvalid[i] ? v0 : 0.f;
-                    v1 = 2 * j + 1 < nvalid[i] ? v1 : 0.f;
-                }
+                if (first) fwd_mask2(v0, v1, j, nvalid[i]);
                 const uint32_t w = io_pack2<IO>(v0, v1);
                 q[i][j] = w;
-                v0 -= __builtin_bit_cast(float, w << 16);
-                v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-                PASTA_KEEP_SCALAR(v0);
+                fwd_residual2(v0, v1, w);
                 b[8 * i + 2 * j] = v0; b[8 * i + 2 * j + 1] = v1;
             }
     };
@@ -966,22 +691,7 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_rows_bf16x6_kernel(ConvFwdP
         }
         return;
     }
-    const float nstr = (p.noise && p.ksplit == 1) ? p.noise_strength[0] : 0.f;
-    const EpiAct ea = conv_epi_act(p.act, p.alpha, p.gain, p.clamp, p.ksplit == 1);
-    conv_epilogue_dispatch<(NP == NP_F16X3 || IO != IO_F32)>(o_blk + BM <= p.Og, ea, [&](auto full_c, auto case_c) {
-#pragma unroll
-    for (int b = 0; b < WNT; b++) {
-        const int64_t pix = pix_blk + (wn * WNT + b) * 32 + jl;
-        const int n = (int)(pix / (P * Q));
-        const int rem = (int)(pix - (int64_t)n * P * Q);
-        const int pp = rem / Q, qq = rem - pp * Q;
-        const int plane_off = (oy0 + pp * p.osy) * p.OW + ox0 + qq * p.osx;
-        const EpiColumn col = conv_epi_column(p, ea, g, ks, n, plane_off, nstr);
-#pragma unroll
-        for (int a = 0; a < WMT; a++)
-            conv_store_subtile<IO>(acc[a][b], col, o_blk + (wm * WMT + a) * 32, p.Og, lane, ea, y_am, full_c, case_c);
-    }
-    });
+    fwd_store_lattice<IO, (NP == NP_F16X3 || IO != IO_F32), false, false, BM>(p, acc, p.cls[cls_i], pix_blk, 0, g, ks, o_blk, wm, wn, lane, y_am);
     if (p.ksplit == 1) amax_commit(y_am, y_slot);
 }
 

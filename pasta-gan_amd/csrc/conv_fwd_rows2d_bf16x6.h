@@ -1,6 +1,6 @@
 // Two-dimensional pixel tiles for the row-reuse forward kernel.  Instantiated by conv_tu_rows2d_*.hip (conv_launch.h).
 #pragma once
-#include "conv_fwd_bf16x6.h"
+#include "conv_fwd_mma.h"
 #include <type_traits>
 
 namespace pasta {
@@ -181,8 +181,6 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         scale_from_amax(amax_of_parts(p.x_amax), sx, isx);
         x_scale = sx; out_scale = isx;                 // the weight rows carry their own scales: p.w_rowinv, applied per output row in the epilogue
     }
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     uint32_t q1[4], q2[4], q3[4];
     auto split_pair = [&](const float (&sb)[8], const float (&sc)[ISC ? 8 : 1], int nv, int j) {
         if constexpr (XP) {
@@ -192,32 +190,8 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
         }
         float v0 = sb[2 * j], v1 = sb[2 * j + 1];
         if constexpr (ISC) { v0 *= sc[2 * j]; v1 *= sc[2 * j + 1]; }
-        if (nv < 8) {
-            v0 = 2 * j < nv ? v0 : 0.f;
-            v1 = 2 * j + 1 < nv ? v1 : 0.f;
-        }
-        if constexpr (HX) {
-            f16_split2(v0 * x_scale, v1 * x_scale, q1[j], q2[j]);
-            return;
-        }
-        f32x2 v = {v0, v1};
-        uint32_t w = io_pack2<IO>(v0, v1);
-        q1[j] = w;
-        if constexpr (NP >= 2) {
-            v0 -= __builtin_bit_cast(float, w << 16);
-            v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-            PASTA_KEEP_SCALAR(v0);
-            v = f32x2{v0, v1};
-            w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-            q2[j] = w;
-        }
-        if constexpr (NP >= 3) {
-            v0 -= __builtin_bit_cast(float, w << 16);
-            v1 -= __builtin_bit_cast(float, w & 0xffff0000u);
-            PASTA_KEEP_SCALAR(v0);
-            v = f32x2{v0, v1};
-            q3[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-        }
+        fwd_mask2(v0, v1, j, nv);
+        fwd_split2<NP, IO>(v0, v1, x_scale, q1[j], q2[j], q3[j]);
     };
     auto store_unit = [&](int k, int bbuf) {
         if (u_lds[k] >= 0) {
@@ -258,20 +232,6 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
 #pragma unroll
     for (int t = 0; t < 9; t++) toff[t] = (p.tap_dy[t] - ymin) * SW + (p.tap_dx[t] - d0);
 
-    struct Frag { bf16x8 a[WMT][3], b[WNT][3]; };
-    auto read_frag = [&](Frag& f, int abuf, int bbuf, int off) {
-        const __bf16* A_ = As + abuf * ABUF;
-        const __bf16* B_ = Bs + bbuf * BBUF;
-#define PASTA_LDA(PC) if constexpr ((PC) < NPA) { _Pragma("unroll") for (int a = 0; a < WMT; a++) f.a[a][PC] = *(const bf16x8*)&A_[(((PC) * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8]; }
-#define PASTA_LDB(PC) if constexpr ((PC) < NPB) { _Pragma("unroll") for (int b = 0; b < WNT; b++) f.b[b][PC] = *(const bf16x8*)&B_[(((PC) * 2 + hl) * SLOTS + fslot[b] + off) * 8]; }
-        // in the order the product groups consume them, so that the first group starts when ITS operands have landed (the LDS
-        // returns reads in order: counted lgkmcnt waits): three-product arithmetic (h'' l'), (l h), (h h)
-        if constexpr (HX) { PASTA_LDA(2) PASTA_LDB(1) PASTA_LDA(1) PASTA_LDB(0) PASTA_LDA(0) }
-        else { PASTA_LDA(2) PASTA_LDB(0) PASTA_LDA(0) PASTA_LDB(2) PASTA_LDA(1) PASTA_LDB(1) }
-#undef PASTA_LDA
-#undef PASTA_LDB
-    };
-
     // One step = one tap of one chunk: 24 MFMAs in six groups.  S (0..8: tap within the chunk) and PAR (parity of the chunk
     // within the trip) are literals; cc = the chunk being multiplied.
     //   weights:  step g = 9 * chunk + S multiplies A buffer g & 1, stores the weights of step g + 1 (fetched by step g - 1
@@ -298,36 +258,21 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void conv_fwd_rows2d_bf16x6_
                 }
         };
         fetches();
-        Frag f;
-        read_frag(f, gpar, PAR, toff[S]);
-#define PASTA_MM(PA, PB)                                                                                       \
-        if constexpr (mm_on<NP>(PA, PB)) {                                                                       \
-        _Pragma("unroll") for (int a = 0; a < WMT; a++) _Pragma("unroll") for (int b = 0; b < WNT; b++)          \
-            acc[a][b] = mfma16<IO, NP>(f.a[a][PA], f.b[b][PB], acc[a][b]); }
-#define PASTA_SPLIT(J) if (ku != NOUNIT) { if ((ku & 1) == 0) split_pair(sb0, sc0, nv0, J); else split_pair(sb1, sc1, nv1, J); }
-        if constexpr (HX) {          // three product groups: h'' l', l h, h h -- smallest terms first
-            PASTA_MM(2, 1)
-            PASTA_SPLIT(0)
-            PASTA_SPLIT(1)
-            PASTA_MM(1, 0)
-            PASTA_SPLIT(2)
-            PASTA_SPLIT(3)
-        } else {
-        PASTA_MM(2, 0)
-        PASTA_SPLIT(0)
-        PASTA_MM(0, 2)
-        PASTA_SPLIT(1)
-        PASTA_MM(1, 1)
-        PASTA_SPLIT(2)
-        PASTA_MM(1, 0)
-        PASTA_SPLIT(3)
-        PASTA_MM(0, 1)
-        }
-        if (ku != NOUNIT) store_unit(ku, PAR ^ 1);
-        store_a(gpar ^ 1, gpar ^ 1);
-        PASTA_MM(0, 0)
-#undef PASTA_MM
-#undef PASTA_SPLIT
+        const __bf16* A_ = As + gpar * ABUF;
+        const __bf16* B_ = Bs + PAR * BBUF;
+        const int off = toff[S];
+        FwdFrag<WMT, WNT> f;
+        fwd_read_frag<NP>(f,
+            [&](int pc, int a) { return (const bf16x8*)&A_[((pc * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8]; },
+            [&](int pc, int b) { return (const bf16x8*)&B_[((pc * 2 + hl) * SLOTS + fslot[b] + off) * 8]; });
+        fwd_products<NP, IO>(f, acc,
+            [&](auto j) {
+                if (ku != NOUNIT) { if ((ku & 1) == 0) split_pair(sb0, sc0, nv0, j); else split_pair(sb1, sc1, nv1, j); }
+            },
+            [&]() {
+                if (ku != NOUNIT) store_unit(ku, PAR ^ 1);
+                store_a(gpar ^ 1, gpar ^ 1);
+            });
         __syncthreads();
     };
 

@@ -2,7 +2,7 @@
 // encoders: conv2d_resample.py:119-122 after the blur; 9.9 ms of the training step at 136 TFLOP/s on the one-tap base kernel,
 // profiles/r4_byshape_classes.txt).  Instantiated by conv_tu_fwd_small.hip (conv_launch.h).
 #pragma once
-#include "conv_fwd_bf16x6.h"
+#include "conv_fwd_mma.h"
 
 namespace pasta {
 
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_f16x3_kernel(ConvFwdParams p
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 float v0 = xv[k][(2 * q) % XV], v1 = xv[k][(2 * q + 1) % XV];
-                if (xvalid[k] < 8) { v0 = 2 * q < xvalid[k] ? v0 : 0.f; v1 = 2 * q + 1 < xvalid[k] ? v1 : 0.f; }
+                fwd_mask2(v0, v1, q, xvalid[k]);
                 f16_split2(v0 * sx, v1 * sx, h[q], l[q]);
             }
             __bf16* const d = &Bs[t_lds[k]];
@@ -183,25 +183,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_f16x3_kernel(ConvFwdParams p
         load_a(rn);
 #pragma unroll
         for (int dx = 0; dx < 3; dx++) {
-            bf16x8 fa[WMT][3], fb[WNT_][2];
+            FwdFrag<WMT, WNT_> f;           // read piece by piece (two workgroups per CU cover the LDS latency, as in conv1x1_f16x3_kernel)
 #pragma unroll
             for (int pc = 0; pc < 3; pc++)
 #pragma unroll
-                for (int a = 0; a < WMT; a++) fa[a][pc] = *(const bf16x8*)&As[(((dx * 3 + pc) * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8];
+                for (int a = 0; a < WMT; a++) f.a[a][pc] = *(const bf16x8*)&As[(((dx * 3 + pc) * 2 + hl) * BM + (wm * WMT + a) * 32 + jl) * 8];
 #pragma unroll
             for (int pc = 0; pc < 2; pc++)
 #pragma unroll
                 for (int b = 0; b < WNT_; b++) {
                     const int slot = dx == 1 ? oslot[b] : eslot[b] + (dx >> 1);
-                    fb[b][pc] = *(const bf16x8*)&Bs[((pc * 2 + hl) * SLOTS + slot) * 8];
+                    f.b[b][pc] = *(const bf16x8*)&Bs[((pc * 2 + hl) * SLOTS + slot) * 8];
                 }
-#define PASTA_MM2(PA, PB)                                                                                          \
-            _Pragma("unroll") for (int a = 0; a < WMT; a++) _Pragma("unroll") for (int b = 0; b < WNT_; b++)         \
-                acc[a][b] = mfma16<IO_F32, NP>(fa[a][PA], fb[b][PB], acc[a][b]);
-            PASTA_MM2(2, 1)     // h'' l', l h, h h: smallest terms first
-            PASTA_MM2(1, 0)
-            PASTA_MM2(0, 0)
-#undef PASTA_MM2
+            fwd_products<NP, IO_F32>(f, acc, FwdNoSlot{}, FwdNoStores{});       // the staging of this kernel runs between the rounds
         }
         __syncthreads();
     }

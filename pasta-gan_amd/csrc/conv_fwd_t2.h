@@ -2,7 +2,7 @@
 // the generator (conv2d_resample.py:104-115, the transposed convolution in front of the blur) and the input gradient of every stride-2
 // convolution.  Instantiated by conv_tu_fwd_t2.hip (conv_launch.h).
 #pragma once
-#include "conv_fwd_bf16x6.h"
+#include "conv_fwd_mma.h"
 
 namespace pasta {
 
@@ -164,8 +164,7 @@ __device__ __forceinline__ void conv_t2_body(const ConvFwdParams& p, const int n
             for (int j = 0; j < 4; j++) {
                 float v0 = sb[set][k][2 * j], v1 = sb[set][k][2 * j + 1];
                 if constexpr (ISC) { v0 *= sc[set][k][2 * j]; v1 *= sc[set][k][2 * j + 1]; }
-                v0 = 2 * j < nv[set][k] ? v0 : 0.f;
-                v1 = 2 * j + 1 < nv[set][k] ? v1 : 0.f;
+                fwd_mask2<false>(v0, v1, j, nv[set][k]);
                 f16_split2(v0 * x_scale, v1 * x_scale, q1[j], q2[j]);
             }
             __bf16* const bd = Bs + buf * BBUF + u_lds[k];
@@ -202,17 +201,15 @@ __device__ __forceinline__ void conv_t2_body(const ConvFwdParams& p, const int n
                 bh[b] = *(const bf16x8*)(b_lane[b] + (buf * BBUF + off * 8) * 2);
             }
         };
-        auto tap = [&](int t, int cls) {                // both literals: three products, smallest terms first (h'' l', l h, h h)
+        auto tap = [&](int t, int cls) {                // both literals: the three products of fwd_products on one row tile and the window's two pixel blocks
             const char* const at = a_lane + (buf * ABUF + t * (6 * BM * 8)) * 2;
-            const bf16x8 a2 = *(const bf16x8*)(at + (4 * BM * 8) * 2);
-            const bf16x8 a1 = *(const bf16x8*)(at + (2 * BM * 8) * 2);
-            const bf16x8 a0 = *(const bf16x8*)(at);
+            FwdFrag<1, 2> f;
+            f.a[0][2] = *(const bf16x8*)(at + (4 * BM * 8) * 2);
+            f.a[0][1] = *(const bf16x8*)(at + (2 * BM * 8) * 2);
+            f.a[0][0] = *(const bf16x8*)(at);
 #pragma unroll
-            for (int b = 0; b < 2; b++) acc[cls][b] = mfma16<IO_F32, NP>(a2, bl[b], acc[cls][b]);
-#pragma unroll
-            for (int b = 0; b < 2; b++) acc[cls][b] = mfma16<IO_F32, NP>(a1, bh[b], acc[cls][b]);
-#pragma unroll
-            for (int b = 0; b < 2; b++) acc[cls][b] = mfma16<IO_F32, NP>(a0, bh[b], acc[cls][b]);
+            for (int b = 0; b < 2; b++) { f.b[b][1] = bl[b]; f.b[b][0] = bh[b]; }
+            fwd_products<NP, IO_F32>(f, &acc[cls], FwdNoSlot{}, FwdNoStores{});      // (&acc[cls])[0][b]: the class's accumulators as [1][2]
         };
         // tap (r, c) = 3 r + c: class (r & 1, c & 1), window position (-(r >> 1), -(c >> 1)); an edge tile has one row / column of windows
         if (kind == 2) { window(-1); tap(8, 0); window(0); tap(2, 0); tap(5, 2); }      // (the column edge's own map: see the head of the file)

@@ -8,10 +8,14 @@
 //   conv_plan.h                the planner: kernel choice, shape predicates, workspace layouts, tap tables (no HIP header)
 //   conv_common.h              parameter blocks, the shared epilogue of the split forward-type kernels (conv_unscale_rows,
 //                              conv_store_subtile) and the (input scale, storage, pieces) -> <NP, IO, ISC> dispatch of their launches
-//   conv_fwd_f32.h             fp32-MFMA forward-type kernel, weight packing        -> conv_tu_pack_f32.hip
+//   conv_fwd_f32.h             fp32-MFMA forward-type kernel, its weight packing    -> conv_tu_pack_f32.hip
+//   conv_pack.h                weight packing of the split forward-type kernels     -> conv_tu_pack_f32.hip
+//   conv_fwd_mma.h             the K-loop body of the split forward-type kernels, once: operand split (fwd_split2), fragment read order
+//                              (fwd_read_frag), product schedule (fwd_products); included by the five headers below
 //   conv_fwd_bf16x6.h          split forward-type kernels (base and row-reuse)      -> conv_tu_fwd_base_{128,64}.hip, conv_tu_fwd_rows_{128,64}.hip
-//   conv_fwd_rows2d_bf16x6.h   2-D pixel tiles                                      -> conv_tu_rows2d_{wide,128_r4,128_r2,64_r8}.hip
+//   conv_fwd_rows2d_bf16x6.h   2-D pixel tiles                                      -> conv_tu_rows2d_{wide,wide_xp,128_r4,128_r2,64_r8}.hip
 //   conv_fwd_1x1.h, conv_fwd_s2.h  pointwise and stride-2 kernels                   -> conv_tu_fwd_small.hip
+//   conv_fwd_t2.h              stride-2 conv_transpose2d in one pass                -> conv_tu_fwd_t2.hip
 //   conv_wgrad_f32.h           fp32-MFMA weight gradients, few-channel kernels, slab reductions -> conv_tu_wgrad_f32.hip
 //   conv_wgrad_bf16x6.h        split weight-gradient kernels                        -> conv_tu_wgrad_{3x3,3x3s2,1x1}.hip
 //   (no header)                K-slice reduction, pair-launch remainder, packed-K set-up -> conv_tu_aux.hip

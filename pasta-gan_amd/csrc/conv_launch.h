@@ -4,9 +4,10 @@
 // a translation unit of its own (conv_tu_*.hip: explicit instances behind plain host functions, built in parallel by
 // torch_utils/custom_ops.py) and reached through the functions declared here -- conv_igemm.hip includes no kernel header.  The kernel headers
 // hold templates only, so including them instantiates nothing; the few non-template kernels are fenced by PASTA_TU_PACK / PASTA_TU_WGRAD_F32
-// and defined by exactly one unit.  What the forward-type kernels share
+// or live in a header that one unit alone includes (conv_pack.h), and are defined by exactly one unit.  What the forward-type kernels share
 // -- the epilogue of a 32 x 32 sub-tile (conv_store_subtile) and the choice of <NP, IO, ISC> for a launch (conv_arith_dispatch) -- is in
-// conv_common.h, and so is what the weight-gradient kernels share (wgrad_slice, wgrad_split_store8, WgradChunkPos, wgrad_arith_dispatch, ...).
+// conv_common.h, and so is what the weight-gradient kernels share (wgrad_slice, wgrad_split_store8, WgradChunkPos, wgrad_arith_dispatch, ...);
+// the K-loop body of the split forward-type kernels (operand split, fragment read order, product schedule) is conv_fwd_mma.h.
 #pragma once
 #include "conv_common.h"
 

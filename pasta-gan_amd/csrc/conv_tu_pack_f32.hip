@@ -1,9 +1,9 @@
-// Translation unit of the convolution family (conv_launch.h): the weight-packing kernels of every arithmetic and the fp32-MFMA
-// forward-type kernels.
+// Translation unit of the convolution family (conv_launch.h): the weight-packing kernels of every arithmetic (conv_fwd_f32.h, conv_pack.h) and
+// the fp32-MFMA forward-type kernels.
 #define PASTA_TU_PACK 1
 #include "conv_launch.h"
 #include "conv_fwd_f32.h"
-#include "conv_fwd_bf16x6.h"
+#include "conv_pack.h"
 
 namespace pasta {
 

@@ -295,7 +295,7 @@ def _f32_exact(t, what):
 
 def effective_weights(case, d, operand_dtype=None):
     """The weights the matrix cores multiply, [C_out, C_in / G, k, k] ([C_in, C_out / G, k, k] transposed), fp64: w * wgain, modulated per group
-    ((w * wgain) * s) * d as the packing kernels form it (csrc/conv_fwd_bf16x6.h).  ``operand_dtype``: the product is formed in fp32 and rounded
+    ((w * wgain) * s) * d as the packing kernels form it (csrc/conv_pack.h).  ``operand_dtype``: the product is formed in fp32 and rounded
     once to that type (generic data; on the exact grids nothing rounds)."""
     w = d['w']
     lo = (lambda t: t.to(torch.float32)) if operand_dtype is not None else (lambda t: t)
