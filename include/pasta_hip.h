@@ -597,6 +597,34 @@ int pasta_tryon_assemble(const uint8_t* image, const uint8_t* stick, const uint8
                          const uint8_t* arm_masks, const uint8_t* erase_masks, const int32_t* erase_hw, float* const* outputs, int N,
                          int H, int W, int ph, int pw, int c_upper, int c_lower, int mh_max, int mw_max, void* stream);
 
+/* Mirrored people (this project's own rule; --mirror-people of train_wo_flow_fullbody.py, training/tryon_batch.py's
+ * mirror_batch).  The reference's --mirror flips the PREPARED tuple, which is undefined for this data (the palm rule pairs label
+ * 14 with joints 5-7 and label 15 with joints 2-4).  Here a raw sample with xflip = 1 is the sample as a mirror shows it, formed
+ * BEFORE any preparation; everything downstream (stick figure, palm, masks, warps, erase rule, float conversions) is unchanged
+ * and does not know about it:
+ *   image     image'[y, x, :] = image[y, W-1-x, :];
+ *   labels    parsing'[y, x] = lut[parsing[y, W-1-x]], lut a 256-byte table: the identity except 14 <-> 15 (arms), 16 <-> 17
+ *             (legs) and 18 <-> 19 (shoes) (training.tryon_batch.mirror_lut);
+ *   erase     erase'[y, x] = erase[y, w_n-1-x] inside the sample's own h_n x w_n (erase_hw[n]); the rest of the stacked tensor,
+ *             the padding, is copied (collate writes 0 there);
+ *   joints    on the host, in float64 (training.tryon_batch.mirror_keypoints): x' = (W-1) - x for every joint whatever its
+ *             confidence, y and confidence unchanged, the rows exchanged for (2,5), (3,6), (4,7), (8,11), (9,12), (10,13),
+ *             (14,15), (16,17); W is the unpadded width and the shift by the (symmetric) padding happens afterwards, as before.
+ * A mirrored batch is NOT the flipped unmirrored batch and is not meant to be: int()-truncation of the joints and the 16 x 16
+ * box's offsets -8..7 are not reflection-symmetric.
+ * This entry is out of place and does a whole batch in one launch: image [N,H,W,3], parsing [N,H,W], erase_masks
+ * [N,mh_max,mw_max] with erase_hw [N][2] int32, flip [N] uint8 and lut [256] on the device -> image_out, parsing_out, erase_out of
+ * the inputs' shapes.  An item with flip[n] == 0 is copied through unchanged, the table not applied; the flags are read on the
+ * device.  erase_masks and erase_out may both be null (erase_hw, mh_max and mw_max are then not read).  A size in erase_hw outside
+ * the stacked tensor is read as the nearest one inside.  With W a multiple of 16 and 16-byte aligned tensors a thread moves 16
+ * pixels with 16-byte loads and stores, the pixel order reversed in registers; any other width goes pixel by pixel.
+ * Refused before any launch: a null image, parsing, flip, lut, image_out or parsing_out; an output equal to its input; N outside
+ * 1..65535, H or W outside 1..16384; an erase pointer pair that is half null; with erase masks, a null erase_hw or mh_max or
+ * mw_max outside 1..16384. */
+int pasta_tryon_mirror_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* erase_masks, const int32_t* erase_hw,
+                          const uint8_t* flip, const uint8_t* lut, uint8_t* image_out, uint8_t* parsing_out, uint8_t* erase_out, int N,
+                          int H, int W, int mh_max, int mw_max, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the try-on TEST pairs (row f4; UvitonDatasetV19_test._load_raw_image / normalize / __getitem__,
  * training/dataset.py:1085-1525, and test.py:104-150).  Same canvas, restated primitives and exactness as the entries

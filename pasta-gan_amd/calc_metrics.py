@@ -106,7 +106,7 @@ def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, wor
         if kwargs is None:
             ctx.fail('Could not look up dataset options; please specify --data')
         args.dataset_kwargs = dnnlib.EasyDict(kwargs)
-    args.dataset_kwargs.update(use_labels=False, xflip=False)
+    args.dataset_kwargs.update(use_labels=False, xflip=False, mirror_people=False)
     if args.verbose:
         print('Dataset options:')
         print(json.dumps(args.dataset_kwargs, indent=2))

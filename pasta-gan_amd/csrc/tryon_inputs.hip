@@ -5,7 +5,9 @@
 //   pasta_tryon_masks_u8    retain mask, gt_parsing, garment images and garment masks (:537-556) of both training sets;
 //   pasta_tryon_assemble    erase mask (__getitem__ :951-973) and the loop's conversions (training_loop...:425-456); its
 //                           per-pixel body is csrc/tryon_common.h's train_pixel (the erase rule with the restated resize, then
-//                           tryon_pixel), shared with the 512 x 320 training kernel of csrc/tryon_pairs.hip.
+//                           tryon_pixel), shared with the 512 x 320 training kernel of csrc/tryon_pairs.hip;
+//   pasta_tryon_mirror_u8   the raw samples of a batch as a mirror shows them (this project's own rule, --mirror-people): the
+//                           photograph, the label map with left and right exchanged and the erase mask, before any of the above.
 // The palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702) is csrc/tryon_pairs.hip's pasta_palm_mask_u8.
 // Every entry is its checks and one launch for a whole batch.  The reference does this on the host with OpenCV, pycocotools and
 // skimage.  What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
@@ -114,7 +116,112 @@ __global__ __launch_bounds__(256) void tryon_assemble_kernel(const uint8_t* __re
                 arm_masks + ((int64_t)n * 4 + 3) * HH, erase_src, erase_hw, mh_max, mw_max);
 }
 
+// ---- mirrored people (this project's own rule: include/pasta_hip.h, pasta_tryon_mirror_u8) ----
+
+// Byte b of the little-endian words w; with constant b the compiler folds a word of these into byte permutes.
+__device__ __forceinline__ uint32_t word_byte(const uint32_t* w, int b) { return (w[b >> 2] >> ((b & 3) * 8)) & 0xffu; }
+
+// One launch for a batch: item n = blockIdx.y; its threads are, in this order, the image's units, the label map's units and the
+// erase mask's bytes.  WIDE: a unit is 16 pixels of a row (W % 16 == 0, 16-byte aligned tensors): three 16-byte loads of the
+// image, the pixel order reversed in registers, three 16-byte stores at the mirrored place; one load and one store of the labels.
+// Otherwise a unit is one pixel.  An item whose flag is 0 is copied; the table (in LDS) is applied to flagged items only.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void tryon_mirror_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ parsing,
+                                                           const uint8_t* __restrict__ erase, const int32_t* __restrict__ erase_hw,
+                                                           const uint8_t* __restrict__ flip, const uint8_t* __restrict__ lut,
+                                                           uint8_t* __restrict__ image_out, uint8_t* __restrict__ parsing_out,
+                                                           uint8_t* __restrict__ erase_out, int H, int W, int eh, int ew) {
+    __shared__ uint8_t table[256];
+    table[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    constexpr int PX = WIDE ? 16 : 1;
+    const int n = blockIdx.y;
+    const bool f = flip[n] != 0;                         // uniform over the workgroup
+    const int cw = W / PX, units = H * cw;
+    int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < 2 * units) {
+        const bool labels = t >= units;
+        if (labels) t -= units;
+        const int y = t / cw, x0 = (t - y * cw) * PX;
+        const int64_t row = ((int64_t)n * H + y) * W;
+        const int64_t src = row + x0, dst = row + (f ? W - PX - x0 : x0);
+        if constexpr (WIDE) {
+            if (!labels) {
+                const uint4* s = reinterpret_cast<const uint4*>(image + src * 3);
+                uint4* d = reinterpret_cast<uint4*>(image_out + dst * 3);
+                const uint4 a = s[0], b = s[1], c = s[2];
+                if (!f) { d[0] = a; d[1] = b; d[2] = c; return; }
+                const uint32_t w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+                uint32_t o[12];
+#pragma unroll
+                for (int k = 0; k < 12; k++) {           // byte j of the output is channel j % 3 of pixel 15 - j / 3
+                    o[k] = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) o[k] |= word_byte(w, (15 - (4 * k + i) / 3) * 3 + (4 * k + i) % 3) << (8 * i);
+                }
+                d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+                d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+                d[2] = make_uint4(o[8], o[9], o[10], o[11]);
+            } else {
+                const uint4 a = *reinterpret_cast<const uint4*>(parsing + src);
+                uint4* d = reinterpret_cast<uint4*>(parsing_out + dst);
+                if (!f) { *d = a; return; }
+                const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+                uint32_t o[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    o[k] = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) o[k] |= (uint32_t)table[word_byte(w, 15 - (4 * k + i))] << (8 * i);
+                }
+                *d = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+        } else {
+            if (!labels) {
+                for (int ch = 0; ch < 3; ch++) image_out[dst * 3 + ch] = image[src * 3 + ch];
+            } else {
+                const uint8_t L = parsing[src];
+                parsing_out[dst] = f ? table[L] : L;
+            }
+        }
+        return;
+    }
+    t -= 2 * units;
+    if (erase == nullptr || t >= eh * ew) return;
+    const int y = t / ew, x = t - y * ew;
+    // the sample's own size, held inside the stacked tensor whatever the device array says
+    const int hn = min(max(erase_hw[2 * n], 0), eh), wn = min(max(erase_hw[2 * n + 1], 0), ew);
+    const int64_t base = ((int64_t)n * eh + y) * ew;
+    erase_out[base + x] = erase[base + ((f && y < hn && x < wn) ? wn - 1 - x : x)];
+}
+
 }  // namespace pasta
+
+extern "C" int pasta_tryon_mirror_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* erase_masks, const int32_t* erase_hw,
+                                     const uint8_t* flip, const uint8_t* lut, uint8_t* image_out, uint8_t* parsing_out,
+                                     uint8_t* erase_out, int N, int H, int W, int mh_max, int mw_max, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && parsing && flip && lut && image_out && parsing_out, "tryon_mirror_u8: null pointer");
+    PASTA_CHECK(image_out != image && parsing_out != parsing && (erase_out == nullptr || erase_out != erase_masks),
+                "tryon_mirror_u8: an output is its input (the entry is out of place)");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "tryon_mirror_u8: bad shape (N %d, %d x %d)", N, H, W);
+    const bool masks = erase_masks != nullptr;
+    PASTA_CHECK(masks == (erase_out != nullptr), "tryon_mirror_u8: erase_masks and erase_out are null together or not at all");
+    PASTA_CHECK(!masks || (erase_hw && mh_max >= 1 && mh_max <= 16384 && mw_max >= 1 && mw_max <= 16384),
+                "tryon_mirror_u8: erase masks need erase_hw and a stack of 1..16384 rows and columns (%d x %d)", mh_max, mw_max);
+    const int eh = masks ? mh_max : 0, ew = masks ? mw_max : 0;
+    const uintptr_t all = (uintptr_t)image | (uintptr_t)parsing | (uintptr_t)image_out | (uintptr_t)parsing_out;
+    const bool wide = W % 16 == 0 && all % 16 == 0;
+    const int64_t threads = 2 * (int64_t)H * (W / (wide ? 16 : 1)) + (int64_t)eh * ew;         // < 2^30: an int in the kernel
+    dim3 grid((unsigned)((threads + 255) / 256), (unsigned)N);
+    if (wide)
+        hipLaunchKernelGGL(tryon_mirror_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, erase_masks, erase_hw, flip, lut,
+                           image_out, parsing_out, erase_out, H, W, eh, ew);
+    else
+        hipLaunchKernelGGL(tryon_mirror_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, erase_masks, erase_hw, flip, lut,
+                           image_out, parsing_out, erase_out, H, W, eh, ew);
+    return launch_status("tryon_mirror_u8");
+}
 
 extern "C" int pasta_pose_stickman_u8(const int32_t* limbs, const int32_t* joints, uint8_t* out, int N, int H, int W, int thickness, int radius,
                                       void* stream) {

@@ -54,16 +54,17 @@ def report_metric(result_dict, run_dir=None, snapshot_pkl=None):
             f.write(line + '\n')
 
 #----------------------------------------------------------------------------
-# Paired reconstruction (metrics/reconstruction.py).
+# Paired reconstruction (metrics/reconstruction.py).  Scored on the people as photographed: a snapshot's training_set_kwargs may carry
+# mirror_people, which is forced off where xflip is.
 
 @register_metric
 def recon_full(opts):
-    opts.dataset_kwargs.update(max_size=None, xflip=False)
+    opts.dataset_kwargs.update(max_size=None, xflip=False, mirror_people=False)
     return reconstruction.compute(opts, 'recon_full')
 
 @register_metric
 def recon2k(opts):
-    opts.dataset_kwargs.update(max_size=2000, random_seed=0, xflip=False)
+    opts.dataset_kwargs.update(max_size=2000, random_seed=0, xflip=False, mirror_people=False)
     return reconstruction.compute(opts, 'recon2k')
 
 #----------------------------------------------------------------------------

@@ -14,6 +14,10 @@ the options the state file recorded:
 
     python train_wo_flow_fullbody.py --outdir=runs --data=<training tree> --continue=runs/00000-...
 
+``--mirror-people=true`` doubles the training set with every person as a mirror shows them: photograph, label map and erase mask
+reversed, left and right labels and joints exchanged, per batch on the GPU before the preparation (the reference's
+``--mirror`` stays refused).
+
 ``--storage=bf16`` (or ``f16``) keeps the activations of G and of every block of D in that type; parameters, demodulation,
 statistics, the images and the loss stay fp32.
 """
@@ -49,7 +53,8 @@ SUPPORTED_METRICS = ('recon_full', 'recon2k')       # metrics/metric_main.py; th
 def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
-                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None):
+                               mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
+                               mirror_people=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -110,7 +115,13 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
             args.training_set_kwargs.random_seed = args.random_seed
     if mirror:
         raise UserError('--mirror=true is not supported: a mirrored person would need mirrored key points and left / right labels, '
-                        'which the data set does not provide')
+                        'which the data set does not provide (the reference flips the prepared tuple; --mirror-people=true trains on '
+                        'people mirrored before the preparation, by this package\'s own rule)')
+    # --mirror-people (own option): every person a second time as a mirror shows them, mirrored per batch on the GPU.  Set after
+    # max_size, which stays the number of people (:154-155 does the same with xflip)
+    if mirror_people:
+        desc += '-mirrorpeople'
+        args.training_set_kwargs.mirror_people = True
 
     # Base config: cfg, gamma, kimg, batch (:161-246)
     cfg = 'auto' if cfg is None else cfg
@@ -267,7 +278,7 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         recorded = {'gpus': args.num_gpus, 'batch': args.batch_size}.get(name)
         if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
             continue
-        option = '--' + ('allow-tf32' if name == 'allow_tf32' else name)
+        option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people'}.get(name, name)
         raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
                         (f' ({recorded})' if recorded is not None else ''))
 
@@ -276,7 +287,8 @@ def setup_continue_kwargs(continue_path, data=None, **given):
     recorded = args.training_set_kwargs
     class_name = training_set_class(data)
     try:
-        training_set = dnnlib.util.construct_class_by_name(**dict(recorded, class_name=class_name, path=data, max_size=None))
+        # the people are counted unmirrored: max_size was recorded before --mirror-people doubled the set
+        training_set = dnnlib.util.construct_class_by_name(**dict(recorded, class_name=class_name, path=data, max_size=None, mirror_people=False))
         people, resolution = len(training_set), training_set.resolution
         del training_set
     except IOError as err:
@@ -384,6 +396,7 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--cond', help='Not supported [default: false]', type=bool, metavar='BOOL')
 @click.option('--subset', help='Train with only N images [default: all]', type=int, metavar='INT')
 @click.option('--mirror', help='Not supported [default: false]', type=bool, metavar='BOOL')
+@click.option('--mirror-people', help='Train on every person a second time, mirrored on the GPU [default: false]', type=bool, metavar='BOOL')
 # Base config.
 @click.option('--cfg', help='Base config [default: auto]', type=click.Choice(list(CFG_SPECS) + list(UNSUPPORTED_CFGS)))
 @click.option('--gamma', help='Override R1 gamma', type=float)
@@ -442,6 +455,7 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
     print(f'Training duration:  {args.total_kimg} kimg')
     print(f'Number of GPUs:     {args.num_gpus}')
     print(f'Number of images:   {args.training_set_kwargs.max_size}')
+    print(f'Mirrored people:    {bool(args.training_set_kwargs.get("mirror_people", False))}')
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

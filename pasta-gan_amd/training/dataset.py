@@ -104,7 +104,12 @@ class UvitonDatasetFull(Dataset):
     returns the raw sample (see the module docstring): a dict with
     ``image`` uint8 [H, W, 3], ``parsing`` uint8 [H, W] (channel 0 as cv2.imread reads it), ``keypoints`` float64 [18, 3],
     ``erase_mask`` uint8 [h, w] (channel 0 of the ACGPN mask file ``raw_idx % count``, whatever its size) and ``raw_idx``.
-    Key points stay float64 because the reference truncates and offsets them in float64."""
+    Key points stay float64 because the reference truncates and offsets them in float64.
+
+    ``mirror_people=True`` (this project's own; the reference's ``xflip`` flips the prepared tuple, which is undefined here and stays
+    refused) doubles the set: positions N .. 2N-1 are the people of positions 0 .. N-1 again, with ``xflip`` = 1 in the raw
+    sample.  The files are read as they are: the builder mirrors the flagged items of a batch on the GPU
+    (``training.tryon_batch.mirror_batch``; include/pasta_hip.h has the rule).  Without the option a sample has no ``xflip``."""
 
     _sub_datasets = SUB_DATASETS
     _vis_sources = (('Zalando_256_192', 'image'), ('Deepfashion_256_192', os.path.join('image', 'train')))     # :461-472, in this order
@@ -113,11 +118,12 @@ class UvitonDatasetFull(Dataset):
     def _label_name(dataset, name):
         return name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')
 
-    def __init__(self, path, resolution=None, **super_kwargs):
+    def __init__(self, path, resolution=None, mirror_people=False, **super_kwargs):
         self._path = path
         if not os.path.isdir(self._path):
             raise IOError('Path must point to a directory')
         self._type = 'dir'
+        self._mirror_people = bool(mirror_people)
         self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
         for dataset in self._sub_datasets:
             with open(os.path.join(self._path, dataset, PAIR_LIST), 'r') as f:
@@ -149,6 +155,9 @@ class UvitonDatasetFull(Dataset):
         if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
             raise IOError('Image files do not match the specified resolution')
         super().__init__(name=os.path.splitext(os.path.basename(self._path))[0], raw_shape=raw_shape, **super_kwargs)
+        if self._mirror_people:         # after max_size, as the reference's base class does with xflip (dataset.py:75-79)
+            self._raw_idx = np.tile(self._raw_idx, 2)
+            self._xflip = np.concatenate([self._xflip, np.ones_like(self._xflip)])
 
     def _load_image(self, raw_idx):
         image = np.array(PIL.Image.open(os.path.join(self._path, self._image_fnames[raw_idx])))
@@ -166,7 +175,10 @@ class UvitonDatasetFull(Dataset):
         return dict(image=image, parsing=parsing, keypoints=keypoints, erase_mask=erase, raw_idx=int(raw_idx))
 
     def __getitem__(self, idx):
-        return self.load_raw(self._raw_idx[idx])
+        sample = self.load_raw(self._raw_idx[idx])
+        if self._mirror_people:
+            sample['xflip'] = int(self._xflip[idx])
+        return sample
 
 
 class UvitonDatasetFull_512(UvitonDatasetFull):
@@ -195,7 +207,8 @@ def training_set_class(path):
 def collate(samples):
     """A list of raw samples -> one batch: ``image`` uint8 [N, H, W, 3], ``parsing`` uint8 [N, H, W], ``keypoints`` float64
     [N, 18, 3], ``erase_masks`` uint8 [N, h_max, w_max] (each mask in the top-left corner) with ``erase_hw`` int32 [N, 2]
-    (its own size), ``raw_idx`` int64 [N].  Use as the DataLoader's ``collate_fn``."""
+    (its own size), ``raw_idx`` int64 [N]; ``xflip`` uint8 [N] when the samples carry it (``mirror_people``).  Use as the
+    DataLoader's ``collate_fn``."""
     n = len(samples)
     h_max = max(s['erase_mask'].shape[0] for s in samples)
     w_max = max(s['erase_mask'].shape[1] for s in samples)
@@ -205,11 +218,14 @@ def collate(samples):
         h, w = s['erase_mask'].shape
         erase[i, :h, :w] = s['erase_mask']
         erase_hw[i] = h, w
-    return dict(image=torch.from_numpy(np.stack([s['image'] for s in samples])),
-                parsing=torch.from_numpy(np.stack([s['parsing'] for s in samples])),
-                keypoints=torch.from_numpy(np.stack([s['keypoints'] for s in samples])),
-                erase_masks=torch.from_numpy(erase), erase_hw=torch.from_numpy(erase_hw),
-                raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
+    batch = dict(image=torch.from_numpy(np.stack([s['image'] for s in samples])),
+                 parsing=torch.from_numpy(np.stack([s['parsing'] for s in samples])),
+                 keypoints=torch.from_numpy(np.stack([s['keypoints'] for s in samples])),
+                 erase_masks=torch.from_numpy(erase), erase_hw=torch.from_numpy(erase_hw),
+                 raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
+    if 'xflip' in samples[0]:
+        batch['xflip'] = torch.as_tensor([s['xflip'] for s in samples], dtype=torch.uint8)
+    return batch
 
 #----------------------------------------------------------------------------
 

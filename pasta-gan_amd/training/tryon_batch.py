@@ -8,11 +8,15 @@ do per sample on the host, as a few launches per batch:
     patch_pipeline.normalize_batch   the ten body-part warps    (csrc/patches.hip)
     pasta_tryon_assemble     erase mask and every float conversion, into the nine tensors of SyntheticFullBodyBatch.KEYS
 
+and, before them, for a batch of a data set opened with ``mirror_people`` that holds a flagged item (``mirror_batch``):
+
+    pasta_tryon_mirror_u8    photograph, label map (left and right exchanged) and erase mask as a mirror shows them
+
 The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
 ``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
-masks), ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their
+masks), ``mirror_batch`` (the training sets' mirrored people), ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their
 pointer array) and ``shift_keypoints``.
 ``builder_for`` picks the training builder of a data set: this one, or training/tryon_regions.py's at 512 x 320."""
 
@@ -34,6 +38,9 @@ QUAD_LIMIT = 1e5                    # palm quadrilateral corners are clamped to 
 STICK_THICKNESS = 2                 # cv2.line(..., 2) of both 256 x 192 sets (dataset.py:724, :1307)
 STICK_RADIUS = 2                    # circle(..., radius=2) (:734, :1318)
 PALM_BOXES = (25, 16)               # get_hand_mask of the training set: upper arm 25 x 25, forearm 16 x 16 (:663, :668)
+# A mirrored person (this project's own rule, include/pasta_hip.h: pasta_tryon_mirror_u8): the labels and the joints that change sides
+MIRROR_LABELS = ((14, 15), (16, 17), (18, 19))          # arms, legs, shoes
+MIRROR_JOINTS = ((2, 5), (3, 6), (4, 7), (8, 11), (9, 12), (10, 13), (14, 15), (16, 17))   # shoulders .. ankles, eyes, ears
 
 
 def stick_tables(keypoints):
@@ -107,6 +114,51 @@ def upload_erase(raw, device, n):
     return erase, erase_hw
 
 
+def mirror_lut():
+    """The label table of a mirrored person, uint8 [256]: the identity except MIRROR_LABELS exchanged."""
+    lut = np.arange(256, dtype=np.uint8)
+    for a, b in MIRROR_LABELS:
+        lut[a], lut[b] = b, a
+    return lut
+
+
+def mirror_keypoints(keypoints, W, flags):
+    """[N, 18, 3] key points of an UNPADDED canvas ``W`` wide -> a float64 copy in which every item with a non-zero flag is the
+    mirrored person's: x' = (W - 1) - x for every joint whatever its confidence, y and confidence kept, the rows of MIRROR_JOINTS
+    exchanged.  Items with flag 0 keep their bits."""
+    kp = np.asarray(keypoints, np.float64).copy()
+    flagged = np.asarray(flags).reshape(-1) != 0
+    assert kp.ndim == 3 and kp.shape[1:] == (18, 3) and flagged.shape == (kp.shape[0],)
+    rows = np.arange(18)
+    for a, b in MIRROR_JOINTS:
+        rows[a], rows[b] = b, a
+    m = kp[flagged][:, rows]
+    m[..., 0] = (W - 1) - m[..., 0]
+    kp[flagged] = m
+    return kp
+
+
+def mirror_batch(raw, image, parsing, keypoints, erase, erase_hw):
+    """What both training builders call straight after ``upload_person`` / ``upload_erase``: (image, parsing, keypoints, erase)
+    with the items that ``raw['xflip']`` flags mirrored, in one launch for the batch (pasta_tryon_mirror_u8) and
+    ``mirror_keypoints`` on the host.  A batch without ``xflip``, or with no flag set, comes back as it is and launches nothing."""
+    if 'xflip' not in raw:
+        return image, parsing, keypoints, erase
+    flags = np.ascontiguousarray(np.asarray(raw['xflip']), dtype=np.uint8)
+    n, H, W, _ = image.shape
+    assert flags.shape == (n,) and (flags <= 1).all()
+    if not flags.any():
+        return image, parsing, keypoints, erase
+    dev = image.device
+    flip, lut = torch.from_numpy(flags).to(dev, non_blocking=True), torch.from_numpy(mirror_lut()).to(dev, non_blocking=True)
+    image_m, parsing_m, erase_m = torch.empty_like(image), torch.empty_like(parsing), torch.empty_like(erase)
+    P = _native.ptr
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().pasta_tryon_mirror_u8(P(image), P(parsing), P(erase), P(erase_hw), P(flip), P(lut), P(image_m), P(parsing_m),
+                                                          P(erase_m), n, H, W, int(erase.shape[1]), int(erase.shape[2]), _native.stream()))
+    return image_m, parsing_m, mirror_keypoints(keypoints, W, flags), erase_m
+
+
 def upload_images(raw, device):
     """``raw`` with its photographs and label maps (every ``*image`` / ``*parsing`` tensor) on ``device``; key points, names and
     indices stay on the host.  The pair builders stack a batch of ``training.dataset.collate_pairs`` after this, on the device."""
@@ -147,7 +199,7 @@ def shift_keypoints(keypoints, left_padding):
 class FullBodyBatch:
     """The interface TrainingStep.run consumes (as SyntheticFullBodyBatch): ``tensors`` (the nine KEYS), ``batch``, ``split``.
     ``stages`` holds the uint8 intermediates when the builder was asked to keep them; ``image`` is the photographs' uint8 batch
-    [N, H, W, 3] as the builder uploaded it (the reconstruction metric scores against it)."""
+    [N, H, W, 3] as the builder uploaded it (the reconstruction metric scores against it), mirrored where the batch says so."""
     KEYS = ['real_img', 'style_input', 'retain', 'pose', 'denorm_upper_input', 'denorm_lower_input',
             'denorm_upper_mask', 'denorm_lower_mask', 'gt_parsing']
 
@@ -179,6 +231,7 @@ class FullBodyBatchBuilder:
         image, parsing, keypoints = upload_person(raw, dev, 'FullBodyBatchBuilder')
         n, H, W, _ = image.shape
         erase, erase_hw = upload_erase(raw, dev, n)
+        image, parsing, keypoints, erase = mirror_batch(raw, image, parsing, keypoints, erase, erase_hw)
         limbs, joints, quads, present = device_tables(keypoints, keypoints, (H - W) // 2, dev)
         u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)
