@@ -625,6 +625,40 @@ int pasta_tryon_mirror_u8(const uint8_t* image, const uint8_t* parsing, const ui
                           const uint8_t* flip, const uint8_t* lut, uint8_t* image_out, uint8_t* parsing_out, uint8_t* erase_out, int N,
                           int H, int W, int mh_max, int mw_max, void* stream);
 
+/* Jittered people (this project's own rule; --jitter-people of train_wo_flow_fullbody.py, training/tryon_batch.py's
+ * jitter_batch).  A raw sample with jitter parameters is the sample as seen after a similarity map, formed BEFORE any preparation
+ * and after mirroring; everything downstream (stick figure, palm, masks, warps, erase rule, float conversions) is unchanged and
+ * does not know about it.  Canvas: the unpadded H x W image, centre c0 = (cx, cy) = ((W-1)/2, (H-1)/2).  Per item a scale s, an
+ * angle theta (degrees, y pointing down) and a shift t = (tx, ty) in pixels: content at p moves to p' = c0 + s R(theta)(p - c0) + t,
+ * R = [[cos, -sin], [sin, cos]].
+ *   inverse   on the host, in float64 (training.tryon_batch.jitter_affine_q16): x = a x' + b y' + c, y = d x' + e y' + f with
+ *             a = e = cos / s, b = sin / s, d = -sin / s, c = cx - (a (cx + tx) + b (cy + ty)), f = cy - (d (cx + tx) + e (cy + ty));
+ *             sent as int64 Q16, rint(v * 65536): affine[n] = (A, B, C, D, E, F);
+ *   image     for the output pixel (x', y'): X = A x' + B y' + C and Y = D x' + E y' + F in int64 (wrapping);
+ *             Xq = (X + 1024) >> 11 (arithmetic: the coordinate in 1/32 pixel), ix = Xq >> 5, ax = Xq & 31, the same for y; the
+ *             four taps (iy, ix), (iy, ix+1), (iy+1, ix), (iy+1, ix+1), each index clamped into the image (replicated border);
+ *             v = (sum w tap + 512) >> 10 with w = (32-ax)(32-ay), ax (32-ay), (32-ax) ay, ax ay;
+ *   colour    applied to v: colour[n] an int32 [3][4] Q8 matrix M,
+ *             out_c = clamp((M[c][0] R + M[c][1] G + M[c][2] B + M[c][3] + 128) >> 8, 0, 255), the sum in int64
+ *             (training.tryon_batch.jitter_colour_q8: M3 = k (q I + (1 - q) 1 L^T), L = (0.299, 0.587, 0.114), offset
+ *             128 (1 - k) + beta, each rint(v * 256));
+ *   labels    the nearest neighbour from the same X, Y: lx = clamp((X + 32768) >> 16, 0, W-1), ly likewise,
+ *             parsing'[y', x'] = parsing[ly, lx]; no table, a similarity does not exchange sides;
+ *   erase     not touched: the mask is file raw_idx % count of another project's random masks and belongs to the canvas;
+ *   joints    on the host, in float64 (training.tryon_batch.jitter_keypoints): with m00 = m11 = s cos, m01 = -(s sin), m10 = s sin,
+ *             ox = (cx + tx) - (m00 cx + m01 cy), oy = (cy + ty) - (m10 cx + m11 cy), a joint with confidence >= 0.1 becomes
+ *             (m00 x + m01 y + ox, m10 x + m11 y + oy) with its confidence; a joint below 0.1 keeps its three numbers bit for bit;
+ *             rows are not exchanged, a joint off the canvas stays as it is (downstream clamps), and the shift by the padding
+ *             happens afterwards, as before.
+ * The identity (A = E = 65536, the rest 0; M = 256 on the diagonal, the rest 0) returns its input byte for byte under these lines.
+ * This entry is out of place and does a whole batch in one launch: image [N,H,W,3], parsing [N,H,W], affine [N][6] int64 and
+ * colour [N][12] int32 on the device -> image_out, parsing_out of the inputs' shapes.  The numbers are read on the device; an item
+ * whose eighteen numbers are the identity is copied.  A thread owns consecutive output pixels of a row: with W a multiple of 16
+ * and 16-byte aligned tensors 16 of them, stored with 16-byte stores; any other width or address goes pixel by pixel.
+ * Refused before any launch: a null pointer; an output equal to its input; N outside 1..65535, H or W outside 1..16384. */
+int pasta_tryon_jitter_u8(const uint8_t* image, const uint8_t* parsing, const int64_t* affine, const int32_t* colour,
+                          uint8_t* image_out, uint8_t* parsing_out, int N, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the try-on TEST pairs (row f4; UvitonDatasetV19_test._load_raw_image / normalize / __getitem__,
  * training/dataset.py:1085-1525, and test.py:104-150).  Same canvas, restated primitives and exactness as the entries

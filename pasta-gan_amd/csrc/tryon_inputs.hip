@@ -7,7 +7,9 @@
 //                           per-pixel body is csrc/tryon_common.h's train_pixel (the erase rule with the restated resize, then
 //                           tryon_pixel), shared with the 512 x 320 training kernel of csrc/tryon_pairs.hip;
 //   pasta_tryon_mirror_u8   the raw samples of a batch as a mirror shows them (this project's own rule, --mirror-people): the
-//                           photograph, the label map with left and right exchanged and the erase mask, before any of the above.
+//                           photograph, the label map with left and right exchanged and the erase mask, before any of the above;
+//   pasta_tryon_jitter_u8   the raw samples of a batch after a similarity map and a colour map per item (this project's own rule,
+//                           --jitter-people): the photograph resampled from four taps, the label map from the nearest one.
 // The palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702) is csrc/tryon_pairs.hip's pasta_palm_mask_u8.
 // Every entry is its checks and one launch for a whole batch.  The reference does this on the host with OpenCV, pycocotools and
 // skimage.  What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
@@ -195,7 +197,133 @@ __global__ __launch_bounds__(256) void tryon_mirror_kernel(const uint8_t* __rest
     erase_out[base + x] = erase[base + ((f && y < hn && x < wn) ? wn - 1 - x : x)];
 }
 
+// ---- jittered people (this project's own rule: include/pasta_hip.h, pasta_tryon_jitter_u8) ----
+
+// An int64 coordinate held into 0 .. hi: every tap and every label read lies inside its item whatever the six numbers are.
+__device__ __forceinline__ int jitter_clamp(int64_t v, int hi) { return (int)(v < 0 ? 0 : (v > hi ? hi : v)); }
+
+// The photograph's output pixel whose source coordinate is (X, Y) in Q16 -> out[3]: four taps at 1/32 pixel with a replicated
+// border, then the Q8 colour map M[3][4].  img: the item's H x W x 3 bytes.  The sums wrap in 64 bits, as the statement's do.
+__device__ __forceinline__ void jitter_photo_pixel(const uint8_t* __restrict__ img, int H, int W, uint64_t X, uint64_t Y, const int32_t* M,
+                                                   uint32_t* out) {
+    const int64_t Xq = (int64_t)(X + 1024u) >> 11, Yq = (int64_t)(Y + 1024u) >> 11;
+    const int ax = (int)(Xq & 31), ay = (int)(Yq & 31);
+    const int64_t ix = Xq >> 5, iy = Yq >> 5;
+    const int x0 = jitter_clamp(ix, W - 1), x1 = jitter_clamp(ix + 1, W - 1);
+    const int y0 = jitter_clamp(iy, H - 1), y1 = jitter_clamp(iy + 1, H - 1);
+    const uint8_t* p00 = img + (y0 * W + x0) * 3;        // < 16384 * 16384 * 3: an int
+    const uint8_t* p01 = img + (y0 * W + x1) * 3;
+    const uint8_t* p10 = img + (y1 * W + x0) * 3;
+    const uint8_t* p11 = img + (y1 * W + x1) * 3;
+    const int w00 = (32 - ax) * (32 - ay), w01 = ax * (32 - ay), w10 = (32 - ax) * ay, w11 = ax * ay;
+    int v[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = (w00 * p00[c] + w01 * p01[c] + w10 * p10[c] + w11 * p11[c] + 512) >> 10;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int64_t m = ((int64_t)M[4 * c] * v[0] + (int64_t)M[4 * c + 1] * v[1] + (int64_t)M[4 * c + 2] * v[2] + M[4 * c + 3] + 128) >> 8;
+        out[c] = (uint32_t)(m < 0 ? 0 : (m > 255 ? 255 : m));
+    }
+}
+
+// One launch for a batch: item n = blockIdx.y; its threads are the image's units, then the label map's units.  A unit is PX
+// consecutive output pixels of a row, gathered through the cache and stored together.  WIDE (W % 16 == 0, 16-byte aligned
+// tensors): 16 pixels, three 16-byte stores of the image and one of the labels.  Otherwise one pixel, byte stores.  The six and
+// twelve numbers of the item are uniform over the workgroup (scalar loads); an item whose numbers are the identity is copied.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void tryon_jitter_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ parsing,
+                                                           const int64_t* __restrict__ affine, const int32_t* __restrict__ colour,
+                                                           uint8_t* __restrict__ image_out, uint8_t* __restrict__ parsing_out, int H, int W) {
+    constexpr int PX = WIDE ? 16 : 1;
+    const int n = blockIdx.y;
+    const int64_t* q = affine + (int64_t)n * 6;
+    const uint64_t A = (uint64_t)q[0], B = (uint64_t)q[1], C = (uint64_t)q[2], D = (uint64_t)q[3], E = (uint64_t)q[4], F = (uint64_t)q[5];
+    int32_t M[12];
+    bool same = A == 65536u && B == 0 && C == 0 && D == 0 && E == 65536u && F == 0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        M[k] = colour[(int64_t)n * 12 + k];
+        same = same && M[k] == (k % 5 == 0 ? 256 : 0);
+    }
+    const int cw = W / PX, units = H * cw;
+    int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2 * units) return;
+    const bool labels = t >= units;
+    if (labels) t -= units;
+    const int y = t / cw, x0 = (t - y * cw) * PX;
+    const int64_t item = (int64_t)n * H * W, at = item + (int64_t)y * W + x0;
+    uint64_t X = A * (uint64_t)x0 + B * (uint64_t)y + C, Y = D * (uint64_t)x0 + E * (uint64_t)y + F;
+    if (!labels) {
+        const uint8_t* img = image + item * 3;
+        if constexpr (WIDE) {
+            uint4* d = reinterpret_cast<uint4*>(image_out + at * 3);
+            if (same) {
+                const uint4* s = reinterpret_cast<const uint4*>(image + at * 3);
+                const uint4 a = s[0], b = s[1], c = s[2];
+                d[0] = a; d[1] = b; d[2] = c;
+                return;
+            }
+            uint32_t o[12];
+#pragma unroll
+            for (int k = 0; k < 12; k++) o[k] = 0;
+#pragma unroll
+            for (int p = 0; p < 16; p++, X += A, Y += D) {
+                uint32_t px[3];
+                jitter_photo_pixel(img, H, W, X, Y, M, px);
+#pragma unroll
+                for (int c = 0; c < 3; c++) o[(3 * p + c) >> 2] |= px[c] << (8 * ((3 * p + c) & 3));
+            }
+            d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+            d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+            d[2] = make_uint4(o[8], o[9], o[10], o[11]);
+        } else {
+            uint32_t px[3];
+            if (same) {
+                for (int c = 0; c < 3; c++) px[c] = image[at * 3 + c];
+            } else {
+                jitter_photo_pixel(img, H, W, X, Y, M, px);
+            }
+            for (int c = 0; c < 3; c++) image_out[at * 3 + c] = (uint8_t)px[c];
+        }
+        return;
+    }
+    const uint8_t* lab = parsing + item;
+    if constexpr (WIDE) {
+        uint4* d = reinterpret_cast<uint4*>(parsing_out + at);
+        if (same) { *d = *reinterpret_cast<const uint4*>(parsing + at); return; }
+        uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int p = 0; p < 16; p++, X += A, Y += D) {
+            const int lx = jitter_clamp((int64_t)(X + 32768u) >> 16, W - 1), ly = jitter_clamp((int64_t)(Y + 32768u) >> 16, H - 1);
+            o[p >> 2] |= (uint32_t)lab[ly * W + lx] << (8 * (p & 3));
+        }
+        *d = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+        const int lx = jitter_clamp((int64_t)(X + 32768u) >> 16, W - 1), ly = jitter_clamp((int64_t)(Y + 32768u) >> 16, H - 1);
+        parsing_out[at] = same ? parsing[at] : lab[ly * W + lx];
+    }
+}
+
 }  // namespace pasta
+
+extern "C" int pasta_tryon_jitter_u8(const uint8_t* image, const uint8_t* parsing, const int64_t* affine, const int32_t* colour,
+                                     uint8_t* image_out, uint8_t* parsing_out, int N, int H, int W, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(image && parsing && affine && colour && image_out && parsing_out, "tryon_jitter_u8: null pointer");
+    PASTA_CHECK(image_out != image && parsing_out != parsing, "tryon_jitter_u8: an output is its input (the entry is out of place)");
+    PASTA_CHECK(N >= 1 && N <= 65535 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "tryon_jitter_u8: bad shape (N %d, %d x %d)", N, H, W);
+    const uintptr_t all = (uintptr_t)image | (uintptr_t)parsing | (uintptr_t)image_out | (uintptr_t)parsing_out;
+    const bool wide = W % 16 == 0 && all % 16 == 0;
+    const int64_t threads = 2 * (int64_t)H * (W / (wide ? 16 : 1));                             // <= 2^29: an int in the kernel
+    dim3 grid((unsigned)((threads + 255) / 256), (unsigned)N);
+    if (wide)
+        hipLaunchKernelGGL(tryon_jitter_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, affine, colour, image_out,
+                           parsing_out, H, W);
+    else
+        hipLaunchKernelGGL(tryon_jitter_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, image, parsing, affine, colour, image_out,
+                           parsing_out, H, W);
+    return launch_status("tryon_jitter_u8");
+}
 
 extern "C" int pasta_tryon_mirror_u8(const uint8_t* image, const uint8_t* parsing, const uint8_t* erase_masks, const int32_t* erase_hw,
                                      const uint8_t* flip, const uint8_t* lut, uint8_t* image_out, uint8_t* parsing_out,

@@ -238,6 +238,7 @@ ABI = {
     'pasta_tryon_masks_u8': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 3 + [_c_ptr]),
     'pasta_tryon_assemble': (ctypes.c_int, [_c_ptr] * 11 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 9 + [_c_ptr]),
     'pasta_tryon_mirror_u8': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 5 + [_c_ptr]),
+    'pasta_tryon_jitter_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 3 + [_c_ptr]),
     'pasta_tryon_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 4 + [_c_ptr]),
     'pasta_patch_composite_eroded_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 7 + [_c_ptr] * 2),
     'pasta_tryon_outfit_assemble': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 7 + [_c_ptr]),
@@ -263,11 +264,12 @@ ABI = {
 # Entries added to the current ABI after its first release (purely additive, so the version did not move): a library built before
 # them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  At 22: the PNG
 # encoder's four entries (csrc/png_encode.hip), pasta_images_keep_to_u8 and pasta_photo_paste_mask_u8 (csrc/tryon_pairs.hip), the five
-# entries of the input-activation mask (pasta_act_mask: csrc/conv_igemm.hip, csrc/upfirdn2d.hip; pasta_bias_sum_db: csrc/bias_act.hip) and
-# pasta_tryon_mirror_u8 (csrc/tryon_inputs.hip).
+# entries of the input-activation mask (pasta_act_mask: csrc/conv_igemm.hip, csrc/upfirdn2d.hip; pasta_bias_sum_db: csrc/bias_act.hip),
+# pasta_tryon_mirror_u8 and pasta_tryon_jitter_u8 (csrc/tryon_inputs.hip).
 LATE_ENTRIES = frozenset(['pasta_png_filter', 'pasta_png_code_lengths', 'pasta_png_segment_tables', 'pasta_png_encode',
                           'pasta_images_keep_to_u8', 'pasta_photo_paste_mask_u8', 'pasta_conv2d_masked', 'pasta_conv2d_mask_available', 'pasta_upfirdn2d_masked',
-                          'pasta_upfirdn2d_mask_available', 'pasta_bias_sum_db', 'pasta_tryon_mirror_u8'])
+                          'pasta_upfirdn2d_mask_available', 'pasta_bias_sum_db', 'pasta_tryon_mirror_u8',
+                          'pasta_tryon_jitter_u8'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

@@ -18,6 +18,11 @@ the options the state file recorded:
 reversed, left and right labels and joints exchanged, per batch on the GPU before the preparation (the reference's
 ``--mirror`` stays refused).
 
+``--jitter-people=scale=0.1,rotate=5,shift=0.03,colour=0.2`` trains on every person under a random similarity map (scale, rotation,
+shift) and colour change, drawn anew at every visit from the run's seed and the sample's position in the sampler's stream, and
+resampled per batch on the GPU before the preparation, after the mirroring.  The sample grid and the metrics see the
+people as photographed.
+
 ``--storage=bf16`` (or ``f16``) keeps the activations of G and of every block of D in that type; parameters, demodulation,
 statistics, the images and the loss stay fp32.
 """
@@ -50,11 +55,32 @@ UNSUPPORTED_CFGS = ('paper256', 'paper512', 'paper1024', 'cifar')
 STORAGE_DTYPES = {None: None, 'f32': None, 'bf16': 'bfloat16', 'f16': 'float16'}      # --storage -> fashion_config's act_dtype
 SUPPORTED_METRICS = ('recon_full', 'recon2k')       # metrics/metric_main.py; the reference's detector metrics are refused
 
+def parse_jitter_people(text):
+    """``--jitter-people``'s SPEC, comma-separated ``name=value`` pairs -> the specification ``training_loop(people_jitter=)``
+    takes: all four names (scale 0..0.5, rotate 0..45 degrees, shift 0..0.25 of the canvas side, colour 0..0.5), absent ones 0."""
+    from training.tryon_batch import jitter_spec
+    spec = {}
+    for pair in text.split(','):
+        name, eq, value = pair.partition('=')
+        name = name.strip()
+        if not eq or not name:
+            raise UserError(f'--jitter-people: {pair!r} is not name=value')
+        if name in spec:
+            raise UserError(f'--jitter-people: {name} is given twice')
+        try:
+            spec[name] = float(value)
+        except ValueError:
+            raise UserError(f'--jitter-people: {name}={value.strip()} is not a number')
+    try:
+        return jitter_spec(spec)
+    except ValueError as err:
+        raise UserError(f'--jitter-people: {err}')
+
 def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=None, seed=None, data=None, cond=None, subset=None, mirror=None, cfg=None,
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
-                               mirror_people=None):
+                               mirror_people=None, jitter_people=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -122,6 +148,11 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     if mirror_people:
         desc += '-mirrorpeople'
         args.training_set_kwargs.mirror_people = True
+    # --jitter-people (own option): a random scale, rotation, shift and colour change per person and visit, resampled per batch on
+    # the GPU after the mirroring.  An argument of the loop, not of the data set: the sample grid and the scores build without it
+    if jitter_people is not None:
+        desc += '-jitterpeople'
+        args.people_jitter = dnnlib.EasyDict(parse_jitter_people(jitter_people))
 
     # Base config: cfg, gamma, kimg, batch (:161-246)
     cfg = 'auto' if cfg is None else cfg
@@ -278,7 +309,7 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         recorded = {'gpus': args.num_gpus, 'batch': args.batch_size}.get(name)
         if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
             continue
-        option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people'}.get(name, name)
+        option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people', 'jitter_people': 'jitter-people'}.get(name, name)
         raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
                         (f' ({recorded})' if recorded is not None else ''))
 
@@ -397,6 +428,8 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--subset', help='Train with only N images [default: all]', type=int, metavar='INT')
 @click.option('--mirror', help='Not supported [default: false]', type=bool, metavar='BOOL')
 @click.option('--mirror-people', help='Train on every person a second time, mirrored on the GPU [default: false]', type=bool, metavar='BOOL')
+@click.option('--jitter-people', help='Train on people jittered on the GPU: comma-separated scale=0..0.5, rotate=0..45 (degrees), '
+              'shift=0..0.25 (of the canvas side), colour=0..0.5 [default: none]', metavar='SPEC')
 # Base config.
 @click.option('--cfg', help='Base config [default: auto]', type=click.Choice(list(CFG_SPECS) + list(UNSUPPORTED_CFGS)))
 @click.option('--gamma', help='Override R1 gamma', type=float)
@@ -456,6 +489,8 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
     print(f'Number of GPUs:     {args.num_gpus}')
     print(f'Number of images:   {args.training_set_kwargs.max_size}')
     print(f'Mirrored people:    {bool(args.training_set_kwargs.get("mirror_people", False))}')
+    jitter = args.get('people_jitter')
+    print(f'Jittered people:    {",".join(f"{k}={v:g}" for k, v in jitter.items()) if jitter else False}')
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

@@ -12,12 +12,17 @@ and, before them, for a batch of a data set opened with ``mirror_people`` that h
 
     pasta_tryon_mirror_u8    photograph, label map (left and right exchanged) and erase mask as a mirror shows them
 
+and after that, for a batch the training loop has numbered for ``--jitter-people`` (``jitter_batch``):
+
+    pasta_tryon_jitter_u8    photograph and label map after a similarity map per item, the photograph through a colour map
+
 The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
 ``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
-masks), ``mirror_batch`` (the training sets' mirrored people), ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their
-pointer array) and ``shift_keypoints``.
+masks), ``mirror_batch`` (the training sets' mirrored people), ``jitter_batch`` (their jittered people), ``device_tables`` (stick
+and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their pointer array) and
+``shift_keypoints``.
 ``builder_for`` picks the training builder of a data set: this one, or training/tryon_regions.py's at 512 x 320."""
 
 import ctypes
@@ -41,6 +46,10 @@ PALM_BOXES = (25, 16)               # get_hand_mask of the training set: upper a
 # A mirrored person (this project's own rule, include/pasta_hip.h: pasta_tryon_mirror_u8): the labels and the joints that change sides
 MIRROR_LABELS = ((14, 15), (16, 17), (18, 19))          # arms, legs, shoes
 MIRROR_JOINTS = ((2, 5), (3, 6), (4, 7), (8, 11), (9, 12), (10, 13), (14, 15), (16, 17))   # shoulders .. ankles, eyes, ears
+# A jittered person (this project's own rule, include/pasta_hip.h: pasta_tryon_jitter_u8): the strengths of a specification with
+# the top of their ranges (rotate in degrees, shift as a fraction of the canvas side), and the luma weights of the saturation
+JITTER_RANGES = dict(scale=0.5, rotate=45.0, shift=0.25, colour=0.5)
+JITTER_LUMA = (0.299, 0.587, 0.114)
 
 
 def stick_tables(keypoints):
@@ -159,6 +168,116 @@ def mirror_batch(raw, image, parsing, keypoints, erase, erase_hw):
     return image_m, parsing_m, mirror_keypoints(keypoints, W, flags), erase_m
 
 
+def jitter_spec(spec):
+    """A jitter specification -> a dict of all four JITTER_RANGES names as floats (absent names are 0), checked: a ValueError
+    names an unknown name, a value outside its range, or a specification without a positive value."""
+    spec = dict(spec)
+    for name in spec:
+        if name not in JITTER_RANGES:
+            raise ValueError(f'unknown name {name!r} (known: {", ".join(JITTER_RANGES)})')
+    out = {}
+    for name, top in JITTER_RANGES.items():
+        value = float(spec.get(name, 0.0))
+        if not 0.0 <= value <= top:          # a NaN fails too
+            raise ValueError(f'{name}={spec[name]} is outside 0..{top:g}')
+        out[name] = value
+    if not any(v > 0 for v in out.values()):
+        raise ValueError('no positive value: ' + ','.join(f'{k}={v:g}' for k, v in out.items()))
+    return out
+
+
+def jitter_uniforms(seed, position):
+    """The seven uniforms on (-1, 1) of stream position ``position`` of the run seeded ``seed``: from the raw 64-bit outputs of
+    ``np.random.PCG64(np.random.SeedSequence((seed, position)))``, whose stream numpy guarantees, as (raw >> 11) * 2^-52 - 1."""
+    raw = np.random.PCG64(np.random.SeedSequence((int(seed), int(position)))).random_raw(7)
+    return (raw >> np.uint64(11)).astype(np.float64) * 2.0 ** -52 - 1.0
+
+
+def jitter_parameters(spec, seed, positions, H, W):
+    """(geometry float64 [N, 4] = s, theta in degrees, tx, ty in pixels; colour float64 [N, 3] = contrast k, saturation q,
+    brightness beta) of the items at ``positions`` of the sampler's global stream.  A draw depends on (seed, position) alone, and
+    all seven uniforms are drawn in this order whichever strengths are zero."""
+    spec = jitter_spec(spec)
+    positions = np.asarray(positions, np.int64).reshape(-1)
+    geometry, colour = np.zeros([len(positions), 4]), np.zeros([len(positions), 3])
+    for i, t in enumerate(positions.tolist()):
+        u = [float(v) for v in jitter_uniforms(seed, t)]
+        geometry[i] = (1.0 + spec['scale']) ** u[0], spec['rotate'] * u[1], spec['shift'] * W * u[2], spec['shift'] * H * u[3]
+        colour[i] = (1.0 + spec['colour']) ** u[4], (1.0 + spec['colour']) ** u[5], 64.0 * spec['colour'] * u[6]
+    return geometry, colour
+
+
+def _jitter_rotation(theta):
+    r = math.radians(theta)
+    return math.cos(r), math.sin(r)
+
+
+def jitter_affine_q16(geometry, H, W):
+    """geometry float64 [N, 4] -> int64 [N, 6]: the INVERSE map (A, B, C, D, E, F) of include/pasta_hip.h in Q16."""
+    geometry = np.asarray(geometry, np.float64).reshape(-1, 4)
+    cx, cy = (W - 1) / 2, (H - 1) / 2
+    out = np.zeros([len(geometry), 6], np.int64)
+    for i, (s, theta, tx, ty) in enumerate(geometry.tolist()):
+        cos, sin = _jitter_rotation(theta)
+        a, b, d, e = cos / s, sin / s, -sin / s, cos / s
+        c = cx - (a * (cx + tx) + b * (cy + ty))
+        f = cy - (d * (cx + tx) + e * (cy + ty))
+        out[i] = [int(np.rint(v * 65536.0)) for v in (a, b, c, d, e, f)]
+    return out
+
+
+def jitter_colour_q8(colour):
+    """colour float64 [N, 3] = k, q, beta -> int32 [N, 12]: M3 = k (q I + (1 - q) 1 L^T) and the offset 128 (1 - k) + beta as the
+    rows (M[c][0..2], offset) of include/pasta_hip.h's matrix in Q8."""
+    k, q, beta = (np.asarray(colour, np.float64).reshape(-1, 3)[:, i, None, None] for i in range(3))
+    m3 = k * (q * np.eye(3) + (1.0 - q) * np.asarray(JITTER_LUMA)) * 256.0                       # [N, 3, 3], term by term as stated
+    offset = np.broadcast_to((128.0 * (1.0 - k) + beta) * 256.0, [len(m3), 3, 1])
+    return np.ascontiguousarray(np.rint(np.concatenate([m3, offset], axis=2)).astype(np.int32).reshape(-1, 12))
+
+
+def jitter_keypoints(keypoints, geometry, H, W):
+    """[N, 18, 3] key points of the UNPADDED ``H x W`` canvas -> a float64 copy in which every joint with confidence >= 0.1 has
+    moved where the content moves (include/pasta_hip.h: ``joints``), its confidence kept; a joint below 0.1 keeps its bits."""
+    kp = np.asarray(keypoints, np.float64).copy()
+    geometry = np.asarray(geometry, np.float64).reshape(-1, 4)
+    assert kp.ndim == 3 and kp.shape[1:] == (18, 3) and len(geometry) == kp.shape[0]
+    cx, cy = (W - 1) / 2, (H - 1) / 2
+    rotation = np.array([_jitter_rotation(theta) for theta in geometry[:, 1].tolist()]).reshape(-1, 2)
+    s, cos, sin, tx, ty = (v[:, None] for v in (geometry[:, 0], rotation[:, 0], rotation[:, 1], geometry[:, 2], geometry[:, 3]))
+    m00, m01, m10, m11 = s * cos, -(s * sin), s * sin, s * cos
+    ox = (cx + tx) - (m00 * cx + m01 * cy)
+    oy = (cy + ty) - (m10 * cx + m11 * cy)
+    seen = kp[..., 2] >= 0.1
+    x, y = kp[..., 0].copy(), kp[..., 1].copy()
+    with np.errstate(all='ignore'):                  # the unseen joints' numbers may be anything; they are not used
+        kp[..., 0] = np.where(seen, m00 * x + m01 * y + ox, x)
+        kp[..., 1] = np.where(seen, m10 * x + m11 * y + oy, y)
+    return kp
+
+
+def jitter_batch(raw, image, parsing, keypoints):
+    """What both training builders call straight after ``mirror_batch``: (image, parsing, keypoints) of the people as
+    ``raw['jitter']`` (``spec``, ``seed``, int64 ``positions`` [N]; attached by the training loop's ``_data_batches``) jitters
+    them, in one launch for the batch (pasta_tryon_jitter_u8) and ``jitter_keypoints`` on the host.  A batch without ``jitter``
+    comes back as it is and launches nothing."""
+    if 'jitter' not in raw:
+        return image, parsing, keypoints
+    jitter = raw['jitter']
+    n, H, W, _ = image.shape
+    positions = np.asarray(jitter['positions'], np.int64)
+    assert positions.shape == (n,)
+    geometry, colour = jitter_parameters(jitter['spec'], jitter['seed'], positions, H, W)
+    dev = image.device
+    affine = torch.from_numpy(jitter_affine_q16(geometry, H, W)).to(dev, non_blocking=True)
+    matrix = torch.from_numpy(jitter_colour_q8(colour)).to(dev, non_blocking=True)
+    image_j, parsing_j = torch.empty_like(image), torch.empty_like(parsing)
+    P = _native.ptr
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().pasta_tryon_jitter_u8(P(image), P(parsing), P(affine), P(matrix), P(image_j), P(parsing_j), n, H, W,
+                                                          _native.stream()))
+    return image_j, parsing_j, jitter_keypoints(keypoints, geometry, H, W)
+
+
 def upload_images(raw, device):
     """``raw`` with its photographs and label maps (every ``*image`` / ``*parsing`` tensor) on ``device``; key points, names and
     indices stay on the host.  The pair builders stack a batch of ``training.dataset.collate_pairs`` after this, on the device."""
@@ -199,7 +318,7 @@ def shift_keypoints(keypoints, left_padding):
 class FullBodyBatch:
     """The interface TrainingStep.run consumes (as SyntheticFullBodyBatch): ``tensors`` (the nine KEYS), ``batch``, ``split``.
     ``stages`` holds the uint8 intermediates when the builder was asked to keep them; ``image`` is the photographs' uint8 batch
-    [N, H, W, 3] as the builder uploaded it (the reconstruction metric scores against it), mirrored where the batch says so."""
+    [N, H, W, 3] as the builder uploaded it (the reconstruction metric scores against it), mirrored and jittered where the batch says so."""
     KEYS = ['real_img', 'style_input', 'retain', 'pose', 'denorm_upper_input', 'denorm_lower_input',
             'denorm_upper_mask', 'denorm_lower_mask', 'gt_parsing']
 
@@ -232,6 +351,7 @@ class FullBodyBatchBuilder:
         n, H, W, _ = image.shape
         erase, erase_hw = upload_erase(raw, dev, n)
         image, parsing, keypoints, erase = mirror_batch(raw, image, parsing, keypoints, erase, erase_hw)
+        image, parsing, keypoints = jitter_batch(raw, image, parsing, keypoints)
         limbs, joints, quads, present = device_tables(keypoints, keypoints, (H - W) // 2, dev)
         u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)

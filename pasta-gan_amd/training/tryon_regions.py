@@ -26,6 +26,7 @@ test_512.py will later feed it.  A sample is the full-body preparation above of 
 training set's photograph as target, ``gt_parsing`` and erase mask (include/pasta_hip.h lists the rules):
 
     pasta_tryon_mirror_u8                 the mirrored people of a ``mirror_people`` batch (training/tryon_batch.py, mirror_batch)
+    pasta_tryon_jitter_u8                 the jittered people of a numbered batch (training/tryon_batch.py, jitter_batch)
     pasta_pose_stickman_u8, pasta_palm_mask_u8     as above
     pasta_tryon_masks_u8                  retain mask, gt_parsing and the person's own two garments in one pass, the 256 set's entry
     patch_pipeline.normalize_outfit_batch everyone their own donor: N solves; the eroded part masks of the upper composite kept
@@ -37,7 +38,7 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import pairs_batch_as_outfits
-from training.tryon_batch import (OUTFIT_OUTPUTS, FullBodyBatch, allocator, device_tables, mirror_batch, output_tensors, shift_keypoints,
+from training.tryon_batch import (OUTFIT_OUTPUTS, FullBodyBatch, allocator, device_tables, jitter_batch, mirror_batch, output_tensors, shift_keypoints,
                                   upload_erase, upload_images, upload_person)
 from training.tryon_pairs import TryOnPairBatch
 
@@ -187,6 +188,7 @@ class FullBodyRegionBatchBuilder:
         lp = (H - W) // 2
         erase, erase_hw = upload_erase(raw, dev, n)
         image, parsing, kp, erase = mirror_batch(raw, image, parsing, kp, erase, erase_hw)
+        image, parsing, kp = jitter_batch(raw, image, parsing, kp)
         limbs, joints, quads, present = device_tables(kp, kp, lp, dev)
         u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)
