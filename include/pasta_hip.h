@@ -917,6 +917,42 @@ int pasta_parsing_confusion(const float* logits, const float* labels, int64_t* m
                             void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The SSIM term of the generator's loss (torch_utils/ops/ssim_loss.py; csrc/ssim_loss.hip): the structural figure
+ * the reconstruction metric reports, in a form that can be trained on.
+ * x (generated) and y (photograph): [N, 3, H, Wt] fp32 as the networks produce them -- values v of nominally [-1, 1], taken as
+ * intensities v + 1 of dynamic range L = 2, NOT clipped and NOT quantised; only the content columns c0 .. c0 + W - 1 are read.
+ * Per channel and per valid position of the 11 x 11 Gaussian window of pasta_recon_image_stats (sigma 1.5, the same fp32
+ * weights w), (H - 10) (W - 10) of them:
+ *   mx = E[x] + 1, my = E[y] + 1, sxx = E[xx] - E[x]^2, syy = E[yy] - E[y]^2, sxy = E[xy] - E[x] E[y],
+ *   a1 = 2 mx my + C1, a2 = 2 sxy + C2, b1 = mx^2 + my^2 + C1, b2 = sxx + syy + C2, C1 = (0.01 L)^2 = 4e-4, C2 = (0.03 L)^2 = 3.6e-3,
+ *   S = a1 a2 / (b1 b2),      loss = 1 - (sum of S) / M,  M = N 3 (H - 10) (W - 10).
+ * The intensities are the bytes the metric scores up to a scale, b = (v + 1) * 127.5, and SSIM does not change under a scaling
+ * when the constants scale with L^2 (under a shift it does, hence the means of v + 1 and not of v): on images that lie on the
+ * byte grid, 1 - loss is the mean of pasta_recon_image_stats' ssim / windows.  Anywhere else the two differ: the metric scores
+ * clipped bytes.
+ * Gradient with respect to x only.  Per position: dS/dmx = 2 my a2 / (b1 b2) - 2 mx S / b1, B = dS/dsxx = -S / b2,
+ * C = dS/dsxy = 2 a1 / (b1 b2), A = dS/dmx - 2 mx B - my C; per pixel q
+ *   dloss/dx[q] = -(1 / M) ((w (*) A)[q] + 2 (x[q] + 1) (w (*) B)[q] + (y[q] + 1) (w (*) C)[q]),
+ *   (w (*) F)[q] = sum over the valid positions p with q - 10 <= p <= q (per axis) of w[q - p] F[p].
+ * Evaluated in fp32 with both images of a tile of positions centred on the photograph's value at the tile's first pixel (the
+ * second moments do not depend on the shift and near white no longer cancel from 1); the sum of S in fp64, one partial per
+ * workgroup and a fixed-order second launch, no floating-point atomics: two calls on the same input give the same bits.
+ * ------------------------------------------------------------------------- */
+/* Bytes of the partials of pasta_ssim_loss; 0 for a shape that is refused. */
+int64_t pasta_ssim_loss_workspace(int N, int H, int W);
+/* loss: one fp32 in device memory.  dmaps: null for the value alone, else [N, 3, 3, H - 10, W - 10] fp32, what
+ * pasta_ssim_loss_backward gathers from (A relative to the tile's shift, B, C per position); it is only meaningful to that entry
+ * with the same x and y.  H >= 11, W >= 11, N <= 65535, H and Wt <= 4096, c0 + W <= Wt. */
+int pasta_ssim_loss(const float* x, const float* y, float* loss, float* dmaps /* null: value only */, void* workspace,
+                    int64_t workspace_bytes, int N, int H, int Wt, int c0, int W, void* stream);
+/* dx [N, 3, H, Wt] = *grad_loss * dloss/dx, written everywhere: exactly 0 outside the content columns.  grad_loss is ONE fp32 in
+ * device memory (the loss weight times the gain), read by the kernel: nothing waits for the host.  Gather form, every element
+ * written by one thread: a run repeats to the bit. */
+int pasta_ssim_loss_backward(const float* x, const float* y, const float* dmaps, const float* grad_loss /* device scalar */,
+                             float* dx /* [N,3,H,Wt], written everywhere, 0 outside the crop */, int N, int H, int Wt, int c0, int W,
+                             void* stream);
+
+/* ------------------------------------------------------------------------- *
  * PNG files of a batch of RGB8 images, encoded on the GPU (torch_utils/ops/png_encode.py; csrc/png_encode.hip).
  * The stream is this project's own choice of a valid PNG:
  *   1. every row is filter type 4 (Paeth, bpp 3) with left, up and upper-left taken from the ORIGINAL pixels, zero outside the

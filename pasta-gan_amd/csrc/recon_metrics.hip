@@ -9,29 +9,17 @@
 // Only the content columns c0 .. c0 + W - 1 of the padded square are scored.
 #include <type_traits>
 
+#include "recon_window.h"
 #include "tryon_common.h"
 
 namespace pasta {
 
 // ---- image statistics ----
 
-constexpr int RS_K = 11, RS_R = RS_K - 1;       // window and halo
-constexpr int RS_TW = 32, RS_TH = 22;           // SSIM positions per workgroup: 22 rows of 32
-constexpr int RS_IW = RS_TW + RS_R;             // 42 staged columns
-constexpr int RS_IH = RS_TH + RS_R;             // 32 staged rows: 32 rows x 8 groups of four columns = 256 threads in the row pass
-constexpr int RS_LD = RS_IW + 1;                // 43: odd, so the four rows a half-wave reads in the row pass fall on different banks
-constexpr int RS_MAPS = 5;                      // E[a], E[b], E[aa], E[bb], E[ab]
-
-struct ReconWeights { float w[RS_K]; };
 struct ReconPartial { double ssim; int64_t sad, ssd; };
 struct RegionPartial { double ssim; int64_t sad, ssd, windows, bytes; };
 template <bool MASKED> using PartialOf = std::conditional_t<MASKED, RegionPartial, ReconPartial>;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -262,24 +250,10 @@ __global__ __launch_bounds__(256) void parsing_confusion_kernel(const float* __r
 
 }  // namespace pasta
 
-static int recon_tiles(int extent, int tile) { return (extent - pasta::RS_R + tile - 1) / tile; }
-
 extern "C" int64_t pasta_recon_image_stats_workspace(int N, int H, int W) {
     using namespace pasta;
     if (N < 1 || H < RS_K || W < RS_K) return 0;
     return (int64_t)N * 3 * recon_tiles(W, RS_TW) * recon_tiles(H, RS_TH) * (int64_t)sizeof(ReconPartial);
-}
-
-static pasta::ReconWeights recon_weights() {
-    using namespace pasta;
-    // the Gaussian in fp64, normalised; after the rounding to fp32 the centre weight takes up what the sum lacks of 1
-    ReconWeights gw;
-    double g[RS_K], total = 0.0;
-    for (int k = 0; k < RS_K; k++) { g[k] = exp(-0.5 * (k - RS_K / 2) * (k - RS_K / 2) / (1.5 * 1.5)); total += g[k]; }
-    double rest = 0.0;
-    for (int k = 0; k < RS_K; k++) { gw.w[k] = (float)(g[k] / total); if (k != RS_K / 2) rest += (double)gw.w[k]; }
-    gw.w[RS_K / 2] = (float)(1.0 - rest);
-    return gw;
 }
 
 extern "C" int pasta_recon_image_stats(const float* images, const uint8_t* photos, int64_t* sums, double* ssim, void* workspace,

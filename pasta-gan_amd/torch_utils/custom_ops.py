@@ -259,17 +259,20 @@ ABI = {
     'pasta_png_code_lengths': (ctypes.c_int, [_c_ptr, ctypes.c_int, ctypes.c_int, _c_ptr]),
     'pasta_png_segment_tables': (ctypes.c_int, [_c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'pasta_png_encode': (ctypes.c_int, [_c_ptr] * 4 + [_c_i64] + [ctypes.c_int] * 3 + [_c_ptr]),
+    'pasta_ssim_loss_workspace': (_c_i64, [ctypes.c_int] * 3),
+    'pasta_ssim_loss': (ctypes.c_int, [_c_ptr] * 5 + [_c_i64] + [ctypes.c_int] * 5 + [_c_ptr]),
+    'pasta_ssim_loss_backward': (ctypes.c_int, [_c_ptr] * 5 + [ctypes.c_int] * 5 + [_c_ptr]),
 }
 
 # Entries added to the current ABI after its first release (purely additive, so the version did not move): a library built before
 # them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  At 22: the PNG
 # encoder's four entries (csrc/png_encode.hip), pasta_images_keep_to_u8 and pasta_photo_paste_mask_u8 (csrc/tryon_pairs.hip), the five
 # entries of the input-activation mask (pasta_act_mask: csrc/conv_igemm.hip, csrc/upfirdn2d.hip; pasta_bias_sum_db: csrc/bias_act.hip),
-# pasta_tryon_mirror_u8 and pasta_tryon_jitter_u8 (csrc/tryon_inputs.hip).
+# pasta_tryon_mirror_u8 and pasta_tryon_jitter_u8 (csrc/tryon_inputs.hip), the three entries of the SSIM loss (csrc/ssim_loss.hip).
 LATE_ENTRIES = frozenset(['pasta_png_filter', 'pasta_png_code_lengths', 'pasta_png_segment_tables', 'pasta_png_encode',
                           'pasta_images_keep_to_u8', 'pasta_photo_paste_mask_u8', 'pasta_conv2d_masked', 'pasta_conv2d_mask_available', 'pasta_upfirdn2d_masked',
                           'pasta_upfirdn2d_mask_available', 'pasta_bias_sum_db', 'pasta_tryon_mirror_u8',
-                          'pasta_tryon_jitter_u8'])
+                          'pasta_tryon_jitter_u8', 'pasta_ssim_loss_workspace', 'pasta_ssim_loss', 'pasta_ssim_loss_backward'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

@@ -23,6 +23,9 @@ shift) and colour change, drawn anew at every visit from the run's seed and the 
 resampled per batch on the GPU before the preparation, after the mirroring.  The sample grid and the metrics see the
 people as photographed.
 
+``--ssim_weight=5`` adds ``5 * (1 - mean SSIM)`` of each of the generator's two images against the photograph to its loss: the
+windows and constants ``recon_full`` reports, on the un-quantised images, value and gradient on the GPU.
+
 ``--storage=bf16`` (or ``f16``) keeps the activations of G and of every block of D in that type; parameters, demodulation,
 statistics, the images and the loss stay fp32.
 """
@@ -80,7 +83,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
-                               mirror_people=None, jitter_people=None):
+                               mirror_people=None, jitter_people=None, ssim_weight=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -113,6 +116,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         args.training_set_kwargs.resolution = training_set.resolution
         args.training_set_kwargs.max_size = len(training_set)
         desc = training_set.name
+        content_width = training_set.content_width
         del training_set
     except IOError as err:
         raise UserError(f'--data: {err}')
@@ -184,6 +188,12 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     config.G_opt_kwargs.lr = config.D_opt_kwargs.lr = spec.lrate
     config.loss_kwargs.update(r1_gamma=spec.gamma, l1_weight=l1_weight or 0, vgg_weight=vgg_weight or 0, pl_weight=pl_weight or 0,
                               contextual_weight=contextual_weight or 0, mask_weight=mask_weight or 0)
+    # --ssim_weight (own option): 1 - mean SSIM of both generated images against the photograph, over the content columns the
+    # batch builder pads from.  Absent or 0 adds no key: the recorded options of every other command stay what they were
+    if ssim_weight is not None and not ssim_weight >= 0:
+        raise UserError('--ssim_weight must be non-negative')
+    if ssim_weight:
+        config.loss_kwargs.update(ssim_weight=ssim_weight, ssim_width=content_width)
     config.ema_kimg, config.ema_rampup = spec.ema, spec.ramp
     args.total_kimg = spec.kimg
     args.batch_size = spec.mb
@@ -257,6 +267,8 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
             raise UserError(f'--fp32=true and --storage={storage} contradict: --fp32 asks for fp32 activations in every block, '
                             '--storage for 16-bit ones')
         desc += f'-{storage}'
+    if ssim_weight:
+        desc += f'-ssim{ssim_weight:g}'
     if fp32:
         config.G_kwargs.synthesis_kwargs.num_fp16_res = config.D_kwargs.num_fp16_res = 0
         config.G_kwargs.synthesis_kwargs.conv_clamp = config.D_kwargs.conv_clamp = None
@@ -454,8 +466,12 @@ class CommaSeparatedList(click.ParamType):
 # Loss weights.
 @click.option('--pl_weight', type=float)
 @click.option('--l1_weight', help='G L1 loss weight', type=float)
-@click.option('--vgg_weight', help='vgg loss weight', type=float)
-@click.option('--contextual_weight', help='contextual loss weight', type=float)
+@click.option('--ssim_weight', help='G SSIM loss weight: 1 - mean SSIM against the photograph, the windows recon_full reports [default: 0]',
+              type=float)
+@click.option('--vgg_weight', help='vgg loss weight (runs from random weights: the checkpoint cannot be obtained; --ssim_weight is the '
+              'structural term that needs none)', type=float)
+@click.option('--contextual_weight', help='contextual loss weight (refused unless 0: its checkpoint cannot be obtained; see --ssim_weight)',
+              type=float)
 @click.option('--mask_weight', type=float)
 @click.option('--use_noise_const_branch', help='Enable const_branch noise input?', type=bool, metavar='BOOL')
 def main(ctx, outdir, dry_run, continue_path, **config_kwargs):

@@ -151,6 +151,7 @@ class UvitonDatasetFull(Dataset):
         if len(self._image_fnames) == 0:
             raise IOError('No image files found in the specified path')
         h, w, c = self._load_image(0).shape
+        self.content_width = int(w)                            # the photographs' own width, which the batch builder pads to the square
         raw_shape = [len(self._image_fnames), c, h, h]         # the padded square, as the reference's image_shape
         if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
             raise IOError('Image files do not match the specified resolution')

@@ -8,7 +8,9 @@ the VGG19 perceptual term (``VGGLoss`` :259-273 over ``VGG19_Feature`` :275-310)
 when ``vgg_weight > 0``; its pretrained weights (``./checkpoints/vgg19-dcbb9e9d.pth``) cannot be obtained here, so the
 file is loaded when present and otherwise ``vgg_random_init=True`` must be passed (random weights: the arithmetic and
 its cost are the reference's, the loss value is not meaningful).  The contextual term needs a second unobtainable
-checkpoint and is rejected unless its weight is 0; statistics reporting is a no-op hook; style mixing picks its cutoff
+checkpoint and is rejected unless its weight is 0; ``ssim_weight`` adds this package's own structural term, 1 - mean SSIM of
+each generated image against the photograph (torch_utils/ops/ssim_loss.py), which needs no checkpoint; statistics reporting
+is a no-op hook; style mixing picks its cutoff
 without a host synchronisation.
 """
 
@@ -19,6 +21,7 @@ import torch
 
 from torch_utils import misc
 from torch_utils.ops import conv2d_gradfix
+from torch_utils.ops import ssim_loss
 
 #----------------------------------------------------------------------------
 
@@ -95,11 +98,15 @@ class Loss:
 class StyleGAN2Loss(Loss):
     def __init__(self, device, G_mapping, G_synthesis, G_const_encoding, G_style_encoding, D, augment_pipe=None,
                  style_mixing_prob=0.9, r1_gamma=10, pl_batch_shrink=2, pl_decay=0.01, pl_weight=0, l1_weight=50,
-                 vgg_weight=50, contextual_weight=1.0, mask_weight=1.0, report_fn=None, vgg_random_init=False):
+                 vgg_weight=50, contextual_weight=1.0, mask_weight=1.0, report_fn=None, vgg_random_init=False, ssim_weight=0,
+                 ssim_width=None):
         super().__init__()
         if contextual_weight > 0:
             raise NotImplementedError('the contextual term needs ./checkpoints/vgg19_conv.pth, which cannot be obtained here; '
-                                      'pass contextual_weight=0 (accumulate_gradients never uses it: :106-254)')
+                                      'pass contextual_weight=0 (accumulate_gradients never uses it: :106-254); ssim_weight is the '
+                                      'structural term that needs no checkpoint')
+        if ssim_weight < 0 or (ssim_weight > 0 and ssim_width is None):
+            raise ValueError('ssim_weight must not be negative, and a positive one needs ssim_width, the content width of the images')
         if pl_weight != 0:
             raise NotImplementedError('path-length regularisation is unreachable in the reference (wrong arity at '
                                       'loss_wo_flow_fullbody.py:185-205; train.sh sets --pl_weight 0)')
@@ -116,6 +123,8 @@ class StyleGAN2Loss(Loss):
         self.l1_weight = l1_weight
         self.vgg_weight = vgg_weight
         self.mask_weight = mask_weight
+        self.ssim_weight = ssim_weight
+        self.ssim_width = ssim_width
         self.report = report_fn if report_fn is not None else (lambda name, value: None)
         if vgg_weight > 0:
             self.criterionVGG = VGGLoss(device, random_init=vgg_random_init)
@@ -227,6 +236,13 @@ class StyleGAN2Loss(Loss):
             self.report('Loss/G/vgg_finetune', loss_G_finetune_VGG)
             loss_G = (loss_Gmain + loss_Gmain_finetune) / 2 + (loss_G_L1 + loss_G_finetune_L1) / 2 + \
                      (loss_G_VGG + loss_G_finetune_VGG) / 2 + loss_mask
+            if self.ssim_weight > 0:      # own term: 1 - mean SSIM over the content columns, the windows recon_full reports
+                c0 = (real_img.shape[3] - self.ssim_width) // 2
+                loss_G_SSIM = ssim_loss.ssim_loss(gen_img.to(torch.float32), real_img, c0, self.ssim_width) * self.ssim_weight
+                loss_G_finetune_SSIM = ssim_loss.ssim_loss(gen_finetune_img.to(torch.float32), real_img, c0, self.ssim_width) * self.ssim_weight
+                loss_G = loss_G + (loss_G_SSIM + loss_G_finetune_SSIM) / 2
+                self.report('Loss/G/ssim', loss_G_SSIM)
+                self.report('Loss/G/ssim_finetune', loss_G_finetune_SSIM)
             self.report('Loss/scores/fake_finetune', gen_finetune_logits)
             self.report('Loss/G/loss', loss_Gmain)
             self.report('Loss/G/loss_finetune', loss_Gmain_finetune)
