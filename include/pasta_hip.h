@@ -659,6 +659,38 @@ int pasta_tryon_mirror_u8(const uint8_t* image, const uint8_t* parsing, const ui
 int pasta_tryon_jitter_u8(const uint8_t* image, const uint8_t* parsing, const int64_t* affine, const int32_t* colour,
                           uint8_t* image_out, uint8_t* parsing_out, int N, int H, int W, void* stream);
 
+/* Erase strokes (this project's own rule; --erase-masks strokes of train_wo_flow_fullbody.py, training/tryon_batch.py's
+ * strokes_batch).  The erase mask of an item is drawn, not read from a file: random thick polylines with round caps and joins on
+ * the padded S x S square (S = 256 or 512), anew at every visit, determined by the run's seed and the item's position in the
+ * sampler's stream.  The mask belongs to the canvas: it covers the whole square, is formed after mirroring and jittering, is never
+ * mirrored, and goes to the unchanged assemble entries as `erase_masks` with erase_hw = (S, S), a size the restated cv2.resize
+ * passes unchanged (taps (d, 2048, 0)).
+ *   uniforms  per item 169 numbers U on [0, 1): the raw outputs of np.random.PCG64(np.random.SeedSequence((seed, position, 1)))
+ *             as (raw >> 11) * 2^-53 (training.tryon_batch.strokes_uniforms).  The third word keeps them independent of the jitter's
+ *             (seed, position).  All 169 are drawn in this order whatever the specification says, so changing one strength leaves
+ *             what the other parameters give unchanged.
+ *   strokes   on the host, in float64, cos and sin the C library's (training.tryon_batch.strokes_segments), from a specification
+ *             (strokes 1..8, vertices 1..8, length 0.01..0.5, width 0.01..0.25, turn 0..180 degrees):
+ *             K = 1 + floor(U[0] strokes) strokes; stroke j uses the block b = 1 + 21 j: V = 1 + floor(U[b] vertices) segments,
+ *             start x = U[b+1] S - 0.5, y = U[b+2] S - 0.5, half-width r = width S (1/3 + 2/3 U[b+3]) / 2, heading a = 2 pi U[b+4];
+ *             for segment i < V: a += radians(turn) (2 U[b+5+2i] - 1), l = length S (1 + U[b+6+2i]) / 2, the segment runs from
+ *             (x, y) to (x + l cos a, y + l sin a), which becomes the new (x, y).
+ *   Q3        coordinates become int32 in 1/8 pixel, clip(rint(v * 8), -8192, 8191); the half-width clip(rint(r * 8), 8, 512).
+ *             segments int32 [N, 64, 5] = (x0, y0, x1, y1, r), counts int32 [N] (0..64; a count outside is read as clamped).
+ *   pixel     (px, py) of item n is 1 iff for one of its segments, with P = (8 px, 8 py), d = p1 - p0, v = P - p0, t = v.d,
+ *             L = d.d:  t <= 0 ? v.v <= r r  :  t >= L ? |P - p1|^2 <= r r  :  cross(v, d)^2 <= r r L;  otherwise 0.
+ *             Exact in integers: by the clamps and S <= 1024 every difference is below 2^14, so t, L, v.v and the cross product
+ *             fit int32; only cross^2 (< 2^58) and r r L (< 2^47) need 64 bits.  p0 == p1 is a disc.
+ * The value is 1, not 255: the reference's erase sum arm_a + arm_b + mask wraps in uint8, so with 255 a stroke that crosses an arm
+ * part would punch an un-erased hole (255 + 1 = 0); 1 + 1 + 1 cannot wrap.
+ * One launch for a batch: a 256-thread workgroup owns a 64 x 64 tile of one item, keeps the item's segments in LDS, its first wave
+ * culls them against the tile (bounding box grown by r) into one 64-bit ballot, and every thread walks the set bits for 16
+ * consecutive pixels of a row; with S a multiple of 16 and a 16-byte aligned `out` they leave in one 16-byte store, otherwise
+ * byte by byte.  segments, counts and out [N, S, S] are on the device.  n == 0 is nothing to do.  Refused before any launch, outputs
+ * untouched: a null pointer with n > 0; n outside 0..65535; S outside 1..1024.  Numbers outside the Q3 clamps give an unspecified
+ * mask, never an access outside `out`. */
+int pasta_erase_strokes_u8(const int32_t* segments, const int32_t* counts, uint8_t* out, int n, int S, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the try-on TEST pairs (row f4; UvitonDatasetV19_test._load_raw_image / normalize / __getitem__,
  * training/dataset.py:1085-1525, and test.py:104-150).  Same canvas, restated primitives and exactness as the entries

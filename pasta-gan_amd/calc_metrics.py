@@ -8,7 +8,9 @@ Without --data the snapshot's own ``training_set_kwargs`` name the tree; --data 
 tree; a tree of ``*_512_320`` folders is read as the 512 x 320 training set).  When the snapshot lies in a training run's directory (one with training_options.json), the result is also appended to
 that directory's ``metric-<name>.jsonl``.  --network must name a local file: URLs are refused (nothing is downloaded).
 --storage f32 | bf16 | f16 scores the generator in that activation storage, whatever it was pickled with; the result line then
-carries a ``storage`` field.  One
+carries a ``storage`` field.  --erase-masks files | none | strokes and --erase-strokes SPEC say where the erase masks of
+the scored batches come from, as train_wo_flow_fullbody.py's options do; their default is what the snapshot recorded, and
+``--erase-masks none`` scores a snapshot trained on mask files on a tree that has none.  One
 process per GPU; for more than one GPU fresh processes are spawned, each loading the snapshot itself."""
 
 import json
@@ -79,7 +81,8 @@ class CommaSeparatedList(click.ParamType):
               show_default=True)
 @click.option('--workers', help='Loader processes (file decoding only)', type=click.IntRange(min=0), default=0, show_default=True)
 @tryon_cli.storage_option
-def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, workers, storage):
+@tryon_cli.erase_options('as the snapshot recorded')
+def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, workers, storage, erase_masks, erase_strokes):
     """Calculate quality metrics of a network snapshot on a tree of the training set's layout."""
     import dnnlib
     from metrics import metric_main
@@ -93,19 +96,31 @@ def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, wor
     if not os.path.isfile(network_pkl):
         ctx.fail('--network: %r is not a file' % network_pkl)
 
-    # Data set options: the tree given, else the one the snapshot was trained on.
+    # Data set options: the tree given, else the one the snapshot was trained on.  Where the erase masks come from: as given,
+    # else as the snapshot recorded (a snapshot trained on files can be scored on a tree that has none: --erase-masks none).
+    import legacy
+    with open(network_pkl, 'rb') as f:
+        kwargs = legacy.load_network_pkl(f).get('training_set_kwargs')
     if data is not None:
         if not os.path.isdir(data):
             ctx.fail('--data: %r is not a directory' % data)
         from training.dataset import training_set_class
         args.dataset_kwargs = dnnlib.EasyDict(class_name=training_set_class(data), path=data)
+        args.dataset_kwargs.update({k: kwargs[k] for k in ('erase_masks', 'erase_strokes') if kwargs is not None and k in kwargs})
     else:
-        import legacy
-        with open(network_pkl, 'rb') as f:
-            kwargs = legacy.load_network_pkl(f).get('training_set_kwargs')
         if kwargs is None:
             ctx.fail('Could not look up dataset options; please specify --data')
         args.dataset_kwargs = dnnlib.EasyDict(kwargs)
+    if erase_masks is not None or erase_strokes is not None:
+        if erase_masks is None:
+            erase_masks = args.dataset_kwargs.get('erase_masks', 'files')       # --erase-strokes alone: new strengths for recorded strokes
+        try:
+            given = tryon_cli.erase_mask_kwargs(erase_masks, erase_strokes)
+        except ValueError as err:
+            ctx.fail(str(err))
+        for k in ('erase_masks', 'erase_strokes'):
+            args.dataset_kwargs.pop(k, None)
+        args.dataset_kwargs.update(given)
     args.dataset_kwargs.update(use_labels=False, xflip=False, mirror_people=False)
     if args.verbose:
         print('Dataset options:')

@@ -9,7 +9,9 @@
 //   pasta_tryon_mirror_u8   the raw samples of a batch as a mirror shows them (this project's own rule, --mirror-people): the
 //                           photograph, the label map with left and right exchanged and the erase mask, before any of the above;
 //   pasta_tryon_jitter_u8   the raw samples of a batch after a similarity map and a colour map per item (this project's own rule,
-//                           --jitter-people): the photograph resampled from four taps, the label map from the nearest one.
+//                           --jitter-people): the photograph resampled from four taps, the label map from the nearest one;
+//   pasta_erase_strokes_u8  the erase masks of a batch drawn on the padded square (this project's own rule, --erase-masks strokes):
+//                           thick polylines with round caps and joins, exact in integers, after both of the above.
 // The palm mask (get_palm / get_hand_mask / get_rectangle_mask, :626-702) is csrc/tryon_pairs.hip's pasta_palm_mask_u8.
 // Every entry is its checks and one launch for a whole batch.  The reference does this on the host with OpenCV, pycocotools and
 // skimage.  What is defined by numpy / skimage is exact here; three primitives are restated (include/pasta_hip.h states the rules,
@@ -304,7 +306,88 @@ __global__ __launch_bounds__(256) void tryon_jitter_kernel(const uint8_t* __rest
     }
 }
 
+// ---- erase strokes (this project's own rule: include/pasta_hip.h, pasta_erase_strokes_u8) ----
+
+constexpr int STROKE_SEGMENTS = 64, STROKE_TILE = 64;
+
+// The point (X, Y), in 1/8 pixel as the segment p0 -> p1 is, lies within r (r2 = r * r) of the segment.  With the Q3 clamps and
+// S <= 1024 every difference is below 2^14: the dot products and the cross product fit an int, its square and r2 * L need 64 bits.
+__device__ __forceinline__ bool stroke_hit(int X, int Y, int x0, int y0, int x1, int y1, int r2) {
+    const int dx = x1 - x0, dy = y1 - y0, vx = X - x0, vy = Y - y0;
+    const int t = vx * dx + vy * dy, L = dx * dx + dy * dy;
+    if (t <= 0) return vx * vx + vy * vy <= r2;                       // also p0 == p1: a disc
+    if (t >= L) { const int wx = X - x1, wy = Y - y1; return wx * wx + wy * wy <= r2; }
+    const int cr = vx * dy - vy * dx;
+    return (int64_t)cr * cr <= (int64_t)r2 * L;
+}
+
+// One launch for a batch: item n = blockIdx.y, blockIdx.x one 64 x 64 tile of its S x S mask.  The item's segments go to LDS, the
+// first wave keeps those whose bounding box grown by r meets the tile (one segment per lane, one ballot), and thread t walks the
+// kept ones for the 16 pixels from column 16 (t % 4) of the tile's row t / 4.  WIDE (S % 16 == 0, `out` 16-byte aligned): one
+// 16-byte store; otherwise byte stores with the column checked.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void erase_strokes_kernel(const int32_t* __restrict__ segments, const int32_t* __restrict__ counts,
+                                                            uint8_t* __restrict__ out, int S, int tiles) {
+    __shared__ int32_t seg[STROKE_SEGMENTS * 5];
+    __shared__ unsigned long long kept;
+    const int n = blockIdx.y;
+    const int ty = blockIdx.x / tiles, tx = blockIdx.x - ty * tiles;
+    int count = counts[n];
+    count = count < 0 ? 0 : (count > STROKE_SEGMENTS ? STROKE_SEGMENTS : count);
+    for (int i = threadIdx.x; i < count * 5; i += 256) seg[i] = segments[(int64_t)n * STROKE_SEGMENTS * 5 + i];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        bool meets = false;
+        if ((int)threadIdx.x < count) {
+            const int32_t* q = seg + 5 * threadIdx.x;
+            const int r = q[4], lo_x = 8 * STROKE_TILE * tx, lo_y = 8 * STROKE_TILE * ty, span = 8 * (STROKE_TILE - 1);
+            meets = min(q[0], q[2]) - r <= lo_x + span && max(q[0], q[2]) + r >= lo_x && min(q[1], q[3]) - r <= lo_y + span &&
+                    max(q[1], q[3]) + r >= lo_y;
+        }
+        const unsigned long long ballot = __ballot(meets);
+        if (threadIdx.x == 0) kept = ballot;
+    }
+    __syncthreads();
+    const int y = STROKE_TILE * ty + (threadIdx.x >> 2), xb = STROKE_TILE * tx + 16 * (threadIdx.x & 3);
+    if (y >= S || xb >= S) return;
+    unsigned long long todo = kept;
+    uint32_t hit = 0;                                                    // bit p: pixel xb + p
+    const int Y = 8 * y, X = 8 * xb;
+    while (todo) {                                                       // no kept segment: zeros, and LDS is not read again
+        const int32_t* q = seg + 5 * (__ffsll(todo) - 1);
+        todo &= todo - 1;
+        const int x0 = q[0], y0 = q[1], x1 = q[2], y1 = q[3], r = q[4];
+        if (Y < min(y0, y1) - r || Y > max(y0, y1) + r || X + 120 < min(x0, x1) - r || X > max(x0, x1) + r) continue;
+#pragma unroll
+        for (int p = 0; p < 16; p++)
+            if (stroke_hit(X + 8 * p, Y, x0, y0, x1, y1, r * r)) hit |= 1u << p;
+    }
+    uint8_t* row = out + ((int64_t)n * S + y) * S + xb;
+    if constexpr (WIDE) {
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = (((hit >> (4 * k)) & 15u) * 0x00204081u) & 0x01010101u;       // bit j -> byte j
+        *reinterpret_cast<uint4*>(row) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (int p = 0; p < 16 && xb + p < S; p++) row[p] = (uint8_t)((hit >> p) & 1u);
+    }
+}
+
 }  // namespace pasta
+
+extern "C" int pasta_erase_strokes_u8(const int32_t* segments, const int32_t* counts, uint8_t* out, int n, int S, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(n >= 0 && n <= 65535 && S >= 1 && S <= 1024, "erase_strokes_u8: bad shape (n %d, S %d)", n, S);
+    if (n == 0) return 0;
+    PASTA_CHECK(segments && counts && out, "erase_strokes_u8: null pointer");
+    const int tiles = (S + STROKE_TILE - 1) / STROKE_TILE;
+    dim3 grid((unsigned)(tiles * tiles), (unsigned)n);
+    if (S % 16 == 0 && (uintptr_t)out % 16 == 0)
+        hipLaunchKernelGGL(erase_strokes_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, segments, counts, out, S, tiles);
+    else
+        hipLaunchKernelGGL(erase_strokes_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, segments, counts, out, S, tiles);
+    return launch_status("erase_strokes_u8");
+}
 
 extern "C" int pasta_tryon_jitter_u8(const uint8_t* image, const uint8_t* parsing, const int64_t* affine, const int32_t* colour,
                                      uint8_t* image_out, uint8_t* parsing_out, int N, int H, int W, void* stream) {

@@ -90,7 +90,7 @@ def compute_partials(opts):
     """This rank's items -- (i * num_gpus + rank) % num_items as the reference's metrics take theirs, without the repeats of the
     wrap-around, so that each item is scored once -- scored into device partials, combined over the ranks by one all_reduce."""
     from training import dataset as dataset_module
-    from training.tryon_batch import builder_for
+    from training.tryon_batch import attach_strokes, builder_for
     dataset = dnnlib.util.construct_class_by_name(**opts.dataset_kwargs)
     num_items = len(dataset)
     rounds = (num_items - 1) // opts.num_gpus + 1
@@ -107,6 +107,8 @@ def compute_partials(opts):
     progress = opts.progress.sub(tag='reconstruction', num_items=len(subset))
     done = 0
     for raw in loader:
+        if getattr(dataset, 'erase_masks', 'files') == 'strokes':       # drawn by the person, not by a visit: scores stay comparable
+            attach_strokes(raw, dataset.erase_strokes, 0, raw['raw_idx'].numpy())
         batch = builder.build(raw)
         score_batch(G, batch, raw['raw_idx'].tolist(), subset[done:done + batch.batch], partials)
         done += batch.batch

@@ -239,6 +239,7 @@ ABI = {
     'pasta_tryon_assemble': (ctypes.c_int, [_c_ptr] * 11 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 9 + [_c_ptr]),
     'pasta_tryon_mirror_u8': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.c_int] * 5 + [_c_ptr]),
     'pasta_tryon_jitter_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 3 + [_c_ptr]),
+    'pasta_erase_strokes_u8': (ctypes.c_int, [_c_ptr] * 3 + [ctypes.c_int] * 2 + [_c_ptr]),
     'pasta_tryon_outfit_masks_u8': (ctypes.c_int, [_c_ptr] * 12 + [ctypes.c_int] * 4 + [_c_ptr]),
     'pasta_patch_composite_eroded_u8': (ctypes.c_int, [_c_ptr] * 6 + [ctypes.c_int] * 7 + [_c_ptr] * 2),
     'pasta_tryon_outfit_assemble': (ctypes.c_int, [_c_ptr] * 9 + [ctypes.POINTER(_c_ptr)] + [ctypes.c_int] * 7 + [_c_ptr]),
@@ -268,11 +269,13 @@ ABI = {
 # them (an old PASTA_LIB_AB build) still loads, and the first call of a missing one raises instead of the import.  At 22: the PNG
 # encoder's four entries (csrc/png_encode.hip), pasta_images_keep_to_u8 and pasta_photo_paste_mask_u8 (csrc/tryon_pairs.hip), the five
 # entries of the input-activation mask (pasta_act_mask: csrc/conv_igemm.hip, csrc/upfirdn2d.hip; pasta_bias_sum_db: csrc/bias_act.hip),
-# pasta_tryon_mirror_u8 and pasta_tryon_jitter_u8 (csrc/tryon_inputs.hip), the three entries of the SSIM loss (csrc/ssim_loss.hip).
+# pasta_tryon_mirror_u8, pasta_tryon_jitter_u8 and pasta_erase_strokes_u8 (csrc/tryon_inputs.hip), the three entries of the SSIM loss
+# (csrc/ssim_loss.hip).
 LATE_ENTRIES = frozenset(['pasta_png_filter', 'pasta_png_code_lengths', 'pasta_png_segment_tables', 'pasta_png_encode',
                           'pasta_images_keep_to_u8', 'pasta_photo_paste_mask_u8', 'pasta_conv2d_masked', 'pasta_conv2d_mask_available', 'pasta_upfirdn2d_masked',
                           'pasta_upfirdn2d_mask_available', 'pasta_bias_sum_db', 'pasta_tryon_mirror_u8',
-                          'pasta_tryon_jitter_u8', 'pasta_ssim_loss_workspace', 'pasta_ssim_loss', 'pasta_ssim_loss_backward'])
+                          'pasta_tryon_jitter_u8', 'pasta_ssim_loss_workspace', 'pasta_ssim_loss', 'pasta_ssim_loss_backward',
+                          'pasta_erase_strokes_u8'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

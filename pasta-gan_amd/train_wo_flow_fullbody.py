@@ -26,6 +26,11 @@ people as photographed.
 ``--ssim_weight=5`` adds ``5 * (1 - mean SSIM)`` of each of the generator's two images against the photograph to its loss: the
 windows and constants ``recon_full`` reports, on the un-quantised images, value and gradient on the GPU.
 
+``--erase-masks=strokes`` trains without the mask files of ``train_random_mask_acgpn``: every item's erase mask is drawn on the GPU,
+random thick polylines on the padded square, anew at every visit from the run's seed and the item's position in the sampler's
+stream (``--erase-strokes=strokes=6,vertices=6,length=0.25,width=0.12,turn=60`` sets their strengths); ``--erase-masks=none`` erases
+only what the arm-part rule erases.  With either the tree needs no mask directory.
+
 ``--storage=bf16`` (or ``f16``) keeps the activations of G and of every block of D in that type; parameters, demodulation,
 statistics, the images and the loss stay fp32.
 """
@@ -40,6 +45,7 @@ import click
 import torch
 
 import dnnlib
+import tryon_cli
 from training import training_loop_wo_flow_fullbody as training_loop
 from training.dataset import training_set_class
 
@@ -62,20 +68,8 @@ def parse_jitter_people(text):
     """``--jitter-people``'s SPEC, comma-separated ``name=value`` pairs -> the specification ``training_loop(people_jitter=)``
     takes: all four names (scale 0..0.5, rotate 0..45 degrees, shift 0..0.25 of the canvas side, colour 0..0.5), absent ones 0."""
     from training.tryon_batch import jitter_spec
-    spec = {}
-    for pair in text.split(','):
-        name, eq, value = pair.partition('=')
-        name = name.strip()
-        if not eq or not name:
-            raise UserError(f'--jitter-people: {pair!r} is not name=value')
-        if name in spec:
-            raise UserError(f'--jitter-people: {name} is given twice')
-        try:
-            spec[name] = float(value)
-        except ValueError:
-            raise UserError(f'--jitter-people: {name}={value.strip()} is not a number')
     try:
-        return jitter_spec(spec)
+        return jitter_spec(tryon_cli.parse_name_values(text))
     except ValueError as err:
         raise UserError(f'--jitter-people: {err}')
 
@@ -83,7 +77,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
-                               mirror_people=None, jitter_people=None, ssim_weight=None):
+                               mirror_people=None, jitter_people=None, ssim_weight=None, erase_masks=None, erase_strokes=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -111,6 +105,13 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     # a tree of *_512_320 folders (and no Zalando_256_192) is the 512 x 320 training set, whose batches carry 45 patch channels
     args.training_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(data), path=data, use_labels=False, max_size=None, xflip=False)
     args.data_loader_kwargs = dnnlib.EasyDict(pin_memory=True, num_workers=0)
+    # --erase-masks, --erase-strokes (own options): where the erase masks come from.  Arguments of the data set, set before it is
+    # opened: with none or strokes it never looks for train_random_mask_acgpn.  The scores and the sample grid inherit them
+    try:
+        erase_kwargs = dnnlib.EasyDict(tryon_cli.erase_mask_kwargs(erase_masks, erase_strokes))
+    except ValueError as err:
+        raise UserError(str(err))
+    args.training_set_kwargs.update(erase_kwargs)
     try:
         training_set = dnnlib.util.construct_class_by_name(**args.training_set_kwargs)
         args.training_set_kwargs.resolution = training_set.resolution
@@ -126,7 +127,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         if not metrics:
             raise UserError('--metrics_data needs --metrics')
         args.metric_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(metrics_data), path=metrics_data, use_labels=False,
-                                                 max_size=None, xflip=False)
+                                                 max_size=None, xflip=False, **erase_kwargs)
         try:
             metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
             if metric_set.resolution != args.training_set_kwargs.resolution:
@@ -157,6 +158,8 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     if jitter_people is not None:
         desc += '-jitterpeople'
         args.people_jitter = dnnlib.EasyDict(parse_jitter_people(jitter_people))
+    if erase_kwargs:
+        desc += '-erase' + erase_kwargs['erase_masks']
 
     # Base config: cfg, gamma, kimg, batch (:161-246)
     cfg = 'auto' if cfg is None else cfg
@@ -321,7 +324,8 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         recorded = {'gpus': args.num_gpus, 'batch': args.batch_size}.get(name)
         if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
             continue
-        option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people', 'jitter_people': 'jitter-people'}.get(name, name)
+        option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people', 'jitter_people': 'jitter-people', 'erase_masks': 'erase-masks',
+                         'erase_strokes': 'erase-strokes'}.get(name, name)
         raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
                         (f' ({recorded})' if recorded is not None else ''))
 
@@ -365,7 +369,8 @@ def setup_continue_kwargs(continue_path, data=None, **given):
             raise UserError('--metrics_data needs --metrics')
         metrics_data = given['metrics_data']
         args.metric_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(metrics_data), path=metrics_data, use_labels=False,
-                                                 max_size=None, xflip=False)
+                                                 max_size=None, xflip=False,
+                                                 **{k: recorded[k] for k in ('erase_masks', 'erase_strokes') if k in recorded})
         try:
             metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
             if metric_set.resolution != recorded.resolution:
@@ -442,6 +447,7 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--mirror-people', help='Train on every person a second time, mirrored on the GPU [default: false]', type=bool, metavar='BOOL')
 @click.option('--jitter-people', help='Train on people jittered on the GPU: comma-separated scale=0..0.5, rotate=0..45 (degrees), '
               'shift=0..0.25 (of the canvas side), colour=0..0.5 [default: none]', metavar='SPEC')
+@tryon_cli.erase_options('files')
 # Base config.
 @click.option('--cfg', help='Base config [default: auto]', type=click.Choice(list(CFG_SPECS) + list(UNSUPPORTED_CFGS)))
 @click.option('--gamma', help='Override R1 gamma', type=float)
@@ -507,6 +513,9 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
     print(f'Mirrored people:    {bool(args.training_set_kwargs.get("mirror_people", False))}')
     jitter = args.get('people_jitter')
     print(f'Jittered people:    {",".join(f"{k}={v:g}" for k, v in jitter.items()) if jitter else False}')
+    strokes = args.training_set_kwargs.get('erase_strokes')
+    print(f'Erase masks:        {args.training_set_kwargs.get("erase_masks", "files")}' +
+          (f' ({",".join(f"{k}={v:g}" for k, v in strokes.items())})' if strokes else ''))
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

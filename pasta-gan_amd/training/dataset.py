@@ -99,6 +99,9 @@ def read_keypoints(path):
     return np.array(data['people'][0]['pose_keypoints_2d'], dtype=np.float64).reshape(-1, 3)
 
 
+ERASE_MASKS = ('files', 'none', 'strokes')          # UvitonDatasetFull(erase_masks=): where a training item's erase mask comes from
+
+
 class UvitonDatasetFull(Dataset):
     """dataset.py:426-995 -- file lists, ``_vis_index`` and the ACGPN erase masks of a directory tree; ``__getitem__``
     returns the raw sample (see the module docstring): a dict with
@@ -109,7 +112,13 @@ class UvitonDatasetFull(Dataset):
     ``mirror_people=True`` (this project's own; the reference's ``xflip`` flips the prepared tuple, which is undefined here and stays
     refused) doubles the set: positions N .. 2N-1 are the people of positions 0 .. N-1 again, with ``xflip`` = 1 in the raw
     sample.  The files are read as they are: the builder mirrors the flagged items of a batch on the GPU
-    (``training.tryon_batch.mirror_batch``; include/pasta_hip.h has the rule).  Without the option a sample has no ``xflip``."""
+    (``training.tryon_batch.mirror_batch``; include/pasta_hip.h has the rule).  Without the option a sample has no ``xflip``.
+
+    ``erase_masks`` (this project's own): ``'files'`` reads the ACGPN masks as above; ``'none'`` and ``'strokes'`` never look at
+    ``train_random_mask_acgpn``, so a tree without it opens, and every ``erase_mask`` is a 1 x 1 zero, which erases nothing.  With
+    ``'strokes'`` whoever numbers the batches attaches ``erase_strokes`` (the checked specification of
+    ``training.tryon_batch.strokes_spec``, an attribute here as ``erase_masks`` is) and the builder draws a mask per item on the
+    GPU (``training.tryon_batch.strokes_batch``; include/pasta_hip.h has the rule)."""
 
     _sub_datasets = SUB_DATASETS
     _vis_sources = (('Zalando_256_192', 'image'), ('Deepfashion_256_192', os.path.join('image', 'train')))     # :461-472, in this order
@@ -118,7 +127,16 @@ class UvitonDatasetFull(Dataset):
     def _label_name(dataset, name):
         return name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')
 
-    def __init__(self, path, resolution=None, mirror_people=False, **super_kwargs):
+    def __init__(self, path, resolution=None, mirror_people=False, erase_masks='files', erase_strokes=None, **super_kwargs):
+        if erase_masks not in ERASE_MASKS:
+            raise ValueError('erase_masks=%r is none of %s' % (erase_masks, ', '.join(ERASE_MASKS)))
+        if erase_strokes is not None and erase_masks != 'strokes':
+            raise ValueError("erase_strokes is a specification for erase_masks='strokes', not %r" % (erase_masks,))
+        self.erase_masks = erase_masks
+        self.erase_strokes = None
+        if erase_masks == 'strokes':
+            from training.tryon_batch import strokes_spec
+            self.erase_strokes = strokes_spec(erase_strokes or {})
         self._path = path
         if not os.path.isdir(self._path):
             raise IOError('Path must point to a directory')
@@ -143,8 +161,10 @@ class UvitonDatasetFull(Dataset):
                     break
         self._vis_index = vis_index
 
-        acgpn_dir = os.path.join(self._path, 'train_random_mask_acgpn')
-        self._random_mask_acgpn_fnames = [os.path.join(acgpn_dir, name) for name in os.listdir(acgpn_dir)]     # os.listdir order (:476)
+        self._random_mask_acgpn_fnames = []
+        if self.erase_masks == 'files':
+            acgpn_dir = os.path.join(self._path, 'train_random_mask_acgpn')
+            self._random_mask_acgpn_fnames = [os.path.join(acgpn_dir, name) for name in os.listdir(acgpn_dir)]     # os.listdir order (:476)
         self._mask_acgpn_numbers = len(self._random_mask_acgpn_fnames)
 
         PIL.Image.init()
@@ -172,7 +192,10 @@ class UvitonDatasetFull(Dataset):
         if parsing.shape != image.shape[:2]:
             raise IOError('%s: label map %s does not match the image %s' % (self._parsing_fnames[raw_idx], parsing.shape, image.shape[:2]))
         keypoints = read_keypoints(os.path.join(self._path, self._kpt_fnames[raw_idx]))
-        erase = read_channel0(self._random_mask_acgpn_fnames[raw_idx % self._mask_acgpn_numbers])
+        if self.erase_masks == 'files':
+            erase = read_channel0(self._random_mask_acgpn_fnames[raw_idx % self._mask_acgpn_numbers])
+        else:
+            erase = np.zeros([1, 1], np.uint8)
         return dict(image=image, parsing=parsing, keypoints=keypoints, erase_mask=erase, raw_idx=int(raw_idx))
 
     def __getitem__(self, idx):

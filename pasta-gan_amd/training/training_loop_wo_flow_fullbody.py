@@ -292,15 +292,21 @@ class TrainingStep:
 
 #----------------------------------------------------------------------------
 
-def _numbered_batches(loader, people_jitter, random_seed, num_gpus, rank, cur_nimg):
-    """The collated batches of ``loader`` with ``raw['jitter']`` attached (``--jitter-people``): the specification, the run's seed
-    and the int64 positions [N] its items have in the sampler's global stream.  Position ``t`` belongs to rank ``t % num_gpus``
-    and a rank reads its positions in increasing order from ``cur_nimg`` (``InfiniteSampler(skip=)``), so a continued run numbers
-    its items as the uninterrupted one does."""
+def _numbered_batches(loader, people_jitter, random_seed, num_gpus, rank, cur_nimg, erase_strokes=None):
+    """The collated batches of ``loader`` numbered: the int64 positions [N] its items have in the sampler's global stream, with the
+    run's seed, attached as ``raw['jitter']`` with the specification ``people_jitter`` (``--jitter-people``) and, through
+    ``attach_strokes``, as ``raw['erase_strokes']`` with the specification ``erase_strokes`` (``--erase-masks strokes``); either
+    may be None.  Position ``t`` belongs to rank ``t % num_gpus`` and a rank reads its positions in increasing order from
+    ``cur_nimg`` (``InfiniteSampler(skip=)``), so a continued run numbers its items as the uninterrupted one does."""
+    from training.tryon_batch import attach_strokes
     t = cur_nimg + (rank - cur_nimg) % num_gpus             # the rank's first position at or after cur_nimg
     for raw in loader:
         n = int(raw['raw_idx'].shape[0])
-        raw['jitter'] = dict(spec=dict(people_jitter), seed=int(random_seed), positions=t + num_gpus * np.arange(n, dtype=np.int64))
+        positions = t + num_gpus * np.arange(n, dtype=np.int64)
+        if people_jitter is not None:
+            raw['jitter'] = dict(spec=dict(people_jitter), seed=int(random_seed), positions=positions)
+        if erase_strokes is not None:
+            attach_strokes(raw, erase_strokes, random_seed, positions)
         t += num_gpus * n
         yield raw
 
@@ -308,7 +314,9 @@ def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_
     """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263).  ``cur_nimg``: the images
     a continued run has consumed; one iteration takes ``batch_size`` positions of the sampler's global stream whatever the
     number of ranks, so the stream goes on at that position.  ``people_jitter``: a specification of
-    ``training.tryon_batch.jitter_spec``; the batches are then numbered (``_numbered_batches``) and the builder jitters them."""
+    ``training.tryon_batch.jitter_spec``; the batches are then numbered (``_numbered_batches``) and the builder jitters them.  A
+    data set opened with ``erase_masks='strokes'`` has its batches numbered as well, with or without the jitter, and the builder
+    draws their erase masks."""
     from training import dataset as dataset_module
     from training.tryon_batch import builder_for, jitter_spec
     training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
@@ -316,8 +324,10 @@ def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_
     loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
                                          collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
     builder = builder_for(training_set, device)
-    if people_jitter is not None:
-        loader = _numbered_batches(loader, jitter_spec(people_jitter), random_seed, num_gpus, rank, int(cur_nimg))
+    erase_strokes = training_set.erase_strokes if getattr(training_set, 'erase_masks', 'files') == 'strokes' else None
+    if people_jitter is not None or erase_strokes is not None:
+        loader = _numbered_batches(loader, jitter_spec(people_jitter) if people_jitter is not None else None, random_seed, num_gpus, rank,
+                                   int(cur_nimg), erase_strokes=erase_strokes)
     return training_set, builder, (builder.build(raw) for raw in loader)
 
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,

@@ -16,12 +16,16 @@ and after that, for a batch the training loop has numbered for ``--jitter-people
 
     pasta_tryon_jitter_u8    photograph and label map after a similarity map per item, the photograph through a colour map
 
+and after that, for a batch that carries ``raw['erase_strokes']`` (``--erase-masks strokes``; ``strokes_batch``):
+
+    pasta_erase_strokes_u8   the erase masks of the batch, drawn: random thick polylines on the padded square, one mask per item
+
 The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
 ``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
-masks), ``mirror_batch`` (the training sets' mirrored people), ``jitter_batch`` (their jittered people), ``device_tables`` (stick
-and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their pointer array) and
+masks), ``mirror_batch`` (the training sets' mirrored people), ``jitter_batch`` (their jittered people), ``strokes_batch`` (their drawn erase masks),
+``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their pointer array) and
 ``shift_keypoints``.
 ``builder_for`` picks the training builder of a data set: this one, or training/tryon_regions.py's at 512 x 320."""
 
@@ -50,6 +54,12 @@ MIRROR_JOINTS = ((2, 5), (3, 6), (4, 7), (8, 11), (9, 12), (10, 13), (14, 15), (
 # the top of their ranges (rotate in degrees, shift as a fraction of the canvas side), and the luma weights of the saturation
 JITTER_RANGES = dict(scale=0.5, rotate=45.0, shift=0.25, colour=0.5)
 JITTER_LUMA = (0.299, 0.587, 0.114)
+# Erase strokes (this project's own rule, include/pasta_hip.h: pasta_erase_strokes_u8): the names of a specification with their
+# type, range and default; the uniforms of an item (1 + 8 blocks of 21) and the segments the device takes per item
+STROKES_RANGES = dict(strokes=(int, 1, 8, 6), vertices=(int, 1, 8, 6), length=(float, 0.01, 0.5, 0.25), width=(float, 0.01, 0.25, 0.12),
+                      turn=(float, 0.0, 180.0, 60.0))
+STROKES_UNIFORMS = 169
+STROKES_SEGMENTS = 64
 
 
 def stick_tables(keypoints):
@@ -278,6 +288,99 @@ def jitter_batch(raw, image, parsing, keypoints):
     return image_j, parsing_j, jitter_keypoints(keypoints, geometry, H, W)
 
 
+def strokes_spec(spec):
+    """An erase-stroke specification -> a dict of all five STROKES_RANGES names (``strokes`` and ``vertices`` ints, the rest floats;
+    absent names take their defaults), checked: a ValueError names an unknown name, a value that is not a whole number where one is
+    asked for, or a value outside its range."""
+    spec = dict(spec)
+    for name in spec:
+        if name not in STROKES_RANGES:
+            raise ValueError(f'unknown name {name!r} (known: {", ".join(STROKES_RANGES)})')
+    out = {}
+    for name, (kind, low, top, default) in STROKES_RANGES.items():
+        value = float(spec.get(name, default))
+        if kind is int and not value.is_integer():              # a NaN fails here and below
+            raise ValueError(f'{name}={spec[name]} is not a whole number')
+        if not low <= value <= top:
+            raise ValueError(f'{name}={spec[name]} is outside {low:g}..{top:g}')
+        out[name] = kind(value)
+    return out
+
+
+def strokes_uniforms(seed, position):
+    """The 169 uniforms on [0, 1) of stream position ``position`` of the run seeded ``seed``: from the raw 64-bit outputs of
+    ``np.random.PCG64(np.random.SeedSequence((seed, position, 1)))`` as (raw >> 11) * 2^-53.  The third word keeps them
+    independent of ``jitter_uniforms``' (seed, position)."""
+    raw = np.random.PCG64(np.random.SeedSequence((int(seed), int(position), 1))).random_raw(STROKES_UNIFORMS)
+    return (raw >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def _strokes_q3(v, low, top):
+    return int(min(max(np.rint(v * 8.0), low), top))
+
+
+def strokes_segments(spec, seed, positions, S):
+    """(segments int32 [N, 64, 5] = (x0, y0, x1, y1, r) in 1/8 pixel, counts int32 [N]) of the items at ``positions`` of the
+    sampler's global stream on the padded ``S x S`` square (include/pasta_hip.h: ``strokes`` and ``Q3``).  A draw depends on
+    (seed, position) alone; rows past an item's count are 0."""
+    spec = strokes_spec(spec)
+    positions = np.asarray(positions, np.int64).reshape(-1)
+    segments = np.zeros([len(positions), STROKES_SEGMENTS, 5], np.int32)
+    counts = np.zeros([len(positions)], np.int32)
+    turn = math.radians(spec['turn'])
+    for n, t in enumerate(positions.tolist()):
+        u = strokes_uniforms(seed, t).tolist()
+        k = 0
+        for j in range(1 + int(math.floor(u[0] * spec['strokes']))):
+            b = 1 + 21 * j
+            x, y = u[b + 1] * S - 0.5, u[b + 2] * S - 0.5
+            r = _strokes_q3(spec['width'] * S * (1.0 / 3.0 + 2.0 / 3.0 * u[b + 3]) / 2.0, 8, 512)
+            a = 2.0 * math.pi * u[b + 4]
+            for i in range(1 + int(math.floor(u[b] * spec['vertices']))):
+                a += turn * (2.0 * u[b + 5 + 2 * i] - 1.0)
+                l = spec['length'] * S * (1.0 + u[b + 6 + 2 * i]) / 2.0
+                x1, y1 = x + l * math.cos(a), y + l * math.sin(a)
+                segments[n, k] = (_strokes_q3(x, -8192, 8191), _strokes_q3(y, -8192, 8191), _strokes_q3(x1, -8192, 8191),
+                                  _strokes_q3(y1, -8192, 8191), r)
+                x, y, k = x1, y1, k + 1
+        counts[n] = k
+    return segments, counts
+
+
+def attach_strokes(raw, spec, seed, positions):
+    """``raw`` with ``raw['erase_strokes']`` = (``spec``, ``seed``, int64 ``positions`` [N]): the one place that writes the key
+    ``strokes_batch`` reads.  The training loop numbers its items by their position in the sampler's stream; the scores and the
+    sample grid by the person (seed 0, ``raw_idx``)."""
+    positions = np.asarray(positions, np.int64).reshape(-1)
+    assert positions.shape == (int(raw['raw_idx'].shape[0]),)
+    raw['erase_strokes'] = dict(spec=strokes_spec(spec), seed=int(seed), positions=positions)
+    return raw
+
+
+def strokes_batch(raw, erase, erase_hw, S):
+    """What both training builders call straight after ``jitter_batch``: (erase, erase_hw) for the assemble entry.  With
+    ``raw['erase_strokes']`` (``attach_strokes``) the masks are drawn on the padded ``S x S`` square in one launch for the batch
+    (pasta_erase_strokes_u8): uint8 [N, S, S] of 0 / 1 with sizes (S, S), after mirroring and jittering and never mirrored.  A
+    batch without the key comes back as it is and launches nothing."""
+    if 'erase_strokes' not in raw:
+        return erase, erase_hw
+    strokes = raw['erase_strokes']
+    n = int(erase.shape[0])
+    positions = np.asarray(strokes['positions'], np.int64)
+    assert positions.shape == (n,)
+    segments, counts = strokes_segments(strokes['spec'], strokes['seed'], positions, S)
+    assert segments.shape == (n, STROKES_SEGMENTS, 5) and ((counts >= 0) & (counts <= STROKES_SEGMENTS)).all()   # the entry clamps; say so here
+    dev = erase.device
+    segments_d = torch.from_numpy(segments).to(dev, non_blocking=True)
+    counts_d = torch.from_numpy(counts).to(dev, non_blocking=True)
+    mask = torch.empty([n, S, S], dtype=torch.uint8, device=dev)
+    sizes = torch.full([n, 2], S, dtype=torch.int32, device=dev)
+    P = _native.ptr
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().pasta_erase_strokes_u8(P(segments_d), P(counts_d), P(mask), n, S, _native.stream()))
+    return mask, sizes
+
+
 def upload_images(raw, device):
     """``raw`` with its photographs and label maps (every ``*image`` / ``*parsing`` tensor) on ``device``; key points, names and
     indices stay on the host.  The pair builders stack a batch of ``training.dataset.collate_pairs`` after this, on the device."""
@@ -352,6 +455,7 @@ class FullBodyBatchBuilder:
         erase, erase_hw = upload_erase(raw, dev, n)
         image, parsing, keypoints, erase = mirror_batch(raw, image, parsing, keypoints, erase, erase_hw)
         image, parsing, keypoints = jitter_batch(raw, image, parsing, keypoints)
+        erase, erase_hw = strokes_batch(raw, erase, erase_hw, H)
         limbs, joints, quads, present = device_tables(keypoints, keypoints, (H - W) // 2, dev)
         u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)

@@ -27,6 +27,7 @@ training set's photograph as target, ``gt_parsing`` and erase mask (include/past
 
     pasta_tryon_mirror_u8                 the mirrored people of a ``mirror_people`` batch (training/tryon_batch.py, mirror_batch)
     pasta_tryon_jitter_u8                 the jittered people of a numbered batch (training/tryon_batch.py, jitter_batch)
+    pasta_erase_strokes_u8                the drawn erase masks of a batch with ``erase_strokes`` (training/tryon_batch.py, strokes_batch)
     pasta_pose_stickman_u8, pasta_palm_mask_u8     as above
     pasta_tryon_masks_u8                  retain mask, gt_parsing and the person's own two garments in one pass, the 256 set's entry
     patch_pipeline.normalize_outfit_batch everyone their own donor: N solves; the eroded part masks of the upper composite kept
@@ -39,7 +40,7 @@ from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import pairs_batch_as_outfits
 from training.tryon_batch import (OUTFIT_OUTPUTS, FullBodyBatch, allocator, device_tables, jitter_batch, mirror_batch, output_tensors, shift_keypoints,
-                                  upload_erase, upload_images, upload_person)
+                                  strokes_batch, upload_erase, upload_images, upload_person)
 from training.tryon_pairs import TryOnPairBatch
 
 PALM_BOXES = (35, 20)       # get_hand_mask of the 512 set: upper arm 35 x 35, forearm 20 x 20 (dataset.py:1790, :1795)
@@ -189,6 +190,7 @@ class FullBodyRegionBatchBuilder:
         erase, erase_hw = upload_erase(raw, dev, n)
         image, parsing, kp, erase = mirror_batch(raw, image, parsing, kp, erase, erase_hw)
         image, parsing, kp = jitter_batch(raw, image, parsing, kp)
+        erase, erase_hw = strokes_batch(raw, erase, erase_hw, H)
         limbs, joints, quads, present = device_tables(kp, kp, lp, dev)
         u8 = allocator(torch.uint8, dev)
         stick, palm, retain_mask, gt = u8(n, H, H, 3), u8(n, H, H), u8(n, H, H), u8(n, H, H)

@@ -1,4 +1,5 @@
-"""What the two try-on command lines, test.py and test_512.py, share: the options the reference declares and this project's own
+"""What the two try-on command lines, test.py and test_512.py, share (and, of the options, the training and scoring command lines:
+--storage, --erase-masks, --erase-strokes): the options the reference declares and this project's own
 (each command line lists its options itself, in the order --help prints them), the refusal of a snapshot that is not a local
 file, loading ``G_ema``, the loader over a test data set, the generator's call sequence, the --scores report, and the ONE loop
 that dresses a data set (``dress``): build, z, generate, score, convert, write.
@@ -58,6 +59,61 @@ def shared_options(dataroot_help, batchsize):
 STORAGE_DTYPES = {'snapshot': None, 'f32': 'float32', 'bf16': 'bfloat16', 'f16': 'float16'}
 storage_option = click.option('--storage', help='Activation storage the generator runs in: as pickled (snapshot), or f32, bf16, f16 '
                               '[default: snapshot]', type=click.Choice(list(STORAGE_DTYPES)))
+
+# --erase-masks, --erase-strokes: where a training item's erase mask comes from.  train_wo_flow_fullbody.py records
+# them with the run; calc_metrics.py's default is what the snapshot recorded.  ``erase_options`` decorates both commands.
+ERASE_STROKES_HELP = ('With --erase-masks strokes: comma-separated strokes=1..8, vertices=1..8, length=0.01..0.5, width=0.01..0.25 '
+                      '(of the square\'s side), turn=0..180 (degrees) [default: strokes=6,vertices=6,length=0.25,width=0.12,turn=60]')
+
+
+def erase_options(erase_masks_default):
+    options = [
+        click.option('--erase-masks', help='Erase masks: the files of train_random_mask_acgpn, none, or strokes drawn on the GPU '
+                     '[default: %s]' % erase_masks_default, type=click.Choice(['files', 'none', 'strokes'])),
+        click.option('--erase-strokes', help=ERASE_STROKES_HELP, metavar='SPEC')]
+
+    def decorate(f):
+        for option in reversed(options):
+            f = option(f)
+        return f
+    return decorate
+
+
+def parse_name_values(text):
+    """``name=value,name=value`` -> a dict of floats; a ValueError names what is not name=value, a name given twice or a value
+    that is no number."""
+    spec = {}
+    for pair in text.split(','):
+        name, eq, value = pair.partition('=')
+        name = name.strip()
+        if not eq or not name:
+            raise ValueError(f'{pair!r} is not name=value')
+        if name in spec:
+            raise ValueError(f'{name} is given twice')
+        try:
+            spec[name] = float(value)
+        except ValueError:
+            raise ValueError(f'{name}={value.strip()} is not a number')
+    return spec
+
+
+def erase_mask_kwargs(erase_masks, erase_strokes):
+    """``--erase-masks`` and ``--erase-strokes`` (None where not given) -> the keyword arguments they add to the training data set:
+    none for ``files``, so that such a run records what it always did.  A ValueError carries the option's name."""
+    from training.tryon_batch import strokes_spec
+    erase_masks = 'files' if erase_masks is None else erase_masks
+    if erase_strokes is not None and erase_masks != 'strokes':
+        raise ValueError(f'--erase-strokes needs --erase-masks strokes (it is {erase_masks})')
+    if erase_masks == 'files':
+        return {}
+    if erase_masks == 'none':
+        return dict(erase_masks='none')
+    try:
+        spec = strokes_spec(parse_name_values(erase_strokes) if erase_strokes is not None else {})
+    except ValueError as err:
+        raise ValueError(f'--erase-strokes: {err}')
+    return dict(erase_masks='strokes', erase_strokes=spec)
+
 
 # --png-encoder: who turns the uint8 batch into PNG files (DESIGN 8g): PIL in this process, one image at a time, or the GPU.  The
 # option comes with ``shared_options`` and hands the commands' callbacks no argument: its value is recorded in the click context,
