@@ -899,6 +899,19 @@ int pasta_grid_assemble(const uint8_t* denorm_upper, const uint8_t* denorm_lower
                         const uint8_t* retain_mask, const uint8_t* norm_img, const uint8_t* norm_img_lower, float* const* outputs,
                         int lo, int n, int gnum, int H, int ph, int pw, int c_upper, int c_lower, void* stream);
 
+/* Additive at ABI 22.  pasta_grid_assemble's garment tensors for the unpaired pass of TRAINING (training/swap_outfits.py; DESIGN
+ * 8k): sample i of a batch of n wears the upper patches of person upper_src[i] and the lower patches of person lower_src[i]
+ * (int32, DEVICE memory) of T people.  outputs: a HOST array of 5 device pointers, swap_denorm_upper_input /
+ * swap_denorm_lower_input [n,3,H,H] = x * (1 / 127.5f) - 1 of denorm_upper / denorm_lower [n,H,H,3] (sample i's own images, made
+ * by pasta_grid_composite_eroded_u8 with the same tables), swap_denorm_upper_mask / swap_denorm_lower_mask [n,1,H,H] = channel
+ * sum > 0, swap_style_input [n,c_upper+c_lower,ph,pw]: the channels of norm_img [T,ph,pw,c_upper] of the upper source followed by
+ * those of norm_img_lower [T,ph,pw,c_lower] of the lower source.  The same device arithmetic as pasta_grid_assemble: for the
+ * sources its cell has, the five tensors are that entry's bit for bit.  A source outside 0 .. T - 1 reads nothing (its style
+ * channels are those of zero bytes).  H and pw multiples of 4, n <= 65535. */
+int pasta_swap_assemble(const uint8_t* denorm_upper, const uint8_t* denorm_lower, const uint8_t* norm_img, const uint8_t* norm_img_lower,
+                        const int32_t* upper_src, const int32_t* lower_src, float* const* outputs, int n, int T, int H, int ph, int pw,
+                        int c_upper, int c_lower, void* stream);
+
 /* save_image_grid (:182-203): images [n, C, H, W] fp32 (C = 1 or 3) become tiles first .. first + n - 1 of a uint8 canvas
  * [canvas_h, canvas_w, C]; tile t sits at tile row t / gw + oy and tile column t % gw + ox (the grid proper: gw = gnum,
  * ox = oy = 1; the side column: gw = 1, ox = 0, oy = 1; the top row: ox = 1, oy = 0, its corner tile a tile of zeros at
@@ -983,6 +996,34 @@ int pasta_ssim_loss(const float* x, const float* y, float* loss, float* dmaps /*
 int pasta_ssim_loss_backward(const float* x, const float* y, const float* dmaps, const float* grad_loss /* device scalar */,
                              float* dx /* [N,3,H,Wt], written everywhere, 0 outside the crop */, int N, int H, int Wt, int c0, int W,
                              void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * The region L1 term of training's unpaired pass (torch_utils/ops/region_l1_loss.py; csrc/region_l1.hip).  Additive
+ * at ABI 22.  An image generated for a person in somebody else's garments has no photograph to be compared with, but three
+ * regions of it have a known answer.
+ * images: K (1 .. 4) fp32 [N,3,H,H] tensors x_k; targets retain, upper, lower: fp32 [N,3,H,H]; keep: uint8 [N,H,H];
+ * upper_mask, lower_mask: fp32 [N,1,H,H].  A pixel belongs to exactly one region: 0 (keep) where keep != 0, else 1 where
+ * upper_mask != 0, else 2 where lower_mask != 0, else none; the targets t_0, t_1, t_2 are retain, upper, lower.
+ *   out[k][r] = (1 / M) * sum over the pixels of region r and the 3 channels of |x_k - t_r|,   M = 3 N H H,
+ * so that out[k][0] + out[k][1] + out[k][2] is the part of F.l1_loss that falls into the regions.  |x - t| is one fp32
+ * subtraction; the sums are fp64, one partial per workgroup and a fixed-order second launch, no floating-point atomics: two
+ * calls on the same input give the same bits, and an empty region gives exactly 0.  out: fp32 [K, 3] in device memory.
+ * Gradient with respect to the images only: with upstream g fp32 [K, 3] (device memory) and q = g[k][r] / (float)M (one fp32
+ * division), dx_k = +q where x > t, -q where x < t, 0 where they are equal or the pixel has no region.
+ * H a multiple of 4 (four pixels per thread, 16-byte accesses), H <= 4096, N <= 65535.
+ * ------------------------------------------------------------------------- */
+/* Bytes of the partials of pasta_region_l1_loss; 0 for a shape that is refused. */
+int64_t pasta_region_l1_loss_workspace(int N, int H);
+/* images: a HOST array of K device pointers.  maps: null for the values alone, else a HOST array of K device pointers to uint8
+ * [N,H,H]: per pixel bits 0-1 = region + 1 (0: none) and bits 2-3, 4-5, 6-7 = channel 0, 1, 2: 0 where x == t, 1 where x > t,
+ * 2 where x < t -- all pasta_region_l1_loss_backward reads. */
+int pasta_region_l1_loss(const float* const* images, const float* retain, const float* upper, const float* lower, const uint8_t* keep,
+                         const float* upper_mask, const float* lower_mask, float* out /* [K,3] */, uint8_t* const* maps,
+                         void* workspace, int64_t workspace_bytes, int K, int N, int H, void* stream);
+/* dx: a HOST array of K device pointers to fp32 [N,3,H,H], every element written by one thread.  grad_out: fp32 [K, 3] in device
+ * memory, read by the kernel: nothing waits for the host. */
+int pasta_region_l1_loss_backward(const uint8_t* const* maps, const float* grad_out /* device [K,3] */, float* const* dx, int K, int N,
+                                  int H, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * PNG files of a batch of RGB8 images, encoded on the GPU (torch_utils/ops/png_encode.py; csrc/png_encode.hip).

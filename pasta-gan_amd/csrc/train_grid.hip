@@ -4,7 +4,9 @@
 //   pasta_grid_composite_eroded_u8   denorm_clothes (:59-107) for every cell of one garment in one launch: patches and masks
 //                                    picked from the per-person pool through an index, every mask eroded 5 x 5;
 //   pasta_grid_assemble              the fp32 tensors G_ema takes for cells lo .. lo + n - 1 (:121-175, :580-583);
-//   pasta_image_grid_tile_u8         save_image_grid's conversion and tiling (:182-203) into the uint8 canvas.
+//   pasta_image_grid_tile_u8         save_image_grid's conversion and tiling (:182-203) into the uint8 canvas;
+//   pasta_swap_assemble              pasta_grid_assemble's garment tensors for a TRAINING batch whose samples wear a batch-mate's
+//                                    patches (training/swap_outfits.py): per-sample source tables in place of (lo, gnum).
 // Cell = row * gnum + col: row is the person (pose, retain, M_inv), col the clothes donor.
 #include "common.h"
 #include "tryon_common.h"      // Px4, load_px4, store4
@@ -100,6 +102,54 @@ __global__ __launch_bounds__(256) void grid_assemble_kernel(const uint8_t* __res
     store4(o.denorm_lower_mask + (int64_t)n * HH + pix, ml[0], ml[1], ml[2], ml[3]);
 }
 
+// ---- the swapped tensors of a training batch ----
+
+struct SwapOut {
+    float *denorm_upper_input, *denorm_lower_input, *denorm_upper_mask, *denorm_lower_mask, *style_input;
+};
+
+// grid_assemble_kernel's body for the unpaired pass of training (training/swap_outfits.py): sample n wears the upper patches of
+// person upper_src[n] and the lower patches of person lower_src[n] of the batch's T people, and den_u / den_l hold its own two
+// images.  The person's pose and retain are the paired batch's tensors and are not written again.  A source outside 0 .. T - 1
+// reads nothing: its style channels are those of zero bytes.
+__global__ __launch_bounds__(256) void swap_assemble_kernel(const uint8_t* __restrict__ den_u, const uint8_t* __restrict__ den_l,
+                                                            const uint8_t* __restrict__ norm_img, const uint8_t* __restrict__ norm_lower,
+                                                            const int32_t* __restrict__ upper_src, const int32_t* __restrict__ lower_src,
+                                                            SwapOut o, int T, int H, int ph, int pw, int CU, int CL) {
+    const int n = blockIdx.y;
+    const int HH = H * H;
+    const int pix = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (pix >= HH) {
+        const int q = pix - HH;
+        if (q >= ph * pw) return;
+        const int up = upper_src[n], low = lower_src[n];
+        const bool up_ok = up >= 0 && up < T, low_ok = low >= 0 && low < T;
+        const int CS = CU + CL;
+        for (int ch = 0; ch < CS; ch++) {
+            const bool ok = ch < CU ? up_ok : low_ok;
+            const uint8_t* src = ch < CU ? norm_img + ((int64_t)(up_ok ? up : 0) * ph * pw + q) * CU + ch
+                                         : norm_lower + ((int64_t)(low_ok ? low : 0) * ph * pw + q) * CL + ch - CU;
+            const int step = ch < CU ? CU : CL;
+            store4(o.style_input + ((int64_t)n * CS + ch) * ph * pw + q, grid_to_unit(ok ? src[0] : 0), grid_to_unit(ok ? src[step] : 0),
+                   grid_to_unit(ok ? src[2 * step] : 0), grid_to_unit(ok ? src[3 * step] : 0));
+        }
+        return;
+    }
+    const Px4 u = load_px4(den_u + ((int64_t)n * HH + pix) * 3), l = load_px4(den_l + ((int64_t)n * HH + pix) * 3);
+    for (int ch = 0; ch < 3; ch++) {
+        const int64_t oc = ((int64_t)n * 3 + ch) * HH + pix;
+        store4(o.denorm_upper_input + oc, grid_to_unit(u.v[ch]), grid_to_unit(u.v[3 + ch]), grid_to_unit(u.v[6 + ch]), grid_to_unit(u.v[9 + ch]));
+        store4(o.denorm_lower_input + oc, grid_to_unit(l.v[ch]), grid_to_unit(l.v[3 + ch]), grid_to_unit(l.v[6 + ch]), grid_to_unit(l.v[9 + ch]));
+    }
+    float mu[4], ml[4];
+    for (int j = 0; j < 4; j++) {
+        mu[j] = u.v[3 * j] + u.v[3 * j + 1] + u.v[3 * j + 2] > 0 ? 1.f : 0.f;
+        ml[j] = l.v[3 * j] + l.v[3 * j + 1] + l.v[3 * j + 2] > 0 ? 1.f : 0.f;
+    }
+    store4(o.denorm_upper_mask + (int64_t)n * HH + pix, mu[0], mu[1], mu[2], mu[3]);
+    store4(o.denorm_lower_mask + (int64_t)n * HH + pix, ml[0], ml[1], ml[2], ml[3]);
+}
+
 // ---- image grid tiling ----
 
 // save_image_grid:184-186 per element in fp32, as numpy evaluates it: one subtraction and one multiplication (a difference
@@ -168,6 +218,26 @@ extern "C" int pasta_grid_assemble(const uint8_t* denorm_upper, const uint8_t* d
     hipLaunchKernelGGL(grid_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, denorm_upper, denorm_lower, image, stick, retain_mask,
                        norm_img, norm_img_lower, o, lo, gnum, H, ph, pw, c_upper, c_lower);
     return launch_status("grid_assemble");
+}
+
+extern "C" int pasta_swap_assemble(const uint8_t* denorm_upper, const uint8_t* denorm_lower, const uint8_t* norm_img,
+                                   const uint8_t* norm_img_lower, const int32_t* upper_src, const int32_t* lower_src, float* const* outputs,
+                                   int n, int T, int H, int ph, int pw, int c_upper, int c_lower, void* stream) {
+    using namespace pasta;
+    PASTA_CHECK(denorm_upper && denorm_lower && norm_img && norm_img_lower && upper_src && lower_src && outputs, "swap_assemble: null pointer");
+    PASTA_CHECK(n >= 1 && n <= 65535 && T >= 1, "swap_assemble: %d samples of %d people", n, T);
+    PASTA_CHECK(H >= 4 && H <= 4096 && H % 4 == 0 && ph >= 1 && pw >= 4 && pw % 4 == 0 && c_upper >= 1 && c_lower >= 1,
+                "swap_assemble: bad shape (H and pw multiples of 4)");
+    SwapOut o;
+    float** f[5] = {&o.denorm_upper_input, &o.denorm_lower_input, &o.denorm_upper_mask, &o.denorm_lower_mask, &o.style_input};
+    for (int i = 0; i < 5; i++) {
+        PASTA_CHECK(outputs[i], "swap_assemble: output %d is null", i);
+        *f[i] = outputs[i];
+    }
+    dim3 grid((unsigned)(((H * H + ph * pw) / 4 + 255) / 256), (unsigned)n);
+    hipLaunchKernelGGL(swap_assemble_kernel, grid, dim3(256), 0, (hipStream_t)stream, denorm_upper, denorm_lower, norm_img, norm_img_lower,
+                       upper_src, lower_src, o, T, H, ph, pw, c_upper, c_lower);
+    return launch_status("swap_assemble");
 }
 
 extern "C" int pasta_image_grid_tile_u8(const float* images, uint8_t* canvas, int n, int C, int H, int W, int first, int gw, int ox, int oy,

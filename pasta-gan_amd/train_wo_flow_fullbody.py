@@ -26,6 +26,11 @@ people as photographed.
 ``--ssim_weight=5`` adds ``5 * (1 - mean SSIM)`` of each of the generator's two images against the photograph to its loss: the
 windows and constants ``recon_full`` reports, on the un-quantised images, value and gradient on the GPU.
 
+``--swap_weight=1`` adds an unpaired second pass: within every per-GPU round each person is also dressed in a batch-mate's garments
+(``--swap-region`` fullbody, upperbody or lowerbody), prepared on the GPU from the batch's own stages; both images of that pass go to
+the discriminator and are held to the regions with a known answer -- the kept parts against the photograph, each garment region
+against its warped patches -- by a region L1 term scaled by ``--l1_weight``.
+
 ``--erase-masks=strokes`` trains without the mask files of ``train_random_mask_acgpn``: every item's erase mask is drawn on the GPU,
 random thick polylines on the padded square, anew at every visit from the run's seed and the item's position in the sampler's
 stream (``--erase-strokes=strokes=6,vertices=6,length=0.25,width=0.12,turn=60`` sets their strengths); ``--erase-masks=none`` erases
@@ -77,7 +82,8 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                                gamma=None, kimg=None, batch=None, aug=None, p=None, target=None, augpipe=None, resume=None, freezed=None,
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
-                               mirror_people=None, jitter_people=None, ssim_weight=None, erase_masks=None, erase_strokes=None):
+                               mirror_people=None, jitter_people=None, ssim_weight=None, erase_masks=None, erase_strokes=None,
+                               swap_weight=None, swap_region=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -197,6 +203,14 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         raise UserError('--ssim_weight must be non-negative')
     if ssim_weight:
         config.loss_kwargs.update(ssim_weight=ssim_weight, ssim_width=content_width)
+    # --swap_weight, --swap-region (own options): the unpaired pass on every person in a batch-mate's garments.  Absent or 0 adds no
+    # key, here or below
+    if swap_weight is not None and not swap_weight >= 0:
+        raise UserError('--swap_weight must be non-negative')
+    if swap_region is not None and not swap_weight:
+        raise UserError('--swap-region needs a positive --swap_weight: without one nobody is dressed in another\'s garments')
+    if swap_weight:
+        config.loss_kwargs.update(swap_weight=swap_weight)
     config.ema_kimg, config.ema_rampup = spec.ema, spec.ramp
     args.total_kimg = spec.kimg
     args.batch_size = spec.mb
@@ -272,6 +286,14 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         desc += f'-{storage}'
     if ssim_weight:
         desc += f'-ssim{ssim_weight:g}'
+    if swap_weight:
+        # the swap group is one per-GPU round: the donors of a round come from that round, so accumulation does not change them
+        if args.batch_gpu < 2:
+            raise UserError(f'--swap_weight needs at least 2 samples per GPU round, --batch={args.batch_size} on {gpus} GPUs gives '
+                            f'{args.batch_gpu}: a person\'s donor is a batch-mate of the same round')
+        swap_region = 'fullbody' if swap_region is None else swap_region
+        desc += f'-swap{swap_weight:g}' + (swap_region if swap_region != 'fullbody' else '')
+        args.swap_outfits = dnnlib.EasyDict(region=swap_region, group=args.batch_gpu)
     if fp32:
         config.G_kwargs.synthesis_kwargs.num_fp16_res = config.D_kwargs.num_fp16_res = 0
         config.G_kwargs.synthesis_kwargs.conv_clamp = config.D_kwargs.conv_clamp = None
@@ -325,7 +347,7 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
             continue
         option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people', 'jitter_people': 'jitter-people', 'erase_masks': 'erase-masks',
-                         'erase_strokes': 'erase-strokes'}.get(name, name)
+                         'erase_strokes': 'erase-strokes', 'swap_region': 'swap-region'}.get(name, name)
         raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
                         (f' ({recorded})' if recorded is not None else ''))
 
@@ -474,6 +496,10 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--l1_weight', help='G L1 loss weight', type=float)
 @click.option('--ssim_weight', help='G SSIM loss weight: 1 - mean SSIM against the photograph, the windows recon_full reports [default: 0]',
               type=float)
+@click.option('--swap_weight', help='Weight of the unpaired pass: every person also in a batch-mate\'s garments, through D and a region L1 '
+              'term [default: 0]', type=float)
+@click.option('--swap-region', help='What the donor gives in the unpaired pass [default: fullbody]',
+              type=click.Choice(['fullbody', 'upperbody', 'lowerbody']))
 @click.option('--vgg_weight', help='vgg loss weight (runs from random weights: the checkpoint cannot be obtained; --ssim_weight is the '
               'structural term that needs none)', type=float)
 @click.option('--contextual_weight', help='contextual loss weight (refused unless 0: its checkpoint cannot be obtained; see --ssim_weight)',
@@ -516,6 +542,9 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
     strokes = args.training_set_kwargs.get('erase_strokes')
     print(f'Erase masks:        {args.training_set_kwargs.get("erase_masks", "files")}' +
           (f' ({",".join(f"{k}={v:g}" for k, v in strokes.items())})' if strokes else ''))
+    swap = args.get('swap_outfits')
+    if swap:
+        print(f'Swapped outfits:    weight {args.cfg.loss_kwargs.swap_weight:g}, {swap.region}, groups of {swap.group}')
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

@@ -9,7 +9,9 @@ when ``vgg_weight > 0``; its pretrained weights (``./checkpoints/vgg19-dcbb9e9d.
 file is loaded when present and otherwise ``vgg_random_init=True`` must be passed (random weights: the arithmetic and
 its cost are the reference's, the loss value is not meaningful).  The contextual term needs a second unobtainable
 checkpoint and is rejected unless its weight is 0; ``ssim_weight`` adds this package's own structural term, 1 - mean SSIM of
-each generated image against the photograph (torch_utils/ops/ssim_loss.py), which needs no checkpoint; statistics reporting
+each generated image against the photograph (torch_utils/ops/ssim_loss.py), which needs no checkpoint; ``swap_weight`` adds this
+package's own unpaired pass: every person again in a batch-mate's garments (training/swap_outfits.py), both images of
+that pass through the discriminator and held to their three known regions (torch_utils/ops/region_l1_loss.py); statistics reporting
 is a no-op hook; style mixing picks its cutoff
 without a host synchronisation.
 """
@@ -22,6 +24,7 @@ import torch
 from torch_utils import misc
 from torch_utils.ops import conv2d_gradfix
 from torch_utils.ops import ssim_loss
+from torch_utils.ops import region_l1_loss
 
 #----------------------------------------------------------------------------
 
@@ -99,7 +102,7 @@ class StyleGAN2Loss(Loss):
     def __init__(self, device, G_mapping, G_synthesis, G_const_encoding, G_style_encoding, D, augment_pipe=None,
                  style_mixing_prob=0.9, r1_gamma=10, pl_batch_shrink=2, pl_decay=0.01, pl_weight=0, l1_weight=50,
                  vgg_weight=50, contextual_weight=1.0, mask_weight=1.0, report_fn=None, vgg_random_init=False, ssim_weight=0,
-                 ssim_width=None):
+                 ssim_width=None, swap_weight=0):
         super().__init__()
         if contextual_weight > 0:
             raise NotImplementedError('the contextual term needs ./checkpoints/vgg19_conv.pth, which cannot be obtained here; '
@@ -107,6 +110,8 @@ class StyleGAN2Loss(Loss):
                                       'structural term that needs no checkpoint')
         if ssim_weight < 0 or (ssim_weight > 0 and ssim_width is None):
             raise ValueError('ssim_weight must not be negative, and a positive one needs ssim_width, the content width of the images')
+        if swap_weight < 0:
+            raise ValueError('swap_weight must not be negative')
         if pl_weight != 0:
             raise NotImplementedError('path-length regularisation is unreachable in the reference (wrong arity at '
                                       'loss_wo_flow_fullbody.py:185-205; train.sh sets --pl_weight 0)')
@@ -125,6 +130,7 @@ class StyleGAN2Loss(Loss):
         self.mask_weight = mask_weight
         self.ssim_weight = ssim_weight
         self.ssim_width = ssim_width
+        self.swap_weight = swap_weight
         self.report = report_fn if report_fn is not None else (lambda name, value: None)
         if vgg_weight > 0:
             self.criterionVGG = VGGLoss(device, random_init=vgg_random_init)
@@ -197,13 +203,45 @@ class StyleGAN2Loss(Loss):
             logits = self.D(merge(imgs), merge(cs))
         return [t.reshape(n, *logits.shape[1:]) for t in logits.reshape(G, k, B, *logits.shape[1:]).unbind(dim=1)]
 
+    def _swap_inputs(self, swap):
+        """The six swapped tensors of a round (training/swap_outfits.py's SWAP_KEYS without their prefix) when the unpaired pass
+        runs, else None.  A positive weight without all of them is an error, and so is the 'torch' exchange."""
+        if not self.swap_weight > 0:
+            return None
+        names = ['swap_style_input', 'swap_denorm_upper_input', 'swap_denorm_lower_input', 'swap_denorm_upper_mask', 'swap_denorm_lower_mask',
+                 'swap_keep']
+        missing = [name for name in names if swap.get(name) is None]
+        if missing:
+            raise ValueError('swap_weight > 0 needs the swapped tensors of the batch (a builder\'s build(raw, swap=...)); missing: ' +
+                             ', '.join(missing))
+        wrapped = [name for name in ('G_mapping', 'G_synthesis', 'G_const_encoding', 'G_style_encoding', 'D')
+                   if isinstance(getattr(self, name), torch.nn.parallel.DistributedDataParallel)]
+        if wrapped:
+            raise NotImplementedError('swap_weight > 0 with ddp_mode=\'torch\': a second forward pass through one DistributedDataParallel '
+                                      'wrapper per backward is not supported (wrapped: ' + ', '.join(wrapped) + '); use the default '
+                                      'ddp_mode=\'flat\'')
+        return {name[len('swap_'):]: swap[name] for name in names}
+
+    def _run_G_swapped(self, gen_z, retain, pose, swap, sync, encoder_sync):
+        """The unpaired pass: the style code of the swapped patches and both images of the person in them, with the same gen_z."""
+        with misc.ddp_sync(self.G_style_encoding, encoder_sync):
+            swap_c, swap_feats = self.G_style_encoding(swap['style_input'], retain)
+        x_s, x_s_ft, _, _ws = self.run_G(gen_z, swap_c, pose, swap_feats, swap['denorm_upper_mask'], swap['denorm_lower_mask'],
+                                         swap['denorm_upper_input'], swap['denorm_lower_input'], sync=sync)
+        return x_s, x_s_ft, swap_c
+
     def accumulate_gradients(self, phase, real_img, gen_z, style_input, retain, pose, denorm_upper_input, denorm_lower_input,
-                             denorm_upper_mask, denorm_lower_mask, gt_parsing, sync, gain):
+                             denorm_upper_mask, denorm_lower_mask, gt_parsing, sync, gain, swap_style_input=None,
+                             swap_denorm_upper_input=None, swap_denorm_lower_input=None, swap_denorm_upper_mask=None,
+                             swap_denorm_lower_mask=None, swap_keep=None):
         assert phase in ['Gmain', 'Greg', 'Gboth', 'Dmain', 'Dreg', 'Dboth']
         do_Gmain = (phase in ['Gmain', 'Gboth'])
         do_Dmain = (phase in ['Dmain', 'Dboth'])
         do_Dr1   = (phase in ['Dreg', 'Dboth']) and (self.r1_gamma != 0)
         softplus = torch.nn.functional.softplus
+        swap = self._swap_inputs(dict(swap_style_input=swap_style_input, swap_denorm_upper_input=swap_denorm_upper_input,
+                                      swap_denorm_lower_input=swap_denorm_lower_input, swap_denorm_upper_mask=swap_denorm_upper_mask,
+                                      swap_denorm_lower_mask=swap_denorm_lower_mask, swap_keep=swap_keep))
 
         # The style code doubles as the conditioning label of both real and generated images (:114-116).
         # Only Gmain back-propagates into the encoder. The reference passes `sync` here in every phase
@@ -217,7 +255,12 @@ class StyleGAN2Loss(Loss):
         # Gmain: maximise logits for both generated images, plus reconstruction terms (:119-182).
         if do_Gmain:
             gen_img, gen_finetune_img, pred_parsing, _ws = self.run_G(gen_z, gen_c, pose, cat_feats, *g_args, sync=sync)
-            gen_logits, gen_finetune_logits = self.run_D_multi([gen_img, gen_finetune_img], [gen_c, gen_c], sync=False)
+            if swap is None:
+                gen_logits, gen_finetune_logits = self.run_D_multi([gen_img, gen_finetune_img], [gen_c, gen_c], sync=False)
+            else:       # the unpaired pass: all four generated images in the one discriminator pass
+                x_s, x_s_ft, swap_c = self._run_G_swapped(gen_z, retain, pose, swap, sync, sync)
+                gen_logits, gen_finetune_logits, swap_logits, swap_finetune_logits = self.run_D_multi(
+                    [gen_img, gen_finetune_img, x_s, x_s_ft], [gen_c, gen_c, swap_c, swap_c], sync=False)
             self.report('Loss/scores/fake', gen_logits)
             loss_Gmain = softplus(-gen_logits).mean()
             loss_Gmain_finetune = softplus(-gen_finetune_logits).mean()
@@ -243,6 +286,18 @@ class StyleGAN2Loss(Loss):
                 loss_G = loss_G + (loss_G_SSIM + loss_G_finetune_SSIM) / 2
                 self.report('Loss/G/ssim', loss_G_SSIM)
                 self.report('Loss/G/ssim_finetune', loss_G_finetune_SSIM)
+            if swap is not None:
+                # the three regions of a swapped image with a known answer: the kept parts against retain, each garment region
+                # against its warped patches; per region "the part of F.l1_loss that falls in it", so l1_weight scales it alike
+                regions = region_l1_loss.region_l1_loss((x_s.to(torch.float32), x_s_ft.to(torch.float32)), retain, swap['denorm_upper_input'],
+                                                        swap['denorm_lower_input'], swap['keep'], swap['denorm_upper_mask'],
+                                                        swap['denorm_lower_mask']) * self.l1_weight
+                loss_swap = (softplus(-swap_logits).mean() + softplus(-swap_finetune_logits).mean()) / 2
+                loss_G = loss_G + self.swap_weight * (loss_swap + regions.sum() / 2)
+                self.report('Loss/scores/fake_swap', swap_logits)
+                self.report('Loss/G/swap_loss', loss_swap)
+                for r, name in enumerate(('keep', 'upper', 'lower')):
+                    self.report('Loss/G/swap_' + name, regions[:, r].mean())
             self.report('Loss/scores/fake_finetune', gen_finetune_logits)
             self.report('Loss/G/loss', loss_Gmain)
             self.report('Loss/G/loss_finetune', loss_Gmain_finetune)
@@ -255,25 +310,41 @@ class StyleGAN2Loss(Loss):
         # calls (:227, :254) add up to the gradient of the summed loss.
         if do_Dmain and not do_Dr1:
             gen_img, gen_finetune_img, _, _ws = self.run_G(gen_z, gen_c, pose, cat_feats, *g_args, sync=False)
-            gen_logits, gen_finetune_logits, real_logits = self.run_D_multi(
-                [gen_img, gen_finetune_img, real_img.detach()], [gen_c, gen_c, real_c], sync=sync)
+            loss_Dswap = 0
+            if swap is None:
+                gen_logits, gen_finetune_logits, real_logits = self.run_D_multi(
+                    [gen_img, gen_finetune_img, real_img.detach()], [gen_c, gen_c, real_c], sync=sync)
+            else:       # the swapped fakes join the pass: five batches
+                x_s, x_s_ft, swap_c = self._run_G_swapped(gen_z, retain, pose, swap, False, False)
+                gen_logits, gen_finetune_logits, swap_logits, swap_finetune_logits, real_logits = self.run_D_multi(
+                    [gen_img, gen_finetune_img, x_s, x_s_ft, real_img.detach()], [gen_c, gen_c, swap_c, swap_c, real_c], sync=sync)
+                self.report('Loss/scores/fake_swap', swap_logits)
+                loss_Dswap = self.swap_weight * (softplus(swap_logits).mean() + softplus(swap_finetune_logits).mean()) / 2
             self.report('Loss/scores/fake', gen_logits)
             self.report('Loss/scores/fake_finetune', gen_finetune_logits)
             self.report('Loss/scores/real', real_logits)
             self.report('Loss/signs/real', real_logits.sign())
             loss_Dgen, loss_Dgen_finetune, loss_Dreal = softplus(gen_logits), softplus(gen_finetune_logits), softplus(-real_logits)
             self.report('Loss/D/loss', loss_Dgen + loss_Dreal)
-            ((loss_Dgen.mean() + loss_Dgen_finetune.mean()) / 2 + loss_Dreal.mean()).mul(gain).backward()
+            ((loss_Dgen.mean() + loss_Dgen_finetune.mean()) / 2 + loss_Dreal.mean() + loss_Dswap).mul(gain).backward()
             return
 
         # Dmain: minimise logits for generated images (:210-228).
         loss_Dgen = 0
         if do_Dmain:
             gen_img, gen_finetune_img, _, _ws = self.run_G(gen_z, gen_c, pose, cat_feats, *g_args, sync=False)
-            gen_logits, gen_finetune_logits = self.run_D_multi([gen_img, gen_finetune_img], [gen_c, gen_c], sync=False)   # gets synced by loss_Dreal
+            loss_Dswap = 0
+            if swap is None:
+                gen_logits, gen_finetune_logits = self.run_D_multi([gen_img, gen_finetune_img], [gen_c, gen_c], sync=False)   # gets synced by loss_Dreal
+            else:
+                x_s, x_s_ft, swap_c = self._run_G_swapped(gen_z, retain, pose, swap, False, False)
+                gen_logits, gen_finetune_logits, swap_logits, swap_finetune_logits = self.run_D_multi(
+                    [gen_img, gen_finetune_img, x_s, x_s_ft], [gen_c, gen_c, swap_c, swap_c], sync=False)
+                self.report('Loss/scores/fake_swap', swap_logits)
+                loss_Dswap = self.swap_weight * (softplus(swap_logits).mean() + softplus(swap_finetune_logits).mean()) / 2
             loss_Dgen = softplus(gen_logits)
             loss_Dgen_finetune = softplus(gen_finetune_logits)
-            ((loss_Dgen.mean() + loss_Dgen_finetune.mean()) / 2).mul(gain).backward()
+            ((loss_Dgen.mean() + loss_Dgen_finetune.mean()) / 2 + loss_Dswap).mul(gain).backward()
 
         # Dmain: maximise logits for real images.  Dr1: R1 penalty on real images (:232-254).
         if do_Dmain or do_Dr1:

@@ -185,11 +185,13 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
     return out, pm
 
 
-def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_factor=2):
+def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_factor=2, want_matrices=False):
     """``normalize`` (dataset.py:838-927) for a batch on the GPU.  Images and 3-channel masks: uint8 [N, H, W, 3] CUDA tensors;
     ``joints`` [N, 18, 3] (host).  Returns the reference's tuple, batched:
     (norm_img [N,h,w,30], norm_img_lower [N,h,w,12], denorm_upper [N,H,W,3], denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32,
-     denorm_hand_masks [N,4,H,W,1], clothes_masks [N,h,w,30], clothes_masks_lower [N,h,w,12])."""
+     denorm_hand_masks [N,4,H,W,1], clothes_masks [N,h,w,30], clothes_masks_lower [N,h,w,12]).  ``want_matrices``: two more values,
+    the float64 patch -> image maps [N,10,3,3] and valid flags [N,10] that part_matrices solved here (training/swap_outfits.py
+    warps a batch-mate's patches back with them instead of solving the people again)."""
     upper_img, lower_img, upper_mask, lower_mask = _u8(upper_img), _u8(lower_img), _u8(upper_mask), _u8(lower_mask)
     n, height, width, _ = upper_img.shape
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
@@ -211,7 +213,8 @@ def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_fa
     hwc = lambda t: t.permute(0, 2, 3, 1, 4).reshape(n, ph, pw, -1)            # parts concatenated along the channel axis (:918-921)
     m_invs = torch.from_numpy(np.where(valid[..., None, None], back, 0.0).astype(np.float32))
     hand_masks = part_masks[:, list(ARM_PARTS)].unsqueeze(-1)
-    return hwc(p_img), hwc(p_img_l), den_u, den_l, m_invs, hand_masks, hwc(p_mask), hwc(p_mask_l)
+    out = (hwc(p_img), hwc(p_img_l), den_u, den_l, m_invs, hand_masks, hwc(p_mask), hwc(p_mask_l))
+    return out + (back, valid) if want_matrices else out
 
 
 UPPER_PARTS = 6             # the test set: parts 0..5 from the clothes donor, 6..9 from the person (dataset.py:1470-1478)
@@ -260,7 +263,8 @@ def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
 
 
-def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2, want_part_masks=False):
+def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2, want_part_masks=False,
+                           want_matrices=False):
     """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch of
     OUTFITS on the GPU.  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image,
     3-channel mask) followed by the N lower garments.  ``people_joints`` [M, 18, 3] float64 (host): the batch's DISTINCT people,
@@ -273,7 +277,8 @@ def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx,
     matrix is missing is zeros; a part whose M_inv is missing is skipped.  Returns (patches [N,10,h,w,3], patches_lower
     [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the
     person's), upper_valid, lower_valid, person_valid [N,10] bool).  ``want_part_masks``: an eleventh value, the eroded 0 / 1
-    masks [N,10,H,W] of the upper composite's parts."""
+    masks [N,10,H,W] of the upper composite's parts.  ``want_matrices``: two last values, the PERSONS' float64 patch -> image maps
+    [N,10,3,3] and valid flags [N,10] as solved here (training/swap_outfits.py)."""
     garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
@@ -296,4 +301,5 @@ def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx,
     den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
     m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
     out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_p)
-    return out + (part_masks,) if want_part_masks else out
+    out = out + (part_masks,) if want_part_masks else out
+    return out + (back, valid_p) if want_matrices else out

@@ -1,0 +1,110 @@
+"""The swapped inputs of training's unpaired pass (``--swap_weight``): every person of a training batch dressed in a
+batch-mate's garments, prepared on the GPU from the stages the batch builder has just made.
+
+    donors          the donor rule: a deterministic roll inside each group of ``batch_gpu`` consecutive samples
+    source_tables   whose upper and whose lower patches every sample wears, by swap region
+    swap_tensors    pasta_grid_composite_eroded_u8 twice (upper, lower) and pasta_swap_assemble (csrc/train_grid.hip): the five fp32
+                    tensors, by the sample grid's rule (training/snapshot_grid.py) -- the donor's patches warped back with the
+                    PERSON's M_inv, every mask eroded 5 x 5
+    attach          what both training builders call: the six extra tensors of a batch
+
+The warp-back matrices are the float64 ones the builder's normalisation has already solved (``want_matrices`` of
+``patch_pipeline.normalize_batch`` / ``normalize_outfit_batch``): the people's 8 x 8 systems are not solved a second time.
+``retain`` and ``pose`` of the swapped pass are the paired batch's own tensors; no erase mask is applied."""
+
+import ctypes
+
+import numpy as np
+import torch
+
+from torch_utils.ops import _native
+from training import patch_pipeline
+
+ERODE_RADIUS = 2            # every part, as training/snapshot_grid.py's cells
+REGIONS = ('fullbody', 'upperbody', 'lowerbody')
+# the five tensors pasta_swap_assemble writes, in its order, and the keep mask of the region L1 term
+SWAP_OUTPUTS = ['swap_denorm_upper_input', 'swap_denorm_lower_input', 'swap_denorm_upper_mask', 'swap_denorm_lower_mask', 'swap_style_input']
+SWAP_KEYS = SWAP_OUTPUTS + ['swap_keep']
+
+
+def donors(n, group):
+    """int64 [n]: the donor of every sample of a rank's batch.  The swap group is ``group`` consecutive samples (one accumulation
+    round); inside it the donor of sample i is its successor, the last one's the first.  No random numbers: the sampler shuffles."""
+    n, b = int(n), int(group)
+    if b < 2 or n % b != 0:
+        raise ValueError('swapped outfits need groups of at least 2 samples that divide the batch: %d samples, groups of %d' % (n, b))
+    i = np.arange(n, dtype=np.int64)
+    g = i // b
+    return g * b + (i - g * b + 1) % b
+
+
+def source_tables(n, group, region='fullbody'):
+    """(upper_src, lower_src) int64 [n]: whose upper and whose lower patches sample i wears."""
+    if region not in REGIONS:
+        raise ValueError('swap region %s is invalid.' % region)
+    own, donor = np.arange(int(n), dtype=np.int64), donors(n, group)
+    return (donor if region != 'lowerbody' else own), (donor if region != 'upperbody' else own)
+
+
+def _composite(pool, mask_pool, index, minv, valid, ph, pw, H):
+    dev = pool.device
+    n, parts = index.shape
+    index_t = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(dev, non_blocking=True)
+    minv_t = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
+    valid_t = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(dev, non_blocking=True)
+    out = torch.empty([n, H, H, 3], dtype=torch.uint8, device=dev)
+    P = _native.ptr
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().pasta_grid_composite_eroded_u8(P(pool), P(mask_pool), P(index_t), P(minv_t), P(valid_t), P(out), n, parts,
+                                                                   int(pool.shape[0]), ph, pw, H, H, ERODE_RADIUS, _native.stream()))
+    return out
+
+
+def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src):
+    """The five fp32 tensors of SWAP_OUTPUTS for arbitrary source tables.  ``stages``: the builder's kept stages (``norm_img``,
+    ``norm_img_lower`` [N, ph, pw, 3 p], ``norm_clothes_mask*``, ``retain_mask``); ``back`` float64 [N, 10, 3, 3] / ``valid``
+    [N, 10]: the people's patch -> image maps as ``patch_pipeline.part_matrices`` returned them; ``lower_parts``: the parts also
+    cut from the lower garment (the builder's).  Three launches."""
+    norm_img, norm_lower = stages['norm_img'], stages['norm_img_lower']
+    dev = norm_img.device
+    n, ph, pw = int(norm_img.shape[0]), int(norm_img.shape[1]), int(norm_img.shape[2])
+    cu, cl = int(norm_img.shape[3]), int(norm_lower.shape[3])
+    pu, pl = cu // 3, cl // 3
+    H = int(stages['retain_mask'].shape[1])
+    upper_src, lower_src = (np.asarray(t, np.int64).reshape(-1) for t in (upper_src, lower_src))
+    lower_parts = np.asarray(lower_parts)
+    assert upper_src.shape == (n,) and lower_src.shape == (n,) and len(lower_parts) == pl and back.shape[:2] == (n, 10)
+    assert upper_src.min() >= 0 and upper_src.max() < n and lower_src.min() >= 0 and lower_src.max() < n, 'a source outside the batch'
+
+    # the pool of patches [T, ph, pw, 3]: part k of person i at i * pu + k, lower part k at n * pu + i * pl + k (SnapshotGrid's)
+    per_part = lambda t, p: t.reshape(n, ph, pw, p, 3).permute(0, 3, 1, 2, 4).reshape(n * p, ph, pw, 3)
+    pool = torch.cat([per_part(norm_img, pu), per_part(norm_lower, pl)]).contiguous()
+    mask_pool = torch.cat([per_part(stages['norm_clothes_mask'], pu), per_part(stages['norm_clothes_mask_lower'], pl)]).contiguous()
+    inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(n, pu, 9)
+    index_u = upper_src[:, None] * pu + np.arange(pu)
+    index_l = n * pu + lower_src[:, None] * pl + np.arange(pl)
+    den_u = _composite(pool, mask_pool, index_u, inv, valid, ph, pw, H)
+    den_l = _composite(pool, mask_pool, index_l, inv[:, lower_parts], valid[:, lower_parts], ph, pw, H)
+
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    t = dict(swap_denorm_upper_input=f32(n, 3, H, H), swap_denorm_lower_input=f32(n, 3, H, H), swap_denorm_upper_mask=f32(n, 1, H, H),
+             swap_denorm_lower_mask=f32(n, 1, H, H), swap_style_input=f32(n, cu + cl, ph, pw))
+    outs = (ctypes.c_void_p * 5)(*[t[k].data_ptr() for k in SWAP_OUTPUTS])
+    up_t = torch.from_numpy(upper_src.astype(np.int32)).to(dev, non_blocking=True)
+    low_t = torch.from_numpy(lower_src.astype(np.int32)).to(dev, non_blocking=True)
+    norm_img, norm_lower = norm_img.contiguous(), norm_lower.contiguous()
+    P = _native.ptr
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().pasta_swap_assemble(P(den_u), P(den_l), P(norm_img), P(norm_lower), P(up_t), P(low_t), outs, n, n, H, ph, pw,
+                                                        cu, cl, _native.stream()))
+    return t
+
+
+def attach(tensors, stages, back, valid, builder, swap):
+    """``tensors`` with the six SWAP_KEYS added for ``swap`` = dict(region=, group=): the five swapped tensors by the donor rule
+    and ``swap_keep``, the ``retain_mask`` stage (uint8 [N, H, H])."""
+    n = int(stages['retain_mask'].shape[0])
+    upper_src, lower_src = source_tables(n, swap['group'], swap.get('region', 'fullbody'))
+    tensors.update(swap_tensors(stages, back, valid, builder.lower_parts, upper_src, lower_src))
+    tensors['swap_keep'] = stages['retain_mask']
+    return tensors

@@ -310,13 +310,15 @@ def _numbered_batches(loader, people_jitter, random_seed, num_gpus, rank, cur_ni
         t += num_gpus * n
         yield raw
 
-def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs, cur_nimg=0, people_jitter=None):
+def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs, cur_nimg=0, people_jitter=None,
+                  swap_outfits=None):
     """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263).  ``cur_nimg``: the images
     a continued run has consumed; one iteration takes ``batch_size`` positions of the sampler's global stream whatever the
     number of ranks, so the stream goes on at that position.  ``people_jitter``: a specification of
     ``training.tryon_batch.jitter_spec``; the batches are then numbered (``_numbered_batches``) and the builder jitters them.  A
     data set opened with ``erase_masks='strokes'`` has its batches numbered as well, with or without the jitter, and the builder
-    draws their erase masks."""
+    draws their erase masks.  ``swap_outfits``: dict(region=, group=) of training/swap_outfits.py; every batch then also carries the
+    swapped inputs of the unpaired pass, made from its own stages after the mirroring and the jitter."""
     from training import dataset as dataset_module
     from training.tryon_batch import builder_for, jitter_spec
     training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
@@ -328,12 +330,15 @@ def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_
     if people_jitter is not None or erase_strokes is not None:
         loader = _numbered_batches(loader, jitter_spec(people_jitter) if people_jitter is not None else None, random_seed, num_gpus, rank,
                                    int(cur_nimg), erase_strokes=erase_strokes)
+    if swap_outfits is not None:
+        swap_outfits = dict(swap_outfits)
+        return training_set, builder, (builder.build(raw, swap=swap_outfits) for raw in loader)
     return training_set, builder, (builder.build(raw) for raw in loader)
 
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
                   training_set_kwargs=None, data_loader_kwargs=None, run_dir=None, total_kimg=25000, kimg_per_tick=4,
                   image_snapshot_ticks=50, network_snapshot_ticks=50, resume_pkl=None, abort_fn=None, snapshot_gnum=23, metrics=None,
-                  metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None):
+                  metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None, swap_outfits=None):
     """Without ``run_dir``: run ``total_iters`` iterations and write nothing.  Without ``training_set_kwargs`` the data is
     synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
     path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
@@ -345,7 +350,9 @@ def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0
     the newest one kept.  ``resume_state``: the path of such a file; the run goes on from it exactly where the other stopped.
     The state file records the text of ``run_dir``'s training_options.json, when the command line has written one, for ``--continue``.
     ``people_jitter``: a specification of ``training.tryon_batch.jitter_spec`` (``--jitter-people``); the training batches, and only
-    they, are jittered per item by the run's seed and the item's position in the sampler's stream."""
+    they, are jittered per item by the run's seed and the item's position in the sampler's stream.
+    ``swap_outfits``: dict(region=, group=) (``--swap_weight``, ``--swap-region``); the training batches, and only they,
+    also carry every person in a batch-mate's garments, which a loss with ``swap_weight > 0`` trains on."""
     device = device if device is not None else torch.device('cuda', rank)
     if resume_state is not None and run_dir is None:
         raise ValueError('resume_state needs a run_dir: only a training run is continued')
@@ -354,14 +361,14 @@ def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0
     if run_dir is not None:
         return training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs,
                             data_loader_kwargs, total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn,
-                            snapshot_gnum, metrics, metric_set_kwargs, save_state, resume_state, people_jitter)
+                            snapshot_gnum, metrics, metric_set_kwargs, save_state, resume_state, people_jitter, swap_outfits)
     step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
     if training_set_kwargs is None:
         data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
         batches = iter(lambda: data, None)
     else:
         _, _, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs,
-                                      people_jitter=people_jitter)
+                                      people_jitter=people_jitter, swap_outfits=swap_outfits)
     for it in range(total_iters):
         step.run(next(batches))
         if progress_fn is not None:
@@ -379,7 +386,7 @@ def sample_images(G_ema, grid, grid_z, batch_gpu):
 
 def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs, data_loader_kwargs,
                  total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn, snapshot_gnum, metrics=None,
-                 metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None):
+                 metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None, swap_outfits=None):
     """The reference's training_loop (:247-654) around ``TrainingStep.run``.  Returns the step; on rank 0 it carries the
     ``snapshot_grid`` and the ``grid_z`` the sample images were drawn with."""
     import psutil
@@ -402,7 +409,8 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
     if rank == 0:
         print('Loading training set...')
     training_set, builder, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs,
-                                                   cur_nimg=int(state['cur_nimg']) if state is not None else 0, people_jitter=people_jitter)
+                                                   cur_nimg=int(state['cur_nimg']) if state is not None else 0, people_jitter=people_jitter,
+                                                   swap_outfits=swap_outfits)
     if rank == 0:
         print()
         print('Num images: ', len(training_set))

@@ -37,6 +37,7 @@ import torch
 
 from torch_utils.ops import _native
 from training import patch_pipeline
+from training.swap_outfits import SWAP_KEYS, attach as attach_swap
 
 # dataset.py:43-52 (1-based joint pairs)
 LIMBSEQ = ((2, 3), (2, 6), (3, 4), (4, 5), (6, 7), (7, 8), (2, 9), (9, 10), (10, 11), (2, 12), (12, 13), (13, 14), (2, 1), (1, 15),
@@ -420,6 +421,7 @@ def shift_keypoints(keypoints, left_padding):
 
 class FullBodyBatch:
     """The interface TrainingStep.run consumes (as SyntheticFullBodyBatch): ``tensors`` (the nine KEYS), ``batch``, ``split``.
+    A batch built with ``swap`` also carries the six SWAP_KEYS of training/swap_outfits.py, which ``split`` passes along.
     ``stages`` holds the uint8 intermediates when the builder was asked to keep them; ``image`` is the photographs' uint8 batch
     [N, H, W, 3] as the builder uploaded it (the reconstruction metric scores against it), mirrored and jittered where the batch says so."""
     KEYS = ['real_img', 'style_input', 'retain', 'pose', 'denorm_upper_input', 'denorm_lower_input',
@@ -433,11 +435,13 @@ class FullBodyBatch:
 
     def split(self, batch_gpu):
         parts = {k: v.split(batch_gpu) for k, v in self.tensors.items()}
-        return [{k: parts[k][i] for k in self.KEYS} for i in range(len(parts['real_img']))]
+        keys = self.KEYS + [k for k in SWAP_KEYS if k in parts]          # a batch built with ``swap`` carries six more
+        return [{k: parts[k][i] for k in keys} for i in range(len(parts['real_img']))]
 
 
 class FullBodyBatchBuilder:
-    """``build(raw_batch)``: a batch of ``training.dataset.collate`` -> FullBodyBatch on ``device``."""
+    """``build(raw_batch)``: a batch of ``training.dataset.collate`` -> FullBodyBatch on ``device``.  ``swap`` = dict(region=,
+    group=): the batch also carries the swapped inputs of training/swap_outfits.py, made from this batch's stages."""
 
     # how the warp-back matrices of this builder's stages are formed (training/snapshot_grid.py forms them again per cell):
     # the parts also cut from the lower garment, part_matrices' x_pad and shin_fallback, and whether the key points are shifted
@@ -448,7 +452,7 @@ class FullBodyBatchBuilder:
         self.device = torch.device(device)
         self.box_factor = box_factor
 
-    def build(self, raw, keep_stages=False):
+    def build(self, raw, keep_stages=False, swap=None):
         dev = self.device
         image, parsing, keypoints = upload_person(raw, dev, 'FullBodyBatchBuilder')
         n, H, W, _ = image.shape
@@ -466,8 +470,8 @@ class FullBodyBatchBuilder:
             _native.check(lib.pasta_pose_stickman_u8(P(limbs), P(joints), P(stick), n, H, W, STICK_THICKNESS, STICK_RADIUS, s))
             _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
             _native.check(lib.pasta_tryon_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), *[P(g) for g in garments], n, H, W, s))
-        norm_img, norm_lower, den_u, den_l, m_invs, hand_masks, norm_mask, norm_mask_lower = patch_pipeline.normalize_batch(
-            *garments, keypoints, self.box_factor)
+        norm_img, norm_lower, den_u, den_l, m_invs, hand_masks, norm_mask, norm_mask_lower, back, valid = patch_pipeline.normalize_batch(
+            *garments, keypoints, self.box_factor, want_matrices=True)
         norm_img, norm_lower, den_u, den_l = (t.contiguous() for t in (norm_img, norm_lower, den_u, den_l))
         arm = hand_masks.reshape(n, 4, H, H).contiguous()
         ph, pw, cu, cl = norm_img.shape[1], norm_img.shape[2], norm_img.shape[3], norm_lower.shape[3]
@@ -477,12 +481,14 @@ class FullBodyBatchBuilder:
                                                    P(arm), P(erase), P(erase_hw), outs, n, H, W, ph, pw, cu, cl,
                                                    int(erase.shape[1]), int(erase.shape[2]), _native.stream()))
         stages = None
-        if keep_stages:
+        if keep_stages or swap is not None:
             stages = dict(stick=stick, palm=palm, retain_mask=retain_mask, gt_parsing=gt, upper_img=garments[0], lower_img=garments[1],
                           upper_mask=garments[2], lower_mask=garments[3], norm_img=norm_img, norm_img_lower=norm_lower,
                           denorm_upper=den_u, denorm_lower=den_l, arm_masks=arm, M_invs=m_invs, norm_clothes_mask=norm_mask.contiguous(),
                           norm_clothes_mask_lower=norm_mask_lower.contiguous())
-        return FullBodyBatch(t, stages, image)
+        if swap is not None:
+            attach_swap(t, stages, back, valid, self, swap)
+        return FullBodyBatch(t, stages if keep_stages else None, image)
 
 
 def builder_for(training_set, device):

@@ -39,6 +39,7 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import pairs_batch_as_outfits
+from training.swap_outfits import attach as attach_swap
 from training.tryon_batch import (OUTFIT_OUTPUTS, FullBodyBatch, allocator, device_tables, jitter_batch, mirror_batch, output_tensors, shift_keypoints,
                                   strokes_batch, upload_erase, upload_images, upload_person)
 from training.tryon_pairs import TryOnPairBatch
@@ -173,7 +174,8 @@ class TryOnRegionBatchBuilder(TryOnOutfitBatchBuilder):
 class FullBodyRegionBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate`` at 512 x 320 -> FullBodyBatch on ``device``, which
     TrainingStep.run consumes as the 256 builder's.  ``stages`` (``keep_stages``) carry the 256 builder's names, so that
-    training/snapshot_grid.py has one code path."""
+    training/snapshot_grid.py has one code path.  ``swap`` = dict(region=, group=), as the 256 builder's: the batch also carries
+    the swapped inputs of training/swap_outfits.py."""
 
     # see FullBodyBatchBuilder: parts 0, 6..9 are also cut from the lower garment; key points shifted in float64, x_pad = 0
     lower_parts, x_pad, shin_fallback, shifted = patch_pipeline.LOWER_PARTS_512, 0, False, True
@@ -182,7 +184,7 @@ class FullBodyRegionBatchBuilder:
         self.device = torch.device(device)
         self.box_factor = box_factor
 
-    def build(self, raw, keep_stages=False):
+    def build(self, raw, keep_stages=False, swap=None):
         dev = self.device
         image, parsing, kp = upload_person(raw, dev, 'FullBodyRegionBatchBuilder')
         n, H, W, _ = image.shape
@@ -204,8 +206,8 @@ class FullBodyRegionBatchBuilder:
             _native.check(lib.pasta_tryon_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), P(garment_img[:n]), P(garment_img[n:]),
                                                    P(garment_mask[:n]), P(garment_mask[n:]), n, H, W, s))
         own = np.arange(n)                  # everyone wears their own garments: the N people are solved once
-        patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, _, part_masks = patch_pipeline.normalize_outfit_batch(
-            garment_img, garment_mask, shift_keypoints(kp, lp), own, own, own, self.box_factor, want_part_masks=True)
+        patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, _, part_masks, back, valid = patch_pipeline.normalize_outfit_batch(
+            garment_img, garment_mask, shift_keypoints(kp, lp), own, own, own, self.box_factor, want_part_masks=True, want_matrices=True)
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
         arm_a, arm_b = patch_pipeline.ARM_PARTS[2], patch_pipeline.ARM_PARTS[3]
         t, outs = output_tensors(FullBodyBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)
@@ -214,10 +216,12 @@ class FullBodyRegionBatchBuilder:
                                                                 P(den_l), P(part_masks), arm_a, arm_b, P(erase), P(erase_hw), outs, n, H, W,
                                                                 pu, pl, ph, pw, int(erase.shape[1]), int(erase.shape[2]), _native.stream()))
         stages = None
-        if keep_stages:
+        if keep_stages or swap is not None:
             hwc = lambda x: x.permute(0, 2, 3, 1, 4).reshape(n, ph, pw, -1).contiguous()       # parts along the channel axis, as at 256
             stages = dict(stick=stick, palm=palm, retain_mask=retain_mask, gt_parsing=gt, upper_img=garment_img[:n], lower_img=garment_img[n:],
                           upper_mask=garment_mask[:n], lower_mask=garment_mask[n:], norm_img=hwc(patches), norm_img_lower=hwc(patches_l),
                           denorm_upper=den_u, denorm_lower=den_l, arm_masks=part_masks[:, list(patch_pipeline.ARM_PARTS)].contiguous(),
                           M_invs=m_invs, norm_clothes_mask=hwc(mask_patches), norm_clothes_mask_lower=hwc(mask_patches_l))
-        return FullBodyBatch(t, stages, image)
+        if swap is not None:
+            attach_swap(t, stages, back, valid, self, swap)
+        return FullBodyBatch(t, stages if keep_stages else None, image)
