@@ -1026,6 +1026,39 @@ int pasta_region_l1_loss_backward(const uint8_t* const* maps, const float* grad_
                                   int H, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The contextual loss of training's unpaired pass (torch_utils/ops/contextual_loss.py; csrc/contextual_loss.hip).
+ * Additive at ABI 22.  It asks for the same texture without asking where: every position of x looks for its nearest position
+ * of y, and is rewarded for how much that neighbour stands out among all of y's positions.
+ * For feature maps x, y ([B, C, N], N positions, y constant) and the channel mean mu_p of y at position p:
+ *   x^_p = (x_p - mu_p) / (|x_p - mu_p|_2 + 2.22e-16),  y^_p likewise          (unit vectors; the front-end forms them)
+ *   d_ij = 1 - x^_i . y^_j                                                       (cosine distance, never stored)
+ *   m_i  = min over the valid columns j of d_ij,  j*_i the smallest column that attains it,  c_i = 1 / (m_i + 1e-3)
+ *   w_ij = exp((1 - d_ij c_i) / h),  S_i = sum over the valid columns of w_ij,  A_ij = w_ij / S_i
+ *   CX_i = max_j A_ij = exp((1 - m_i c_i) / h) / S_i                             (w falls as d grows)
+ *   loss_b = -log((1 / R) sum over the valid rows of CX_i),  R the number of valid rows.
+ * Masks (uint8 [B, N], null = all valid, the same bits as all ones): a column with y_valid == 0 does not exist; a row with
+ * x_valid == 0 does not enter the mean and gets gradient 0; a sample without a valid row or a valid column has loss 0 and
+ * gradient 0.  Every exponent is at most 1 / h, so nothing is rescaled.
+ * Gradient with respect to x^ only.  With E_i = sum_j A_ij d_ij and upstream g_b,
+ *   dloss/dx^_i = g_b CX_i / (sum over valid rows of CX) ((c_i / h) (sum_j A_ij y^_j - y^_{j*}) - c_i^2 (E_i - m_i) / h  y^_{j*}).
+ * The entries take x^ and y^; all products are the exact fp32-input MFMA; the workspace is O(B N): per row m, j*, S, E, CX,
+ * per sample 1 / sum CX.  Row sums run in a fixed order (one lane, its twin, the other column half, then fp64 over the rows):
+ * two calls on the same input give the same bits.  Column tiles (64) without a valid column and row groups (32) without a valid
+ * row are skipped.  B <= 65535, 1 <= C <= 512, 1 <= N <= 16384; ragged C and N are handled in the kernels.
+ * ------------------------------------------------------------------------- */
+/* Bytes of the row statistics of pasta_contextual_loss, which pasta_contextual_loss_backward reads; 0 for a refused shape. */
+int64_t pasta_contextual_loss_workspace(int B, int C, int N);
+/* xh, yh: fp32 [B,C,N] unit vectors; loss: fp32 [B] in device memory.  The workspace must live until the backward has run. */
+int pasta_contextual_loss(const float* xh, const float* yh, const uint8_t* x_valid /* [B,N] or null */,
+                          const uint8_t* y_valid /* [B,N] or null */, float* loss /* [B] */, void* workspace, int64_t workspace_bytes,
+                          int B, int C, int N, float h, void* stream);
+/* dxh: fp32 [B,C,N], every element written by one thread.  yhT: yh as [B,N,C].  workspace: as pasta_contextual_loss left it for the
+ * same xh, yh and masks.  grad_loss: fp32 [B] in device memory, read by the kernel: nothing waits for the host. */
+int pasta_contextual_loss_backward(const float* xh, const float* yh, const float* yhT, const uint8_t* x_valid, const uint8_t* y_valid,
+                                   const void* workspace, const float* grad_loss /* device [B] */, float* dxh, int B, int C, int N, float h,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------- *
  * PNG files of a batch of RGB8 images, encoded on the GPU (torch_utils/ops/png_encode.py; csrc/png_encode.hip).
  * The stream is this project's own choice of a valid PNG:
  *   1. every row is filter type 4 (Paeth, bpp 3) with left, up and upper-left taken from the ORIGINAL pixels, zero outside the

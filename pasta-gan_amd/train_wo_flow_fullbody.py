@@ -29,7 +29,9 @@ windows and constants ``recon_full`` reports, on the un-quantised images, value 
 ``--swap_weight=1`` adds an unpaired second pass: within every per-GPU round each person is also dressed in a batch-mate's garments
 (``--swap-region`` fullbody, upperbody or lowerbody), prepared on the GPU from the batch's own stages; both images of that pass go to
 the discriminator and are held to the regions with a known answer -- the kept parts against the photograph, each garment region
-against its warped patches -- by a region L1 term scaled by ``--l1_weight``.
+against its warped patches -- by a region L1 term scaled by ``--l1_weight``.  ``--swap_cx_weight=W`` adds, inside
+that pass, a contextual term on the garment regions: VGG-19 relu3_1 / relu4_1 features of the swapped images against those of the
+warped patches, matched wherever they lie, value and gradient on the GPU without an N x N matrix.
 
 ``--erase-masks=strokes`` trains without the mask files of ``train_random_mask_acgpn``: every item's erase mask is drawn on the GPU,
 random thick polylines on the padded square, anew at every visit from the run's seed and the item's position in the sampler's
@@ -83,7 +85,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
                                mirror_people=None, jitter_people=None, ssim_weight=None, erase_masks=None, erase_strokes=None,
-                               swap_weight=None, swap_region=None):
+                               swap_weight=None, swap_region=None, swap_cx_weight=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -211,6 +213,13 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         raise UserError('--swap-region needs a positive --swap_weight: without one nobody is dressed in another\'s garments')
     if swap_weight:
         config.loss_kwargs.update(swap_weight=swap_weight)
+    # --swap_cx_weight (own option): the contextual term of the unpaired pass, same texture without asking where
+    if swap_cx_weight is not None and not swap_cx_weight >= 0:
+        raise UserError('--swap_cx_weight must be non-negative')
+    if swap_cx_weight and not swap_weight:
+        raise UserError('--swap_cx_weight needs a positive --swap_weight: it is a term of the unpaired pass')
+    if swap_cx_weight:
+        config.loss_kwargs.update(swap_cx_weight=swap_cx_weight)
     config.ema_kimg, config.ema_rampup = spec.ema, spec.ramp
     args.total_kimg = spec.kimg
     args.batch_size = spec.mb
@@ -292,7 +301,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
             raise UserError(f'--swap_weight needs at least 2 samples per GPU round, --batch={args.batch_size} on {gpus} GPUs gives '
                             f'{args.batch_gpu}: a person\'s donor is a batch-mate of the same round')
         swap_region = 'fullbody' if swap_region is None else swap_region
-        desc += f'-swap{swap_weight:g}' + (swap_region if swap_region != 'fullbody' else '')
+        desc += f'-swap{swap_weight:g}' + (swap_region if swap_region != 'fullbody' else '') + (f'-cx{swap_cx_weight:g}' if swap_cx_weight else '')
         args.swap_outfits = dnnlib.EasyDict(region=swap_region, group=args.batch_gpu)
     if fp32:
         config.G_kwargs.synthesis_kwargs.num_fp16_res = config.D_kwargs.num_fp16_res = 0
@@ -500,6 +509,10 @@ class CommaSeparatedList(click.ParamType):
               'term [default: 0]', type=float)
 @click.option('--swap-region', help='What the donor gives in the unpaired pass [default: fullbody]',
               type=click.Choice(['fullbody', 'upperbody', 'lowerbody']))
+@click.option('--swap_cx_weight', help='Weight, within the unpaired pass, of a contextual term on its garment regions: VGG-19 relu3_1 and relu4_1 '
+              'features of the swapped images against those of the warped patches, matched wherever they lie.  Needs --swap_weight.  The '
+              'features come from ./checkpoints/vgg19-dcbb9e9d.pth when it exists, otherwise from seeded RANDOM weights, whose values mean '
+              'only what random features mean [default: 0]', type=float)
 @click.option('--vgg_weight', help='vgg loss weight (runs from random weights: the checkpoint cannot be obtained; --ssim_weight is the '
               'structural term that needs none)', type=float)
 @click.option('--contextual_weight', help='contextual loss weight (refused unless 0: its checkpoint cannot be obtained; see --ssim_weight)',
@@ -544,7 +557,8 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
           (f' ({",".join(f"{k}={v:g}" for k, v in strokes.items())})' if strokes else ''))
     swap = args.get('swap_outfits')
     if swap:
-        print(f'Swapped outfits:    weight {args.cfg.loss_kwargs.swap_weight:g}, {swap.region}, groups of {swap.group}')
+        print(f'Swapped outfits:    weight {args.cfg.loss_kwargs.swap_weight:g}, {swap.region}, groups of {swap.group}' +
+              (f', contextual weight {args.cfg.loss_kwargs.swap_cx_weight:g}' if args.cfg.loss_kwargs.get('swap_cx_weight') else ''))
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

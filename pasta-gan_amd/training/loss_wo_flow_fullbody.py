@@ -11,7 +11,9 @@ its cost are the reference's, the loss value is not meaningful).  The contextual
 checkpoint and is rejected unless its weight is 0; ``ssim_weight`` adds this package's own structural term, 1 - mean SSIM of
 each generated image against the photograph (torch_utils/ops/ssim_loss.py), which needs no checkpoint; ``swap_weight`` adds this
 package's own unpaired pass: every person again in a batch-mate's garments (training/swap_outfits.py), both images of
-that pass through the discriminator and held to their three known regions (torch_utils/ops/region_l1_loss.py); statistics reporting
+that pass through the discriminator and held to their three known regions (torch_utils/ops/region_l1_loss.py), and with
+``swap_cx_weight`` also to the texture of the warped patches wherever it lies (torch_utils/ops/contextual_loss.py:
+the reference's contextual loss, which it constructs and never applies, over this file's VGG-19 taps); statistics reporting
 is a no-op hook; style mixing picks its cutoff
 without a host synchronisation.
 """
@@ -25,6 +27,7 @@ from torch_utils import misc
 from torch_utils.ops import conv2d_gradfix
 from torch_utils.ops import ssim_loss
 from torch_utils.ops import region_l1_loss
+from torch_utils.ops import contextual_loss
 
 #----------------------------------------------------------------------------
 
@@ -62,9 +65,12 @@ class VGG19_Feature(torch.nn.Module):
             if convs == VGG19_TAPS[-1]:
                 break
 
-    def forward(self, x):
+    def forward(self, x, upto=len(VGG19_TAPS)):
+        """The first ``upto`` taps; the layers behind the last of them do not run."""
         feats, convs = [], 0
         for kind, idx in self.layers:
+            if len(feats) == upto:
+                break
             if kind == 'pool':
                 x = torch.nn.functional.max_pool2d(x, kernel_size=2, stride=2)
                 continue
@@ -102,7 +108,7 @@ class StyleGAN2Loss(Loss):
     def __init__(self, device, G_mapping, G_synthesis, G_const_encoding, G_style_encoding, D, augment_pipe=None,
                  style_mixing_prob=0.9, r1_gamma=10, pl_batch_shrink=2, pl_decay=0.01, pl_weight=0, l1_weight=50,
                  vgg_weight=50, contextual_weight=1.0, mask_weight=1.0, report_fn=None, vgg_random_init=False, ssim_weight=0,
-                 ssim_width=None, swap_weight=0):
+                 ssim_width=None, swap_weight=0, swap_cx_weight=0):
         super().__init__()
         if contextual_weight > 0:
             raise NotImplementedError('the contextual term needs ./checkpoints/vgg19_conv.pth, which cannot be obtained here; '
@@ -112,6 +118,9 @@ class StyleGAN2Loss(Loss):
             raise ValueError('ssim_weight must not be negative, and a positive one needs ssim_width, the content width of the images')
         if swap_weight < 0:
             raise ValueError('swap_weight must not be negative')
+        if swap_cx_weight < 0 or (swap_cx_weight > 0 and not swap_weight > 0):
+            raise ValueError('swap_cx_weight must not be negative, and a positive one needs a positive swap_weight: it is a term of '
+                             'the unpaired pass')
         if pl_weight != 0:
             raise NotImplementedError('path-length regularisation is unreachable in the reference (wrong arity at '
                                       'loss_wo_flow_fullbody.py:185-205; train.sh sets --pl_weight 0)')
@@ -131,9 +140,12 @@ class StyleGAN2Loss(Loss):
         self.ssim_weight = ssim_weight
         self.ssim_width = ssim_width
         self.swap_weight = swap_weight
+        self.swap_cx_weight = swap_cx_weight
         self.report = report_fn if report_fn is not None else (lambda name, value: None)
         if vgg_weight > 0:
             self.criterionVGG = VGGLoss(device, random_init=vgg_random_init)
+        if swap_cx_weight > 0:      # the checkpoint when the file exists, else the class's seeded random weights (the same either way)
+            self.cx_vgg = self.criterionVGG.vgg if vgg_weight > 0 else VGG19_Feature(device, random_init=True)
         class_weight = torch.tensor([1, 2, 2, 3, 3, 3], dtype=torch.float32, device=device)
         self.ce_parsing = torch.nn.CrossEntropyLoss(ignore_index=255, weight=class_weight)
 
@@ -230,6 +242,43 @@ class StyleGAN2Loss(Loss):
                                          swap['denorm_upper_input'], swap['denorm_lower_input'], sync=sync)
         return x_s, x_s_ft, swap_c
 
+    SWAP_CX_TAPS = ((2, 4), (3, 8))      # (tap of VGG19_Feature, its stride): relu3_1 and relu4_1
+
+    @staticmethod
+    def swap_cx_inputs(images, swap):
+        """What the contextual term of the unpaired pass compares: the two garment regions exactly as region_l1_loss forms them (keep
+        first, then upper, then lower), the images inside their union, and the target -- the warped upper patches in the upper
+        region, the lower ones in the lower region, 0 elsewhere.  -> (cat of the masked images, target, (upper, lower) regions)."""
+        kept = (swap['keep'] != 0)[:, None]
+        upper = ~kept & (swap['denorm_upper_mask'] != 0)
+        lower = ~kept & ~upper & (swap['denorm_lower_mask'] != 0)
+        zero = torch.zeros([], dtype=torch.float32, device=kept.device)
+        target = torch.where(upper, swap['denorm_upper_input'], torch.where(lower, swap['denorm_lower_input'], zero))
+        union = (upper | lower).to(torch.float32)
+        return torch.cat([x.to(torch.float32) * union for x in images]), target, (upper, lower)
+
+    @staticmethod
+    def swap_cx_valid(region, stride):
+        """uint8 [N, H / stride, W / stride]: the feature positions at least half inside the region."""
+        return (torch.nn.functional.avg_pool2d(region.to(torch.float32), stride) >= 0.5)[:, 0].to(torch.uint8)
+
+    def swap_cx_terms(self, images, swap, loss_fn=contextual_loss.contextual_loss):
+        """(upper, lower): the contextual loss of each garment region, averaged over the samples, the taps and the images.  One VGG
+        pass with gradient over all images, one without over the target; the same mask serves rows and columns."""
+        k = len(images)
+        stacked, target, regions = self.swap_cx_inputs(images, swap)
+        feats = self.cx_vgg(stacked, upto=self.SWAP_CX_TAPS[-1][0] + 1)
+        with torch.no_grad():
+            target_feats = self.cx_vgg(target, upto=self.SWAP_CX_TAPS[-1][0] + 1)
+        terms = []
+        for region in regions:
+            per_tap = []
+            for tap, stride in self.SWAP_CX_TAPS:
+                valid = self.swap_cx_valid(region, stride).repeat(k, 1, 1)
+                per_tap.append(loss_fn(feats[tap], target_feats[tap].detach().repeat(k, 1, 1, 1), valid, valid).mean())
+            terms.append(sum(per_tap) / len(per_tap))
+        return tuple(terms)
+
     def accumulate_gradients(self, phase, real_img, gen_z, style_input, retain, pose, denorm_upper_input, denorm_lower_input,
                              denorm_upper_mask, denorm_lower_mask, gt_parsing, sync, gain, swap_style_input=None,
                              swap_denorm_upper_input=None, swap_denorm_lower_input=None, swap_denorm_upper_mask=None,
@@ -298,6 +347,11 @@ class StyleGAN2Loss(Loss):
                 self.report('Loss/G/swap_loss', loss_swap)
                 for r, name in enumerate(('keep', 'upper', 'lower')):
                     self.report('Loss/G/swap_' + name, regions[:, r].mean())
+                if self.swap_cx_weight > 0:      # same texture, wherever it lies
+                    cx_upper, cx_lower = self.swap_cx_terms((x_s, x_s_ft), swap)
+                    loss_G = loss_G + self.swap_weight * self.swap_cx_weight * (cx_upper + cx_lower) / 2
+                    self.report('Loss/G/swap_cx_upper', cx_upper)
+                    self.report('Loss/G/swap_cx_lower', cx_lower)
             self.report('Loss/scores/fake_finetune', gen_finetune_logits)
             self.report('Loss/G/loss', loss_Gmain)
             self.report('Loss/G/loss_finetune', loss_Gmain_finetune)
