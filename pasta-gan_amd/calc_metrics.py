@@ -1,8 +1,10 @@
 """Score a network snapshot with the metrics of ``metrics/`` (the reference's calc_metrics.py, restricted to what this package
-registers: the paired-reconstruction metrics ``recon_full`` and ``recon2k``).
+registers: the paired-reconstruction metrics ``recon_full`` and ``recon2k``, and the unpaired try-on metrics ``tryon_full`` and
+``tryon2k``, every person in the next person's garments scored by region -- DESIGN 8m).
 
     python calc_metrics.py --network runs/00000-x/network-snapshot-000200.pkl                  # on the snapshot's training tree
     python calc_metrics.py --network snapshot.pkl --metrics recon2k --data held_out_tree --gpus 8
+    python calc_metrics.py --network snapshot.pkl --metrics recon2k,tryon2k --data held_out_tree
 
 Without --data the snapshot's own ``training_set_kwargs`` name the tree; --data names another one of the same layout (a held-out
 tree; a tree of ``*_512_320`` folders is read as the 512 x 320 training set).  When the snapshot lies in a training run's directory (one with training_options.json), the result is also appended to
@@ -10,7 +12,8 @@ that directory's ``metric-<name>.jsonl``.  --network must name a local file: URL
 --storage f32 | bf16 | f16 scores the generator in that activation storage, whatever it was pickled with; the result line then
 carries a ``storage`` field.  --erase-masks files | none | strokes and --erase-strokes SPEC say where the erase masks of
 the scored batches come from, as train_wo_flow_fullbody.py's options do; their default is what the snapshot recorded, and
-``--erase-masks none`` scores a snapshot trained on mask files on a tree that has none.  One
+``--erase-masks none`` scores a snapshot trained on mask files on a tree that has none; the ``tryon_*`` metrics
+apply no erase mask and never look for one.  One
 process per GPU; for more than one GPU fresh processes are spawned, each loading the snapshot itself."""
 
 import json
@@ -73,7 +76,7 @@ class CommaSeparatedList(click.ParamType):
 @click.command()
 @click.pass_context
 @click.option('network_pkl', '--network', help='Network pickle filename (a local file)', metavar='PATH', required=True)
-@click.option('--metrics', help='Comma-separated list or "none"', type=CommaSeparatedList(), default='recon_full', show_default=True)
+@click.option('--metrics', help='Comma-separated list of recon_full, recon2k, tryon_full, tryon2k, or "none"', type=CommaSeparatedList(), default='recon_full', show_default=True)
 @click.option('--data', help='Tree to score against (directory) [default: the snapshot\'s training data]', metavar='PATH')
 @click.option('--gpus', help='Number of GPUs to use', type=click.IntRange(min=1), default=1, metavar='INT', show_default=True)
 @click.option('--verbose', help='Print optional information', type=bool, default=True, metavar='BOOL', show_default=True)
@@ -90,7 +93,7 @@ def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, wor
                            storage=storage)
     unknown = [m for m in args.metrics if not metric_main.is_valid_metric(m)]
     if unknown:
-        ctx.fail('\n'.join(['--metrics: unknown metric ' + ', '.join(unknown), 'valid metrics: ' + ', '.join(metric_main.list_valid_metrics())]))
+        ctx.fail('\n'.join(['--metrics: unknown metric ' + ', '.join(unknown), 'valid metrics: ' + ', '.join(metric_main.list_metrics())]))
     if re.match(r'^[A-Za-z][A-Za-z0-9+.-]*://', network_pkl):
         ctx.fail('--network: %r is a URL: give the path of a local snapshot file' % network_pkl)
     if not os.path.isfile(network_pkl):

@@ -10,8 +10,10 @@ Three regions of every output have a known answer, so they need no detector netw
 
 Per region and pair, ``pasta_region_image_stats`` (csrc/recon_metrics.hip) gives sum |d|, sum d^2 and the bytes of the region's
 pixels, and the SSIM sum and count of the 11 x 11 windows lying wholly inside it.  These are this project's own figures, not
-the reference's (which scores try-on by FID and KID); they are an option of test.py and test_512.py (``finish`` with
-``pixels=512 * 320``) and not a registered metric.
+the reference's (which scores try-on by FID and KID).  They are an option of test.py and test_512.py (``finish`` with
+``pixels=512 * 320``), which score the pairs of a test tree's lists, and the registered metrics ``tryon_full`` and ``tryon2k``
+(metrics/tryon_swapped.py), which score a training-layout tree with every person in the next person's garments and share
+``score_regions``, ``new_partials`` and ``finish`` with the option.
 
 Partials are ``int64 [num_pairs, 3, 5]``: per region sum |d|, sum d^2, SSIM windows, bytes and the bits of the fp64 SSIM sum.
 Row i belongs to pair i of the pair lists and is written by whoever scores it (zeros elsewhere), the scheme of
@@ -89,17 +91,25 @@ def score_batch(images, batch, rows, partials):
     of a 512 x 320 ``TryOnRegionBatch`` or ``TryOnOutfitBatch``, built with ``keep_stages=True``, scored into rows ``rows`` of
     ``partials``.  It reads the stages every one of them keeps: the person's unpadded ``image`` and ``parsing``, ``palm``,
     ``denorm_upper`` and ``denorm_lower``; the retain rule (``keep_mask``) is the same at both sizes."""
-    from metrics import metric_utils
     st, t = batch.stages, batch.tensors
     assert st is not None, 'tryon_fidelity.score_batch: build the batch with keep_stages=True'
     photos = st['image']
     H, W = int(photos.shape[1]), int(photos.shape[2])
     c0 = (H - W) // 2
+    score_regions(images, dict(keep=(keep_mask(st), 0, photos, 0),
+                               upper=(garment_mask(t['denorm_upper_mask']), c0, st['denorm_upper'], c0),
+                               lower=(garment_mask(t['denorm_lower_mask']), c0, st['denorm_lower'], c0)), c0, W, rows, partials)
+
+def garment_mask(mask):
+    """fp32 [N, 1, H, H], a ``denorm_*_mask`` input of G -> uint8 [N, H, H]: where it is not zero."""
+    return (mask[:, 0] != 0).to(torch.uint8)
+
+def score_regions(images, regions, c0, W, rows, partials):
+    """images [N, 3, H, Wt], content columns c0 .. c0 + W - 1, scored per region of REGIONS into rows ``rows`` of ``partials``.
+    ``regions[name]`` = (mask uint8 [N, H, Wm], the mask's first content column, reference uint8 [N, H, Wr, 3], the reference's
+    first content column).  One ``pasta_region_image_stats`` launch per region; shared with metrics/tryon_swapped.py."""
+    from metrics import metric_utils
     images = images.to(torch.float32)
-    u8 = lambda m: (m[:, 0] != 0).to(torch.uint8)
-    regions = dict(keep=(keep_mask(st), 0, photos, 0),
-                   upper=(u8(t['denorm_upper_mask']), c0, st['denorm_upper'], c0),
-                   lower=(u8(t['denorm_lower_mask']), c0, st['denorm_lower'], c0))
     words = []
     for region in REGIONS:
         mask, m0, ref, r0 = regions[region]

@@ -69,7 +69,7 @@ CFG_SPECS = {
 }
 UNSUPPORTED_CFGS = ('paper256', 'paper512', 'paper1024', 'cifar')
 STORAGE_DTYPES = {None: None, 'f32': None, 'bf16': 'bfloat16', 'f16': 'float16'}      # --storage -> fashion_config's act_dtype
-SUPPORTED_METRICS = ('recon_full', 'recon2k')       # metrics/metric_main.py; the reference's detector metrics are refused
+SUPPORTED_METRICS = ('recon_full', 'recon2k', 'tryon_full', 'tryon2k')     # metrics/metric_main.py; the reference's detector metrics are refused
 
 def parse_jitter_people(text):
     """``--jitter-people``'s SPEC, comma-separated ``name=value`` pairs -> the specification ``training_loop(people_jitter=)``
@@ -463,7 +463,7 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--outdir', help='Where to save the results', required=True, metavar='DIR')
 @click.option('--gpus', help='Number of GPUs to use [default: 1]', type=int, metavar='INT')
 @click.option('--snap', help='Snapshot interval [default: 50 ticks]', type=int, metavar='INT')
-@click.option('--metrics', help='Comma-separated list of recon_full, recon2k, or "none" [default: none]', type=CommaSeparatedList())
+@click.option('--metrics', help='Comma-separated list of recon_full, recon2k, tryon_full, tryon2k, or "none" [default: none]', type=CommaSeparatedList())
 @click.option('--metrics_data', help='Tree the metrics are evaluated on [default: the training data]', metavar='PATH')
 @click.option('--seed', help='Random seed [default: 0]', type=int, metavar='INT')
 @click.option('-n', '--dry-run', help='Print training options and exit', is_flag=True)

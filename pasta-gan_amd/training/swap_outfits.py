@@ -6,7 +6,8 @@ batch-mate's garments, prepared on the GPU from the stages the batch builder has
     swap_tensors    pasta_grid_composite_eroded_u8 twice (upper, lower) and pasta_swap_assemble (csrc/train_grid.hip): the five fp32
                     tensors, by the sample grid's rule (training/snapshot_grid.py) -- the donor's patches warped back with the
                     PERSON's M_inv, every mask eroded 5 x 5
-    attach          what both training builders call: the six extra tensors of a batch
+    attach          what both training builders call: the six extra tensors of a batch, by the donor rule or by explicit tables
+                    (metrics/tryon_swapped.py takes its donors over the data set, not over the batch)
 
 The warp-back matrices are the float64 ones the builder's normalisation has already solved (``want_matrices`` of
 ``patch_pipeline.normalize_batch`` / ``normalize_outfit_batch``): the people's 8 x 8 systems are not solved a second time.
@@ -25,6 +26,7 @@ REGIONS = ('fullbody', 'upperbody', 'lowerbody')
 # the five tensors pasta_swap_assemble writes, in its order, and the keep mask of the region L1 term
 SWAP_OUTPUTS = ['swap_denorm_upper_input', 'swap_denorm_lower_input', 'swap_denorm_upper_mask', 'swap_denorm_lower_mask', 'swap_style_input']
 SWAP_KEYS = SWAP_OUTPUTS + ['swap_keep']
+SWAP_STAGES = ('swap_denorm_upper', 'swap_denorm_lower')       # the two uint8 composites [N, H, H, 3], kept with the stages
 
 
 def donors(n, group):
@@ -60,11 +62,12 @@ def _composite(pool, mask_pool, index, minv, valid, ph, pw, H):
     return out
 
 
-def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src):
+def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src, composites=None):
     """The five fp32 tensors of SWAP_OUTPUTS for arbitrary source tables.  ``stages``: the builder's kept stages (``norm_img``,
     ``norm_img_lower`` [N, ph, pw, 3 p], ``norm_clothes_mask*``, ``retain_mask``); ``back`` float64 [N, 10, 3, 3] / ``valid``
     [N, 10]: the people's patch -> image maps as ``patch_pipeline.part_matrices`` returned them; ``lower_parts``: the parts also
-    cut from the lower garment (the builder's).  Three launches."""
+    cut from the lower garment (the builder's).  Three launches.  ``composites``: a dict that receives the two uint8 composites
+    [N, H, H, 3] the assemble reads (SWAP_STAGES: the donor's patches on the person, eroded), which are otherwise dropped."""
     norm_img, norm_lower = stages['norm_img'], stages['norm_img_lower']
     dev = norm_img.device
     n, ph, pw = int(norm_img.shape[0]), int(norm_img.shape[1]), int(norm_img.shape[2])
@@ -97,14 +100,25 @@ def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src):
     with torch.cuda.device(dev):
         _native.check(_native.lib().pasta_swap_assemble(P(den_u), P(den_l), P(norm_img), P(norm_lower), P(up_t), P(low_t), outs, n, n, H, ph, pw,
                                                         cu, cl, _native.stream()))
+    if composites is not None:
+        composites.update(zip(SWAP_STAGES, (den_u, den_l)))
     return t
 
 
-def attach(tensors, stages, back, valid, builder, swap):
-    """``tensors`` with the six SWAP_KEYS added for ``swap`` = dict(region=, group=): the five swapped tensors by the donor rule
-    and ``swap_keep``, the ``retain_mask`` stage (uint8 [N, H, H])."""
+def attach(tensors, stages, back, valid, builder, swap, keep_stages=False):
+    """``tensors`` with the six SWAP_KEYS added: the five swapped tensors and ``swap_keep``, the ``retain_mask`` stage (uint8
+    [N, H, H]).  ``swap`` is dict(region=, group=), the donor rule inside the batch, or dict(upper_src=, lower_src=), explicit
+    tables of batch indices [N].  With ``keep_stages`` the two composites join ``stages`` under SWAP_STAGES."""
     n = int(stages['retain_mask'].shape[0])
-    upper_src, lower_src = source_tables(n, swap['group'], swap.get('region', 'fullbody'))
-    tensors.update(swap_tensors(stages, back, valid, builder.lower_parts, upper_src, lower_src))
+    if 'upper_src' in swap or 'lower_src' in swap:
+        if set(swap) != {'upper_src', 'lower_src'}:
+            raise ValueError('swap takes region= and group=, or upper_src= and lower_src=, not %s' % ', '.join(sorted(swap)))
+        upper_src, lower_src = (np.asarray(swap[k], np.int64).reshape(-1) for k in ('upper_src', 'lower_src'))
+        for name, table in (('upper_src', upper_src), ('lower_src', lower_src)):
+            if table.shape != (n,) or table.min() < 0 or table.max() >= n:
+                raise ValueError('swap %s %s does not name one of the %d samples of the batch for each of them' % (name, table.tolist(), n))
+    else:
+        upper_src, lower_src = source_tables(n, swap['group'], swap.get('region', 'fullbody'))
+    tensors.update(swap_tensors(stages, back, valid, builder.lower_parts, upper_src, lower_src, composites=stages if keep_stages else None))
     tensors['swap_keep'] = stages['retain_mask']
     return tensors

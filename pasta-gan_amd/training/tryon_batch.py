@@ -441,7 +441,8 @@ class FullBodyBatch:
 
 class FullBodyBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate`` -> FullBodyBatch on ``device``.  ``swap`` = dict(region=,
-    group=): the batch also carries the swapped inputs of training/swap_outfits.py, made from this batch's stages."""
+    group=) or dict(upper_src=, lower_src=): the batch also carries the swapped inputs of training/swap_outfits.py, made from this
+    batch's stages; kept stages then include that module's two SWAP_STAGES."""
 
     # how the warp-back matrices of this builder's stages are formed (training/snapshot_grid.py forms them again per cell):
     # the parts also cut from the lower garment, part_matrices' x_pad and shin_fallback, and whether the key points are shifted
@@ -487,7 +488,7 @@ class FullBodyBatchBuilder:
                           denorm_upper=den_u, denorm_lower=den_l, arm_masks=arm, M_invs=m_invs, norm_clothes_mask=norm_mask.contiguous(),
                           norm_clothes_mask_lower=norm_mask_lower.contiguous())
         if swap is not None:
-            attach_swap(t, stages, back, valid, self, swap)
+            attach_swap(t, stages, back, valid, self, swap, keep_stages)
         return FullBodyBatch(t, stages if keep_stages else None, image)
 
 

@@ -174,8 +174,8 @@ class TryOnRegionBatchBuilder(TryOnOutfitBatchBuilder):
 class FullBodyRegionBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate`` at 512 x 320 -> FullBodyBatch on ``device``, which
     TrainingStep.run consumes as the 256 builder's.  ``stages`` (``keep_stages``) carry the 256 builder's names, so that
-    training/snapshot_grid.py has one code path.  ``swap`` = dict(region=, group=), as the 256 builder's: the batch also carries
-    the swapped inputs of training/swap_outfits.py."""
+    training/snapshot_grid.py has one code path.  ``swap`` = dict(region=, group=) or dict(upper_src=, lower_src=), as the 256
+    builder's: the batch also carries the swapped inputs of training/swap_outfits.py."""
 
     # see FullBodyBatchBuilder: parts 0, 6..9 are also cut from the lower garment; key points shifted in float64, x_pad = 0
     lower_parts, x_pad, shin_fallback, shifted = patch_pipeline.LOWER_PARTS_512, 0, False, True
@@ -223,5 +223,5 @@ class FullBodyRegionBatchBuilder:
                           denorm_upper=den_u, denorm_lower=den_l, arm_masks=part_masks[:, list(patch_pipeline.ARM_PARTS)].contiguous(),
                           M_invs=m_invs, norm_clothes_mask=hwc(mask_patches), norm_clothes_mask_lower=hwc(mask_patches_l))
         if swap is not None:
-            attach_swap(t, stages, back, valid, self, swap)
+            attach_swap(t, stages, back, valid, self, swap, keep_stages)
         return FullBodyBatch(t, stages if keep_stages else None, image)
