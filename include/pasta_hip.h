@@ -539,6 +539,31 @@ int pasta_warp_perspective_u8(const uint8_t* src, const int32_t* src_index, cons
 int pasta_patch_composite_u8(const uint8_t* patches, const uint8_t* masks, const double* minv, const uint8_t* valid,
                              uint8_t* out, uint8_t* part_mask, int N, int P, int ph, int pw, int H, int W, void* stream);
 
+/* The geometry of the ten body parts of M people in ONE launch (csrc/part_geometry.hip; added in ABI 22 without a
+ * bump, purely additive): what training/patch_pipeline.py's part_matrices and adjugate_inverse do on the host, one part at a
+ * time.  keypoints: [M, 18, 3] doubles (x, y, confidence; device).  Every output may be NULL (not written):
+ *   quads [M,10,4,2] float32 the source quadrilaterals; fwd / back [M,10,9] doubles, image -> patch and patch -> image;
+ *   fwd_inv / back_inv [M,10,9] doubles, their inverses (the `minv` of the warp and composite entries); m_inv [M,10,9] float32,
+ *   back cast; valid [M,10] uint8.  A part whose key points are missing is zeros in every output.
+ * The rule (a SECOND rule next to the host's LAPACK solve, which no elimination reproduces to the last bit):
+ *   1. quadrilateral: part_quadrilateral operation for operation in float32 -- the key points converted to float32 first, x_pad
+ *      added after that in float32; a key point is seen when its confidence >= 0.1 (compared in double); a thigh without its knee
+ *      and, with shin_fallback, a shin without its ankle go straight down to row image_height - 1; a head without the nose is the
+ *      square on the shoulder line whose normal is negated when normal[1] > 0; _box_around's corner order, the head's [b, c, d, a];
+ *   2. systems: perspective_matrix's eight rows in its order ((x, y, 1, 0, 0, 0, -x u, -y u | u) four times, then (0, 0, 0, x, y,
+ *      1, -x v, -y v | v)), formed in double from the float32 points and the corners (0,0), (0,ph), (pw,ph), (pw,0); solved by
+ *      Gaussian elimination, every product and difference rounded on its own: for column c = 0..7 the pivot is the FIRST row
+ *      r >= c with the largest |a[r,c]| (a later row replaces it only if strictly larger); a pivot of exactly 0 ends the solve
+ *      with h = 0 (the matrix is then 0,...,0,1); the pivot row is swapped into place; for r > c: m = a[r,c] / a[c,c], a[r,k] =
+ *      a[r,k] - m a[c,k] for k > c, b[r] = b[r] - m b[c]; back substitution from row 7 up: s = b[r], s = s - a[r,k] x[k] for
+ *      k = r+1..7 ascending, x[r] = s / a[r,r];
+ *   3. inverses: adjugate_inverse's cofactor expressions in its order, each times 1.0 / det; zeros when det == 0.
+ * No address depends on the key points except the pivot row (0..7): non-finite coordinates give some matrices, never a fault.
+ * M 1 .. 2^20; image_height, patch_w, patch_h 1 .. 65536; x_pad 0 .. 65536. */
+int pasta_part_geometry(const double* keypoints, int M, int image_height, int patch_w, int patch_h, int x_pad, int shin_fallback,
+                        float* quads, double* fwd, double* back, double* fwd_inv, double* back_inv, float* m_inv, uint8_t* valid,
+                        void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Per-sample preparation of the try-on data set (row f4; UvitonDatasetFull._load_raw_image / __getitem__,
  * training/dataset.py:515-568, 619-736, 929-993, and the loop's conversions, training_loop_wo_flow_fullbody.py:425-456),

@@ -26,6 +26,9 @@ Differences from the reference, on purpose:
   the lower garment of another, ``-`` for a garment the person keeps (training.dataset.UvitonOutfits_256_test), written to
   ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower stem>.png``.  Both options are this project's own
   (include/pasta_hip.h lists the rules) and exclude each other.
+  --part-geometry host | gpu (tryon_cli.part_geometry_option; default host, the bytes this command always wrote): with gpu the body
+  parts' matrices of a batch are solved in one launch on the GPU instead of numpy on the host, a second rule that prepares almost
+  exactly the same bytes; --scores then says ``part_geometry: gpu``.
 """
 
 from typing import List, Optional

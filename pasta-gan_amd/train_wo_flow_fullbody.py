@@ -40,6 +40,11 @@ only what the arm-part rule erases.  With either the tree needs no mask director
 
 ``--storage=bf16`` (or ``f16``) keeps the activations of G and of every block of D in that type; parameters, demodulation,
 statistics, the images and the loss stay fp32.
+
+``--part-geometry=gpu`` solves the body parts' quadrilaterals, 8 x 8 systems and inverses of every training batch in one launch
+(``training.patch_pipeline.part_geometry``) instead of numpy on the host, one part at a time; with ``--swap_weight`` the swapped pass
+uses the same device maps.  A second rule that prepares almost exactly the same bytes; recorded with the run only when
+given as ``gpu``.  The sample grid and the metrics keep the host's geometry.
 """
 
 import json
@@ -85,7 +90,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
                                mirror_people=None, jitter_people=None, ssim_weight=None, erase_masks=None, erase_strokes=None,
-                               swap_weight=None, swap_region=None, swap_cx_weight=None):
+                               swap_weight=None, swap_region=None, swap_cx_weight=None, part_geometry=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -303,6 +308,13 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         swap_region = 'fullbody' if swap_region is None else swap_region
         desc += f'-swap{swap_weight:g}' + (swap_region if swap_region != 'fullbody' else '') + (f'-cx{swap_cx_weight:g}' if swap_cx_weight else '')
         args.swap_outfits = dnnlib.EasyDict(region=swap_region, group=args.batch_gpu)
+    # --part-geometry (own option): the body parts' matrices in one launch per batch instead of numpy on the host.  Absent
+    # or host records nothing, so that such a run's options and launches are what they always were.
+    if part_geometry not in (None, 'host', 'gpu'):
+        raise UserError(f'--part-geometry must be host or gpu, not {part_geometry}')
+    if part_geometry == 'gpu':
+        desc += '-geomgpu'
+        args.part_geometry = 'gpu'
     if fp32:
         config.G_kwargs.synthesis_kwargs.num_fp16_res = config.D_kwargs.num_fp16_res = 0
         config.G_kwargs.synthesis_kwargs.conv_clamp = config.D_kwargs.conv_clamp = None
@@ -356,7 +368,7 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
             continue
         option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people', 'jitter_people': 'jitter-people', 'erase_masks': 'erase-masks',
-                         'erase_strokes': 'erase-strokes', 'swap_region': 'swap-region'}.get(name, name)
+                         'erase_strokes': 'erase-strokes', 'swap_region': 'swap-region', 'part_geometry': 'part-geometry'}.get(name, name)
         raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
                         (f' ({recorded})' if recorded is not None else ''))
 
@@ -513,6 +525,8 @@ class CommaSeparatedList(click.ParamType):
               'features of the swapped images against those of the warped patches, matched wherever they lie.  Needs --swap_weight.  The '
               'features come from ./checkpoints/vgg19-dcbb9e9d.pth when it exists, otherwise from seeded RANDOM weights, whose values mean '
               'only what random features mean [default: 0]', type=float)
+@click.option('--part-geometry', help='Where the body-part matrices of a batch are solved: numpy on the host, or one launch on the GPU (almost '
+              'exactly the same bytes: DESIGN 8n) [default: host]', type=click.Choice(['host', 'gpu']))
 @click.option('--vgg_weight', help='vgg loss weight (runs from random weights: the checkpoint cannot be obtained; --ssim_weight is the '
               'structural term that needs none)', type=float)
 @click.option('--contextual_weight', help='contextual loss weight (refused unless 0: its checkpoint cannot be obtained; see --ssim_weight)',
@@ -559,6 +573,8 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
     if swap:
         print(f'Swapped outfits:    weight {args.cfg.loss_kwargs.swap_weight:g}, {swap.region}, groups of {swap.group}' +
               (f', contextual weight {args.cfg.loss_kwargs.swap_cx_weight:g}' if args.cfg.loss_kwargs.get('swap_cx_weight') else ''))
+    if args.get('part_geometry'):
+        print(f'Part geometry:      {args.part_geometry}')
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

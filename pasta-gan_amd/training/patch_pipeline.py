@@ -5,7 +5,9 @@ host (the reason the reference's loader, not its networks, bounds rea
 fourteen) forward warps of a whole batch are ONE launch of ``pasta_warp_perspective_u8`` per source tensor and the warp-back
 + mask test + compositing of all parts one launch of ``pasta_patch_composite_u8`` per garment.
 
-The projective matrices are 8 x 8 solves on eighteen key points -- host work, numpy float64, as in the reference.  Image
+The projective matrices are 8 x 8 solves on eighteen key points -- host work, numpy float64, as in the reference -- or, with
+``geometry='gpu'``, ONE launch of ``pasta_part_geometry`` per batch (part_geometry below): a second, documented rule
+that no host solve and no upload of matrices precedes.  Image
 tensors stay uint8 HWC as the reference's arrays.  Numerics: OpenCV's fixed-point bilinear interpolation restated from its
 published algorithm (csrc/patches.hip); OpenCV is not installed here, so parity with cv2 is UNPINNED (DESIGN.md section 9);
 the kernels are held bit for bit to oracle/ref_patches.py in tests/test_patches_gpu.py."""
@@ -118,21 +120,95 @@ def part_matrices(joints, width, height, box_factor=2, x_pad=32, shin_fallback=F
     return fwd, back, valid
 
 
+GEOMETRIES = ('host', 'gpu')
+GEOMETRY_OUTPUTS = ('quads', 'fwd', 'back', 'fwd_inv', 'back_inv', 'm_inv', 'valid')       # pasta_part_geometry's, in its order
+
+
+def check_geometry(geometry):
+    if geometry not in GEOMETRIES:
+        raise ValueError('part geometry %r is invalid (one of %s).' % (geometry, ', '.join(GEOMETRIES)))
+    return geometry
+
+
+def part_geometry(joints, width, height, box_factor=2, x_pad=32, shin_fallback=False, device='cuda', outputs=GEOMETRY_OUTPUTS):
+    """part_matrices and the inverses the warps take, on the GPU in one launch (csrc/part_geometry.hip; include/pasta_hip.h states
+    the rule): ``joints`` [M, 18, 3] (host, uploaded once, or a float64 tensor already on ``device``) -> dict of device tensors
+    ``quads`` float32 [M,10,4,2], ``fwd`` / ``back`` / ``fwd_inv`` / ``back_inv`` float64 [M,10,9], ``m_inv`` float32 [M,10,9]
+    (``back`` cast, zeros where invalid: the M_invs tensor) and ``valid`` uint8 [M,10]; ``outputs`` names the ones wanted.  Nothing
+    is read back."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('part_geometry needs a GPU device (there is no CPU path), not %s' % dev)
+    unknown = [k for k in outputs if k not in GEOMETRY_OUTPUTS]
+    if unknown:
+        raise ValueError('part_geometry: unknown output %s' % ', '.join(unknown))
+    if isinstance(joints, torch.Tensor):
+        kp = joints.to(dev, torch.float64).contiguous()
+    else:
+        kp = torch.from_numpy(np.ascontiguousarray(joints, dtype=np.float64)).to(dev, non_blocking=True)
+    assert kp.ndim == 3 and kp.shape[1:] == (18, 3), 'key points [M, 18, 3]'
+    m = int(kp.shape[0])
+    shapes = dict(quads=([m, 10, 4, 2], torch.float32), m_inv=([m, 10, 9], torch.float32), valid=([m, 10], torch.uint8))
+    shaped = lambda size, dtype: torch.empty(size, dtype=dtype, device=dev)
+    out = {k: shaped(*shapes.get(k, ([m, 10, 9], torch.float64))) for k in outputs}
+    if m == 0:
+        return out
+    pw, ph = width // 2 ** box_factor, height // 2 ** box_factor
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().pasta_part_geometry(_native.ptr(kp), m, int(height), pw, ph, int(x_pad), 1 if shin_fallback else 0,
+                                                        *[_native.ptr(out.get(k)) for k in GEOMETRY_OUTPUTS], _native.stream()))
+    return out
+
+
+_PART_JOINTS = [[_JOINT[name] for name in part] for part in BODY_PARTS]
+
+
+def part_valid(joints, shin_fallback=False):
+    """bool [N, 10]: part_matrices' valid flags for key points [N, 18, 3], the _seen / fall-back rule of part_quadrilateral
+    vectorised -- no solve (the builders' upper_valid / lower_valid / person_valid under ``geometry='gpu'``)."""
+    seen = np.asarray(joints, np.float64)[..., 2] >= 0.1                                # [N, 18]
+    first = np.stack([seen[:, j[0]] for j in _PART_JOINTS], axis=1)
+    everything = np.stack([seen[:, j].all(axis=1) for j in _PART_JOINTS], axis=1)
+    valid = everything.copy()
+    valid[:, 1] = seen[:, _JOINT['lshoulder']] & seen[:, _JOINT['rshoulder']]          # head without the nose
+    alone = [6, 8] + ([7, 9] if shin_fallback else [])                                  # thigh without knee, shin without ankle
+    valid[:, alone] = first[:, alone]
+    return valid
+
+
 def _u8(t):
     assert t.dtype == torch.uint8 and t.is_cuda and t.ndim == 4 and t.shape[-1] == 3, 'uint8 [N, H, W, 3] tensors on the GPU'
     return t.contiguous()
 
 
-def warp_perspective(src, matrices, out_hw, border='constant', src_index=None, valid=None):
+def _on_device(t, dtype, dev):
+    """A table for a launch: a tensor already on the device as it is (made contiguous), a host array uploaded."""
+    if t is None:
+        return None
+    if isinstance(t, torch.Tensor):
+        assert t.device == dev and t.dtype == dtype, 'a %s tensor on %s' % (dtype, dev)
+        return t.contiguous()
+    return torch.as_tensor(np.asarray(t, torch.empty(0, dtype=dtype).numpy().dtype), device=dev)
+
+
+def warp_perspective(src, matrices, out_hw, border='constant', src_index=None, valid=None, minv=None):
     """Batched ``cv2.warpPerspective(src[i], M, (w, h), borderMode=...)`` for uint8 [*, H, W, C] GPU tensors: ``matrices``
-    [B, 3, 3] float64 (host), one output per matrix; ``src_index`` [B] picks the source of each (default: i)."""
+    [B, 3, 3] float64 (host), one output per matrix; ``src_index`` [B] picks the source of each (default: i).  ``minv`` (with
+    ``matrices`` None): the INVERTED matrices [B, 9] float64 already on the device (part_geometry's ``fwd_inv``), nothing inverted
+    or uploaded here; ``src_index`` (int32) and ``valid`` (uint8) may be device tensors as well."""
     _native.require_gpu(src, 'warp_perspective')
-    b = int(len(matrices))
-    inv = np.ascontiguousarray(np.stack([adjugate_inverse(m) for m in matrices]).reshape(b, 9))
     dev = src.device
-    inv_t = torch.from_numpy(inv).to(dev)
-    idx_t = torch.as_tensor(np.asarray(src_index, np.int32), device=dev) if src_index is not None else None
-    val_t = torch.as_tensor(np.asarray(valid, np.uint8), device=dev) if valid is not None else None
+    if minv is not None:
+        assert matrices is None and minv.ndim == 2 and minv.shape[1] == 9
+        inv_t = _on_device(minv, torch.float64, dev)
+        b = int(inv_t.shape[0])
+    else:
+        b = int(len(matrices))
+        inv = np.ascontiguousarray(np.stack([adjugate_inverse(m) for m in matrices]).reshape(b, 9))
+        inv_t = torch.from_numpy(inv).to(dev)
+    idx_t = _on_device(src_index, torch.int32, dev)
+    val_t = _on_device(valid, torch.uint8, dev)
+    assert (idx_t is None or idx_t.numel() == b) and (val_t is None or val_t.numel() == b)
     oh, ow = out_hw
     dst = torch.empty([b, oh, ow, src.shape[-1]], dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
@@ -151,13 +227,19 @@ def inverse_maps(back, parts):
 MAX_ERODE_RADIUS = 8        # ER_MAX_R of csrc/patch_erode.h: the halo its LDS tiles hold
 
 
+def _parts_on(parts, dev):
+    return torch.as_tensor(np.asarray(parts, np.int64), device=dev)
+
+
 def composite(patches, masks, back, valid, parts, height, width, radius=None, want_part_masks=False):
     """patch -> image (BORDER_CONSTANT) + mask test + compositing of ``patches`` / ``masks`` [N, p, h, w, 3] in order, one launch:
     index j is part ``parts[j]`` of ``back`` [N, 10, 3, 3] / ``valid`` [N, 10], the maps of the people the result is drawn on.
     ``radius`` None: pasta_patch_composite_u8, the mask tested as warped; a value: pasta_patch_composite_eroded_u8, the mask eroded
     (2 * radius + 1) square first; a sequence [N]: the same entry with its ``radii``, sample i eroded by ``radius[i]`` (0: as warped),
     still one launch.  A radius outside 0 .. 8 raises ValueError.  Returns (image uint8 [N, height, width, 3], part masks uint8
-    [N, p, height, width] or None)."""
+    [N, p, height, width] or None).  ``back`` and ``valid`` as device tensors: part_geometry's ``back_inv`` [N, 10, 9] float64 (already
+    inverted) and ``valid`` [N, 10] uint8 of those people; the parts are then gathered on the device, nothing is inverted or uploaded
+    but the list of parts."""
     n, p, ph, pw = patches.shape[:4]
     dev = patches.device
     lib = _native.lib()
@@ -174,8 +256,13 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
             raise ValueError('composite: radius %d of sample %d (0..%d)' % (radii[bad[0]], bad[0], MAX_ERODE_RADIUS))
         radius_t = torch.from_numpy(radii.astype(np.uint8)).to(dev)       # held until the launch is queued
         entry, extra = lib.pasta_patch_composite_eroded_u8, (0, _native.ptr(radius_t))
-    inv_t = torch.from_numpy(inverse_maps(back, parts)).to(dev)
-    val_t = torch.as_tensor(np.ascontiguousarray(valid[:, parts]).astype(np.uint8), device=dev)
+    if isinstance(back, torch.Tensor):
+        assert back.shape == (n, 10, 9) and back.dtype == torch.float64 and valid.shape == (n, 10) and valid.dtype == torch.uint8
+        parts_t = _parts_on(parts, dev)
+        inv_t, val_t = back.index_select(1, parts_t).contiguous(), valid.index_select(1, parts_t).contiguous()
+    else:
+        inv_t = torch.from_numpy(inverse_maps(back, parts)).to(dev)
+        val_t = torch.as_tensor(np.ascontiguousarray(valid[:, parts]).astype(np.uint8), device=dev)
     out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
     pm = torch.empty([n, p, height, width], dtype=torch.uint8, device=dev) if want_part_masks else None
     patches, masks = patches.contiguous(), masks.contiguous()             # held until the launch is queued
@@ -185,43 +272,69 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
     return out, pm
 
 
-def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_factor=2, want_matrices=False):
+def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_factor=2, want_matrices=False, geometry='host'):
     """``normalize`` (dataset.py:838-927) for a batch on the GPU.  Images and 3-channel masks: uint8 [N, H, W, 3] CUDA tensors;
     ``joints`` [N, 18, 3] (host).  Returns the reference's tuple, batched:
     (norm_img [N,h,w,30], norm_img_lower [N,h,w,12], denorm_upper [N,H,W,3], denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32,
      denorm_hand_masks [N,4,H,W,1], clothes_masks [N,h,w,30], clothes_masks_lower [N,h,w,12]).  ``want_matrices``: two more values,
     the float64 patch -> image maps [N,10,3,3] and valid flags [N,10] that part_matrices solved here (training/swap_outfits.py
-    warps a batch-mate's patches back with them instead of solving the people again)."""
+    warps a batch-mate's patches back with them instead of solving the people again).  ``geometry='gpu'``: the matrices come from
+    part_geometry and stay on the device -- no host solve, M_invs a device tensor, and ``want_matrices`` gives the device
+    ``back_inv`` [N,10,9] float64 and ``valid`` [N,10] uint8 in place of the host maps and flags."""
     upper_img, lower_img, upper_mask, lower_mask = _u8(upper_img), _u8(lower_img), _u8(upper_mask), _u8(lower_mask)
     n, height, width, _ = upper_img.shape
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    fwd, back, valid = part_matrices(joints, width, height, box_factor)
     sample = np.repeat(np.arange(n, dtype=np.int32), 10)
-    flat_valid = valid.reshape(-1)
-    # image -> patch (BORDER_REPLICATE): all ten parts of every sample in one launch per source tensor
-    warp = lambda src, sel: warp_perspective(src, fwd.reshape(-1, 3, 3)[sel], (ph, pw), 'replicate', sample[sel], flat_valid[sel])
-    everything = np.arange(n * 10)
-    legs = everything.reshape(n, 10)[:, LOWER_FROM:].reshape(-1)
-    p_img = warp(upper_img, everything).reshape(n, 10, ph, pw, 3)
-    p_mask = warp(upper_mask, everything).reshape(n, 10, ph, pw, 3)
-    p_img_l = warp(lower_img, legs).reshape(n, 10 - LOWER_FROM, ph, pw, 3)
-    p_mask_l = warp(lower_mask, legs).reshape(n, 10 - LOWER_FROM, ph, pw, 3)
+    if check_geometry(geometry) == 'gpu':
+        g = part_geometry(joints, width, height, box_factor, device=upper_img.device, outputs=('fwd_inv', 'back_inv', 'm_inv', 'valid'))
+        back, valid, m_invs = g['back_inv'], g['valid'], g['m_inv'].reshape(n, 10, 3, 3)
+        sample_t = torch.from_numpy(sample).to(upper_img.device, non_blocking=True)
+        def cut(t, which):                  # [n, 10, ...] -> the items of a forward launch, flat
+            t = t if which == 'all' else t[:, LOWER_FROM:]
+            return t.reshape(-1, *t.shape[2:])
+        warp = lambda src, which: warp_perspective(src, None, (ph, pw), 'replicate', cut(sample_t.reshape(n, 10), which), cut(valid, which),
+                                                   minv=cut(g['fwd_inv'], which))
+    else:
+        fwd, back, valid = part_matrices(joints, width, height, box_factor)
+        flat_valid = valid.reshape(-1)
+        everything = np.arange(n * 10)
+        rows = dict(all=everything, legs=everything.reshape(n, 10)[:, LOWER_FROM:].reshape(-1))       # the items of a forward launch
+        m_invs = torch.from_numpy(np.where(valid[..., None, None], back, 0.0).astype(np.float32))
+        # image -> patch (BORDER_REPLICATE): all ten parts of every sample in one launch per source tensor
+        warp = lambda src, which: warp_perspective(src, fwd.reshape(-1, 3, 3)[rows[which]], (ph, pw), 'replicate', sample[rows[which]],
+                                                   flat_valid[rows[which]])
+    p_img = warp(upper_img, 'all').reshape(n, 10, ph, pw, 3)
+    p_mask = warp(upper_mask, 'all').reshape(n, 10, ph, pw, 3)
+    p_img_l = warp(lower_img, 'legs').reshape(n, 10 - LOWER_FROM, ph, pw, 3)
+    p_mask_l = warp(lower_mask, 'legs').reshape(n, 10 - LOWER_FROM, ph, pw, 3)
 
     # patch -> image + mask test + compositing, all parts in order, one launch per garment
     den_u, part_masks = composite(p_img, p_mask, back, valid, list(range(10)), height, width, want_part_masks=True)
     den_l, _ = composite(p_img_l, p_mask_l, back, valid, list(range(LOWER_FROM, 10)), height, width)
     hwc = lambda t: t.permute(0, 2, 3, 1, 4).reshape(n, ph, pw, -1)            # parts concatenated along the channel axis (:918-921)
-    m_invs = torch.from_numpy(np.where(valid[..., None, None], back, 0.0).astype(np.float32))
     hand_masks = part_masks[:, list(ARM_PARTS)].unsqueeze(-1)
     out = (hwc(p_img), hwc(p_img_l), den_u, den_l, m_invs, hand_masks, hwc(p_mask), hwc(p_mask_l))
     return out + (back, valid) if want_matrices else out
+
+
+def _people_geometry(people_joints, person_idx, items, width, height, box_factor, shin_fallback, dev):
+    """``geometry='gpu'`` of the outfit normalisers: the M people solved in one launch (key points already shifted: x_pad = 0), the
+    forward launches' inverse maps and flags gathered by ``items`` (flat: owner * 10 + part) and the PERSONS' maps by ``person_idx``,
+    on the device: (minv [B, 9], flags [B], back_inv [N, 10, 9], valid [N, 10] uint8, M_invs [N, 10, 3, 3] float32)."""
+    g = part_geometry(people_joints, width, height, box_factor, 0, shin_fallback, dev, ('fwd_inv', 'back_inv', 'm_inv', 'valid'))
+    items_t = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int64)).to(dev, non_blocking=True)
+    person_t = torch.from_numpy(np.ascontiguousarray(person_idx, dtype=np.int64)).to(dev, non_blocking=True)
+    return (g['fwd_inv'].reshape(-1, 9).index_select(0, items_t), g['valid'].reshape(-1).index_select(0, items_t),
+            g['back_inv'].index_select(0, person_t), g['valid'].index_select(0, person_t),
+            g['m_inv'].index_select(0, person_t).reshape(-1, 10, 3, 3))
 
 
 UPPER_PARTS = 6             # the test set: parts 0..5 from the clothes donor, 6..9 from the person (dataset.py:1470-1478)
 ERODE_RADIUS = 2            # cv2.erode(..., np.ones((5, 5))) of the warped-back masks of parts 0..5 (:1460, :1484-1485)
 
 
-def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2):
+def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2,
+                                geometry='host'):
     """The test set's ``normalize`` (dataset.py:1430-1500) for a batch of OUTFITS on the GPU (include/pasta_hip.h lists the
     rules).  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image, 3-channel mask)
     followed by the N lower garments.  ``people_stick`` [M, H, W, 3]: the stick figures of the batch's M DISTINCT people;
@@ -233,22 +346,29 @@ def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_
     parts 6..9 into denorm_lower in one launch whose radius is per sample, 0 (the plain composite) where the person wears their
     own lower garment and ERODE_RADIUS where it is somebody else's.  Returns (patches, stick_patches, mask_patches
     [N,10,h,w,3], denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid,
-    person_valid [N,10] bool)."""
+    person_valid [N,10] bool).  ``geometry='gpu'``: part_geometry in place of part_matrices -- no host solve, the owner and person
+    tables are index_select on the device, M_invs is a device tensor and the three flag arrays come from part_valid."""
     garment_img, people_stick, garment_mask = _u8(garment_img), _u8(people_stick), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
     assert n2 == 2 * n and garment_mask.shape == garment_img.shape and people_stick.shape[1:] == garment_img.shape[1:]
     person_idx, upper_idx, lower_idx = (np.asarray(ix, np.int64).reshape(n) for ix in (person_idx, upper_idx, lower_idx))
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
-    back, valid_p = back[person_idx], valid_all[person_idx]
     from_upper = np.arange(10) < UPPER_PARTS
     owner = np.where(from_upper[None, :], upper_idx[:, None], lower_idx[:, None])      # [N, 10]: whose matrices and stick figure part k takes
     part = np.arange(10)[None, :]
-    mats, valid = fwd[owner, part].reshape(-1, 3, 3), valid_all[owner, part].reshape(-1)
+    if check_geometry(geometry) == 'gpu':
+        mats, valid_all = None, part_valid(people_joints, shin_fallback=True)
+        minv, valid, back, valid_p, m_invs = _people_geometry(people_joints, person_idx, (owner * 10 + part).reshape(-1), width, height,
+                                                              box_factor, True, garment_img.device)
+    else:
+        fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
+        back, valid_p = back[person_idx], valid_all[person_idx]
+        mats, valid, minv = fwd[owner, part].reshape(-1, 3, 3), valid_all[owner, part].reshape(-1), None
+        m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
     # item (i, k) reads garment i of the upper ones (0..N-1) for k < 6 and of the lower ones (N..2N-1) otherwise
     garment = (np.arange(n, dtype=np.int32)[:, None] + np.where(from_upper, 0, n).astype(np.int32)[None, :]).reshape(-1)
-    warp = lambda src, index: warp_perspective(src, mats, (ph, pw), 'replicate', index, valid).reshape(n, 10, ph, pw, 3)
+    warp = lambda src, index: warp_perspective(src, mats, (ph, pw), 'replicate', index, valid, minv=minv).reshape(n, 10, ph, pw, 3)
     patches, mask_patches = warp(garment_img, garment), warp(garment_mask, garment)
     stick_patches = warp(people_stick, owner.astype(np.int32).reshape(-1))
 
@@ -256,15 +376,14 @@ def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_
     den_u, _ = composite(patches[:, upper], mask_patches[:, upper], back, valid_p, upper, height, width, ERODE_RADIUS)
     radius = np.where(lower_idx != person_idx, ERODE_RADIUS, 0)
     den_l, _ = composite(patches[:, lower], mask_patches[:, lower], back, valid_p, lower, height, width, radius)
-    m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
-    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_p
+    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_all[person_idx]
 
 
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
 
 
 def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx, upper_idx, lower_idx, box_factor=2, want_part_masks=False,
-                           want_matrices=False):
+                           want_matrices=False, geometry='host'):
     """``normalize_full`` / ``normalize_upper`` / ``normalize_lower`` of the 512 x 320 set (dataset.py:1967-2193) for a batch of
     OUTFITS on the GPU.  ``garment_img`` / ``garment_mask``: uint8 [2N, H, W, 3] CUDA tensors, the N upper garments (image,
     3-channel mask) followed by the N lower garments.  ``people_joints`` [M, 18, 3] float64 (host): the batch's DISTINCT people,
@@ -278,28 +397,37 @@ def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx,
     [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the
     person's), upper_valid, lower_valid, person_valid [N,10] bool).  ``want_part_masks``: an eleventh value, the eroded 0 / 1
     masks [N,10,H,W] of the upper composite's parts.  ``want_matrices``: two last values, the PERSONS' float64 patch -> image maps
-    [N,10,3,3] and valid flags [N,10] as solved here (training/swap_outfits.py)."""
+    [N,10,3,3] and valid flags [N,10] as solved here (training/swap_outfits.py).  ``geometry='gpu'``: as
+    normalize_pair_outfit_batch's; ``want_matrices`` then gives the PERSONS' device ``back_inv`` [N,10,9] float64 and ``valid`` [N,10]
+    uint8."""
     garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
     assert n2 == 2 * n and garment_mask.shape == garment_img.shape
     person_idx, upper_idx, lower_idx = (np.asarray(ix, np.int64).reshape(n) for ix in (person_idx, upper_idx, lower_idx))
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0)
-    back, valid_p = back[person_idx], valid_all[person_idx]
     low = list(LOWER_PARTS_512)
     pu, pl = 10, len(low)
     # items: (i, k) of the upper garments, then (i, k) of the lower garments, which read source N + i
-    mats = np.concatenate([fwd[upper_idx].reshape(-1, 3, 3), fwd[lower_idx][:, low].reshape(-1, 3, 3)])
-    valid = np.concatenate([valid_all[upper_idx].reshape(-1), valid_all[lower_idx][:, low].reshape(-1)])
+    if check_geometry(geometry) == 'gpu':
+        items = np.concatenate([(upper_idx[:, None] * 10 + np.arange(pu)).reshape(-1), (lower_idx[:, None] * 10 + np.asarray(low)).reshape(-1)])
+        mats, valid_all = None, part_valid(people_joints)
+        minv, valid, back, valid_p, m_invs = _people_geometry(people_joints, person_idx, items, width, height, box_factor, False,
+                                                              garment_img.device)
+    else:
+        fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0)
+        back, valid_p = back[person_idx], valid_all[person_idx]
+        mats = np.concatenate([fwd[upper_idx].reshape(-1, 3, 3), fwd[lower_idx][:, low].reshape(-1, 3, 3)])
+        valid, minv = np.concatenate([valid_all[upper_idx].reshape(-1), valid_all[lower_idx][:, low].reshape(-1)]), None
+        m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
     src_index = np.concatenate([np.repeat(np.arange(n, dtype=np.int32), pu), np.repeat(np.arange(n, 2 * n, dtype=np.int32), pl)])
-    warp = lambda src: warp_perspective(src, mats, (ph, pw), 'replicate', src_index, valid)
+    warp = lambda src: warp_perspective(src, mats, (ph, pw), 'replicate', src_index, valid, minv=minv)
     split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
     (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
 
     den_u, part_masks = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS, want_part_masks)
     den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
-    m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
-    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_p)
+    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx],
+           valid_all[person_idx])
     out = out + (part_masks,) if want_part_masks else out
     return out + (back, valid_p) if want_matrices else out

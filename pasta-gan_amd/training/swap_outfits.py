@@ -11,6 +11,8 @@ batch-mate's garments, prepared on the GPU from the stages the batch builder has
 
 The warp-back matrices are the float64 ones the builder's normalisation has already solved (``want_matrices`` of
 ``patch_pipeline.normalize_batch`` / ``normalize_outfit_batch``): the people's 8 x 8 systems are not solved a second time.
+A builder with ``geometry='gpu'`` hands over the device ``back_inv`` and flags of ``patch_pipeline.part_geometry`` instead: nothing
+is inverted or uploaded here, and the lower garment's parts are gathered on the device.
 ``retain`` and ``pose`` of the swapped pass are the paired batch's own tensors; no erase mask is applied."""
 
 import ctypes
@@ -52,8 +54,11 @@ def _composite(pool, mask_pool, index, minv, valid, ph, pw, H):
     dev = pool.device
     n, parts = index.shape
     index_t = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(dev, non_blocking=True)
-    minv_t = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
-    valid_t = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(dev, non_blocking=True)
+    if isinstance(minv, torch.Tensor):              # already on the device (geometry='gpu')
+        minv_t, valid_t = minv.contiguous(), valid.contiguous()
+    else:
+        minv_t = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
+        valid_t = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(dev, non_blocking=True)
     out = torch.empty([n, H, H, 3], dtype=torch.uint8, device=dev)
     P = _native.ptr
     with torch.cuda.device(dev):
@@ -66,7 +71,8 @@ def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src, composi
     """The five fp32 tensors of SWAP_OUTPUTS for arbitrary source tables.  ``stages``: the builder's kept stages (``norm_img``,
     ``norm_img_lower`` [N, ph, pw, 3 p], ``norm_clothes_mask*``, ``retain_mask``); ``back`` float64 [N, 10, 3, 3] / ``valid``
     [N, 10]: the people's patch -> image maps as ``patch_pipeline.part_matrices`` returned them; ``lower_parts``: the parts also
-    cut from the lower garment (the builder's).  Three launches.  ``composites``: a dict that receives the two uint8 composites
+    cut from the lower garment (the builder's).  Or ``back`` float64 [N, 10, 9] / ``valid`` uint8 [N, 10] on the device: the INVERTED
+    maps and flags of ``patch_pipeline.part_geometry`` (``back_inv``), used as they are.  Three launches.  ``composites``: a dict that receives the two uint8 composites
     [N, H, H, 3] the assemble reads (SWAP_STAGES: the donor's patches on the person, eroded), which are otherwise dropped."""
     norm_img, norm_lower = stages['norm_img'], stages['norm_img_lower']
     dev = norm_img.device
@@ -83,11 +89,17 @@ def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src, composi
     per_part = lambda t, p: t.reshape(n, ph, pw, p, 3).permute(0, 3, 1, 2, 4).reshape(n * p, ph, pw, 3)
     pool = torch.cat([per_part(norm_img, pu), per_part(norm_lower, pl)]).contiguous()
     mask_pool = torch.cat([per_part(stages['norm_clothes_mask'], pu), per_part(stages['norm_clothes_mask_lower'], pl)]).contiguous()
-    inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(n, pu, 9)
+    if isinstance(back, torch.Tensor):
+        assert pu == 10 and back.shape == (n, 10, 9) and back.dtype == torch.float64 and valid.shape == (n, 10) and valid.dtype == torch.uint8
+        lower_t = torch.from_numpy(lower_parts.astype(np.int64)).to(dev, non_blocking=True)
+        inv, inv_l, valid_l = back, back.index_select(1, lower_t), valid.index_select(1, lower_t)
+    else:
+        inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(n, pu, 9)
+        inv_l, valid_l = inv[:, lower_parts], valid[:, lower_parts]
     index_u = upper_src[:, None] * pu + np.arange(pu)
     index_l = n * pu + lower_src[:, None] * pl + np.arange(pl)
     den_u = _composite(pool, mask_pool, index_u, inv, valid, ph, pw, H)
-    den_l = _composite(pool, mask_pool, index_l, inv[:, lower_parts], valid[:, lower_parts], ph, pw, H)
+    den_l = _composite(pool, mask_pool, index_l, inv_l, valid_l, ph, pw, H)
 
     f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     t = dict(swap_denorm_upper_input=f32(n, 3, H, H), swap_denorm_lower_input=f32(n, 3, H, H), swap_denorm_upper_mask=f32(n, 1, H, H),

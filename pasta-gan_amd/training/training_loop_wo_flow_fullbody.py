@@ -311,34 +311,37 @@ def _numbered_batches(loader, people_jitter, random_seed, num_gpus, rank, cur_ni
         yield raw
 
 def _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs, cur_nimg=0, people_jitter=None,
-                  swap_outfits=None):
+                  swap_outfits=None, part_geometry='host'):
     """(training_set, builder, iterator over prepared batches) of the reference's data set (:261-263).  ``cur_nimg``: the images
     a continued run has consumed; one iteration takes ``batch_size`` positions of the sampler's global stream whatever the
     number of ranks, so the stream goes on at that position.  ``people_jitter``: a specification of
     ``training.tryon_batch.jitter_spec``; the batches are then numbered (``_numbered_batches``) and the builder jitters them.  A
     data set opened with ``erase_masks='strokes'`` has its batches numbered as well, with or without the jitter, and the builder
     draws their erase masks.  ``swap_outfits``: dict(region=, group=) of training/swap_outfits.py; every batch then also carries the
-    swapped inputs of the unpaired pass, made from its own stages after the mirroring and the jitter."""
+    swapped inputs of the unpaired pass, made from its own stages after the mirroring and the jitter.  ``part_geometry``: 'host' or
+    'gpu' (``--part-geometry``), where the batches' body-part matrices are solved; the builder RETURNED is always the
+    host's, since it serves the sample grid, which keeps the host geometry."""
     from training import dataset as dataset_module
     from training.tryon_batch import builder_for, jitter_spec
     training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
     sampler = misc.InfiniteSampler(dataset=training_set, rank=rank, num_replicas=num_gpus, seed=random_seed, skip=cur_nimg)
     loader = torch.utils.data.DataLoader(dataset=training_set, sampler=sampler, batch_size=batch_size // num_gpus,
                                          collate_fn=dataset_module.collate, **(data_loader_kwargs or {}))
-    builder = builder_for(training_set, device)
+    grid_builder = builder_for(training_set, device)
+    builder = builder_for(training_set, device, part_geometry) if part_geometry != 'host' else grid_builder
     erase_strokes = training_set.erase_strokes if getattr(training_set, 'erase_masks', 'files') == 'strokes' else None
     if people_jitter is not None or erase_strokes is not None:
         loader = _numbered_batches(loader, jitter_spec(people_jitter) if people_jitter is not None else None, random_seed, num_gpus, rank,
                                    int(cur_nimg), erase_strokes=erase_strokes)
     if swap_outfits is not None:
         swap_outfits = dict(swap_outfits)
-        return training_set, builder, (builder.build(raw, swap=swap_outfits) for raw in loader)
-    return training_set, builder, (builder.build(raw) for raw in loader)
+        return training_set, grid_builder, (builder.build(raw, swap=swap_outfits) for raw in loader)
+    return training_set, grid_builder, (builder.build(raw) for raw in loader)
 
 def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0, total_iters=4, cfg=None, device=None, progress_fn=None,
                   training_set_kwargs=None, data_loader_kwargs=None, run_dir=None, total_kimg=25000, kimg_per_tick=4,
                   image_snapshot_ticks=50, network_snapshot_ticks=50, resume_pkl=None, abort_fn=None, snapshot_gnum=23, metrics=None,
-                  metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None, swap_outfits=None):
+                  metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None, swap_outfits=None, part_geometry='host'):
     """Without ``run_dir``: run ``total_iters`` iterations and write nothing.  Without ``training_set_kwargs`` the data is
     synthetic; with them the data set is built by ``construct_class_by_name`` (e.g. ``class_name='training.dataset.UvitonDatasetFull',
     path=...``) and read through an InfiniteSampler and a DataLoader (:147-152), each batch prepared on the GPU by
@@ -352,7 +355,9 @@ def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0
     ``people_jitter``: a specification of ``training.tryon_batch.jitter_spec`` (``--jitter-people``); the training batches, and only
     they, are jittered per item by the run's seed and the item's position in the sampler's stream.
     ``swap_outfits``: dict(region=, group=) (``--swap_weight``, ``--swap-region``); the training batches, and only they,
-    also carry every person in a batch-mate's garments, which a loss with ``swap_weight > 0`` trains on."""
+    also carry every person in a batch-mate's garments, which a loss with ``swap_weight > 0`` trains on.
+    ``part_geometry``: 'host' or 'gpu' (``--part-geometry``; DESIGN 8n): where the training batches' body-part matrices are solved;
+    the sample grid and the metrics keep the host's."""
     device = device if device is not None else torch.device('cuda', rank)
     if resume_state is not None and run_dir is None:
         raise ValueError('resume_state needs a run_dir: only a training run is continued')
@@ -361,14 +366,14 @@ def training_loop(num_gpus=1, rank=0, batch_size=16, batch_gpu=16, random_seed=0
     if run_dir is not None:
         return training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs,
                             data_loader_kwargs, total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn,
-                            snapshot_gnum, metrics, metric_set_kwargs, save_state, resume_state, people_jitter, swap_outfits)
+                            snapshot_gnum, metrics, metric_set_kwargs, save_state, resume_state, people_jitter, swap_outfits, part_geometry)
     step = TrainingStep(device, cfg=cfg, num_gpus=num_gpus, rank=rank, batch_size=batch_size, batch_gpu=batch_gpu, random_seed=random_seed)
     if training_set_kwargs is None:
         data = SyntheticFullBodyBatch(batch_size // num_gpus, device, seed=rank)
         batches = iter(lambda: data, None)
     else:
         _, _, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs,
-                                      people_jitter=people_jitter, swap_outfits=swap_outfits)
+                                      people_jitter=people_jitter, swap_outfits=swap_outfits, part_geometry=part_geometry)
     for it in range(total_iters):
         step.run(next(batches))
         if progress_fn is not None:
@@ -386,7 +391,7 @@ def sample_images(G_ema, grid, grid_z, batch_gpu):
 
 def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cfg, device, progress_fn, training_set_kwargs, data_loader_kwargs,
                  total_kimg, kimg_per_tick, image_snapshot_ticks, network_snapshot_ticks, resume_pkl, abort_fn, snapshot_gnum, metrics=None,
-                 metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None, swap_outfits=None):
+                 metric_set_kwargs=None, save_state=False, resume_state=None, people_jitter=None, swap_outfits=None, part_geometry='host'):
     """The reference's training_loop (:247-654) around ``TrainingStep.run``.  Returns the step; on rank 0 it carries the
     ``snapshot_grid`` and the ``grid_z`` the sample images were drawn with."""
     import psutil
@@ -410,7 +415,7 @@ def training_run(run_dir, num_gpus, rank, batch_size, batch_gpu, random_seed, cf
         print('Loading training set...')
     training_set, builder, batches = _data_batches(num_gpus, rank, batch_size, random_seed, device, training_set_kwargs, data_loader_kwargs,
                                                    cur_nimg=int(state['cur_nimg']) if state is not None else 0, people_jitter=people_jitter,
-                                                   swap_outfits=swap_outfits)
+                                                   swap_outfits=swap_outfits, part_geometry=part_geometry)
     if rank == 0:
         print()
         print('Num images: ', len(training_set))

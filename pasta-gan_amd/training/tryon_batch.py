@@ -20,7 +20,8 @@ and after that, for a batch that carries ``raw['erase_strokes']`` (``--erase-mas
 
     pasta_erase_strokes_u8   the erase masks of the batch, drawn: random thick polylines on the padded square, one mask per item
 
-The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps.
+The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps
+(a builder with geometry='gpu': one launch, patch_pipeline.part_geometry).
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
 ``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
@@ -442,16 +443,18 @@ class FullBodyBatch:
 class FullBodyBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate`` -> FullBodyBatch on ``device``.  ``swap`` = dict(region=,
     group=) or dict(upper_src=, lower_src=): the batch also carries the swapped inputs of training/swap_outfits.py, made from this
-    batch's stages; kept stages then include that module's two SWAP_STAGES."""
+    batch's stages; kept stages then include that module's two SWAP_STAGES.  ``geometry`` = 'host' or 'gpu': where the body parts'
+    matrices are solved (patch_pipeline.part_matrices, or part_geometry's one launch: DESIGN 8n)."""
 
     # how the warp-back matrices of this builder's stages are formed (training/snapshot_grid.py forms them again per cell):
     # the parts also cut from the lower garment, part_matrices' x_pad and shin_fallback, and whether the key points are shifted
     # by the padding in float64 first
     lower_parts, x_pad, shin_fallback, shifted = (6, 7, 8, 9), 32, False, False
 
-    def __init__(self, device, box_factor=2):
+    def __init__(self, device, box_factor=2, geometry='host'):
         self.device = torch.device(device)
         self.box_factor = box_factor
+        self.geometry = patch_pipeline.check_geometry(geometry)
 
     def build(self, raw, keep_stages=False, swap=None):
         dev = self.device
@@ -472,7 +475,7 @@ class FullBodyBatchBuilder:
             _native.check(lib.pasta_palm_mask_u8(P(parsing), P(quads), P(present), P(palm), n, H, W, *PALM_BOXES, s))
             _native.check(lib.pasta_tryon_masks_u8(P(image), P(parsing), P(palm), P(retain_mask), P(gt), *[P(g) for g in garments], n, H, W, s))
         norm_img, norm_lower, den_u, den_l, m_invs, hand_masks, norm_mask, norm_mask_lower, back, valid = patch_pipeline.normalize_batch(
-            *garments, keypoints, self.box_factor, want_matrices=True)
+            *garments, keypoints, self.box_factor, want_matrices=True, geometry=self.geometry)
         norm_img, norm_lower, den_u, den_l = (t.contiguous() for t in (norm_img, norm_lower, den_u, den_l))
         arm = hand_masks.reshape(n, 4, H, H).contiguous()
         ph, pw, cu, cl = norm_img.shape[1], norm_img.shape[2], norm_img.shape[3], norm_lower.shape[3]
@@ -492,12 +495,12 @@ class FullBodyBatchBuilder:
         return FullBodyBatch(t, stages if keep_stages else None, image)
 
 
-def builder_for(training_set, device):
+def builder_for(training_set, device, geometry='host'):
     """The builder that prepares the batches of ``training_set``: by the data set's class."""
     from training import dataset
     if isinstance(training_set, dataset.UvitonDatasetFull_512):
         from training.tryon_regions import FullBodyRegionBatchBuilder
-        return FullBodyRegionBatchBuilder(device)
+        return FullBodyRegionBatchBuilder(device, geometry=geometry)
     if isinstance(training_set, dataset.UvitonDatasetFull):
-        return FullBodyBatchBuilder(device)
+        return FullBodyBatchBuilder(device, geometry=geometry)
     raise TypeError('no training batch builder for %s' % type(training_set).__name__)

@@ -15,7 +15,8 @@ and, after the generator, ``images_to_u8`` (pasta_images_to_u8: the bytes test.p
 region of ``photo_paste_mask`` (pasta_photo_paste_mask_u8: the kept parts, and with --background / --kept-garments photo the
 background and the person's own garments where the generator's region heads agree; ``paste_rules`` fills its table).
 
-The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
+The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps
+(a builder with geometry='gpu': one launch, patch_pipeline.part_geometry).  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads).
 
@@ -68,11 +69,13 @@ class TryOnPairOutfitBatch(TryOnPairBatch):
 class TryOnPairOutfitBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` at 256 x 192 -> TryOnPairOutfitBatch on ``device``.
     The batch's M distinct people are uploaded once, their stick figures drawn once and their matrices solved once; the
-    per-sample views (the person, the owner of the upper garment, the owner of the lower one) are gathered on the device."""
+    per-sample views (the person, the owner of the upper garment, the owner of the lower one) are gathered on the device.
+    ``geometry`` = 'host' or 'gpu': where the matrices are solved (patch_pipeline.part_geometry: DESIGN 8n)."""
 
-    def __init__(self, device, box_factor=2):
+    def __init__(self, device, box_factor=2, geometry='host'):
         self.device = torch.device(device)
         self.box_factor = box_factor
+        self.geometry = patch_pipeline.check_geometry(geometry)
 
     def build(self, raw, keep_stages=False):
         dev = self.device
@@ -98,7 +101,7 @@ class TryOnPairOutfitBatchBuilder:
                                                           P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
                                                           P(garment_mask[n:]), n, H, W, SIX_IS_LOWER, s))
         patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_u, valid_l, valid_p = patch_pipeline.normalize_pair_outfit_batch(
-            garment_img, sticks, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
+            garment_img, sticks, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor, geometry=self.geometry)
         stick = sticks.index_select(0, person_ix)
         parts, ph, pw = patches.shape[1], patches.shape[2], patches.shape[3]
         t, outs = output_tensors(TryOnPairOutfitBatch.KEYS, n, H, (6 * parts, ph, pw), dev, OUTFIT_OUTPUTS)

@@ -9,7 +9,8 @@ in four loader processes, as a few launches per batch:
     patch_pipeline.normalize_outfit_batch   two forward warps + two eroded composites (csrc/patches.hip, csrc/tryon_pairs.hip)
     pasta_tryon_outfit_assemble       the nine fp32 tensors of test_512.py (its outputs 0..8)
 
-The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps.  Key points
+The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps
+(a builder with geometry='gpu': one launch, patch_pipeline.part_geometry).  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621).
 
@@ -102,11 +103,13 @@ class TryOnOutfitBatch(TryOnRegionBatch):
 class TryOnOutfitBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` -> TryOnOutfitBatch on ``device``.  The batch's M
     distinct people are uploaded once and their matrices solved once; the per-sample views (the person, the owner of the upper
-    garment, the owner of the lower one) are gathered on the device."""
+    garment, the owner of the lower one) are gathered on the device.  ``geometry`` = 'host' or 'gpu': where the matrices are solved
+    (patch_pipeline.part_geometry: DESIGN 8n)."""
 
-    def __init__(self, device, box_factor=2):
+    def __init__(self, device, box_factor=2, geometry='host'):
         self.device = torch.device(device)
         self.box_factor = box_factor
+        self.geometry = patch_pipeline.check_geometry(geometry)
 
     def build(self, raw, keep_stages=False):
         t, stages = self._prepare(raw, ('upper', 'lower'), dict(upper='upper_valid', lower='lower_valid', person='person_valid'), keep_stages)
@@ -134,7 +137,7 @@ class TryOnOutfitBatchBuilder:
                                                           P(retain_img), P(garment_img[:n]), P(garment_mask[:n]), P(garment_img[n:]),
                                                           P(garment_mask[n:]), n, H, W, SIX_IS_LOWER, _native.stream()))
         *normalized, valid_u, valid_l, valid_p = patch_pipeline.normalize_outfit_batch(
-            garment_img, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor)
+            garment_img, garment_mask, shift_keypoints(people_kp, lp), *host_idx, self.box_factor, geometry=self.geometry)
         patches, patches_l, _, _, den_u, den_l, _ = normalized
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
         photograph = dict(upper=u_image, lower=l_image)
@@ -158,10 +161,10 @@ class TryOnRegionBatchBuilder(TryOnOutfitBatchBuilder):
     stacked on the device after the upload.  ``clothes`` is always the DONOR's photograph, which at 'lowerbody' is not the upper
     garment's owner, and there is no ``clothes_lower``."""
 
-    def __init__(self, device, change_region, box_factor=2):
+    def __init__(self, device, change_region, box_factor=2, geometry='host'):
         if change_region not in REGIONS:
             raise ValueError('change region %s is invalid.' % change_region)
-        super().__init__(device, box_factor)
+        super().__init__(device, box_factor, geometry)
         self.change_region = change_region
 
     def build(self, raw, keep_stages=False):
@@ -180,9 +183,10 @@ class FullBodyRegionBatchBuilder:
     # see FullBodyBatchBuilder: parts 0, 6..9 are also cut from the lower garment; key points shifted in float64, x_pad = 0
     lower_parts, x_pad, shin_fallback, shifted = patch_pipeline.LOWER_PARTS_512, 0, False, True
 
-    def __init__(self, device, box_factor=2):
+    def __init__(self, device, box_factor=2, geometry='host'):
         self.device = torch.device(device)
         self.box_factor = box_factor
+        self.geometry = patch_pipeline.check_geometry(geometry)
 
     def build(self, raw, keep_stages=False, swap=None):
         dev = self.device
@@ -207,7 +211,8 @@ class FullBodyRegionBatchBuilder:
                                                    P(garment_mask[:n]), P(garment_mask[n:]), n, H, W, s))
         own = np.arange(n)                  # everyone wears their own garments: the N people are solved once
         patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, _, _, _, part_masks, back, valid = patch_pipeline.normalize_outfit_batch(
-            garment_img, garment_mask, shift_keypoints(kp, lp), own, own, own, self.box_factor, want_part_masks=True, want_matrices=True)
+            garment_img, garment_mask, shift_keypoints(kp, lp), own, own, own, self.box_factor, want_part_masks=True, want_matrices=True,
+            geometry=self.geometry)
         pu, pl, ph, pw = patches.shape[1], patches_l.shape[1], patches.shape[2], patches.shape[3]
         arm_a, arm_b = patch_pipeline.ARM_PARTS[2], patch_pipeline.ARM_PARTS[3]
         t, outs = output_tensors(FullBodyBatch.KEYS, n, H, (3 * (pu + pl), ph, pw), dev)

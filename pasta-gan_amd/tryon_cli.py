@@ -33,8 +33,8 @@ def _local_snapshot(path):
 
 
 def shared_options(dataroot_help, batchsize):
-    """The decorator of the options both command lines take up to --storage, --png-encoder, the two --kept options, --background
-    and --kept-garments, in the order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
+    """The decorator of the options both command lines take up to --storage, --png-encoder, the two --kept options, --background,
+    --kept-garments and --part-geometry, in the order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
     options = [
         click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True),
         click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)'),
@@ -46,7 +46,8 @@ def shared_options(dataroot_help, batchsize):
         click.option('--outdir', help='Where to save the output images', type=str, required=True, metavar='DIR'),
         click.option('--dataroot', help=dataroot_help, type=str, required=True),
         click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=batchsize, show_default=True),
-        storage_option, png_encoder_option, kept_parts_option, kept_feather_option, background_option, kept_garments_option]
+        storage_option, png_encoder_option, kept_parts_option, kept_feather_option, background_option, kept_garments_option,
+        part_geometry_option]
 
     def decorate(f):
         for option in reversed(options):
@@ -139,6 +140,32 @@ def _chosen_encoder(png_encoder):
     if png_encoder == 'pil' and context is not None:
         return context.meta.get(_ENCODER_KEY, png_encoder)
     return png_encoder
+
+
+# --part-geometry: where the body parts' quadrilaterals, 8 x 8 systems and inverses are solved: numpy on the host, one
+# part at a time, or one launch per batch (training.patch_pipeline.part_geometry), a second rule that prepares almost exactly the
+# same bytes.  Recorded in the click context like --png-encoder; train_wo_flow_fullbody.py declares its own option of this name.
+_GEOMETRY_KEY = 'pasta.part_geometry'
+PART_GEOMETRY_HELP = ('Where the body-part matrices are solved: numpy on the host, or one launch per batch on the GPU (almost exactly the '
+                      'same bytes: DESIGN 8n)')
+
+
+def _record_geometry(context, param, value):
+    context.meta[_GEOMETRY_KEY] = value
+    return value
+
+
+part_geometry_option = click.option('--part-geometry', help=PART_GEOMETRY_HELP, type=click.Choice(['host', 'gpu']), default='host',
+                                    show_default=True, expose_value=False, callback=_record_geometry)
+
+
+def _chosen_geometry(part_geometry):
+    """The ``part_geometry`` keyword of ``generate_256`` / ``generate_512``; left at 'host' under a running command line, it is what
+    that command line's --part-geometry said (``_chosen_encoder``)."""
+    context = click.get_current_context(silent=True)
+    if part_geometry == 'host' and context is not None:
+        return context.meta.get(_GEOMETRY_KEY, part_geometry)
+    return part_geometry
 
 
 # --kept-parts photo: the photograph's head, palms and shoes (metrics.tryon_fidelity.keep_mask, the region `retain` carries) are
@@ -295,10 +322,11 @@ def generate(G, t, gen_z, truncation_psi, noise_mode):
 
 
 def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None, kept_radius=None,
-                 pasted=('kept_parts',)):
+                 pasted=('kept_parts',), part_geometry='host'):
     """--scores: the figures of ``metrics.tryon_fidelity.finish`` (prefix ``tryon``) and what the run was, as one JSON line,
     printed and written to ``scores_file``.  ``mode``: what was dressed, when it was not the plain pair lists; ``kept_radius``:
-    the feather of a run that pastes from the photograph, whose report says so and names each of ``pasted`` (PASTE_OPTIONS)."""
+    the feather of a run that pastes from the photograph, whose report says so and names each of ``pasted`` (PASTE_OPTIONS);
+    ``part_geometry``: named in the report only when it is not the host's."""
     import json
     from metrics import tryon_fidelity
     report = dict(results=tryon_fidelity.finish(partials, 'tryon', pixels=pixels), pairs=pairs, network=network_pkl, dataroot=dataroot,
@@ -310,6 +338,8 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
     if kept_radius is not None:
         report.update([(name, 'photo') for name in pasted if name == 'kept_parts'], kept_feather=kept_radius)
         report.update((name, 'photo') for name in pasted if name != 'kept_parts')
+    if part_geometry != 'host':
+        report['part_geometry'] = part_geometry
     line = json.dumps(report)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
@@ -318,7 +348,7 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
 
 
 def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None,
-          kept_radius=None, pasted=('kept_parts',), png_encoder='pil'):
+          kept_radius=None, pasted=('kept_parts',), part_geometry='host', png_encoder='pil'):
     """The loop of both command lines.  ``choose(device)`` -> (data set, collate function, builder, ``pictures``), called once the
     snapshot is loaded; ``pictures(batch, raw, gen_imgs, count, content)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names
     under ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
@@ -331,10 +361,14 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
     then those of these bytes, handed to
     ``score_batch`` as the centres (b + 0.5) / 127.5 - 1 of the bytes' intervals, which ``unit_to_u8`` returns to b.
     ``png_encoder``: 'pil' copies the batch to the host and saves image by image; 'gpu' encodes the batch where it is
-    (torch_utils.ops.png_encode.save) and copies back the compressed bytes.  Names, layout and scores are settled before either."""
+    (torch_utils.ops.png_encode.save) and copies back the compressed bytes.  Names, layout and scores are settled before either.
+    ``part_geometry``: 'host' or 'gpu', handed to ``choose(device, part_geometry)`` for its builder and named in the scores report
+    when 'gpu'."""
     _local_snapshot(network_pkl)
     if png_encoder not in ('pil', 'gpu'):
         raise click.BadParameter('%r is not one of pil, gpu' % (png_encoder,), param_hint='--png-encoder')
+    if part_geometry not in ('host', 'gpu'):
+        raise click.BadParameter('%r is not one of host, gpu' % (part_geometry,), param_hint='--part-geometry')
 
     import numpy as np
     import PIL.Image
@@ -347,7 +381,7 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
     device = torch.device('cuda')
     G = load_generator(network_pkl, device, storage)
     os.makedirs(outdir, exist_ok=True)
-    dataset, collate_fn, builder, pictures = choose(device)
+    dataset, collate_fn, builder, pictures = choose(device, part_geometry)
     loader = pair_loader(dataset, batchsize, workers, collate_fn)
     scoring = scores_file is not None
     partials = tryon_fidelity.new_partials(len(dataset), device) if scoring else None
@@ -386,12 +420,12 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
             count += 1
     print('finish: %d images under %s' % (count, outdir))
     if scoring:
-        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius, pasted)
+        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius, pasted, part_geometry)
 
 
 def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
                  scores_file=None, storage=None, kept_parts='generated', kept_feather=None, background='generated',
-                 kept_garments='generated', png_encoder='pil'):
+                 kept_garments='generated', part_geometry='host', png_encoder='pil'):
     """test_512.py: the 512 x 320 model on outfits, prepared by training.tryon_regions.TryOnOutfitBatchBuilder and written to
     ``<outdir>/<count>.png`` in list order.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_512_test), written as ``upper donor | lower donor | person | generated`` (512 x 2048).
@@ -401,12 +435,13 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     is refused before anything is read.  ``kept_parts`` 'photo' with ``kept_feather`` (None: 2): the ``generated`` panel's content
     columns carry the photograph's kept parts (``dress``), the other panels and the panel's padding are untouched; ``background``
     / ``kept_garments`` 'photo' widen the pasted region to the photograph's background and to the garment(s) of the person's own
-    that an item keeps; a feather with none of the three is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
+    that an item keeps (DESIGN 8i); a feather with none of the three is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``);
+    ``part_geometry``: where the builder solves the body parts (``_chosen_geometry``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
     kept_radius, pasted = _paste_plan(kept_parts, kept_feather, background, kept_garments)
 
-    def choose(device):
+    def choose(device, geometry='host'):
         import torch
         from training import dataset as custom_dataset
         from training.tryon_pairs import images_to_u8
@@ -428,14 +463,14 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
                 c0 = len(panels) * side + (side - content.shape[2]) // 2
                 images[:, :, c0:c0 + content.shape[2]] = content
             return images, [str(count + i).zfill(3) + '.png' for i in range(batch.batch)]
-        return dataset, collate_fn, TryOnOutfitBatchBuilder(device), pictures
+        return dataset, collate_fn, TryOnOutfitBatchBuilder(device, geometry=geometry), pictures
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage,
-          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder))
+          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder), part_geometry=_chosen_geometry(part_geometry))
 
 
 def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
                  scores_file=None, storage=None, kept_parts='generated', kept_feather=None, background='generated',
-                 kept_garments='generated', png_encoder='pil'):
+                 kept_garments='generated', part_geometry='host', png_encoder='pil'):
     """test.py: the 256 x 192 model on outfits, prepared by training.tryon_pairs.TryOnPairOutfitBatchBuilder; only the generated
     image is written, columns 32..223 of the generator's square.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
@@ -445,12 +480,13 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     ``outfits`` or ``change-region <region>``; a run with neither option has none.  ``kept_parts`` 'photo' with ``kept_feather``
     (None: 2): the written image carries the photograph's kept parts (``dress``); ``background`` / ``kept_garments`` 'photo' widen
     the pasted region to the photograph's background and to the garment(s) of the person's own that an item keeps; a
-    feather with none of the three is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``)."""
+    feather with none of the three is refused like the two modes.  ``png_encoder``: who writes the files (``dress``, ``_chosen_encoder``);
+    ``part_geometry``: where the builder solves the body parts (``_chosen_geometry``)."""
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
     kept_radius, pasted = _paste_plan(kept_parts, kept_feather, background, kept_garments)
 
-    def choose(device):
+    def choose(device, geometry='host'):
         from training import dataset as custom_dataset
         from training.tryon_pairs import TryOnPairOutfitBatchBuilder, images_to_u8
         if outfits_file is not None:
@@ -466,7 +502,7 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             names = [os.path.join(who[0].split('/')[0], '__'.join(stem(name) for name in who) + '.png')
                      for who in zip(raw['person_name'], *[raw[k] for k in worn])]
             return (images_to_u8(gen_imgs, (height - width) // 2, width) if content is None else content), names
-        return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device), pictures
+        return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device, geometry=geometry), pictures
     mode = 'outfits' if outfits_file is not None else change_region and 'change-region ' + change_region
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode,
-          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder))
+          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder), part_geometry=_chosen_geometry(part_geometry))

@@ -129,6 +129,8 @@ def run_command(args):
         timed(tryon_regions.TryOnOutfitBatchBuilder if args.size == 512 else tryon_pairs.TryOnPairOutfitBatchBuilder, 'build', 'builder')
     tree, pkl = os.path.join(args.dir, 'tree%d' % args.size), os.path.join(args.dir, 'snapshot%d.pkl' % args.size)
     extra = {} if args.encoder == 'parent' else dict(png_encoder=args.encoder)
+    if args.geometry != 'parent':
+        extra['part_geometry'] = args.geometry
 
     def call(outdir):
         if args.size == 512:
@@ -148,7 +150,7 @@ def run_command(args):
     finally:
         sys.stdout = real_stdout
     files = [os.path.join(d, f) for d, _, fs in os.walk(outdir) for f in fs]
-    line = dict(package=os.path.relpath(package, ROOT), size=args.size, encoder=args.encoder, seconds=round(seconds, 3), images=65,
+    line = dict(package=os.path.relpath(package, ROOT), size=args.size, encoder=args.encoder, geometry=args.geometry, seconds=round(seconds, 3), images=65,
                 images_per_s=round(65 / seconds, 2), files=len(files), bytes_written=sum(os.path.getsize(f) for f in files))
     if args.phases:
         line['phases_s'] = {k: round(v, 3) for k, v in phases.items()}
@@ -169,6 +171,8 @@ def main():
     c.add_argument('--package', default=os.path.join(ROOT, 'pasta-gan_amd'))
     c.add_argument('--size', type=int, choices=[256, 512], required=True)
     c.add_argument('--encoder', choices=['parent', 'pil', 'gpu'], required=True, help="'parent': a tree from before the option, called without it")
+    c.add_argument('--geometry', choices=['parent', 'host', 'gpu'], default='parent',
+                   help="the commands' part_geometry keyword (DESIGN 8n); 'parent': a tree from before that option, called without it")
     c.add_argument('--phases', action='store_true')
     args = ap.parse_args()
     dict(batch=run_batch, prepare=run_prepare, command=run_command)[args.what](args)

@@ -1,6 +1,6 @@
 """Timings of the test builders on one GPU, the figures of DESIGN.md section 9 (outfits), at 512 x 320:
 
-    python tools/bench_tryon_builders.py [--batch 16] [--warmup 5] [--repeats 30]
+    python tools/bench_tryon_builders.py [--batch 16] [--warmup 5] [--repeats 30] [--rounds 1]
 
   1. TryOnOutfitBatchBuilder.build for --batch fully mixed outfits (three distinct people each: M = 3 * batch);
   2. the same for --batch (p, c, -) outfits (M = 2 * batch);
@@ -10,7 +10,9 @@ and at 256 x 192, with the people of tests/tryon_pairs_tree.py:
   5. the same for --batch (p, c, -) outfits (M = 2 * batch);
   6. TryOnPairBatchBuilder.build for --batch pairs (M = 2 * batch), which 5 equals bit for bit.
 Each line is the median wall time around build() and torch.cuda.synchronize() after the warm-ups, and the median host time
-spent inside patch_pipeline.part_matrices (the 8 x 8 solves) with its share.  The people are those of the tiny trees that have
+spent inside patch_pipeline.part_matrices (the 8 x 8 solves) with its share.  Every builder is measured twice, ``geometry`` 'host'
+and, on the next line, 'gpu' (patch_pipeline.part_geometry's one launch: DESIGN 8n; its part_matrices time is 0 by construction);
+--rounds repeats the whole list in the same process on the same batches.  The people are those of the tiny trees that have
 key points, repeated under distinct names: only the count of distinct people matters to the timing."""
 import argparse
 import json
@@ -44,6 +46,7 @@ def main():
     parser.add_argument('--batch', type=int, default=16)
     parser.add_argument('--warmup', type=int, default=5)
     parser.add_argument('--repeats', type=int, default=30)
+    parser.add_argument('--rounds', type=int, default=1)
     args = parser.parse_args()
 
     import torch
@@ -76,7 +79,7 @@ def main():
         return out
     patch_pipeline.part_matrices = timed_solve
 
-    def measure(name, build, raw):
+    def measure(name, build, raw, geometry):
         for _ in range(args.warmup):
             build(raw)
             torch.cuda.synchronize()
@@ -90,17 +93,20 @@ def main():
             total.append(time.perf_counter() - t)
             host.append(solving[0])
         ms, solve_ms = 1e3 * float(np.median(total)), 1e3 * float(np.median(host))
-        print(json.dumps(dict(name=name, median_ms=round(ms, 2), part_matrices_ms=round(solve_ms, 2), part_matrices_share=round(solve_ms / ms, 3),
+        print(json.dumps(dict(name=name, geometry=geometry, median_ms=round(ms, 2), part_matrices_ms=round(solve_ms, 2), part_matrices_share=round(solve_ms / ms, 3),
                               min_ms=round(1e3 * min(total), 2), max_ms=round(1e3 * max(total), 2))), flush=True)
 
-    outfits, regions = TryOnOutfitBatchBuilder('cuda'), TryOnRegionBatchBuilder('cuda', 'fullbody')
-    measure('outfits, fully mixed (M = %d)' % (3 * n), outfits.build, outfit_batch(people, mixed))
-    measure('outfits (p, c, -) (M = %d)' % (2 * n), outfits.build, outfit_batch(people, own_lower))
-    measure('region builder, fullbody (M = %d)' % (2 * n), regions.build, collate_pairs([pairs[i % len(pairs)] for i in range(n)]))
-    outfits, plain = TryOnPairOutfitBatchBuilder('cuda'), TryOnPairBatchBuilder('cuda')
-    measure('256: outfits, fully mixed (M = %d)' % (3 * n), outfits.build, outfit_batch(people_256, mixed))
-    measure('256: outfits (p, c, -) (M = %d)' % (2 * n), outfits.build, outfit_batch(people_256, own_lower))
-    measure('256: pair builder (M = %d)' % (2 * n), plain.build, collate_pairs([pairs_256[i % len(pairs_256)] for i in range(n)]))
+    cases = [('outfits, fully mixed (M = %d)' % (3 * n), TryOnOutfitBatchBuilder, (), outfit_batch(people, mixed)),
+             ('outfits (p, c, -) (M = %d)' % (2 * n), TryOnOutfitBatchBuilder, (), outfit_batch(people, own_lower)),
+             ('region builder, fullbody (M = %d)' % (2 * n), TryOnRegionBatchBuilder, ('fullbody',),
+              collate_pairs([pairs[i % len(pairs)] for i in range(n)])),
+             ('256: outfits, fully mixed (M = %d)' % (3 * n), TryOnPairOutfitBatchBuilder, (), outfit_batch(people_256, mixed)),
+             ('256: outfits (p, c, -) (M = %d)' % (2 * n), TryOnPairOutfitBatchBuilder, (), outfit_batch(people_256, own_lower)),
+             ('256: pair builder (M = %d)' % (2 * n), TryOnPairBatchBuilder, (), collate_pairs([pairs_256[i % len(pairs_256)] for i in range(n)]))]
+    for _ in range(args.rounds):
+        for name, cls, extra, raw in cases:
+            for geometry in ('host', 'gpu'):
+                measure(name, cls('cuda', *extra, geometry=geometry).build, raw, geometry)
 
 
 if __name__ == '__main__':
