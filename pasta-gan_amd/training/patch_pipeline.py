@@ -6,12 +6,14 @@ fourteen) forward warps of a whole batch are ONE launch of ``pasta_warp_perspect
 + mask test + compositing of all parts one launch of ``pasta_patch_composite_u8`` per garment.
 
 The projective matrices are 8 x 8 solves on eighteen key points -- host work, numpy float64, as in the reference -- or, with
-``geometry='gpu'``, ONE launch of ``pasta_part_geometry`` per batch (part_geometry below): a second, documented rule
-that no host solve and no upload of matrices precedes.  Image
+``geometry='gpu'``, ONE launch of ``pasta_part_geometry`` per batch (part_geometry below): a second, documented rule.
+Either way every consumer takes one form, PartMaps: the INVERTED maps and the flags on the device, made once per batch by
+``part_maps``; host matrices handed to a launch wrapper are converted at its entry by ``on_device``.  Image
 tensors stay uint8 HWC as the reference's arrays.  Numerics: OpenCV's fixed-point bilinear interpolation restated from its
 published algorithm (csrc/patches.hip); OpenCV is not installed here, so parity with cv2 is UNPINNED (DESIGN.md section 9);
 the kernels are held bit for bit to oracle/ref_patches.py in tests/test_patches_gpu.py."""
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -92,15 +94,17 @@ def perspective_matrix(src, dst):
 
 
 def adjugate_inverse(m):
-    """Inverse of a 3 x 3 float64 matrix by cofactors (what cv2.warpPerspective applies to its argument); zeros if singular."""
+    """Inverses of 3 x 3 float64 matrices [..., 3, 3] by cofactors (what cv2.warpPerspective applies to its argument), all of them in
+    one pass; zeros where singular."""
     m = np.asarray(m, np.float64)
-    c = np.empty([3, 3])
-    c[0, 0] = m[1, 1] * m[2, 2] - m[1, 2] * m[2, 1]; c[0, 1] = m[0, 2] * m[2, 1] - m[0, 1] * m[2, 2]; c[0, 2] = m[0, 1] * m[1, 2] - m[0, 2] * m[1, 1]
-    c[1, 0] = m[1, 2] * m[2, 0] - m[1, 0] * m[2, 2]; c[1, 1] = m[0, 0] * m[2, 2] - m[0, 2] * m[2, 0]; c[1, 2] = m[0, 2] * m[1, 0] - m[0, 0] * m[1, 2]
-    c[2, 0] = m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0]; c[2, 1] = m[0, 1] * m[2, 0] - m[0, 0] * m[2, 1]; c[2, 2] = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
-    det = (m[0, 0] * (m[1, 1] * m[2, 2] - m[1, 2] * m[2, 1]) - m[0, 1] * (m[1, 0] * m[2, 2] - m[1, 2] * m[2, 0]) +
-           m[0, 2] * (m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0]))
-    return c * (1.0 / det) if det != 0 else np.zeros([3, 3])
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = (m[..., i, j] for i in range(3) for j in range(3))
+    with np.errstate(all='ignore'):
+        c = np.stack([m11 * m22 - m12 * m21, m02 * m21 - m01 * m22, m01 * m12 - m02 * m11,
+                      m12 * m20 - m10 * m22, m00 * m22 - m02 * m20, m02 * m10 - m00 * m12,
+                      m10 * m21 - m11 * m20, m01 * m20 - m00 * m21, m00 * m11 - m01 * m10], axis=-1)
+        det = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20)
+        det = det[..., None]
+        return np.where(det != 0, c * (1.0 / det), 0.0).reshape(m.shape)
 
 
 def part_matrices(joints, width, height, box_factor=2, x_pad=32, shin_fallback=False):
@@ -181,34 +185,65 @@ def _u8(t):
     return t.contiguous()
 
 
-def _on_device(t, dtype, dev):
-    """A table for a launch: a tensor already on the device as it is (made contiguous), a host array uploaded."""
+class PartMaps(NamedTuple):
+    """The body-part maps of M people, the one form every consumer takes, whoever solved them."""
+    fwd_inv: torch.Tensor       # float64 [M, 10, 9] on the device: what the forward warp launches take (the image -> patch maps, inverted)
+    back_inv: torch.Tensor      # float64 [M, 10, 9] on the device: what the composites take (the patch -> image maps, inverted)
+    valid: torch.Tensor         # uint8 [M, 10] on the device: the part flags
+    m_invs: torch.Tensor        # float32 [M, 10, 3, 3]: the patch -> image maps cast, zeros where invalid (the M_invs tensor); a host
+                                # tensor under 'host', a device tensor under 'gpu'
+    flags: np.ndarray           # bool [M, 10] on the host: what upper_valid / lower_valid / person_valid are cut from
+
+
+def host_part_maps(joints, width, height, box_factor=2, x_pad=32, shin_fallback=False):
+    """PartMaps' five fields as numpy arrays, no GPU: ONE part_matrices call for the M people and one batched inverse each of
+    their forward and back maps."""
+    fwd, back, flags = part_matrices(joints, width, height, box_factor, x_pad, shin_fallback)
+    m = len(flags)
+    return PartMaps(adjugate_inverse(fwd).reshape(m, 10, 9), adjugate_inverse(back).reshape(m, 10, 9), flags.astype(np.uint8),
+                    np.where(flags[..., None, None], back, 0.0).astype(np.float32), flags)
+
+
+def part_maps(joints, width, height, box_factor=2, x_pad=32, shin_fallback=False, device='cuda', geometry='host'):
+    """PartMaps of the people ``joints`` [M, 18, 3] (host) on ``device``.  ``geometry='host'``: host_part_maps and three uploads;
+    ``'gpu'``: part_geometry's one launch, nothing solved or inverted in Python, the host flags from part_valid."""
+    dev = torch.device(device)
+    if check_geometry(geometry) == 'gpu':
+        g = part_geometry(joints, width, height, box_factor, x_pad, shin_fallback, dev, ('fwd_inv', 'back_inv', 'm_inv', 'valid'))
+        return PartMaps(g['fwd_inv'], g['back_inv'], g['valid'], g['m_inv'].reshape(-1, 10, 3, 3), part_valid(joints, shin_fallback))
+    h = host_part_maps(joints, width, height, box_factor, x_pad, shin_fallback)
+    return PartMaps(*[torch.from_numpy(a).to(dev) for a in h[:3]], torch.from_numpy(h.m_invs), h.flags)
+
+
+def on_device(t, dtype, dev, shape=None, invert=False):
+    """An argument of a launch, the ONE place host arguments are converted: a tensor already on the device is checked (device, dtype,
+    ``shape``) and made contiguous; a host array is cast and uploaded.  ``invert``: host 3 x 3 float64 matrices [..., 3, 3], inverted
+    here, all at once, into the [..., 9] the kernels read -- a device tensor is taken as inverted already."""
     if t is None:
         return None
-    if isinstance(t, torch.Tensor):
-        assert t.device == dev and t.dtype == dtype, 'a %s tensor on %s' % (dtype, dev)
-        return t.contiguous()
-    return torch.as_tensor(np.asarray(t, torch.empty(0, dtype=dtype).numpy().dtype), device=dev)
+    if not isinstance(t, torch.Tensor):
+        t = np.asarray(t, torch.empty(0, dtype=dtype).numpy().dtype)
+        if invert:
+            t = adjugate_inverse(t).reshape(*t.shape[:-2], 9)
+        t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    assert t.device == dev and t.dtype == dtype and (shape is None or t.shape == tuple(shape)), \
+        'a %s tensor %s on %s, not %s %s on %s' % (dtype, shape, dev, t.dtype, list(t.shape), t.device)
+    return t.contiguous()
 
 
-def warp_perspective(src, matrices, out_hw, border='constant', src_index=None, valid=None, minv=None):
+def _upload(table, dtype, dev):
+    return torch.from_numpy(np.ascontiguousarray(table, dtype=dtype)).to(dev, non_blocking=True)
+
+
+def warp_perspective(src, matrices, out_hw, border='constant', src_index=None, valid=None):
     """Batched ``cv2.warpPerspective(src[i], M, (w, h), borderMode=...)`` for uint8 [*, H, W, C] GPU tensors: ``matrices``
-    [B, 3, 3] float64 (host), one output per matrix; ``src_index`` [B] picks the source of each (default: i).  ``minv`` (with
-    ``matrices`` None): the INVERTED matrices [B, 9] float64 already on the device (part_geometry's ``fwd_inv``), nothing inverted
-    or uploaded here; ``src_index`` (int32) and ``valid`` (uint8) may be device tensors as well."""
+    [B, 3, 3] float64 on the host, or the INVERTED ones [B, 9] float64 already on the device (PartMaps' ``fwd_inv``); one output
+    per matrix.  ``src_index`` [B] int32 picks the source of each (default: i) and ``valid`` [B] uint8 flags it; host or device."""
     _native.require_gpu(src, 'warp_perspective')
     dev = src.device
-    if minv is not None:
-        assert matrices is None and minv.ndim == 2 and minv.shape[1] == 9
-        inv_t = _on_device(minv, torch.float64, dev)
-        b = int(inv_t.shape[0])
-    else:
-        b = int(len(matrices))
-        inv = np.ascontiguousarray(np.stack([adjugate_inverse(m) for m in matrices]).reshape(b, 9))
-        inv_t = torch.from_numpy(inv).to(dev)
-    idx_t = _on_device(src_index, torch.int32, dev)
-    val_t = _on_device(valid, torch.uint8, dev)
-    assert (idx_t is None or idx_t.numel() == b) and (val_t is None or val_t.numel() == b)
+    b = int(len(matrices))
+    inv_t = on_device(matrices, torch.float64, dev, (b, 9), invert=True)
+    idx_t, val_t = on_device(src_index, torch.int32, dev, (b,)), on_device(valid, torch.uint8, dev, (b,))
     oh, ow = out_hw
     dst = torch.empty([b, oh, ow, src.shape[-1]], dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
@@ -221,25 +256,21 @@ def warp_perspective(src, matrices, out_hw, border='constant', src_index=None, v
 def inverse_maps(back, parts):
     """[n * p, 9] float64: the inverse cv2.warpPerspective applies to ``back[i, k]`` for every sample i and every k of ``parts``,
     sample-major."""
-    return np.ascontiguousarray(np.stack([adjugate_inverse(back[i, k]) for i in range(len(back)) for k in parts]).reshape(-1, 9))
+    return np.ascontiguousarray(adjugate_inverse(np.asarray(back)[:, list(parts)]).reshape(-1, 9))
 
 
 MAX_ERODE_RADIUS = 8        # ER_MAX_R of csrc/patch_erode.h: the halo its LDS tiles hold
 
 
-def _parts_on(parts, dev):
-    return torch.as_tensor(np.asarray(parts, np.int64), device=dev)
-
-
 def composite(patches, masks, back, valid, parts, height, width, radius=None, want_part_masks=False):
     """patch -> image (BORDER_CONSTANT) + mask test + compositing of ``patches`` / ``masks`` [N, p, h, w, 3] in order, one launch:
-    index j is part ``parts[j]`` of ``back`` [N, 10, 3, 3] / ``valid`` [N, 10], the maps of the people the result is drawn on.
+    index j is part ``parts[j]`` of ``back`` / ``valid``, the maps of the people the result is drawn on: PartMaps' ``back_inv``
+    [N, 10, 9] float64 and ``valid`` [N, 10] uint8 on the device, or the host's ``back`` [N, 10, 3, 3] and flags [N, 10], converted
+    on entry; the parts are gathered on the device.
     ``radius`` None: pasta_patch_composite_u8, the mask tested as warped; a value: pasta_patch_composite_eroded_u8, the mask eroded
     (2 * radius + 1) square first; a sequence [N]: the same entry with its ``radii``, sample i eroded by ``radius[i]`` (0: as warped),
     still one launch.  A radius outside 0 .. 8 raises ValueError.  Returns (image uint8 [N, height, width, 3], part masks uint8
-    [N, p, height, width] or None).  ``back`` and ``valid`` as device tensors: part_geometry's ``back_inv`` [N, 10, 9] float64 (already
-    inverted) and ``valid`` [N, 10] uint8 of those people; the parts are then gathered on the device, nothing is inverted or uploaded
-    but the list of parts."""
+    [N, p, height, width] or None)."""
     n, p, ph, pw = patches.shape[:4]
     dev = patches.device
     lib = _native.lib()
@@ -256,13 +287,11 @@ def composite(patches, masks, back, valid, parts, height, width, radius=None, wa
             raise ValueError('composite: radius %d of sample %d (0..%d)' % (radii[bad[0]], bad[0], MAX_ERODE_RADIUS))
         radius_t = torch.from_numpy(radii.astype(np.uint8)).to(dev)       # held until the launch is queued
         entry, extra = lib.pasta_patch_composite_eroded_u8, (0, _native.ptr(radius_t))
-    if isinstance(back, torch.Tensor):
-        assert back.shape == (n, 10, 9) and back.dtype == torch.float64 and valid.shape == (n, 10) and valid.dtype == torch.uint8
-        parts_t = _parts_on(parts, dev)
-        inv_t, val_t = back.index_select(1, parts_t).contiguous(), valid.index_select(1, parts_t).contiguous()
-    else:
-        inv_t = torch.from_numpy(inverse_maps(back, parts)).to(dev)
-        val_t = torch.as_tensor(np.ascontiguousarray(valid[:, parts]).astype(np.uint8), device=dev)
+    back = on_device(back, torch.float64, dev, invert=True)
+    assert back.ndim == 3 and back.shape[0] == n and back.shape[2] == 9 and len(parts) == p and 0 <= min(parts) and max(parts) < back.shape[1]
+    valid = on_device(valid, torch.uint8, dev, back.shape[:2])
+    parts_t = torch.as_tensor(np.asarray(parts, np.int64), device=dev)
+    inv_t, val_t = back.index_select(1, parts_t).contiguous(), valid.index_select(1, parts_t).contiguous()
     out = torch.empty([n, height, width, 3], dtype=torch.uint8, device=dev)
     pm = torch.empty([n, p, height, width], dtype=torch.uint8, device=dev) if want_part_masks else None
     patches, masks = patches.contiguous(), masks.contiguous()             # held until the launch is queued
@@ -276,57 +305,46 @@ def normalize_batch(upper_img, lower_img, upper_mask, lower_mask, joints, box_fa
     """``normalize`` (dataset.py:838-927) for a batch on the GPU.  Images and 3-channel masks: uint8 [N, H, W, 3] CUDA tensors;
     ``joints`` [N, 18, 3] (host).  Returns the reference's tuple, batched:
     (norm_img [N,h,w,30], norm_img_lower [N,h,w,12], denorm_upper [N,H,W,3], denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32,
-     denorm_hand_masks [N,4,H,W,1], clothes_masks [N,h,w,30], clothes_masks_lower [N,h,w,12]).  ``want_matrices``: two more values,
-    the float64 patch -> image maps [N,10,3,3] and valid flags [N,10] that part_matrices solved here (training/swap_outfits.py
-    warps a batch-mate's patches back with them instead of solving the people again).  ``geometry='gpu'``: the matrices come from
-    part_geometry and stay on the device -- no host solve, M_invs a device tensor, and ``want_matrices`` gives the device
-    ``back_inv`` [N,10,9] float64 and ``valid`` [N,10] uint8 in place of the host maps and flags."""
+     denorm_hand_masks [N,4,H,W,1], clothes_masks [N,h,w,30], clothes_masks_lower [N,h,w,12]).  M_invs is PartMaps' ``m_invs``: a
+    host tensor under ``geometry='host'``, a device tensor under ``'gpu'``.  ``want_matrices``: two more values, PartMaps' device
+    ``back_inv`` [N,10,9] float64 and ``valid`` [N,10] uint8 (training/swap_outfits.py warps a batch-mate's patches back with them
+    instead of solving the people again)."""
     upper_img, lower_img, upper_mask, lower_mask = _u8(upper_img), _u8(lower_img), _u8(upper_mask), _u8(lower_mask)
     n, height, width, _ = upper_img.shape
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
-    sample = np.repeat(np.arange(n, dtype=np.int32), 10)
-    if check_geometry(geometry) == 'gpu':
-        g = part_geometry(joints, width, height, box_factor, device=upper_img.device, outputs=('fwd_inv', 'back_inv', 'm_inv', 'valid'))
-        back, valid, m_invs = g['back_inv'], g['valid'], g['m_inv'].reshape(n, 10, 3, 3)
-        sample_t = torch.from_numpy(sample).to(upper_img.device, non_blocking=True)
-        def cut(t, which):                  # [n, 10, ...] -> the items of a forward launch, flat
-            t = t if which == 'all' else t[:, LOWER_FROM:]
-            return t.reshape(-1, *t.shape[2:])
-        warp = lambda src, which: warp_perspective(src, None, (ph, pw), 'replicate', cut(sample_t.reshape(n, 10), which), cut(valid, which),
-                                                   minv=cut(g['fwd_inv'], which))
-    else:
-        fwd, back, valid = part_matrices(joints, width, height, box_factor)
-        flat_valid = valid.reshape(-1)
-        everything = np.arange(n * 10)
-        rows = dict(all=everything, legs=everything.reshape(n, 10)[:, LOWER_FROM:].reshape(-1))       # the items of a forward launch
-        m_invs = torch.from_numpy(np.where(valid[..., None, None], back, 0.0).astype(np.float32))
-        # image -> patch (BORDER_REPLICATE): all ten parts of every sample in one launch per source tensor
-        warp = lambda src, which: warp_perspective(src, fwd.reshape(-1, 3, 3)[rows[which]], (ph, pw), 'replicate', sample[rows[which]],
-                                                   flat_valid[rows[which]])
+    dev = upper_img.device
+    maps = part_maps(joints, width, height, box_factor, device=dev, geometry=geometry)
+    sample = _upload(np.repeat(np.arange(n), 10), np.int32, dev).reshape(n, 10)
+
+    def cut(t, which):                  # [n, 10, ...] -> the items of a forward launch, flat
+        t = t if which == 'all' else t[:, LOWER_FROM:]
+        return t.reshape(-1, *t.shape[2:])
+    # image -> patch (BORDER_REPLICATE): all ten parts of every sample in one launch per source tensor
+    warp = lambda src, which: warp_perspective(src, cut(maps.fwd_inv, which), (ph, pw), 'replicate', cut(sample, which), cut(maps.valid, which))
     p_img = warp(upper_img, 'all').reshape(n, 10, ph, pw, 3)
     p_mask = warp(upper_mask, 'all').reshape(n, 10, ph, pw, 3)
     p_img_l = warp(lower_img, 'legs').reshape(n, 10 - LOWER_FROM, ph, pw, 3)
     p_mask_l = warp(lower_mask, 'legs').reshape(n, 10 - LOWER_FROM, ph, pw, 3)
 
     # patch -> image + mask test + compositing, all parts in order, one launch per garment
-    den_u, part_masks = composite(p_img, p_mask, back, valid, list(range(10)), height, width, want_part_masks=True)
-    den_l, _ = composite(p_img_l, p_mask_l, back, valid, list(range(LOWER_FROM, 10)), height, width)
+    den_u, part_masks = composite(p_img, p_mask, maps.back_inv, maps.valid, list(range(10)), height, width, want_part_masks=True)
+    den_l, _ = composite(p_img_l, p_mask_l, maps.back_inv, maps.valid, list(range(LOWER_FROM, 10)), height, width)
     hwc = lambda t: t.permute(0, 2, 3, 1, 4).reshape(n, ph, pw, -1)            # parts concatenated along the channel axis (:918-921)
     hand_masks = part_masks[:, list(ARM_PARTS)].unsqueeze(-1)
-    out = (hwc(p_img), hwc(p_img_l), den_u, den_l, m_invs, hand_masks, hwc(p_mask), hwc(p_mask_l))
-    return out + (back, valid) if want_matrices else out
+    out = (hwc(p_img), hwc(p_img_l), den_u, den_l, maps.m_invs, hand_masks, hwc(p_mask), hwc(p_mask_l))
+    return out + (maps.back_inv, maps.valid) if want_matrices else out
 
 
-def _people_geometry(people_joints, person_idx, items, width, height, box_factor, shin_fallback, dev):
-    """``geometry='gpu'`` of the outfit normalisers: the M people solved in one launch (key points already shifted: x_pad = 0), the
-    forward launches' inverse maps and flags gathered by ``items`` (flat: owner * 10 + part) and the PERSONS' maps by ``person_idx``,
-    on the device: (minv [B, 9], flags [B], back_inv [N, 10, 9], valid [N, 10] uint8, M_invs [N, 10, 3, 3] float32)."""
-    g = part_geometry(people_joints, width, height, box_factor, 0, shin_fallback, dev, ('fwd_inv', 'back_inv', 'm_inv', 'valid'))
-    items_t = torch.from_numpy(np.ascontiguousarray(items, dtype=np.int64)).to(dev, non_blocking=True)
-    person_t = torch.from_numpy(np.ascontiguousarray(person_idx, dtype=np.int64)).to(dev, non_blocking=True)
-    return (g['fwd_inv'].reshape(-1, 9).index_select(0, items_t), g['valid'].reshape(-1).index_select(0, items_t),
-            g['back_inv'].index_select(0, person_t), g['valid'].index_select(0, person_t),
-            g['m_inv'].index_select(0, person_t).reshape(-1, 10, 3, 3))
+def _gathered(maps, items, person_idx, dev):
+    """What the outfit normalisers take from the M people's ``maps``, gathered on the device by two tables uploaded once: the forward
+    launches' inverse maps and flags by ``items`` (flat: owner * 10 + part) and the PERSONS' maps by ``person_idx``:
+    (minv [B, 9], flags [B], back_inv [N, 10, 9], valid [N, 10] uint8, M_invs [N, 10, 3, 3] float32, where ``maps.m_invs`` lives)."""
+    m = len(maps.flags)
+    assert items.min() >= 0 and items.max() < 10 * m and person_idx.min() >= 0 and person_idx.max() < m, 'an index outside the %d people' % m
+    items_t, person_t = _upload(items, np.int64, dev), _upload(person_idx, np.int64, dev)
+    return (maps.fwd_inv.reshape(-1, 9).index_select(0, items_t), maps.valid.reshape(-1).index_select(0, items_t),
+            maps.back_inv.index_select(0, person_t), maps.valid.index_select(0, person_t),
+            maps.m_invs.index_select(0, person_t if maps.m_invs.is_cuda else torch.from_numpy(person_idx)))
 
 
 UPPER_PARTS = 6             # the test set: parts 0..5 from the clothes donor, 6..9 from the person (dataset.py:1470-1478)
@@ -345,38 +363,31 @@ def normalize_pair_outfit_batch(garment_img, people_stick, garment_mask, people_
     mask).  All ten parts are warped back with the PERSON's M_inv: parts 0..5 into denorm_upper through the eroded composite,
     parts 6..9 into denorm_lower in one launch whose radius is per sample, 0 (the plain composite) where the person wears their
     own lower garment and ERODE_RADIUS where it is somebody else's.  Returns (patches, stick_patches, mask_patches
-    [N,10,h,w,3], denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's), upper_valid, lower_valid,
-    person_valid [N,10] bool).  ``geometry='gpu'``: part_geometry in place of part_matrices -- no host solve, the owner and person
-    tables are index_select on the device, M_invs is a device tensor and the three flag arrays come from part_valid."""
+    [N,10,h,w,3], denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the person's; where PartMaps' ``m_invs``
+    lives), upper_valid, lower_valid, person_valid [N,10] bool).  ``geometry``: part_maps'; the owner and person tables are
+    index_select on the device."""
     garment_img, people_stick, garment_mask = _u8(garment_img), _u8(people_stick), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
     assert n2 == 2 * n and garment_mask.shape == garment_img.shape and people_stick.shape[1:] == garment_img.shape[1:]
     person_idx, upper_idx, lower_idx = (np.asarray(ix, np.int64).reshape(n) for ix in (person_idx, upper_idx, lower_idx))
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
+    dev = garment_img.device
     from_upper = np.arange(10) < UPPER_PARTS
     owner = np.where(from_upper[None, :], upper_idx[:, None], lower_idx[:, None])      # [N, 10]: whose matrices and stick figure part k takes
-    part = np.arange(10)[None, :]
-    if check_geometry(geometry) == 'gpu':
-        mats, valid_all = None, part_valid(people_joints, shin_fallback=True)
-        minv, valid, back, valid_p, m_invs = _people_geometry(people_joints, person_idx, (owner * 10 + part).reshape(-1), width, height,
-                                                              box_factor, True, garment_img.device)
-    else:
-        fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0, shin_fallback=True)
-        back, valid_p = back[person_idx], valid_all[person_idx]
-        mats, valid, minv = fwd[owner, part].reshape(-1, 3, 3), valid_all[owner, part].reshape(-1), None
-        m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
+    maps = part_maps(people_joints, width, height, box_factor, 0, True, dev, geometry)
+    minv, valid, back, valid_p, m_invs = _gathered(maps, (owner * 10 + np.arange(10)[None, :]).reshape(-1), person_idx, dev)
     # item (i, k) reads garment i of the upper ones (0..N-1) for k < 6 and of the lower ones (N..2N-1) otherwise
-    garment = (np.arange(n, dtype=np.int32)[:, None] + np.where(from_upper, 0, n).astype(np.int32)[None, :]).reshape(-1)
-    warp = lambda src, index: warp_perspective(src, mats, (ph, pw), 'replicate', index, valid, minv=minv).reshape(n, 10, ph, pw, 3)
+    garment = _upload((np.arange(n)[:, None] + np.where(from_upper, 0, n)[None, :]).reshape(-1), np.int32, dev)
+    warp = lambda src, index: warp_perspective(src, minv, (ph, pw), 'replicate', index, valid).reshape(n, 10, ph, pw, 3)
     patches, mask_patches = warp(garment_img, garment), warp(garment_mask, garment)
-    stick_patches = warp(people_stick, owner.astype(np.int32).reshape(-1))
+    stick_patches = warp(people_stick, _upload(owner.reshape(-1), np.int32, dev))
 
     upper, lower = list(range(UPPER_PARTS)), list(range(UPPER_PARTS, 10))
     den_u, _ = composite(patches[:, upper], mask_patches[:, upper], back, valid_p, upper, height, width, ERODE_RADIUS)
     radius = np.where(lower_idx != person_idx, ERODE_RADIUS, 0)
     den_l, _ = composite(patches[:, lower], mask_patches[:, lower], back, valid_p, lower, height, width, radius)
-    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx], valid_all[person_idx]
+    return patches, stick_patches, mask_patches, den_u, den_l, m_invs, maps.flags[upper_idx], maps.flags[lower_idx], maps.flags[person_idx]
 
 
 LOWER_PARTS_512 = (0, 6, 7, 8, 9)       # the 512 x 320 set: the torso and the legs are also cut from the lower garment (dataset.py:2023)
@@ -396,38 +407,29 @@ def normalize_outfit_batch(garment_img, garment_mask, people_joints, person_idx,
     matrix is missing is zeros; a part whose M_inv is missing is skipped.  Returns (patches [N,10,h,w,3], patches_lower
     [N,5,h,w,3], mask_patches, mask_patches_lower, denorm_upper, denorm_lower [N,H,W,3], M_invs [N,10,3,3] float32 (the
     person's), upper_valid, lower_valid, person_valid [N,10] bool).  ``want_part_masks``: an eleventh value, the eroded 0 / 1
-    masks [N,10,H,W] of the upper composite's parts.  ``want_matrices``: two last values, the PERSONS' float64 patch -> image maps
-    [N,10,3,3] and valid flags [N,10] as solved here (training/swap_outfits.py).  ``geometry='gpu'``: as
-    normalize_pair_outfit_batch's; ``want_matrices`` then gives the PERSONS' device ``back_inv`` [N,10,9] float64 and ``valid`` [N,10]
-    uint8."""
+    masks [N,10,H,W] of the upper composite's parts.  ``want_matrices``: two last values, the PERSONS' device ``back_inv`` [N,10,9]
+    float64 and ``valid`` [N,10] uint8 (training/swap_outfits.py).  ``geometry`` and M_invs: as normalize_pair_outfit_batch's."""
     garment_img, garment_mask = _u8(garment_img), _u8(garment_mask)
     n2, height, width, _ = garment_img.shape
     n = n2 // 2
     assert n2 == 2 * n and garment_mask.shape == garment_img.shape
     person_idx, upper_idx, lower_idx = (np.asarray(ix, np.int64).reshape(n) for ix in (person_idx, upper_idx, lower_idx))
     ph, pw = height // 2 ** box_factor, width // 2 ** box_factor
+    dev = garment_img.device
     low = list(LOWER_PARTS_512)
     pu, pl = 10, len(low)
     # items: (i, k) of the upper garments, then (i, k) of the lower garments, which read source N + i
-    if check_geometry(geometry) == 'gpu':
-        items = np.concatenate([(upper_idx[:, None] * 10 + np.arange(pu)).reshape(-1), (lower_idx[:, None] * 10 + np.asarray(low)).reshape(-1)])
-        mats, valid_all = None, part_valid(people_joints)
-        minv, valid, back, valid_p, m_invs = _people_geometry(people_joints, person_idx, items, width, height, box_factor, False,
-                                                              garment_img.device)
-    else:
-        fwd, back, valid_all = part_matrices(people_joints, width, height, box_factor, x_pad=0)
-        back, valid_p = back[person_idx], valid_all[person_idx]
-        mats = np.concatenate([fwd[upper_idx].reshape(-1, 3, 3), fwd[lower_idx][:, low].reshape(-1, 3, 3)])
-        valid, minv = np.concatenate([valid_all[upper_idx].reshape(-1), valid_all[lower_idx][:, low].reshape(-1)]), None
-        m_invs = torch.from_numpy(np.where(valid_p[..., None, None], back, 0.0).astype(np.float32))
-    src_index = np.concatenate([np.repeat(np.arange(n, dtype=np.int32), pu), np.repeat(np.arange(n, 2 * n, dtype=np.int32), pl)])
-    warp = lambda src: warp_perspective(src, mats, (ph, pw), 'replicate', src_index, valid, minv=minv)
+    items = np.concatenate([(upper_idx[:, None] * 10 + np.arange(pu)).reshape(-1), (lower_idx[:, None] * 10 + np.asarray(low)).reshape(-1)])
+    maps = part_maps(people_joints, width, height, box_factor, 0, False, dev, geometry)
+    minv, valid, back, valid_p, m_invs = _gathered(maps, items, person_idx, dev)
+    src_index = _upload(np.concatenate([np.repeat(np.arange(n), pu), np.repeat(np.arange(n, 2 * n), pl)]), np.int32, dev)
+    warp = lambda src: warp_perspective(src, minv, (ph, pw), 'replicate', src_index, valid)
     split = lambda t: (t[:n * pu].reshape(n, pu, ph, pw, 3), t[n * pu:].reshape(n, pl, ph, pw, 3))
     (patches, patches_l), (mask_patches, mask_patches_l) = split(warp(garment_img)), split(warp(garment_mask))
 
     den_u, part_masks = composite(patches, mask_patches, back, valid_p, list(range(pu)), height, width, ERODE_RADIUS, want_part_masks)
     den_l, _ = composite(patches_l, mask_patches_l, back, valid_p, low, height, width, ERODE_RADIUS)
-    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, valid_all[upper_idx], valid_all[lower_idx],
-           valid_all[person_idx])
+    out = (patches, patches_l, mask_patches, mask_patches_l, den_u, den_l, m_invs, maps.flags[upper_idx], maps.flags[lower_idx],
+           maps.flags[person_idx])
     out = out + (part_masks,) if want_part_masks else out
     return out + (back, valid_p) if want_matrices else out

@@ -5,7 +5,7 @@ the whole outfit, the last the top.  The reference warps and erodes every cell o
 gnum = 23) and keeps fp32 tensors of all cells on the device; here
 
     setup    the training builder's build(keep_stages=True) of the gnum people, then pasta_grid_composite_eroded_u8 twice
-             (upper, lower) for all cells                                                  (csrc/train_grid.hip)
+             (upper, lower) for all cells: swap_outfits.grid_composites                    (csrc/train_grid.hip)
     inputs   pasta_grid_assemble: the fp32 tensors G_ema takes, for one minibatch of cells
     save     pasta_image_grid_tile_u8 per minibatch into one uint8 canvas, one copy to the host, PIL writes the PNG
 
@@ -22,9 +22,9 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 from training.dataset import collate
+from training.swap_outfits import grid_composites
 from training.tryon_batch import shift_keypoints
 
-ERODE_RADIUS = 2            # cv2.erode(..., np.ones((5, 5))) of every warped-back mask, upper and lower (:63, :91, :98)
 INPUT_KEYS = ['denorm_upper_input', 'denorm_lower_input', 'denorm_upper_mask', 'denorm_lower_mask', 'style_input', 'pose', 'retain']
 
 
@@ -62,47 +62,22 @@ class SnapshotGrid:
         self.image = torch.nn.functional.pad(image, (0, 0, lp, H - W - lp), value=255).contiguous()
         self.stick, self.retain_mask = stages['stick'], stages['retain_mask']
         self.norm_img, self.norm_lower = stages['norm_img'], stages['norm_img_lower']
-        ph, pw = self.norm_img.shape[1], self.norm_img.shape[2]
-        pu, pl = self.norm_img.shape[3] // 3, self.norm_lower.shape[3] // 3
-
-        # the pool of patches [T, ph, pw, 3]: part k of person i at i * pu + k, lower part k at g * pu + i * pl + k
-        per_part = lambda t, p: t.reshape(g, ph, pw, p, 3).permute(0, 3, 1, 2, 4).reshape(g * p, ph, pw, 3)
-        pool = torch.cat([per_part(self.norm_img, pu), per_part(self.norm_lower, pl)]).contiguous()
-        mask_pool = torch.cat([per_part(stages['norm_clothes_mask'], pu), per_part(stages['norm_clothes_mask_lower'], pl)]).contiguous()
 
         # Every part is warped with the ROW's M_inv (:86), inverted as cv2.warpPerspective inverts its argument.  These are the
         # float64 matrices normalize_batch inverts, not the float32 copy it returns.  The reference skips a part on
         # M_inv.sum() == 0 (:87), its stand-in for "get_crop found no quadrilateral"; part_matrices' valid flag says that
         # directly (a present matrix whose entries happen to sum to zero is used here and skipped there).
         # The builder says how it formed them: 256 x 192 adds the padding inside get_crop, 512 x 320 shifts the key points first.
+        # The grid keeps the host geometry whatever the training batches use.
         keypoints = np.asarray(raw['keypoints'], np.float64)
         if builder.shifted:
             keypoints = shift_keypoints(keypoints, lp)
-        _, back, valid = patch_pipeline.part_matrices(keypoints, H, H, builder.box_factor, x_pad=builder.x_pad,
-                                                      shin_fallback=builder.shin_fallback)
-        inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(g, pu, 9)
+        maps = patch_pipeline.part_maps(keypoints, H, H, builder.box_factor, builder.x_pad, builder.shin_fallback, self.norm_img.device, 'host')
         upper_src, lower_src = cell_sources(gnum)
-        lower_parts = np.asarray(builder.lower_parts)              # the parts also cut from the lower garment (:76: 6..9 at 256 x 192)
-        assert len(lower_parts) == pl
-        parts_u, parts_l = np.arange(pu, dtype=np.int32), np.arange(pl, dtype=np.int32)
-        index_u = (upper_src.reshape(-1, 1) * pu + parts_u).astype(np.int32)
-        index_l = (g * pu + lower_src.reshape(-1, 1) * pl + parts_l).astype(np.int32)
-        row_of = np.repeat(np.arange(g), g)
-        self.denorm_upper = self._composite(pool, mask_pool, index_u, inv[row_of], valid[row_of], ph, pw)
-        self.denorm_lower = self._composite(pool, mask_pool, index_l, inv[row_of][:, lower_parts], valid[row_of][:, lower_parts], ph, pw)
+        # builder.lower_parts: the parts also cut from the lower garment (:76: 6..9 at 256 x 192)
+        self.denorm_upper, self.denorm_lower = grid_composites(stages, maps.back_inv, maps.valid, builder.lower_parts, upper_src, lower_src,
+                                                               np.repeat(np.arange(g), g))
         self._frame = {}
-
-    def _composite(self, pool, mask_pool, index, minv, valid, ph, pw):
-        dev, H = self.device, self.H
-        cells, parts = index.shape
-        index_t, minv_t = torch.from_numpy(np.ascontiguousarray(index)).to(dev), torch.from_numpy(np.ascontiguousarray(minv)).to(dev)
-        valid_t = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(dev)
-        out = torch.empty([cells, H, H, 3], dtype=torch.uint8, device=dev)
-        P = _native.ptr
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().pasta_grid_composite_eroded_u8(P(pool), P(mask_pool), P(index_t), P(minv_t), P(valid_t), P(out), cells,
-                                                                       parts, int(pool.shape[0]), ph, pw, H, H, ERODE_RADIUS, _native.stream()))
-        return out
 
     def inputs(self, lo, hi):
         """The generator's keyword arguments (``c`` = style_input) for cells lo .. hi - 1, fp32 NCHW, made by one launch."""

@@ -3,16 +3,16 @@ batch-mate's garments, prepared on the GPU from the stages the batch builder has
 
     donors          the donor rule: a deterministic roll inside each group of ``batch_gpu`` consecutive samples
     source_tables   whose upper and whose lower patches every sample wears, by swap region
-    swap_tensors    pasta_grid_composite_eroded_u8 twice (upper, lower) and pasta_swap_assemble (csrc/train_grid.hip): the five fp32
+    grid_composites pasta_grid_composite_eroded_u8 twice (upper, lower): the package's one launcher of it, the sample grid's as well
+    swap_tensors    grid_composites and pasta_swap_assemble (csrc/train_grid.hip): the five fp32
                     tensors, by the sample grid's rule (training/snapshot_grid.py) -- the donor's patches warped back with the
                     PERSON's M_inv, every mask eroded 5 x 5
     attach          what both training builders call: the six extra tensors of a batch, by the donor rule or by explicit tables
                     (metrics/tryon_swapped.py takes its donors over the data set, not over the batch)
 
-The warp-back matrices are the float64 ones the builder's normalisation has already solved (``want_matrices`` of
-``patch_pipeline.normalize_batch`` / ``normalize_outfit_batch``): the people's 8 x 8 systems are not solved a second time.
-A builder with ``geometry='gpu'`` hands over the device ``back_inv`` and flags of ``patch_pipeline.part_geometry`` instead: nothing
-is inverted or uploaded here, and the lower garment's parts are gathered on the device.
+The warp-back maps are the device ``back_inv`` and flags the builder's normalisation already holds (``want_matrices`` of
+``patch_pipeline.normalize_batch`` / ``normalize_outfit_batch``, whichever geometry made them): the people are not solved a second
+time and nothing is inverted here.
 ``retain`` and ``pose`` of the swapped pass are the paired batch's own tensors; no erase mask is applied."""
 
 import ctypes
@@ -23,7 +23,8 @@ import torch
 from torch_utils.ops import _native
 from training import patch_pipeline
 
-ERODE_RADIUS = 2            # every part, as training/snapshot_grid.py's cells
+ERODE_RADIUS = 2            # cv2.erode(..., np.ones((5, 5))) of every warped-back mask, upper and lower, of the reference's grid
+                            # (training_loop_wo_flow_fullbody.py:63, :91, :98)
 REGIONS = ('fullbody', 'upperbody', 'lowerbody')
 # the five tensors pasta_swap_assemble writes, in its order, and the keep mask of the region L1 term
 SWAP_OUTPUTS = ['swap_denorm_upper_input', 'swap_denorm_lower_input', 'swap_denorm_upper_mask', 'swap_denorm_lower_mask', 'swap_style_input']
@@ -50,56 +51,60 @@ def source_tables(n, group, region='fullbody'):
     return (donor if region != 'lowerbody' else own), (donor if region != 'upperbody' else own)
 
 
-def _composite(pool, mask_pool, index, minv, valid, ph, pw, H):
-    dev = pool.device
-    n, parts = index.shape
-    index_t = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(dev, non_blocking=True)
-    if isinstance(minv, torch.Tensor):              # already on the device (geometry='gpu')
-        minv_t, valid_t = minv.contiguous(), valid.contiguous()
-    else:
-        minv_t = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
-        valid_t = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(dev, non_blocking=True)
-    out = torch.empty([n, H, H, 3], dtype=torch.uint8, device=dev)
-    P = _native.ptr
-    with torch.cuda.device(dev):
-        _native.check(_native.lib().pasta_grid_composite_eroded_u8(P(pool), P(mask_pool), P(index_t), P(minv_t), P(valid_t), P(out), n, parts,
-                                                                   int(pool.shape[0]), ph, pw, H, H, ERODE_RADIUS, _native.stream()))
-    return out
+def grid_composites(stages, back, valid, lower_parts, upper_src, lower_src, rows):
+    """(upper, lower) uint8 [C, H, H, 3], pasta_grid_composite_eroded_u8 twice: output c wears the upper patches of person
+    ``upper_src[c]`` and the lower ones of ``lower_src[c]``, warped back with the maps of person ``rows[c]`` and eroded 5 x 5 -- the
+    swapped pass (``rows`` = arange(n)) and the sample grid (training/snapshot_grid.py: repeat(arange(g), g)) alike.  ``stages``: the
+    builder's kept stages of the n people; ``back`` / ``valid``: their maps as ``patch_pipeline.composite`` takes them (PartMaps'
+    device ``back_inv`` [n, 10, 9] and ``valid`` [n, 10], or the host's, converted here); ``lower_parts``: the parts also cut from
+    the lower garment (the builder's)."""
+    norm_img, norm_lower = stages['norm_img'], stages['norm_img_lower']
+    dev = norm_img.device
+    n, ph, pw = int(norm_img.shape[0]), int(norm_img.shape[1]), int(norm_img.shape[2])
+    pu, pl = int(norm_img.shape[3]) // 3, int(norm_lower.shape[3]) // 3
+    H = int(stages['retain_mask'].shape[1])
+    upper_src, lower_src, rows = (np.asarray(t, np.int64).reshape(-1) for t in (upper_src, lower_src, rows))
+    assert pu == 10 and len(lower_parts) == pl and 0 <= min(lower_parts) and max(lower_parts) < pu
+    assert upper_src.shape == lower_src.shape == rows.shape and all(t.min() >= 0 and t.max() < n for t in (upper_src, lower_src, rows)), 'a source outside the batch'
+    back = patch_pipeline.on_device(back, torch.float64, dev, (n, 10, 9), invert=True)
+    valid = patch_pipeline.on_device(valid, torch.uint8, dev, (n, 10))
+
+    # the pool of patches [T, ph, pw, 3]: part k of person i at i * pu + k, lower part k at n * pu + i * pl + k
+    per_part = lambda t, p: t.reshape(n, ph, pw, p, 3).permute(0, 3, 1, 2, 4).reshape(n * p, ph, pw, 3)
+    pool = torch.cat([per_part(norm_img, pu), per_part(norm_lower, pl)]).contiguous()
+    mask_pool = torch.cat([per_part(stages['norm_clothes_mask'], pu), per_part(stages['norm_clothes_mask_lower'], pl)]).contiguous()
+    upload = lambda table, dtype: torch.from_numpy(np.ascontiguousarray(table, dtype=dtype)).to(dev, non_blocking=True)
+    rows_t, lower_t = upload(rows, np.int64), upload(lower_parts, np.int64)
+    back, valid = back.index_select(0, rows_t), valid.index_select(0, rows_t)
+
+    def launch(index, minv_t, valid_t):
+        index_t = upload(index, np.int32)
+        out = torch.empty([len(rows), H, H, 3], dtype=torch.uint8, device=dev)
+        P = _native.ptr
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().pasta_grid_composite_eroded_u8(P(pool), P(mask_pool), P(index_t), P(minv_t), P(valid_t), P(out), len(rows),
+                                                                       index.shape[1], int(pool.shape[0]), ph, pw, H, H, ERODE_RADIUS,
+                                                                       _native.stream()))
+        return out
+    return (launch(upper_src[:, None] * pu + np.arange(pu), back, valid),
+            launch(n * pu + lower_src[:, None] * pl + np.arange(pl), back.index_select(1, lower_t).contiguous(),
+                   valid.index_select(1, lower_t).contiguous()))
 
 
 def swap_tensors(stages, back, valid, lower_parts, upper_src, lower_src, composites=None):
     """The five fp32 tensors of SWAP_OUTPUTS for arbitrary source tables.  ``stages``: the builder's kept stages (``norm_img``,
-    ``norm_img_lower`` [N, ph, pw, 3 p], ``norm_clothes_mask*``, ``retain_mask``); ``back`` float64 [N, 10, 3, 3] / ``valid``
-    [N, 10]: the people's patch -> image maps as ``patch_pipeline.part_matrices`` returned them; ``lower_parts``: the parts also
-    cut from the lower garment (the builder's).  Or ``back`` float64 [N, 10, 9] / ``valid`` uint8 [N, 10] on the device: the INVERTED
-    maps and flags of ``patch_pipeline.part_geometry`` (``back_inv``), used as they are.  Three launches.  ``composites``: a dict that receives the two uint8 composites
+    ``norm_img_lower`` [N, ph, pw, 3 p], ``norm_clothes_mask*``, ``retain_mask``); ``back`` / ``valid``: the people's patch -> image
+    maps, as grid_composites takes them (the builders hand over the device pair of their normalisation); ``lower_parts``: the parts
+    also cut from the lower garment (the builder's).  Three launches.  ``composites``: a dict that receives the two uint8 composites
     [N, H, H, 3] the assemble reads (SWAP_STAGES: the donor's patches on the person, eroded), which are otherwise dropped."""
     norm_img, norm_lower = stages['norm_img'], stages['norm_img_lower']
     dev = norm_img.device
     n, ph, pw = int(norm_img.shape[0]), int(norm_img.shape[1]), int(norm_img.shape[2])
     cu, cl = int(norm_img.shape[3]), int(norm_lower.shape[3])
-    pu, pl = cu // 3, cl // 3
     H = int(stages['retain_mask'].shape[1])
     upper_src, lower_src = (np.asarray(t, np.int64).reshape(-1) for t in (upper_src, lower_src))
-    lower_parts = np.asarray(lower_parts)
-    assert upper_src.shape == (n,) and lower_src.shape == (n,) and len(lower_parts) == pl and back.shape[:2] == (n, 10)
-    assert upper_src.min() >= 0 and upper_src.max() < n and lower_src.min() >= 0 and lower_src.max() < n, 'a source outside the batch'
-
-    # the pool of patches [T, ph, pw, 3]: part k of person i at i * pu + k, lower part k at n * pu + i * pl + k (SnapshotGrid's)
-    per_part = lambda t, p: t.reshape(n, ph, pw, p, 3).permute(0, 3, 1, 2, 4).reshape(n * p, ph, pw, 3)
-    pool = torch.cat([per_part(norm_img, pu), per_part(norm_lower, pl)]).contiguous()
-    mask_pool = torch.cat([per_part(stages['norm_clothes_mask'], pu), per_part(stages['norm_clothes_mask_lower'], pl)]).contiguous()
-    if isinstance(back, torch.Tensor):
-        assert pu == 10 and back.shape == (n, 10, 9) and back.dtype == torch.float64 and valid.shape == (n, 10) and valid.dtype == torch.uint8
-        lower_t = torch.from_numpy(lower_parts.astype(np.int64)).to(dev, non_blocking=True)
-        inv, inv_l, valid_l = back, back.index_select(1, lower_t), valid.index_select(1, lower_t)
-    else:
-        inv = patch_pipeline.inverse_maps(back, range(pu)).reshape(n, pu, 9)
-        inv_l, valid_l = inv[:, lower_parts], valid[:, lower_parts]
-    index_u = upper_src[:, None] * pu + np.arange(pu)
-    index_l = n * pu + lower_src[:, None] * pl + np.arange(pl)
-    den_u = _composite(pool, mask_pool, index_u, inv, valid, ph, pw, H)
-    den_l = _composite(pool, mask_pool, index_l, inv_l, valid_l, ph, pw, H)
+    assert upper_src.shape == (n,) and lower_src.shape == (n,)
+    den_u, den_l = grid_composites(stages, back, valid, lower_parts, upper_src, lower_src, np.arange(n))
 
     f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     t = dict(swap_denorm_upper_input=f32(n, 3, H, H), swap_denorm_lower_input=f32(n, 3, H, H), swap_denorm_upper_mask=f32(n, 1, H, H),

@@ -21,7 +21,7 @@ and after that, for a batch that carries ``raw['erase_strokes']`` (``--erase-mas
     pasta_erase_strokes_u8   the erase masks of the batch, drawn: random thick polylines on the padded square, one mask per item
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry below and the 8 x 8 solves of the warps
-(a builder with geometry='gpu': one launch, patch_pipeline.part_geometry).
+(patch_pipeline.part_maps; a builder with geometry='gpu': one launch instead).
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
 ``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
@@ -444,7 +444,7 @@ class FullBodyBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate`` -> FullBodyBatch on ``device``.  ``swap`` = dict(region=,
     group=) or dict(upper_src=, lower_src=): the batch also carries the swapped inputs of training/swap_outfits.py, made from this
     batch's stages; kept stages then include that module's two SWAP_STAGES.  ``geometry`` = 'host' or 'gpu': where the body parts'
-    matrices are solved (patch_pipeline.part_matrices, or part_geometry's one launch: DESIGN 8n)."""
+    matrices are solved (patch_pipeline.part_maps: DESIGN 8n)."""
 
     # how the warp-back matrices of this builder's stages are formed (training/snapshot_grid.py forms them again per cell):
     # the parts also cut from the lower garment, part_matrices' x_pad and shin_fallback, and whether the key points are shifted

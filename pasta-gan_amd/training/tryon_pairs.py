@@ -16,7 +16,7 @@ region of ``photo_paste_mask`` (pasta_photo_paste_mask_u8: the kept parts, and w
 background and the person's own garments where the generator's region heads agree; ``paste_rules`` fills its table).
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps
-(a builder with geometry='gpu': one launch, patch_pipeline.part_geometry).  Key points
+(patch_pipeline.part_maps; a builder with geometry='gpu': one launch instead).  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1100, :1129), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the palm quadrilaterals add the same float64 shift (tryon_batch.palm_quads).
 
@@ -70,7 +70,7 @@ class TryOnPairOutfitBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` at 256 x 192 -> TryOnPairOutfitBatch on ``device``.
     The batch's M distinct people are uploaded once, their stick figures drawn once and their matrices solved once; the
     per-sample views (the person, the owner of the upper garment, the owner of the lower one) are gathered on the device.
-    ``geometry`` = 'host' or 'gpu': where the matrices are solved (patch_pipeline.part_geometry: DESIGN 8n)."""
+    ``geometry`` = 'host' or 'gpu': where the matrices are solved (patch_pipeline.part_maps: DESIGN 8n)."""
 
     def __init__(self, device, box_factor=2, geometry='host'):
         self.device = torch.device(device)

@@ -10,7 +10,7 @@ in four loader processes, as a few launches per batch:
     pasta_tryon_outfit_assemble       the nine fp32 tensors of test_512.py (its outputs 0..8)
 
 The host keeps the file decoding (training/dataset.py), the key-point geometry and the 8 x 8 solves of the warps
-(a builder with geometry='gpu': one launch, patch_pipeline.part_geometry).  Key points
+(patch_pipeline.part_maps; a builder with geometry='gpu': one launch instead).  Key points
 are shifted by the padding in float64 before get_crop's float32 conversion (dataset.py:1623, :1660), so the quadrilaterals are
 formed with x_pad = 0 from pre-shifted joints; the stick figure is drawn from the unshifted ones (:1621).
 
@@ -104,7 +104,7 @@ class TryOnOutfitBatchBuilder:
     """``build(raw_batch)``: a batch of ``training.dataset.collate_outfits`` -> TryOnOutfitBatch on ``device``.  The batch's M
     distinct people are uploaded once and their matrices solved once; the per-sample views (the person, the owner of the upper
     garment, the owner of the lower one) are gathered on the device.  ``geometry`` = 'host' or 'gpu': where the matrices are solved
-    (patch_pipeline.part_geometry: DESIGN 8n)."""
+    (patch_pipeline.part_maps: DESIGN 8n)."""
 
     def __init__(self, device, box_factor=2, geometry='host'):
         self.device = torch.device(device)

@@ -87,14 +87,15 @@ def _same(got, want, what):
     assert got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want), (what, got.dtype, want.dtype, got.shape, want.shape)
 
 
-def _same_matrices(got, want, what):
-    """``want_matrices``: the device back_inv / valid against the host's back / valid."""
+def _same_matrices(got, want, what, joints, **solve):
+    """``want_matrices``: the device back_inv / valid of either geometry against the back / valid of ``part_matrices`` for the
+    persons' ``joints``, solved and inverted here."""
     from training import patch_pipeline
-    back_inv, valid_dev = got
-    back, valid = want
-    _same(back_inv, patch_pipeline.inverse_maps(back, range(10)).reshape(len(back), 10, 9), what + ' back_inv')
-    assert valid_dev.dtype == torch.uint8
-    _same(valid_dev, valid, what + ' valid')
+    _, back, valid = patch_pipeline.part_matrices(joints, 256, 256, **solve)
+    for name, (back_inv, valid_dev) in (('gpu', got), ('host', want)):
+        assert back_inv.is_cuda and valid_dev.is_cuda and valid_dev.dtype == torch.uint8
+        _same(back_inv, patch_pipeline.inverse_maps(back, range(10)).reshape(len(back), 10, 9), '%s %s back_inv' % (what, name))
+        _same(valid_dev, valid, '%s %s valid' % (what, name))
 
 
 @pytest.fixture()
@@ -127,7 +128,7 @@ def test_the_three_normalisations_are_the_hosts(restated):
     assert len(got) == len(want) == 10 and got[4].is_cuda
     for i in range(8):
         _same(got[i], want[i], 'normalize_batch %d' % i)
-    _same_matrices(got[8:], want[8:], 'normalize_batch')
+    _same_matrices(got[8:], want[8:], 'normalize_batch', joints)
     assert want[2].any() and want[3].any()
 
     garments, masks, sticks = _images(rng, 6), _masks(rng, 6), _images(rng, 5)
@@ -143,7 +144,7 @@ def test_the_three_normalisations_are_the_hosts(restated):
     assert len(got) == len(want) == 13 and got[6].is_cuda
     for i in range(11):
         _same(got[i], want[i], 'normalize_outfit_batch %d' % i)
-    _same_matrices(got[11:], want[11:], 'normalize_outfit_batch')
+    _same_matrices(got[11:], want[11:], 'normalize_outfit_batch', people[person], x_pad=0)
     assert want[4].any() and want[5].any()
 
 
