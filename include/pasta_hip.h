@@ -716,6 +716,51 @@ int pasta_tryon_jitter_u8(const uint8_t* image, const uint8_t* parsing, const in
  * mask, never an access outside `out`. */
 int pasta_erase_strokes_u8(const int32_t* segments, const int32_t* counts, uint8_t* out, int n, int S, void* stream);
 
+/* People fitted to the canvas (this project's own rule; --fit-people pad | crop and --fit-filter bilinear | box of
+ * train_wo_flow_fullbody.py, test.py, test_512.py and calc_metrics.py; training/tryon_batch.py's fit_batch, csrc/fit_people.hip).
+ * A raw sample of any size h x w (h >= w) becomes the sample on the canvas H x W of its data set's class, (256, 192) or
+ * (512, 320), BEFORE the mirroring, the jitter and any preparation; everything downstream is unchanged and does not know about it.
+ *   rectangle in integers, with tall = (h W >= w H) and rhu(a / b) = (2 a + b) // (2 b) (training.tryon_batch.fit_rectangle):
+ *             pad   shows the whole photograph: tall ? (Hc, Wc) = (H, rhu(w H / h)) : (Wc, Hc) = (W, rhu(h W / w));
+ *                   oy = (H - Hc) // 2, ox = (W - Wc) // 2; outside the rectangle the photograph is 255 and the label 0;
+ *             crop  fills the canvas with a centre crop: tall ? (Wc, Hc) = (W, rhu(h W / w)) : (Hc, Wc) = (H, rhu(w H / h));
+ *                   oy = -((Hc - H) // 2), ox = -((Wc - W) // 2); only the visible window is computed;
+ *             refused by the data set, with the file's name: h > 8 Hc, w > 8 Wc, Hc > 4 h or Wc > 4 w.
+ *   taps      per axis, from length n_in to n_out, PIL's 8-bit rule (Pillow's Resample.c, precompute_coeffs / normalize_coeffs_8bpc)
+ *             in float64, every operation rounded on its own (training.tryon_batch.fit_taps): scale = n_in / n_out,
+ *             fs = max(scale, 1), support = S0 fs (S0 = 0.5 box, 1 bilinear), ss = 1 / fs; for output position xx:
+ *             center = (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0), cnt = min(int(center + support + 0.5), n_in) - xmin
+ *             (int truncates); wgt[x] = f(((x + xmin) - center + 0.5) ss) for x < cnt, f box: 1 on -0.5 < t <= 0.5, f bilinear:
+ *             1 - |t| on |t| < 1, else 0; ww the sum of wgt in order, wgt[x] /= ww when ww != 0; k[x] = int(0.5 + wgt[x] 2^22).
+ *             Equal lengths: the single tap 2^22 (PIL skips such a pass; the tap returns the byte).
+ *   image     the Hc x Wc image PIL.Image.resize((Wc, Hc), BOX | BILINEAR) returns, byte for byte, placed at (oy, ox):
+ *             out[xx] = min(((2^21 + sum_x src[xmin + x] k[x]) >> 22), 255) per channel, the horizontal pass first into uint8
+ *             [h, Wc] -- that rounded intermediate is part of the result -- then the vertical pass over it.
+ *   labels    a weighted mode over the BOX taps ky, kx of the same two axes, whatever the photograph's filter: the weight of label
+ *             L at fitted (r, c) is the int64 sum of ky[r][i] kx[c][j] over the taps with src[ymin + i][xmin + j] == L; the label of
+ *             greatest weight wins; among tied labels the label of source pixel (((2 r + 1) h) // (2 Hc), ((2 c + 1) w) // (2 Wc))
+ *             when it is one of them, else the smallest.
+ *   erase     not touched: the assemble entries resize a mask from its own size.
+ *   joints    on the host, in float64 (training.tryon_batch.fit_keypoints): a joint with confidence >= 0.1 becomes
+ *             (x sx + ((0.5 sx - 0.5) + ox), y sy + ((0.5 sy - 0.5) + oy)) with sx = Wc / w, sy = Hc / h; one below 0.1 keeps its bits.
+ * An item already at the canvas size is an identity in all three.
+ *   plan      one int32 array for the batch, plan_words long (training.tryon_batch.fit_plan): N records of 16 words
+ *             (h, w, Hc, Wc, oy, ox, the word offsets in the plan of the photograph's x and y tables and of the label map's x and y
+ *             tables, the low 31 bits and the rest of the item's first PIXEL in the packed buffers, 0 ...), then the tables, each
+ *             distinct (n_in, n_out, filter) once: (n_out, ksize) and n_out rows (xmin, cnt, k[ksize]), ksize <= 17.
+ * One entry, out of place, two launches for a whole batch: images [3 pixels] and labels [pixels] are the packed bytes of the N
+ * items (item n at byte 3 off_n and off_n), plan is on the device -> image_out [N,H,W,3], parsing_out [N,H,W], every byte written.
+ * The photographs: a 256-thread workgroup owns a 16 x 64 tile of one item's canvas, runs the horizontal pass for the at most 144
+ * source rows the tile needs into LDS (they never reach HBM), then the vertical pass from LDS; with W a multiple of 16 and a 16-byte
+ * aligned image_out the tile leaves in 16-byte stores along the rows, otherwise byte by byte.  The label maps: a thread owns 16
+ * pixels of a row (one 16-byte store) or one; the labels present in a footprint are collected in a 256-bit set and the weights
+ * summed per present label.  Every number of the plan is read on the device and every index is held inside its buffer whatever the
+ * plan says; an item whose record, tables or row span are not what the rule above makes within the limits is written as padding.
+ * Refused before any launch: a null pointer; an output equal to its input; N outside 1..65535, H or W outside 1..16384; pixels < 1;
+ * plan_words below 16 N or above 2^31 - 1. */
+int pasta_fit_people_u8(const uint8_t* images, const uint8_t* labels, int64_t pixels, const int32_t* plan, int64_t plan_words,
+                        uint8_t* image_out, uint8_t* parsing_out, int N, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Per-batch preparation of the try-on TEST pairs (row f4; UvitonDatasetV19_test._load_raw_image / normalize / __getitem__,
  * training/dataset.py:1085-1525, and test.py:104-150).  Same canvas, restated primitives and exactness as the entries

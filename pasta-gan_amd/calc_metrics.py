@@ -13,7 +13,8 @@ that directory's ``metric-<name>.jsonl``.  --network must name a local file: URL
 carries a ``storage`` field.  --erase-masks files | none | strokes and --erase-strokes SPEC say where the erase masks of
 the scored batches come from, as train_wo_flow_fullbody.py's options do; their default is what the snapshot recorded, and
 ``--erase-masks none`` scores a snapshot trained on mask files on a tree that has none; the ``tryon_*`` metrics
-apply no erase mask and never look for one.  One
+apply no erase mask and never look for one.  --fit-people pad | crop and --fit-filter bilinear | box score a tree whose photographs
+have sizes of their own, fitted to the canvas on the GPU; their default, too, is what the snapshot recorded.  One
 process per GPU; for more than one GPU fresh processes are spawned, each loading the snapshot itself."""
 
 import json
@@ -85,7 +86,8 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--workers', help='Loader processes (file decoding only)', type=click.IntRange(min=0), default=0, show_default=True)
 @tryon_cli.storage_option
 @tryon_cli.erase_options('as the snapshot recorded')
-def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, workers, storage, erase_masks, erase_strokes):
+@tryon_cli.fit_options('as the snapshot recorded', 'as the snapshot recorded, else bilinear')
+def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, workers, storage, erase_masks, erase_strokes, fit_people, fit_filter):
     """Calculate quality metrics of a network snapshot on a tree of the training set's layout."""
     import dnnlib
     from metrics import metric_main
@@ -109,7 +111,7 @@ def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, wor
             ctx.fail('--data: %r is not a directory' % data)
         from training.dataset import training_set_class
         args.dataset_kwargs = dnnlib.EasyDict(class_name=training_set_class(data), path=data)
-        args.dataset_kwargs.update({k: kwargs[k] for k in ('erase_masks', 'erase_strokes') if kwargs is not None and k in kwargs})
+        args.dataset_kwargs.update({k: kwargs[k] for k in ('erase_masks', 'erase_strokes', 'fit', 'fit_filter') if kwargs is not None and k in kwargs})
     else:
         if kwargs is None:
             ctx.fail('Could not look up dataset options; please specify --data')
@@ -123,6 +125,14 @@ def calc_metrics(ctx, network_pkl, metrics, data, gpus, verbose, batch_size, wor
             ctx.fail(str(err))
         for k in ('erase_masks', 'erase_strokes'):
             args.dataset_kwargs.pop(k, None)
+        args.dataset_kwargs.update(given)
+    if fit_people is not None or fit_filter is not None:
+        # --fit-filter alone: another filter for the recorded mode
+        try:
+            given = tryon_cli.fit_kwargs(args.dataset_kwargs.get('fit') if fit_people is None else fit_people,
+                                         args.dataset_kwargs.get('fit_filter') if fit_filter is None else fit_filter)
+        except ValueError as err:
+            ctx.fail(str(err))
         args.dataset_kwargs.update(given)
     args.dataset_kwargs.update(use_labels=False, xflip=False, mirror_people=False)
     if args.verbose:

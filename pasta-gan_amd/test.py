@@ -29,6 +29,10 @@ Differences from the reference, on purpose:
   --part-geometry host | gpu (tryon_cli.part_geometry_option; default host, the bytes this command always wrote): with gpu the body
   parts' matrices of a batch are solved in one launch on the GPU instead of numpy on the host, a second rule that prepares almost
   exactly the same bytes; --scores then says ``part_geometry: gpu``.
+  --fit-people pad | crop with --fit-filter bilinear | box (tryon_cli.fit_people_option; default: none) takes photographs of any
+  size, which need not match within a pair or an outfit: every person is fitted to the model's canvas on the GPU before anything
+  else (training.tryon_batch.fit_batch), padded so that all of the photograph shows or centre-cropped so that it fills
+  the canvas; --scores then names both options.
 """
 
 from typing import List, Optional

@@ -271,6 +271,7 @@ ABI = {
     'pasta_contextual_loss': (ctypes.c_int, [_c_ptr] * 6 + [_c_i64] + [ctypes.c_int] * 3 + [_c_f32, _c_ptr]),
     'pasta_contextual_loss_backward': (ctypes.c_int, [_c_ptr] * 8 + [ctypes.c_int] * 3 + [_c_f32, _c_ptr]),
     'pasta_part_geometry': (ctypes.c_int, [_c_ptr] + [ctypes.c_int] * 6 + [_c_ptr] * 8),
+    'pasta_fit_people_u8': (ctypes.c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr] + [ctypes.c_int] * 3 + [_c_ptr]),
 }
 
 # Entries added to the current ABI after its first release (purely additive, so the version did not move): a library built before
@@ -279,14 +280,15 @@ ABI = {
 # entries of the input-activation mask (pasta_act_mask: csrc/conv_igemm.hip, csrc/upfirdn2d.hip; pasta_bias_sum_db: csrc/bias_act.hip),
 # pasta_tryon_mirror_u8, pasta_tryon_jitter_u8 and pasta_erase_strokes_u8 (csrc/tryon_inputs.hip), the three entries of the SSIM loss
 # (csrc/ssim_loss.hip), pasta_swap_assemble (csrc/train_grid.hip), the three entries of the region L1 loss (csrc/region_l1.hip) and the
-# three of the contextual loss (csrc/contextual_loss.hip), and pasta_part_geometry (csrc/part_geometry.hip).
+# three of the contextual loss (csrc/contextual_loss.hip), pasta_part_geometry (csrc/part_geometry.hip) and pasta_fit_people_u8
+# (csrc/fit_people.hip).
 LATE_ENTRIES = frozenset(['pasta_png_filter', 'pasta_png_code_lengths', 'pasta_png_segment_tables', 'pasta_png_encode',
                           'pasta_images_keep_to_u8', 'pasta_photo_paste_mask_u8', 'pasta_conv2d_masked', 'pasta_conv2d_mask_available', 'pasta_upfirdn2d_masked',
                           'pasta_upfirdn2d_mask_available', 'pasta_bias_sum_db', 'pasta_tryon_mirror_u8',
                           'pasta_tryon_jitter_u8', 'pasta_ssim_loss_workspace', 'pasta_ssim_loss', 'pasta_ssim_loss_backward',
                           'pasta_erase_strokes_u8', 'pasta_swap_assemble', 'pasta_region_l1_loss_workspace', 'pasta_region_l1_loss',
                           'pasta_region_l1_loss_backward', 'pasta_contextual_loss_workspace', 'pasta_contextual_loss',
-                          'pasta_contextual_loss_backward', 'pasta_part_geometry'])
+                          'pasta_contextual_loss_backward', 'pasta_part_geometry', 'pasta_fit_people_u8'])
 
 def _missing_entry(lib_path, name):
     def missing(*args, **kwargs):

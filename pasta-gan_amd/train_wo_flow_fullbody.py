@@ -20,7 +20,9 @@ reversed, left and right labels and joints exchanged, per batch on the GPU befor
 
 ``--jitter-people=scale=0.1,rotate=5,shift=0.03,colour=0.2`` trains on every person under a random similarity map (scale, rotation,
 shift) and colour change, drawn anew at every visit from the run's seed and the sample's position in the sampler's stream, and
-resampled per batch on the GPU before the preparation, after the mirroring.  The sample grid and the metrics see the
+resampled per batch on the GPU before the preparation, after the mirroring.  ``--fit-people pad|crop`` with
+``--fit-filter bilinear|box`` trains on a tree whose photographs have sizes of their own: every batch is fitted to the canvas on the
+GPU before the mirroring; recorded with the run, so the sample grid, the metrics and --continue see the same people.  The sample grid and the metrics see the
 people as photographed.
 
 ``--ssim_weight=5`` adds ``5 * (1 - mean SSIM)`` of each of the generator's two images against the photograph to its loss: the
@@ -90,7 +92,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
                                fp32=None, nhwc=None, allow_tf32=None, nobench=None, workers=None, l1_weight=0, vgg_weight=0, pl_weight=0,
                                mask_weight=0, contextual_weight=0, use_noise_const_branch=False, save_state=None, storage=None,
                                mirror_people=None, jitter_people=None, ssim_weight=None, erase_masks=None, erase_strokes=None,
-                               swap_weight=None, swap_region=None, swap_cx_weight=None, part_geometry=None):
+                               swap_weight=None, swap_region=None, swap_cx_weight=None, part_geometry=None, fit_people=None, fit_filter=None):
     """The command line's options -> (run description, keyword arguments of ``training_loop``)."""
     args = dnnlib.EasyDict()
 
@@ -125,6 +127,13 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
     except ValueError as err:
         raise UserError(str(err))
     args.training_set_kwargs.update(erase_kwargs)
+    # --fit-people, --fit-filter (own options): photographs of any size, fitted to the canvas per batch on the GPU before the
+    # mirroring.  Arguments of the data set, recorded only when given: the scores, the sample grid and --continue inherit them
+    try:
+        fit_kwargs = dnnlib.EasyDict(tryon_cli.fit_kwargs(fit_people, fit_filter))
+    except ValueError as err:
+        raise UserError(str(err))
+    args.training_set_kwargs.update(fit_kwargs)
     try:
         training_set = dnnlib.util.construct_class_by_name(**args.training_set_kwargs)
         args.training_set_kwargs.resolution = training_set.resolution
@@ -140,7 +149,7 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         if not metrics:
             raise UserError('--metrics_data needs --metrics')
         args.metric_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(metrics_data), path=metrics_data, use_labels=False,
-                                                 max_size=None, xflip=False, **erase_kwargs)
+                                                 max_size=None, xflip=False, **erase_kwargs, **fit_kwargs)
         try:
             metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
             if metric_set.resolution != args.training_set_kwargs.resolution:
@@ -173,6 +182,8 @@ def setup_training_loop_kwargs(gpus=None, snap=None, metrics=None, metrics_data=
         args.people_jitter = dnnlib.EasyDict(parse_jitter_people(jitter_people))
     if erase_kwargs:
         desc += '-erase' + erase_kwargs['erase_masks']
+    if fit_kwargs:
+        desc += '-fit' + fit_kwargs['fit']
 
     # Base config: cfg, gamma, kimg, batch (:161-246)
     cfg = 'auto' if cfg is None else cfg
@@ -368,7 +379,8 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         if name in CONTINUE_MAY_CHANGE or (recorded is not None and value == recorded):
             continue
         option = '--' + {'allow_tf32': 'allow-tf32', 'mirror_people': 'mirror-people', 'jitter_people': 'jitter-people', 'erase_masks': 'erase-masks',
-                         'erase_strokes': 'erase-strokes', 'swap_region': 'swap-region', 'part_geometry': 'part-geometry'}.get(name, name)
+                         'erase_strokes': 'erase-strokes', 'swap_region': 'swap-region', 'part_geometry': 'part-geometry',
+                         'fit_people': 'fit-people', 'fit_filter': 'fit-filter'}.get(name, name)
         raise UserError(f'{option} cannot be given with --continue: a continued run keeps its recorded value' +
                         (f' ({recorded})' if recorded is not None else ''))
 
@@ -413,7 +425,7 @@ def setup_continue_kwargs(continue_path, data=None, **given):
         metrics_data = given['metrics_data']
         args.metric_set_kwargs = dnnlib.EasyDict(class_name=training_set_class(metrics_data), path=metrics_data, use_labels=False,
                                                  max_size=None, xflip=False,
-                                                 **{k: recorded[k] for k in ('erase_masks', 'erase_strokes') if k in recorded})
+                                                 **{k: recorded[k] for k in ('erase_masks', 'erase_strokes', 'fit', 'fit_filter') if k in recorded})
         try:
             metric_set = dnnlib.util.construct_class_by_name(**args.metric_set_kwargs)
             if metric_set.resolution != recorded.resolution:
@@ -491,6 +503,7 @@ class CommaSeparatedList(click.ParamType):
 @click.option('--jitter-people', help='Train on people jittered on the GPU: comma-separated scale=0..0.5, rotate=0..45 (degrees), '
               'shift=0..0.25 (of the canvas side), colour=0..0.5 [default: none]', metavar='SPEC')
 @tryon_cli.erase_options('files')
+@tryon_cli.fit_options()
 # Base config.
 @click.option('--cfg', help='Base config [default: auto]', type=click.Choice(list(CFG_SPECS) + list(UNSUPPORTED_CFGS)))
 @click.option('--gamma', help='Override R1 gamma', type=float)
@@ -575,6 +588,8 @@ def main(ctx, outdir, dry_run, continue_path, **config_kwargs):
               (f', contextual weight {args.cfg.loss_kwargs.swap_cx_weight:g}' if args.cfg.loss_kwargs.get('swap_cx_weight') else ''))
     if args.get('part_geometry'):
         print(f'Part geometry:      {args.part_geometry}')
+    if args.training_set_kwargs.get('fit'):
+        print(f'Fitted people:      {args.training_set_kwargs.fit} ({args.training_set_kwargs.fit_filter})')
     print(f'Image resolution:   {args.training_set_kwargs.resolution}')
     print()
     if dry_run:

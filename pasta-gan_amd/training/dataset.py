@@ -11,7 +11,10 @@ The test pairs (``UvitonDatasetV19_test``, dataset.py:997-1525) follow the same 
 ``UvitonOutfits_512_test`` is this project's own: outfits (person, upper garment's donor, lower garment's donor) from a list
 file, ``collate_outfits`` and ``training.tryon_regions.TryOnOutfitBatchBuilder``.
 ``UvitonDatasetFull_512`` is this project's own: the training layout at 512 x 320, which the reference does not ship, prepared
-by ``training.tryon_regions.FullBodyRegionBatchBuilder``."""
+by ``training.tryon_regions.FullBodyRegionBatchBuilder``.
+Every class takes ``fit='pad' | 'crop'`` (this project's own): the files may then have any size, samples keep it, the collate
+functions pack them instead of stacking (``pack_people``), and the builders fit them to the class's ``canvas`` on the GPU
+(``training.tryon_batch.fit_batch``; include/pasta_hip.h has the rule)."""
 
 import json
 import os
@@ -99,6 +102,37 @@ def read_keypoints(path):
     return np.array(data['people'][0]['pose_keypoints_2d'], dtype=np.float64).reshape(-1, 3)
 
 
+def fit_options(dataset, fit, fit_filter):
+    """``fit`` (None, 'pad' or 'crop') and ``fit_filter`` ('bilinear' or 'box') of a data set, checked and kept as its attributes
+    (this project's own: people of any size, fitted to the class's ``canvas`` per batch on the GPU by
+    ``training.tryon_batch.fit_batch``; include/pasta_hip.h has the rule).  A ValueError names an unknown value."""
+    from training.tryon_batch import FIT_MODES, fit_check
+    fit_check(FIT_MODES[0] if fit is None else fit, fit_filter)
+    dataset.fit, dataset.fit_filter = fit, fit_filter
+
+
+def fit_sample(dataset, fname, shape):
+    """The ``fit`` entry of a raw sample of a data set opened with ``fit``, after the rule's limits are checked for the file's
+    ``shape``: an IOError names the file."""
+    from training.tryon_batch import fit_limits, fit_rectangle
+    H, W = dataset.canvas
+    Hc, Wc, _, _ = fit_rectangle(shape[0], shape[1], H, W, dataset.fit)
+    wrong = fit_limits(shape[0], shape[1], Hc, Wc)
+    if wrong is not None:
+        raise IOError('%s: cannot be fitted (%s) to %d x %d: %s' % (fname, dataset.fit, H, W, wrong))
+    return dict(mode=dataset.fit, filter=dataset.fit_filter, canvas=(int(H), int(W)))
+
+
+def pack_people(people):
+    """[(image uint8 [h, w, 3], parsing uint8 [h, w]), ...] of any sizes -> (the photographs' bytes in one flat uint8 tensor, the
+    label maps' in another, ``image_hw`` int32 [N, 2], ``image_offsets`` int64 [N]: each item's first PIXEL in both)."""
+    hw = np.array([p[1].shape for p in people], np.int64).reshape(-1, 2)
+    offsets = np.concatenate([[0], np.cumsum(hw[:, 0] * hw[:, 1])[:-1]]).astype(np.int64)
+    image = np.concatenate([np.ascontiguousarray(p[0]).reshape(-1) for p in people])
+    parsing = np.concatenate([np.ascontiguousarray(p[1]).reshape(-1) for p in people])
+    return torch.from_numpy(image), torch.from_numpy(parsing), torch.from_numpy(hw.astype(np.int32)), torch.from_numpy(offsets)
+
+
 ERASE_MASKS = ('files', 'none', 'strokes')          # UvitonDatasetFull(erase_masks=): where a training item's erase mask comes from
 
 
@@ -118,16 +152,25 @@ class UvitonDatasetFull(Dataset):
     ``train_random_mask_acgpn``, so a tree without it opens, and every ``erase_mask`` is a 1 x 1 zero, which erases nothing.  With
     ``'strokes'`` whoever numbers the batches attaches ``erase_strokes`` (the checked specification of
     ``training.tryon_batch.strokes_spec``, an attribute here as ``erase_masks`` is) and the builder draws a mask per item on the
-    GPU (``training.tryon_batch.strokes_batch``; include/pasta_hip.h has the rule)."""
+    GPU (``training.tryon_batch.strokes_batch``; include/pasta_hip.h has the rule).
+
+    ``fit`` = 'pad' or 'crop' with ``fit_filter`` = 'bilinear' or 'box' (this project's own): the photographs may have any size.
+    The set is sized by the class's ``canvas`` instead of by file 0, ``content_width`` is the canvas width, ``resolution`` must be
+    the canvas height, and a sample keeps its files' own size and carries ``fit`` (mode, filter, canvas): ``collate`` packs such
+    samples and the builder fits them on the GPU (``training.tryon_batch.fit_batch``; include/pasta_hip.h has the rule).  A file
+    outside the rule's limits raises IOError at load."""
 
     _sub_datasets = SUB_DATASETS
+    canvas = (256, 192)
     _vis_sources = (('Zalando_256_192', 'image'), ('Deepfashion_256_192', os.path.join('image', 'train')))     # :461-472, in this order
 
     @staticmethod
     def _label_name(dataset, name):
         return name.replace('.jpg', '.png') if dataset == 'MPV_256_192' else name.replace('.jpg', '_label.png')
 
-    def __init__(self, path, resolution=None, mirror_people=False, erase_masks='files', erase_strokes=None, **super_kwargs):
+    def __init__(self, path, resolution=None, mirror_people=False, erase_masks='files', erase_strokes=None, fit=None, fit_filter='bilinear',
+                 **super_kwargs):
+        fit_options(self, fit, fit_filter)
         if erase_masks not in ERASE_MASKS:
             raise ValueError('erase_masks=%r is none of %s' % (erase_masks, ', '.join(ERASE_MASKS)))
         if erase_strokes is not None and erase_masks != 'strokes':
@@ -170,7 +213,7 @@ class UvitonDatasetFull(Dataset):
         PIL.Image.init()
         if len(self._image_fnames) == 0:
             raise IOError('No image files found in the specified path')
-        h, w, c = self._load_image(0).shape
+        h, w, c = self.canvas + (3,) if self.fit is not None else self._load_image(0).shape
         self.content_width = int(w)                            # the photographs' own width, which the batch builder pads to the square
         raw_shape = [len(self._image_fnames), c, h, h]         # the padded square, as the reference's image_shape
         if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
@@ -186,6 +229,11 @@ class UvitonDatasetFull(Dataset):
             raise IOError('%s: expected an RGB image at least as tall as wide, got %s' % (self._image_fnames[raw_idx], image.shape))
         return image
 
+    def _fit_sample(self, raw_idx, sample):
+        if self.fit is not None:
+            sample['fit'] = fit_sample(self, self._image_fnames[raw_idx], sample['image'].shape)
+        return sample
+
     def load_raw(self, raw_idx):
         image = self._load_image(raw_idx)
         parsing = read_channel0(os.path.join(self._path, self._parsing_fnames[raw_idx]))
@@ -196,7 +244,7 @@ class UvitonDatasetFull(Dataset):
             erase = read_channel0(self._random_mask_acgpn_fnames[raw_idx % self._mask_acgpn_numbers])
         else:
             erase = np.zeros([1, 1], np.uint8)
-        return dict(image=image, parsing=parsing, keypoints=keypoints, erase_mask=erase, raw_idx=int(raw_idx))
+        return self._fit_sample(raw_idx, dict(image=image, parsing=parsing, keypoints=keypoints, erase_mask=erase, raw_idx=int(raw_idx)))
 
     def __getitem__(self, idx):
         sample = self.load_raw(self._raw_idx[idx])
@@ -213,6 +261,7 @@ class UvitonDatasetFull_512(UvitonDatasetFull):
     ``Deepfashion_512_320/image/train``.  Raw samples as ``UvitonDatasetFull``'s, so ``collate`` serves both."""
 
     _sub_datasets = SUB_DATASETS_512
+    canvas = (512, 320)
     _vis_sources = (('Zalando_512_320', 'image'), ('Deepfashion_512_320', os.path.join('image', 'train')))
 
     @staticmethod
@@ -231,8 +280,10 @@ def training_set_class(path):
 def collate(samples):
     """A list of raw samples -> one batch: ``image`` uint8 [N, H, W, 3], ``parsing`` uint8 [N, H, W], ``keypoints`` float64
     [N, 18, 3], ``erase_masks`` uint8 [N, h_max, w_max] (each mask in the top-left corner) with ``erase_hw`` int32 [N, 2]
-    (its own size), ``raw_idx`` int64 [N]; ``xflip`` uint8 [N] when the samples carry it (``mirror_people``).  Use as the
-    DataLoader's ``collate_fn``."""
+    (its own size), ``raw_idx`` int64 [N]; ``xflip`` uint8 [N] when the samples carry it (``mirror_people``).  Samples that carry
+    ``fit`` (people of their own sizes) are PACKED instead of stacked (``pack_people``): ``image`` and ``parsing`` are flat, with
+    ``image_hw`` int32 [N, 2] and ``image_offsets`` int64 [N] next to them and the samples' ``fit``.  Use as the DataLoader's
+    ``collate_fn``."""
     n = len(samples)
     h_max = max(s['erase_mask'].shape[0] for s in samples)
     w_max = max(s['erase_mask'].shape[1] for s in samples)
@@ -242,9 +293,13 @@ def collate(samples):
         h, w = s['erase_mask'].shape
         erase[i, :h, :w] = s['erase_mask']
         erase_hw[i] = h, w
-    batch = dict(image=torch.from_numpy(np.stack([s['image'] for s in samples])),
-                 parsing=torch.from_numpy(np.stack([s['parsing'] for s in samples])),
-                 keypoints=torch.from_numpy(np.stack([s['keypoints'] for s in samples])),
+    if 'fit' in samples[0]:
+        image, parsing, image_hw, image_offsets = pack_people([(s['image'], s['parsing']) for s in samples])
+        people = dict(image=image, parsing=parsing, image_hw=image_hw, image_offsets=image_offsets, fit=dict(samples[0]['fit']))
+    else:
+        people = dict(image=torch.from_numpy(np.stack([s['image'] for s in samples])),
+                      parsing=torch.from_numpy(np.stack([s['parsing'] for s in samples])))
+    batch = dict(people, keypoints=torch.from_numpy(np.stack([s['keypoints'] for s in samples])),
                  erase_masks=torch.from_numpy(erase), erase_hw=torch.from_numpy(erase_hw),
                  raw_idx=torch.as_tensor([s['raw_idx'] for s in samples], dtype=torch.int64))
     if 'xflip' in samples[0]:
@@ -252,6 +307,14 @@ def collate(samples):
     return batch
 
 #----------------------------------------------------------------------------
+
+class _SubDatasetCanvas:
+    """The ``canvas`` class attribute of the test sets, which differ in ``_sub_datasets`` and ``_label_name`` only: the canvas of the
+    folders a class reads."""
+
+    def __get__(self, obj, owner):
+        return (512, 320) if owner._sub_datasets is SUB_DATASETS_512 else (256, 192)
+
 
 class UvitonDatasetV19_test(Dataset):
     """dataset.py:997-1153 -- the unpaired test pairs of ``UPT_subset1_256_192`` and ``UPT_subset2_256_192``: each line
@@ -262,6 +325,8 @@ class UvitonDatasetV19_test(Dataset):
     relative paths, ``<sub-dataset>/image/<file>``)."""
 
     _sub_datasets = TEST_SUB_DATASETS
+    canvas = _SubDatasetCanvas()                # (256, 192), or (512, 320) in the classes that read the ``*_512_320`` folders
+    fit, fit_filter = None, 'bilinear'          # every test set takes them as UvitonDatasetFull does (``fit_options``)
 
     @staticmethod
     def _label_name(dataset, name):
@@ -279,13 +344,14 @@ class UvitonDatasetV19_test(Dataset):
         PIL.Image.init()
         if count == 0:
             raise IOError(nothing)
-        h, w, c = self._load_person(*first_person)[0].shape
+        h, w, c = self.canvas + (3,) if self.fit is not None else self._load_person(*first_person)[0].shape
         raw_shape = [count, c, h, h]                           # the padded square, as the reference's image_shape
         if resolution is not None and (raw_shape[2] != resolution or raw_shape[3] != resolution):
             raise IOError('Image files do not match the specified resolution')
         Dataset.__init__(self, name=os.path.splitext(os.path.basename(self._path))[0], raw_shape=raw_shape, **super_kwargs)
 
-    def __init__(self, path, resolution=None, **super_kwargs):
+    def __init__(self, path, resolution=None, fit=None, fit_filter='bilinear', **super_kwargs):
+        fit_options(self, fit, fit_filter)
         self._open_tree(path)
         self._image_fnames, self._kpt_fnames, self._parsing_fnames = [], [], []
         self._clothes_image_fnames, self._clothes_kpt_fnames, self._clothes_parsing_fnames = [], [], []
@@ -310,17 +376,24 @@ class UvitonDatasetV19_test(Dataset):
         parsing = read_channel0(os.path.join(self._path, parsing_fname))
         if parsing.shape != image.shape[:2]:
             raise IOError('%s: label map %s does not match the image %s' % (parsing_fname, parsing.shape, image.shape[:2]))
+        if self.fit is not None:
+            fit_sample(self, image_fname, image.shape)              # the limits, at load
         return image, parsing, read_keypoints(os.path.join(self._path, kpt_fname))
+
+    def _fit_entry(self, sample):
+        if self.fit is not None:
+            sample['fit'] = dict(mode=self.fit, filter=self.fit_filter, canvas=tuple(int(v) for v in self.canvas))
+        return sample
 
     def load_raw(self, raw_idx):
         image, parsing, keypoints = self._load_person(self._image_fnames[raw_idx], self._parsing_fnames[raw_idx], self._kpt_fnames[raw_idx])
         c_image, c_parsing, c_keypoints = self._load_person(self._clothes_image_fnames[raw_idx], self._clothes_parsing_fnames[raw_idx],
                                                             self._clothes_kpt_fnames[raw_idx])
-        if c_image.shape != image.shape:
+        if self.fit is None and c_image.shape != image.shape:
             raise IOError('%s: the clothes image %s does not match the person %s' % (self._clothes_image_fnames[raw_idx], c_image.shape, image.shape))
-        return dict(image=image, parsing=parsing, keypoints=keypoints, clothes_image=c_image, clothes_parsing=c_parsing,
-                    clothes_keypoints=c_keypoints, person_name=self._image_fnames[raw_idx], clothes_name=self._clothes_image_fnames[raw_idx],
-                    raw_idx=int(raw_idx))
+        return self._fit_entry(dict(image=image, parsing=parsing, keypoints=keypoints, clothes_image=c_image, clothes_parsing=c_parsing,
+                                    clothes_keypoints=c_keypoints, person_name=self._image_fnames[raw_idx],
+                                    clothes_name=self._clothes_image_fnames[raw_idx], raw_idx=int(raw_idx)))
 
     def __getitem__(self, idx):
         return self.load_raw(self._raw_idx[idx])
@@ -386,7 +459,8 @@ class UvitonOutfits_512_test(UvitonDatasetV19_test):
     _sub_datasets = SUB_DATASETS_512
     _label_name = staticmethod(UvitonDatasetFull_512_test._label_name)
 
-    def __init__(self, path, outfits_file, resolution=None, **super_kwargs):
+    def __init__(self, path, outfits_file, resolution=None, fit=None, fit_filter='bilinear', **super_kwargs):
+        fit_options(self, fit, fit_filter)
         self._open_tree(path)
         self._outfits = []              # per line: the (image, parsing, keypoints) file names of person, upper, lower
         with open(outfits_file, 'r') as f:
@@ -421,10 +495,10 @@ class UvitonOutfits_512_test(UvitonDatasetV19_test):
             if files not in decoded:
                 decoded[files] = self._load_person(*files)
             image, parsing, keypoints = decoded[files]
-            if image.shape != decoded[outfit[0]][0].shape:
+            if self.fit is None and image.shape != decoded[outfit[0]][0].shape:
                 raise IOError('%s: the image %s does not match the person %s' % (files[0], image.shape, decoded[outfit[0]][0].shape))
             out.update({prefix + 'image': image, prefix + 'parsing': parsing, prefix + 'keypoints': keypoints, role + '_name': files[0]})
-        return out
+        return self._fit_entry(out)
 
 
 class UvitonOutfits_256_test(UvitonOutfits_512_test):
@@ -444,7 +518,9 @@ def collate_outfits(samples):
     appearance (samples in order; person, upper, lower within a sample): ``people_image`` uint8 [M, H, W, 3], ``people_parsing``
     uint8 [M, H, W], ``people_keypoints`` float64 [M, 18, 3], ``people_name`` list of str; ``person_idx`` / ``upper_idx`` /
     ``lower_idx`` int64 [N] into that stack; ``person_name`` / ``upper_name`` / ``lower_name`` lists of str, ``raw_idx`` int64
-    [N].  A person who keeps a garment, or a donor several outfits of the batch use, is uploaded and solved for once.  Use as the
+    [N].  A person who keeps a garment, or a donor several outfits of the batch use, is uploaded and solved for once.  Samples that
+    carry ``fit`` (people of their own sizes) are PACKED instead of stacked, as ``collate`` packs them: ``people_image`` and
+    ``people_parsing`` flat, with ``people_image_hw`` int32 [M, 2], ``people_image_offsets`` int64 [M] and ``fit``.  Use as the
     DataLoader's ``collate_fn``."""
     roles = (('person', ''), ('upper', 'upper_'), ('lower', 'lower_'))
     slot, people = {}, []
@@ -456,7 +532,12 @@ def collate_outfits(samples):
                 slot[name] = len(people)
                 people.append((s[prefix + 'image'], s[prefix + 'parsing'], s[prefix + 'keypoints']))
             index[role].append(slot[name])
-    out = {key: torch.from_numpy(np.stack([p[k] for p in people])) for k, key in enumerate(('people_image', 'people_parsing', 'people_keypoints'))}
+    if 'fit' in samples[0]:
+        image, parsing, image_hw, image_offsets = pack_people([p[:2] for p in people])
+        out = dict(people_image=image, people_parsing=parsing, people_image_hw=image_hw, people_image_offsets=image_offsets,
+                   people_keypoints=torch.from_numpy(np.stack([p[2] for p in people])), fit=dict(samples[0]['fit']))
+    else:
+        out = {key: torch.from_numpy(np.stack([p[k] for p in people])) for k, key in enumerate(('people_image', 'people_parsing', 'people_keypoints'))}
     out['people_name'] = list(slot)
     for role, _ in roles:
         out[role + '_idx'] = torch.as_tensor(index[role], dtype=torch.int64)
@@ -470,7 +551,7 @@ def pair_as_outfit(sample, change_region):
     dresses it, lower body (P, P, D), full body (P, D, D).  ``clothes_name`` stays."""
     if change_region not in CHANGE_REGIONS:
         raise ValueError('change region %s is invalid.' % change_region)
-    out = {k: sample[k] for k in ('image', 'parsing', 'keypoints', 'person_name', 'clothes_name', 'raw_idx')}
+    out = {k: sample[k] for k in ('image', 'parsing', 'keypoints', 'person_name', 'clothes_name', 'raw_idx') + (('fit',) if 'fit' in sample else ())}
     for role, prefix, donor in (('upper', 'upper_', change_region != 'lowerbody'), ('lower', 'lower_', change_region != 'upperbody')):
         src, name = ('clothes_', 'clothes_name') if donor else ('', 'person_name')
         out.update({prefix + k: sample[src + k] for k in ('image', 'parsing', 'keypoints')})

@@ -46,6 +46,8 @@ class SnapshotGrid:
         if len(vis) < gnum:
             raise IOError('the snapshot grid needs %d people listed in train_img_vis, the data set has %d' % (gnum, len(vis)))
         raw = collate([training_set[i] for i in vis[:gnum]])       # grid_indices = training_set.vis_index (:113-116)
+        from training.tryon_batch import fitted
+        raw = fitted(raw, device)                                   # a set opened with ``fit``: the people on their canvas
         if getattr(training_set, 'erase_masks', 'files') == 'strokes':      # drawn by the person: every snapshot shows the same holes
             from training.tryon_batch import attach_strokes
             attach_strokes(raw, training_set.erase_strokes, 0, raw['raw_idx'].numpy())

@@ -8,7 +8,11 @@ do per sample on the host, as a few launches per batch:
     patch_pipeline.normalize_batch   the ten body-part warps    (csrc/patches.hip)
     pasta_tryon_assemble     erase mask and every float conversion, into the nine tensors of SyntheticFullBodyBatch.KEYS
 
-and, before them, for a batch of a data set opened with ``mirror_people`` that holds a flagged item (``mirror_batch``):
+and, before all of them, for a packed batch of a data set opened with ``fit`` (people of their own sizes; ``fit_batch``):
+
+    pasta_fit_people_u8      photograph and label map of every person resampled and placed on the canvas
+
+and then, for a batch of a data set opened with ``mirror_people`` that holds a flagged item (``mirror_batch``):
 
     pasta_tryon_mirror_u8    photograph, label map (left and right exchanged) and erase mask as a mirror shows them
 
@@ -24,13 +28,14 @@ The host keeps the file decoding (training/dataset.py), the key-point geometry b
 (patch_pipeline.part_maps; a builder with geometry='gpu': one launch instead).
 
 The steps every builder takes are stated here once, for this one and for training/tryon_pairs.py and training/tryon_regions.py:
-``upload_person`` (upload and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
+``upload_person`` (upload, ``fit_batch`` for a packed batch, and checks), ``upload_images`` (a pair batch's tensors), ``upload_erase`` (the training sets' erase
 masks), ``mirror_batch`` (the training sets' mirrored people), ``jitter_batch`` (their jittered people), ``strokes_batch`` (their drawn erase masks),
 ``device_tables`` (stick and palm tables), ``allocator``, ``output_tensors`` (the fp32 tensors of a KEYS list with their pointer array) and
 ``shift_keypoints``.
 ``builder_for`` picks the training builder of a data set: this one, or training/tryon_regions.py's at 512 x 320."""
 
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -62,6 +67,11 @@ STROKES_RANGES = dict(strokes=(int, 1, 8, 6), vertices=(int, 1, 8, 6), length=(f
                       turn=(float, 0.0, 180.0, 60.0))
 STROKES_UNIFORMS = 169
 STROKES_SEGMENTS = 64
+# People fitted to the canvas (this project's own rule, include/pasta_hip.h: pasta_fit_people_u8): the modes, the filters of the
+# photograph (the label map always takes the box taps), and the words of an item's record in the plan
+FIT_MODES = ('pad', 'crop')
+FIT_FILTERS = ('bilinear', 'box')
+FIT_RECORD = 16
 
 
 def stick_tables(keypoints):
@@ -111,9 +121,193 @@ def palm_quads(keypoints, left_padding):
     return np.ascontiguousarray(np.clip(np.nan_to_num(quads), -QUAD_LIMIT, QUAD_LIMIT)), present
 
 
+def fit_check(mode, filter):
+    """(mode, filter) of a fit, checked: a ValueError names an unknown one."""
+    if mode not in FIT_MODES:
+        raise ValueError('fit=%r is none of %s' % (mode, ', '.join(FIT_MODES)))
+    if filter not in FIT_FILTERS:
+        raise ValueError('fit_filter=%r is none of %s' % (filter, ', '.join(FIT_FILTERS)))
+    return mode, filter
+
+
+def _rhu(a, b):
+    return (2 * a + b) // (2 * b)
+
+
+def fit_rectangle(h, w, H, W, mode):
+    """The fitted rectangle (Hc, Wc, oy, ox) of an ``h x w`` item on the ``H x W`` canvas (include/pasta_hip.h: ``rectangle``), in
+    integers.  No limit is checked here (``fit_limits``)."""
+    h, w, H, W = int(h), int(w), int(H), int(W)
+    tall = h * W >= w * H
+    if mode not in FIT_MODES:
+        raise ValueError('fit=%r is none of %s' % (mode, ', '.join(FIT_MODES)))
+    if tall == (mode == 'pad'):
+        Hc, Wc = H, _rhu(w * H, h)
+    else:
+        Hc, Wc = _rhu(h * W, w), W
+    if mode == 'pad':
+        return Hc, Wc, (H - Hc) // 2, (W - Wc) // 2
+    return Hc, Wc, -((Hc - H) // 2), -((Wc - W) // 2)
+
+
+def fit_limits(h, w, Hc, Wc):
+    """None, or what is wrong with resampling ``h x w`` to ``Hc x Wc``: more than 8 source pixels per fitted one, or more than 4
+    fitted ones per source pixel, along either axis (the tap footprints the kernels are built for)."""
+    if Hc < 1 or Wc < 1:
+        return 'fits to an empty %d x %d' % (Hc, Wc)
+    if h > 8 * Hc or w > 8 * Wc:
+        return '%d x %d is more than 8 times the fitted %d x %d' % (h, w, Hc, Wc)
+    if Hc > 4 * h or Wc > 4 * w:
+        return 'the fitted %d x %d is more than 4 times %d x %d' % (Hc, Wc, h, w)
+    return None
+
+
+@functools.lru_cache(maxsize=256)
+def fit_taps(n_in, n_out, filter):
+    """The fixed-point taps of one axis from length ``n_in`` to ``n_out`` (include/pasta_hip.h: ``taps``; PIL's 8-bit rule in
+    float64): (xmin int32 [n_out], cnt int32 [n_out], k int32 [n_out, ksize]), k zero past cnt.  Equal lengths: the single tap
+    2^22, which returns the source byte.  Cached per (n_in, n_out, filter); the arrays are read-only."""
+    n_in, n_out = int(n_in), int(n_out)
+    assert n_in >= 1 and n_out >= 1 and filter in FIT_FILTERS
+    if n_in == n_out:
+        out = np.arange(n_out, dtype=np.int32), np.ones([n_out], np.int32), np.full([n_out, 1], 1 << 22, np.int32)
+    else:
+        scale = n_in / n_out
+        fs = max(scale, 1.0)
+        support = (0.5 if filter == 'box' else 1.0) * fs
+        ss = 1.0 / fs
+        ksize = int(math.ceil(support)) * 2 + 1
+        center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+        xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)             # astype truncates, as C's (int)
+        cnt = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+        x = np.arange(ksize, dtype=np.int64)
+        t = (((x[None, :] + xmin[:, None]).astype(np.float64) - center[:, None]) + 0.5) * ss
+        if filter == 'box':
+            wgt = np.where((t > -0.5) & (t <= 0.5), 1.0, 0.0)
+        else:
+            wgt = np.where(np.abs(t) < 1.0, 1.0 - np.abs(t), 0.0)
+        wgt = np.where(x[None, :] < cnt[:, None], wgt, 0.0)
+        ww = np.zeros([n_out], np.float64)
+        for j in range(ksize):                                                       # summed in tap order
+            ww = ww + wgt[:, j]
+        wgt = np.where(ww[:, None] != 0.0, wgt / np.where(ww == 0.0, 1.0, ww)[:, None], wgt)
+        k = (0.5 + wgt * float(1 << 22)).astype(np.int64)
+        out = xmin.astype(np.int32), cnt.astype(np.int32), np.ascontiguousarray(k.astype(np.int32))
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def fit_keypoints(keypoints, hw, rectangles):
+    """[N, 18, 3] key points of items of sizes ``hw`` [N, 2] -> a float64 copy on the canvas (include/pasta_hip.h: ``joints``): a
+    joint with confidence >= 0.1 moves with the content, one below keeps its bits, an item already at its fitted size and offset
+    0 keeps all of them."""
+    kp = np.asarray(keypoints, np.float64).copy()
+    assert kp.ndim == 3 and kp.shape[1:] == (18, 3) and len(hw) == len(rectangles) == kp.shape[0]
+    for i, ((h, w), (Hc, Wc, oy, ox)) in enumerate(zip(np.asarray(hw).tolist(), rectangles)):
+        if (h, w, 0, 0) == (Hc, Wc, oy, ox):
+            continue
+        sx, sy = Wc / w, Hc / h
+        seen = kp[i, :, 2] >= 0.1
+        x, y = kp[i, :, 0].copy(), kp[i, :, 1].copy()
+        with np.errstate(all='ignore'):
+            kp[i, :, 0] = np.where(seen, x * sx + ((0.5 * sx - 0.5) + ox), x)
+            kp[i, :, 1] = np.where(seen, y * sy + ((0.5 * sy - 0.5) + oy), y)
+    return kp
+
+
+def fit_rectangles(hw, canvas, mode):
+    """[(Hc, Wc, oy, ox)] of items of sizes ``hw`` [N, 2] on ``canvas`` (``fit_rectangle``), the rule's limits asserted: the data
+    sets refuse such a file by name at load."""
+    out = []
+    for h, w in np.asarray(hw, np.int64).reshape(-1, 2).tolist():
+        rect = fit_rectangle(h, w, canvas[0], canvas[1], mode)
+        wrong = fit_limits(h, w, rect[0], rect[1])
+        assert h >= 1 and w >= 1 and wrong is None, wrong
+        out.append(rect)
+    return out
+
+
+def fit_plan(hw, offsets, rectangles, filter):
+    """The one int32 array ``pasta_fit_people_u8`` reads for a packed batch (include/pasta_hip.h: ``plan``): a record of FIT_RECORD
+    words per item, then every distinct tap table the batch uses, once.  ``rectangles``: (Hc, Wc, oy, ox) per item."""
+    assert filter in FIT_FILTERS
+    hw = np.asarray(hw, np.int64).reshape(-1, 2)
+    offsets = np.asarray(offsets, np.int64).reshape(-1)
+    n = len(hw)
+    assert len(offsets) == len(rectangles) == n and (offsets >= 0).all()
+    records = np.zeros([n, FIT_RECORD], np.int32)
+    tables, where, words = [], {}, n * FIT_RECORD
+
+    def table(n_in, n_out, f):
+        nonlocal words
+        key = (n_in, n_out, f if n_in != n_out else 'box')
+        if key not in where:
+            xmin, cnt, k = fit_taps(*key)
+            flat = np.concatenate([np.array([n_out, k.shape[1]], np.int32),
+                                   np.concatenate([xmin[:, None], cnt[:, None], k], axis=1).reshape(-1)])
+            where[key] = words
+            tables.append(flat)
+            words += len(flat)
+        return where[key]
+
+    for i, ((h, w), (Hc, Wc, oy, ox)) in enumerate(zip(hw.tolist(), rectangles)):
+        off = int(offsets[i])
+        records[i, :12] = (h, w, Hc, Wc, oy, ox, table(w, Wc, filter), table(h, Hc, filter), table(w, Wc, 'box'), table(h, Hc, 'box'),
+                           off & 0x7fffffff, off >> 31)
+    return np.concatenate([records.reshape(-1)] + tables)
+
+
+def fit_batch(raw, device, prefix=''):
+    """The people of a PACKED batch (``training.dataset.collate`` / ``collate_outfits`` of samples that carry ``fit``) fitted to
+    their canvas: (image uint8 [N, H, W, 3], parsing uint8 [N, H, W] on ``device``, key points float64 [N, 18, 3] on the host).
+    Three uploads (the packed photographs, the packed label maps, the plan with its tap tables) and two launches for the batch
+    (pasta_fit_people_u8), ``fit_keypoints`` on the host; before ``mirror_batch``, ``jitter_batch`` and ``strokes_batch``."""
+    fit = raw['fit']
+    H, W = (int(v) for v in fit['canvas'])
+    hw = np.asarray(raw[prefix + 'image_hw'], np.int64)
+    offsets = np.asarray(raw[prefix + 'image_offsets'], np.int64)
+    n = len(hw)
+    packed_image, packed_parsing = torch.as_tensor(raw[prefix + 'image']), torch.as_tensor(raw[prefix + 'parsing'])
+    assert packed_image.dtype == torch.uint8 and packed_parsing.dtype == torch.uint8 and packed_image.ndim == 1 and packed_parsing.ndim == 1
+    assert hw.shape == (n, 2) and offsets.shape == (n,) and n >= 1
+    assert (offsets + hw[:, 0] * hw[:, 1] <= packed_parsing.numel()).all() and packed_image.numel() == 3 * packed_parsing.numel()
+    mode, filter = fit_check(fit['mode'], fit['filter'])
+    rectangles = fit_rectangles(hw, (H, W), mode)
+    plan = fit_plan(hw, offsets, rectangles, filter)
+    image_s, parsing_s = (t.to(device, non_blocking=True).contiguous() for t in (packed_image, packed_parsing))
+    plan_d = torch.from_numpy(plan).to(device, non_blocking=True)
+    _native.require_gpu(image_s, 'fit_batch')
+    image = torch.empty([n, H, W, 3], dtype=torch.uint8, device=image_s.device)
+    parsing = torch.empty([n, H, W], dtype=torch.uint8, device=image_s.device)
+    P = _native.ptr
+    with torch.cuda.device(image_s.device):
+        _native.check(_native.lib().pasta_fit_people_u8(P(image_s), P(parsing_s), int(packed_parsing.numel()), P(plan_d), int(plan.size),
+                                                        P(image), P(parsing), n, H, W, _native.stream()))
+    return image, parsing, fit_keypoints(raw[prefix + 'keypoints'], hw, rectangles)
+
+
+def fitted(raw, device, prefix=''):
+    """``raw`` itself when its people are stacked; for a packed batch a copy with the fitted people in their place (``fit_batch``:
+    ``image`` and ``parsing`` on ``device``, the key points moved) and without the packing's keys: what a caller takes that reads a
+    batch's people itself (training/snapshot_grid.py)."""
+    if 'fit' not in raw or prefix + 'image_hw' not in raw:
+        return raw
+    image, parsing, keypoints = fit_batch(raw, device, prefix)
+    out = {k: v for k, v in raw.items() if k not in ('fit', prefix + 'image_hw', prefix + 'image_offsets')}
+    out.update({prefix + 'image': image, prefix + 'parsing': parsing, prefix + 'keypoints': torch.from_numpy(keypoints)})
+    return out
+
+
 def upload_person(raw, device, who, prefix=''):
     """One person set of a collated batch (``prefix`` 'clothes_': the donors) -> (image uint8 [N, H, W, 3], parsing uint8 [N, H, W]
-    on ``device``, key points float64 [N, 18, 3] on the host), checked."""
+    on ``device``, key points float64 [N, 18, 3] on the host), checked.  A packed batch (people of their own sizes, ``fit``) is
+    fitted to its canvas here (``fit_batch``), so every builder gets the shapes it always got."""
+    if 'fit' in raw and prefix + 'image_hw' in raw:
+        image, parsing, keypoints = fit_batch(raw, device, prefix)
+        n, H, W, _ = image.shape
+        assert H >= W and keypoints.shape == (n, 18, 3)
+        return image, parsing, keypoints
     up = lambda t: torch.as_tensor(t).to(device, non_blocking=True).contiguous()
     image, parsing = up(raw[prefix + 'image']), up(raw[prefix + 'parsing'])
     keypoints = np.asarray(raw[prefix + 'keypoints'], np.float64)

@@ -26,6 +26,7 @@ reference has no 512 training set, so the rule is this project's own: the genera
 test_512.py will later feed it.  A sample is the full-body preparation above of the pair (person, person), plus the 256
 training set's photograph as target, ``gt_parsing`` and erase mask (include/pasta_hip.h lists the rules):
 
+    pasta_fit_people_u8                   the people of a packed ``fit`` batch on their canvas (training/tryon_batch.py, fit_batch)
     pasta_tryon_mirror_u8                 the mirrored people of a ``mirror_people`` batch (training/tryon_batch.py, mirror_batch)
     pasta_tryon_jitter_u8                 the jittered people of a numbered batch (training/tryon_batch.py, jitter_batch)
     pasta_erase_strokes_u8                the drawn erase masks of a batch with ``erase_strokes`` (training/tryon_batch.py, strokes_batch)

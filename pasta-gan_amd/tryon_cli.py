@@ -34,7 +34,7 @@ def _local_snapshot(path):
 
 def shared_options(dataroot_help, batchsize):
     """The decorator of the options both command lines take up to --storage, --png-encoder, the two --kept options, --background,
-    --kept-garments and --part-geometry, in the order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
+    --kept-garments, --part-geometry, --fit-people and --fit-filter, in the order --help prints them; each command line puts its own options and --workers (``workers_option``) below it."""
     options = [
         click.option('--network', 'network_pkl', help='Network pickle filename (a local file)', required=True),
         click.option('--seeds', type=num_range, help='List of random seeds (unused, as in the reference)'),
@@ -47,7 +47,7 @@ def shared_options(dataroot_help, batchsize):
         click.option('--dataroot', help=dataroot_help, type=str, required=True),
         click.option('--batchsize', help='Pairs per batch', type=click.IntRange(min=1), default=batchsize, show_default=True),
         storage_option, png_encoder_option, kept_parts_option, kept_feather_option, background_option, kept_garments_option,
-        part_geometry_option]
+        part_geometry_option, fit_people_option, fit_filter_option]
 
     def decorate(f):
         for option in reversed(options):
@@ -168,6 +168,74 @@ def _chosen_geometry(part_geometry):
     return part_geometry
 
 
+def _record(key):
+    def record(context, param, value):
+        context.meta[key] = value
+        return value
+    return record
+
+
+# --fit-people pad | crop, --fit-filter bilinear | box: photographs of any size, fitted to the model's canvas per batch on the GPU
+# (training.tryon_batch.fit_batch; include/pasta_hip.h has the rule).  Arguments of the data set.  test.py and
+# test_512.py get them with ``shared_options``, recorded in the click context like --png-encoder; train_wo_flow_fullbody.py and
+# calc_metrics.py declare them with ``fit_options`` and take their values.
+_FIT_KEY, _FIT_FILTER_KEY = 'pasta.fit_people', 'pasta.fit_filter'
+FIT_PEOPLE_HELP = ('Take photographs of any size: fit each to the canvas on the GPU, padded to show all of it or centre-cropped to fill the '
+                   'canvas [default: %s]')
+FIT_FILTER_HELP = 'With --fit-people: how the photographs are resampled, as PIL\'s BILINEAR or BOX [default: %s]'
+
+
+def fit_options(fit_default='none: every photograph has the canvas size', filter_default='bilinear'):
+    options = [click.option('--fit-people', help=FIT_PEOPLE_HELP % fit_default, type=click.Choice(['pad', 'crop'])),
+               click.option('--fit-filter', help=FIT_FILTER_HELP % filter_default, type=click.Choice(['bilinear', 'box']))]
+
+    def decorate(f):
+        for option in reversed(options):
+            f = option(f)
+        return f
+    return decorate
+
+
+def fit_kwargs(fit_people, fit_filter):
+    """``--fit-people`` and ``--fit-filter`` (None where not given) -> the keyword arguments they add to a data set: none without
+    --fit-people, so that such a run records what it always did.  A ValueError carries the option's name."""
+    if fit_people is None:
+        if fit_filter is not None:
+            raise ValueError('--fit-filter needs --fit-people pad or crop')
+        return {}
+    from training.tryon_batch import fit_check
+    try:
+        mode, filter = fit_check(fit_people, 'bilinear' if fit_filter is None else fit_filter)
+    except ValueError as err:
+        raise ValueError(f'--fit-people / --fit-filter: {err}')
+    return dict(fit=mode, fit_filter=filter)
+
+
+fit_people_option = click.option('--fit-people', help=FIT_PEOPLE_HELP % 'none: every photograph has the canvas size',
+                                 type=click.Choice(['pad', 'crop']), expose_value=False, callback=_record(_FIT_KEY))
+fit_filter_option = click.option('--fit-filter', help=FIT_FILTER_HELP % 'bilinear', type=click.Choice(['bilinear', 'box']), expose_value=False,
+                                 callback=_record(_FIT_FILTER_KEY))
+
+
+def _chosen_fit(fit_people, fit_filter):
+    """The data set's ``fit`` keywords of ``generate_256`` / ``generate_512`` (``fit_kwargs``); keywords both left at None under a
+    running command line are what that command line's options said (``_chosen_encoder``)."""
+    context = click.get_current_context(silent=True)
+    if fit_people is None and fit_filter is None and context is not None:
+        fit_people, fit_filter = context.meta.get(_FIT_KEY), context.meta.get(_FIT_FILTER_KEY)
+    try:
+        return fit_kwargs(fit_people, fit_filter)
+    except ValueError as err:
+        raise click.UsageError(str(err))
+
+
+def canvas_of(raw):
+    """(height, width) of the people of a batch of ``collate_outfits``: the stack's, or a packed batch's canvas."""
+    if 'fit' in raw:
+        return tuple(int(v) for v in raw['fit']['canvas'])
+    return int(raw['people_image'].shape[1]), int(raw['people_image'].shape[2])
+
+
 # --kept-parts photo: the photograph's head, palms and shoes (metrics.tryon_fidelity.keep_mask, the region `retain` carries) are
 # pasted into the generated picture where its bytes are made (DESIGN 8h; training.tryon_pairs.images_keep_to_u8), feathered over
 # --kept-feather pixels.  Both options come with ``shared_options`` and, like --png-encoder, hand the commands' callbacks no
@@ -177,13 +245,6 @@ _KEPT_PARTS_KEY, _KEPT_FEATHER_KEY = 'pasta.kept_parts', 'pasta.kept_feather'
 KEPT_PARTS = ('generated', 'photo')
 KEPT_FEATHER_DEFAULT = 2            # the 5 x 5 window of the project's erosions
 KEPT_FEATHER_MAX = 8
-
-
-def _record(key):
-    def record(context, param, value):
-        context.meta[key] = value
-        return value
-    return record
 
 
 kept_parts_option = click.option('--kept-parts', help='Where the written head, palms and shoes come from: the generator, or the person\'s '
@@ -322,11 +383,12 @@ def generate(G, t, gen_z, truncation_psi, noise_mode):
 
 
 def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, noise_mode, storage=None, mode=None, kept_radius=None,
-                 pasted=('kept_parts',), part_geometry='host'):
+                 pasted=('kept_parts',), part_geometry='host', fit=None):
     """--scores: the figures of ``metrics.tryon_fidelity.finish`` (prefix ``tryon``) and what the run was, as one JSON line,
     printed and written to ``scores_file``.  ``mode``: what was dressed, when it was not the plain pair lists; ``kept_radius``:
     the feather of a run that pastes from the photograph, whose report says so and names each of ``pasted`` (PASTE_OPTIONS);
-    ``part_geometry``: named in the report only when it is not the host's."""
+    ``part_geometry``: named in the report only when it is not the host's; ``fit``: the data set's fit keywords (``fit_kwargs``),
+    named as ``fit_people`` and ``fit_filter`` when the run had the option."""
     import json
     from metrics import tryon_fidelity
     report = dict(results=tryon_fidelity.finish(partials, 'tryon', pixels=pixels), pairs=pairs, network=network_pkl, dataroot=dataroot,
@@ -340,6 +402,8 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
         report.update((name, 'photo') for name in pasted if name != 'kept_parts')
     if part_geometry != 'host':
         report['part_geometry'] = part_geometry
+    if fit:
+        report.update(fit_people=fit['fit'], fit_filter=fit['fit_filter'])
     line = json.dumps(report)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(scores_file)), exist_ok=True)
@@ -348,7 +412,7 @@ def write_scores(scores_file, partials, pixels, pairs, network_pkl, dataroot, no
 
 
 def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode=None,
-          kept_radius=None, pasted=('kept_parts',), part_geometry='host', png_encoder='pil'):
+          kept_radius=None, pasted=('kept_parts',), part_geometry='host', fit=None, png_encoder='pil'):
     """The loop of both command lines.  ``choose(device)`` -> (data set, collate function, builder, ``pictures``), called once the
     snapshot is loaded; ``pictures(batch, raw, gen_imgs, count, content)`` -> (uint8 [N, h, w, 3] on the GPU, the N file names
     under ``outdir``): what is written for the items of a batch, ``count`` items having been written before it.  --scores FILE: z of
@@ -408,7 +472,7 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
                 scored[:, :, :, c0:c0 + width] = ((content.to(torch.float32) + 0.5) / 127.5 - 1).permute(0, 3, 1, 2)
         if scoring:
             tryon_fidelity.score_batch(scored, batch, index, partials)
-            pixels = raw['people_image'].shape[1] * raw['people_image'].shape[2]
+            pixels = canvas_of(raw)[0] * canvas_of(raw)[1]
         images, names = pictures(batch, raw, gen_imgs, count, content)
         if png_encoder == 'gpu':
             png_encode.save(images, [os.path.join(outdir, name) for name in names])
@@ -420,12 +484,12 @@ def dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, bat
             count += 1
     print('finish: %d images under %s' % (count, outdir))
     if scoring:
-        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius, pasted, part_geometry)
+        write_scores(scores_file, partials, pixels, count, network_pkl, dataroot, noise_mode, storage, mode, kept_radius, pasted, part_geometry, fit)
 
 
 def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, change_region, workers, outfits_file=None,
                  scores_file=None, storage=None, kept_parts='generated', kept_feather=None, background='generated',
-                 kept_garments='generated', part_geometry='host', png_encoder='pil'):
+                 kept_garments='generated', part_geometry='host', fit_people=None, fit_filter=None, png_encoder='pil'):
     """test_512.py: the 512 x 320 model on outfits, prepared by training.tryon_regions.TryOnOutfitBatchBuilder and written to
     ``<outdir>/<count>.png`` in list order.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_512_test), written as ``upper donor | lower donor | person | generated`` (512 x 2048).
@@ -440,6 +504,7 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
     kept_radius, pasted = _paste_plan(kept_parts, kept_feather, background, kept_garments)
+    fit = _chosen_fit(fit_people, fit_filter)          # photographs of any size, fitted to the canvas on the GPU
 
     def choose(device, geometry='host'):
         import torch
@@ -447,11 +512,12 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
         from training.tryon_pairs import images_to_u8
         from training.tryon_regions import TryOnOutfitBatchBuilder
         if outfits_file is not None:
-            dataset = custom_dataset.UvitonOutfits_512_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
+            dataset = custom_dataset.UvitonOutfits_512_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False, **fit)
             collate_fn, panels = custom_dataset.collate_outfits, ('clothes', 'clothes_lower', 'image')
         else:
             region = change_region or 'fullbody'
-            dataset = custom_dataset.UvitonDatasetFull_512_test(path=dataroot, change_region=region, use_labels=True, max_size=None, xflip=False)
+            dataset = custom_dataset.UvitonDatasetFull_512_test(path=dataroot, change_region=region, use_labels=True, max_size=None, xflip=False,
+                                                                **fit)
             collate_fn = functools.partial(custom_dataset.collate_region_outfits, region)
             panels = ('clothes_lower' if region == 'lowerbody' else 'clothes', 'image')
 
@@ -465,12 +531,12 @@ def generate_512(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
             return images, [str(count + i).zfill(3) + '.png' for i in range(batch.batch)]
         return dataset, collate_fn, TryOnOutfitBatchBuilder(device, geometry=geometry), pictures
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage,
-          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder), part_geometry=_chosen_geometry(part_geometry))
+          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder), part_geometry=_chosen_geometry(part_geometry), fit=fit)
 
 
 def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, outfits_file=None, change_region=None,
                  scores_file=None, storage=None, kept_parts='generated', kept_feather=None, background='generated',
-                 kept_garments='generated', part_geometry='host', png_encoder='pil'):
+                 kept_garments='generated', part_geometry='host', fit_people=None, fit_filter=None, png_encoder='pil'):
     """test.py: the 256 x 192 model on outfits, prepared by training.tryon_pairs.TryOnPairOutfitBatchBuilder; only the generated
     image is written, columns 32..223 of the generator's square.  --outfits FILE: every line ``person upper lower`` of FILE
     (training.dataset.UvitonOutfits_256_test), written to ``<outdir>/<person's sub-dataset>/<person stem>__<upper stem>__<lower
@@ -485,24 +551,25 @@ def generate_256(network_pkl, truncation_psi, noise_mode, outdir, dataroot, batc
     if outfits_file is not None and change_region is not None:
         raise click.UsageError(BOTH_MODES)
     kept_radius, pasted = _paste_plan(kept_parts, kept_feather, background, kept_garments)
+    fit = _chosen_fit(fit_people, fit_filter)          # photographs of any size, fitted to the canvas on the GPU
 
     def choose(device, geometry='host'):
         from training import dataset as custom_dataset
         from training.tryon_pairs import TryOnPairOutfitBatchBuilder, images_to_u8
         if outfits_file is not None:
-            dataset = custom_dataset.UvitonOutfits_256_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False)
+            dataset = custom_dataset.UvitonOutfits_256_test(path=dataroot, outfits_file=outfits_file, use_labels=True, max_size=None, xflip=False, **fit)
             collate_fn, worn = custom_dataset.collate_outfits, ('upper_name', 'lower_name')
         else:
-            dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False)
+            dataset = custom_dataset.UvitonDatasetV19_test(path=dataroot, use_labels=True, max_size=None, xflip=False, **fit)
             collate_fn, worn = functools.partial(custom_dataset.collate_region_outfits, change_region or 'upperbody'), ('clothes_name',)
         stem = lambda name: os.path.basename(name)[:-4]
 
         def pictures(batch, raw, gen_imgs, count, content):
-            height, width = raw['people_image'].shape[1], raw['people_image'].shape[2]
+            height, width = canvas_of(raw)
             names = [os.path.join(who[0].split('/')[0], '__'.join(stem(name) for name in who) + '.png')
                      for who in zip(raw['person_name'], *[raw[k] for k in worn])]
             return (images_to_u8(gen_imgs, (height - width) // 2, width) if content is None else content), names
         return dataset, collate_fn, TryOnPairOutfitBatchBuilder(device, geometry=geometry), pictures
     mode = 'outfits' if outfits_file is not None else change_region and 'change-region ' + change_region
     dress(choose, network_pkl, truncation_psi, noise_mode, outdir, dataroot, batchsize, workers, scores_file, storage, mode,
-          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder), part_geometry=_chosen_geometry(part_geometry))
+          kept_radius=kept_radius, pasted=pasted, png_encoder=_chosen_encoder(png_encoder), part_geometry=_chosen_geometry(part_geometry), fit=fit)
